@@ -4,9 +4,11 @@
 Step  = one pass of the hot path (K1 tile_stats + the sequential greedy scan, both on the GPU by default [--scan host: stats
         D2H + host scan threads] → per-tile assignment maps + pcc/mae/atol on the host) over a batch of `--tensors` (128) synthetic 4096x4096 bf16 tensors
         (BASELINE.json configs[1], streamed; the batch is > 256 MiB so the Infinity Cache cannot hold it).
-value = tiles/s, whole job, inputs resident in HBM when the timed region starts; the median of `--regions` (3) timed regions of
-        `--steps` steps each, every region bracketed by barrier + synchronize (a 20-step region lasts 50 ms: one scheduling hiccup of
-        the host moved a single region by 5 %).
+value = tiles/s, whole job, inputs resident in HBM when the timed region starts; exactly `--steps` timed steps, split into
+        `--regions` (1) regions, every region bracketed by barrier + synchronize; value and ms_per_step are the median region's
+        per-step figures (a region's last step carries the pipeline's drain, so shorter regions read slower per step).
+--dump-outputs DIR: what the last timed step returned (per tensor: assignment map, format counts, pcc / mae / atol columns) as
+        DIR/<name>.npy in float32 / float64, at most 64 MB; the inputs are seeded, so two builds can be compared output for output.
 roofline = the K1 kernel alone: algorithmic 2048 B read per tile / HIP-event launch duration vs 8 TB/s.
 cpu_baseline = the C oracle (oracle/, a port of the reference's CPU path) on rank 0's host, 1 thread, on a bounded sample of
         the same tensors; cpu_baseline_threads = the same port on every core of the rank's CPU quota; cpu_baseline_emulation =
@@ -38,7 +40,7 @@ import torch
 ROWS = COLS = 4096
 FORMATS = ["bf16", "bfp8", "bfp4", "bfp2"]
 METRIC, THRESHOLD, SEED = "pcc", 0.999, 123
-HBM_PEAK_GBS = 8000.0          # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0          # MI355X spec
 BYTES_PER_TILE_READ = 2048     # 32*32 bf16, SURVEY §8(d)
 METRIC_NAME = "32x32 tiles/s for mixed-tile-greedy (bf16->BFP{8,4,2}); achieved HBM GB/s vs peak"
 
@@ -247,6 +249,41 @@ def dry_run(args) -> None:
 def median(v):
     s = sorted(v)
     return s[len(s) // 2] if len(s) % 2 else 0.5 * (s[len(s) // 2 - 1] + s[len(s) // 2])
+
+
+def region_sizes(steps: int, regions: int) -> list[int]:
+    """--steps timed steps over --regions regions, as even as they go (never an empty region): the steps are the job's, not per region."""
+    n = max(1, min(regions, steps))
+    return [steps // n + (1 if i < steps % n else 0) for i in range(n)]
+
+
+DUMP_BYTES = 63_000_000        # --dump-outputs: data of all files of a rank, under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, indexed_results, prefix: str = "", budget: int = DUMP_BYTES) -> None:
+    """--dump-outputs: the TensorResults of the last timed step, as `(tensor index, result)` pairs, to out_dir/<prefix><name>.npy in
+    tensor order: tensor_index, counts (tensors x FORMATS), pcc / mae / atol / tile_bytes / metric_value (float64), and the int8
+    assignment maps as float32, concatenated flat (assignment_shapes: each map's (tiles_h, tiles_w)).  Maps larger than the budget
+    leave a fixed seeded sample of their entries, their flat positions in assignment_positions."""
+    import numpy as np
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    pairs = sorted(indexed_results, key=lambda p: p[0])
+    rs = [r for _i, r in pairs]
+    arrays = {"tensor_index": np.array([i for i, _r in pairs], dtype=np.float64),
+              "counts": np.array([[r.counts[f] for f in FORMATS] for r in rs], dtype=np.float64),
+              **{k: np.array([getattr(r, k) for r in rs], dtype=np.float64) for k in ("pcc", "mae", "atol", "tile_bytes", "metric_value")},
+              "assignment_shapes": np.array([r.assignment.shape for r in rs], dtype=np.float64).reshape(len(rs), 2)}
+    maps = np.concatenate([r.assignment.ravel() for r in rs]).astype(np.float32)
+    room = budget - sum(a.nbytes for a in arrays.values())
+    if maps.nbytes > room:   # 4 B per sampled entry + 8 B for its position
+        pos = np.sort(np.random.default_rng(0).choice(maps.size, room // 12, replace=False))
+        arrays["assignment_positions"] = pos.astype(np.float64)
+        maps = maps[pos]
+    arrays["assignment"] = maps
+    for name, a in arrays.items():
+        np.save(out / f"{prefix}{name}.npy", a)
 
 
 def timed(fn, reps: int = 5):
@@ -466,9 +503,12 @@ def k1_profile_blocks(tiles_per_launch: float, k_ms: float, lazy: bool = True):
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps in all")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--regions", type=int, default=3, help="timed regions of --steps steps each; value is their median")
+    ap.add_argument("--regions", type=int, default=1,
+                    help="timed regions the --steps steps are split into; value and ms_per_step are the median region's")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64, at most 64 MB; N > 1: rank<r>_<name>.npy)")
     ap.add_argument("--workload", choices=["m1", "llama3-8b"], default="m1",
                     help="m1: 128 x 4096x4096 bf16 per GPU per step (BASELINE.json configs[1], weak scaling); llama3-8b: the 224 linear weights of "
                          "Llama-3-8B sharded over the ranks (configs[3], strong scaling)")
@@ -484,6 +524,8 @@ def main() -> None:
                          "host scan threads), auto = device where it serves the search")
     ap.add_argument("--dry-run", action="store_true", help="rank plumbing only, on the CPU over gloo (tests); prints no measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))   # nothing above this line touches the GPU
@@ -552,11 +594,12 @@ def run_llama_workload(args, dist, rank, world, device, barrier, numa) -> None:
         res = pipe.run_batches(xs)
     pipe.timing.drain()
     pipe.timing.__init__()
+    sizes = region_sizes(args.steps, args.regions)
     region_s, my_region_s = [], []
-    for _ in range(max(1, args.regions)):
+    for n in sizes:
         barrier()
         t0 = time.perf_counter()
-        for _s in range(args.steps):
+        for _s in range(n):
             res = pipe.run_batches(xs)
         torch.cuda.synchronize()
         mine_dt = time.perf_counter() - t0
@@ -564,7 +607,10 @@ def run_llama_workload(args, dist, rank, world, device, barrier, numa) -> None:
         my_region_s.append(mine_dt)
         region_s.append(time.perf_counter() - t0)
     pipe.timing.drain()
-    mid = sorted(range(len(region_s)), key=lambda i: region_s[i])[len(region_s) // 2]
+    mid = sorted(range(len(region_s)), key=lambda i: region_s[i] / sizes[i])[len(region_s) // 2]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [(i, r) for (part, _x), rs in zip(batches, res) for i, r in zip(part, rs)],
+                     "" if world == 1 else f"rank{rank}_", DUMP_BYTES // world)
     rows = torch.tensor([[i, index.numel(names[i]), r.pcc, r.mae, r.atol, r.tile_bytes, r.counts["bf16"], r.counts["bfp8"], r.counts["bfp4"], r.counts["bfp2"], float(rank)]
                          for (part, _x), rs in zip(batches, res) for i, r in zip(part, rs)], dtype=torch.float64, device=device)
     all_rows, dt = gather_summary(rows, region_s[mid], dist, rank, world)
@@ -578,14 +624,14 @@ def run_llama_workload(args, dist, rank, world, device, barrier, numa) -> None:
     if rank == 0:
         total_tiles = int(per_rank_all[:, 1].sum())
         kt = pipe.timing
-        secs = per_rank_all[:, 0] / args.steps
+        secs = per_rank_all[:, 0] / sizes[mid]
         frac = BYTES_PER_TILE_READ * kt.tiles / max(kt.kernel_ms, 1e-9) / 1e6 / HBM_PEAK_GBS
-        out = {"metric": METRIC_NAME, "value": total_tiles * args.steps / dt, "unit": "tiles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32/f64", "data": "synthetic",
+        out = {"metric": METRIC_NAME, "value": total_tiles * sizes[mid] / dt, "unit": "tiles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": dt / sizes[mid] * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32/f64", "data": "synthetic",
                "config": {"workload": "Llama-3-8B model.layers.* linear weights: 224 synthetic bf16 tensors (6.8 M tiles, 14 GB) drawn on the device, mixed-tile-greedy "
                                       "{bf16,bfp8,bfp4,bfp2} pcc>=0.999 seed 123 (BASELINE.json configs[3]); a step = the whole model once",
                           "sharding": f"224 tensors LPT by element count over {world} ranks (model_source.lpt_shards), RCCL gather of summary rows",
-                          "tensors": int(all_rows.shape[0]), "tiles": total_tiles, "regions_ms_per_step": [s / args.steps * 1e3 for s in region_s],
+                          "tensors": int(all_rows.shape[0]), "tiles": total_tiles, "regions_steps": sizes, "regions_ms_per_step": [s / n * 1e3 for s, n in zip(region_s, sizes)],
                           "per_rank_pipeline_ms_per_step": (secs * 1e3).tolist(), "per_rank_tiles": per_rank_all[:, 1].astype(int).tolist(),
                           "imbalance_tiles": float(per_rank_all[:, 1].max() / per_rank_all[:, 1].mean()), "imbalance_time": float(secs.max() / secs.mean()),
                           "loader_seconds_per_rank": per_rank_all[:, 2].tolist(), "scan": "device (csrc/mtq_scan.hip)" if pipe.device_scan else "host",
@@ -637,18 +683,21 @@ def run_m1_workload(args, dist, rank, world, device, barrier, numa) -> None:
     res = pipe.run_steps(batch for _ in range(args.warmup))
     pipe.timing.drain()
     pipe.timing.__init__()
+    sizes = region_sizes(args.steps, args.regions)
     regions, cpu_ms = [], []
-    for _ in range(max(1, args.regions)):   # every region: exactly --steps steps between two barriers; every step fully processed
+    for n in sizes:   # every region: its share of the --steps steps between two barriers; every step fully processed
         barrier()
         cpu0 = time.process_time()
         t0 = time.perf_counter()
-        res = pipe.run_steps(batch for _ in range(args.steps))  # step s+1's GPU work overlaps step s's scan tail
+        res = pipe.run_steps(batch for _ in range(n))  # step s+1's GPU work overlaps step s's scan tail
         barrier()
         regions.append(time.perf_counter() - t0)
-        cpu_ms.append((time.process_time() - cpu0) / args.steps * 1e3)   # CPU time of every thread of this rank, per step
+        cpu_ms.append((time.process_time() - cpu0) / n * 1e3)   # CPU time of every thread of this rank, per step
     pipe.timing.drain()
-    mid = sorted(range(len(regions)), key=lambda i: regions[i])[len(regions) // 2]
+    mid = sorted(range(len(regions)), key=lambda i: regions[i] / sizes[i])[len(regions) // 2]
     host_cpu_ms = cpu_ms[mid]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [(r.index, r) for r in res], "" if world == 1 else f"rank{rank}_", DUMP_BYTES // world)
 
     # the only data-path collective: per-tensor summary rows to rank 0; outside the timed steps
     # the rows of the LAST step are gathered so the multi-GPU path is exercised end to end.
@@ -670,20 +719,20 @@ def run_m1_workload(args, dist, rank, world, device, barrier, numa) -> None:
         achieved = BYTES_PER_TILE_READ * tiles_per_launch / (k_ms * 1e-3) / 1e9
         lazy = pipe.lazy_plan(batch[: args.chunk]) is not None
         traffic, traffic_source, valu = k1_profile_blocks(tiles_per_launch, k_ms, lazy)
-        total_steps = args.steps * len(regions)
+        total_steps = args.steps
         out = {
             "metric": METRIC_NAME,
-            "value": world * args.steps * tiles_per_step / dt,
+            "value": world * sizes[mid] * tiles_per_step / dt,
             "unit": "tiles/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
+            "ms_per_step": dt / sizes[mid] * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32/f64", "data": "synthetic",
             "config": {"workload": f"{args.tensors} x 4096x4096 bf16 N(0,0.02^2) per GPU per step, mixed-tile-greedy "
                                    f"{{bf16,bfp8,bfp4,bfp2}} pcc>=0.999 seed 123 (BASELINE.json configs[1], streamed)",
                        "tensors_per_step_per_gpu": args.tensors, "tiles_per_step_per_gpu": tiles_per_step,
-                       "regions": len(regions), "regions_tiles_per_s": [world * args.steps * tiles_per_step / s for s in regions_max],
-                       "value_is": "the median region (each region = exactly --steps steps between barrier + synchronize)",
+                       "regions": len(regions), "regions_steps": sizes, "regions_tiles_per_s": [world * n * tiles_per_step / s for s, n in zip(regions_max, sizes)],
+                       "value_is": "the median region's rate (the --steps timed steps split into --regions regions, each between barrier + synchronize)",
                        "k1_chunk": args.chunk, "scan": "device (csrc/mtq_scan.hip)" if pipe.device_scan else f"host ({args.workers} threads)",
                        "route": ("lazy: K1 evaluates bfp8 (five statistics) and bfp4 (three sums); the search stops before its last pass, the listed kernel evaluates bfp2 and "
                                  "bfp4's error statistics for that pass's candidates, the last pass follows (DESIGN.md §4)") if lazy else "whole records",

@@ -273,6 +273,35 @@ def test_bench_model_workload_shards_over_two_ranks(tmp_path):
     assert len(names) == 224 and sum(len(v) for v in groups.values()) == len(mine) and set(groups) <= {(4096, 4096), (1024, 4096), (14336, 4096), (4096, 14336)}
 
 
+def test_bench_steps_and_dumped_outputs(tmp_path):
+    """--steps is the number of timed steps however many --regions share them; --dump-outputs writes the last step's results in
+    tensor order as float32 / float64 .npy files, and a fixed seeded sample of the maps when they exceed the byte budget."""
+    from bench import FORMATS, dump_outputs, region_sizes
+    from quantization_analysis_amd.pipeline_common import TensorResult
+
+    for steps, regions in ((1, 1), (20, 1), (20, 3), (2, 3), (100, 7)):
+        sizes = region_sizes(steps, regions)
+        assert sum(sizes) == steps and min(sizes) >= 1 and max(sizes) - min(sizes) <= 1 and len(sizes) == min(steps, regions)
+    rng = np.random.default_rng(1)
+    res = [TensorResult(i, rng.integers(0, 4, size=(3 + i, 5), dtype=np.int8), {f: i + k for k, f in enumerate(FORMATS)}, 100.0 + i,
+                        1 - 1e-4 * i, 1e-3 * i, 2e-3 * i, 0.5 + i) for i in range(3)]
+    pairs = [(7, res[2]), (2, res[0]), (5, res[1])]
+    dump_outputs(tmp_path / "all", pairs)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").glob("*.npy")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["tensor_index"].tolist() == [2, 5, 7] and got["counts"][2].tolist() == [2, 3, 4, 5] and got["pcc"][1] == 1 - 1e-4
+    assert got["assignment_shapes"].tolist() == [[3, 5], [4, 5], [5, 5]] and "assignment_positions" not in got
+    assert np.array_equal(got["assignment"], np.concatenate([r.assignment.ravel() for r in res]).astype(np.float32))
+    budget = sum(a.nbytes for k, a in got.items() if k != "assignment") + 12 * 10
+    for d in ("s1", "s2"):
+        dump_outputs(tmp_path / d, pairs, "rank0_", budget)
+    s1 = {p.stem: np.load(p) for p in (tmp_path / "s1").glob("*.npy")}
+    s2 = {p.stem: np.load(p) for p in (tmp_path / "s2").glob("*.npy")}
+    pos = s1["rank0_assignment_positions"].astype(np.int64)
+    assert pos.size == 10 and np.all(np.diff(pos) > 0) and np.array_equal(s1["rank0_assignment"], got["assignment"][pos])
+    assert all(np.array_equal(s1[k], s2[k]) for k in s1) and sum(a.nbytes for a in s1.values()) <= budget
+
+
 @pytest.mark.gpu
 def test_wq_hip_backend(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)
