@@ -151,6 +151,28 @@ int mtq_quantize(const void *x, int in_dtype, int64_t rows, int64_t cols, int64_
                  int fmt, float *y, int64_t ldy, void *stream);
 
 /*
+ * K1T tile_stats_transposed — K1 of Xᵀ read from the row-major X, for `count` equally shaped matrices at x + i*stride_elems (one
+ * launch).  Replaces, for the `transpose` algorithm, the quantisation of np.transpose(x) per format (compression_algorithms/
+ * transpose.py:13-33 → quantization_formats.py:84-164, a shared exponent per 16 consecutive ROWS of one column of X) plus the float32
+ * metrics wq forms from it (wq:683-687); no transposed copy of X is made.
+ *
+ * The records are exactly those mtq_tile_stats writes for a contiguous copy of Xᵀ (cols × rows), bit for bit: the same layout
+ * (2 + 5·popcount(fmt_mask) doubles), terms and summation order, applied to Xᵀ.  Tiles are numbered row-major over Xᵀ's grid:
+ * element (r, c) of X lies in tile (c/32)·ceil(rows/32) + r/32 of its matrix; matrix i's tiles follow matrix i−1's.
+ * fmt_mask: 1..4 of bf16|bfp8|bfp4|bfp2 (MTQ_ERR_INVALID otherwise).
+ */
+int mtq_tile_stats_transposed(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,
+                              int64_t ld, uint32_t fmt_mask, double *stats, void *stream);
+
+/*
+ * K2T quantize_transposed — y = (K2 of Xᵀ)ᵀ as float32 into a row-major rows × cols y (leading dimension ldy): bit for bit
+ * np.transpose(quantize_weight_values(np.transpose(X), fmt)) (transpose.py:27-28), quirks included, for fmt in
+ * {bf16, bfp8, bfp4, bfp2, fp0} (MTQ_ERR_UNSUPPORTED otherwise).  Rows past `rows` count as zero pads of the last group of a column.
+ */
+int mtq_quantize_transposed(const void *x, int in_dtype, int64_t rows, int64_t cols, int64_t ld,
+                            int fmt, float *y, int64_t ldy, void *stream);
+
+/*
  * K3 apply_assignment — y where each 32×32 tile uses the format its int8 map entry names.
  * Replaces the tile gather/scatter of mixed_tile_threshold.py:125-132, mixed_tile_greedy.py:273,348-352
  * and scripts/reconstruct_mixed_tile_assignment.py:82-94.  map is tiles_h × tiles_w, row-major, on device.

@@ -175,7 +175,7 @@ def _columns_emulation(xf: np.ndarray, y: np.ndarray):
 def _none_rows_hip(x, formats, quantizer):
     """`none` baseline on the hip backend: pcc/mae/atol of every pure mixed-tile format come from ONE
     K1 pass (sum the per-tile records); fp0 from three device reductions.  y is not materialised or cached."""
-    from .compression_algorithms.tile_search import columns_from_stats, compute_tile_stats
+    from .compression_algorithms.tile_search import columns_from_stats, compute_tile_stats, fp0_columns
 
     out = {}
     mixed = [f for f in formats if f in MIXED_TILE_FORMATS]
@@ -186,9 +186,7 @@ def _none_rows_hip(x, formats, quantizer):
             c = columns_from_stats(ts, amap)
             out[f] = (c["pcc"], c["mae"], c["atol"])
     if "fp0" in formats:
-        ax = x.float().abs()
-        mx = float(ax.max()) if ax.numel() else 0.0
-        out["fp0"] = (1.0 if mx == 0.0 else 0.0, float(ax.mean()) if ax.numel() else 0.0, mx)  # metrics.py:14-15 with y = 0
+        out["fp0"] = fp0_columns(x)  # metrics.py:14-15 with y = 0
     return out
 
 
@@ -228,6 +226,9 @@ def _evaluate_tensor(idx, name, index, algorithms, formats, quantizer, args, run
                 rows.append([idx, ci, SUPPORTED_FORMATS.index(f), pcc, mae, atol, elapsed, numel * FORMAT_BYTES_PER_ELEM[f] / 1e9,
                              np.nan, -1, -1, -1, -1, *meta])
             continue
+        if hip and algo.name == "transpose" and not args.literal_metrics:
+            # the analogue of the `none` rows: the columns from one K1T pass, no y materialised (compression_algorithms/transpose.py)
+            algo = type(algo)({**algo.params, "materialize_y": False})
         results = algo.run(xf=x, formats=formats, quantizer=quantizer, cache=cache_ctx)
         if hip:
             import torch
@@ -500,7 +501,7 @@ def run(argv=None) -> int:
             processed_root = Path("data/processed") / safe_repo_revision_key(index.repo_id, index.revision)
 
             shards = lpt_shards(tensor_names, index.numel, world)
-            per_tensor_rows = len(formats) + (0 if selected_algo.name == "none" else 1)
+            per_tensor_rows = len(formats) + {"none": 0, "transpose": len(formats)}.get(selected_algo.name, 1)
             ctx = {"shards": shards, "per_tensor_rows": per_tensor_rows, "tensor_names": tensor_names, "index": index, "comp_names": comp_names,
                    "formats": formats, "results_dir": results_dir}
             mine, notes = _evaluate_shard(shards[rank], tensor_names, index, algorithms, selected_algo, formats, quantizer, args, run_tag,

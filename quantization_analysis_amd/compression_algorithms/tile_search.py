@@ -232,6 +232,13 @@ def literal_inputs(ts: TileStats, tile_ids: np.ndarray, fmt: str, quantizer, pin
     return xt, yt, ids
 
 
+def fp0_columns(x) -> tuple[float, float, float]:
+    """pcc / mae / atol of the fp0 reconstruction (y = 0, metrics.py:14-15) of a device tensor, from three device reductions."""
+    ax = x.float().abs()
+    mx = float(ax.max()) if ax.numel() else 0.0
+    return 1.0 if mx == 0.0 else 0.0, float(ax.mean()) if ax.numel() else 0.0, mx
+
+
 def columns_from_stats(ts: TileStats, assignment: np.ndarray) -> dict:
     """Tensor-level pcc / mae / atol of the reconstruction, from the float64 raw sums — summed on the device when the records
     live there and have not been brought to the host anyway (1 B/tile up, seven doubles back)."""

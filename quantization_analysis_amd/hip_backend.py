@@ -34,7 +34,10 @@ EXPORTS = [
     "mtq_selftest_slot_ring", "mtq_device_copy_2d", "mtq_knife_tiles_device", "mtq_greedy_scan_scratch_bytes", "mtq_greedy_scan_device", "mtq_greedy_scan_device_ex", "mtq_scan_carry_bytes",
     "mtq_scan_orders_bytes", "mtq_scan_orders_device", "mtq_debug_scan_ticks", "mtq_threshold_enqueue", "mtq_threshold_columns",
     "mtq_tile_stats_ragged", "mtq_knife_tiles_ragged", "mtq_column_sums_device_ragged", "mtq_threshold_enqueue_ragged", "mtq_threshold_columns_ragged",
+    "mtq_tile_stats_transposed", "mtq_quantize_transposed",
 ]
+# found by name, not by MTQ_VERSION: an older build of the same version (an A/B library at MTQ_LIB) lacks them and still loads
+OPTIONAL_EXPORTS = ("mtq_tile_stats_transposed", "mtq_quantize_transposed")
 
 
 class MtqError(RuntimeError):
@@ -130,6 +133,10 @@ def lib() -> ctypes.CDLL:
     L.mtq_column_sums_device_ragged.argtypes = [vp, vp, ci, u32, vp, vp, vp]
     L.mtq_threshold_enqueue_ragged.argtypes = [vp, ci, ci, u32, u32, vp, ci, ci, dbl, dbl, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.mtq_threshold_columns_ragged.argtypes = [vp, vp, ci, u32, vp, vp, vp, vp]
+    if hasattr(L, "mtq_tile_stats_transposed"):
+        L.mtq_tile_stats_transposed.argtypes = [vp, ci, i64, i64, i64, i64, i64, u32, vp, vp]
+    if hasattr(L, "mtq_quantize_transposed"):
+        L.mtq_quantize_transposed.argtypes = [vp, ci, i64, i64, i64, ci, vp, i64, vp]
     if L.mtq_version() < 141:
         raise MtqError("libmtq_hip.so is older than this package")
     _lib = L
@@ -406,6 +413,62 @@ def quantize(x2d, fmt: str, out=None):
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.float32, device=x2d.device)
     check(lib().mtq_quantize(x2d.data_ptr(), _dtype_code(x2d), rows, cols, ld, FMT_CODE[fmt], out.data_ptr(), out.stride(0), _stream_ptr()))
+    return out
+
+
+def _transposed_entry(name: str):
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise MtqError(f"{LIB_PATH} has no {name}: rebuild it from this tree (`make -C {_PKG / 'csrc'}`)")
+    return fn
+
+
+def _check_transposed_input(x, dims: tuple) -> None:
+    """The checks the transposed entry points need before a pointer is taken: device tensor, rank, contiguous rows, storage type."""
+    torch = _torch()
+    if not getattr(x, "is_cuda", False):
+        raise MtqError("expected a device tensor (the hip backend has no CPU fallback)")
+    if x.dim() not in dims:
+        raise MtqError(f"expected a {' or '.join(f'{d}-D' for d in dims)} device tensor, got {x.dim()}-D")
+    if x.stride(-1) != 1:
+        raise MtqError("expected contiguous rows (stride(-1) == 1)")
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise MtqError(f"hip backend takes bfloat16 or float32 tensors, got {x.dtype}")
+
+
+def tile_stats_transposed(x, mask: int, out=None):
+    """K1T (mtq_tile_stats_transposed) on the current stream: the K1 records of Xᵀ for a (rows, cols) or (count, rows, cols) device tensor X
+    with contiguous rows, read in place → float64 [tiles] / [count, tiles] × rec, tiles numbered row-major over Xᵀ's grid
+    (element (r, c) of X in tile (c // 32) * ceil(rows / 32) + r // 32)."""
+    _check_transposed_input(x, (2, 3))
+    torch = _torch()
+    require_gpu()
+    fn = _transposed_entry("mtq_tile_stats_transposed")
+    x3 = x if x.dim() == 3 else x[None]
+    count, rows, cols = x3.shape
+    ld = x3.stride(1) if rows > 1 else max(x3.stride(1), cols)
+    stride = x3.stride(0) if count > 1 else 0
+    th_t, tw_t = tiles_hw(cols, rows)
+    rec = record_doubles(mask)
+    if out is None:
+        out = torch.empty((count, th_t * tw_t, rec), dtype=torch.float64, device=x.device)
+    check(fn(x3.data_ptr(), _dtype_code(x3), count, stride, rows, cols, ld, mask, out.data_ptr(), _stream_ptr()))
+    return out if x.dim() == 3 else out[0]
+
+
+def quantize_transposed(x2d, fmt: str, out=None):
+    """K2T (mtq_quantize_transposed) on the current stream: (K2 of Xᵀ)ᵀ for a 2-D device tensor with contiguous rows → float32, X's shape."""
+    _check_transposed_input(x2d, (2,))
+    torch = _torch()
+    if fmt not in FMT_CODE:
+        raise ValueError(f"Unsupported weight format: {fmt}")
+    require_gpu()
+    fn = _transposed_entry("mtq_quantize_transposed")
+    rows, cols = x2d.shape
+    ld = x2d.stride(0) if rows > 1 else max(x2d.stride(0), cols)
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.float32, device=x2d.device)
+    check(fn(x2d.data_ptr(), _dtype_code(x2d), rows, cols, ld, FMT_CODE[fmt], out.data_ptr(), out.stride(0), _stream_ptr()))
     return out
 
 

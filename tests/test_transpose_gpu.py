@@ -1,0 +1,199 @@
+"""GPU: K2T and K1T (csrc/mtq_transpose.hip) against the reference's `transpose` results (F15) and the oracle on Xᵀ, the plugin on
+the hip backend, and `wq --backend hip --literal-metrics` against `--backend emulation`."""
+import hashlib
+import json
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from oracle import mtq_oracle as orc
+from quantization_analysis_amd import hip_backend as hb
+from tests.inputs import gen
+from tests.test_cli import strip_time
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parent.parent
+FORMATS = ["bf16", "bfp8", "bfp4", "bfp2", "fp0"]
+MIXED = ["bf16", "bfp8", "bfp4", "bfp2"]
+
+
+@pytest.fixture(scope="module")
+def f15():
+    g = ROOT / "tests" / "golden"
+    return np.load(g / "f15_transpose.npz"), json.loads((g / "golden_meta_f15.json").read_text())
+
+
+def _torch():
+    import torch
+
+    hb.require_gpu()
+    return torch
+
+
+def _v(x: np.ndarray) -> np.ndarray:
+    d0 = x.shape[0] if x.ndim else 1
+    return np.ascontiguousarray(x.reshape(d0, -1))
+
+
+def _is_bf16_valued(a: np.ndarray) -> bool:
+    return not np.any(np.ascontiguousarray(a, dtype=np.float32).view(np.uint32) & 0xFFFF)
+
+
+def _k2t(torch, v: np.ndarray, fmt: str, dtype, pad: int = 0) -> np.ndarray:
+    """K2T on v stored as `dtype`, rows `pad` elements longer than needed (ld > cols when pad > 0)."""
+    rows, cols = v.shape
+    base = torch.zeros((rows, cols + pad), dtype=torch.float32)
+    base[:, :cols] = torch.from_numpy(v)
+    xd = base.to(dtype).cuda()[:, :cols]
+    y = hb.quantize_transposed(xd, fmt)
+    torch.cuda.synchronize()
+    return y.cpu().numpy()
+
+
+def test_k2t_equals_reference_and_oracle(f15):
+    torch = _torch()
+    data, meta = f15
+    for case in meta["cases"]:
+        x = data[f"{case}__x"]
+        v = _v(x)
+        dtypes = [torch.float32] + ([torch.bfloat16] if _is_bf16_valued(v) else [])
+        for fmt in FORMATS:
+            want = data[f"{case}__{fmt}"].reshape(v.shape)
+            with np.errstate(all="ignore"):
+                assert np.array_equal(orc.quantize_np(np.ascontiguousarray(v.T), fmt).T.view(np.uint32), want), (case, fmt)
+            for dt in dtypes:
+                for pad in (0, 5):
+                    y = _k2t(torch, v, fmt, dt, pad)
+                    assert np.array_equal(y.view(np.uint32), want), (case, fmt, dt, pad)
+
+
+def test_k2t_bf16_storage_narrow_and_ragged():
+    """bf16 storage on shapes with cols = 1..15 and rows not a multiple of 16, against the oracle on Vᵀ."""
+    torch = _torch()
+    for rows, cols in [(37, 1), (50, 3), (16, 15), (129, 7), (1, 40), (300, 33)]:
+        v = gen("heavy_bf16", rows * 100 + cols, (rows, cols))
+        for fmt in FORMATS:
+            want = orc.quantize_np(np.ascontiguousarray(v.T), fmt).T
+            y = _k2t(torch, v, fmt, torch.bfloat16, pad=3)
+            assert np.array_equal(y.view(np.uint32), np.ascontiguousarray(want).view(np.uint32)), (rows, cols, fmt)
+
+
+def _masks():
+    return range(1, 16)
+
+
+def _oracle_t(x2d: np.ndarray, mask: int) -> np.ndarray:
+    return orc.tile_stats(np.ascontiguousarray(x2d.T), hb.mask_formats(mask)).view(np.uint64)
+
+
+def test_k1t_records_equal_oracle_small_shapes(f15):
+    torch = _torch()
+    data, meta = f15
+    for case in meta["cases"]:
+        v = _v(data[f"{case}__x"])
+        xd = torch.from_numpy(v).cuda()
+        for mask in _masks():
+            with np.errstate(all="ignore"):
+                want = _oracle_t(v, mask)
+            got = hb.tile_stats_transposed(xd, mask).cpu().numpy().view(np.uint64)
+            assert got.shape == want.shape and np.array_equal(got, want), (case, mask)
+
+
+@pytest.mark.parametrize("kind,shape,dt", [("normal_bf16", (4096, 1024), "bf16"), ("heavy_f32", (14336, 4096), "f32")])
+def test_k1t_records_equal_oracle_large(kind, shape, dt):
+    torch = _torch()
+    x = gen(kind, 77, shape)
+    tdt = torch.bfloat16 if dt == "bf16" else torch.float32
+    xd = torch.from_numpy(x).to(tdt).cuda()
+    masks = list(_masks()) if dt == "bf16" else [0xF, 0xE, 0x1, 0x6]
+    for mask in masks:
+        got = hb.tile_stats_transposed(xd, mask).cpu().numpy().view(np.uint64)
+        assert np.array_equal(got, _oracle_t(x, mask)), mask
+        ref = hb.tile_stats(xd.T.contiguous(), mask).cpu().numpy().view(np.uint64)   # K1 on a transposed copy
+        assert np.array_equal(got, ref), mask
+
+
+def test_k1t_batched_count3():
+    torch = _torch()
+    xs = gen("heavy_f32", 5, (3, 100, 70))
+    for dt in (torch.float32, torch.bfloat16):
+        xd = torch.from_numpy(xs).to(dt).cuda()
+        xh = xd.float().cpu().numpy()
+        for mask in _masks():
+            got = hb.tile_stats_transposed(xd, mask).cpu().numpy().view(np.uint64)
+            for i in range(3):
+                assert np.array_equal(got[i], _oracle_t(xh[i], mask)), (dt, mask, i)
+
+
+def test_k1t_columns(f15):
+    """Columns summed from K1T records: within 1e-12 of the oracle's columns on Xᵀ, within 2e-4 of the reference's float32 pcc."""
+    torch = _torch()
+    data, meta = f15
+    big = meta["big"]
+    x = gen(big["kind"], big["seed"], tuple(big["shape"]))
+    assert hashlib.sha256(x.tobytes()).hexdigest() == big["x_sha256"]
+    xd = torch.from_numpy(x).to(torch.bfloat16).cuda()
+    stats = hb.tile_stats_transposed(xd, 0xF)
+    host = stats.cpu().numpy()
+    for i, f in enumerate(MIXED):
+        amap = np.full(host.shape[0], i, dtype=np.int8)
+        dev = hb.columns_from_stats_device(stats, 0xF, amap, float(x.size))
+        want = orc.columns_from_stats(orc.tile_stats(np.ascontiguousarray(x.T), MIXED), orc.mask_slots(0xF), amap, x.size)
+        for k, w in zip(("pcc", "mae", "atol"), want):
+            assert abs(dev[k] - w) <= 1e-12 * max(1.0, abs(w)), (f, k, dev[k], w)
+        ref = big["formats"][f]
+        assert abs(dev["pcc"] - ref["pcc"]) <= 2e-4, (f, dev["pcc"], ref["pcc"])
+
+
+def test_plugin_hip_equals_emulation(f15, tmp_path):
+    torch = _torch()
+    from quantization_analysis_amd.compression_algorithms import create_algorithm
+    from quantization_analysis_amd.compression_algorithms.cache import CacheContext
+    from quantization_analysis_amd.compression_algorithms.quantizer import Quantizer
+
+    data, meta = f15
+    for case in meta["cases"]:
+        x = data[f"{case}__x"]
+        xd = torch.from_numpy(x).cuda()
+        cache = CacheContext(tmp_path, case, "hip", True, "t")
+        res = create_algorithm("transpose").run(xd, FORMATS, Quantizer("hip"), cache)
+        slim = create_algorithm("transpose", {"materialize_y": False}).run(xd, FORMATS, Quantizer("hip"), cache)
+        assert [r.fmt for r in res] == [f.upper() for f in FORMATS] and all(r.compression == "transpose" for r in res)
+        for fmt, r, s in zip(FORMATS, res, slim):
+            assert tuple(r.y.shape) == x.shape
+            assert np.array_equal(r.y.cpu().numpy().view(np.uint32).reshape(-1), data[f"{case}__{fmt}"].reshape(-1)), (case, fmt)
+            c_slim, c_full = (np.array([c.meta["columns"][k] for k in ("pcc", "mae", "atol")]) for c in (s, r))
+            assert s.y is None and np.array_equal(c_slim, c_full, equal_nan=True), (case, fmt)
+    # host input gives host output
+    x = data["s33x47__x"]
+    res = create_algorithm("transpose").run(x, ["bfp4"], Quantizer("hip"), CacheContext(tmp_path, "np", "hip", True, "t"))
+    assert isinstance(res[0].y, np.ndarray) and np.array_equal(res[0].y.view(np.uint32), data["s33x47__bfp4"])
+
+
+def _wq(tmp_path, backend, *extra):
+    out = subprocess.run([sys.executable, str(ROOT / "wq"), "synthetic:gpt2", "h.0.attn.c_attn.weight", "--backend", backend,
+                          "--compression-config", str(ROOT / "compression_configs" / "compression_config.transpose.example.json"),
+                          "--results-dir", str(tmp_path / backend), "--no-plots", *extra],
+                         cwd=tmp_path, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr
+    return out.stdout
+
+
+def _table(text):
+    lines = text.splitlines()
+    start = next(i for i, ln in enumerate(lines) if ln.startswith("h.0.attn.c_attn.weight"))
+    end = next(i for i, ln in enumerate(lines) if ln.startswith("results:"))
+    return strip_time("\n".join(lines[start:end]))
+
+
+def test_wq_hip_literal_equals_emulation(tmp_path):
+    emu = _wq(tmp_path, "emulation")
+    lit = _wq(tmp_path, "hip", "--literal-metrics")
+    assert _table(lit) == _table(emu)
+    fast = _wq(tmp_path, "hip")
+    rows = [ln.split() for ln in fast.splitlines() if ln.startswith("  transpose ")]
+    assert [r[1] for r in rows] == [f.upper() for f in FORMATS]
