@@ -20,15 +20,36 @@ from .quantizer import Quantizer
 from .tile_search import TileStats, columns_from_stats, compute_tile_stats, gather_tiles, reconstruct
 from .tile_utils import MIXED_TILE_BYTES_PER_ELEM, MIXED_TILE_FORMATS, mixed_tile_total_bytes, tile_metrics
 
-# float64-moment score vs float32 two-pass score differ by <= 3.1e-7 for scores of order 1 (measured); the
-# float32 error is relative, so the band is KNIFE_BAND * max(1, |threshold|) (csrc/mtq_decide.hpp, sweep.knife_width):
-# golden F13 holds mae thresholds around 1e3.
+# The reference's float32 two-pass score carries a noise of its own (<= 3.1e-7 measured on zero-mean data for scores of order
+# 1); the float32 error is relative, so the band is KNIFE_BAND * max(1, |threshold|) (csrc/mtq_decide.hpp,
+# sweep.knife_width): golden F13 holds mae thresholds around 1e3.  For pcc the band is widened per (tile, format) by the
+# moment form's own error bound, pcc_moment_error.
 KNIFE_BAND = 2e-6
+# csrc/mtq_decide.hpp kSumSqLo, kSumSqHi, kMomentU2, kMomentCondMax
+SUMSQ_LO, SUMSQ_HI, MOMENT_U2, MOMENT_COND_MAX = 2.0 ** -92, 2.0 ** 124, 2.0 ** -23, 2.0 ** 20
 
 
 def knife_width(threshold, band: float = KNIFE_BAND):
-    """Half-width of the band around float32(threshold) inside which a float64-moment score is re-decided literally."""
+    """Half-width of the band around float32(threshold) inside which a float64-moment score is re-decided literally
+    (pcc adds pcc_moment_error per tile)."""
     return band * np.maximum(1.0, np.abs(np.asarray(threshold, dtype=np.float64)))
+
+
+def pcc_moment_error(stats: np.ndarray, slot: int) -> np.ndarray:
+    """The bound of csrc/mtq_decide.hpp pcc_moment_near for every record of float64 [T, 2+5F] `stats` at format slot `slot`
+    → float64 [T]: how far the moment-form pcc can lie from the Pearson r of the float32 data, 2^-23·(κx + κy), and +inf
+    where only the literal float32 score can decide (ill-conditioned tiles, sums of squares outside the float32 dots' safe
+    range)."""
+    n = 1024.0
+    sx, sx2 = stats[:, 0], stats[:, 1]
+    sy, sy2 = stats[:, 2 + 5 * slot], stats[:, 3 + 5 * slot]
+    mean_x, mean_y = sx / n, sy / n
+    am2, bm2 = sx2 - n * mean_x * mean_x, sy2 - n * mean_y * mean_y
+    prod, cross = am2 * bm2, sx2 * bm2 + sy2 * am2
+    ok = (sx2 >= SUMSQ_LO) & (sx2 <= SUMSQ_HI) & (sy2 >= SUMSQ_LO) & (sy2 <= SUMSQ_HI) & (am2 > 0.0) & (bm2 > 0.0)
+    ok &= cross <= MOMENT_COND_MAX * prod
+    with np.errstate(all="ignore"):
+        return np.where(ok, MOMENT_U2 * (cross / prod), np.inf)
 
 
 def threshold_assign(ts: TileStats, tile_formats: list[str], metric: str, threshold: float, quantizer: Quantizer,

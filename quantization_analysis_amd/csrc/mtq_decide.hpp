@@ -70,13 +70,45 @@ MTQ_HD inline double tile_score(const double *r, int slot, int metric)
     return pcc_from_moments(1024.0, r[0], r[1], b.y, b.y2, b.xy, b.ab);
 }
 
+// Is the moment-form pcc of one record slot (n = 1024) possibly further than `gap` from the Pearson r of the float32 data it
+// summarises?  (`gap` = its distance from the threshold beyond the reference's own float32 noise, the caller's band.)  True
+// as well wherever only the literal float32 expression can decide (DESIGN "The knife-edge band of the threshold rule").
+//  - Conditioning: K1 sums float32 products, fl(x·x) = x²(1+δ), |δ| <= u = 2^-24, so Σx², Σy², Σxy are each off by at
+//    most u·Σx², u·Σy², u·Σ|xy| <= u·sqrt(Σx²·Σy²).  The moment form subtracts n·mean² from them, which leaves those errors
+//    standing against am2 = Σx² − n·mean_x² and bm2: to first order |Δr| <= u·(sqrt(κx·κy) + (κx + κy)/2) <= u·(κx + κy)
+//    with κx = Σx²/am2, κy = Σy²/bm2 (1 for zero-mean data, (mean/std)² + 1 for offset data).  The bound used is twice
+//    that, 2^-23·(κx + κy), which also covers the second-order terms while u·(κx + κy) <= 1/16; beyond that (and for
+//    am2 or bm2 <= 0: e.g. a constant side whose float32 squares do not cancel exactly) the answer is always true.  Both
+//    comparisons are multiplied out by am2·bm2 (no division: K4 evaluates this for nearly every tile).
+//  - Range: the reference's float32 dots of the centred values overflow to inf (and its score to NaN) as Σx² or Σy²
+//    approaches FLT_MAX ≈ 2^128, and lose digits to subnormal products (|pc·qc| < 2^-126, up to 2^-126 each, n·2^-126 =
+//    2^-116 in all) — relative to am2 >= Σx²/κx that stays below u·κx while Σx² >= 2^-92.  Outside [2^-92, 2^124] on
+//    either side (non-finite sums included) the answer is true.  Zero is outside too: the float32 squares of non-zero
+//    values below 2^-75 are 0, so a zero Σx² does not mean a zero tile.
+constexpr double kSumSqLo = 0x1p-92, kSumSqHi = 0x1p124, kMomentU2 = 0x1p-23, kMomentCondMax = 0x1p20;   // 1/16 / u
+MTQ_HD inline bool sum_sq_ok(double s2) { return s2 >= kSumSqLo && s2 <= kSumSqHi; }
+MTQ_HD inline bool pcc_moment_near(const double *r, int slot, double gap)
+{
+    const Sums5 b = load5(r, slot);
+    const double n = 1024.0;
+    const double mean_x = r[0] / n;
+    const double mean_y = b.y / n;
+    const double am2 = r[1] - n * mean_x * mean_x;
+    const double bm2 = b.y2 - n * mean_y * mean_y;
+    if (!(sum_sq_ok(r[1]) && sum_sq_ok(b.y2) && am2 > 0.0 && bm2 > 0.0)) return true;
+    const double prod = am2 * bm2, cross = r[1] * bm2 + b.y2 * am2;   // cross / prod = κx + κy
+    if (!(cross <= kMomentCondMax * prod)) return true;
+    return gap * prod <= kMomentU2 * cross;
+}
+
 // mixed_tile_threshold.py:111-123 for one tile: formats in ascending bytes (order[], their record slots in slots[]), the
 // first whose score passes, else `best` (the highest-bytes one).  The reference compares float32 scores with a
 // float32-rounded threshold (NumPy >= 2, NEP 50): thr32 = (double)(float)threshold.  `near` gets bit c for every looked-at
-// format code c whose score lies within `band`·max(1, |thr32|) of thr32 (its decision is inside the float32 noise band — the
-// reference's float32 mean / Pearson carry a RELATIVE error, so for mae thresholds far above 1 the band scales with the
-// threshold: the caller decides exactly those with the literal float32 expression; formats behind the chosen one were not
-// looked at).
+// format code c whose score lies within `band`·max(1, |thr32|) of thr32, widened for pcc by pcc_moment_near (its decision
+// is inside the noise band — the reference's float32 mean / Pearson carry a RELATIVE error, so for mae thresholds far
+// above 1 the band scales with the threshold; the moment form's own error grows with the tile's conditioning, and where
+// the float32 range decides the band is unbounded: the caller decides exactly those with the literal float32 expression;
+// formats behind the chosen one were not looked at).
 struct ThresholdPlan { int order[MTQ_NUM_TILE_FORMATS], slots[MTQ_NUM_TILE_FORMATS], n, best; };
 MTQ_HD inline int threshold_decide(const double *r, const ThresholdPlan &p, int metric, double thr32, double band, unsigned &near)
 {
@@ -85,7 +117,8 @@ MTQ_HD inline int threshold_decide(const double *r, const ThresholdPlan &p, int 
     const double a32 = __builtin_fabs(thr32), width = band * (a32 > 1.0 ? a32 : 1.0);
     for (int i = 0; i < p.n; ++i) {
         const double s = tile_score(r, p.slots[i], metric);
-        if (__builtin_fabs(s - thr32) <= width) near |= 1u << p.order[i];
+        const double d = __builtin_fabs(s - thr32);
+        if (d <= width || (metric == MTQ_METRIC_PCC && pcc_moment_near(r, p.slots[i], d - width))) near |= 1u << p.order[i];
         if (is_good((double)(float)s, metric, thr32)) { chosen = p.order[i]; break; }
     }
     return chosen;

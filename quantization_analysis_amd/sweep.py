@@ -3,16 +3,16 @@
 The reference quantizes the tensor once per format, scores every tile (float32), then for each of `steps` thresholds
 re-gathers 64 MiB of tiles and recomputes float32 tensor metrics.  Here ONE K1 pass gives the per-tile records; every
 threshold step is then an O(tiles) selection plus a sum of already-computed records.  Tiles whose
-float64-moment score comes within KNIFE_BAND of any threshold get the literal float32 score, so every step's
-assignment is the reference's assignment.
+float64-moment score comes within the knife-edge band of any threshold (KNIFE_BAND, for pcc widened by the moment form's
+error bound of the tile) get the literal float32 score, so every step's assignment is the reference's assignment.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .compression_algorithms.mixed_tile_threshold import KNIFE_BAND, knife_width
+from .compression_algorithms.mixed_tile_threshold import KNIFE_BAND, knife_width, pcc_moment_error
 from .compression_algorithms.quantizer import Quantizer
-from .compression_algorithms.tile_search import columns_from_stats, compute_tile_stats, literal_inputs, tile_scores
+from .compression_algorithms.tile_search import columns_from_stats, compute_tile_stats, literal_inputs, slot_of, tile_scores
 from .compression_algorithms.tile_utils import MIXED_TILE_BYTES_PER_ELEM, MIXED_TILE_FORMATS, mixed_tile_total_bytes, tile_metrics
 
 
@@ -115,6 +115,11 @@ def sweep_tensor(xf, formats: list[str], metric: str, lowest_metric_val: float, 
     s32 = s64.astype(np.float32)
 
     hi = by_prec.index(highest)
+    # the moment form's own error per (format, tile) widens the band (+inf: only the literal score decides; csrc/mtq_decide.hpp)
+    err = np.zeros_like(s64)
+    if metric == "pcc":
+        recs = ts.host_stats if ts.host_stats is not None else ts.stats_dev.cpu().numpy()   # not cached: the columns stay on the device
+        err = np.stack([pcc_moment_error(recs, slot_of(ts.mask, f)) for f in by_prec])
     if metric == "pcc":                                                               # :659-670
         start = float(np.max(s32[hi]))
         if lowest_metric_val > start:
@@ -126,8 +131,11 @@ def sweep_tensor(xf, formats: list[str], metric: str, lowest_metric_val: float, 
     # the start of the sweep is itself a float32 tile score of the reference: take the literal one for the extreme tile
     literal_hi = np.zeros(s64.shape[1], dtype=bool)   # tiles of the highest-precision format that already carry their literal score
     if metric != "atol":
-        t_ext = int(np.argmax(s32[hi]) if metric == "pcc" else np.argmin(s32[hi]))
-        cand = np.unique(np.concatenate([[t_ext], np.where(np.abs(s64[hi] - s64[hi][t_ext]) <= knife_width(s64[hi][t_ext]))[0]]))
+        # the extreme among the tiles with a bounded error; every tile whose literal score could pass it is scored literally
+        bounded = np.where(np.isinf(err[hi]), np.float32(-np.inf if metric == "pcc" else np.inf), s32[hi])
+        t_ext = int(np.argmax(bounded) if metric == "pcc" else np.argmin(bounded))
+        reach = knife_width(s64[hi][t_ext]) + err[hi][t_ext] + err[hi]
+        cand = np.unique(np.concatenate([[t_ext], np.where((np.abs(s64[hi] - s64[hi][t_ext]) <= reach) | np.isinf(err[hi]))[0]]))
         # identity-like formats (bf16 of bf16 data, bf16 of fp8-block data) put EVERY tile inside the band: the literal float32 scores
         # are 1 ± a few ulp and the reference's start value is their exact maximum (a 2-ulp outlier among 10^5 tiles decides it, so a
         # sample is not enough: golden-size check tests/test_configs_gpu.py::test_config4_sweep_deepseek_layer0) — all of them are scored,
@@ -147,7 +155,8 @@ def sweep_tensor(xf, formats: list[str], metric: str, lowest_metric_val: float, 
             pos = np.searchsorted(srt, s64[fi])
             for off in (-1, 0):
                 idx = np.clip(pos + off, 0, srt.size - 1)
-                near |= np.abs(s64[fi] - srt[idx]) <= knife_width(srt[idx])
+                near |= np.abs(s64[fi] - srt[idx]) <= knife_width(srt[idx]) + err[fi]
+            near |= np.isinf(err[fi])
             if fi == hi:
                 near &= ~literal_hi
             ids = np.where(near)[0]

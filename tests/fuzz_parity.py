@@ -1,7 +1,9 @@
 """Randomised GPU-vs-oracle parity sweep (not collected by pytest; run by hand on an MI355X box):
     python tests/fuzz_parity.py [cases] [seed]
 Random shapes (ragged and aligned), storage types, value distributions (wide exponent spreads, zeros, sparse groups,
-huge / tiny scales, ±Inf / NaN / denormals — two NaNs compare equal whatever their payload), format subsets: K1 records, K2 / K3 outputs and greedy / threshold maps against the CPU oracle, bit for bit."""
+huge / tiny scales, ±Inf / NaN / denormals, offset tensors, the scales where the reference's float32 dots overflow or go
+subnormal — two NaNs compare equal whatever their payload), format subsets: K1 / K1T records, K2 / K2T / K3 outputs and
+greedy / threshold maps against the CPU oracle, bit for bit."""
 import sys
 import time
 
@@ -12,12 +14,15 @@ import torch  # noqa: E402
 
 from oracle import mtq_oracle as orc  # noqa: E402
 from quantization_analysis_amd import hip_backend as hb  # noqa: E402
+from quantization_analysis_amd.compression_algorithms.mixed_tile_threshold import threshold_assign  # noqa: E402
+from quantization_analysis_amd.compression_algorithms.quantizer import Quantizer  # noqa: E402
+from quantization_analysis_amd.compression_algorithms.tile_search import compute_tile_stats  # noqa: E402
 
 ALL = ["bf16", "bfp8", "bfp4", "bfp2"]
 
 
 def make(rng, shape, bf16):
-    kind = rng.integers(0, 8)
+    kind = rng.integers(0, 10)
     x = rng.standard_normal(shape)
     if kind == 1:
         x *= np.exp(rng.standard_normal(shape) * 2.0)
@@ -29,6 +34,10 @@ def make(rng, shape, bf16):
         x *= np.repeat(rng.random((shape[0], -(-shape[1] // 16))) < 0.5, 16, axis=1)[:, : shape[1]]
     elif kind == 5:
         x *= np.exp2(float(rng.integers(-60, 60)))
+    elif kind == 8:  # offset (mean >> spread: layer-norm-like weights), mean/std from 1 to 10^3
+        x = x + float(rng.choice([1.0, 10.0, 50.0, 100.0, 1000.0]))
+    elif kind == 9:  # the windows where the reference's float32 dots overflow (2^60..2^70) or go subnormal (2^-75..2^-62)
+        x *= np.exp2(float(rng.choice([rng.integers(60, 71), rng.integers(-75, -61)])))
     x = (x * 0.02).astype(np.float32)
     if kind == 6:   # specials: ±Inf, NaN, ±0, float32 denormals, the largest finite values
         pool = np.array([np.inf, -np.inf, np.nan, 0.0, -0.0, 1e-40, -3e-39, 3.4e38, -3.3e38, 1.1754944e-38], dtype=np.float32)
@@ -102,6 +111,7 @@ def run(cases: int, seed: int) -> int:
     t0 = time.time()
     bad = 0
     compared = handed_back = specials = specials_back = 0
+    thr_compared = thr_knife = 0
     for c in range(cases):
         aligned = rng.random() < 0.4
         rows = int(rng.integers(1, 6)) * 32 if aligned else int(rng.integers(1, 200))
@@ -120,6 +130,9 @@ def run(cases: int, seed: int) -> int:
             th, tw = -(-rows // 32), -(-cols // 32)
             amap = rng.integers(0, 4, size=(th, tw)).astype(np.int8)
             ok_a = eq(hb.apply_assignment(xd, amap).cpu().numpy(), orc.apply_assignment(x, amap))
+            # K1T / K2T (the transpose algorithm's record and quantize kernels) against the oracle on Xᵀ
+            ok_tr = eq(hb.tile_stats_transposed(xd, mask).cpu().numpy(), orc.tile_stats(np.ascontiguousarray(x.T), fm))
+            ok_tr &= eq(hb.quantize_transposed(xd, fmt).cpu().numpy(), np.ascontiguousarray(orc.quantize_weight_values(np.ascontiguousarray(x.T), fmt).T))
             ok_g = ok_t = True
             if c % 4 == 0 and kind_ok(x):
                 thr = float(rng.choice([0.99, 0.999, 0.9]))
@@ -154,6 +167,19 @@ def run(cases: int, seed: int) -> int:
                 ga, _ca, _oa = hb.greedy_run(full, 0xF, ALL, "atol", thr_a, float(x.size), 7)
                 dm, ds = hb.greedy_scan_device(recs_d, 0xF, ALL, "atol", thr_a, float(x.size), sd)
                 ok_g &= int(ds.cpu()[0]) == 0 and np.array_equal(dm.cpu().numpy()[0], ga)
+                # the threshold rule (K4 on the device, knife-edge tiles re-scored literally through K2) against the literal float32 rule:
+                # pcc at a threshold ON a tile's float32 score, and mae
+                ts = compute_tile_stats(xd, ALL, Quantizer("hip"))
+                for met in ("pcc", "mae"):
+                    sc = orc.threshold_scores(x, ALL, met)
+                    pick = sc[ALL[int(rng.integers(1, 4))]]
+                    pick = pick[np.isfinite(pick)]
+                    thr_t = float(pick[int(rng.integers(0, pick.size))]) if pick.size else (thr if met == "pcc" else thr_m)
+                    want_t = orc.threshold_assign(sc, ALL, met, thr_t)
+                    got_t, n_knife = threshold_assign(ts, ALL, met, thr_t, Quantizer("hip"))
+                    ok_t &= np.array_equal(got_t.reshape(-1), want_t)
+                    thr_compared += 1
+                    thr_knife += n_knife
                 order = [ALL[k] for k in rng.permutation(4)[: int(rng.integers(1, 5))]]
                 s2 = int(rng.integers(1, 2**31))
                 gh, _ch, _oh = hb.greedy_run(full, 0xF, order, "pcc", thr, float(x.size), s2)
@@ -192,11 +218,19 @@ def run(cases: int, seed: int) -> int:
                     dm2, ds2 = hb.greedy_scan_device(torch.from_numpy(full).cuda()[None], 0xF, ALL, met, th2, float(x.size), sd)
                     if int(ds2.cpu()[0]) == 0:
                         ok_g &= np.array_equal(dm2.cpu().numpy()[0], gh2)
-        if not (ok and ok_q and ok_a and ok_g and ok_t):
+        if not (ok and ok_q and ok_a and ok_g and ok_t and ok_tr):
             bad += 1
-            print(f"MISMATCH case {c}: shape {(rows, cols)} bf16 {bf16} mask {mask:#x} fmt {fmt}: stats {ok} quantize {ok_q} apply {ok_a} greedy {ok_g}", flush=True)
+            print(f"MISMATCH case {c}: shape {(rows, cols)} bf16 {bf16} mask {mask:#x} fmt {fmt}: stats {ok} quantize {ok_q} apply {ok_a} greedy {ok_g} "
+                  f"threshold {ok_t} transposed {ok_tr}", flush=True)
     print(f"{cases} cases, {bad} mismatches, {time.time() - t0:.1f} s; device pcc searches compared {compared}, handed back {handed_back} "
-          f"(each checked against the host scan's zero-denominator branch); special-value inputs {specials}, handed back {specials_back}")
+          f"(each checked against the host scan's zero-denominator branch); special-value inputs {specials}, handed back {specials_back}; "
+          f"threshold maps compared {thr_compared}, knife-edge tiles {thr_knife}")
+    if cases >= 8 and not thr_compared:
+        print("no threshold map was compared")
+        bad += 1
+    if thr_compared >= 20 and not thr_knife:
+        print("no threshold comparison met a knife-edge tile: the thresholds placed on tile scores are not reaching the band")
+        bad += 1
     if compared and handed_back > compared // 2:
         print("more than half of the device searches were handed back: the comparison is not comparing")
         bad += 1
