@@ -173,6 +173,16 @@ int mtq_quantize_transposed(const void *x, int in_dtype, int64_t rows, int64_t c
                             int fmt, float *y, int64_t ldy, void *stream);
 
 /*
+ * K3T apply_assignment_transposed — y = (K3 of Xᵀ with `map`)ᵀ as float32 into a row-major rows × cols y (leading dimension ldy) for
+ * `count` equally shaped matrices at x + i*stride_elems (y of matrix i at y + i*rows*ldy, its map at map + i*tiles): bit for bit
+ * mtq_apply_assignment on a contiguous copy of Xᵀ, transposed back.  map is Xᵀ's grid, ceil(cols/32) × ceil(rows/32), row-major, on
+ * device — K1T's tile numbering: element (r, c) of X takes the format of entry (c/32)·ceil(rows/32) + r/32.  A shared exponent covers
+ * 16 consecutive rows of one column of X (the mixed-tile searches with params["layout"] = "transpose").
+ */
+int mtq_apply_assignment_transposed(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,
+                                    int64_t ld, const int8_t *map, float *y, int64_t ldy, void *stream);
+
+/*
  * K3 apply_assignment — y where each 32×32 tile uses the format its int8 map entry names.
  * Replaces the tile gather/scatter of mixed_tile_threshold.py:125-132, mixed_tile_greedy.py:273,348-352
  * and scripts/reconstruct_mixed_tile_assignment.py:82-94.  map is tiles_h × tiles_w, row-major, on device.
@@ -366,6 +376,12 @@ int mtq_scan_orders_device(uint64_t seed, int64_t tiles, int n_orders, void *ord
 int mtq_knife_tiles_device(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
                            const int8_t *near, const int *formats, int n_formats, int64_t cap, int64_t *list, float *tiles_out, void *stream);
 
+/* mtq_knife_tiles_device applied to Xᵀ, read from the row-major X in place: `near` holds one int8 per tile of Xᵀ's grid (K1T's
+ * numbering), list as there, and slot p = 0 of tiles_out holds the 32×32 Xᵀ tile in Xᵀ's row-major order, p = 1 + i its reconstruction
+ * in formats[i].  Equal to mtq_knife_tiles_device on a contiguous copy of Xᵀ.  n_formats may be 0 (formats may then be NULL): the tiles alone. */
+int mtq_knife_tiles_transposed(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                               const int8_t *near, const int *formats, int n_formats, int64_t cap, int64_t *list, float *tiles_out, void *stream);
+
 /* One batch of the streamed threshold driver as ONE call (round 4: behind Python every launch costs the driver 10–20 us, and a model's
  * small tensors — DeepSeek-R1 layer 0: seven tensors, 183 k tiles, 0.45 ms of K1 — were launch-bound at a dozen calls per batch):
  * mtq_tile_stats_batched(k1_mask) → mtq_threshold_assign_device(dec_mask: k1_mask, or k1_mask | MTQ_MASK_BF16_IDENTITY) into
@@ -380,6 +396,13 @@ int mtq_threshold_enqueue(const void *x, int in_dtype, int64_t count, int64_t st
                           uint32_t k1_mask, uint32_t dec_mask, const int *formats, int n_formats, int metric, double threshold, double band,
                           double *stats, int8_t *both_dev, int8_t *both_host, int64_t cap, int64_t *list_dev, float *knife_dev,
                           int64_t *list_host, double *scratch, double *sums_host, void *stream, void *side_stream);
+/* mtq_threshold_enqueue for the search of Xᵀ of every matrix (params["layout"] = "transpose"): the same arguments and stages with
+ * mtq_tile_stats_transposed as stage one and mtq_knife_tiles_transposed as the listing — records, maps, masks and list ids over Xᵀ's
+ * grid (K1T's numbering, as many tiles as X's).  mtq_threshold_columns serves its records unchanged. */
+int mtq_threshold_enqueue_transposed(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                                     uint32_t k1_mask, uint32_t dec_mask, const int *formats, int n_formats, int metric, double threshold, double band,
+                                     double *stats, int8_t *both_dev, int8_t *both_host, int64_t cap, int64_t *list_dev, float *knife_dev,
+                                     int64_t *list_host, double *scratch, double *sums_host, void *stream, void *side_stream);
 /* … and its second half: mtq_column_sums_device_batched under the (patched) maps, the seven sums of every tensor and behind them the
  * map's tile count per format code 0..3 (mixed_tile_threshold.py:133-135's bincount, as doubles) into the pinned sums_host[count][11]
  * (wq:683-706's columns come from the sums: mtq_columns_from_sums). */

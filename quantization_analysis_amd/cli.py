@@ -37,6 +37,16 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 FORMAT_BYTES_PER_ELEM = {"bf16": 2.0, "bfp8": 1.088, "bfp4": 0.50097, "bfp2": 0.25097, "fp0": 0.0}  # wq:132-140
 MIXED_ALGOS = {"mixed-tile-greedy", "mixed-tile-random", "mixed-tile-threshold"}
+
+
+def display_name(algo) -> str:
+    """The name of an algorithm's rows, results directory and plots: a mixed-tile search over the transposed layout
+    (params["layout"] = "transpose") reads "<algorithm>+transpose", as its CompressionResult.compression does."""
+    return f"{algo.name}+transpose" if getattr(algo, "layout", "rows") == "transpose" else algo.name
+
+
+def _is_mixed(comp: str) -> bool:
+    return comp.split("+", 1)[0] in MIXED_ALGOS
 ROW_W = 16  # summary row: idx, comp, fmt, pcc, mae, atol, time, gb, tile_bytes, 4 counts, xmin, xmean, xmax
 
 
@@ -250,14 +260,14 @@ def _evaluate_tensor(idx, name, index, algorithms, formats, quantizer, args, run
             rows.append([idx, ci, fcode, pcc, mae, atol, elapsed, gb, res.tile_bytes if res.tile_bytes is not None else np.nan,
                          *counts, *meta])
             draw = not args.no_plots
-            if res.compression == "mixed-tile-random" and res.meta:  # wq:711-722
+            if res.compression.split("+", 1)[0] == "mixed-tile-random" and res.meta:  # wq:711-722 (either layout)
                 if isinstance(res.meta.get("samples"), list) and res.meta.get("tile_formats"):
                     write_random_outputs(results_dir, name, res.meta["samples"], res.meta["tile_formats"], res.meta.get("assignment"), draw)
-            elif res.compression in MIXED_ALGOS and res.meta and isinstance(res.meta.get("assignment"), np.ndarray):
+            elif _is_mixed(res.compression) and res.meta and isinstance(res.meta.get("assignment"), np.ndarray):
                 write_assignment_outputs(results_dir, name, res.meta["assignment"], res.compression.replace("-", "_"), draw)
     out = np.asarray(rows, dtype=np.float64).reshape(-1, ROW_W)
     if not args.no_plots and len(algorithms) > 1 and algorithms[1].name in {"mixed-tile-threshold", "mixed-tile-greedy"}:  # wq:743-750
-        write_size_plot(results_dir, name, algorithms[1].params.get("metric", "pcc"), out, formats, algorithms[1].name)
+        write_size_plot(results_dir, name, algorithms[1].params.get("metric", "pcc"), out, formats, display_name(algorithms[1]))
     return out
 
 
@@ -284,7 +294,7 @@ def _print_tables(names, rows, comp_names, shapes, table_lines, summary: bool, f
                 continue
             fmts = ["MIXED" if int(r[2]) < 0 else SUPPORTED_FORMATS[int(r[2])].upper() for r in crs]
             fmt_w = max(len(f) for f in fmts)
-            mixed = comp in MIXED_ALGOS
+            mixed = _is_mixed(comp)
             pcc_w = max(len("PCC"), max(len(f"{r[3]: .5f}") for r in crs))
             mae_w = max(len("MAE"), max(len(f"{r[4]:.3e}") for r in crs))
             atol_w = max(len("ATOL"), max(len(f"{r[5]:.3e}") for r in crs))
@@ -309,7 +319,7 @@ def _print_tables(names, rows, comp_names, shapes, table_lines, summary: bool, f
     if summary:  # wq:851-879
         emit("Summary (mean across matched tensors)")
         for comp in comp_names:
-            for f in (["MIXED"] if comp in MIXED_ALGOS else [x.upper() for x in formats]):
+            for f in (["MIXED"] if _is_mixed(comp) else [x.upper() for x in formats]):
                 rs = aggregate.get((comp, f), [])
                 if not rs:
                     continue
@@ -354,7 +364,7 @@ def _evaluate_shard(shard, tensor_names, index, algorithms, selected_algo, forma
         groups: dict = {}
         per_tensor = []
         for i in shard:
-            k = streamed.group_key(index, tensor_names[i])
+            k = streamed.group_key(index, tensor_names[i], getattr(selected_algo, "layout", "rows"))
             if k is None:
                 per_tensor.append(i)
             else:
@@ -376,12 +386,12 @@ def _evaluate_shard(shard, tensor_names, index, algorithms, selected_algo, forma
         streamed_note = None
     for i in per_tensor:
         rows_by_idx[i] = _evaluate_tensor(i, tensor_names[i], index, algorithms, formats, quantizer, args, run_tag, processed_root, results_dir)
-    algo_dir = selected_algo.name.replace("-", "_")
+    algo_dir = display_name(selected_algo).replace("-", "_")   # as the per-tensor route names it (res.compression)
     t_art = time.perf_counter()
     for idx, name, assignment in deferred:   # wq:696-750, after the GPU work
         write_assignment_outputs(results_dir, name, assignment, algo_dir, not args.no_plots)
         if not args.no_plots:
-            write_size_plot(results_dir, name, selected_algo.params.get("metric", "pcc"), rows_by_idx[idx], formats, selected_algo.name)
+            write_size_plot(results_dir, name, selected_algo.params.get("metric", "pcc"), rows_by_idx[idx], formats, display_name(selected_algo))
     if streamed_note:   # where the wall time of the streamed part went: the path itself is the middle number
         notes.append(streamed_note + f"; wall: loader {load_s:.1f} s, pipeline {ev.compute_seconds:.3f} s, maps and plots to disk {time.perf_counter() - t_art:.1f} s")
     ordered = [rows_by_idx[i] for i in sorted(rows_by_idx)]
@@ -475,7 +485,7 @@ def run(argv=None) -> int:
             except Exception as exc:  # noqa: BLE001
                 raise _JobError(f"error: {exc}") from exc
 
-            comp_names = [a.name for a in algorithms]
+            comp_names = [display_name(a) for a in algorithms]
             if rank == 0:
                 print(f"{index.repo_id} @{index.revision} - {len(tensor_names)} tensors")
                 print(f"formats: {', '.join(formats)}")
@@ -485,7 +495,7 @@ def run(argv=None) -> int:
                     print(f"config: {args.compression_config}")
                 print()
 
-            results_dir = Path(args.results_dir) / index.repo_id.replace("/", "__") / selected_algo.name / run_tag  # wq:629-631
+            results_dir = Path(args.results_dir) / index.repo_id.replace("/", "__") / display_name(selected_algo) / run_tag  # wq:629-631
             results_dir.mkdir(parents=True, exist_ok=True)
             if rank == 0:
                 used_params = dict(algo_params)

@@ -14,7 +14,7 @@ import numpy as np
 from .base import CompressionAlgorithm, CompressionResult
 from .cache import CacheContext
 from .quantizer import Quantizer
-from .tile_search import TileStats, columns_from_stats, compute_tile_stats, reconstruct
+from .tile_search import TileStats, columns_from_stats, compute_tile_stats, parse_layout, reconstruct, run_in_layout
 from .tile_utils import MIXED_TILE_FORMATS, mixed_tile_total_bytes
 
 
@@ -78,6 +78,7 @@ class MixedTileGreedyCompression(CompressionAlgorithm):
         self.seed = int(self.params.get("seed", 0))
         self.tile_formats = parse_tile_formats(raw_formats) if raw_formats is not None else None
         self.materialize_y = bool(self.params.get("materialize_y", True))  # ours: skip the y copy in throughput runs
+        self.layout = parse_layout(self.params)   # "transpose": the search runs on np.transpose(x) (tile_search.run_in_layout)
         if self.metric not in {"pcc", "mae", "atol"}:
             raise ValueError(f"Unsupported metric: {self.metric}")
 
@@ -101,6 +102,9 @@ class MixedTileGreedyCompression(CompressionAlgorithm):
         return allowed
 
     def run(self, xf, formats: list[str], quantizer: Quantizer, cache: CacheContext) -> list[CompressionResult]:
+        return run_in_layout(lambda x: self._run_rows(x, formats, quantizer, cache), xf, quantizer, self.layout)
+
+    def _run_rows(self, xf, formats: list[str], quantizer: Quantizer, cache: CacheContext) -> list[CompressionResult]:
         tile_formats = self.tile_formats or self._filter_from_formats(formats)
         size = int(np.asarray(xf).size) if isinstance(xf, np.ndarray) or np.isscalar(xf) else int(xf.numel())
         if size == 0:  # :78-83

@@ -18,13 +18,15 @@ import numpy as np
 from .base import CompressionAlgorithm, CompressionResult
 from .metrics import metric_better, metric_is_good, metric_value
 from .mixed_tile_greedy import parse_tile_formats
-from .tile_search import TileStats, columns_from_stats, compute_tile_stats, reconstruct
+from .tile_search import TileStats, TransposedInput, columns_from_stats, compute_tile_stats, parse_layout, reconstruct, run_in_layout
 from .tile_utils import MIXED_TILE_BYTES_PER_ELEM, MIXED_TILE_FORMATS, mixed_tile_total_bytes
 
 SCORE_BAND = 1e-5  # |float64-moment score − float32 whole-tensor score| stays below this (relative to max(1, |thr|))
 
 
 def _host_f32(x) -> np.ndarray:
+    if isinstance(x, TransposedInput):
+        return x.host()
     return np.asarray(x.float().cpu().numpy() if hasattr(x, "cpu") else x, dtype=np.float32)
 
 
@@ -47,7 +49,8 @@ def random_search(ts: TileStats, xf, tile_formats: list[str], metric: str, thres
         if i not in literal:
             if x_host is None:
                 x_host = _host_f32(xf)
-            literal[i] = metric_value(x_host, _host_f32(reconstruct(ts, maps[i], quantizer)), metric)  # :138-139
+            y_host = np.ascontiguousarray(_host_f32(reconstruct(ts, maps[i], quantizer)))   # the reference's y is a fresh C-order array
+            literal[i] = metric_value(x_host, y_host, metric)  # :138-139
         return literal[i]
 
     def near(a: float, b: float) -> bool:
@@ -90,6 +93,7 @@ class MixedTileRandomCompression(CompressionAlgorithm):
         self.seed = int(self.params.get("seed", 0))
         self.formats = parse_tile_formats(self.params.get("formats"))
         self.materialize_y = bool(self.params.get("materialize_y", True))
+        self.layout = parse_layout(self.params)   # "transpose": the search runs on np.transpose(x) (tile_search.run_in_layout)
         if self.metric not in {"pcc", "mae", "atol"}:
             raise ValueError(f"Unsupported metric: {self.metric}")
         if self.iters < 1:
@@ -111,6 +115,9 @@ class MixedTileRandomCompression(CompressionAlgorithm):
         return allowed
 
     def run(self, xf, formats: list[str], quantizer, cache) -> list[CompressionResult]:
+        return run_in_layout(lambda x: self._run_rows(x, formats, quantizer, cache), xf, quantizer, self.layout)
+
+    def _run_rows(self, xf, formats: list[str], quantizer, cache) -> list[CompressionResult]:
         tile_formats = self.formats or self._filter_from_formats(formats)
         size = int(np.asarray(xf).size) if isinstance(xf, np.ndarray) or np.isscalar(xf) else int(xf.numel())
         counts = {fmt: 0 for fmt in MIXED_TILE_FORMATS}

@@ -17,7 +17,7 @@ from .cache import CacheContext
 from .metrics import metric_is_good
 from .mixed_tile_greedy import parse_tile_formats
 from .quantizer import Quantizer
-from .tile_search import TileStats, columns_from_stats, compute_tile_stats, gather_tiles, reconstruct
+from .tile_search import TileStats, columns_from_stats, compute_tile_stats, gather_tiles, parse_layout, reconstruct, run_in_layout
 from .tile_utils import MIXED_TILE_BYTES_PER_ELEM, MIXED_TILE_FORMATS, mixed_tile_total_bytes, tile_metrics
 
 # The reference's float32 two-pass score carries a noise of its own (<= 3.1e-7 measured on zero-mean data for scores of order
@@ -131,6 +131,7 @@ class MixedTileThresholdCompression(CompressionAlgorithm):
         raw_formats = self.params.get("formats", self.params.get("tile_formats"))
         self.tile_formats = parse_tile_formats(raw_formats) if raw_formats is not None else None
         self.materialize_y = bool(self.params.get("materialize_y", True))
+        self.layout = parse_layout(self.params)   # "transpose": the search runs on np.transpose(x) (tile_search.run_in_layout)
         if self.metric not in {"pcc", "mae", "atol"}:
             raise ValueError(f"Unsupported metric: {self.metric}")
 
@@ -154,6 +155,9 @@ class MixedTileThresholdCompression(CompressionAlgorithm):
         return allowed
 
     def run(self, xf, formats: list[str], quantizer: Quantizer, cache: CacheContext) -> list[CompressionResult]:
+        return run_in_layout(lambda x: self._run_rows(x, formats, quantizer, cache), xf, quantizer, self.layout)
+
+    def _run_rows(self, xf, formats: list[str], quantizer: Quantizer, cache: CacheContext) -> list[CompressionResult]:
         tile_formats = self.tile_formats or self._filter_from_formats(formats)
         size = int(np.asarray(xf).size) if isinstance(xf, np.ndarray) or np.isscalar(xf) else int(xf.numel())
         if size == 0:  # :76-81

@@ -23,6 +23,7 @@ from .quantizer import Quantizer
 from .tile_utils import MIXED_TILE_FORMATS, flatten_2d, unflatten_2d
 
 TILE = 32
+LAYOUTS = ("rows", "transpose")
 
 
 def fmt_mask(formats) -> int:
@@ -53,6 +54,7 @@ class TileStats:
     input_was_numpy: bool
     host_stats: Optional[np.ndarray] = None   # float64 [tiles, 2+5F] on the host
     stats_dev: object = None                  # the same records where K1 wrote them (hip backend)
+    transposed: bool = False                  # x2d is the 2-D X itself and the records are K1T's records of Xᵀ (layout "transpose", hip)
 
     @property
     def stats(self) -> np.ndarray:
@@ -78,6 +80,81 @@ class TileStats:
 
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
+
+
+def parse_layout(params: dict) -> str:
+    """params["layout"] of a mixed-tile search: "rows" (the default) or "transpose" (the search runs on np.transpose(x))."""
+    layout = params.get("layout", "rows")
+    if layout not in LAYOUTS:
+        raise ValueError(f"Unsupported layout: {layout!r} (expected one of {', '.join(LAYOUTS)})")
+    return layout
+
+
+class TransposedInput:
+    """Xᵀ of a device tensor X for the row-layout body of a mixed-tile search (layout "transpose", hip backend).  Rank 2: X is read in
+    place (K1T records, K3T for y, the transposed knife-edge gather).  Rank >= 3: np.transpose reverses every axis, so the 2-D view of
+    Xᵀ is not V.T for V = X.reshape(d0, -1); a permuted contiguous copy then goes through the row-layout kernels."""
+
+    def __init__(self, x, was_numpy: bool):
+        self.x = x
+        self.was_numpy = was_numpy
+        self.copy = None if x.dim() == 2 else x.permute(*reversed(range(x.dim()))).contiguous()
+
+    def numel(self) -> int:
+        return int(self.x.numel())
+
+    def host(self) -> np.ndarray:
+        """np.transpose of X's float32 host copy: a view, as the reference holds np.transpose(x)."""
+        return np.transpose(self.x.float().cpu().numpy())
+
+
+def _transpose_back(y):
+    if y is None:
+        return None
+    if _is_torch(y):
+        return y.permute(*reversed(range(y.dim()))).contiguous()
+    return np.ascontiguousarray(np.transpose(np.asarray(y)))
+
+
+def _transposed_input(xf) -> TransposedInput:
+    """A host array or torch tensor of rank >= 2 → TransposedInput over its device copy (bf16 stays bf16, everything else → float32)."""
+    from .. import hip_backend as hb
+
+    was_np = not _is_torch(xf)
+    if was_np:
+        x = hb.to_device_2d(xf)[0].reshape(np.shape(xf))
+    else:
+        torch = __import__("torch")
+        x = xf if xf.dtype in (torch.bfloat16, torch.float32) else xf.float()
+        if not x.is_cuda:
+            x = x.to(torch.device("cuda", torch.cuda.current_device()))
+        if x.stride(-1) != 1:   # a fresh tensor: .contiguous() keeps the strides of a view whose odd dimensions have size 1
+            x = torch.empty(x.shape, dtype=x.dtype, device=x.device).copy_(x)
+    return TransposedInput(x, was_np)
+
+
+def run_in_layout(body, xf, quantizer: Quantizer, layout: str) -> list:
+    """body(x) → the row-layout results of a mixed-tile search on x.  Layout "transpose": body runs on np.transpose(xf) (a TransposedInput
+    on the hip backend), y is transposed back and `compression` reads "<algorithm>+transpose".  Rank <= 1 (np.transpose is the identity)
+    and empty tensors give the row-layout results."""
+    if layout == "rows":
+        return body(xf)
+    ndim = int(xf.dim()) if _is_torch(xf) else int(np.ndim(xf))
+    size = int(xf.numel()) if _is_torch(xf) else int(np.size(xf))
+    if ndim <= 1 or size == 0:
+        results = body(xf)
+    elif quantizer.backend == "hip":
+        results = body(_transposed_input(xf))
+        for r in results:
+            r.y = _transpose_back(r.y)
+    else:
+        xh = xf.detach().to("cpu").float().numpy() if _is_torch(xf) else np.asarray(xf, dtype=np.float32)
+        results = body(np.transpose(xh))
+        for r in results:
+            r.y = _transpose_back(r.y)
+    for r in results:
+        r.compression = f"{r.compression}+transpose"
+    return results
 
 
 def host_tile_stats(x2d: np.ndarray, formats_in_mask_order: list[str], quantizer: Quantizer) -> np.ndarray:
@@ -119,10 +196,31 @@ def host_tile_stats(x2d: np.ndarray, formats_in_mask_order: list[str], quantizer
     return np.ascontiguousarray(np.stack(cols, axis=1))
 
 
-def compute_tile_stats(xf, formats: list[str], quantizer: Quantizer) -> TileStats:
-    """One stats record per 32x32 tile of xf for the given mixed-tile formats."""
+def compute_tile_stats(xf, formats: list[str], quantizer: Quantizer, layout: str = "rows") -> TileStats:
+    """One stats record per 32x32 tile of xf for the given mixed-tile formats.  layout "transpose": the tiles of np.transpose(xf) —
+    K1T's records of X read in place for a rank-2 device tensor, the row-layout records of a transposed copy otherwise."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"Unsupported layout: {layout!r}")
+    if layout == "transpose":
+        ndim = int(xf.dim()) if _is_torch(xf) else int(np.ndim(xf))
+        if ndim >= 2:
+            if quantizer.backend == "hip":
+                return compute_tile_stats(_transposed_input(xf), formats, quantizer)
+            xh = xf.detach().to("cpu").float().numpy() if _is_torch(xf) else np.asarray(xf, dtype=np.float32)
+            return compute_tile_stats(np.transpose(xh), formats, quantizer)
     mask = fmt_mask(formats)
     fm = mask_formats(mask)
+    if isinstance(xf, TransposedInput):
+        if xf.copy is not None:
+            ts = compute_tile_stats(xf.copy, formats, quantizer)
+            ts.input_was_numpy = xf.was_numpy
+            return ts
+        from .. import hip_backend as hb
+
+        rows, cols = xf.x.shape
+        th, tw = hb.tiles_hw(cols, rows)
+        return TileStats(mask, th, tw, xf.numel(), ("nd", (cols, rows)), xf.x, "hip", xf.was_numpy,
+                         stats_dev=hb.tile_stats_transposed(xf.x, mask), transposed=True)
     if quantizer.backend == "hip":
         from .. import hip_backend as hb
 
@@ -143,6 +241,11 @@ def reconstruct(ts: TileStats, assignment: np.ndarray, quantizer: Quantizer):
     """y whose tile t uses format MIXED_TILE_FORMATS[assignment[t]] (mixed_tile_threshold.py:125-132,
     mixed_tile_greedy.py:273,348-352).  hip: K3 on the device."""
     a = np.asarray(assignment, dtype=np.int8).reshape(ts.tiles_h, ts.tiles_w)
+    if ts.transposed:   # K3T reads X in place and writes y in X's orientation: Xᵀ's reconstruction is its transpose
+        from .. import hip_backend as hb
+
+        y = hb.apply_assignment_transposed(ts.x2d, a).T
+        return y.cpu().numpy() if ts.input_was_numpy else y
     if ts.backend == "hip":
         from .. import hip_backend as hb
 
@@ -162,6 +265,9 @@ def gather_tiles(ts: TileStats, tile_ids: np.ndarray) -> np.ndarray:
     the tiles are gathered on the device with one indexed read and come over in one copy."""
     ids = np.asarray(tile_ids, dtype=np.int64).reshape(-1)
     h, w = ts.x2d.shape
+    if ts.transposed and ids.size:   # Xᵀ tiles through the transposed knife-edge gather, put back in the order of tile_ids
+        xt, _, got = _knife_tiles_transposed(ts, ids, None)
+        return xt[np.argsort(got)][np.argsort(np.argsort(ids))]
     if ts.backend == "hip" and ids.size:
         torch = __import__("torch")
         dev = ts.x2d.device
@@ -179,6 +285,25 @@ def gather_tiles(ts: TileStats, tile_ids: np.ndarray) -> np.ndarray:
         blk = ts.x2d[r0:min(r0 + TILE, h), c0:min(c0 + TILE, w)]
         out[k, : blk.shape[0], : blk.shape[1]] = blk
     return out
+
+
+def _knife_tiles_transposed(ts: TileStats, ids: np.ndarray, fmt):
+    """(Xᵀ tiles, their reconstruction in fmt — None: the tiles alone —, their ids in the order the device listed them) of a TileStats
+    over X read in place."""
+    from .. import hip_backend as hb
+
+    torch = __import__("torch")
+    dev = ts.x2d.device
+    with torch.cuda.device(dev):
+        flags = torch.zeros((ts.tiles,), dtype=torch.int8, device=dev)
+        flags[torch.from_numpy(ids).to(dev)] = 1
+        k = int(ids.size)
+        lst = torch.empty((k + 1,), dtype=torch.int64, device=dev)
+        fmts = [fmt] if fmt else []
+        out = torch.empty((1 + len(fmts), k, TILE, TILE), dtype=torch.float32, device=dev)
+        hb.knife_tiles_device(ts.x2d[None], flags, fmts, k, lst, out, transposed=True)
+        host = out.cpu().numpy()
+        return host[0], (host[1] if fmts else None), lst[:k].cpu().numpy()
 
 
 _PINNED = {}   # thread id -> flat pinned float32 staging buffer of literal_inputs(pinned=True); grows, never shrinks
@@ -201,6 +326,8 @@ def literal_inputs(ts: TileStats, tile_ids: np.ndarray, fmt: str, quantizer, pin
     of the tiles).  On the hip backend both come from one device call (mtq_knife_tiles_device: the tiles fetched and quantised where the
     tensor lives, 8 KB per tile home, in the order the device listed them) instead of tiles down, tiles up, K2, y down."""
     ids = np.asarray(tile_ids, dtype=np.int64).reshape(-1)
+    if ts.transposed and ids.size and fmt in MIXED_TILE_FORMATS:
+        return _knife_tiles_transposed(ts, ids, fmt)
     if ts.backend == "hip" and ids.size and fmt in MIXED_TILE_FORMATS and ts.x2d.stride(-1) == 1:
         from .. import hip_backend as hb
 

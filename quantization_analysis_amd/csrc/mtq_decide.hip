@@ -213,15 +213,17 @@ extern "C" int mtq_column_sums_device(const double *stats, int64_t tiles, uint32
 }
 
 // One batch of the streamed threshold driver as one call (include/mtq.h): the launches ThresholdPipeline.enqueue issued one by one.
-extern "C" int mtq_threshold_enqueue(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
-                                     uint32_t k1_mask, uint32_t dec_mask, const int *formats, int n_formats, int metric, double threshold, double band,
-                                     double *stats, int8_t *both_dev, int8_t *both_host, int64_t cap, int64_t *list_dev, float *knife_dev,
-                                     int64_t *list_host, double *scratch, double *sums_host, void *stream, void *side_stream)
+// transposed: the search of Xᵀ for every matrix — K1T records and the transposed knife-edge gather (the grid has as many tiles).
+static int threshold_enqueue(bool transposed, const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                             uint32_t k1_mask, uint32_t dec_mask, const int *formats, int n_formats, int metric, double threshold, double band,
+                             double *stats, int8_t *both_dev, int8_t *both_host, int64_t cap, int64_t *list_dev, float *knife_dev,
+                             int64_t *list_host, double *scratch, double *sums_host, void *stream, void *side_stream)
 {
     if (!x || !formats || !stats || !both_dev || !both_host || !list_dev || !list_host) return fail(MTQ_ERR_INVALID, "null argument");
     if (count <= 0 || rows <= 0 || cols <= 0 || cap < 0) return fail(MTQ_ERR_INVALID, "count, rows, cols must be positive and cap non-negative");
     const int64_t tiles = ((rows + 31) / 32) * ((cols + 31) / 32), T = count * tiles;
-    if (int rc = mtq_tile_stats_batched(x, in_dtype, count, stride_elems, rows, cols, ld, k1_mask, stats, stream)) return rc;
+    if (int rc = transposed ? mtq_tile_stats_transposed(x, in_dtype, count, stride_elems, rows, cols, ld, k1_mask, stats, stream)
+                            : mtq_tile_stats_batched(x, in_dtype, count, stride_elems, rows, cols, ld, k1_mask, stats, stream)) return rc;
     if (int rc = mtq_threshold_assign_device(stats, T, dec_mask, formats, n_formats, metric, threshold, band, both_dev,
                                              reinterpret_cast<uint8_t *>(both_dev + T), stream)) return rc;
     if (int rc = mtq_device_copy_2d(both_host, (size_t)(2 * T), both_dev, (size_t)(2 * T), (size_t)(2 * T), 1, stream)) return rc;
@@ -233,11 +235,29 @@ extern "C" int mtq_threshold_enqueue(const void *x, int in_dtype, int64_t count,
         (void)hipEventDestroy(ev);
         if (!ok) return fail(MTQ_ERR_HIP, "could not order the side stream behind the masks");
     }
-    if (int rc = mtq_knife_tiles_device(x, in_dtype, count, stride_elems, rows, cols, ld, both_dev + T, formats, n_formats, cap, list_dev,
-                                        cap ? knife_dev : nullptr, side)) return rc;
+    if (int rc = (transposed ? mtq_knife_tiles_transposed : mtq_knife_tiles_device)(x, in_dtype, count, stride_elems, rows, cols, ld, both_dev + T, formats,
+                                                                                  n_formats, cap, list_dev, cap ? knife_dev : nullptr, side)) return rc;
     if (int rc = mtq_device_copy_2d(list_host, (size_t)(cap + 1) * 8, list_dev, (size_t)(cap + 1) * 8, (size_t)(cap + 1) * 8, 1, side)) return rc;
     // the column sums under the maps as K4 left them: final unless the list names a knife-edge tile (the caller then patches and sums again)
     return scratch && sums_host ? mtq_threshold_columns(stats, count, tiles, dec_mask, both_dev, scratch, sums_host, stream) : MTQ_OK;
+}
+
+extern "C" int mtq_threshold_enqueue(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                                     uint32_t k1_mask, uint32_t dec_mask, const int *formats, int n_formats, int metric, double threshold, double band,
+                                     double *stats, int8_t *both_dev, int8_t *both_host, int64_t cap, int64_t *list_dev, float *knife_dev,
+                                     int64_t *list_host, double *scratch, double *sums_host, void *stream, void *side_stream)
+{
+    return threshold_enqueue(false, x, in_dtype, count, stride_elems, rows, cols, ld, k1_mask, dec_mask, formats, n_formats, metric, threshold, band, stats,
+                             both_dev, both_host, cap, list_dev, knife_dev, list_host, scratch, sums_host, stream, side_stream);
+}
+
+extern "C" int mtq_threshold_enqueue_transposed(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                                                uint32_t k1_mask, uint32_t dec_mask, const int *formats, int n_formats, int metric, double threshold,
+                                                double band, double *stats, int8_t *both_dev, int8_t *both_host, int64_t cap, int64_t *list_dev,
+                                                float *knife_dev, int64_t *list_host, double *scratch, double *sums_host, void *stream, void *side_stream)
+{
+    return threshold_enqueue(true, x, in_dtype, count, stride_elems, rows, cols, ld, k1_mask, dec_mask, formats, n_formats, metric, threshold, band, stats,
+                             both_dev, both_host, cap, list_dev, knife_dev, list_host, scratch, sums_host, stream, side_stream);
 }
 
 extern "C" int mtq_threshold_columns(const double *stats, int64_t count, int64_t tiles, uint32_t dec_mask, const int8_t *maps_dev, double *scratch,

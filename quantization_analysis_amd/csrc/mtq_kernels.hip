@@ -489,15 +489,52 @@ __global__ __launch_bounds__(64) void knife_tiles(const T *__restrict__ x, int64
         for (int i = 0; i < 4; ++i) q[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
     }
 }
+
+// The knife-edge tiles of Xᵀ read from the row-major X (mtq_knife_tiles_transposed): the tile's 32 rows × 32 columns of X are read as
+// knife_tiles reads a tile (two lanes per row, 16 consecutive elements each), staged in LDS and read back along the columns, so that
+// lane 2i + h holds row i, half h of the Xᵀ tile — the group the row kernel holds — and every later step is knife_tiles' own.
+template <typename T>
+__global__ __launch_bounds__(64) void knife_tiles_transposed(const T *__restrict__ x, int64_t stride, int64_t rows, int64_t cols, int64_t ld, int tiles_w,
+                                                             int64_t tiles, const long long *__restrict__ list, int64_t cap, int4 fmts, int n_fmts,
+                                                             float *__restrict__ out, int vec_ok)
+{
+    __shared__ uint32_t s[kTile][kTile + 1];
+    const int64_t listed = list[cap] < cap ? list[cap] : cap;
+    const int64_t b = blockIdx.x;
+    if (b >= listed) return;                                              // block-uniform: before the barrier
+    const int64_t id = list[b];
+    const int lane = threadIdx.x;
+    const int r = lane >> 1, c0 = (lane & 1) * kGroup;
+    const int64_t j = id / tiles, t = id - j * tiles;
+    const int64_t tr = t / tiles_w, tc = t - tr * tiles_w;                // Xᵀ tile (tr, tc) = X rows 32·tc.., columns 32·tr..
+    uint32_t u[kGroup];
+    Loader<T>::group(x + j * stride, tc * kTile + r, tr * kTile + c0, rows, cols, ld, vec_ok != 0, u);
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) s[r][c0 + i] = u[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) u[i] = s[c0 + i][r];                // Xᵀ row r, columns c0 .. c0 + 15
+    const uint32_t shared = group_shared_exp(u);
+    const int f4[4] = {fmts.x, fmts.y, fmts.z, fmts.w};
+    for (int p = 0; p <= n_fmts; ++p) {
+        uint4 *q = reinterpret_cast<uint4 *>(out + ((int64_t)p * cap + b) * (kTile * kTile) + r * kTile + c0);
+        uint32_t o[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) o[i] = p == 0 ? u[i] : quant_elem_bits_mixed(f4[p - 1], u[i], shared);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+    }
+}
 } // namespace
 
 static int knife_tiles_launch(const void *x, int in_dtype, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld, int64_t tw, int64_t tiles, int64_t total,
                               int vec_ok, const RaggedTable &tb, const int8_t *near, const int *formats, int n_formats, int64_t cap, int64_t *list,
-                              float *tiles_out, void *stream)
+                              float *tiles_out, void *stream, bool transposed = false)
 {
-    if (!near || !list || !formats) return fail(MTQ_ERR_INVALID, "null argument");
+    if (!near || !list || (!formats && n_formats > 0)) return fail(MTQ_ERR_INVALID, "null argument");
     if (cap < 0 || (cap > 0 && !tiles_out)) return fail(MTQ_ERR_INVALID, "cap must be non-negative and tiles_out set when cap > 0");
-    if (n_formats < 1 || n_formats > 4) return fail(MTQ_ERR_INVALID, "n_formats must be 1..4");
+    // the transposed gather also serves tiles without reconstructions (tile_search.gather_tiles: slot p = 0 only)
+    if (n_formats < (transposed ? 0 : 1) || n_formats > 4) return fail(MTQ_ERR_INVALID, transposed ? "n_formats must be 0..4" : "n_formats must be 1..4");
     for (int i = 0; i < n_formats; ++i)
         if (formats[i] < 0 || formats[i] > 3) return fail(MTQ_ERR_INVALID, "format codes are 0..3 (bf16, bfp8, bfp4, bfp2)");
     if (!aligned16(tiles_out)) return fail(MTQ_ERR_INVALID, "tiles_out must be 16-byte aligned");
@@ -508,7 +545,16 @@ static int knife_tiles_launch(const void *x, int in_dtype, int64_t stride_elems,
     hipLaunchKernelGGL(knife_list, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, near, total, cap, reinterpret_cast<long long *>(list));
     if (int rc = check_launch("mtq_knife_tiles_device (list)")) return rc;
     if (cap == 0) return MTQ_OK;
-    int4 f = make_int4(formats[0], n_formats > 1 ? formats[1] : 0, n_formats > 2 ? formats[2] : 0, n_formats > 3 ? formats[3] : 0);
+    int4 f = make_int4(n_formats > 0 ? formats[0] : 0, n_formats > 1 ? formats[1] : 0, n_formats > 2 ? formats[2] : 0, n_formats > 3 ? formats[3] : 0);
+    if (transposed) {   // tw: the tile columns of Xᵀ = ceil(rows / 32)
+        if (in_dtype == MTQ_DTYPE_BF16)
+            hipLaunchKernelGGL(knife_tiles_transposed<uint16_t>, dim3((unsigned)cap), dim3(64), 0, s, static_cast<const uint16_t *>(x), stride_elems, rows, cols, ld,
+                               (int)tw, tiles, reinterpret_cast<const long long *>(list), cap, f, n_formats, tiles_out, vec_ok);
+        else
+            hipLaunchKernelGGL(knife_tiles_transposed<float>, dim3((unsigned)cap), dim3(64), 0, s, static_cast<const float *>(x), stride_elems, rows, cols, ld,
+                               (int)tw, tiles, reinterpret_cast<const long long *>(list), cap, f, n_formats, tiles_out, vec_ok);
+        return check_launch("mtq_knife_tiles_transposed");
+    }
     if (in_dtype == MTQ_DTYPE_BF16)
         hipLaunchKernelGGL(knife_tiles<uint16_t>, dim3((unsigned)cap), dim3(64), 0, s, static_cast<const uint16_t *>(x), stride_elems, rows, cols, ld, (int)tw, tiles,
                            reinterpret_cast<const long long *>(list), cap, f, n_formats, tiles_out, vec_ok, tb);
@@ -529,6 +575,18 @@ extern "C" int mtq_knife_tiles_device(const void *x, int in_dtype, int64_t count
     const int64_t esz = in_dtype == MTQ_DTYPE_BF16 ? 2 : 4;
     const int vec_ok = aligned16(x) && (ld * esz) % 16 == 0 && (stride_elems * esz) % 16 == 0;
     return knife_tiles_launch(x, in_dtype, stride_elems, rows, cols, ld, tw, tiles, total, vec_ok, kUniform, near, formats, n_formats, cap, list, tiles_out, stream);
+}
+
+extern "C" int mtq_knife_tiles_transposed(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                                          const int8_t *near, const int *formats, int n_formats, int64_t cap, int64_t *list, float *tiles_out, void *stream)
+{
+    if (int rc = check_matrix(x, in_dtype, rows, cols, ld)) return rc;
+    if (count <= 0) return fail(MTQ_ERR_INVALID, "count must be positive");
+    const int64_t th = (cols + kTile - 1) / kTile, tw = (rows + kTile - 1) / kTile, tiles = th * tw, total = count * tiles;   // Xᵀ's grid
+    const int64_t esz = in_dtype == MTQ_DTYPE_BF16 ? 2 : 4;
+    const int vec_ok = aligned16(x) && (ld * esz) % 16 == 0 && (stride_elems * esz) % 16 == 0;
+    return knife_tiles_launch(x, in_dtype, stride_elems, rows, cols, ld, tw, tiles, total, vec_ok, kUniform, near, formats, n_formats, cap, list, tiles_out, stream,
+                              true);
 }
 
 // The table of a ragged batch from the caller's matrices (include/mtq.h, MtqMatrix): every matrix checked as mtq_tile_stats checks one.

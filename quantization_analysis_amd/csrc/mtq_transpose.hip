@@ -12,6 +12,8 @@
 // tile, lane ℓ holding the group (Xᵀ row ℓ>>1, half ℓ&1) — the mapping and order of tile_terms_literal.
 //
 // K2T: one thread per (column, group of 16 rows); a wave's loads and stores are row segments of 64 consecutive columns.
+//
+// K3T: K2T's layout with a format per group read from a map over Xᵀ's grid (the mixed-tile searches with params["layout"] = "transpose").
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -243,6 +245,84 @@ __global__ __launch_bounds__(256) void quantize_transposed(const T *__restrict__
     }
 }
 
+// K3T: y[r][c] = the element (c, r) of K3 of Xᵀ with `map` (Xᵀ's grid, row-major): the group is rows 16g .. 16g+15 of column c and
+// lies in Xᵀ tile (c / 32, r0 / 32).  The thread layout of K2T; blockIdx.z walks the matrices of a batch.
+template <typename T>
+__global__ __launch_bounds__(256) void apply_assignment_transposed(const T *__restrict__ x, int64_t count, int64_t stride, int64_t rows, int64_t cols,
+                                                                  int64_t ld, int64_t row_groups, int64_t tiles_w, int64_t tiles,
+                                                                  const int8_t *__restrict__ map, float *__restrict__ y, int64_t ldy)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    for (int64_t b = blockIdx.z; b < count; b += gridDim.z) {
+        const T *xb = x + b * stride;
+        float *yb = y + b * rows * ldy;
+        const int8_t *mb = map + b * tiles + (c / kTile) * tiles_w;
+        for (int64_t g = blockIdx.y; g < row_groups; g += gridDim.y) {
+            const int64_t r0 = g * kGroup;
+            uint32_t u[kGroup];
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) {
+                uint32_t v = 0u;
+                if (r0 + i < rows) {
+                    if constexpr (sizeof(T) == 2) v = (uint32_t)xb[(r0 + i) * ld + c] << 16;
+                    else v = __float_as_uint(xb[(r0 + i) * ld + c]);
+                }
+                u[i] = v;
+            }
+            const uint32_t shared = group_shared_exp(u);
+            const int f = mb[r0 / kTile];
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i)
+                if (r0 + i < rows) yb[(r0 + i) * ldy + c] = __uint_as_float(quant_elem_bits(f, u[i], shared));
+        }
+    }
+}
+
+// K3T, vector form (cols % 4 == 0, rows of X and y aligned for 4-element words): a thread owns four adjacent columns, so a wave's load
+// is 512 B (bf16) / 1 KiB (float32) of one row and its store 1 KiB.  The four columns lie in one Xᵀ tile row and share a map entry.
+template <typename T>
+__global__ __launch_bounds__(256) void apply_assignment_transposed_quad(const T *__restrict__ x, int64_t count, int64_t stride, int64_t rows,
+                                                                       int64_t cols, int64_t ld, int64_t row_groups, int64_t tiles_w, int64_t tiles,
+                                                                       const int8_t *__restrict__ map, float *__restrict__ y, int64_t ldy)
+{
+    const int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (c >= cols) return;                                                   // cols % 4 == 0: c .. c + 3 are all inside
+    for (int64_t b = blockIdx.z; b < count; b += gridDim.z) {
+        const T *xb = x + b * stride;
+        float *yb = y + b * rows * ldy;
+        const int8_t *mb = map + b * tiles + (c / kTile) * tiles_w;
+        for (int64_t g = blockIdx.y; g < row_groups; g += gridDim.y) {
+            const int64_t r0 = g * kGroup;
+            uint32_t u[4][kGroup];
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) {
+                uint32_t v[4] = {0u, 0u, 0u, 0u};
+                if (r0 + i < rows) {
+                    if constexpr (sizeof(T) == 2) {
+                        const uint2 w = *reinterpret_cast<const uint2 *>(xb + (r0 + i) * ld + c);
+                        v[0] = w.x << 16; v[1] = w.x & 0xFFFF0000u; v[2] = w.y << 16; v[3] = w.y & 0xFFFF0000u;
+                    } else {
+                        const uint4 w = *reinterpret_cast<const uint4 *>(xb + (r0 + i) * ld + c);
+                        v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) u[k][i] = v[k];
+            }
+            uint32_t shared[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) shared[k] = group_shared_exp(u[k]);
+            const int f = mb[r0 / kTile];
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i)
+                if (r0 + i < rows)
+                    *reinterpret_cast<uint4 *>(yb + (r0 + i) * ldy + c) = make_uint4(quant_elem_bits(f, u[0][i], shared[0]), quant_elem_bits(f, u[1][i], shared[1]),
+                                                                                     quant_elem_bits(f, u[2][i], shared[2]), quant_elem_bits(f, u[3][i], shared[3]));
+        }
+    }
+}
+
 template <typename T>
 static void launch_transposed(uint32_t fm, dim3 grid, hipStream_t st, const T *x, int64_t stride, int64_t rows, int64_t cols, int64_t ld,
                               uint32_t tiles_h, uint32_t tiles_w, uint32_t units_c, int64_t units, double *stats, int pair_ok, unsigned *work,
@@ -326,4 +406,41 @@ extern "C" int mtq_quantize_transposed(const void *x, int in_dtype, int64_t rows
     else
         hipLaunchKernelGGL(quantize_transposed<float>, grid, dim3(256), 0, st, static_cast<const float *>(x), rows, cols, ld, row_groups, fmt, y, ldy);
     return check_launch("mtq_quantize_transposed");
+}
+
+extern "C" int mtq_apply_assignment_transposed(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                                               const int8_t *map, float *y, int64_t ldy, void *stream)
+{
+    if (!x || !y || !map) return fail(MTQ_ERR_INVALID, "null argument");
+    if (in_dtype != MTQ_DTYPE_BF16 && in_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "in_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    if (count < 1) return fail(MTQ_ERR_INVALID, "count must be positive");
+    if (rows <= 0 || cols <= 0) return fail(MTQ_ERR_INVALID, "rows and cols must be positive (empty tensors are handled by the caller)");
+    if (ld < cols) return fail(MTQ_ERR_INVALID, "ld < cols");
+    if (ldy < cols) return fail(MTQ_ERR_INVALID, "ldy < cols");
+    if (count > 1 && stride_elems < 0) return fail(MTQ_ERR_INVALID, "stride_elems must not be negative");
+    if (rows > (int64_t)1 << 30 || cols > (int64_t)1 << 30 || count * rows * ldy > ((int64_t)1 << 40)) return fail(MTQ_ERR_INVALID, "matrix too large");
+    if (int rc = require_device()) return rc;
+    const int64_t row_groups = (rows + kGroup - 1) / kGroup, tw = (rows + kTile - 1) / kTile, tiles = tw * ((cols + kTile - 1) / kTile);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t esz = in_dtype == MTQ_DTYPE_BF16 ? 2 : 4;
+    const bool quad = cols % 4 == 0 && reinterpret_cast<uintptr_t>(x) % (uintptr_t)(4 * esz) == 0 && ld % 4 == 0 && (count == 1 || stride_elems % 4 == 0) &&
+                      reinterpret_cast<uintptr_t>(y) % 16 == 0 && ldy % 4 == 0;
+    if (quad) {
+        const dim3 qgrid((unsigned)((cols / 4 + 255) / 256), (unsigned)std::min<int64_t>(row_groups, 65535), (unsigned)std::min<int64_t>(count, 65535));
+        if (in_dtype == MTQ_DTYPE_BF16)
+            hipLaunchKernelGGL(apply_assignment_transposed_quad<uint16_t>, qgrid, dim3(256), 0, st, static_cast<const uint16_t *>(x), count, stride_elems, rows,
+                               cols, ld, row_groups, tw, tiles, map, y, ldy);
+        else
+            hipLaunchKernelGGL(apply_assignment_transposed_quad<float>, qgrid, dim3(256), 0, st, static_cast<const float *>(x), count, stride_elems, rows, cols,
+                               ld, row_groups, tw, tiles, map, y, ldy);
+        return check_launch("mtq_apply_assignment_transposed");
+    }
+    const dim3 grid((unsigned)((cols + 255) / 256), (unsigned)std::min<int64_t>(row_groups, 65535), (unsigned)std::min<int64_t>(count, 65535));
+    if (in_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(apply_assignment_transposed<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(x), count, stride_elems, rows, cols,
+                           ld, row_groups, tw, tiles, map, y, ldy);
+    else
+        hipLaunchKernelGGL(apply_assignment_transposed<float>, grid, dim3(256), 0, st, static_cast<const float *>(x), count, stride_elems, rows, cols, ld,
+                           row_groups, tw, tiles, map, y, ldy);
+    return check_launch("mtq_apply_assignment_transposed");
 }

@@ -34,10 +34,12 @@ EXPORTS = [
     "mtq_selftest_slot_ring", "mtq_device_copy_2d", "mtq_knife_tiles_device", "mtq_greedy_scan_scratch_bytes", "mtq_greedy_scan_device", "mtq_greedy_scan_device_ex", "mtq_scan_carry_bytes",
     "mtq_scan_orders_bytes", "mtq_scan_orders_device", "mtq_debug_scan_ticks", "mtq_threshold_enqueue", "mtq_threshold_columns",
     "mtq_tile_stats_ragged", "mtq_knife_tiles_ragged", "mtq_column_sums_device_ragged", "mtq_threshold_enqueue_ragged", "mtq_threshold_columns_ragged",
-    "mtq_tile_stats_transposed", "mtq_quantize_transposed",
+    "mtq_tile_stats_transposed", "mtq_quantize_transposed", "mtq_apply_assignment_transposed", "mtq_knife_tiles_transposed",
+    "mtq_threshold_enqueue_transposed",
 ]
 # found by name, not by MTQ_VERSION: an older build of the same version (an A/B library at MTQ_LIB) lacks them and still loads
-OPTIONAL_EXPORTS = ("mtq_tile_stats_transposed", "mtq_quantize_transposed")
+OPTIONAL_EXPORTS = ("mtq_tile_stats_transposed", "mtq_quantize_transposed", "mtq_apply_assignment_transposed", "mtq_knife_tiles_transposed",
+                    "mtq_threshold_enqueue_transposed")
 
 
 class MtqError(RuntimeError):
@@ -137,6 +139,12 @@ def lib() -> ctypes.CDLL:
         L.mtq_tile_stats_transposed.argtypes = [vp, ci, i64, i64, i64, i64, i64, u32, vp, vp]
     if hasattr(L, "mtq_quantize_transposed"):
         L.mtq_quantize_transposed.argtypes = [vp, ci, i64, i64, i64, ci, vp, i64, vp]
+    if hasattr(L, "mtq_apply_assignment_transposed"):
+        L.mtq_apply_assignment_transposed.argtypes = [vp, ci, i64, i64, i64, i64, i64, vp, vp, i64, vp]
+    if hasattr(L, "mtq_knife_tiles_transposed"):
+        L.mtq_knife_tiles_transposed.argtypes = [vp, ci, i64, i64, i64, i64, i64, vp, vp, ci, i64, vp, vp, vp]
+    if hasattr(L, "mtq_threshold_enqueue_transposed"):
+        L.mtq_threshold_enqueue_transposed.argtypes = L.mtq_threshold_enqueue.argtypes
     if L.mtq_version() < 141:
         raise MtqError("libmtq_hip.so is older than this package")
     _lib = L
@@ -472,6 +480,32 @@ def quantize_transposed(x2d, fmt: str, out=None):
     return out
 
 
+def apply_assignment_transposed(x, assignment, out=None):
+    """K3T (mtq_apply_assignment_transposed) on the current stream: (K3 of Xᵀ with `assignment`)ᵀ for a (rows, cols) or (count, rows, cols)
+    device tensor X with contiguous rows, read in place → float32, X's shape.  assignment: int8 numpy array or device tensor with
+    ceil(cols / 32) × ceil(rows / 32) entries per matrix (Xᵀ's grid, K1T's numbering)."""
+    _check_transposed_input(x, (2, 3))
+    torch = _torch()
+    require_gpu()
+    fn = _transposed_entry("mtq_apply_assignment_transposed")
+    x3 = x if x.dim() == 3 else x[None]
+    count, rows, cols = x3.shape
+    ld = x3.stride(1) if rows > 1 else max(x3.stride(1), cols)
+    stride = x3.stride(0) if count > 1 else 0
+    th_t, tw_t = tiles_hw(cols, rows)
+    if isinstance(assignment, np.ndarray):
+        assignment = torch.from_numpy(np.ascontiguousarray(assignment, dtype=np.int8)).to(x.device)
+    a = assignment.to(device=x.device, dtype=torch.int8).contiguous()
+    if a.numel() != count * th_t * tw_t:
+        raise MtqError(f"assignment has {a.numel()} entries, the transposed grid has {count}x{th_t}x{tw_t} tiles")
+    if out is None:
+        out = torch.empty((count, rows, cols), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (count, rows, cols) or not out.is_contiguous() or out.device != x.device:
+        raise MtqError("out must be a contiguous float32 device tensor of X's shape")
+    check(fn(x3.data_ptr(), _dtype_code(x3), count, stride, rows, cols, ld, a.data_ptr(), out.data_ptr(), cols, _stream_ptr()))
+    return out if x.dim() == 3 else out[0]
+
+
 def apply_assignment(x2d, assignment, out=None):
     """K3: assignment is an int8 (tiles_h, tiles_w) numpy array or device tensor."""
     torch = _torch()
@@ -766,25 +800,27 @@ def threshold_assign_device_raw(stats_dev, mask: int, formats, metric: str, thre
     return both
 
 
-def knife_tiles_device(x3d, near, formats, cap: int, list_out, tiles_out) -> None:
+def knife_tiles_device(x3d, near, formats, cap: int, list_out, tiles_out, transposed: bool = False) -> None:
     """The threshold rule's knife-edge tiles, prepared on the device (mtq_knife_tiles_device): `near` = the int8 masks of
     threshold_assign_device_raw for the (count, rows, cols) batch x3d; list_out int64 [cap + 1] ← flat tile ids (any order) and,
     last, how many were flagged; tiles_out float32 [1 + len(formats), cap, 32, 32] ← their values and every format's reconstruction.
-    Asynchronous on the current stream."""
+    Asynchronous on the current stream.  transposed=True: the same for Xᵀ of every matrix, read in place (mtq_knife_tiles_transposed):
+    `near` and the ids follow Xᵀ's grid (K1T's numbering) and the tiles are Xᵀ tiles in Xᵀ's row-major order."""
     torch = _torch()
     require_gpu()
     count, rows, cols = x3d.shape
     if x3d.stride(2) != 1 or not x3d.is_cuda:
         raise ValueError("knife_tiles_device needs a device tensor with contiguous rows")
-    th, tw = tiles_hw(rows, cols)
+    th, tw = tiles_hw(cols, rows) if transposed else tiles_hw(rows, cols)
     if near.dtype != torch.int8 or near.numel() != count * th * tw or not near.is_contiguous():
         raise ValueError("near must be a contiguous int8 vector of one entry per tile")
     if list_out.dtype != torch.int64 or list_out.numel() != cap + 1 or not list_out.is_contiguous():
         raise ValueError("list_out must be a contiguous int64 vector of cap + 1 entries")
     if cap and (tiles_out.dtype != torch.float32 or tiles_out.numel() != (1 + len(formats)) * cap * 1024 or not tiles_out.is_contiguous()):
         raise ValueError("tiles_out must be a contiguous float32 tensor of (1 + formats) x cap x 32 x 32")
-    fm = (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats])
-    check(lib().mtq_knife_tiles_device(x3d.data_ptr(), _dtype_code(x3d), count, x3d.stride(0) if count > 1 else rows * x3d.stride(1), rows, cols, x3d.stride(1),
+    fm = (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats]) if formats else None
+    fn = _transposed_entry("mtq_knife_tiles_transposed") if transposed else lib().mtq_knife_tiles_device
+    check(fn(x3d.data_ptr(), _dtype_code(x3d), count, x3d.stride(0) if count > 1 else rows * x3d.stride(1), rows, cols, x3d.stride(1),
                                        near.data_ptr(), fm, len(formats), int(cap), list_out.data_ptr(), tiles_out.data_ptr() if cap else None, _stream_ptr()))
 
 

@@ -23,15 +23,19 @@ class GreedyPipeline:
                                                          # beside K1 launches of ~2 ms, so three slots made the K1 stream wait for a slot (2.65 against 2.47 ms per step at four)
 
     def __init__(self, tile_formats=None, metric: str = "pcc", threshold: float = 0.999, seed: int = 123,
-                 chunk: int = 8, workers: int = 8, pure_formats=(), scan: str = "auto", scan_streams: int | None = None):
+                 chunk: int = 8, workers: int = 8, pure_formats=(), scan: str = "auto", scan_streams: int | None = None, layout: str = "rows"):
         """scan: "device" — the sequential scan runs on the GPU where K1 wrote the records (csrc/mtq_scan.hip: only maps, counts and
         seven sums per tensor cross PCIe, the host does not scan); "host" — records over PCIe, scans on host threads; "auto" —
         "device" where mtq_greedy_scan_device serves the search (distinct formats), else "host".  MTQ_DEVICE_SCAN=0
-        forces "host"."""
+        forces "host".  layout "transpose": the search of np.transpose(x) for every matrix x of a batch — K1T's records
+        (mtq_tile_stats_transposed, X read in place) instead of K1's, maps over Xᵀ's grid; the lazy route stays row-only."""
         import torch
 
         hb.require_gpu()
         self.torch = torch
+        if layout not in ("rows", "transpose"):
+            raise ValueError(f"Unsupported layout: {layout!r}")
+        self.transposed = layout == "transpose"
         self.tile_formats = list(tile_formats or MIXED_TILE_FORMATS)
         self.mask = hb.fmt_mask(self.tile_formats)
         # whole-tensor columns of these formats on their own (wq's `none` rows) come out of the same records: no second K1 pass
@@ -76,7 +80,7 @@ class GreedyPipeline:
         # tiles that accepted every earlier format — 15 % at pcc >= 0.999), and the last pass follows.  Same maps, same columns.
         self.shared_orders = settings().shared_orders
         self.lazy = (settings().lazy and self.metric == "pcc" and len(self.tile_formats) >= 3 and self.tile_formats[0] == "bf16"
-                     and len(set(self.tile_formats)) == len(self.tile_formats) and not self.pure_formats)
+                     and len(set(self.tile_formats)) == len(self.tile_formats) and not self.pure_formats and not self.transposed)
         self.listed_tiles = 0                    # tiles the lazy route evaluated late (diagnostics)
         # The lazy route pays when few tiles reach the last pass: K1 <3,1> costs 469 instructions per tile and the listed kernel 432 per
         # listed tile, against 652 for the whole record — break-even at 42 % listed, less the phases' launches.  A batch that listed more
@@ -106,13 +110,23 @@ class GreedyPipeline:
         slim = self.metric == "pcc" and settings().slim_records
         return k1_mask, host_mask | (hb.MASK_SLIM if slim else 0), slim
 
+    def _grid(self, rows: int, cols: int) -> tuple[int, int]:
+        """Tile grid of a matrix's search: X's, or Xᵀ's in the transposed layout."""
+        return hb.tiles_hw(cols, rows) if self.transposed else hb.tiles_hw(rows, cols)
+
+    def _k1(self, x3d, mask: int, out=None):
+        """The whole-record stats launch of the batch's layout: K1, or K1T reading X in place."""
+        if self.transposed:
+            return hb.tile_stats_transposed(x3d, mask, out=out)
+        return hb.tile_stats_batched(x3d, mask, out=out)
+
     def lazy_plan(self, x3d):
         """→ None, or (layout mask, formats K1 evaluates in full, format K1 evaluates without Σ|x−y| / max|x−y|, format left to the listed
         kernel) when a batch shaped like x3d takes the lazy route (see __init__): bf16 storage in whole 32x128 units — what the exact-integer
         kernel serves — and the search on the device."""
         torch = self.torch
         count, rows, cols = x3d.shape
-        th, tw = hb.tiles_hw(rows, cols)
+        th, tw = self._grid(rows, cols)
         k1_mask = self._layout(x3d)[0]
         if not (self.lazy and self._use_device_scan(th * tw) and x3d.dtype == torch.bfloat16 and (k1_mask & 1) == 0 and rows % 32 == 0 and cols % 128 == 0):
             return None
@@ -126,7 +140,7 @@ class GreedyPipeline:
         """The K1 launch a batch's route issues (the whole record, or the lazy route's partial one) on the current stream."""
         plan = self.lazy_plan(x3d)
         if plan is None:
-            return hb.tile_stats_batched(x3d, self._layout(x3d)[0], out=out)
+            return self._k1(x3d, self._layout(x3d)[0], out=out)
         return hb.tile_stats_partial(x3d, plan[0], plan[1], plan[2], out=out)
 
     def _buffers(self, slot: int, count: int, tiles: int, rec: int, rec_host: int, device):
@@ -148,7 +162,7 @@ class GreedyPipeline:
         no allocation or thread creation lands in a timed region."""
         torch = self.torch
         count, rows, cols = x3d.shape
-        th, tw = hb.tiles_hw(rows, cols)
+        th, tw = self._grid(rows, cols)
         k1_mask, host_mask, slim = self._layout(x3d)
         if self._use_device_scan(th * tw):
             self._warm_device_scan(x3d.device)
@@ -176,7 +190,7 @@ class GreedyPipeline:
         if len(self._open) >= self.SLOTS:
             raise RuntimeError("finish() an enqueued batch before enqueuing another one: every record slot is in use")
         count, rows, cols = x3d.shape
-        th, tw = hb.tiles_hw(rows, cols)
+        th, tw = self._grid(rows, cols)
         k1_mask, host_mask, slim = self._layout(x3d)
         tiles = th * tw
         slot = self._next_slot
@@ -200,7 +214,7 @@ class GreedyPipeline:
                 e0 = torch.cuda.Event(enable_timing=True)
                 e1 = torch.cuda.Event(enable_timing=True)
                 e0.record(self.stream)
-                hb.tile_stats_batched(x3d[first:first + n], k1_mask, out=dev[first:first + n])
+                self._k1(x3d[first:first + n], k1_mask, out=dev[first:first + n])
                 e1.record(self.stream)
                 self.timing.events.append((e0, e1, n * tiles))
                 ready = e1
@@ -360,7 +374,7 @@ class GreedyPipeline:
                 # fix-up — usually nothing to do — on the search stream: nothing sits between two K1 launches on this stream
                 # (what mtq_tile_stats_partial_begin takes: 16-byte aligned rows of every tensor of the chunk, and no MTQ_FORCE_GENERIC — anything
                 # else goes through the one-call forms below, which pick the generic / direct kernel themselves)
-                two_launch = (x3d.dtype == torch.bfloat16 and (k1_mask & 1) == 0 and rows % 32 == 0 and cols % 128 == 0 and settings().k1_two_launch
+                two_launch = (not self.transposed and x3d.dtype == torch.bfloat16 and (k1_mask & 1) == 0 and rows % 32 == 0 and cols % 128 == 0 and settings().k1_two_launch
                               and x3d.data_ptr() % 16 == 0 and (x3d.stride(0) * 2) % 16 == 0 and (x3d.stride(1) * 2) % 16 == 0
                               and os.environ.get("MTQ_FORCE_GENERIC", "0") != "1")
                 k1_id = None
@@ -370,7 +384,7 @@ class GreedyPipeline:
                 elif lazy:
                     hb.tile_stats_partial(x3d[first:first + n], k1_mask, full_now, prev_bit, out=b["dev"][first:first + n])
                 else:
-                    hb.tile_stats_batched(x3d[first:first + n], k1_mask, out=b["dev"][first:first + n])
+                    self._k1(x3d[first:first + n], k1_mask, out=b["dev"][first:first + n])
                 e1.record(self.stream)
             self.timing.events.append((e0, e1, n * tiles))
             if trace:
@@ -476,8 +490,10 @@ class GreedyPipeline:
                     self.lazy_off.setdefault(th * tw, listed / float(n * th * tw))
             for j in bad:   # handed back by the device scan: the host scan on this tensor's records
                 self.host_fallbacks += 1
-                if enq.get("lazy"):   # the records hold only what the search had asked for so far: the whole record of this one tensor now
-                    full = hb.tile_stats_batched(enq["x"][first + j:first + j + 1], enq["k1_mask"])[0].cpu().numpy()
+                if enq.get("lazy") or self.transposed:
+                    # lazy: the records hold only what the search had asked for so far — the whole record of this one tensor now; transposed:
+                    # the records of this one Xᵀ again through K1T, as the batch's were written (no row-layout K1 over X)
+                    full = self._k1(enq["x"][first + j:first + j + 1], enq["k1_mask"])[0].cpu().numpy()
                 else:
                     full = b["dev"][first + j].cpu().numpy()
                 amap, c, out = hb.greedy_run(full, enq["dec_mask"], self.tile_formats, self.metric, self.threshold, n_el, int(enq["seeds"][first + j]))
@@ -657,10 +673,10 @@ class GreedyPipeline:
             if first and self.device_scan:
                 self._warm_device_scan(x3d.device)
                 with self.torch.cuda.stream(self.stream):
-                    hb.tile_stats_batched(x3d[:1], self._layout(x3d)[0])  # K1's code object, the work-counter ring, the launch stream's queue
+                    self._k1(x3d[:1], self._layout(x3d)[0])  # K1's code object, the work-counter ring, the launch stream's queue
                 first = False
             count, rows, cols = x3d.shape
-            th, tw = hb.tiles_hw(rows, cols)
+            th, tw = self._grid(rows, cols)
             k1_mask, host_mask, slim = self._layout(x3d)
             if not self._use_device_scan(th * tw):
                 host_route.append((i, count, th * tw, hb.record_doubles(k1_mask), hb.record_doubles(host_mask), x3d.device, slim))

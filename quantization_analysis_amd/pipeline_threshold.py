@@ -23,12 +23,18 @@ class ThresholdPipeline:
     compression_algorithms.mixed_tile_threshold does for one tensor) → patched maps back up → column sums on the device.
     There is no host scan: the GPU is the pacing resource."""
 
-    def __init__(self, tile_formats=None, metric: str = "pcc", threshold: float = 0.999, chunk: int = 16, band: float = 2e-6, pure_formats=()):
+    def __init__(self, tile_formats=None, metric: str = "pcc", threshold: float = 0.999, chunk: int = 16, band: float = 2e-6, pure_formats=(),
+                 layout: str = "rows"):
+        """layout "transpose": the search of np.transpose(x) for every matrix x of a batch — K1T records, the transposed knife-edge gather
+        and mtq_threshold_enqueue_transposed, maps over Xᵀ's grid; such batches go one shape group per launch chain (no ragged route)."""
         import torch
 
         from .compression_algorithms.quantizer import Quantizer
 
         hb.require_gpu()
+        if layout not in ("rows", "transpose"):
+            raise ValueError(f"Unsupported layout: {layout!r}")
+        self.transposed = layout == "transpose"
         self.torch = torch
         self.tile_formats = list(tile_formats or MIXED_TILE_FORMATS)
         self.pure_formats = [f for f in pure_formats if f in self.tile_formats]
@@ -78,6 +84,8 @@ class ThresholdPipeline:
         indices (device int64; entries < 0 are padding and read tile 0).  ONE indexed gather, K2 once per format → float32
         (1 + formats, len(idx), 32, 32), plane 0 the tile itself (pads of ragged edge tiles zero, as the reference's padded view has them)."""
         torch = self.torch
+        if self.transposed:   # the tiles of Xᵀ: the same indexed gather on the transposed view
+            xc = xc.transpose(1, 2)
         n, h, w = xc.shape
         dev = xc.device
         k = int(idx.numel())
@@ -175,7 +183,7 @@ class ThresholdPipeline:
         """A batch of few matrices that K1's direct kernel serves anyway (hb.RAGGED_MAX of them fit a launch; the LDS-staged bf16 kernel
         is the faster one where it applies: csrc/mtq_kernels.hip tile_stats_launch)."""
         count, rows, cols = x3d.shape
-        if count > 4 or x3d.stride(2) != 1:
+        if self.transposed or count > 4 or x3d.stride(2) != 1:   # no ragged K1T: a transposed batch takes its own launch chain
             return False
         staged = (x3d.dtype == self.torch.bfloat16 and rows % 32 == 0 and cols % 128 == 0 and x3d.data_ptr() % 16 == 0
                   and (x3d.stride(1) * 2) % 16 == 0 and (x3d.stride(0) * 2) % 16 == 0 and (self.mask & 0xE))
@@ -232,7 +240,7 @@ class ThresholdPipeline:
         torch = self.torch
         count, rows, cols = x3d.shape
         dev = x3d.device
-        th, tw = hb.tiles_hw(rows, cols)
+        th, tw = hb.tiles_hw(cols, rows) if self.transposed else hb.tiles_hw(rows, cols)
         tiles, numel = th * tw, (rows * cols if numel is None else int(numel))
         identity = x3d.dtype == torch.bfloat16 and (self.mask & 1) and (self.mask & 0xE)
         k1_mask = self.mask & 0xE if identity else self.mask
@@ -268,7 +276,10 @@ class ThresholdPipeline:
             part = slice(first * tiles, (first + n) * tiles)
             if len(chunks) > 1:
                 # several chunks: a chunk's maps and masks are not adjacent in the batch's [2, T] arrays — the calls one by one
-                hb.tile_stats_batched(xs, k1_mask, out=recs)
+                if self.transposed:
+                    hb.tile_stats_transposed(xs, k1_mask, out=recs)
+                else:
+                    hb.tile_stats_batched(xs, k1_mask, out=recs)
                 hb.threshold_assign_device_raw(recs.view(n * tiles, -1), dec_mask, self.tile_formats, self.metric, self.threshold, self.band,
                                                out=(both_dev[0, part], both_dev[1, part]))
                 hb.device_copy(both_host[:, part], both_dev[:, part])
@@ -277,13 +288,14 @@ class ThresholdPipeline:
                 with (contextlib.nullcontext() if single else torch.cuda.stream(self._side)):
                     if not single:
                         self._side.wait_event(decided)
-                    hb.knife_tiles_device(xs, both_dev[1, part], self.tile_formats, cap, idx_dev[c], knife_dev[c])
+                    hb.knife_tiles_device(xs, both_dev[1, part], self.tile_formats, cap, idx_dev[c], knife_dev[c], transposed=self.transposed)
                     hb.device_copy(idx_host[c], idx_dev[c])
                     landed = torch.cuda.Event()
                     landed.record()
             else:
                 scratch = self._devbuf(f"colscr{slot}_{c}", P * n * self._scratch_n, torch.float64, dev)
-                hb.check(hb.lib().mtq_threshold_enqueue(
+                enqueue_call = hb._transposed_entry("mtq_threshold_enqueue_transposed") if self.transposed else hb.lib().mtq_threshold_enqueue
+                hb.check(enqueue_call(
                     xs.data_ptr(), hb._dtype_code(xs), n, xs.stride(0) if n > 1 else rows * xs.stride(1), rows, cols, xs.stride(1), k1_mask, dec_mask, fm,
                     len(self.tile_formats), hb.METRIC_CODE[self.metric], self.threshold, self.band, recs.data_ptr(), both_dev.data_ptr(), both_host.data_ptr(),
                     cap, idx_dev[c].data_ptr(), knife_dev[c].data_ptr(), idx_host[c].data_ptr(), scratch.data_ptr(), sums_host.data_ptr(), main_ptr,

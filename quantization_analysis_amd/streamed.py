@@ -1,5 +1,7 @@
 """Streamed evaluation of a rank's shard behind `wq --backend hip` (replaces the per-tensor loop wq:655-706 for the two
-search algorithms the north star names).
+search algorithms the north star names).  Searches over the transposed layout (params["layout"] = "transpose") go through the pipelines'
+transposed mode (K1T records, maps over Xᵀ's grid) for 2-D tensors; their `none` rows are not the search's records, which are records
+of Xᵀ, but come from a row-layout K1 pass (pure formats) over the resident batch.  Tensors of other ranks keep the per-tensor path.
 
 The shard's tensors are grouped by (2-D shape, storage type); a group goes through `pipeline.GreedyPipeline` /
 `pipeline.ThresholdPipeline` in batches: batched K1 launches, records D2H overlapped with the next chunk's K1, the scans of
@@ -43,10 +45,11 @@ def streamable(algo, formats, args) -> bool:
     return algo.name != "mixed-tile-greedy" or int(algo.seed) != 0
 
 
-def group_key(index, name):
-    """(rows, cols, storage) of a tensor's exact 2-D flatten (tile_utils.py:103-107), or None for vectors / scalars."""
+def group_key(index, name, layout: str = "rows"):
+    """(rows, cols, storage) of a tensor's exact 2-D flatten (tile_utils.py:103-107), or None for vectors / scalars — and, for the
+    transposed layout, for every tensor that is not 2-D (np.transpose reverses all axes: a permuted copy, on the per-tensor path)."""
     shape, dtype = index.shape_dtype(name)
-    if len(shape) < 2 or int(np.prod(shape)) == 0:
+    if len(shape) < 2 or int(np.prod(shape)) == 0 or (layout == "transpose" and len(shape) != 2):
         return None
     return (int(np.prod(shape[:-1])), int(shape[-1]), dtype)
 
@@ -59,6 +62,8 @@ class ShardEvaluator:
         self.row_w, self.bytes_per_elem = row_w, bytes_per_elem
         self.tile_formats = algo.tile_formats or [f for f in formats if f in MIXED_TILE_FORMATS]
         self.pure = [f for f in formats if f in MIXED_TILE_FORMATS]
+        self.layout = getattr(algo, "layout", "rows")
+        self.search_pure = self.pure if self.layout == "rows" else []   # pure-format columns out of the search's own records (row layout only)
         self.compute_seconds = 0.0
         self.compute_tiles = 0
         self.load_seconds = 0.0      # tensors to HBM (synthetic presets: drawn on the CPU; safetensors: read + H2D) and their min / mean / max
@@ -70,11 +75,12 @@ class ShardEvaluator:
         a = self.algo
         if a.name == "mixed-tile-greedy":
             if self._pipe is None:
-                self._pipe = GreedyPipeline(self.tile_formats, a.metric, a.threshold, a.seed, chunk=chunk, workers=default_workers(), pure_formats=self.pure)   # three search streams (the pipeline's default): 8, one per batch in flight, measured 27 % slower in round 3
+                self._pipe = GreedyPipeline(self.tile_formats, a.metric, a.threshold, a.seed, chunk=chunk, workers=default_workers(), pure_formats=self.search_pure,
+                                            layout=self.layout)   # three search streams (the pipeline's default): 8, one per batch in flight, measured 27 % slower in round 3
             self._pipe.chunk = chunk
         else:
             if self._pipe is None:
-                self._pipe = ThresholdPipeline(self.tile_formats, a.metric, a.threshold, chunk=chunk, pure_formats=self.pure)
+                self._pipe = ThresholdPipeline(self.tile_formats, a.metric, a.threshold, chunk=chunk, pure_formats=self.search_pure, layout=self.layout)
             self._pipe.chunk = chunk
         return self._pipe
 
@@ -98,6 +104,25 @@ class ShardEvaluator:
             metas.append((float(xf.min()), float(xf.mean()), float(xf.max()), float(ax.mean()), float(ax.max())))
             del xf, ax
         return torch.stack([x.reshape(rows_, cols_) for x in xs]), metas
+
+    def _pure_columns(self, x3d, numel: int) -> list:
+        """The `none` rows of a transposed search: per tensor, fmt → (pcc, mae, atol) of every pure mixed-tile format from a row-layout K1
+        pass over the resident batch (the search's records are Xᵀ's, whose float64 sums run in another order)."""
+        if not self.pure:
+            return [None] * x3d.shape[0]
+        from . import hip_backend as hb
+
+        mask = hb.fmt_mask(self.pure)
+        recs = hb.tile_stats_batched(x3d, mask)
+        out = []
+        for j in range(x3d.shape[0]):
+            cols = {}
+            for f in self.pure:
+                amap = np.full(recs.shape[1], MIXED_TILE_FORMATS.index(f), dtype=np.int8)
+                c = hb.columns_from_stats_device(recs[j], mask, amap, float(numel))
+                cols[f] = (c["pcc"], c["mae"], c["atol"])
+            out.append(cols)
+        return out
 
     def _rows(self, part, results, metas, numel, per):
         out = {}
@@ -181,7 +206,10 @@ class ShardEvaluator:
             if hasattr(pipe, "timing"):
                 pipe.timing.drain()
                 self.k1_ms, self.k1_tiles = pipe.timing.kernel_ms, pipe.timing.tiles
-            for (key, part, tiles), (_x, metas), results in zip(window, loaded, all_results):
+            for (key, part, tiles), (x3d, metas), results in zip(window, loaded, all_results):
+                if self.layout != "rows":
+                    for r, pure in zip(results, self._pure_columns(x3d, key[0] * key[1])):
+                        r.pure = pure
                 per = dt * (tiles * len(part) / n_tiles) / len(part)   # TIME(s): the window's wall time shared by tiles (wq:680-682 times one tensor's run())
                 out.update(self._rows(part, results, metas, key[0] * key[1], per))
             del loaded
