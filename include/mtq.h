@@ -191,6 +191,24 @@ int mtq_apply_assignment(const void *x, int in_dtype, int64_t rows, int64_t cols
                          const int8_t *map, float *y, int64_t ldy, void *stream);
 
 /*
+ * LOE output_error — the layer-output error of quantised weights (no reference counterpart: the consumer of the files
+ * scripts/generate_deepseek_layer0_io.py records).  x: m × k bf16 activations (ldx), w: n × k weight (w_dtype, ldw, nn.Linear
+ * convention), bias: n float32 or NULL.  R = x·wᵀ + b is compared with Y_f = x·Ŵ_fᵀ + b for every format bit of fmt_mask (bits 0..3:
+ * Ŵ = K2 of w, row layout), with the map candidate when `map` is not NULL (Ŵ = K3 of w with map: ceil(n/32) × ceil(k/32) int8 codes,
+ * row-major, on device), with fp0 (Y = b) always, and with `recorded` (m × n, rec_dtype, ldr) when it is not NULL.  Ŵ and Y are never
+ * written.  sums: device doubles [MTQ_OE_SLOTS][7] in the order of mtq_columns_from_sums (Σr, Σr², Σq, Σq², Σrq, Σ|r−q|, max|r−q|),
+ * slots bf16, bfp8, bfp4, bfp2, map, fp0, recorded; the call ADDS this chunk's sums to them (max for the last), so a caller zeroes
+ * them once and passes m in chunks.  Slots not requested are left untouched.  scratch: device doubles, at least
+ * mtq_output_error_scratch_doubles(m, n).  Deterministic: a fixed reduction order, no float atomics.  csrc/mtq_output_error.hip.
+ */
+#define MTQ_OE_SLOTS 7
+enum { MTQ_OE_BF16 = 0, MTQ_OE_BFP8 = 1, MTQ_OE_BFP4 = 2, MTQ_OE_BFP2 = 3, MTQ_OE_MAP = 4, MTQ_OE_FP0 = 5, MTQ_OE_RECORDED = 6 };
+size_t mtq_output_error_scratch_doubles(int64_t m, int64_t n);
+int mtq_output_error(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
+                     const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
+                     double *sums, double *scratch, size_t scratch_doubles, void *stream);
+
+/*
  * K5 dequant_fp8_block (loader) — float8-e4m3fn weights × float32 inverse block scales → float32: the on-load
  * dequantisation of DeepSeek-style checkpoints, `w.float() * scale_inv.repeat_interleave(block)` with
  * block = ceil(dim / scale_dim) (hf_model_utils.py:199-215, used at :273-281).  w: rows × cols bytes (ldw),

@@ -1,0 +1,357 @@
+// mtq_output_error.hip — LOE: the layer-output error of quantised weights on recorded activations.
+//
+// Y_f = X·Ŵ_fᵀ (+ b) for every candidate f against R = X·Wᵀ (+ b), in one pass over X and W, reduced to the seven float64 sums
+// mtq_columns_from_sums takes; neither Ŵ nor Y is written.  X is bf16 (M × K), W is N × K (bf16 or float32) in the nn.Linear convention.
+//
+// Tiling: a workgroup of 4 waves owns a 128 (M) × 64 (N) output block and walks K in steps of 64.  Per step
+//   * X: 128 × 64 bf16 → LDS;
+//   * W: 64 rows × 64 = 256 groups of 16 → one lane per group computes the group's shared exponent once and writes a bf16 LDS image of
+//     its 16 values for each candidate (bfp8 / bfp4 / bfp2 / map) and for the reference (hi = bf16(W); for float32 W also mid = bf16(W − hi)
+//     and lo = bf16(W − hi − mid), which is exact: hi + mid + lo = W for |W| ≥ 2^-100).  Every BFP value has its low 16 bits zero, so each
+//     image is exact in bf16 and the MFMA forms every product exactly; only the f32 accumulation rounds.
+//   * each wave: 32 M rows × 64 N columns (2 subtiles of mfma_f32_32x32x16_bf16) per accumulator; one A fragment of X feeds them all.
+// Accumulators: hi (the reference for bf16 W and the bf16 candidate for both: bf16(W) = hi), res (mid + lo, float32 W only), bfp8,
+// bfp4, bfp2, map.  Epilogue: r = hi + res + b, q_f = acc_f + b, in f32; the sums of (r, q) in float64 per lane, then a fixed-order
+// reduction over the workgroup into one partial record per workgroup, and a second kernel adds the records in index order into `sums`
+// (no float atomics: the same inputs give the same bits).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "mtq_device.hpp"
+#include "mtq_error.hpp"
+
+namespace mtq {
+namespace {
+
+constexpr int kBM = 128, kBN = 64, kBK = 64, kThreads = 256;
+constexpr int kLdk = kBK + 8;                      // LDS row pitch in bf16 (144 B: 16-B fragment reads of 32 rows spread over the banks)
+constexpr int kImgHi = 0, kImgMid = 1, kImgLo = 2, kImgB8 = 3, kImgB4 = 4, kImgB2 = 5, kImgMap = 6, kNumImg = 7;
+constexpr int kSlots = 7;                          // bf16, bfp8, bfp4, bfp2, map, fp0, recorded
+constexpr int kRecord = 2 + 5 * kSlots;            // Σr, Σr², then Σq, Σq², Σrq, Σ|r−q|, max|r−q| per slot
+constexpr int kLdsBytes = (kBM + kNumImg * kBN) * kLdk * 2;
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ float bits_f(uint32_t v) { return __uint_as_float(v); }
+
+// One BFP element by the group's constants (mtq_direct.hpp bfp_pair): xs = x truncated to the group's 24-bit window.
+__device__ __forceinline__ uint32_t bfp_fast(float xs, float C, float ymax)
+{
+    const float r = (xs + C) - C;
+    return __float_as_uint(__builtin_amdgcn_fmed3f(r, -ymax, ymax));
+}
+
+struct GroupConsts {
+    float k_align, k_back, c[4], ymax[4];
+};
+
+__device__ __forceinline__ GroupConsts group_consts(uint32_t E)
+{
+    GroupConsts g;
+    g.k_align = bits_f((277u - E) << 23);
+    g.k_back = bits_f((E - 23u) << 23);
+#pragma unroll
+    for (int f = 1; f <= 3; ++f) {
+        const uint32_t M = f == 1 ? 7u : (f == 2 ? 3u : 1u);
+        g.c[f] = bits_f(((E + 24u - M) << 23) | 0x400000u);
+        g.ymax[f] = (float)((1u << M) - 1u) * bits_f((E - (M - 1u)) << 23);
+    }
+    g.c[0] = g.ymax[0] = 0.0f;
+    return g;
+}
+
+// y bits of format f (0..3; anything else → +0, as K3) for element u of a group with shared exponent E; fast = E in [80, 180].
+__device__ __forceinline__ uint32_t quant_bits(int f, uint32_t u, uint32_t E, bool fast, const GroupConsts &g)
+{
+    if (f == 0) return bf16_round_bits(u);
+    if (f < 1 || f > 3) return 0u;
+    if (fast) {
+        const float xs = __builtin_truncf(bits_f(u) * g.k_align) * g.k_back;
+        return bfp_fast(xs, g.c[f], g.ymax[f]);
+    }
+    return bfp_elem_bits_rt(u, E, f == 1 ? 7u : (f == 2 ? 3u : 1u));
+}
+
+__device__ __forceinline__ void store_image(uint16_t *dst, const uint32_t (&y)[kGroup])
+{
+    uint32_t pk[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pk[i] = (y[2 * i] >> 16) | (y[2 * i + 1] & 0xFFFF0000u);
+    uint4 *d = reinterpret_cast<uint4 *>(dst);
+    d[0] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+    d[1] = make_uint4(pk[4], pk[5], pk[6], pk[7]);
+}
+
+// One W group → every image the launch needs.  imask: bit i = image i is used.
+__device__ __forceinline__ void stage_w_group(const uint32_t (&u)[kGroup], int64_t n, int64_t k, int64_t N, int64_t K,
+                                              uint32_t imask, const int8_t *__restrict__ map, int64_t map_w, uint16_t *img0, int img_off)
+{
+    const uint32_t E = group_shared_exp(u);
+    const bool fast = (E - 80u) <= 100u;
+    const GroupConsts g = group_consts(fast ? E : 127u);
+    uint32_t y[kGroup];
+    constexpr int kImgElems = kBN * kLdk;
+    {   // hi (and mid / lo for float32 storage)
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) y[i] = bf16_round_bits(u[i]);
+        store_image(img0 + kImgHi * kImgElems + img_off, y);
+        if (imask & (1u << kImgMid)) {
+            uint32_t r1[kGroup];
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) {
+                const float d1 = bits_f(u[i]) - bits_f(y[i]);            // exact
+                r1[i] = bf16_round_bits(__float_as_uint(d1));
+                y[i] = __float_as_uint(d1 - bits_f(r1[i]));              // exact, at most 8 significant bits
+            }
+            store_image(img0 + kImgMid * kImgElems + img_off, r1);
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) y[i] = bf16_round_bits(y[i]);
+            store_image(img0 + kImgLo * kImgElems + img_off, y);
+        }
+    }
+#pragma unroll
+    for (int f = 1; f <= 3; ++f) {
+        const int im = kImgB8 + f - 1;
+        if (imask & (1u << im)) {                                        // launch-uniform
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) y[i] = quant_bits(f, u[i], E, fast, g);
+            store_image(img0 + im * kImgElems + img_off, y);
+        }
+    }
+    if (imask & (1u << kImgMap)) {
+        const int f = (n < N && k < K) ? (int)map[(n / kTile) * map_w + k / kTile] : 4;   // the zero padding of a ragged edge stays zero
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) y[i] = quant_bits(f, u[i], E, fast, g);
+        store_image(img0 + kImgMap * kImgElems + img_off, y);
+    }
+}
+
+__device__ __forceinline__ void fold(double (&s)[kRecord], int slot, double r, double q)
+{
+    const double d = fabs(r - q);
+    s[2 + 5 * slot] += q;
+    s[3 + 5 * slot] += q * q;
+    s[4 + 5 * slot] += r * q;
+    s[5 + 5 * slot] += d;
+    s[6 + 5 * slot] = fmax(s[6 + 5 * slot], d);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec,
+                                                                const T *__restrict__ w, int64_t N, int64_t ldw, int w_vec,
+                                                                const float *__restrict__ bias, uint32_t imask, uint32_t smask,
+                                                                const int8_t *__restrict__ map, int64_t map_w,
+                                                                const void *__restrict__ rec, int rec_f32, int64_t ldr,
+                                                                double *__restrict__ partials)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[kLdsBytes / 2];
+    __shared__ double red[4][kRecord];
+    uint16_t *xs = lds;
+    uint16_t *img0 = lds + kBM * kLdk;
+    constexpr int kImgElems = kBN * kLdk;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t nblocks = (N + kBN - 1) / kBN;
+    const int64_t bm = blockIdx.x / nblocks, bn = blockIdx.x % nblocks;
+    const int64_t m0 = bm * kBM, n0 = bn * kBN;
+    const bool f32w = (imask & (1u << kImgMid)) != 0;
+
+    f32x16 acc[6][2];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][s][r] = 0.0f;
+
+    // global → registers one K-step ahead: the loads of step k0 + 64 are in flight while the MFMAs of step k0 run
+    const int wrow = tid >> 2, wc16 = (tid & 3) * kGroup;
+    uint4 xr[4];
+    uint32_t wu[kGroup];
+    auto load_step = [&](int64_t k0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {   // X: 128 rows × 64 columns = 1024 pieces of 8 bf16, 4 per thread
+            const int p = tid + kThreads * i, row = p >> 3, c8 = (p & 7) * 8;
+            const int64_t gm = m0 + row, gk = k0 + c8;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (gm < M) {
+                const uint16_t *src = x + gm * ldx + gk;
+                if (x_vec && gk + 8 <= K) {
+                    v = *reinterpret_cast<const uint4 *>(src);
+                } else {
+                    uint32_t h[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) h[j] = gk + j < K ? (uint32_t)src[j] : 0u;
+                    v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+                }
+            }
+            xr[i] = v;
+        }
+        Loader<T>::group(w, n0 + wrow, k0 + wc16, N, K, ldw, w_vec != 0, wu);   // W: lane tid owns group (row tid / 4, columns 16·(tid % 4) ..)
+    };
+    load_step(0);
+    for (int64_t k0 = 0; k0 < K; k0 += kBK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int p = tid + kThreads * i;
+            *reinterpret_cast<uint4 *>(xs + (p >> 3) * kLdk + (p & 7) * 8) = xr[i];
+        }
+        stage_w_group(wu, n0 + wrow, k0 + wc16, N, K, imask, map, map_w, img0, wrow * kLdk + wc16);
+        __syncthreads();
+        if (k0 + kBK < K) load_step(k0 + kBK);
+#pragma unroll
+        for (int kk = 0; kk < kBK / 16; ++kk) {
+            const int koff = kk * 16 + 8 * (lane >> 5);
+            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (wave * 32 + (lane & 31)) * kLdk + koff);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int boff = (s * 32 + (lane & 31)) * kLdk + koff;
+#define MTQ_OE_MFMA(ACC, IMG) acc[ACC][s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, *reinterpret_cast<const bf16x8 *>(img0 + (IMG) * kImgElems + boff), acc[ACC][s], 0, 0, 0)
+                MTQ_OE_MFMA(0, kImgHi);
+                if (f32w) { MTQ_OE_MFMA(1, kImgMid); MTQ_OE_MFMA(1, kImgLo); }
+                if (imask & (1u << kImgB8)) MTQ_OE_MFMA(2, kImgB8);
+                if (imask & (1u << kImgB4)) MTQ_OE_MFMA(3, kImgB4);
+                if (imask & (1u << kImgB2)) MTQ_OE_MFMA(4, kImgB2);
+                if (imask & (1u << kImgMap)) MTQ_OE_MFMA(5, kImgMap);
+#undef MTQ_OE_MFMA
+            }
+        }
+        __syncthreads();
+    }
+
+    // epilogue: lane's outputs are (m0 + 32·wave + (r&3) + 8(r>>2) + 4(lane>>5), n0 + 32s + (lane&31))
+    double sum[kRecord];
+#pragma unroll
+    for (int i = 0; i < kRecord; ++i) sum[i] = 0.0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int64_t n = n0 + 32 * s + (lane & 31);
+        if (n >= N) continue;
+        const float b = bias ? bias[n] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t m = m0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (m >= M) continue;
+            const float hi = acc[0][s][r];
+            const float rf = (f32w ? hi + acc[1][s][r] : hi) + b;
+            const double rd = (double)rf;
+            sum[0] += rd;
+            sum[1] += rd * rd;
+            if (smask & 1u) fold(sum, 0, rd, (double)(hi + b));
+            if (smask & 2u) fold(sum, 1, rd, (double)(acc[2][s][r] + b));
+            if (smask & 4u) fold(sum, 2, rd, (double)(acc[3][s][r] + b));
+            if (smask & 8u) fold(sum, 3, rd, (double)(acc[4][s][r] + b));
+            if (smask & 16u) fold(sum, 4, rd, (double)(acc[5][s][r] + b));
+            if (smask & 32u) fold(sum, 5, rd, (double)b);
+            if (smask & 64u) {
+                const float q = rec_f32 ? static_cast<const float *>(rec)[m * ldr + n]
+                                        : bits_f((uint32_t)static_cast<const uint16_t *>(rec)[m * ldr + n] << 16);
+                fold(sum, 6, rd, (double)q);
+            }
+        }
+    }
+    // fixed-order reduction: butterfly within the wave (the same tree in every run), then the 4 waves in order
+#pragma unroll
+    for (int i = 0; i < kRecord; ++i) {
+        const bool is_max = i >= 2 && (i - 2) % 5 == 4;
+        double v = sum[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double t = __shfl_xor(v, o, 64);
+            v = is_max ? fmax(v, t) : v + t;
+        }
+        if (lane == 0) red[wave][i] = v;
+    }
+    __syncthreads();
+    if (tid < kRecord) {
+        const bool is_max = tid >= 2 && (tid - 2) % 5 == 4;
+        double v = red[0][tid];
+        for (int wv = 1; wv < 4; ++wv) v = is_max ? fmax(v, red[wv][tid]) : v + red[wv][tid];
+        partials[(int64_t)blockIdx.x * kRecord + tid] = v;
+    }
+}
+
+// sums[slot][7] (+)= the workgroup records in index order: one workgroup per record entry, each thread a strided slice, then a fixed tree.
+__global__ __launch_bounds__(256) void output_error_reduce(const double *__restrict__ partials, int64_t nblocks, double *__restrict__ sums,
+                                                           uint32_t smask)
+{
+    __shared__ double buf[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const bool is_max = i >= 2 && (i - 2) % 5 == 4;
+    double v = 0.0;
+    for (int64_t b = tid; b < nblocks; b += 256) {
+        const double p = partials[b * kRecord + i];
+        v = is_max ? fmax(v, p) : v + p;
+    }
+    buf[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) buf[tid] = is_max ? fmax(buf[tid], buf[tid + s]) : buf[tid] + buf[tid + s];
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const double t = buf[0];
+    if (i < 2) {                                   // Σr, Σr²: shared by every slot
+        for (int slot = 0; slot < kSlots; ++slot)
+            if (smask & (1u << slot)) sums[slot * 7 + i] += t;
+    } else {
+        const int slot = (i - 2) / 5, j = 2 + (i - 2) % 5;
+        if (smask & (1u << slot)) sums[slot * 7 + j] = j == 6 ? fmax(sums[slot * 7 + j], t) : sums[slot * 7 + j] + t;
+    }
+}
+
+} // namespace
+} // namespace mtq
+
+using namespace mtq;
+
+extern "C" size_t mtq_output_error_scratch_doubles(int64_t m, int64_t n)
+{
+    if (m <= 0 || n <= 0) return 0;
+    return (size_t)(((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN)) * kRecord;
+}
+
+extern "C" int mtq_output_error(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
+                                const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
+                                double *sums, double *scratch, size_t scratch_doubles, void *stream)
+{
+    if (!x || !w || !sums || !scratch) return fail(MTQ_ERR_INVALID, "null argument");
+    if (w_dtype != MTQ_DTYPE_BF16 && w_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "w_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    if (recorded && rec_dtype != MTQ_DTYPE_BF16 && rec_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "rec_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    if ((fmt_mask & ~MTQ_MASK_ALL) != 0) return fail(MTQ_ERR_UNSUPPORTED, "fmt_mask may name only bf16|bfp8|bfp4|bfp2 (bits 0..3)");
+    if (m <= 0 || n <= 0 || k <= 0) return fail(MTQ_ERR_INVALID, "m, n and k must be positive (empty operands are handled by the caller)");
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldw < k) return fail(MTQ_ERR_INVALID, "ldw < k");
+    if (recorded && ldr < n) return fail(MTQ_ERR_INVALID, "ldr < n");
+    if (m > (int64_t)1 << 40 || n > (int64_t)1 << 30 || k > (int64_t)1 << 30) return fail(MTQ_ERR_INVALID, "matrix too large");
+    const int64_t blocks = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
+    if (scratch_doubles < mtq_output_error_scratch_doubles(m, n)) return fail(MTQ_ERR_INVALID, "scratch smaller than mtq_output_error_scratch_doubles(m, n)");
+    if (int rc = require_device()) return rc;
+
+    const int f32w = w_dtype == MTQ_DTYPE_F32;
+    uint32_t imask = 1u << kImgHi;
+    if (f32w) imask |= (1u << kImgMid) | (1u << kImgLo);
+    for (int f = 1; f <= 3; ++f)
+        if (fmt_mask & (1u << f)) imask |= 1u << (kImgB8 + f - 1);
+    if (map) imask |= 1u << kImgMap;
+    const uint32_t smask = (fmt_mask & MTQ_MASK_ALL) | (map ? 16u : 0u) | 32u | (recorded ? 64u : 0u);
+    const int64_t esz = f32w ? 4 : 2;
+    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
+    const int w_vec = reinterpret_cast<uintptr_t>(w) % 16 == 0 && (ldw * esz) % 16 == 0;
+    const int64_t map_w = (k + kTile - 1) / kTile;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)blocks);
+    if (f32w)
+        hipLaunchKernelGGL(output_error_kernel<float>, grid, dim3(kThreads), 0, st, static_cast<const uint16_t *>(x), m, k, ldx, x_vec,
+                           static_cast<const float *>(w), n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_dtype == MTQ_DTYPE_F32, ldr, scratch);
+    else
+        hipLaunchKernelGGL(output_error_kernel<uint16_t>, grid, dim3(kThreads), 0, st, static_cast<const uint16_t *>(x), m, k, ldx, x_vec,
+                           static_cast<const uint16_t *>(w), n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_dtype == MTQ_DTYPE_F32, ldr, scratch);
+    if (int rc = check_launch("mtq_output_error")) return rc;
+    hipLaunchKernelGGL(output_error_reduce, dim3(kRecord), dim3(256), 0, st, scratch, blocks, sums, smask);
+    return check_launch("mtq_output_error (reduce)");
+}

@@ -35,11 +35,11 @@ EXPORTS = [
     "mtq_scan_orders_bytes", "mtq_scan_orders_device", "mtq_debug_scan_ticks", "mtq_threshold_enqueue", "mtq_threshold_columns",
     "mtq_tile_stats_ragged", "mtq_knife_tiles_ragged", "mtq_column_sums_device_ragged", "mtq_threshold_enqueue_ragged", "mtq_threshold_columns_ragged",
     "mtq_tile_stats_transposed", "mtq_quantize_transposed", "mtq_apply_assignment_transposed", "mtq_knife_tiles_transposed",
-    "mtq_threshold_enqueue_transposed",
+    "mtq_threshold_enqueue_transposed", "mtq_output_error_scratch_doubles", "mtq_output_error",
 ]
 # found by name, not by MTQ_VERSION: an older build of the same version (an A/B library at MTQ_LIB) lacks them and still loads
 OPTIONAL_EXPORTS = ("mtq_tile_stats_transposed", "mtq_quantize_transposed", "mtq_apply_assignment_transposed", "mtq_knife_tiles_transposed",
-                    "mtq_threshold_enqueue_transposed")
+                    "mtq_threshold_enqueue_transposed", "mtq_output_error_scratch_doubles", "mtq_output_error")
 
 
 class MtqError(RuntimeError):
@@ -145,6 +145,10 @@ def lib() -> ctypes.CDLL:
         L.mtq_knife_tiles_transposed.argtypes = [vp, ci, i64, i64, i64, i64, i64, vp, vp, ci, i64, vp, vp, vp]
     if hasattr(L, "mtq_threshold_enqueue_transposed"):
         L.mtq_threshold_enqueue_transposed.argtypes = L.mtq_threshold_enqueue.argtypes
+    if hasattr(L, "mtq_output_error"):
+        L.mtq_output_error_scratch_doubles.argtypes = [i64, i64]
+        L.mtq_output_error_scratch_doubles.restype = ctypes.c_size_t
+        L.mtq_output_error.argtypes = [vp, i64, i64, i64, vp, ci, i64, i64, vp, u32, vp, vp, ci, i64, vp, vp, ctypes.c_size_t, vp]
     if L.mtq_version() < 141:
         raise MtqError("libmtq_hip.so is older than this package")
     _lib = L
@@ -504,6 +508,59 @@ def apply_assignment_transposed(x, assignment, out=None):
         raise MtqError("out must be a contiguous float32 device tensor of X's shape")
     check(fn(x3.data_ptr(), _dtype_code(x3), count, stride, rows, cols, ld, a.data_ptr(), out.data_ptr(), cols, _stream_ptr()))
     return out if x.dim() == 3 else out[0]
+
+
+OE_SLOTS = ("bf16", "bfp8", "bfp4", "bfp2", "map", "fp0", "recorded")  # include/mtq.h MTQ_OE_* (rows of the sums array)
+
+
+def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded=None, scratch=None):
+    """LOE (mtq_output_error) on the current stream: ADDS the output-error sums of one M-chunk to `sums` (float64 device tensor
+    [7, 7], zeroed by the caller once per op).  x: (m, k) bf16 device tensor with contiguous rows; w: (n, k) bf16 / float32 device
+    tensor with contiguous rows; bias: float32 [n] or None; assignment: int8 map of w's 32×32 grid or None; recorded: (m, n) bf16 /
+    float32 or None.  scratch: float64 device tensor of at least output_error_scratch(m, n) elements (allocated when None)."""
+    torch = _torch()
+    require_gpu()
+    fn = _transposed_entry("mtq_output_error")
+    for name, t in (("x", x), ("w", w)):
+        if not getattr(t, "is_cuda", False) or t.dim() != 2 or t.stride(-1) != 1:
+            raise MtqError(f"{name}: expected a 2-D device tensor with contiguous rows")
+    if x.dtype != torch.bfloat16:
+        raise MtqError(f"x must be bfloat16, got {x.dtype}")
+    m, k = int(x.shape[0]), int(x.shape[1])
+    n = int(w.shape[0])
+    if int(w.shape[1]) != k:
+        raise MtqError(f"x has {k} columns, w has {int(w.shape[1])}")
+    if sums.dtype != torch.float64 or tuple(sums.shape) != (len(OE_SLOTS), 7) or not sums.is_contiguous() or not sums.is_cuda:
+        raise MtqError("sums must be a contiguous float64 device tensor of shape (7, 7)")
+    bp = 0
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.numel() != n or not bias.is_contiguous() or not bias.is_cuda:
+            raise MtqError("bias must be a contiguous float32 device tensor of n elements")
+        bp = bias.data_ptr()
+    mp = 0
+    if assignment is not None:
+        th, tw = tiles_hw(n, k)
+        if assignment.dtype != torch.int8 or assignment.numel() != th * tw or not assignment.is_contiguous() or not assignment.is_cuda:
+            raise MtqError(f"assignment must be a contiguous int8 device tensor of {th}x{tw} entries")
+        mp = assignment.data_ptr()
+    rp, rdt, ldr = 0, 0, 0
+    if recorded is not None:
+        if tuple(recorded.shape) != (m, n) or recorded.stride(-1) != 1 or not recorded.is_cuda:
+            raise MtqError(f"recorded must be a ({m}, {n}) device tensor with contiguous rows")
+        rp, rdt, ldr = recorded.data_ptr(), _dtype_code(recorded), int(recorded.stride(0))
+    need = output_error_scratch(m, n)
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.float64, device=x.device)
+    elif scratch.numel() < need:
+        raise MtqError(f"scratch holds {scratch.numel()} doubles, the launch needs {need}")
+    check(fn(x.data_ptr(), m, k, int(x.stride(0)), w.data_ptr(), _dtype_code(w), n, int(w.stride(0)), bp, fmt_mask, mp, rp, rdt, ldr,
+             sums.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream_ptr()))
+    return sums
+
+
+def output_error_scratch(m: int, n: int) -> int:
+    """Doubles of scratch one mtq_output_error launch over m × n outputs needs."""
+    return int(_transposed_entry("mtq_output_error_scratch_doubles")(m, n))
 
 
 def apply_assignment(x2d, assignment, out=None):

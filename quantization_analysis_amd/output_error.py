@@ -1,0 +1,239 @@
+"""Layer-output error of quantised weights on recorded activations.
+
+For one op with weight W (n × k, nn.Linear convention) and activations X (m × k, bf16) the reference output is R = X·Wᵀ (+ b) and
+every candidate f gives Y_f = X·Ŵ_fᵀ (+ b): Ŵ_f = quantize_weight_values(W, f) in the row layout for a pure format, the search's
+reconstruction for the map of a mixed-tile algorithm, Y = b (or 0) for fp0.  Each row reports pcc, mae and atol of Y_f against R
+over all m·n outputs, from the seven float64 sums mtq_columns_from_sums takes (so its zero-denominator rule is the one of the
+searches); the `recorded` row compares R with the op's recorded output.
+
+Backends:
+  * hip       — csrc/mtq_output_error.hip: one pass per M-chunk with every candidate's W image built on the fly in LDS, the sums
+                reduced in the epilogue; neither Ŵ nor Y is materialised;
+  * emulation — the same contract on the host in float64 (torch), from quantization_formats.quantize_weight_values: the oracle of
+                the GPU tests and the route for small CPU runs.
+"""
+from __future__ import annotations
+
+import tempfile
+from dataclasses import dataclass, field
+from pathlib import Path
+from typing import Iterable, Optional
+
+import numpy as np
+
+from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS
+from .layer_io import OpIO, check_op, chunks
+from .quantization_formats import SUPPORTED_FORMATS, quantize_weight_values
+
+FORMAT_BYTES_PER_ELEM = {"bf16": 2.0, "bfp8": 1.088, "bfp4": 0.50097, "bfp2": 0.25097, "fp0": 0.0}  # wq:132-140 (cli.py)
+SLOTS = ("bf16", "bfp8", "bfp4", "bfp2", "map", "fp0", "recorded")  # include/mtq.h MTQ_OE_*
+BACKENDS = ("emulation", "hip")
+MIXED_ALGOS = {"mixed-tile-greedy", "mixed-tile-random", "mixed-tile-threshold"}
+
+
+@dataclass
+class MapCandidate:
+    """The map of a mixed-tile search over W: `assignment` int8 (tiles_h, tiles_w) of codes into MIXED_TILE_FORMATS, `y` the search's
+    reconstruction (host ndarray or device tensor), `tile_bytes` its weight bytes."""
+
+    name: str
+    assignment: np.ndarray
+    y: object
+    tile_bytes: float
+
+
+@dataclass
+class Row:
+    candidate: str
+    bytes: Optional[float]
+    pcc: float
+    mae: float
+    atol: float
+    sums: tuple = ()
+
+
+@dataclass
+class OpResult:
+    op: str
+    weight: str
+    shape: tuple = ()
+    m: int = 0
+    splits: list = field(default_factory=list)
+    x_cast: bool = False
+    rows: list = field(default_factory=list)
+    skipped: Optional[str] = None
+
+
+def check_layout(config) -> None:
+    """Only the row layout is supported: the BFP groups of the transposed layout run along N, across the W rows the kernel stages."""
+    if config is None:
+        return
+    if config.algorithm == "transpose" or str((config.params or {}).get("layout", "rows")) == "transpose":
+        raise ValueError("layer output error supports only the row layout: compression configs with \"layout\": \"transpose\" "
+                         "(or the transpose algorithm) are not supported")
+
+
+def search_map(w, config, backend: str, name: str = "weight") -> Optional[MapCandidate]:
+    """Runs the config's mixed-tile algorithm on W through the plugin API → its map candidate (None for a config without one)."""
+    from .compression_algorithms import create_algorithm
+    from .compression_algorithms.cache import CacheContext
+    from .compression_algorithms.quantizer import Quantizer
+    from .model_source import resolve_format_list
+
+    if config is None or config.algorithm not in MIXED_ALGOS:
+        return None
+    check_layout(config)
+    params = dict(config.params)
+    if config.seed is not None:                      # wq's seed rule for a config seed (cli.resolve_seed); params["seed"] otherwise
+        params["seed"] = int(config.seed)
+    algo = create_algorithm(config.algorithm, params)
+    formats = resolve_format_list(config.quantization_formats, SUPPORTED_FORMATS)
+    with tempfile.TemporaryDirectory() as tmp:
+        cache = CacheContext(root=Path(tmp), tensor_name=name, backend=backend, recompute=True, run_tag="output-error")
+        results = algo.run(xf=w, formats=formats, quantizer=Quantizer(backend), cache=cache)
+    for res in results:
+        if res.fmt == "MIXED" and res.meta and isinstance(res.meta.get("assignment"), np.ndarray) and res.y is not None:
+            return MapCandidate(name=f"map:{algo.name}", assignment=np.ascontiguousarray(res.meta["assignment"], dtype=np.int8),
+                                y=res.y, tile_bytes=float(res.tile_bytes))
+    raise RuntimeError(f"{config.algorithm} returned no map with a reconstruction")
+
+
+def _columns(sums7, elem_count: float) -> tuple:
+    from .hip_backend import columns_from_sums
+
+    c = columns_from_sums(np.asarray(sums7, dtype=np.float64), elem_count)
+    return c["pcc"], c["mae"], c["atol"]
+
+
+def _fold64(acc: np.ndarray, r, q) -> None:
+    """acc[0..6] += Σr, Σr², Σq, Σq², Σrq, Σ|r−q|; acc[6] = max(acc[6], max|r−q|) — float64 torch tensors r, q of one chunk."""
+    d = (r - q).abs()
+    acc[0] += float(r.sum())
+    acc[1] += float((r * r).sum())
+    acc[2] += float(q.sum())
+    acc[3] += float((q * q).sum())
+    acc[4] += float((r * q).sum())
+    acc[5] += float(d.sum())
+    acc[6] = max(acc[6], float(d.max())) if d.numel() else acc[6]
+
+
+def emulation_sums(chunk_iter: Iterable, w, formats, bias=None, map_y=None) -> tuple[np.ndarray, int, bool, bool]:
+    """Float64 host route → (sums [7, 7] in SLOTS order, m, any recorded output seen, any cast)."""
+    import torch
+
+    w32 = np.asarray(w.float().cpu().numpy() if hasattr(w, "cpu") else w, dtype=np.float32)
+    w64 = torch.from_numpy(w32.astype(np.float64))
+    b64 = None if bias is None else torch.from_numpy(np.asarray(bias.float().cpu().numpy() if hasattr(bias, "cpu") else bias, dtype=np.float64))
+    what = {}
+    for f in formats:
+        if f in MIXED_TILE_FORMATS:
+            what[f] = torch.from_numpy(quantize_weight_values(w32, f).astype(np.float64))
+    if map_y is not None:
+        what["map"] = torch.from_numpy(np.asarray(map_y.float().cpu().numpy() if hasattr(map_y, "cpu") else map_y, dtype=np.float64))
+    sums = np.zeros((len(SLOTS), 7), dtype=np.float64)
+    m, seen_rec, cast = 0, False, False
+    for ch in chunk_iter:
+        x64 = ch.x.to(torch.float64)
+        r = x64 @ w64.T
+        if b64 is not None:
+            r = r + b64
+        for slot, wh in what.items():
+            q = x64 @ wh.T
+            if b64 is not None:
+                q = q + b64
+            _fold64(sums[SLOTS.index(slot)], r, q)
+        q0 = torch.zeros_like(r) if b64 is None else b64.expand_as(r)
+        _fold64(sums[SLOTS.index("fp0")], r, q0)
+        if ch.recorded is not None:
+            seen_rec = True
+            _fold64(sums[SLOTS.index("recorded")], r, ch.recorded.to(torch.float64))
+        m += int(ch.x.shape[0])
+        cast = cast or ch.cast
+    return sums, m, seen_rec, cast
+
+
+def hip_sums(chunk_iter: Iterable, w, formats, bias=None, assignment=None) -> tuple[np.ndarray, int, bool, bool]:
+    """The fused kernel over every chunk, partial sums carried on the device → the same as emulation_sums."""
+    import torch
+
+    from . import hip_backend as hb
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    wd = w.to(dev) if w.dtype in (torch.bfloat16, torch.float32) else w.float().to(dev)
+    wd = wd if wd.stride(-1) == 1 else wd.contiguous()
+    bd = None if bias is None else bias.float().contiguous().to(dev)
+    ad = None if assignment is None else torch.from_numpy(np.ascontiguousarray(assignment, dtype=np.int8)).to(dev)
+    mask = hb.fmt_mask([f for f in formats if f in MIXED_TILE_FORMATS])
+    sums = torch.zeros((len(SLOTS), 7), dtype=torch.float64, device=dev)
+    scratch = None
+    m, seen_rec, cast = 0, False, False
+    for ch in chunk_iter:
+        xd = ch.x.to(dev, non_blocking=False).contiguous()
+        rd = None
+        if ch.recorded is not None:
+            seen_rec = True
+            rd = ch.recorded.to(dev)
+            rd = rd if rd.dtype in (torch.bfloat16, torch.float32) else rd.float()
+            rd = rd.contiguous()
+        need = hb.output_error_scratch(int(xd.shape[0]), int(wd.shape[0]))
+        if scratch is None or scratch.numel() < need:
+            scratch = torch.empty((need,), dtype=torch.float64, device=dev)
+        hb.output_error(xd, wd, mask, sums, bias=bd, assignment=ad, recorded=rd, scratch=scratch)
+        m += int(ch.x.shape[0])
+        cast = cast or ch.cast
+    torch.cuda.synchronize()
+    return sums.cpu().numpy(), m, seen_rec, cast
+
+
+def rows_from_sums(sums: np.ndarray, m: int, n: int, k: int, formats, map_cand: Optional[MapCandidate], recorded: bool) -> list[Row]:
+    numel_w = float(n * k)
+    count = float(m) * float(n)
+    rows = []
+    for f in formats:
+        rows.append(Row(f, FORMAT_BYTES_PER_ELEM[f] * numel_w, *_columns(sums[SLOTS.index(f)], count), tuple(sums[SLOTS.index(f)])))
+    if map_cand is not None:
+        s = sums[SLOTS.index("map")]
+        rows.append(Row(map_cand.name, map_cand.tile_bytes, *_columns(s, count), tuple(s)))
+    if recorded:
+        s = sums[SLOTS.index("recorded")]
+        rows.append(Row("recorded", None, *_columns(s, count), tuple(s)))
+    return rows
+
+
+def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation", chunk_rows: int = 16384) -> OpResult:
+    """One op of `select_ops` → its rows (or the reason it is skipped).  formats ⊆ SUPPORTED_FORMATS; config: a CompressionConfig
+    whose mixed-tile algorithm adds the map candidate (None = pure formats only)."""
+    if backend not in BACKENDS:
+        raise ValueError(f"backend must be one of {', '.join(BACKENDS)}")
+    check_layout(config)
+    bad = [f for f in formats if f not in SUPPORTED_FORMATS]
+    if bad:
+        raise ValueError(f"Unsupported format(s) {bad}. Supported: {', '.join(SUPPORTED_FORMATS)}")
+    shape, _ = index.shape_dtype(op.weight)
+    res = OpResult(op=op.op, weight=op.weight, shape=tuple(shape), splits=op.splits)
+    why = check_op(op, tuple(shape))
+    if why is not None:
+        res.skipped = why
+        return res
+    n, k = int(shape[0]), int(shape[1])
+    if backend == "hip":
+        import torch
+
+        dev = torch.device("cuda", torch.cuda.current_device())
+        w = index.load(op.weight, device=dev)
+        bias = index.load(op.bias, device=dev) if op.bias else None
+    else:
+        w = index.load(op.weight)
+        bias = index.load(op.bias) if op.bias else None
+    if bias is not None and bias.numel() != n:
+        res.skipped = f"bias has {bias.numel()} elements, the weight {n} rows"
+        return res
+    map_cand = search_map(w, config, backend, op.weight)
+    it = chunks(op, k, n, chunk_rows)
+    if backend == "hip":
+        sums, m, seen_rec, cast = hip_sums(it, w, formats, bias, None if map_cand is None else map_cand.assignment)
+    else:
+        sums, m, seen_rec, cast = emulation_sums(it, w, formats, bias, None if map_cand is None else map_cand.y)
+    res.m, res.x_cast = m, cast
+    res.rows = rows_from_sums(sums, m, n, k, formats, map_cand, seen_rec)
+    return res

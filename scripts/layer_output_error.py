@@ -1,0 +1,94 @@
+#!/usr/bin/env python3
+"""Layer-output error of quantised weights on recorded activations (the consumer of the files the reference's
+scripts/generate_deepseek_layer0_io.py writes).  For every selected op: R = X·Wᵀ (+ b) against Y_f = X·Ŵ_fᵀ (+ b) for each format
+and for the map of the compression config's mixed-tile algorithm, as pcc / mae / atol over all outputs, plus a `recorded` row
+(R against the recorded output).  Weights come from quantization_analysis_amd.model_source (synthetic presets or a local safetensors
+directory); io_root is a directory in the reference's layout or `synthetic:<tokens>[:seed]`.
+
+  python scripts/layer_output_error.py /path/to/DeepSeek-R1 /path/to/io model.layers.0.mlp --backend hip -c bf16 bfp8 bfp4 bfp2 \\
+      --compression-config compression_configs/compression_config.mixed_tile_greedy.example.json --split test --out-dir results/loe
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import json
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+from quantization_analysis_amd.compression_algorithms import load_compression_config
+from quantization_analysis_amd.layer_io import select_ops
+from quantization_analysis_amd.model_source import build_model_index, resolve_format_list
+from quantization_analysis_amd.output_error import BACKENDS, check_layout, evaluate_op
+from quantization_analysis_amd.quantization_formats import SUPPORTED_FORMATS
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Layer-output error of quantised weights on recorded activations.")
+    p.add_argument("repo_or_url", help="'synthetic:<preset>[:seed]' or a local directory of *.safetensors.")
+    p.add_argument("io_root", help="Directory of recorded op inputs / outputs (reference layout) or 'synthetic:<tokens>[:seed]'.")
+    p.add_argument("filter_query", nargs="*", help="Optional filter on the op weights: substring, or dotted torch-style prefix path.")
+    p.add_argument("--revision", default="main")
+    p.add_argument("--backend", choices=list(BACKENDS), default="emulation", help="emulation = float64 on the host; hip = MI355X kernel.")
+    p.add_argument("-c", "--formats", nargs="+", default=None, help="Candidate formats (default: the config's, else all).")
+    p.add_argument("--compression-config", default=None, help="A mixed-tile config adds the map of its search as a candidate.")
+    p.add_argument("--split", choices=["calibration", "test", "all"], default="all")
+    p.add_argument("--max-samples", type=int, default=None, help="First N samples of the split (by sample index).")
+    p.add_argument("--chunk-rows", type=int, default=16384, help="Activation rows per kernel launch (partial sums are carried).")
+    p.add_argument("--out-dir", default="results/layer_output_error")
+    return p.parse_args(argv)
+
+
+def _fmt(v, spec):
+    return "-" if v is None else format(v, spec)
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
+    config = load_compression_config(args.compression_config) if args.compression_config else None
+    check_layout(config)
+    formats = resolve_format_list(args.formats or (config.quantization_formats if config else None), SUPPORTED_FORMATS)
+    if args.backend == "hip":
+        import torch
+
+        torch.cuda.set_device(0)
+    index = build_model_index(args.repo_or_url, revision=args.revision)
+    query = " ".join(args.filter_query).strip() or None
+    ops, skipped = select_ops(index, args.io_root, query, args.split, args.max_samples)
+    out_dir = Path(args.out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    records, csv_rows = [], []
+    for op in ops:
+        res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows)
+        if res.skipped:
+            skipped.append((op.op, res.skipped))
+            continue
+        n, k = res.shape
+        print(f"\n{res.op}  W {n}x{k}  M {res.m}  splits {','.join(res.splits)}{'  (X cast to bf16)' if res.x_cast else ''}")
+        print(f"{'candidate':<28} | {'bytes':>14} | {'pcc':>12} | {'mae':>12} | {'atol':>12}")
+        print("-" * 90)
+        for r in res.rows:
+            print(f"{r.candidate:<28} | {_fmt(r.bytes, '14.0f')} | {r.pcc:12.8f} | {r.mae:12.6e} | {r.atol:12.6e}")
+            csv_rows.append([res.op, r.candidate, r.bytes, r.pcc, r.mae, r.atol, res.m, n, k])
+        records.append({"op": res.op, "weight": res.weight, "shape": [n, k], "M": res.m, "splits": res.splits, "x_cast": res.x_cast,
+                        "rows": [{"candidate": r.candidate, "bytes": r.bytes, "pcc": r.pcc, "mae": r.mae, "atol": r.atol} for r in res.rows]})
+    if skipped:
+        print("\nskipped:")
+        for op, why in skipped:
+            print(f"  {op}: {why}")
+    with open(out_dir / "layer_output_error.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["op", "candidate", "bytes", "pcc", "mae", "atol", "M", "N", "K"])
+        w.writerows(csv_rows)
+    doc = {"repo_or_url": args.repo_or_url, "io_root": args.io_root, "backend": args.backend, "formats": formats,
+           "compression_config": args.compression_config, "split": args.split, "max_samples": args.max_samples,
+           "ops": records, "skipped": [{"op": o, "reason": r} for o, r in skipped]}
+    (out_dir / "layer_output_error.json").write_text(json.dumps(doc, indent=2))
+    print(f"\nwrote {out_dir / 'layer_output_error.csv'} and {out_dir / 'layer_output_error.json'}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

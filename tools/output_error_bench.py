@@ -1,0 +1,105 @@
+"""Layer-output error: the fused kernel (csrc/mtq_output_error.hip) against the unfused torch route on the same GPU.
+
+Shapes: every 2-D weight of the synthetic:deepseek-r1-layer0 preset plus the three layer-0 MLP weights (gate / up 18432×7168,
+down 7168×18432; float32 fp8-block-like values as the loader returns DeepSeek weights), M = 12 800 synthetic N(0, 1) bf16 tokens,
+candidates bf16, bfp8, bfp4, bfp2 and the reference.
+  fused   : one mtq_output_error launch (+ its reduction) over all of X.
+  unfused : per format K2 → bf16 Ŵ → torch.matmul (bf16 out) → torch float64 reductions of the seven sums; the reference
+            R = X·bf16(W)ᵀ by one torch.matmul.  (Cheaper than the contract: R and Y are rounded to bf16.)
+TFLOP/s counts 2·M·N·K per candidate GEMM (4 formats + the reference).
+
+  python tools/output_error_bench.py [--tokens 12800] [--reps 3] [--only mlp] [--json out.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+import torch
+
+from quantization_analysis_amd import hip_backend as hb
+from quantization_analysis_amd.model_source import TensorSpec, build_model_index
+
+FMTS = ["bf16", "bfp8", "bfp4", "bfp2"]
+MLP = {"model.layers.0.mlp.gate_proj.weight": (18432, 7168), "model.layers.0.mlp.up_proj.weight": (18432, 7168),
+       "model.layers.0.mlp.down_proj.weight": (7168, 18432)}
+
+
+def _time(fn, reps: int) -> float:
+    fn()
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        best = min(best, time.perf_counter() - t0)
+    return best
+
+
+def unfused(x, w):
+    hi = w.to(torch.bfloat16)
+    r = torch.matmul(x, hi.T).double()
+    out = []
+    for f in FMTS:
+        wq = hb.quantize(w, f).to(torch.bfloat16)
+        q = torch.matmul(x, wq.T).double()
+        d = (r - q).abs()
+        out.append(torch.stack([r.sum(), (r * r).sum(), q.sum(), (q * q).sum(), (r * q).sum(), d.sum(), d.max()]))
+        del q, d
+    return torch.stack(out)
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tokens", type=int, default=12800)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--only", choices=["all", "mlp"], default="all")
+    ap.add_argument("--no-unfused", action="store_true")
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    hb.require_gpu()
+    dev = torch.device("cuda", 0)
+    index = build_model_index("synthetic:deepseek-r1-layer0")
+    for i, (name, shape) in enumerate(MLP.items()):
+        index.specs[name] = TensorSpec(shape, "f32", 1000 + i, "fp8block")
+    names = [n for n in index.tensor_names if len(index.specs[n].shape) == 2 and (args.only == "all" or n in MLP)]
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    rows = []
+    for name in names:
+        w = index.load(name, device=dev, draw_on_device=True)
+        n, k = w.shape
+        x = torch.randn((args.tokens, k), generator=g, device=dev).to(torch.bfloat16)
+        sums = torch.zeros((7, 7), dtype=torch.float64, device=dev)
+        scratch = torch.empty((hb.output_error_scratch(args.tokens, n),), dtype=torch.float64, device=dev)
+        mask = hb.fmt_mask(FMTS)
+
+        def fused():
+            sums.zero_()
+            hb.output_error(x, w, mask, sums, scratch=scratch)
+
+        t_f = _time(fused, args.reps)
+        flop = 2.0 * args.tokens * n * k * (len(FMTS) + 1)
+        row = {"op": name, "N": n, "K": k, "M": args.tokens, "fused_ms": t_f * 1e3, "fused_tflops": flop / t_f / 1e12}
+        if not args.no_unfused:
+            t_u = _time(lambda: unfused(x, w), args.reps)
+            row.update({"unfused_ms": t_u * 1e3, "unfused_tflops": flop / t_u / 1e12, "speedup": t_u / t_f})
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del w, x, scratch
+        torch.cuda.empty_cache()
+    if args.json:
+        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.json).write_text(json.dumps(rows, indent=1))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
