@@ -129,6 +129,9 @@ __device__ __forceinline__ void stage_w_group(const uint32_t (&u)[kGroup], int64
     }
 }
 
+// max|r − q| with np.max semantics: a NaN on either side wins (fmax would drop it and report the largest finite difference).
+__device__ __forceinline__ double nan_max(double a, double b) { return (a == a && b == b) ? fmax(a, b) : a + b; }
+
 __device__ __forceinline__ void fold(double (&s)[kRecord], int slot, double r, double q)
 {
     const double d = fabs(r - q);
@@ -136,7 +139,7 @@ __device__ __forceinline__ void fold(double (&s)[kRecord], int slot, double r, d
     s[3 + 5 * slot] += q * q;
     s[4 + 5 * slot] += r * q;
     s[5 + 5 * slot] += d;
-    s[6 + 5 * slot] = fmax(s[6 + 5 * slot], d);
+    s[6 + 5 * slot] = nan_max(s[6 + 5 * slot], d);
 }
 
 template <typename T>
@@ -261,7 +264,7 @@ __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const double t = __shfl_xor(v, o, 64);
-            v = is_max ? fmax(v, t) : v + t;
+            v = is_max ? nan_max(v, t) : v + t;
         }
         if (lane == 0) red[wave][i] = v;
     }
@@ -269,7 +272,7 @@ __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *
     if (tid < kRecord) {
         const bool is_max = tid >= 2 && (tid - 2) % 5 == 4;
         double v = red[0][tid];
-        for (int wv = 1; wv < 4; ++wv) v = is_max ? fmax(v, red[wv][tid]) : v + red[wv][tid];
+        for (int wv = 1; wv < 4; ++wv) v = is_max ? nan_max(v, red[wv][tid]) : v + red[wv][tid];
         partials[(int64_t)blockIdx.x * kRecord + tid] = v;
     }
 }
@@ -284,12 +287,12 @@ __global__ __launch_bounds__(256) void output_error_reduce(const double *__restr
     double v = 0.0;
     for (int64_t b = tid; b < nblocks; b += 256) {
         const double p = partials[b * kRecord + i];
-        v = is_max ? fmax(v, p) : v + p;
+        v = is_max ? nan_max(v, p) : v + p;
     }
     buf[tid] = v;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) buf[tid] = is_max ? fmax(buf[tid], buf[tid + s]) : buf[tid] + buf[tid + s];
+        if (tid < s) buf[tid] = is_max ? nan_max(buf[tid], buf[tid + s]) : buf[tid] + buf[tid + s];
         __syncthreads();
     }
     if (tid != 0) return;
@@ -299,7 +302,7 @@ __global__ __launch_bounds__(256) void output_error_reduce(const double *__restr
             if (smask & (1u << slot)) sums[slot * 7 + i] += t;
     } else {
         const int slot = (i - 2) / 5, j = 2 + (i - 2) % 5;
-        if (smask & (1u << slot)) sums[slot * 7 + j] = j == 6 ? fmax(sums[slot * 7 + j], t) : sums[slot * 7 + j] + t;
+        if (smask & (1u << slot)) sums[slot * 7 + j] = j == 6 ? nan_max(sums[slot * 7 + j], t) : sums[slot * 7 + j] + t;
     }
 }
 

@@ -4,7 +4,8 @@ For one op with weight W (n × k, nn.Linear convention) and activations X (m × 
 every candidate f gives Y_f = X·Ŵ_fᵀ (+ b): Ŵ_f = quantize_weight_values(W, f) in the row layout for a pure format, the search's
 reconstruction for the map of a mixed-tile algorithm, Y = b (or 0) for fp0.  Each row reports pcc, mae and atol of Y_f against R
 over all m·n outputs, from the seven float64 sums mtq_columns_from_sums takes (so its zero-denominator rule is the one of the
-searches); the `recorded` row compares R with the op's recorded output.
+searches); the `recorded` row compares R with the op's recorded output.  atol follows np.max: a NaN anywhere in |r − q| (a NaN
+recorded output, an Inf weight giving ∞ − ∞) makes that row's atol NaN on both backends, whichever M-chunk holds it.
 
 Backends:
   * hip       — csrc/mtq_output_error.hip: one pass per M-chunk with every candidate's W image built on the fly in LDS, the sums
@@ -106,7 +107,8 @@ def _columns(sums7, elem_count: float) -> tuple:
 
 
 def _fold64(acc: np.ndarray, r, q) -> None:
-    """acc[0..6] += Σr, Σr², Σq, Σq², Σrq, Σ|r−q|; acc[6] = max(acc[6], max|r−q|) — float64 torch tensors r, q of one chunk."""
+    """acc[0..6] += Σr, Σr², Σq, Σq², Σrq, Σ|r−q|; acc[6] = max(acc[6], max|r−q|) — float64 torch tensors r, q of one chunk.
+    The max propagates NaN whichever chunk holds it (np.max semantics, as the kernel)."""
     d = (r - q).abs()
     acc[0] += float(r.sum())
     acc[1] += float((r * r).sum())
@@ -114,7 +116,8 @@ def _fold64(acc: np.ndarray, r, q) -> None:
     acc[3] += float((q * q).sum())
     acc[4] += float((r * q).sum())
     acc[5] += float(d.sum())
-    acc[6] = max(acc[6], float(d.max())) if d.numel() else acc[6]
+    if d.numel():
+        acc[6] = np.maximum(acc[6], float(d.max()))
 
 
 def emulation_sums(chunk_iter: Iterable, w, formats, bias=None, map_y=None) -> tuple[np.ndarray, int, bool, bool]:
