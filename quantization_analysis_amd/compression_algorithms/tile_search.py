@@ -19,22 +19,12 @@ from typing import Optional
 
 import numpy as np
 
+from ..hip_backend import fmt_mask, mask_formats  # importing hip_backend loads neither torch nor the library
 from .quantizer import Quantizer
 from .tile_utils import MIXED_TILE_FORMATS, flatten_2d, unflatten_2d
 
 TILE = 32
 LAYOUTS = ("rows", "transpose")
-
-
-def fmt_mask(formats) -> int:
-    m = 0
-    for f in formats:
-        m |= 1 << MIXED_TILE_FORMATS.index(f)
-    return m
-
-
-def mask_formats(mask: int) -> list[str]:
-    return [f for i, f in enumerate(MIXED_TILE_FORMATS) if mask & (1 << i)]
 
 
 def slot_of(mask: int, fmt: str) -> int:

@@ -3,10 +3,13 @@
 This module is the ONLY place the package talks to the GPU.  There is no CPU fallback: if the
 shared library is missing, or no HIP device is visible, device entry points raise MtqError.
 PyTorch is used for device memory and streams only (tensor.data_ptr(), current stream).
+SIGNATURES is the one description of the C ABI; the wrappers below are the only callers of the
+library, and each checks what a launch will dereference before it hands a pointer over.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 from pathlib import Path
 
@@ -22,24 +25,78 @@ METRIC_CODE = {"pcc": 0, "mae": 1, "atol": 2}
 DTYPE_BF16, DTYPE_F32 = 0, 1
 TILE = 32
 
-# every symbol include/mtq.h declares (tests check the library exports exactly these)
-EXPORTS = [
-    "mtq_version", "mtq_last_error", "mtq_device_count", "mtq_stats_record_doubles",
-    "mtq_shutdown", "mtq_tile_stats", "mtq_tile_stats_batched", "mtq_tile_stats_partial", "mtq_tile_stats_partial_begin", "mtq_tile_stats_partial_end", "mtq_tile_stats_listed", "mtq_quantize", "mtq_apply_assignment", "mtq_dequant_fp8_block", "mtq_pack_slim_records",
-    "mtq_greedy_create", "mtq_greedy_pass", "mtq_greedy_assignment", "mtq_greedy_fixed",
-    "mtq_greedy_counts", "mtq_greedy_value", "mtq_greedy_destroy",
-    "mtq_tile_scores", "mtq_threshold_assign", "mtq_columns_from_stats", "mtq_columns_from_sums", "mtq_tile_scores_device",
-    "mtq_threshold_assign_device", "mtq_columns_scratch_doubles", "mtq_column_sums_device", "mtq_column_sums_device_batched",
-    "mtq_rng_create", "mtq_rng_permutation", "mtq_rng_integers", "mtq_rng_destroy", "mtq_greedy_run", "mtq_greedy_run_batch",
-    "mtq_selftest_slot_ring", "mtq_device_copy_2d", "mtq_knife_tiles_device", "mtq_greedy_scan_scratch_bytes", "mtq_greedy_scan_device", "mtq_greedy_scan_device_ex", "mtq_scan_carry_bytes",
-    "mtq_scan_orders_bytes", "mtq_scan_orders_device", "mtq_debug_scan_ticks", "mtq_threshold_enqueue", "mtq_threshold_columns",
-    "mtq_tile_stats_ragged", "mtq_knife_tiles_ragged", "mtq_column_sums_device_ragged", "mtq_threshold_enqueue_ragged", "mtq_threshold_columns_ragged",
-    "mtq_tile_stats_transposed", "mtq_quantize_transposed", "mtq_apply_assignment_transposed", "mtq_knife_tiles_transposed",
-    "mtq_threshold_enqueue_transposed", "mtq_output_error_scratch_doubles", "mtq_output_error",
-]
-# found by name, not by MTQ_VERSION: an older build of the same version (an A/B library at MTQ_LIB) lacks them and still loads
-OPTIONAL_EXPORTS = ("mtq_tile_stats_transposed", "mtq_quantize_transposed", "mtq_apply_assignment_transposed", "mtq_knife_tiles_transposed",
-                    "mtq_threshold_enqueue_transposed", "mtq_output_error_scratch_doubles", "mtq_output_error")
+MTQ_VERSION = 143   # include/mtq.h MTQ_VERSION: the oldest library this package binds
+
+# Every function include/mtq.h declares: name → (result, parameters, optional).  One letter per C type class: p pointer or array,
+# l int64_t, u uint32_t, i int, d double, z size_t, q uint64_t; results also v void, s const char *.  Optional symbols are found by
+# name, not by MTQ_VERSION: an older build of the same version (an A/B library at MTQ_LIB) lacks them and still loads.
+SIGNATURES = {
+    "mtq_version": ("i", "", False),
+    "mtq_last_error": ("s", "", False),
+    "mtq_device_count": ("i", "p", False),
+    "mtq_stats_record_doubles": ("z", "u", False),
+    "mtq_shutdown": ("i", "", False),
+    "mtq_tile_stats": ("i", "pilllupp", False),
+    "mtq_tile_stats_batched": ("i", "pilllllupp", False),
+    "mtq_tile_stats_partial": ("i", "pillllluuupp", False),
+    "mtq_tile_stats_partial_begin": ("i", "pillllluuupppp", False),
+    "mtq_tile_stats_partial_end": ("i", "pillllluppup", False),
+    "mtq_tile_stats_listed": ("i", "pillllluuupplppp", False),
+    "mtq_quantize": ("i", "pillliplp", False),
+    "mtq_apply_assignment": ("i", "pilllpplp", False),
+    "mtq_dequant_fp8_block": ("i", "pplllllplp", False),
+    "mtq_pack_slim_records": ("i", "plupp", False),
+    "mtq_greedy_create": ("i", "ppluiddi", False),
+    "mtq_greedy_pass": ("i", "pipl", False),
+    "mtq_greedy_assignment": ("i", "pp", False),
+    "mtq_greedy_fixed": ("i", "pp", False),
+    "mtq_greedy_counts": ("i", "pp", False),
+    "mtq_greedy_value": ("i", "pp", False),
+    "mtq_greedy_destroy": ("v", "p", False),
+    "mtq_tile_scores": ("i", "pluip", False),
+    "mtq_threshold_assign": ("i", "plupiiddppplp", False),
+    "mtq_columns_from_stats": ("i", "plupdp", False),
+    "mtq_columns_from_sums": ("i", "pdp", False),
+    "mtq_tile_scores_device": ("i", "pluipp", False),
+    "mtq_threshold_assign_device": ("i", "plupiiddppp", False),
+    "mtq_columns_scratch_doubles": ("z", "", False),
+    "mtq_column_sums_device": ("i", "pluppp", False),
+    "mtq_column_sums_device_batched": ("i", "plluppp", False),
+    "mtq_rng_create": ("i", "pq", False),
+    "mtq_rng_permutation": ("i", "plp", False),
+    "mtq_rng_integers": ("i", "pllp", False),
+    "mtq_rng_destroy": ("v", "p", False),
+    "mtq_greedy_run": ("i", "plupiiddqppp", False),
+    "mtq_greedy_run_batch": ("i", "pllupiiddppppi", False),
+    "mtq_selftest_slot_ring": ("i", "", False),
+    "mtq_device_copy_2d": ("i", "pzpzzzp", False),
+    "mtq_knife_tiles_device": ("i", "pilllllppilppp", False),
+    "mtq_greedy_scan_scratch_bytes": ("z", "ll", False),
+    "mtq_greedy_scan_device": ("i", "pllupiiddpppppzp", False),
+    "mtq_greedy_scan_device_ex": ("i", "pllupiiddpppppzpipppp", False),
+    "mtq_scan_carry_bytes": ("z", "l", False),
+    "mtq_scan_orders_bytes": ("z", "l", False),
+    "mtq_scan_orders_device": ("i", "qlipzp", False),
+    "mtq_debug_scan_ticks": ("i", "p", False),
+    "mtq_threshold_enqueue": ("i", "pillllluupiiddppplppppppp", False),
+    "mtq_threshold_columns": ("i", "pllupppp", False),
+    "mtq_tile_stats_ragged": ("i", "piiupp", False),
+    "mtq_knife_tiles_ragged": ("i", "piippilppp", False),
+    "mtq_column_sums_device_ragged": ("i", "ppiuppp", False),
+    "mtq_threshold_enqueue_ragged": ("i", "piiuupiiddppplppppppp", False),
+    "mtq_threshold_columns_ragged": ("i", "ppiupppp", False),
+    "mtq_tile_stats_transposed": ("i", "pilllllupp", True),
+    "mtq_quantize_transposed": ("i", "pillliplp", True),
+    "mtq_apply_assignment_transposed": ("i", "pilllllpplp", True),
+    "mtq_knife_tiles_transposed": ("i", "pilllllppilppp", True),
+    "mtq_threshold_enqueue_transposed": ("i", "pillllluupiiddppplppppppp", True),
+    "mtq_output_error_scratch_doubles": ("z", "ll", True),
+    "mtq_output_error": ("i", "plllpillpuppilppzp", True),
+}
+EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
+OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
+_CTYPE = {"p": ctypes.c_void_p, "l": ctypes.c_int64, "u": ctypes.c_uint32, "i": ctypes.c_int, "d": ctypes.c_double, "z": ctypes.c_size_t,
+          "q": ctypes.c_uint64, "v": None, "s": ctypes.c_char_p}
 
 
 class MtqError(RuntimeError):
@@ -47,6 +104,7 @@ class MtqError(RuntimeError):
 
 
 _lib = None
+_REBUILD = f"rebuild it from this tree (`make -C {_PKG / 'csrc'}`)"
 
 
 def build(force: bool = False) -> Path:
@@ -74,83 +132,7 @@ def lib() -> ctypes.CDLL:
     import torch  # noqa: F401
 
     L = ctypes.CDLL(str(LIB_PATH))
-    vp, i64, u32, ci, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double
-    L.mtq_version.restype = ci
-    L.mtq_last_error.restype = ctypes.c_char_p
-    L.mtq_device_count.argtypes = [ctypes.POINTER(ci)]
-    L.mtq_stats_record_doubles.argtypes = [u32]
-    L.mtq_stats_record_doubles.restype = ctypes.c_size_t
-    L.mtq_tile_stats.argtypes = [vp, ci, i64, i64, i64, u32, vp, vp]
-    L.mtq_tile_stats_batched.argtypes = [vp, ci, i64, i64, i64, i64, i64, u32, vp, vp]
-    L.mtq_tile_stats_partial.argtypes = [vp, ci, i64, i64, i64, i64, i64, u32, u32, u32, vp, vp]
-    L.mtq_tile_stats_partial_begin.argtypes = [vp, ci, i64, i64, i64, i64, i64, u32, u32, u32, vp, vp, ctypes.POINTER(u32), vp]
-    L.mtq_tile_stats_partial_end.argtypes = [vp, ci, i64, i64, i64, i64, i64, u32, vp, vp, u32, vp]
-    L.mtq_quantize.argtypes = [vp, ci, i64, i64, i64, ci, vp, i64, vp]
-    L.mtq_apply_assignment.argtypes = [vp, ci, i64, i64, i64, vp, vp, i64, vp]
-    L.mtq_dequant_fp8_block.argtypes = [vp, vp, i64, i64, i64, i64, i64, vp, i64, vp]
-    L.mtq_greedy_create.argtypes = [ctypes.POINTER(vp), vp, i64, u32, ci, dbl, dbl, ci]
-    L.mtq_greedy_pass.argtypes = [vp, ci, vp, i64]
-    L.mtq_greedy_assignment.argtypes = [vp, vp]
-    L.mtq_greedy_fixed.argtypes = [vp, vp]
-    L.mtq_greedy_counts.argtypes = [vp, vp]
-    L.mtq_greedy_value.argtypes = [vp, ctypes.POINTER(dbl)]
-    L.mtq_greedy_destroy.argtypes = [vp]
-    L.mtq_greedy_destroy.restype = None
-    L.mtq_tile_scores.argtypes = [vp, i64, u32, ci, vp]
-    L.mtq_threshold_assign.argtypes = [vp, i64, u32, vp, ci, ci, dbl, dbl, vp, vp, vp, i64, ctypes.POINTER(i64)]
-    L.mtq_columns_from_stats.argtypes = [vp, i64, u32, vp, dbl, vp]
-    L.mtq_columns_from_sums.argtypes = [vp, dbl, vp]
-    L.mtq_pack_slim_records.argtypes = [vp, i64, u32, vp, vp]
-    L.mtq_tile_scores_device.argtypes = [vp, i64, u32, ci, vp, vp]
-    L.mtq_threshold_assign_device.argtypes = [vp, i64, u32, vp, ci, ci, dbl, dbl, vp, vp, vp]
-    L.mtq_columns_scratch_doubles.argtypes = []
-    L.mtq_columns_scratch_doubles.restype = ctypes.c_size_t
-    L.mtq_column_sums_device.argtypes = [vp, i64, u32, vp, vp, vp]
-    L.mtq_column_sums_device_batched.argtypes = [vp, i64, i64, u32, vp, vp, vp]
-    L.mtq_rng_create.argtypes = [ctypes.POINTER(vp), ctypes.c_uint64]
-    L.mtq_rng_permutation.argtypes = [vp, i64, vp]
-    L.mtq_rng_integers.argtypes = [vp, i64, i64, vp]
-    L.mtq_rng_destroy.argtypes = [vp]
-    L.mtq_rng_destroy.restype = None
-    L.mtq_greedy_run.argtypes = [vp, i64, u32, vp, ci, ci, dbl, dbl, ctypes.c_uint64, vp, vp, vp]
-    L.mtq_greedy_run_batch.argtypes = [vp, i64, i64, u32, vp, ci, ci, dbl, dbl, vp, vp, vp, vp, ci]
-    L.mtq_greedy_scan_scratch_bytes.argtypes = [i64, i64]
-    L.mtq_greedy_scan_scratch_bytes.restype = ctypes.c_size_t
-    L.mtq_greedy_scan_device.argtypes = [vp, i64, i64, u32, vp, ci, ci, dbl, dbl, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    L.mtq_greedy_scan_device_ex.argtypes = [vp, i64, i64, u32, vp, ci, ci, dbl, dbl, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, ci, vp, vp, vp, vp]
-    L.mtq_scan_carry_bytes.argtypes = [i64]
-    L.mtq_scan_carry_bytes.restype = ctypes.c_size_t
-    L.mtq_scan_orders_bytes.argtypes = [i64]
-    L.mtq_scan_orders_bytes.restype = ctypes.c_size_t
-    L.mtq_scan_orders_device.argtypes = [ctypes.c_uint64, i64, ci, vp, ctypes.c_size_t, vp]
-    L.mtq_tile_stats_listed.argtypes = [vp, ci, i64, i64, i64, i64, i64, u32, u32, u32, vp, vp, i64, vp, vp, vp]
-    L.mtq_shutdown.restype = ci
-    L.mtq_selftest_slot_ring.restype = ci
-    L.mtq_device_copy_2d.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp]
-    L.mtq_knife_tiles_device.argtypes = [vp, ci, i64, i64, i64, i64, i64, vp, vp, ci, i64, vp, vp, vp]
-    L.mtq_threshold_enqueue.argtypes = [vp, ci, i64, i64, i64, i64, i64, u32, u32, vp, ci, ci, dbl, dbl, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.mtq_threshold_columns.argtypes = [vp, i64, i64, u32, vp, vp, vp, vp]
-    L.mtq_tile_stats_ragged.argtypes = [vp, ci, ci, u32, vp, vp]
-    L.mtq_knife_tiles_ragged.argtypes = [vp, ci, ci, vp, vp, ci, i64, vp, vp, vp]
-    L.mtq_column_sums_device_ragged.argtypes = [vp, vp, ci, u32, vp, vp, vp]
-    L.mtq_threshold_enqueue_ragged.argtypes = [vp, ci, ci, u32, u32, vp, ci, ci, dbl, dbl, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.mtq_threshold_columns_ragged.argtypes = [vp, vp, ci, u32, vp, vp, vp, vp]
-    if hasattr(L, "mtq_tile_stats_transposed"):
-        L.mtq_tile_stats_transposed.argtypes = [vp, ci, i64, i64, i64, i64, i64, u32, vp, vp]
-    if hasattr(L, "mtq_quantize_transposed"):
-        L.mtq_quantize_transposed.argtypes = [vp, ci, i64, i64, i64, ci, vp, i64, vp]
-    if hasattr(L, "mtq_apply_assignment_transposed"):
-        L.mtq_apply_assignment_transposed.argtypes = [vp, ci, i64, i64, i64, i64, i64, vp, vp, i64, vp]
-    if hasattr(L, "mtq_knife_tiles_transposed"):
-        L.mtq_knife_tiles_transposed.argtypes = [vp, ci, i64, i64, i64, i64, i64, vp, vp, ci, i64, vp, vp, vp]
-    if hasattr(L, "mtq_threshold_enqueue_transposed"):
-        L.mtq_threshold_enqueue_transposed.argtypes = L.mtq_threshold_enqueue.argtypes
-    if hasattr(L, "mtq_output_error"):
-        L.mtq_output_error_scratch_doubles.argtypes = [i64, i64]
-        L.mtq_output_error_scratch_doubles.restype = ctypes.c_size_t
-        L.mtq_output_error.argtypes = [vp, i64, i64, i64, vp, ci, i64, i64, vp, u32, vp, vp, ci, i64, vp, vp, ctypes.c_size_t, vp]
-    if L.mtq_version() < 141:
-        raise MtqError("libmtq_hip.so is older than this package")
+    _bind(L)
     _lib = L
     # torch registered its exit hooks when it was imported above; a hook registered now runs BEFORE them: the library's threads,
     # events and device tables are released while the HIP runtime is still there (mtq_shutdown; nothing is left to static destructors)
@@ -158,6 +140,25 @@ def lib() -> ctypes.CDLL:
 
     atexit.register(shutdown)
     return L
+
+
+def _bind(L) -> None:
+    """Sets every symbol's result and parameter types from SIGNATURES, the version first: an older library fails with its version,
+    not with the first symbol it lacks."""
+    version = getattr(L, "mtq_version", None)
+    if version is None:
+        raise MtqError(f"{LIB_PATH} has no mtq_version: {_REBUILD}")
+    version.restype, version.argtypes = ctypes.c_int, []
+    found = version()
+    if found < MTQ_VERSION:
+        raise MtqError(f"{LIB_PATH} is version {found}, older than this package (it needs {MTQ_VERSION}): {_REBUILD}")
+    for name, (result, params, optional) in SIGNATURES.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            if optional:
+                continue
+            raise MtqError(f"{LIB_PATH} has no {name}: {_REBUILD}")
+        fn.restype, fn.argtypes = _CTYPE[result], [_CTYPE[c] for c in params]
 
 
 def shutdown() -> None:
@@ -272,13 +273,59 @@ def _stream_ptr() -> int:
     return _torch().cuda.current_stream().cuda_stream
 
 
+def _matrix(x, ranks=(2, 3)):
+    """The checks before a matrix pointer is taken, in the order rank, contiguous rows, storage type, device (the first three need no
+    device) → (storage code, count, stride_elems, rows, cols, ld) of a (rows, cols) or (count, rows, cols) tensor; a 2-D tensor is a
+    batch of one.  ld and stride_elems of a single row or matrix are what the kernels' bounds and alignment checks expect."""
+    if x.dim() not in ranks:
+        raise MtqError(f"expected a {' or '.join(f'{d}-D' for d in ranks)} device tensor, got {x.dim()}-D")
+    if x.stride(-1) != 1:
+        raise MtqError("expected a device tensor with contiguous rows (stride(-1) == 1)")
+    code = _dtype_code(x)
+    if not x.is_cuda:
+        raise MtqError("expected a device tensor (the hip backend has no CPU fallback)")
+    count, rows, cols = x.shape if x.dim() == 3 else (1, *x.shape)
+    ld = x.stride(-2) if rows > 1 else max(x.stride(-2), cols)
+    return code, count, x.stride(0) if count > 1 else rows * ld, rows, cols, ld
+
+
+def _contiguous_batch(x3d):
+    """_matrix of a contiguous (count, rows, cols) device tensor."""
+    m = _matrix(x3d, (3,))
+    if not x3d.is_contiguous():
+        raise MtqError("expected a contiguous (count, rows, cols) device tensor")
+    return m
+
+
 def _as_device_matrix(t):
-    """2-D, last-dim-contiguous device tensor → (tensor, rows, cols, ld)."""
-    if t.dim() != 2 or not t.is_cuda:
-        raise MtqError("expected a 2-D device tensor (use to_device_2d for host / N-D input)")
-    if t.stride(1) != 1:
-        t = t.contiguous()
-    return t, t.shape[0], t.shape[1], t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    """2-D device tensor → (tensor with contiguous rows, storage code, rows, cols, ld); other inner strides are copied.  A single
+    column's stride means nothing (contiguous() keeps it, e.g. on the transpose of one row): it is set to 1 in place."""
+    if t.dim() == 2 and t.stride(1) != 1:
+        t = t.contiguous() if t.shape[1] > 1 else t.as_strided(t.shape, (t.stride(0), 1))
+    code, _count, _stride, rows, cols, ld = _matrix(t, (2,))
+    return t, code, rows, cols, ld
+
+
+def _buffer(t, dtype, numel: int, name: str, device: bool = True) -> int:
+    """The pointer of a buffer a launch reads or writes numel elements of, after checking it can: dtype, contiguity, size (a lower
+    bound: callers pass views of grow-only storage) and, unless it is a host mirror, that it is device memory."""
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < numel or (device and not t.is_cuda):
+        raise MtqError(f"{name} must be a contiguous {dtype} {'device ' if device else ''}tensor of at least {numel} elements")
+    return t.data_ptr()
+
+
+def _stream(s):
+    """The HIP handle of a torch stream; None is the null stream."""
+    return None if s is None else s.cuda_stream
+
+
+def _format_codes(formats):
+    return (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats])
+
+
+def _columns(out) -> dict:
+    """The columns of mtq_columns_from_sums' nine doubles."""
+    return {"pcc": out[0], "mae": out[1], "atol": out[2], "sums": tuple(out[3:9])}
 
 
 def to_device_2d(x, device=None):
@@ -321,12 +368,12 @@ def tile_stats(x2d, mask: int, out=None):
     """K1 on a 2-D device tensor → device float64 [tiles, 2+5F] (async on the current stream)."""
     torch = _torch()
     require_gpu()
-    x2d, rows, cols, ld = _as_device_matrix(x2d)
+    x2d, code, rows, cols, ld = _as_device_matrix(x2d)
     th, tw = tiles_hw(rows, cols)
     rec = record_doubles(mask)
     if out is None:
         out = torch.empty((th * tw, rec), dtype=torch.float64, device=x2d.device)
-    check(lib().mtq_tile_stats(x2d.data_ptr(), _dtype_code(x2d), rows, cols, ld, mask, out.data_ptr(), _stream_ptr()))
+    check(lib().mtq_tile_stats(x2d.data_ptr(), code, rows, cols, ld, mask, out.data_ptr(), _stream_ptr()))
     return out
 
 
@@ -334,15 +381,12 @@ def tile_stats_batched(x3d, mask: int, out=None):
     """K1 over a (count, rows, cols) contiguous device tensor in one launch → [count, tiles, rec]."""
     torch = _torch()
     require_gpu()
-    if x3d.dim() != 3 or not x3d.is_cuda or not x3d.is_contiguous():
-        raise MtqError("expected a contiguous (count, rows, cols) device tensor")
-    count, rows, cols = x3d.shape
+    code, count, stride, rows, cols, ld = _contiguous_batch(x3d)
     th, tw = tiles_hw(rows, cols)
     rec = record_doubles(mask)
     if out is None:
         out = torch.empty((count, th * tw, rec), dtype=torch.float64, device=x3d.device)
-    check(lib().mtq_tile_stats_batched(x3d.data_ptr(), _dtype_code(x3d), count, rows * cols, rows, cols, cols, mask,
-                                       out.data_ptr(), _stream_ptr()))
+    check(lib().mtq_tile_stats_batched(x3d.data_ptr(), code, count, stride, rows, cols, ld, mask, out.data_ptr(), _stream_ptr()))
     return out
 
 
@@ -356,17 +400,17 @@ class MtqMatrix(ctypes.Structure):
 
 def ragged_matrices(mats):
     """(MtqMatrix array, storage code, tiles per matrix) of 2-D device tensors of one storage type with contiguous rows."""
-    require_gpu()
     if not 0 < len(mats) <= RAGGED_MAX:
         raise MtqError(f"a ragged batch holds 1..{RAGGED_MAX} matrices")
-    code = _dtype_code(mats[0])
     arr = (MtqMatrix * len(mats))()
-    tiles = []
+    codes, tiles = set(), []
     for j, m in enumerate(mats):
-        if m.dim() != 2 or not m.is_cuda or m.stride(1) != 1 or _dtype_code(m) != code or m.device != mats[0].device:
+        code, _count, _stride, rows, cols, ld = _matrix(m, (2,))
+        codes.add(code)
+        if len(codes) > 1 or m.device != mats[0].device:
             raise MtqError("a ragged batch is 2-D tensors of one storage type on one device with contiguous rows")
-        arr[j] = MtqMatrix(m.data_ptr(), m.shape[0], m.shape[1], m.stride(0))
-        th, tw = tiles_hw(m.shape[0], m.shape[1])
+        arr[j] = MtqMatrix(m.data_ptr(), rows, cols, ld)
+        th, tw = tiles_hw(rows, cols)
         tiles.append(th * tw)
     return arr, code, tiles
 
@@ -375,6 +419,7 @@ def tile_stats_ragged(mats, mask: int, out=None):
     """K1 over matrices of ANY shapes (one storage type) in one launch (mtq_tile_stats_ragged) → [sum of their tiles, rec], matrix j's
     tiles row-major behind matrix j-1's."""
     torch = _torch()
+    require_gpu()
     arr, code, tiles = ragged_matrices(mats)
     if out is None:
         out = torch.empty((sum(tiles), record_doubles(mask)), dtype=torch.float64, device=mats[0].device)
@@ -387,13 +432,11 @@ def tile_stats_partial(x3d, layout_mask: int, full_mask: int, sums_mask: int, ou
     the formats in full_mask, Σy, Σy², Σxy of those in sums_mask; the rest of the layout is unspecified → [count, tiles, rec(layout)]."""
     torch = _torch()
     require_gpu()
-    if x3d.dim() != 3 or not x3d.is_cuda or not x3d.is_contiguous():
-        raise MtqError("expected a contiguous (count, rows, cols) device tensor")
-    count, rows, cols = x3d.shape
+    code, count, stride, rows, cols, ld = _contiguous_batch(x3d)
     th, tw = tiles_hw(rows, cols)
     if out is None:
         out = torch.empty((count, th * tw, record_doubles(layout_mask)), dtype=torch.float64, device=x3d.device)
-    check(lib().mtq_tile_stats_partial(x3d.data_ptr(), _dtype_code(x3d), count, rows * cols, rows, cols, cols, layout_mask, full_mask, sums_mask,
+    check(lib().mtq_tile_stats_partial(x3d.data_ptr(), code, count, stride, rows, cols, ld, layout_mask, full_mask, sums_mask,
                                        out.data_ptr(), _stream_ptr()))
     return out
 
@@ -401,17 +444,17 @@ def tile_stats_partial(x3d, layout_mask: int, full_mask: int, sums_mask: int, ou
 def tile_stats_partial_begin(x3d, layout_mask: int, full_mask: int, sums_mask: int, out, mark) -> int:
     """mtq_tile_stats_partial_begin on the current stream (the exact-integer kernel alone) → the launch id tile_stats_partial_end wants.
     mark: int32 device tensor of one element that stays the caller's until _end has run."""
-    count, rows, cols = x3d.shape
+    code, count, stride, rows, cols, ld = _contiguous_batch(x3d)
     lid = ctypes.c_uint32(0)
-    check(lib().mtq_tile_stats_partial_begin(x3d.data_ptr(), _dtype_code(x3d), count, rows * cols, rows, cols, cols, layout_mask, full_mask, sums_mask,
+    check(lib().mtq_tile_stats_partial_begin(x3d.data_ptr(), code, count, stride, rows, cols, ld, layout_mask, full_mask, sums_mask,
                                              out.data_ptr(), mark.data_ptr(), ctypes.byref(lid), _stream_ptr()))
     return int(lid.value)
 
 
 def tile_stats_partial_end(x3d, layout_mask: int, stats, mark, launch_id: int) -> None:
     """mtq_tile_stats_partial_end on the current stream: the literal fix-up of the tiles that launch could not take (usually none)."""
-    count, rows, cols = x3d.shape
-    check(lib().mtq_tile_stats_partial_end(x3d.data_ptr(), _dtype_code(x3d), count, rows * cols, rows, cols, cols, layout_mask, stats.data_ptr(),
+    code, count, stride, rows, cols, ld = _contiguous_batch(x3d)
+    check(lib().mtq_tile_stats_partial_end(x3d.data_ptr(), code, count, stride, rows, cols, ld, layout_mask, stats.data_ptr(),
                                            mark.data_ptr(), int(launch_id), _stream_ptr()))
 
 
@@ -421,66 +464,51 @@ def quantize(x2d, fmt: str, out=None):
     require_gpu()
     if fmt not in FMT_CODE:
         raise ValueError(f"Unsupported weight format: {fmt}")
-    x2d, rows, cols, ld = _as_device_matrix(x2d)
+    x2d, code, rows, cols, ld = _as_device_matrix(x2d)
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.float32, device=x2d.device)
-    check(lib().mtq_quantize(x2d.data_ptr(), _dtype_code(x2d), rows, cols, ld, FMT_CODE[fmt], out.data_ptr(), out.stride(0), _stream_ptr()))
+    check(lib().mtq_quantize(x2d.data_ptr(), code, rows, cols, ld, FMT_CODE[fmt], out.data_ptr(), out.stride(0), _stream_ptr()))
     return out
 
 
-def _transposed_entry(name: str):
+def _entry(name: str):
+    """An optional symbol of the library (SIGNATURES), or MtqError if this build lacks it."""
     fn = getattr(lib(), name, None)
     if fn is None:
-        raise MtqError(f"{LIB_PATH} has no {name}: rebuild it from this tree (`make -C {_PKG / 'csrc'}`)")
+        raise MtqError(f"{LIB_PATH} has no {name}: {_REBUILD}")
     return fn
 
 
-def _check_transposed_input(x, dims: tuple) -> None:
-    """The checks the transposed entry points need before a pointer is taken: device tensor, rank, contiguous rows, storage type."""
-    torch = _torch()
-    if not getattr(x, "is_cuda", False):
-        raise MtqError("expected a device tensor (the hip backend has no CPU fallback)")
-    if x.dim() not in dims:
-        raise MtqError(f"expected a {' or '.join(f'{d}-D' for d in dims)} device tensor, got {x.dim()}-D")
-    if x.stride(-1) != 1:
-        raise MtqError("expected contiguous rows (stride(-1) == 1)")
-    if x.dtype not in (torch.bfloat16, torch.float32):
-        raise MtqError(f"hip backend takes bfloat16 or float32 tensors, got {x.dtype}")
+_transposed_entry = _entry   # its earlier name, which the tests of the optional symbols still use
 
 
 def tile_stats_transposed(x, mask: int, out=None):
     """K1T (mtq_tile_stats_transposed) on the current stream: the K1 records of Xᵀ for a (rows, cols) or (count, rows, cols) device tensor X
     with contiguous rows, read in place → float64 [tiles] / [count, tiles] × rec, tiles numbered row-major over Xᵀ's grid
     (element (r, c) of X in tile (c // 32) * ceil(rows / 32) + r // 32)."""
-    _check_transposed_input(x, (2, 3))
+    code, count, stride, rows, cols, ld = _matrix(x)
     torch = _torch()
     require_gpu()
-    fn = _transposed_entry("mtq_tile_stats_transposed")
-    x3 = x if x.dim() == 3 else x[None]
-    count, rows, cols = x3.shape
-    ld = x3.stride(1) if rows > 1 else max(x3.stride(1), cols)
-    stride = x3.stride(0) if count > 1 else 0
+    fn = _entry("mtq_tile_stats_transposed")
     th_t, tw_t = tiles_hw(cols, rows)
     rec = record_doubles(mask)
     if out is None:
         out = torch.empty((count, th_t * tw_t, rec), dtype=torch.float64, device=x.device)
-    check(fn(x3.data_ptr(), _dtype_code(x3), count, stride, rows, cols, ld, mask, out.data_ptr(), _stream_ptr()))
+    check(fn(x.data_ptr(), code, count, stride, rows, cols, ld, mask, out.data_ptr(), _stream_ptr()))
     return out if x.dim() == 3 else out[0]
 
 
 def quantize_transposed(x2d, fmt: str, out=None):
     """K2T (mtq_quantize_transposed) on the current stream: (K2 of Xᵀ)ᵀ for a 2-D device tensor with contiguous rows → float32, X's shape."""
-    _check_transposed_input(x2d, (2,))
+    code, _count, _stride, rows, cols, ld = _matrix(x2d, (2,))
     torch = _torch()
     if fmt not in FMT_CODE:
         raise ValueError(f"Unsupported weight format: {fmt}")
     require_gpu()
-    fn = _transposed_entry("mtq_quantize_transposed")
-    rows, cols = x2d.shape
-    ld = x2d.stride(0) if rows > 1 else max(x2d.stride(0), cols)
+    fn = _entry("mtq_quantize_transposed")
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.float32, device=x2d.device)
-    check(fn(x2d.data_ptr(), _dtype_code(x2d), rows, cols, ld, FMT_CODE[fmt], out.data_ptr(), out.stride(0), _stream_ptr()))
+    check(fn(x2d.data_ptr(), code, rows, cols, ld, FMT_CODE[fmt], out.data_ptr(), out.stride(0), _stream_ptr()))
     return out
 
 
@@ -488,14 +516,10 @@ def apply_assignment_transposed(x, assignment, out=None):
     """K3T (mtq_apply_assignment_transposed) on the current stream: (K3 of Xᵀ with `assignment`)ᵀ for a (rows, cols) or (count, rows, cols)
     device tensor X with contiguous rows, read in place → float32, X's shape.  assignment: int8 numpy array or device tensor with
     ceil(cols / 32) × ceil(rows / 32) entries per matrix (Xᵀ's grid, K1T's numbering)."""
-    _check_transposed_input(x, (2, 3))
+    code, count, stride, rows, cols, ld = _matrix(x)
     torch = _torch()
     require_gpu()
-    fn = _transposed_entry("mtq_apply_assignment_transposed")
-    x3 = x if x.dim() == 3 else x[None]
-    count, rows, cols = x3.shape
-    ld = x3.stride(1) if rows > 1 else max(x3.stride(1), cols)
-    stride = x3.stride(0) if count > 1 else 0
+    fn = _entry("mtq_apply_assignment_transposed")
     th_t, tw_t = tiles_hw(cols, rows)
     if isinstance(assignment, np.ndarray):
         assignment = torch.from_numpy(np.ascontiguousarray(assignment, dtype=np.int8)).to(x.device)
@@ -506,7 +530,7 @@ def apply_assignment_transposed(x, assignment, out=None):
         out = torch.empty((count, rows, cols), dtype=torch.float32, device=x.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (count, rows, cols) or not out.is_contiguous() or out.device != x.device:
         raise MtqError("out must be a contiguous float32 device tensor of X's shape")
-    check(fn(x3.data_ptr(), _dtype_code(x3), count, stride, rows, cols, ld, a.data_ptr(), out.data_ptr(), cols, _stream_ptr()))
+    check(fn(x.data_ptr(), code, count, stride, rows, cols, ld, a.data_ptr(), out.data_ptr(), cols, _stream_ptr()))
     return out if x.dim() == 3 else out[0]
 
 
@@ -520,16 +544,13 @@ def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded
     float32 or None.  scratch: float64 device tensor of at least output_error_scratch(m, n) elements (allocated when None)."""
     torch = _torch()
     require_gpu()
-    fn = _transposed_entry("mtq_output_error")
-    for name, t in (("x", x), ("w", w)):
-        if not getattr(t, "is_cuda", False) or t.dim() != 2 or t.stride(-1) != 1:
-            raise MtqError(f"{name}: expected a 2-D device tensor with contiguous rows")
+    fn = _entry("mtq_output_error")
+    _code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    w_code, _count, _stride, n, kw, ldw = _matrix(w, (2,))
     if x.dtype != torch.bfloat16:
         raise MtqError(f"x must be bfloat16, got {x.dtype}")
-    m, k = int(x.shape[0]), int(x.shape[1])
-    n = int(w.shape[0])
-    if int(w.shape[1]) != k:
-        raise MtqError(f"x has {k} columns, w has {int(w.shape[1])}")
+    if kw != k:
+        raise MtqError(f"x has {k} columns, w has {kw}")
     if sums.dtype != torch.float64 or tuple(sums.shape) != (len(OE_SLOTS), 7) or not sums.is_contiguous() or not sums.is_cuda:
         raise MtqError("sums must be a contiguous float64 device tensor of shape (7, 7)")
     bp = 0
@@ -545,29 +566,30 @@ def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded
         mp = assignment.data_ptr()
     rp, rdt, ldr = 0, 0, 0
     if recorded is not None:
-        if tuple(recorded.shape) != (m, n) or recorded.stride(-1) != 1 or not recorded.is_cuda:
+        rdt, _count, _stride, rm, rn, ldr = _matrix(recorded, (2,))
+        if (rm, rn) != (m, n):
             raise MtqError(f"recorded must be a ({m}, {n}) device tensor with contiguous rows")
-        rp, rdt, ldr = recorded.data_ptr(), _dtype_code(recorded), int(recorded.stride(0))
+        rp = recorded.data_ptr()
     need = output_error_scratch(m, n)
     if scratch is None:
         scratch = torch.empty((need,), dtype=torch.float64, device=x.device)
     elif scratch.numel() < need:
         raise MtqError(f"scratch holds {scratch.numel()} doubles, the launch needs {need}")
-    check(fn(x.data_ptr(), m, k, int(x.stride(0)), w.data_ptr(), _dtype_code(w), n, int(w.stride(0)), bp, fmt_mask, mp, rp, rdt, ldr,
+    check(fn(x.data_ptr(), m, k, ldx, w.data_ptr(), w_code, n, ldw, bp, fmt_mask, mp, rp, rdt, ldr,
              sums.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream_ptr()))
     return sums
 
 
 def output_error_scratch(m: int, n: int) -> int:
     """Doubles of scratch one mtq_output_error launch over m × n outputs needs."""
-    return int(_transposed_entry("mtq_output_error_scratch_doubles")(m, n))
+    return int(_entry("mtq_output_error_scratch_doubles")(m, n))
 
 
 def apply_assignment(x2d, assignment, out=None):
     """K3: assignment is an int8 (tiles_h, tiles_w) numpy array or device tensor."""
     torch = _torch()
     require_gpu()
-    x2d, rows, cols, ld = _as_device_matrix(x2d)
+    x2d, code, rows, cols, ld = _as_device_matrix(x2d)
     th, tw = tiles_hw(rows, cols)
     if isinstance(assignment, np.ndarray):
         assignment = torch.from_numpy(np.ascontiguousarray(assignment, dtype=np.int8)).to(x2d.device)
@@ -576,7 +598,7 @@ def apply_assignment(x2d, assignment, out=None):
         raise MtqError(f"assignment has {a.numel()} entries, tensor has {th}x{tw} tiles")
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.float32, device=x2d.device)
-    check(lib().mtq_apply_assignment(x2d.data_ptr(), _dtype_code(x2d), rows, cols, ld, a.data_ptr(), out.data_ptr(), out.stride(0), _stream_ptr()))
+    check(lib().mtq_apply_assignment(x2d.data_ptr(), code, rows, cols, ld, a.data_ptr(), out.data_ptr(), out.stride(0), _stream_ptr()))
     return out
 
 
@@ -673,13 +695,13 @@ def greedy_run(stats: np.ndarray, mask: int, formats, metric: str, threshold: fl
     """H1 end to end in one GIL-free call → (int8[T] map, counts dict, columns dict)."""
     stats = np.ascontiguousarray(stats, dtype=np.float64)
     T = stats.shape[0]
-    fm = (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats])
+    fm = _format_codes(formats)
     amap = np.empty(T, dtype=np.int8)
     counts = (ctypes.c_int64 * 4)()
     out = (ctypes.c_double * 9)()
     check(lib().mtq_greedy_run(stats.ctypes.data, T, mask, fm, len(formats), METRIC_CODE[metric], float(threshold),
                                float(elem_count), int(seed), amap.ctypes.data, counts, out))
-    return amap, {f: int(counts[i]) for i, f in enumerate(MIXED_TILE_FORMATS)}, {"pcc": out[0], "mae": out[1], "atol": out[2], "sums": tuple(out[3:9])}
+    return amap, {f: int(counts[i]) for i, f in enumerate(MIXED_TILE_FORMATS)}, _columns(out)
 
 
 SCAN_DEVICE_MAX_TILES = 1 << 22
@@ -728,10 +750,10 @@ def greedy_scan_device(stats_dev, mask: int, formats, metric: str, threshold: fl
     status) device tensors, asynchronous on the current stream.  seeds_dev: uint64/int64 device tensor [count]."""
     torch = _torch()
     count, T = int(stats_dev.shape[0]), int(stats_dev.shape[1])
-    fm = (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats])
+    fm = _format_codes(formats)
     maps = maps_out if maps_out is not None else torch.empty((count, T), dtype=torch.int8, device=stats_dev.device)
     status = status_out if status_out is not None else torch.empty((count,), dtype=torch.int32, device=stats_dev.device)
-    need = int(lib().mtq_greedy_scan_scratch_bytes(count, T))
+    need = greedy_scan_scratch_bytes(count, T)
     if scratch is None:
         scratch = torch.empty((need,), dtype=torch.uint8, device=stats_dev.device)
     elif scratch.numel() < need:   # a caller's slicing bug must not turn into a device allocation per call
@@ -762,10 +784,10 @@ def greedy_scan_device_ex(stats_dev, mask: int, formats, metric: str, threshold:
     tensors share) and / or in phases (1: every pass but the last + the last pass's candidates → listed / n_listed, state → carry;
     2: the last pass).  Caller-owned buffers throughout; scratch must hold mtq_greedy_scan_scratch_bytes(count, tiles) bytes."""
     count, T = int(stats_dev.shape[0]), int(stats_dev.shape[1])
-    need = int(lib().mtq_greedy_scan_scratch_bytes(count, T))
+    need = greedy_scan_scratch_bytes(count, T)
     if scratch.numel() < need:
         raise ValueError("scratch is smaller than mtq_greedy_scan_scratch_bytes()")
-    fm = (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats])
+    fm = _format_codes(formats)
     check(lib().mtq_greedy_scan_device_ex(stats_dev.data_ptr(), count, T, mask, fm, len(formats), METRIC_CODE[metric], float(threshold), float(elem_count),
                                           seeds_dev.data_ptr(), maps_out.data_ptr(), status_out.data_ptr(),
                                           counts_out.data_ptr() if counts_out is not None else None, scratch.data_ptr(), int(scratch.numel()),
@@ -779,10 +801,8 @@ def tile_stats_listed(x3d, layout_mask: int, full_mask: int, err_mask: int, list
     statistics of full_mask's formats and Σ|x−y|, max|x−y| of err_mask's, into stats [count, tiles, rec(layout)] in place.  scratch:
     int32 device tensor of listed.numel() + 1 entries (lets bf16 input take the exact-integer kernel), or None."""
     require_gpu()
-    if x3d.dim() != 3 or not x3d.is_cuda or not x3d.is_contiguous():
-        raise MtqError("expected a contiguous (count, rows, cols) device tensor")
-    count, rows, cols = x3d.shape
-    check(lib().mtq_tile_stats_listed(x3d.data_ptr(), _dtype_code(x3d), count, rows * cols, rows, cols, cols, layout_mask, full_mask, err_mask,
+    code, count, stride, rows, cols, ld = _contiguous_batch(x3d)
+    check(lib().mtq_tile_stats_listed(x3d.data_ptr(), code, count, stride, rows, cols, ld, layout_mask, full_mask, err_mask,
                                       listed.data_ptr(), n_listed.data_ptr(), int(listed.numel()),
                                       scratch.data_ptr() if scratch is not None else None, stats.data_ptr(), _stream_ptr()))
 
@@ -792,7 +812,7 @@ def greedy_run_batch(stats: np.ndarray, mask: int, formats, metric: str, thresho
     → (int8 [count, tiles] maps, int64 [count, 4] counts, float64 [count, 9] columns+sums)."""
     stats = np.ascontiguousarray(stats, dtype=np.float64)
     count, T = stats.shape[0], stats.shape[1]
-    fm = (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats])
+    fm = _format_codes(formats)
     sd = np.ascontiguousarray(seeds, dtype=np.uint64)
     maps = np.empty((count, T), dtype=np.int8)
     counts = np.empty((count, 4), dtype=np.int64)
@@ -802,11 +822,15 @@ def greedy_run_batch(stats: np.ndarray, mask: int, formats, metric: str, thresho
     return maps, counts, outs
 
 
+def _score_rows(mask: int) -> int:
+    """Rows of mtq_tile_scores' output: one per format of the mask, the identity bf16 (first) included."""
+    return bin(mask & 0xF).count("1") + (1 if (mask & MASK_BF16_IDENTITY) and not (mask & 1) else 0)
+
+
 def tile_scores(stats: np.ndarray, mask: int, metric: str) -> np.ndarray:
     stats = np.ascontiguousarray(stats, dtype=np.float64)
     T = stats.shape[0]
-    rows = bin(mask & 0xF).count("1") + (1 if (mask & MASK_BF16_IDENTITY) and not (mask & 1) else 0)  # identity bf16 comes first
-    out = np.empty((rows, T), dtype=np.float64)
+    out = np.empty((_score_rows(mask), T), dtype=np.float64)
     check(lib().mtq_tile_scores(stats.ctypes.data, T, mask, METRIC_CODE[metric], out.ctypes.data))
     return out
 
@@ -815,7 +839,7 @@ def threshold_assign(stats: np.ndarray, mask: int, formats, metric: str, thresho
     """K4 on host stats → (int8[T] map, knife-edge tile ids[, uint8 masks of the format codes inside the band per id])."""
     stats = np.ascontiguousarray(stats, dtype=np.float64)
     T = stats.shape[0]
-    fm = (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats])
+    fm = _format_codes(formats)
     amap = np.empty(T, dtype=np.int8)
     knife = np.empty(T, dtype=np.int64)
     near = np.empty(T, dtype=np.uint8)
@@ -824,10 +848,6 @@ def threshold_assign(stats: np.ndarray, mask: int, formats, metric: str, thresho
                                      amap.ctypes.data, knife.ctypes.data, near.ctypes.data, T, ctypes.byref(nk)))
     k = min(nk.value, T)
     return (amap, knife[:k].copy(), near[:k].copy()) if with_near else (amap, knife[:k].copy())
-
-
-def _score_rows(mask: int) -> int:
-    return bin(mask & 0xF).count("1") + (1 if (mask & MASK_BF16_IDENTITY) and not (mask & 1) else 0)
 
 
 def tile_scores_device(stats_dev, mask: int, metric: str):
@@ -847,7 +867,7 @@ def threshold_assign_device_raw(stats_dev, mask: int, formats, metric: str, thre
     torch = _torch()
     require_gpu()
     T = stats_dev.shape[0]
-    fm = (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats])
+    fm = _format_codes(formats)
     both = torch.empty((2, T), dtype=torch.int8, device=stats_dev.device) if out is None else out
     for row in (both[0], both[1]):
         if row.dtype != torch.int8 or row.numel() != T or not row.is_contiguous() or not row.is_cuda:
@@ -863,11 +883,9 @@ def knife_tiles_device(x3d, near, formats, cap: int, list_out, tiles_out, transp
     last, how many were flagged; tiles_out float32 [1 + len(formats), cap, 32, 32] ← their values and every format's reconstruction.
     Asynchronous on the current stream.  transposed=True: the same for Xᵀ of every matrix, read in place (mtq_knife_tiles_transposed):
     `near` and the ids follow Xᵀ's grid (K1T's numbering) and the tiles are Xᵀ tiles in Xᵀ's row-major order."""
+    code, count, stride, rows, cols, ld = _matrix(x3d, (3,))
     torch = _torch()
     require_gpu()
-    count, rows, cols = x3d.shape
-    if x3d.stride(2) != 1 or not x3d.is_cuda:
-        raise ValueError("knife_tiles_device needs a device tensor with contiguous rows")
     th, tw = tiles_hw(cols, rows) if transposed else tiles_hw(rows, cols)
     if near.dtype != torch.int8 or near.numel() != count * th * tw or not near.is_contiguous():
         raise ValueError("near must be a contiguous int8 vector of one entry per tile")
@@ -875,10 +893,10 @@ def knife_tiles_device(x3d, near, formats, cap: int, list_out, tiles_out, transp
         raise ValueError("list_out must be a contiguous int64 vector of cap + 1 entries")
     if cap and (tiles_out.dtype != torch.float32 or tiles_out.numel() != (1 + len(formats)) * cap * 1024 or not tiles_out.is_contiguous()):
         raise ValueError("tiles_out must be a contiguous float32 tensor of (1 + formats) x cap x 32 x 32")
-    fm = (ctypes.c_int * len(formats))(*[MIXED_TILE_FORMATS.index(f) for f in formats]) if formats else None
-    fn = _transposed_entry("mtq_knife_tiles_transposed") if transposed else lib().mtq_knife_tiles_device
-    check(fn(x3d.data_ptr(), _dtype_code(x3d), count, x3d.stride(0) if count > 1 else rows * x3d.stride(1), rows, cols, x3d.stride(1),
-                                       near.data_ptr(), fm, len(formats), int(cap), list_out.data_ptr(), tiles_out.data_ptr() if cap else None, _stream_ptr()))
+    fm = _format_codes(formats) if formats else None
+    fn = _entry("mtq_knife_tiles_transposed") if transposed else lib().mtq_knife_tiles_device
+    check(fn(x3d.data_ptr(), code, count, stride, rows, cols, ld, near.data_ptr(), fm, len(formats), int(cap), list_out.data_ptr(),
+             tiles_out.data_ptr() if cap else None, _stream_ptr()))
 
 
 def threshold_assign_device(stats_dev, mask: int, formats, metric: str, threshold: float, band: float = 2e-6, with_near: bool = False):
@@ -894,7 +912,7 @@ def columns_from_sums(sums7: np.ndarray, elem_count: float) -> dict:
     sums = np.ascontiguousarray(sums7, dtype=np.float64)
     out = (ctypes.c_double * 9)()
     check(lib().mtq_columns_from_sums(sums.ctypes.data, float(elem_count), out))
-    return {"pcc": out[0], "mae": out[1], "atol": out[2], "sums": tuple(out[3:9])}
+    return _columns(out)
 
 
 def columns_from_stats_device(stats_dev, mask: int, assignment, elem_count: float) -> dict:
@@ -909,14 +927,12 @@ def columns_from_stats_device(stats_dev, mask: int, assignment, elem_count: floa
         amap = assignment.reshape(-1).to(device=stats_dev.device, dtype=torch.int8).contiguous()
     if amap.numel() != T:
         raise MtqError("assignment has the wrong number of tiles")
-    scratch = torch.empty(int(lib().mtq_columns_scratch_doubles()), dtype=torch.float64, device=stats_dev.device)
+    scratch = torch.empty(columns_scratch_doubles(), dtype=torch.float64, device=stats_dev.device)
     check(lib().mtq_column_sums_device(stats_dev.data_ptr(), T, mask, amap.data_ptr(), scratch.data_ptr(), _stream_ptr()))
     sums = np.ascontiguousarray(scratch[:7].cpu().numpy())
     if np.isnan(sums[0]) and not np.isnan(sums[1]):
         raise MtqError("map names a format that is not in fmt_mask")
-    out = (ctypes.c_double * 9)()
-    check(lib().mtq_columns_from_sums(sums.ctypes.data, float(elem_count), out))
-    return {"pcc": out[0], "mae": out[1], "atol": out[2], "sums": tuple(out[3:9])}
+    return columns_from_sums(sums, elem_count)
 
 
 def columns_from_stats(stats: np.ndarray, mask: int, assignment: np.ndarray, elem_count: float) -> dict:
@@ -924,4 +940,91 @@ def columns_from_stats(stats: np.ndarray, mask: int, assignment: np.ndarray, ele
     a = np.ascontiguousarray(assignment, dtype=np.int8).reshape(-1)
     out = (ctypes.c_double * 9)()
     check(lib().mtq_columns_from_stats(stats.ctypes.data, stats.shape[0], mask, a.ctypes.data, float(elem_count), out))
-    return {"pcc": out[0], "mae": out[1], "atol": out[2], "sums": tuple(out[3:9])}
+    return _columns(out)
+
+
+# ----------------------------------------------------------------------------- the streamed drivers' launches
+# Called once per chunk or batch: the streams are explicit (each call site picks its own), and the checks read attributes only — no
+# device query, allocation, copy or synchronisation.  Buffers are views of grow-only storage, so their sizes are lower bounds.
+
+@functools.lru_cache(maxsize=None)
+def columns_scratch_doubles() -> int:
+    """Doubles of column-sum scratch per tensor (mtq_columns_scratch_doubles: a constant of the library)."""
+    return int(lib().mtq_columns_scratch_doubles())
+
+
+def greedy_scan_scratch_bytes(count: int, tiles: int) -> int:
+    return int(lib().mtq_greedy_scan_scratch_bytes(int(count), int(tiles)))
+
+
+def scan_carry_bytes(count: int) -> int:
+    return int(lib().mtq_scan_carry_bytes(int(count)))
+
+
+def _sums_ptrs(stats, count: int, T: int, mask: int, maps, scratch, sums_host=None) -> tuple:
+    """The pointers of a column-sum launch over `count` tensors of T tiles in all, checked: full records (2 + 5 doubles per format of
+    mask), a map entry per tile, columns_scratch_doubles() of scratch per tensor and, for the threshold calls, 11 doubles per tensor."""
+    torch = _torch()
+    return (_buffer(stats, torch.float64, T * record_doubles(mask & ~MASK_SLIM), "records"), _buffer(maps, torch.int8, T, "maps"),
+            _buffer(scratch, torch.float64, count * columns_scratch_doubles(), "scratch"),
+            None if sums_host is None else _buffer(sums_host, torch.float64, count * 11, "sums_host", device=False))
+
+
+def column_sums_device_batched(stats, count: int, tiles: int, mask: int, maps, scratch, stream) -> None:
+    """mtq_column_sums_device_batched on `stream`: the seven column sums of `count` tensors' maps [count, tiles] over their records
+    → scratch [count, columns_scratch_doubles()], tensor i's sums at the head of row i."""
+    sp, mp, wp, _ = _sums_ptrs(stats, count, count * tiles, mask, maps, scratch)
+    check(lib().mtq_column_sums_device_batched(sp, count, tiles, mask, mp, wp, _stream(stream)))
+
+
+def threshold_columns(stats, count: int, tiles: int, dec_mask: int, maps, scratch, sums_host, stream) -> None:
+    """mtq_threshold_columns on `stream`: column_sums_device_batched, then every tensor's seven sums and its tile count per format
+    into the pinned sums_host [count, 11]."""
+    sp, mp, wp, hp = _sums_ptrs(stats, count, count * tiles, dec_mask, maps, scratch, sums_host)
+    check(lib().mtq_threshold_columns(sp, count, tiles, dec_mask, mp, wp, hp, _stream(stream)))
+
+
+def threshold_columns_ragged(stats, tiles_per, dec_mask: int, maps, scratch, sums_host, stream) -> None:
+    """mtq_threshold_columns_ragged: threshold_columns for a ragged group, matrix j's tiles_per[j] tiles behind matrix j-1's."""
+    n = len(tiles_per)
+    sp, mp, wp, hp = _sums_ptrs(stats, n, sum(tiles_per), dec_mask, maps, scratch, sums_host)
+    check(lib().mtq_threshold_columns_ragged(sp, (ctypes.c_int64 * n)(*tiles_per), n, dec_mask, mp, wp, hp, _stream(stream)))
+
+
+def _enqueue_ptrs(count: int, T: int, k1_mask: int, formats, stats, both_dev, both_host, cap: int, list_dev, knife_dev, list_host,
+                  scratch, sums_host) -> tuple:
+    """The arguments of mtq_threshold_enqueue(_ragged) from records to sums_host for `count` tensors of T tiles in all, checked."""
+    torch = _torch()
+    return (_buffer(stats, torch.float64, T * record_doubles(k1_mask & ~MASK_SLIM), "records"), _buffer(both_dev, torch.int8, 2 * T, "both_dev"),
+            _buffer(both_host, torch.int8, 2 * T, "both_host", device=False), int(cap), _buffer(list_dev, torch.int64, cap + 1, "list_dev"),
+            _buffer(knife_dev, torch.float32, (1 + len(formats)) * cap * 1024, "knife_dev") if cap else None,
+            _buffer(list_host, torch.int64, cap + 1, "list_host", device=False),
+            None if scratch is None else _buffer(scratch, torch.float64, count * columns_scratch_doubles(), "scratch"),
+            None if sums_host is None else _buffer(sums_host, torch.float64, count * 11, "sums_host", device=False))
+
+
+def threshold_enqueue(x3d, k1_mask: int, dec_mask: int, formats, metric: str, threshold: float, band: float, stats, both_dev, both_host,
+                      cap: int, list_dev, knife_dev, list_host, scratch, sums_host, stream, side_stream, transposed: bool = False) -> None:
+    """One batch (count, rows, cols) of the streamed threshold driver as one call (mtq_threshold_enqueue; transposed: the search of Xᵀ,
+    mtq_threshold_enqueue_transposed): K1 → records, K4 → both_dev [2, T] (maps, knife-edge masks) and its pinned mirror both_host on
+    `stream`; the knife-edge list (list_dev, list_host [cap + 1]) and tiles (knife_dev [1 + formats, cap, 32, 32]) on side_stream (None:
+    on `stream`); with scratch and sums_host, the column sums under K4's maps on `stream` (threshold_columns)."""
+    code, count, stride, rows, cols, ld = _matrix(x3d, (3,))
+    th, tw = tiles_hw(rows, cols)
+    ptrs = _enqueue_ptrs(count, count * th * tw, k1_mask, formats, stats, both_dev, both_host, cap, list_dev, knife_dev, list_host,
+                         scratch, sums_host)
+    fn = _entry("mtq_threshold_enqueue_transposed") if transposed else lib().mtq_threshold_enqueue
+    check(fn(x3d.data_ptr(), code, count, stride, rows, cols, ld, k1_mask, dec_mask, _format_codes(formats), len(formats), METRIC_CODE[metric],
+             threshold, band, *ptrs, _stream(stream), _stream(side_stream)))
+
+
+def threshold_enqueue_ragged(mats, k1_mask: int, dec_mask: int, formats, metric: str, threshold: float, band: float, stats, both_dev,
+                             both_host, cap: int, list_dev, knife_dev, list_host, scratch, sums_host, stream, side_stream) -> list[int]:
+    """threshold_enqueue for a ragged group (mtq_threshold_enqueue_ragged): 2-D matrices of one storage type and any shapes, their
+    tiles numbered through → the tiles of every matrix."""
+    arr, code, tiles_per = ragged_matrices(mats)
+    ptrs = _enqueue_ptrs(len(mats), sum(tiles_per), k1_mask, formats, stats, both_dev, both_host, cap, list_dev, knife_dev, list_host,
+                         scratch, sums_host)
+    check(lib().mtq_threshold_enqueue_ragged(arr, len(mats), code, k1_mask, dec_mask, _format_codes(formats), len(formats), METRIC_CODE[metric],
+                                             threshold, band, *ptrs, _stream(stream), _stream(side_stream)))
+    return tiles_per

@@ -269,7 +269,7 @@ class GreedyPipeline:
         key = (count, tiles, rec)
         if b["key"] == key:
             return b
-        n_scratch = int(hb.lib().mtq_columns_scratch_doubles())
+        n_scratch = hb.columns_scratch_doubles()
         P = 1 + len(self.pure_formats)
         nf = len(MIXED_TILE_FORMATS)
 
@@ -289,7 +289,7 @@ class GreedyPipeline:
             "counts_dev": flat("counts_dev", count * nf, torch.int32).view(count, nf),
             "seeds_dev": flat("seeds_dev", count, torch.int64),
             "seeds_host": flat("seeds_host", count, torch.int64, pinned=True),
-            "scratch": flat("scratch", int(hb.lib().mtq_greedy_scan_scratch_bytes(count, tiles)), torch.uint8),
+            "scratch": flat("scratch", hb.greedy_scan_scratch_bytes(count, tiles), torch.uint8),
             "sums_dev": flat("sums_dev", P * count * n_scratch, torch.float64).view(P, count, n_scratch),
             "pure_maps": [flat(f"pure_{f}", count * tiles, torch.int8).view(count, tiles) for f in self.pure_formats],
             "maps_host": flat("maps_host", count * tiles, torch.int8, pinned=True).view(count, tiles),
@@ -300,7 +300,7 @@ class GreedyPipeline:
             # it carries from phase 1 to phase 2, and the listed kernel's hand-back list
             "listed": flat("listed", count * tiles, torch.int32),
             "n_listed": flat("n_listed", count, torch.int32),
-            "carry": flat("carry", int(hb.lib().mtq_scan_carry_bytes(count)), torch.uint8),
+            "carry": flat("carry", hb.scan_carry_bytes(count), torch.uint8),
             "lscr": flat("lscr", count * tiles + count, torch.int32),
             "n_listed_host": flat("n_listed_host", count, torch.int32, pinned=True),
             "mark": flat("mark", count, torch.int32),   # per chunk: id of the K1 launch that met a tile for the literal fix-up (mtq_tile_stats_partial_begin / _end)
@@ -328,8 +328,8 @@ class GreedyPipeline:
         sh[:] = np.uint64(self.seed) if seeds is None else np.asarray([int(v) for v in seeds], dtype=np.uint64)
         if (sh == 0).any():
             raise ValueError("seed 0 means 'draw a random seed' in the reference; pass non-zero seeds")
-        per = int(hb.lib().mtq_greedy_scan_scratch_bytes(1, tiles))
-        per_carry = int(hb.lib().mtq_scan_carry_bytes(1))
+        per = hb.greedy_scan_scratch_bytes(1, tiles)
+        per_carry = hb.scan_carry_bytes(1)
         uniform = seeds is None or len(set(int(v) for v in seeds)) == 1
         shared = self.shared_orders and uniform and self.metric in ("pcc", "mae")
         plan = self.lazy_plan(x3d)   # what K1 writes now, and what the listed kernel writes later (masks by format code)
@@ -417,11 +417,9 @@ class GreedyPipeline:
                     hb.greedy_scan_device_ex(*args, counts_out=b["counts_dev"][first:first + n], phase=2, carry=carry)
                 else:
                     hb.greedy_scan_device_ex(*args, counts_out=b["counts_dev"][first:first + n], orders=orders)
-                hb.check(hb.lib().mtq_column_sums_device_batched(recs.data_ptr(), n, tiles, dec_mask, maps.data_ptr(),
-                                                                 b["sums_dev"][0, first:first + n].data_ptr(), scan_stream.cuda_stream))
+                hb.column_sums_device_batched(recs, n, tiles, dec_mask, maps, b["sums_dev"][0, first:first + n], scan_stream)
                 for k, pm in enumerate(b["pure_maps"]):
-                    hb.check(hb.lib().mtq_column_sums_device_batched(recs.data_ptr(), n, tiles, dec_mask, pm[first:first + n].data_ptr(),
-                                                                     b["sums_dev"][1 + k, first:first + n].data_ptr(), scan_stream.cuda_stream))
+                    hb.column_sums_device_batched(recs, n, tiles, dec_mask, pm[first:first + n], b["sums_dev"][1 + k, first:first + n], scan_stream)
                 scanned = torch.cuda.Event(enable_timing=trace)
                 scanned.record(scan_stream)
             if trace:
@@ -579,11 +577,9 @@ class GreedyPipeline:
         self.stream.wait_event(maps_up)
         dec_mask = enq["host_mask"] & ~hb.MASK_SLIM
         if enq["slim"]:   # the searched maps' columns (other metrics: the host scan already produced them)
-            hb.check(hb.lib().mtq_column_sums_device_batched(dev.data_ptr(), count, tiles, dec_mask, cb["maps_dev"].data_ptr(),
-                                                             cb["scratch"][0].data_ptr(), self.stream.cuda_stream))
+            hb.column_sums_device_batched(dev, count, tiles, dec_mask, cb["maps_dev"], cb["scratch"][0], self.stream)
         for k, pm in enumerate(self._colbufs["pure_maps"]):   # one constant map per pure format (flat: any (count, tiles) view of it is constant)
-            hb.check(hb.lib().mtq_column_sums_device_batched(dev.data_ptr(), count, tiles, dec_mask, pm.data_ptr(), cb["scratch"][1 + k].data_ptr(),
-                                                             self.stream.cuda_stream))
+            hb.column_sums_device_batched(dev, count, tiles, dec_mask, pm, cb["scratch"][1 + k], self.stream)
         summed = torch.cuda.Event()
         summed.record(self.stream)
         with torch.cuda.stream(self.col_stream):
@@ -608,7 +604,7 @@ class GreedyPipeline:
                 self._unresolved = [u for u in self._unresolved if u is not user]
         cap_tiles = max(count * tiles, cb.get("cap_tiles", 0) if cb.get("device") == str(device) else 0)
         cap_count = max(count, cb.get("cap_count", 0) if cb.get("device") == str(device) else 0)
-        n_scratch = int(hb.lib().mtq_columns_scratch_doubles())
+        n_scratch = hb.columns_scratch_doubles()
         self._colbufs = {"device": str(device), "cap_tiles": cap_tiles, "cap_count": cap_count, "n_scratch": n_scratch, "next": 0, "ring": [
             {"maps_host": torch.empty((cap_tiles,), dtype=torch.int8, pin_memory=True),
              "maps_dev": torch.empty((cap_tiles,), dtype=torch.int8, device=device),

@@ -3,7 +3,6 @@ from __future__ import annotations
 
 import concurrent.futures as cf
 import contextlib
-import ctypes
 import os
 import time
 from dataclasses import replace
@@ -45,7 +44,7 @@ class ThresholdPipeline:
         self.knife_tiles = 0
         self._side = torch.cuda.Stream()      # the knife-edge tiles' fetch and way home, beside the main stream's K1
         self.knife_cap = settings().knife_cap   # knife-edge tiles per chunk fetched without a round trip (more: one extra trip)
-        self._scratch_n = int(hb.lib().mtq_columns_scratch_doubles())
+        self._scratch_n = hb.columns_scratch_doubles()
         self._pin = {}
         self._dev = {}
 
@@ -199,9 +198,8 @@ class ThresholdPipeline:
             for j in range(x3d.shape[0]):
                 mats.append(x3d[j])
                 numels.append(x3d.shape[1] * x3d.shape[2] if numel is None else int(numel))
-        arr, code, tiles_per = hb.ragged_matrices(mats)
         dev = mats[0].device
-        T, n = sum(tiles_per), len(mats)
+        T, n = sum(th * tw for th, tw in (hb.tiles_hw(*m.shape) for m in mats)), len(mats)
         identity = mats[0].dtype == torch.bfloat16 and (self.mask & 1) and (self.mask & 0xE)
         k1_mask = self.mask & 0xE if identity else self.mask
         dec_mask = k1_mask | hb.MASK_BF16_IDENTITY if identity else self.mask
@@ -218,16 +216,14 @@ class ThresholdPipeline:
         knife_dev = self._devbuf(f"knife{slot}", planes * cap * 1024, torch.float32, dev).view(1, planes, cap, 32, 32)
         rec = hb.record_doubles(k1_mask)
         recs = self._devbuf(f"recs{slot}", T * rec, torch.float64, dev).view(T, rec)
-        fm = (ctypes.c_int * len(self.tile_formats))(*[MIXED_TILE_FORMATS.index(f) for f in self.tile_formats])
         scratch = self._devbuf(f"colscr{slot}_0", P * n * self._scratch_n, torch.float64, dev)
-        hb.check(hb.lib().mtq_threshold_enqueue_ragged(
-            arr, n, code, k1_mask, dec_mask, fm, len(self.tile_formats), hb.METRIC_CODE[self.metric], self.threshold, self.band, recs.data_ptr(),
-            both_dev.data_ptr(), both_host.data_ptr(), cap, idx_dev[0].data_ptr(), knife_dev[0].data_ptr(), idx_host[0].data_ptr(),
-            scratch.data_ptr(), sums_host.data_ptr(), torch.cuda.current_stream().cuda_stream, None if single else self._side.cuda_stream))
+        tiles_per = hb.threshold_enqueue_ragged(mats, k1_mask, dec_mask, self.tile_formats, self.metric, self.threshold, self.band, recs, both_dev,
+                                                both_host, cap, idx_dev[0], knife_dev[0], idx_host[0], scratch, sums_host,
+                                                torch.cuda.current_stream(), None if single else self._side)
         landed = torch.cuda.Event()
         landed.record(torch.cuda.current_stream() if single else self._side)
         first = np.concatenate([[0], np.cumsum(tiles_per)]).astype(np.int64)
-        return {"x": None, "ragged": {"mats": mats, "arr": arr, "tiles_per": tiles_per, "first": first, "numels": numels}, "tiles_sent": False, "slot": slot, "speculated": True,
+        return {"x": None, "ragged": {"mats": mats, "tiles_per": tiles_per, "first": first, "numels": numels}, "tiles_sent": False, "slot": slot, "speculated": True,
                 "numel": None, "hw": None, "tiles": T, "dec_mask": dec_mask, "cap": cap, "single": single, "planes": planes,
                 "launched": [(0, n, recs, slice(0, T), landed, landed)], "both_host": both_host, "idx_host": idx_host, "knife_host": knife_host,
                 "sums_host": sums_host, "both_dev": both_dev, "idx_dev": idx_dev, "knife_dev": knife_dev, "maps": np.empty((T,), dtype=np.int8)}
@@ -261,8 +257,7 @@ class ThresholdPipeline:
         knife_dev = self._devbuf(f"knife{slot}", len(chunks) * planes * cap * 1024, torch.float32, dev).view(len(chunks), planes, cap, 32, 32)
         rec = hb.record_doubles(k1_mask)
         recs_all = self._devbuf(f"recs{slot}", count * tiles * rec, torch.float64, dev).view(count, tiles, rec)
-        fm = (ctypes.c_int * len(self.tile_formats))(*[MIXED_TILE_FORMATS.index(f) for f in self.tile_formats])
-        main_ptr = torch.cuda.current_stream().cuda_stream
+        main = torch.cuda.current_stream()
         speculated = len(chunks) == 1   # one chunk: the call sums the columns under K4's maps at once (final unless a knife-edge tile is listed)
         launched = []  # (first, n, records, chunk's tile range, map-landed event, knife-tiles-landed event)
         for c, (first, n) in enumerate(chunks):
@@ -294,14 +289,11 @@ class ThresholdPipeline:
                     landed.record()
             else:
                 scratch = self._devbuf(f"colscr{slot}_{c}", P * n * self._scratch_n, torch.float64, dev)
-                enqueue_call = hb._transposed_entry("mtq_threshold_enqueue_transposed") if self.transposed else hb.lib().mtq_threshold_enqueue
-                hb.check(enqueue_call(
-                    xs.data_ptr(), hb._dtype_code(xs), n, xs.stride(0) if n > 1 else rows * xs.stride(1), rows, cols, xs.stride(1), k1_mask, dec_mask, fm,
-                    len(self.tile_formats), hb.METRIC_CODE[self.metric], self.threshold, self.band, recs.data_ptr(), both_dev.data_ptr(), both_host.data_ptr(),
-                    cap, idx_dev[c].data_ptr(), knife_dev[c].data_ptr(), idx_host[c].data_ptr(), scratch.data_ptr(), sums_host.data_ptr(), main_ptr,
-                    None if single else self._side.cuda_stream))
+                hb.threshold_enqueue(xs, k1_mask, dec_mask, self.tile_formats, self.metric, self.threshold, self.band, recs, both_dev, both_host, cap,
+                                     idx_dev[c], knife_dev[c], idx_host[c], scratch, sums_host, main, None if single else self._side,
+                                     transposed=self.transposed)
                 landed = torch.cuda.Event()
-                landed.record(torch.cuda.current_stream() if single else self._side)
+                landed.record(main if single else self._side)
                 decided = landed      # the side stream runs behind the masks' copy: one event covers both
             launched.append((first, n, recs, part, decided, landed))
         return {"x": x3d, "tiles_sent": False, "slot": slot, "speculated": speculated, "numel": numel, "hw": (th, tw), "tiles": tiles, "dec_mask": dec_mask, "cap": cap, "single": single, "planes": planes,
@@ -362,15 +354,13 @@ class ThresholdPipeline:
                 self.knife_tiles += k
             dmaps = both_dev[0, part]
             scratch = self._devbuf(f"colscr{st['slot']}_{c}", P * n * scratch_n, torch.float64, dev).view(P, n, scratch_n)
-            sp = hb._stream_ptr()
-            if rg:
-                per = (ctypes.c_int64 * n)(*rg["tiles_per"])
+            cur = torch.cuda.current_stream()
 
-                def columns(maps_dev, q):
-                    hb.check(hb.lib().mtq_threshold_columns_ragged(recs.data_ptr(), per, n, dec_mask, maps_dev.data_ptr(), scratch[q].data_ptr(), sums_host[q].data_ptr(), sp))
-            else:
-                def columns(maps_dev, q):
-                    hb.check(hb.lib().mtq_threshold_columns(recs.data_ptr(), n, tiles, dec_mask, maps_dev.data_ptr(), scratch[q].data_ptr(), sums_host[q, first:first + n].data_ptr(), sp))
+            def columns(maps_dev, q):
+                if rg:
+                    hb.threshold_columns_ragged(recs, rg["tiles_per"], dec_mask, maps_dev, scratch[q], sums_host[q], cur)
+                else:
+                    hb.threshold_columns(recs, n, tiles, dec_mask, maps_dev, scratch[q], sums_host[q, first:first + n], cur)
             if not final:
                 columns(dmaps, 0)
             for q, f in enumerate(self.pure_formats):   # wq's `none` rows from the same records

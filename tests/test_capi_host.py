@@ -323,3 +323,174 @@ def test_greedy_run_batch_equals_single_runs():
         assert np.array_equal(maps[i].reshape(8, 8), orc.greedy(x, ALL, "pcc", 0.999, seeds[i])[0])
     with pytest.raises(hb.MtqError):
         hb.greedy_run_batch(st, 0xF, ALL, "pcc", 0.999, 1.0, [1, 2, 0, 4, 5], n_threads=2)  # a zero seed is reported, not ignored
+
+
+def _header_signatures() -> dict:
+    """Every prototype of include/mtq.h → (result class, parameter classes) in hip_backend.SIGNATURES' letters."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", (ROOT / "include" / "mtq.h").read_text(), flags=re.S)
+    scalar = {"int64_t": "l", "uint32_t": "u", "int": "i", "double": "d", "size_t": "z", "uint64_t": "q"}
+    sigs = {}
+    for ret, name, params in re.findall(r"([\w\s*]*?)\b(mtq_\w+)\s*\(([^)]*)\)\s*;", text):
+        result = "s" if "*" in ret else {"int": "i", "size_t": "z", "void": "v"}[ret.split()[-1]]
+        classes = ""
+        for p in params.split(","):
+            words = [w for w in p.split() if w != "const"]
+            if p.strip() in ("", "void"):
+                continue
+            classes += "p" if "*" in p or "[" in p else scalar[" ".join(words[:-1])]
+        sigs[name] = (result, classes)
+    return sigs
+
+
+def test_signature_table_matches_the_header():
+    """hip_backend.SIGNATURES is the binding: its result and parameter classes are those include/mtq.h declares, and lib() set them."""
+    want = _header_signatures()
+    assert set(want) == set(hb.SIGNATURES)
+    for name, (result, params, _optional) in hb.SIGNATURES.items():
+        assert (result, params) == want[name], (name, (result, params), want[name])
+    L = hb.lib()
+    for name, (result, params, _optional) in hb.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is hb._CTYPE[result] and list(fn.argtypes) == [hb._CTYPE[c] for c in params], name
+
+
+class _StubFunction:
+    def __init__(self, value):
+        self.value = value
+
+    def __call__(self, *args):
+        return self.value
+
+
+class _StubLibrary:
+    """Stands in for ctypes.CDLL: every function returns `version`, the names in `missing` do not exist, every lookup is recorded."""
+
+    def __init__(self, version, missing=()):
+        self.version, self.missing, self.looked_up = version, set(missing), []
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+        self.looked_up.append(name)
+        if name in self.missing:
+            raise AttributeError(name)
+        fn = _StubFunction(self.version)
+        setattr(self, name, fn)
+        return fn
+
+
+def _load(monkeypatch, stub):
+    import torch  # noqa: F401  (lib() imports it before the library; it must not meet the stub loader)
+
+    monkeypatch.setattr(hb, "_lib", None)
+    monkeypatch.setattr(hb.ctypes, "CDLL", lambda path: stub)
+    return hb.lib()
+
+
+def test_lib_checks_the_version_before_any_other_symbol(monkeypatch):
+    old = _StubLibrary(142)
+    with pytest.raises(hb.MtqError, match=r"version 142.*needs 143"):
+        _load(monkeypatch, old)
+    assert old.looked_up == ["mtq_version"]
+
+
+def test_lib_names_a_missing_symbol(monkeypatch):
+    with pytest.raises(hb.MtqError, match="has no mtq_threshold_columns"):
+        _load(monkeypatch, _StubLibrary(143, missing={"mtq_threshold_columns"}))
+
+
+def test_lib_serves_a_build_without_the_optional_symbols(monkeypatch):
+    stub = _StubLibrary(143, missing=hb.OPTIONAL_EXPORTS)
+    assert _load(monkeypatch, stub) is stub and stub.mtq_tile_stats.argtypes is not None
+    for name in hb.OPTIONAL_EXPORTS:
+        with pytest.raises(hb.MtqError, match="rebuild"):
+            hb._entry(name)
+
+
+class _OnDevice:
+    """A host tensor that passes for a device tensor in the binding's checks (the _FakeCuda pattern of test_transpose_host.py), with a
+    null pointer: a call that got past every check would be refused by the library's own null check, never launched."""
+
+    is_cuda = True
+
+    def __init__(self, t):
+        self.t = t
+
+    def __getattr__(self, name):
+        return getattr(self.t, name)
+
+    def data_ptr(self):
+        return 0
+
+
+def test_matrix_helper_checks_and_leading_dimensions():
+    import torch
+
+    x = torch.zeros((3, 40, 64), dtype=torch.bfloat16)
+    assert hb._matrix(_OnDevice(x)) == (hb.DTYPE_BF16, 3, 40 * 64, 40, 64, 64)
+    assert hb._matrix(_OnDevice(x[:, :, :48])) == (hb.DTYPE_BF16, 3, 40 * 64, 40, 48, 64)         # rows at a pitch
+    assert hb._matrix(_OnDevice(x[0].float())) == (hb.DTYPE_F32, 1, 40 * 64, 40, 64, 64)           # 2-D: a batch of one
+    assert hb._matrix(_OnDevice(torch.zeros((1, 1, 64))[:, :, :33]), (3,))[5] == 64                 # one row: ld >= cols all the same
+    for bad, msg in ((x, "device tensor"), (_OnDevice(x[0]), "3-D"), (_OnDevice(x[:, :, ::2]), "contiguous rows"),
+                     (_OnDevice(x.half()), "bfloat16 or float32")):
+        with pytest.raises(hb.MtqError, match=msg):
+            hb._matrix(bad, (3,))
+    with pytest.raises(hb.MtqError, match="contiguous"):
+        hb._contiguous_batch(_OnDevice(x[:, :, :48]))                          # the batched K1 entry points take no pitch
+
+
+def test_driver_wrappers_check_what_they_dereference():
+    """The streamed drivers' launches (threshold_enqueue / _ragged / _columns / _columns_ragged, column_sums_device_batched) refuse
+    host tensors, the wrong rank, inner-strided rows, float16 and undersized buffers; buffers larger than needed (views of grow-only
+    storage) pass on to the library."""
+    import torch
+
+    def D(*shape, dtype=torch.float64):
+        return _OnDevice(torch.zeros(shape, dtype=dtype))
+
+    count, rows, cols = 2, 64, 96
+    T = count * 2 * 3
+    rec = hb.record_doubles(0xE)
+    ns = hb.columns_scratch_doubles()
+    cap = 4
+
+    def enqueue(x, stats=None, scratch=None, knife=None):
+        hb.threshold_enqueue(x, 0xE, 0xE | hb.MASK_BF16_IDENTITY, ALL, "pcc", 0.999, 2e-6, stats or D(T * rec), D(2 * T, dtype=torch.int8),
+                             torch.zeros(2 * T, dtype=torch.int8), cap, D(cap + 1, dtype=torch.int64), knife or D(5 * cap * 1024, dtype=torch.float32),
+                             torch.zeros(cap + 1, dtype=torch.int64), scratch or D(count * ns), torch.zeros(count * 11, dtype=torch.float64), None, None)
+
+    x = torch.zeros((count, rows, cols), dtype=torch.bfloat16)
+    for bad, msg in ((x, "device tensor"), (_OnDevice(x[0]), "3-D"), (_OnDevice(torch.zeros((count, rows, 2 * cols))[:, :, ::2]), "contiguous rows"),
+                     (_OnDevice(x.half()), "bfloat16 or float32")):
+        with pytest.raises(hb.MtqError, match=msg):
+            enqueue(bad)
+    xd = _OnDevice(x)
+    for kw, msg in ((dict(stats=D(T * rec - 1)), "records"), (dict(scratch=D(count * ns - 1)), "scratch"),
+                    (dict(knife=D(5 * cap * 1024 - 1, dtype=torch.float32)), "knife_dev"), (dict(stats=D(T, rec, dtype=torch.float32)), "records")):
+        with pytest.raises(hb.MtqError, match=msg):
+            enqueue(xd, **kw)
+    with pytest.raises(hb.MtqError, match="null argument"):
+        enqueue(xd, stats=D(2 * T * rec))
+    with pytest.raises(hb.MtqError, match="device tensor"):
+        hb.threshold_enqueue_ragged([_OnDevice(x[0]), x[1]], 0xE, 0xE, ALL, "pcc", 0.999, 2e-6, *([None] * 3), cap, *([None] * 5), None, None)
+
+    sums_host = torch.zeros(count * 11, dtype=torch.float64)
+    calls = (lambda *a: hb.column_sums_device_batched(*a[:3], 0xF, *a[3:], None),
+             lambda *a: hb.threshold_columns(*a[:3], 0xF, *a[3:], sums_host, None))
+    full = hb.record_doubles(0xF)
+    for args, msg in (((torch.zeros(T * full, dtype=torch.float64), D(T, dtype=torch.int8), D(count * ns)), "records"),
+                      ((D(T * full - 1), D(T, dtype=torch.int8), D(count * ns)), "records"),
+                      ((D(T * full), D(T - 1, dtype=torch.int8), D(count * ns)), "maps"),
+                      ((D(T * full), D(T, dtype=torch.int8), D(count * ns - 1)), "scratch"),
+                      ((D(T * full), D(T, dtype=torch.int8), _OnDevice(torch.zeros((count, ns))[:, :7])), "scratch")):
+        for call in calls:
+            with pytest.raises(hb.MtqError, match=msg):
+                call(args[0], count, 6, *args[1:])
+    with pytest.raises(hb.MtqError, match="sums_host"):
+        hb.threshold_columns(D(T * full), count, 6, 0xF, D(T, dtype=torch.int8), D(count * ns), sums_host[1:], None)
+    with pytest.raises(hb.MtqError, match="null argument"):                          # larger maps (a constant map's ring) pass
+        hb.column_sums_device_batched(D(T * full), count, 6, 0xF, D(4 * T, dtype=torch.int8), D(count * ns), None)
+    with pytest.raises(hb.MtqError, match="scratch"):
+        hb.threshold_columns_ragged(D(T * full), [6, 6], 0xF, D(T, dtype=torch.int8), D(ns), torch.zeros(22, dtype=torch.float64), None)
+    with pytest.raises(hb.MtqError, match="null argument"):
+        hb.threshold_columns_ragged(D(T * full), [6, 6], 0xF, D(T, dtype=torch.int8), D(2 * ns), torch.zeros(22, dtype=torch.float64), None)

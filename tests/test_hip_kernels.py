@@ -529,6 +529,19 @@ def test_threshold_run_batches_equals_run():
         assert np.array_equal(got[3][0].assignment, a) and got[3][0].counts == counts
 
 
+def test_threshold_pipeline_refuses_inner_strided_batches():
+    """A batch whose rows are not contiguous (x[:, :, ::2]) is refused by the one-call enqueue, on its own and through run_batches,
+    instead of being read as if its rows were."""
+    from quantization_analysis_amd.pipeline import ThresholdPipeline
+
+    x = dev(np.stack([gen("normal_bf16", 60 + i, (64, 256)) for i in range(2)]), bf16=True)[:, :, ::2]
+    with ThresholdPipeline(ALL, "pcc", 0.999) as pipe:
+        with pytest.raises(hb.MtqError, match="contiguous rows"):
+            pipe.enqueue(x)
+        with pytest.raises(hb.MtqError, match="contiguous rows"):
+            pipe.run_batches([x])
+
+
 def _ragged_inputs(bf16: bool):
     """Matrices of assorted shapes (whole tiles, ragged edges, one tile, a (n/32, 32) vector form, a strided view), some with values the
     exact routes hand to the literal fix-up (NaN, inf, huge, subnormal)."""
