@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTQ_VERSION 143 /* 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
+#define MTQ_VERSION 143 /* 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
 
 typedef enum {
     MTQ_OK = 0,
@@ -46,8 +46,9 @@ typedef enum {
 enum { MTQ_DTYPE_BF16 = 0, MTQ_DTYPE_F32 = 1 };
 
 /* format codes = index into MIXED_TILE_FORMATS (tile_utils.py:8) = value stored in assignment maps;
- * FP0 is quantize-only (quantization_formats.py:167-168). */
-enum { MTQ_FMT_BF16 = 0, MTQ_FMT_BFP8 = 1, MTQ_FMT_BFP4 = 2, MTQ_FMT_BFP2 = 3, MTQ_FMT_FP0 = 4 };
+ * FP0 (quantization_formats.py:167-168) and the scalar MXFP4 / NVFP4 proxies (:174-183,257-278) are quantize-only: mtq_quantize
+ * takes them, every record and map entry point refuses them. */
+enum { MTQ_FMT_BF16 = 0, MTQ_FMT_BFP8 = 1, MTQ_FMT_BFP4 = 2, MTQ_FMT_BFP2 = 3, MTQ_FMT_FP0 = 4, MTQ_FMT_MXFP4 = 5, MTQ_FMT_NVFP4 = 6 };
 #define MTQ_NUM_TILE_FORMATS 4
 #define MTQ_MASK_ALL 0xFu
 /* HOST functions only: "the records hold no bf16 slot; the bf16 candidate is the identity" — true for bf16 STORAGE, where
@@ -144,11 +145,26 @@ int mtq_tile_stats_listed(const void *x, int in_dtype, int64_t count, int64_t st
 /*
  * K2 quantize — materialise y = quantize→dequantize(x) for one format as float32.
  * Replaces quantize_weight_values (quantization_formats.py:171-194) behind Quantizer.quantize
- * (quantizer.py:34) for fmt in {bf16, bfp8, bfp4, bfp2, fp0}.  Bit-exact, including the
- * reference's saturating round-up, sign-of-zero, denormal→0 and uint32 wrap-around quirks.
+ * (quantizer.py:34) for fmt in {bf16, bfp8, bfp4, bfp2, fp0, mxfp4, nvfp4}.  Bit-exact, including the
+ * reference's saturating round-up, sign-of-zero, denormal→0 and uint32 wrap-around quirks, and for the
+ * two proxies its float32 log2 at the binade edges, tie-low fp4 levels and e4m3 with a largest value of 240
+ * (csrc/mtq_fp4_proxy.hip).  Other codes: MTQ_ERR_UNSUPPORTED.
  */
 int mtq_quantize(const void *x, int in_dtype, int64_t rows, int64_t cols, int64_t ld,
                  int fmt, float *y, int64_t ldy, void *stream);
+
+/*
+ * FP4P fp4_proxy_sums — the `none` rows of the MXFP4 / NVFP4 proxies (quantization_formats.py:174-183,257-278: y = sign(x)·g(|x|),
+ * elementwise) for `count` equally shaped matrices at x + i*stride_elems, in one read of x; y is never written.  fmt_mask: bit 0 mxfp4,
+ * bit 1 nvfp4 (1..3, MTQ_ERR_INVALID otherwise).  sums: device doubles [count][2][7] in the order of mtq_columns_from_sums
+ * (Σx, Σx², Σy, Σy², Σxy, Σ|x−y|, max|x−y|; the products and |x−y| formed in float32, summed in float64); the slots of formats outside
+ * fmt_mask are left untouched.  Deterministic: per-block partials in a fixed order whose blocking depends on rows × cols alone (a
+ * matrix gets the same bits alone or in a batch), then a fixed tree; no float atomics.  scratch: device doubles, at least
+ * mtq_fp4_proxy_scratch_doubles(count, rows, cols).  csrc/mtq_fp4_proxy.hip.
+ */
+size_t mtq_fp4_proxy_scratch_doubles(int64_t count, int64_t rows, int64_t cols);
+int mtq_fp4_proxy_sums(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                       uint32_t fmt_mask, double *sums, double *scratch, size_t scratch_doubles, void *stream);
 
 /*
  * K1T tile_stats_transposed — K1 of Xᵀ read from the row-major X, for `count` equally shaped matrices at x + i*stride_elems (one

@@ -26,7 +26,7 @@ from .compression_algorithms.metrics import pearson_corr
 from .compression_algorithms.quantizer import BACKENDS, Quantizer
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS
 from .model_source import build_model_index, lpt_shards, resolve_format_list, resolve_selected_tensors, safe_repo_revision_key
-from .quantization_formats import SUPPORTED_FORMATS
+from .quantization_formats import PROXY_FORMATS, ROW_FORMATS, SUPPORTED_FORMATS
 
 # The HIP runtime maps a process's streams onto this many hardware queues (its default is 4), and kernels of streams that share a
 # queue run one after the other.  A window of the streamed search (streamed.py) has the scans of several shape groups in flight
@@ -35,7 +35,7 @@ from .quantization_formats import SUPPORTED_FORMATS
 # Read by the runtime at its first call — nothing in this process has touched the GPU yet; a value already in the environment wins.
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-FORMAT_BYTES_PER_ELEM = {"bf16": 2.0, "bfp8": 1.088, "bfp4": 0.50097, "bfp2": 0.25097, "fp0": 0.0}  # wq:132-140
+FORMAT_BYTES_PER_ELEM = {"mxfp4": 0.5, "nvfp4": 0.5, "bf16": 2.0, "bfp8": 1.088, "bfp4": 0.50097, "bfp2": 0.25097, "fp0": 0.0}  # wq:132-140
 MIXED_ALGOS = {"mixed-tile-greedy", "mixed-tile-random", "mixed-tile-threshold"}
 
 
@@ -174,7 +174,7 @@ def write_size_plot(out_dir: Path, tensor_name: str, metric_name: str, rows, for
 
 
 def formats_of_row(r) -> str:
-    return "mixed" if int(r[2]) < 0 else SUPPORTED_FORMATS[int(r[2])]
+    return "mixed" if int(r[2]) < 0 else ROW_FORMATS[int(r[2])]
 
 
 def _columns_emulation(xf: np.ndarray, y: np.ndarray):
@@ -184,7 +184,8 @@ def _columns_emulation(xf: np.ndarray, y: np.ndarray):
 
 def _none_rows_hip(x, formats, quantizer):
     """`none` baseline on the hip backend: pcc/mae/atol of every pure mixed-tile format come from ONE
-    K1 pass (sum the per-tile records); fp0 from three device reductions.  y is not materialised or cached."""
+    K1 pass (sum the per-tile records); fp0 from three device reductions; the mxfp4 / nvfp4 proxies from ONE fp4_proxy_sums
+    pass.  y is not materialised or cached."""
     from .compression_algorithms.tile_search import columns_from_stats, compute_tile_stats, fp0_columns
 
     out = {}
@@ -197,7 +198,34 @@ def _none_rows_hip(x, formats, quantizer):
             out[f] = (c["pcc"], c["mae"], c["atol"])
     if "fp0" in formats:
         out["fp0"] = fp0_columns(x)  # metrics.py:14-15 with y = 0
+    proxies = [f for f in formats if f in PROXY_FORMATS]
+    if proxies:
+        out.update(_proxy_columns_hip(x, proxies))
     return out
+
+
+def _proxy_columns_hip(x, proxies) -> dict:
+    """fmt → (pcc, mae, atol) of the mxfp4 / nvfp4 proxies of a device tensor of any rank (elementwise: its 2-D flatten serves)."""
+    from . import hip_backend as hb
+
+    if x.numel() == 0:
+        return {f: (1.0, 0.0, 0.0) for f in proxies}   # as fp0_columns on an empty tensor
+    x2d, _info = hb.to_device_2d(x, x.device)
+    if x2d.stride(-1) != 1:
+        x2d = x2d.contiguous()
+    return hb.fp4_proxy_columns(x2d, proxies, float(x.numel()))[0]
+
+
+def _proxy_y_hip(x, fmt: str):
+    """y of an mxfp4 / nvfp4 proxy for a device tensor of any rank through mtq_quantize (elementwise: the 2-D flatten's y, reshaped)."""
+    import torch
+
+    from . import hip_backend as hb
+
+    if x.numel() == 0:
+        return torch.zeros(tuple(x.shape), dtype=torch.float32, device=x.device)
+    x2d, info = hb.to_device_2d(x, x.device)
+    return hb.unflatten(hb.quantize(x2d, fmt), info)
 
 
 def _none_rows_literal(x, formats, quantizer):
@@ -205,7 +233,7 @@ def _none_rows_literal(x, formats, quantizer):
     xh = x.float().cpu().numpy()
     out = {}
     for f in formats:
-        y = quantizer.quantize(x, f)
+        y = _proxy_y_hip(x, f) if f in PROXY_FORMATS else quantizer.quantize(x, f)
         out[f] = _columns_emulation(xh, y.cpu().numpy() if hasattr(y, "cpu") else np.asarray(y, dtype=np.float32))
     return out
 
@@ -233,7 +261,7 @@ def _evaluate_tensor(idx, name, index, algorithms, formats, quantizer, args, run
             elapsed = time.perf_counter() - t0
             for f in formats:
                 pcc, mae, atol = cols[f]
-                rows.append([idx, ci, SUPPORTED_FORMATS.index(f), pcc, mae, atol, elapsed, numel * FORMAT_BYTES_PER_ELEM[f] / 1e9,
+                rows.append([idx, ci, ROW_FORMATS.index(f), pcc, mae, atol, elapsed, numel * FORMAT_BYTES_PER_ELEM[f] / 1e9,
                              np.nan, -1, -1, -1, -1, *meta])
             continue
         if hip and algo.name == "transpose" and not args.literal_metrics:
@@ -256,7 +284,7 @@ def _evaluate_tensor(idx, name, index, algorithms, formats, quantizer, args, run
             fmt_l = res.fmt.lower()
             gb = float(res.tile_bytes) / 1e9 if res.tile_bytes is not None else numel * FORMAT_BYTES_PER_ELEM.get(fmt_l, 0.0) / 1e9
             counts = [res.tile_counts.get(k, 0) for k in MIXED_TILE_FORMATS] if res.tile_counts else [-1, -1, -1, -1]
-            fcode = -1 if res.fmt == "MIXED" else SUPPORTED_FORMATS.index(fmt_l)
+            fcode = -1 if res.fmt == "MIXED" else ROW_FORMATS.index(fmt_l)
             rows.append([idx, ci, fcode, pcc, mae, atol, elapsed, gb, res.tile_bytes if res.tile_bytes is not None else np.nan,
                          *counts, *meta])
             draw = not args.no_plots
@@ -292,7 +320,7 @@ def _print_tables(names, rows, comp_names, shapes, table_lines, summary: bool, f
             crs = [r for r in trs if int(r[1]) == ci]
             if not crs:
                 continue
-            fmts = ["MIXED" if int(r[2]) < 0 else SUPPORTED_FORMATS[int(r[2])].upper() for r in crs]
+            fmts = ["MIXED" if int(r[2]) < 0 else ROW_FORMATS[int(r[2])].upper() for r in crs]
             fmt_w = max(len(f) for f in fmts)
             mixed = _is_mixed(comp)
             pcc_w = max(len("PCC"), max(len(f"{r[3]: .5f}") for r in crs))

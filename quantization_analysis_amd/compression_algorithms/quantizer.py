@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..quantization_formats import SUPPORTED_FORMATS, quantize_weight_values
+from ..quantization_formats import BASE_FORMATS, quantize_weight_values
 
 BACKENDS = ("emulation", "hip", "ttnn")
 
@@ -32,7 +32,9 @@ class Quantizer:
         if self.backend == "ttnn":
             raise RuntimeError("Internal error: TTNN backend selected but ttnn is not initialized.")  # reference :24-25
         if self.backend == "hip":
-            if fmt_l not in SUPPORTED_FORMATS:
+            # the tile-path formats and fp0; the mxfp4 / nvfp4 proxies reach the device through hip_backend.quantize /
+            # fp4_proxy_sums in wq's `none` and `transpose` rows
+            if fmt_l not in BASE_FORMATS:
                 raise ValueError(f"Unsupported weight format: {fmt_l}")
             from .. import hip_backend as hb
 

@@ -1,7 +1,9 @@
 """`transpose`: every requested format applied to np.transpose(x) and transposed back — does the shared exponent do better along the
 weight's other axis? (reference compression_algorithms/transpose.py:13-33).
 
-np.transpose reverses all axes and quantize_dequantize_bfp_ttnn shares one exponent per 16 elements of the LAST axis, so with
+The mxfp4 / nvfp4 proxies are elementwise, so their transpose rows are their `none` rows bit for bit (the columns from one fp4_proxy_sums
+pass, y from mtq_quantize).  np.transpose reverses all axes and quantize_dequantize_bfp_ttnn shares one exponent per 16 elements of the LAST
+axis, so with
 d0 = x.shape[0] (1 for a 0-d tensor) and V = x.reshape(d0, -1):
 
     transpose_y(x) == quantize(V.T).T.reshape(x.shape)
@@ -44,6 +46,10 @@ def _columns_hip(v2d, formats: list) -> dict:
     if "fp0" in formats:
         pcc, mae, atol = fp0_columns(v2d)
         out["fp0"] = {"pcc": pcc, "mae": mae, "atol": atol}
+    proxies = [f for f in formats if f in hb.PROXY_FORMATS]
+    if proxies:
+        for f, (pcc, mae, atol) in hb.fp4_proxy_columns(v2d, proxies)[0].items():
+            out[f] = {"pcc": pcc, "mae": mae, "atol": atol}
     return out
 
 
@@ -93,7 +99,7 @@ class TransposeCompression(CompressionAlgorithm):
                 if cached is not None and cached.shape == shape:
                     y = cached if was_np else torch.from_numpy(cached).to(x.device)
                 else:
-                    y = hb.quantize_transposed(v, fmt).reshape(shape)
+                    y = (hb.quantize(v, fmt) if fmt in hb.PROXY_FORMATS else hb.quantize_transposed(v, fmt)).reshape(shape)
                     host = _to_host(y)
                     cache.save_array(self.name, fmt, host)
                     if was_np:

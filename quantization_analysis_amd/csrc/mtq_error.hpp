@@ -30,6 +30,8 @@ void work_counter_release(const WorkSlot &slot, void *stream);
 void work_counter_abandon(const WorkSlot &slot);
 // hipGetLastError() → MTQ_OK / MTQ_ERR_HIP with the kernel name in the message.
 int check_launch(const char *what);
+// mtq_quantize for MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4, arguments already checked (mtq_fp4_proxy.hip)
+int fp4_proxy_quantize(const void *x, int in_dtype, int64_t rows, int64_t cols, int64_t ld, int fmt, float *y, int64_t ldy, void *stream);
 // mtq_shutdown's parts (each translation unit releases what it owns; none of them runs from a static destructor)
 void scan_shutdown();       // mtq_scan.hip: the device jump-ahead tables
 void host_shutdown();       // mtq_host.cpp: the scan thread pool

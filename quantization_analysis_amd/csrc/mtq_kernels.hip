@@ -917,7 +917,14 @@ static int launch_quantize(const void *x, int in_dtype, int64_t rows, int64_t co
 extern "C" int mtq_quantize(const void *x, int in_dtype, int64_t rows, int64_t cols, int64_t ld, int fmt, float *y,
                             int64_t ldy, void *stream)
 {
-    if (fmt < MTQ_FMT_BF16 || fmt > MTQ_FMT_FP0) return fail(MTQ_ERR_UNSUPPORTED, "format code must be 0..4 (bf16,bfp8,bfp4,bfp2,fp0)");
+    if (fmt == MTQ_FMT_MXFP4 || fmt == MTQ_FMT_NVFP4) {   // elementwise proxies (mtq_fp4_proxy.hip): no groups, no tiles
+        if (int rc = check_matrix(x, in_dtype, rows, cols, ld)) return rc;
+        if (!y) return fail(MTQ_ERR_INVALID, "y is null");
+        if (ldy < cols) return fail(MTQ_ERR_INVALID, "ldy < cols");
+        if (int rc = require_device()) return rc;
+        return fp4_proxy_quantize(x, in_dtype, rows, cols, ld, fmt, y, ldy, stream);
+    }
+    if (fmt < MTQ_FMT_BF16 || fmt > MTQ_FMT_FP0) return fail(MTQ_ERR_UNSUPPORTED, "format code must be 0..6 (bf16,bfp8,bfp4,bfp2,fp0,mxfp4,nvfp4)");
     return launch_quantize(x, in_dtype, rows, cols, ld, fmt, nullptr, y, ldy, stream, "mtq_quantize");
 }
 

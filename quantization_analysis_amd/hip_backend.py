@@ -21,6 +21,8 @@ LIB_PATH = Path(os.environ["MTQ_LIB"]).resolve() if os.environ.get("MTQ_LIB") el
 
 MIXED_TILE_FORMATS = ["bf16", "bfp8", "bfp4", "bfp2"]
 FMT_CODE = {"bf16": 0, "bfp8": 1, "bfp4": 2, "bfp2": 3, "fp0": 4}
+PROXY_FORMATS = ["mxfp4", "nvfp4"]   # the scalar proxies: mtq_quantize codes 5, 6 and bits 0, 1 of mtq_fp4_proxy_sums' mask
+QUANTIZE_CODE = {**FMT_CODE, "mxfp4": 5, "nvfp4": 6}   # mtq_quantize only; the transposed and map entry points take FMT_CODE
 METRIC_CODE = {"pcc": 0, "mae": 1, "atol": 2}
 DTYPE_BF16, DTYPE_F32 = 0, 1
 TILE = 32
@@ -92,6 +94,8 @@ SIGNATURES = {
     "mtq_threshold_enqueue_transposed": ("i", "pillllluupiiddppplppppppp", True),
     "mtq_output_error_scratch_doubles": ("z", "ll", True),
     "mtq_output_error": ("i", "plllpillpuppilppzp", True),
+    "mtq_fp4_proxy_scratch_doubles": ("z", "lll", True),
+    "mtq_fp4_proxy_sums": ("i", "pillllluppzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -459,15 +463,56 @@ def tile_stats_partial_end(x3d, layout_mask: int, stats, mark, launch_id: int) -
 
 
 def quantize(x2d, fmt: str, out=None):
-    """K2 on a 2-D device tensor → device float32 (rows, cols)."""
+    """K2 on a 2-D device tensor → device float32 (rows, cols); the proxies mxfp4 / nvfp4 elementwise (csrc/mtq_fp4_proxy.hip)."""
     torch = _torch()
     require_gpu()
-    if fmt not in FMT_CODE:
+    if fmt not in QUANTIZE_CODE:
         raise ValueError(f"Unsupported weight format: {fmt}")
     x2d, code, rows, cols, ld = _as_device_matrix(x2d)
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.float32, device=x2d.device)
-    check(lib().mtq_quantize(x2d.data_ptr(), code, rows, cols, ld, FMT_CODE[fmt], out.data_ptr(), out.stride(0), _stream_ptr()))
+    check(lib().mtq_quantize(x2d.data_ptr(), code, rows, cols, ld, QUANTIZE_CODE[fmt], out.data_ptr(), out.stride(0), _stream_ptr()))
+    return out
+
+
+def fp4_proxy_sums(x, formats, out=None, scratch=None):
+    """FP4P (mtq_fp4_proxy_sums) on the current stream: one read of a (rows, cols) or (count, rows, cols) device tensor with contiguous
+    rows → float64 [2, 7] / [count, 2, 7] device sums (Σx, Σx², Σy, Σy², Σxy, Σ|x−y|, max|x−y|) of the proxies, slot 0 mxfp4, slot 1
+    nvfp4; the slot of a proxy not in `formats` is zero.  The tensor is checked before any pointer is taken."""
+    code, count, stride, rows, cols, ld = _matrix(x)
+    bad = [f for f in formats if f not in PROXY_FORMATS]
+    if bad or not formats:
+        raise MtqError(f"fp4_proxy_sums takes a non-empty subset of {PROXY_FORMATS}, got {list(formats)}")
+    mask = sum(1 << PROXY_FORMATS.index(f) for f in set(formats))
+    torch = _torch()
+    require_gpu()
+    fn = _entry("mtq_fp4_proxy_sums")
+    need = int(_entry("mtq_fp4_proxy_scratch_doubles")(count, rows, cols))
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.float64, device=x.device)
+    else:
+        _buffer(scratch, torch.float64, need, "scratch")
+    if out is None:
+        out = torch.zeros((count, 2, 7), dtype=torch.float64, device=x.device)
+    else:
+        _buffer(out, torch.float64, count * 14, "out")
+    check(fn(x.data_ptr(), code, count, stride, rows, cols, ld, mask, out.data_ptr(), scratch.data_ptr(), need, _stream_ptr()))
+    return out if x.dim() == 3 else out[0]
+
+
+def fp4_proxy_columns(x, formats, elem_count: float | None = None) -> list:
+    """fmt → (pcc, mae, atol) of each proxy in `formats` for every matrix of x (a list of dicts, one per matrix), from one
+    fp4_proxy_sums launch; elem_count defaults to rows × cols (a vector's zero padding adds nothing to the sums)."""
+    s = fp4_proxy_sums(x, formats)
+    host = s.reshape(-1, 2, 7).cpu().numpy()
+    n = float(elem_count if elem_count is not None else x.shape[-1] * x.shape[-2])
+    out = []
+    for sums in host:
+        cols = {}
+        for f in formats:
+            c = columns_from_sums(sums[PROXY_FORMATS.index(f)], n)
+            cols[f] = (c["pcc"], c["mae"], c["atol"])
+        out.append(cols)
     return out
 
 

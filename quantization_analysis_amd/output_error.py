@@ -24,7 +24,7 @@ import numpy as np
 
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS
 from .layer_io import OpIO, check_op, chunks
-from .quantization_formats import SUPPORTED_FORMATS, quantize_weight_values
+from .quantization_formats import BASE_FORMATS as SUPPORTED_FORMATS, quantize_weight_values  # no proxy rows here
 
 FORMAT_BYTES_PER_ELEM = {"bf16": 2.0, "bfp8": 1.088, "bfp4": 0.50097, "bfp2": 0.25097, "fp0": 0.0}  # wq:132-140 (cli.py)
 SLOTS = ("bf16", "bfp8", "bfp4", "bfp2", "map", "fp0", "recorded")  # include/mtq.h MTQ_OE_*

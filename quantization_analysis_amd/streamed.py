@@ -6,7 +6,8 @@ of Xᵀ, but come from a row-layout K1 pass (pure formats) over the resident bat
 The shard's tensors are grouped by (2-D shape, storage type); a group goes through `pipeline.GreedyPipeline` /
 `pipeline.ThresholdPipeline` in batches: batched K1 launches, records D2H overlapped with the next chunk's K1, the scans of
 a chunk fanned out over host threads (greedy) or K4 on the device (threshold).  The `none` rows (wq:589-590) come out of the
-same records (pure-format column sums): one K1 pass per tensor serves every row of its table.  y is not materialised
+same records (pure-format column sums): one K1 pass per tensor serves every row of its table but the mxfp4 / nvfp4 proxies', which come
+from one fp4_proxy_sums launch per resident batch.  y is not materialised
 (K3 runs only for --literal-metrics, which takes the per-tensor path), PNGs are written after the GPU work.
 Vectors and scalars (their 2-D image is zero-filled: tile_utils.py:96-102) keep the per-tensor path.
 """
@@ -19,7 +20,7 @@ import numpy as np
 
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS
 from .pipeline import GreedyPipeline, ThresholdPipeline, cpu_budget, default_workers
-from .quantization_formats import SUPPORTED_FORMATS
+from .quantization_formats import PROXY_FORMATS, ROW_FORMATS
 from .settings import settings
 
 STREAMED_ALGOS = {"mixed-tile-greedy", "mixed-tile-threshold"}
@@ -124,16 +125,28 @@ class ShardEvaluator:
             out.append(cols)
         return out
 
-    def _rows(self, part, results, metas, numel, per):
+    def _proxy_columns(self, x3d) -> list:
+        """The `none` rows of the mxfp4 / nvfp4 proxies: per tensor, fmt → (pcc, mae, atol) from one fp4_proxy_sums launch over the
+        resident batch."""
+        proxies = [f for f in self.formats if f in PROXY_FORMATS]
+        if not proxies:
+            return [{} for _ in range(x3d.shape[0])]
+        from . import hip_backend as hb
+
+        return hb.fp4_proxy_columns(x3d, proxies)
+
+    def _rows(self, part, results, metas, numel, per, proxy_cols):
         out = {}
-        for (idx, _name), r, m in zip(part, results, metas):
+        for (idx, _name), r, m, pc in zip(part, results, metas, proxy_cols):
             rows = []
             for f in self.formats:   # comp 0 = none (wq:589-590)
                 if f in MIXED_TILE_FORMATS:
                     pcc, mae, atol = r.pure[f]
+                elif f in PROXY_FORMATS:
+                    pcc, mae, atol = pc[f]
                 else:                # fp0: y = 0 (metrics.py:14-15)
                     pcc, mae, atol = (1.0 if m[4] == 0.0 else 0.0), m[3], m[4]
-                rows.append([idx, 0, SUPPORTED_FORMATS.index(f), pcc, mae, atol, per, numel * self.bytes_per_elem[f] / 1e9, np.nan, -1, -1, -1, -1, *m[:3]])
+                rows.append([idx, 0, ROW_FORMATS.index(f), pcc, mae, atol, per, numel * self.bytes_per_elem[f] / 1e9, np.nan, -1, -1, -1, -1, *m[:3]])
             counts = [r.counts.get(k, 0) for k in MIXED_TILE_FORMATS]
             rows.append([idx, 1, -1, r.pcc, r.mae, r.atol, per, float(r.tile_bytes) / 1e9, r.tile_bytes, *counts, *m[:3]])
             out[idx] = (np.asarray(rows, dtype=np.float64).reshape(-1, self.row_w), r.assignment)
@@ -211,7 +224,7 @@ class ShardEvaluator:
                     for r, pure in zip(results, self._pure_columns(x3d, key[0] * key[1])):
                         r.pure = pure
                 per = dt * (tiles * len(part) / n_tiles) / len(part)   # TIME(s): the window's wall time shared by tiles (wq:680-682 times one tensor's run())
-                out.update(self._rows(part, results, metas, key[0] * key[1], per))
+                out.update(self._rows(part, results, metas, key[0] * key[1], per, self._proxy_columns(x3d)))
             del loaded
             w0 = w1
         return out

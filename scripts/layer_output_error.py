@@ -22,7 +22,7 @@ from quantization_analysis_amd.compression_algorithms import load_compression_co
 from quantization_analysis_amd.layer_io import select_ops
 from quantization_analysis_amd.model_source import build_model_index, resolve_format_list
 from quantization_analysis_amd.output_error import BACKENDS, check_layout, evaluate_op
-from quantization_analysis_amd.quantization_formats import SUPPORTED_FORMATS
+from quantization_analysis_amd.quantization_formats import BASE_FORMATS as SUPPORTED_FORMATS  # no proxy rows here
 
 
 def parse_args(argv=None):
