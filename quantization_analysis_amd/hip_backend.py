@@ -475,10 +475,15 @@ def quantize(x2d, fmt: str, out=None):
     return out
 
 
+PROXY_MAX_COUNT = 65535   # matrices per mtq_fp4_proxy_sums launch (the grid's y dimension)
+
+
 def fp4_proxy_sums(x, formats, out=None, scratch=None):
     """FP4P (mtq_fp4_proxy_sums) on the current stream: one read of a (rows, cols) or (count, rows, cols) device tensor with contiguous
     rows → float64 [2, 7] / [count, 2, 7] device sums (Σx, Σx², Σy, Σy², Σxy, Σ|x−y|, max|x−y|) of the proxies, slot 0 mxfp4, slot 1
-    nvfp4; the slot of a proxy not in `formats` is zero.  The tensor is checked before any pointer is taken."""
+    nvfp4; the slot of a proxy not in `formats` is zero.  The tensor is checked before any pointer is taken.  A batch of more than
+    PROXY_MAX_COUNT matrices takes one launch per PROXY_MAX_COUNT of them, in order on the stream, sharing one chunk's scratch; the
+    matrices are independent, so each gets the bits it gets alone."""
     code, count, stride, rows, cols, ld = _matrix(x)
     bad = [f for f in formats if f not in PROXY_FORMATS]
     if bad or not formats:
@@ -487,7 +492,7 @@ def fp4_proxy_sums(x, formats, out=None, scratch=None):
     torch = _torch()
     require_gpu()
     fn = _entry("mtq_fp4_proxy_sums")
-    need = int(_entry("mtq_fp4_proxy_scratch_doubles")(count, rows, cols))
+    need = int(_entry("mtq_fp4_proxy_scratch_doubles")(min(count, PROXY_MAX_COUNT), rows, cols))
     if scratch is None:
         scratch = torch.empty(max(need, 1), dtype=torch.float64, device=x.device)
     else:
@@ -496,7 +501,11 @@ def fp4_proxy_sums(x, formats, out=None, scratch=None):
         out = torch.zeros((count, 2, 7), dtype=torch.float64, device=x.device)
     else:
         _buffer(out, torch.float64, count * 14, "out")
-    check(fn(x.data_ptr(), code, count, stride, rows, cols, ld, mask, out.data_ptr(), scratch.data_ptr(), need, _stream_ptr()))
+    x_ptr, out_ptr, esz = x.data_ptr(), out.data_ptr(), x.element_size()
+    for m0 in range(0, count, PROXY_MAX_COUNT):
+        n = min(PROXY_MAX_COUNT, count - m0)
+        check(fn(x_ptr + m0 * stride * esz, code, n, stride, rows, cols, ld, mask, out_ptr + m0 * 14 * 8, scratch.data_ptr(), need,
+                 _stream_ptr()))
     return out if x.dim() == 3 else out[0]
 
 

@@ -210,3 +210,59 @@ def test_binding_checks_before_any_pointer():
         hb.fp4_proxy_sums(_FakeCuda(torch.zeros((8, 8))), ["bfp8"])
     with pytest.raises(ValueError, match="Unsupported"):
         hb.quantize_transposed(_FakeCuda(torch.zeros((8, 8))), "mxfp4")
+
+
+class _HostAsDevice:
+    """A host tensor that passes for a device tensor, with its real host pointer: a fake entry point can read it."""
+
+    is_cuda = True
+
+    def __init__(self, t):
+        self.t = t
+
+    def __getattr__(self, name):
+        return getattr(self.t, name)
+
+
+def test_sums_split_a_batch_into_launches_of_65535(monkeypatch):
+    """More matrices than one launch takes: hb.fp4_proxy_sums hands the C entry point consecutive chunks of at most PROXY_MAX_COUNT
+    matrices, each at its own x and out offset, with one chunk's scratch.  The fake entry point refuses what the C one refuses and
+    writes Σx of every matrix it is given, read from the pointer it got, so a wrong offset shows as a wrong sum."""
+    import ctypes
+
+    count, rows, cols, ld = 2 * hb.PROXY_MAX_COUNT + 7, 2, 3, 5
+    x = torch.arange(count * rows * ld, dtype=torch.float32).reshape(count, rows, ld) % 251
+    view = x[:, :, :cols]                               # stride_elems = rows * ld, ld > cols
+    per_matrix = 12 * 4                                 # any positive scratch size per matrix
+    calls = []
+
+    def scratch_doubles(n, r, c):
+        assert (r, c) == (rows, cols)
+        return n * per_matrix
+
+    def sums(xp, code, n, stride, r, c, l, mask, outp, scratchp, scratch_n, stream):
+        assert 0 < n <= hb.PROXY_MAX_COUNT and scratch_n >= n * per_matrix, "the C entry point refuses this"
+        assert (code, stride, r, c, l, mask) == (hb.DTYPE_F32, rows * ld, rows, cols, ld, 3)
+        calls.append((xp, n, outp, scratchp))
+        xs = np.ctypeslib.as_array((ctypes.c_float * ((n - 1) * stride + (r - 1) * l + c)).from_address(xp))
+        xs = np.concatenate([xs, np.zeros(n * stride - xs.size, np.float32)]).reshape(n, r, l)[:, :, :c]
+        o = np.ctypeslib.as_array((ctypes.c_double * (n * 14)).from_address(outp)).reshape(n, 2, 7)
+        o[:, :, 0] = xs.astype(np.float64).sum(axis=(1, 2))[:, None]
+        return 0
+
+    fakes = {"mtq_fp4_proxy_sums": sums, "mtq_fp4_proxy_scratch_doubles": scratch_doubles}
+    monkeypatch.setattr(hb, "_entry", lambda name: fakes[name])
+    monkeypatch.setattr(hb, "require_gpu", lambda: None)
+    monkeypatch.setattr(hb, "_stream_ptr", lambda: 0)
+    got = hb.fp4_proxy_sums(_HostAsDevice(view), PROXIES)
+    M = hb.PROXY_MAX_COUNT
+    offsets = [((xp - x.data_ptr()) // 4, n, (outp - got.data_ptr()) // 8) for xp, n, outp, _s in calls]
+    assert offsets == [(0, M, 0), (M * rows * ld, M, M * 14), (2 * M * rows * ld, 7, 2 * M * 14)]
+    assert len({c[3] for c in calls}) == 1
+    want = view.double().sum(dim=(1, 2))
+    assert torch.equal(got[:, 0, 0], want) and torch.equal(got[:, 1, 0], want)
+    # a batch that fits takes one launch, and a 2-D tensor is a batch of one
+    calls.clear()
+    hb.fp4_proxy_sums(_HostAsDevice(view[:M]), PROXIES)
+    hb.fp4_proxy_sums(_HostAsDevice(view[5]), PROXIES)
+    assert [c[1] for c in calls] == [M, 1]
