@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTQ_VERSION 143 /* 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
+#define MTQ_VERSION 143 /* 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
 
 typedef enum {
     MTQ_OK = 0,
@@ -223,6 +223,24 @@ size_t mtq_output_error_scratch_doubles(int64_t m, int64_t n);
 int mtq_output_error(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
                      const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
                      double *sums, double *scratch, size_t scratch_doubles, void *stream);
+
+/*
+ * LOE with quantised activations — mtq_output_error with the candidates fed Q(X): Y_f = xq·Ŵ_fᵀ + b for every format bit (bf16: Ŵ = bf16(w))
+ * and for the map, while R = x·wᵀ + b keeps x; fp0 and `recorded` are unchanged.  xq: m × k bf16 on device (ldxq >= k), normally
+ * mtq_quantize_rows_bf16 of x; xq == x gives the sums of mtq_output_error bit for bit.  Same sums, slots, scratch, accumulation and
+ * determinism as mtq_output_error; a null xq or ldxq < k is MTQ_ERR_INVALID, the other checks are its own.  csrc/mtq_output_error.hip.
+ */
+int mtq_output_error_qx(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
+                        const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
+                        double *sums, double *scratch, size_t scratch_doubles, void *stream, const void *xq, int64_t ldxq);
+
+/*
+ * LOE activation pre-pass — Q(X) of a bf16 rows × cols matrix (ld) in the row layout (groups of 16 consecutive columns of one row),
+ * written as bf16 (ldy): the upper 16 bits of mtq_quantize's float32 y for in_dtype bf16, specials included (a BFP value has its low
+ * 16 bits zero).  fmt: MTQ_FMT_BF16 (a copy), _BFP8, _BFP4, _BFP2; fp0 and the fp4 proxies are not activation formats
+ * (MTQ_ERR_UNSUPPORTED).  x and y must not overlap.  csrc/mtq_output_error.hip.
+ */
+int mtq_quantize_rows_bf16(const void *x, int64_t rows, int64_t cols, int64_t ld, int fmt, void *y, int64_t ldy, void *stream);
 
 /*
  * K5 dequant_fp8_block (loader) — float8-e4m3fn weights × float32 inverse block scales → float32: the on-load

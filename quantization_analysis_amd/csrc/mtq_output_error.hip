@@ -14,6 +14,12 @@
 // bfp4, bfp2, map.  Epilogue: r = hi + res + b, q_f = acc_f + b, in f32; the sums of (r, q) in float64 per lane, then a fixed-order
 // reduction over the workgroup into one partial record per workgroup, and a second kernel adds the records in index order into `sums`
 // (no float atomics: the same inputs give the same bits).
+//
+// Activation formats (mtq_output_error_qx): the candidates see Q(X), a bf16 image of the BFP-quantised activations that the row pre-pass
+// quantize_rows_bf16 writes once per chunk (exact: a BFP value has at most 8 significant bits), while R keeps X.  The QX instantiations
+// stage the Q(X) tile beside X in LDS and take their A fragment for bfp8 / bfp4 / bfp2 / map from it; the bf16 candidate gets an
+// accumulator of its own (Q(X)·hi), since hi is R's.  There the float32-W flag is a compile-time property of T, so the bf16-W
+// instantiation holds no res accumulator.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,6 +37,7 @@ constexpr int kImgHi = 0, kImgMid = 1, kImgLo = 2, kImgB8 = 3, kImgB4 = 4, kImgB
 constexpr int kSlots = 7;                          // bf16, bfp8, bfp4, bfp2, map, fp0, recorded
 constexpr int kRecord = 2 + 5 * kSlots;            // Σr, Σr², then Σq, Σq², Σrq, Σ|r−q|, max|r−q| per slot
 constexpr int kLdsBytes = (kBM + kNumImg * kBN) * kLdk * 2;
+constexpr int kLdsBytesQx = kLdsBytes + kBM * kLdk * 2;   // + the Q(X) tile
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -142,29 +149,33 @@ __device__ __forceinline__ void fold(double (&s)[kRecord], int slot, double r, d
     s[6 + 5 * slot] = nan_max(s[6 + 5 * slot], d);
 }
 
-template <typename T>
+// QX: the candidates take their A operand from xq (Q(X), bf16, ldxq) and the bf16 candidate accumulates in acc[6]; !QX ignores xq.
+template <typename T, bool QX>
 __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec,
                                                                 const T *__restrict__ w, int64_t N, int64_t ldw, int w_vec,
                                                                 const float *__restrict__ bias, uint32_t imask, uint32_t smask,
                                                                 const int8_t *__restrict__ map, int64_t map_w,
                                                                 const void *__restrict__ rec, int rec_f32, int64_t ldr,
-                                                                double *__restrict__ partials)
+                                                                double *__restrict__ partials,
+                                                                const uint16_t *__restrict__ xq, int64_t ldxq, int xq_vec)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[kLdsBytes / 2];
+    __shared__ __attribute__((aligned(16))) uint16_t lds[(QX ? kLdsBytesQx : kLdsBytes) / 2];
     __shared__ double red[4][kRecord];
     uint16_t *xs = lds;
     uint16_t *img0 = lds + kBM * kLdk;
+    uint16_t *xqs = lds + (kBM + kNumImg * kBN) * kLdk;   // QX only
     constexpr int kImgElems = kBN * kLdk;
+    constexpr int kAcc = QX ? 7 : 6;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t nblocks = (N + kBN - 1) / kBN;
     const int64_t bm = blockIdx.x / nblocks, bn = blockIdx.x % nblocks;
     const int64_t m0 = bm * kBM, n0 = bn * kBN;
-    const bool f32w = (imask & (1u << kImgMid)) != 0;
+    const bool f32w = QX ? sizeof(T) == 4 : (imask & (1u << kImgMid)) != 0;
 
-    f32x16 acc[6][2];
+    f32x16 acc[kAcc][2];
 #pragma unroll
-    for (int a = 0; a < 6; ++a)
+    for (int a = 0; a < kAcc; ++a)
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -172,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *
 
     // global → registers one K-step ahead: the loads of step k0 + 64 are in flight while the MFMAs of step k0 run
     const int wrow = tid >> 2, wc16 = (tid & 3) * kGroup;
-    uint4 xr[4];
+    uint4 xr[4], xqr[QX ? 4 : 1];
     uint32_t wu[kGroup];
     auto load_step = [&](int64_t k0) {
 #pragma unroll
@@ -193,6 +204,26 @@ __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *
             }
             xr[i] = v;
         }
+        if constexpr (QX) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {   // Q(X): the same pieces
+                const int p = tid + kThreads * i, row = p >> 3, c8 = (p & 7) * 8;
+                const int64_t gm = m0 + row, gk = k0 + c8;
+                uint4 v = make_uint4(0u, 0u, 0u, 0u);
+                if (gm < M) {
+                    const uint16_t *src = xq + gm * ldxq + gk;
+                    if (xq_vec && gk + 8 <= K) {
+                        v = *reinterpret_cast<const uint4 *>(src);
+                    } else {
+                        uint32_t h[8];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) h[j] = gk + j < K ? (uint32_t)src[j] : 0u;
+                        v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+                    }
+                }
+                xqr[i] = v;
+            }
+        }
         Loader<T>::group(w, n0 + wrow, k0 + wc16, N, K, ldw, w_vec != 0, wu);   // W: lane tid owns group (row tid / 4, columns 16·(tid % 4) ..)
     };
     load_step(0);
@@ -201,6 +232,7 @@ __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *
         for (int i = 0; i < 4; ++i) {
             const int p = tid + kThreads * i;
             *reinterpret_cast<uint4 *>(xs + (p >> 3) * kLdk + (p & 7) * 8) = xr[i];
+            if constexpr (QX) *reinterpret_cast<uint4 *>(xqs + (p >> 3) * kLdk + (p & 7) * 8) = xqr[i];
         }
         stage_w_group(wu, n0 + wrow, k0 + wc16, N, K, imask, map, map_w, img0, wrow * kLdk + wc16);
         __syncthreads();
@@ -208,17 +240,22 @@ __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *
 #pragma unroll
         for (int kk = 0; kk < kBK / 16; ++kk) {
             const int koff = kk * 16 + 8 * (lane >> 5);
-            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (wave * 32 + (lane & 31)) * kLdk + koff);
+            const int aoff = (wave * 32 + (lane & 31)) * kLdk + koff;
+            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + aoff);
+            const bf16x8 aq = QX ? *reinterpret_cast<const bf16x8 *>(xqs + aoff) : a;   // the candidates' A fragment
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const int boff = (s * 32 + (lane & 31)) * kLdk + koff;
-#define MTQ_OE_MFMA(ACC, IMG) acc[ACC][s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, *reinterpret_cast<const bf16x8 *>(img0 + (IMG) * kImgElems + boff), acc[ACC][s], 0, 0, 0)
-                MTQ_OE_MFMA(0, kImgHi);
-                if (f32w) { MTQ_OE_MFMA(1, kImgMid); MTQ_OE_MFMA(1, kImgLo); }
-                if (imask & (1u << kImgB8)) MTQ_OE_MFMA(2, kImgB8);
-                if (imask & (1u << kImgB4)) MTQ_OE_MFMA(3, kImgB4);
-                if (imask & (1u << kImgB2)) MTQ_OE_MFMA(4, kImgB2);
-                if (imask & (1u << kImgMap)) MTQ_OE_MFMA(5, kImgMap);
+#define MTQ_OE_MFMA(ACC, A, IMG) acc[ACC][s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, *reinterpret_cast<const bf16x8 *>(img0 + (IMG) * kImgElems + boff), acc[ACC][s], 0, 0, 0)
+                MTQ_OE_MFMA(0, a, kImgHi);
+                if (f32w) { MTQ_OE_MFMA(1, a, kImgMid); MTQ_OE_MFMA(1, a, kImgLo); }
+                if constexpr (QX) {
+                    if (smask & 1u) MTQ_OE_MFMA(kAcc - 1, aq, kImgHi);
+                }
+                if (imask & (1u << kImgB8)) MTQ_OE_MFMA(2, aq, kImgB8);
+                if (imask & (1u << kImgB4)) MTQ_OE_MFMA(3, aq, kImgB4);
+                if (imask & (1u << kImgB2)) MTQ_OE_MFMA(4, aq, kImgB2);
+                if (imask & (1u << kImgMap)) MTQ_OE_MFMA(5, aq, kImgMap);
 #undef MTQ_OE_MFMA
             }
         }
@@ -243,7 +280,7 @@ __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *
             const double rd = (double)rf;
             sum[0] += rd;
             sum[1] += rd * rd;
-            if (smask & 1u) fold(sum, 0, rd, (double)(hi + b));
+            if (smask & 1u) fold(sum, 0, rd, (double)((QX ? acc[kAcc - 1][s][r] : hi) + b));
             if (smask & 2u) fold(sum, 1, rd, (double)(acc[2][s][r] + b));
             if (smask & 4u) fold(sum, 2, rd, (double)(acc[3][s][r] + b));
             if (smask & 8u) fold(sum, 3, rd, (double)(acc[4][s][r] + b));
@@ -306,6 +343,36 @@ __global__ __launch_bounds__(256) void output_error_reduce(const double *__restr
     }
 }
 
+// The activation pre-pass: one lane per 16-element group of a bf16 row → Q(X) as bf16, the upper half of K2's float32 y (every BFP value,
+// specials included, has its low 16 bits zero; fmt 0 is the identity on bf16 input).  Rows walk gridDim.y; a group past `cols` reads
+// zero padding and stores only its live elements.  F is the format code (a template parameter: indexed at run time, the group
+// constants would live in LDS).
+template <int F>
+__global__ __launch_bounds__(256) void quantize_rows_bf16(const uint16_t *__restrict__ x, int64_t rows, int64_t cols, int64_t ld,
+                                                          uint16_t *__restrict__ y, int64_t ldy, int vec_ok, int vec_ok_y)
+{
+    const int64_t col0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * kGroup;
+    if (col0 >= cols) return;
+    for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {
+        uint32_t u[kGroup];
+        Loader<uint16_t>::group(x, row, col0, rows, cols, ld, vec_ok != 0, u);
+        const uint32_t E = group_shared_exp(u);
+        const bool fast = (E - 80u) <= 100u;
+        const GroupConsts g = group_consts(fast ? E : 127u);
+        uint32_t o[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) o[i] = quant_bits(F, u[i], E, fast, g);
+        uint16_t *yr = y + row * ldy + col0;
+        if (col0 + kGroup <= cols && vec_ok_y) {
+            store_image(yr, o);
+        } else {
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i)
+                if (col0 + i < cols) yr[i] = (uint16_t)(o[i] >> 16);
+        }
+    }
+}
+
 } // namespace
 } // namespace mtq
 
@@ -317,17 +384,20 @@ extern "C" size_t mtq_output_error_scratch_doubles(int64_t m, int64_t n)
     return (size_t)(((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN)) * kRecord;
 }
 
-extern "C" int mtq_output_error(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
-                                const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
-                                double *sums, double *scratch, size_t scratch_doubles, void *stream)
+// The checks and the launch of both LOE entries; qx = mtq_output_error_qx (xq, ldxq), otherwise mtq_output_error exactly.
+static int launch_output_error(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
+                               const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
+                               double *sums, double *scratch, size_t scratch_doubles, void *stream, bool qx, const void *xq, int64_t ldxq)
 {
     if (!x || !w || !sums || !scratch) return fail(MTQ_ERR_INVALID, "null argument");
+    if (qx && !xq) return fail(MTQ_ERR_INVALID, "xq is null");
     if (w_dtype != MTQ_DTYPE_BF16 && w_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "w_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
     if (recorded && rec_dtype != MTQ_DTYPE_BF16 && rec_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "rec_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
     if ((fmt_mask & ~MTQ_MASK_ALL) != 0) return fail(MTQ_ERR_UNSUPPORTED, "fmt_mask may name only bf16|bfp8|bfp4|bfp2 (bits 0..3)");
     if (m <= 0 || n <= 0 || k <= 0) return fail(MTQ_ERR_INVALID, "m, n and k must be positive (empty operands are handled by the caller)");
     if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
     if (ldw < k) return fail(MTQ_ERR_INVALID, "ldw < k");
+    if (qx && ldxq < k) return fail(MTQ_ERR_INVALID, "ldxq < k");
     if (recorded && ldr < n) return fail(MTQ_ERR_INVALID, "ldr < n");
     if (m > (int64_t)1 << 40 || n > (int64_t)1 << 30 || k > (int64_t)1 << 30) return fail(MTQ_ERR_INVALID, "matrix too large");
     const int64_t blocks = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
@@ -348,13 +418,68 @@ extern "C" int mtq_output_error(const void *x, int64_t m, int64_t k, int64_t ldx
     const int64_t map_w = (k + kTile - 1) / kTile;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)blocks);
+    const uint16_t *xp = static_cast<const uint16_t *>(x), *xqp = static_cast<const uint16_t *>(xq);
+    const int rec_f32 = rec_dtype == MTQ_DTYPE_F32;
+    if (qx) {
+        const int xq_vec = reinterpret_cast<uintptr_t>(xq) % 16 == 0 && ldxq % 8 == 0;
+        if (f32w)
+            hipLaunchKernelGGL((output_error_kernel<float, true>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, static_cast<const float *>(w), n,
+                                 ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, xqp, ldxq, xq_vec);
+        else
+            hipLaunchKernelGGL((output_error_kernel<uint16_t, true>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, static_cast<const uint16_t *>(w),
+                                 n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, xqp, ldxq, xq_vec);
+        if (int rc = check_launch("mtq_output_error_qx")) return rc;
+        hipLaunchKernelGGL(output_error_reduce, dim3(kRecord), dim3(256), 0, st, scratch, blocks, sums, smask);
+        return check_launch("mtq_output_error_qx (reduce)");
+    }
     if (f32w)
-        hipLaunchKernelGGL(output_error_kernel<float>, grid, dim3(kThreads), 0, st, static_cast<const uint16_t *>(x), m, k, ldx, x_vec,
-                           static_cast<const float *>(w), n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_dtype == MTQ_DTYPE_F32, ldr, scratch);
+        hipLaunchKernelGGL((output_error_kernel<float, false>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec,
+                           static_cast<const float *>(w), n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, nullptr, 0, 0);
     else
-        hipLaunchKernelGGL(output_error_kernel<uint16_t>, grid, dim3(kThreads), 0, st, static_cast<const uint16_t *>(x), m, k, ldx, x_vec,
-                           static_cast<const uint16_t *>(w), n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_dtype == MTQ_DTYPE_F32, ldr, scratch);
+        hipLaunchKernelGGL((output_error_kernel<uint16_t, false>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec,
+                           static_cast<const uint16_t *>(w), n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, nullptr, 0, 0);
     if (int rc = check_launch("mtq_output_error")) return rc;
     hipLaunchKernelGGL(output_error_reduce, dim3(kRecord), dim3(256), 0, st, scratch, blocks, sums, smask);
     return check_launch("mtq_output_error (reduce)");
+}
+
+extern "C" int mtq_output_error(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
+                                const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
+                                double *sums, double *scratch, size_t scratch_doubles, void *stream)
+{
+    return launch_output_error(x, m, k, ldx, w, w_dtype, n, ldw, bias, fmt_mask, map, recorded, rec_dtype, ldr, sums, scratch, scratch_doubles,
+                               stream, false, nullptr, 0);
+}
+
+extern "C" int mtq_output_error_qx(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
+                                   const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
+                                   double *sums, double *scratch, size_t scratch_doubles, void *stream, const void *xq, int64_t ldxq)
+{
+    return launch_output_error(x, m, k, ldx, w, w_dtype, n, ldw, bias, fmt_mask, map, recorded, rec_dtype, ldr, sums, scratch, scratch_doubles,
+                               stream, true, xq, ldxq);
+}
+
+extern "C" int mtq_quantize_rows_bf16(const void *x, int64_t rows, int64_t cols, int64_t ld, int fmt, void *y, int64_t ldy, void *stream)
+{
+    if (!x || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (fmt < MTQ_FMT_BF16 || fmt > MTQ_FMT_BFP2) return fail(MTQ_ERR_UNSUPPORTED, "activation format code must be 0..3 (bf16,bfp8,bfp4,bfp2)");
+    if (rows <= 0 || cols <= 0) return fail(MTQ_ERR_INVALID, "rows and cols must be positive (empty tensors are handled by the caller)");
+    if (ld < cols) return fail(MTQ_ERR_INVALID, "ld < cols");
+    if (ldy < cols) return fail(MTQ_ERR_INVALID, "ldy < cols");
+    if (rows > (int64_t)1 << 40 || cols > (int64_t)1 << 30) return fail(MTQ_ERR_INVALID, "matrix too large");
+    if (int rc = require_device()) return rc;
+    const int vec_ok = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ld % 8 == 0;
+    const int vec_ok_y = reinterpret_cast<uintptr_t>(y) % 16 == 0 && ldy % 8 == 0;
+    const int64_t gw = (cols + kGroup - 1) / kGroup;
+    const dim3 grid((unsigned)((gw + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535));
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    uint16_t *yp = static_cast<uint16_t *>(y);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (fmt) {
+    case MTQ_FMT_BF16: hipLaunchKernelGGL(quantize_rows_bf16<0>, grid, dim3(256), 0, st, xp, rows, cols, ld, yp, ldy, vec_ok, vec_ok_y); break;
+    case MTQ_FMT_BFP8: hipLaunchKernelGGL(quantize_rows_bf16<1>, grid, dim3(256), 0, st, xp, rows, cols, ld, yp, ldy, vec_ok, vec_ok_y); break;
+    case MTQ_FMT_BFP4: hipLaunchKernelGGL(quantize_rows_bf16<2>, grid, dim3(256), 0, st, xp, rows, cols, ld, yp, ldy, vec_ok, vec_ok_y); break;
+    default: hipLaunchKernelGGL(quantize_rows_bf16<3>, grid, dim3(256), 0, st, xp, rows, cols, ld, yp, ldy, vec_ok, vec_ok_y); break;
+    }
+    return check_launch("mtq_quantize_rows_bf16");
 }

@@ -96,6 +96,8 @@ SIGNATURES = {
     "mtq_output_error": ("i", "plllpillpuppilppzp", True),
     "mtq_fp4_proxy_scratch_doubles": ("z", "lll", True),
     "mtq_fp4_proxy_sums": ("i", "pillllluppzp", True),
+    "mtq_output_error_qx": ("i", "plllpillpuppilppzppl", True),
+    "mtq_quantize_rows_bf16": ("i", "pllliplp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -591,14 +593,40 @@ def apply_assignment_transposed(x, assignment, out=None):
 OE_SLOTS = ("bf16", "bfp8", "bfp4", "bfp2", "map", "fp0", "recorded")  # include/mtq.h MTQ_OE_* (rows of the sums array)
 
 
-def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded=None, scratch=None):
+X_FORMATS = ("bf16", "bfp8", "bfp4", "bfp2")   # activation formats of the LOE (mtq_quantize_rows_bf16); fp0 and the proxies are not
+
+
+def quantize_rows_bf16(x, fmt: str, out=None):
+    """LOE activation pre-pass (mtq_quantize_rows_bf16) on the current stream: Q(X) of an (m, k) bf16 device tensor with contiguous rows in
+    the row layout, as bf16 (the upper halves of K2's float32 y).  out: an (m, k) bf16 device tensor with contiguous rows (allocated when
+    None), not overlapping x."""
+    if fmt not in X_FORMATS:
+        raise ValueError(f"Unsupported activation format: {fmt} (one of {', '.join(X_FORMATS)})")
+    torch = _torch()
+    _code, _count, _stride, m, k, ld = _matrix(x, (2,))
+    if x.dtype != torch.bfloat16:
+        raise MtqError(f"x must be bfloat16, got {x.dtype}")
+    require_gpu()
+    fn = _entry("mtq_quantize_rows_bf16")
+    if out is None:
+        out = torch.empty((m, k), dtype=torch.bfloat16, device=x.device)
+    _code, _count, _stride, om, ok, ldy = _matrix(out, (2,))
+    if out.dtype != torch.bfloat16 or (om, ok) != (m, k) or out.device != x.device:
+        raise MtqError(f"out must be a ({m}, {k}) bfloat16 tensor with contiguous rows on x's device")
+    check(fn(x.data_ptr(), m, k, ld, FMT_CODE[fmt], out.data_ptr(), ldy, _stream_ptr()))
+    return out
+
+
+def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded=None, scratch=None, xq=None):
     """LOE (mtq_output_error) on the current stream: ADDS the output-error sums of one M-chunk to `sums` (float64 device tensor
     [7, 7], zeroed by the caller once per op).  x: (m, k) bf16 device tensor with contiguous rows; w: (n, k) bf16 / float32 device
     tensor with contiguous rows; bias: float32 [n] or None; assignment: int8 map of w's 32×32 grid or None; recorded: (m, n) bf16 /
-    float32 or None.  scratch: float64 device tensor of at least output_error_scratch(m, n) elements (allocated when None)."""
+    float32 or None.  scratch: float64 device tensor of at least output_error_scratch(m, n) elements (allocated when None).
+    xq: None, or the candidates' activations Q(X) — an (m, k) bf16 device tensor with contiguous rows (quantize_rows_bf16 of x) — which
+    takes mtq_output_error_qx: R keeps x, every candidate but fp0 is fed xq."""
     torch = _torch()
     require_gpu()
-    fn = _entry("mtq_output_error")
+    fn = _entry("mtq_output_error" if xq is None else "mtq_output_error_qx")
     _code, _count, _stride, m, k, ldx = _matrix(x, (2,))
     w_code, _count, _stride, n, kw, ldw = _matrix(w, (2,))
     if x.dtype != torch.bfloat16:
@@ -624,13 +652,19 @@ def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded
         if (rm, rn) != (m, n):
             raise MtqError(f"recorded must be a ({m}, {n}) device tensor with contiguous rows")
         rp = recorded.data_ptr()
+    qx = ()
+    if xq is not None:
+        _code, _count, _stride, qm, qk, ldxq = _matrix(xq, (2,))
+        if xq.dtype != torch.bfloat16 or (qm, qk) != (m, k) or xq.device != x.device:
+            raise MtqError(f"xq must be a ({m}, {k}) bfloat16 tensor with contiguous rows on x's device")
+        qx = (xq.data_ptr(), ldxq)
     need = output_error_scratch(m, n)
     if scratch is None:
         scratch = torch.empty((need,), dtype=torch.float64, device=x.device)
     elif scratch.numel() < need:
         raise MtqError(f"scratch holds {scratch.numel()} doubles, the launch needs {need}")
     check(fn(x.data_ptr(), m, k, ldx, w.data_ptr(), w_code, n, ldw, bp, fmt_mask, mp, rp, rdt, ldr,
-             sums.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream_ptr()))
+             sums.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream_ptr(), *qx))
     return sums
 
 

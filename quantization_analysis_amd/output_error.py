@@ -7,9 +7,14 @@ over all m·n outputs, from the seven float64 sums mtq_columns_from_sums takes (
 searches); the `recorded` row compares R with the op's recorded output.  atol follows np.max: a NaN anywhere in |r − q| (a NaN
 recorded output, an Inf weight giving ∞ − ∞) makes that row's atol NaN on both backends, whichever M-chunk holds it.
 
+Activation formats (x_format): with bfp8 / bfp4 / bfp2 every candidate but fp0 is fed Q(X) = quantize_weight_values(X, x_format) of
+each M-chunk (the row layout: groups of 16 consecutive K elements of one token, so Q(X) does not depend on the chunking) while R keeps
+the raw X: Y_f = Q(X)·Ŵ_fᵀ (+ b), the bf16 row Q(X)·bf16(W)ᵀ (+ b).  x_format = "bf16" (the default) is X as recorded.
+
 Backends:
   * hip       — csrc/mtq_output_error.hip: one pass per M-chunk with every candidate's W image built on the fly in LDS, the sums
-                reduced in the epilogue; neither Ŵ nor Y is materialised;
+                reduced in the epilogue; neither Ŵ nor Y is materialised.  A BFP x_format adds one row pre-pass per chunk that writes
+                Q(X) as bf16, and the pass takes it as the candidates' A operand;
   * emulation — the same contract on the host in float64 (torch), from quantization_formats.quantize_weight_values: the oracle of
                 the GPU tests and the route for small CPU runs.
 """
@@ -30,6 +35,7 @@ FORMAT_BYTES_PER_ELEM = {"bf16": 2.0, "bfp8": 1.088, "bfp4": 0.50097, "bfp2": 0.
 SLOTS = ("bf16", "bfp8", "bfp4", "bfp2", "map", "fp0", "recorded")  # include/mtq.h MTQ_OE_*
 BACKENDS = ("emulation", "hip")
 MIXED_ALGOS = {"mixed-tile-greedy", "mixed-tile-random", "mixed-tile-threshold"}
+X_FORMATS = ("bf16", "bfp8", "bfp4", "bfp2")   # activation formats; bf16 = X as recorded
 
 
 @dataclass
@@ -63,6 +69,7 @@ class OpResult:
     x_cast: bool = False
     rows: list = field(default_factory=list)
     skipped: Optional[str] = None
+    x_format: str = "bf16"
 
 
 def check_layout(config) -> None:
@@ -72,6 +79,20 @@ def check_layout(config) -> None:
     if config.algorithm == "transpose" or str((config.params or {}).get("layout", "rows")) == "transpose":
         raise ValueError("layer output error supports only the row layout: compression configs with \"layout\": \"transpose\" "
                          "(or the transpose algorithm) are not supported")
+
+
+def check_x_format(x_format: str) -> None:
+    if x_format not in X_FORMATS:
+        raise ValueError(f"Unsupported activation format {x_format!r}. Supported: {', '.join(X_FORMATS)}")
+
+
+def quantize_x(x, x_format: str):
+    """Q(X) of one (m, k) chunk on the host as a float64 torch tensor: quantize_weight_values of its float32 values in the row layout."""
+    import torch
+
+    check_x_format(x_format)
+    x32 = x.float().cpu().numpy()
+    return torch.from_numpy(quantize_weight_values(x32, x_format).astype(np.float64))
 
 
 def search_map(w, config, backend: str, name: str = "weight") -> Optional[MapCandidate]:
@@ -120,9 +141,11 @@ def _fold64(acc: np.ndarray, r, q) -> None:
         acc[6] = np.maximum(acc[6], float(d.max()))
 
 
-def emulation_sums(chunk_iter: Iterable, w, formats, bias=None, map_y=None) -> tuple[np.ndarray, int, bool, bool]:
+def emulation_sums(chunk_iter: Iterable, w, formats, bias=None, map_y=None, x_format: str = "bf16") -> tuple[np.ndarray, int, bool, bool]:
     """Float64 host route → (sums [7, 7] in SLOTS order, m, any recorded output seen, any cast)."""
     import torch
+
+    check_x_format(x_format)
 
     w32 = np.asarray(w.float().cpu().numpy() if hasattr(w, "cpu") else w, dtype=np.float32)
     w64 = torch.from_numpy(w32.astype(np.float64))
@@ -140,8 +163,9 @@ def emulation_sums(chunk_iter: Iterable, w, formats, bias=None, map_y=None) -> t
         r = x64 @ w64.T
         if b64 is not None:
             r = r + b64
+        xq64 = x64 if x_format == "bf16" else quantize_x(ch.x, x_format)
         for slot, wh in what.items():
-            q = x64 @ wh.T
+            q = xq64 @ wh.T
             if b64 is not None:
                 q = q + b64
             _fold64(sums[SLOTS.index(slot)], r, q)
@@ -155,11 +179,14 @@ def emulation_sums(chunk_iter: Iterable, w, formats, bias=None, map_y=None) -> t
     return sums, m, seen_rec, cast
 
 
-def hip_sums(chunk_iter: Iterable, w, formats, bias=None, assignment=None) -> tuple[np.ndarray, int, bool, bool]:
-    """The fused kernel over every chunk, partial sums carried on the device → the same as emulation_sums."""
+def hip_sums(chunk_iter: Iterable, w, formats, bias=None, assignment=None, x_format: str = "bf16") -> tuple[np.ndarray, int, bool, bool]:
+    """The fused kernel over every chunk, partial sums carried on the device → the same as emulation_sums.  A BFP x_format quantises
+    each chunk's X into one reused bf16 buffer first."""
     import torch
 
     from . import hip_backend as hb
+
+    check_x_format(x_format)
 
     dev = torch.device("cuda", torch.cuda.current_device())
     wd = w.to(dev) if w.dtype in (torch.bfloat16, torch.float32) else w.float().to(dev)
@@ -168,7 +195,7 @@ def hip_sums(chunk_iter: Iterable, w, formats, bias=None, assignment=None) -> tu
     ad = None if assignment is None else torch.from_numpy(np.ascontiguousarray(assignment, dtype=np.int8)).to(dev)
     mask = hb.fmt_mask([f for f in formats if f in MIXED_TILE_FORMATS])
     sums = torch.zeros((len(SLOTS), 7), dtype=torch.float64, device=dev)
-    scratch = None
+    scratch = xq_buf = None
     m, seen_rec, cast = 0, False, False
     for ch in chunk_iter:
         xd = ch.x.to(dev, non_blocking=False).contiguous()
@@ -181,7 +208,12 @@ def hip_sums(chunk_iter: Iterable, w, formats, bias=None, assignment=None) -> tu
         need = hb.output_error_scratch(int(xd.shape[0]), int(wd.shape[0]))
         if scratch is None or scratch.numel() < need:
             scratch = torch.empty((need,), dtype=torch.float64, device=dev)
-        hb.output_error(xd, wd, mask, sums, bias=bd, assignment=ad, recorded=rd, scratch=scratch)
+        xq = None
+        if x_format != "bf16":
+            if xq_buf is None or xq_buf.numel() < xd.numel():
+                xq_buf = torch.empty((xd.numel(),), dtype=torch.bfloat16, device=dev)
+            xq = hb.quantize_rows_bf16(xd, x_format, out=xq_buf[: xd.numel()].view(xd.shape))
+        hb.output_error(xd, wd, mask, sums, bias=bd, assignment=ad, recorded=rd, scratch=scratch, xq=xq)
         m += int(ch.x.shape[0])
         cast = cast or ch.cast
     torch.cuda.synchronize()
@@ -203,17 +235,19 @@ def rows_from_sums(sums: np.ndarray, m: int, n: int, k: int, formats, map_cand: 
     return rows
 
 
-def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation", chunk_rows: int = 16384) -> OpResult:
+def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation", chunk_rows: int = 16384,
+                x_format: str = "bf16") -> OpResult:
     """One op of `select_ops` → its rows (or the reason it is skipped).  formats ⊆ SUPPORTED_FORMATS; config: a CompressionConfig
-    whose mixed-tile algorithm adds the map candidate (None = pure formats only)."""
+    whose mixed-tile algorithm adds the map candidate (None = pure formats only); x_format: the candidates' activation format."""
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {', '.join(BACKENDS)}")
+    check_x_format(x_format)
     check_layout(config)
     bad = [f for f in formats if f not in SUPPORTED_FORMATS]
     if bad:
         raise ValueError(f"Unsupported format(s) {bad}. Supported: {', '.join(SUPPORTED_FORMATS)}")
     shape, _ = index.shape_dtype(op.weight)
-    res = OpResult(op=op.op, weight=op.weight, shape=tuple(shape), splits=op.splits)
+    res = OpResult(op=op.op, weight=op.weight, shape=tuple(shape), splits=op.splits, x_format=x_format)
     why = check_op(op, tuple(shape))
     if why is not None:
         res.skipped = why
@@ -234,9 +268,9 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
     map_cand = search_map(w, config, backend, op.weight)
     it = chunks(op, k, n, chunk_rows)
     if backend == "hip":
-        sums, m, seen_rec, cast = hip_sums(it, w, formats, bias, None if map_cand is None else map_cand.assignment)
+        sums, m, seen_rec, cast = hip_sums(it, w, formats, bias, None if map_cand is None else map_cand.assignment, x_format)
     else:
-        sums, m, seen_rec, cast = emulation_sums(it, w, formats, bias, None if map_cand is None else map_cand.y)
+        sums, m, seen_rec, cast = emulation_sums(it, w, formats, bias, None if map_cand is None else map_cand.y, x_format)
     res.m, res.x_cast = m, cast
     res.rows = rows_from_sums(sums, m, n, k, formats, map_cand, seen_rec)
     return res

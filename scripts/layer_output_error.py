@@ -2,7 +2,7 @@
 """Layer-output error of quantised weights on recorded activations (the consumer of the files the reference's
 scripts/generate_deepseek_layer0_io.py writes).  For every selected op: R = X·Wᵀ (+ b) against Y_f = X·Ŵ_fᵀ (+ b) for each format
 and for the map of the compression config's mixed-tile algorithm, as pcc / mae / atol over all outputs, plus a `recorded` row
-(R against the recorded output).  Weights come from quantization_analysis_amd.model_source (synthetic presets or a local safetensors
+(R against the recorded output).  --x-format bfp8 / bfp4 / bfp2 feeds every candidate BFP-quantised activations Q(X) (R keeps X).  Weights come from quantization_analysis_amd.model_source (synthetic presets or a local safetensors
 directory); io_root is a directory in the reference's layout or `synthetic:<tokens>[:seed]`.
 
   python scripts/layer_output_error.py /path/to/DeepSeek-R1 /path/to/io model.layers.0.mlp --backend hip -c bf16 bfp8 bfp4 bfp2 \\
@@ -21,7 +21,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from quantization_analysis_amd.compression_algorithms import load_compression_config
 from quantization_analysis_amd.layer_io import select_ops
 from quantization_analysis_amd.model_source import build_model_index, resolve_format_list
-from quantization_analysis_amd.output_error import BACKENDS, check_layout, evaluate_op
+from quantization_analysis_amd.output_error import BACKENDS, X_FORMATS, check_layout, evaluate_op
 from quantization_analysis_amd.quantization_formats import BASE_FORMATS as SUPPORTED_FORMATS  # no proxy rows here
 
 
@@ -37,6 +37,8 @@ def parse_args(argv=None):
     p.add_argument("--split", choices=["calibration", "test", "all"], default="all")
     p.add_argument("--max-samples", type=int, default=None, help="First N samples of the split (by sample index).")
     p.add_argument("--chunk-rows", type=int, default=16384, help="Activation rows per kernel launch (partial sums are carried).")
+    p.add_argument("--x-format", choices=list(X_FORMATS), default="bf16",
+                   help="Activation format the candidates see: bf16 = X as recorded; bfp* = Q(X) in the row layout (R keeps X).")
     p.add_argument("--out-dir", default="results/layer_output_error")
     return p.parse_args(argv)
 
@@ -61,12 +63,13 @@ def main(argv=None) -> int:
     out_dir.mkdir(parents=True, exist_ok=True)
     records, csv_rows = [], []
     for op in ops:
-        res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows)
+        res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows, args.x_format)
         if res.skipped:
             skipped.append((op.op, res.skipped))
             continue
         n, k = res.shape
-        print(f"\n{res.op}  W {n}x{k}  M {res.m}  splits {','.join(res.splits)}{'  (X cast to bf16)' if res.x_cast else ''}")
+        xf = f"  X {res.x_format}" if res.x_format != "bf16" else ""
+        print(f"\n{res.op}  W {n}x{k}{xf}  M {res.m}  splits {','.join(res.splits)}{'  (X cast to bf16)' if res.x_cast else ''}")
         print(f"{'candidate':<28} | {'bytes':>14} | {'pcc':>12} | {'mae':>12} | {'atol':>12}")
         print("-" * 90)
         for r in res.rows:
@@ -83,7 +86,7 @@ def main(argv=None) -> int:
         w.writerow(["op", "candidate", "bytes", "pcc", "mae", "atol", "M", "N", "K"])
         w.writerows(csv_rows)
     doc = {"repo_or_url": args.repo_or_url, "io_root": args.io_root, "backend": args.backend, "formats": formats,
-           "compression_config": args.compression_config, "split": args.split, "max_samples": args.max_samples,
+           "compression_config": args.compression_config, "split": args.split, "max_samples": args.max_samples, "x_format": args.x_format,
            "ops": records, "skipped": [{"op": o, "reason": r} for o, r in skipped]}
     (out_dir / "layer_output_error.json").write_text(json.dumps(doc, indent=2))
     print(f"\nwrote {out_dir / 'layer_output_error.csv'} and {out_dir / 'layer_output_error.json'}")

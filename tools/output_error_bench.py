@@ -7,8 +7,10 @@ candidates bf16, bfp8, bfp4, bfp2 and the reference.
   unfused : per format K2 → bf16 Ŵ → torch.matmul (bf16 out) → torch float64 reductions of the seven sums; the reference
             R = X·bf16(W)ᵀ by one torch.matmul.  (Cheaper than the contract: R and Y are rounded to bf16.)
 TFLOP/s counts 2·M·N·K per candidate GEMM (4 formats + the reference).
+--x-format bfp8 / bfp4 / bfp2: `fused` is the activation pre-pass (mtq_quantize_rows_bf16) plus one mtq_output_error_qx launch; the row
+also reports the pre-pass alone (prepass_ms) and the W-only launch of the same session (w_only_ms), and qx_ratio = fused / W-only.
 
-  python tools/output_error_bench.py [--tokens 12800] [--reps 3] [--only mlp] [--json out.json]
+  python tools/output_error_bench.py [--tokens 12800] [--reps 3] [--only mlp] [--x-format bfp8] [--json out.json]
 """
 from __future__ import annotations
 
@@ -61,6 +63,7 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--only", choices=["all", "mlp"], default="all")
     ap.add_argument("--no-unfused", action="store_true")
+    ap.add_argument("--x-format", choices=list(hb.X_FORMATS), default="bf16", help="the candidates' activation format (bf16: X as is)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -85,15 +88,26 @@ def main() -> int:
             sums.zero_()
             hb.output_error(x, w, mask, sums, scratch=scratch)
 
-        t_f = _time(fused, args.reps)
-        flop = 2.0 * args.tokens * n * k * (len(FMTS) + 1)
+        xq = torch.empty_like(x)
+
+        def fused_qx():
+            sums.zero_()
+            hb.output_error(x, w, mask, sums, scratch=scratch, xq=hb.quantize_rows_bf16(x, args.x_format, out=xq))
+
+        qx = args.x_format != "bf16"
+        t_f = _time(fused_qx if qx else fused, args.reps)
+        flop = 2.0 * args.tokens * n * k * (len(FMTS) + 1 + (1 if qx else 0))
         row = {"op": name, "N": n, "K": k, "M": args.tokens, "fused_ms": t_f * 1e3, "fused_tflops": flop / t_f / 1e12}
+        if qx:
+            t_p = _time(lambda: hb.quantize_rows_bf16(x, args.x_format, out=xq), max(args.reps, 10))
+            t_w = _time(fused, args.reps)
+            row.update({"x_format": args.x_format, "prepass_ms": t_p * 1e3, "w_only_ms": t_w * 1e3, "qx_ratio": t_f / t_w})
         if not args.no_unfused:
             t_u = _time(lambda: unfused(x, w), args.reps)
             row.update({"unfused_ms": t_u * 1e3, "unfused_tflops": flop / t_u / 1e12, "speedup": t_u / t_f})
         rows.append(row)
         print(json.dumps(row), flush=True)
-        del w, x, scratch
+        del w, x, xq, scratch
         torch.cuda.empty_cache()
     if args.json:
         Path(args.json).parent.mkdir(parents=True, exist_ok=True)
