@@ -8,7 +8,7 @@ stats pass (K1 on the GPU for backend "hip") yields per-tile raw sums for every 
 pcc / mae / atol are those sums added up under its map — O(tiles) per sample, no re-quantisation.  The draws come
 from mtq_rng_integers, a bit-compatible restatement of Generator.integers (pinned against NumPy in
 tests/test_capi_host.py), so the maps are the reference's maps.  The reference scores in float32; a sample whose
-float64 score is within `SCORE_BAND` of the threshold, or of the incumbent it is compared with, is re-scored with
+float64 score is within `score_band(n)` of the threshold, or of the incumbent it is compared with, is re-scored with
 the literal float32 expression on its reconstruction (K3) so that the selection is the reference's selection.
 """
 from __future__ import annotations
@@ -21,7 +21,15 @@ from .mixed_tile_greedy import parse_tile_formats
 from .tile_search import TileStats, TransposedInput, columns_from_stats, compute_tile_stats, parse_layout, reconstruct, run_in_layout
 from .tile_utils import MIXED_TILE_BYTES_PER_ELEM, MIXED_TILE_FORMATS, mixed_tile_total_bytes
 
-SCORE_BAND = 1e-5  # |float64-moment score − float32 whole-tensor score| stays below this (relative to max(1, |thr|))
+SCORE_BAND = 1e-5        # the least half-width of the re-scoring band (relative to max(1, |thr|))
+SCORE_BAND_SQRT_N = 4.0  # c of score_band: NumPy's float32 pcc of n elements measured up to 0.6·2^-24·√n from float64
+
+
+def score_band(n: int) -> float:
+    """Half-width (relative to max(1, |thr|)) around which a sample's score is re-scored with the reference's float32 expression:
+    max(SCORE_BAND, c·2^-24·√n).  A model of how far NumPy's float32 pcc / mean of n elements strays from the float64 value the
+    columns carry (pairwise sums and BLAS dots lose ~2^-24·√n), not a bound."""
+    return max(SCORE_BAND, SCORE_BAND_SQRT_N * 2.0 ** -24 * float(np.sqrt(n)))
 
 
 def _host_f32(x) -> np.ndarray:
@@ -31,7 +39,7 @@ def _host_f32(x) -> np.ndarray:
 
 
 def random_search(ts: TileStats, xf, tile_formats: list[str], metric: str, threshold: float, iters: int, seed: int,
-                  quantizer, band: float = SCORE_BAND):
+                  quantizer, band: float | None = None):
     """reference :112-173 on a TileStats → (int8 (tiles_h, tiles_w) map, samples, number of literal re-scores)."""
     from .. import hip_backend as hb
 
@@ -39,7 +47,7 @@ def random_search(ts: TileStats, xf, tile_formats: list[str], metric: str, thres
                              dtype=np.int8)  # :113-116
     rng = hb.NumpyCompatRng(seed)  # :117 — seed 0 is an ordinary seed for this algorithm
     bytes_per_elem = np.asarray([MIXED_TILE_BYTES_PER_ELEM[f] for f in MIXED_TILE_FORMATS], dtype=np.float32)  # :118-126
-    width = band * max(1.0, abs(threshold))
+    width = (score_band(ts.numel) if band is None else band) * max(1.0, abs(threshold))
     maps: list[np.ndarray] = []
     literal: dict[int, float] = {}
     x_host = None

@@ -241,13 +241,24 @@ def reconstruct(ts: TileStats, assignment: np.ndarray, quantizer: Quantizer):
 
         y = hb.unflatten(hb.apply_assignment(ts.x2d, a), ts.shape_info)
         return y.cpu().numpy() if ts.input_was_numpy else y
+    return unflatten_2d(_reconstruct_2d(ts, a, quantizer), ts.shape_info)
+
+
+def _reconstruct_2d(ts: TileStats, assignment: np.ndarray, quantizer: Optional[Quantizer] = None):
+    """y of `assignment` in the layout of ts.x2d (device float32 for hip, a padded vector's pads included)."""
+    a = np.asarray(assignment, dtype=np.int8).reshape(ts.tiles_h, ts.tiles_w)
+    if ts.backend == "hip":
+        from .. import hip_backend as hb
+
+        return hb.apply_assignment_transposed(ts.x2d, a) if ts.transposed else hb.apply_assignment(ts.x2d, a)
+    quantizer = quantizer or Quantizer(ts.backend)
     h, w = ts.x2d.shape
     sel = np.repeat(np.repeat(a, TILE, axis=0), TILE, axis=1)[:h, :w]
     y2d = np.array(ts.x2d, dtype=np.float32, copy=True)
     for idx in np.unique(a):
         yq = quantizer.quantize(ts.x2d, MIXED_TILE_FORMATS[int(idx)])
         y2d = np.where(sel == idx, yq, y2d)
-    return unflatten_2d(y2d, ts.shape_info)
+    return y2d
 
 
 def gather_tiles(ts: TileStats, tile_ids: np.ndarray) -> np.ndarray:
@@ -361,10 +372,15 @@ def columns_from_stats(ts: TileStats, assignment: np.ndarray) -> dict:
     live there and have not been brought to the host anyway (1 B/tile up, seven doubles back)."""
     from .. import hip_backend as hb
 
+    from ..pipeline_common import gated_pcc
+
     amap = np.asarray(assignment, dtype=np.int8).reshape(-1)
     if ts.on_device and ts.host_stats is None:
-        return hb.columns_from_stats_device(ts.stats_dev, ts.mask, amap, float(ts.numel))
-    return hb.columns_from_stats(ts.stats, ts.mask, amap, float(ts.numel))
+        c = hb.columns_from_stats_device(ts.stats_dev, ts.mask, amap, float(ts.numel))
+    else:
+        c = hb.columns_from_stats(ts.stats, ts.mask, amap, float(ts.numel))
+    c["pcc"] = gated_pcc(c["pcc"], c["sums"], ts.numel, ts.x2d, lambda: _reconstruct_2d(ts, amap))
+    return c
 
 
 def tile_scores(ts: TileStats, metric: str) -> np.ndarray:

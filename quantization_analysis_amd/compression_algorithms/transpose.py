@@ -25,6 +25,7 @@ from .tile_utils import MIXED_TILE_FORMATS
 def _columns_hip(v2d, formats: list) -> dict:
     """fmt → {pcc, mae, atol} of the transposed reconstruction of the device matrix v2d, from one K1T pass (float64 moments)."""
     from .. import hip_backend as hb
+    from ..pipeline_common import gated_pcc
     from .tile_search import fp0_columns, fmt_mask
 
     out = {}
@@ -42,7 +43,8 @@ def _columns_hip(v2d, formats: list) -> dict:
                 # that is the true sum: the same records are summed on the host instead
                 host = stats.cpu().numpy() if host is None else host
                 c = hb.columns_from_stats(host, mask, amap, float(v2d.numel()))
-            out[f] = {"pcc": c["pcc"], "mae": c["mae"], "atol": c["atol"]}
+            pcc = gated_pcc(c["pcc"], c["sums"], v2d.numel(), v2d, lambda: hb.quantize_transposed(v2d, f))
+            out[f] = {"pcc": pcc, "mae": c["mae"], "atol": c["atol"]}
     if "fp0" in formats:
         pcc, mae, atol = fp0_columns(v2d)
         out["fp0"] = {"pcc": pcc, "mae": mae, "atol": atol}

@@ -514,15 +514,19 @@ def fp4_proxy_sums(x, formats, out=None, scratch=None):
 def fp4_proxy_columns(x, formats, elem_count: float | None = None) -> list:
     """fmt → (pcc, mae, atol) of each proxy in `formats` for every matrix of x (a list of dicts, one per matrix), from one
     fp4_proxy_sums launch; elem_count defaults to rows × cols (a vector's zero padding adds nothing to the sums)."""
+    from .pipeline_common import gated_pcc
+
     s = fp4_proxy_sums(x, formats)
     host = s.reshape(-1, 2, 7).cpu().numpy()
     n = float(elem_count if elem_count is not None else x.shape[-1] * x.shape[-2])
     out = []
-    for sums in host:
+    for m, sums in enumerate(host):
+        xm = x[m] if x.dim() == 3 else x
         cols = {}
         for f in formats:
             c = columns_from_sums(sums[PROXY_FORMATS.index(f)], n)
-            cols[f] = (c["pcc"], c["mae"], c["atol"])
+            pcc = gated_pcc(c["pcc"], c["sums"], n, xm, lambda: quantize(xm, f))
+            cols[f] = (pcc, c["mae"], c["atol"])
         out.append(cols)
     return out
 

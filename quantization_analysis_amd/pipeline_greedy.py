@@ -12,7 +12,7 @@ import numpy as np
 from . import hip_backend as hb
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS, mixed_tile_total_bytes
 from .settings import settings
-from .pipeline_common import KernelTiming, TensorResult, _scan_chunk, _sleep_until, _when_landed, columns_from_sums_batch  # noqa: F401
+from .pipeline_common import KernelTiming, TensorResult, _scan_chunk, _sleep_until, _when_landed, columns_from_sums_batch, gated_pcc  # noqa: F401
 
 
 class GreedyPipeline:
@@ -480,7 +480,9 @@ class GreedyPipeline:
                 pure = {f: tuple(pure_cols[i][j]) for i, f in enumerate(self.pure_formats)} if self.pure_formats else None
                 c = dict(zip(names, counts[j]))
                 cj = cols[j]
-                results.append(TensorResult(first + j, maps[j], c, mixed_tile_total_bytes(c), cj[0], cj[1], cj[2], cj[k], pure))
+                results.append(TensorResult(first + j, maps[j], c, mixed_tile_total_bytes(c), cj[0], cj[1], cj[2], cj[k], pure, sums=sums[0][j].copy()))
+                for i, f in enumerate(self.pure_formats):
+                    self._gate_pure(enq, results[-1], f, sums[1 + i][j].copy())
             if enq.get("lazy"):
                 listed = int(b["n_listed_host"][first // self.chunk])
                 self.listed_tiles += listed
@@ -498,6 +500,8 @@ class GreedyPipeline:
                 r = results[len(results) - n + j]
                 r.assignment, r.counts, r.tile_bytes = amap.reshape(th, tw), c, mixed_tile_total_bytes(c)
                 r.pcc, r.mae, r.atol, r.metric_value = out["pcc"], out["mae"], out["atol"], out[self.metric]
+                r.sums = np.asarray(out["sums"])
+            self._gate_searched(enq, results[len(results) - n:])
             self.host_seconds["wait"] += t1 - t0
             self.host_seconds["wrap"] += time.perf_counter() - t1
             if settings().pipe_trace:
@@ -534,12 +538,15 @@ class GreedyPipeline:
                 full = enq["dev"][first:first + n].cpu().numpy()
                 results.extend(_scan_chunk(*self._scan_args(enq, first, n, full, enq["host_mask"] & ~hb.MASK_SLIM)))
         self._open.pop(0)
-        enq["x"] = None
         t_scanned = time.perf_counter()
+        if not enq["slim"]:
+            self._gate_searched(enq, results)
         if enq["slim"] or self.pure_formats:
-            self._launch_columns(enq, results)
+            self._launch_columns(enq, results)   # resolve() drops x once it has gated these columns
             if not defer_columns:
                 self.resolve(enq)
+        else:
+            enq["x"] = None
         if settings().pipe_trace:
             print(f"[pipe] finish (host route) {len(results)} tensors: scans collected after {1e3 * (t_scanned - t_fin):.2f} ms, columns after {1e3 * (time.perf_counter() - t_scanned):.2f} ms", flush=True)
         return results
@@ -623,15 +630,45 @@ class GreedyPipeline:
         if enq["slim"]:
             cols = columns_from_sums_batch(sums[0], float(enq["numel"]))
             k = {"pcc": 0, "mae": 1, "atol": 2}[self.metric]
-            for r, c in zip(results, cols):
-                r.pcc, r.mae, r.atol, r.metric_value = float(c[0]), float(c[1]), float(c[2]), float(c[k])
+            for r, c, s in zip(results, cols, sums[0]):
+                r.pcc, r.mae, r.atol, r.metric_value, r.sums = float(c[0]), float(c[1]), float(c[2]), float(c[k]), s.copy()
+            self._gate_searched(enq, results)
         for j, f in enumerate(self.pure_formats):
             cols = columns_from_sums_batch(sums[1 + j], float(enq["numel"]))
-            for r, c in zip(results, cols):
+            for r, c, s in zip(results, cols, sums[1 + j]):
                 if r.pure is None:
                     r.pure = {}
                 r.pure[f] = (float(c[0]), float(c[1]), float(c[2]))
+                self._gate_pure(enq, r, f, s)
         enq["dev"] = None
+        enq["x"] = None
+
+    def _y(self, x2d, assignment):
+        """y of a map in the batch's layout (K3, or K3T over X read in place), X's shape."""
+        return hb.apply_assignment_transposed(x2d, assignment) if self.transposed else hb.apply_assignment(x2d, assignment)
+
+    def _gate_searched(self, enq: dict, results: list) -> None:
+        """The searched maps' pcc columns through gated_pcc (pipeline_common): recomputed centred where the moment form of a float32
+        tensor is too ill-conditioned.  The scan's own decisions are untouched."""
+        x3d = enq.get("x")
+        if x3d is None or x3d.dtype != self.torch.float32:
+            return
+        for r in results:
+            if r.sums is None:
+                continue
+            x = x3d[r.index]
+            r.pcc = gated_pcc(r.pcc, r.sums, enq["numel"], x, lambda: self._y(x, r.assignment))
+            if self.metric == "pcc":
+                r.metric_value = r.pcc
+
+    def _gate_pure(self, enq: dict, r, fmt: str, sums) -> None:
+        x3d = enq.get("x")
+        if x3d is None or x3d.dtype != self.torch.float32:
+            return
+        x = x3d[r.index]
+        pcc, mae, atol = r.pure[fmt]
+        amap = np.full(r.assignment.size, MIXED_TILE_FORMATS.index(fmt), dtype=np.int8).reshape(r.assignment.shape)
+        r.pure[fmt] = (gated_pcc(pcc, sums, enq["numel"], x, lambda: self._y(x, amap)), mae, atol)
 
     def _warm_device_scan(self, device) -> None:
         """One-time costs of the device-scan route, paid here instead of inside the first batches: every scan stream's hardware queue

@@ -12,7 +12,7 @@ import numpy as np
 from . import hip_backend as hb
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS, mixed_tile_total_bytes
 from .settings import settings
-from .pipeline_common import TensorResult, columns_from_sums_batch
+from .pipeline_common import TensorResult, columns_from_sums_batch, gated_columns
 
 
 class ThresholdPipeline:
@@ -383,8 +383,14 @@ class ThresholdPipeline:
             numel = float(st["numel"])
             grids = [st["hw"]] * count
             maps_of = [maps_all[j] for j in range(count)]
-        cols = columns_from_sums_batch(sums[0], numel)
-        pure_cols = [columns_from_sums_batch(sums[1 + i], numel) for i in range(len(self.pure_formats))]
+        # float32 storage: each pcc through the gate of pipeline_common (centred recomputation from x and y where the moment form is
+        # too ill-conditioned); x is still resident here
+        xs = rg["mats"] if rg else st["x"]
+        ys = hb.apply_assignment_transposed if self.transposed else hb.apply_assignment
+        cols = gated_columns(columns_from_sums_batch(sums[0], numel), sums[0], numel, xs, lambda j: ys(xs[j], maps_of[j].reshape(grids[j])))
+        pure_cols = [gated_columns(columns_from_sums_batch(sums[1 + i], numel), sums[1 + i], numel, xs,
+                                   lambda j, c=MIXED_TILE_FORMATS.index(f): ys(xs[j], np.full(grids[j], c, dtype=np.int8)))
+                     for i, f in enumerate(self.pure_formats)]
         results: list[TensorResult] = []
         for j in range(count):
             counts = {f: int(sums[0][j, 7 + i]) for i, f in enumerate(MIXED_TILE_FORMATS)}   # the column kernel's histogram of the final map

@@ -20,6 +20,7 @@ import numpy as np
 
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS
 from .pipeline import GreedyPipeline, ThresholdPipeline, cpu_budget, default_workers
+from .pipeline_common import gated_pcc
 from .quantization_formats import PROXY_FORMATS, ROW_FORMATS
 from .settings import settings
 
@@ -121,7 +122,8 @@ class ShardEvaluator:
             for f in self.pure:
                 amap = np.full(recs.shape[1], MIXED_TILE_FORMATS.index(f), dtype=np.int8)
                 c = hb.columns_from_stats_device(recs[j], mask, amap, float(numel))
-                cols[f] = (c["pcc"], c["mae"], c["atol"])
+                pcc = gated_pcc(c["pcc"], c["sums"], numel, x3d[j], lambda: hb.quantize(x3d[j], f))
+                cols[f] = (pcc, c["mae"], c["atol"])
             out.append(cols)
         return out
 
