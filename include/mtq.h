@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTQ_VERSION 143 /* 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
+#define MTQ_VERSION 143 /* 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
 
 typedef enum {
     MTQ_OK = 0,
@@ -241,6 +241,32 @@ int mtq_output_error_qx(const void *x, int64_t m, int64_t k, int64_t ldx, const 
  * (MTQ_ERR_UNSUPPORTED).  x and y must not overlap.  csrc/mtq_output_error.hip.
  */
 int mtq_quantize_rows_bf16(const void *x, int64_t rows, int64_t cols, int64_t ld, int fmt, void *y, int64_t ldy, void *stream);
+
+/*
+ * Budget maps, device half (no reference counterpart; quantization_analysis_amd/budget_maps.py holds the host half and the contract).
+ * W is one op's weight, n × k (bf16 or float32, nn.Linear convention); X_cal its calibration activations, m × k bf16; the tiles are the
+ * 32 × 32 row-layout tiles of W, zero padded, and c is a tile's column block.
+ *
+ * Gram blocks — H_c = X[:, 32c : 32c+32]ᵀ · X[:, 32c : 32c+32] as float64 32 × 32 blocks, c = 0 .. ceil(k/32) − 1 (columns past k are zero;
+ * only the diagonal blocks of XᵀX are formed).  x: m × k bf16 on device (ldx >= k); h: device doubles [ceil(k/32)][32][32], h_doubles
+ * their count.  The call ADDS this chunk's blocks to h, so a caller zeroes h once and passes m in chunks.  bf16 products are exact in
+ * f32 and the f32 sums are folded into float64 at least every 256 tokens: an entry is within 2^-16 · (|X|ᵀ|X|)_ab of the exact value.
+ * scratch: device doubles, at least mtq_gram_blocks_scratch_doubles(m, k).  Deterministic: a fixed reduction order, no float atomics.
+ *
+ * Tile error tables — for every tile t = (r, c), t = r · ceil(k/32) + c, and format code f (bf16, bfp8, bfp4, bfp2), with
+ * Δ_f = K2_f(w) − w in float64 (row layout: the Ŵ that K3 builds for a tile coded f) and δ_i row i of the tile in Δ_f:
+ * e_out[t][f] = Σ_i δ_iᵀ H_c δ_i (the tile's share of ‖X·Δᵀ‖²_F without the cross-block terms) and e_w[t][f] = Σ δ², both float64 in a
+ * fixed order.  w: n × k (w_dtype, ldw >= k); h: the Gram blocks of k (h_doubles = ceil(k/32) · 1024); e_out, e_w: device doubles
+ * [tiles][4], table_doubles = tiles · 4; e_w may be NULL.
+ *
+ * A null pointer, m, n or k <= 0, ld < k, a w_dtype that is not BF16 / F32 or a size mismatch returns MTQ_ERR_INVALID before a device
+ * is looked for.  csrc/mtq_budget.hip.
+ */
+size_t mtq_gram_blocks_scratch_doubles(int64_t m, int64_t k);
+int mtq_gram_blocks(const void *x, int64_t m, int64_t k, int64_t ldx, double *h, size_t h_doubles, double *scratch, size_t scratch_doubles,
+                    void *stream);
+int mtq_tile_error_tables(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw, const double *h, size_t h_doubles, double *e_out,
+                          double *e_w, size_t table_doubles, void *stream);
 
 /*
  * K5 dequant_fp8_block (loader) — float8-e4m3fn weights × float32 inverse block scales → float32: the on-load

@@ -98,6 +98,9 @@ SIGNATURES = {
     "mtq_fp4_proxy_sums": ("i", "pillllluppzp", True),
     "mtq_output_error_qx": ("i", "plllpillpuppilppzppl", True),
     "mtq_quantize_rows_bf16": ("i", "pllliplp", True),
+    "mtq_gram_blocks_scratch_doubles": ("z", "ll", True),
+    "mtq_gram_blocks": ("i", "plllpzpzp", True),
+    "mtq_tile_error_tables": ("i", "pilllpzppzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -675,6 +678,50 @@ def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded
 def output_error_scratch(m: int, n: int) -> int:
     """Doubles of scratch one mtq_output_error launch over m × n outputs needs."""
     return int(_entry("mtq_output_error_scratch_doubles")(m, n))
+
+
+def gram_blocks(x, h, scratch=None):
+    """Budget maps' Gram blocks (mtq_gram_blocks) on the current stream: ADDS the diagonal 32 × 32 blocks of XᵀX of one chunk to h.
+    x: (m, k) bf16 device tensor with contiguous rows; h: contiguous float64 device tensor (ceil(k/32), 32, 32), zeroed by the caller
+    once.  scratch: float64 device tensor of at least gram_blocks_scratch(m, k) elements (allocated when None)."""
+    torch = _torch()
+    _code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x.dtype != torch.bfloat16:
+        raise MtqError(f"x must be bfloat16, got {x.dtype}")
+    nb = -(-k // TILE)
+    if h.dtype != torch.float64 or tuple(h.shape) != (nb, TILE, TILE) or not h.is_contiguous() or not h.is_cuda or h.device != x.device:
+        raise MtqError(f"h must be a contiguous float64 tensor of shape ({nb}, 32, 32) on x's device")
+    require_gpu()
+    fn = _entry("mtq_gram_blocks")
+    need = gram_blocks_scratch(m, k)
+    if scratch is None:
+        scratch = torch.empty((max(need, 1),), dtype=torch.float64, device=x.device)
+    elif scratch.dtype != torch.float64 or not scratch.is_contiguous() or not scratch.is_cuda or scratch.numel() < need:
+        raise MtqError(f"scratch must be a contiguous float64 device tensor of at least {need} elements")
+    check(fn(x.data_ptr(), m, k, ldx, h.data_ptr(), h.numel(), scratch.data_ptr(), scratch.numel(), _stream_ptr()))
+    return h
+
+
+def gram_blocks_scratch(m: int, k: int) -> int:
+    """Doubles of scratch one mtq_gram_blocks launch over an (m, k) chunk needs."""
+    return int(_entry("mtq_gram_blocks_scratch_doubles")(m, k))
+
+
+def tile_error_tables(w, h, want_weight: bool = True):
+    """Budget maps' tile error tables (mtq_tile_error_tables) on the current stream → (e_out, e_w or None), float64 device tensors
+    [tiles, 4] indexed by MIXED_TILE_FORMATS code, tiles row-major over w's 32 × 32 grid.  w: (n, k) bf16 / float32 device tensor with
+    contiguous rows; h: its Gram blocks, a contiguous float64 tensor (ceil(k/32), 32, 32) on w's device."""
+    torch = _torch()
+    w_code, _count, _stride, n, k, ldw = _matrix(w, (2,))
+    th, tw = tiles_hw(n, k)
+    if h.dtype != torch.float64 or tuple(h.shape) != (tw, TILE, TILE) or not h.is_contiguous() or not h.is_cuda or h.device != w.device:
+        raise MtqError(f"h must be a contiguous float64 tensor of shape ({tw}, 32, 32) on w's device")
+    require_gpu()
+    fn = _entry("mtq_tile_error_tables")
+    out = torch.empty((2 if want_weight else 1, th * tw, 4), dtype=torch.float64, device=w.device)
+    check(fn(w.data_ptr(), w_code, n, k, ldw, h.data_ptr(), h.numel(), out[0].data_ptr(), out[1].data_ptr() if want_weight else 0,
+             th * tw * 4, _stream_ptr()))
+    return out[0], (out[1] if want_weight else None)
 
 
 def apply_assignment(x2d, assignment, out=None):

@@ -28,7 +28,7 @@ from typing import Iterable, Optional
 import numpy as np
 
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS
-from .layer_io import OpIO, check_op, chunks
+from .layer_io import Chunk, OpIO, check_op, chunks
 from .quantization_formats import BASE_FORMATS as SUPPORTED_FORMATS, quantize_weight_values  # no proxy rows here
 
 FORMAT_BYTES_PER_ELEM = {"bf16": 2.0, "bfp8": 1.088, "bfp4": 0.50097, "bfp2": 0.25097, "fp0": 0.0}  # wq:132-140 (cli.py)
@@ -57,6 +57,7 @@ class Row:
     mae: float
     atol: float
     sums: tuple = ()
+    extra: dict = field(default_factory=dict)   # budget maps: bits, basis, calib_tokens, predicted_sse_calib
 
 
 @dataclass
@@ -70,6 +71,8 @@ class OpResult:
     rows: list = field(default_factory=list)
     skipped: Optional[str] = None
     x_format: str = "bf16"
+    budget_skipped: list = field(default_factory=list)   # (candidate, reason) of budget maps that were not made
+    calib_splits: list = field(default_factory=list)
 
 
 def check_layout(config) -> None:
@@ -236,12 +239,22 @@ def rows_from_sums(sums: np.ndarray, m: int, n: int, k: int, formats, map_cand: 
 
 
 def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation", chunk_rows: int = 16384,
-                x_format: str = "bf16") -> OpResult:
+                x_format: str = "bf16", budgets=(), calib: Optional[OpIO] = None) -> OpResult:
     """One op of `select_ops` → its rows (or the reason it is skipped).  formats ⊆ SUPPORTED_FORMATS; config: a CompressionConfig
-    whose mixed-tile algorithm adds the map candidate (None = pure formats only); x_format: the candidates' activation format."""
+    whose mixed-tile algorithm adds the map candidate (None = pure formats only); x_format: the candidates' activation format.
+    budgets: bits per weight, each adding the maps budget:<bits>:output and budget:<bits>:weight (budget_maps.py) chosen on the
+    calibration activations `calib` (an OpIO of the same op) and evaluated here, after the other rows; bf16 x_format only."""
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {', '.join(BACKENDS)}")
     check_x_format(x_format)
+    budgets = tuple(budgets or ())
+    if budgets:
+        from .budget_maps import check_bits
+
+        if x_format != "bf16":
+            raise ValueError("budget maps are chosen and evaluated on bf16 activations: x_format must be bf16")
+        for b in budgets:
+            check_bits(b)
     check_layout(config)
     bad = [f for f in formats if f not in SUPPORTED_FORMATS]
     if bad:
@@ -273,4 +286,50 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
         sums, m, seen_rec, cast = emulation_sums(it, w, formats, bias, None if map_cand is None else map_cand.y, x_format)
     res.m, res.x_cast = m, cast
     res.rows = rows_from_sums(sums, m, n, k, formats, map_cand, seen_rec)
+    if budgets:
+        _budget_rows(res, index, op, w, bias, formats, backend, chunk_rows, budgets, calib)
     return res
+
+
+def _budget_rows(res: OpResult, index, op: OpIO, w, bias, formats, backend: str, chunk_rows: int, budgets, calib: Optional[OpIO]) -> None:
+    """Appends the budget maps' rows to res (each map its own LOE pass over the evaluation chunks, the map slot alone), or records in
+    res.budget_skipped why a map was not made."""
+    from . import budget_maps as bm
+
+    n, k = res.shape
+    names = [(b, basis, bm.map_name(b, basis)) for b in budgets for basis in bm.BASES]
+    why = "no calibration samples for this op" if calib is None else check_op(calib, (n, k))
+    if why is None:
+        res.calib_splits = calib.splits
+        cal = chunks(calib, k, n, chunk_rows)
+        if backend == "hip":
+            h, m_cal = bm.gram_blocks_hip(cal, k, device=w.device)
+            tables = bm.tile_error_tables_hip(w, h) if m_cal else None
+        else:
+            h, m_cal = bm.gram_blocks_emulation(cal, k)
+            tables = bm.tile_error_tables_emulation(w, h) if m_cal else None
+        if not m_cal:
+            why = "the calibration samples hold no tokens"
+    if why is not None:
+        res.budget_skipped.extend((name, why) for _b, _basis, name in names)
+        return
+    e_out, e_w = tables
+    grid = bm.tiles_hw(n, k)
+    for b, basis, name in names:
+        got = bm.allocate(e_out if basis == "output" else e_w, formats, b, grid)
+        if isinstance(got, str):
+            res.budget_skipped.append((name, got))
+            continue
+        assignment, _counts, tile_bytes = got
+        it = (Chunk(x=ch.x, cast=ch.cast) for ch in chunks(op, k, n, chunk_rows))   # the map slot alone: no recorded output
+        if backend == "hip":
+            sums, m, _rec, _cast = hip_sums(it, w, [], bias, assignment)
+            y = None
+        else:
+            y = bm.reconstruct_emulation(w, assignment)
+            sums, m, _rec, _cast = emulation_sums(it, w, [], bias, y)
+        cand = MapCandidate(name=name, assignment=assignment, y=y, tile_bytes=tile_bytes)
+        row = rows_from_sums(sums, m, n, k, [], cand, False)[0]
+        row.extra = {"bits": float(b), "basis": basis, "calib_tokens": int(m_cal),
+                     "predicted_sse_calib": bm.predicted_sse(e_out, assignment), "assignment": assignment}
+        res.rows.append(row)

@@ -3,7 +3,9 @@
 scripts/generate_deepseek_layer0_io.py writes).  For every selected op: R = X·Wᵀ (+ b) against Y_f = X·Ŵ_fᵀ (+ b) for each format
 and for the map of the compression config's mixed-tile algorithm, as pcc / mae / atol over all outputs, plus a `recorded` row
 (R against the recorded output).  --x-format bfp8 / bfp4 / bfp2 feeds every candidate BFP-quantised activations Q(X) (R keeps X).  Weights come from quantization_analysis_amd.model_source (synthetic presets or a local safetensors
-directory); io_root is a directory in the reference's layout or `synthetic:<tokens>[:seed]`.
+directory); io_root is a directory in the reference's layout or `synthetic:<tokens>[:seed]`.  --budget-bits B ... adds, per B, the
+maps budget:<B>:output and budget:<B>:weight chosen on the calibration activations (--calib-io / --calib-split, quantization_analysis_amd
+/budget_maps.py) and evaluated like every other candidate.
 
   python scripts/layer_output_error.py /path/to/DeepSeek-R1 /path/to/io model.layers.0.mlp --backend hip -c bf16 bfp8 bfp4 bfp2 \\
       --compression-config compression_configs/compression_config.mixed_tile_greedy.example.json --split test --out-dir results/loe
@@ -18,6 +20,9 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
+import numpy as np
+
+from quantization_analysis_amd.budget_maps import bits_tag
 from quantization_analysis_amd.compression_algorithms import load_compression_config
 from quantization_analysis_amd.layer_io import select_ops
 from quantization_analysis_amd.model_source import build_model_index, resolve_format_list
@@ -40,7 +45,20 @@ def parse_args(argv=None):
     p.add_argument("--x-format", choices=list(X_FORMATS), default="bf16",
                    help="Activation format the candidates see: bf16 = X as recorded; bfp* = Q(X) in the row layout (R keeps X).")
     p.add_argument("--out-dir", default="results/layer_output_error")
-    return p.parse_args(argv)
+    p.add_argument("--budget-bits", type=float, nargs="+", default=None, metavar="B",
+                   help="Bits per weight: each adds the maps budget:<B>:output (activation-aware) and budget:<B>:weight (weight-only).")
+    p.add_argument("--calib-io", default=None, help="Calibration activations of the budget maps (default: io_root).")
+    p.add_argument("--calib-split", choices=["calibration", "test", "all"], default="calibration")
+    p.add_argument("--calib-max-samples", type=int, default=None, help="First N calibration samples (by sample index).")
+    p.add_argument("--save-maps", action="store_true", help="Write <out-dir>/maps/<op>/budget_<B>_{output,weight}.npy.")
+    args = p.parse_args(argv)
+    if args.budget_bits:
+        if args.x_format != "bf16":
+            p.error("--budget-bits needs --x-format bf16: the budget maps are chosen and evaluated on bf16 activations")
+        for b in args.budget_bits:
+            if not 0.0 < b <= 16.0:
+                p.error(f"--budget-bits: {b:g} is outside (0, 16]")
+    return args
 
 
 def _fmt(v, spec):
@@ -59,11 +77,18 @@ def main(argv=None) -> int:
     index = build_model_index(args.repo_or_url, revision=args.revision)
     query = " ".join(args.filter_query).strip() or None
     ops, skipped = select_ops(index, args.io_root, query, args.split, args.max_samples)
+    budgets = tuple(args.budget_bits or ())
+    calib_io = args.calib_io or args.io_root
+    calib = {}
+    if budgets:
+        cal_ops, _cal_skipped = select_ops(index, calib_io, query, args.calib_split, args.calib_max_samples)
+        calib = {o.op: o for o in cal_ops}
     out_dir = Path(args.out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     records, csv_rows = [], []
     for op in ops:
-        res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows, args.x_format)
+        res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows, args.x_format,
+                          **({"budgets": budgets, "calib": calib.get(op.op)} if budgets else {}))
         if res.skipped:
             skipped.append((op.op, res.skipped))
             continue
@@ -75,8 +100,21 @@ def main(argv=None) -> int:
         for r in res.rows:
             print(f"{r.candidate:<28} | {_fmt(r.bytes, '14.0f')} | {r.pcc:12.8f} | {r.mae:12.6e} | {r.atol:12.6e}")
             csv_rows.append([res.op, r.candidate, r.bytes, r.pcc, r.mae, r.atol, res.m, n, k])
-        records.append({"op": res.op, "weight": res.weight, "shape": [n, k], "M": res.m, "splits": res.splits, "x_cast": res.x_cast,
-                        "rows": [{"candidate": r.candidate, "bytes": r.bytes, "pcc": r.pcc, "mae": r.mae, "atol": r.atol} for r in res.rows]})
+        rec = {"op": res.op, "weight": res.weight, "shape": [n, k], "M": res.m, "splits": res.splits, "x_cast": res.x_cast,
+               "rows": [{"candidate": r.candidate, "bytes": r.bytes, "pcc": r.pcc, "mae": r.mae, "atol": r.atol,
+                         **{key: v for key, v in r.extra.items() if key != "assignment"}} for r in res.rows]}
+        if budgets:
+            rec["calib_splits"] = res.calib_splits
+            rec["budget_skipped"] = [{"candidate": c, "reason": why} for c, why in res.budget_skipped]
+            for c, why in res.budget_skipped:
+                skipped.append((f"{res.op} {c}", why))
+            if args.save_maps:
+                for r in res.rows:
+                    if "assignment" in r.extra:
+                        d = out_dir / "maps" / res.op
+                        d.mkdir(parents=True, exist_ok=True)
+                        np.save(d / f"budget_{bits_tag(r.extra['bits'])}_{r.extra['basis']}.npy", r.extra["assignment"])
+        records.append(rec)
     if skipped:
         print("\nskipped:")
         for op, why in skipped:
@@ -88,6 +126,9 @@ def main(argv=None) -> int:
     doc = {"repo_or_url": args.repo_or_url, "io_root": args.io_root, "backend": args.backend, "formats": formats,
            "compression_config": args.compression_config, "split": args.split, "max_samples": args.max_samples, "x_format": args.x_format,
            "ops": records, "skipped": [{"op": o, "reason": r} for o, r in skipped]}
+    if budgets:
+        doc.update({"budget_bits": list(budgets), "calib_io": calib_io, "calib_split": args.calib_split,
+                    "calib_max_samples": args.calib_max_samples})
     (out_dir / "layer_output_error.json").write_text(json.dumps(doc, indent=2))
     print(f"\nwrote {out_dir / 'layer_output_error.csv'} and {out_dir / 'layer_output_error.json'}")
     return 0
