@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTQ_VERSION 143 /* 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
+#define MTQ_VERSION 143 /* 0.1.4.7 (optional symbols as well): + mtq_gram_full / _scratch_doubles, mtq_gptq_sweep / _scratch_doubles; 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
 
 typedef enum {
     MTQ_OK = 0,
@@ -267,6 +267,35 @@ int mtq_gram_blocks(const void *x, int64_t m, int64_t k, int64_t ldx, double *h,
                     void *stream);
 int mtq_tile_error_tables(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw, const double *h, size_t h_doubles, double *e_out,
                           double *e_w, size_t table_doubles, void *stream);
+
+/*
+ * GPTQ's error-compensated BFP weights, device half (no reference counterpart; quantization_analysis_amd/gptq.py holds the host half
+ * and the contract).  W is one op's weight, n × k (bf16 or float32, nn.Linear convention); X_cal its calibration activations, m × k bf16.
+ *
+ * Full Gram — H = XᵀX as k × k float64 (row-major, h_doubles = k · k), ADDED into h: a caller zeroes h once and passes m in chunks.
+ * The numerics of mtq_gram_blocks (bf16 MFMA, f32 folded into float64 at least every 256 tokens: an entry within 2^-16 · (|X|ᵀ|X|)_ab);
+ * each entry is formed once and written to (a, b) and (b, a), so a symmetric h stays bitwise symmetric.  scratch: device doubles, at
+ * least mtq_gram_full_scratch_doubles(m, k), which is 0 when the column-block pairs alone fill the device (k >= 5632); a non-null
+ * pointer is still required.  Deterministic: a fixed reduction order, no float atomics.
+ *
+ * Sweep — for every row and column j in order (float64): at the start of a 16-column group E = the largest exponent field of the float32
+ * of the group's current values; q_j = q_E(w_j, code of j's tile) (bf16: RNE of float32(w_j); BFP: the element rule of mtq_quantize with
+ * shared exponent E, an exponent above E saturating to ±(2^M − 1)·step); e_j = (w_j − q_j) / U_jj; w_j' −= e_j · U_jj' for j' > j.
+ * w: n × k (w_dtype, ldw >= k); u: device doubles k × k (u_doubles = k · k), the upper Cholesky factor of the damped inverse Hessian,
+ * only its upper triangle read; codes: int8 [ceil(n/32)][ceil(k/32)] MIXED_TILE_FORMATS codes 0..3 (code_count entries; values are not
+ * checked); out: n × k float32 (ldo >= k) receives Ŵ = q; loss: n doubles receive Σ_j e_j² per row; scratch: device doubles, 16-byte
+ * aligned, at least mtq_gptq_sweep_scratch_doubles(n, k) (e of every row and column).  The summation order of the updates differs from a
+ * column-by-column sweep (a blocked, left-looking update); the rest is the per-element arithmetic above.
+ *
+ * A null pointer, m, n or k <= 0, ld < k, a w_dtype that is not BF16 / F32 or a size mismatch returns MTQ_ERR_INVALID before a device
+ * is looked for.  csrc/mtq_gptq.hip.
+ */
+size_t mtq_gram_full_scratch_doubles(int64_t m, int64_t k);
+int mtq_gram_full(const void *x, int64_t m, int64_t k, int64_t ldx, double *h, size_t h_doubles, double *scratch, size_t scratch_doubles,
+                  void *stream);
+size_t mtq_gptq_sweep_scratch_doubles(int64_t n, int64_t k);
+int mtq_gptq_sweep(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw, const double *u, size_t u_doubles, const int8_t *codes,
+                   size_t code_count, float *out, int64_t ldo, double *loss, double *scratch, size_t scratch_doubles, void *stream);
 
 /*
  * K5 dequant_fp8_block (loader) — float8-e4m3fn weights × float32 inverse block scales → float32: the on-load

@@ -68,6 +68,34 @@ __device__ __forceinline__ uint32_t bfp_elem_bits_rt(uint32_t u, uint32_t shared
     return (u & 0x80000000u) | (exp_out << 23) | (ms << (23u - M));
 }
 
+// bfp_elem_bits_rt with the shared exponent FIXED by the caller (GPTQ's sweep, mtq_gptq.hip): an element whose exponent field is above
+// `shared` saturates to ±(2^M − 1)·step with its sign kept, where bfp_elem_bits_rt returns 0 through the d > 31 wrap.  For
+// e <= shared the two are the same function (quantization_analysis_amd/gptq.py: bfp_fixed_bits).
+__device__ __forceinline__ uint32_t bfp_elem_bits_sat(uint32_t u, uint32_t shared, uint32_t M)
+{
+    const uint32_t shift = 24u - M, round_mask = (1u << shift) - 1u, tie = 1u << (shift - 1u), qmax = (1u << M) - 1u;
+    const uint32_t e = (u >> 23) & 0xFFu;
+    uint32_t man;
+    if (e > shared) {
+        man = qmax;
+    } else {
+        const uint32_t d = shared - e;
+        man = (1u << 23) | (u & 0x007FFFFFu);
+        man = d > 31u ? 0u : (man >> d);
+        const uint32_t rv = man & round_mask;
+        man >>= shift;
+        const uint32_t up = (rv > tie) | ((rv == tie) & (man & 1u));
+        man = min(man + up, qmax);
+        man = e == 0u ? 0u : man;
+    }
+    if (man == 0u) return 0u;
+    const uint32_t msb = 31u - (uint32_t)__clz((int)man);
+    const uint32_t sc = (M - 1u) - msb;
+    const uint32_t ms = (man << (sc + 1u)) & qmax;
+    const uint32_t exp_out = shared - sc;
+    return (u & 0x80000000u) | (exp_out << 23) | (ms << (23u - M));
+}
+
 // format code → y bits with NO divergence between the mixed-tile formats: one BFP evaluation with a per-lane
 // mantissa width, bf16 / fp0 by select.
 __device__ __forceinline__ uint32_t quant_elem_bits_mixed(int fmt, uint32_t u, uint32_t shared)

@@ -101,6 +101,10 @@ SIGNATURES = {
     "mtq_gram_blocks_scratch_doubles": ("z", "ll", True),
     "mtq_gram_blocks": ("i", "plllpzpzp", True),
     "mtq_tile_error_tables": ("i", "pilllpzppzp", True),
+    "mtq_gram_full_scratch_doubles": ("z", "ll", True),
+    "mtq_gram_full": ("i", "plllpzpzp", True),
+    "mtq_gptq_sweep_scratch_doubles": ("z", "ll", True),
+    "mtq_gptq_sweep": ("i", "pilllpzpzplppzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -722,6 +726,62 @@ def tile_error_tables(w, h, want_weight: bool = True):
     check(fn(w.data_ptr(), w_code, n, k, ldw, h.data_ptr(), h.numel(), out[0].data_ptr(), out[1].data_ptr() if want_weight else 0,
              th * tw * 4, _stream_ptr()))
     return out[0], (out[1] if want_weight else None)
+
+
+def gram_full(x, h, scratch=None):
+    """GPTQ's full Gram matrix (mtq_gram_full) on the current stream: ADDS XᵀX of one chunk to h.  x: (m, k) bf16 device tensor with
+    contiguous rows; h: contiguous float64 (k, k) tensor on x's device, zeroed by the caller once.  scratch: float64 device tensor of at
+    least gram_full_scratch(m, k) elements (allocated when None)."""
+    torch = _torch()
+    _code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x.dtype != torch.bfloat16:
+        raise MtqError(f"x must be bfloat16, got {x.dtype}")
+    if h.dtype != torch.float64 or tuple(h.shape) != (k, k) or not h.is_contiguous() or not h.is_cuda or h.device != x.device:
+        raise MtqError(f"h must be a contiguous float64 tensor of shape ({k}, {k}) on x's device")
+    require_gpu()
+    fn = _entry("mtq_gram_full")
+    need = gram_full_scratch(m, k)
+    if scratch is None:
+        scratch = torch.empty((max(need, 1),), dtype=torch.float64, device=x.device)
+    elif scratch.dtype != torch.float64 or not scratch.is_contiguous() or not scratch.is_cuda or scratch.numel() < max(need, 1):
+        raise MtqError(f"scratch must be a contiguous float64 device tensor of at least {max(need, 1)} elements")
+    check(fn(x.data_ptr(), m, k, ldx, h.data_ptr(), h.numel(), scratch.data_ptr(), scratch.numel(), _stream_ptr()))
+    return h
+
+
+def gram_full_scratch(m: int, k: int) -> int:
+    """Doubles of scratch one mtq_gram_full launch over an (m, k) chunk needs (0 when the block pairs alone fill the device)."""
+    return int(_entry("mtq_gram_full_scratch_doubles")(m, k))
+
+
+def gptq_sweep(w, u, codes, out=None, loss=None):
+    """GPTQ's column sweep (mtq_gptq_sweep) on the current stream → (Ŵ float32 (n, k), loss float64 (n,)) device tensors.  w: (n, k)
+    bf16 / float32 device tensor with contiguous rows; u: contiguous float64 (k, k) tensor on w's device (upper triangle read); codes:
+    contiguous int8 (ceil(n/32), ceil(k/32)) device tensor of MIXED_TILE_FORMATS codes 0..3."""
+    torch = _torch()
+    w_code, _count, _stride, n, k, ldw = _matrix(w, (2,))
+    th, tw = tiles_hw(n, k)
+    if u.dtype != torch.float64 or tuple(u.shape) != (k, k) or not u.is_contiguous() or not u.is_cuda or u.device != w.device:
+        raise MtqError(f"u must be a contiguous float64 tensor of shape ({k}, {k}) on w's device")
+    if codes.dtype != torch.int8 or codes.numel() != th * tw or not codes.is_contiguous() or not codes.is_cuda or codes.device != w.device:
+        raise MtqError(f"codes must be a contiguous int8 tensor of {th}x{tw} entries on w's device")
+    if codes.numel() and (int(codes.min()) < 0 or int(codes.max()) > 3):
+        raise MtqError("codes must be MIXED_TILE_FORMATS codes 0..3")
+    require_gpu()
+    fn = _entry("mtq_gptq_sweep")
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=w.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (n, k) or out.stride(1) != 1 or out.device != w.device:
+        raise MtqError(f"out must be a float32 ({n}, {k}) tensor with contiguous rows on w's device")
+    if loss is None:
+        loss = torch.empty((n,), dtype=torch.float64, device=w.device)
+    elif loss.dtype != torch.float64 or loss.numel() != n or not loss.is_contiguous() or loss.device != w.device:
+        raise MtqError(f"loss must be a contiguous float64 tensor of {n} elements on w's device")
+    need = int(_entry("mtq_gptq_sweep_scratch_doubles")(n, k))
+    scratch = torch.empty((need,), dtype=torch.float64, device=w.device)
+    check(fn(w.data_ptr(), w_code, n, k, ldw, u.data_ptr(), u.numel(), codes.data_ptr(), codes.numel(), out.data_ptr(), out.stride(0),
+             loss.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream_ptr()))
+    return out, loss
 
 
 def apply_assignment(x2d, assignment, out=None):

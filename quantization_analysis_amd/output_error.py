@@ -239,11 +239,14 @@ def rows_from_sums(sums: np.ndarray, m: int, n: int, k: int, formats, map_cand: 
 
 
 def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation", chunk_rows: int = 16384,
-                x_format: str = "bf16", budgets=(), calib: Optional[OpIO] = None) -> OpResult:
+                x_format: str = "bf16", budgets=(), calib: Optional[OpIO] = None, gptq: bool = False, gptq_damp: float = 0.01) -> OpResult:
     """One op of `select_ops` → its rows (or the reason it is skipped).  formats ⊆ SUPPORTED_FORMATS; config: a CompressionConfig
     whose mixed-tile algorithm adds the map candidate (None = pure formats only); x_format: the candidates' activation format.
     budgets: bits per weight, each adding the maps budget:<bits>:output and budget:<bits>:weight (budget_maps.py) chosen on the
-    calibration activations `calib` (an OpIO of the same op) and evaluated here, after the other rows; bf16 x_format only."""
+    calibration activations `calib` (an OpIO of the same op) and evaluated here, after the other rows; bf16 x_format only.
+    gptq: adds, after those, the error-compensated weights (gptq.py) built on `calib` with damp gptq_damp: gptq:<f> for each of bfp8 /
+    bfp4 / bfp2 among the formats, gptq:<map name> for the config's map and gptq:budget:<bits>:output for each budget map, each with the
+    bytes of its round-to-nearest counterpart; bf16 x_format only."""
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {', '.join(BACKENDS)}")
     check_x_format(x_format)
@@ -255,6 +258,12 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
             raise ValueError("budget maps are chosen and evaluated on bf16 activations: x_format must be bf16")
         for b in budgets:
             check_bits(b)
+    if gptq:
+        from .gptq import check_damp
+
+        if x_format != "bf16":
+            raise ValueError("GPTQ weights are built and evaluated on bf16 activations: x_format must be bf16")
+        check_damp(gptq_damp)
     check_layout(config)
     bad = [f for f in formats if f not in SUPPORTED_FORMATS]
     if bad:
@@ -288,6 +297,8 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
     res.rows = rows_from_sums(sums, m, n, k, formats, map_cand, seen_rec)
     if budgets:
         _budget_rows(res, index, op, w, bias, formats, backend, chunk_rows, budgets, calib)
+    if gptq:
+        _gptq_rows(res, op, w, bias, formats, map_cand, backend, chunk_rows, budgets, calib, gptq_damp)
     return res
 
 
@@ -332,4 +343,78 @@ def _budget_rows(res: OpResult, index, op: OpIO, w, bias, formats, backend: str,
         row = rows_from_sums(sums, m, n, k, [], cand, False)[0]
         row.extra = {"bits": float(b), "basis": basis, "calib_tokens": int(m_cal),
                      "predicted_sse_calib": bm.predicted_sse(e_out, assignment), "assignment": assignment}
+        res.rows.append(row)
+
+
+def _gptq_outputs(chunk_iter: Iterable, what, bias):
+    """Each chunk with Y = X·Ŵᵀ (+ b) as its recorded output, a float32 device tensor: the fused kernel forms R from W as for every row
+    and compares it with Y in the recorded slot.  X and Ŵ are bf16 values, so every product is exact in float32 and only the
+    accumulation rounds, as in the kernel's own candidates."""
+    import torch
+
+    wt = what.T
+    for ch in chunk_iter:
+        y = ch.x.to(what.device).float() @ wt
+        if bias is not None:
+            y = y + bias.float().to(what.device)
+        yield Chunk(x=ch.x, recorded=y, cast=ch.cast)
+
+
+def _gptq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[MapCandidate], backend: str, chunk_rows: int, budgets,
+               calib: Optional[OpIO], damp: float) -> None:
+    """Appends the GPTQ rows to res: one Gram matrix and one host factorisation per op, one sweep and one LOE pass (Ŵ as the weight)
+    per candidate; or records in res.budget_skipped why a candidate was not made."""
+    from . import budget_maps as bm
+    from . import gptq as gq
+
+    n, k = res.shape
+    cands = [(f"gptq:{f}", gq.constant_codes(n, k, f), FORMAT_BYTES_PER_ELEM[f] * float(n * k)) for f in gq.GPTQ_FORMATS if f in formats]
+    if map_cand is not None:
+        cands.append((f"gptq:{map_cand.name}", map_cand.assignment, map_cand.tile_bytes))
+    for b in budgets:
+        name = bm.map_name(b, "output")
+        row = next((r for r in res.rows if r.candidate == name), None)
+        if row is not None:
+            cands.append((f"gptq:{name}", row.extra["assignment"], row.bytes))
+        else:
+            res.budget_skipped.append((f"gptq:{name}", f"no {name} map was made"))
+    if not cands:
+        return
+    why = "no calibration samples for this op" if calib is None else check_op(calib, (n, k))
+    if why is None:
+        res.calib_splits = calib.splits
+        cal = chunks(calib, k, n, chunk_rows)
+        if backend == "hip":
+            h, m_cal = gq.gram_full_hip(cal, k, device=w.device)
+            h = h.cpu().numpy()
+        else:
+            h, m_cal = gq.gram_full_emulation(cal, k)
+        why = "the calibration samples hold no tokens" if not m_cal else None
+    if why is None:
+        u = gq.factor(h, damp)
+        if isinstance(u, str):
+            why = u
+    if why is not None:
+        res.budget_skipped.extend((name, why) for name, _codes, _bytes in cands)
+        return
+    if backend == "hip":
+        import torch
+
+        ud = torch.from_numpy(u).to(w.device)
+    for name, codes, nbytes in cands:
+        it = (Chunk(x=ch.x, cast=ch.cast) for ch in chunks(op, k, n, chunk_rows))   # Ŵ's slot alone: no recorded output
+        if backend == "hip":
+            what, loss = gq.sweep_hip(w, ud, codes)
+            if not bool((what.to(torch.bfloat16).float() == what).all()):
+                raise RuntimeError(f"{name}: a GPTQ weight is not a bf16 value, so its products with X are not exact in float32")
+            sums, m, _rec, _cast = hip_sums(_gptq_outputs(it, what, bias), w, [], bias)
+            s = sums[SLOTS.index("recorded")]
+            loss = float(loss.sum())
+        else:
+            what, loss, _margin = gq.sweep_emulation(w, u, codes)
+            sums, m, _rec, _cast = emulation_sums(it, w, [], bias, what)
+            s = sums[SLOTS.index("map")]
+            loss = float(loss.sum())
+        row = Row(name, nbytes, *_columns(s, float(m) * float(n)), tuple(s))
+        row.extra = {"damp": float(damp), "calib_tokens": int(m_cal), "calib_loss": loss}
         res.rows.append(row)

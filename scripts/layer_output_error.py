@@ -5,7 +5,8 @@ and for the map of the compression config's mixed-tile algorithm, as pcc / mae /
 (R against the recorded output).  --x-format bfp8 / bfp4 / bfp2 feeds every candidate BFP-quantised activations Q(X) (R keeps X).  Weights come from quantization_analysis_amd.model_source (synthetic presets or a local safetensors
 directory); io_root is a directory in the reference's layout or `synthetic:<tokens>[:seed]`.  --budget-bits B ... adds, per B, the
 maps budget:<B>:output and budget:<B>:weight chosen on the calibration activations (--calib-io / --calib-split, quantization_analysis_amd
-/budget_maps.py) and evaluated like every other candidate.
+/budget_maps.py) and evaluated like every other candidate.  --gptq adds GPTQ error-compensated weights built on the same calibration
+activations (quantization_analysis_amd/gptq.py): gptq:<bfp*>, gptq:<map> and gptq:budget:<B>:output, each at its RTN counterpart's bytes.
 
   python scripts/layer_output_error.py /path/to/DeepSeek-R1 /path/to/io model.layers.0.mlp --backend hip -c bf16 bfp8 bfp4 bfp2 \\
       --compression-config compression_configs/compression_config.mixed_tile_greedy.example.json --split test --out-dir results/loe
@@ -14,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import csv
+import math
 import json
 import sys
 from pathlib import Path
@@ -51,7 +53,15 @@ def parse_args(argv=None):
     p.add_argument("--calib-split", choices=["calibration", "test", "all"], default="calibration")
     p.add_argument("--calib-max-samples", type=int, default=None, help="First N calibration samples (by sample index).")
     p.add_argument("--save-maps", action="store_true", help="Write <out-dir>/maps/<op>/budget_<B>_{output,weight}.npy.")
+    p.add_argument("--gptq", action="store_true",
+                   help="Add GPTQ error-compensated weights built on the calibration activations: gptq:<bfp*>, gptq:<map>, gptq:budget:<B>:output.")
+    p.add_argument("--gptq-damp", type=float, default=0.01, metavar="D", help="GPTQ damping: λ = D · mean(diag H) (finite, > 0).")
     args = p.parse_args(argv)
+    if args.gptq:
+        if args.x_format != "bf16":
+            p.error("--gptq needs --x-format bf16: the GPTQ weights are built and evaluated on bf16 activations")
+    if not (math.isfinite(args.gptq_damp) and args.gptq_damp > 0.0):
+        p.error(f"--gptq-damp: {args.gptq_damp:g} is not finite and > 0")
     if args.budget_bits:
         if args.x_format != "bf16":
             p.error("--budget-bits needs --x-format bf16: the budget maps are chosen and evaluated on bf16 activations")
@@ -80,15 +90,17 @@ def main(argv=None) -> int:
     budgets = tuple(args.budget_bits or ())
     calib_io = args.calib_io or args.io_root
     calib = {}
-    if budgets:
+    if budgets or args.gptq:
         cal_ops, _cal_skipped = select_ops(index, calib_io, query, args.calib_split, args.calib_max_samples)
         calib = {o.op: o for o in cal_ops}
     out_dir = Path(args.out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     records, csv_rows = [], []
     for op in ops:
-        res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows, args.x_format,
-                          **({"budgets": budgets, "calib": calib.get(op.op)} if budgets else {}))
+        extra = {"budgets": budgets, "calib": calib.get(op.op)} if budgets or args.gptq else {}
+        if args.gptq:
+            extra.update(gptq=True, gptq_damp=args.gptq_damp)
+        res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows, args.x_format, **extra)
         if res.skipped:
             skipped.append((op.op, res.skipped))
             continue
@@ -103,7 +115,7 @@ def main(argv=None) -> int:
         rec = {"op": res.op, "weight": res.weight, "shape": [n, k], "M": res.m, "splits": res.splits, "x_cast": res.x_cast,
                "rows": [{"candidate": r.candidate, "bytes": r.bytes, "pcc": r.pcc, "mae": r.mae, "atol": r.atol,
                          **{key: v for key, v in r.extra.items() if key != "assignment"}} for r in res.rows]}
-        if budgets:
+        if budgets or args.gptq:
             rec["calib_splits"] = res.calib_splits
             rec["budget_skipped"] = [{"candidate": c, "reason": why} for c, why in res.budget_skipped]
             for c, why in res.budget_skipped:
@@ -127,8 +139,11 @@ def main(argv=None) -> int:
            "compression_config": args.compression_config, "split": args.split, "max_samples": args.max_samples, "x_format": args.x_format,
            "ops": records, "skipped": [{"op": o, "reason": r} for o, r in skipped]}
     if budgets:
-        doc.update({"budget_bits": list(budgets), "calib_io": calib_io, "calib_split": args.calib_split,
-                    "calib_max_samples": args.calib_max_samples})
+        doc.update({"budget_bits": list(budgets)})
+    if budgets or args.gptq:
+        doc.update({"calib_io": calib_io, "calib_split": args.calib_split, "calib_max_samples": args.calib_max_samples})
+    if args.gptq:
+        doc.update({"gptq_damp": args.gptq_damp})
     (out_dir / "layer_output_error.json").write_text(json.dumps(doc, indent=2))
     print(f"\nwrote {out_dir / 'layer_output_error.csv'} and {out_dir / 'layer_output_error.json'}")
     return 0
