@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTQ_VERSION 143 /* 0.1.4.7 (optional symbols as well): + mtq_gram_full / _scratch_doubles, mtq_gptq_sweep / _scratch_doubles; 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
+#define MTQ_VERSION 143 /* 0.1.4.8 (optional symbols as well): + mtq_output_error_transposed, mtq_tile_error_tables_transposed; 0.1.4.7 (optional symbols as well): + mtq_gram_full / _scratch_doubles, mtq_gptq_sweep / _scratch_doubles; 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
 
 typedef enum {
     MTQ_OK = 0,
@@ -243,6 +243,18 @@ int mtq_output_error_qx(const void *x, int64_t m, int64_t k, int64_t ldx, const 
 int mtq_quantize_rows_bf16(const void *x, int64_t rows, int64_t cols, int64_t ld, int fmt, void *y, int64_t ldy, void *stream);
 
 /*
+ * LOE in the transposed BFP layout — mtq_output_error (xq == NULL) or mtq_output_error_qx (xq != NULL) with Ŵ_f = K2_f(wᵀ)ᵀ for the
+ * bfp8 / bfp4 / bfp2 bits: a group is 16 consecutive rows (n) of one column (k), aligned from row 0, a ragged last group completed with
+ * +0.  `map`, when not NULL, is over wᵀ's grid: ceil(k/32) × ceil(n/32) int8 codes, row-major (the code of w[n][k] is
+ * map[(k/32) · ceil(n/32) + n/32]).  R, the bf16 candidate, fp0 and `recorded` are layout-free: their sums are bit-identical to
+ * mtq_output_error's (mtq_output_error_qx's with xq) for the same inputs.  Same sums, slots, scratch (mtq_output_error_scratch_doubles),
+ * checks and determinism.  csrc/mtq_output_error.hip.
+ */
+int mtq_output_error_transposed(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
+                                const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
+                                double *sums, double *scratch, size_t scratch_doubles, void *stream, const void *xq, int64_t ldxq);
+
+/*
  * Budget maps, device half (no reference counterpart; quantization_analysis_amd/budget_maps.py holds the host half and the contract).
  * W is one op's weight, n × k (bf16 or float32, nn.Linear convention); X_cal its calibration activations, m × k bf16; the tiles are the
  * 32 × 32 row-layout tiles of W, zero padded, and c is a tile's column block.
@@ -267,6 +279,15 @@ int mtq_gram_blocks(const void *x, int64_t m, int64_t k, int64_t ldx, double *h,
                     void *stream);
 int mtq_tile_error_tables(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw, const double *h, size_t h_doubles, double *e_out,
                           double *e_w, size_t table_doubles, void *stream);
+
+/*
+ * Tile error tables in the transposed layout — mtq_tile_error_tables with Δ_f = K2_f(wᵀ)ᵀ − w (groups of 16 consecutive rows of one
+ * column) and the tiles over wᵀ's grid: t = kb · ceil(n/32) + nb pairs column block kb of w with row block nb, and
+ * e_out[t][f] = Σ_i δ_iᵀ H_kb δ_i over the rows i of the tile (δ_i = row i of Δ_f restricted to column block kb).  Same arguments, h,
+ * table sizes and checks as mtq_tile_error_tables.  csrc/mtq_budget.hip.
+ */
+int mtq_tile_error_tables_transposed(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw, const double *h, size_t h_doubles,
+                                     double *e_out, double *e_w, size_t table_doubles, void *stream);
 
 /*
  * GPTQ's error-compensated BFP weights, device half (no reference counterpart; quantization_analysis_amd/gptq.py holds the host half

@@ -28,8 +28,14 @@ Two maps per budget, from the same rule: `budget:<bits>:output` allocated on e_o
 (the weight-only baseline at the same budget).  The LOE evaluates both exactly, cross terms included, on the evaluation chunks; the
 block-diagonal model only chooses the map.
 
+Transposed layout (layout="transpose"; output_error's budget:<bits>:<basis>+transpose): Δ_f = quantize_weight_values(Wᵀ, f)ᵀ − W, whose
+groups are 16 consecutive rows of one column, and the tiles are those of Wᵀ's grid, tiles_hw(k, n): tile (r, c) holds columns 32r .. of
+W (Wᵀ's rows) and rows 32c .. (Wᵀ's columns).  The same block-diagonal model applies with δ_i row i of W restricted to the tile's column
+block r: e_out[t, f] = Σ_i δ_iᵀ H_r δ_i with the same Gram blocks.  allocate is unchanged (grid = tiles_hw(k, n)), and
+reconstruct_emulation(w, a, "transpose") is the map's Ŵ, as reconstruct_mixed_tile_assignment.py --layout transpose builds it.
+
 Backends: emulation — float64 torch / NumPy on the host; hip — csrc/mtq_budget.hip (mtq_gram_blocks per chunk, then
-mtq_tile_error_tables and one device-to-host copy).
+mtq_tile_error_tables or mtq_tile_error_tables_transposed and one device-to-host copy).
 """
 from __future__ import annotations
 
@@ -113,8 +119,9 @@ def _w32(w) -> np.ndarray:
     return np.asarray(w.float().cpu().numpy() if hasattr(w, "cpu") else w, dtype=np.float32)
 
 
-def tile_error_tables_emulation(w, h) -> tuple[np.ndarray, np.ndarray]:
-    """Float64 host route → (e_out, e_w), each [T, 4].  w: (n, k) weight (torch or NumPy); h: [ceil(k/32), 32, 32] Gram blocks."""
+def tile_error_tables_emulation(w, h, layout: str = "rows") -> tuple[np.ndarray, np.ndarray]:
+    """Float64 host route → (e_out, e_w), each [T, 4].  w: (n, k) weight (torch or NumPy); h: [ceil(k/32), 32, 32] Gram blocks.
+    layout "transpose": Δ from column groups, tiles over Wᵀ's grid (module docstring)."""
     w32 = _w32(w)
     n, k = w32.shape
     th, tw = tiles_hw(n, k)
@@ -124,6 +131,18 @@ def tile_error_tables_emulation(w, h) -> tuple[np.ndarray, np.ndarray]:
     w64 = w32.astype(np.float64)
     e_out = np.zeros((th * tw, len(MIXED_TILE_FORMATS)), dtype=np.float64)
     e_w = np.zeros_like(e_out)
+    if layout == "transpose":
+        wt = np.ascontiguousarray(w32.T)
+        for code, f in enumerate(MIXED_TILE_FORMATS):
+            d = np.zeros((tw * TILE, th * TILE), dtype=np.float64)             # Δᵀ over Wᵀ's grid
+            d[:k, :n] = quantize_weight_values(wt, f).astype(np.float64) - w64.T
+            dt = d.reshape(tw, TILE, th, TILE)                                 # [r, a, c, i]: column a of W's block r, row i
+            g = np.einsum("raci,rab->rbci", dt, h)                             # (H_r δ_i)[b]
+            e_out[:, code] = np.einsum("rbci,rbci->rc", g, dt).reshape(-1)
+            e_w[:, code] = np.einsum("raci,raci->rc", dt, dt).reshape(-1)
+        return e_out, e_w
+    if layout != "rows":
+        raise ValueError(f"layout must be rows or transpose, got {layout!r}")
     for code, f in enumerate(MIXED_TILE_FORMATS):
         d = np.zeros((th * TILE, tw * TILE), dtype=np.float64)
         d[:n, :k] = quantize_weight_values(w32, f).astype(np.float64) - w64
@@ -134,15 +153,19 @@ def tile_error_tables_emulation(w, h) -> tuple[np.ndarray, np.ndarray]:
     return e_out, e_w
 
 
-def tile_error_tables_hip(w, h) -> tuple[np.ndarray, np.ndarray]:
-    """mtq_tile_error_tables on the device weight and Gram blocks, then one device-to-host copy → (e_out, e_w), each [T, 4]."""
+def tile_error_tables_hip(w, h, layout: str = "rows") -> tuple[np.ndarray, np.ndarray]:
+    """mtq_tile_error_tables (layout "transpose": mtq_tile_error_tables_transposed) on the device weight and Gram blocks, then one
+    device-to-host copy → (e_out, e_w), each [T, 4]."""
     import torch
 
     from . import hip_backend as hb
 
     wd = w if w.dtype in (torch.bfloat16, torch.float32) else w.float()
     wd = wd if wd.stride(-1) == 1 else wd.contiguous()
-    e_out, e_w = hb.tile_error_tables(wd, h, want_weight=True)
+    if layout not in ("rows", "transpose"):
+        raise ValueError(f"layout must be rows or transpose, got {layout!r}")
+    fn = hb.tile_error_tables_transposed if layout == "transpose" else hb.tile_error_tables
+    e_out, e_w = fn(wd, h, want_weight=True)
     both = torch.stack((e_out, e_w)).cpu().numpy()
     return both[0], both[1]
 
@@ -239,9 +262,14 @@ def predicted_sse(table: np.ndarray, assignment: np.ndarray) -> float:
     return float(np.asarray(table, dtype=np.float64)[np.arange(a.size), a].sum())
 
 
-def reconstruct_emulation(w, assignment: np.ndarray) -> np.ndarray:
-    """Ŵ of a map on the host (float32): each tile quantised in the format its entry names, as K3 builds it."""
+def reconstruct_emulation(w, assignment: np.ndarray, layout: str = "rows") -> np.ndarray:
+    """Ŵ of a map on the host (float32): each tile quantised in the format its entry names, as K3 builds it.  layout "transpose": the
+    map is over Wᵀ's grid and Ŵ = (the map's Ŵ of Wᵀ)ᵀ."""
     w32 = _w32(w)
+    if layout == "transpose":
+        return np.ascontiguousarray(reconstruct_emulation(np.ascontiguousarray(w32.T), assignment).T)
+    if layout != "rows":
+        raise ValueError(f"layout must be rows or transpose, got {layout!r}")
     n, k = w32.shape
     a = np.asarray(assignment, dtype=np.int8)
     codes = np.repeat(np.repeat(a, TILE, axis=0), TILE, axis=1)[:n, :k]

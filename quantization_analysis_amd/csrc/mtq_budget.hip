@@ -10,6 +10,7 @@
 // mtq_tile_error_tables: for every 32 × 32 tile t = (r, c) of W and format f, Δ = K2_f(W) − W in float64 (the literal helpers of
 //   mtq_device.hpp, so Δ is the one K2 / K3 build) and e_out[t, f] = Σ_i δ_iᵀ H_c δ_i, e_w[t, f] = Σ δ², both in a fixed order.
 //   One wave per workgroup walks a column of tiles with H_c's rows in registers.
+// mtq_tile_error_tables_transposed: the same tables in the transposed layout (Δ from column groups, tiles over Wᵀ's grid).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -184,6 +185,66 @@ __global__ __launch_bounds__(64) void tile_error_tables_kernel(const T *__restri
     }
 }
 
+// The transposed layout: Δ = K2_f(Wᵀ)ᵀ − W, groups of 16 consecutive rows of one column, and tiles over Wᵀ's grid (t = kb · tn + nb,
+// tn = ceil(N/32)).  Tile (kb, nb) pairs rows nb of W with column block kb, so H_kb is the one it needs.  One wave per workgroup: tile
+// row kb = blockIdx.x of Wᵀ (H_kb's rows in registers), tile columns blockIdx.y, + gridDim.y, ...  Lane l loads the column group
+// (column 32kb + (l>>1), rows 32nb + 16(l&1) ..) and writes its δ transposed into dl, so that dl[i] is again row i of W over the
+// block's 32 columns; the rest is tile_error_tables_kernel's.
+template <typename T>
+__global__ __launch_bounds__(64) void tile_error_tables_t_kernel(const T *__restrict__ w, int64_t N, int64_t K, int64_t ldw,
+                                                                 const double *__restrict__ h, int64_t tk, int64_t tn,
+                                                                 double *__restrict__ e_out, double *__restrict__ e_w)
+{
+    __shared__ __attribute__((aligned(16))) double dl[kTile][kTile];
+    const int lane = threadIdx.x, a = lane & 31, half = lane >> 5;
+    const int64_t kb = blockIdx.x;
+    double hrow[kTile];
+#pragma unroll
+    for (int b = 0; b < kTile; ++b) hrow[b] = h[kb * kBlock + a * kTile + b];
+    const int lcol = lane >> 1, lrow = 16 * (lane & 1);
+    const int64_t col = kb * kTile + lcol;
+    for (int64_t nb = blockIdx.y; nb < tn; nb += gridDim.y) {
+        const int64_t row0 = nb * kTile + lrow;
+        uint32_t u[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            const int64_t row = row0 + i;
+            u[i] = (row < N && col < K) ? (sizeof(T) == 4 ? __float_as_uint((float)w[row * ldw + col])
+                                                          : (uint32_t)w[row * ldw + col] << 16)
+                                        : 0u;
+        }
+        const uint32_t E = group_shared_exp(u);
+        const int64_t t = kb * tn + nb;
+#pragma unroll 1
+        for (int f = 0; f < kNumFmt; ++f) {
+            double sq = 0.0;
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) {
+                const double d = (double)__uint_as_float(quant_elem_bits(f, u[i], E)) - (double)__uint_as_float(u[i]);
+                dl[lrow + i][lcol] = d;
+                sq += d * d;
+            }
+            __syncthreads();
+            double part = 0.0;
+#pragma unroll 4
+            for (int j = 0; j < kTile / 2; ++j) {
+                const int i = 2 * j + half;
+                double gsum = 0.0;
+#pragma unroll
+                for (int b = 0; b < kTile; ++b) gsum = fma(hrow[b], dl[i][b], gsum);
+                part = fma(dl[i][a], gsum, part);
+            }
+            __syncthreads();
+            part = wave_sum(part);
+            if (e_w) sq = wave_sum(sq);
+            if (lane == 0) {
+                e_out[t * kNumFmt + f] = part;
+                if (e_w) e_w[t * kNumFmt + f] = sq;
+            }
+        }
+    }
+}
+
 } // namespace
 } // namespace mtq
 
@@ -244,4 +305,27 @@ extern "C" int mtq_tile_error_tables(const void *w, int w_dtype, int64_t n, int6
         hipLaunchKernelGGL(tile_error_tables_kernel<uint16_t>, grid, dim3(64), 0, st, static_cast<const uint16_t *>(w), n, k, ldw, w_vec, h, th, tw,
                            e_out, e_w);
     return check_launch("mtq_tile_error_tables");
+}
+
+extern "C" int mtq_tile_error_tables_transposed(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw, const double *h,
+                                                size_t h_doubles, double *e_out, double *e_w, size_t table_doubles, void *stream)
+{
+    if (!w || !h || !e_out) return fail(MTQ_ERR_INVALID, "null argument");
+    if (w_dtype != MTQ_DTYPE_BF16 && w_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "w_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    if (n <= 0 || k <= 0) return fail(MTQ_ERR_INVALID, "n and k must be positive");
+    if (ldw < k) return fail(MTQ_ERR_INVALID, "ldw < k");
+    if (n > (int64_t)1 << 30 || k > (int64_t)1 << 30) return fail(MTQ_ERR_INVALID, "matrix too large");
+    const int64_t tk = (k + kTile - 1) / kTile, tn = (n + kTile - 1) / kTile;   // Wᵀ's grid: tk × tn
+    if (h_doubles != (size_t)tk * kBlock) return fail(MTQ_ERR_INVALID, "h_doubles != ceil(k / 32) * 1024");
+    if (table_doubles != (size_t)(tk * tn) * kNumFmt) return fail(MTQ_ERR_INVALID, "table_doubles != tiles * 4");
+    if (tk > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many tile rows for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)tk, (unsigned)std::min<int64_t>(tn, std::max<int64_t>(1, 16384 / tk)));
+    if (w_dtype == MTQ_DTYPE_F32)
+        hipLaunchKernelGGL(tile_error_tables_t_kernel<float>, grid, dim3(64), 0, st, static_cast<const float *>(w), n, k, ldw, h, tk, tn, e_out, e_w);
+    else
+        hipLaunchKernelGGL(tile_error_tables_t_kernel<uint16_t>, grid, dim3(64), 0, st, static_cast<const uint16_t *>(w), n, k, ldw, h, tk, tn,
+                           e_out, e_w);
+    return check_launch("mtq_tile_error_tables_transposed");
 }

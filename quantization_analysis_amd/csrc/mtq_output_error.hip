@@ -136,6 +136,106 @@ __device__ __forceinline__ void stage_w_group(const uint32_t (&u)[kGroup], int64
     }
 }
 
+// ---- transposed layout (mtq_output_error_transposed): a group is 16 consecutive rows (N) of one column (k), aligned from row 0.
+// The staging keeps the row kernel's ownership — lane tid holds row n0 + tid/4, columns 16·(tid%4) .. +15 — so wave w holds rows
+// n0 + 16w .. +15 and element i's group is column k + i over the 16 lanes of the wave with equal lane & 3 (n0 is a multiple of 64).
+// Its shared exponent is a max over lane bits 2..5; the constants become per element.  hi / mid / lo and the LDS images are untouched.
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+
+// E[i] = the max exponent field of element i over the 16 lanes of the wave with this lane's lane & 3 (EXEC must be full).  Two 8-bit
+// fields per dword: the two in-row steps are DPP rotations (row_ror:4, row_ror:8 keep lane & 3), the two cross-row steps lane shuffles.
+__device__ __forceinline__ void column_shared_exps(const uint32_t (&u)[kGroup], uint32_t (&E)[kGroup])
+{
+#pragma unroll
+    for (int j = 0; j < kGroup / 2; ++j) {
+        uint32_t v = ((u[2 * j] >> 23) & 0xFFu) | (((u[2 * j + 1] >> 23) & 0xFFu) << 16);
+        v = pk_max_u16(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false));
+        v = pk_max_u16(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false));
+        v = pk_max_u16(v, (uint32_t)__shfl_xor((int)v, 16, 64));
+        v = pk_max_u16(v, (uint32_t)__shfl_xor((int)v, 32, 64));
+        E[2 * j] = v & 0xFFFFu;
+        E[2 * j + 1] = v >> 16;
+    }
+}
+
+// One element by bfp_fast with the constants of its own shared exponent E in [80, 180] (group_consts, per element).
+__device__ __forceinline__ uint32_t bfp_fast_elem(uint32_t u, uint32_t E, uint32_t M)
+{
+    const float xs = __builtin_truncf(bits_f(u) * bits_f((277u - E) << 23)) * bits_f((E - 23u) << 23);
+    const float c = bits_f(((E + 24u - M) << 23) | 0x400000u);
+    const float ymax = (float)((1u << M) - 1u) * bits_f((E - (M - 1u)) << 23);
+    return bfp_fast(xs, c, ymax);
+}
+
+// The lane's 16 elements (each of its own column group) → the images the launch needs; map: ceil(N/32) entries per tile row of Wᵀ.
+__device__ __forceinline__ void stage_w_group_t(const uint32_t (&u)[kGroup], int64_t n, int64_t k, int64_t N, int64_t K,
+                                                uint32_t imask, const int8_t *__restrict__ map, int64_t map_w, uint16_t *img0, int img_off)
+{
+    uint32_t E[kGroup];
+    column_shared_exps(u, E);
+    bool fast = true;
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) fast = fast && (E[i] - 80u) <= 100u;
+    uint32_t y[kGroup];
+    constexpr int kImgElems = kBN * kLdk;
+    {   // hi (and mid / lo for float32 storage): layout-free, as stage_w_group
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) y[i] = bf16_round_bits(u[i]);
+        store_image(img0 + kImgHi * kImgElems + img_off, y);
+        if (imask & (1u << kImgMid)) {
+            uint32_t r1[kGroup];
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) {
+                const float d1 = bits_f(u[i]) - bits_f(y[i]);
+                r1[i] = bf16_round_bits(__float_as_uint(d1));
+                y[i] = __float_as_uint(d1 - bits_f(r1[i]));
+            }
+            store_image(img0 + kImgMid * kImgElems + img_off, r1);
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) y[i] = bf16_round_bits(y[i]);
+            store_image(img0 + kImgLo * kImgElems + img_off, y);
+        }
+    }
+#pragma unroll
+    for (int f = 1; f <= 3; ++f) {
+        const int im = kImgB8 + f - 1;
+        if (imask & (1u << im)) {                                        // launch-uniform
+            const uint32_t M = f == 1 ? 7u : (f == 2 ? 3u : 1u);
+            if (fast) {
+#pragma unroll
+                for (int i = 0; i < kGroup; ++i) y[i] = bfp_fast_elem(u[i], E[i], M);
+            } else {
+#pragma unroll
+                for (int i = 0; i < kGroup; ++i) y[i] = bfp_elem_bits_rt(u[i], E[i], M);
+            }
+            store_image(img0 + im * kImgElems + img_off, y);
+        }
+    }
+    if (imask & (1u << kImgMap)) {
+        const int f = (n < N && k < K) ? (int)map[(k / kTile) * map_w + n / kTile] : 4;   // the zero padding of a ragged edge stays zero
+        const uint32_t M = f == 1 ? 7u : (f == 2 ? 3u : 1u);
+        if (f == 0) {
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) y[i] = bf16_round_bits(u[i]);
+        } else if (f < 1 || f > 3) {
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) y[i] = 0u;
+        } else if (fast) {
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) y[i] = bfp_fast_elem(u[i], E[i], M);
+        } else {
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) y[i] = bfp_elem_bits_rt(u[i], E[i], M);
+        }
+        store_image(img0 + kImgMap * kImgElems + img_off, y);
+    }
+}
+
 // max|r − q| with np.max semantics: a NaN on either side wins (fmax would drop it and report the largest finite difference).
 __device__ __forceinline__ double nan_max(double a, double b) { return (a == a && b == b) ? fmax(a, b) : a + b; }
 
@@ -150,7 +250,8 @@ __device__ __forceinline__ void fold(double (&s)[kRecord], int slot, double r, d
 }
 
 // QX: the candidates take their A operand from xq (Q(X), bf16, ldxq) and the bf16 candidate accumulates in acc[6]; !QX ignores xq.
-template <typename T, bool QX>
+// TR: the transposed layout (stage_w_group_t; map over Wᵀ's grid); everything else is the row kernel's.
+template <typename T, bool QX, bool TR>
 __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec,
                                                                 const T *__restrict__ w, int64_t N, int64_t ldw, int w_vec,
                                                                 const float *__restrict__ bias, uint32_t imask, uint32_t smask,
@@ -234,7 +335,10 @@ __global__ __launch_bounds__(kThreads) void output_error_kernel(const uint16_t *
             *reinterpret_cast<uint4 *>(xs + (p >> 3) * kLdk + (p & 7) * 8) = xr[i];
             if constexpr (QX) *reinterpret_cast<uint4 *>(xqs + (p >> 3) * kLdk + (p & 7) * 8) = xqr[i];
         }
-        stage_w_group(wu, n0 + wrow, k0 + wc16, N, K, imask, map, map_w, img0, wrow * kLdk + wc16);
+        if constexpr (TR)
+            stage_w_group_t(wu, n0 + wrow, k0 + wc16, N, K, imask, map, map_w, img0, wrow * kLdk + wc16);
+        else
+            stage_w_group(wu, n0 + wrow, k0 + wc16, N, K, imask, map, map_w, img0, wrow * kLdk + wc16);
         __syncthreads();
         if (k0 + kBK < K) load_step(k0 + kBK);
 #pragma unroll
@@ -384,10 +488,31 @@ extern "C" size_t mtq_output_error_scratch_doubles(int64_t m, int64_t n)
     return (size_t)(((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN)) * kRecord;
 }
 
-// The checks and the launch of both LOE entries; qx = mtq_output_error_qx (xq, ldxq), otherwise mtq_output_error exactly.
+// One fused launch and its reduce; QX takes the candidates' A operand from xq, TR the transposed layout.
+template <bool QX, bool TR>
+static int launch_fused(bool f32w, int64_t blocks, hipStream_t st, const uint16_t *xp, int64_t m, int64_t k, int64_t ldx, int x_vec,
+                        const void *w, int64_t n, int64_t ldw, int w_vec, const float *bias, uint32_t imask, uint32_t smask,
+                        const int8_t *map, int64_t map_w, const void *recorded, int rec_f32, int64_t ldr, double *sums, double *scratch,
+                        const uint16_t *xqp, int64_t ldxq, int xq_vec, const char *what, const char *what_reduce)
+{
+    const dim3 grid((unsigned)blocks);
+    if (f32w)
+        hipLaunchKernelGGL((output_error_kernel<float, QX, TR>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, static_cast<const float *>(w), n,
+                           ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, xqp, ldxq, xq_vec);
+    else
+        hipLaunchKernelGGL((output_error_kernel<uint16_t, QX, TR>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, static_cast<const uint16_t *>(w),
+                           n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, xqp, ldxq, xq_vec);
+    if (int rc = check_launch(what)) return rc;
+    hipLaunchKernelGGL(output_error_reduce, dim3(kRecord), dim3(256), 0, st, scratch, blocks, sums, smask);
+    return check_launch(what_reduce);
+}
+
+// The checks and the launch of the LOE entries; qx = the candidates see xq (mtq_output_error_qx, or mtq_output_error_transposed with a
+// non-null xq), tr = the transposed layout (the map over Wᵀ's grid, ceil(n/32) entries per row), otherwise mtq_output_error exactly.
 static int launch_output_error(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
                                const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype, int64_t ldr,
-                               double *sums, double *scratch, size_t scratch_doubles, void *stream, bool qx, const void *xq, int64_t ldxq)
+                               double *sums, double *scratch, size_t scratch_doubles, void *stream, bool qx, const void *xq, int64_t ldxq,
+                               bool tr = false)
 {
     if (!x || !w || !sums || !scratch) return fail(MTQ_ERR_INVALID, "null argument");
     if (qx && !xq) return fail(MTQ_ERR_INVALID, "xq is null");
@@ -415,32 +540,25 @@ static int launch_output_error(const void *x, int64_t m, int64_t k, int64_t ldx,
     const int64_t esz = f32w ? 4 : 2;
     const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
     const int w_vec = reinterpret_cast<uintptr_t>(w) % 16 == 0 && (ldw * esz) % 16 == 0;
-    const int64_t map_w = (k + kTile - 1) / kTile;
+    const int64_t map_w = tr ? (n + kTile - 1) / kTile : (k + kTile - 1) / kTile;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)blocks);
     const uint16_t *xp = static_cast<const uint16_t *>(x), *xqp = static_cast<const uint16_t *>(xq);
     const int rec_f32 = rec_dtype == MTQ_DTYPE_F32;
-    if (qx) {
-        const int xq_vec = reinterpret_cast<uintptr_t>(xq) % 16 == 0 && ldxq % 8 == 0;
-        if (f32w)
-            hipLaunchKernelGGL((output_error_kernel<float, true>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, static_cast<const float *>(w), n,
-                                 ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, xqp, ldxq, xq_vec);
-        else
-            hipLaunchKernelGGL((output_error_kernel<uint16_t, true>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, static_cast<const uint16_t *>(w),
-                                 n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, xqp, ldxq, xq_vec);
-        if (int rc = check_launch("mtq_output_error_qx")) return rc;
-        hipLaunchKernelGGL(output_error_reduce, dim3(kRecord), dim3(256), 0, st, scratch, blocks, sums, smask);
-        return check_launch("mtq_output_error_qx (reduce)");
+    const int xq_vec = qx && reinterpret_cast<uintptr_t>(xq) % 16 == 0 && ldxq % 8 == 0;
+    if (tr) {
+        if (qx)
+            return launch_fused<true, true>(f32w, blocks, st, xp, m, k, ldx, x_vec, w, n, ldw, w_vec, bias, imask, smask, map, map_w, recorded,
+                                            rec_f32, ldr, sums, scratch, xqp, ldxq, xq_vec, "mtq_output_error_transposed",
+                                            "mtq_output_error_transposed (reduce)");
+        return launch_fused<false, true>(f32w, blocks, st, xp, m, k, ldx, x_vec, w, n, ldw, w_vec, bias, imask, smask, map, map_w, recorded,
+                                         rec_f32, ldr, sums, scratch, nullptr, 0, 0, "mtq_output_error_transposed",
+                                         "mtq_output_error_transposed (reduce)");
     }
-    if (f32w)
-        hipLaunchKernelGGL((output_error_kernel<float, false>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec,
-                           static_cast<const float *>(w), n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, nullptr, 0, 0);
-    else
-        hipLaunchKernelGGL((output_error_kernel<uint16_t, false>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec,
-                           static_cast<const uint16_t *>(w), n, ldw, w_vec, bias, imask, smask, map, map_w, recorded, rec_f32, ldr, scratch, nullptr, 0, 0);
-    if (int rc = check_launch("mtq_output_error")) return rc;
-    hipLaunchKernelGGL(output_error_reduce, dim3(kRecord), dim3(256), 0, st, scratch, blocks, sums, smask);
-    return check_launch("mtq_output_error (reduce)");
+    if (qx)
+        return launch_fused<true, false>(f32w, blocks, st, xp, m, k, ldx, x_vec, w, n, ldw, w_vec, bias, imask, smask, map, map_w, recorded,
+                                         rec_f32, ldr, sums, scratch, xqp, ldxq, xq_vec, "mtq_output_error_qx", "mtq_output_error_qx (reduce)");
+    return launch_fused<false, false>(f32w, blocks, st, xp, m, k, ldx, x_vec, w, n, ldw, w_vec, bias, imask, smask, map, map_w, recorded,
+                                      rec_f32, ldr, sums, scratch, nullptr, 0, 0, "mtq_output_error", "mtq_output_error (reduce)");
 }
 
 extern "C" int mtq_output_error(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
@@ -457,6 +575,15 @@ extern "C" int mtq_output_error_qx(const void *x, int64_t m, int64_t k, int64_t 
 {
     return launch_output_error(x, m, k, ldx, w, w_dtype, n, ldw, bias, fmt_mask, map, recorded, rec_dtype, ldr, sums, scratch, scratch_doubles,
                                stream, true, xq, ldxq);
+}
+
+extern "C" int mtq_output_error_transposed(const void *x, int64_t m, int64_t k, int64_t ldx, const void *w, int w_dtype, int64_t n, int64_t ldw,
+                                           const float *bias, uint32_t fmt_mask, const int8_t *map, const void *recorded, int rec_dtype,
+                                           int64_t ldr, double *sums, double *scratch, size_t scratch_doubles, void *stream, const void *xq,
+                                           int64_t ldxq)
+{
+    return launch_output_error(x, m, k, ldx, w, w_dtype, n, ldw, bias, fmt_mask, map, recorded, rec_dtype, ldr, sums, scratch, scratch_doubles,
+                               stream, xq != nullptr, xq, ldxq, true);
 }
 
 extern "C" int mtq_quantize_rows_bf16(const void *x, int64_t rows, int64_t cols, int64_t ld, int fmt, void *y, int64_t ldy, void *stream)

@@ -105,6 +105,8 @@ SIGNATURES = {
     "mtq_gram_full": ("i", "plllpzpzp", True),
     "mtq_gptq_sweep_scratch_doubles": ("z", "ll", True),
     "mtq_gptq_sweep": ("i", "pilllpzpzplppzp", True),
+    "mtq_output_error_transposed": ("i", "plllpillpuppilppzppl", True),
+    "mtq_tile_error_tables_transposed": ("i", "pilllpzppzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -635,9 +637,23 @@ def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded
     float32 or None.  scratch: float64 device tensor of at least output_error_scratch(m, n) elements (allocated when None).
     xq: None, or the candidates' activations Q(X) — an (m, k) bf16 device tensor with contiguous rows (quantize_rows_bf16 of x) — which
     takes mtq_output_error_qx: R keeps x, every candidate but fp0 is fed xq."""
+    return _output_error(x, w, fmt_mask, sums, bias, assignment, recorded, scratch, xq, False)
+
+
+def output_error_transposed(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded=None, scratch=None, xq=None):
+    """LOE in the transposed BFP layout (mtq_output_error_transposed): output_error with Ŵ_f = K2_f(wᵀ)ᵀ for the bfp8 / bfp4 / bfp2 bits
+    (groups of 16 consecutive rows of one column) and `assignment` over wᵀ's grid, an int8 map of tiles_hw(k, n).  R, the bf16 slot,
+    fp0 and `recorded` are those of output_error bit for bit.  xq: as output_error (None = W-only)."""
+    return _output_error(x, w, fmt_mask, sums, bias, assignment, recorded, scratch, xq, True)
+
+
+def _output_error(x, w, fmt_mask: int, sums, bias, assignment, recorded, scratch, xq, transposed: bool):
     torch = _torch()
     require_gpu()
-    fn = _entry("mtq_output_error" if xq is None else "mtq_output_error_qx")
+    if transposed:
+        fn = _entry("mtq_output_error_transposed")
+    else:
+        fn = _entry("mtq_output_error" if xq is None else "mtq_output_error_qx")
     _code, _count, _stride, m, k, ldx = _matrix(x, (2,))
     w_code, _count, _stride, n, kw, ldw = _matrix(w, (2,))
     if x.dtype != torch.bfloat16:
@@ -653,7 +669,7 @@ def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded
         bp = bias.data_ptr()
     mp = 0
     if assignment is not None:
-        th, tw = tiles_hw(n, k)
+        th, tw = tiles_hw(k, n) if transposed else tiles_hw(n, k)
         if assignment.dtype != torch.int8 or assignment.numel() != th * tw or not assignment.is_contiguous() or not assignment.is_cuda:
             raise MtqError(f"assignment must be a contiguous int8 device tensor of {th}x{tw} entries")
         mp = assignment.data_ptr()
@@ -663,7 +679,7 @@ def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded
         if (rm, rn) != (m, n):
             raise MtqError(f"recorded must be a ({m}, {n}) device tensor with contiguous rows")
         rp = recorded.data_ptr()
-    qx = ()
+    qx = (0, 0) if transposed else ()
     if xq is not None:
         _code, _count, _stride, qm, qk, ldxq = _matrix(xq, (2,))
         if xq.dtype != torch.bfloat16 or (qm, qk) != (m, k) or xq.device != x.device:
@@ -722,6 +738,22 @@ def tile_error_tables(w, h, want_weight: bool = True):
         raise MtqError(f"h must be a contiguous float64 tensor of shape ({tw}, 32, 32) on w's device")
     require_gpu()
     fn = _entry("mtq_tile_error_tables")
+    out = torch.empty((2 if want_weight else 1, th * tw, 4), dtype=torch.float64, device=w.device)
+    check(fn(w.data_ptr(), w_code, n, k, ldw, h.data_ptr(), h.numel(), out[0].data_ptr(), out[1].data_ptr() if want_weight else 0,
+             th * tw * 4, _stream_ptr()))
+    return out[0], (out[1] if want_weight else None)
+
+
+def tile_error_tables_transposed(w, h, want_weight: bool = True):
+    """tile_error_tables in the transposed layout (mtq_tile_error_tables_transposed): Δ from groups of 16 consecutive rows of one column,
+    tiles row-major over wᵀ's grid, tiles_hw(k, n).  Same arguments and h as tile_error_tables."""
+    torch = _torch()
+    w_code, _count, _stride, n, k, ldw = _matrix(w, (2,))
+    th, tw = tiles_hw(k, n)
+    if h.dtype != torch.float64 or tuple(h.shape) != (th, TILE, TILE) or not h.is_contiguous() or not h.is_cuda or h.device != w.device:
+        raise MtqError(f"h must be a contiguous float64 tensor of shape ({th}, 32, 32) on w's device")
+    require_gpu()
+    fn = _entry("mtq_tile_error_tables_transposed")
     out = torch.empty((2 if want_weight else 1, th * tw, 4), dtype=torch.float64, device=w.device)
     check(fn(w.data_ptr(), w_code, n, k, ldw, h.data_ptr(), h.numel(), out[0].data_ptr(), out[1].data_ptr() if want_weight else 0,
              th * tw * 4, _stream_ptr()))

@@ -7,6 +7,9 @@ directory); io_root is a directory in the reference's layout or `synthetic:<toke
 maps budget:<B>:output and budget:<B>:weight chosen on the calibration activations (--calib-io / --calib-split, quantization_analysis_amd
 /budget_maps.py) and evaluated like every other candidate.  --gptq adds GPTQ error-compensated weights built on the same calibration
 activations (quantization_analysis_amd/gptq.py): gptq:<bfp*>, gptq:<map> and gptq:budget:<B>:output, each at its RTN counterpart's bytes.
+--transpose (implied by a config with the transpose algorithm) adds <bfp*>+transpose, Ŵ = quantize(Wᵀ)ᵀ with one shared exponent per 16
+rows of a column, and with --budget-bits the maps budget:<B>:<basis>+transpose over Wᵀ's grid; a mixed-tile config with
+"layout": "transpose" gives map:<algorithm>+transpose.  GPTQ stays row-layout only.
 
   python scripts/layer_output_error.py /path/to/DeepSeek-R1 /path/to/io model.layers.0.mlp --backend hip -c bf16 bfp8 bfp4 bfp2 \\
       --compression-config compression_configs/compression_config.mixed_tile_greedy.example.json --split test --out-dir results/loe
@@ -28,7 +31,7 @@ from quantization_analysis_amd.budget_maps import bits_tag
 from quantization_analysis_amd.compression_algorithms import load_compression_config
 from quantization_analysis_amd.layer_io import select_ops
 from quantization_analysis_amd.model_source import build_model_index, resolve_format_list
-from quantization_analysis_amd.output_error import BACKENDS, X_FORMATS, check_layout, evaluate_op
+from quantization_analysis_amd.output_error import BACKENDS, LAYOUTS, X_FORMATS, check_layout, evaluate_op
 from quantization_analysis_amd.quantization_formats import BASE_FORMATS as SUPPORTED_FORMATS  # no proxy rows here
 
 
@@ -52,7 +55,10 @@ def parse_args(argv=None):
     p.add_argument("--calib-io", default=None, help="Calibration activations of the budget maps (default: io_root).")
     p.add_argument("--calib-split", choices=["calibration", "test", "all"], default="calibration")
     p.add_argument("--calib-max-samples", type=int, default=None, help="First N calibration samples (by sample index).")
-    p.add_argument("--save-maps", action="store_true", help="Write <out-dir>/maps/<op>/budget_<B>_{output,weight}.npy.")
+    p.add_argument("--save-maps", action="store_true",
+                   help="Write <out-dir>/maps/<op>/budget_<B>_{output,weight}.npy (and budget_<B>_<basis>_transpose.npy over Wᵀ's grid).")
+    p.add_argument("--transpose", action="store_true",
+                   help="Add the transposed BFP layout: <bfp*>+transpose and, with --budget-bits, budget:<B>:<basis>+transpose.")
     p.add_argument("--gptq", action="store_true",
                    help="Add GPTQ error-compensated weights built on the calibration activations: gptq:<bfp*>, gptq:<map>, gptq:budget:<B>:output.")
     p.add_argument("--gptq-damp", type=float, default=0.01, metavar="D", help="GPTQ damping: λ = D · mean(diag H) (finite, > 0).")
@@ -78,7 +84,8 @@ def _fmt(v, spec):
 def main(argv=None) -> int:
     args = parse_args(argv)
     config = load_compression_config(args.compression_config) if args.compression_config else None
-    check_layout(config)
+    check_layout(config, LAYOUTS)
+    transpose = args.transpose or (config is not None and config.algorithm == "transpose")
     formats = resolve_format_list(args.formats or (config.quantization_formats if config else None), SUPPORTED_FORMATS)
     if args.backend == "hip":
         import torch
@@ -100,6 +107,8 @@ def main(argv=None) -> int:
         extra = {"budgets": budgets, "calib": calib.get(op.op)} if budgets or args.gptq else {}
         if args.gptq:
             extra.update(gptq=True, gptq_damp=args.gptq_damp)
+        if transpose:
+            extra.update(transpose=True)
         res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows, args.x_format, **extra)
         if res.skipped:
             skipped.append((op.op, res.skipped))
@@ -125,7 +134,8 @@ def main(argv=None) -> int:
                     if "assignment" in r.extra:
                         d = out_dir / "maps" / res.op
                         d.mkdir(parents=True, exist_ok=True)
-                        np.save(d / f"budget_{bits_tag(r.extra['bits'])}_{r.extra['basis']}.npy", r.extra["assignment"])
+                        tag = "_transpose" if r.extra.get("layout") == "transpose" else ""
+                        np.save(d / f"budget_{bits_tag(r.extra['bits'])}_{r.extra['basis']}{tag}.npy", r.extra["assignment"])
         records.append(rec)
     if skipped:
         print("\nskipped:")
@@ -144,6 +154,8 @@ def main(argv=None) -> int:
         doc.update({"calib_io": calib_io, "calib_split": args.calib_split, "calib_max_samples": args.calib_max_samples})
     if args.gptq:
         doc.update({"gptq_damp": args.gptq_damp})
+    if transpose:
+        doc.update({"transpose": True})
     (out_dir / "layer_output_error.json").write_text(json.dumps(doc, indent=2))
     print(f"\nwrote {out_dir / 'layer_output_error.csv'} and {out_dir / 'layer_output_error.json'}")
     return 0

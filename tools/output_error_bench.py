@@ -9,8 +9,10 @@ candidates bf16, bfp8, bfp4, bfp2 and the reference.
 TFLOP/s counts 2·M·N·K per candidate GEMM (4 formats + the reference).
 --x-format bfp8 / bfp4 / bfp2: `fused` is the activation pre-pass (mtq_quantize_rows_bf16) plus one mtq_output_error_qx launch; the row
 also reports the pre-pass alone (prepass_ms) and the W-only launch of the same session (w_only_ms), and qx_ratio = fused / W-only.
+--layout transpose: `fused` is one mtq_output_error_transposed launch with the same candidates (bfp8 / bfp4 / bfp2 in the transposed
+layout); the row also reports the row launch of the same session (rows_ms) and t_ratio = fused / rows.
 
-  python tools/output_error_bench.py [--tokens 12800] [--reps 3] [--only mlp] [--x-format bfp8] [--json out.json]
+  python tools/output_error_bench.py [--tokens 12800] [--reps 3] [--only mlp] [--x-format bfp8] [--layout transpose] [--json out.json]
 """
 from __future__ import annotations
 
@@ -64,6 +66,7 @@ def main() -> int:
     ap.add_argument("--only", choices=["all", "mlp"], default="all")
     ap.add_argument("--no-unfused", action="store_true")
     ap.add_argument("--x-format", choices=list(hb.X_FORMATS), default="bf16", help="the candidates' activation format (bf16: X as is)")
+    ap.add_argument("--layout", choices=["rows", "transpose"], default="rows", help="the BFP layout of the fused launch")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -84,15 +87,17 @@ def main() -> int:
         scratch = torch.empty((hb.output_error_scratch(args.tokens, n),), dtype=torch.float64, device=dev)
         mask = hb.fmt_mask(FMTS)
 
+        oe = hb.output_error_transposed if args.layout == "transpose" else hb.output_error
+
         def fused():
             sums.zero_()
-            hb.output_error(x, w, mask, sums, scratch=scratch)
+            oe(x, w, mask, sums, scratch=scratch)
 
         xq = torch.empty_like(x)
 
         def fused_qx():
             sums.zero_()
-            hb.output_error(x, w, mask, sums, scratch=scratch, xq=hb.quantize_rows_bf16(x, args.x_format, out=xq))
+            oe(x, w, mask, sums, scratch=scratch, xq=hb.quantize_rows_bf16(x, args.x_format, out=xq))
 
         qx = args.x_format != "bf16"
         t_f = _time(fused_qx if qx else fused, args.reps)
@@ -102,6 +107,13 @@ def main() -> int:
             t_p = _time(lambda: hb.quantize_rows_bf16(x, args.x_format, out=xq), max(args.reps, 10))
             t_w = _time(fused, args.reps)
             row.update({"x_format": args.x_format, "prepass_ms": t_p * 1e3, "w_only_ms": t_w * 1e3, "qx_ratio": t_f / t_w})
+        if args.layout == "transpose":
+            def rows_launch():
+                sums.zero_()
+                hb.output_error(x, w, mask, sums, scratch=scratch)
+
+            t_r = _time(rows_launch, args.reps)
+            row.update({"layout": "transpose", "rows_ms": t_r * 1e3, "t_ratio": t_f / t_r})
         if not args.no_unfused:
             t_u = _time(lambda: unfused(x, w), args.reps)
             row.update({"unfused_ms": t_u * 1e3, "unfused_tflops": flop / t_u / 1e12, "speedup": t_u / t_f})
