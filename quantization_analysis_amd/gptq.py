@@ -19,7 +19,8 @@ Fixed-exponent element rule q_E(x, f) of a float64 value x:
   With E = the group's own maximum exponent field, q_E equals quantize_weight_values bit for bit.
 
 Sweep (row-independent, float64): for each row and j = 0 .. k−1 in order:
-  1. at the start of a 16-column group, E = the maximum exponent field of float32 of the group's CURRENT values (columns < k only);
+  1. at the start of a 16-column group, E = the maximum exponent field of float32 of the group's CURRENT values (columns < k only; the
+     device pads the last group with zeros instead, whose exponent field 0 never raises a maximum: the same rule);
   2. f = the code of j's tile; q_j = q_E(w_j, f);
   3. e_j = (w_j − q_j) / U_jj;
   4. w_j' −= e_j · U_jj' for every j' > j.

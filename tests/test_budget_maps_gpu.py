@@ -1,6 +1,7 @@
 """Budget maps on the MI355X: the Gram kernel against float64 within its contract's bound, the tile error tables against float64 from
 the kernel's own H, hip maps against emulation maps where the cut has a slope margin above the tables' error, the budget rows' LOE,
-the activation-aware map's quality and the CLI."""
+the activation-aware map's quality and the CLI.  The exact cases (integer X and H, dyadic W: bit equality, every span, fold and step
+edge of the Gram kernel, shapes where the tables' grid-stride loop iterates) are in test_calibration_exact_gpu.py."""
 from __future__ import annotations
 
 import json

@@ -1,6 +1,7 @@
 """GPTQ on the MI355X: the full Gram kernel against float64 within its contract's bound (symmetric, deterministic, chunked), the sweep
 against the host emulation on the same host-factorised U (bitwise on rows whose decisions are clear), the diagonal-H case against
-round-to-nearest, and the GPTQ rows of evaluate_op and the CLI."""
+round-to-nearest, and the GPTQ rows of evaluate_op and the CLI.  The exact cases (integer X, dyadic W and U: bit equality on every
+entry and every row, the rows on a tie and the saturating ones included) are in test_calibration_exact_gpu.py."""
 from __future__ import annotations
 
 import functools

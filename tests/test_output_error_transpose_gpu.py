@@ -1,6 +1,8 @@
 """Layer-output error in the transposed BFP layout on the MI355X (mtq_output_error_transposed, mtq_tile_error_tables_transposed):
 bounds against the float64 emulation on ragged shapes, exact one-hot probes of whole column groups (the reference's own transposed
-bits included), the layout-free slots against the row launch bit for bit, the transposed tables and maps, and the CLI end to end."""
+bits included), the layout-free slots against the row launch bit for bit, the transposed tables and maps, and the CLI end to end.
+The transposed tables' exact cases (integer H, dyadic W: bit equality, shapes where the grid-stride loop iterates) are in
+test_calibration_exact_gpu.py."""
 from __future__ import annotations
 
 import json
