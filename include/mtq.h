@@ -576,6 +576,20 @@ int mtq_selftest_slot_ring(void);
  * [0] start-up + initial sums, [1] base pass + draw-only shuffle, then for pass p = 1..3: [2+3(p-1)] candidates + shuffle,
  * [3+3(p-1)] deltas, [4+3(p-1)] visits.  Synchronises the device. */
 int mtq_debug_scan_ticks(uint64_t out[16]);
+/* The grid K1 launches over `total` work items on a device of `cus` compute units: kind MTQ_K1_BF16 (the LDS-staged bf16 kernel,
+ * total in 32x128 units) or MTQ_K1_DIRECT (the direct kernel, uniform or ragged, total in tiles).  A host function: no GPU.
+ * out[0] blocks; out[1] the claims a wave makes before it retires, as passed to the kernel (0: no limit; the direct kernel's is
+ * 16 x units_per_wave); out[2] the counter groups in use, min(blocks, 64): group g's blocks g, g + groups, ... claim units
+ * g, g + groups, ...  waves_per_simd < 0 and units_per_wave < 0 stand for what this process uses (MTQ_K1_WAVES, else what the
+ * kernel is compiled for - for MTQ_K1_BF16 that of the instantiations evaluating two or three BFP formats; MTQ_K1_UNITS_PER_WAVE,
+ * else 8).  units_per_wave 0: waves never retire.  This is the function both launchers size their grids with. */
+#define MTQ_K1_BF16 0
+#define MTQ_K1_DIRECT 1
+int mtq_debug_k1_grid(int kind, int64_t total, int cus, int waves_per_simd, int units_per_wave, int64_t out[3]);
+/* Synchronises the current device and counts the K1 claim counters and wave-completion words of its slot ring that are not zero
+ * (the launch-id stamp word of a slot is not counted).  Every K1 launch leaves its slot zeroed, so *nonzero is 0 between launches -
+ * also when no launch has allocated the ring yet. */
+int mtq_debug_work_counters(int64_t *nonzero);
 
 #ifdef __cplusplus
 }

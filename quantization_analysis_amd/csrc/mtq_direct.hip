@@ -27,6 +27,7 @@
 namespace mtq {
 
 constexpr int kDirectWaves = 2;                                   // waves per block (independent waves; 2 instead of 4 for the same reason as mtq_fast.hip's kFastWaves)
+constexpr int kDirectQuotaScale = 16;                             // tiles a wave takes per unit of MTQ_K1_UNITS_PER_WAVE (direct_grid)
 constexpr unsigned long long kRedoMagicDirect = 0x7FF8C0DE5EED0001ull; // same pattern as mtq_fast.hip / mtq_kernels.hip
 __host__ __device__ constexpr int direct_pad(uint32_t fm) { return (2 + 4 * popc4(fm)) | 1; }  // odd stride in doubles
 
@@ -276,22 +277,19 @@ static int direct_grid(int64_t total, dim3 &grid, int &quota)
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return fail(MTQ_ERR_HIP, "hipGetDeviceProperties failed");
         cus = p.multiProcessorCount;
     }
-    const int64_t need = (total + kDirectWaves - 1) / kDirectWaves;
-    const int64_t max_blocks = (int64_t)cus * MTQ_DIRECT_WAVES_PER_SIMD * 4 / kDirectWaves;   // resident blocks: that many waves on each of a CU's 4 SIMDs
     // MTQ_K1_UNITS_PER_WAVE (mtq_fast.hip; default 8) x 16 tiles: a wave of this kernel restarts more expensively (its prefetch chain),
     // measured on 8 x 4096² float32: 32 tiles per wave cost 10 % of the launch, 128 tiles 1 %
-    static int tpw = -1;
-    if (tpw < 0) { const char *e = getenv("MTQ_K1_UNITS_PER_WAVE"); tpw = 16 * (e ? atoi(e) : 8); if (tpw < 0) tpw = 0; }
-    int64_t want = need < max_blocks ? need : max_blocks;
-    quota = 0;
-    if (tpw > 0 && need > max_blocks) {
-        const int64_t by_quota = (total + (int64_t)kDirectWaves * tpw - 1) / ((int64_t)kDirectWaves * tpw);
-        want = ((by_quota + kWorkGroups - 1) / kWorkGroups + 1) * kWorkGroups;
-        if (want < max_blocks) want = max_blocks;
-        quota = tpw;
-    }
-    grid = dim3((unsigned)want);
+    const K1Grid kg = k1_grid(total, cus, MTQ_DIRECT_WAVES_PER_SIMD, kDirectWaves, kDirectQuotaScale * k1_units_per_wave());
+    quota = kg.quota;
+    grid = dim3((unsigned)kg.blocks);
     return MTQ_OK;
+}
+
+void mtq::direct_k1_constants(int *waves_per_block, int *waves_per_simd, int *quota_scale)
+{
+    *waves_per_block = kDirectWaves;
+    *waves_per_simd = MTQ_DIRECT_WAVES_PER_SIMD;
+    *quota_scale = kDirectQuotaScale;
 }
 
 // Launcher used by mtq_tile_stats_batched for every input the bf16 LDS-staged kernel does not take (mtq_kernels.hip

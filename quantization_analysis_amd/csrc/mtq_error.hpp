@@ -20,6 +20,33 @@ constexpr int kWorkStamp = 1;
 // Word 2 of a slot counts the waves of the launch that have finished (exact-integer bf16 kernel): the wave that completes the count sets
 // the unit counters and this word back to zero, so that launch needs no follow-up kernel for the reset (round 3).
 constexpr int kWorkDone = 2;
+// Grid of a K1 launch over `total` units (bf16 kernel) or tiles (direct kernel), the ONE place its arithmetic lives (both launchers
+// and mtq_debug_k1_grid call it).  Waves claim units from the group counters above: group g of `groups` = min(blocks, kWorkGroups)
+// owns units g, g + groups, …  Three regimes:
+//   all resident        every unit has a wave of its own and the blocks fit the chip (need <= max_blocks): quota 0;
+//   quota, resident     waves retire after `quota` claims, and the grid that needs is still no larger than max_blocks;
+//   oversubscribed      the units need more blocks at `quota` per wave than are resident at once: whole counter groups plus one
+//                       spare block per group (a block that finds its group's queue empty exits at once).
+// quota 0 on input: waves never retire (a fully persistent grid of at most max_blocks).
+struct K1Grid { int64_t blocks; int quota, groups; };
+inline K1Grid k1_grid(int64_t total, int cus, int waves_per_simd, int waves_per_block, int quota)
+{
+    const int64_t need = (total + waves_per_block - 1) / waves_per_block;
+    const int64_t max_blocks = (int64_t)cus * waves_per_simd * 4 / waves_per_block;   // resident blocks: that many waves on each of a CU's 4 SIMDs
+    K1Grid g{need < max_blocks ? need : max_blocks, 0, 0};
+    if (quota > 0 && need > max_blocks) {
+        const int64_t by_quota = (total + (int64_t)waves_per_block * quota - 1) / ((int64_t)waves_per_block * quota);
+        g.blocks = ((by_quota + kWorkGroups - 1) / kWorkGroups + 1) * kWorkGroups;
+        if (g.blocks < max_blocks) g.blocks = max_blocks;
+        g.quota = quota;
+    }
+    g.groups = (int)(g.blocks < kWorkGroups ? g.blocks : kWorkGroups);
+    return g;
+}
+// MTQ_K1_UNITS_PER_WAVE, read once (default 8; 0 or negative: persistent waves).  The direct kernel's quota is 16 tiles per unit of it.
+int k1_units_per_wave();
+// The direct kernel's share of mtq_debug_k1_grid (mtq_direct.hip): waves per block, waves per SIMD, tiles of quota per unit of the switch.
+void direct_k1_constants(int *waves_per_block, int *waves_per_simd, int *quota_scale);
 unsigned next_launch_id();
 struct WorkSlot { unsigned *counters = nullptr; int index = -1, device = -1; };
 // MTQ_OK and a slot whose previous user `stream` now waits for, or MTQ_ERR_HIP.

@@ -792,6 +792,40 @@ static int fast_cus()
     return cus;
 }
 
+// MTQ_K1_WAVES: waves per SIMD the grid is sized for (experiments); 0: what the instantiation is compiled for
+static int k1_env_waves()
+{
+    static int wps = -1;
+    if (wps < 0) { const char *e = getenv("MTQ_K1_WAVES"); wps = e ? atoi(e) : 0; if (wps < 0) wps = 0; }
+    return wps;
+}
+
+int mtq::k1_units_per_wave()
+{
+    static int upw = -1;
+    if (upw < 0) { const char *e = getenv("MTQ_K1_UNITS_PER_WAVE"); upw = e ? atoi(e) : 8; if (upw < 0) upw = 0; }
+    return upw;
+}
+
+// include/mtq.h.  A host function: it asks no device, the caller names the CU count.
+extern "C" int mtq_debug_k1_grid(int kind, int64_t total, int cus, int waves_per_simd, int units_per_wave, int64_t out[3])
+{
+    if (!out) return fail(MTQ_ERR_INVALID, "null argument");
+    if ((kind != MTQ_K1_BF16 && kind != MTQ_K1_DIRECT) || total <= 0 || total >= ((int64_t)1 << 31) || cus <= 0 || cus > (1 << 20) || waves_per_simd > 64)
+        return fail(MTQ_ERR_INVALID, "mtq_debug_k1_grid: kind must be MTQ_K1_BF16 or MTQ_K1_DIRECT, total in [1, 2^31), cus positive, waves_per_simd at most 64");
+    int waves_per_block = kFastWaves, wps = k1_env_waves() > 0 ? k1_env_waves() : rolled_waves(7u, 7u), scale = 1;
+    if (kind == MTQ_K1_DIRECT) direct_k1_constants(&waves_per_block, &wps, &scale);
+    if (waves_per_simd > 0) wps = waves_per_simd;
+    if (waves_per_simd == 0) return fail(MTQ_ERR_INVALID, "mtq_debug_k1_grid: waves_per_simd must be positive, or negative for this process's value");
+    const int64_t upw = units_per_wave < 0 ? k1_units_per_wave() : units_per_wave;
+    if (upw * scale > INT32_MAX / 2) return fail(MTQ_ERR_INVALID, "mtq_debug_k1_grid: units_per_wave out of range");
+    const K1Grid g = k1_grid(total, cus, wps, waves_per_block, (int)(upw * scale));
+    out[0] = g.blocks;
+    out[1] = g.quota;
+    out[2] = g.groups;
+    return MTQ_OK;
+}
+
 // Launcher used by mtq_tile_stats_batched / mtq_tile_stats_partial when the input qualifies (mtq_kernels.hip decides).
 // fmt_mask: record layout; eval_mask ⊂ fmt_mask: slots to write; part_mask ⊂ eval_mask: slots that only get Σy, Σy², Σxy
 // (served for the combinations instantiated below; any other part_mask is widened to full slots, which is always allowed).
@@ -811,23 +845,10 @@ extern "C" int mtq_launch_tile_stats_bf16_fast(const void *x, int64_t count, int
     uint32_t part = (part_mask >> 1) & 7u;
     if (!((bfp == 3u && part == 2u) || (bfp == 1u && part == 1u) || (bfp == 2u && part == 2u))) { part = 0u; part_mask = 0u; }
     const uint32_t sums = bfp, errs = bfp & ~part;
-    const int64_t need = (total + kFastWaves - 1) / kFastWaves;
-    static int wps_env = -1;                              // MTQ_K1_WAVES: waves per SIMD the grid is sized for (experiments)
-    if (wps_env < 0) { const char *e = getenv("MTQ_K1_WAVES"); wps_env = e ? atoi(e) : 0; }
-    const int wps = wps_env > 0 ? wps_env : rolled_waves(sums, errs);
-    const int64_t max_blocks = (int64_t)cus * wps * 4 / kFastWaves; // resident blocks: that many waves on each of a CU's 4 SIMDs
-    // MTQ_K1_UNITS_PER_WAVE (default 8; 0 = persistent waves): with a bound, the grid is what the units need at that many per wave,
-    // rounded up to whole counter groups plus one spare block per group (a block that finds its group's queue empty exits at once)
-    static int upw = -1;
-    if (upw < 0) { const char *e = getenv("MTQ_K1_UNITS_PER_WAVE"); upw = e ? atoi(e) : 8; if (upw < 0) upw = 0; }
-    int64_t want = need < max_blocks ? need : max_blocks;
-    if (upw > 0 && need > max_blocks) {
-        const int64_t by_quota = (total + (int64_t)kFastWaves * upw - 1) / ((int64_t)kFastWaves * upw);
-        want = ((by_quota + kWorkGroups - 1) / kWorkGroups + 1) * kWorkGroups;
-        if (want < max_blocks) want = max_blocks;
-    }
-    const unsigned blocks = (unsigned)want;
-    const dim3 grid(blocks), block(kFastWaves * 64);
+    const int env_wps = k1_env_waves();
+    // MTQ_K1_UNITS_PER_WAVE (default 8; 0 = persistent waves): with a bound, the grid is what the units need at that many per wave (k1_grid)
+    const K1Grid kg = k1_grid(total, cus, env_wps > 0 ? env_wps : rolled_waves(sums, errs), kFastWaves, k1_units_per_wave());
+    const dim3 grid((unsigned)kg.blocks), block(kFastWaves * 64);
     static int lds_pad = -1;                              // MTQ_K1_LDS_PAD: extra LDS bytes per block (experiments on what fits beside K1)
     if (lds_pad < 0) { const char *e = getenv("MTQ_K1_LDS_PAD"); lds_pad = e ? atoi(e) : 0; }
     const size_t lds_bytes = kFastWaves * kRolledWaveLds + (size_t)lds_pad;
@@ -837,7 +858,7 @@ extern "C" int mtq_launch_tile_stats_bf16_fast(const void *x, int64_t count, int
     unsigned *work = work_out->counters;
     const ListedArgs none{};
 #define MTQ_LAUNCH_FAST(S, E) \
-    hipLaunchKernelGGL((tile_stats_bf16_rolled<S, E, true, false>), grid, block, lds_bytes, st, xp, stride_elems, ld, (int)tw, tiles, (int)units_w, (int)upt, (int)total, fmt_mask, eval_mask, part_mask, rec, stats, work, launch_id, (need > max_blocks ? upw : 0), none, mark, self_reset)
+    hipLaunchKernelGGL((tile_stats_bf16_rolled<S, E, true, false>), grid, block, lds_bytes, st, xp, stride_elems, ld, (int)tw, tiles, (int)units_w, (int)upt, (int)total, fmt_mask, eval_mask, part_mask, rec, stats, work, launch_id, kg.quota, none, mark, self_reset)
     switch (sums | (errs << 4)) { // one instantiation per evaluated subset: what is not asked for costs nothing
     case 0x11: MTQ_LAUNCH_FAST(1u, 1u); break;
     case 0x22: MTQ_LAUNCH_FAST(2u, 2u); break;

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <vector>
 
 #include "../../include/mtq.h"
 #include "mtq_device.hpp"
@@ -363,6 +364,30 @@ void mtq::work_counter_abandon(const WorkSlot &slot)
 {
     if (slot.index < 0 || slot.device < 0) return;
     g_rings[slot.device].slots.abandon(slot.index);
+}
+
+// include/mtq.h: the claim counters and kWorkDone words of the current device's ring that are not zero (every launch leaves them at
+// zero: by its follow-up kernel, or by its own last wave).  The stamp word keeps its last launch id by design and is not counted.
+extern "C" int mtq_debug_work_counters(int64_t *nonzero)
+{
+    if (!nonzero) return fail(MTQ_ERR_INVALID, "null argument");
+    *nonzero = 0;
+    if (int rc = require_device()) return rc;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return fail(MTQ_ERR_HIP, "hipGetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(MTQ_ERR_HIP, "hipDeviceSynchronize failed");
+    const unsigned *base = g_rings[dev].base.load(std::memory_order_acquire);
+    if (!base) return MTQ_OK;                            // no K1 launch on this device yet
+    std::vector<unsigned> host(kWorkSlots * kSlotUnsigned);
+    if (hipMemcpy(host.data(), base, host.size() * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return fail(MTQ_ERR_HIP, "could not read the work counters");
+    int64_t n = 0;
+    for (int s = 0; s < kWorkSlots; ++s) {
+        const unsigned *slot = host.data() + (size_t)s * kSlotUnsigned;
+        for (int g = 0; g < kWorkGroups; ++g) n += slot[g * kWorkStride] != 0u;
+        n += slot[kWorkDone] != 0u;
+    }
+    *nonzero = n;
+    return MTQ_OK;
 }
 
 // Everything the library holds on to between calls is released here, on request — never from a static destructor, where the HIP

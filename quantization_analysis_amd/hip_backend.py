@@ -107,6 +107,8 @@ SIGNATURES = {
     "mtq_gptq_sweep": ("i", "pilllpzpzplppzp", True),
     "mtq_output_error_transposed": ("i", "plllpillpuppilppzppl", True),
     "mtq_tile_error_tables_transposed": ("i", "pilllpzppzp", True),
+    "mtq_debug_k1_grid": ("i", "iliiip", True),
+    "mtq_debug_work_counters": ("i", "p", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -471,6 +473,41 @@ def tile_stats_partial_end(x3d, layout_mask: int, stats, mark, launch_id: int) -
     code, count, stride, rows, cols, ld = _contiguous_batch(x3d)
     check(lib().mtq_tile_stats_partial_end(x3d.data_ptr(), code, count, stride, rows, cols, ld, layout_mask, stats.data_ptr(),
                                            mark.data_ptr(), int(launch_id), _stream_ptr()))
+
+
+K1_BF16, K1_DIRECT = 0, 1   # include/mtq.h MTQ_K1_BF16, MTQ_K1_DIRECT
+
+
+def k1_grid(kind: int, total: int, cus: int, waves_per_simd: int = -1, units_per_wave: int = -1) -> tuple[int, int, int]:
+    """mtq_debug_k1_grid (a host function): (blocks, per-wave quota as the kernel gets it, counter groups) of a K1 launch over `total`
+    units (K1_BF16) or tiles (K1_DIRECT) on `cus` compute units; negative switches stand for this process's own."""
+    out = (ctypes.c_int64 * 3)()
+    check(_entry("mtq_debug_k1_grid")(int(kind), int(total), int(cus), int(waves_per_simd), int(units_per_wave), out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def k1_waves_per_block(kind: int) -> int:
+    """Waves in a block of that kernel, read off the grid of 64 units on a device with room for all of them (blocks = ceil(64 / W))."""
+    return 64 // k1_grid(kind, 64, 4096, 8, 0)[0]
+
+
+def k1_regime(kind: int, total: int, cus: int, waves_per_simd: int = -1, units_per_wave: int = -1) -> str:
+    """The regime of that launch (csrc/mtq_error.hpp k1_grid): 'resident' (every unit has a wave of its own), 'quota' (waves retire
+    after their quota, the grid is what fits the chip), 'oversubscribed' (more blocks than fit), or 'persistent' (more units than
+    waves and no quota: units_per_wave 0)."""
+    blocks, quota, _groups = k1_grid(kind, total, cus, waves_per_simd, units_per_wave)
+    if quota == 0:
+        return "resident" if blocks * k1_waves_per_block(kind) >= total else "persistent"
+    resident = k1_grid(kind, total, cus, waves_per_simd, 0)[0]
+    return "quota" if blocks == resident else "oversubscribed"
+
+
+def work_counters_nonzero() -> int:
+    """mtq_debug_work_counters: synchronises the current device; how many K1 claim counters and completion words of its ring are not zero
+    (0 between launches, whatever ran before)."""
+    n = ctypes.c_int64(-1)
+    check(_entry("mtq_debug_work_counters")(ctypes.byref(n)))
+    return int(n.value)
 
 
 def quantize(x2d, fmt: str, out=None):

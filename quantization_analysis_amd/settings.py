@@ -2,8 +2,12 @@
 
 The product has no configuration beyond the reference's own (CLI flags, compression config JSON).  What is listed here are
 MEASUREMENT switches: A/B levers of experiments recorded in DESIGN.md / profiles/, read ONCE per process by `settings()`
-(Python side) or on first use by the library (C side).  Defaults are what ships; nothing here changes results — every
-combination is covered by the same parity tests.
+(Python side) or on first use by the library (C side).  Defaults are what ships; nothing here changes results.  What checks that:
+MTQ_K1_UNITS_PER_WAVE x MTQ_K1_WAVES (every regime of the K1 grid), MTQ_K1_LDS_PAD, MTQ_LISTED_WAVES and MTQ_LISTED_DIRECT each run
+tests/k1_claim_cases.py in a process of their own (tests/test_k1_work_claim_gpu.py::test_geometry_switches_in_fresh_processes; the
+grid arithmetic at other CU counts: tests/test_k1_grid_host.py); MTQ_FORCE_GENERIC: test_pipeline_under_force_generic_switch;
+MTQ_LAZY / MTQ_K1_TWO_LAUNCH: test_lazy_pipeline_equals_whole_record_pipeline; MTQ_KNIFE_CAP: test_threshold_ragged_groups
+(all tests/test_hip_kernels.py).  The other switches have no test that sets them: their defaults are what the suite runs.
 
 Python side (this module)
 | variable | default | meaning |

@@ -35,6 +35,22 @@ def test_work_counter_slot_bookkeeping():
     assert hb.lib().mtq_selftest_slot_ring() == 0
 
 
+def test_k1_diagnostics_are_host_callable():
+    """mtq_debug_k1_grid needs no device (tests/test_k1_grid_host.py sweeps it); mtq_debug_work_counters reports the missing device
+    instead of counting, and both refuse a null result pointer."""
+    import torch
+
+    L = hb.lib()
+    out = (ctypes.c_int64 * 3)()
+    assert L.mtq_debug_k1_grid(hb.K1_BF16, 1000, 256, 3, 8, out) == 0 and list(out) == [500, 0, 64]
+    assert L.mtq_debug_k1_grid(hb.K1_DIRECT, 1000, 256, 3, 8, None) == -1 and b"null" in L.mtq_last_error()
+    assert L.mtq_debug_k1_grid(2, 1000, 256, 3, 8, out) == -1 and b"kind" in L.mtq_last_error()
+    assert L.mtq_debug_work_counters(None) == -1
+    if not torch.cuda.is_available():
+        n = ctypes.c_int64(-1)
+        assert L.mtq_debug_work_counters(ctypes.byref(n)) == -3 and n.value == 0
+
+
 def test_argument_errors_are_reported():
     L = hb.lib()
     assert L.mtq_tile_stats(None, 0, 32, 32, 32, 0xF, None, None) == -1
