@@ -3,7 +3,7 @@
 Random shapes (ragged and aligned), storage types, value distributions (wide exponent spreads, zeros, sparse groups,
 huge / tiny scales, ±Inf / NaN / denormals, offset tensors, the scales where the reference's float32 dots overflow or go
 subnormal — two NaNs compare equal whatever their payload), format subsets: K1 / K1T records, K2 / K2T / K3 outputs and
-greedy / threshold maps against the CPU oracle, bit for bit."""
+greedy / threshold maps (pcc, mae, atol; the plugin route and ThresholdPipeline) against the CPU oracle, bit for bit."""
 import sys
 import time
 
@@ -17,6 +17,7 @@ from quantization_analysis_amd import hip_backend as hb  # noqa: E402
 from quantization_analysis_amd.compression_algorithms.mixed_tile_threshold import threshold_assign  # noqa: E402
 from quantization_analysis_amd.compression_algorithms.quantizer import Quantizer  # noqa: E402
 from quantization_analysis_amd.compression_algorithms.tile_search import compute_tile_stats  # noqa: E402
+from quantization_analysis_amd.pipeline import ThresholdPipeline  # noqa: E402
 
 ALL = ["bf16", "bfp8", "bfp4", "bfp2"]
 
@@ -111,7 +112,7 @@ def run(cases: int, seed: int) -> int:
     t0 = time.time()
     bad = 0
     compared = handed_back = specials = specials_back = 0
-    thr_compared = thr_knife = 0
+    thr_compared = thr_knife = thr_piped = 0
     for c in range(cases):
         aligned = rng.random() < 0.4
         rows = int(rng.integers(1, 6)) * 32 if aligned else int(rng.integers(1, 200))
@@ -168,16 +169,23 @@ def run(cases: int, seed: int) -> int:
                 dm, ds = hb.greedy_scan_device(recs_d, 0xF, ALL, "atol", thr_a, float(x.size), sd)
                 ok_g &= int(ds.cpu()[0]) == 0 and np.array_equal(dm.cpu().numpy()[0], ga)
                 # the threshold rule (K4 on the device, knife-edge tiles re-scored literally through K2) against the literal float32 rule:
-                # pcc at a threshold ON a tile's float32 score, and mae
+                # pcc, mae and atol at a threshold ON a tile's float32 score; every fourth comparison also through ThresholdPipeline (one
+                # chunk: the fused enqueue call, the literal decisions of pipeline_threshold.py)
                 ts = compute_tile_stats(xd, ALL, Quantizer("hip"))
-                for met in ("pcc", "mae"):
+                for met in ("pcc", "mae", "atol"):
                     sc = orc.threshold_scores(x, ALL, met)
                     pick = sc[ALL[int(rng.integers(1, 4))]]
                     pick = pick[np.isfinite(pick)]
-                    thr_t = float(pick[int(rng.integers(0, pick.size))]) if pick.size else (thr if met == "pcc" else thr_m)
+                    thr_t = float(pick[int(rng.integers(0, pick.size))]) if pick.size else {"pcc": thr, "mae": thr_m, "atol": thr_a}[met]
                     want_t = orc.threshold_assign(sc, ALL, met, thr_t)
                     got_t, n_knife = threshold_assign(ts, ALL, met, thr_t, Quantizer("hip"))
                     ok_t &= np.array_equal(got_t.reshape(-1), want_t)
+                    if thr_compared % 4 == 0:
+                        with ThresholdPipeline(ALL, met, thr_t) as pipe:
+                            res = pipe.run(xd[None])
+                        ok_t &= np.array_equal(res[0].assignment.reshape(-1), want_t)
+                        ok_t &= res[0].counts == {f: int(np.sum(want_t == k)) for k, f in enumerate(ALL)}
+                        thr_piped += 1
                     thr_compared += 1
                     thr_knife += n_knife
                 order = [ALL[k] for k in rng.permutation(4)[: int(rng.integers(1, 5))]]
@@ -224,9 +232,12 @@ def run(cases: int, seed: int) -> int:
                   f"threshold {ok_t} transposed {ok_tr}", flush=True)
     print(f"{cases} cases, {bad} mismatches, {time.time() - t0:.1f} s; device pcc searches compared {compared}, handed back {handed_back} "
           f"(each checked against the host scan's zero-denominator branch); special-value inputs {specials}, handed back {specials_back}; "
-          f"threshold maps compared {thr_compared}, knife-edge tiles {thr_knife}")
+          f"threshold maps compared {thr_compared} ({thr_piped} of them through ThresholdPipeline as well), knife-edge tiles {thr_knife}")
     if cases >= 8 and not thr_compared:
         print("no threshold map was compared")
+        bad += 1
+    if thr_compared >= 8 and not thr_piped:
+        print("no threshold comparison went through ThresholdPipeline")
         bad += 1
     if thr_compared >= 20 and not thr_knife:
         print("no threshold comparison met a knife-edge tile: the thresholds placed on tile scores are not reaching the band")

@@ -39,20 +39,29 @@ def dev(x: np.ndarray, bf16: bool):
     return t.to(torch.bfloat16).cuda() if bf16 else t.cuda()
 
 
-def test_device_rule_equals_host_rule_bit_for_bit():
+@pytest.mark.parametrize("metric", ["pcc", "mae", "atol"])
+def test_device_rule_equals_host_rule_bit_for_bit(metric):
     """threshold_assign_device against threshold_assign on the same device-written records: maps, knife ids, near masks —
-    full records and (bf16 storage) the identity-bf16 records the pipelines decide on."""
+    full records and (bf16 storage) the identity-bf16 records the pipelines decide on.  mae and atol (band·max(1, |threshold|), no
+    moment widening): the inputs and thresholds of tests/test_threshold_metrics_host.py."""
+    from tests import test_threshold_metrics_host as tm
+
     total_knife = 0
-    for label, x, bf16 in inputs():
+    for label, x, bf16 in (inputs() if metric == "pcc" else tm.cases()):
         x2d, _ = hb.to_device_2d(dev(x, bf16))
         layouts = [(0xF, 0xF)] + ([(0xE, 0xE | hb.MASK_BF16_IDENTITY)] if bf16 else [])
-        scores, _ = oracle_maps(x, "pcc", [])
+        if metric == "pcc":
+            scores, _ = oracle_maps(x, "pcc", [])
+            thresholds = list(FIXED) + knife_thresholds(scores, per_format=1)
+        else:
+            knife, far = tm.thresholds(x, metric)
+            thresholds = knife + [far]
         for k1, dec in layouts:
             sdev = hb.tile_stats(x2d, k1)
             shost = sdev.cpu().numpy()
-            for thr in list(FIXED) + knife_thresholds(scores, per_format=1):
-                a_d, k_d, n_d = hb.threshold_assign_device(sdev, dec, ALL, "pcc", thr, 2e-6, with_near=True)
-                a_h, k_h, n_h = hb.threshold_assign(shost, dec, ALL, "pcc", thr, 2e-6, with_near=True)
+            for thr in thresholds:
+                a_d, k_d, n_d = hb.threshold_assign_device(sdev, dec, ALL, metric, thr, 2e-6, with_near=True)
+                a_h, k_h, n_h = hb.threshold_assign(shost, dec, ALL, metric, thr, 2e-6, with_near=True)
                 assert np.array_equal(a_d, a_h) and np.array_equal(k_d, k_h) and np.array_equal(n_d, n_h), (label, hex(dec), thr)
                 total_knife += k_d.size
     assert total_knife > 0
