@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTQ_VERSION 143 /* 0.1.4.8 (optional symbols as well): + mtq_output_error_transposed, mtq_tile_error_tables_transposed; 0.1.4.7 (optional symbols as well): + mtq_gram_full / _scratch_doubles, mtq_gptq_sweep / _scratch_doubles; 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
+#define MTQ_VERSION 143 /* 0.1.4.9 (optional symbols as well): + mtq_packed_tile_bytes, mtq_packed_offsets, mtq_pack_tiles, mtq_unpack_tiles, mtq_packed_linear; 0.1.4.8 (optional symbols as well): + mtq_output_error_transposed, mtq_tile_error_tables_transposed; 0.1.4.7 (optional symbols as well): + mtq_gram_full / _scratch_doubles, mtq_gptq_sweep / _scratch_doubles; 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
 
 typedef enum {
     MTQ_OK = 0,
@@ -590,6 +590,57 @@ int mtq_debug_k1_grid(int kind, int64_t total, int cus, int waves_per_simd, int 
  * (the launch-id stamp word of a slot is not counted).  Every K1 launch leaves its slot zeroed, so *nonzero is 0 between launches -
  * also when no launch has allocated the ring yet. */
 int mtq_debug_work_counters(int64_t *nonzero);
+
+/* ------------------------------------------------------------------ PACKED mixed-tile weights (csrc/mtq_packed.hip)
+ *
+ * The bytes a tile map promises (no reference counterpart: the reference only models sizes, tile_utils.py:8-14).  This is THIS
+ * project's layout, fixed here because it is an ABI; it does not claim to be TTNN's on-device tile format.
+ *
+ * Scope: the row layout (a group is 16 consecutive columns of one row) over the 2-D flatten and zero padding of tile_utils.py:91-113;
+ * tiles numbered tr * tiles_w + tc; map codes 0..3 (bf16, bfp8, bfp4, bfp2), one int8 per tile.
+ *
+ *   stream   = the tiles' blobs in tile order.  Blob sizes by code: 2048, 1088, 576, 320 bytes (all multiples of 64).
+ *   offsets  = uint32[tiles + 1], the exclusive prefix sum of the blob sizes in units of 64 bytes: tile t's blob starts at byte
+ *              64 * offsets[t], and 64 * offsets[tiles] is the stream's length.
+ *   BFP blob = 64 shared-exponent bytes, group g = 2 * row + half (row 0..31, half 0..1): the maximum float32 exponent field over
+ *              the group's 16 zero-padded elements; then the element codes in row-major order e = 32 * row + col.
+ *                bfp8: one byte per element.   bfp4: two per byte, even e in the low nibble.
+ *                bfp2: four per byte, element e in bits 2 * (e % 4) .. 2 * (e % 4) + 1.
+ *              code = (sign << M) | man, M = 7 / 3 / 1, with man as quantization_formats.py:118-158 forms it (the aligned mantissa
+ *              with its hidden bit, rounded to nearest even, saturated at 2^M - 1; 0 for an input whose exponent field is 0) and
+ *              the sign cleared when man == 0.  The float32 value K2 / K3 write is a pure function of (exponent byte, code).
+ *   bf16 blob = 1024 little-endian uint16, row-major: the upper halves of the bf16 rounding of quantization_formats.py:29-45.
+ *   Padding elements of edge tiles encode +0 (code 0); an all-padding group has exponent 0.  Every byte of the stream is written:
+ *   two packings of the same input are byte-identical.
+ *
+ * Real sizes against the reference's size model (which stays as it is): 1.0625 / 0.5625 / 0.3125 bytes per element for bfp8 / bfp4 /
+ * bfp2, where the model says 1.088 / 0.50097 / 0.25097.
+ *
+ * mtq_packed_tile_bytes and mtq_packed_offsets are HOST functions (host pointers, no device).  In the three device entry points x, y,
+ * packed, map, offsets and bias are device pointers owned by the caller and the calls are asynchronous on `stream`; packed must be
+ * 16-byte aligned.  Argument errors are MTQ_ERR_INVALID before a device is looked for.  A buffer shorter than the smallest stream the
+ * tile grid can have (320 bytes per tile) is refused at once; the stream's exact length is 64 * offsets[tiles], which the caller who
+ * built the offsets knows, and on the device every blob is checked against the buffer's length before it is touched (a blob that does
+ * not fit is not written by pack, not stored by unpack, read as zeros by linear).
+ */
+/* 2048 / 1088 / 576 / 320 for fmt 0..3, 0 for any other code. */
+size_t mtq_packed_tile_bytes(int fmt);
+/* offsets[0 .. tiles] of a host map; a code outside 0..3 (or a stream past 2^32 units) is MTQ_ERR_INVALID. */
+int mtq_packed_offsets(const int8_t *map, int64_t tiles, uint32_t *offsets);
+/* x (in_dtype, rows × cols, ld >= cols, ragged edges zero-padded) → the stream in out[0 .. 64 * offsets[tiles]).  One wave per tile,
+ * one lane per group. */
+int mtq_pack_tiles(const void *x, int in_dtype, int64_t rows, int64_t cols, int64_t ld, const int8_t *map, const uint32_t *offsets,
+                   void *out, size_t out_bytes, void *stream);
+/* The stream → y (rows × cols, ldy >= cols).  out_dtype MTQ_DTYPE_F32: bit for bit what mtq_apply_assignment writes for the packed x
+ * and map; MTQ_DTYPE_BF16: the upper halves, which is exact (every BFP and bf16 value has its low 16 bits zero). */
+int mtq_unpack_tiles(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows, int64_t cols,
+                     void *y, int out_dtype, int64_t ldy, void *stream);
+/* Y = X·Ŵᵀ + b: x m × k bf16 (ldx), Ŵ the packed n × k weight (nn.Linear convention; map grid ceil(n/32) × ceil(k/32)), bias n
+ * float32 or NULL, y m × n float32 or bf16 (out_dtype, ldy).  The weight is decoded into a bf16 LDS image (exact) and multiplied by
+ * mfma_f32_32x32x16_bf16 with f32 accumulation in a fixed K order; bias is added in f32, a bf16 y is rounded to nearest even once.
+ * No atomics: two calls give the same bits.  Any m >= 1. */
+int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                      const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream);
 
 #ifdef __cplusplus
 }

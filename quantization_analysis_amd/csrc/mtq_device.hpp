@@ -48,7 +48,10 @@ __device__ __forceinline__ uint32_t bfp_elem_bits(uint32_t u, uint32_t shared)
 
 // Same arithmetic with the mantissa width as a run-time value (1..7): lets lanes holding different BFP formats
 // share one instruction stream (K3, where neighbouring tiles of a wave use different formats).
-__device__ __forceinline__ uint32_t bfp_elem_bits_rt(uint32_t u, uint32_t shared, uint32_t M)
+// It has two halves, which the packed format (include/mtq.h, csrc/mtq_packed.hip) stores between: the ENCODE half gives the element's
+// aligned, rounded and saturated mantissa `man` (0 for an exp == 0 input), the DECODE half rebuilds the float32 word from the sign
+// bit, `man` and the shared exponent.
+__device__ __forceinline__ uint32_t bfp_encode_man_rt(uint32_t u, uint32_t shared, uint32_t M)
 {
     const uint32_t shift = 24u - M, round_mask = (1u << shift) - 1u, tie = 1u << (shift - 1u), qmax = (1u << M) - 1u;
     const uint32_t e = (u >> 23) & 0xFFu;
@@ -59,13 +62,37 @@ __device__ __forceinline__ uint32_t bfp_elem_bits_rt(uint32_t u, uint32_t shared
     man >>= shift;
     const uint32_t up = (rv > tie) | ((rv == tie) & (man & 1u));
     man = min(man + up, qmax);
-    man = e == 0u ? 0u : man;
+    return e == 0u ? 0u : man;
+}
+
+// sign31: the sign in bit 31, every other bit zero.
+__device__ __forceinline__ uint32_t bfp_decode_man_rt(uint32_t sign31, uint32_t man, uint32_t shared, uint32_t M)
+{
+    const uint32_t qmax = (1u << M) - 1u;
+    __builtin_assume(man <= qmax);                       // both callers' man is at most qmax: keeps the code of the unsplit function
     if (man == 0u) return 0u;
     const uint32_t msb = 31u - (uint32_t)__clz((int)man);
     const uint32_t sc = (M - 1u) - msb;
     const uint32_t ms = (man << (sc + 1u)) & qmax;
     const uint32_t exp_out = shared - sc;
-    return (u & 0x80000000u) | (exp_out << 23) | (ms << (23u - M));
+    return sign31 | (exp_out << 23) | (ms << (23u - M));
+}
+
+__device__ __forceinline__ uint32_t bfp_elem_bits_rt(uint32_t u, uint32_t shared, uint32_t M)
+{
+    return bfp_decode_man_rt(u & 0x80000000u, bfp_encode_man_rt(u, shared, M), shared, M);
+}
+
+// The packed code of one element, (sign << M) | man with the sign cleared when man == 0, and its inverse.
+__device__ __forceinline__ uint32_t bfp_code_rt(uint32_t u, uint32_t shared, uint32_t M)
+{
+    const uint32_t man = bfp_encode_man_rt(u, shared, M);
+    return man == 0u ? 0u : (((u >> 31) << M) | man);
+}
+
+__device__ __forceinline__ uint32_t bfp_code_bits_rt(uint32_t code, uint32_t shared, uint32_t M)
+{
+    return bfp_decode_man_rt((code >> M) << 31, code & ((1u << M) - 1u), shared, M);
 }
 
 // bfp_elem_bits_rt with the shared exponent FIXED by the caller (GPTQ's sweep, mtq_gptq.hip): an element whose exponent field is above

@@ -1,0 +1,446 @@
+// mtq_packed.hip — the packed mixed-tile weight: the bytes a tile map promises, and a linear layer that multiplies with them.
+//
+// Format (include/mtq.h, DESIGN.md "Packed mixed-tile weights"): row layout only.  Tile t = tr * tiles_w + tc of the zero-padded 2-D
+// flatten is one blob at packed + 64 * offsets[t], of 2048 / 1088 / 576 / 320 bytes for the map codes 0..3 (bf16, bfp8, bfp4, bfp2).
+// A BFP blob is 64 shared-exponent bytes (group g = 2 * row + half, 16 consecutive columns of one row) and then the element codes
+// (sign << M) | man in row-major order e = 32 * row + col: one byte each (bfp8), two per byte with even e in the low nibble (bfp4), four
+// per byte with e at bits 2(e % 4) (bfp2).  A bf16 blob is 1024 little-endian uint16, the upper halves of bf16_round_bits.  Group g's
+// codes are therefore the 16 / 8 / 4 (or, bf16, 32) contiguous bytes at 64 + 16g / 8g / 4g (32g): one lane, one vector access.
+//
+//   pack_tiles_kernel / unpack_tiles_kernel   one wave per tile, one lane per group; the format is uniform across the wave.
+//   packed_linear_kernel                      Y = X·Ŵᵀ + b in the shape of mtq_output_error.hip: a workgroup of 4 waves owns a
+//       128 (M) × 64 (N) block and walks K in steps of 64; per step each of the 256 lanes takes one group of the 64 × 64 W block, reads
+//       its exponent byte and its code bytes and decodes them into the bf16 LDS image (every BFP value has its low 16 bits zero: the
+//       image is exact), X goes to LDS beside it, mfma_f32_32x32x16_bf16 accumulates in f32.  One accumulator, one K order per output,
+//       no atomics: the same inputs give the same bits.
+//
+// Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
+// blob does not fit is not written (pack), not stored (unpack) or read as zeros (linear).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "mtq_device.hpp"
+#include "mtq_error.hpp"
+
+namespace mtq {
+namespace {
+
+constexpr int kUnit = 64;                           // offsets count units of 64 bytes
+constexpr int kExpBytes = 64;                       // shared exponents at the head of a BFP blob
+
+__host__ __device__ constexpr uint32_t packed_tile_bytes(int f)
+{
+    return f == 0 ? 2048u : (f == 1 ? 1088u : (f == 2 ? 576u : (f == 3 ? 320u : 0u)));
+}
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// 16 float32 words with zero low halves → 16 bf16, 32 bytes
+__device__ __forceinline__ void pack_halves(const uint32_t (&y)[kGroup], uint4 &lo, uint4 &hi)
+{
+    uint32_t pk[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pk[i] = (y[2 * i] >> 16) | (y[2 * i + 1] & 0xFFFF0000u);
+    lo = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+    hi = make_uint4(pk[4], pk[5], pk[6], pk[7]);
+}
+
+// The raw bytes of one group as a lane holds them: w[0..7] little-endian (32 bytes for bf16, 16 / 8 / 4 for bfp8 / bfp4 / bfp2).
+struct GroupRaw {
+    uint32_t w[8];
+    uint32_t E;
+    int f;                                           // 0..3, anything else: zeros
+};
+
+template <int F>
+__device__ __forceinline__ void decode_as(const GroupRaw &g, uint32_t (&y)[kGroup])
+{
+    constexpr uint32_t M = F == 1 ? 7u : (F == 2 ? 3u : 1u);
+    constexpr uint32_t B = M + 1u;                  // bits per code
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) {
+        const uint32_t code = (g.w[(i * B) >> 5] >> ((i * B) & 31u)) & ((1u << B) - 1u);
+        y[i] = bfp_code_bits_rt(code, g.E, M);
+    }
+}
+
+__device__ __forceinline__ void decode_group(const GroupRaw &g, uint32_t (&y)[kGroup])
+{
+    if (g.f == 0) {
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) y[i] = (i & 1) ? (g.w[i >> 1] & 0xFFFF0000u) : (g.w[i >> 1] << 16);
+    } else if (g.f == 1) {
+        decode_as<1>(g, y);
+    } else if (g.f == 2) {
+        decode_as<2>(g, y);
+    } else if (g.f == 3) {
+        decode_as<3>(g, y);
+    } else {
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) y[i] = 0u;
+    }
+}
+
+// Where tile t's blob is and what it holds: f < 0 when the tile's code is no format or its blob passes the end of the buffer.
+struct TileAt {
+    uint64_t off;
+    int f;
+};
+
+__device__ __forceinline__ TileAt tile_at(uint64_t packed_bytes, const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t t)
+{
+    TileAt a;
+    const int f = map[t];
+    a.off = (uint64_t)offsets[t] * kUnit;
+    const uint32_t size = packed_tile_bytes(f);
+    a.f = (size == 0u || a.off + size > packed_bytes) ? -1 : f;
+    return a;
+}
+
+// Group gi (0..63) of the blob at `a`.
+__device__ __forceinline__ void load_group(const uint8_t *__restrict__ packed, const TileAt &a, int gi, GroupRaw &g)
+{
+#pragma unroll
+    for (int i = 0; i < 8; ++i) g.w[i] = 0u;
+    g.E = 0u;
+    g.f = a.f;
+    if (a.f < 0) return;
+    const int f = a.f;
+    const uint8_t *blob = packed + a.off;
+    if (f == 0) {
+        const uint4 *q = reinterpret_cast<const uint4 *>(blob + gi * 32);
+        const uint4 lo = q[0], hi = q[1];
+        g.w[0] = lo.x; g.w[1] = lo.y; g.w[2] = lo.z; g.w[3] = lo.w;
+        g.w[4] = hi.x; g.w[5] = hi.y; g.w[6] = hi.z; g.w[7] = hi.w;
+        return;
+    }
+    g.E = blob[gi];
+    if (f == 1) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(blob + kExpBytes + gi * 16);
+        g.w[0] = v.x; g.w[1] = v.y; g.w[2] = v.z; g.w[3] = v.w;
+    } else if (f == 2) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(blob + kExpBytes + gi * 8);
+        g.w[0] = v.x; g.w[1] = v.y;
+    } else {
+        g.w[0] = *reinterpret_cast<const uint32_t *>(blob + kExpBytes + gi * 4);
+    }
+}
+
+// ---- pack: lane = group (row lane >> 1, half lane & 1) of the wave's tile
+template <typename T>
+__global__ __launch_bounds__(256) void pack_tiles_kernel(const T *__restrict__ x, int64_t rows, int64_t cols, int64_t ld, int vec_ok,
+                                                         const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t tiles,
+                                                         int64_t tiles_w, uint8_t *__restrict__ out, uint64_t out_bytes)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < tiles; t += (int64_t)gridDim.x * 4) {
+        const int f = map[t];
+        const uint32_t size = packed_tile_bytes(f);
+        const uint64_t off = (uint64_t)offsets[t] * kUnit;
+        if (size == 0u || off + size > out_bytes) continue;   // wave-uniform
+        const int64_t row = (t / tiles_w) * kTile + (lane >> 1), col0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
+        uint32_t u[kGroup];
+        Loader<T>::group(x, row, col0, rows, cols, ld, vec_ok != 0, u);
+        uint8_t *blob = out + off;
+        if (f == 0) {
+            uint32_t y[kGroup];
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i) y[i] = bf16_round_bits(u[i]);
+            uint4 lo, hi;
+            pack_halves(y, lo, hi);
+            uint4 *d = reinterpret_cast<uint4 *>(blob + lane * 32);
+            d[0] = lo;
+            d[1] = hi;
+            continue;
+        }
+        const uint32_t E = group_shared_exp(u);
+        const uint32_t M = f == 1 ? 7u : (f == 2 ? 3u : 1u), B = M + 1u;
+        blob[lane] = (uint8_t)E;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            const uint32_t code = bfp_code_rt(u[i], E, M);
+            if (f == 1) w[i >> 2] |= code << (8 * (i & 3));
+            else if (f == 2) w[i >> 3] |= code << (4 * (i & 7));
+            else w[0] |= code << (2 * i);
+        }
+        uint8_t *dst = blob + kExpBytes + lane * (2 * (int)B);   // 16 codes of B bits
+        if (f == 1) *reinterpret_cast<uint4 *>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+        else if (f == 2) *reinterpret_cast<uint2 *>(dst) = make_uint2(w[0], w[1]);
+        else *reinterpret_cast<uint32_t *>(dst) = w[0];
+    }
+}
+
+// ---- unpack: the same ownership; y float32 (the words) or bf16 (their upper halves)
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void unpack_tiles_kernel(const uint8_t *__restrict__ packed, uint64_t packed_bytes, const int8_t *__restrict__ map,
+                                                           const uint32_t *__restrict__ offsets, int64_t tiles, int64_t tiles_w, int64_t rows,
+                                                           int64_t cols, void *__restrict__ yv, int64_t ldy, int vec_ok)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < tiles; t += (int64_t)gridDim.x * 4) {
+        const int64_t row = (t / tiles_w) * kTile + (lane >> 1), col0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
+        GroupRaw g;
+        load_group(packed, tile_at(packed_bytes, map, offsets, t), lane, g);
+        if (g.f < 0 || row >= rows || col0 >= cols) continue;
+        uint32_t y[kGroup];
+        decode_group(g, y);
+        const bool whole = col0 + kGroup <= cols && vec_ok;
+        if constexpr (BF16OUT) {
+            uint16_t *yr = static_cast<uint16_t *>(yv) + row * ldy + col0;
+            if (whole) {
+                uint4 lo, hi;
+                pack_halves(y, lo, hi);
+                reinterpret_cast<uint4 *>(yr)[0] = lo;
+                reinterpret_cast<uint4 *>(yr)[1] = hi;
+            } else {
+#pragma unroll
+                for (int i = 0; i < kGroup; ++i)
+                    if (col0 + i < cols) yr[i] = (uint16_t)(y[i] >> 16);
+            }
+        } else {
+            uint32_t *yr = static_cast<uint32_t *>(yv) + row * ldy + col0;
+            if (whole) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(yr)[i] = make_uint4(y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < kGroup; ++i)
+                    if (col0 + i < cols) yr[i] = y[i];
+            }
+        }
+    }
+}
+
+// ---- linear
+constexpr int kBM = 128, kBN = 64, kBK = 64, kThreads = 256;
+constexpr int kLdk = kBK + 8;                      // LDS row pitch in bf16, as mtq_output_error.hip
+
+// float32 → bf16, round to nearest even; NaN stays NaN
+__device__ __forceinline__ uint16_t f32_to_bf16(float v)
+{
+    const uint32_t u = __float_as_uint(v);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x0040u);
+    return (uint16_t)((u + (0x7FFFu + ((u >> 16) & 1u))) >> 16);
+}
+
+template <bool BF16OUT>
+__global__ __launch_bounds__(kThreads) void packed_linear_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec,
+                                                                 const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+                                                                 const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N,
+                                                                 int64_t tiles_h, int64_t tiles_w, const float *__restrict__ bias,
+                                                                 void *__restrict__ yv, int64_t ldy)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[(kBM + kBN) * kLdk];
+    uint16_t *xs = lds;
+    uint16_t *ws = lds + kBM * kLdk;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t nblocks = (N + kBN - 1) / kBN;
+    const int64_t bm = blockIdx.x / nblocks, bn = blockIdx.x % nblocks;
+    const int64_t m0 = bm * kBM, n0 = bn * kBN;
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[s][r] = 0.0f;
+
+    // lane tid owns the group (row n0 + tid / 4, columns k0 + 16 (tid % 4) ..) of the W block: group 2 (n % 32) + half of tile (n / 32, k / 32)
+    const int wrow = tid >> 2, wc16 = (tid & 3) * kGroup;
+    const int64_t wtr = (n0 + wrow) >> 5;
+    const int wgi = 2 * (int)((n0 + wrow) & 31) + ((tid & 3) & 1);
+    uint4 xr[4];
+    GroupRaw wr;
+    TileAt at;                                       // of the step after the one in xr / wr: map and offsets run two steps ahead of the MFMAs
+    auto locate = [&](int64_t k0) {
+        const int64_t wtc = (k0 + wc16) >> 5;
+        at.off = 0;
+        at.f = -1;
+        if (wtr < tiles_h && wtc < tiles_w) at = tile_at(packed_bytes, map, offsets, wtr * tiles_w + wtc);
+    };
+    auto load_step = [&](int64_t k0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {   // X: 128 rows × 64 columns = 1024 pieces of 8 bf16, 4 per thread; columns past K are zeros, never read
+            const int p = tid + kThreads * i, row = p >> 3, c8 = (p & 7) * 8;
+            const int64_t gm = m0 + row, gk = k0 + c8;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (gm < M && gk < K) {
+                const uint16_t *src = x + gm * ldx + gk;
+                if (x_vec && gk + 8 <= K) {
+                    v = *reinterpret_cast<const uint4 *>(src);
+                } else {
+                    uint32_t h[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) h[j] = gk + j < K ? (uint32_t)src[j] : 0u;
+                    v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+                }
+            }
+            xr[i] = v;
+        }
+        load_group(packed, at, wgi, wr);             // the blob `at` names: located one step earlier
+        locate(k0 + kBK);
+    };
+    locate(0);
+    load_step(0);
+    for (int64_t k0 = 0; k0 < K; k0 += kBK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int p = tid + kThreads * i;
+            *reinterpret_cast<uint4 *>(xs + (p >> 3) * kLdk + (p & 7) * 8) = xr[i];
+        }
+        {
+            uint32_t y[kGroup];
+            decode_group(wr, y);
+            uint4 lo, hi;
+            pack_halves(y, lo, hi);
+            uint4 *d = reinterpret_cast<uint4 *>(ws + wrow * kLdk + wc16);
+            d[0] = lo;
+            d[1] = hi;
+        }
+        __syncthreads();
+        if (k0 + kBK < K) load_step(k0 + kBK);
+#pragma unroll
+        for (int kk = 0; kk < kBK / 16; ++kk) {
+            const int koff = kk * 16 + 8 * (lane >> 5);
+            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (wave * 32 + (lane & 31)) * kLdk + koff);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const bf16x8 b = *reinterpret_cast<const bf16x8 *>(ws + (s * 32 + (lane & 31)) * kLdk + koff);
+                acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[s], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+
+    // epilogue: lane's outputs are (m0 + 32·wave + (r&3) + 8(r>>2) + 4(lane>>5), n0 + 32s + (lane&31))
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int64_t n = n0 + 32 * s + (lane & 31);
+        if (n >= N) continue;
+        const float b = bias ? bias[n] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t m = m0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (m >= M) continue;
+            const float v = acc[s][r] + b;
+            if constexpr (BF16OUT) static_cast<uint16_t *>(yv)[m * ldy + n] = f32_to_bf16(v);
+            else static_cast<float *>(yv)[m * ldy + n] = v;
+        }
+    }
+}
+
+int tile_grid(int64_t rows, int64_t cols, int64_t *tiles_h, int64_t *tiles_w)
+{
+    if (rows <= 0 || cols <= 0) return fail(MTQ_ERR_INVALID, "rows and cols must be positive (empty tensors are handled by the caller)");
+    if (rows > (int64_t)1 << 30 || cols > (int64_t)1 << 30) return fail(MTQ_ERR_INVALID, "matrix too large");
+    *tiles_h = (rows + kTile - 1) / kTile;
+    *tiles_w = (cols + kTile - 1) / kTile;
+    if (*tiles_h * *tiles_w > (int64_t)1 << 31) return fail(MTQ_ERR_INVALID, "too many tiles for 32-bit offsets");
+    return MTQ_OK;
+}
+
+unsigned tile_blocks(int64_t tiles) { return (unsigned)std::min<int64_t>((tiles + 3) / 4, (int64_t)1 << 20); }
+
+} // namespace
+} // namespace mtq
+
+using namespace mtq;
+
+extern "C" size_t mtq_packed_tile_bytes(int fmt) { return packed_tile_bytes(fmt); }
+
+extern "C" int mtq_packed_offsets(const int8_t *map, int64_t tiles, uint32_t *offsets)
+{
+    if (!map || !offsets) return fail(MTQ_ERR_INVALID, "null argument");
+    if (tiles <= 0) return fail(MTQ_ERR_INVALID, "tiles must be positive");
+    uint64_t units = 0;
+    for (int64_t t = 0; t < tiles; ++t) {
+        const uint32_t size = packed_tile_bytes(map[t]);
+        if (size == 0u) return failf(MTQ_ERR_INVALID, "map[%lld] = %d is no packed format (codes 0..3: bf16, bfp8, bfp4, bfp2)", (long long)t, (int)map[t]);
+        offsets[t] = (uint32_t)units;
+        units += size / kUnit;
+        if (units > UINT32_MAX) return fail(MTQ_ERR_INVALID, "the stream is too long for 32-bit offsets in units of 64 bytes");
+    }
+    offsets[tiles] = (uint32_t)units;
+    return MTQ_OK;
+}
+
+extern "C" int mtq_pack_tiles(const void *x, int in_dtype, int64_t rows, int64_t cols, int64_t ld, const int8_t *map, const uint32_t *offsets,
+                              void *out, size_t out_bytes, void *stream)
+{
+    if (!x || !map || !offsets || !out) return fail(MTQ_ERR_INVALID, "null argument");
+    if (in_dtype != MTQ_DTYPE_BF16 && in_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "in_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    if (int rc = tile_grid(rows, cols, &th, &tw)) return rc;
+    if (ld < cols) return fail(MTQ_ERR_INVALID, "ld < cols");
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(MTQ_ERR_INVALID, "out must be 16-byte aligned");
+    if (out_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "out_bytes is smaller than the stream");
+    if (int rc = require_device()) return rc;
+    const int64_t esz = in_dtype == MTQ_DTYPE_F32 ? 4 : 2;
+    const int vec_ok = reinterpret_cast<uintptr_t>(x) % 16 == 0 && (ld * esz) % 16 == 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(th * tw));
+    if (in_dtype == MTQ_DTYPE_F32)
+        hipLaunchKernelGGL(pack_tiles_kernel<float>, grid, dim3(256), 0, st, static_cast<const float *>(x), rows, cols, ld, vec_ok, map, offsets,
+                           th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    else
+        hipLaunchKernelGGL(pack_tiles_kernel<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(x), rows, cols, ld, vec_ok, map, offsets,
+                           th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    return check_launch("mtq_pack_tiles");
+}
+
+extern "C" int mtq_unpack_tiles(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows, int64_t cols,
+                                void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    if (!packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    if (int rc = tile_grid(rows, cols, &th, &tw)) return rc;
+    if (ldy < cols) return fail(MTQ_ERR_INVALID, "ldy < cols");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
+    if (int rc = require_device()) return rc;
+    const int64_t esz = out_dtype == MTQ_DTYPE_F32 ? 4 : 2;
+    const int vec_ok = reinterpret_cast<uintptr_t>(y) % 16 == 0 && (ldy * esz) % 16 == 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(th * tw));
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(unpack_tiles_kernel<true>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy, vec_ok);
+    else
+        hipLaunchKernelGGL(unpack_tiles_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy, vec_ok);
+    return check_launch("mtq_unpack_tiles");
+}
+
+extern "C" int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                                 const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    if (!x || !packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    if (m <= 0) return fail(MTQ_ERR_INVALID, "m must be positive (empty operands are handled by the caller)");
+    int64_t th, tw;
+    if (int rc = tile_grid(n, k, &th, &tw)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if (m > (int64_t)1 << 40) return fail(MTQ_ERR_INVALID, "matrix too large");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
+    const int64_t blocks = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
+    if (int rc = require_device()) return rc;
+    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    const dim3 grid((unsigned)blocks);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(packed_linear_kernel<true>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th,
+                           tw, bias, y, ldy);
+    else
+        hipLaunchKernelGGL(packed_linear_kernel<false>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th,
+                           tw, bias, y, ldy);
+    return check_launch("mtq_packed_linear");
+}

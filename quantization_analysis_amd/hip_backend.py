@@ -109,6 +109,11 @@ SIGNATURES = {
     "mtq_tile_error_tables_transposed": ("i", "pilllpzppzp", True),
     "mtq_debug_k1_grid": ("i", "iliiip", True),
     "mtq_debug_work_counters": ("i", "p", True),
+    "mtq_packed_tile_bytes": ("z", "i", True),
+    "mtq_packed_offsets": ("i", "plp", True),
+    "mtq_pack_tiles": ("i", "pilllpppzp", True),
+    "mtq_unpack_tiles": ("i", "pzppllpilp", True),
+    "mtq_packed_linear": ("i", "plllpzpplppilp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -867,6 +872,135 @@ def apply_assignment(x2d, assignment, out=None):
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.float32, device=x2d.device)
     check(lib().mtq_apply_assignment(x2d.data_ptr(), code, rows, cols, ld, a.data_ptr(), out.data_ptr(), out.stride(0), _stream_ptr()))
+    return out
+
+
+# ----------------------------------------------------------------------------- packed mixed-tile weights (csrc/mtq_packed.hip)
+
+PACKED_TILE_BYTES = (2048, 1088, 576, 320)   # include/mtq.h: blob bytes by map code (bf16, bfp8, bfp4, bfp2)
+
+
+def packed_offsets(amap) -> np.ndarray:
+    """mtq_packed_offsets (a host function: no GPU): uint32[tiles + 1], the exclusive prefix sum of the blob sizes in units of 64 bytes.
+    A code outside 0..3 is refused."""
+    a = np.ascontiguousarray(np.asarray(amap, dtype=np.int8).reshape(-1))
+    if a.size == 0:
+        raise MtqError("the map has no tiles")
+    out = np.empty(a.size + 1, dtype=np.uint32)
+    check(_entry("mtq_packed_offsets")(a.ctypes.data, a.size, out.ctypes.data))
+    return out
+
+
+class PackedTables:
+    """What the packed kernels read beside the stream: the int8 map (1 B per tile) and the uint32 offsets, on the device, checked on the
+    host first — the map's codes are 0..3 and the offsets are those of the map, so `nbytes` is the stream's exact length and a launch
+    that is given at least that many bytes stays inside them.  map_dev: contiguous int8 [tiles]; offsets_dev: contiguous int32 [tiles + 1]
+    holding the uint32 words (torch has no arithmetic on uint32; nothing here needs any)."""
+
+    def __init__(self, amap, map_dev, offsets_dev):
+        torch = _torch()
+        a = np.asarray(amap)
+        if a.ndim != 2 or a.size == 0:
+            raise MtqError("the map must be a 2-D (tiles_h, tiles_w) array")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 3):
+            raise MtqError("map codes must be MIXED_TILE_FORMATS codes 0..3 (bf16, bfp8, bfp4, bfp2)")
+        self.tiles_h, self.tiles_w = (int(v) for v in a.shape)
+        tiles = self.tiles_h * self.tiles_w
+        self.nbytes = int(np.asarray(PACKED_TILE_BYTES, dtype=np.int64)[a.reshape(-1).astype(np.int64)].sum())
+        self.map_ptr = _buffer(map_dev, torch.int8, tiles, "the device map")
+        self.offsets_ptr = _buffer(offsets_dev, torch.int32, tiles + 1, "the device offsets")
+        self.map_dev, self.offsets_dev = map_dev, offsets_dev
+
+    @classmethod
+    def on_device(cls, amap, offsets=None, device=None):
+        """The tables of a host map (and its offsets, computed when not given) copied to `device`."""
+        torch = _torch()
+        require_gpu()
+        device = device or torch.device("cuda", torch.cuda.current_device())
+        a = np.ascontiguousarray(np.asarray(amap, dtype=np.int8))
+        own = packed_offsets(a)
+        if offsets is not None and not np.array_equal(np.asarray(offsets, dtype=np.uint32).reshape(-1), own):
+            raise MtqError("the offsets are not those of the map")
+        return cls(a, torch.from_numpy(a.reshape(-1).copy()).to(device), torch.from_numpy(own.view(np.int32).copy()).to(device))
+
+
+def _packed_out_code(dtype) -> int:
+    torch = _torch()
+    if dtype == torch.float32:
+        return DTYPE_F32
+    if dtype == torch.bfloat16:
+        return DTYPE_BF16
+    raise MtqError(f"the output type must be torch.float32 or torch.bfloat16, got {dtype}")
+
+
+def _packed_stream_ptr(stream):
+    return _stream_ptr() if isinstance(stream, str) else _stream(stream)
+
+
+def _packed_stream(data, tables, name="data") -> int:
+    torch = _torch()
+    ptr = _buffer(data, torch.uint8, tables.nbytes, name)
+    if data.data_ptr() % 16:
+        raise MtqError(f"{name} must be 16-byte aligned")
+    return ptr
+
+
+def pack_tiles(x2d, tables: PackedTables, out=None, stream="current"):
+    """mtq_pack_tiles on the current stream (or a torch stream; None is the null stream): a (rows, cols) bf16 / float32 device tensor with contiguous rows → the packed stream, a
+    uint8 device tensor of tables.nbytes bytes."""
+    torch = _torch()
+    code, _count, _stride, rows, cols, ld = _matrix(x2d, (2,))
+    if tiles_hw(rows, cols) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, the tensor has {'x'.join(map(str, tiles_hw(rows, cols)))}")
+    fn = _entry("mtq_pack_tiles")
+    if out is None:
+        require_gpu()
+        out = torch.empty((tables.nbytes,), dtype=torch.uint8, device=x2d.device)
+    ptr = _packed_stream(out, tables, "out")
+    check(fn(x2d.data_ptr(), code, rows, cols, ld, tables.map_ptr, tables.offsets_ptr, ptr, tables.nbytes, _packed_stream_ptr(stream)))
+    return out
+
+
+def unpack_tiles(data, tables: PackedTables, rows: int, cols: int, dtype=None, out=None, stream="current"):
+    """mtq_unpack_tiles on the current stream → a (rows, cols) device tensor: float32 (the bits K3 writes) or bfloat16 (exact)."""
+    torch = _torch()
+    dtype = dtype or torch.float32
+    code = _packed_out_code(dtype)
+    if tiles_hw(rows, cols) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {rows}x{cols} tensor has {'x'.join(map(str, tiles_hw(rows, cols)))}")
+    ptr = _packed_stream(data, tables)
+    fn = _entry("mtq_unpack_tiles")
+    if out is None:
+        require_gpu()
+        out = torch.empty((rows, cols), dtype=dtype, device=data.device)
+    elif out.dtype != dtype or out.dim() != 2 or tuple(out.shape) != (rows, cols) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {dtype} ({rows}, {cols}) device tensor with contiguous rows")
+    ldy = out.stride(0) if rows > 1 else max(out.stride(0), cols)
+    check(fn(ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, rows, cols, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_linear(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, stream="current"):
+    """mtq_packed_linear on the current stream: Y = X·Ŵᵀ + b for an (m, k) bf16 device tensor X with contiguous rows and the packed
+    (n, k) weight → (m, n) float32 or bfloat16 device tensor."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code = _packed_out_code(out_dtype)
+    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if tiles_hw(n, k) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {n}x{k} weight has {'x'.join(map(str, tiles_hw(n, k)))}")
+    ptr = _packed_stream(data, tables)
+    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
+    fn = _entry("mtq_packed_linear")
+    if out is None:
+        require_gpu()
+        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
+    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
+    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
+    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
     return out
 
 
