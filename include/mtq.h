@@ -642,6 +642,35 @@ int mtq_unpack_tiles(const void *packed, size_t packed_bytes, const int8_t *map,
 int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                       const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream);
 
+/* The same product for decode, 1 <= m <= MTQ_PACKED_SKINNY_MAX_M: a split over K.  One wave takes the run of tiles of one tile row over
+ * one K slice (a contiguous byte range of the stream), loads it straight to registers several tiles ahead, decodes each lane's group to
+ * the same bf16 words as the block kernel and feeds them to mfma_f32_32x32x16_bf16 directly (no LDS).  The K range is cut into `split`
+ * slices of whole tile columns (a split above tiles_w acts as tiles_w; split 0 is the library's choice, a pure function of (m, n, k));
+ * with an effective split above 1 each slice writes its f32 partial into `workspace` and a second kernel on `stream` sums the partials
+ * of an output in ascending slice order from slice 0, adds the bias last in f32 and rounds a bf16 y to nearest even once.  An effective
+ * split of 1 writes y directly and touches no workspace.
+ *
+ * Numerics: a fixed order, no atomics - the same inputs and the same split give the same bits.  |Y - Y64| <= (k + 2) * 2^-24 *
+ * (sum |x||w^| + |b|), the block kernel's bound, which holds for any summation order.  The skinny and the block kernel sum in different
+ * orders: their results may differ in the last bits, and so may results under different splits.
+ *
+ * Arguments are checked as for the block kernel, and m > MTQ_PACKED_SKINNY_MAX_M, a negative split, and - when the size function's
+ * answer is nonzero - a workspace that is null, not 16-byte aligned or shorter than that answer are MTQ_ERR_INVALID before a device is
+ * looked for.  The workspace's contents on entry mean nothing and nothing the call leaves there is needed by a later call; calls that
+ * share a workspace must be ordered on one stream. */
+#define MTQ_PACKED_SKINNY_MAX_M 32
+/* HOST function: bytes of workspace the skinny linear needs for (m, n, k, split); split 0 = the library's choice.  0 when the effective
+ * split is 1.  MTQ_ERR_INVALID arguments give (size_t)-1. */
+size_t mtq_packed_linear_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split);
+int mtq_packed_linear_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                             const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
+                             void *workspace, size_t workspace_bytes, void *stream);
+/* Test hook: the skinny kernel's decode (a cheaper form of the block kernel's for exponent bytes M..254, the same code elsewhere)
+ * beside the reference decode, for fmt MTQ_FMT_BFP8 / BFP4 / BFP2.  got, want: device uint32 [16][256][16][16] = [rot][E][q][i], the
+ * float32 word of code (16 q + (i + rot) % 16) mod 2^(M + 1) at element i of a group with exponent byte E: every (E, code) at every
+ * position. */
+int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

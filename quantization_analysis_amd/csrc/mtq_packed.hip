@@ -333,6 +333,264 @@ __global__ __launch_bounds__(kThreads) void packed_linear_kernel(const uint16_t 
     }
 }
 
+// ---- skinny linear (m <= 32): one wave per (K slice, tile row) unit, W straight to registers, no LDS.
+//
+// A unit is the run of tiles [c0, c1) of tile row tr: one contiguous byte range of the stream.  Lane l owns group (row l & 31, half
+// l >> 5) of every tile of the run, i.e. 16 consecutive K positions of one output feature.  mfma_f32_32x32x16_bf16 takes eight K values
+// per lane and sums over whatever K positions the two operands agree on, so the lane's 16 decoded values feed two MFMAs (values 0..7,
+// then 8..15) and the X operand of lane l is row l & 31 of X at the same sixteen positions 32 tc + 16 (l >> 5) + 0..15.  Rows of X at or
+// past m and positions at or past k are zeros that are never read.  The map and offsets of up to 64 tiles of the run are fetched with one
+// load (a lane each) and handed out with readlane; the loads of kSkinnyRing tiles (W and X) are issued before the first is decoded.
+// split > 1: the unit's 32 × m partial goes to ws[slice][m][n] as f32 and skinny_reduce_kernel sums the slices in ascending order.
+constexpr int kSkinnyRing = 8;                       // tiles in flight per wave: 9 VGPRs of W and 8 of X each
+constexpr int kSkinnyWaves = 4;                      // units per workgroup; the waves share nothing
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// decode_as for a group whose exponent byte E is in [M, 254], in a third of the instructions.  bfp_code_bits_rt's word is the float
+// ±man · 2^(E − 126 − M) (man = 2^msb · 1.frac, exponent field E − (M − 1 − msb) >= 1: normal), so it is the integer mantissa converted
+// to float (exact) times the power of two with exponent field E − M + 1 >= 1 (exact: no rounding, no underflow, and the product's
+// field is at most E <= 254), the code's sign bit moved into the factor.  man == 0 gives ±0, and fma(±0, s, +0) is +0 under round to
+// nearest: the word 0 that bfp_code_bits_rt returns for man == 0 whatever the sign bit.  Below M the exponent wraps and at 255 the word
+// is an Inf / NaN pattern that a product does not form: decode_skinny sends those groups to decode_as.
+// tests/test_packed_skinny_gpu.py compares the two for every (exponent byte, code, position) on the device.
+template <int F>
+__device__ __forceinline__ void decode_scaled(const GroupRaw &g, uint32_t (&y)[kGroup])
+{
+    constexpr uint32_t M = F == 1 ? 7u : (F == 2 ? 3u : 1u);
+    constexpr uint32_t B = M + 1u;
+    const uint32_t scale = (g.E - (M - 1u)) << 23;
+    float mf[kGroup];
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) {
+        if constexpr (F == 1) {                      // a byte of the word with the sign bits masked off: one cvt_f32_ubyte each
+            mf[i] = (float)(((g.w[i >> 2] & 0x7F7F7F7Fu) >> (8 * (i & 3))) & 0xFFu);
+        } else if constexpr (F == 2) {               // even nibbles and odd nibbles spread to bytes first
+            const uint32_t word = g.w[i >> 3], src = (i & 1) ? ((word >> 4) & 0x07070707u) : (word & 0x07070707u);
+            mf[i] = (float)((src >> (8 * ((i & 7) >> 1))) & 0xFFu);
+        } else {
+            mf[i] = (float)((g.w[0] >> (2 * i)) & 1u);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kGroup; i += 2) {
+        f32x2 a, s;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t pos = (((i + j) * B) & 31u) + M;              // the sign bit of code i + j in its word
+            const uint32_t t = g.w[((i + j) * B) >> 5] << (31u - pos);
+            a[j] = mf[i + j];
+            s[j] = __uint_as_float((t & 0x80000000u) | scale);
+        }
+        const f32x2 zero = {0.0f, 0.0f};
+        const f32x2 r = __builtin_elementwise_fma(a, s, zero);
+        y[i] = __float_as_uint(r[0]);
+        y[i + 1] = __float_as_uint(r[1]);
+    }
+}
+
+template <int F>
+__device__ __forceinline__ void decode_either(const GroupRaw &g, uint32_t (&y)[kGroup])
+{
+    constexpr uint32_t M = F == 1 ? 7u : (F == 2 ? 3u : 1u);
+    if (g.E >= M && g.E <= 254u) decode_scaled<F>(g, y);
+    else decode_as<F>(g, y);
+}
+
+// decode_group's words exactly
+__device__ __forceinline__ void decode_skinny(const GroupRaw &g, uint32_t (&y)[kGroup])
+{
+    if (g.f == 1) decode_either<1>(g, y);
+    else if (g.f == 2) decode_either<2>(g, y);
+    else if (g.f == 3) decode_either<3>(g, y);
+    else decode_group(g, y);
+}
+
+// The probe of decode_skinny: thread (rot, E, q) decodes the group with exponent byte E whose element i holds code
+// (16 q + (i + rot) % 16) mod 2^B, and writes its words beside bfp_code_bits_rt's: 16 × 256 × 16 groups cover every (E, code) at every
+// position of the group.  got, want: uint32 [16][256][16][16].
+constexpr int kProbeGroups = 16 * 256 * 16;
+
+__global__ __launch_bounds__(256) void packed_decode_probe_kernel(int f, uint32_t *__restrict__ got, uint32_t *__restrict__ want)
+{
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= kProbeGroups) return;
+    const uint32_t rot = idx >> 12, E = (idx >> 4) & 255u, q = idx & 15u;
+    const uint32_t M = f == 1 ? 7u : (f == 2 ? 3u : 1u), B = M + 1u;
+    GroupRaw g;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) g.w[i] = 0u;
+    g.E = E;
+    g.f = f;
+    uint32_t code[kGroup];
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) {
+        code[i] = (16u * q + ((i + rot) & 15u)) & ((1u << B) - 1u);
+        if (f == 1) g.w[i >> 2] |= code[i] << (8 * (i & 3));
+        else if (f == 2) g.w[i >> 3] |= code[i] << (4 * (i & 7));
+        else g.w[0] |= code[i] << (2 * i);
+    }
+    uint32_t y[kGroup];
+    decode_skinny(g, y);
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) {
+        got[(int64_t)idx * kGroup + i] = y[i];
+        want[(int64_t)idx * kGroup + i] = bfp_code_bits_rt(code[i], E, M);
+    }
+}
+
+__device__ __forceinline__ void load_x16(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec, int row, int64_t k0,
+                                         uint4 &lo, uint4 &hi)
+{
+    lo = make_uint4(0u, 0u, 0u, 0u);
+    hi = lo;
+    if (row >= M || k0 >= K) return;
+    const uint16_t *src = x + (int64_t)row * ldx + k0;
+    if (x_vec && k0 + kGroup <= K) {
+        lo = reinterpret_cast<const uint4 *>(src)[0];
+        hi = reinterpret_cast<const uint4 *>(src)[1];
+    } else {
+        uint32_t h[kGroup];
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) h[j] = k0 + j < K ? (uint32_t)src[j] : 0u;
+        lo = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+        hi = make_uint4(h[8] | (h[9] << 16), h[10] | (h[11] << 16), h[12] | (h[13] << 16), h[14] | (h[15] << 16));
+    }
+}
+
+__device__ __forceinline__ bf16x8 as_bf16x8(const uint4 &v) { return __builtin_bit_cast(bf16x8, v); }
+
+template <bool BF16OUT>
+__device__ __forceinline__ void store_y(void *__restrict__ yv, int64_t at, float v)
+{
+    if constexpr (BF16OUT) static_cast<uint16_t *>(yv)[at] = f32_to_bf16(v);
+    else static_cast<float *>(yv)[at] = v;
+}
+
+template <bool BF16OUT>
+__global__ __launch_bounds__(64 * kSkinnyWaves) void packed_linear_skinny_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx,
+                                                                                  int x_vec, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+                                                                                  const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets,
+                                                                                  int64_t N, int64_t tiles_h, int64_t tiles_w, int split,
+                                                                                  const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy,
+                                                                                  float *__restrict__ ws)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= tiles_h * split) return;             // wave-uniform; the kernel has no barrier
+    const int64_t s = unit / tiles_h, tr = unit % tiles_h;   // the waves of a workgroup share a slice of X
+    const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
+    const int row = lane & 31, half = lane >> 5, gi = 2 * row + half;
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+
+    for (int64_t cb = c0; cb < c1; cb += 64) {
+        const int cnt = (int)std::min<int64_t>(64, c1 - cb);
+        int mf = -1, mo = 0;                         // lane i: map code and offset of tile cb + i
+        if (lane < cnt) {
+            const int64_t t = tr * tiles_w + cb + lane;
+            mf = map[t];
+            mo = (int)offsets[t];
+        }
+        for (int b = 0; b < cnt; b += kSkinnyRing) {
+            GroupRaw g[kSkinnyRing];
+            uint4 xl[kSkinnyRing], xh[kSkinnyRing];
+#pragma unroll
+            for (int j = 0; j < kSkinnyRing; ++j) {
+                const int i = b + j;                 // uniform
+                TileAt a;
+                a.off = 0;
+                a.f = -1;
+                xl[j] = make_uint4(0u, 0u, 0u, 0u);
+                xh[j] = xl[j];
+                if (i < cnt) {
+                    const int f = __builtin_amdgcn_readlane(mf, i);
+                    a.off = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(mo, i) * kUnit;
+                    const uint32_t size = packed_tile_bytes(f);
+                    a.f = (size == 0u || a.off + size > packed_bytes) ? -1 : f;
+                    load_x16(x, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
+                }
+                load_group(packed, a, gi, g[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < kSkinnyRing; ++j) {
+                if (b + j < cnt) {
+                    uint32_t y[kGroup];
+                    decode_skinny(g[j], y);
+                    uint4 lo, hi;
+                    pack_halves(y, lo, hi);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(lo), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(hi), acc, 0, 0, 0);
+                }
+            }
+        }
+    }
+
+    // lane's outputs are (m = (r&3) + 8(r>>2) + 4·half, n = 32·tr + row)
+    const int64_t n = tr * kTile + row;
+    if (n >= N) return;
+    if (split == 1) {
+        const float bv = bias ? bias[n] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t m = (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[r] + bv);
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t m = (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (m < M) ws[(s * M + m) * N + n] = acc[r];
+        }
+    }
+}
+
+// Y[m][n] = ((p0 + p1) + ... + p_{split-1}) + b: ascending slices from slice 0, the bias last, one rounding for a bf16 Y.
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void skinny_reduce_kernel(const float *__restrict__ ws, int64_t MN, int64_t N, int split,
+                                                            const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= MN) return;
+    const int64_t m = idx / N, n = idx % N;
+    float v = ws[idx];
+    for (int s = 1; s < split; ++s) v += ws[(int64_t)s * MN + idx];
+    v += bias ? bias[n] : 0.0f;
+    store_y<BF16OUT>(yv, m * ldy + n, v);
+}
+
+// The library's split for (m, n, k): a pure function of the shape.  Units (tile rows × slices) fill at most kSkinnyUnits waves, what the
+// chip holds at once (256 CUs × 8: one unit over that and a second round of waves starts), and a slice keeps at least kSkinnyMinRun tiles
+// (DESIGN.md §A.6h has the measurement behind both).
+constexpr int64_t kSkinnyUnits = 2048, kSkinnyMinRun = 4;
+
+int tile_grid(int64_t rows, int64_t cols, int64_t *tiles_h, int64_t *tiles_w);
+
+int skinny_split(int64_t m, int64_t tiles_h, int64_t tiles_w)
+{
+    (void)m;
+    const int64_t by_units = kSkinnyUnits / tiles_h, by_run = tiles_w / kSkinnyMinRun;
+    return (int)std::max<int64_t>(1, std::min(by_units, by_run));
+}
+
+// MTQ_OK and the effective split, or the refusal every skinny entry shares
+int skinny_shape(int64_t m, int64_t n, int64_t k, int split, int64_t *tiles_h, int64_t *tiles_w, int *split_eff)
+{
+    if (m <= 0) return fail(MTQ_ERR_INVALID, "m must be positive (empty operands are handled by the caller)");
+    if (m > MTQ_PACKED_SKINNY_MAX_M) return fail(MTQ_ERR_INVALID, "m > 32: the skinny kernel takes at most MTQ_PACKED_SKINNY_MAX_M rows");
+    if (split < 0) return fail(MTQ_ERR_INVALID, "split must not be negative (0: the library's choice)");
+    if (int rc = tile_grid(n, k, tiles_h, tiles_w)) return rc;
+    *split_eff = (int)std::min<int64_t>(split == 0 ? skinny_split(m, *tiles_h, *tiles_w) : split, *tiles_w);
+    return MTQ_OK;
+}
+
+size_t skinny_workspace(int64_t m, int64_t n, int split_eff)
+{
+    return split_eff <= 1 ? 0 : (((size_t)split_eff * (size_t)m * (size_t)n * sizeof(float) + 15) & ~(size_t)15);
+}
+
 int tile_grid(int64_t rows, int64_t cols, int64_t *tiles_h, int64_t *tiles_w)
 {
     if (rows <= 0 || cols <= 0) return fail(MTQ_ERR_INVALID, "rows and cols must be positive (empty tensors are handled by the caller)");
@@ -443,4 +701,67 @@ extern "C" int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ld
         hipLaunchKernelGGL(packed_linear_kernel<false>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th,
                            tw, bias, y, ldy);
     return check_launch("mtq_packed_linear");
+}
+
+extern "C" size_t mtq_packed_linear_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
+{
+    int64_t th, tw;
+    int eff;
+    if (skinny_shape(m, n, k, split, &th, &tw, &eff)) return (size_t)-1;
+    return skinny_workspace(m, n, eff);
+}
+
+extern "C" int mtq_packed_linear_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                                        const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
+                                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!x || !packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    int eff;
+    if (int rc = skinny_shape(m, n, k, split, &th, &tw, &eff)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
+    const size_t need = skinny_workspace(m, n, eff);
+    if (need != 0) {
+        if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and this split needs one");
+        if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
+        if (workspace_bytes < need)
+            return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this split needs", workspace_bytes, need);
+    }
+    const int64_t blocks = (th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    float *ws = static_cast<float *>(workspace);
+    const dim3 grid((unsigned)blocks), block(64 * kSkinnyWaves);
+    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(packed_linear_skinny_kernel<true>, grid, block, 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th, tw,
+                           eff, bias, y, ldy, ws);
+    else
+        hipLaunchKernelGGL(packed_linear_skinny_kernel<false>, grid, block, 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th, tw,
+                           eff, bias, y, ldy, ws);
+    if (eff > 1) {
+        if (int rc = check_launch("mtq_packed_linear_skinny")) return rc;
+        const dim3 rgrid((unsigned)((m * n + 255) / 256));
+        if (out_dtype == MTQ_DTYPE_BF16)
+            hipLaunchKernelGGL(skinny_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
+        else
+            hipLaunchKernelGGL(skinny_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
+    }
+    return check_launch("mtq_packed_linear_skinny");
+}
+
+extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)
+{
+    if (!got || !want) return fail(MTQ_ERR_INVALID, "null argument");
+    if (fmt < MTQ_FMT_BFP8 || fmt > MTQ_FMT_BFP2) return fail(MTQ_ERR_INVALID, "fmt must be MTQ_FMT_BFP8, MTQ_FMT_BFP4 or MTQ_FMT_BFP2");
+    if (int rc = require_device()) return rc;
+    hipLaunchKernelGGL(packed_decode_probe_kernel, dim3(kProbeGroups / 256), dim3(256), 0, static_cast<hipStream_t>(stream), fmt, got, want);
+    return check_launch("mtq_debug_packed_decode");
 }

@@ -114,6 +114,9 @@ SIGNATURES = {
     "mtq_pack_tiles": ("i", "pilllpppzp", True),
     "mtq_unpack_tiles": ("i", "pzppllpilp", True),
     "mtq_packed_linear": ("i", "plllpzpplppilp", True),
+    "mtq_packed_linear_skinny_workspace_bytes": ("z", "llli", True),
+    "mtq_packed_linear_skinny": ("i", "plllpzpplppilipzp", True),
+    "mtq_debug_packed_decode": ("i", "ippp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1002,6 +1005,69 @@ def packed_linear(x, data, tables: PackedTables, n: int, bias=None, out_dtype=No
     ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
     check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
     return out
+
+
+PACKED_SKINNY_MAX_M = 32   # include/mtq.h MTQ_PACKED_SKINNY_MAX_M
+
+
+def packed_linear_skinny_workspace_bytes(m: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_linear_skinny_workspace_bytes (a host function: no GPU): the bytes of workspace the skinny kernel needs for
+    (m, n, k, split); split 0 is the library's choice; 0 when the effective split is 1."""
+    size = int(_entry("mtq_packed_linear_skinny_workspace_bytes")(int(m), int(n), int(k), int(split)))
+    if size == ctypes.c_size_t(-1).value:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return size
+
+
+def packed_linear_skinny(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, split: int = 0, workspace=None,
+                         stream="current"):
+    """mtq_packed_linear_skinny on the current stream: packed_linear for m <= 32 with a split over K (split 0: the library's choice).
+    workspace: a uint8 device tensor of at least packed_linear_skinny_workspace_bytes(m, n, k, split) bytes, 16-byte aligned;
+    allocated here when none is given.  The same inputs and the same split give the same bits."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code = _packed_out_code(out_dtype)
+    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if m > PACKED_SKINNY_MAX_M:
+        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
+    if tiles_hw(n, k) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {n}x{k} weight has {'x'.join(map(str, tiles_hw(n, k)))}")
+    ptr = _packed_stream(data, tables)
+    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
+    need = packed_linear_skinny_workspace_bytes(m, n, k, split)
+    fn = _entry("mtq_packed_linear_skinny")
+    if out is None:
+        require_gpu()
+        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
+    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
+    ws_ptr, ws_bytes = None, 0
+    if need:
+        if workspace is None:
+            require_gpu()
+            workspace = torch.empty((need,), dtype=torch.uint8, device=x.device)
+        ws_ptr, ws_bytes = _buffer(workspace, torch.uint8, need, "workspace"), int(workspace.numel())
+        if workspace.data_ptr() % 16:
+            raise MtqError("workspace must be 16-byte aligned")
+    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
+    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, int(split),
+             ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
+    return out
+
+
+def debug_packed_decode(fmt: str):
+    """mtq_debug_packed_decode: (got, want) int32 device tensors [16][256][16][16] = [rot][E][q][i] holding the float32 words the skinny
+    kernel's decode and the reference decode give code (16 q + (i + rot) % 16) mod 2^bits at element i under exponent byte E."""
+    torch = _torch()
+    require_gpu()
+    if fmt not in ("bfp8", "bfp4", "bfp2"):
+        raise MtqError(f"fmt must be bfp8, bfp4 or bfp2, got {fmt!r}")
+    got = torch.empty((16, 256, 16, 16), dtype=torch.int32, device="cuda")
+    want = torch.empty_like(got)
+    check(_entry("mtq_debug_packed_decode")(FMT_CODE[fmt], got.data_ptr(), want.data_ptr(), _stream_ptr()))
+    return got, want
 
 
 def dequant_fp8_block(w, scale_inv):

@@ -27,6 +27,11 @@ TILE = 32
 GROUP = 16
 _MANT = {1: 7, 2: 3, 3: 1}
 BACKENDS = ("hip", "emulation")
+KERNELS = ("block", "skinny", "auto")
+SKINNY_MAX_M = 32           # include/mtq.h MTQ_PACKED_SKINNY_MAX_M
+# kernel="auto" takes the skinny kernel up to this m and the block kernel above it: the largest measured m at which the skinny
+# kernel's median is below the block kernel's minimum at every shape and map (profiles/packed_linear_skinny.txt).
+AUTO_SKINNY_MAX_M = 32
 
 
 def _is_torch(x) -> bool:
@@ -284,11 +289,19 @@ def unpack(pt: PackedTensor, backend: str = "emulation", dtype: str = "float32")
     return half.reshape(()) if kind == "scalar" else (half.reshape(-1)[:v] if kind == "vector" else half.reshape(tuple(v)))
 
 
-def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
+def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block", split: int = 0,
+           workspace=None):
     """Y = X·Ŵᵀ + b with the packed (n, k) weight `pt` (nn.Linear convention).  hip (the default when the stream is on the device):
     X an (m, k) bf16 device tensor, bias float32, through mtq_packed_linear.  emulation: the float64 product of the unpacked weight,
-    rounded once to float32 (or from there to bf16) — the reference the GPU tests hold the kernel to, not a fast path."""
+    rounded once to float32 (or from there to bf16) — the reference the GPU tests hold the kernel to, not a fast path.
+
+    kernel: "block" (the default; any m), "skinny" (the split-K kernel for decode, m <= 32; `split` slices of K, 0 = the library's
+    choice, and an optional uint8 device `workspace` of hip_backend.packed_linear_skinny_workspace_bytes bytes) or "auto" (skinny for
+    m <= AUTO_SKINNY_MAX_M, block above).  The two kernels sum in different orders: each is bit-stable, they may differ in the last
+    bits.  The emulation computes the same float64 product under all three names."""
     _check_layout(pt.layout)
+    if kernel not in KERNELS:
+        raise MtqError(f"kernel must be one of {KERNELS}, got {kernel!r}")
     if len(pt.shape) != 2:
         raise MtqError(f"linear needs a 2-D (n, k) weight, the packed tensor is {pt.shape}")
     backend = backend or ("hip" if pt.on_device else "emulation")
@@ -302,7 +315,13 @@ def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
 
         if x.dim() != 2 or x.shape[1] != k:
             raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
-        return hb.packed_linear(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=torch.float32 if out_dtype == "float32" else torch.bfloat16)
+        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        m = int(x.shape[0])
+        if kernel == "skinny" and m > SKINNY_MAX_M:
+            raise MtqError(f'kernel="skinny" takes m <= {SKINNY_MAX_M}, got m = {m}')
+        if kernel == "skinny" or (kernel == "auto" and m <= AUTO_SKINNY_MAX_M):
+            return hb.packed_linear_skinny(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype, split=split, workspace=workspace)
+        return hb.packed_linear(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
     if backend != "emulation":
         raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
     import torch
@@ -317,6 +336,76 @@ def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     with np.errstate(over="ignore"):
         y32 = y.astype(np.float32)
     return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
+
+
+def _packed_linear_class():
+    import torch
+
+    class PackedLinear(torch.nn.Module):
+        """A linear layer over a packed (n, k) weight.  INFERENCE ONLY: the kernels have no backward, no gradient reaches x, the weight
+        or the bias.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through linear() with
+        `kernel` ("auto": the skinny split-K kernel for decode-sized m, the block kernel above) and returns (..., n) in out_dtype.
+        hip: the tables, the bias and a workspace sized for every m <= 32 stay on the device across calls, so a decode step
+        allocates only its output.  emulation: CPU tensors, the float64 product (for use without a GPU)."""
+
+        def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", kernel: str = "auto", backend: Optional[str] = None):
+            super().__init__()
+            _check_layout(pt.layout)
+            if len(pt.shape) != 2:
+                raise MtqError(f"PackedLinear needs a 2-D (n, k) weight, the packed tensor is {pt.shape}")
+            if kernel not in KERNELS:
+                raise MtqError(f"kernel must be one of {KERNELS}, got {kernel!r}")
+            if out_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            self.backend = backend or ("hip" if pt.on_device else "emulation")
+            if self.backend not in BACKENDS:
+                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            self.packed, self.kernel, self.out_dtype = pt, kernel, out_dtype
+            self.out_features, self.in_features = pt.rows, pt.cols
+            self._workspace = None
+            if bias is not None and not _is_torch(bias):
+                bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
+            if self.backend == "hip":
+                from . import hip_backend as hb
+
+                data = _device_data(pt)
+                pt.tables()
+                if bias is not None:
+                    bias = bias.detach().to(device=data.device, dtype=torch.float32).contiguous()
+                if kernel != "block":
+                    need = max(hb.packed_linear_skinny_workspace_bytes(m, pt.rows, pt.cols) for m in range(1, SKINNY_MAX_M + 1))
+                    self._workspace = torch.empty((need,), dtype=torch.uint8, device=data.device) if need else None
+            self.register_buffer("bias", None if bias is None else bias.detach(), persistent=False)
+
+        def extra_repr(self) -> str:
+            return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, kernel={self.kernel!r}, " \
+                   f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}"
+
+        @torch.no_grad()
+        def forward(self, x):
+            if x.shape[-1] != self.in_features:
+                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
+            lead = tuple(x.shape[:-1])
+            x2 = x.reshape(-1, self.in_features)
+            dtype = torch.float32 if self.out_dtype == "float32" else torch.bfloat16
+            if x2.shape[0] == 0:
+                return torch.zeros(lead + (self.out_features,), dtype=dtype, device=x.device)
+            y = linear(x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel,
+                       workspace=self._workspace)
+            if not _is_torch(y):
+                y = torch.from_numpy(y)
+            return y.reshape(lead + (self.out_features,))
+
+    return PackedLinear
+
+
+def __getattr__(name):
+    """PackedLinear is a torch.nn.Module: the class is made on first use, so that importing this module does not import torch."""
+    if name == "PackedLinear":
+        cls = _packed_linear_class()
+        globals()["PackedLinear"] = cls
+        return cls
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def save(path, pt: PackedTensor) -> None:

@@ -7,8 +7,12 @@
                   The weight stream is what bounds small m, so both sides rotate over enough copies of the weight (--cold-mb in all)
                   that a call does not find the previous call's weight in the 256 MiB Infinity Cache.  GB/s = the packed stream's
                   bytes over the packed kernel's time; for matmul, the bf16 weight's bytes over its time.
+  skinny        : for m <= 32 the split-K kernel (mtq_packed_linear_skinny, the C entry with a preallocated workspace) is a third side
+                  of the same alternation, once per value of --splits (0 = the library's choice); `skinny/block-min` is the skinny
+                  median over the block kernel's MINIMUM of the same run, the gate of DESIGN.md §A.6h.
 
   python tools/packed_linear_bench.py [--rounds 5] [--window-ms 30] [--out profiles/packed_linear.txt] [--json out.json]
+  python tools/packed_linear_bench.py --linear-only --ms 1,4,16,32 --out profiles/packed_linear_skinny.txt
 """
 from __future__ import annotations
 
@@ -63,6 +67,8 @@ def main() -> int:
     p.add_argument("--hbm-tbs", type=float, default=8.0)
     p.add_argument("--shapes", default="4096x4096,14336x4096")
     p.add_argument("--ms", default="1,16,256,4096")
+    p.add_argument("--splits", default="0", help="skinny side: the split values to time, comma separated (0: the library's choice)")
+    p.add_argument("--linear-only", action="store_true", help="skip the pack / unpack timings")
     p.add_argument("--out", default=None)
     p.add_argument("--json", default=None)
     args = p.parse_args()
@@ -89,7 +95,7 @@ def main() -> int:
             wq = hb.unpack_tiles(data, tables, n, k, dtype=torch.bfloat16)
             y32 = torch.empty((n, k), dtype=torch.float32, device="cuda")
             # pack / unpack: bytes moved over time
-            for what, fn, moved in (("pack", lambda i: hb.pack_tiles(w, tables, out=data), 2 * n * k + tables.nbytes),
+            for what, fn, moved in () if args.linear_only else (("pack", lambda i: hb.pack_tiles(w, tables, out=data), 2 * n * k + tables.nbytes),
                                     ("unpack_bf16", lambda i: hb.unpack_tiles(data, tables, n, k, dtype=torch.bfloat16, out=wq), tables.nbytes + 2 * n * k),
                                     ("unpack_f32", lambda i: hb.unpack_tiles(data, tables, n, k, out=y32), tables.nbytes + 4 * n * k)):
                 iters = calibrate(fn, args.window_ms)
@@ -121,10 +127,30 @@ def main() -> int:
                 def f_matmul(i):
                     torch.matmul(x, wqs[i % copies_w].t(), out=ym)
 
+                # the skinny kernel, one side per split: the C entry with a workspace allocated once
+                skinny = []
+                if m <= hb.PACKED_SKINNY_MAX_M:
+                    ys = torch.empty((m, n), dtype=torch.bfloat16, device="cuda")
+                    sentry = hb._entry("mtq_packed_linear_skinny")
+                    for split in (int(v) for v in args.splits.split(",")):
+                        need = hb.packed_linear_skinny_workspace_bytes(m, n, k, split)
+                        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device="cuda")
+                        hb.packed_linear_skinny(x, data, tables, n, out_dtype=torch.bfloat16, out=ys, split=split, workspace=ws)   # the checks, once
+                        scalls = [(x.data_ptr(), m, k, x.stride(0), d.data_ptr(), tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, None,
+                                   ys.data_ptr(), hb.DTYPE_BF16, n, split, ws.data_ptr(), need, stream) for d in datas]
+
+                        def f_skinny(i, scalls=scalls):
+                            hb.check(sentry(*scalls[i % copies_p]))
+
+                        skinny.append({"split": split, "workspace_bytes": need, "fn": f_skinny, "ws": ws, "iters": calibrate(f_skinny, args.window_ms),
+                                       "ts": []})
+
                 ip, im = calibrate(f_packed, args.window_ms), calibrate(f_matmul, args.window_ms)
                 tp, tm = [], []
                 for _ in range(args.rounds):
                     tp.append(window_ms(f_packed, ip))
+                    for side in skinny:
+                        side["ts"].append(window_ms(side["fn"], side["iters"]))
                     tm.append(window_ms(f_matmul, im))
                 f_packed(0)
                 f_matmul(0)
@@ -137,6 +163,18 @@ def main() -> int:
                 say(f"linear       {n}x{k} m={m:5d} map={name:6s} packed {mp * 1e3:9.1f} us (min {min(tp) * 1e3:9.1f}, {tables.nbytes / mp / 1e6:7.1f} GB/s of stream) "
                     f"matmul {mm * 1e3:9.1f} us (min {min(tm) * 1e3:9.1f}, {2 * n * k / mm / 1e6:7.1f} GB/s of bf16 W)  packed/matmul {mp / mm:6.2f}  "
                     f"max rel diff {err:.2e}")
+                for side in skinny:
+                    side["fn"](0)
+                    serr = float((ys.float() - ym.float()).abs().max() / ym.float().abs().max().clamp_min(1e-30))
+                    ms_, mn_ = statistics.median(side["ts"]), min(side["ts"])
+                    rows.append({"what": "packed_linear_skinny", "n": n, "k": k, "m": m, "map": name, "counts": counts, "split": side["split"],
+                                 "workspace_bytes": side["workspace_bytes"], "skinny_ms_median": ms_, "skinny_ms_min": mn_,
+                                 "block_ms_median": mp, "block_ms_min": min(tp), "matmul_ms_median": mm, "skinny_over_block_min": ms_ / min(tp),
+                                 "skinny_over_matmul": ms_ / mm, "skinny_stream_gbs": tables.nbytes / ms_ / 1e6, "max_rel_diff": serr})
+                    say(f"skinny       {n}x{k} m={m:5d} map={name:6s} split={side['split']:3d} {ms_ * 1e3:9.1f} us (min {mn_ * 1e3:9.1f}, "
+                        f"{tables.nbytes / ms_ / 1e6:7.1f} GB/s of stream)  skinny/block-min {ms_ / min(tp):6.3f}  skinny/matmul {ms_ / mm:6.2f}  "
+                        f"max rel diff {serr:.2e}")
+                del skinny
             del datas, wqs, data, wq
         del w
     if args.out:
