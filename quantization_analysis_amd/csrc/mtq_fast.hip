@@ -21,8 +21,8 @@
 // (global_load_lds_dwordx4, 1 KiB each, 256-B contiguous row segments) fill a wave-private LDS image;
 // 16 lanes serve one tile, lane j takes rows 2j, 2j+1 (4 groups, 2 × ds_read_b128 each, XOR-swizzled so the
 // reads are bank-conflict free).  A lane sums its 4 groups sequentially; the per-lane float64 partials meet in
-// an LDS scratch (14 sums per tile, balanced tree over the 16 lanes); the three maxima go through lane
-// permutes.  The 4 finished records of a unit leave as two coalesced wave-stores.
+// an LDS scratch (14 sums per tile, balanced tree over the 16 lanes); the three maxima go over a tile's
+// 16 lanes with DPP row operations.  The 4 finished records of a unit leave as two coalesced wave-stores.
 // No MFMA, no block barrier: waves never share data.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -271,15 +271,58 @@ __device__ __forceinline__ void fast_group(const uint32_t w[8], GroupOut &G, Rel
 //     max|x−y|: a maximum is exact.
 // Σx and Σx² need up to 26 / 48 bits: they are float64 chains over the elements (v_cvt_f64_f32, v_add_f64, v_fma_f64 — x² is exact in
 // float64, so the fused form equals the literal add of the float32 product), exact for the main class (< 2^53·u²).
-// A lane whose group holds a non-zero TAIL element (d ≥ 15: |x| < P·2^−14; about 6e-5 of Gaussian elements) redoes Σx, Σx² and
-// Σ|x−y| of that group in the contract's main + tail form in a divergent loop (the maxima and the y-side sums are unaffected: y = 0
-// there).  Groups with E outside [80,180] or a NaN mark the tile for the literal fix-up, all-zero groups contribute ±0, as above.
+// A group that holds a TAIL element (d ≥ 15: |x| < P·2^−14; about 6e-5 of Gaussian elements) has Σx, Σx² and Σ|x−y| formed again in
+// the contract's main + tail form, by the whole wave for one such group after the other (the maxima and the y-side sums are unaffected:
+// y = 0 there).  Groups with E outside [80,180] or a NaN mark the tile for the literal fix-up, all-zero groups contribute ±0, as above.
 // ---------------------------------------------------------------------------------------------
 typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float u2f(uint32_t v) { return __uint_as_float(v); }
 __device__ __forceinline__ uint32_t f2u(float v) { return __float_as_uint(v); }
 __device__ __forceinline__ void max3_abs(float &m, float a, float b) { asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(m) : "v"(a), "v"(b)); }
 __device__ __forceinline__ void min3_abs(float &m, float a, float b) { asm("v_min3_f32 %0, %0, |%1|, |%2|" : "+v"(m) : "v"(a), "v"(b)); }
+
+// DPP row operations (a row = 16 lanes = the lanes of one tile): each step combines a lane's value with one partner's inside the row;
+// after quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror and row_mirror every lane of the row holds the combination of all 16.
+constexpr int kDppQuad1 = 0xB1, kDppQuad2 = 0x4E, kDppHalfMirror = 0x141, kDppMirror = 0x140;
+template <int CTRL> __device__ __forceinline__ uint32_t dpp_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true); }   // every lane has a partner: `old` is never used
+template <int CTRL> __device__ __forceinline__ float dpp_f32(float v) { return u2f(dpp_u32<CTRL>(f2u(v))); }
+template <int CTRL> __device__ __forceinline__ double dpp_f64(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const uint32_t lo = dpp_u32<CTRL>((uint32_t)b), hi = dpp_u32<CTRL>((uint32_t)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// maximum of a non-negative float32 over the row: such floats order like their bit patterns, and the unsigned maximum folds into the
+// DPP instruction (v_max_f32 through the compiler would canonicalise its operands first).  A maximum is idempotent and commutative:
+// every lane ends with the same value whatever the partner order.
+__device__ __forceinline__ float row_max_nonneg(float v)
+{
+    uint32_t m = f2u(v);
+    m = max(m, dpp_u32<kDppQuad1>(m)); m = max(m, dpp_u32<kDppQuad2>(m));
+    m = max(m, dpp_u32<kDppHalfMirror>(m)); m = max(m, dpp_u32<kDppMirror>(m));
+    return u2f(m);
+}
+// Row sums of the tail-class redo.  Every addend is an integer multiple of one unit and every partial sum stays representable, so the
+// result is exact — equal to the float64 sum in index order — whatever the order.  kF32: leading steps done in float32 (exact while the
+// partial sums stay at or below 2^24 units); the remaining steps in float64.
+template <int kF32> __device__ __forceinline__ double row_sum_exact(float v)
+{
+    if constexpr (kF32 >= 1) v += dpp_f32<kDppQuad1>(v);
+    if constexpr (kF32 >= 2) v += dpp_f32<kDppQuad2>(v);
+    if constexpr (kF32 >= 3) v += dpp_f32<kDppHalfMirror>(v);
+    if constexpr (kF32 >= 4) v += dpp_f32<kDppMirror>(v);
+    double d = (double)v;
+    if constexpr (kF32 < 1) d += dpp_f64<kDppQuad1>(d);
+    if constexpr (kF32 < 2) d += dpp_f64<kDppQuad2>(d);
+    if constexpr (kF32 < 3) d += dpp_f64<kDppHalfMirror>(d);
+    if constexpr (kF32 < 4) d += dpp_f64<kDppMirror>(d);
+    return d;
+}
+__device__ __forceinline__ double row_sum_exact(double d)
+{
+    d += dpp_f64<kDppQuad1>(d); d += dpp_f64<kDppQuad2>(d); d += dpp_f64<kDppHalfMirror>(d); d += dpp_f64<kDppMirror>(d);
+    return d;
+}
 
 template <int M> struct FmtF {   // per-group constants of one BFP format as multiples of P = 2^(E−127)
     static constexpr float kC = M == 7 ? 196608.0f : (M == 3 ? 3145728.0f : 12582912.0f);   // 1.5·2^(24−M)
@@ -300,21 +343,26 @@ __device__ __forceinline__ void f32_step(f2 x, float C, float hi, int i, FAcc &A
     f2 y;
     y.x = __builtin_amdgcn_fmed3f(r.x, -hi, hi);
     y.y = __builtin_amdgcn_fmed3f(r.y, -hi, hi);
+    // Pair 0 SEEDS the accumulators instead of being added to a zero (no `v_pk_add_f32 …, 0`, no zero to materialise).  The only thing
+    // that changes is the sign of a zero: 0 + (−0) = +0, a seed keeps −0 (Σy, Σδ, Σδ·y, Σx·y of a group whose terms are all −0; y·y,
+    // |δ| are never −0).  A −0 sum cannot reach a record: f32_terms adds an accumulator's halves and joins sums (−0 + s = s for every
+    // s but −0), and every group term then enters the unit accumulator as 0.0 + term = +0 for term = ±0 (the kernel's group loop).
     if constexpr (kSum) {
-        A.sy += y;
-        A.sy2 = __builtin_elementwise_fma(y, y, A.sy2);
+        if (i == 0) { A.sy = y; A.sy2 = y * y; }
+        else { A.sy += y; A.sy2 = __builtin_elementwise_fma(y, y, A.sy2); }
     }
     if constexpr (kErr || (kSum && M == 7)) {
         const f2 d = x - y;
-        if constexpr (kSd) A.sd += d;
-        if constexpr (kSum && M == 7) A.sxy = __builtin_elementwise_fma(d, y, A.sxy);
+        if constexpr (kSd) A.sd = i == 0 ? d : A.sd + d;
+        if constexpr (kSum && M == 7) A.sxy = i == 0 ? d * y : __builtin_elementwise_fma(d, y, A.sxy);
         if constexpr (kErr) {
-            if (M == 1 && i >= 4) { A.sad2 += __builtin_fabsf(d.x); A.sad2 += __builtin_fabsf(d.y); }
+            if (M == 1 && i >= 4) { if (i == 4) A.sad2 = __builtin_fabsf(d.x) + __builtin_fabsf(d.y); else { A.sad2 += __builtin_fabsf(d.x); A.sad2 += __builtin_fabsf(d.y); } }
+            else if (i == 0) A.sad = __builtin_fabsf(d.x) + __builtin_fabsf(d.y);
             else { A.sad += __builtin_fabsf(d.x); A.sad += __builtin_fabsf(d.y); }
             max3_abs(A.mx, d.x, d.y);
         }
     }
-    if constexpr (kSum && M != 7) A.sxy = __builtin_elementwise_fma(x, y, A.sxy);
+    if constexpr (kSum && M != 7) A.sxy = i == 0 ? x * y : __builtin_elementwise_fma(x, y, A.sxy);
 }
 
 // the group's terms of one format from its float32 sums
@@ -333,8 +381,18 @@ __device__ __forceinline__ void f32_terms(const FAcc &A, double *t, float &mx)
     }
 }
 
+// |x − y| of one main-class element under the format's constants of the group whose P = 2^(E−127) has the bit pattern `pb` (E in [80,180]):
+// P·kC and P·kHi written as bit patterns (P has no mantissa bits), so that they stay scalar when `pb` is wave-uniform
+template <int M> __device__ __forceinline__ float redo_abs_delta(float x, uint32_t pb)
+{
+    constexpr uint32_t c_exp = M == 7 ? 17u : (M == 3 ? 21u : 23u);                  // kC = 1.5·2^c_exp
+    constexpr uint32_t hi_man = M == 7 ? 0x7E0000u : (M == 3 ? 0x600000u : 0u);     // mantissa field of kHi = 1.984375, 1.75, 1
+    const float C = u2f((pb + (c_exp << 23)) | 0x00400000u), hi = u2f(pb | hi_man);
+    return __builtin_fabsf(x - __builtin_amdgcn_fmed3f((x + C) - C, -hi, hi));
+}
+
 template <uint32_t SUMS, uint32_t ERRS, bool XS, typename Reload>
-__device__ __forceinline__ void fast_group_f32(const uint32_t w[8], GroupOut &G, Reload reload)
+__device__ __forceinline__ void fast_group_f32(uint32_t lane, const uint32_t w[8], GroupOut &G, Reload reload)
 {
     constexpr uint32_t ANY = SUMS | ERRS;
     constexpr bool XSD = XS && (SUMS & 1u) != 0;                   // Σx from bfp8's Σy + Σδ instead of a float64 chain
@@ -380,32 +438,41 @@ __device__ __forceinline__ void fast_group_f32(const uint32_t w[8], GroupOut &G,
     else probe = G.term[(SUMS & 1u) ? 4 : ((SUMS & 2u) ? 8 : 12)];
     G.bad = (out_of_range && !zero_group) || probe != probe;
 
-    // tail class present (a zero element alone also gets here — the loop then changes nothing but the order of a sum of exact terms).
-    // A ROLLED loop over the group's words, read again from the LDS image one at a time, with the constants formed again from P: what the
-    // branch keeps alive beside the fast path's registers decides the kernel's occupancy (unrolled: 149 VGPRs for <3,1>, 126 without it).
-    if (__builtin_expect(amin < thr && !zero_group && !out_of_range, 0)) {
-        double mx_ = 0.0, mx2 = 0.0, tx = 0.0, tx2 = 0.0, tab = 0.0, m8 = 0.0, m4 = 0.0, m2 = 0.0;
-#pragma nounroll
-        for (int i = 0; i < 8; ++i) {
-            const uint32_t wi = reload(i);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float xv = h == 0 ? u2f(wi << 16) : u2f(wi & 0xFFFF0000u);
-                const double xd = (double)xv;
-                if (__builtin_fabsf(xv) < P * 0x1p-14f) {          // tail (zeros included): y = 0 in every BFP format, |x − y| = |x|
-                    tx += xd; tx2 = __builtin_fma(xd, xd, tx2); tab += __builtin_fabs(xd);
-                } else {
-                    mx_ += xd; mx2 = __builtin_fma(xd, xd, mx2);
-                    if constexpr (ERRS & 1u) m8 += (double)__builtin_fabsf(xv - __builtin_amdgcn_fmed3f((xv + P * FmtF<7>::kC) - P * FmtF<7>::kC, -(P * FmtF<7>::kHi), P * FmtF<7>::kHi));
-                    if constexpr (ERRS & 2u) m4 += (double)__builtin_fabsf(xv - __builtin_amdgcn_fmed3f((xv + P * FmtF<3>::kC) - P * FmtF<3>::kC, -(P * FmtF<3>::kHi), P * FmtF<3>::kHi));
-                    if constexpr (ERRS & 4u) m2 += (double)__builtin_fabsf(xv - __builtin_amdgcn_fmed3f((xv + P * FmtF<1>::kC) - P * FmtF<1>::kC, -P, P));
-                }
+    // tail class present in some lane's group (a zero element alone also gets here — the redo then returns the same exact sums).
+    // The WAVE redoes the offending lanes' groups one after the other, in ascending lane order: in every 16-lane row lane e takes element e
+    // of the owner's group (read again from the LDS image; the four rows do the same work, so the owner finds the result in its own row),
+    // with the owner's P broadcast and every constant formed from it in scalar registers.  An entry costs what ONE group needs instead of
+    // a 16-element loop issued for the whole wave.
+    //   main class: Σx, Σx², Σ|x−y| are sums of integer multiples of u = 2^(E−148) (u² for Σx²) whose partial sums stay below 2^53 units,
+    //   so they are exact in float64 in ANY order (the argument above) and may be reduced across the lanes — in float32 for as long as the
+    //   partial sums stay within 2^24 units: |x| < 2^22·u (4 elements), |δ| ≤ 2^15·u, 2^19·u (16 elements), 2^21·u (bfp2: 8 elements).
+    //   tail class: the contract's order matters (the terms are not multiples of u): added in float64 in ascending element index, zeros
+    //   skipped (x + ±0 = x, and the sums start at +0); joined as before, S = S_main + S_tail, one float64 add per statistic.
+    // What the branch keeps alive beside the fast path's registers decides the kernel's occupancy: nothing of the fast path is reused.
+    const unsigned long long todo = __builtin_amdgcn_ballot_w64(amin < thr && !zero_group && !out_of_range);
+    if (__builtin_expect(todo != 0ull, 0)) {
+        for (unsigned long long rest = todo; rest != 0ull; rest &= rest - 1ull) {
+            const uint32_t owner = (uint32_t)__builtin_ctzll(rest);
+            const uint32_t pb = (uint32_t)__builtin_amdgcn_readlane((int)f2u(P), (int)owner);   // the owner's P: in range, or it would not be listed
+            const float xv = u2f(reload(owner) << 16);
+            const bool tail = __builtin_fabsf(xv) < u2f(pb - (14u << 23));                    // |x| < P·2^−14 (zeros included): y = 0 in every BFP format, |x − y| = |x|
+            const float xm = tail ? 0.0f : xv;                                                // a tail element adds +0 to every main-class sum
+            double tx = 0.0, tx2 = 0.0, tab = 0.0;
+            for (uint32_t tl = (uint32_t)__builtin_amdgcn_ballot_w64(tail && xv != 0.0f) & 0xFFFFu; tl != 0u; tl &= tl - 1u) {
+                const double xd = (double)u2f((uint32_t)__builtin_amdgcn_readlane((int)f2u(xv), __builtin_ctz(tl)));
+                tx += xd; tx2 = __builtin_fma(xd, xd, tx2); tab += __builtin_fabs(xd);
             }
+            const bool own = lane == owner;
+            if constexpr (XS) {
+                const double xd = (double)xm;
+                const double sx_main = row_sum_exact<2>(xm), sx2_main = row_sum_exact(xd * xd);
+                G.term[0] = own ? sx_main + tx : G.term[0];
+                G.term[1] = own ? sx2_main + tx2 : G.term[1];
+            }
+            if constexpr (ERRS & 1u) { const double m = row_sum_exact<4>(redo_abs_delta<7>(xm, pb)); G.term[5] = own ? m + tab : G.term[5]; }
+            if constexpr (ERRS & 2u) { const double m = row_sum_exact<4>(redo_abs_delta<3>(xm, pb)); G.term[9] = own ? m + tab : G.term[9]; }
+            if constexpr (ERRS & 4u) { const double m = row_sum_exact<3>(redo_abs_delta<1>(xm, pb)); G.term[13] = own ? m + tab : G.term[13]; }
         }
-        if constexpr (XS) { G.term[0] = mx_ + tx; G.term[1] = mx2 + tx2; }
-        if constexpr (ERRS & 1u) G.term[5] = m8 + tab;
-        if constexpr (ERRS & 2u) G.term[9] = m4 + tab;
-        if constexpr (ERRS & 4u) G.term[13] = m2 + tab;
     }
 }
 
@@ -450,6 +517,16 @@ __host__ __device__ constexpr int rolled_waves(uint32_t sums, uint32_t errs)
 #endif
 }
 
+// The most waves per SIMD an instantiation may be RESIDENT at (0: whatever its registers allow).  The forms compiled for 3 waves are
+// pinned there: one that happens to fit 128 registers would otherwise be placed four to a SIMD, which the streamed search pays for (above);
+// the compiler then reports the smallest allocation that keeps a fourth wave out (136 registers).  The pin covers <3,1>, <3,3>, <5,5>,
+// <6,6> and <7,7>: the occupancy of these forms no longer rises by itself when a change shrinks their registers — whoever wants a
+// fourth wave has to change rolled_waves (and the grid with it) on purpose.
+__host__ __device__ constexpr int rolled_max_waves(uint32_t sums, uint32_t errs, bool listed)
+{
+    return !listed && rolled_waves(sums, errs) == 3 ? 3 : 0;
+}
+
 struct PlaceArgs { uint32_t eval_mask; int o_bf16, o8, o4, o2; };
 __device__ __forceinline__ void place_stat(const PlaceArgs pa, double *rec_t, int sidx, double r)
 {
@@ -478,7 +555,8 @@ struct ListedArgs {
 };
 
 template <uint32_t SUMS, uint32_t ERRS, bool XS, bool LISTED>
-__global__ __launch_bounds__(kFastWaves * 64, rolled_waves(SUMS, ERRS)) void tile_stats_bf16_rolled(
+__global__ __launch_bounds__(kFastWaves * 64)   // (the waves per SIMD go through the attribute: a second launch-bounds argument would replace it)
+__attribute__((amdgpu_waves_per_eu(rolled_waves(SUMS, ERRS), rolled_max_waves(SUMS, ERRS, LISTED)))) void tile_stats_bf16_rolled(
     const uint16_t *__restrict__ x, int64_t stride, int64_t ld, int tiles_w, int64_t tiles, int units_w, int units_per_tensor,
     int total_units, uint32_t fmt_mask, uint32_t eval_mask, uint32_t part_mask, int rec, double *__restrict__ stats, unsigned *__restrict__ work,
     unsigned launch_id, int units_per_wave, ListedArgs la, unsigned *__restrict__ mark, int self_reset)
@@ -664,8 +742,11 @@ __global__ __launch_bounds__(kFastWaves * 64, rolled_waves(SUMS, ERRS)) void til
                 w2[0] = l2.x; w2[1] = l2.y; w2[2] = l2.z; w2[3] = l2.w; w2[4] = h2.x; w2[5] = h2.y; w2[6] = h2.z; w2[7] = h2.w;
             });
 #else
-            fast_group_f32<SUMS, ERRS, XS>(w, G, [&](int i) -> uint32_t {   // word i of the group, from the LDS image
-                return *reinterpret_cast<const uint32_t *>(rowp + ((c0 ^ (kl | (uint32_t)(i >> 2))) << 4) + 4 * (i & 3));
+            // element j of lane `owner`'s group, from the LDS image (owner wave-uniform: its row slot and swizzle are scalar work; element e of a
+            // group sits at byte 2(e & 7) of chunk c0 ^ kl ^ (e >> 3), that is at ((c0 ^ kl) << 4) ^ 2e)
+            fast_group_f32<SUMS, ERRS, XS>((uint32_t)lane, w, G, [&](uint32_t owner) -> uint32_t {
+                const uint32_t jo = owner & 15u, co = ((4u * (owner >> 4)) ^ swz(jo) ^ kl) << 4;
+                return *reinterpret_cast<const uint16_t *>((g < 2 ? half_a : half_b) + jo * 256u + (co ^ (2u * j)));
             });
 #endif
 #pragma unroll
@@ -682,8 +763,7 @@ __global__ __launch_bounds__(kFastWaves * 64, rolled_waves(SUMS, ERRS)) void til
 #pragma unroll
         for (int f = 0; f < 3; ++f) {
             if (!(ERRS & (1u << f))) continue;
-#pragma unroll
-            for (int sft = 1; sft < 16; sft <<= 1) { const float o = __shfl_xor(mx[f], sft, 16); asm("v_max_f32 %0, %0, %1" : "+v"(mx[f]) : "v"(o)); }
+            mx[f] = row_max_nonneg(mx[f]);   // magnitudes (or the tile is marked and the value never used)
         }
         const unsigned long long bad_lanes = __ballot(bad);
         const bool tile_bad = ((bad_lanes >> (16 * t)) & 0xFFFFull) != 0ull;
