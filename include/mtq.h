@@ -635,6 +635,35 @@ int mtq_pack_tiles(const void *x, int in_dtype, int64_t rows, int64_t cols, int6
  * and map; MTQ_DTYPE_BF16: the upper halves, which is exact (every BFP and bf16 value has its low 16 bits zero). */
 int mtq_unpack_tiles(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows, int64_t cols,
                      void *y, int out_dtype, int64_t ldy, void *stream);
+
+/* The batch: `count` tensors of one shape into ONE arena, tensor i's stream at byte 64 * bases[i], with no host work per tensor.  All
+ * pointers are device pointers and the calls are asynchronous on `stream`.
+ *
+ * The offsets entry is the device counterpart of the host offsets function for `count` maps of `tiles` int8 codes each, contiguous:
+ * offsets[count][tiles + 1] uint32, row i the same numbers the host function gives for map i; bases[count + 1] uint64, the exclusive
+ * prefix sum over tensors of offsets[i][tiles] (units of 64 bytes; 64 * bases[count] is the arena's length); bad[count] int32, the
+ * number of codes outside 0..3 in map i.  Such a tile counts 0 units (the host function refuses it: read `bad` before trusting row i).
+ * Two kernels on `stream` (one workgroup per tensor, then one workgroup over the totals); plain stores, no atomics, no waiting between
+ * workgroups: deterministic.  tiles > MTQ_PACKED_BATCH_MAX_TILES (a tensor's stream must fit 32-bit units) is MTQ_ERR_INVALID.
+ *
+ * The pack entry: x holds `count` rows × cols matrices (in_dtype, row pitch ld >= cols), matrix i starting i * stride elements in
+ * (stride >= (rows - 1) * ld + cols when count > 1).  One wave per (tensor, tile); tile t of tensor i goes to
+ * out + 64 * (bases[i] + offsets[i][t]), byte for byte what the single-tensor entry writes for matrix i.  Every blob is checked
+ * against out_bytes on the device before it is written and a tile whose code is outside 0..3 is skipped.  The 16-byte loads are taken
+ * only when x, ld and stride keep every matrix 16-byte aligned.
+ *
+ * The unpack entry is the mirror image: the arena → y[count][rows][cols] (out_dtype, row pitch ldy, matrix stride in elements), with
+ * the edge handling of the single-tensor entry: nothing is stored outside rows × cols, nor for a tile whose blob does not fit
+ * packed_bytes.
+ *
+ * Argument errors (null pointers, count <= 0, ld < cols, a buffer below 320 bytes per tile, an arena that is not 16-byte aligned) are
+ * MTQ_ERR_INVALID before a device is looked for. */
+#define MTQ_PACKED_BATCH_MAX_TILES ((int64_t)(0xFFFFFFFFu / 32u))
+int mtq_packed_offsets_batched(const int8_t *maps, int64_t count, int64_t tiles, uint32_t *offsets, uint64_t *bases, int32_t *bad, void *stream);
+int mtq_pack_tiles_batched(const void *x, int in_dtype, int64_t count, int64_t rows, int64_t cols, int64_t ld, int64_t stride,
+                           const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, void *out, size_t out_bytes, void *stream);
+int mtq_unpack_tiles_batched(const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases,
+                             int64_t count, int64_t rows, int64_t cols, void *y, int out_dtype, int64_t ldy, int64_t stride, void *stream);
 /* Y = X·Ŵᵀ + b: x m × k bf16 (ldx), Ŵ the packed n × k weight (nn.Linear convention; map grid ceil(n/32) × ceil(k/32)), bias n
  * float32 or NULL, y m × n float32 or bf16 (out_dtype, ldy).  The weight is decoded into a bf16 LDS image (exact) and multiplied by
  * mfma_f32_32x32x16_bf16 with f32 accumulation in a fixed K order; bias is added in f32, a bf16 y is rounded to nearest even once.

@@ -8,6 +8,10 @@
 // codes are therefore the 16 / 8 / 4 (or, bf16, 32) contiguous bytes at 64 + 16g / 8g / 4g (32g): one lane, one vector access.
 //
 //   pack_tiles_kernel / unpack_tiles_kernel   one wave per tile, one lane per group; the format is uniform across the wave.
+//   packed_offsets_batched_kernel, packed_bases_kernel, pack_tiles_batched_kernel / unpack_tiles_batched_kernel
+//                                             a batch of equal-shaped tensors into one arena: the offsets of every map and the tensors'
+//       bases by block scans on the device (plain stores, no atomics, no waiting between workgroups), then one wave per (tensor, tile)
+//       through the same per-tile bodies as the single-tensor kernels.
 //   packed_linear_kernel                      Y = X·Ŵᵀ + b in the shape of mtq_output_error.hip: a workgroup of 4 waves owns a
 //       128 (M) × 64 (N) block and walks K in steps of 64; per step each of the 256 lanes takes one group of the 64 × 64 W block, reads
 //       its exponent byte and its code bytes and decodes them into the bf16 LDS image (every BFP value has its low 16 bits zero: the
@@ -90,11 +94,12 @@ struct TileAt {
     int f;
 };
 
-__device__ __forceinline__ TileAt tile_at(uint64_t packed_bytes, const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t t)
+__device__ __forceinline__ TileAt tile_at(uint64_t packed_bytes, const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t t,
+                                          uint64_t base = 0)   // base: where the tensor's stream starts in an arena, in units
 {
     TileAt a;
     const int f = map[t];
-    a.off = (uint64_t)offsets[t] * kUnit;
+    a.off = (base + offsets[t]) * kUnit;
     const uint32_t size = packed_tile_bytes(f);
     a.f = (size == 0u || a.off + size > packed_bytes) ? -1 : f;
     return a;
@@ -130,6 +135,42 @@ __device__ __forceinline__ void load_group(const uint8_t *__restrict__ packed, c
 }
 
 // ---- pack: lane = group (row lane >> 1, half lane & 1) of the wave's tile
+// Tile t (format f, 0..3) of the rows × cols matrix x → the blob: what one wave does, for the single-tensor and the batched kernel alike.
+template <typename T>
+__device__ __forceinline__ void pack_tile(const T *__restrict__ x, int64_t rows, int64_t cols, int64_t ld, bool vec_ok, int64_t tiles_w, int64_t t,
+                                          int f, int lane, uint8_t *__restrict__ blob)
+{
+    const int64_t row = (t / tiles_w) * kTile + (lane >> 1), col0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
+    uint32_t u[kGroup];
+    Loader<T>::group(x, row, col0, rows, cols, ld, vec_ok, u);
+    if (f == 0) {
+        uint32_t y[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) y[i] = bf16_round_bits(u[i]);
+        uint4 lo, hi;
+        pack_halves(y, lo, hi);
+        uint4 *d = reinterpret_cast<uint4 *>(blob + lane * 32);
+        d[0] = lo;
+        d[1] = hi;
+        return;
+    }
+    const uint32_t E = group_shared_exp(u);
+    const uint32_t M = f == 1 ? 7u : (f == 2 ? 3u : 1u), B = M + 1u;
+    blob[lane] = (uint8_t)E;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) {
+        const uint32_t code = bfp_code_rt(u[i], E, M);
+        if (f == 1) w[i >> 2] |= code << (8 * (i & 3));
+        else if (f == 2) w[i >> 3] |= code << (4 * (i & 7));
+        else w[0] |= code << (2 * i);
+    }
+    uint8_t *dst = blob + kExpBytes + lane * (2 * (int)B);   // 16 codes of B bits
+    if (f == 1) *reinterpret_cast<uint4 *>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+    else if (f == 2) *reinterpret_cast<uint2 *>(dst) = make_uint2(w[0], w[1]);
+    else *reinterpret_cast<uint32_t *>(dst) = w[0];
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void pack_tiles_kernel(const T *__restrict__ x, int64_t rows, int64_t cols, int64_t ld, int vec_ok,
                                                          const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t tiles,
@@ -141,78 +182,172 @@ __global__ __launch_bounds__(256) void pack_tiles_kernel(const T *__restrict__ x
         const uint32_t size = packed_tile_bytes(f);
         const uint64_t off = (uint64_t)offsets[t] * kUnit;
         if (size == 0u || off + size > out_bytes) continue;   // wave-uniform
-        const int64_t row = (t / tiles_w) * kTile + (lane >> 1), col0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
-        uint32_t u[kGroup];
-        Loader<T>::group(x, row, col0, rows, cols, ld, vec_ok != 0, u);
-        uint8_t *blob = out + off;
-        if (f == 0) {
-            uint32_t y[kGroup];
-#pragma unroll
-            for (int i = 0; i < kGroup; ++i) y[i] = bf16_round_bits(u[i]);
-            uint4 lo, hi;
-            pack_halves(y, lo, hi);
-            uint4 *d = reinterpret_cast<uint4 *>(blob + lane * 32);
-            d[0] = lo;
-            d[1] = hi;
-            continue;
-        }
-        const uint32_t E = group_shared_exp(u);
-        const uint32_t M = f == 1 ? 7u : (f == 2 ? 3u : 1u), B = M + 1u;
-        blob[lane] = (uint8_t)E;
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < kGroup; ++i) {
-            const uint32_t code = bfp_code_rt(u[i], E, M);
-            if (f == 1) w[i >> 2] |= code << (8 * (i & 3));
-            else if (f == 2) w[i >> 3] |= code << (4 * (i & 7));
-            else w[0] |= code << (2 * i);
-        }
-        uint8_t *dst = blob + kExpBytes + lane * (2 * (int)B);   // 16 codes of B bits
-        if (f == 1) *reinterpret_cast<uint4 *>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
-        else if (f == 2) *reinterpret_cast<uint2 *>(dst) = make_uint2(w[0], w[1]);
-        else *reinterpret_cast<uint32_t *>(dst) = w[0];
+        pack_tile(x, rows, cols, ld, vec_ok != 0, tiles_w, t, f, lane, out + off);
+    }
+}
+
+// The batch: wave g of count * tiles takes tile t = g % tiles of tensor i = g / tiles, whose matrix starts i * stride elements into x and
+// whose stream starts at unit bases[i] of the arena `out`.  maps [count][tiles], offsets [count][tiles + 1].
+template <typename T>
+__global__ __launch_bounds__(256) void pack_tiles_batched_kernel(const T *__restrict__ x, int64_t count, int64_t rows, int64_t cols, int64_t ld,
+                                                                 int64_t stride, int vec_ok, const int8_t *__restrict__ maps,
+                                                                 const uint32_t *__restrict__ offsets, const uint64_t *__restrict__ bases,
+                                                                 int64_t tiles, int64_t tiles_w, uint8_t *__restrict__ out, uint64_t out_bytes)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t total = count * tiles;
+    for (int64_t g = (int64_t)blockIdx.x * 4 + wave; g < total; g += (int64_t)gridDim.x * 4) {
+        const int64_t i = g / tiles, t = g - i * tiles;
+        const int f = maps[g];
+        const uint32_t size = packed_tile_bytes(f);
+        const uint64_t off = (bases[i] + offsets[i * (tiles + 1) + t]) * kUnit;
+        if (size == 0u || off > out_bytes || size > out_bytes - off) continue;   // wave-uniform
+        pack_tile(x + i * stride, rows, cols, ld, vec_ok != 0, tiles_w, t, f, lane, out + off);
     }
 }
 
 // ---- unpack: the same ownership; y float32 (the words) or bf16 (their upper halves)
+// The blob at `a` → tile t of the rows × cols matrix y: a tile whose blob is not there stores nothing, nor does a lane past an edge.
+template <bool BF16OUT>
+__device__ __forceinline__ void unpack_tile(const uint8_t *__restrict__ packed, const TileAt &a, int64_t tiles_w, int64_t t, int lane, int64_t rows,
+                                            int64_t cols, void *__restrict__ yv, int64_t ldy, bool vec_ok)
+{
+    const int64_t row = (t / tiles_w) * kTile + (lane >> 1), col0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
+    GroupRaw g;
+    load_group(packed, a, lane, g);
+    if (g.f < 0 || row >= rows || col0 >= cols) return;
+    uint32_t y[kGroup];
+    decode_group(g, y);
+    const bool whole = col0 + kGroup <= cols && vec_ok;
+    if constexpr (BF16OUT) {
+        uint16_t *yr = static_cast<uint16_t *>(yv) + row * ldy + col0;
+        if (whole) {
+            uint4 lo, hi;
+            pack_halves(y, lo, hi);
+            reinterpret_cast<uint4 *>(yr)[0] = lo;
+            reinterpret_cast<uint4 *>(yr)[1] = hi;
+        } else {
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i)
+                if (col0 + i < cols) yr[i] = (uint16_t)(y[i] >> 16);
+        }
+    } else {
+        uint32_t *yr = static_cast<uint32_t *>(yv) + row * ldy + col0;
+        if (whole) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(yr)[i] = make_uint4(y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < kGroup; ++i)
+                if (col0 + i < cols) yr[i] = y[i];
+        }
+    }
+}
+
 template <bool BF16OUT>
 __global__ __launch_bounds__(256) void unpack_tiles_kernel(const uint8_t *__restrict__ packed, uint64_t packed_bytes, const int8_t *__restrict__ map,
                                                            const uint32_t *__restrict__ offsets, int64_t tiles, int64_t tiles_w, int64_t rows,
                                                            int64_t cols, void *__restrict__ yv, int64_t ldy, int vec_ok)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < tiles; t += (int64_t)gridDim.x * 4) {
-        const int64_t row = (t / tiles_w) * kTile + (lane >> 1), col0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
-        GroupRaw g;
-        load_group(packed, tile_at(packed_bytes, map, offsets, t), lane, g);
-        if (g.f < 0 || row >= rows || col0 >= cols) continue;
-        uint32_t y[kGroup];
-        decode_group(g, y);
-        const bool whole = col0 + kGroup <= cols && vec_ok;
-        if constexpr (BF16OUT) {
-            uint16_t *yr = static_cast<uint16_t *>(yv) + row * ldy + col0;
-            if (whole) {
-                uint4 lo, hi;
-                pack_halves(y, lo, hi);
-                reinterpret_cast<uint4 *>(yr)[0] = lo;
-                reinterpret_cast<uint4 *>(yr)[1] = hi;
-            } else {
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < tiles; t += (int64_t)gridDim.x * 4)
+        unpack_tile<BF16OUT>(packed, tile_at(packed_bytes, map, offsets, t), tiles_w, t, lane, rows, cols, yv, ldy, vec_ok != 0);
+}
+
+// The batch, as pack_tiles_batched_kernel numbers it: matrix i of y starts i * stride elements in.
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void unpack_tiles_batched_kernel(const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+                                                                   const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets,
+                                                                   const uint64_t *__restrict__ bases, int64_t count, int64_t tiles, int64_t tiles_w,
+                                                                   int64_t rows, int64_t cols, void *__restrict__ yv, int64_t ldy, int64_t stride,
+                                                                   int vec_ok)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t total = count * tiles;
+    for (int64_t g = (int64_t)blockIdx.x * 4 + wave; g < total; g += (int64_t)gridDim.x * 4) {
+        const int64_t i = g / tiles, t = g - i * tiles;
+        const TileAt a = tile_at(packed_bytes, maps + i * tiles, offsets + i * (tiles + 1), t, bases[i]);
+        void *yi = BF16OUT ? static_cast<void *>(static_cast<uint16_t *>(yv) + i * stride) : static_cast<void *>(static_cast<uint32_t *>(yv) + i * stride);
+        unpack_tile<BF16OUT>(packed, a, tiles_w, t, lane, rows, cols, yi, ldy, vec_ok != 0);
+    }
+}
+
+// ---- batched offsets: the device counterpart of mtq_packed_offsets
+// Exclusive prefix of v over the 256 threads of the workgroup (thread order) and the workgroup's total: a shuffle scan in each wave, the
+// four wave totals through LDS.  lds: 4 words, free to reuse after the call.
+template <typename U>
+__device__ __forceinline__ U block_exclusive_scan(U v, U *lds, U &total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    U incl = v;
 #pragma unroll
-                for (int i = 0; i < kGroup; ++i)
-                    if (col0 + i < cols) yr[i] = (uint16_t)(y[i] >> 16);
-            }
-        } else {
-            uint32_t *yr = static_cast<uint32_t *>(yv) + row * ldy + col0;
-            if (whole) {
+    for (int d = 1; d < 64; d <<= 1) {
+        const U up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    __syncthreads();                                  // the previous use of lds is over
+    if (lane == 63) lds[wave] = incl;
+    __syncthreads();
+    U before = 0;
+    total = 0;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(yr)[i] = make_uint4(y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < kGroup; ++i)
-                    if (col0 + i < cols) yr[i] = y[i];
-            }
+    for (int w = 0; w < 4; ++w) {
+        const U s = lds[w];
+        if (w < wave) before += s;
+        total += s;
+    }
+    return before + incl - v;
+}
+
+// One workgroup per tensor: thread k sums the units of tiles [k * per, (k + 1) * per), the workgroup scans the 256 sums, and a second
+// pass over the same run writes the offsets.  A code outside 0..3 counts 0 units and 1 in bad[i].  tiles * 32 fits 32 bits (the entry
+// checks it), so no sum wraps.
+__global__ __launch_bounds__(256) void packed_offsets_batched_kernel(const int8_t *__restrict__ maps, int64_t count, int64_t tiles,
+                                                                     uint32_t *__restrict__ offsets, int32_t *__restrict__ bad)
+{
+    __shared__ uint32_t lds[4];
+    const int64_t per = (tiles + 255) / 256;
+    const int64_t t0 = std::min<int64_t>((int64_t)threadIdx.x * per, tiles), t1 = std::min<int64_t>(t0 + per, tiles);
+    for (int64_t i = blockIdx.x; i < count; i += gridDim.x) {
+        const int8_t *map = maps + i * tiles;
+        uint32_t *off = offsets + i * (tiles + 1);
+        uint32_t sum = 0u, nbad = 0u;
+        for (int64_t t = t0; t < t1; ++t) {
+            const uint32_t size = packed_tile_bytes(map[t]);
+            sum += size / kUnit;
+            nbad += size == 0u;
+        }
+        uint32_t total, total_bad;
+        uint32_t run = block_exclusive_scan(sum, lds, total);
+        block_exclusive_scan(nbad, lds, total_bad);
+        for (int64_t t = t0; t < t1; ++t) {
+            off[t] = run;
+            run += packed_tile_bytes(map[t]) / kUnit;
+        }
+        if (threadIdx.x == 0) {
+            off[tiles] = total;
+            bad[i] = (int32_t)total_bad;
         }
     }
+}
+
+// bases[0 .. count]: the exclusive prefix sum of the tensors' totals offsets[i][tiles], by one workgroup (behind the kernel above on the
+// same stream).
+__global__ __launch_bounds__(256) void packed_bases_kernel(const uint32_t *__restrict__ offsets, int64_t count, int64_t tiles,
+                                                           uint64_t *__restrict__ bases)
+{
+    __shared__ unsigned long long lds[4];
+    const int64_t per = (count + 255) / 256;
+    const int64_t i0 = std::min<int64_t>((int64_t)threadIdx.x * per, count), i1 = std::min<int64_t>(i0 + per, count);
+    unsigned long long sum = 0ull;
+    for (int64_t i = i0; i < i1; ++i) sum += offsets[i * (tiles + 1) + tiles];
+    unsigned long long total;
+    unsigned long long run = block_exclusive_scan(sum, lds, total);
+    for (int64_t i = i0; i < i1; ++i) {
+        bases[i] = run;
+        run += offsets[i * (tiles + 1) + tiles];
+    }
+    if (threadIdx.x == 0) bases[count] = total;
 }
 
 // ---- linear
@@ -671,6 +806,90 @@ extern "C" int mtq_unpack_tiles(const void *packed, size_t packed_bytes, const i
     else
         hipLaunchKernelGGL(unpack_tiles_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy, vec_ok);
     return check_launch("mtq_unpack_tiles");
+}
+
+// What the batched entries share: the tile grid of one matrix and the batch's tile total
+static int batch_grid(int64_t count, int64_t rows, int64_t cols, int64_t *tiles_h, int64_t *tiles_w)
+{
+    if (count <= 0) return fail(MTQ_ERR_INVALID, "count must be positive");
+    if (int rc = tile_grid(rows, cols, tiles_h, tiles_w)) return rc;
+    if (*tiles_h * *tiles_w > MTQ_PACKED_BATCH_MAX_TILES) return fail(MTQ_ERR_INVALID, "too many tiles: a tensor's stream must fit 32-bit units");
+    if (count > ((int64_t)1 << 40) / (*tiles_h * *tiles_w)) return fail(MTQ_ERR_INVALID, "too many tiles in the batch");
+    return MTQ_OK;
+}
+
+// A matrix of the batch must not reach into the next: stride 0 is allowed for a batch of one only
+static int batch_pitch(int64_t count, int64_t rows, int64_t cols, int64_t ld, int64_t stride, const char *ld_msg)
+{
+    if (ld < cols) return fail(MTQ_ERR_INVALID, ld_msg);
+    if (count > 1 && stride < (rows - 1) * ld + cols) return fail(MTQ_ERR_INVALID, "the matrix stride is smaller than a matrix");
+    return MTQ_OK;
+}
+
+extern "C" int mtq_packed_offsets_batched(const int8_t *maps, int64_t count, int64_t tiles, uint32_t *offsets, uint64_t *bases, int32_t *bad,
+                                          void *stream)
+{
+    if (!maps || !offsets || !bases || !bad) return fail(MTQ_ERR_INVALID, "null argument");
+    if (count <= 0) return fail(MTQ_ERR_INVALID, "count must be positive");
+    if (tiles <= 0) return fail(MTQ_ERR_INVALID, "tiles must be positive");
+    if (tiles > MTQ_PACKED_BATCH_MAX_TILES) return fail(MTQ_ERR_INVALID, "too many tiles: a tensor's stream must fit 32-bit units");
+    if (count > ((int64_t)1 << 40) / tiles) return fail(MTQ_ERR_INVALID, "too many tiles in the batch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)std::min<int64_t>(count, (int64_t)1 << 20));
+    hipLaunchKernelGGL(packed_offsets_batched_kernel, grid, dim3(256), 0, st, maps, count, tiles, offsets, bad);
+    if (int rc = check_launch("mtq_packed_offsets_batched")) return rc;
+    hipLaunchKernelGGL(packed_bases_kernel, dim3(1), dim3(256), 0, st, offsets, count, tiles, bases);
+    return check_launch("mtq_packed_offsets_batched");
+}
+
+extern "C" int mtq_pack_tiles_batched(const void *x, int in_dtype, int64_t count, int64_t rows, int64_t cols, int64_t ld, int64_t stride,
+                                      const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, void *out, size_t out_bytes, void *stream)
+{
+    if (!x || !maps || !offsets || !bases || !out) return fail(MTQ_ERR_INVALID, "null argument");
+    if (in_dtype != MTQ_DTYPE_BF16 && in_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "in_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    if (int rc = batch_grid(count, rows, cols, &th, &tw)) return rc;
+    if (int rc = batch_pitch(count, rows, cols, ld, stride, "ld < cols")) return rc;
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(MTQ_ERR_INVALID, "out must be 16-byte aligned");
+    if (out_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "out_bytes is smaller than the streams");
+    if (int rc = require_device()) return rc;
+    const int64_t esz = in_dtype == MTQ_DTYPE_F32 ? 4 : 2;
+    const int vec_ok = reinterpret_cast<uintptr_t>(x) % 16 == 0 && (ld * esz) % 16 == 0 && (count == 1 || (stride * esz) % 16 == 0);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(count * th * tw));
+    if (in_dtype == MTQ_DTYPE_F32)
+        hipLaunchKernelGGL(pack_tiles_batched_kernel<float>, grid, dim3(256), 0, st, static_cast<const float *>(x), count, rows, cols, ld, stride, vec_ok,
+                           maps, offsets, bases, th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    else
+        hipLaunchKernelGGL(pack_tiles_batched_kernel<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(x), count, rows, cols, ld, stride,
+                           vec_ok, maps, offsets, bases, th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    return check_launch("mtq_pack_tiles_batched");
+}
+
+extern "C" int mtq_unpack_tiles_batched(const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases,
+                                        int64_t count, int64_t rows, int64_t cols, void *y, int out_dtype, int64_t ldy, int64_t stride, void *stream)
+{
+    if (!packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    if (int rc = batch_grid(count, rows, cols, &th, &tw)) return rc;
+    if (int rc = batch_pitch(count, rows, cols, ldy, stride, "ldy < cols")) return rc;
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
+    if (int rc = require_device()) return rc;
+    const int64_t esz = out_dtype == MTQ_DTYPE_F32 ? 4 : 2;
+    const int vec_ok = reinterpret_cast<uintptr_t>(y) % 16 == 0 && (ldy * esz) % 16 == 0 && (count == 1 || (stride * esz) % 16 == 0);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(count * th * tw));
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(unpack_tiles_batched_kernel<true>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, maps, offsets, bases, count, th * tw, tw,
+                           rows, cols, y, ldy, stride, vec_ok);
+    else
+        hipLaunchKernelGGL(unpack_tiles_batched_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, maps, offsets, bases, count, th * tw, tw,
+                           rows, cols, y, ldy, stride, vec_ok);
+    return check_launch("mtq_unpack_tiles_batched");
 }
 
 extern "C" int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,

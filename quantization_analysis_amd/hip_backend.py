@@ -117,6 +117,9 @@ SIGNATURES = {
     "mtq_packed_linear_skinny_workspace_bytes": ("z", "llli", True),
     "mtq_packed_linear_skinny": ("i", "plllpzpplppilipzp", True),
     "mtq_debug_packed_decode": ("i", "ippp", True),
+    "mtq_packed_offsets_batched": ("i", "pllpppp", True),
+    "mtq_pack_tiles_batched": ("i", "pilllllppppzp", True),
+    "mtq_unpack_tiles_batched": ("i", "pzppplllpillp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -980,6 +983,81 @@ def unpack_tiles(data, tables: PackedTables, rows: int, cols: int, dtype=None, o
         raise MtqError(f"out must be a {dtype} ({rows}, {cols}) device tensor with contiguous rows")
     ldy = out.stride(0) if rows > 1 else max(out.stride(0), cols)
     check(fn(ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, rows, cols, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+PACKED_BATCH_MAX_TILES = 0xFFFFFFFF // 32   # include/mtq.h MTQ_PACKED_BATCH_MAX_TILES: a tensor's stream must fit 32-bit units
+
+
+def _batch_tables(maps_dev, offsets_dev, bases_dev, count: int, tiles: int):
+    """The pointers of a batch's device tables after checking their types and sizes: maps int8 [count * tiles], offsets int32
+    [count * (tiles + 1)] holding the uint32 words, bases int64 [count + 1] holding the uint64 words."""
+    torch = _torch()
+    return (_buffer(maps_dev, torch.int8, count * tiles, "the device maps"), _buffer(offsets_dev, torch.int32, count * (tiles + 1), "the device offsets"),
+            _buffer(bases_dev, torch.int64, count + 1, "the device bases"))
+
+
+def _arena(data, count: int, tiles: int, name: str) -> int:
+    """The pointer of a batch's arena: uint8, contiguous, on the device, 16-byte aligned and no shorter than the smallest streams the
+    batch can have (the kernels check every blob against the arena's real length themselves)."""
+    ptr = _buffer(data, _torch().uint8, count * tiles * PACKED_TILE_BYTES[3], name)
+    if data.data_ptr() % 16:
+        raise MtqError(f"{name} must be 16-byte aligned")
+    return ptr
+
+
+def packed_offsets_device(maps_dev, count: int, tiles: int, stream="current"):
+    """mtq_packed_offsets_batched on the current stream: `count` maps of `tiles` int8 codes each, contiguous on the device →
+    (offsets int32 [count, tiles + 1] holding the uint32 words, row i what packed_offsets gives for map i; bases int64 [count + 1], the
+    exclusive prefix sum of the tensors' totals in units of 64 bytes; bad int32 [count], the codes outside 0..3 per map).  Nothing is
+    read back: the caller looks at `bad` before it trusts a row."""
+    torch = _torch()
+    count, tiles = int(count), int(tiles)
+    if count <= 0 or tiles <= 0:
+        raise MtqError("count and tiles must be positive")
+    if tiles > PACKED_BATCH_MAX_TILES:
+        raise MtqError("too many tiles: a tensor's stream must fit 32-bit units")
+    ptr = _buffer(maps_dev, torch.int8, count * tiles, "the device maps")
+    fn = _entry("mtq_packed_offsets_batched")
+    require_gpu()
+    offsets = torch.empty((count, tiles + 1), dtype=torch.int32, device=maps_dev.device)
+    bases = torch.empty((count + 1,), dtype=torch.int64, device=maps_dev.device)
+    bad = torch.empty((count,), dtype=torch.int32, device=maps_dev.device)
+    check(fn(ptr, count, tiles, offsets.data_ptr(), bases.data_ptr(), bad.data_ptr(), _packed_stream_ptr(stream)))
+    return offsets, bases, bad
+
+
+def pack_tiles_batched(x3d, maps_dev, offsets_dev, bases_dev, out, stream="current"):
+    """mtq_pack_tiles_batched on the current stream: a (count, rows, cols) bf16 / float32 device tensor with contiguous rows (any row
+    pitch and matrix stride: views are read in place) → the arena `out`, a uint8 device tensor of 64 * bases[count] bytes, tensor i's
+    stream at byte 64 * bases[i]."""
+    code, count, stride, rows, cols, ld = _matrix(x3d, (3,))
+    th, tw = tiles_hw(rows, cols)
+    pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+    fn = _entry("mtq_pack_tiles_batched")
+    ptr = _arena(out, count, th * tw, "out")
+    check(fn(x3d.data_ptr(), code, count, rows, cols, ld, stride, pm, po, pb, ptr, out.numel(), _packed_stream_ptr(stream)))
+    return out
+
+
+def unpack_tiles_batched(data, maps_dev, offsets_dev, bases_dev, count: int, rows: int, cols: int, dtype=None, out=None, stream="current"):
+    """mtq_unpack_tiles_batched on the current stream: the arena → a (count, rows, cols) device tensor, float32 (the bits K3 writes) or
+    bfloat16 (exact).  out: a tensor of that shape and type with contiguous rows; what lies outside rows × cols of a pitched view stays."""
+    torch = _torch()
+    dtype = dtype or torch.float32
+    code = _packed_out_code(dtype)
+    count, rows, cols = int(count), int(rows), int(cols)
+    th, tw = tiles_hw(rows, cols)
+    pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+    ptr = _arena(data, count, th * tw, "data")
+    fn = _entry("mtq_unpack_tiles_batched")
+    if out is None:
+        require_gpu()
+        out = torch.empty((count, rows, cols), dtype=dtype, device=data.device)
+    elif out.dtype != dtype or out.dim() != 3 or tuple(out.shape) != (count, rows, cols) or out.stride(2) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {dtype} ({count}, {rows}, {cols}) device tensor with contiguous rows")
+    _code, _count, stride, _rows, _cols, ldy = _matrix(out, (3,))
+    check(fn(ptr, data.numel(), pm, po, pb, count, rows, cols, out.data_ptr(), code, ldy, stride, _packed_stream_ptr(stream)))
     return out
 
 

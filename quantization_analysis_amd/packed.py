@@ -4,6 +4,9 @@ The format is the one include/mtq.h fixes (row layout; tile t = tr * tiles_w + t
 576 / 320 bytes for the map codes 0..3; uint32 offsets in units of 64 bytes).  It is this project's own layout, not TTNN's on-device
 tile format.
 
+pack_batch / unpack_batch take a batch of equal-shaped tensors and their maps (a search pipeline's resident batch and its results) to one
+arena and back with a fixed number of launches; save_dir / load_dir keep a named set of packed tensors in a directory.
+
 Two backends:
   "hip"        the C ABI (csrc/mtq_packed.hip) through hip_backend's wrappers; data lives on the device.
   "emulation"  a NumPy encoder and decoder written from the format's description: the byte-level oracle of the GPU tests, and the way
@@ -64,6 +67,7 @@ class PackedTensor:
     data: object
     layout: str = "rows"
     _tables: object = None      # hip: the device copies of map and offsets (hip_backend.PackedTables), made on first use
+    _batch: object = None       # (PackedBatch, index) of a tensor pack_batch made: its data is a slice of the batch's arena
 
     @property
     def nbytes(self) -> int:
@@ -91,9 +95,13 @@ class PackedTensor:
         return self._tables
 
 
-def _check_layout(layout: str) -> None:
+def check_layout(layout: str) -> None:
+    """Raises for every layout but "rows": the packed format holds row groups only."""
     if layout != "rows":
         raise MtqError(f"the packed format holds the row layout only; a map over layout {layout!r} cannot be packed")
+
+
+_check_layout = check_layout
 
 
 def _check_map(amap, rows: int, cols: int) -> np.ndarray:
@@ -338,6 +346,171 @@ def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
 
 
+# ----------------------------------------------------------------------------- batches
+
+@dataclass
+class PackedBatch:
+    """What the tensors of one pack_batch call share.  arena: the uint8 streams back to back (a NumPy array, or a device tensor);
+    bases: uint64 [count + 1] on the host, tensor i's stream is arena[64 * bases[i] : 64 * bases[i + 1]]; hip: maps_dev int8
+    [count, tiles], offsets_dev int32 [count, tiles + 1] (the uint32 words) and bases_dev int64 [count + 1], the tables the batched
+    kernels read."""
+
+    count: int
+    rows: int
+    cols: int
+    arena: object
+    bases: np.ndarray
+    maps_dev: object = None
+    offsets_dev: object = None
+    bases_dev: object = None
+
+
+def batch_of(pts):
+    """The PackedBatch a list of packed tensors came from, if the list is that batch in order; None otherwise."""
+    pts = list(pts)
+    if not pts or pts[0]._batch is None:
+        return None
+    batch = pts[0]._batch[0]
+    if len(pts) != batch.count or any(pt._batch is None or pt._batch[0] is not batch or pt._batch[1] != i for i, pt in enumerate(pts)):
+        return None
+    return batch
+
+
+def _check_maps(maps, count: int, rows: int, cols: int) -> np.ndarray:
+    """Host maps of a batch → int8 (count, tiles_h, tiles_w), every code 0..3."""
+    th, tw = -(-rows // TILE), -(-cols // TILE)
+    a = np.asarray(maps)
+    if a.size != count * th * tw:
+        raise MtqError(f"the maps have {a.size} entries, {count} tensors of {th}x{tw} tiles have {count * th * tw}")
+    a = np.ascontiguousarray(a.astype(np.int8).reshape(count, th, tw))
+    bad = np.flatnonzero(((a < 0) | (a > 3)).reshape(count, -1).any(axis=1))
+    if bad.size:
+        raise MtqError(f"tensor {int(bad[0])} of the batch: map codes must be MIXED_TILE_FORMATS codes 0..3 (bf16, bfp8, bfp4, bfp2)")
+    return a
+
+
+def _batch_shapes(shapes, count: int, rows: int, cols: int) -> list:
+    """The original shape of every tensor of the batch: (rows, cols) unless `shapes` names tensors of higher rank with that flatten."""
+    if shapes is None:
+        return [(rows, cols)] * count
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    if len(shapes) != count or any(len(s) < 2 or s[-1] != cols or int(np.prod(s[:-1])) != rows for s in shapes):
+        raise MtqError(f"shapes must name {count} tensors whose 2-D flatten is ({rows}, {cols})")
+    return shapes
+
+
+def pack_batch(x3d, maps, backend: str = "emulation", layout: str = "rows", shapes=None) -> list:
+    """`count` tensors of one 2-D shape and their tile maps → a list of PackedTensor whose streams are slices of one arena.
+
+    x3d: (count, rows, cols), a NumPy array or a torch tensor; on hip a bf16 / float32 device tensor is read in place, whatever its row
+    pitch and matrix stride (a [::2] view, a view of a wider buffer).  maps: int8 (count, tiles_h, tiles_w), a NumPy array or (hip) a
+    device tensor, e.g. a search's maps that never left the device.  shapes: the tensors' original shapes when they are of higher rank
+    than their 2-D flatten.
+
+    hip: host maps are checked on the host and uploaded once; device maps are checked on the device.  The offsets of every map and the
+    tensors' bases come from one launch pair, the streams from one more; the call synchronises once, to read back the bases, the count
+    of bad codes per tensor and (device maps) the maps.  A tensor with a code outside 0..3 raises MtqError before anything is packed.
+    emulation: a loop over the NumPy encoder into one NumPy arena with the same slicing.
+
+    Every returned tensor is a full PackedTensor (unpack, linear, PackedLinear, save); unpack_batch undoes the call in one launch."""
+    _check_layout(layout)
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    if len(x3d.shape) != 3 or 0 in tuple(x3d.shape):
+        raise MtqError(f"pack_batch takes a non-empty (count, rows, cols) batch, got {tuple(x3d.shape)}")
+    count, rows, cols = (int(v) for v in x3d.shape)
+    th, tw = -(-rows // TILE), -(-cols // TILE)
+    tiles = th * tw
+    shapes = _batch_shapes(shapes, count, rows, cols)
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        hb.require_gpu()
+        if not _is_torch(x3d):
+            x3d = torch.from_numpy(np.ascontiguousarray(x3d, dtype=np.float32))
+        if x3d.dtype not in (torch.bfloat16, torch.float32):
+            x3d = x3d.to(torch.float32)
+        if not x3d.is_cuda:
+            x3d = x3d.to(torch.device("cuda", torch.cuda.current_device()))
+        if x3d.stride(-1) != 1:
+            x3d = x3d.contiguous()
+        host_maps = None
+        if _is_torch(maps) and maps.is_cuda:
+            if maps.dtype != torch.int8 or maps.numel() != count * tiles:
+                raise MtqError(f"device maps must be int8 with {count} x {th}x{tw} entries, got {maps.dtype} with {maps.numel()}")
+            maps_dev = maps.contiguous().reshape(count, tiles)
+        else:
+            host_maps = _check_maps(maps.numpy() if _is_torch(maps) else maps, count, rows, cols)
+            maps_dev = torch.from_numpy(host_maps.reshape(count, tiles)).to(x3d.device)
+        offsets_dev, bases_dev, bad_dev = hb.packed_offsets_device(maps_dev, count, tiles)
+        # the one read-back: bases, bad and (device maps) the maps as one byte string
+        parts = [bases_dev.view(torch.uint8), bad_dev.view(torch.uint8)] + ([maps_dev.view(torch.uint8).reshape(-1)] if host_maps is None else [])
+        back = torch.cat(parts).cpu().numpy()
+        bases = back[: 8 * (count + 1)].view(np.uint64).copy()
+        bad = back[8 * (count + 1): 8 * (count + 1) + 4 * count].view(np.int32)
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise MtqError(f"tensor {i} of the batch: {int(bad[i])} map codes are not MIXED_TILE_FORMATS codes 0..3 (bf16, bfp8, bfp4, bfp2)")
+        if host_maps is None:
+            host_maps = back[8 * (count + 1) + 4 * count:].view(np.int8).reshape(count, th, tw).copy()
+        arena = torch.empty((int(bases[count]) * 64,), dtype=torch.uint8, device=x3d.device)
+        hb.pack_tiles_batched(x3d, maps_dev, offsets_dev, bases_dev, arena)
+        batch = PackedBatch(count, rows, cols, arena, bases, maps_dev, offsets_dev, bases_dev)
+        out = []
+        for i in range(count):
+            a = host_maps[i]
+            offsets = offsets_of(a)
+            if int(offsets[-1]) != int(bases[i + 1] - bases[i]):
+                raise MtqError(f"tensor {i} of the batch: the device's offsets are not those of the map")
+            tables = hb.PackedTables(a, maps_dev[i], offsets_dev[i])
+            data = arena[int(bases[i]) * 64: int(bases[i + 1]) * 64]
+            out.append(PackedTensor(shapes[i], ("nd", shapes[i]), rows, cols, a, offsets, data, _tables=tables, _batch=(batch, i)))
+        return out
+    xf = x3d.detach().to("cpu").float().numpy() if _is_torch(x3d) else np.asarray(x3d, dtype=np.float32)
+    host_maps = _check_maps(maps.detach().to("cpu").numpy() if _is_torch(maps) else maps, count, rows, cols)
+    streams = [encode(xf[i], host_maps[i]) for i in range(count)]
+    bases = np.concatenate([[0], np.cumsum([int(o[-1]) for _d, o in streams])]).astype(np.uint64)
+    arena = np.concatenate([d for d, _o in streams])
+    batch = PackedBatch(count, rows, cols, arena, bases)
+    return [PackedTensor(shapes[i], ("nd", shapes[i]), rows, cols, host_maps[i], streams[i][1], arena[int(bases[i]) * 64: int(bases[i + 1]) * 64],
+                         _batch=(batch, i)) for i in range(count)]
+
+
+def unpack_batch(pts, backend: str = "emulation", dtype: str = "float32"):
+    """The inverse of pack_batch for a list it produced: the (count, rows, cols) reconstructions, float32 (bit for bit K3's) or bfloat16
+    (exact).  hip: one launch over the batch's arena → a device tensor (a list that is not one whole batch in order is unpacked tensor by
+    tensor, through the same kernels).  emulation: a loop over the NumPy decoder → a NumPy float32 array, or a torch CPU bfloat16 tensor."""
+    pts = list(pts)
+    if not pts:
+        raise MtqError("unpack_batch needs at least one packed tensor")
+    for pt in pts:
+        _check_layout(pt.layout)
+    if dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"dtype must be 'float32' or 'bfloat16', got {dtype!r}")
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    rows, cols = pts[0].rows, pts[0].cols
+    if any((pt.rows, pt.cols) != (rows, cols) for pt in pts):
+        raise MtqError("unpack_batch takes tensors of one 2-D shape")
+    import torch
+
+    if backend == "hip":
+        from . import hip_backend as hb
+
+        hb.require_gpu()
+        tdtype = torch.float32 if dtype == "float32" else torch.bfloat16
+        batch = batch_of(pts)
+        if batch is not None and batch.maps_dev is not None:
+            return hb.unpack_tiles_batched(batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, batch.count, rows, cols, tdtype)
+        return torch.stack([hb.unpack_tiles(_device_data(pt), pt.tables(), rows, cols, tdtype) for pt in pts])
+    bits = np.stack([decode(_host_data(pt), pt.map, pt.offsets, rows, cols) for pt in pts])
+    if dtype == "float32":
+        return bits.view(np.float32)
+    return torch.from_numpy((bits >> np.uint32(16)).astype(np.uint16).view(np.int16)).view(torch.bfloat16)
+
+
 def _packed_linear_class():
     import torch
 
@@ -433,3 +606,79 @@ def load(path) -> PackedTensor:
     if data.size != int(offsets[-1]) * 64:
         raise MtqError(f"{path}: the stream holds {data.size} bytes, its offsets say {int(offsets[-1]) * 64}")
     return PackedTensor(shape, info, rows, cols, amap, offsets, data, layout=layout)
+
+
+# ----------------------------------------------------------------------------- a directory of packed tensors
+
+INDEX_NAME = "index.json"
+
+
+def slug(name: str) -> str:
+    """The file-name form of a tensor's name: the one wq uses for a tensor's artifacts (cli._slug, restated here because importing the
+    CLI module has side effects on the process environment)."""
+    import re
+
+    return re.sub(r"[^a-zA-Z0-9._-]+", "_", name).strip("_") or "tensor"
+
+
+def save_dir(path, named: dict, meta=None, run=None) -> dict:
+    """{tensor name: PackedTensor} → `path`/<slug>.npz through save(), one file per tensor, and `path`/index.json: the format version and,
+    per tensor, its file, shape, counts, nbytes and total_bytes, with meta[name] (a dict of JSON values) merged in; run: a dict of JSON
+    values about the whole set (what made it), kept under "run".  Two names with one slug get distinct files.  Returns the index."""
+    import json
+    from pathlib import Path
+
+    root = Path(path)
+    root.mkdir(parents=True, exist_ok=True)
+    tensors, used = {}, set()
+    for name, pt in named.items():
+        base = slug(name)
+        stem, k = base, 1
+        while stem in used:
+            stem, k = f"{base}-{k}", k + 1
+        used.add(stem)
+        save(root / f"{stem}.npz", pt)
+        entry = {"file": f"{stem}.npz", "shape": [int(v) for v in pt.shape], "counts": pt.counts(), "nbytes": pt.nbytes, "total_bytes": pt.total_bytes}
+        extra = dict((meta or {}).get(name, {}))
+        clash = set(extra) & set(entry)
+        if clash:
+            raise MtqError(f"meta of {name!r} may not set {sorted(clash)}")
+        tensors[name] = {**entry, **extra}
+    index = {"format_version": FORMAT_VERSION, **({"run": dict(run)} if run else {}), "tensors": tensors}
+    (root / INDEX_NAME).write_text(json.dumps(index, indent=1) + "\n", encoding="utf-8")
+    return index
+
+
+def load_dir(path, device=None) -> dict:
+    """`path` as save_dir wrote it → {tensor name: PackedTensor}, each file checked against its index entry (an unknown format version, a
+    missing file, another shape or a stream of another length than the index says is refused).  device: a torch device the streams are
+    uploaded to."""
+    import json
+    from pathlib import Path
+
+    root = Path(path)
+    file = root / INDEX_NAME
+    if not file.exists():
+        raise MtqError(f"{file} is missing: not a directory of packed tensors")
+    index = json.loads(file.read_text(encoding="utf-8"))
+    version = index.get("format_version") if isinstance(index, dict) else None
+    if version != FORMAT_VERSION:
+        raise MtqError(f"{file}: packed format version {version}, this package reads version {FORMAT_VERSION}")
+    out = {}
+    for name, entry in index.get("tensors", {}).items():
+        f = root / str(entry.get("file"))
+        if not f.is_file():
+            raise MtqError(f"{f} is missing: {file} lists it for {name!r}")
+        pt = load(f)
+        if list(pt.shape) != list(entry.get("shape", [])):
+            raise MtqError(f"{f}: shape {pt.shape}, the index says {tuple(entry.get('shape', []))}")
+        if pt.nbytes != entry.get("nbytes"):
+            raise MtqError(f"{f}: the stream holds {pt.nbytes} bytes, the index says {entry.get('nbytes')}")
+        if pt.counts() != entry.get("counts"):
+            raise MtqError(f"{f}: the map's counts are not the index's")
+        if device is not None:
+            import torch
+
+            pt.data = torch.from_numpy(pt.data).to(device)
+        out[name] = pt
+    return out

@@ -1,0 +1,290 @@
+"""GPU: the batched packed kernels (csrc/mtq_packed.hip) and packed.pack_batch / unpack_batch on the hip backend.
+
+  * offsets: the device offsets of `count` random maps are packed.offsets_of per map and the bases the cumulative totals, exactly, at
+    tile counts on both sides of the workgroup's 256 threads and counts up to 300; a code outside 0..3 is counted for its tensor only;
+  * pack: the arena is the NumPy encoder's streams back to back, byte for byte, each slice is what the single-tensor kernel writes, for
+    float32 and bf16 storage, ragged edges, every uniform map and random maps, strided and row-pitched views on the scalar load path;
+    device maps give the arena host maps give; two calls give the same bytes;
+  * unpack: float32 is the oracle's reconstruction and K3's bit for bit, bf16 its upper halves; nothing outside rows × cols is stored;
+  * linear: both kernels on a pack_batch product give the bits they give on the tensor packed alone (the table slices, the alignment);
+  * bounds: an arena one blob short keeps the last blob out and everything before it right;
+  * scripts/pack_model.py on the hip backend writes what it writes on the emulation backend.
+"""
+from __future__ import annotations
+
+import functools
+import json
+
+import numpy as np
+import pytest
+import torch
+
+from quantization_analysis_amd import hip_backend as hb
+from quantization_analysis_amd import packed
+from tests.inputs import gen
+from tests.packed_cases import TILE_BYTES, expected_bits, random_map, specials, uniform_map
+from tests.test_packed_batch_host import ROOT, pack_model_script
+from tests.test_packed_gpu import bf16_valued_bits, dev
+
+pytestmark = pytest.mark.gpu
+FILL = 0xA5
+
+
+def _random_maps(count, shape, seed):
+    maps = np.stack([random_map(shape, seed + i) for i in range(count)])
+    flat = maps.reshape(count, -1)
+    if flat.shape[1] >= 4:
+        flat[0, :4] = [0, 1, 2, 3]                          # every code present
+    else:
+        flat[:, 0] = np.arange(count) % 4
+    return maps
+
+
+@functools.lru_cache(maxsize=None)
+def batches():
+    """(name, storage, float32 values (count, rows, cols), maps) — computed once, shared, never written to."""
+    out = []
+    x = np.stack([specials((70, 100), seed=11 + i) for i in range(3)])
+    out.append(("3x70x100-f32-specials", "f32", x, _random_maps(3, (70, 100), 50)))
+    x = np.stack([gen("heavy_bf16", 60 + i, (64, 96)) for i in range(4)])
+    out.append(("4x64x96-bf16", "bf16", x, _random_maps(4, (64, 96), 70)))
+    out.append(("3x70x100-bf16-specials", "bf16", bf16_valued_bits(np.stack([specials((70, 100), seed=21 + i) for i in range(3)])), _random_maps(3, (70, 100), 80)))
+    for code in range(4):
+        out.append((f"1x32x32-{hb.MIXED_TILE_FORMATS[code]}", "f32", gen("heavy_f32", 90 + code, (1, 32, 32)), uniform_map((32, 32), code)[None]))
+        out.append((f"3x70x100-{hb.MIXED_TILE_FORMATS[code]}", "f32", np.stack([specials((70, 100), seed=31 + i) for i in range(3)]),
+                    np.stack([uniform_map((70, 100), code)] * 3)))
+    for _n, _s, xv, maps in out:
+        xv.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def encoded(name):
+    """The NumPy encoder's streams of a batch, back to back, and their lengths."""
+    _n, _s, x, maps = next(b for b in batches() if b[0] == name)
+    singles = [packed.pack(x[i], maps[i], backend="emulation") for i in range(x.shape[0])]
+    arena = np.concatenate([s.data for s in singles])
+    arena.setflags(write=False)
+    return arena, [s.nbytes for s in singles]
+
+
+def _arena(pts) -> np.ndarray:
+    return packed.batch_of(pts).arena.cpu().numpy()
+
+
+# ----------------------------------------------------------------------------- offsets
+
+@pytest.mark.parametrize("count", [1, 3, 300])
+def test_device_offsets_equal_the_host_prefix_sums(count):
+    for tiles in (1, 63, 64, 65, 255, 256, 257, 1025, 4099):
+        maps = np.random.default_rng(1000 * count + tiles).integers(0, 4, size=(count, tiles)).astype(np.int8)
+        offsets, bases, bad = hb.packed_offsets_device(torch.from_numpy(maps).cuda(), count, tiles)
+        got = offsets.cpu().numpy().view(np.uint32)
+        assert got.shape == (count, tiles + 1)
+        want = np.stack([packed.offsets_of(maps[i]) for i in range(count)])
+        assert np.array_equal(got, want), (count, tiles, np.argwhere(got != want)[:4])
+        assert np.array_equal(want[0], hb.packed_offsets(maps[0]))                     # the host entry point's numbers
+        totals = want[:, -1].astype(np.uint64)
+        assert np.array_equal(bases.cpu().numpy().view(np.uint64), np.concatenate([[0], np.cumsum(totals)]).astype(np.uint64)), (count, tiles)
+        assert not bad.cpu().numpy().any()
+
+
+def test_bad_codes_are_counted_for_their_tensor_only():
+    x, maps = gen("normal_f32", 1, (5, 64, 96)), _random_maps(5, (64, 96), 7).copy()
+    maps[1, 1, 2] = 4
+    maps[3, 0, 0] = -1
+    md = torch.from_numpy(maps.reshape(5, -1)).cuda()
+    offsets, bases, bad = hb.packed_offsets_device(md, 5, 6)
+    assert list(bad.cpu().numpy()) == [0, 1, 0, 1, 0]
+    # such a tile counts 0 units; the others as ever
+    units = np.where((maps < 0) | (maps > 3), 0, np.asarray(TILE_BYTES)[np.clip(maps, 0, 3)] // 64).reshape(5, -1)
+    want = np.concatenate([np.zeros((5, 1), dtype=np.int64), np.cumsum(units, axis=1)], axis=1)
+    assert np.array_equal(offsets.cpu().numpy().view(np.uint32), want)
+    assert np.array_equal(bases.cpu().numpy(), np.concatenate([[0], np.cumsum(want[:, -1])]))
+    xd = torch.from_numpy(x).cuda()
+    with pytest.raises(hb.MtqError, match="tensor 1 of the batch: 1 map codes"):
+        packed.pack_batch(xd, md.reshape(5, 2, 3), backend="hip")                      # device maps: found on the device
+    with pytest.raises(hb.MtqError, match="tensor 1 of the batch"):
+        packed.pack_batch(xd, maps, backend="hip")                                     # host maps: found on the host
+    maps[1, 1, 2] = 2
+    with pytest.raises(hb.MtqError, match="tensor 3 of the batch: 1 map codes"):
+        packed.pack_batch(xd, torch.from_numpy(maps).cuda(), backend="hip")
+
+
+# ----------------------------------------------------------------------------- pack
+
+@pytest.mark.parametrize("name", [b[0] for b in batches()])
+def test_arena_is_the_encoders_streams_back_to_back(name):
+    _n, storage, x, maps = next(b for b in batches() if b[0] == name)
+    want, sizes = encoded(name)
+    count = x.shape[0]
+    xd = dev(x, storage)
+    pts = packed.pack_batch(xd, maps, backend="hip")
+    batch = packed.batch_of(pts)
+    g = _arena(pts)
+    assert g.size == want.size == 64 * int(batch.bases[count]) and batch.arena.dtype == torch.uint8
+    diff = np.flatnonzero(g != want)
+    assert diff.size == 0, (name, diff[:8], g[diff[:8]], want[diff[:8]])
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    assert np.array_equal(batch.bases.astype(np.int64) * 64, starts)
+    for i, pt in enumerate(pts):
+        assert pt.on_device and pt.data.data_ptr() == batch.arena.data_ptr() + starts[i] and pt.data.data_ptr() % 64 == 0 and pt.nbytes == sizes[i]
+        assert np.array_equal(pt.map, maps[i]) and np.array_equal(pt.offsets, packed.offsets_of(maps[i])) and pt.shape == x.shape[1:]
+        alone = hb.pack_tiles(xd[i], hb.PackedTables.on_device(maps[i]))
+        assert torch.equal(pt.data, alone), (name, i)                                   # the single-tensor kernel's bytes
+        assert pt.tables().nbytes == sizes[i] and pt.tables().map_dev.data_ptr() == batch.maps_dev[i].data_ptr()      # slices, no second upload
+    from_device = packed.pack_batch(xd, torch.from_numpy(maps).cuda(), backend="hip")
+    assert np.array_equal(_arena(from_device), g), name
+    assert all(np.array_equal(a.map, b.map) and np.array_equal(a.offsets, b.offsets) for a, b in zip(from_device, pts))
+    # two calls, the same bytes, whatever the arena held before: every byte is written
+    again = torch.full((g.size,), FILL, dtype=torch.uint8, device="cuda")
+    hb.pack_tiles_batched(xd, batch.maps_dev, batch.offsets_dev, batch.bases_dev, again)
+    assert np.array_equal(again.cpu().numpy(), g), name
+
+
+@pytest.mark.parametrize("storage", ["f32", "bf16"])
+def test_views_are_read_in_place_on_the_scalar_path(storage):
+    count, rows, cols = 3, 70, 100
+    x = np.stack([specials((rows, cols), seed=41 + i) for i in range(2 * count)])
+    x = x if storage == "f32" else bf16_valued_bits(x)
+    maps = _random_maps(count, (rows, cols), 90)
+    want = np.concatenate([packed.pack(x[2 * i], maps[i], backend="emulation").data for i in range(count)])
+    esz = 4 if storage == "f32" else 2
+    # [::2] of a buffer that starts one element past an aligned address: no matrix is 16-byte aligned
+    flat = torch.zeros(x.size + 8, dtype=dev(x[:1], storage).dtype, device="cuda")
+    flat[1: 1 + x.size] = dev(x, storage).reshape(-1)
+    view = flat[1: 1 + x.size].view(2 * count, rows, cols)[::2]
+    assert view.data_ptr() % 16 == esz and view.stride(0) == 2 * rows * cols and not view.is_contiguous()
+    assert np.array_equal(_arena(packed.pack_batch(view, maps, backend="hip")), want), storage
+    # the same view at an aligned address: the vector path with a matrix stride
+    aligned = dev(x, storage)[::2]
+    assert aligned.data_ptr() % 16 == 0
+    assert np.array_equal(_arena(packed.pack_batch(aligned, maps, backend="hip")), want), storage
+    # a row-pitched view of a wider buffer whose rows start at no aligned address
+    wide = torch.zeros((count, rows + 3, cols + 9), dtype=flat.dtype, device="cuda")
+    wide[:, 1: 1 + rows, 2: 2 + cols] = dev(x[::2], storage)
+    pitched = wide[:, 1: 1 + rows, 2: 2 + cols]
+    assert pitched.stride(1) == cols + 9 and pitched.stride(0) == (rows + 3) * (cols + 9) and pitched.data_ptr() % 16 != 0
+    assert np.array_equal(_arena(packed.pack_batch(pitched, maps, backend="hip")), want), storage
+
+
+# ----------------------------------------------------------------------------- unpack
+
+@pytest.mark.parametrize("name", ["3x70x100-f32-specials", "4x64x96-bf16", "3x70x100-bf16-specials", "1x32x32-bfp4", "3x70x100-bfp2"])
+def test_unpack_batch_is_the_reconstruction_bit_for_bit(name):
+    _n, storage, x, maps = next(b for b in batches() if b[0] == name)
+    count, rows, cols = x.shape
+    xd = dev(x, storage)
+    pts = packed.pack_batch(xd, maps, backend="hip")
+    y = packed.unpack_batch(pts, backend="hip")
+    assert y.dtype == torch.float32 and tuple(y.shape) == x.shape
+    yb = y.cpu().numpy().view(np.uint32)
+    for i in range(count):
+        want = expected_bits(x[i], maps[i])
+        assert np.array_equal(yb[i], want), (name, i, np.argwhere(yb[i] != want)[:4])
+        assert np.array_equal(hb.apply_assignment(xd[i], maps[i]).cpu().numpy().view(np.uint32), want), (name, i)      # K3
+        assert np.array_equal(packed.unpack(pts[i], backend="hip").cpu().numpy().view(np.uint32), want), (name, i)     # the slice alone
+    half = packed.unpack_batch(pts, backend="hip", dtype="bfloat16")
+    assert half.dtype == torch.bfloat16
+    assert np.array_equal(half.view(torch.int16).cpu().numpy().view(np.uint16).astype(np.uint32) << np.uint32(16), yb), name
+    # a list that is not the whole batch in order goes tensor by tensor, to the same bits
+    assert np.array_equal(packed.unpack_batch(pts[::-1], backend="hip").cpu().numpy().view(np.uint32), yb[::-1]), name
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_unpack_stores_nothing_outside_the_matrices(dtype):
+    _n, storage, x, maps = next(b for b in batches() if b[0] == "3x70x100-f32-specials")
+    count, rows, cols = x.shape
+    pts = packed.pack_batch(dev(x, storage), maps, backend="hip")
+    b = packed.batch_of(pts)
+    want = packed.unpack_batch(pts, backend="hip", dtype="float32" if dtype == torch.float32 else "bfloat16")
+    for r0, c0 in ((0, 0), (1, 3)):                                                       # the vector stores, and a pitched odd start
+        big = torch.full((count, rows + 7, cols + 12), -7.0, dtype=dtype, device="cuda")
+        out = big[:, r0: r0 + rows, c0: c0 + cols]
+        hb.unpack_tiles_batched(b.arena, b.maps_dev, b.offsets_dev, b.bases_dev, count, rows, cols, dtype, out=out)
+        ints = torch.int32 if dtype == torch.float32 else torch.int16
+        assert torch.equal(out.contiguous().view(ints), want.view(ints))
+        outside = torch.ones_like(big, dtype=torch.bool)
+        outside[:, r0: r0 + rows, c0: c0 + cols] = False
+        assert bool((big[outside] == -7.0).all()), (dtype, r0, c0)
+
+
+# ----------------------------------------------------------------------------- the tensors of a batch are full citizens
+
+def test_linear_on_a_batch_product_is_linear_on_the_tensor_alone(tmp_path):
+    w = np.stack([gen("heavy_bf16", 3 + i, (70, 100)) for i in range(2)])
+    maps = _random_maps(2, (70, 100), 6)
+    wd = dev(w, "bf16")
+    pts = packed.pack_batch(wd, maps, backend="hip")
+    x = dev(gen("normal_bf16", 4, (5, 100)) * 64, "bf16")
+    bias = torch.from_numpy(gen("normal_f32", 5, (70,))).cuda()
+    for i, pt in enumerate(pts):
+        alone = packed.pack(wd[i], maps[i], backend="hip")
+        for kernel, kw in (("block", {}), ("skinny", {}), ("skinny", {"split": 1}), ("skinny", {"split": 3})):
+            for out_dtype in ("float32", "bfloat16"):
+                got = packed.linear(x, pt, bias=bias, out_dtype=out_dtype, kernel=kernel, **kw)
+                want = packed.linear(x, alone, bias=bias, out_dtype=out_dtype, kernel=kernel, **kw)
+                ints = torch.int32 if out_dtype == "float32" else torch.int16
+                assert torch.equal(got.view(ints), want.view(ints)), (i, kernel, kw, out_dtype)
+        layer = packed.PackedLinear(pt, bias=bias)
+        assert torch.equal(layer(x).view(torch.int32), packed.linear(x, alone, bias=bias, kernel="auto").view(torch.int32))
+        packed.save(tmp_path / f"{i}.npz", pt)
+        back = packed.load(tmp_path / f"{i}.npz")
+        assert np.array_equal(back.data, alone.data.cpu().numpy()) and np.array_equal(back.map, maps[i])
+    packed.save_dir(tmp_path / "d", {"a/0": pts[0], "a.1": pts[1]})
+    loaded = packed.load_dir(tmp_path / "d", device="cuda")
+    assert list(loaded) == ["a/0", "a.1"] and all(pt.on_device for pt in loaded.values())
+    assert torch.equal(packed.linear(x, loaded["a.1"], bias=bias).view(torch.int32), packed.linear(x, pts[1], bias=bias).view(torch.int32))
+
+
+# ----------------------------------------------------------------------------- bounds
+
+def test_an_arena_one_blob_short_keeps_the_last_blob_out():
+    """Not a fault: the kernel checks every blob against the arena's length itself."""
+    _n, storage, x, maps = next(b for b in batches() if b[0] == "3x70x100-f32-specials")
+    want, _sizes = encoded("3x70x100-f32-specials")
+    count, tiles = x.shape[0], maps[0].size
+    last = TILE_BYTES[int(maps[-1].reshape(-1)[-1])]
+    md = torch.from_numpy(maps.reshape(count, tiles)).cuda()
+    offsets, bases, _bad = hb.packed_offsets_device(md, count, tiles)
+    arena = torch.full((want.size,), FILL, dtype=torch.uint8, device="cuda")
+    assert want.size - last >= count * tiles * TILE_BYTES[3]                              # the entry's own lower bound still holds
+    hb.pack_tiles_batched(dev(x, storage), md, offsets, bases, arena[: want.size - last])
+    g = arena.cpu().numpy()
+    assert np.array_equal(g[: want.size - last], want[: want.size - last])
+    assert np.all(g[want.size - last:] == FILL)
+    # and one byte short of that blob is as short: nothing of it is written
+    arena.fill_(FILL)
+    hb.pack_tiles_batched(dev(x, storage), md, offsets, bases, arena[: want.size - 1])
+    g = arena.cpu().numpy()
+    assert np.array_equal(g[: want.size - last], want[: want.size - last]) and np.all(g[want.size - last:] == FILL)
+    # unpack of the short arena stores nothing for that tile
+    y = torch.full(x.shape, -7.0, dtype=torch.float32, device="cuda")
+    arena[: want.size] = torch.from_numpy(np.array(want)).cuda()
+    hb.unpack_tiles_batched(arena[: want.size - last], md, offsets, bases, count, x.shape[1], x.shape[2], out=y)
+    yb = y.cpu().numpy()
+    full = np.stack([expected_bits(x[i], maps[i]) for i in range(count)])
+    in_last = np.zeros(x.shape, dtype=bool)
+    in_last[-1, 64:, 96:] = True                                                          # tile (2, 3) of the last tensor
+    assert np.array_equal(yb.view(np.uint32)[~in_last], full[~in_last]) and np.all(yb[in_last] == -7.0)
+
+
+# ----------------------------------------------------------------------------- the script
+
+@pytest.mark.parametrize("config", ["greedy_seed123.json", "compression_config.mixed_tile_threshold.example.json"], ids=["greedy", "threshold"])
+def test_pack_model_on_hip_writes_what_the_emulation_writes(tmp_path, capsys, config):
+    script = pack_model_script()
+    cfg = str(ROOT / "compression_configs" / config)
+    assert script.main(["synthetic:tiny", "--compression-config", cfg, "--out-dir", str(tmp_path / "hip"), "--backend", "hip", "--verify"]) == 0
+    text = capsys.readouterr().out
+    assert "verify: ok (5 tensors" in text and "MISMATCH" not in text
+    assert script.main(["synthetic:tiny", "--compression-config", cfg, "--out-dir", str(tmp_path / "emu"), "--backend", "emulation", "--verify"]) == 0
+    hip, emu = packed.load_dir(tmp_path / "hip"), packed.load_dir(tmp_path / "emu")
+    assert list(hip) == list(emu) and len(hip) == 5
+    for name in hip:
+        a, b = hip[name], emu[name]
+        assert a.shape == b.shape and np.array_equal(a.map, b.map) and np.array_equal(a.offsets, b.offsets) and np.array_equal(a.data, b.data), name
+    index = json.loads((tmp_path / "hip" / "index.json").read_text())
+    routes = {name: e["route"] for name, e in index["tensors"].items()}
+    assert routes["model.layers.0.norm.weight"] == "per-tensor" and sorted(routes.values()).count("batched") == 4      # the vector alone goes one by one
+    assert all(e["verified"] is True for e in index["tensors"].values())
