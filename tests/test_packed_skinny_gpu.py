@@ -29,6 +29,7 @@ from tests.packed_cases import expected_bits, random_map, uniform_map
 pytestmark = pytest.mark.gpu
 GRID = 2.0 ** -8
 SPLITS = (0, 1, 2, 5, 9)
+MAPS = ("random", "0", "1", "2", "3")
 
 
 def _what(w: np.ndarray, amap: np.ndarray) -> np.ndarray:
@@ -59,34 +60,40 @@ def _grid_weight(n, k, which):
     return packed.pack(w, amap, backend="hip"), what, b
 
 
+def grid_case_is_exact(m, n, k, splits=SPLITS, maps=MAPS):
+    """The integer-grid case (m, n, k) under every map of `maps` and every split of `splits` (tests/test_packed_long_k_gpu.py runs it
+    at long K)."""
+    x = np.random.default_rng(1000 * m + 10 * n + k).integers(-4, 5, size=(m, k)).astype(np.float32)
+    assert np.all(np.abs(x) <= 4) and np.array_equal(x, np.round(x))
+    xd = _x_dev(x)
+    for which in maps:
+        pt, what, b = _grid_weight(n, k, which)
+        b64 = b.astype(np.float64)
+        worst = (np.abs(x).astype(np.float64) @ np.abs(what).T + np.abs(b64)[None, :]) / GRID
+        assert worst.max() < 2.0 ** 24                             # every partial sum is exact in f32, in any order
+        want = x.astype(np.float64) @ what.T + b64[None, :]
+        assert np.array_equal(want.astype(np.float32).astype(np.float64), want)
+        bd = torch.from_numpy(b.copy()).cuda()
+        block = packed.linear(xd, pt, bias=bd)
+        block_nob = packed.linear(xd, pt)
+        want_bf16 = torch.from_numpy(want.astype(np.float32)).to(torch.bfloat16)
+        for split in splits:
+            y = packed.linear(xd, pt, bias=bd, kernel="skinny", split=split)
+            got = y.cpu().numpy()
+            assert got.shape == (m, n) and got.dtype == np.float32
+            assert np.array_equal(got.astype(np.float64), want), (m, n, k, which, split, np.argwhere(got != want)[:4])
+            nob = packed.linear(xd, pt, kernel="skinny", split=split)
+            assert np.array_equal(nob.cpu().numpy().astype(np.float64), want - b64[None, :]), (m, n, k, which, split)
+            yb = packed.linear(xd, pt, bias=bd, kernel="skinny", split=split, out_dtype="bfloat16")
+            assert yb.dtype == torch.bfloat16 and np.array_equal(_bits(yb), _bits(want_bf16)), (m, n, k, which, split)
+            assert np.array_equal(_bits(y), _bits(block)) and np.array_equal(_bits(nob), _bits(block_nob)), (m, n, k, which, split)
+
+
 @pytest.mark.parametrize("m", [1, 5, 16, 17, 32])
 def test_skinny_integer_grid_is_exact(m):
     for n in (64, 70):
         for k in (64, 100, 160):
-            x = np.random.default_rng(1000 * m + 10 * n + k).integers(-4, 5, size=(m, k)).astype(np.float32)
-            assert np.all(np.abs(x) <= 4) and np.array_equal(x, np.round(x))
-            xd = _x_dev(x)
-            for which in ("random", "0", "1", "2", "3"):
-                pt, what, b = _grid_weight(n, k, which)
-                b64 = b.astype(np.float64)
-                worst = (np.abs(x).astype(np.float64) @ np.abs(what).T + np.abs(b64)[None, :]) / GRID
-                assert worst.max() < 2.0 ** 24                             # every partial sum is exact in f32, in any order
-                want = x.astype(np.float64) @ what.T + b64[None, :]
-                assert np.array_equal(want.astype(np.float32).astype(np.float64), want)
-                bd = torch.from_numpy(b.copy()).cuda()
-                block = packed.linear(xd, pt, bias=bd)
-                block_nob = packed.linear(xd, pt)
-                want_bf16 = torch.from_numpy(want.astype(np.float32)).to(torch.bfloat16)
-                for split in SPLITS:
-                    y = packed.linear(xd, pt, bias=bd, kernel="skinny", split=split)
-                    got = y.cpu().numpy()
-                    assert got.shape == (m, n) and got.dtype == np.float32
-                    assert np.array_equal(got.astype(np.float64), want), (m, n, k, which, split, np.argwhere(got != want)[:4])
-                    nob = packed.linear(xd, pt, kernel="skinny", split=split)
-                    assert np.array_equal(nob.cpu().numpy().astype(np.float64), want - b64[None, :]), (m, n, k, which, split)
-                    yb = packed.linear(xd, pt, bias=bd, kernel="skinny", split=split, out_dtype="bfloat16")
-                    assert yb.dtype == torch.bfloat16 and np.array_equal(_bits(yb), _bits(want_bf16)), (m, n, k, which, split)
-                    assert np.array_equal(_bits(y), _bits(block)) and np.array_equal(_bits(nob), _bits(block_nob)), (m, n, k, which, split)
+            grid_case_is_exact(m, n, k)
 
 
 def _one_hot_mismatches(n, k, s, seed, split, corrupt=False):
@@ -118,8 +125,8 @@ def test_skinny_one_hot_fails_on_a_wrong_image(split):
     assert [tuple(r) for r in bad] == [(5, 0)]          # Y[k = 5, n = 0] alone
 
 
-@pytest.mark.parametrize("m,n,k", [(1, 70, 100), (17, 130, 200), (32, 70, 160)])
-def test_skinny_random_is_within_the_f32_accumulation_bound(m, n, k):
+def random_case_is_within_the_bound(m, n, k):
+    """Random values at (m, n, k): the bound, both X layouts, splits 0, 1 and 3, repeatability, the workspace's contents, a pitched Y."""
     w = gen("heavy_f32", 60 + m, (n, k))
     x = to_bf16_valued(gen("normal_f32", 61 + m, (m, k)) * 40)
     b = gen("normal_f32", 62 + m, (n,))
@@ -161,6 +168,11 @@ def test_skinny_random_is_within_the_f32_accumulation_bound(m, n, k):
         hb.packed_linear_skinny(_x_dev(x), pt.data, tables, n, split=2, workspace=torch.empty(15, dtype=torch.uint8, device="cuda"))
 
 
+@pytest.mark.parametrize("m,n,k", [(1, 70, 100), (17, 130, 200), (32, 70, 160)])
+def test_skinny_random_is_within_the_f32_accumulation_bound(m, n, k):
+    random_case_is_within_the_bound(m, n, k)
+
+
 @pytest.mark.parametrize("fmt,mant", [("bfp8", 7), ("bfp4", 3), ("bfp2", 1)])
 def test_skinny_decode_is_the_reference_decode_for_every_exponent_and_code(fmt, mant):
     got, want = (t.cpu().numpy().view(np.uint32) for t in hb.debug_packed_decode(fmt))
@@ -200,6 +212,6 @@ def test_routing_and_the_module():
         y = layer(x3)
         assert tuple(y.shape) == (2, 3, n) and y.is_cuda and not y.requires_grad
         assert np.array_equal(_bits(y.reshape(6, n)), _bits(packed.linear(x33[:6], pt, bias=bd, out_dtype=out_dtype, kernel="auto")))
-        assert np.array_equal(_bits(layer(x3)), _bits(y))                                   # the kept workspace, used again
+        assert np.array_equal(_bits(layer(x3)), _bits(y))                                   # k = 160 needs no workspace: test_packed_long_k_gpu.py has a kept one
         big = layer(x33)                                                                     # m = 33: the block kernel
         assert np.array_equal(_bits(big), _bits(packed.linear(x33, pt, bias=bd, out_dtype=out_dtype)))
