@@ -694,6 +694,38 @@ size_t mtq_packed_linear_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k,
 int mtq_packed_linear_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                              const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
                              void *workspace, size_t workspace_bytes, void *stream);
+/* The grouped form: `count` experts of one (n, k) shape in ONE arena (the batch entries' maps / offsets / bases), each multiplied with
+ * its own rows of x, in one launch: y[rows of group e] = x[rows of group e] · Ŵ[e]ᵀ (+ bias[e]).
+ *
+ * group_rows is a DEVICE array of count + 1 int32: group e owns rows [group_rows[e], group_rows[e + 1]) of x and of y (both
+ * total_rows rows).  The kernels clamp before any use, r0 = clamp(group_rows[e], 0, total_rows), r1 = clamp(group_rows[e + 1], r0,
+ * total_rows): whatever the array holds, no row at or past total_rows is read or written.  A group without rows reads nothing of its
+ * expert.  Rows of y that belong to no group are not written.  Nondecreasing group_rows give disjoint groups, and then the same inputs
+ * and the same split give the same bits.  An array that decreases can clamp to groups that OVERLAP: several waves then write the
+ * overlapped rows of y (and of the workspace) without an order among them, so the values left in those rows are unspecified - inside
+ * the allocation, and every other row as stated.  Group e reads maps[e * tiles ..], offsets[e * (tiles + 1) ..] and the
+ * stream at byte 64 * bases[e]; a blob is checked on the device against its group's own stream [64 * bases[e], 64 * bases[e + 1]) and
+ * against packed_bytes and reads as zeros when it passes either, as does a tile whose map code is outside 0..3.
+ *
+ * One wave per (slice, group, tile row); a group above 32 rows is walked in chunks of 32 rows by the same wave, which reads the weight
+ * again for every chunk: the entry is for decode-sized groups, and mtq_packed_linear per expert is the route for large m.  For every
+ * group and every 32-row chunk of it the result is bit for bit what mtq_packed_linear_skinny gives for that chunk and that expert's
+ * stream and tables at the same effective split.  An effective split above 1 writes f32 partials to workspace[slice][total_rows][n]
+ * with plain stores and a second kernel on `stream` sums them in ascending slice order, adds the group's bias last and rounds a bf16 y
+ * once; it writes only rows inside a clamped group.  No atomics, no counters, no waiting between workgroups; nothing in the workspace
+ * needs initialising.  split 0 is the library's choice: the single-tensor rule with count * tiles_h tile rows (for count == 1 the same
+ * split).  bias: NULL, or count rows of n floats at pitch ldb.
+ *
+ * Arguments are checked as for the skinny entry (null pointers, total_rows, count, n, k positive, the tile grid, a negative split, an
+ * arena below 320 bytes per tile or not 16-byte aligned, a workspace that is null, misaligned or too small when the size function's
+ * answer is nonzero): MTQ_ERR_INVALID before a device is looked for. */
+/* HOST function: bytes of workspace for (total_rows, count, n, k, split): 0 when the effective split is 1, else
+ * split_eff * total_rows * n * 4 rounded up to 16.  MTQ_ERR_INVALID arguments give (size_t)-1. */
+size_t mtq_packed_linear_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split);
+int mtq_packed_linear_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows, const void *packed,
+                                     size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, int64_t count,
+                                     int64_t n, const float *bias, int64_t ldb, void *y, int out_dtype, int64_t ldy, int split,
+                                     void *workspace, size_t workspace_bytes, void *stream);
 /* Test hook: the skinny kernel's decode (a cheaper form of the block kernel's for exponent bytes M..254, the same code elsewhere)
  * beside the reference decode, for fmt MTQ_FMT_BFP8 / BFP4 / BFP2.  got, want: device uint32 [16][256][16][16] = [rot][E][q][i], the
  * float32 word of code (16 q + (i + rot) % 16) mod 2^(M + 1) at element i of a group with exponent byte E: every (E, code) at every

@@ -17,6 +17,9 @@
 //       its exponent byte and its code bytes and decodes them into the bf16 LDS image (every BFP value has its low 16 bits zero: the
 //       image is exact), X goes to LDS beside it, mfma_f32_32x32x16_bf16 accumulates in f32.  One accumulator, one K order per output,
 //       no atomics: the same inputs give the same bits.
+//   packed_linear_skinny_kernel               the same product for m <= 32: one wave per (K slice, tile row), W straight to registers.
+//   packed_linear_skinny_grouped_kernel       that wave's work for every expert of an arena over the expert's own rows of X, one launch:
+//       for decode-sized groups (a group above 32 rows is walked in chunks and re-reads W; the block kernel is the route for large m).
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
 // blob does not fit is not written (pack), not stored (unpack) or read as zeros (linear).
@@ -726,6 +729,162 @@ size_t skinny_workspace(int64_t m, int64_t n, int split_eff)
     return split_eff <= 1 ? 0 : (((size_t)split_eff * (size_t)m * (size_t)n * sizeof(float) + 15) & ~(size_t)15);
 }
 
+// ---- grouped skinny linear: the experts of one arena (pack_tiles_batched's tables), each over its own rows of X, in one launch.
+//
+// A unit is (slice s, group e, tile row tr), numbered ((s * count + e) * tiles_h + tr): the four waves of a workgroup share a slice of X
+// and, but for a seam, an expert.  Group e owns rows [group_rows[e], group_rows[e + 1]) of X and Y, clamped into [0, T] before any use; a
+// group without rows returns before its first load.  The wave walks its rows in chunks of 32 and does on each chunk exactly what
+// packed_linear_skinny_kernel does for an m <= 32 call on that chunk and that expert at the same split: the same readlane hand-out, ring,
+// decode and two MFMAs per tile in ascending K, so the bits are those of that call.  W is read again for every chunk: the entry is for
+// decode-sized groups, and mtq_packed_linear per expert stays the route for a group of hundreds of rows.
+// A blob is checked (wave-uniformly) against its group's own stream [64 bases[e], 64 bases[e + 1]) and against packed_bytes before it is
+// touched; all sizes are multiples of 64, so the check is made in units.
+struct GroupRows {
+    int64_t r0, r1;
+};
+
+__device__ __forceinline__ GroupRows group_rows_of(const int32_t *__restrict__ group_rows, int64_t e, int64_t T)
+{
+    GroupRows g;
+    g.r0 = std::min<int64_t>(std::max<int64_t>(group_rows[e], 0), T);
+    g.r1 = std::min<int64_t>(std::max<int64_t>(group_rows[e + 1], g.r0), T);
+    return g;
+}
+
+template <bool BF16OUT>
+__global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_linear_skinny_grouped_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
+    const uint8_t *__restrict__ packed, uint64_t packed_bytes, const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets,
+    const uint64_t *__restrict__ bases, int count, int N, int tiles_h, int tiles_w, int split, const float *__restrict__ bias, int64_t ldb,
+    void *__restrict__ yv, int64_t ldy, float *__restrict__ ws)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= (int64_t)tiles_h * count * split) return;   // wave-uniform; the kernel has no barrier
+    const int64_t tr = unit % tiles_h, se = unit / tiles_h, e = se % count, s = se / count;
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    if (gr.r1 == gr.r0) return;                      // nothing of this expert is read
+    const int64_t tiles = (int64_t)tiles_h * tiles_w;
+    const int8_t *map = maps + e * tiles;
+    const uint32_t *off = offsets + e * (tiles + 1);
+    const uint64_t base = bases[e], limit = std::min<uint64_t>(bases[e + 1], packed_bytes / kUnit);   // units
+    const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
+
+    for (int64_t row0 = gr.r0; row0 < gr.r1; row0 += kTile) {
+        int lv = lane;
+        asm volatile("" : "+v"(lv));                 // the lane's addresses are formed per chunk, not kept in registers across chunks
+        const int row = lv & 31, half = lv >> 5, gi = 2 * row + half;
+        const int64_t n = tr * kTile + row;
+        const int64_t M = std::min<int64_t>(kTile, gr.r1 - row0);
+        const uint16_t *xc = x + row0 * ldx;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+
+        for (int64_t cb = c0; cb < c1; cb += 64) {
+            const int cnt = (int)std::min<int64_t>(64, c1 - cb);
+            int mf = -1, mo = 0;                     // lane i: map code and offset of tile cb + i
+            if (lane < cnt) {
+                const int64_t t = tr * tiles_w + cb + lane;
+                mf = map[t];
+                mo = (int)off[t];
+            }
+            for (int b = 0; b < cnt; b += kSkinnyRing) {
+                GroupRaw g[kSkinnyRing];
+                uint4 xl[kSkinnyRing], xh[kSkinnyRing];
+#pragma unroll
+                for (int j = 0; j < kSkinnyRing; ++j) {
+                    const int i = b + j;             // uniform
+                    TileAt a;
+                    a.off = 0;
+                    a.f = -1;
+                    xl[j] = make_uint4(0u, 0u, 0u, 0u);
+                    xh[j] = xl[j];
+                    if (i < cnt) {
+                        const int f = __builtin_amdgcn_readlane(mf, i);
+                        const uint64_t at = base + (uint32_t)__builtin_amdgcn_readlane(mo, i);   // base <= limit < 2^58 where it counts
+                        const uint32_t size = packed_tile_bytes(f);
+                        a.off = at * kUnit;
+                        a.f = (size == 0u || base > limit || at + size / kUnit > limit) ? -1 : f;
+                        load_x16(xc, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
+                    }
+                    load_group(packed, a, gi, g[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < kSkinnyRing; ++j) {
+                    if (b + j < cnt) {
+                        uint32_t y[kGroup];
+                        decode_skinny(g[j], y);
+                        uint4 lo, hi;
+                        pack_halves(y, lo, hi);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(lo), acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(hi), acc, 0, 0, 0);
+                    }
+                }
+            }
+        }
+
+        // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row): the lane's own part of the address first, so that what
+        // varies with r is uniform
+        if (n < N) {
+            const int64_t mh = row0 + 4 * half;
+            if (split == 1) {
+                const float bv = bias ? bias[e * ldb + n] : 0.0f;
+                const int64_t at = mh * ldy + n;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int mu = (r & 3) + 8 * (r >> 2);
+                    if (mu + 4 * half < M) store_y<BF16OUT>(yv, at + mu * ldy, acc[r] + bv);
+                }
+            } else {
+                float *wl = ws + (s * T + mh) * N + n;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int mu = (r & 3) + 8 * (r >> 2);
+                    if (mu + 4 * half < M) wl[mu * N] = acc[r];
+                }
+            }
+        }
+    }
+}
+
+// One workgroup per (group e, 256 columns): thread n walks the group's clamped rows, so only rows inside a clamped group are written,
+// whatever group_rows holds.  Per output: ((p0 + p1) + ... + p_{split-1}) + b[e], as skinny_reduce_kernel.
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void skinny_grouped_reduce_kernel(const float *__restrict__ ws, int64_t T, int64_t N, int split,
+                                                                    const int32_t *__restrict__ group_rows, int64_t nchunks,
+                                                                    const float *__restrict__ bias, int64_t ldb, void *__restrict__ yv, int64_t ldy)
+{
+    const int64_t e = blockIdx.x / nchunks, n = (blockIdx.x % nchunks) * 256 + threadIdx.x;
+    if (n >= N) return;
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    if (gr.r1 == gr.r0) return;
+    const float bv = bias ? bias[e * ldb + n] : 0.0f;
+    for (int64_t m = gr.r0; m < gr.r1; ++m) {
+        float v = ws[m * N + n];
+        for (int s = 1; s < split; ++s) v += ws[((int64_t)s * T + m) * N + n];
+        v += bv;
+        store_y<BF16OUT>(yv, m * ldy + n, v);
+    }
+}
+
+// skinny_shape for the grouped entry: skinny_split's rule with count * tiles_h tile rows, which for count == 1 is that rule.
+int grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *tiles_h, int64_t *tiles_w, int *split_eff)
+{
+    if (total_rows <= 0) return fail(MTQ_ERR_INVALID, "total_rows must be positive (empty operands are handled by the caller)");
+    if (total_rows > INT32_MAX) return fail(MTQ_ERR_INVALID, "total_rows does not fit the 32-bit group_rows");
+    if (count <= 0) return fail(MTQ_ERR_INVALID, "count must be positive");
+    if (count > INT32_MAX) return fail(MTQ_ERR_INVALID, "count does not fit 32 bits");
+    if (split < 0) return fail(MTQ_ERR_INVALID, "split must not be negative (0: the library's choice)");
+    if (int rc = tile_grid(n, k, tiles_h, tiles_w)) return rc;
+    if (*tiles_h * *tiles_w > MTQ_PACKED_BATCH_MAX_TILES) return fail(MTQ_ERR_INVALID, "too many tiles: a tensor's stream must fit 32-bit units");
+    if (count > ((int64_t)1 << 40) / (*tiles_h * *tiles_w)) return fail(MTQ_ERR_INVALID, "too many tiles in the batch");
+    const int64_t own = std::max<int64_t>(1, std::min(kSkinnyUnits / (count * *tiles_h), *tiles_w / kSkinnyMinRun));
+    *split_eff = (int)std::min<int64_t>(split == 0 ? own : split, *tiles_w);
+    if (*split_eff > 1 && total_rows > ((int64_t)1 << 56) / n / *split_eff) return fail(MTQ_ERR_INVALID, "the workspace of this split is too large");
+    return MTQ_OK;
+}
+
 int tile_grid(int64_t rows, int64_t cols, int64_t *tiles_h, int64_t *tiles_w)
 {
     if (rows <= 0 || cols <= 0) return fail(MTQ_ERR_INVALID, "rows and cols must be positive (empty tensors are handled by the caller)");
@@ -974,6 +1133,63 @@ extern "C" int mtq_packed_linear_skinny(const void *x, int64_t m, int64_t k, int
             hipLaunchKernelGGL(skinny_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
     }
     return check_launch("mtq_packed_linear_skinny");
+}
+
+extern "C" size_t mtq_packed_linear_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    int64_t th, tw;
+    int eff;
+    if (grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
+    return skinny_workspace(total_rows, n, eff);
+}
+
+extern "C" int mtq_packed_linear_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                                const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                                int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!x || !group_rows || !packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    int eff;
+    if (int rc = grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if (bias && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
+    const size_t need = skinny_workspace(total_rows, n, eff);
+    if (need != 0) {
+        if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and this split needs one");
+        if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
+        if (workspace_bytes < need)
+            return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this split needs", workspace_bytes, need);
+    }
+    const int64_t blocks = (count * th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    const int64_t nchunks = (n + 255) / 256;
+    if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    float *ws = static_cast<float *>(workspace);
+    const dim3 grid((unsigned)blocks), block(64 * kSkinnyWaves);
+    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(packed_linear_skinny_grouped_kernel<true>, grid, block, 0, st, xp, total_rows, k, ldx, x_vec, group_rows, pp,
+                           (uint64_t)packed_bytes, maps, offsets, bases, count, n, th, tw, eff, bias, ldb, y, ldy, ws);
+    else
+        hipLaunchKernelGGL(packed_linear_skinny_grouped_kernel<false>, grid, block, 0, st, xp, total_rows, k, ldx, x_vec, group_rows, pp,
+                           (uint64_t)packed_bytes, maps, offsets, bases, count, n, th, tw, eff, bias, ldb, y, ldy, ws);
+    if (eff > 1) {
+        if (int rc = check_launch("mtq_packed_linear_skinny_grouped")) return rc;
+        const dim3 rgrid((unsigned)(count * nchunks));
+        if (out_dtype == MTQ_DTYPE_BF16)
+            hipLaunchKernelGGL(skinny_grouped_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
+        else
+            hipLaunchKernelGGL(skinny_grouped_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
+    }
+    return check_launch("mtq_packed_linear_skinny_grouped");
 }
 
 extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)

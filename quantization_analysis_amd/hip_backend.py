@@ -120,6 +120,8 @@ SIGNATURES = {
     "mtq_packed_offsets_batched": ("i", "pllpppp", True),
     "mtq_pack_tiles_batched": ("i", "pilllllppppzp", True),
     "mtq_unpack_tiles_batched": ("i", "pzppplllpillp", True),
+    "mtq_packed_linear_skinny_grouped_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_linear_skinny_grouped": ("i", "plllppzpppllplpilipzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1131,6 +1133,64 @@ def packed_linear_skinny(x, data, tables: PackedTables, n: int, bias=None, out_d
             raise MtqError("workspace must be 16-byte aligned")
     ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
     check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, int(split),
+             ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_linear_skinny_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_linear_skinny_grouped_workspace_bytes (a host function: no GPU): the bytes of workspace the grouped skinny kernel needs
+    for `count` (n, k) experts over total_rows rows; split 0 is the library's choice; 0 when the effective split is 1."""
+    size = int(_entry("mtq_packed_linear_skinny_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k), int(split)))
+    if size == ctypes.c_size_t(-1).value:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return size
+
+
+def packed_linear_skinny_grouped(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None, out=None,
+                                 split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_linear_skinny_grouped on the current stream: Y[rows of group e] = X[rows of group e]·Ŵ[e]ᵀ (+ bias[e]) for the `count`
+    packed (n, k) experts of one arena (pack_tiles_batched's tables) in one launch.  x: (T, k) bf16 with contiguous rows; group_rows: a
+    contiguous int32 device tensor of count + 1 entries, group e owning rows [group_rows[e], group_rows[e + 1]) (the kernel clamps them
+    into [0, T]); bias: None or a float32 (count, n) device tensor with contiguous rows.  → (T, n); an `out` allocated here starts as
+    zeros, so rows outside every group are zeros.  workspace: as packed_linear_skinny, of
+    packed_linear_skinny_grouped_workspace_bytes(T, count, n, k, split) bytes."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code = _packed_out_code(out_dtype)
+    count, n = int(count), int(n)
+    x_code, _count, _stride, T, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if count <= 0 or n <= 0:
+        raise MtqError("count and n must be positive")
+    th, tw = tiles_hw(n, k)
+    pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+    ptr = _arena(arena, count, th * tw, "arena")
+    pg = _buffer(group_rows, torch.int32, count + 1, "group_rows")
+    if group_rows.numel() != count + 1:
+        raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got {group_rows.numel()}")
+    bias_ptr, ldb = None, 0
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.dim() != 2 or tuple(bias.shape) != (count, n) or bias.stride(1) != 1 or not bias.is_cuda:
+            raise MtqError(f"bias must be a float32 ({count}, {n}) device tensor with contiguous rows")
+        bias_ptr, ldb = bias.data_ptr(), bias.stride(0) if count > 1 else max(bias.stride(0), n)
+    need = packed_linear_skinny_grouped_workspace_bytes(T, count, n, k, split)
+    fn = _entry("mtq_packed_linear_skinny_grouped")
+    if out is None:
+        require_gpu()
+        out = torch.zeros((T, n), dtype=out_dtype, device=x.device)
+    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (T, n) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {out_dtype} ({T}, {n}) device tensor with contiguous rows")
+    ws_ptr, ws_bytes = None, 0
+    if need:
+        if workspace is None:
+            require_gpu()
+            workspace = torch.empty((need,), dtype=torch.uint8, device=x.device)
+        ws_ptr, ws_bytes = _buffer(workspace, torch.uint8, need, "workspace"), int(workspace.numel())
+        if workspace.data_ptr() % 16:
+            raise MtqError("workspace must be 16-byte aligned")
+    ldy = out.stride(0) if T > 1 else max(out.stride(0), n)
+    check(fn(x.data_ptr(), T, k, ldx, pg, ptr, arena.numel(), pm, po, pb, count, n, bias_ptr, ldb, out.data_ptr(), code, ldy, int(split),
              ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
     return out
 

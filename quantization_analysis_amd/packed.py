@@ -5,7 +5,9 @@ The format is the one include/mtq.h fixes (row layout; tile t = tr * tiles_w + t
 tile format.
 
 pack_batch / unpack_batch take a batch of equal-shaped tensors and their maps (a search pipeline's resident batch and its results) to one
-arena and back with a fixed number of launches; save_dir / load_dir keep a named set of packed tensors in a directory.
+arena and back with a fixed number of launches; save_dir / load_dir keep a named set of packed tensors in a directory.  linear_grouped /
+linear_batch / PackedExperts multiply with every tensor of such an arena (the experts of an MoE layer) over its own rows of X in one
+launch; as_batch makes the arena of any list of equal-shaped packed tensors.
 
 Two backends:
   "hip"        the C ABI (csrc/mtq_packed.hip) through hip_backend's wrappers; data lives on the device.
@@ -353,7 +355,8 @@ class PackedBatch:
     """What the tensors of one pack_batch call share.  arena: the uint8 streams back to back (a NumPy array, or a device tensor);
     bases: uint64 [count + 1] on the host, tensor i's stream is arena[64 * bases[i] : 64 * bases[i + 1]]; hip: maps_dev int8
     [count, tiles], offsets_dev int32 [count, tiles + 1] (the uint32 words) and bases_dev int64 [count + 1], the tables the batched
-    kernels read."""
+    kernels read.  maps: the host maps, int8 (count, tiles_h, tiles_w): with the arena and the bases they are the whole batch, so the
+    grouped linear needs nothing but this object."""
 
     count: int
     rows: int
@@ -363,6 +366,7 @@ class PackedBatch:
     maps_dev: object = None
     offsets_dev: object = None
     bases_dev: object = None
+    maps: np.ndarray = None
 
 
 def batch_of(pts):
@@ -457,7 +461,7 @@ def pack_batch(x3d, maps, backend: str = "emulation", layout: str = "rows", shap
             host_maps = back[8 * (count + 1) + 4 * count:].view(np.int8).reshape(count, th, tw).copy()
         arena = torch.empty((int(bases[count]) * 64,), dtype=torch.uint8, device=x3d.device)
         hb.pack_tiles_batched(x3d, maps_dev, offsets_dev, bases_dev, arena)
-        batch = PackedBatch(count, rows, cols, arena, bases, maps_dev, offsets_dev, bases_dev)
+        batch = PackedBatch(count, rows, cols, arena, bases, maps_dev, offsets_dev, bases_dev, maps=host_maps)
         out = []
         for i in range(count):
             a = host_maps[i]
@@ -473,7 +477,7 @@ def pack_batch(x3d, maps, backend: str = "emulation", layout: str = "rows", shap
     streams = [encode(xf[i], host_maps[i]) for i in range(count)]
     bases = np.concatenate([[0], np.cumsum([int(o[-1]) for _d, o in streams])]).astype(np.uint64)
     arena = np.concatenate([d for d, _o in streams])
-    batch = PackedBatch(count, rows, cols, arena, bases)
+    batch = PackedBatch(count, rows, cols, arena, bases, maps=host_maps)
     return [PackedTensor(shapes[i], ("nd", shapes[i]), rows, cols, host_maps[i], streams[i][1], arena[int(bases[i]) * 64: int(bases[i + 1]) * 64],
                          _batch=(batch, i)) for i in range(count)]
 
@@ -509,6 +513,201 @@ def unpack_batch(pts, backend: str = "emulation", dtype: str = "float32"):
     if dtype == "float32":
         return bits.view(np.float32)
     return torch.from_numpy((bits >> np.uint32(16)).astype(np.uint16).view(np.int16)).view(torch.bfloat16)
+
+
+def _resolve_batch(pts_or_batch) -> PackedBatch:
+    """What the grouped entries take → its PackedBatch: a PackedBatch as it is (nothing is walked), a list through as_batch."""
+    return pts_or_batch if isinstance(pts_or_batch, PackedBatch) else as_batch(pts_or_batch)
+
+
+def as_batch(pts, device=None) -> PackedBatch:
+    """The PackedBatch of a list of equal-shaped 2-D packed tensors: one arena with tensor i's stream at byte 64 * bases[i], as
+    pack_batch lays it out.  A list that already is one whole batch in order is that batch (no copy); any other list, e.g. the tensors
+    load_dir returned, is concatenated — once per call, so a caller on a hot path keeps the batch and passes it on (PackedExperts
+    does).  hip (the streams are on the device, or `device` is given): the arena and the tables maps_dev / offsets_dev / bases_dev live
+    on the device, the offsets computed there and checked against the host's.  emulation: a NumPy arena."""
+    pts = list(pts)
+    if not pts:
+        raise MtqError("as_batch needs at least one packed tensor")
+    for pt in pts:
+        _check_layout(pt.layout)
+        if len(pt.shape) != 2:
+            raise MtqError(f"as_batch takes 2-D (n, k) weights, got a packed tensor of shape {pt.shape}")
+    rows, cols = pts[0].rows, pts[0].cols
+    if any((pt.rows, pt.cols) != (rows, cols) for pt in pts):
+        raise MtqError("as_batch takes tensors of one 2-D shape")
+    batch = batch_of(pts)
+    if batch is not None and (device is None or (_batch_on_device(batch) and batch.arena.device == _torch_device(device))):
+        return batch
+    count = len(pts)
+    bases = np.concatenate([[0], np.cumsum([pt.nbytes // 64 for pt in pts])]).astype(np.uint64)
+    maps = np.stack([pt.map for pt in pts]).astype(np.int8)
+    if device is None and not any(pt.on_device for pt in pts):
+        arena = np.concatenate([_host_data(pt)[: pt.nbytes] for pt in pts])
+        return PackedBatch(count, rows, cols, arena, bases, maps=maps)
+    import torch
+
+    from . import hip_backend as hb
+
+    hb.require_gpu()
+    dev = _torch_device(device) if device is not None else next(pt.data.device for pt in pts if pt.on_device)
+    parts = [(pt.data if pt.on_device else torch.from_numpy(np.ascontiguousarray(_host_data(pt))))[: pt.nbytes].to(dev) for pt in pts]
+    return _device_batch(count, rows, cols, torch.cat(parts), bases, maps)
+
+
+def _device_batch(count: int, rows: int, cols: int, arena, bases: np.ndarray, maps: np.ndarray) -> PackedBatch:
+    """A device arena, its host bases and host maps → the PackedBatch with device tables: the maps uploaded, the offsets and bases
+    computed on the device and held to the host's (one read-back)."""
+    import torch
+
+    from . import hip_backend as hb
+
+    maps_dev = torch.from_numpy(np.ascontiguousarray(maps.reshape(count, -1))).to(arena.device)
+    offsets_dev, bases_dev, bad_dev = hb.packed_offsets_device(maps_dev, count, maps_dev.shape[1])
+    back = torch.cat([bases_dev.view(torch.uint8), bad_dev.view(torch.uint8)]).cpu().numpy()
+    bad = back[8 * (count + 1):].view(np.int32)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise MtqError(f"tensor {i} of the list: {int(bad[i])} map codes are not MIXED_TILE_FORMATS codes 0..3 (bf16, bfp8, bfp4, bfp2)")
+    if not np.array_equal(back[: 8 * (count + 1)].view(np.uint64), bases):
+        raise MtqError("the device's bases are not those of the tensors' offsets")
+    return PackedBatch(count, rows, cols, arena, bases, maps_dev, offsets_dev, bases_dev, maps=maps)
+
+
+def _torch_device(device):
+    import torch
+
+    d = torch.device(device)
+    return torch.device("cuda", torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
+
+
+def _batch_on_device(batch: PackedBatch) -> bool:
+    return _is_torch(batch.arena) and bool(batch.arena.is_cuda) and batch.maps_dev is not None
+
+
+def _host_maps(batch: PackedBatch) -> np.ndarray:
+    """int8 (count, tiles_h, tiles_w): the batch's own host maps, or (a batch made by hand) its device maps read back."""
+    if batch.maps is not None:
+        return np.asarray(batch.maps)
+    if batch.maps_dev is None:
+        raise MtqError("the batch has no maps: make it with pack_batch or as_batch")
+    return batch.maps_dev.cpu().numpy().reshape(batch.count, -(-batch.rows // TILE), -(-batch.cols // TILE))
+
+
+def batch_to_device(batch: PackedBatch, device="cuda") -> PackedBatch:
+    """A host batch (the emulation's) as a device batch: one upload of the arena and the maps; a device batch is returned as it is."""
+    if _batch_on_device(batch):
+        return batch
+    import torch
+
+    from . import hip_backend as hb
+
+    hb.require_gpu()
+    arena = batch.arena if _is_torch(batch.arena) else torch.from_numpy(np.ascontiguousarray(batch.arena, dtype=np.uint8))
+    return _device_batch(batch.count, batch.rows, batch.cols, arena.to(_torch_device(device)), np.asarray(batch.bases, dtype=np.uint64), _host_maps(batch))
+
+
+def _batch_host_tensors(batch: PackedBatch):
+    """(map, offsets, host stream) per tensor of a batch, for the emulation."""
+    arena = batch.arena.cpu().numpy() if _is_torch(batch.arena) else np.asarray(batch.arena, dtype=np.uint8)
+    maps = _host_maps(batch)
+    return [(maps[i], offsets_of(maps[i]), arena[int(batch.bases[i]) * 64: int(batch.bases[i + 1]) * 64]) for i in range(batch.count)]
+
+
+def _host_group_rows(group_rows, count: int, total_rows: int) -> np.ndarray:
+    g = np.asarray(group_rows)
+    if g.ndim != 1 or g.size != count + 1:
+        raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {g.shape}")
+    if not np.issubdtype(g.dtype, np.integer):
+        raise MtqError(f"group_rows must hold integers, got {g.dtype}")
+    g = g.astype(np.int64)
+    if g[0] != 0 or g[-1] != total_rows:
+        raise MtqError(f"group_rows must start at 0 and end at the {total_rows} rows of x, got {int(g[0])} .. {int(g[-1])}")
+    if (np.diff(g) < 0).any():
+        raise MtqError("group_rows must not decrease")
+    return g
+
+
+def clamp_group_rows(group_rows, total_rows: int):
+    """What the kernels make of a device group_rows before any use → (r0, r1), int64 [count] each: r0 = clamp(g[e], 0, T),
+    r1 = clamp(g[e + 1], r0, T).  Whatever g holds, 0 <= r0 <= r1 <= T."""
+    g = np.asarray(group_rows, dtype=np.int64)
+    r0 = np.clip(g[:-1], 0, total_rows)
+    return r0, np.minimum(np.maximum(g[1:], r0), total_rows)
+
+
+def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
+                   workspace=None):
+    """Y[rows of group e] = X[rows of group e]·Ŵ[e]ᵀ (+ bias[e]) for all experts of a batch at once → (T, n).
+
+    x: (T, k); group_rows: count + 1 entries, group e owning rows [group_rows[e], group_rows[e + 1]) — a list or NumPy array is checked
+    here (count + 1 entries, nondecreasing, first 0, last T), a device tensor (int32) is passed on as it is and clamped by the kernel;
+    pts_or_batch: a PackedBatch (taken as it is: no per-tensor work before the launch) or a list of equal-shaped 2-D packed tensors,
+    which goes through as_batch on every call — all its checks, and for a list that is no pack_batch batch a concatenation; a host
+    batch on the hip backend is uploaded on every call (batch_to_device does it once); bias: (count, n) float32 or None.
+    hip (the default when the arena is on the device): one launch of mtq_packed_linear_skinny_grouped (two with a split over K; `split`
+    and `workspace` as in linear(kernel="skinny")), for decode-sized groups: for every group and 32-row chunk of it the bits of
+    linear(kernel="skinny") on that chunk and that expert at the same effective split.  Rows outside every group are zeros.
+    emulation: per group the float64 product of the decoded weight, rounded once, as linear does."""
+    batch = _resolve_batch(pts_or_batch)
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    count, n, k = batch.count, batch.rows, batch.cols
+    if len(x.shape) != 2 or x.shape[1] != k:
+        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
+    T = int(x.shape[0])
+    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
+    if not on_device:
+        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
+    import torch
+
+    if backend == "hip":
+        from . import hip_backend as hb
+
+        batch = batch_to_device(batch)
+        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        if T == 0:
+            return torch.zeros((0, n), dtype=dtype, device=batch.arena.device)
+        if not on_device:
+            group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(batch.arena.device)
+        if bias is not None and not _is_torch(bias):
+            bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32)).to(batch.arena.device)
+        return hb.packed_linear_skinny_grouped(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias,
+                                               out_dtype=dtype, split=split, workspace=workspace)
+    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
+    if on_device:                                    # trusted, as on hip: what the kernel makes of it
+        if tuple(group_rows.shape) != (count + 1,):
+            raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {tuple(group_rows.shape)}")
+        r0, r1 = clamp_group_rows(group_rows.cpu().numpy(), T)
+    else:
+        r0, r1 = group_rows[:-1], group_rows[1:]
+    b = None if bias is None else (bias.detach().to("cpu").double().numpy() if _is_torch(bias) else np.asarray(bias, dtype=np.float64))
+    if b is not None and b.shape != (count, n):
+        raise MtqError(f"bias must be ({count}, {n}), got {b.shape}")
+    y = np.zeros((T, n), dtype=np.float64)
+    for e, (amap, offsets, data) in enumerate(_batch_host_tensors(batch)):
+        if r1[e] == r0[e]:
+            continue
+        w = decode(data, amap, offsets, n, k).view(np.float32)
+        ye = xf[r0[e]: r1[e]].astype(np.float64) @ w.astype(np.float64).T
+        y[r0[e]: r1[e]] = ye if b is None else ye + b[e][None, :]
+    with np.errstate(over="ignore"):
+        y32 = y.astype(np.float32)
+    return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
+
+
+def linear_batch(x3d, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0, workspace=None):
+    """x3d (count, m, k): expert e multiplies x3d[e] → (count, m, n).  linear_grouped with group_rows = m * arange(count + 1)."""
+    batch = _resolve_batch(pts_or_batch)
+    if len(x3d.shape) != 3 or x3d.shape[0] != batch.count or x3d.shape[2] != batch.cols:
+        raise MtqError(f"x3d must be ({batch.count}, m, {batch.cols}), got {tuple(x3d.shape)}")
+    m = int(x3d.shape[1])
+    y = linear_grouped(x3d.reshape(batch.count * m, batch.cols), m * np.arange(batch.count + 1, dtype=np.int64), batch,
+                       bias=bias, out_dtype=out_dtype, backend=backend, split=split, workspace=workspace)
+    return y.reshape(batch.count, m, batch.rows)
 
 
 def _packed_linear_class():
@@ -572,11 +771,65 @@ def _packed_linear_class():
     return PackedLinear
 
 
+def _packed_experts_class():
+    import torch
+
+    class PackedExperts(torch.nn.Module):
+        """The experts of one batch as a module.  INFERENCE ONLY, as PackedLinear.  forward(x, group_rows): x (T, k), group e owning
+        rows [group_rows[e], group_rows[e + 1]) → (T, n) through linear_grouped.  The batch is made once, here (as_batch for a list), and
+        every forward multiplies with that arena: hip: the arena, its tables and the bias stay on the device, no host work per expert
+        and no synchronisation in forward (with a device group_rows), and the workspace grows to the largest T seen.  emulation: CPU tensors, the float64 product."""
+
+        def __init__(self, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0):
+            super().__init__()
+            if out_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            batch = _resolve_batch(pts_or_batch)                # once: forward hands the batch down and walks no list
+            self.backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
+            if self.backend not in BACKENDS:
+                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            if self.backend == "hip":
+                batch = batch_to_device(batch)
+            self.batch = batch
+            self.out_dtype, self.split = out_dtype, int(split)
+            self.count, self.out_features, self.in_features = batch.count, batch.rows, batch.cols
+            self._workspace = None
+            if bias is not None:
+                if not _is_torch(bias):
+                    bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
+                if tuple(bias.shape) != (self.count, self.out_features):
+                    raise MtqError(f"bias must be ({self.count}, {self.out_features}), got {tuple(bias.shape)}")
+                bias = bias.detach().to(device=batch.arena.device if self.backend == "hip" else "cpu", dtype=torch.float32).contiguous()
+            self.register_buffer("bias", bias, persistent=False)
+
+        def extra_repr(self) -> str:
+            return f"count={self.count}, in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, " \
+                   f"backend={self.backend!r}, split={self.split}"
+
+        @torch.no_grad()
+        def forward(self, x, group_rows):
+            if x.dim() != 2 or x.shape[1] != self.in_features:
+                raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
+            T = int(x.shape[0])
+            if self.backend == "hip" and T:
+                from . import hip_backend as hb
+
+                need = hb.packed_linear_skinny_grouped_workspace_bytes(T, self.count, self.out_features, self.in_features, self.split)
+                if need and (self._workspace is None or self._workspace.numel() < need):
+                    self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.batch.arena.device)
+            y = linear_grouped(x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype,
+                               backend=self.backend, split=self.split, workspace=self._workspace)
+            return y if _is_torch(y) else torch.from_numpy(y)
+
+    return PackedExperts
+
+
 def __getattr__(name):
-    """PackedLinear is a torch.nn.Module: the class is made on first use, so that importing this module does not import torch."""
-    if name == "PackedLinear":
-        cls = _packed_linear_class()
-        globals()["PackedLinear"] = cls
+    """PackedLinear and PackedExperts are torch.nn.Modules: a class is made on first use, so that importing this module does not import
+    torch."""
+    if name in ("PackedLinear", "PackedExperts"):
+        cls = _packed_linear_class() if name == "PackedLinear" else _packed_experts_class()
+        globals()[name] = cls
         return cls
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
