@@ -670,6 +670,26 @@ int mtq_unpack_tiles_batched(const void *packed, size_t packed_bytes, const int8
  * No atomics: two calls give the same bits.  Any m >= 1. */
 int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                       const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream);
+/* The same product from a wider block, for m above the decode range (prefill): mtq_packed_linear's parameters, argument checks and
+ * refusals.  A workgroup of 4 waves (2 x 2) owns 128 (M) x 128 (N) outputs and walks K in steps of 64, a wave 64 x 64 outputs in four
+ * accumulators, two workgroups to a CU; a wave decodes whole tiles of the weight (one format per wave, no divergence).  Two LDS images
+ * and two register sets: while one step multiplies, the next is decoded into the other image, and the loads of the step after that
+ * are issued two steps ahead in program order, the map codes and offsets a step further (how far the compiler's waits let them run
+ * beside the MFMAs: DESIGN.md A.6k; today a step still waits for the loads it has just issued).
+ *
+ * Bit contract: for every input the result equals mtq_packed_linear's bit for bit, in both output types, with and without bias.  An
+ * output has one accumulator that starts at +0 and takes mfma_f32_32x32x16_bf16 over ascending blocks of 16 K positions, x as the A
+ * operand and the decoded weight as B, K zero-filled to the step, the bias added once in f32, a bf16 y rounded once: the block
+ * kernel's sequence for that output.  The guards are the block kernel's too: a tile whose blob passes packed_bytes or whose map code is
+ * outside 0..3 multiplies as zeros, rows at or past m and columns at or past k of x are never read, nothing outside m x n of y is
+ * written, any ldx / ldy (x is read by 16-byte loads when it is 16-byte aligned with ldx % 8 == 0 and k % 8 == 0, element by element
+ * otherwise).  No atomics, no workspace, nothing waits on another workgroup: two calls give the same bits.
+ *
+ * Correct for any m >= 1 and measured faster than mtq_packed_linear from m = 64 on (below that nothing was measured; m <= 32 is the
+ * skinny entry's).  m = 0 and n = 0 are refused as by the block entry: an empty product is the caller's, and the Python binding
+ * returns it without a call. */
+int mtq_packed_linear_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                           const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream);
 
 /* The same product for decode, 1 <= m <= MTQ_PACKED_SKINNY_MAX_M: a split over K.  One wave takes the run of tiles of one tile row over
  * one K slice (a contiguous byte range of the stream), loads it straight to registers several tiles ahead, decodes each lane's group to

@@ -20,6 +20,7 @@
 //   packed_linear_skinny_kernel               the same product for m <= 32: one wave per (K slice, tile row), W straight to registers.
 //   packed_linear_skinny_grouped_kernel       that wave's work for every expert of an arena over the expert's own rows of X, one launch:
 //       for decode-sized groups (a group above 32 rows is walked in chunks and re-reads W; the block kernel is the route for large m).
+//   packed_linear_wide_kernel                 the block kernel's bits from a 128 × 128 block whose waves decode whole tiles: for m >= 64.
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
 // blob does not fit is not written (pack), not stored (unpack) or read as zeros (linear).
@@ -868,6 +869,225 @@ __global__ __launch_bounds__(256) void skinny_grouped_reduce_kernel(const float 
     }
 }
 
+// ---- wide linear (m above the decode range): packed_linear_kernel's bits from a 128 × 128 block.
+//
+// A workgroup of 4 waves, 2 (M) × 2 (N), owns a 128 (M) × 128 (N) block and walks K in steps of 64; each wave owns 64 × 64 outputs,
+// four accumulators; two workgroups fit a CU.  The W block of a step is 4 tile rows × 2 tile columns: wave w takes the two tiles of
+// tile row n0 / 32 + w, a lane the group of its own number, so a tile's format is uniform over the wave and its 64 loads cover the
+// blob's codes end to end.  decode_skinny gives decode_group's words at a third of the instructions.
+// Two LDS images of 256 rows at pitch kLdk and two register sets: while step s multiplies from image s & 1, the registers that hold
+// step s + 1 are decoded into the other image between the MFMA groups; the loads of step s + 2 are issued at the top of step s, two
+// steps ahead in program order, the map codes and offsets of step s + 3 with them (looked at a step after they were fetched).  How
+// much of that runs beside the MFMAs is the compiler's s_waitcnt placement: today its waits before a staged register is used are mostly
+// vmcnt(0), so a step still waits for the loads it has just issued.  One barrier per step, no atomics, no workspace,
+// nothing waits on another workgroup.
+// Bits: an output has one accumulator that starts at +0 and takes mfma_f32_32x32x16_bf16 over ascending blocks of 16 K positions, X as
+// the A operand and W as B, positions 8h .. 8h + 7 in lane half h, K zero-filled to the step of 64, the bias added once in f32 at the
+// end: packed_linear_kernel's sequence for that output, operand for operand, so the result is that kernel's bit for bit.
+constexpr int kWideBM = 128, kWideBN = 128;
+
+template <int V>
+struct Tag {                                         // a compile-time integer as an argument: a register set's parity
+    static constexpr int value = V;
+};
+
+// The second launch bound is HIP's minimum of waves per SIMD, not workgroups per CU: a workgroup here is one wave per SIMD, so 2 is
+// what lets two workgroups share a CU and caps the kernel at 256 VGPRs, which it uses to the last: re-read `make report` on any edit.
+template <bool XV, bool BF16OUT>
+__global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+    const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N, int64_t tiles_h, int64_t tiles_w,
+    const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy)
+{
+    constexpr int BM = kWideBM, MT = BM / 64, XP = BM * 8 / kThreads;   // a wave's 32-row MFMA blocks; pieces of 8 bf16 of the X block per thread
+    constexpr int kImage = (BM + kWideBN) * kLdk;
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kImage];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
+    const int64_t bm = blockIdx.x / nblocks, bn = blockIdx.x % nblocks;
+    const int64_t m0 = bm * BM, n0 = bn * kWideBN;
+    const int64_t steps = (K + kBK - 1) / kBK;
+
+    f32x16 acc[MT][2];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
+
+    const int64_t wtr = (n0 >> 5) + wave;            // the wave's tile row
+    uint4 xr[2][XP];                                 // register set p holds the steps of parity p
+    GroupRaw wr[2][2];
+    int tf[2];                                       // map code and offset of the wave's two tiles of the step after the last one loaded,
+    uint32_t to[2];                                  // fetched a step before they are looked at: no load waits for them
+    auto fetch_tables = [&](int64_t s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int64_t wtc = 2 * s + i;
+            const bool there = wtr < tiles_h && wtc < tiles_w;
+            const int64_t t = there ? wtr * tiles_w + wtc : 0;               // tile 0 is always there: the loads are unconditional
+            const int f = map[t];
+            const uint32_t o = offsets[t];
+            tf[i] = there ? f : -1;
+            to[i] = there ? o : 0u;
+        }
+    };
+    // load_group for a whole tile by one wave (lane = group), with two loads whatever the tile is: every step issues the same
+    // number of loads on every path, which is what a counted wait for an earlier step's registers needs (the compiler does not
+    // emit one yet: the kernel's head comment).
+    // A tile that is not there reads bytes of the first 320 of the stream instead (they are there: the entry checks packed_bytes
+    // against 320 bytes per tile) and keeps f < 0, which decodes as zeros.
+    auto load_tile = [&](const TileAt &a, GroupRaw &g) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) g.w[i] = 0u;
+        g.E = 0u;
+        g.f = a.f;
+        const int f = __builtin_amdgcn_readfirstlane(a.f);                   // uniform over the wave
+        const uint8_t *blob = packed + (f < 0 ? 0 : __builtin_amdgcn_readfirstlane((uint32_t)(a.off / kUnit)) * (uint64_t)kUnit);
+        if (f == 0) {
+            const uint4 *q = reinterpret_cast<const uint4 *>(blob + lane * 32);
+            const uint4 lo = q[0], hi = q[1];
+            g.w[0] = lo.x; g.w[1] = lo.y; g.w[2] = lo.z; g.w[3] = lo.w;
+            g.w[4] = hi.x; g.w[5] = hi.y; g.w[6] = hi.z; g.w[7] = hi.w;
+        } else if (f == 1) {
+            g.E = blob[lane];
+            const uint4 v = *reinterpret_cast<const uint4 *>(blob + kExpBytes + lane * 16);
+            g.w[0] = v.x; g.w[1] = v.y; g.w[2] = v.z; g.w[3] = v.w;
+        } else if (f == 2) {
+            g.E = blob[lane];
+            const uint2 v = *reinterpret_cast<const uint2 *>(blob + kExpBytes + lane * 8);
+            g.w[0] = v.x; g.w[1] = v.y;
+        } else {
+            g.E = blob[lane];
+            g.w[0] = *reinterpret_cast<const uint32_t *>(blob + kExpBytes + lane * 4);
+        }
+    };
+    auto located = [&](int i) __attribute__((always_inline)) {   // tile_at's answer from the fetched pair
+        TileAt a;
+        const uint32_t size = packed_tile_bytes(tf[i]);
+        a.off = (uint64_t)to[i] * kUnit;
+        a.f = (size == 0u || a.off + size > packed_bytes) ? -1 : tf[i];
+        return a;
+    };
+    auto load_step = [&](auto par, int64_t s) __attribute__((always_inline)) {
+        constexpr int p = decltype(par)::value;
+        const int64_t k0 = s * kBK;
+        const TileAt at[2] = {located(0), located(1)};
+        fetch_tables(s + 1);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) load_tile(at[i], wr[p][i]);
+#pragma unroll
+        for (int j = 0; j < XP; ++j) {               // columns past K and rows past M are zeros, never read
+            const int q = tid + kThreads * j, row = q >> 3, c8 = (q & 7) * 8;
+            const int64_t gm = m0 + row, gk = k0 + c8;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if constexpr (XV) {                      // K % 8 == 0: a piece is inside or outside; the load is of a piece that is inside
+                const bool inside = gm < M && gk < K;
+                const uint4 got = *reinterpret_cast<const uint4 *>(x + (gm < M ? gm : M - 1) * ldx + (gk < K ? gk : K - 8));
+                if (inside) v = got;
+            } else if (gm < M && gk < K) {
+                const uint16_t *src = x + gm * ldx + gk;
+                uint32_t h[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) h[e] = gk + e < K ? (uint32_t)src[e] : 0u;
+                v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+            }
+            xr[p][j] = v;
+        }
+    };
+    // register set p → image `img`: tile i of the wave's tile row (rows 32 wave .. of the W part), and X pieces [j0, j1)
+    auto stage_w = [&](auto par, int i, uint16_t *img) __attribute__((always_inline)) {
+        constexpr int p = decltype(par)::value;
+        uint32_t y[kGroup];
+        decode_skinny(wr[p][i], y);
+        uint4 lo, hi;
+        pack_halves(y, lo, hi);
+        uint4 *d = reinterpret_cast<uint4 *>(img + (BM + kTile * wave + (lane >> 1)) * kLdk + kTile * i + kGroup * (lane & 1));
+        d[0] = lo;
+        d[1] = hi;
+    };
+    auto stage_x = [&](auto par, int j0, int j1, uint16_t *img) __attribute__((always_inline)) {
+        constexpr int p = decltype(par)::value;
+#pragma unroll
+        for (int j = j0; j < j1; ++j) {
+            const int q = tid + kThreads * j;
+            *reinterpret_cast<uint4 *>(img + (q >> 3) * kLdk + (q & 7) * 8) = xr[p][j];
+        }
+    };
+    // MFMA group kk of a step: the 16 K positions 16 kk .. of the images xs / ws, 2 MT MFMAs
+    auto mfma_group = [&](const uint16_t *xs, const uint16_t *ws, int kk) __attribute__((always_inline)) {
+        const int koff = kk * 16 + 8 * (lane >> 5);
+        bf16x8 b[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) b[nt] = *reinterpret_cast<const bf16x8 *>(ws + (64 * wn + 32 * nt + (lane & 31)) * kLdk + koff);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (32 * MT * wm + 32 * mt + (lane & 31)) * kLdk + koff);
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[nt], acc[mt][nt], 0, 0, 0);
+        }
+    };
+    // step s from image s & 1; the registers of step s + 1 go to the other image between the MFMA groups (two waves to a SIMD: the
+    // other workgroup's MFMAs run beside this wave's decode)
+    auto step = [&](auto par, int64_t s) __attribute__((always_inline)) {
+        constexpr int cur = decltype(par)::value;
+        const Tag<cur ^ 1> other;
+        const uint16_t *xs = lds + cur * kImage, *ws = xs + BM * kLdk;
+        uint16_t *next = lds + (cur ^ 1) * kImage;
+        const bool more = s + 1 < steps;
+        load_step(par, s + 2 < steps ? s + 2 : steps - 1);   // into this parity's registers, staged a step ago; past the end the
+                                                     // last step is loaded again and not used: the same loads on every path
+#pragma unroll
+        for (int kk = 0; kk < kBK / 16; ++kk) {
+            if (!more) {
+                mfma_group(xs, ws, kk);
+            } else if (kk < 2) {
+                mfma_group(xs, ws, kk);
+                stage_w(other, kk, next);
+            } else {
+                mfma_group(xs, ws, kk);
+                stage_x(other, (kk - 2) * (XP / 2), (kk - 1) * (XP / 2), next);
+            }
+        }
+        __syncthreads();
+    };
+
+    fetch_tables(0);
+    load_step(Tag<0>(), 0);
+    load_step(Tag<1>(), steps > 1 ? 1 : 0);
+    stage_w(Tag<0>(), 0, lds);
+    stage_w(Tag<0>(), 1, lds);
+    stage_x(Tag<0>(), 0, XP, lds);
+    __syncthreads();
+    int64_t s = 0;
+    for (; s + 1 < steps; s += 2) {
+        step(Tag<0>(), s);
+        step(Tag<1>(), s + 1);
+    }
+    if (s < steps) {                                 // an odd count's last step: nothing left to load or stage
+#pragma unroll
+        for (int kk = 0; kk < kBK / 16; ++kk) mfma_group(lds, lds + BM * kLdk, kk);
+    }
+
+    // epilogue: lane's outputs are (m0 + 32 MT·wm + 32 mt + (r&3) + 8(r>>2) + 4(lane>>5), n0 + 64·wn + 32 nt + (lane&31))
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        const int64_t n = n0 + 64 * wn + 32 * nt + (lane & 31);
+        if (n >= N) continue;
+        const float b = bias ? bias[n] : 0.0f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t m = m0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[mt][nt][r] + b);
+            }
+    }
+}
+
 // skinny_shape for the grouped entry: skinny_split's rule with count * tiles_h tile rows, which for count == 1 is that rule.
 int grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *tiles_h, int64_t *tiles_w, int *split_eff)
 {
@@ -1051,19 +1271,27 @@ extern "C" int mtq_unpack_tiles_batched(const void *packed, size_t packed_bytes,
     return check_launch("mtq_unpack_tiles_batched");
 }
 
-extern "C" int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
-                                 const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+// What the block and the wide entry check before a device is looked for, and the tile grid
+static int linear_args(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                       const uint32_t *offsets, int64_t n, const void *y, int out_dtype, int64_t ldy, int64_t *tiles_h, int64_t *tiles_w)
 {
     if (!x || !packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
     if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
     if (m <= 0) return fail(MTQ_ERR_INVALID, "m must be positive (empty operands are handled by the caller)");
-    int64_t th, tw;
-    if (int rc = tile_grid(n, k, &th, &tw)) return rc;
+    if (int rc = tile_grid(n, k, tiles_h, tiles_w)) return rc;
     if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
     if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
     if (m > (int64_t)1 << 40) return fail(MTQ_ERR_INVALID, "matrix too large");
     if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
+    if (packed_bytes < (uint64_t)(*tiles_h * *tiles_w) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
+    return MTQ_OK;
+}
+
+extern "C" int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                                 const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    int64_t th, tw;
+    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, &th, &tw)) return rc;
     const int64_t blocks = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
     if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
     if (int rc = require_device()) return rc;
@@ -1079,6 +1307,37 @@ extern "C" int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ld
         hipLaunchKernelGGL(packed_linear_kernel<false>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th,
                            tw, bias, y, ldy);
     return check_launch("mtq_packed_linear");
+}
+
+template <bool XV>
+static void launch_wide(int64_t blocks, hipStream_t st, const uint16_t *xp, int64_t m, int64_t k, int64_t ldx, const uint8_t *pp,
+                        uint64_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t n, int64_t th, int64_t tw, const float *bias,
+                        void *y, int out_dtype, int64_t ldy)
+{
+    const dim3 grid((unsigned)blocks);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL((packed_linear_wide_kernel<XV, true>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, pp, packed_bytes, map, offsets, n, th, tw,
+                           bias, y, ldy);
+    else
+        hipLaunchKernelGGL((packed_linear_wide_kernel<XV, false>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, pp, packed_bytes, map, offsets, n, th, tw,
+                           bias, y, ldy);
+}
+
+extern "C" int mtq_packed_linear_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                                      const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    int64_t th, tw;
+    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, &th, &tw)) return rc;
+    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kWideBN - 1) / kWideBN);
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
+    if (int rc = require_device()) return rc;
+    // whole pieces of 8 bf16 by 16-byte loads; any other x (a ragged k included) element by element
+    const bool x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0 && k % 8 == 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    (x_vec ? launch_wide<true> : launch_wide<false>)(blocks, st, xp, m, k, ldx, pp, (uint64_t)packed_bytes, map, offsets, n, th, tw, bias, y, out_dtype, ldy);
+    return check_launch("mtq_packed_linear_wide");
 }
 
 extern "C" size_t mtq_packed_linear_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)

@@ -37,6 +37,10 @@ SKINNY_MAX_M = 32           # include/mtq.h MTQ_PACKED_SKINNY_MAX_M
 # kernel="auto" takes the skinny kernel up to this m and the block kernel above it: the largest measured m at which the skinny
 # kernel's median is below the block kernel's minimum at every shape and map (profiles/packed_linear_skinny.txt).
 AUTO_SKINNY_MAX_M = 32
+# kernel="auto" takes the wide-block kernel (linear_wide) from this m on when the library has it; None: never.  The smallest measured m
+# from which on the wide kernel's median is below the block kernel's minimum of the same run at every shape and map (DESIGN.md §A.6k,
+# profiles/packed_linear_wide.txt).  Both kernels give the same bits, so the gate changes no result.
+AUTO_WIDE_MIN_M = 64
 
 
 def _is_torch(x) -> bool:
@@ -307,8 +311,9 @@ def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
 
     kernel: "block" (the default; any m), "skinny" (the split-K kernel for decode, m <= 32; `split` slices of K, 0 = the library's
     choice, and an optional uint8 device `workspace` of hip_backend.packed_linear_skinny_workspace_bytes bytes) or "auto" (skinny for
-    m <= AUTO_SKINNY_MAX_M, block above).  The two kernels sum in different orders: each is bit-stable, they may differ in the last
-    bits.  The emulation computes the same float64 product under all three names."""
+    m <= AUTO_SKINNY_MAX_M, block above; from m = AUTO_WIDE_MIN_M on, when that is not None and the library has it, the wide-block
+    kernel of linear_wide, whose bits are the block kernel's).  The skinny and the block kernel sum in different orders: each is
+    bit-stable, they may differ in the last bits.  The emulation computes the same float64 product under all three names."""
     _check_layout(pt.layout)
     if kernel not in KERNELS:
         raise MtqError(f"kernel must be one of {KERNELS}, got {kernel!r}")
@@ -331,6 +336,8 @@ def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
             raise MtqError(f'kernel="skinny" takes m <= {SKINNY_MAX_M}, got m = {m}')
         if kernel == "skinny" or (kernel == "auto" and m <= AUTO_SKINNY_MAX_M):
             return hb.packed_linear_skinny(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype, split=split, workspace=workspace)
+        if kernel == "auto" and AUTO_WIDE_MIN_M is not None and m >= AUTO_WIDE_MIN_M and hb.has_packed_linear_wide():
+            return hb.packed_linear_wide(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
         return hb.packed_linear(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
     if backend != "emulation":
         raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
@@ -346,6 +353,30 @@ def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     with np.errstate(over="ignore"):
         y32 = y.astype(np.float32)
     return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
+
+
+def linear_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
+    """linear(kernel="block")'s product and, on hip, its bits, through mtq_packed_linear_wide: the wide-block kernel for m above the
+    decode range (prefill), 128 x 128 outputs to a workgroup, whose waves decode whole tiles of the weight.  Correct for any m
+    (m = 0 gives (0, n)); faster than the block kernel from m = 64 on, the smallest m measured.  A library without the symbol raises MtqError: there is no
+    fall-back to the block kernel here (linear(kernel="auto") is the call that chooses).  emulation: linear's float64 product."""
+    _check_layout(pt.layout)
+    if len(pt.shape) != 2:
+        raise MtqError(f"linear needs a 2-D (n, k) weight, the packed tensor is {pt.shape}")
+    backend = backend or ("hip" if pt.on_device else "emulation")
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    if backend != "hip":
+        return linear(x, pt, bias=bias, out_dtype=out_dtype, backend=backend)
+    import torch
+
+    from . import hip_backend as hb
+
+    n, k = pt.rows, pt.cols
+    if x.dim() != 2 or x.shape[1] != k:
+        raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+    dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+    return hb.packed_linear_wide(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
 
 
 # ----------------------------------------------------------------------------- batches
@@ -716,7 +747,8 @@ def _packed_linear_class():
     class PackedLinear(torch.nn.Module):
         """A linear layer over a packed (n, k) weight.  INFERENCE ONLY: the kernels have no backward, no gradient reaches x, the weight
         or the bias.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through linear() with
-        `kernel` ("auto": the skinny split-K kernel for decode-sized m, the block kernel above) and returns (..., n) in out_dtype.
+        `kernel` ("auto": the skinny split-K kernel for decode-sized m, the block kernel above, the wide-block kernel with the same
+        bits from AUTO_WIDE_MIN_M on) and returns (..., n) in out_dtype.
         hip: the tables, the bias and a workspace sized for every m <= 32 stay on the device across calls, so a decode step
         allocates only its output.  emulation: CPU tensors, the float64 product (for use without a GPU)."""
 

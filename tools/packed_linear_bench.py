@@ -11,8 +11,14 @@
                   of the same alternation, once per value of --splits (0 = the library's choice); `skinny/block-min` is the skinny
                   median over the block kernel's MINIMUM of the same run, the gate of DESIGN.md §A.6h.
 
+  wide          : --wide adds the wide-block kernel for m above the decode range (mtq_packed_linear_wide, the C entry) as one more
+                  side of the same alternation; `wide/block-min` is the wide median over the block kernel's MINIMUM of the same run,
+                  the gate of DESIGN.md §A.6k; the line also says whether the result's bits are the block kernel's.
+
   python tools/packed_linear_bench.py [--rounds 5] [--window-ms 30] [--out profiles/packed_linear.txt] [--json out.json]
   python tools/packed_linear_bench.py --linear-only --ms 1,4,16,32 --out profiles/packed_linear_skinny.txt
+  python tools/packed_linear_bench.py --linear-only --wide --ms 64,128,256,512,1024,2048,4096 --out profiles/packed_linear_wide.txt
+  (the record kept there also has rows=256 lines: a 256 x 128 instantiation that was measured beside the kernel, lost and was removed)
 """
 from __future__ import annotations
 
@@ -68,6 +74,7 @@ def main() -> int:
     p.add_argument("--shapes", default="4096x4096,14336x4096")
     p.add_argument("--ms", default="1,16,256,4096")
     p.add_argument("--splits", default="0", help="skinny side: the split values to time, comma separated (0: the library's choice)")
+    p.add_argument("--wide", action="store_true", help="time the wide-block kernel beside the block kernel and torch.matmul")
     p.add_argument("--linear-only", action="store_true", help="skip the pack / unpack timings")
     p.add_argument("--out", default=None)
     p.add_argument("--json", default=None)
@@ -145,10 +152,25 @@ def main() -> int:
                         skinny.append({"split": split, "workspace_bytes": need, "fn": f_skinny, "ws": ws, "iters": calibrate(f_skinny, args.window_ms),
                                        "ts": []})
 
+                # the wide kernel: the C entry, as the block side
+                wide = []
+                if args.wide:
+                    yw = torch.empty((m, n), dtype=torch.bfloat16, device="cuda")
+                    hb.packed_linear_wide(x, data, tables, n, out_dtype=torch.bfloat16, out=yw)   # the wrapper's checks, once
+                    wentry = hb._entry("mtq_packed_linear_wide")
+                    wcalls = [c[:10] + (yw.data_ptr(),) + c[11:] for c in calls]
+
+                    def f_wide(i):
+                        hb.check(wentry(*wcalls[i % copies_p]))
+
+                    wide.append({"fn": f_wide, "iters": calibrate(f_wide, args.window_ms), "ts": []})
+
                 ip, im = calibrate(f_packed, args.window_ms), calibrate(f_matmul, args.window_ms)
                 tp, tm = [], []
                 for _ in range(args.rounds):
                     tp.append(window_ms(f_packed, ip))
+                    for side in wide:
+                        side["ts"].append(window_ms(side["fn"], side["iters"]))
                     for side in skinny:
                         side["ts"].append(window_ms(side["fn"], side["iters"]))
                     tm.append(window_ms(f_matmul, im))
@@ -163,6 +185,21 @@ def main() -> int:
                 say(f"linear       {n}x{k} m={m:5d} map={name:6s} packed {mp * 1e3:9.1f} us (min {min(tp) * 1e3:9.1f}, {tables.nbytes / mp / 1e6:7.1f} GB/s of stream) "
                     f"matmul {mm * 1e3:9.1f} us (min {min(tm) * 1e3:9.1f}, {2 * n * k / mm / 1e6:7.1f} GB/s of bf16 W)  packed/matmul {mp / mm:6.2f}  "
                     f"max rel diff {err:.2e}")
+                flop = 2.0 * m * n * k
+                for side in wide:
+                    yw.zero_()
+                    side["fn"](0)
+                    same = bool(torch.equal(yw.view(torch.int16), yp.view(torch.int16)))
+                    mw, mnw = statistics.median(side["ts"]), min(side["ts"])
+                    rows.append({"what": "packed_linear_wide", "n": n, "k": k, "m": m, "map": name, "counts": counts,
+                                 "wide_ms_median": mw, "wide_ms_min": mnw, "block_ms_median": mp, "block_ms_min": min(tp), "matmul_ms_median": mm,
+                                 "matmul_ms_min": min(tm), "wide_over_block_min": mw / min(tp), "wide_over_matmul": mw / mm,
+                                 "wide_tflops": flop / mw / 1e9, "block_tflops": flop / mp / 1e9, "matmul_tflops": flop / mm / 1e9,
+                                 "bits_equal_block": same})
+                    say(f"wide         {n}x{k} m={m:5d} map={name:6s} {mw * 1e3:9.1f} us (min {mnw * 1e3:9.1f}, "
+                        f"{flop / mw / 1e9:7.1f} TFLOP/s; block {flop / mp / 1e9:7.1f}, matmul {flop / mm / 1e9:7.1f})  wide/block-min {mw / min(tp):6.3f}  "
+                        f"wide/matmul {mw / mm:6.2f}  bits equal block: {same}")
+                del wide
                 for side in skinny:
                     side["fn"](0)
                     serr = float((ys.float() - ym.float()).abs().max() / ym.float().abs().max().clamp_min(1e-30))
