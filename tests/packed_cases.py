@@ -1,5 +1,5 @@
-"""Inputs shared by tests/test_packed_host.py and tests/test_packed_gpu.py: the specials tensor, seeded maps, and the expected
-reconstruction from the oracle."""
+"""Inputs shared by the packed test modules: the specials tensor, seeded maps, the expected reconstruction from the oracle, and the
+integer-grid case of the linear tests with its preconditions."""
 from __future__ import annotations
 
 import numpy as np
@@ -8,6 +8,7 @@ from oracle import mtq_oracle as orc
 
 FORMATS = ["bf16", "bfp8", "bfp4", "bfp2"]
 TILE_BYTES = (2048, 1088, 576, 320)
+GRID = 2.0 ** -8
 
 
 def specials(shape, seed: int = 11) -> np.ndarray:
@@ -57,3 +58,19 @@ def expected_bits(x: np.ndarray, amap: np.ndarray) -> np.ndarray:
 
 def stream_bytes(amap: np.ndarray) -> int:
     return int(sum(int((amap == c).sum()) * TILE_BYTES[c] for c in range(4)))
+
+
+def _grid_case(m, n, k, seed):
+    """The integer grid: X integers |x| <= 4, W and the bias on the 2^-8 grid with |w| < 1."""
+    rng = np.random.default_rng(seed)
+    x = rng.integers(-4, 5, size=(m, k)).astype(np.float32)
+    w = (rng.integers(-255, 256, size=(n, k)) * GRID).astype(np.float32)
+    b = (rng.integers(-255, 256, size=(n,)) * GRID).astype(np.float32)
+    return x, w, b
+
+
+def _grid_preconditions(x, what, b):
+    assert np.all(np.abs(x) <= 4) and np.array_equal(x, np.round(x))
+    assert np.array_equal(what / GRID, np.round(what / GRID)) and np.array_equal(b / GRID, np.round(b / GRID))
+    worst = (np.abs(x).astype(np.float64) @ np.abs(what).T + np.abs(b)[None, :]) / GRID
+    assert worst.max() < 2.0 ** 24

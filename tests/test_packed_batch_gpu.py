@@ -8,6 +8,8 @@
   * unpack: float32 is the oracle's reconstruction and K3's bit for bit, bf16 its upper halves; nothing outside rows × cols is stored;
   * linear: both kernels on a pack_batch product give the bits they give on the tensor packed alone (the table slices, the alignment);
   * bounds: an arena one blob short keeps the last blob out and everything before it right;
+  * the grid-stride loops: a batch of 2²² + 5 tensors of shape 1 × 1 is five waves more than the grid's cap of 2²⁰ workgroups of four
+    holds, so the pack and the unpack kernel each take a second round: every tensor's word is the oracle's, bit for bit;
   * scripts/pack_model.py on the hip backend writes what it writes on the emulation backend.
 """
 from __future__ import annotations
@@ -267,6 +269,72 @@ def test_an_arena_one_blob_short_keeps_the_last_blob_out():
     in_last = np.zeros(x.shape, dtype=bool)
     in_last[-1, 64:, 96:] = True                                                          # tile (2, 3) of the last tensor
     assert np.array_equal(yb.view(np.uint32)[~in_last], full[~in_last]) and np.all(yb[in_last] == -7.0)
+
+
+# ----------------------------------------------------------------------------- the grid-stride loops' second round
+
+ROUND = 2 ** 22                                      # the waves of one round: 2²⁰ workgroups (the grid's cap) of four
+
+
+def _scalars(storage) -> np.ndarray:
+    """64 distinct float32 words (bf16 storage: with zero low halves): ±0, ±Inf, NaNs of both signs, denormals, the largest finite
+    values, and finite values over the whole exponent range."""
+    special = np.array([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00001, 0x7F800001, 0x00000001, 0x807FFFFF,
+                        0x00400000, 0x7F7FFFFF, 0xFF7FFFFF, 0x00800000, 0x3F808000, 0x3F818000, 0x7F7F8000], dtype=np.uint32)
+    if storage == "bf16":
+        special = np.array([0x0000, 0x8000, 0x7F80, 0xFF80, 0x7FC0, 0xFFC1, 0x7F81, 0x0001, 0x807F, 0x0040, 0x7F7F, 0xFF7F, 0x0080, 0x3F80,
+                            0x3F81, 0x7F7E], dtype=np.uint32) << np.uint32(16)
+    rng = np.random.default_rng(64)
+    exp = np.linspace(1, 254, 48).astype(np.uint32)
+    finite = (rng.integers(0, 2, size=48).astype(np.uint32) << np.uint32(31)) | (exp << np.uint32(23)) | rng.integers(0, 1 << 23, size=48).astype(np.uint32)
+    if storage == "bf16":
+        finite &= np.uint32(0xFFFF0000)
+    u = np.concatenate([special, finite])
+    assert u.size == 64 and np.unique(u).size == 64
+    return u
+
+
+@pytest.mark.parametrize("storage", ["f32", "bf16"])
+def test_the_grid_stride_loops_take_a_second_round(storage):
+    count = ROUND + 5
+    u = _scalars(storage)
+    # the reference: the 64 × 4 (value, code) pairs through the oracle once, a value at the head of a 16-group of zeros (what a 1 × 1
+    # tensor's only group is after zero padding)
+    carrier = np.zeros((64, 16), dtype=np.uint32)
+    carrier[:, 0] = u
+    table = np.stack([expected_bits(carrier.view(np.float32), uniform_map((64, 16), c))[:, 0] for c in range(4)], axis=1)
+    assert table.shape == (64, 4) and table.dtype == np.uint32
+    rng = np.random.default_rng(4242)
+    codes = rng.choice(4, size=count, p=[1 / 64, 21 / 64, 21 / 64, 21 / 64]).astype(np.int8)     # bf16 blobs (2048 B) are rare
+    codes[[0, ROUND - 1, ROUND, ROUND + 4]] = [0, 1, 2, 3]
+    ids = np.arange(count) % 64
+    units = np.asarray(TILE_BYTES)[codes] // 64
+    assert 64 * int(units.sum()) < 3 * 2 ** 30
+    xd = dev(u.view(np.float32)[ids].reshape(count, 1, 1), storage)
+    maps_dev = torch.from_numpy(codes.reshape(count, 1)).cuda()
+    offsets, bases_dev, bad = hb.packed_offsets_device(maps_dev, count, 1)
+    assert not bool(bad.any())
+    bases = bases_dev.cpu().numpy().view(np.uint64)
+    assert np.array_equal(bases, np.concatenate([[0], np.cumsum(units)]).astype(np.uint64))
+    arena = torch.empty((64 * int(bases[count]),), dtype=torch.uint8, device="cuda")
+    arena[64 * int(bases[ROUND]):] = FILL                                                      # what a kernel without a second round leaves
+    hb.pack_tiles_batched(xd, maps_dev, offsets, bases_dev, arena)
+    for i in (0, ROUND - 1, ROUND, ROUND + 4):
+        value = u.view(np.float32)[ids[i]].reshape(1, 1)
+        want = packed.pack(value, np.array([[codes[i]]], dtype=np.int8), backend="emulation").data
+        got = arena[64 * int(bases[i]): 64 * int(bases[i + 1])].cpu().numpy()
+        assert np.array_equal(got, want), (storage, i, np.flatnonzero(got != want)[:8])
+    want_dev = torch.from_numpy(table.view(np.int32)).cuda()[torch.from_numpy(ids).cuda(), maps_dev.reshape(-1).long()]
+    y = torch.full((count, 1, 1), -7.0, dtype=torch.float32, device="cuda")
+    hb.unpack_tiles_batched(arena, maps_dev, offsets, bases_dev, count, 1, 1, torch.float32, out=y)
+    got = y.view(torch.int32).reshape(-1)
+    wrong = (got != want_dev).nonzero().reshape(-1)
+    assert wrong.numel() == 0, (storage, "tensors", wrong[:8].tolist(), "of", count, "; the second round starts at", ROUND)
+    assert bool((want_dev & 0xFFFF == 0).all())                                               # bf16-valued: the bf16 unpack is exact
+    half = torch.full((count, 1, 1), -7.0, dtype=torch.bfloat16, device="cuda")
+    hb.unpack_tiles_batched(arena, maps_dev, offsets, bases_dev, count, 1, 1, torch.bfloat16, out=half)
+    wrong = (half.view(torch.int16).reshape(-1).to(torch.int32) << 16 != want_dev).nonzero().reshape(-1)
+    assert wrong.numel() == 0, (storage, "bf16 output, tensors", wrong[:8].tolist())
 
 
 # ----------------------------------------------------------------------------- the script

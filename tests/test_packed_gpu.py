@@ -25,10 +25,9 @@ from oracle import mtq_oracle as orc
 from quantization_analysis_amd import hip_backend as hb
 from quantization_analysis_amd import packed
 from tests.inputs import gen, to_bf16_valued
-from tests.packed_cases import expected_bits, random_map, specials, uniform_map
+from tests.packed_cases import GRID, _grid_case, _grid_preconditions, expected_bits, random_map, specials, uniform_map
 
 pytestmark = pytest.mark.gpu
-GRID = 2.0 ** -8
 
 
 def dev(x: np.ndarray, storage: str):
@@ -139,21 +138,6 @@ def _what(w: np.ndarray, amap: np.ndarray) -> np.ndarray:
 def _x_dev(x: np.ndarray):
     assert np.array_equal(to_bf16_valued(x), x)
     return torch.from_numpy(x).to(torch.bfloat16).cuda()
-
-
-def _grid_case(m, n, k, seed):
-    rng = np.random.default_rng(seed)
-    x = rng.integers(-4, 5, size=(m, k)).astype(np.float32)
-    w = (rng.integers(-255, 256, size=(n, k)) * GRID).astype(np.float32)
-    b = (rng.integers(-255, 256, size=(n,)) * GRID).astype(np.float32)
-    return x, w, b
-
-
-def _grid_preconditions(x, what, b):
-    assert np.all(np.abs(x) <= 4) and np.array_equal(x, np.round(x))
-    assert np.array_equal(what / GRID, np.round(what / GRID)) and np.array_equal(b / GRID, np.round(b / GRID))
-    worst = (np.abs(x).astype(np.float64) @ np.abs(what).T + np.abs(b)[None, :]) / GRID
-    assert worst.max() < 2.0 ** 24
 
 
 @pytest.mark.parametrize("m", [1, 33, 133])

@@ -38,8 +38,7 @@ from oracle import mtq_oracle as orc
 from quantization_analysis_amd import hip_backend as hb
 from quantization_analysis_amd import packed
 from tests.inputs import gen, to_bf16_valued
-from tests.packed_cases import TILE_BYTES, random_map
-from tests.test_packed_gpu import _grid_preconditions
+from tests.packed_cases import TILE_BYTES, _grid_preconditions, random_map
 from tests.test_packed_skinny_gpu import _bits, _grid_weight, _what, _x_dev, grid_case_is_exact, random_case_is_within_the_bound
 
 pytestmark = pytest.mark.gpu

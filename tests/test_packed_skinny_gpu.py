@@ -24,10 +24,9 @@ import torch
 from quantization_analysis_amd import hip_backend as hb
 from quantization_analysis_amd import packed
 from tests.inputs import gen, to_bf16_valued
-from tests.packed_cases import expected_bits, random_map, uniform_map
+from tests.packed_cases import GRID, expected_bits, random_map, uniform_map
 
 pytestmark = pytest.mark.gpu
-GRID = 2.0 ** -8
 SPLITS = (0, 1, 2, 5, 9)
 MAPS = ("random", "0", "1", "2", "3")
 

@@ -37,10 +37,9 @@ import torch
 from quantization_analysis_amd import hip_backend as hb
 from quantization_analysis_amd import packed
 from tests.inputs import gen, to_bf16_valued
-from tests.packed_cases import TILE_BYTES, expected_bits, random_map, specials, uniform_map
+from tests.packed_cases import GRID, TILE_BYTES, _grid_case, _grid_preconditions, expected_bits, random_map, specials, uniform_map
 
 pytestmark = pytest.mark.gpu
-GRID = 2.0 ** -8
 SHAPES = [(m, n, k) for m in (1, 33, 257, 300) for n in (72, 200) for k in (100, 300)] + [(300, 200, 2100)]
 SHAPES += [(1, 72, 320), (33, 200, 104), (257, 72, 104), (300, 200, 320)]       # k % 8 == 0: the kernel's 16-byte loads of X
 DTYPES = (("float32", torch.float32), ("bfloat16", torch.bfloat16))
@@ -137,22 +136,6 @@ def test_wide_is_the_block_kernel_on_specials(m, n, k):
 
 
 # ----------------------------------------------------------------------------- independent of the block kernel
-
-def _grid_case(m, n, k, seed):
-    """tests/test_packed_gpu.py's construction."""
-    rng = np.random.default_rng(seed)
-    x = rng.integers(-4, 5, size=(m, k)).astype(np.float32)
-    w = (rng.integers(-255, 256, size=(n, k)) * GRID).astype(np.float32)
-    b = (rng.integers(-255, 256, size=(n,)) * GRID).astype(np.float32)
-    return x, w, b
-
-
-def _grid_preconditions(x, what, b):
-    assert np.all(np.abs(x) <= 4) and np.array_equal(x, np.round(x))
-    assert np.array_equal(what / GRID, np.round(what / GRID)) and np.array_equal(b / GRID, np.round(b / GRID))
-    worst = (np.abs(x).astype(np.float64) @ np.abs(what).T + np.abs(b)[None, :]) / GRID
-    assert worst.max() < 2.0 ** 24
-
 
 @pytest.mark.parametrize("m,n,k", [(300, 200, 300), (257, 72, 2100), (300, 200, 320)])
 def test_wide_integer_grid_is_exact(m, n, k):
