@@ -8,7 +8,12 @@ exact routes cannot take (groups scaled by 1e-28, a 2e18 element) sit in the fir
 strided fix-up kernels run at every size too.
 
 Sizes beyond what the oracle does in reasonable time are built from a few distinct blocks repeated (whole tensors in a shuffled
-order, or one strip repeated along its row): `idx` maps every tile of the launch to the distinct record it must equal."""
+order, or one strip repeated along its row): `idx` maps every tile of the launch to the distinct record it must equal.
+
+listed_cases() holds lists of at most 288 tiles, sorted, where every wave of a listed kernel takes one item; lists of more than two
+rounds of each listed kernel (unsorted ones too, a claimed length above the capacity, hundreds of handed-back tiles) are in
+tests/test_k1_listed_long_gpu.py, which builds its inputs with uniform_case.  K1T (the ring walk's fifth launch) on batches, views and
+long redo lists is in tests/test_k1t_views_gpu.py."""
 import json
 import sys
 import time

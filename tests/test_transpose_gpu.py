@@ -1,5 +1,7 @@
 """GPU: K2T and K1T (csrc/mtq_transpose.hip) against the reference's `transpose` results (F15) and the oracle on Xᵀ, the plugin on
-the hip backend, and `wq --backend hip --literal-metrics` against `--backend emulation`."""
+the hip backend, and `wq --backend hip --literal-metrics` against `--backend emulation`.  Every K1T input here is one fresh contiguous
+tensor; batches that are views (ld > cols, odd offsets and strides), the literal redo in a batch and over several rounds of its grid,
+and a matrix past element 2^31 are in tests/test_k1t_views_gpu.py."""
 import hashlib
 import json
 import subprocess
