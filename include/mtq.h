@@ -746,6 +746,37 @@ int mtq_packed_linear_skinny_grouped(const void *x, int64_t total_rows, int64_t 
                                      size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, int64_t count,
                                      int64_t n, const float *bias, int64_t ldb, void *y, int out_dtype, int64_t ldy, int split,
                                      void *workspace, size_t workspace_bytes, void *stream);
+/* The grouped form with a wave per 32-row CHUNK, for routings with hot experts: the same product, parameters (in the same order),
+ * argument checks and refusals as mtq_packed_linear_skinny_grouped, and the same bits.  The entry above gives a group's chunks to one
+ * wave, one after another, so an expert of hundreds of rows is the critical path of the launch; here a unit is (slice, 32-row chunk of a
+ * group, tile row), a wave each.  The chunk list comes from group_rows ON THE DEVICE: a one-workgroup plan kernel on `stream` clamps
+ * the groups as above, forms chunks_e = ceil((r1 - r0) / 32) and writes their exclusive prefix sum, count + 1 int32, into the head of
+ * the workspace; the main kernel follows on `stream`, and each of its waves finds its chunk's group by a search of that prefix.  Nothing
+ * is read back: the grid covers U = floor((total_rows + 31 * min(count, total_rows)) / 32) chunk slots, a bound that holds for disjoint
+ * groups (a group with rows adds at most 31/32 of a chunk) and is formed from the arguments alone; a wave whose slot is past the last
+ * chunk returns before any other load.
+ *
+ * Contract.  For nondecreasing group_rows the result equals mtq_packed_linear_skinny_grouped's bit for bit at the same `split` (the
+ * effective split of every (count, n, k, split), 0 included, is that entry's), in both output types, with and without bias: the wave
+ * does on its chunk what that entry's wave does on it.  Rows of y that belong to no group are not written.  Whatever group_rows holds,
+ * nothing outside total_rows x n of y or outside the workspace is written and no row of x at or past total_rows is read.  An array
+ * that decreases can clamp to groups that overlap; their chunks can then number more than U, the chunks past U are not computed, and
+ * the rows of the overlapping groups are unspecified, as above, inside the allocation; every row of a group that overlaps no other
+ * and whose chunks lie below U is as stated.  Deterministic: no atomics, no counters, no waiting between workgroups; nothing in the
+ * workspace needs initialising and nothing the call leaves there is needed by a later call (calls that share a workspace must be
+ * ordered on one stream).
+ *
+ * The workspace is NEVER empty: the size function's answer is the entry above's for the same arguments plus a plan region of
+ * (count + 1) * 4 bytes rounded up to 16 (a function of count alone), the plan first and the f32 partials behind it.  A workspace that
+ * is null, not 16-byte aligned or shorter than that answer is MTQ_ERR_INVALID before a device is looked for, at every split.
+ *
+ * Both symbols are optional: a build of this version may lack them. */
+/* HOST function: bytes of workspace for (total_rows, count, n, k, split), never 0.  MTQ_ERR_INVALID arguments give (size_t)-1. */
+size_t mtq_packed_linear_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split);
+int mtq_packed_linear_skinny_grouped_chunked(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                             const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                             const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                             int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream);
 /* Test hook: the skinny kernel's decode (a cheaper form of the block kernel's for exponent bytes M..254, the same code elsewhere)
  * beside the reference decode, for fmt MTQ_FMT_BFP8 / BFP4 / BFP2.  got, want: device uint32 [16][256][16][16] = [rot][E][q][i], the
  * float32 word of code (16 q + (i + rot) % 16) mod 2^(M + 1) at element i of a group with exponent byte E: every (E, code) at every

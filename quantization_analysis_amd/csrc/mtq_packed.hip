@@ -20,6 +20,9 @@
 //   packed_linear_skinny_kernel               the same product for m <= 32: one wave per (K slice, tile row), W straight to registers.
 //   packed_linear_skinny_grouped_kernel       that wave's work for every expert of an arena over the expert's own rows of X, one launch:
 //       for decode-sized groups (a group above 32 rows is walked in chunks and re-reads W; the block kernel is the route for large m).
+//   packed_grouped_plan_kernel, packed_linear_skinny_grouped_chunked_kernel
+//                                             the same product and bits with a wave per 32-row chunk of a group, for hot experts: the
+//       groups' chunk counts are prefix-summed on the device before the launch and each wave finds its group by a search of that prefix.
 //   packed_linear_wide_kernel                 the block kernel's bits from a 128 × 128 block whose waves decode whole tiles: for m >= 64.
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
@@ -869,6 +872,149 @@ __global__ __launch_bounds__(256) void skinny_grouped_reduce_kernel(const float 
     }
 }
 
+// ---- grouped skinny linear, a wave per 32-row chunk: the kernel above with its `for row0` loop handed out over waves.
+//
+// A unit is (slice s, chunk slot c, tile row tr), numbered ((s * slots + c) * tiles_h + tr): the four waves of a workgroup share a slice
+// and, but for a seam, a chunk, i.e. the same rows of X, as in the kernel above.  (Chunks of one group next to each other in a workgroup
+// would share a W run instead; a full chunk's X is 2 KiB a tile, no less than any packed tile, and X is what the waves of a workgroup
+// share at every routing, a one-chunk group included.)  The chunks of all groups are numbered through: group e owns chunks
+// [cstart[e], cstart[e + 1]), cstart the exclusive prefix sum of ceil(rows_e / 32) over the clamped groups, written by
+// packed_grouped_plan_kernel on the same stream before this kernel.  slots is the host's bound on cstart[count], formed from
+// (T, count) alone: floor((T + 31 min(count, T)) / 32).  A wave whose slot is at or past cstart[count] returns before any other load;
+// chunks at or past `slots` (overlapping groups of a decreasing group_rows only) are not computed.
+// The wave finds its group by search, not from a per-chunk table: cstart is count + 1 words whatever T is, a table would be `slots`
+// words written by a plan kernel that walks them; the search is wave-uniform (scalar loads) down to a window of 64 entries, which one
+// load, a lane each, and a ballot finish - for count <= 64 that one load is the whole search.
+// On its chunk the wave issues the loads and MFMAs of the kernel above for (expert, chunk, slice) in the same order: the same bits.
+
+// cstart[0 .. count], by one workgroup: thread k sums the chunk counts of groups [k * per, (k + 1) * per), the workgroup scans the 256
+// sums, and a second pass over the same run writes the prefix (packed_bases_kernel's pattern).  Sums are 64-bit and stored saturated at
+// INT32_MAX, above every slot number, so the prefix stays nondecreasing whatever group_rows holds.
+__global__ __launch_bounds__(256) void packed_grouped_plan_kernel(const int32_t *__restrict__ group_rows, int count, int T,
+                                                                  int32_t *__restrict__ cstart)
+{
+    __shared__ unsigned long long lds[4];
+    const int64_t per = ((int64_t)count + 255) / 256;
+    const int64_t i0 = std::min<int64_t>((int64_t)threadIdx.x * per, count), i1 = std::min<int64_t>(i0 + per, count);
+    unsigned long long sum = 0ull;
+    for (int64_t e = i0; e < i1; ++e) {
+        const GroupRows gr = group_rows_of(group_rows, e, T);
+        sum += (unsigned long long)((gr.r1 - gr.r0 + kTile - 1) / kTile);
+    }
+    unsigned long long total;
+    unsigned long long run = block_exclusive_scan(sum, lds, total);
+    for (int64_t e = i0; e < i1; ++e) {
+        cstart[e] = (int32_t)std::min<unsigned long long>(run, INT32_MAX);
+        const GroupRows gr = group_rows_of(group_rows, e, T);
+        run += (unsigned long long)((gr.r1 - gr.r0 + kTile - 1) / kTile);
+    }
+    if (threadIdx.x == 0) cstart[count] = (int32_t)std::min<unsigned long long>(total, INT32_MAX);
+}
+
+template <bool BF16OUT>
+__global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_linear_skinny_grouped_chunked_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
+    const int32_t *__restrict__ cstart, int slots, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+    const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets, const uint64_t *__restrict__ bases, int count, int N, int tiles_h,
+    int tiles_w, int split, const float *__restrict__ bias, int64_t ldb, void *__restrict__ yv, int64_t ldy, float *__restrict__ ws)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= (int64_t)tiles_h * slots * split) return;   // wave-uniform; the kernel has no barrier
+    const int64_t tr = unit % tiles_h, sc = unit / tiles_h, s = sc / slots;
+    const int c = (int)(sc % slots);
+    if (c >= cstart[count]) return;                  // a surplus slot: nothing else is read
+
+    // the group of chunk c: the last e with cstart[e] <= c.  cstart[lo] <= c < cstart[hi] throughout
+    int lo = 0, hi = count;
+    while (hi - lo > 64) {
+        const int mid = lo + (hi - lo) / 2;
+        if (cstart[mid] <= c) lo = mid;
+        else hi = mid;
+    }
+    const int at = lo + 1 + lane;
+    const int e = lo + (int)__popcll(__ballot(at < hi && cstart[at] <= c));
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    const int64_t row0 = gr.r0 + (int64_t)(c - cstart[e]) * kTile;
+    if (row0 >= gr.r1) return;                       // never for a prefix this launch's plan kernel wrote
+    const int64_t tiles = (int64_t)tiles_h * tiles_w;
+    const int8_t *map = maps + e * tiles;
+    const uint32_t *off = offsets + e * (tiles + 1);
+    const uint64_t base = bases[e], limit = std::min<uint64_t>(bases[e + 1], packed_bytes / kUnit);   // units
+    const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
+
+    const int row = lane & 31, half = lane >> 5, gi = 2 * row + half;
+    const int64_t n = tr * kTile + row;
+    const int64_t M = std::min<int64_t>(kTile, gr.r1 - row0);
+    const uint16_t *xc = x + row0 * ldx;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+
+    for (int64_t cb = c0; cb < c1; cb += 64) {
+        const int cnt = (int)std::min<int64_t>(64, c1 - cb);
+        int mf = -1, mo = 0;                         // lane i: map code and offset of tile cb + i
+        if (lane < cnt) {
+            const int64_t t = tr * tiles_w + cb + lane;
+            mf = map[t];
+            mo = (int)off[t];
+        }
+        for (int b = 0; b < cnt; b += kSkinnyRing) {
+            GroupRaw g[kSkinnyRing];
+            uint4 xl[kSkinnyRing], xh[kSkinnyRing];
+#pragma unroll
+            for (int j = 0; j < kSkinnyRing; ++j) {
+                const int i = b + j;                 // uniform
+                TileAt a;
+                a.off = 0;
+                a.f = -1;
+                xl[j] = make_uint4(0u, 0u, 0u, 0u);
+                xh[j] = xl[j];
+                if (i < cnt) {
+                    const int f = __builtin_amdgcn_readlane(mf, i);
+                    const uint64_t pos = base + (uint32_t)__builtin_amdgcn_readlane(mo, i);   // base <= limit < 2^58 where it counts
+                    const uint32_t size = packed_tile_bytes(f);
+                    a.off = pos * kUnit;
+                    a.f = (size == 0u || base > limit || pos + size / kUnit > limit) ? -1 : f;
+                    load_x16(xc, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
+                }
+                load_group(packed, a, gi, g[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < kSkinnyRing; ++j) {
+                if (b + j < cnt) {
+                    uint32_t y[kGroup];
+                    decode_skinny(g[j], y);
+                    uint4 wl, wh;
+                    pack_halves(y, wl, wh);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(wl), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(wh), acc, 0, 0, 0);
+                }
+            }
+        }
+    }
+
+    // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row)
+    if (n >= N) return;
+    const int64_t mh = row0 + 4 * half;
+    if (split == 1) {
+        const float bv = bias ? bias[e * ldb + n] : 0.0f;
+        const int64_t to = mh * ldy + n;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int mu = (r & 3) + 8 * (r >> 2);
+            if (mu + 4 * half < M) store_y<BF16OUT>(yv, to + mu * ldy, acc[r] + bv);
+        }
+    } else {
+        float *wl = ws + (s * T + mh) * N + n;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int mu = (r & 3) + 8 * (r >> 2);
+            if (mu + 4 * half < M) wl[mu * N] = acc[r];
+        }
+    }
+}
+
 // ---- wide linear (m above the decode range): packed_linear_kernel's bits from a 128 × 128 block.
 //
 // A workgroup of 4 waves, 2 (M) × 2 (N), owns a 128 (M) × 128 (N) block and walks K in steps of 64; each wave owns 64 × 64 outputs,
@@ -1449,6 +1595,74 @@ extern "C" int mtq_packed_linear_skinny_grouped(const void *x, int64_t total_row
             hipLaunchKernelGGL(skinny_grouped_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
     }
     return check_launch("mtq_packed_linear_skinny_grouped");
+}
+
+// The chunked entry's plan region: cstart[0 .. count] as int32 at the head of the workspace, rounded to 16 so that the f32 partials
+// behind it keep the workspace's alignment.  A function of count alone.
+static size_t grouped_plan_bytes(int64_t count)
+{
+    return (((size_t)count + 1) * sizeof(int32_t) + 15) & ~(size_t)15;
+}
+
+extern "C" size_t mtq_packed_linear_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    int64_t th, tw;
+    int eff;
+    if (grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
+    return grouped_plan_bytes(count) + skinny_workspace(total_rows, n, eff);
+}
+
+extern "C" int mtq_packed_linear_skinny_grouped_chunked(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                        const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                                        const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                                        int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                                        void *stream)
+{
+    if (!x || !group_rows || !packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    int eff;
+    if (int rc = grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if (bias && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
+    const size_t plan = grouped_plan_bytes(count), need = plan + skinny_workspace(total_rows, n, eff);
+    if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and the chunk plan needs one at every split");
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
+    if (workspace_bytes < need)
+        return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this call needs", workspace_bytes, need);
+    // every chunk of disjoint groups has a slot: a group with rows adds at most 31/32 of a chunk over its rows / 32
+    const int64_t slots = (total_rows + 31 * std::min(count, total_rows)) / kTile;
+    const int64_t blocks = (slots * th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    const int64_t nchunks = (n + 255) / 256;
+    if (slots > INT32_MAX || blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    int32_t *cstart = static_cast<int32_t *>(workspace);
+    float *ws = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + plan);
+    hipLaunchKernelGGL(packed_grouped_plan_kernel, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, cstart);
+    if (int rc = check_launch("mtq_packed_linear_skinny_grouped_chunked")) return rc;
+    const dim3 grid((unsigned)blocks), block(64 * kSkinnyWaves);
+    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(packed_linear_skinny_grouped_chunked_kernel<true>, grid, block, 0, st, xp, total_rows, k, ldx, x_vec, group_rows, cstart,
+                           (int)slots, pp, (uint64_t)packed_bytes, maps, offsets, bases, count, n, th, tw, eff, bias, ldb, y, ldy, ws);
+    else
+        hipLaunchKernelGGL(packed_linear_skinny_grouped_chunked_kernel<false>, grid, block, 0, st, xp, total_rows, k, ldx, x_vec, group_rows, cstart,
+                           (int)slots, pp, (uint64_t)packed_bytes, maps, offsets, bases, count, n, th, tw, eff, bias, ldb, y, ldy, ws);
+    if (eff > 1) {
+        if (int rc = check_launch("mtq_packed_linear_skinny_grouped_chunked")) return rc;
+        const dim3 rgrid((unsigned)(count * nchunks));
+        if (out_dtype == MTQ_DTYPE_BF16)
+            hipLaunchKernelGGL(skinny_grouped_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
+        else
+            hipLaunchKernelGGL(skinny_grouped_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
+    }
+    return check_launch("mtq_packed_linear_skinny_grouped_chunked");
 }
 
 extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)

@@ -123,6 +123,8 @@ SIGNATURES = {
     "mtq_packed_linear_skinny_grouped_workspace_bytes": ("z", "lllli", True),
     "mtq_packed_linear_skinny_grouped": ("i", "plllppzpppllplpilipzp", True),
     "mtq_packed_linear_wide": ("i", "plllpzpplppilp", True),
+    "mtq_packed_linear_skinny_grouped_chunked_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_linear_skinny_grouped_chunked": ("i", "plllppzpppllplpilipzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1187,6 +1189,13 @@ def packed_linear_skinny_grouped(x, group_rows, arena, maps_dev, offsets_dev, ba
     into [0, T]); bias: None or a float32 (count, n) device tensor with contiguous rows.  → (T, n); an `out` allocated here starts as
     zeros, so rows outside every group are zeros.  workspace: as packed_linear_skinny, of
     packed_linear_skinny_grouped_workspace_bytes(T, count, n, k, split) bytes."""
+    return _packed_linear_grouped_call("mtq_packed_linear_skinny_grouped", packed_linear_skinny_grouped_workspace_bytes, x, group_rows, arena,
+                                       maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out, split, workspace, stream)
+
+
+def _packed_linear_grouped_call(name, workspace_bytes, x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out,
+                                split, workspace, stream):
+    """The checks and the call the two grouped entries share; `workspace_bytes` is the entry's own size function."""
     torch = _torch()
     out_dtype = out_dtype or torch.float32
     code = _packed_out_code(out_dtype)
@@ -1207,8 +1216,8 @@ def packed_linear_skinny_grouped(x, group_rows, arena, maps_dev, offsets_dev, ba
         if bias.dtype != torch.float32 or bias.dim() != 2 or tuple(bias.shape) != (count, n) or bias.stride(1) != 1 or not bias.is_cuda:
             raise MtqError(f"bias must be a float32 ({count}, {n}) device tensor with contiguous rows")
         bias_ptr, ldb = bias.data_ptr(), bias.stride(0) if count > 1 else max(bias.stride(0), n)
-    need = packed_linear_skinny_grouped_workspace_bytes(T, count, n, k, split)
-    fn = _entry("mtq_packed_linear_skinny_grouped")
+    need = workspace_bytes(T, count, n, k, split)
+    fn = _entry(name)
     if out is None:
         require_gpu()
         out = torch.zeros((T, n), dtype=out_dtype, device=x.device)
@@ -1226,6 +1235,32 @@ def packed_linear_skinny_grouped(x, group_rows, arena, maps_dev, offsets_dev, ba
     check(fn(x.data_ptr(), T, k, ldx, pg, ptr, arena.numel(), pm, po, pb, count, n, bias_ptr, ldb, out.data_ptr(), code, ldy, int(split),
              ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
     return out
+
+
+def has_packed_linear_grouped_chunked() -> bool:
+    """Whether this build of the library has mtq_packed_linear_skinny_grouped_chunked and its size function (optional symbols: an older
+    build of the same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None
+               for name in ("mtq_packed_linear_skinny_grouped_chunked", "mtq_packed_linear_skinny_grouped_chunked_workspace_bytes"))
+
+
+def packed_linear_skinny_grouped_chunked_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_linear_skinny_grouped_chunked_workspace_bytes (a host function: no GPU): packed_linear_skinny_grouped_workspace_bytes
+    for the same arguments plus the chunk plan's (count + 1) * 4 bytes rounded up to 16.  Never 0."""
+    size = int(_entry("mtq_packed_linear_skinny_grouped_chunked_workspace_bytes")(int(total_rows), int(count), int(n), int(k), int(split)))
+    if size == ctypes.c_size_t(-1).value:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return size
+
+
+def packed_linear_skinny_grouped_chunked(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None,
+                                         out=None, split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_linear_skinny_grouped_chunked on the current stream: packed_linear_skinny_grouped's product, arguments and bits with a
+    wave per 32-row chunk of a group (the chunk list is made from group_rows on the device, nothing is read back), for routings with
+    hot experts.  workspace: of packed_linear_skinny_grouped_chunked_workspace_bytes(T, count, n, k, split) bytes, needed at every
+    split; allocated here when none is given."""
+    return _packed_linear_grouped_call("mtq_packed_linear_skinny_grouped_chunked", packed_linear_skinny_grouped_chunked_workspace_bytes, x,
+                                       group_rows, arena, maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out, split, workspace, stream)
 
 
 def debug_packed_decode(fmt: str):

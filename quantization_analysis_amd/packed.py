@@ -667,8 +667,35 @@ def clamp_group_rows(group_rows, total_rows: int):
     return r0, np.minimum(np.maximum(g[1:], r0), total_rows)
 
 
+GROUPED_KERNELS = ("walk", "chunks", "auto")
+# What "auto" means.  The two kernels give the same bits, so this decides time alone, by the rule of DESIGN.md §A.6m: "chunks", because
+# in profiles/packed_linear_grouped_chunked.txt its median at split 0 is below the walking entry's minimum on every row, the four rows
+# with 4 rows per expert included (0.945–0.952) and the sparse rows at 0.19–0.52.  Shapes and counts outside that record are unmeasured.
+GROUPED_AUTO_KERNEL = "chunks"
+
+
+def _grouped_kernel(kernel: str) -> str:
+    """`kernel` of the grouped entries, "auto" resolved."""
+    if kernel not in GROUPED_KERNELS:
+        raise MtqError(f"kernel must be one of {GROUPED_KERNELS}, got {kernel!r}")
+    return GROUPED_AUTO_KERNEL if kernel == "auto" else kernel
+
+
+def _grouped_entries(kernel: str):
+    """(the launch, its workspace-size function) of hip_backend for a resolved grouped kernel; "chunks" on a library without the symbol is
+    an error, never the other kernel."""
+    from . import hip_backend as hb
+
+    if kernel == "walk":
+        return hb.packed_linear_skinny_grouped, hb.packed_linear_skinny_grouped_workspace_bytes
+    if not hb.has_packed_linear_grouped_chunked():
+        raise MtqError('kernel="chunks" needs mtq_packed_linear_skinny_grouped_chunked, which this build of libmtq_hip.so lacks: rebuild it '
+                       'from this tree, or use kernel="walk"')
+    return hb.packed_linear_skinny_grouped_chunked, hb.packed_linear_skinny_grouped_chunked_workspace_bytes
+
+
 def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
-                   workspace=None):
+                   workspace=None, kernel: str = "walk"):
     """Y[rows of group e] = X[rows of group e]·Ŵ[e]ᵀ (+ bias[e]) for all experts of a batch at once → (T, n).
 
     x: (T, k); group_rows: count + 1 entries, group e owning rows [group_rows[e], group_rows[e + 1]) — a list or NumPy array is checked
@@ -679,7 +706,11 @@ def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "flo
     hip (the default when the arena is on the device): one launch of mtq_packed_linear_skinny_grouped (two with a split over K; `split`
     and `workspace` as in linear(kernel="skinny")), for decode-sized groups: for every group and 32-row chunk of it the bits of
     linear(kernel="skinny") on that chunk and that expert at the same effective split.  Rows outside every group are zeros.
-    emulation: per group the float64 product of the decoded weight, rounded once, as linear does."""
+    kernel (GROUPED_KERNELS): "walk", one wave per (slice, expert, tile row) that walks the expert's 32-row chunks; "chunks",
+    mtq_packed_linear_skinny_grouped_chunked, one wave per (slice, chunk, tile row) with the chunk list made on the device, for routings
+    with hot experts — the same bits, a workspace at every split, MtqError when the library lacks it; "auto", GROUPED_AUTO_KERNEL.
+    emulation: per group the float64 product of the decoded weight, rounded once, as linear does, under every kernel name."""
+    kernel = _grouped_kernel(kernel)
     batch = _resolve_batch(pts_or_batch)
     if out_dtype not in ("float32", "bfloat16"):
         raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
@@ -698,6 +729,7 @@ def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "flo
     if backend == "hip":
         from . import hip_backend as hb
 
+        launch = None if kernel == "walk" else _grouped_entries(kernel)[0]      # a missing kernel is refused before any device work
         batch = batch_to_device(batch)
         dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
         if T == 0:
@@ -706,8 +738,11 @@ def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "flo
             group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(batch.arena.device)
         if bias is not None and not _is_torch(bias):
             bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32)).to(batch.arena.device)
-        return hb.packed_linear_skinny_grouped(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias,
-                                               out_dtype=dtype, split=split, workspace=workspace)
+        if launch is None:                           # "walk": looked up here, by name, as before there was a choice
+            return hb.packed_linear_skinny_grouped(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias,
+                                                   out_dtype=dtype, split=split, workspace=workspace)
+        return launch(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias, out_dtype=dtype,
+                      split=split, workspace=workspace)
     xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
     if on_device:                                    # trusted, as on hip: what the kernel makes of it
         if tuple(group_rows.shape) != (count + 1,):
@@ -730,14 +765,15 @@ def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "flo
     return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
 
 
-def linear_batch(x3d, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0, workspace=None):
+def linear_batch(x3d, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0, workspace=None,
+                 kernel: str = "walk"):
     """x3d (count, m, k): expert e multiplies x3d[e] → (count, m, n).  linear_grouped with group_rows = m * arange(count + 1)."""
     batch = _resolve_batch(pts_or_batch)
     if len(x3d.shape) != 3 or x3d.shape[0] != batch.count or x3d.shape[2] != batch.cols:
         raise MtqError(f"x3d must be ({batch.count}, m, {batch.cols}), got {tuple(x3d.shape)}")
     m = int(x3d.shape[1])
     y = linear_grouped(x3d.reshape(batch.count * m, batch.cols), m * np.arange(batch.count + 1, dtype=np.int64), batch,
-                       bias=bias, out_dtype=out_dtype, backend=backend, split=split, workspace=workspace)
+                       bias=bias, out_dtype=out_dtype, backend=backend, split=split, workspace=workspace, kernel=kernel)
     return y.reshape(batch.count, m, batch.rows)
 
 
@@ -810,10 +846,13 @@ def _packed_experts_class():
         """The experts of one batch as a module.  INFERENCE ONLY, as PackedLinear.  forward(x, group_rows): x (T, k), group e owning
         rows [group_rows[e], group_rows[e + 1]) → (T, n) through linear_grouped.  The batch is made once, here (as_batch for a list), and
         every forward multiplies with that arena: hip: the arena, its tables and the bias stay on the device, no host work per expert
-        and no synchronisation in forward (with a device group_rows), and the workspace grows to the largest T seen.  emulation: CPU tensors, the float64 product."""
+        and no synchronisation in forward (with a device group_rows), and the workspace grows to the largest T seen.  emulation: CPU tensors, the float64 product.
+        kernel: as linear_grouped's, resolved here; the kept workspace is sized by the size function of the kernel in use."""
 
-        def __init__(self, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0):
+        def __init__(self, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
+                     kernel: str = "walk"):
             super().__init__()
+            self.kernel = _grouped_kernel(kernel)
             if out_dtype not in ("float32", "bfloat16"):
                 raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
             batch = _resolve_batch(pts_or_batch)                # once: forward hands the batch down and walks no list
@@ -821,6 +860,8 @@ def _packed_experts_class():
             if self.backend not in BACKENDS:
                 raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
             if self.backend == "hip":
+                if self.kernel != "walk":
+                    _grouped_entries(self.kernel)   # a library without the kernel is refused here, not at the first forward
                 batch = batch_to_device(batch)
             self.batch = batch
             self.out_dtype, self.split = out_dtype, int(split)
@@ -836,7 +877,7 @@ def _packed_experts_class():
 
         def extra_repr(self) -> str:
             return f"count={self.count}, in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, " \
-                   f"backend={self.backend!r}, split={self.split}"
+                   f"backend={self.backend!r}, split={self.split}" + ("" if self.kernel == "walk" else f", kernel={self.kernel!r}")
 
         @torch.no_grad()
         def forward(self, x, group_rows):
@@ -846,11 +887,12 @@ def _packed_experts_class():
             if self.backend == "hip" and T:
                 from . import hip_backend as hb
 
-                need = hb.packed_linear_skinny_grouped_workspace_bytes(T, self.count, self.out_features, self.in_features, self.split)
+                size = hb.packed_linear_skinny_grouped_workspace_bytes if self.kernel == "walk" else _grouped_entries(self.kernel)[1]
+                need = size(T, self.count, self.out_features, self.in_features, self.split)
                 if need and (self._workspace is None or self._workspace.numel() < need):
                     self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.batch.arena.device)
             y = linear_grouped(x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype,
-                               backend=self.backend, split=self.split, workspace=self._workspace)
+                               backend=self.backend, split=self.split, workspace=self._workspace, kernel=self.kernel)
             return y if _is_torch(y) else torch.from_numpy(y)
 
     return PackedExperts

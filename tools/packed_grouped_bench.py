@@ -4,13 +4,17 @@ warm-up (the method of DESIGN.md §A.6g: sides alternated in one process, --roun
   grouped : the grouped C entry with a workspace allocated once, one side per value of --splits (0 = the library's choice);
   loop    : mtq_packed_linear_skinny per non-empty group (per 32-row chunk of a larger group) at the library's split, the C entry with
             prebuilt arguments and one workspace: the route a caller has without the grouped entry;
-  matmul  : torch.matmul per non-empty group on the unpacked bf16 Ŵ, for information.
+  matmul  : torch.matmul per non-empty group on the unpacked bf16 Ŵ, for information;
+  chunked : with --chunked, mtq_packed_linear_skinny_grouped_chunked (a wave per 32-row chunk, the chunk list made on the device) at the
+            same splits, alternated with the other sides; its output is compared with the grouped entry's bit for bit, and the run ends
+            with the two questions DESIGN.md §A.6m asks of it, answered from this run's numbers alone.
 
 Experts of --shapes (n x k), bf16 storage, maps drawn with 85 % bfp8 and 15 % bfp4 tiles (the mix the greedy search leaves on such
 weights), --counts experts.  Routings: `uniform` gives every expert 4 rows; `sparse` spreads 512 rows over the experts with a seeded skewed
 draw that leaves many of them empty (the seed and the histogram are printed).
 
   python tools/packed_grouped_bench.py [--rounds 3] [--window-ms 20] [--out profiles/packed_linear_grouped.txt] [--json out.json]
+  python tools/packed_grouped_bench.py --chunked --out profiles/packed_linear_grouped_chunked.txt
 """
 from __future__ import annotations
 
@@ -65,6 +69,7 @@ def main() -> int:
     p.add_argument("--routings", default="uniform,sparse")
     p.add_argument("--splits", default="1,2,4,0")
     p.add_argument("--seed", type=int, default=123)
+    p.add_argument("--chunked", action="store_true", help="add the chunked grouped entry as a side at every split")
     p.add_argument("--out", default=None)
     p.add_argument("--json", default=None)
     args = p.parse_args()
@@ -82,6 +87,8 @@ def main() -> int:
     say(f"# grouped packed linear on {torch.cuda.get_device_name(0)}; device events, {args.rounds} rounds of ~{args.window_ms:.0f} ms windows, "
         f"sides alternated; bf16 output; maps 85% bfp8 / 15% bfp4; seed {args.seed}")
     gentry, sentry = hb._entry("mtq_packed_linear_skinny_grouped"), hb._entry("mtq_packed_linear_skinny")
+    centry = hb._entry("mtq_packed_linear_skinny_grouped_chunked") if args.chunked else None
+    verdict = []                                             # per row: what the expectation and the rule for "auto" need
     for shape in args.shapes.split(","):
         n, k = (int(v) for v in shape.split("x"))
         th, tw = hb.tiles_hw(n, k)
@@ -108,7 +115,7 @@ def main() -> int:
                 x = torch.randn((T, k), generator=g, device="cuda").to(torch.bfloat16)
                 grd = torch.from_numpy(gr.astype(np.int32)).cuda()
                 ya = torch.zeros((T, n), dtype=torch.bfloat16, device="cuda")
-                yb, yc = torch.zeros_like(ya), torch.zeros_like(ya)
+                yb, yc, yd = torch.zeros_like(ya), torch.zeros_like(ya), torch.zeros_like(ya)
                 sides = []
                 for split in (int(v) for v in args.splits.split(",")):
                     need = hb.packed_linear_skinny_grouped_workspace_bytes(T, count, n, k, split)
@@ -121,6 +128,20 @@ def main() -> int:
                             ws.data_ptr(), need, stream)
                     sides.append({"name": f"grouped split={split} (eff {eff})", "split": split, "eff": eff, "ws": ws,
                                   "fn": (lambda call=call: hb.check(gentry(*call)))})
+                for split in (int(v) for v in args.splits.split(",")) if args.chunked else ():
+                    need = hb.packed_linear_skinny_grouped_chunked_workspace_bytes(T, count, n, k, split)
+                    eff = max(1, hb.packed_linear_skinny_grouped_workspace_bytes(T, count, n, k, split) // (4 * T * n))
+                    ws = torch.empty((need,), dtype=torch.uint8, device="cuda")
+                    hb.packed_linear_skinny_grouped_chunked(x, grd, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n,
+                                                            out_dtype=torch.bfloat16, out=yd, split=split, workspace=ws)   # the wrapper's checks, once
+                    hb.packed_linear_skinny_grouped(x, grd, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n,
+                                                    out_dtype=torch.bfloat16, out=ya, split=split)
+                    same = bool(torch.equal(yd.view(torch.int16), ya.view(torch.int16)))
+                    call = (x.data_ptr(), T, k, k, grd.data_ptr(), batch.arena.data_ptr(), batch.arena.numel(), batch.maps_dev.data_ptr(),
+                            batch.offsets_dev.data_ptr(), batch.bases_dev.data_ptr(), count, n, None, 0, yd.data_ptr(), hb.DTYPE_BF16, n, split,
+                            ws.data_ptr(), need, stream)
+                    sides.append({"name": f"chunked split={split} (eff {eff})", "csplit": split, "eff": eff, "ws": ws, "same": same,
+                                  "fn": (lambda call=call: hb.check(centry(*call)))})
                 # the loop of single-tensor skinny calls at the library's split, one workspace for all
                 chunks = [(e, r, min(32, int(gr[e + 1]) - r)) for e in range(count) for r in range(int(gr[e]), int(gr[e + 1]), 32)]
                 need1 = max(hb.packed_linear_skinny_workspace_bytes(c, n, k, 0) for _e, _r, c in chunks)
@@ -152,6 +173,15 @@ def main() -> int:
                 scale = float(yc.float().abs().max().clamp_min(1e-30))
                 err_b = float((yb.float() - yc.float()).abs().max()) / scale
                 loop_min = min(sides[-2]["ts"])
+                if args.chunked:
+                    walk = {s["split"]: s["ts"] for s in sides if "split" in s}
+                    chunk = {s["csplit"]: s["ts"] for s in sides if "csplit" in s}
+                    verdict.append({"row": f"{n}x{k} count={count} {kind}", "kind": kind, "loop_min": loop_min,
+                                    "chunk1_median": statistics.median(chunk[1]) if 1 in chunk else None,
+                                    "chunk0_median": statistics.median(chunk[0]) if 0 in chunk else None,
+                                    "walk0_min": min(walk[0]) if 0 in walk else None,
+                                    "spread": max(statistics.median(s["ts"]) / min(s["ts"]) for s in sides[:-1]),   # the packed sides; not torch.matmul's
+                                    "same_bits": all(s["same"] for s in sides if "csplit" in s)})
                 for s in sides:
                     med, mn = statistics.median(s["ts"]), min(s["ts"])
                     row = {"n": n, "k": k, "count": count, "routing": kind, "T": T, "active": active, "side": s["name"], "ms_median": med,
@@ -162,13 +192,38 @@ def main() -> int:
                         torch.cuda.synchronize()
                         row.update(split=s["split"], split_eff=s["eff"], max_rel_diff=float((ya.float() - yc.float()).abs().max()) / scale)
                         extra = f"  max rel diff to matmul {row['max_rel_diff']:.2e}"
+                    if "csplit" in s:
+                        row.update(chunked_split=s["csplit"], split_eff=s["eff"], same_bits_as_grouped=s["same"])
+                        extra = f"  bits {'equal to' if s['same'] else 'DIFFER from'} grouped at this split"
                     rows_out.append(row)
                     say(f"{s['name']:34s} {med * 1e3:9.1f} us (min {mn * 1e3:9.1f}, spread {(med - mn) / med * 100:4.1f}%)  {active_mb / med:8.1f} GB/s of "
                         f"active streams  /loop-min {med / loop_min:6.3f}{extra}")
                 say(f"{'loop vs matmul':34s} max rel diff {err_b:.2e}")
-                del sides, lcalls, x, ya, yb, yc, ws1
+                del sides, lcalls, x, ya, yb, yc, yd, ws1
             del pts, batch, what
             torch.cuda.empty_cache()
+    if verdict and all(v["chunk1_median"] is not None and v["chunk0_median"] is not None and v["walk0_min"] is not None for v in verdict):
+        spread = max(v["spread"] for v in verdict)           # the run's own noise: the largest median / min over the packed sides of every row
+        say(f"## the questions of DESIGN.md A.6m, from this run alone (spread = largest median/min of any grouped, chunked or loop side of any row = {spread:.4f})")
+        say(f"bits: chunked equal to grouped at every row and split: {all(v['same_bits'] for v in verdict)}")
+        holds = []
+        for v in verdict:
+            ok = v["chunk1_median"] < v["loop_min"]
+            holds.append(ok)
+            say(f"expectation  {v['row']:34s} chunked split=1 median {v['chunk1_median'] * 1e3:9.1f} us {'<' if ok else '>='} loop min "
+                f"{v['loop_min'] * 1e3:9.1f} us  ratio {v['chunk1_median'] / v['loop_min']:6.3f}  {'holds' if ok else 'FAILS'}")
+        say(f"expectation (chunked split=1 median below the loop's minimum at every row): {'HOLDS' if all(holds) else 'FAILS'} "
+            f"({sum(holds)} of {len(holds)} rows)")
+        rule = []
+        for v in verdict:
+            bound = v["walk0_min"] * (1.0 if v["kind"] == "sparse" else spread)
+            ok = v["chunk0_median"] < bound if v["kind"] == "sparse" else v["chunk0_median"] <= bound
+            rule.append(ok)
+            say(f"auto rule    {v['row']:34s} chunked split=0 median {v['chunk0_median'] * 1e3:9.1f} us vs grouped split=0 min "
+                f"{v['walk0_min'] * 1e3:9.1f} us{'' if v['kind'] == 'sparse' else f' x spread = {bound * 1e3:9.1f} us'}  ratio "
+                f"{v['chunk0_median'] / v['walk0_min']:6.3f}  {'passes' if ok else 'DECIDES AGAINST'}")
+        say(f"auto rule (sparse rows: below grouped's min; other rows: within the spread of it): GROUPED_AUTO_KERNEL = "
+            f"{'chunks' if all(rule) else 'walk'}")
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text("\n".join(lines) + "\n")
