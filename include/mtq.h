@@ -728,7 +728,8 @@ int mtq_packed_linear_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, c
  * against packed_bytes and reads as zeros when it passes either, as does a tile whose map code is outside 0..3.
  *
  * One wave per (slice, group, tile row); a group above 32 rows is walked in chunks of 32 rows by the same wave, which reads the weight
- * again for every chunk: the entry is for decode-sized groups, and mtq_packed_linear per expert is the route for large m.  For every
+ * again for every chunk: the entry is for decode-sized groups, and mtq_packed_linear per expert is the route for large m (for all
+ * experts in one launch: mtq_packed_linear_wide_grouped, below).  For every
  * group and every 32-row chunk of it the result is bit for bit what mtq_packed_linear_skinny gives for that chunk and that expert's
  * stream and tables at the same effective split.  An effective split above 1 writes f32 partials to workspace[slice][total_rows][n]
  * with plain stores and a second kernel on `stream` sums them in ascending slice order, adds the group's bias last and rounds a bf16 y
@@ -777,6 +778,45 @@ int mtq_packed_linear_skinny_grouped_chunked(const void *x, int64_t total_rows, 
                                              const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
                                              const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
                                              int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream);
+/* The grouped form of mtq_packed_linear_wide, for experts that hold hundreds of rows (MoE prefill): the parameters of
+ * mtq_packed_linear_skinny_grouped_chunked in its order, without `split` - there is no split over K and there are no partial sums.  The
+ * two entries above run the skinny kernel's wave on 32 rows at a time, so an expert's stream is read and decoded once per 32 rows; here a
+ * workgroup owns 128 rows x 128 columns of ONE group and does on them what mtq_packed_linear_wide's workgroup does, so the stream is
+ * decoded once per 128 rows.  The block list comes from group_rows ON THE DEVICE, as the chunked entry's chunk list does: a one-workgroup
+ * plan kernel on `stream` clamps the groups as above, forms blocks_e = ceil((r1 - r0) / 128) and writes their exclusive prefix sum,
+ * count + 1 int32 saturated at INT32_MAX, into the head of the workspace; the main kernel follows on `stream` and each of its
+ * workgroups finds its block's group by the chunked kernel's search of that prefix.  Nothing is read back: the grid covers
+ * U = floor((total_rows + 127 * min(count, total_rows)) / 128) row-block slots (times ceil(n / 128) column blocks, the column block
+ * fastest), a bound that holds for disjoint groups (a group with rows adds at most 127/128 of a block) and is formed from the arguments
+ * alone; a workgroup whose slot is past the last block returns before any other load and before any barrier.
+ *
+ * Bit contract.  For nondecreasing group_rows and every group with rows, y[r0:r1] equals bit for bit what mtq_packed_linear gives for
+ * x[r0:r1] with expert e's stream and tables (and bias row e); mtq_packed_linear_wide gives the same bits.  This holds in both output
+ * types, with and without bias, and for any ldx / ldy (x is read by 16-byte loads when it is 16-byte aligned with ldx % 8 == 0 and
+ * k % 8 == 0, element by element otherwise).  These are the BLOCK family's bits, not the skinny family's: the two families sum in
+ * different orders, so this entry and the two grouped entries above may differ in the last bits, which is why it is an entry of its own.
+ * Rows of y that belong to no group are not written.  Whatever group_rows holds, nothing outside total_rows x n of y or outside the
+ * workspace is written and no row of x at or past total_rows is read: every row limit of a block is its group's clamped end.  A blob is
+ * checked on the device against its group's own stream [64 * bases[e], 64 * bases[e + 1]) and against packed_bytes and multiplies as
+ * zeros when it passes either, as does a tile whose map code is outside 0..3; what the kernel loads for such a tile comes from the
+ * arena's first 320 bytes.  An array that decreases can clamp to groups that overlap; their blocks can then number more than U, the
+ * blocks past U are not computed, and the rows of the overlapping groups are unspecified inside the allocation; every row of a group
+ * that overlaps no other and whose blocks lie below U is as stated.  Deterministic: no atomics, no counters, nothing waits on another
+ * workgroup; nothing in the workspace needs initialising and nothing the call leaves there is needed by a later call (calls that share
+ * a workspace must be ordered on one stream).
+ *
+ * The workspace holds the plan only: (count + 1) * 4 bytes rounded up to 16, a function of count alone, never 0.  Arguments are
+ * checked as by the chunked entry, minus the split (null pointers, total_rows, count, n, k positive, the tile grid, ldx / ldy / ldb, an
+ * arena below 320 bytes per tile or not 16-byte aligned, a workspace that is null, not 16-byte aligned or too short):
+ * MTQ_ERR_INVALID before a device is looked for.
+ *
+ * Both symbols are optional: a build of this version may lack them. */
+/* HOST function: bytes of workspace for (total_rows, count, n, k): the plan region, never 0.  MTQ_ERR_INVALID arguments give (size_t)-1. */
+size_t mtq_packed_linear_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k);
+int mtq_packed_linear_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows, const void *packed,
+                                   size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, int64_t count,
+                                   int64_t n, const float *bias, int64_t ldb, void *y, int out_dtype, int64_t ldy, void *workspace,
+                                   size_t workspace_bytes, void *stream);
 /* Test hook: the skinny kernel's decode (a cheaper form of the block kernel's for exponent bytes M..254, the same code elsewhere)
  * beside the reference decode, for fmt MTQ_FMT_BFP8 / BFP4 / BFP2.  got, want: device uint32 [16][256][16][16] = [rot][E][q][i], the
  * float32 word of code (16 q + (i + rot) % 16) mod 2^(M + 1) at element i of a group with exponent byte E: every (E, code) at every

@@ -24,6 +24,9 @@
 //                                             the same product and bits with a wave per 32-row chunk of a group, for hot experts: the
 //       groups' chunk counts are prefix-summed on the device before the launch and each wave finds its group by a search of that prefix.
 //   packed_linear_wide_kernel                 the block kernel's bits from a 128 × 128 block whose waves decode whole tiles: for m >= 64.
+//   packed_grouped_wide_plan_kernel, packed_linear_wide_grouped_kernel
+//                                             that block for every expert of an arena over the expert's own rows, one launch: the groups'
+//       128-row block counts are prefix-summed on the device and each workgroup finds its group by the chunked kernel's search.
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
 // blob does not fit is not written (pack), not stored (unpack) or read as zeros (linear).
@@ -1234,6 +1237,260 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
     }
 }
 
+// ---- grouped wide linear: packed_linear_wide_kernel's block for every expert of an arena over the expert's own rows, one launch.
+//
+// The 128-row blocks of all groups are numbered through, as the chunked kernel numbers 32-row chunks: group e owns blocks
+// [bstart[e], bstart[e + 1]), bstart the exclusive prefix sum of ceil(rows_e / 128) over the clamped groups, written by
+// packed_grouped_wide_plan_kernel on the same stream before this kernel.  The grid is slots × ceil(N / 128) workgroups, the column block
+// fastest; slots is the host's bound on bstart[count], formed from (T, count) alone: floor((T + 127 min(count, T)) / 128).  A workgroup
+// whose slot is at or past bstart[count] returns before any other load and before any barrier; blocks at or past `slots` (overlapping
+// groups of a decreasing group_rows only) are not computed.  The group of a slot is found by the chunked kernel's search, by every wave
+// alike: the group, its rows, its tables and its stream are uniform over the workgroup and live in scalar registers.
+// On its block the workgroup does what packed_linear_wide_kernel does for x[r0:r1] and expert e's stream and tables at row block
+// (slot - bstart[e]): M is the group's end r1 (every row limit, the clamped 16-byte X loads included), a blob is checked against the
+// group's own stream and against packed_bytes, an absent tile's unconditional loads read the arena's first 320 bytes.  The same loads,
+// decode and MFMAs in the same order: that kernel's bits, which are the block kernel's.
+
+// bstart[0 .. count] by one workgroup: packed_grouped_plan_kernel with 128-row blocks for 32-row chunks.
+__global__ __launch_bounds__(256) void packed_grouped_wide_plan_kernel(const int32_t *__restrict__ group_rows, int count, int T,
+                                                                       int32_t *__restrict__ bstart)
+{
+    __shared__ unsigned long long lds[4];
+    const int64_t per = ((int64_t)count + 255) / 256;
+    const int64_t i0 = std::min<int64_t>((int64_t)threadIdx.x * per, count), i1 = std::min<int64_t>(i0 + per, count);
+    unsigned long long sum = 0ull;
+    for (int64_t e = i0; e < i1; ++e) {
+        const GroupRows gr = group_rows_of(group_rows, e, T);
+        sum += (unsigned long long)((gr.r1 - gr.r0 + kWideBM - 1) / kWideBM);
+    }
+    unsigned long long total;
+    unsigned long long run = block_exclusive_scan(sum, lds, total);
+    for (int64_t e = i0; e < i1; ++e) {
+        bstart[e] = (int32_t)std::min<unsigned long long>(run, INT32_MAX);
+        const GroupRows gr = group_rows_of(group_rows, e, T);
+        run += (unsigned long long)((gr.r1 - gr.r0 + kWideBM - 1) / kWideBM);
+    }
+    if (threadIdx.x == 0) bstart[count] = (int32_t)std::min<unsigned long long>(total, INT32_MAX);
+}
+
+// A 64-bit value every lane of the wave holds alike, into scalar registers.
+__device__ __forceinline__ uint64_t uniform64(uint64_t v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// 256 VGPRs at two waves per SIMD, as packed_linear_wide_kernel: re-read `make report` on any edit.
+template <bool XV, bool BF16OUT>
+__global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_grouped_kernel(
+    const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
+    const uint8_t *__restrict__ packed, uint64_t packed_bytes, const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets,
+    const uint64_t *__restrict__ bases, int count, int64_t N, int64_t tiles_h, int64_t tiles_w, const float *__restrict__ bias, int64_t ldb,
+    void *__restrict__ yv, int64_t ldy)
+{
+    constexpr int BM = kWideBM, MT = BM / 64, XP = BM * 8 / kThreads;
+    constexpr int kImage = (BM + kWideBN) * kLdk;
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kImage];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
+    const int slot = (int)(blockIdx.x / nblocks);
+    const int64_t bn = blockIdx.x % nblocks;
+    if (slot >= bstart[count]) return;               // a surplus slot: nothing else is read; uniform over the workgroup, before any barrier
+
+    // the group of block `slot`: the last e with bstart[e] <= slot.  bstart[lo] <= slot < bstart[hi] throughout
+    int lo = 0, hi = count;
+    while (hi - lo > 64) {
+        const int mid = lo + (hi - lo) / 2;
+        if (bstart[mid] <= slot) lo = mid;
+        else hi = mid;
+    }
+    const int at = lo + 1 + lane;
+    const int e = __builtin_amdgcn_readfirstlane(lo + (int)__popcll(__ballot(at < hi && bstart[at] <= slot)));
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    const int64_t r0 = __builtin_amdgcn_readfirstlane((int)gr.r0), M = __builtin_amdgcn_readfirstlane((int)gr.r1);   // 0 <= r0 <= M <= T
+    const int64_t m0 = r0 + (int64_t)BM * (slot - __builtin_amdgcn_readfirstlane(bstart[e]));
+    if (m0 >= M) return;                             // never for a prefix this launch's plan kernel wrote
+    const int64_t n0 = bn * kWideBN;
+    const int64_t steps = (K + kBK - 1) / kBK;
+    const int64_t tiles = tiles_h * tiles_w;
+    const int8_t *map = maps + e * tiles;
+    const uint32_t *off = offsets + e * (tiles + 1);
+    const uint64_t base = uniform64(bases[e]), limit = uniform64(std::min<uint64_t>(bases[e + 1], packed_bytes / kUnit));   // units
+
+    f32x16 acc[MT][2];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
+
+    const int64_t wtr = (n0 >> 5) + wave;            // the wave's tile row
+    uint4 xr[2][XP];                                 // register set p holds the steps of parity p
+    GroupRaw wr[2][2];
+    int tf[2];                                       // as packed_linear_wide_kernel: fetched a step before they are looked at
+    uint32_t to[2];
+    auto fetch_tables = [&](int64_t s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int64_t wtc = 2 * s + i;
+            const bool there = wtr < tiles_h && wtc < tiles_w;
+            const int64_t t = there ? wtr * tiles_w + wtc : 0;               // the group's tile 0 is always there: the loads are unconditional
+            const int f = map[t];
+            const uint32_t o = off[t];
+            tf[i] = there ? f : -1;
+            to[i] = there ? o : 0u;
+        }
+    };
+    // packed_linear_wide_kernel's load_tile.  A tile that is not there reads bytes of the first 320 of the ARENA (they are there: the
+    // entry checks packed_bytes against 320 bytes per tile), not of the group's stream, which a cut-short `bases` may not own.
+    auto load_tile = [&](const TileAt &a, GroupRaw &g) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) g.w[i] = 0u;
+        g.E = 0u;
+        g.f = a.f;
+        const int f = __builtin_amdgcn_readfirstlane(a.f);                   // uniform over the wave
+        const uint8_t *blob = packed + (f < 0 ? 0 : uniform64(a.off));
+        if (f == 0) {
+            const uint4 *q = reinterpret_cast<const uint4 *>(blob + lane * 32);
+            const uint4 lo = q[0], hi = q[1];
+            g.w[0] = lo.x; g.w[1] = lo.y; g.w[2] = lo.z; g.w[3] = lo.w;
+            g.w[4] = hi.x; g.w[5] = hi.y; g.w[6] = hi.z; g.w[7] = hi.w;
+        } else if (f == 1) {
+            g.E = blob[lane];
+            const uint4 v = *reinterpret_cast<const uint4 *>(blob + kExpBytes + lane * 16);
+            g.w[0] = v.x; g.w[1] = v.y; g.w[2] = v.z; g.w[3] = v.w;
+        } else if (f == 2) {
+            g.E = blob[lane];
+            const uint2 v = *reinterpret_cast<const uint2 *>(blob + kExpBytes + lane * 8);
+            g.w[0] = v.x; g.w[1] = v.y;
+        } else {
+            g.E = blob[lane];
+            g.w[0] = *reinterpret_cast<const uint32_t *>(blob + kExpBytes + lane * 4);
+        }
+    };
+    auto located = [&](int i) __attribute__((always_inline)) {   // the chunked kernel's guard on the fetched pair, in units
+        TileAt a;
+        const uint32_t size = packed_tile_bytes(tf[i]);
+        const uint64_t pos = base + to[i];           // base <= limit < 2^58 where it counts
+        a.off = pos * kUnit;
+        a.f = (size == 0u || base > limit || pos + size / kUnit > limit) ? -1 : tf[i];
+        return a;
+    };
+    auto load_step = [&](auto par, int64_t s) __attribute__((always_inline)) {
+        constexpr int p = decltype(par)::value;
+        const int64_t k0 = s * kBK;
+        const TileAt ta[2] = {located(0), located(1)};
+        fetch_tables(s + 1);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) load_tile(ta[i], wr[p][i]);
+#pragma unroll
+        for (int j = 0; j < XP; ++j) {               // columns past K and rows past the group's end are zeros, never read
+            const int q = tid + kThreads * j, row = q >> 3, c8 = (q & 7) * 8;
+            const int64_t gm = m0 + row, gk = k0 + c8;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if constexpr (XV) {                      // K % 8 == 0: the load is of a piece inside the group's rows (m0 <= M - 1)
+                const bool inside = gm < M && gk < K;
+                const uint4 got = *reinterpret_cast<const uint4 *>(x + (gm < M ? gm : M - 1) * ldx + (gk < K ? gk : K - 8));
+                if (inside) v = got;
+            } else if (gm < M && gk < K) {
+                const uint16_t *src = x + gm * ldx + gk;
+                uint32_t h[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) h[c] = gk + c < K ? (uint32_t)src[c] : 0u;
+                v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+            }
+            xr[p][j] = v;
+        }
+    };
+    auto stage_w = [&](auto par, int i, uint16_t *img) __attribute__((always_inline)) {
+        constexpr int p = decltype(par)::value;
+        uint32_t y[kGroup];
+        decode_skinny(wr[p][i], y);
+        uint4 lo, hi;
+        pack_halves(y, lo, hi);
+        uint4 *d = reinterpret_cast<uint4 *>(img + (BM + kTile * wave + (lane >> 1)) * kLdk + kTile * i + kGroup * (lane & 1));
+        d[0] = lo;
+        d[1] = hi;
+    };
+    auto stage_x = [&](auto par, int j0, int j1, uint16_t *img) __attribute__((always_inline)) {
+        constexpr int p = decltype(par)::value;
+#pragma unroll
+        for (int j = j0; j < j1; ++j) {
+            const int q = tid + kThreads * j;
+            *reinterpret_cast<uint4 *>(img + (q >> 3) * kLdk + (q & 7) * 8) = xr[p][j];
+        }
+    };
+    auto mfma_group = [&](const uint16_t *xs, const uint16_t *ws, int kk) __attribute__((always_inline)) {
+        const int koff = kk * 16 + 8 * (lane >> 5);
+        bf16x8 b[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) b[nt] = *reinterpret_cast<const bf16x8 *>(ws + (64 * wn + 32 * nt + (lane & 31)) * kLdk + koff);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (32 * MT * wm + 32 * mt + (lane & 31)) * kLdk + koff);
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[nt], acc[mt][nt], 0, 0, 0);
+        }
+    };
+    auto step = [&](auto par, int64_t s) __attribute__((always_inline)) {
+        constexpr int cur = decltype(par)::value;
+        const Tag<cur ^ 1> other;
+        const uint16_t *xs = lds + cur * kImage, *ws = xs + BM * kLdk;
+        uint16_t *next = lds + (cur ^ 1) * kImage;
+        const bool more = s + 1 < steps;
+        load_step(par, s + 2 < steps ? s + 2 : steps - 1);
+#pragma unroll
+        for (int kk = 0; kk < kBK / 16; ++kk) {
+            if (!more) {
+                mfma_group(xs, ws, kk);
+            } else if (kk < 2) {
+                mfma_group(xs, ws, kk);
+                stage_w(other, kk, next);
+            } else {
+                mfma_group(xs, ws, kk);
+                stage_x(other, (kk - 2) * (XP / 2), (kk - 1) * (XP / 2), next);
+            }
+        }
+        __syncthreads();
+    };
+
+    fetch_tables(0);
+    load_step(Tag<0>(), 0);
+    load_step(Tag<1>(), steps > 1 ? 1 : 0);
+    stage_w(Tag<0>(), 0, lds);
+    stage_w(Tag<0>(), 1, lds);
+    stage_x(Tag<0>(), 0, XP, lds);
+    __syncthreads();
+    int64_t s = 0;
+    for (; s + 1 < steps; s += 2) {
+        step(Tag<0>(), s);
+        step(Tag<1>(), s + 1);
+    }
+    if (s < steps) {                                 // an odd count's last step: nothing left to load or stage
+#pragma unroll
+        for (int kk = 0; kk < kBK / 16; ++kk) mfma_group(lds, lds + BM * kLdk, kk);
+    }
+
+    // epilogue: lane's outputs are (m0 + 32 MT·wm + 32 mt + (r&3) + 8(r>>2) + 4(lane>>5), n0 + 64·wn + 32 nt + (lane&31)), rows absolute
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        const int64_t n = n0 + 64 * wn + 32 * nt + (lane & 31);
+        if (n >= N) continue;
+        const float b = bias ? bias[e * ldb + n] : 0.0f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t m = m0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[mt][nt][r] + b);
+            }
+    }
+}
+
 // skinny_shape for the grouped entry: skinny_split's rule with count * tiles_h tile rows, which for count == 1 is that rule.
 int grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *tiles_h, int64_t *tiles_w, int *split_eff)
 {
@@ -1663,6 +1920,68 @@ extern "C" int mtq_packed_linear_skinny_grouped_chunked(const void *x, int64_t t
             hipLaunchKernelGGL(skinny_grouped_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
     }
     return check_launch("mtq_packed_linear_skinny_grouped_chunked");
+}
+
+extern "C" size_t mtq_packed_linear_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
+{
+    int64_t th, tw;
+    int eff;
+    if (grouped_shape(total_rows, count, n, k, 1, &th, &tw, &eff)) return (size_t)-1;   // split 1: no split over K, no partials
+    return grouped_plan_bytes(count);
+}
+
+template <bool XV>
+static void launch_wide_grouped(int64_t blocks, hipStream_t st, const uint16_t *xp, int64_t total_rows, int64_t k, int64_t ldx,
+                                const int32_t *group_rows, const int32_t *bstart, const uint8_t *pp, uint64_t packed_bytes, const int8_t *maps,
+                                const uint32_t *offsets, const uint64_t *bases, int64_t count, int64_t n, int64_t th, int64_t tw, const float *bias,
+                                int64_t ldb, void *y, int out_dtype, int64_t ldy)
+{
+    const dim3 grid((unsigned)blocks);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL((packed_linear_wide_grouped_kernel<XV, true>), grid, dim3(kThreads), 0, st, xp, (int)total_rows, k, ldx, group_rows, bstart,
+                           pp, packed_bytes, maps, offsets, bases, (int)count, n, th, tw, bias, ldb, y, ldy);
+    else
+        hipLaunchKernelGGL((packed_linear_wide_grouped_kernel<XV, false>), grid, dim3(kThreads), 0, st, xp, (int)total_rows, k, ldx, group_rows, bstart,
+                           pp, packed_bytes, maps, offsets, bases, (int)count, n, th, tw, bias, ldb, y, ldy);
+}
+
+extern "C" int mtq_packed_linear_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                              const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                              const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                              int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!x || !group_rows || !packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    int eff;
+    if (int rc = grouped_shape(total_rows, count, n, k, 1, &th, &tw, &eff)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if (bias && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
+    const size_t need = grouped_plan_bytes(count);
+    if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and the block plan needs one");
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
+    if (workspace_bytes < need)
+        return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this call needs", workspace_bytes, need);
+    // every block of disjoint groups has a slot: a group with rows adds at most 127/128 of a block over its rows / 128
+    const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
+    const int64_t blocks = slots * ((n + kWideBN - 1) / kWideBN);
+    if (slots > INT32_MAX || blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    int32_t *bstart = static_cast<int32_t *>(workspace);
+    hipLaunchKernelGGL(packed_grouped_wide_plan_kernel, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
+    if (int rc = check_launch("mtq_packed_linear_wide_grouped")) return rc;
+    // whole pieces of 8 bf16 by 16-byte loads (a group may start at any row: ldx % 8 == 0 keeps every row aligned); any other x
+    // (a ragged k included) element by element
+    const bool x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0 && k % 8 == 0;
+    (x_vec ? launch_wide_grouped<true> : launch_wide_grouped<false>)(blocks, st, xp, total_rows, k, ldx, group_rows, bstart, pp, (uint64_t)packed_bytes,
+                                                                     maps, offsets, bases, count, n, th, tw, bias, ldb, y, out_dtype, ldy);
+    return check_launch("mtq_packed_linear_wide_grouped");
 }
 
 extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)

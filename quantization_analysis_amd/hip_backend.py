@@ -125,6 +125,8 @@ SIGNATURES = {
     "mtq_packed_linear_wide": ("i", "plllpzpplppilp", True),
     "mtq_packed_linear_skinny_grouped_chunked_workspace_bytes": ("z", "lllli", True),
     "mtq_packed_linear_skinny_grouped_chunked": ("i", "plllppzpppllplpilipzp", True),
+    "mtq_packed_linear_wide_grouped_workspace_bytes": ("z", "llll", True),
+    "mtq_packed_linear_wide_grouped": ("i", "plllppzpppllplpilpzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1195,7 +1197,8 @@ def packed_linear_skinny_grouped(x, group_rows, arena, maps_dev, offsets_dev, ba
 
 def _packed_linear_grouped_call(name, workspace_bytes, x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out,
                                 split, workspace, stream):
-    """The checks and the call the two grouped entries share; `workspace_bytes` is the entry's own size function."""
+    """The checks and the call the grouped entries share; `workspace_bytes` is the entry's own size function.  split None: an entry
+    without a split parameter (the wide one), whose size function takes (T, count, n, k)."""
     torch = _torch()
     out_dtype = out_dtype or torch.float32
     code = _packed_out_code(out_dtype)
@@ -1216,7 +1219,7 @@ def _packed_linear_grouped_call(name, workspace_bytes, x, group_rows, arena, map
         if bias.dtype != torch.float32 or bias.dim() != 2 or tuple(bias.shape) != (count, n) or bias.stride(1) != 1 or not bias.is_cuda:
             raise MtqError(f"bias must be a float32 ({count}, {n}) device tensor with contiguous rows")
         bias_ptr, ldb = bias.data_ptr(), bias.stride(0) if count > 1 else max(bias.stride(0), n)
-    need = workspace_bytes(T, count, n, k, split)
+    need = workspace_bytes(T, count, n, k) if split is None else workspace_bytes(T, count, n, k, split)
     fn = _entry(name)
     if out is None:
         require_gpu()
@@ -1232,8 +1235,8 @@ def _packed_linear_grouped_call(name, workspace_bytes, x, group_rows, arena, map
         if workspace.data_ptr() % 16:
             raise MtqError("workspace must be 16-byte aligned")
     ldy = out.stride(0) if T > 1 else max(out.stride(0), n)
-    check(fn(x.data_ptr(), T, k, ldx, pg, ptr, arena.numel(), pm, po, pb, count, n, bias_ptr, ldb, out.data_ptr(), code, ldy, int(split),
-             ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
+    check(fn(x.data_ptr(), T, k, ldx, pg, ptr, arena.numel(), pm, po, pb, count, n, bias_ptr, ldb, out.data_ptr(), code, ldy,
+             *(() if split is None else (int(split),)), ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
     return out
 
 
@@ -1261,6 +1264,35 @@ def packed_linear_skinny_grouped_chunked(x, group_rows, arena, maps_dev, offsets
     split; allocated here when none is given."""
     return _packed_linear_grouped_call("mtq_packed_linear_skinny_grouped_chunked", packed_linear_skinny_grouped_chunked_workspace_bytes, x,
                                        group_rows, arena, maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out, split, workspace, stream)
+
+
+WIDE_GROUPED = ("mtq_packed_linear_wide_grouped", "mtq_packed_linear_wide_grouped_workspace_bytes")
+
+
+def has_packed_linear_wide_grouped() -> bool:
+    """Whether this build of the library has mtq_packed_linear_wide_grouped and its size function (optional symbols: an older build of
+    the same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in WIDE_GROUPED)
+
+
+def packed_linear_wide_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int) -> int:
+    """mtq_packed_linear_wide_grouped_workspace_bytes (a host function: no GPU): the block plan's (count + 1) * 4 bytes rounded up to
+    16, whatever (total_rows, n, k) is.  Never 0."""
+    size = int(_entry("mtq_packed_linear_wide_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k)))
+    if size == ctypes.c_size_t(-1).value:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return size
+
+
+def packed_linear_wide_grouped(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None, out=None,
+                               workspace=None, stream="current"):
+    """mtq_packed_linear_wide_grouped on the current stream: packed_linear_skinny_grouped's product and arguments (no split) from the
+    wide-block kernel, a workgroup per 128 rows x 128 columns of one group (the block list is made from group_rows on the device,
+    nothing is read back), for experts with hundreds of rows.  Per group the bits of packed_linear / packed_linear_wide on the group's
+    rows, not the skinny family's.  workspace: of packed_linear_wide_grouped_workspace_bytes(T, count, n, k) bytes; allocated here when
+    none is given."""
+    return _packed_linear_grouped_call("mtq_packed_linear_wide_grouped", packed_linear_wide_grouped_workspace_bytes, x, group_rows, arena,
+                                       maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out, None, workspace, stream)
 
 
 def debug_packed_decode(fmt: str):

@@ -7,7 +7,8 @@ tile format.
 pack_batch / unpack_batch take a batch of equal-shaped tensors and their maps (a search pipeline's resident batch and its results) to one
 arena and back with a fixed number of launches; save_dir / load_dir keep a named set of packed tensors in a directory.  linear_grouped /
 linear_batch / PackedExperts multiply with every tensor of such an arena (the experts of an MoE layer) over its own rows of X in one
-launch; as_batch makes the arena of any list of equal-shaped packed tensors.
+launch; linear_grouped_wide is that product for experts with hundreds of rows (prefill), from the wide-block kernel; as_batch makes the
+arena of any list of equal-shaped packed tensors.
 
 Two backends:
   "hip"        the C ABI (csrc/mtq_packed.hip) through hip_backend's wrappers; data lives on the device.
@@ -777,6 +778,51 @@ def linear_batch(x3d, pts_or_batch, bias=None, out_dtype: str = "float32", backe
     return y.reshape(batch.count, m, batch.rows)
 
 
+def linear_grouped_wide(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, workspace=None):
+    """linear_grouped's product for experts that hold hundreds of rows (MoE prefill), through mtq_packed_linear_wide_grouped: one launch
+    in which a workgroup owns 128 rows x 128 columns of one group, so an expert's stream is decoded once per 128 rows, not once per 32 as
+    by linear_grouped's kernels.  x, group_rows (host: checked here as by linear_grouped; device int32: passed on as it is and clamped by
+    the kernel), pts_or_batch and bias as linear_grouped's; there is no split over K; workspace: an optional uint8 device tensor of
+    hip_backend.packed_linear_wide_grouped_workspace_bytes bytes (the block plan: a function of count alone).
+    hip: for every group the bits of linear(kernel="block") / linear_wide on the group's rows and that expert - the block family's bits,
+    not linear_grouped's: the two families sum in different orders, so the two functions may differ in the last bits, which is why this is
+    a function of its own and no GROUPED_KERNELS name.  Rows outside every group are zeros; T = 0 gives (0, n) without a call.  A library
+    without the symbol raises MtqError before any device work: no other kernel runs in its place.
+    emulation: linear_grouped's float64 product."""
+    batch = _resolve_batch(pts_or_batch)
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    if backend != "hip":
+        return linear_grouped(x, group_rows, batch, bias=bias, out_dtype=out_dtype, backend=backend)
+    import torch
+
+    from . import hip_backend as hb
+
+    count, n, k = batch.count, batch.rows, batch.cols
+    if len(x.shape) != 2 or x.shape[1] != k:
+        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
+    T = int(x.shape[0])
+    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
+    if not on_device:
+        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
+    if not hb.has_packed_linear_wide_grouped():      # a missing kernel is refused before any device work
+        raise MtqError("linear_grouped_wide needs mtq_packed_linear_wide_grouped, which this build of libmtq_hip.so lacks: rebuild it from "
+                       "this tree, or use linear_grouped")
+    batch = batch_to_device(batch)
+    dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+    if T == 0:
+        return torch.zeros((0, n), dtype=dtype, device=batch.arena.device)
+    if not on_device:
+        group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(batch.arena.device)
+    if bias is not None and not _is_torch(bias):
+        bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32)).to(batch.arena.device)
+    return hb.packed_linear_wide_grouped(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias,
+                                         out_dtype=dtype, workspace=workspace)
+
+
 def _packed_linear_class():
     import torch
 
@@ -847,12 +893,20 @@ def _packed_experts_class():
         rows [group_rows[e], group_rows[e + 1]) → (T, n) through linear_grouped.  The batch is made once, here (as_batch for a list), and
         every forward multiplies with that arena: hip: the arena, its tables and the bias stay on the device, no host work per expert
         and no synchronisation in forward (with a device group_rows), and the workspace grows to the largest T seen.  emulation: CPU tensors, the float64 product.
-        kernel: as linear_grouped's, resolved here; the kept workspace is sized by the size function of the kernel in use."""
+        kernel: as linear_grouped's, resolved here; the kept workspace is sized by the size function of the kernel in use.
+        wide_min_rows: None (the default: every call goes through linear_grouped), or an int: a forward whose x has T >= wide_min_rows
+        rows goes through linear_grouped_wide, the wide-block kernel for experts with hundreds of rows (T is known on the host: no
+        synchronisation); its plan workspace is allocated once, here, and is the one kept workspace of both routes.  Crossing the threshold changes the summation order (the block
+        family's bits above it, the skinny family's below), so the last bits of a row may differ between a call below and a call at or
+        above it.  DESIGN.md §A.6n has the measurement that informs the choice of a value."""
 
         def __init__(self, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
-                     kernel: str = "walk"):
+                     kernel: str = "walk", wide_min_rows: Optional[int] = None):
             super().__init__()
             self.kernel = _grouped_kernel(kernel)
+            if wide_min_rows is not None and (isinstance(wide_min_rows, bool) or not isinstance(wide_min_rows, (int, np.integer)) or wide_min_rows < 0):
+                raise MtqError(f"wide_min_rows must be None or a non-negative int, got {wide_min_rows!r}")
+            self.wide_min_rows = None if wide_min_rows is None else int(wide_min_rows)
             if out_dtype not in ("float32", "bfloat16"):
                 raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
             batch = _resolve_batch(pts_or_batch)                # once: forward hands the batch down and walks no list
@@ -862,11 +916,22 @@ def _packed_experts_class():
             if self.backend == "hip":
                 if self.kernel != "walk":
                     _grouped_entries(self.kernel)   # a library without the kernel is refused here, not at the first forward
+                if self.wide_min_rows is not None:
+                    from . import hip_backend as hb
+
+                    if not hb.has_packed_linear_wide_grouped():
+                        raise MtqError("wide_min_rows needs mtq_packed_linear_wide_grouped, which this build of libmtq_hip.so lacks: rebuild "
+                                       "it from this tree, or leave wide_min_rows None")
                 batch = batch_to_device(batch)
             self.batch = batch
             self.out_dtype, self.split = out_dtype, int(split)
             self.count, self.out_features, self.in_features = batch.count, batch.rows, batch.cols
             self._workspace = None
+            if self.backend == "hip" and self.wide_min_rows is not None:
+                from . import hip_backend as hb
+
+                need = hb.packed_linear_wide_grouped_workspace_bytes(1, self.count, self.out_features, self.in_features)   # count alone
+                self._workspace = torch.empty((need,), dtype=torch.uint8, device=batch.arena.device)   # only ever replaced by a larger one
             if bias is not None:
                 if not _is_torch(bias):
                     bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
@@ -877,13 +942,18 @@ def _packed_experts_class():
 
         def extra_repr(self) -> str:
             return f"count={self.count}, in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, " \
-                   f"backend={self.backend!r}, split={self.split}" + ("" if self.kernel == "walk" else f", kernel={self.kernel!r}")
+                   f"backend={self.backend!r}, split={self.split}" + ("" if self.kernel == "walk" else f", kernel={self.kernel!r}") + \
+                   ("" if self.wide_min_rows is None else f", wide_min_rows={self.wide_min_rows}")
 
         @torch.no_grad()
         def forward(self, x, group_rows):
             if x.dim() != 2 or x.shape[1] != self.in_features:
                 raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
             T = int(x.shape[0])
+            if self.wide_min_rows is not None and T >= self.wide_min_rows:
+                y = linear_grouped_wide(x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend,
+                                        workspace=self._workspace)
+                return y if _is_torch(y) else torch.from_numpy(y)
             if self.backend == "hip" and T:
                 from . import hip_backend as hb
 

@@ -51,13 +51,13 @@ def calibrate(fn, target_ms: float) -> int:
     return int(min(max(target_ms / one, 3), 200))
 
 
-def routing(kind: str, count: int, seed: int) -> np.ndarray:
-    """Rows per expert."""
+def routing(kind: str, count: int, seed: int, rows: int = 512) -> np.ndarray:
+    """Rows per expert; `rows`: what the skewed draw spreads (tools/packed_grouped_wide_bench.py spreads a prefill batch with it)."""
     if kind == "uniform":
         return np.full(count, 4, dtype=np.int64)
     rng = np.random.default_rng(seed)
     p = rng.pareto(0.6, size=count) + 1e-3                   # a few hot experts, most cold
-    return np.bincount(rng.choice(count, size=512, p=p / p.sum()), minlength=count).astype(np.int64)
+    return np.bincount(rng.choice(count, size=rows, p=p / p.sum()), minlength=count).astype(np.int64)
 
 
 def main() -> int:
