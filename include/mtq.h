@@ -817,6 +817,66 @@ int mtq_packed_linear_wide_grouped(const void *x, int64_t total_rows, int64_t k,
                                    size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, int64_t count,
                                    int64_t n, const float *bias, int64_t ldb, void *y, int out_dtype, int64_t ldy, void *workspace,
                                    size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ gated MLP (SwiGLU) on packed weights
+ * h = act(x·Ŵgᵀ + bg) * (x·Ŵuᵀ + bu), the first half of down(act(gate(x)) * up(x)), with the gate and the up projection as two
+ * packed (n, k) weights of the format above (nothing is repacked: the tile rows of a packed weight are independent blobs).
+ *
+ * The activation is one device function (csrc/mtq_glu.hpp, glu_value) that every entry below calls, all in separately rounded float32
+ * operations, no contraction:
+ *   MTQ_ACT_SILU  h = (g / (1 + expf(-g))) * u, the accurate expf
+ *   MTQ_ACT_NONE  h = g * u, one rounding (the bilinear GLU)
+ * Inf, NaN and -0 get no special case: what the sequence gives is the definition.  Any other code is MTQ_ERR_UNSUPPORTED.
+ * All four symbols are optional: a build of this version may lack them. */
+enum { MTQ_ACT_SILU = 0, MTQ_ACT_NONE = 1 };
+
+/* y[r][c] = act(g[r][c]) * u[r][c] for float32 device matrices g and u of rows x cols at pitches ldg, ldu → y float32 or bf16
+ * (out_dtype, pitch ldy; a bf16 y is rounded to nearest even once).  Asynchronous on `stream`; nothing outside rows x cols of y is
+ * written.  Null pointers, rows or cols not positive, a pitch below cols and an out_dtype that is neither are MTQ_ERR_INVALID before a
+ * device is looked for.  The second half of the unfused route, and the yardstick of the bit contract below. */
+int mtq_glu_combine(const float *g, int64_t ldg, const float *u, int64_t ldu, int64_t rows, int64_t cols, int act, void *y, int out_dtype,
+                    int64_t ldy, void *stream);
+
+/* The gated product in one launch from mtq_packed_linear_wide's step: x, m, k, ldx as there; (gate_packed, gate_bytes, gate_map,
+ * gate_offsets) and the same four for up, both n x k; bias_gate, bias_up float32 [n], each may be NULL; y m x n (out_dtype, ldy).  A
+ * workgroup of 4 waves owns 128 rows x 64 HIDDEN columns (the grid is ceil(m / 128) x ceil(n / 64)); the four tile-row slots of its
+ * weight image alternate between the two streams, so each lane holds the gate's and the up's accumulator of the same output and
+ * applies the activation itself: the two float32 (m, n) intermediates never reach memory and x is read once.
+ *
+ * Bit contract: for every input, y equals bit for bit the result of (1) mtq_packed_linear on the gate stream with bias_gate into
+ * float32, (2) the same on the up stream with bias_up, (3) mtq_glu_combine of the two.  This holds in both output types, with or
+ * without either bias, and for any ldx / ldy.  The guards are the wide kernel's, per stream: a tile whose blob passes its own stream's
+ * packed_bytes or whose map code is outside 0..3 multiplies as zeros in its own projection only; rows at or past m and columns at or
+ * past k of x are never read; nothing outside m x n of y is written.  No atomics, no workspace, nothing waits on another workgroup: two
+ * calls give the same bits.
+ *
+ * Arguments are checked as by mtq_packed_linear_wide, for each stream (null pointers, m, n, k positive, the tile grid, ldx / ldy, a
+ * stream below 320 bytes per tile or not 16-byte aligned): MTQ_ERR_INVALID before a device is looked for.  m = 0 and n = 0 are
+ * refused as there; the Python binding returns the empty result without a call.  Correct for any m >= 1; m <= 32 is better served by
+ * two skinny calls and the combine (there is no fused kernel for the decode range: a split over K has partial sums). */
+int mtq_packed_glu_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes, const int8_t *gate_map,
+                        const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes, const int8_t *up_map, const uint32_t *up_offsets,
+                        int64_t n, const float *bias_gate, const float *bias_up, int act, void *y, int out_dtype, int64_t ldy, void *stream);
+
+/* The same block in mtq_packed_linear_wide_grouped's frame, for the experts of an MoE layer: x, total_rows, k, ldx, group_rows as
+ * there; two arenas (packed, bytes, maps, offsets, bases), one with the `count` gate experts and one with the `count` up experts, all
+ * n x k; bias_gate, bias_up float32 (count, n) at pitch ldb, each may be NULL.  The plan kernel, the slot bound U, the early return of
+ * surplus workgroups before any other load or barrier, the clamping of group_rows and the workspace (its size included) are that
+ * entry's; the grid is U x ceil(n / 64).
+ *
+ * Bit contract: for nondecreasing group_rows and every group with rows, y[r0:r1] equals bit for bit the three-step sequence above on
+ * x[r0:r1] with expert e's gate and up streams and tables (and bias rows e).  Rows of y that belong to no group are not written.  A
+ * blob is checked against its own group's range [64 * bases[e], 64 * bases[e + 1]) of its OWN arena and against that arena's bytes,
+ * and multiplies as zeros in its own projection only when it passes either.  Whatever group_rows holds, nothing outside
+ * total_rows x n of y or outside the workspace is written and no row of x at or past total_rows is read.  Deterministic, as there.
+ * Arguments are checked as by that entry, for each arena. */
+size_t mtq_packed_glu_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k);
+int mtq_packed_glu_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows, const void *gate_packed,
+                                size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets, const uint64_t *gate_bases,
+                                const void *up_packed, size_t up_bytes, const int8_t *up_maps, const uint32_t *up_offsets,
+                                const uint64_t *up_bases, int64_t count, int64_t n, const float *bias_gate, const float *bias_up, int64_t ldb,
+                                int act, void *y, int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Test hook: the skinny kernel's decode (a cheaper form of the block kernel's for exponent bytes M..254, the same code elsewhere)
  * beside the reference decode, for fmt MTQ_FMT_BFP8 / BFP4 / BFP2.  got, want: device uint32 [16][256][16][16] = [rot][E][q][i], the
  * float32 word of code (16 q + (i + rot) % 16) mod 2^(M + 1) at element i of a group with exponent byte E: every (E, code) at every

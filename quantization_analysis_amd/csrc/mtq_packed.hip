@@ -27,6 +27,11 @@
 //   packed_grouped_wide_plan_kernel, packed_linear_wide_grouped_kernel
 //                                             that block for every expert of an arena over the expert's own rows, one launch: the groups'
 //       128-row block counts are prefix-summed on the device and each workgroup finds its group by the chunked kernel's search.
+//   packed_glu_wide_kernel, packed_glu_wide_grouped_kernel, glu_combine_kernel
+//                                             the gated MLP's first half, glu_value(X·Ŵgᵀ + bg, X·Ŵuᵀ + bu): the wide kernel's step on a
+//       128 × 64 block whose four tile-row slots alternate between the gate and the up stream, so a lane holds both projections of its
+//       outputs; the same block in the grouped wide frame; and the element-wise combine that finishes the unfused route with the same
+//       function (mtq_glu.hpp) and so the same bits.
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
 // blob does not fit is not written (pack), not stored (unpack) or read as zeros (linear).
@@ -37,6 +42,7 @@
 
 #include "mtq_device.hpp"
 #include "mtq_error.hpp"
+#include "mtq_glu.hpp"
 
 namespace mtq {
 namespace {
@@ -1491,6 +1497,293 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_grouped_kernel
     }
 }
 
+// ---- gated wide linear (SwiGLU): glu_value(X·Ŵgᵀ + bg, X·Ŵuᵀ + bu) from packed_linear_wide_kernel's step, one launch, one store.
+//
+// A workgroup of 4 waves owns 128 rows × 64 HIDDEN columns.  The W part of its LDS image keeps the wide kernel's four tile-row slots:
+// slot sl holds hidden tile row n0 / 32 + (sl >> 1), from the gate stream when sl is even and from the up stream when sl is odd.  Wave w
+// stages slot w, as there: its stream, its tables and its limits are uniform over the wave and chosen once, in scalar registers.  Wave
+// (wm, wn) multiplies slots 2 wn and 2 wn + 1 with the wide kernel's mfma_group unchanged, so acc[mt][0] is the gate's and acc[mt][1]
+// the up's output at the SAME (row, hidden column n0 + 32 wn + lane % 32): the epilogue is lane-local.  The loads (unconditional, an
+// absent tile clamped to its stream's tile 0 and read from the stream's head), the blob check against the tile's own stream, a map code
+// outside 0..3 as zeros, both X paths, two images, two register sets, one barrier per step: packed_linear_wide_grouped_kernel's, with
+// the stream limits in units ([base, limit) of 64 bytes; for a single tensor base = 0, limit = packed_bytes / 64, the byte check's
+// equal since every blob size is a multiple of 64).
+// Bits: each accumulator takes the block kernel's sequence for its projection, the bias is added once in f32 as there, and glu_value
+// (mtq_glu.hpp) is what mtq_glu_combine applies to the two stored f32 results: the unfused route's bits.
+struct GluStream {                                   // one projection's stream as the wave that stages it holds it
+    const uint8_t *packed;                           // the tensor's stream, or the arena
+    const int8_t *map;                               // the tensor's (the expert's) tables
+    const uint32_t *off;
+    uint64_t base, limit;                            // units: the blobs of this tensor lie in [base, limit)
+};
+
+constexpr int kGluBN = 64;                           // hidden columns of a workgroup
+constexpr int kGluImage = (kWideBM + kWideBN) * kLdk;
+
+// The block at rows [m0, min(m0 + 128, M)) of x / y and hidden columns [n0, n0 + 64): M is the row limit of every access.
+template <bool XV, bool BF16OUT>
+__device__ __forceinline__ void glu_wide_block(uint16_t *__restrict__ lds, const uint16_t *__restrict__ x, int64_t m0, int64_t M, int64_t K,
+                                               int64_t ldx, const GluStream &st, int64_t n0, int64_t N, int64_t tiles_h, int64_t tiles_w,
+                                               const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int act,
+                                               void *__restrict__ yv, int64_t ldy, int wave)
+{
+    constexpr int BM = kWideBM, MT = BM / 64, XP = BM * 8 / kThreads, kImage = kGluImage;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int64_t steps = (K + kBK - 1) / kBK;
+    const uint8_t *__restrict__ packed = st.packed;
+    const int8_t *__restrict__ map = st.map;
+    const uint32_t *__restrict__ off = st.off;
+    const uint64_t base = st.base, limit = st.limit;
+
+    f32x16 acc[MT][2];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
+
+    const int64_t wtr = (n0 >> 5) + (wave >> 1);     // the hidden tile row of the wave's slot
+    uint4 xr[2][XP];                                 // register set p holds the steps of parity p
+    GroupRaw wr[2][2];
+    int tf[2];                                       // as packed_linear_wide_kernel: fetched a step before they are looked at
+    uint32_t to[2];
+    auto fetch_tables = [&](int64_t s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int64_t wtc = 2 * s + i;
+            const bool there = wtr < tiles_h && wtc < tiles_w;
+            const int64_t t = there ? wtr * tiles_w + wtc : 0;               // tile 0 is always there: the loads are unconditional
+            const int f = map[t];
+            const uint32_t o = off[t];
+            tf[i] = there ? f : -1;
+            to[i] = there ? o : 0u;
+        }
+    };
+    // packed_linear_wide_grouped_kernel's load_tile.  A tile that is not there reads bytes of the first 320 of `packed` (they are there:
+    // the entry checks each stream's packed_bytes against 320 bytes per tile) and keeps f < 0, which decodes as zeros.
+    auto load_tile = [&](const TileAt &a, GroupRaw &g) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) g.w[i] = 0u;
+        g.E = 0u;
+        g.f = a.f;
+        const int f = __builtin_amdgcn_readfirstlane(a.f);                   // uniform over the wave
+        const uint8_t *blob = packed + (f < 0 ? 0 : uniform64(a.off));
+        if (f == 0) {
+            const uint4 *q = reinterpret_cast<const uint4 *>(blob + lane * 32);
+            const uint4 lo = q[0], hi = q[1];
+            g.w[0] = lo.x; g.w[1] = lo.y; g.w[2] = lo.z; g.w[3] = lo.w;
+            g.w[4] = hi.x; g.w[5] = hi.y; g.w[6] = hi.z; g.w[7] = hi.w;
+        } else if (f == 1) {
+            g.E = blob[lane];
+            const uint4 v = *reinterpret_cast<const uint4 *>(blob + kExpBytes + lane * 16);
+            g.w[0] = v.x; g.w[1] = v.y; g.w[2] = v.z; g.w[3] = v.w;
+        } else if (f == 2) {
+            g.E = blob[lane];
+            const uint2 v = *reinterpret_cast<const uint2 *>(blob + kExpBytes + lane * 8);
+            g.w[0] = v.x; g.w[1] = v.y;
+        } else {
+            g.E = blob[lane];
+            g.w[0] = *reinterpret_cast<const uint32_t *>(blob + kExpBytes + lane * 4);
+        }
+    };
+    auto located = [&](int i) __attribute__((always_inline)) {   // the grouped kernel's guard on the fetched pair, in units
+        TileAt a;
+        const uint32_t size = packed_tile_bytes(tf[i]);
+        const uint64_t pos = base + to[i];           // base <= limit < 2^58 where it counts
+        a.off = pos * kUnit;
+        a.f = (size == 0u || base > limit || pos + size / kUnit > limit) ? -1 : tf[i];
+        return a;
+    };
+    auto load_step = [&](auto par, int64_t s) __attribute__((always_inline)) {
+        constexpr int p = decltype(par)::value;
+        const int64_t k0 = s * kBK;
+        const TileAt ta[2] = {located(0), located(1)};
+        fetch_tables(s + 1);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) load_tile(ta[i], wr[p][i]);
+#pragma unroll
+        for (int j = 0; j < XP; ++j) {               // columns past K and rows past M are zeros, never read
+            const int q = tid + kThreads * j, row = q >> 3, c8 = (q & 7) * 8;
+            const int64_t gm = m0 + row, gk = k0 + c8;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if constexpr (XV) {                      // K % 8 == 0: the load is of a piece inside the rows (m0 <= M - 1)
+                const bool inside = gm < M && gk < K;
+                const uint4 got = *reinterpret_cast<const uint4 *>(x + (gm < M ? gm : M - 1) * ldx + (gk < K ? gk : K - 8));
+                if (inside) v = got;
+            } else if (gm < M && gk < K) {
+                const uint16_t *src = x + gm * ldx + gk;
+                uint32_t h[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) h[c] = gk + c < K ? (uint32_t)src[c] : 0u;
+                v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+            }
+            xr[p][j] = v;
+        }
+    };
+    auto stage_w = [&](auto par, int i, uint16_t *img) __attribute__((always_inline)) {   // slot `wave`: rows 32 wave .. of the W part
+        constexpr int p = decltype(par)::value;
+        uint32_t y[kGroup];
+        decode_skinny(wr[p][i], y);
+        uint4 lo, hi;
+        pack_halves(y, lo, hi);
+        uint4 *d = reinterpret_cast<uint4 *>(img + (BM + kTile * wave + (lane >> 1)) * kLdk + kTile * i + kGroup * (lane & 1));
+        d[0] = lo;
+        d[1] = hi;
+    };
+    auto stage_x = [&](auto par, int j0, int j1, uint16_t *img) __attribute__((always_inline)) {
+        constexpr int p = decltype(par)::value;
+#pragma unroll
+        for (int j = j0; j < j1; ++j) {
+            const int q = tid + kThreads * j;
+            *reinterpret_cast<uint4 *>(img + (q >> 3) * kLdk + (q & 7) * 8) = xr[p][j];
+        }
+    };
+    // nt = 0: slot 2 wn (gate), nt = 1: slot 2 wn + 1 (up), both of hidden tile row n0 / 32 + wn
+    auto mfma_group = [&](const uint16_t *xs, const uint16_t *ws, int kk) __attribute__((always_inline)) {
+        const int koff = kk * 16 + 8 * (lane >> 5);
+        bf16x8 b[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) b[nt] = *reinterpret_cast<const bf16x8 *>(ws + (64 * wn + 32 * nt + (lane & 31)) * kLdk + koff);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (32 * MT * wm + 32 * mt + (lane & 31)) * kLdk + koff);
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[nt], acc[mt][nt], 0, 0, 0);
+        }
+    };
+    auto step = [&](auto par, int64_t s) __attribute__((always_inline)) {
+        constexpr int cur = decltype(par)::value;
+        const Tag<cur ^ 1> other;
+        const uint16_t *xs = lds + cur * kImage, *ws = xs + BM * kLdk;
+        uint16_t *next = lds + (cur ^ 1) * kImage;
+        const bool more = s + 1 < steps;
+        load_step(par, s + 2 < steps ? s + 2 : steps - 1);
+#pragma unroll
+        for (int kk = 0; kk < kBK / 16; ++kk) {
+            if (!more) {
+                mfma_group(xs, ws, kk);
+            } else if (kk < 2) {
+                mfma_group(xs, ws, kk);
+                stage_w(other, kk, next);
+            } else {
+                mfma_group(xs, ws, kk);
+                stage_x(other, (kk - 2) * (XP / 2), (kk - 1) * (XP / 2), next);
+            }
+        }
+        __syncthreads();
+    };
+
+    fetch_tables(0);
+    load_step(Tag<0>(), 0);
+    load_step(Tag<1>(), steps > 1 ? 1 : 0);
+    stage_w(Tag<0>(), 0, lds);
+    stage_w(Tag<0>(), 1, lds);
+    stage_x(Tag<0>(), 0, XP, lds);
+    __syncthreads();
+    int64_t s = 0;
+    for (; s + 1 < steps; s += 2) {
+        step(Tag<0>(), s);
+        step(Tag<1>(), s + 1);
+    }
+    if (s < steps) {                                 // an odd count's last step: nothing left to load or stage
+#pragma unroll
+        for (int kk = 0; kk < kBK / 16; ++kk) mfma_group(lds, lds + BM * kLdk, kk);
+    }
+
+    // epilogue: lane's outputs are (m0 + 32 MT·wm + 32 mt + (r&3) + 8(r>>2) + 4(lane>>5), n0 + 32·wn + (lane&31)); the bias is added as
+    // the block kernel adds it (+0 without one), glu_value is the one place the activation is computed
+    const int64_t n = n0 + 32 * wn + (lane & 31);
+    if (n >= N) return;
+    const float bg = bias_gate ? bias_gate[n] : 0.0f, bu = bias_up ? bias_up[n] : 0.0f;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t m = m0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (m < M) store_y<BF16OUT>(yv, m * ldy + n, glu_value(acc[mt][0][r] + bg, acc[mt][1][r] + bu, act));
+        }
+}
+
+// 256 VGPRs at two waves per SIMD, as packed_linear_wide_kernel: re-read `make report` on any edit.
+template <bool XV, bool BF16OUT>
+__global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ gate, uint64_t gate_bytes,
+    const int8_t *__restrict__ gate_map, const uint32_t *__restrict__ gate_offsets, const uint8_t *__restrict__ up, uint64_t up_bytes,
+    const int8_t *__restrict__ up_map, const uint32_t *__restrict__ up_offsets, int64_t N, int64_t tiles_h, int64_t tiles_w,
+    const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int act, void *__restrict__ yv, int64_t ldy)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kGluImage];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
+    const int64_t bm = blockIdx.x / nblocks, bn = blockIdx.x % nblocks;
+    const bool is_up = wave & 1;                     // the wave's slot: even from the gate stream, odd from the up stream
+    GluStream st;
+    st.packed = is_up ? up : gate;
+    st.map = is_up ? up_map : gate_map;
+    st.off = is_up ? up_offsets : gate_offsets;
+    st.base = 0;
+    st.limit = (is_up ? up_bytes : gate_bytes) / kUnit;
+    glu_wide_block<XV, BF16OUT>(lds, x, bm * kWideBM, M, K, ldx, st, bn * kGluBN, N, tiles_h, tiles_w, bias_gate, bias_up, act, yv, ldy, wave);
+}
+
+// packed_linear_wide_grouped_kernel's frame around the same block: the plan (bstart, by packed_grouped_wide_plan_kernel), the slot bound,
+// the early return of a surplus workgroup before any other load or barrier, the group search and the clamped rows are that kernel's; the
+// column blocks are of 64 hidden columns.  A blob is checked against its own group's range of its own arena.
+template <bool XV, bool BF16OUT>
+__global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_grouped_kernel(
+    const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
+    const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps, const uint32_t *__restrict__ gate_offsets,
+    const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes, const int8_t *__restrict__ up_maps,
+    const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int64_t N, int64_t tiles_h, int64_t tiles_w,
+    const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int64_t ldb, int act, void *__restrict__ yv, int64_t ldy)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kGluImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
+    const int slot = (int)(blockIdx.x / nblocks);
+    const int64_t bn = blockIdx.x % nblocks;
+    if (slot >= bstart[count]) return;               // a surplus slot: nothing else is read; uniform over the workgroup, before any barrier
+
+    // the group of block `slot`: the last e with bstart[e] <= slot.  bstart[lo] <= slot < bstart[hi] throughout
+    int lo = 0, hi = count;
+    while (hi - lo > 64) {
+        const int mid = lo + (hi - lo) / 2;
+        if (bstart[mid] <= slot) lo = mid;
+        else hi = mid;
+    }
+    const int at = lo + 1 + lane;
+    const int e = __builtin_amdgcn_readfirstlane(lo + (int)__popcll(__ballot(at < hi && bstart[at] <= slot)));
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    const int64_t r0 = __builtin_amdgcn_readfirstlane((int)gr.r0), M = __builtin_amdgcn_readfirstlane((int)gr.r1);   // 0 <= r0 <= M <= T
+    const int64_t m0 = r0 + (int64_t)kWideBM * (slot - __builtin_amdgcn_readfirstlane(bstart[e]));
+    if (m0 >= M) return;                             // never for a prefix this launch's plan kernel wrote
+    const int64_t tiles = tiles_h * tiles_w;
+    const bool is_up = wave & 1;
+    const uint64_t *bases = is_up ? up_bases : gate_bases;
+    GluStream st;
+    st.packed = is_up ? up : gate;
+    st.map = (is_up ? up_maps : gate_maps) + e * tiles;
+    st.off = (is_up ? up_offsets : gate_offsets) + e * (tiles + 1);
+    st.base = uniform64(bases[e]);
+    st.limit = uniform64(std::min<uint64_t>(bases[e + 1], (is_up ? up_bytes : gate_bytes) / kUnit));
+    glu_wide_block<XV, BF16OUT>(lds, x, m0, M, K, ldx, st, bn * kGluBN, N, tiles_h, tiles_w, bias_gate ? bias_gate + e * ldb : nullptr,
+                                bias_up ? bias_up + e * ldb : nullptr, act, yv, ldy, wave);
+}
+
+// y[r][c] = glu_value(g[r][c], u[r][c], act): the second half of the unfused route, one thread per element in a grid-stride walk.
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void glu_combine_kernel(const float *__restrict__ g, int64_t ldg, const float *__restrict__ u, int64_t ldu,
+                                                          int64_t rows, int64_t cols, int act, void *__restrict__ yv, int64_t ldy)
+{
+    const int64_t total = rows * cols;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / cols, c = i - r * cols;
+        store_y<BF16OUT>(yv, r * ldy + c, glu_value(g[r * ldg + c], u[r * ldu + c], act));
+    }
+}
+
 // skinny_shape for the grouped entry: skinny_split's rule with count * tiles_h tile rows, which for count == 1 is that rule.
 int grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *tiles_h, int64_t *tiles_w, int *split_eff)
 {
@@ -1982,6 +2275,144 @@ extern "C" int mtq_packed_linear_wide_grouped(const void *x, int64_t total_rows,
     (x_vec ? launch_wide_grouped<true> : launch_wide_grouped<false>)(blocks, st, xp, total_rows, k, ldx, group_rows, bstart, pp, (uint64_t)packed_bytes,
                                                                      maps, offsets, bases, count, n, th, tw, bias, ldb, y, out_dtype, ldy);
     return check_launch("mtq_packed_linear_wide_grouped");
+}
+
+// ---- gated entries
+static int glu_act(int act)
+{
+    if (act != MTQ_ACT_SILU && act != MTQ_ACT_NONE) return fail(MTQ_ERR_UNSUPPORTED, "act must be MTQ_ACT_SILU or MTQ_ACT_NONE");
+    return MTQ_OK;
+}
+
+extern "C" int mtq_glu_combine(const float *g, int64_t ldg, const float *u, int64_t ldu, int64_t rows, int64_t cols, int act, void *y,
+                               int out_dtype, int64_t ldy, void *stream)
+{
+    if (!g || !u || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    if (rows <= 0 || cols <= 0) return fail(MTQ_ERR_INVALID, "rows and cols must be positive (empty operands are handled by the caller)");
+    if (rows > (int64_t)1 << 40 || cols > (int64_t)1 << 30 || rows > ((int64_t)1 << 56) / cols) return fail(MTQ_ERR_INVALID, "matrix too large");
+    if (ldg < cols) return fail(MTQ_ERR_INVALID, "ldg < cols");
+    if (ldu < cols) return fail(MTQ_ERR_INVALID, "ldu < cols");
+    if (ldy < cols) return fail(MTQ_ERR_INVALID, "ldy < cols");
+    if (int rc = glu_act(act)) return rc;
+    if (int rc = require_device()) return rc;
+    const dim3 grid((unsigned)std::min<int64_t>((rows * cols + 255) / 256, (int64_t)1 << 20));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (out_dtype == MTQ_DTYPE_BF16) hipLaunchKernelGGL(glu_combine_kernel<true>, grid, dim3(256), 0, st, g, ldg, u, ldu, rows, cols, act, y, ldy);
+    else hipLaunchKernelGGL(glu_combine_kernel<false>, grid, dim3(256), 0, st, g, ldg, u, ldu, rows, cols, act, y, ldy);
+    return check_launch("mtq_glu_combine");
+}
+
+template <bool XV>
+static void launch_glu_wide(int64_t blocks, hipStream_t st, const uint16_t *xp, int64_t m, int64_t k, int64_t ldx, const uint8_t *gp,
+                            uint64_t gate_bytes, const int8_t *gate_map, const uint32_t *gate_offsets, const uint8_t *up, uint64_t up_bytes,
+                            const int8_t *up_map, const uint32_t *up_offsets, int64_t n, int64_t th, int64_t tw, const float *bias_gate,
+                            const float *bias_up, int act, void *y, int out_dtype, int64_t ldy)
+{
+    const dim3 grid((unsigned)blocks);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL((packed_glu_wide_kernel<XV, true>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, gp, gate_bytes, gate_map, gate_offsets, up,
+                           up_bytes, up_map, up_offsets, n, th, tw, bias_gate, bias_up, act, y, ldy);
+    else
+        hipLaunchKernelGGL((packed_glu_wide_kernel<XV, false>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, gp, gate_bytes, gate_map, gate_offsets, up,
+                           up_bytes, up_map, up_offsets, n, th, tw, bias_gate, bias_up, act, y, ldy);
+}
+
+extern "C" int mtq_packed_glu_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                                   const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
+                                   const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up,
+                                   int act, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    int64_t th, tw;
+    if (int rc = linear_args(x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, n, y, out_dtype, ldy, &th, &tw)) return rc;
+    if (int rc = linear_args(x, m, k, ldx, up_packed, up_bytes, up_map, up_offsets, n, y, out_dtype, ldy, &th, &tw)) return rc;
+    if (int rc = glu_act(act)) return rc;
+    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kGluBN - 1) / kGluBN);
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
+    if (int rc = require_device()) return rc;
+    // whole pieces of 8 bf16 by 16-byte loads; any other x (a ragged k included) element by element
+    const bool x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0 && k % 8 == 0;
+    (x_vec ? launch_glu_wide<true> : launch_glu_wide<false>)(blocks, static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(x), m, k, ldx,
+                                                             static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
+                                                             static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, th, tw,
+                                                             bias_gate, bias_up, act, y, out_dtype, ldy);
+    return check_launch("mtq_packed_glu_wide");
+}
+
+extern "C" size_t mtq_packed_glu_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
+{
+    return mtq_packed_linear_wide_grouped_workspace_bytes(total_rows, count, n, k);   // the same plan
+}
+
+namespace {
+struct GluArena {                                    // one projection's arena as the grouped entry is given it
+    const uint8_t *packed;
+    uint64_t bytes;
+    const int8_t *maps;
+    const uint32_t *offsets;
+    const uint64_t *bases;
+};
+}
+
+template <bool XV>
+static void launch_glu_wide_grouped(int64_t blocks, hipStream_t st, const uint16_t *xp, int64_t total_rows, int64_t k, int64_t ldx,
+                                    const int32_t *group_rows, const int32_t *bstart, const GluArena &g, const GluArena &u, int64_t count, int64_t n,
+                                    int64_t th, int64_t tw, const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y,
+                                    int out_dtype, int64_t ldy)
+{
+    const dim3 grid((unsigned)blocks);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL((packed_glu_wide_grouped_kernel<XV, true>), grid, dim3(kThreads), 0, st, xp, (int)total_rows, k, ldx, group_rows, bstart,
+                           g.packed, g.bytes, g.maps, g.offsets, g.bases, u.packed, u.bytes, u.maps, u.offsets, u.bases, (int)count, n, th, tw,
+                           bias_gate, bias_up, ldb, act, y, ldy);
+    else
+        hipLaunchKernelGGL((packed_glu_wide_grouped_kernel<XV, false>), grid, dim3(kThreads), 0, st, xp, (int)total_rows, k, ldx, group_rows, bstart,
+                           g.packed, g.bytes, g.maps, g.offsets, g.bases, u.packed, u.bytes, u.maps, u.offsets, u.bases, (int)count, n, th, tw,
+                           bias_gate, bias_up, ldb, act, y, ldy);
+}
+
+extern "C" int mtq_packed_glu_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                           const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                           const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                           const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n, const float *bias_gate,
+                                           const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, void *workspace,
+                                           size_t workspace_bytes, void *stream)
+{
+    if (!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets || !up_bases || !y)
+        return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    int eff;
+    if (int rc = grouped_shape(total_rows, count, n, k, 1, &th, &tw, &eff)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if ((bias_gate || bias_up) && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
+    if (reinterpret_cast<uintptr_t>(gate_packed) % 16 != 0 || reinterpret_cast<uintptr_t>(up_packed) % 16 != 0)
+        return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    const uint64_t least = (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2);
+    if (gate_bytes < least || up_bytes < least) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
+    if (int rc = glu_act(act)) return rc;
+    const size_t need = grouped_plan_bytes(count);
+    if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and the block plan needs one");
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
+    if (workspace_bytes < need)
+        return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this call needs", workspace_bytes, need);
+    // mtq_packed_linear_wide_grouped's slot bound
+    const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
+    const int64_t blocks = slots * ((n + kGluBN - 1) / kGluBN);
+    if (slots > INT32_MAX || blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *bstart = static_cast<int32_t *>(workspace);
+    hipLaunchKernelGGL(packed_grouped_wide_plan_kernel, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
+    if (int rc = check_launch("mtq_packed_glu_wide_grouped")) return rc;
+    const bool x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0 && k % 8 == 0;
+    const GluArena ga = {static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases};
+    const GluArena ua = {static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases};
+    (x_vec ? launch_glu_wide_grouped<true> : launch_glu_wide_grouped<false>)(blocks, st, static_cast<const uint16_t *>(x), total_rows, k, ldx,
+                                                                             group_rows, bstart, ga, ua, count, n, th, tw, bias_gate, bias_up, ldb,
+                                                                             act, y, out_dtype, ldy);
+    return check_launch("mtq_packed_glu_wide_grouped");
 }
 
 extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)

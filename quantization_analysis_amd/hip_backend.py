@@ -127,6 +127,10 @@ SIGNATURES = {
     "mtq_packed_linear_skinny_grouped_chunked": ("i", "plllppzpppllplpilipzp", True),
     "mtq_packed_linear_wide_grouped_workspace_bytes": ("z", "llll", True),
     "mtq_packed_linear_wide_grouped": ("i", "plllppzpppllplpilpzp", True),
+    "mtq_glu_combine": ("i", "plplllipilp", True),
+    "mtq_packed_glu_wide": ("i", "plllpzpppzpplppipilp", True),
+    "mtq_packed_glu_wide_grouped_workspace_bytes": ("z", "llll", True),
+    "mtq_packed_glu_wide_grouped": ("i", "plllppzppppzpppllpplipilpzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1293,6 +1297,141 @@ def packed_linear_wide_grouped(x, group_rows, arena, maps_dev, offsets_dev, base
     none is given."""
     return _packed_linear_grouped_call("mtq_packed_linear_wide_grouped", packed_linear_wide_grouped_workspace_bytes, x, group_rows, arena,
                                        maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out, None, workspace, stream)
+
+
+ACT_CODE = {"silu": 0, "none": 1}   # include/mtq.h MTQ_ACT_SILU, MTQ_ACT_NONE
+PACKED_GLU = ("mtq_glu_combine", "mtq_packed_glu_wide", "mtq_packed_glu_wide_grouped", "mtq_packed_glu_wide_grouped_workspace_bytes")
+
+
+def has_packed_glu() -> bool:
+    """Whether this build of the library has the gated entries (mtq_glu_combine, mtq_packed_glu_wide, mtq_packed_glu_wide_grouped and
+    its size function; optional symbols: an older build of the same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in PACKED_GLU)
+
+
+def _act_code(act) -> int:
+    if act not in ACT_CODE:
+        raise MtqError(f"act must be one of {tuple(ACT_CODE)}, got {act!r}")
+    return ACT_CODE[act]
+
+
+def _glu_out(out, rows: int, cols: int, out_dtype, device, zeros: bool = False):
+    """`out` checked, or a new (rows, cols) tensor → (out, ldy)."""
+    torch = _torch()
+    if out is None:
+        require_gpu()
+        out = (torch.zeros if zeros else torch.empty)((rows, cols), dtype=out_dtype, device=device)
+    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (rows, cols) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {out_dtype} ({rows}, {cols}) device tensor with contiguous rows")
+    return out, (out.stride(0) if rows > 1 else max(out.stride(0), cols))
+
+
+def glu_combine(g, u, act="silu", out_dtype=None, out=None, stream="current"):
+    """mtq_glu_combine on the current stream: y = act(g) * u element by element for two float32 (rows, cols) device tensors with
+    contiguous rows (any row pitch) → float32 or bfloat16 (rows, cols); the activation is the fused kernels' own function, every
+    operation a float32 one.  An empty operand gives the empty result without a call."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    for name, t in (("g", g), ("u", u)):
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_cuda or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise MtqError(f"{name} must be a float32 2-D device tensor with contiguous rows")
+    if tuple(g.shape) != tuple(u.shape):
+        raise MtqError(f"g and u must have one shape, got {tuple(g.shape)} and {tuple(u.shape)}")
+    rows, cols = (int(v) for v in g.shape)
+    fn = _entry("mtq_glu_combine")
+    out, ldy = _glu_out(out, rows, cols, out_dtype, g.device)
+    if rows == 0 or cols == 0:
+        return out
+    ldg, ldu = (t.stride(0) if rows > 1 else max(t.stride(0), cols) for t in (g, u))
+    check(fn(g.data_ptr(), ldg, u.data_ptr(), ldu, rows, cols, a, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_glu_wide(x, gate_data, gate_tables: PackedTables, up_data, up_tables: PackedTables, n: int, act="silu", bias_gate=None, bias_up=None,
+                    out_dtype=None, out=None, stream="current"):
+    """mtq_packed_glu_wide on the current stream: act(X·Ŵgᵀ + bg) * (X·Ŵuᵀ + bu) for an (m, k) bf16 device tensor X and two packed
+    (n, k) weights in one launch → (m, n) float32 or bfloat16: bit for bit two packed_linear calls into float32 and glu_combine.
+    m = 0 or n = 0 gives the empty (m, n) tensor without a launch."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    for name, tables in (("gate", gate_tables), ("up", up_tables)):
+        if tiles_hw(n, k) != (tables.tiles_h, tables.tiles_w):
+            raise MtqError(f"the {name} map is {tables.tiles_h}x{tables.tiles_w} tiles, a {n}x{k} weight has {'x'.join(map(str, tiles_hw(n, k)))}")
+    pg, pu = _packed_stream(gate_data, gate_tables, "gate data"), _packed_stream(up_data, up_tables, "up data")
+    bg = None if bias_gate is None else _buffer(bias_gate, torch.float32, n, "bias_gate")
+    bu = None if bias_up is None else _buffer(bias_up, torch.float32, n, "bias_up")
+    fn = _entry("mtq_packed_glu_wide")
+    out, ldy = _glu_out(out, m, n, out_dtype, x.device)
+    if m == 0 or n == 0:                             # the entry refuses empty operands, as the wide entry does: they end here
+        return out
+    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
+             up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_glu_wide_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int) -> int:
+    """mtq_packed_glu_wide_grouped_workspace_bytes (a host function: no GPU): packed_linear_wide_grouped_workspace_bytes' answer."""
+    size = int(_entry("mtq_packed_glu_wide_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k)))
+    if size == ctypes.c_size_t(-1).value:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return size
+
+
+def packed_glu_wide_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None, out=None,
+                            workspace=None, stream="current"):
+    """mtq_packed_glu_wide_grouped on the current stream: packed_glu_wide's product for the `count` experts of two arenas, each over its
+    own rows of X, in one launch.  gate, up: (arena, maps_dev, offsets_dev, bases_dev) as packed_linear_wide_grouped takes them, of
+    `count` (n, k) experts each; x, group_rows, out and workspace as there; bias_gate, bias_up: None or float32 (count, n) device
+    tensors of one row pitch.  Per group the bits of two packed_linear calls into float32 and glu_combine on the group's rows.  An
+    `out` allocated here starts as zeros, so rows outside every group are zeros."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    count, n = int(count), int(n)
+    x_code, _count, _stride, T, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if count <= 0 or n <= 0:
+        raise MtqError("count and n must be positive")
+    th, tw = tiles_hw(n, k)
+    sides = []
+    for name, (arena, maps_dev, offsets_dev, bases_dev) in (("gate", gate), ("up", up)):
+        pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+        sides += [_arena(arena, count, th * tw, f"the {name} arena"), arena.numel(), pm, po, pb]
+    pg = _buffer(group_rows, torch.int32, count + 1, "group_rows")
+    if group_rows.numel() != count + 1:
+        raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got {group_rows.numel()}")
+    ptrs, ldb = [], 0
+    for name, bias in (("bias_gate", bias_gate), ("bias_up", bias_up)):
+        if bias is None:
+            ptrs.append(None)
+            continue
+        if bias.dtype != torch.float32 or bias.dim() != 2 or tuple(bias.shape) != (count, n) or bias.stride(1) != 1 or not bias.is_cuda:
+            raise MtqError(f"{name} must be a float32 ({count}, {n}) device tensor with contiguous rows")
+        pitch = bias.stride(0) if count > 1 else max(bias.stride(0), n)
+        if ldb and pitch != ldb:
+            raise MtqError("bias_gate and bias_up must have one row pitch")
+        ptrs.append(bias.data_ptr())
+        ldb = pitch
+    need = packed_glu_wide_grouped_workspace_bytes(T, count, n, k) if T else 0
+    fn = _entry("mtq_packed_glu_wide_grouped")
+    out, ldy = _glu_out(out, T, n, out_dtype, x.device, zeros=True)
+    if T == 0:
+        return out
+    if workspace is None:
+        require_gpu()
+        workspace = torch.empty((need,), dtype=torch.uint8, device=x.device)
+    ws_ptr, ws_bytes = _buffer(workspace, torch.uint8, need, "workspace"), int(workspace.numel())
+    if workspace.data_ptr() % 16:
+        raise MtqError("workspace must be 16-byte aligned")
+    check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, ws_ptr, ws_bytes,
+             _packed_stream_ptr(stream)))
+    return out
 
 
 def debug_packed_decode(fmt: str):

@@ -8,7 +8,10 @@ pack_batch / unpack_batch take a batch of equal-shaped tensors and their maps (a
 arena and back with a fixed number of launches; save_dir / load_dir keep a named set of packed tensors in a directory.  linear_grouped /
 linear_batch / PackedExperts multiply with every tensor of such an arena (the experts of an MoE layer) over its own rows of X in one
 launch; linear_grouped_wide is that product for experts with hundreds of rows (prefill), from the wide-block kernel; as_batch makes the
-arena of any list of equal-shaped packed tensors.
+arena of any list of equal-shaped packed tensors.  glu / glu_grouped are the first half of a gated MLP, act(gate(x)) * up(x), with the
+two projections fused in one launch of the wide-block kernel (or, bit for bit the same, unfused); PackedMLP and PackedExpertsMLP are
+down(act(gate(x)) * up(x)) as modules, dense and over an arena of experts.  Not built: a fused kernel for the decode range (the skinny
+family's split over K has partial sums), the transposed layout, activations other than ACTS.
 
 Two backends:
   "hip"        the C ABI (csrc/mtq_packed.hip) through hip_backend's wrappers; data lives on the device.
@@ -42,6 +45,20 @@ AUTO_SKINNY_MAX_M = 32
 # from which on the wide kernel's median is below the block kernel's minimum of the same run at every shape and map (DESIGN.md §A.6k,
 # profiles/packed_linear_wide.txt).  Both kernels give the same bits, so the gate changes no result.
 AUTO_WIDE_MIN_M = 64
+ACTS = ("silu", "none")     # include/mtq.h MTQ_ACT_SILU, MTQ_ACT_NONE
+GLU_KERNELS = ("fused", "unfused", "auto")
+GLU_GROUPED_KERNELS = ("fused", "unfused")
+# glu(kernel="auto") above the skinny range takes the fused kernel (mtq_packed_glu_wide) from this m on; None: never, "auto" stays
+# unfused there.  The rule of AUTO_WIDE_MIN_M: the smallest measured m from which on the fused median is below the unfused minimum of the
+# same run at every shape and map (profiles/packed_glu.txt).  Both routes give the same bits, so the gate changes no
+# result.
+AUTO_GLU_FUSED_MIN_M = 64
+# The largest error of the device's silu (csrc/mtq_glu.hpp glu_value at u = 1) against float64, in units of 2^-24 relative to the value,
+# over every 2^10-th float32 of [-88.7228, 100], rounded up to a hundredth: measured; the GPU tests hold the kernel to
+# it and form their bound's constant from it.  Below -88.7228 expf(-g) overflows and the sequence gives -0.
+GLU_SILU_MAX_ULPS = 2.43
+# A bound on |silu'| (its maximum is 1.09984 near g = 2.4): the slope the accuracy bound of glu's tests multiplies the gate's error by.
+GLU_SILU_SLOPE_MAX = 1.1
 
 
 def _is_torch(x) -> bool:
@@ -823,6 +840,298 @@ def linear_grouped_wide(x, group_rows, pts_or_batch, bias=None, out_dtype: str =
                                          out_dtype=dtype, workspace=workspace)
 
 
+# ----------------------------------------------------------------------------- the gated product (SwiGLU)
+
+def _check_act(act) -> None:
+    if act not in ACTS:
+        raise MtqError(f"act must be one of {ACTS}, got {act!r}")
+
+
+def _glu_host(g64: np.ndarray, u64: np.ndarray, act: str) -> np.ndarray:
+    """act(g) * u in float64: the emulation's value before its final rounding."""
+    if act == "none":
+        return g64 * u64
+    with np.errstate(over="ignore", invalid="ignore"):
+        return g64 / (1.0 + np.exp(-g64)) * u64
+
+
+def _host_f64(v, shape, name: str):
+    if v is None:
+        return None
+    b = v.detach().to("cpu").double().numpy() if _is_torch(v) else np.asarray(v, dtype=np.float64)
+    if b.shape != shape:
+        raise MtqError(f"{name} must be {shape}, got {b.shape}")
+    return b
+
+
+def _round_out(h64: np.ndarray, out_dtype: str):
+    """float64 → float32 once, and from there to bf16, as linear's emulation rounds."""
+    with np.errstate(over="ignore"):
+        y32 = h64.astype(np.float32)
+    if out_dtype == "float32":
+        return y32
+    import torch
+
+    return torch.from_numpy(y32).to(torch.bfloat16)
+
+
+def _glu_pair(gate: PackedTensor, up: PackedTensor) -> None:
+    for name, pt in (("gate", gate), ("up", up)):
+        _check_layout(pt.layout)
+        if len(pt.shape) != 2:
+            raise MtqError(f"glu needs 2-D (n, k) weights, the packed {name} tensor is {pt.shape}")
+    if (gate.rows, gate.cols) != (up.rows, up.cols):
+        raise MtqError(f"gate and up must have one shape, got {gate.rows}x{gate.cols} and {up.rows}x{up.cols}")
+
+
+def _need_glu(hb, what: str) -> None:
+    if not hb.has_packed_glu():
+        raise MtqError(f"{what} needs mtq_glu_combine, mtq_packed_glu_wide and mtq_packed_glu_wide_grouped, which this build of libmtq_hip.so "
+                       "lacks: rebuild it from this tree")
+
+
+def glu(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
+        backend: Optional[str] = None, kernel: str = "auto"):
+    """H = act(X·Ŵgᵀ + bg) * (X·Ŵuᵀ + bu), the first half of a gated MLP, with two packed (n, k) weights of one shape in the row layout.
+    act (ACTS): "silu", g / (1 + exp(-g)) * u, or "none", g * u (the bilinear GLU).
+
+    hip (the default when the gate's stream is on the device): X an (m, k) bf16 device tensor, the biases float32 [n] or None.  kernel
+    (GLU_KERNELS): "fused", mtq_packed_glu_wide, one launch in which a workgroup holds both projections of its outputs, so X is read
+    once and no (m, n) intermediate reaches memory; "unfused", two linear(kernel="block") calls into float32 and hip_backend.glu_combine,
+    bit for bit what "fused" gives; "auto": for m <= AUTO_SKINNY_MAX_M two linear(kernel="skinny") calls and the combine (the skinny
+    family's sums, which may differ from the block family's in the last bits, as linear(kernel="auto") already does; there is no fused
+    kernel for the decode range), above that "fused" from m = AUTO_GLU_FUSED_MIN_M on when that is not None, "unfused" otherwise.  A
+    library without the gated entries raises MtqError under every name: there is no fall-back.
+    emulation: float64 throughout from the unpacked weights, g = X·Ŵgᵀ + bg, u likewise, act(g) * u, rounded once to float32 and from
+    there to bf16, as linear's emulation rounds; the same value under every kernel name."""
+    _glu_pair(gate, up)
+    _check_act(act)
+    if kernel not in GLU_KERNELS:
+        raise MtqError(f"kernel must be one of {GLU_KERNELS}, got {kernel!r}")
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    backend = backend or ("hip" if gate.on_device else "emulation")
+    n, k = gate.rows, gate.cols
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        if x.dim() != 2 or x.shape[1] != k:
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        _need_glu(hb, "glu")
+        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        m = int(x.shape[0])
+        if kernel == "auto":
+            kernel = "skinny" if m <= AUTO_SKINNY_MAX_M else ("fused" if AUTO_GLU_FUSED_MIN_M is not None and m >= AUTO_GLU_FUSED_MIN_M else "unfused")
+        if kernel == "fused":
+            return hb.packed_glu_wide(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act, bias_gate=bias_gate,
+                                      bias_up=bias_up, out_dtype=dtype)
+        if kernel == "skinny":
+            g = hb.packed_linear_skinny(x, _device_data(gate), gate.tables(), n, bias=bias_gate, out_dtype=torch.float32)
+            u = hb.packed_linear_skinny(x, _device_data(up), up.tables(), n, bias=bias_up, out_dtype=torch.float32)
+        else:
+            g = hb.packed_linear(x, _device_data(gate), gate.tables(), n, bias=bias_gate, out_dtype=torch.float32)
+            u = hb.packed_linear(x, _device_data(up), up.tables(), n, bias=bias_up, out_dtype=torch.float32)
+        return hb.glu_combine(g, u, act=act, out_dtype=dtype)
+    if backend != "emulation":
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
+    if xf.ndim != 2 or xf.shape[1] != k:
+        raise MtqError(f"x must be (m, {k}), got {xf.shape}")
+    return _round_out(glu_emulation_f64(xf, gate, up, act, bias_gate, bias_up), out_dtype)
+
+
+def glu_emulation_f64(xf: np.ndarray, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None) -> np.ndarray:
+    """The emulation's float64 (m, n) value before its final rounding: what the accuracy tests measure against."""
+    n, k = gate.rows, gate.cols
+    x64 = np.asarray(xf, dtype=np.float32).astype(np.float64)
+    sides = []
+    for pt, bias, name in ((gate, bias_gate, "bias_gate"), (up, bias_up, "bias_up")):
+        w = decode(_host_data(pt), pt.map, pt.offsets, n, k).view(np.float32)
+        with np.errstate(over="ignore", invalid="ignore"):
+            y = x64 @ w.astype(np.float64).T
+        b = _host_f64(bias, (n,), name)
+        sides.append(y if b is None else y + b[None, :])
+    return _glu_host(sides[0], sides[1], act)
+
+
+def glu_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
+                backend: Optional[str] = None, kernel: str = "fused", workspace=None):
+    """glu for all experts of an MoE layer at once → (T, n): H[rows of group e] = act(X[rows]·Ŵg[e]ᵀ + bg[e]) * (X[rows]·Ŵu[e]ᵀ + bu[e]).
+    x, group_rows as linear_grouped_wide's; gate_batch, up_batch: two batches of `count` (n, k) experts each, resolved as
+    linear_grouped_wide resolves its argument (a PackedBatch as it is, a list through as_batch); the biases (count, n) float32 or None.
+    hip: kernel "fused", mtq_packed_glu_wide_grouped, one launch over both arenas with the block list made on the device (workspace: an
+    optional uint8 device tensor of hip_backend.packed_glu_wide_grouped_workspace_bytes bytes); "unfused", two linear_grouped_wide calls
+    into float32 and hip_backend.glu_combine over all T rows - the same bits on every row of a group (a row of no group is zero under
+    "fused" and act(0) * 0 = 0 under "unfused").  T = 0 gives (0, n) without a call.
+    emulation: per group glu's float64 value, rounded once."""
+    gate_b, up_b = _resolve_batch(gate_batch), _resolve_batch(up_batch)
+    _check_act(act)
+    if kernel not in GLU_GROUPED_KERNELS:
+        raise MtqError(f"kernel must be one of {GLU_GROUPED_KERNELS}, got {kernel!r}")
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    if (gate_b.count, gate_b.rows, gate_b.cols) != (up_b.count, up_b.rows, up_b.cols):
+        raise MtqError(f"the gate and the up batch must hold as many experts of one shape, got {gate_b.count} of {gate_b.rows}x{gate_b.cols} and "
+                       f"{up_b.count} of {up_b.rows}x{up_b.cols}")
+    backend = backend or ("hip" if _batch_on_device(gate_b) else "emulation")
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    count, n, k = gate_b.count, gate_b.rows, gate_b.cols
+    if len(x.shape) != 2 or x.shape[1] != k:
+        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
+    T = int(x.shape[0])
+    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
+    if not on_device:
+        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        _need_glu(hb, "glu_grouped")                 # a missing kernel is refused before any device work
+        gate_b, up_b = batch_to_device(gate_b), batch_to_device(up_b)
+        dev = gate_b.arena.device
+        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        if T == 0:
+            return torch.zeros((0, n), dtype=dtype, device=dev)
+        if not on_device:
+            group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(dev)
+        bias_gate, bias_up = (b if b is None or _is_torch(b) else torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(dev)
+                              for b in (bias_gate, bias_up))
+        if kernel == "fused":
+            return hb.packed_glu_wide_grouped(x, group_rows, (gate_b.arena, gate_b.maps_dev, gate_b.offsets_dev, gate_b.bases_dev),
+                                              (up_b.arena, up_b.maps_dev, up_b.offsets_dev, up_b.bases_dev), count, n, act=act,
+                                              bias_gate=bias_gate, bias_up=bias_up, out_dtype=dtype, workspace=workspace)
+        g = linear_grouped_wide(x, group_rows, gate_b, bias=bias_gate, out_dtype="float32", backend="hip", workspace=workspace)
+        u = linear_grouped_wide(x, group_rows, up_b, bias=bias_up, out_dtype="float32", backend="hip", workspace=workspace)
+        return hb.glu_combine(g, u, act=act, out_dtype=dtype)
+    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
+    if on_device:                                    # trusted, as on hip: what the kernel makes of it
+        if tuple(group_rows.shape) != (count + 1,):
+            raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {tuple(group_rows.shape)}")
+        r0, r1 = clamp_group_rows(group_rows.cpu().numpy(), T)
+    else:
+        r0, r1 = group_rows[:-1], group_rows[1:]
+    bg, bu = _host_f64(bias_gate, (count, n), "bias_gate"), _host_f64(bias_up, (count, n), "bias_up")
+    h = np.zeros((T, n), dtype=np.float64)
+    x64 = xf.astype(np.float64)
+    for e, (tg, tu) in enumerate(zip(_batch_host_tensors(gate_b), _batch_host_tensors(up_b))):
+        if r1[e] == r0[e]:
+            continue
+        sides = []
+        for (amap, offsets, data), b in ((tg, bg), (tu, bu)):
+            w = decode(data, amap, offsets, n, k).view(np.float32)
+            y = x64[r0[e]: r1[e]] @ w.astype(np.float64).T
+            sides.append(y if b is None else y + b[e][None, :])
+        h[r0[e]: r1[e]] = _glu_host(sides[0], sides[1], act)
+    return _round_out(h, out_dtype)
+
+
+def _packed_mlp_class():
+    import torch
+
+    class PackedMLP(torch.nn.Module):
+        """A gated MLP over three packed weights, down(act(gate(x)) * up(x)): gate and up (n, k), down (k_out, n).  INFERENCE ONLY, as
+        PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, runs glu(kernel="auto") into bf16 and
+        linear(kernel="auto") with `down`, and returns (..., k_out) in out_dtype; m = 0 gives the empty result without a call."""
+
+        def __init__(self, gate: PackedTensor, up: PackedTensor, down: PackedTensor, act: str = "silu", out_dtype: str = "bfloat16",
+                     backend: Optional[str] = None):
+            super().__init__()
+            _glu_pair(gate, up)
+            _check_act(act)
+            _check_layout(down.layout)
+            if len(down.shape) != 2 or down.cols != gate.rows:
+                raise MtqError(f"down must be a 2-D (k_out, {gate.rows}) weight, the packed tensor is {down.shape}")
+            if out_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            self.backend = backend or ("hip" if gate.on_device else "emulation")
+            if self.backend not in BACKENDS:
+                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            if self.backend == "hip":
+                from . import hip_backend as hb
+
+                _need_glu(hb, "PackedMLP")           # refused here, not at the first forward
+                for pt in (gate, up, down):
+                    _device_data(pt)
+                    pt.tables()
+            self.gate, self.up, self.down, self.act, self.out_dtype = gate, up, down, act, out_dtype
+            self.in_features, self.hidden_features, self.out_features = gate.cols, gate.rows, down.rows
+
+        def extra_repr(self) -> str:
+            return f"in_features={self.in_features}, hidden_features={self.hidden_features}, out_features={self.out_features}, " \
+                   f"act={self.act!r}, backend={self.backend!r}"
+
+        @torch.no_grad()
+        def forward(self, x):
+            if x.shape[-1] != self.in_features:
+                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
+            lead = tuple(x.shape[:-1])
+            x2 = x.reshape(-1, self.in_features)
+            if x2.shape[0] == 0:
+                return torch.zeros(lead + (self.out_features,), dtype=torch.float32 if self.out_dtype == "float32" else torch.bfloat16, device=x.device)
+            h = glu(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="auto")
+            y = linear(h, self.down, out_dtype=self.out_dtype, backend=self.backend, kernel="auto")
+            if not _is_torch(y):
+                y = torch.from_numpy(y)
+            return y.reshape(lead + (self.out_features,))
+
+    return PackedMLP
+
+
+def _packed_experts_mlp_class():
+    import torch
+
+    class PackedExpertsMLP(torch.nn.Module):
+        """The gated MLPs of the experts of one MoE layer: three batches of `count` experts, gate and up (n, k), down (k_out, n).
+        INFERENCE ONLY.  forward(x, group_rows): x (T, k) bf16, group e owning rows [group_rows[e], group_rows[e + 1]) → (T, k_out):
+        glu_grouped (kernel "fused") into bf16, then linear_grouped_wide with the down batch.  The batches are resolved once, here; on hip
+        the arenas, their tables and the one plan workspace both launches use stay on the device.  T = 0 gives the empty result."""
+
+        def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", backend: Optional[str] = None):
+            super().__init__()
+            _check_act(act)
+            if out_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            gate, up, down = (_resolve_batch(b) for b in (gate_pts, up_pts, down_pts))
+            if (gate.count, gate.rows, gate.cols) != (up.count, up.rows, up.cols):
+                raise MtqError("the gate and the up batch must hold as many experts of one shape")
+            if down.count != gate.count or down.cols != gate.rows:
+                raise MtqError(f"the down batch must hold {gate.count} experts of (k_out, {gate.rows}), got {down.count} of {down.rows}x{down.cols}")
+            self.backend = backend or ("hip" if _batch_on_device(gate) else "emulation")
+            if self.backend not in BACKENDS:
+                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            self._workspace = None
+            if self.backend == "hip":
+                from . import hip_backend as hb
+
+                _need_glu(hb, "PackedExpertsMLP")    # refused here, not at the first forward
+                if not hb.has_packed_linear_wide_grouped():
+                    raise MtqError("PackedExpertsMLP needs mtq_packed_linear_wide_grouped, which this build of libmtq_hip.so lacks")
+                gate, up, down = (batch_to_device(b) for b in (gate, up, down))
+                need = hb.packed_glu_wide_grouped_workspace_bytes(1, gate.count, gate.rows, gate.cols)   # a function of count alone
+                self._workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
+            self.gate, self.up, self.down, self.act, self.out_dtype = gate, up, down, act, out_dtype
+            self.count, self.in_features, self.hidden_features, self.out_features = gate.count, gate.cols, gate.rows, down.rows
+
+        def extra_repr(self) -> str:
+            return f"count={self.count}, in_features={self.in_features}, hidden_features={self.hidden_features}, " \
+                   f"out_features={self.out_features}, act={self.act!r}, backend={self.backend!r}"
+
+        @torch.no_grad()
+        def forward(self, x, group_rows):
+            if x.dim() != 2 or x.shape[1] != self.in_features:
+                raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
+            h = glu_grouped(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="fused",
+                            workspace=self._workspace)
+            y = linear_grouped_wide(h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend, workspace=self._workspace)
+            return y if _is_torch(y) else torch.from_numpy(y)
+
+    return PackedExpertsMLP
+
+
 def _packed_linear_class():
     import torch
 
@@ -969,10 +1278,12 @@ def _packed_experts_class():
 
 
 def __getattr__(name):
-    """PackedLinear and PackedExperts are torch.nn.Modules: a class is made on first use, so that importing this module does not import
-    torch."""
-    if name in ("PackedLinear", "PackedExperts"):
-        cls = _packed_linear_class() if name == "PackedLinear" else _packed_experts_class()
+    """PackedLinear, PackedExperts, PackedMLP and PackedExpertsMLP are torch.nn.Modules: a class is made on first use, so that importing
+    this module does not import torch."""
+    makers = {"PackedLinear": _packed_linear_class, "PackedExperts": _packed_experts_class, "PackedMLP": _packed_mlp_class,
+              "PackedExpertsMLP": _packed_experts_mlp_class}
+    if name in makers:
+        cls = makers[name]()
         globals()[name] = cls
         return cls
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
