@@ -636,6 +636,26 @@ int mtq_pack_tiles(const void *x, int in_dtype, int64_t rows, int64_t cols, int6
 int mtq_unpack_tiles(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows, int64_t cols,
                      void *y, int out_dtype, int64_t ldy, void *stream);
 
+/* The transposed pair: a weight stored rows × cols whose packed form is the stream of its TRANSPOSE.  A map over the transposed layout of
+ * W (a shared exponent per 16 rows of one column) is by definition a row-layout map of Wᵀ over Wᵀ's tile grid
+ * ceil(cols/32) × ceil(rows/32), numbered row-major as mtq_tile_stats_transposed numbers it (element (r, c) of W lies in tile
+ * (c / 32) * ceil(rows / 32) + r / 32).  So the packed transposed weight is the format above of the cols × rows matrix Wᵀ: no new byte
+ * format, no new layout value.  These entries read and write W's own orientation; no transposed copy is made.
+ *
+ * mtq_pack_tiles_transposed: w (in_dtype, rows × cols as stored, pitch ld >= cols), map and offsets over Wᵀ's grid → out, byte for byte
+ * what mtq_pack_tiles writes for a contiguous copy of Wᵀ with the same map.  One wave per tile, one lane per group; a lane's 16 values
+ * are 16 consecutive rows of one column of w, rows and columns past the edge read +0; the blob checks against out_bytes are
+ * mtq_pack_tiles's.
+ * mtq_unpack_tiles_transposed: the mirror image, the stream of Wᵀ → y (rows × cols, ldy >= cols).  MTQ_DTYPE_F32: bit for bit what
+ * mtq_apply_assignment_transposed writes for the packed w and map; MTQ_DTYPE_BF16: the upper halves.  Nothing is stored outside
+ * rows × cols, nor for a tile whose blob passes packed_bytes.
+ * Argument errors (null pointers, a dtype, rows or cols <= 0, ld < cols, a buffer below 320 bytes per tile, a stream that is not 16-byte
+ * aligned) are MTQ_ERR_INVALID before a device is looked for.  Optional symbols. */
+int mtq_pack_tiles_transposed(const void *w, int in_dtype, int64_t rows, int64_t cols, int64_t ld, const int8_t *map, const uint32_t *offsets,
+                              void *out, size_t out_bytes, void *stream);
+int mtq_unpack_tiles_transposed(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows, int64_t cols,
+                                void *y, int out_dtype, int64_t ldy, void *stream);
+
 /* The batch: `count` tensors of one shape into ONE arena, tensor i's stream at byte 64 * bases[i], with no host work per tensor.  All
  * pointers are device pointers and the calls are asynchronous on `stream`.
  *
@@ -690,6 +710,24 @@ int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const vo
  * returns it without a call. */
 int mtq_packed_linear_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                            const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream);
+
+/* Y = X·P̂ + b for a packed k × n matrix P̂ (input-major weights, y = x @ W; and the transposed layout of an n × k weight, whose stream
+ * is that of its k × n transpose: mtq_pack_tiles_transposed): x m × k bf16 (ldx), map grid ceil(k/32) × ceil(n/32), bias n float32 or
+ * NULL, y m × n (out_dtype, ldy).  Argument checks, refusals and device guards are mtq_packed_linear's: a tile whose blob passes
+ * packed_bytes or whose map code is outside 0..3 multiplies as zeros in its own tile only, rows at or past m and columns at or past k of
+ * x are never read, k-rows of P̂ at or past k count as zeros, nothing outside m x n of y is written.
+ *
+ * mtq_packed_linear's frame (4 waves, 128 (M) x 64 (N), K steps of 64, the fetch one step ahead, mfma_f32_32x32x16_bf16 into two
+ * accumulators per wave, its epilogue).  A group's 16 values run along n at one k here, so a lane stores its decoded group as it lies
+ * into a [k][n] LDS image and the B operand (8 consecutive k at one n) is read from it with the transposed LDS read of gfx950, two
+ * reads per operand.
+ *
+ * Bit contract: for every input, y equals bit for bit what mtq_packed_linear gives for the same x and bias with the all-bf16 row-layout
+ * packing of unpack(P̂)ᵀ (n × k; lossless, every decoded value is a bf16), in both output types, with or without bias.  The operand
+ * positions are the block kernel's: the same k at the same lane half and element, the same order of 16-blocks, the same K step.
+ * No atomics, no workspace: two calls give the same bits.  Any m >= 1.  Optional symbol. */
+int mtq_packed_matmul(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                      const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream);
 
 /* The same product for decode, 1 <= m <= MTQ_PACKED_SKINNY_MAX_M: a split over K.  One wave takes the run of tiles of one tile row over
  * one K slice (a contiguous byte range of the stream), loads it straight to registers several tiles ahead, decodes each lane's group to

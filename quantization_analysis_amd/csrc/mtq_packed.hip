@@ -32,6 +32,11 @@
 //       128 × 64 block whose four tile-row slots alternate between the gate and the up stream, so a lane holds both projections of its
 //       outputs; the same block in the grouped wide frame; and the element-wise combine that finishes the unfused route with the same
 //       function (mtq_glu.hpp) and so the same bits.
+//   pack_tiles_transposed_kernel / unpack_tiles_transposed_kernel
+//                                             the stream of the TRANSPOSE of a stored matrix, read / written in the stored orientation: a
+//       map over the transposed layout of W is a row-layout map of Wᵀ, so this is the same format (no new bytes, no new layout value).
+//   packed_matmul_kernel                      Y = X·P̂ + b for a packed k × n matrix: the block kernel's frame over a [k][n] LDS image
+//       that is read with the transposed LDS read (ds_read_b64_tr_b16); bit for bit the block kernel on the transposed weight.
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
 // blob does not fit is not written (pack), not stored (unpack) or read as zeros (linear).
@@ -151,14 +156,9 @@ __device__ __forceinline__ void load_group(const uint8_t *__restrict__ packed, c
 }
 
 // ---- pack: lane = group (row lane >> 1, half lane & 1) of the wave's tile
-// Tile t (format f, 0..3) of the rows × cols matrix x → the blob: what one wave does, for the single-tensor and the batched kernel alike.
-template <typename T>
-__device__ __forceinline__ void pack_tile(const T *__restrict__ x, int64_t rows, int64_t cols, int64_t ld, bool vec_ok, int64_t tiles_w, int64_t t,
-                                          int f, int lane, uint8_t *__restrict__ blob)
+// The group's 16 float32 words u → its bytes in the blob of format f (0..3): the same for whichever way the words were fetched.
+__device__ __forceinline__ void pack_group(const uint32_t (&u)[kGroup], int f, int lane, uint8_t *__restrict__ blob)
 {
-    const int64_t row = (t / tiles_w) * kTile + (lane >> 1), col0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
-    uint32_t u[kGroup];
-    Loader<T>::group(x, row, col0, rows, cols, ld, vec_ok, u);
     if (f == 0) {
         uint32_t y[kGroup];
 #pragma unroll
@@ -187,6 +187,17 @@ __device__ __forceinline__ void pack_tile(const T *__restrict__ x, int64_t rows,
     else *reinterpret_cast<uint32_t *>(dst) = w[0];
 }
 
+// Tile t (format f, 0..3) of the rows × cols matrix x → the blob: what one wave does, for the single-tensor and the batched kernel alike.
+template <typename T>
+__device__ __forceinline__ void pack_tile(const T *__restrict__ x, int64_t rows, int64_t cols, int64_t ld, bool vec_ok, int64_t tiles_w, int64_t t,
+                                          int f, int lane, uint8_t *__restrict__ blob)
+{
+    const int64_t row = (t / tiles_w) * kTile + (lane >> 1), col0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
+    uint32_t u[kGroup];
+    Loader<T>::group(x, row, col0, rows, cols, ld, vec_ok, u);
+    pack_group(u, f, lane, blob);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void pack_tiles_kernel(const T *__restrict__ x, int64_t rows, int64_t cols, int64_t ld, int vec_ok,
                                                          const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t tiles,
@@ -199,6 +210,31 @@ __global__ __launch_bounds__(256) void pack_tiles_kernel(const T *__restrict__ x
         const uint64_t off = (uint64_t)offsets[t] * kUnit;
         if (size == 0u || off + size > out_bytes) continue;   // wave-uniform
         pack_tile(x, rows, cols, ld, vec_ok != 0, tiles_w, t, f, lane, out + off);
+    }
+}
+
+// The transposed entry: w is rows × cols as stored and the stream is that of wᵀ (cols × rows), whose grid the map, the offsets, `tiles` and
+// `tiles_w` (= ceil(rows / 32)) describe.  The lane's group is row c = 32 tr + lane / 2 of wᵀ, columns r0 = 32 tc + 16 (lane & 1) ..: 16
+// consecutive rows of column c of w.  For a fixed value index the wave reads two runs of 32 consecutive elements of a row of w.
+__device__ __forceinline__ uint32_t word_of(const uint16_t *__restrict__ p, int64_t at) { return (uint32_t)p[at] << 16; }
+__device__ __forceinline__ uint32_t word_of(const float *__restrict__ p, int64_t at) { return __float_as_uint(p[at]); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void pack_tiles_transposed_kernel(const T *__restrict__ w, int64_t rows, int64_t cols, int64_t ld,
+                                                                    const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets,
+                                                                    int64_t tiles, int64_t tiles_w, uint8_t *__restrict__ out, uint64_t out_bytes)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < tiles; t += (int64_t)gridDim.x * 4) {
+        const int f = map[t];
+        const uint32_t size = packed_tile_bytes(f);
+        const uint64_t off = (uint64_t)offsets[t] * kUnit;
+        if (size == 0u || off + size > out_bytes) continue;   // wave-uniform
+        const int64_t c = (t / tiles_w) * kTile + (lane >> 1), r0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
+        uint32_t u[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) u[i] = (c < cols && r0 + i < rows) ? word_of(w, (r0 + i) * ld + c) : 0u;
+        pack_group(u, f, lane, out + off);
     }
 }
 
@@ -268,6 +304,31 @@ __global__ __launch_bounds__(256) void unpack_tiles_kernel(const uint8_t *__rest
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < tiles; t += (int64_t)gridDim.x * 4)
         unpack_tile<BF16OUT>(packed, tile_at(packed_bytes, map, offsets, t), tiles_w, t, lane, rows, cols, yv, ldy, vec_ok != 0);
+}
+
+// The mirror image of pack_tiles_transposed_kernel: the stream of wᵀ → y in w's orientation (rows × cols, pitch ldy).  Nothing is stored
+// outside rows × cols, nor for a tile whose blob is not there.
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void unpack_tiles_transposed_kernel(const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+                                                                      const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets,
+                                                                      int64_t tiles, int64_t tiles_w, int64_t rows, int64_t cols,
+                                                                      void *__restrict__ yv, int64_t ldy)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < tiles; t += (int64_t)gridDim.x * 4) {
+        const int64_t c = (t / tiles_w) * kTile + (lane >> 1), r0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
+        GroupRaw g;
+        load_group(packed, tile_at(packed_bytes, map, offsets, t), lane, g);
+        if (g.f < 0 || c >= cols) continue;
+        uint32_t y[kGroup];
+        decode_group(g, y);
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            if (r0 + i >= rows) continue;
+            if constexpr (BF16OUT) static_cast<uint16_t *>(yv)[(r0 + i) * ldy + c] = (uint16_t)(y[i] >> 16);
+            else static_cast<uint32_t *>(yv)[(r0 + i) * ldy + c] = y[i];
+        }
+    }
 }
 
 // The batch, as pack_tiles_batched_kernel numbers it: matrix i of y starts i * stride elements in.
@@ -462,6 +523,145 @@ __global__ __launch_bounds__(kThreads) void packed_linear_kernel(const uint16_t 
             for (int s = 0; s < 2; ++s) {
                 const bf16x8 b = *reinterpret_cast<const bf16x8 *>(ws + (s * 32 + (lane & 31)) * kLdk + koff);
                 acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[s], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+
+    // epilogue: lane's outputs are (m0 + 32·wave + (r&3) + 8(r>>2) + 4(lane>>5), n0 + 32s + (lane&31))
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int64_t n = n0 + 32 * s + (lane & 31);
+        if (n >= N) continue;
+        const float b = bias ? bias[n] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t m = m0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (m >= M) continue;
+            const float v = acc[s][r] + b;
+            if constexpr (BF16OUT) static_cast<uint16_t *>(yv)[m * ldy + n] = f32_to_bf16(v);
+            else static_cast<float *>(yv)[m * ldy + n] = v;
+        }
+    }
+}
+
+// ---- matmul: Y = X·P̂ + b for a packed k × n matrix P̂ (a group's 16 values run along n at one k)
+//
+// packed_linear_kernel's frame: the same block, K step, X staging, one-step-ahead fetch, MFMA sequence and epilogue.  The W side differs:
+// lane tid owns the group at k-row k0 + tid / 4, columns n0 + 16 (tid % 4) .., and stores its 16 decoded bf16 as they lie (n-contiguous)
+// into a [k][n] image; the B operand (8 consecutive k at one n per lane) comes out of that image through the transposed LDS read, two
+// per operand (k +0..3, then +4..7).  Operand positions are the block kernel's - the same k at the same lane half and element, the same
+// kk order - so the sums are the block kernel's on the transposed weight, bit for bit.
+//
+// The image: one sub-image per 32-column slot s, [64 k][32 n] bf16 with a 64-byte row pitch, sub-image 1 a further 16 bytes on.  A
+// transposed read's 32-lane half takes 4 k-rows × 32 columns: byte q * 64 + 32 (g & 1) + 8 p for row q, group g, quarter p - 256
+// consecutive bytes, every one of the 64 banks once: conflict-free by the bank rule ((a / 4) % 64).  A plain [64][64 (+ 8)] image would
+// put rows q and q + 2 (128-byte pitch) or q + 2 less 8 banks (144-byte pitch) on the same banks: 2-way.  The 16 bytes between the
+// sub-images keep the 16-byte stores of an 8-lane group (4 lanes to each sub-image, 128 consecutive bytes each) on disjoint banks
+// ((a / 4) % 32): 0-3, 8-11, .. for s = 0 and 4-7, 12-15, .. for s = 1.
+//
+// The transposed read needs EXEC all ones: the kernel has no early return and the reads sit in no lane-dependent branch.  Tiles that are
+// absent (past the grid, a bad code, a blob past packed_bytes) and k-rows at or past K are zeros in the image.
+constexpr int kMmPitch = 32;                         // bf16 per image row: 64 bytes
+constexpr int kMmSub = kBK * kMmPitch + 8;           // bf16 from sub-image 0 to sub-image 1: the rows and 16 bytes
+
+typedef short i16x4 __attribute__((ext_vector_type(4)));
+typedef short i16x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ i16x4 lds_read_tr16(const uint16_t *p)
+{
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4 *)(p));
+}
+
+template <bool BF16OUT>
+__global__ __launch_bounds__(kThreads) void packed_matmul_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec,
+                                                                 const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+                                                                 const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N,
+                                                                 int64_t tiles_h, int64_t tiles_w, const float *__restrict__ bias,
+                                                                 void *__restrict__ yv, int64_t ldy)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[kBM * kLdk + 2 * kMmSub];
+    uint16_t *xs = lds;
+    uint16_t *ws = lds + kBM * kLdk;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t nblocks = (N + kBN - 1) / kBN;
+    const int64_t bm = blockIdx.x / nblocks, bn = blockIdx.x % nblocks;
+    const int64_t m0 = bm * kBM, n0 = bn * kBN;
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[s][r] = 0.0f;
+
+    // lane tid owns the group (k-row k0 + tid / 4, columns n0 + 16 (tid % 4) ..): group 2 (k % 32) + half of tile (k / 32, n / 32)
+    const int wrow = tid >> 2, wq = tid & 3;
+    const int64_t wtc = (n0 + wq * kGroup) >> 5;
+    const int wgi = 2 * (wrow & 31) + (wq & 1);      // k0 is a multiple of 64: (k0 + wrow) % 32 is wrow % 32
+    uint16_t *wdst = ws + (wq >> 1) * kMmSub + wrow * kMmPitch + (wq & 1) * kGroup;
+    // the transposed read of lane 16 g + 4 q + p: row 8 (lane >> 5) + q of the kk block, columns 16 (g & 1) + 4 p .. of the slot
+    const uint16_t *wsrc = ws + (8 * (lane >> 5) + ((lane >> 2) & 3)) * kMmPitch + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    uint4 xr[4];
+    GroupRaw wr;
+    TileAt at;                                       // of the step after the one in xr / wr: map and offsets run two steps ahead of the MFMAs
+    auto locate = [&](int64_t k0) {
+        const int64_t wtr = (k0 + wrow) >> 5;
+        at.off = 0;
+        at.f = -1;
+        if (k0 + wrow < K && wtc < tiles_w) at = tile_at(packed_bytes, map, offsets, wtr * tiles_w + wtc);
+    };
+    auto load_step = [&](int64_t k0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {   // X: 128 rows × 64 columns = 1024 pieces of 8 bf16, 4 per thread; columns past K are zeros, never read
+            const int p = tid + kThreads * i, row = p >> 3, c8 = (p & 7) * 8;
+            const int64_t gm = m0 + row, gk = k0 + c8;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (gm < M && gk < K) {
+                const uint16_t *src = x + gm * ldx + gk;
+                if (x_vec && gk + 8 <= K) {
+                    v = *reinterpret_cast<const uint4 *>(src);
+                } else {
+                    uint32_t h[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) h[j] = gk + j < K ? (uint32_t)src[j] : 0u;
+                    v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+                }
+            }
+            xr[i] = v;
+        }
+        load_group(packed, at, wgi, wr);             // the blob `at` names: located one step earlier
+        locate(k0 + kBK);
+    };
+    locate(0);
+    load_step(0);
+    for (int64_t k0 = 0; k0 < K; k0 += kBK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int p = tid + kThreads * i;
+            *reinterpret_cast<uint4 *>(xs + (p >> 3) * kLdk + (p & 7) * 8) = xr[i];
+        }
+        {
+            uint32_t y[kGroup];
+            decode_group(wr, y);
+            uint4 lo, hi;
+            pack_halves(y, lo, hi);
+            uint4 *d = reinterpret_cast<uint4 *>(wdst);
+            d[0] = lo;
+            d[1] = hi;
+        }
+        __syncthreads();
+        if (k0 + kBK < K) load_step(k0 + kBK);
+#pragma unroll
+        for (int kk = 0; kk < kBK / 16; ++kk) {
+            const int koff = kk * 16 + 8 * (lane >> 5);
+            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (wave * 32 + (lane & 31)) * kLdk + koff);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const uint16_t *src = wsrc + s * kMmSub + kk * 16 * kMmPitch;
+                const i16x4 b0 = lds_read_tr16(src), b1 = lds_read_tr16(src + 4 * kMmPitch);   // k + 0..3, k + 4..7
+                const i16x8 b = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+                acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, b), acc[s], 0, 0, 0);
             }
         }
         __syncthreads();
@@ -1883,6 +2083,50 @@ extern "C" int mtq_unpack_tiles(const void *packed, size_t packed_bytes, const i
     return check_launch("mtq_unpack_tiles");
 }
 
+// The transposed pair: w / y in the stored orientation (rows × cols), the stream that of the cols × rows transpose.
+extern "C" int mtq_pack_tiles_transposed(const void *w, int in_dtype, int64_t rows, int64_t cols, int64_t ld, const int8_t *map,
+                                         const uint32_t *offsets, void *out, size_t out_bytes, void *stream)
+{
+    if (!w || !map || !offsets || !out) return fail(MTQ_ERR_INVALID, "null argument");
+    if (in_dtype != MTQ_DTYPE_BF16 && in_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "in_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;                                   // of the transpose
+    if (int rc = tile_grid(cols, rows, &th, &tw)) return rc;
+    if (ld < cols) return fail(MTQ_ERR_INVALID, "ld < cols");
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(MTQ_ERR_INVALID, "out must be 16-byte aligned");
+    if (out_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "out_bytes is smaller than the stream");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(th * tw));
+    if (in_dtype == MTQ_DTYPE_F32)
+        hipLaunchKernelGGL(pack_tiles_transposed_kernel<float>, grid, dim3(256), 0, st, static_cast<const float *>(w), rows, cols, ld, map, offsets,
+                           th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    else
+        hipLaunchKernelGGL(pack_tiles_transposed_kernel<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(w), rows, cols, ld, map,
+                           offsets, th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    return check_launch("mtq_pack_tiles_transposed");
+}
+
+extern "C" int mtq_unpack_tiles_transposed(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows,
+                                           int64_t cols, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    if (!packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;                                   // of the transpose
+    if (int rc = tile_grid(cols, rows, &th, &tw)) return rc;
+    if (ldy < cols) return fail(MTQ_ERR_INVALID, "ldy < cols");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(th * tw));
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(unpack_tiles_transposed_kernel<true>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy);
+    else
+        hipLaunchKernelGGL(unpack_tiles_transposed_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy);
+    return check_launch("mtq_unpack_tiles_transposed");
+}
+
 // What the batched entries share: the tile grid of one matrix and the batch's tile total
 static int batch_grid(int64_t count, int64_t rows, int64_t cols, int64_t *tiles_h, int64_t *tiles_w)
 {
@@ -2003,6 +2247,29 @@ extern "C" int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ld
         hipLaunchKernelGGL(packed_linear_kernel<false>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th,
                            tw, bias, y, ldy);
     return check_launch("mtq_packed_linear");
+}
+
+// The product with a packed k × n matrix: the block entry's checks (the tile count of k × n is that of n × k), the grid the other way round.
+extern "C" int mtq_packed_matmul(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                                 const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    int64_t tn, tk;
+    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, &tn, &tk)) return rc;
+    const int64_t blocks = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
+    if (int rc = require_device()) return rc;
+    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    const dim3 grid((unsigned)blocks);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(packed_matmul_kernel<true>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, tk,
+                           tn, bias, y, ldy);
+    else
+        hipLaunchKernelGGL(packed_matmul_kernel<false>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, tk,
+                           tn, bias, y, ldy);
+    return check_launch("mtq_packed_matmul");
 }
 
 template <bool XV>

@@ -131,6 +131,9 @@ SIGNATURES = {
     "mtq_packed_glu_wide": ("i", "plllpzpppzpplppipilp", True),
     "mtq_packed_glu_wide_grouped_workspace_bytes": ("z", "llll", True),
     "mtq_packed_glu_wide_grouped": ("i", "plllppzppppzpppllpplipilpzp", True),
+    "mtq_pack_tiles_transposed": ("i", "pilllpppzp", True),
+    "mtq_unpack_tiles_transposed": ("i", "pzppllpilp", True),
+    "mtq_packed_matmul": ("i", "plllpzpplppilp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1126,6 +1129,78 @@ def packed_linear_wide(x, data, tables: PackedTables, n: int, bias=None, out_dty
 def has_packed_linear_wide() -> bool:
     """Whether this build of the library has mtq_packed_linear_wide (an optional symbol: an older build of the same version lacks it)."""
     return getattr(lib(), "mtq_packed_linear_wide", None) is not None
+
+
+PACKED_MATMUL = ("mtq_pack_tiles_transposed", "mtq_unpack_tiles_transposed", "mtq_packed_matmul")
+
+
+def has_packed_matmul() -> bool:
+    """Whether this build of the library has the transposed pack / unpack entries and mtq_packed_matmul (optional symbols: an older build
+    of the same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in PACKED_MATMUL)
+
+
+def pack_tiles_transposed(w2d, tables: PackedTables, out=None, stream="current"):
+    """mtq_pack_tiles_transposed on the current stream: a (rows, cols) bf16 / float32 device tensor with contiguous rows, read in place →
+    the packed stream of its (cols, rows) transpose, a uint8 device tensor of tables.nbytes bytes.  tables: over the transpose's grid."""
+    torch = _torch()
+    code, _count, _stride, rows, cols, ld = _matrix(w2d, (2,))
+    if tiles_hw(cols, rows) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, the transposed tensor has {'x'.join(map(str, tiles_hw(cols, rows)))}")
+    fn = _entry("mtq_pack_tiles_transposed")
+    if out is None:
+        require_gpu()
+        out = torch.empty((tables.nbytes,), dtype=torch.uint8, device=w2d.device)
+    ptr = _packed_stream(out, tables, "out")
+    check(fn(w2d.data_ptr(), code, rows, cols, ld, tables.map_ptr, tables.offsets_ptr, ptr, tables.nbytes, _packed_stream_ptr(stream)))
+    return out
+
+
+def unpack_tiles_transposed(data, tables: PackedTables, rows: int, cols: int, dtype=None, out=None, stream="current"):
+    """mtq_unpack_tiles_transposed on the current stream: the stream of a (cols, rows) matrix → its (rows, cols) transpose as a device
+    tensor, float32 (the bits K3T writes) or bfloat16 (exact).  What lies outside rows × cols of a pitched `out` stays."""
+    torch = _torch()
+    dtype = dtype or torch.float32
+    code = _packed_out_code(dtype)
+    rows, cols = int(rows), int(cols)
+    if tiles_hw(cols, rows) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a transposed {rows}x{cols} tensor has {'x'.join(map(str, tiles_hw(cols, rows)))}")
+    ptr = _packed_stream(data, tables)
+    fn = _entry("mtq_unpack_tiles_transposed")
+    if out is None:
+        require_gpu()
+        out = torch.empty((rows, cols), dtype=dtype, device=data.device)
+    elif out.dtype != dtype or out.dim() != 2 or tuple(out.shape) != (rows, cols) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {dtype} ({rows}, {cols}) device tensor with contiguous rows")
+    ldy = out.stride(0) if rows > 1 else max(out.stride(0), cols)
+    check(fn(ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, rows, cols, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_matmul(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, stream="current"):
+    """mtq_packed_matmul on the current stream: Y = X·P̂ + b for an (m, k) bf16 device tensor X with contiguous rows and the packed
+    (k, n) matrix → (m, n) float32 or bfloat16 device tensor.  m = 0 gives the empty (0, n) tensor without a launch."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code = _packed_out_code(out_dtype)
+    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if tiles_hw(k, n) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {k}x{n} matrix has {'x'.join(map(str, tiles_hw(k, n)))}")
+    ptr = _packed_stream(data, tables)
+    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
+    fn = _entry("mtq_packed_matmul")
+    if out is None:
+        require_gpu()
+        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
+    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
+    if m == 0:                                       # the entry refuses empty operands, as the block entry does: they end here
+        return out
+    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
+    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
 
 
 PACKED_SKINNY_MAX_M = 32   # include/mtq.h MTQ_PACKED_SKINNY_MAX_M

@@ -10,16 +10,26 @@ linear_batch / PackedExperts multiply with every tensor of such an arena (the ex
 launch; linear_grouped_wide is that product for experts with hundreds of rows (prefill), from the wide-block kernel; as_batch makes the
 arena of any list of equal-shaped packed tensors.  glu / glu_grouped are the first half of a gated MLP, act(gate(x)) * up(x), with the
 two projections fused in one launch of the wide-block kernel (or, bit for bit the same, unfused); PackedMLP and PackedExpertsMLP are
-down(act(gate(x)) * up(x)) as modules, dense and over an arena of experts.  Not built: a fused kernel for the decode range (the skinny
-family's split over K has partial sums), the transposed layout, activations other than ACTS.
+down(act(gate(x)) * up(x)) as modules, dense and over an arena of experts.
+
+pack_transposed / unpack_transposed / matmul / PackedMatmul close the gap to the transposed layout and to input-major weights without a
+new byte format: a transposed-layout map of W (n, k) is a row-layout map of Wᵀ (k, n), so the packed transposed weight IS the ordinary
+packed tensor of Wᵀ (shape (k, n), layout "rows"); pack_transposed reads W in place, unpack_transposed writes W's orientation, and
+matmul is Y = X·P̂ + b for a packed (k, n) matrix (mtq_packed_matmul: the block kernel's frame over a [k][n] LDS image read with the
+transposed LDS read).  A weight stored input-major (y = x @ W) packs with pack() and multiplies with matmul.
+
+Not built: a fused kernel for the decode range (the skinny family's split over K has partial sums); skinny, wide, grouped and GLU
+variants of the (k, n) product; pack_batch and scripts/pack_model.py for transposed configs; pack_transposed of tensors of rank other
+than 2; activations other than ACTS.
 
 Two backends:
   "hip"        the C ABI (csrc/mtq_packed.hip) through hip_backend's wrappers; data lives on the device.
   "emulation"  a NumPy encoder and decoder written from the format's description: the byte-level oracle of the GPU tests, and the way
                the feature works without a GPU.
 
-A map over the transposed layout (params["layout"] = "transpose") is refused: a group there runs down a column, and the packed format
-holds row groups only.
+A map over the transposed layout (params["layout"] = "transpose") is refused by every row-layout entry (pack(layout=...), pack_batch,
+as_batch, linear, glu, ...): a group there runs down a column, and the packed format holds row groups only.  pack_transposed is the
+entry for such a map.
 """
 from __future__ import annotations
 
@@ -395,6 +405,109 @@ def linear_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", back
         raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
     dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
     return hb.packed_linear_wide(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
+
+
+# ----------------------------------------------------------------------------- the transposed layout and (k, n) weights
+
+def _need_matmul(hb, what: str) -> None:
+    if not hb.has_packed_matmul():
+        raise MtqError(f"{what} needs mtq_pack_tiles_transposed, mtq_unpack_tiles_transposed and mtq_packed_matmul, which this build of "
+                       "libmtq_hip.so lacks: rebuild it from this tree")
+
+
+def _check_kn(pt: PackedTensor, what: str) -> None:
+    _check_layout(pt.layout)
+    if len(pt.shape) != 2:
+        raise MtqError(f"{what} needs a 2-D packed (k, n) matrix, the packed tensor is {pt.shape}")
+
+
+def pack_transposed(w, amap, backend: str = "emulation") -> PackedTensor:
+    """The packed TRANSPOSE of the 2-D weight w (n, k) under a map over Wᵀ's tile grid ceil(k/32) × ceil(n/32) - what a mixed-tile
+    search with params["layout"] = "transpose" (or layer_output_error.py's budget_<B>_<basis>_transpose.npy) writes for W.  The result
+    is an ordinary PackedTensor of shape (k, n) in the row layout: save / load, unpack (which gives Wᵀ) and matmul take it as it is.
+    hip: w is read in place through mtq_pack_tiles_transposed (no transposed copy).  emulation: pack(np.ascontiguousarray(w.T), amap)."""
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    if len(tuple(w.shape)) != 2 or 0 in tuple(w.shape):
+        raise MtqError(f"pack_transposed takes a non-empty 2-D (n, k) weight, got {tuple(w.shape)}")
+    n, k = (int(v) for v in w.shape)
+    a = _check_map(amap, k, n)
+    if np.ndim(amap) == 2 and tuple(np.shape(amap)) != a.shape:
+        raise MtqError(f"the map is {'x'.join(map(str, np.shape(amap)))} tiles, the transposed weight has {a.shape[0]}x{a.shape[1]}: "
+                       "pack_transposed takes a map over the transpose's grid")
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        _need_matmul(hb, "pack_transposed")
+        hb.require_gpu()
+        if _is_torch(w) and w.is_cuda and w.dtype in (torch.bfloat16, torch.float32) and w.stride(-1) == 1:
+            w2d = w                                  # a device view with contiguous rows is read in place, whatever its pitch
+        else:
+            w2d, _info = hb.to_device_2d(w)
+        tables = hb.PackedTables.on_device(a, device=w2d.device)
+        data = hb.pack_tiles_transposed(w2d, tables)
+        return PackedTensor((k, n), ("nd", (k, n)), k, n, a, offsets_of(a), data, _tables=tables)
+    wf = w.detach().to("cpu").float().numpy() if _is_torch(w) else np.asarray(w, dtype=np.float32)
+    return pack(np.ascontiguousarray(wf.T), a)
+
+
+def unpack_transposed(pt: PackedTensor, backend: str = "emulation", dtype: str = "float32"):
+    """The (n, k) weight whose packed transpose `pt` (shape (k, n)) is: unpack(pt) transposed, written in W's orientation.  float32: bit
+    for bit what K3T (mtq_apply_assignment_transposed) and scripts/reconstruct_mixed_tile_assignment.py --layout transpose give for W
+    and the map; bfloat16: the same values, exact.  hip: mtq_unpack_tiles_transposed, a device tensor."""
+    _check_kn(pt, "unpack_transposed")
+    if dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"dtype must be 'float32' or 'bfloat16', got {dtype!r}")
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        _need_matmul(hb, "unpack_transposed")
+        hb.require_gpu()
+        return hb.unpack_tiles_transposed(_device_data(pt), pt.tables(), pt.cols, pt.rows, torch.float32 if dtype == "float32" else torch.bfloat16)
+    if backend != "emulation":
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    y = unpack(pt, backend="emulation", dtype=dtype)
+    return y.t().contiguous() if _is_torch(y) else np.ascontiguousarray(y.T)
+
+
+def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
+    """Y = X·P̂ + b with the packed (k, n) matrix `pt`: (m, k) · (k, n) → (m, n).  For weights stored input-major (y = x @ W) and for
+    pack_transposed's result, where it is the linear layer of the (n, k) weight in the transposed layout.  hip (the default when the
+    stream is on the device): X an (m, k) bf16 device tensor, bias float32 [n], through mtq_packed_matmul; bit for bit
+    linear(kernel="block") on the all-bf16 packing of unpack(pt)ᵀ.  A library without the symbol raises MtqError: no other kernel stands
+    in.  emulation: the float64 product of the unpacked matrix, rounded once to float32 (or from there to bf16), as linear's."""
+    _check_kn(pt, "matmul")
+    backend = backend or ("hip" if pt.on_device else "emulation")
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    k, n = pt.rows, pt.cols
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        if x.dim() != 2 or x.shape[1] != k:
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        _need_matmul(hb, "matmul")
+        return hb.packed_matmul(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=torch.float32 if out_dtype == "float32" else torch.bfloat16)
+    if backend != "emulation":
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    import torch
+
+    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
+    if xf.ndim != 2 or xf.shape[1] != k:
+        raise MtqError(f"x must be (m, {k}), got {xf.shape}")
+    w = decode(_host_data(pt), pt.map, pt.offsets, k, n).view(np.float32)
+    y = xf.astype(np.float64) @ w.astype(np.float64)
+    if bias is not None:
+        y = y + (bias.detach().to("cpu").double().numpy() if _is_torch(bias) else np.asarray(bias, dtype=np.float64))[None, :]
+    with np.errstate(over="ignore"):
+        y32 = y.astype(np.float32)
+    return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
 
 
 # ----------------------------------------------------------------------------- batches
@@ -1194,6 +1307,58 @@ def _packed_linear_class():
     return PackedLinear
 
 
+def _packed_matmul_class():
+    import torch
+
+    class PackedMatmul(torch.nn.Module):
+        """x @ P̂ + b over a packed (k, n) matrix (pack of an input-major weight, or pack_transposed of an (n, k) one).  INFERENCE ONLY,
+        as PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through matmul() and returns
+        (..., n) in out_dtype.  hip: the tables and the bias stay on the device across calls; a library without mtq_packed_matmul is
+        refused here, not at the first forward.  emulation: CPU tensors, the float64 product."""
+
+        def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
+            super().__init__()
+            _check_kn(pt, "PackedMatmul")
+            if out_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            self.backend = backend or ("hip" if pt.on_device else "emulation")
+            if self.backend not in BACKENDS:
+                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            self.packed, self.out_dtype = pt, out_dtype
+            self.in_features, self.out_features = pt.rows, pt.cols
+            if bias is not None and not _is_torch(bias):
+                bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
+            if self.backend == "hip":
+                from . import hip_backend as hb
+
+                _need_matmul(hb, "PackedMatmul")
+                data = _device_data(pt)
+                pt.tables()
+                if bias is not None:
+                    bias = bias.detach().to(device=data.device, dtype=torch.float32).contiguous()
+            self.register_buffer("bias", None if bias is None else bias.detach(), persistent=False)
+
+        def extra_repr(self) -> str:
+            return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, " \
+                   f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}"
+
+        @torch.no_grad()
+        def forward(self, x):
+            if x.shape[-1] != self.in_features:
+                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
+            lead = tuple(x.shape[:-1])
+            x2 = x.reshape(-1, self.in_features)
+            dtype = torch.float32 if self.out_dtype == "float32" else torch.bfloat16
+            if x2.shape[0] == 0:
+                return torch.zeros(lead + (self.out_features,), dtype=dtype, device=x.device)
+            y = matmul(x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend)
+            if not _is_torch(y):
+                y = torch.from_numpy(y)
+            return y.reshape(lead + (self.out_features,))
+
+    return PackedMatmul
+
+
 def _packed_experts_class():
     import torch
 
@@ -1278,10 +1443,10 @@ def _packed_experts_class():
 
 
 def __getattr__(name):
-    """PackedLinear, PackedExperts, PackedMLP and PackedExpertsMLP are torch.nn.Modules: a class is made on first use, so that importing
-    this module does not import torch."""
-    makers = {"PackedLinear": _packed_linear_class, "PackedExperts": _packed_experts_class, "PackedMLP": _packed_mlp_class,
-              "PackedExpertsMLP": _packed_experts_mlp_class}
+    """PackedLinear, PackedMatmul, PackedExperts, PackedMLP and PackedExpertsMLP are torch.nn.Modules: a class is made on first use, so
+    that importing this module does not import torch."""
+    makers = {"PackedLinear": _packed_linear_class, "PackedMatmul": _packed_matmul_class, "PackedExperts": _packed_experts_class,
+              "PackedMLP": _packed_mlp_class, "PackedExpertsMLP": _packed_experts_mlp_class}
     if name in makers:
         cls = makers[name]()
         globals()[name] = cls
