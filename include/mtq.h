@@ -752,6 +752,31 @@ size_t mtq_packed_linear_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k,
 int mtq_packed_linear_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                              const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
                              void *workspace, size_t workspace_bytes, void *stream);
+/* The skinny product with a packed k × n matrix P̂, Y = X·P̂ + b for 1 <= m <= MTQ_PACKED_SKINNY_MAX_M: mtq_packed_matmul's operands (x
+ * m × k bf16, map grid ceil(k/32) × ceil(n/32), bias n float32 or NULL, y m × n) with mtq_packed_linear_skinny's parameter list, split
+ * and workspace, one for one.  One wave takes one tile column of P̂ (32 outputs) over one K slice of whole tile rows; the map codes and
+ * offsets of up to 64 tiles of the run come with one strided load, the loads of W and X run several tiles ahead.  A group's 16 values
+ * run along n at one k here, so a lane stores its decoded group as it lies into a wave-private [32 k][32 n] LDS image and the two B
+ * operands of the tile are read from it with the transposed LDS read of gfx950, two reads per operand; two images per wave, no
+ * workgroup barrier.  Split, partials, reduce, bias and rounding are the skinny linear's with tiles_h = ceil(n/32), tiles_w = ceil(k/32):
+ * a split above ceil(k/32) acts as ceil(k/32), split 0 is the same pure function of (m, n, k), an effective split of 1 writes y directly.
+ *
+ * Bit contract: for every input, y equals bit for bit what mtq_packed_linear_skinny gives, at the same split (split 0 included), for
+ * the same x and bias with the all-bf16 row-layout packing of unpack(P̂)ᵀ (n × k; lossless, every decoded value is a bf16), in both
+ * output types, with or without bias.  It holds by construction: the same k at the same lane half and element of each MFMA, the same
+ * tile order, the same slices (the linear kernel's tile columns are this kernel's tile rows), the same split rule and the same reduce.
+ * No atomics, no counters: the same inputs and the same split give the same bits.
+ *
+ * Argument checks and refusals are the skinny linear entry's (m > MTQ_PACKED_SKINNY_MAX_M, a negative split, a workspace that is null,
+ * not 16-byte aligned or short) with mtq_packed_matmul's grid check for a k × n tensor, all before a device is looked for.  Device
+ * guards: a tile whose blob passes packed_bytes or whose map code is outside 0..3 multiplies as zeros in its own tile only, k-rows of P̂
+ * at or past k count as zeros whatever their bytes hold, rows at or past m and columns at or past k of x are never read, nothing outside
+ * m x n of y is written.  The size function equals the skinny linear's for the same (m, n, k, split): n outputs, k contraction.
+ * Both symbols are optional: a build of this version may lack them. */
+size_t mtq_packed_matmul_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split);
+int mtq_packed_matmul_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                             const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
+                             void *workspace, size_t workspace_bytes, void *stream);
 /* The grouped form: `count` experts of one (n, k) shape in ONE arena (the batch entries' maps / offsets / bases), each multiplied with
  * its own rows of x, in one launch: y[rows of group e] = x[rows of group e] · Ŵ[e]ᵀ (+ bias[e]).
  *

@@ -37,6 +37,8 @@
 //       map over the transposed layout of W is a row-layout map of Wᵀ, so this is the same format (no new bytes, no new layout value).
 //   packed_matmul_kernel                      Y = X·P̂ + b for a packed k × n matrix: the block kernel's frame over a [k][n] LDS image
 //       that is read with the transposed LDS read (ds_read_b64_tr_b16); bit for bit the block kernel on the transposed weight.
+//   packed_matmul_skinny_kernel               that product for m <= 32: one wave per (K slice, tile column), each tile through a
+//       wave-private [32 k][32 n] LDS image and the transposed read; bit for bit the skinny linear kernel on the transposed weight.
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
 // blob does not fit is not written (pack), not stored (unpack) or read as zeros (linear).
@@ -940,6 +942,134 @@ int skinny_shape(int64_t m, int64_t n, int64_t k, int split, int64_t *tiles_h, i
 size_t skinny_workspace(int64_t m, int64_t n, int split_eff)
 {
     return split_eff <= 1 ? 0 : (((size_t)split_eff * (size_t)m * (size_t)n * sizeof(float) + 15) & ~(size_t)15);
+}
+
+// ---- skinny matmul (m <= 32): Y = X·P̂ + b for a packed k × n P̂, one wave per (K slice s, tile column tc) unit.
+//
+// packed_linear_skinny_kernel with the weight the other way round: the wave covers 32 output columns over the tile rows
+// [s tiles_kh / split, (s + 1) tiles_kh / split) of P̂'s grid tiles_kh × tiles_nw, unit = s tiles_nw + tc, so the four waves of a workgroup
+// read four neighbouring blobs of each tile row and share a slice of X.  The hand-out, the ring, the blob check and the decode are the
+// linear kernel's; the tiles of a run are tiles_nw apart, so the one load of up to 64 map codes and offsets is a strided gather.
+//
+// A group's 16 values run along n at one k-row, an MFMA operand wants 8 consecutive k at one n: lane l decodes group l of the tile
+// (k-row l >> 1, columns 16 (l & 1) ..) and stores its 16 bf16 as they lie at bytes 32 l .. 32 l + 31 of a wave-private [32 k][32 n] image
+// with 64-byte rows, in two 16-byte pieces; the two B operands of the tile come out of the image through the transposed LDS read, two
+// reads per operand: lane 16 g + 4 q + p supplies row r0 + q, columns 16 (g & 1) + 4 p .., and gets column lane & 31, rows r0 .. r0 + 3.
+// MFMA 1 takes k-rows 16 (lane >> 5) + 0..7 of the tile and MFMA 2 rows 16 (lane >> 5) + 8..15, element j at position j, X as in the
+// linear kernel (row lane & 31, positions 32 tile_row + 16 (lane >> 5) + 0..15): the linear kernel's operands on the transposed weight,
+// in its tile order, over its slices, so its bits at the same split.
+//
+// Banks: a 32-lane half of a transposed read takes 4 k-rows × 64 bytes, 256 consecutive bytes, every one of the 64 banks once.  The
+// 16-byte stores go by 8-lane groups over 32 banks; bytes 32 l of eight lanes would put lanes i and i + 4 on the same banks, so lanes
+// with (l >> 2) & 1 set store their upper piece first: an 8-lane group then covers 32 distinct banks with each of its two stores.
+//
+// The transposed read needs EXEC all ones: the only early exit is the wave-uniform return below (the wave index is made scalar, so every
+// branch on the run's length is a scalar branch), and the reads sit in no lane-dependent branch.  Tiles with a bad code or a blob past
+// packed_bytes and k-rows at or past K are zeros in the image (pad, don't mask); columns at or past N are never stored.
+//
+// The image is one wave's: no __syncthreads.  Stores and reads are by different lanes, so a workgroup-scope fence (an s_waitcnt on the
+// LDS counter) and a wave barrier stand between a tile's stores and its reads, and a fence and a wave barrier after the reads keep the
+// next stores into that image behind them.  Two images per wave (4 KB; 16 KB a workgroup) alternate by tile.
+constexpr int kMmsImage = kTile * kMmPitch;          // bf16 per image: [32 k][32 n]
+
+template <bool BF16OUT>
+__global__ __launch_bounds__(64 * kSkinnyWaves) void packed_matmul_skinny_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx,
+                                                                                  int x_vec, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+                                                                                  const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets,
+                                                                                  int64_t N, int64_t tiles_kh, int64_t tiles_nw, int split,
+                                                                                  const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy,
+                                                                                  float *__restrict__ ws)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[kSkinnyWaves * 2 * kMmsImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= tiles_nw * split) return;            // wave-uniform; the kernel has no workgroup barrier
+    const int64_t s = unit / tiles_nw, tc = unit % tiles_nw;   // the waves of a workgroup share a slice of X
+    const int64_t r0 = s * tiles_kh / split, r1 = (s + 1) * tiles_kh / split;
+    const int row = lane & 31, half = lane >> 5;
+
+    uint16_t *img = lds + wave * (2 * kMmsImage);
+    const int up = (lane >> 2) & 1;                  // this lane stores its upper 16 bytes first
+    uint16_t *st = img + lane * kGroup;
+    const uint16_t *rd = img + (kGroup * half + ((lane >> 2) & 3)) * kMmPitch + kGroup * ((lane >> 4) & 1) + 4 * (lane & 3);
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+
+    for (int64_t rb = r0; rb < r1; rb += 64) {
+        const int cnt = (int)std::min<int64_t>(64, r1 - rb);
+        int mf = -1, mo = 0;                         // lane i: map code and offset of tile (rb + i, tc)
+        if (lane < cnt) {
+            const int64_t t = (rb + lane) * tiles_nw + tc;
+            mf = map[t];
+            mo = (int)offsets[t];
+        }
+        for (int b = 0; b < cnt; b += kSkinnyRing) {
+            GroupRaw g[kSkinnyRing];
+            uint4 xl[kSkinnyRing], xh[kSkinnyRing];
+#pragma unroll
+            for (int j = 0; j < kSkinnyRing; ++j) {
+                const int i = b + j;                 // uniform
+                TileAt a;
+                a.off = 0;
+                a.f = -1;
+                xl[j] = make_uint4(0u, 0u, 0u, 0u);
+                xh[j] = xl[j];
+                if (i < cnt) {
+                    const int f = __builtin_amdgcn_readlane(mf, i);
+                    a.off = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(mo, i) * kUnit;
+                    const uint32_t size = packed_tile_bytes(f);
+                    const bool absent = size == 0u || a.off + size > packed_bytes || (rb + i) * kTile + (lane >> 1) >= K;   // the last: this lane's k-row
+                    a.f = absent ? -1 : f;
+                    load_x16(x, M, K, ldx, x_vec, row, (rb + i) * kTile + kGroup * half, xl[j], xh[j]);
+                }
+                load_group(packed, a, lane, g[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < kSkinnyRing; ++j) {
+                if (b + j < cnt) {
+                    uint32_t y[kGroup];
+                    decode_skinny(g[j], y);
+                    uint4 lo, hi;
+                    pack_halves(y, lo, hi);
+                    uint16_t *dst = st + (j & 1) * kMmsImage;
+                    *reinterpret_cast<uint4 *>(dst + 8 * up) = make_uint4(up ? hi.x : lo.x, up ? hi.y : lo.y, up ? hi.z : lo.z, up ? hi.w : lo.w);
+                    *reinterpret_cast<uint4 *>(dst + 8 * (up ^ 1)) = make_uint4(up ? lo.x : hi.x, up ? lo.y : hi.y, up ? lo.z : hi.z, up ? lo.w : hi.w);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    const uint16_t *src = rd + (j & 1) * kMmsImage;
+                    const i16x4 b0 = lds_read_tr16(src), b1 = lds_read_tr16(src + 4 * kMmPitch);         // k + 0..3, k + 4..7
+                    const i16x4 b2 = lds_read_tr16(src + 8 * kMmPitch), b3 = lds_read_tr16(src + 12 * kMmPitch);
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    const i16x8 blo = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+                    const i16x8 bhi = __builtin_shufflevector(b2, b3, 0, 1, 2, 3, 4, 5, 6, 7);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), __builtin_bit_cast(bf16x8, blo), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), __builtin_bit_cast(bf16x8, bhi), acc, 0, 0, 0);
+                }
+            }
+        }
+    }
+
+    // lane's outputs are (m = (r&3) + 8(r>>2) + 4·half, n = 32·tc + row)
+    const int64_t n = tc * kTile + row;
+    if (n >= N) return;
+    if (split == 1) {
+        const float bv = bias ? bias[n] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t m = (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[r] + bv);
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t m = (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (m < M) ws[(s * M + m) * N + n] = acc[r];
+        }
+    }
 }
 
 // ---- grouped skinny linear: the experts of one arena (pack_tiles_batched's tables), each over its own rows of X, in one launch.
@@ -2355,6 +2485,62 @@ extern "C" int mtq_packed_linear_skinny(const void *x, int64_t m, int64_t k, int
             hipLaunchKernelGGL(skinny_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
     }
     return check_launch("mtq_packed_linear_skinny");
+}
+
+// The skinny product with a packed k × n matrix: the skinny entry's checks and split rule (tile_grid of n × k is the grid check of k × n),
+// the grid the other way round.
+extern "C" size_t mtq_packed_matmul_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
+{
+    int64_t tn, tk;
+    int eff;
+    if (skinny_shape(m, n, k, split, &tn, &tk, &eff)) return (size_t)-1;
+    return skinny_workspace(m, n, eff);
+}
+
+extern "C" int mtq_packed_matmul_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                                        const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
+                                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!x || !packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t tn, tk;
+    int eff;
+    if (int rc = skinny_shape(m, n, k, split, &tn, &tk, &eff)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(tn * tk) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
+    const size_t need = skinny_workspace(m, n, eff);
+    if (need != 0) {
+        if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and this split needs one");
+        if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
+        if (workspace_bytes < need)
+            return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this split needs", workspace_bytes, need);
+    }
+    const int64_t blocks = (tn * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    float *ws = static_cast<float *>(workspace);
+    const dim3 grid((unsigned)blocks), block(64 * kSkinnyWaves);
+    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(packed_matmul_skinny_kernel<true>, grid, block, 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, tk, tn,
+                           eff, bias, y, ldy, ws);
+    else
+        hipLaunchKernelGGL(packed_matmul_skinny_kernel<false>, grid, block, 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, tk, tn,
+                           eff, bias, y, ldy, ws);
+    if (eff > 1) {
+        if (int rc = check_launch("mtq_packed_matmul_skinny")) return rc;
+        const dim3 rgrid((unsigned)((m * n + 255) / 256));
+        if (out_dtype == MTQ_DTYPE_BF16)
+            hipLaunchKernelGGL(skinny_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
+        else
+            hipLaunchKernelGGL(skinny_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
+    }
+    return check_launch("mtq_packed_matmul_skinny");
 }
 
 extern "C" size_t mtq_packed_linear_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)

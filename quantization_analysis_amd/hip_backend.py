@@ -134,6 +134,8 @@ SIGNATURES = {
     "mtq_pack_tiles_transposed": ("i", "pilllpppzp", True),
     "mtq_unpack_tiles_transposed": ("i", "pzppllpilp", True),
     "mtq_packed_matmul": ("i", "plllpzpplppilp", True),
+    "mtq_packed_matmul_skinny_workspace_bytes": ("z", "llli", True),
+    "mtq_packed_matmul_skinny": ("i", "plllpzpplppilipzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1239,6 +1241,66 @@ def packed_linear_skinny(x, data, tables: PackedTables, n: int, bias=None, out_d
         out = torch.empty((m, n), dtype=out_dtype, device=x.device)
     elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
         raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
+    ws_ptr, ws_bytes = None, 0
+    if need:
+        if workspace is None:
+            require_gpu()
+            workspace = torch.empty((need,), dtype=torch.uint8, device=x.device)
+        ws_ptr, ws_bytes = _buffer(workspace, torch.uint8, need, "workspace"), int(workspace.numel())
+        if workspace.data_ptr() % 16:
+            raise MtqError("workspace must be 16-byte aligned")
+    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
+    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, int(split),
+             ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
+    return out
+
+
+PACKED_MATMUL_SKINNY = ("mtq_packed_matmul_skinny_workspace_bytes", "mtq_packed_matmul_skinny")
+
+
+def has_packed_matmul_skinny() -> bool:
+    """Whether this build of the library has mtq_packed_matmul_skinny and its size function (optional symbols: an older build of the
+    same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in PACKED_MATMUL_SKINNY)
+
+
+def packed_matmul_skinny_workspace_bytes(m: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_matmul_skinny_workspace_bytes (a host function: no GPU): the bytes of workspace the skinny (k, n) product needs for
+    (m, n, k, split) - n outputs, k contraction; split 0 is the library's choice; 0 when the effective split is 1.  Equal to
+    packed_linear_skinny_workspace_bytes for the same arguments."""
+    size = int(_entry("mtq_packed_matmul_skinny_workspace_bytes")(int(m), int(n), int(k), int(split)))
+    if size == ctypes.c_size_t(-1).value:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return size
+
+
+def packed_matmul_skinny(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, split: int = 0, workspace=None,
+                         stream="current"):
+    """mtq_packed_matmul_skinny on the current stream: packed_matmul for m <= 32 with a split over K (split 0: the library's choice).
+    workspace: a uint8 device tensor of at least packed_matmul_skinny_workspace_bytes(m, n, k, split) bytes, 16-byte aligned; allocated
+    here when none is given.  Bit for bit packed_linear_skinny at the same split on the all-bf16 packing of the unpacked matrix's
+    transpose.  m = 0 gives the empty (0, n) tensor without a launch."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code = _packed_out_code(out_dtype)
+    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if m > PACKED_SKINNY_MAX_M:
+        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
+    if tiles_hw(k, n) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {k}x{n} matrix has {'x'.join(map(str, tiles_hw(k, n)))}")
+    ptr = _packed_stream(data, tables)
+    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
+    fn = _entry("mtq_packed_matmul_skinny")
+    if out is None:
+        require_gpu()
+        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
+    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
+    if m == 0:                                       # the entry refuses empty operands, as the block entry does: they end here
+        return out
+    need = packed_matmul_skinny_workspace_bytes(m, n, k, split)
     ws_ptr, ws_bytes = None, 0
     if need:
         if workspace is None:

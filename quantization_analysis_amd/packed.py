@@ -16,11 +16,13 @@ pack_transposed / unpack_transposed / matmul / PackedMatmul close the gap to the
 new byte format: a transposed-layout map of W (n, k) is a row-layout map of Wᵀ (k, n), so the packed transposed weight IS the ordinary
 packed tensor of Wᵀ (shape (k, n), layout "rows"); pack_transposed reads W in place, unpack_transposed writes W's orientation, and
 matmul is Y = X·P̂ + b for a packed (k, n) matrix (mtq_packed_matmul: the block kernel's frame over a [k][n] LDS image read with the
-transposed LDS read).  A weight stored input-major (y = x @ W) packs with pack() and multiplies with matmul.
+transposed LDS read).  A weight stored input-major (y = x @ W) packs with pack() and multiplies with matmul.  matmul(kernel="skinny")
+is that product for decode, m <= 32 (mtq_packed_matmul_skinny: the skinny linear kernel's split over K with each tile passed through
+a wave-private [k][n] LDS image), and PackedMatmul(kernel="skinny" | "auto") keeps its workspace across calls.
 
-Not built: a fused kernel for the decode range (the skinny family's split over K has partial sums); skinny, wide, grouped and GLU
-variants of the (k, n) product; pack_batch and scripts/pack_model.py for transposed configs; pack_transposed of tensors of rank other
-than 2; activations other than ACTS.
+Not built: a fused kernel for the decode range (the skinny family's split over K has partial sums); wide, grouped and GLU variants of
+the (k, n) product; pack_batch and scripts/pack_model.py for transposed configs; pack_transposed of tensors of rank other than 2;
+activations other than ACTS.
 
 Two backends:
   "hip"        the C ABI (csrc/mtq_packed.hip) through hip_backend's wrappers; data lives on the device.
@@ -55,7 +57,12 @@ AUTO_SKINNY_MAX_M = 32
 # from which on the wide kernel's median is below the block kernel's minimum of the same run at every shape and map (DESIGN.md §A.6k,
 # profiles/packed_linear_wide.txt).  Both kernels give the same bits, so the gate changes no result.
 AUTO_WIDE_MIN_M = 64
-ACTS = ("silu", "none")     # include/mtq.h MTQ_ACT_SILU, MTQ_ACT_NONE
+MATMUL_KERNELS = ("block", "skinny", "auto")
+# matmul(kernel="auto") takes the skinny (k, n) kernel up to this m when the library has it and the block kernel above it; None: never,
+# "auto" is "block".  The largest measured m at which, at every shape and map, the skinny kernel's median is below mtq_packed_matmul's
+# minimum of the same run by more than that side's own minimum-to-median spread (profiles/packed_matmul_skinny.txt).
+AUTO_MATMUL_SKINNY_MAX_M = 32
+ACTS =("silu", "none")     # include/mtq.h MTQ_ACT_SILU, MTQ_ACT_NONE
 GLU_KERNELS = ("fused", "unfused", "auto")
 GLU_GROUPED_KERNELS = ("fused", "unfused")
 # glu(kernel="auto") above the skinny range takes the fused kernel (mtq_packed_glu_wide) from this m on; None: never, "auto" stays
@@ -474,13 +481,40 @@ def unpack_transposed(pt: PackedTensor, backend: str = "emulation", dtype: str =
     return y.t().contiguous() if _is_torch(y) else np.ascontiguousarray(y.T)
 
 
-def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
+def _need_matmul_skinny(hb, what: str) -> None:
+    if not hb.has_packed_matmul_skinny():
+        raise MtqError(f"{what} needs {' and '.join(hb.PACKED_MATMUL_SKINNY)}, which this build of libmtq_hip.so lacks: rebuild it from "
+                       "this tree")
+
+
+def _matmul_takes_skinny(hb, kernel: str, m: int) -> bool:
+    """Whether matmul's `kernel` means the skinny entry at this m: "skinny" always (a library without it raises, no other kernel stands
+    in), "auto" up to AUTO_MATMUL_SKINNY_MAX_M on a library that has it."""
+    if kernel == "skinny":
+        if m > SKINNY_MAX_M:
+            raise MtqError(f'kernel="skinny" takes m <= {SKINNY_MAX_M}, got m = {m}')
+        _need_matmul_skinny(hb, 'matmul(kernel="skinny")')
+        return True
+    return kernel == "auto" and AUTO_MATMUL_SKINNY_MAX_M is not None and m <= AUTO_MATMUL_SKINNY_MAX_M and hb.has_packed_matmul_skinny()
+
+
+def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block", split: int = 0,
+           workspace=None):
     """Y = X·P̂ + b with the packed (k, n) matrix `pt`: (m, k) · (k, n) → (m, n).  For weights stored input-major (y = x @ W) and for
     pack_transposed's result, where it is the linear layer of the (n, k) weight in the transposed layout.  hip (the default when the
     stream is on the device): X an (m, k) bf16 device tensor, bias float32 [n], through mtq_packed_matmul; bit for bit
     linear(kernel="block") on the all-bf16 packing of unpack(pt)ᵀ.  A library without the symbol raises MtqError: no other kernel stands
-    in.  emulation: the float64 product of the unpacked matrix, rounded once to float32 (or from there to bf16), as linear's."""
+    in.  emulation: the float64 product of the unpacked matrix, rounded once to float32 (or from there to bf16), as linear's.
+
+    kernel: one of MATMUL_KERNELS.  "block" (the default; any m); "skinny", the split-K kernel for decode (mtq_packed_matmul_skinny,
+    m <= 32; `split` slices of K, 0 = the library's choice, and an optional uint8 device `workspace` of
+    hip_backend.packed_matmul_skinny_workspace_bytes bytes): bit for bit linear(kernel="skinny") at the same split on the all-bf16
+    packing of unpack(pt)ᵀ, and MtqError naming the missing symbols on a library without them; "auto", the skinny kernel for
+    m <= AUTO_MATMUL_SKINNY_MAX_M when that is not None and the library has it, else block.  The two kernels sum in different orders:
+    each is bit-stable, they may differ in the last bits.  The emulation computes the same float64 product under all three names."""
     _check_kn(pt, "matmul")
+    if kernel not in MATMUL_KERNELS:
+        raise MtqError(f"kernel must be one of {MATMUL_KERNELS}, got {kernel!r}")
     backend = backend or ("hip" if pt.on_device else "emulation")
     if out_dtype not in ("float32", "bfloat16"):
         raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
@@ -493,7 +527,10 @@ def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
         if x.dim() != 2 or x.shape[1] != k:
             raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
         _need_matmul(hb, "matmul")
-        return hb.packed_matmul(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=torch.float32 if out_dtype == "float32" else torch.bfloat16)
+        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        if _matmul_takes_skinny(hb, kernel, int(x.shape[0])):
+            return hb.packed_matmul_skinny(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype, split=split, workspace=workspace)
+        return hb.packed_matmul(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
     if backend != "emulation":
         raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
     import torch
@@ -1314,32 +1351,43 @@ def _packed_matmul_class():
         """x @ P̂ + b over a packed (k, n) matrix (pack of an input-major weight, or pack_transposed of an (n, k) one).  INFERENCE ONLY,
         as PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through matmul() and returns
         (..., n) in out_dtype.  hip: the tables and the bias stay on the device across calls; a library without mtq_packed_matmul is
-        refused here, not at the first forward.  emulation: CPU tensors, the float64 product."""
+        refused here, not at the first forward.  emulation: CPU tensors, the float64 product.
+        kernel: matmul's, "block" by default.  With "skinny" or "auto" on hip one workspace, sized for m = 32 at the library's split,
+        stays on the device across calls (its contents never need initialising), so a decode step allocates only its output;
+        "skinny" on a library without mtq_packed_matmul_skinny is refused here."""
 
-        def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
+        def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block"):
             super().__init__()
             _check_kn(pt, "PackedMatmul")
+            if kernel not in MATMUL_KERNELS:
+                raise MtqError(f"kernel must be one of {MATMUL_KERNELS}, got {kernel!r}")
             if out_dtype not in ("float32", "bfloat16"):
                 raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
             self.backend = backend or ("hip" if pt.on_device else "emulation")
             if self.backend not in BACKENDS:
                 raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
-            self.packed, self.out_dtype = pt, out_dtype
+            self.packed, self.out_dtype, self.kernel = pt, out_dtype, kernel
             self.in_features, self.out_features = pt.rows, pt.cols
+            self._workspace = None
             if bias is not None and not _is_torch(bias):
                 bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
             if self.backend == "hip":
                 from . import hip_backend as hb
 
                 _need_matmul(hb, "PackedMatmul")
+                if kernel == "skinny":
+                    _need_matmul_skinny(hb, 'PackedMatmul(kernel="skinny")')
                 data = _device_data(pt)
                 pt.tables()
                 if bias is not None:
                     bias = bias.detach().to(device=data.device, dtype=torch.float32).contiguous()
+                if kernel != "block" and hb.has_packed_matmul_skinny():
+                    need = hb.packed_matmul_skinny_workspace_bytes(SKINNY_MAX_M, pt.cols, pt.rows)   # monotone in m: serves every m <= 32
+                    self._workspace = torch.empty((need,), dtype=torch.uint8, device=data.device) if need else None
             self.register_buffer("bias", None if bias is None else bias.detach(), persistent=False)
 
         def extra_repr(self) -> str:
-            return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, " \
+            return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, kernel={self.kernel!r}, " \
                    f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}"
 
         @torch.no_grad()
@@ -1351,7 +1399,8 @@ def _packed_matmul_class():
             dtype = torch.float32 if self.out_dtype == "float32" else torch.bfloat16
             if x2.shape[0] == 0:
                 return torch.zeros(lead + (self.out_features,), dtype=dtype, device=x.device)
-            y = matmul(x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend)
+            y = matmul(x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel,
+                       workspace=self._workspace)
             if not _is_torch(y):
                 y = torch.from_numpy(y)
             return y.reshape(lead + (self.out_features,))

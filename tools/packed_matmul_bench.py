@@ -11,7 +11,16 @@ directly, the weights rotated over --cold-mb of copies.
   pack    : mtq_pack_tiles_transposed / mtq_unpack_tiles_transposed on the stored n × k weight against mtq_pack_tiles /
             mtq_unpack_tiles on the same tensor under the transposed map; bytes moved over time.
 
+  --skinny: mtq_packed_matmul_skinny (the split-K kernel for m <= 32) at split 0, m in {1, 16, 32}, the same shapes and maps.  Four
+            sides: the new entry; mtq_packed_matmul (the route before it, the baseline of the gate); mtq_packed_linear_skinny on the
+            n × k stream of Pᵀ under the transposed map (the same tiles, the same bytes); torch.matmul on the unpacked bf16 P̂.  The
+            workspace is allocated once.  Before timing, the bit contract is checked: the new entry against mtq_packed_linear_skinny
+            on the all-bf16 packing of unpack(P̂)ᵀ at split 0.  `gate` is pass when the new kernel's median is below the block side's
+            minimum by more than the block side's own minimum-to-median spread; the last line names the largest m at which every
+            row passes (packed.AUTO_MATMUL_SKINNY_MAX_M).  --sweep-splits times explicit splits on the first shape and map.
+
   python tools/packed_matmul_bench.py [--rounds 5] [--window-ms 30] [--out profiles/packed_matmul.txt] [--json out.json]
+  python tools/packed_matmul_bench.py --skinny [--sweep-splits 1,2,4,8,16,32,64,128] [--out profiles/packed_matmul_skinny.txt]
 """
 from __future__ import annotations
 
@@ -30,6 +39,124 @@ from quantization_analysis_amd import hip_backend as hb
 from tools.packed_linear_bench import calibrate, greedy_map, window_ms
 
 
+def _calibrate(fn, target_ms: float) -> int:
+    """calibrate() with room for a 20 us kernel to fill the window."""
+    fn(0)
+    torch.cuda.synchronize()
+    one = max(window_ms(fn, 20), 1e-4)
+    return int(min(max(target_ms / one, 5), 4000))
+
+
+def _timed(fns, args):
+    """(medians, minima) in ms of the sides `fns`, alternated round by round."""
+    iters = [_calibrate(fn, args.window_ms) for fn in fns]
+    ts = [[] for _ in fns]
+    for _ in range(args.rounds):
+        for j, fn in enumerate(fns):
+            ts[j].append(window_ms(fn, iters[j]))
+    return [statistics.median(t) for t in ts], [min(t) for t in ts]
+
+
+def skinny(args, say, rows) -> None:
+    if not hb.has_packed_matmul_skinny():
+        raise hb.MtqError("this build of libmtq_hip.so lacks mtq_packed_matmul_skinny")
+    stream = torch.cuda.current_stream().cuda_stream
+    e_new, e_blk, e_lin = hb._entry("mtq_packed_matmul_skinny"), hb._entry("mtq_packed_matmul"), hb._entry("mtq_packed_linear_skinny")
+    ms = [int(v) for v in args.ms.split(",")]
+    passed = {m: True for m in ms}
+    first = True
+    for shape in args.shapes.split(","):
+        k, n = (int(v) for v in shape.split("x"))
+        g = torch.Generator(device="cuda").manual_seed(n + k)
+        pm = (torch.randn((k, n), generator=g, device="cuda") * 0.02).to(torch.bfloat16)      # P, k × n
+        w = pm.t().contiguous()
+        th, tw = hb.tiles_hw(k, n)
+        maps = {"bfp8": lambda: np.full((th, tw), 1, dtype=np.int8), "bfp4": lambda: np.full((th, tw), 2, dtype=np.int8), "greedy": lambda: greedy_map(pm)}
+        need = hb.packed_matmul_skinny_workspace_bytes(32, n, k, 0)
+        for s in args.sweep_splits:
+            need = max(need, hb.packed_matmul_skinny_workspace_bytes(32, n, k, s))
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device="cuda")                  # once, for every m and split
+        for name in args.maps.split(","):
+            amap = maps[name]()
+            counts = np.bincount(amap.reshape(-1), minlength=4).tolist()
+            tp = hb.PackedTables.on_device(amap)                                              # over P's grid
+            tl = hb.PackedTables.on_device(np.ascontiguousarray(amap.T))                      # over W's grid: the same counts
+            dp = hb.pack_tiles(pm, tp)
+            dl = hb.pack_tiles(w, tl)
+            pq = hb.unpack_tiles(dp, tp, k, n, dtype=torch.bfloat16)                          # P̂ bf16, k × n
+            tb = hb.PackedTables.on_device(np.zeros(hb.tiles_hw(n, k), dtype=np.int8))
+            db = hb.pack_tiles(pq.t().contiguous(), tb)                                       # the contract pair
+            copies_p = max(2, int(np.ceil(args.cold_mb * 1e6 / tp.nbytes)))
+            copies_w = max(2, int(np.ceil(args.cold_mb * 1e6 / (2 * n * k))))
+            dps = [dp] + [dp.clone() for _ in range(copies_p - 1)]
+            dls = [dl] + [dl.clone() for _ in range(copies_p - 1)]
+            pqs = [pq] + [pq.clone() for _ in range(copies_w - 1)]
+            for m in ms:
+                x = torch.randn((m, k), generator=g, device="cuda").to(torch.bfloat16)
+                ya, yb, yc, ym = (torch.empty((m, n), dtype=torch.bfloat16, device="cuda") for _ in range(4))
+
+                def equal_bits(split):
+                    hb.packed_matmul_skinny(x, dp, tp, n, out_dtype=torch.bfloat16, out=ya, split=split, workspace=ws)   # the wrappers' checks, once
+                    hb.packed_linear_skinny(x, db, tb, n, out_dtype=torch.bfloat16, out=yb, split=split, workspace=ws)
+                    return bool(torch.equal(ya.view(torch.int16), yb.view(torch.int16)))
+
+                same = equal_bits(0)
+
+                def new_calls(split):
+                    return [(x.data_ptr(), m, k, x.stride(0), d.data_ptr(), tp.nbytes, tp.map_ptr, tp.offsets_ptr, n, None, ya.data_ptr(), hb.DTYPE_BF16, n,
+                             split, ws.data_ptr(), ws.numel(), stream) for d in dps]
+
+                c_new = new_calls(0)
+                c_blk = [(x.data_ptr(), m, k, x.stride(0), d.data_ptr(), tp.nbytes, tp.map_ptr, tp.offsets_ptr, n, None, yc.data_ptr(), hb.DTYPE_BF16, n,
+                          stream) for d in dps]
+                c_lin = [(x.data_ptr(), m, k, x.stride(0), d.data_ptr(), tl.nbytes, tl.map_ptr, tl.offsets_ptr, n, None, yb.data_ptr(), hb.DTYPE_BF16, n,
+                          0, ws.data_ptr(), ws.numel(), stream) for d in dls]
+
+                def f_new(i):
+                    hb.check(e_new(*c_new[i % copies_p]))
+
+                def f_blk(i):
+                    hb.check(e_blk(*c_blk[i % copies_p]))
+
+                def f_lin(i):
+                    hb.check(e_lin(*c_lin[i % copies_p]))
+
+                def f_torch(i):
+                    torch.matmul(x, pqs[i % copies_w], out=ym)
+
+                med, mn = _timed((f_new, f_blk, f_lin, f_torch), args)
+                f_new(0)
+                f_torch(0)
+                err = float((ya.float() - ym.float()).abs().max() / ym.float().abs().max().clamp_min(1e-30))
+                gate = med[0] < mn[1] - (med[1] - mn[1])
+                passed[m] = passed[m] and gate and same
+                rows.append({"what": "packed_matmul_skinny", "k": k, "n": n, "m": m, "map": name, "counts": counts, "skinny_ms_median": med[0],
+                             "skinny_ms_min": mn[0], "block_ms_median": med[1], "block_ms_min": mn[1], "linear_skinny_ms_median": med[2],
+                             "linear_skinny_ms_min": mn[2], "torch_ms_median": med[3], "torch_ms_min": mn[3], "skinny_over_block_min": med[0] / mn[1],
+                             "block_spread": med[1] / mn[1], "skinny_over_linear_skinny": med[0] / med[2], "skinny_over_torch": med[0] / med[3],
+                             "stream_gbs": tp.nbytes / med[0] / 1e6, "gate": bool(gate), "contract_bits_equal": same, "max_rel_diff_torch": err})
+                say(f"skinny P {k}x{n} m={m:3d} map={name:6s} new {med[0] * 1e3:7.1f} us (min {mn[0] * 1e3:7.1f}, {tp.nbytes / med[0] / 1e6:7.1f} GB/s of stream) "
+                    f"block {med[1] * 1e3:7.1f} us (min {mn[1] * 1e3:7.1f}) linear-skinny {med[2] * 1e3:7.1f} us (min {mn[2] * 1e3:7.1f}) "
+                    f"torch {med[3] * 1e3:7.1f} us (min {mn[3] * 1e3:7.1f})  new/block-min {med[0] / mn[1]:6.3f} spread {med[1] / mn[1]:5.3f} "
+                    f"gate {'pass' if gate else 'FAIL'}  new/linear-skinny {med[0] / med[2]:5.2f} new/torch {med[0] / med[3]:5.2f}  "
+                    f"contract bits equal: {same}  max rel diff to torch {err:.2e}")
+                if first and args.sweep_splits:          # explicit splits on the first shape and map, the linear skinny kernel beside it
+                    for split in args.sweep_splits:
+                        ok = equal_bits(split)
+                        c_s = new_calls(split)
+                        c_l = [c[:13] + (split,) + c[14:] for c in c_lin]
+                        med_s, mn_s = _timed((lambda i: hb.check(e_new(*c_s[i % copies_p])), lambda i: hb.check(e_lin(*c_l[i % copies_p]))), args)
+                        rows.append({"what": "packed_matmul_skinny_split", "k": k, "n": n, "m": m, "map": name, "split": split, "skinny_ms_median": med_s[0],
+                                     "skinny_ms_min": mn_s[0], "linear_skinny_ms_median": med_s[1], "linear_skinny_ms_min": mn_s[1], "contract_bits_equal": ok})
+                        say(f"  split sweep P {k}x{n} m={m:3d} map={name:6s} split={split:4d} new {med_s[0] * 1e3:7.1f} us (min {mn_s[0] * 1e3:7.1f}) "
+                            f"linear-skinny {med_s[1] * 1e3:7.1f} us (min {mn_s[1] * 1e3:7.1f})  contract bits equal: {ok}")
+            first = False
+            del dps, dls, pqs, dp, dl, pq, db
+        del pm, w, ws
+    good = [m for m in ms if passed[m]]
+    say(f"# gate: every shape and map passes at m in {good}; AUTO_MATMUL_SKINNY_MAX_M = {max(good) if good else None}")
+
+
 def main() -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--rounds", type=int, default=5)
@@ -40,6 +167,8 @@ def main() -> int:
     p.add_argument("--ms", default="1,16,256,4096")
     p.add_argument("--maps", default="bfp8,bfp4,greedy")
     p.add_argument("--skip-pack", action="store_true", help="skip the pack / unpack timings")
+    p.add_argument("--skinny", action="store_true", help="time mtq_packed_matmul_skinny (m <= 32) against the block entry, the skinny linear and torch")
+    p.add_argument("--sweep-splits", default="", help="--skinny: explicit splits timed on the first shape and map, comma separated")
     p.add_argument("--out", default=None)
     p.add_argument("--json", default=None)
     args = p.parse_args()
@@ -53,6 +182,13 @@ def main() -> int:
         print(line, flush=True)
         lines.append(line)
 
+    if args.skinny:
+        args.ms = "1,16,32" if args.ms == p.get_default("ms") else args.ms
+        args.sweep_splits = [int(v) for v in args.sweep_splits.split(",") if v]
+        say(f"# mtq_packed_matmul_skinny on {torch.cuda.get_device_name(0)}; device events, {args.rounds} rounds of ~{args.window_ms:.0f} ms windows, "
+            f"sides alternated, weights rotated over {args.cold_mb:.0f} MB, bf16 output, split 0 unless named")
+        skinny(args, say, rows)
+        return finish(args, lines, rows)
     say(f"# mtq_packed_matmul on {torch.cuda.get_device_name(0)}; device events, {args.rounds} rounds of ~{args.window_ms:.0f} ms windows, "
         f"weights rotated over {args.cold_mb:.0f} MB; HBM figure {args.hbm_tbs} TB/s")
     stream = torch.cuda.current_stream().cuda_stream
@@ -143,6 +279,10 @@ def main() -> int:
                     f"contract bits equal: {same}  max rel diff to torch {err:.2e}")
             del dps, dls, pqs, dp, dl, pq, db
         del pm, w
+    return finish(args, lines, rows)
+
+
+def finish(args, lines, rows) -> int:
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text("\n".join(lines) + "\n")
