@@ -916,7 +916,7 @@ int mtq_glu_combine(const float *g, int64_t ldg, const float *u, int64_t ldu, in
  * Arguments are checked as by mtq_packed_linear_wide, for each stream (null pointers, m, n, k positive, the tile grid, ldx / ldy, a
  * stream below 320 bytes per tile or not 16-byte aligned): MTQ_ERR_INVALID before a device is looked for.  m = 0 and n = 0 are
  * refused as there; the Python binding returns the empty result without a call.  Correct for any m >= 1; m <= 32 is better served by
- * two skinny calls and the combine (there is no fused kernel for the decode range: a split over K has partial sums). */
+ * the split-K entries: two skinny calls and the combine, or mtq_packed_glu_skinny below, which is that sequence in two launches. */
 int mtq_packed_glu_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes, const int8_t *gate_map,
                         const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes, const int8_t *up_map, const uint32_t *up_offsets,
                         int64_t n, const float *bias_gate, const float *bias_up, int act, void *y, int out_dtype, int64_t ldy, void *stream);
@@ -939,6 +939,55 @@ int mtq_packed_glu_wide_grouped(const void *x, int64_t total_rows, int64_t k, in
                                 const void *up_packed, size_t up_bytes, const int8_t *up_maps, const uint32_t *up_offsets,
                                 const uint64_t *up_bases, int64_t count, int64_t n, const float *bias_gate, const float *bias_up, int64_t ldb,
                                 int act, void *y, int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The gated product for decode, 1 <= m <= MTQ_PACKED_SKINNY_MAX_M: mtq_packed_linear_skinny's split over K with one more unit axis,
+ * the projection.  Operands are mtq_packed_glu_wide's, followed by split, workspace and workspace_bytes as in the skinny entries.  A
+ * wave takes one (slice, projection, tile row) unit, reads its own projection's stream exactly as the skinny linear wave does and
+ * writes its float32 partial to the workspace; a second kernel on the same stream sums each projection's slices in ascending order
+ * from slice 0, adds that projection's bias last, applies glu_value and stores y (one rounding for a bf16 y).  Two launches at every
+ * split, against five for the two skinny calls and the combine; the two float32 (m, n) intermediates are not formed.
+ *
+ * split: 0 is the library's choice, mtq_packed_linear_skinny's rule for (m, n, k) unchanged (the projection axis is not counted
+ * into it); any other value is clamped to the number of tile columns.  The workspace is never empty: 2 * max(split_eff, 1) * m * n
+ * float32, rounded up to 16 bytes, the gate's partials first and the up's behind them; mtq_packed_glu_skinny_workspace_bytes gives
+ * the size ((size_t)-1 on bad arguments).  Nothing in it needs initialising and nothing a call leaves there is needed later.
+ *
+ * Bit contract: for every input and every split (0 included), y equals bit for bit the result of (1) mtq_packed_linear_skinny on the
+ * gate stream with bias_gate into float32 at that split, (2) the same on the up stream with bias_up, (3) mtq_glu_combine of the two.
+ * This holds in both output types, with or without either bias, and for any ldx / ldy.  Guards: a tile whose blob passes its own
+ * stream's packed_bytes or whose map code is outside 0..3 multiplies as zeros in its own projection only; rows at or past m and
+ * columns at or past k of x are never read; nothing outside m x n of y or outside the workspace is written.  No atomics, no
+ * counters, nothing waits on another workgroup: two calls give the same bits.
+ *
+ * Everything mtq_packed_linear_skinny refuses is refused here, for each stream, and so are m > MTQ_PACKED_SKINNY_MAX_M, a negative
+ * split, and - at every split - a workspace that is NULL, not 16-byte aligned or shorter than the size function's answer:
+ * MTQ_ERR_INVALID before a device is looked for.  An unknown act is MTQ_ERR_UNSUPPORTED.  Optional symbols, as the wide ones. */
+size_t mtq_packed_glu_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split);
+int mtq_packed_glu_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes, const int8_t *gate_map,
+                          const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes, const int8_t *up_map,
+                          const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up, int act, void *y, int out_dtype,
+                          int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same step on mtq_packed_linear_skinny_grouped, for the experts of an MoE layer at decode: mtq_packed_glu_wide_grouped's
+ * operands with `split` in front of the workspace.  A unit is (slice, projection, group, tile row); a group's rows are clamped as
+ * there and a group above 32 rows is walked in 32-row chunks by the same wave.  split 0 is mtq_packed_linear_skinny_grouped's rule
+ * for (count, n, k) unchanged.  The workspace is 2 * max(split_eff, 1) * total_rows * n float32 rounded up to 16 bytes, laid out and
+ * treated as above.
+ *
+ * Bit contract: for nondecreasing group_rows and every group with rows, y[r0:r1] equals bit for bit (1) mtq_packed_linear_skinny_grouped
+ * on the gate arena with bias_gate into float32 at that split, (2) the same on the up arena with bias_up, (3) mtq_glu_combine of the
+ * two.  Rows of y that belong to no group are not written.  A blob is checked against its own group's range
+ * [64 * bases[e], 64 * bases[e + 1]) of its OWN arena and against that arena's bytes, and multiplies as zeros in its own projection
+ * only when it passes either.  Whatever group_rows holds, nothing outside total_rows x n of y or outside the workspace is written
+ * and no row of x at or past total_rows is read.  Deterministic, as above.  Arguments are checked as by
+ * mtq_packed_linear_skinny_grouped, for each arena; the workspace and act as above. */
+size_t mtq_packed_glu_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split);
+int mtq_packed_glu_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                  const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                  const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                  const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n, const float *bias_gate,
+                                  const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace,
+                                  size_t workspace_bytes, void *stream);
 
 /* Test hook: the skinny kernel's decode (a cheaper form of the block kernel's for exponent bytes M..254, the same code elsewhere)
  * beside the reference decode, for fmt MTQ_FMT_BFP8 / BFP4 / BFP2.  got, want: device uint32 [16][256][16][16] = [rot][E][q][i], the

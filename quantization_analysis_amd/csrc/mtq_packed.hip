@@ -2114,6 +2114,232 @@ __global__ __launch_bounds__(256) void glu_combine_kernel(const float *__restric
     }
 }
 
+// ---- skinny GLU (m <= 32): packed_linear_skinny_kernel's wave on one more unit axis, the projection p (0 the gate, 1 the up).
+//
+// A unit is (slice s, projection p, tile row tr), numbered ((2 s + p) * tiles_h + tr): the tile row is fastest, so the four waves of a
+// workgroup share a slice of X as in the linear kernel.  The wave takes its projection's stream, map, offsets and bytes and does on them
+// what that kernel's wave does: the readlane hand-out of up to 64 tiles per load, the ring of kSkinnyRing tiles with every load issued
+// before the first decode, the blob check against its own stream's bytes, decode_skinny and two MFMAs per tile in ascending K.  Its f32
+// partial always goes to ws[p][s][m][n] with plain stores, at split 1 too: no wave holds both projections, and glu_skinny_reduce_kernel
+// is where they meet.  No LDS, no barrier, no atomics; the only early exit before the loads is the wave-uniform unit bound.
+__global__ __launch_bounds__(64 * kSkinnyWaves) void packed_glu_skinny_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec, const uint8_t *__restrict__ gate, uint64_t gate_bytes,
+    const int8_t *__restrict__ gate_map, const uint32_t *__restrict__ gate_offsets, const uint8_t *__restrict__ up, uint64_t up_bytes,
+    const int8_t *__restrict__ up_map, const uint32_t *__restrict__ up_offsets, int64_t N, int64_t tiles_h, int64_t tiles_w, int split,
+    float *__restrict__ ws)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= 2 * tiles_h * split) return;         // wave-uniform; the kernel has no barrier
+    const int64_t tr = unit % tiles_h, sp = unit / tiles_h, p = sp & 1, s = sp >> 1;
+    const uint8_t *__restrict__ packed = p ? up : gate;
+    const uint64_t packed_bytes = p ? up_bytes : gate_bytes;
+    const int8_t *__restrict__ map = p ? up_map : gate_map;
+    const uint32_t *__restrict__ offsets = p ? up_offsets : gate_offsets;
+    const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
+    const int row = lane & 31, half = lane >> 5, gi = 2 * row + half;
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+
+    for (int64_t cb = c0; cb < c1; cb += 64) {
+        const int cnt = (int)std::min<int64_t>(64, c1 - cb);
+        int mf = -1, mo = 0;                         // lane i: map code and offset of tile cb + i
+        if (lane < cnt) {
+            const int64_t t = tr * tiles_w + cb + lane;
+            mf = map[t];
+            mo = (int)offsets[t];
+        }
+        for (int b = 0; b < cnt; b += kSkinnyRing) {
+            GroupRaw g[kSkinnyRing];
+            uint4 xl[kSkinnyRing], xh[kSkinnyRing];
+#pragma unroll
+            for (int j = 0; j < kSkinnyRing; ++j) {
+                const int i = b + j;                 // uniform
+                TileAt a;
+                a.off = 0;
+                a.f = -1;
+                xl[j] = make_uint4(0u, 0u, 0u, 0u);
+                xh[j] = xl[j];
+                if (i < cnt) {
+                    const int f = __builtin_amdgcn_readlane(mf, i);
+                    a.off = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(mo, i) * kUnit;
+                    const uint32_t size = packed_tile_bytes(f);
+                    a.f = (size == 0u || a.off + size > packed_bytes) ? -1 : f;
+                    load_x16(x, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
+                }
+                load_group(packed, a, gi, g[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < kSkinnyRing; ++j) {
+                if (b + j < cnt) {
+                    uint32_t y[kGroup];
+                    decode_skinny(g[j], y);
+                    uint4 lo, hi;
+                    pack_halves(y, lo, hi);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(lo), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(hi), acc, 0, 0, 0);
+                }
+            }
+        }
+    }
+
+    // lane's outputs are (m = (r&3) + 8(r>>2) + 4·half, n = 32·tr + row) of slice s of projection p
+    const int64_t n = tr * kTile + row;
+    if (n >= N) return;
+    float *wl = ws + (((int64_t)p * split + s) * M + 4 * half) * N + n;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int mu = (r & 3) + 8 * (r >> 2);
+        if (mu + 4 * half < M) wl[mu * N] = acc[r];
+    }
+}
+
+// One thread per output: g = ((p0 + p1) + ... + p_{split-1}) + bias_gate over the gate's slices in ascending order from slice 0, the
+// bias last, as skinny_reduce_kernel forms it; u the same from the up's slices, which lie `split` slices behind the gate's; then
+// glu_value and one rounding for a bf16 Y.
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void glu_skinny_reduce_kernel(const float *__restrict__ ws, int64_t MN, int64_t N, int split,
+                                                                const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int act,
+                                                                void *__restrict__ yv, int64_t ldy)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= MN) return;
+    const int64_t m = idx / N, n = idx % N;
+    const float *wu = ws + (int64_t)split * MN;
+    float g = ws[idx], u = wu[idx];
+    for (int s = 1; s < split; ++s) g += ws[(int64_t)s * MN + idx];
+    for (int s = 1; s < split; ++s) u += wu[(int64_t)s * MN + idx];
+    g += bias_gate ? bias_gate[n] : 0.0f;
+    u += bias_up ? bias_up[n] : 0.0f;
+    store_y<BF16OUT>(yv, m * ldy + n, glu_value(g, u, act));
+}
+
+// ---- grouped skinny GLU: packed_linear_skinny_grouped_kernel's wave on the projection axis, over two arenas.
+//
+// A unit is (slice s, projection p, group e, tile row tr), numbered (((2 s + p) * count + e) * tiles_h + tr).  The group's clamped rows,
+// the walk in 32-row chunks by the same wave, the hand-out, ring, decode and MFMAs are that kernel's; the maps, offsets, bases and bytes
+// are the wave's own arena's, and a blob is checked against its own group's range of that arena.  The partial of every chunk goes to
+// ws[p][s][row][n] with plain stores at every split.
+__global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_skinny_grouped_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
+    const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps, const uint32_t *__restrict__ gate_offsets,
+    const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes, const int8_t *__restrict__ up_maps,
+    const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int N, int tiles_h, int tiles_w, int split,
+    float *__restrict__ ws)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= (int64_t)2 * tiles_h * count * split) return;   // wave-uniform; the kernel has no barrier
+    const int64_t tr = unit % tiles_h, spe = unit / tiles_h, e = spe % count, sp = spe / count, p = sp & 1, s = sp >> 1;
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    if (gr.r1 == gr.r0) return;                      // nothing of this expert is read
+    const int64_t tiles = (int64_t)tiles_h * tiles_w;
+    const uint8_t *__restrict__ packed = p ? up : gate;
+    const int8_t *map = (p ? up_maps : gate_maps) + e * tiles;
+    const uint32_t *off = (p ? up_offsets : gate_offsets) + e * (tiles + 1);
+    const uint64_t *bases = p ? up_bases : gate_bases;
+    const uint64_t base = bases[e], limit = std::min<uint64_t>(bases[e + 1], (p ? up_bytes : gate_bytes) / kUnit);   // units
+    const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
+
+    for (int64_t row0 = gr.r0; row0 < gr.r1; row0 += kTile) {
+        int lv = lane;
+        asm volatile("" : "+v"(lv));                 // the lane's addresses are formed per chunk, not kept in registers across chunks
+        const int row = lv & 31, half = lv >> 5, gi = 2 * row + half;
+        const int64_t n = tr * kTile + row;
+        const int64_t M = std::min<int64_t>(kTile, gr.r1 - row0);
+        const uint16_t *xc = x + row0 * ldx;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+
+        for (int64_t cb = c0; cb < c1; cb += 64) {
+            const int cnt = (int)std::min<int64_t>(64, c1 - cb);
+            int mf = -1, mo = 0;                     // lane i: map code and offset of tile cb + i
+            if (lane < cnt) {
+                const int64_t t = tr * tiles_w + cb + lane;
+                mf = map[t];
+                mo = (int)off[t];
+            }
+            for (int b = 0; b < cnt; b += kSkinnyRing) {
+                GroupRaw g[kSkinnyRing];
+                uint4 xl[kSkinnyRing], xh[kSkinnyRing];
+#pragma unroll
+                for (int j = 0; j < kSkinnyRing; ++j) {
+                    const int i = b + j;             // uniform
+                    TileAt a;
+                    a.off = 0;
+                    a.f = -1;
+                    xl[j] = make_uint4(0u, 0u, 0u, 0u);
+                    xh[j] = xl[j];
+                    if (i < cnt) {
+                        const int f = __builtin_amdgcn_readlane(mf, i);
+                        const uint64_t at = base + (uint32_t)__builtin_amdgcn_readlane(mo, i);   // base <= limit < 2^58 where it counts
+                        const uint32_t size = packed_tile_bytes(f);
+                        a.off = at * kUnit;
+                        a.f = (size == 0u || base > limit || at + size / kUnit > limit) ? -1 : f;
+                        load_x16(xc, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
+                    }
+                    load_group(packed, a, gi, g[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < kSkinnyRing; ++j) {
+                    if (b + j < cnt) {
+                        uint32_t y[kGroup];
+                        decode_skinny(g[j], y);
+                        uint4 lo, hi;
+                        pack_halves(y, lo, hi);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(lo), acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(hi), acc, 0, 0, 0);
+                    }
+                }
+            }
+        }
+
+        // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row) of slice s of projection p
+        if (n < N) {
+            float *wl = ws + ((((int64_t)p * split + s) * T + row0 + 4 * half) * N + n);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int mu = (r & 3) + 8 * (r >> 2);
+                if (mu + 4 * half < M) wl[(int64_t)mu * N] = acc[r];
+            }
+        }
+    }
+}
+
+// skinny_grouped_reduce_kernel's frame: one workgroup per (group e, 256 columns), thread n walks the group's clamped rows, so only rows
+// inside a clamped group are written.  Per output glu_value(g, u) with g and u formed as glu_skinny_reduce_kernel forms them, the
+// biases rows e of both bias matrices.
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void glu_skinny_grouped_reduce_kernel(const float *__restrict__ ws, int64_t T, int64_t N, int split,
+                                                                        const int32_t *__restrict__ group_rows, int64_t nchunks,
+                                                                        const float *__restrict__ bias_gate, const float *__restrict__ bias_up,
+                                                                        int64_t ldb, int act, void *__restrict__ yv, int64_t ldy)
+{
+    const int64_t e = blockIdx.x / nchunks, n = (blockIdx.x % nchunks) * 256 + threadIdx.x;
+    if (n >= N) return;
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    if (gr.r1 == gr.r0) return;
+    const float bg = bias_gate ? bias_gate[e * ldb + n] : 0.0f, bu = bias_up ? bias_up[e * ldb + n] : 0.0f;
+    const float *wu = ws + (int64_t)split * T * N;
+    for (int64_t m = gr.r0; m < gr.r1; ++m) {
+        float g = ws[m * N + n], u = wu[m * N + n];
+        for (int s = 1; s < split; ++s) g += ws[((int64_t)s * T + m) * N + n];
+        for (int s = 1; s < split; ++s) u += wu[((int64_t)s * T + m) * N + n];
+        g += bg;
+        u += bu;
+        store_y<BF16OUT>(yv, m * ldy + n, glu_value(g, u, act));
+    }
+}
+
+// The skinny GLU entries' workspace: both projections' partials at every split, the gate's first; never empty.
+size_t glu_skinny_workspace(int64_t m, int64_t n, int split_eff)
+{
+    return (2 * (size_t)std::max(split_eff, 1) * (size_t)m * (size_t)n * sizeof(float) + 15) & ~(size_t)15;
+}
+
 // skinny_shape for the grouped entry: skinny_split's rule with count * tiles_h tile rows, which for count == 1 is that rule.
 int grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *tiles_h, int64_t *tiles_w, int *split_eff)
 {
@@ -2866,6 +3092,121 @@ extern "C" int mtq_packed_glu_wide_grouped(const void *x, int64_t total_rows, in
                                                                              group_rows, bstart, ga, ua, count, n, th, tw, bias_gate, bias_up, ldb,
                                                                              act, y, out_dtype, ldy);
     return check_launch("mtq_packed_glu_wide_grouped");
+}
+
+// ---- gated entries for decode: both projections in one split-K launch, the activation in the reduce
+static int glu_skinny_workspace_args(const void *workspace, size_t workspace_bytes, size_t need)
+{
+    if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null: the partial sums of both projections need one at every split");
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
+    if (workspace_bytes < need)
+        return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this split needs", workspace_bytes, need);
+    return MTQ_OK;
+}
+
+extern "C" size_t mtq_packed_glu_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
+{
+    int64_t th, tw;
+    int eff;
+    if (skinny_shape(m, n, k, split, &th, &tw, &eff)) return (size_t)-1;
+    return glu_skinny_workspace(m, n, eff);
+}
+
+extern "C" int mtq_packed_glu_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                                     const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
+                                     const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up,
+                                     int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                     void *stream)
+{
+    if (!x || !gate_packed || !gate_map || !gate_offsets || !up_packed || !up_map || !up_offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    int eff;
+    if (int rc = skinny_shape(m, n, k, split, &th, &tw, &eff)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if (reinterpret_cast<uintptr_t>(gate_packed) % 16 != 0 || reinterpret_cast<uintptr_t>(up_packed) % 16 != 0)
+        return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    const uint64_t least = (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2);
+    if (gate_bytes < least || up_bytes < least) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
+    if (int rc = glu_act(act)) return rc;
+    if (int rc = glu_skinny_workspace_args(workspace, workspace_bytes, glu_skinny_workspace(m, n, eff))) return rc;
+    const int64_t blocks = (2 * th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
+    hipLaunchKernelGGL(packed_glu_skinny_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), m, k, ldx,
+                       x_vec, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
+                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, th, tw, eff, ws);
+    if (int rc = check_launch("mtq_packed_glu_skinny")) return rc;
+    const dim3 rgrid((unsigned)((m * n + 255) / 256));
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(glu_skinny_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias_gate, bias_up, act, y, ldy);
+    else
+        hipLaunchKernelGGL(glu_skinny_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias_gate, bias_up, act, y, ldy);
+    return check_launch("mtq_packed_glu_skinny");
+}
+
+// grouped_shape and the bound that keeps the two projections' partials inside size_t at every split
+static int glu_grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *th, int64_t *tw, int *eff)
+{
+    if (int rc = grouped_shape(total_rows, count, n, k, split, th, tw, eff)) return rc;
+    if (total_rows > ((int64_t)1 << 55) / n / *eff) return fail(MTQ_ERR_INVALID, "the workspace of this split is too large");
+    return MTQ_OK;
+}
+
+extern "C" size_t mtq_packed_glu_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    int64_t th, tw;
+    int eff;
+    if (glu_grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
+    return glu_skinny_workspace(total_rows, n, eff);
+}
+
+extern "C" int mtq_packed_glu_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                             const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                             const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                             const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n,
+                                             const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y, int out_dtype,
+                                             int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets || !up_bases || !y)
+        return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;
+    int eff;
+    if (int rc = glu_grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if ((bias_gate || bias_up) && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
+    if (reinterpret_cast<uintptr_t>(gate_packed) % 16 != 0 || reinterpret_cast<uintptr_t>(up_packed) % 16 != 0)
+        return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    const uint64_t least = (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2);
+    if (gate_bytes < least || up_bytes < least) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
+    if (int rc = glu_act(act)) return rc;
+    if (int rc = glu_skinny_workspace_args(workspace, workspace_bytes, glu_skinny_workspace(total_rows, n, eff))) return rc;
+    const int64_t blocks = (2 * count * th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    const int64_t nchunks = (n + 255) / 256;
+    if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
+    hipLaunchKernelGGL(packed_glu_skinny_grouped_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x),
+                       (int)total_rows, (int)k, ldx, x_vec, group_rows, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps,
+                       gate_offsets, gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases, (int)count,
+                       (int)n, (int)th, (int)tw, eff, ws);
+    if (int rc = check_launch("mtq_packed_glu_skinny_grouped")) return rc;
+    const dim3 rgrid((unsigned)(count * nchunks));
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(glu_skinny_grouped_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias_gate, bias_up,
+                           ldb, act, y, ldy);
+    else
+        hipLaunchKernelGGL(glu_skinny_grouped_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias_gate,
+                           bias_up, ldb, act, y, ldy);
+    return check_launch("mtq_packed_glu_skinny_grouped");
 }
 
 extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)

@@ -136,6 +136,10 @@ SIGNATURES = {
     "mtq_packed_matmul": ("i", "plllpzpplppilp", True),
     "mtq_packed_matmul_skinny_workspace_bytes": ("z", "llli", True),
     "mtq_packed_matmul_skinny": ("i", "plllpzpplppilipzp", True),
+    "mtq_packed_glu_skinny_workspace_bytes": ("z", "llli", True),
+    "mtq_packed_glu_skinny": ("i", "plllpzpppzpplppipilipzp", True),
+    "mtq_packed_glu_skinny_grouped_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_glu_skinny_grouped": ("i", "plllppzppppzpppllpplipilipzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1519,16 +1523,10 @@ def packed_glu_wide_grouped_workspace_bytes(total_rows: int, count: int, n: int,
     return size
 
 
-def packed_glu_wide_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None, out=None,
-                            workspace=None, stream="current"):
-    """mtq_packed_glu_wide_grouped on the current stream: packed_glu_wide's product for the `count` experts of two arenas, each over its
-    own rows of X, in one launch.  gate, up: (arena, maps_dev, offsets_dev, bases_dev) as packed_linear_wide_grouped takes them, of
-    `count` (n, k) experts each; x, group_rows, out and workspace as there; bias_gate, bias_up: None or float32 (count, n) device
-    tensors of one row pitch.  Per group the bits of two packed_linear calls into float32 and glu_combine on the group's rows.  An
-    `out` allocated here starts as zeros, so rows outside every group are zeros."""
+def _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up):
+    """The grouped gated entries' operands checked → (count, n, T, k, ldx, group_rows pointer, the ten arena arguments, the two bias
+    pointers, ldb)."""
     torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code, a = _packed_out_code(out_dtype), _act_code(act)
     count, n = int(count), int(n)
     x_code, _count, _stride, T, k, ldx = _matrix(x, (2,))
     if x_code != DTYPE_BF16:
@@ -1555,6 +1553,20 @@ def packed_glu_wide_grouped(x, group_rows, gate, up, count: int, n: int, act="si
             raise MtqError("bias_gate and bias_up must have one row pitch")
         ptrs.append(bias.data_ptr())
         ldb = pitch
+    return count, n, T, k, ldx, pg, sides, ptrs, ldb
+
+
+def packed_glu_wide_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None, out=None,
+                            workspace=None, stream="current"):
+    """mtq_packed_glu_wide_grouped on the current stream: packed_glu_wide's product for the `count` experts of two arenas, each over its
+    own rows of X, in one launch.  gate, up: (arena, maps_dev, offsets_dev, bases_dev) as packed_linear_wide_grouped takes them, of
+    `count` (n, k) experts each; x, group_rows, out and workspace as there; bias_gate, bias_up: None or float32 (count, n) device
+    tensors of one row pitch.  Per group the bits of two packed_linear calls into float32 and glu_combine on the group's rows.  An
+    `out` allocated here starts as zeros, so rows outside every group are zeros."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    count, n, T, k, ldx, pg, sides, ptrs, ldb = _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up)
     need = packed_glu_wide_grouped_workspace_bytes(T, count, n, k) if T else 0
     fn = _entry("mtq_packed_glu_wide_grouped")
     out, ldy = _glu_out(out, T, n, out_dtype, x.device, zeros=True)
@@ -1567,6 +1579,96 @@ def packed_glu_wide_grouped(x, group_rows, gate, up, count: int, n: int, act="si
     if workspace.data_ptr() % 16:
         raise MtqError("workspace must be 16-byte aligned")
     check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, ws_ptr, ws_bytes,
+             _packed_stream_ptr(stream)))
+    return out
+
+
+PACKED_GLU_SKINNY = ("mtq_packed_glu_skinny_workspace_bytes", "mtq_packed_glu_skinny", "mtq_packed_glu_skinny_grouped_workspace_bytes",
+                     "mtq_packed_glu_skinny_grouped")
+
+
+def has_packed_glu_skinny() -> bool:
+    """Whether this build of the library has the fused gated entries for decode (mtq_packed_glu_skinny, mtq_packed_glu_skinny_grouped and
+    their size functions; optional symbols: an older build of the same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in PACKED_GLU_SKINNY)
+
+
+def _size_or_raise(size: int) -> int:
+    if size == ctypes.c_size_t(-1).value:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return size
+
+
+def _glu_workspace(workspace, need: int, device):
+    """`workspace` checked, or a new one of `need` bytes → (pointer, bytes)."""
+    torch = _torch()
+    if workspace is None:
+        require_gpu()
+        workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+    ws_ptr = _buffer(workspace, torch.uint8, need, "workspace")
+    if workspace.data_ptr() % 16:
+        raise MtqError("workspace must be 16-byte aligned")
+    return ws_ptr, int(workspace.numel())
+
+
+def packed_glu_skinny_workspace_bytes(m: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_glu_skinny_workspace_bytes (a host function: no GPU): the bytes of workspace the fused decode call needs for
+    (m, n, k, split); split 0 is the library's choice.  Never 0: both projections' partial sums go through it at every split."""
+    return _size_or_raise(int(_entry("mtq_packed_glu_skinny_workspace_bytes")(int(m), int(n), int(k), int(split))))
+
+
+def packed_glu_skinny(x, gate_data, gate_tables: PackedTables, up_data, up_tables: PackedTables, n: int, act="silu", bias_gate=None,
+                      bias_up=None, out_dtype=None, out=None, split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_glu_skinny on the current stream: packed_glu_wide's product for m <= 32 with a split over K (split 0: the library's
+    choice), two launches: bit for bit two packed_linear_skinny calls into float32 at that split and glu_combine.  workspace: a uint8
+    device tensor of at least packed_glu_skinny_workspace_bytes(m, n, k, split) bytes, 16-byte aligned; allocated here when none is
+    given.  m = 0 or n = 0 gives the empty (m, n) tensor without a launch."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if m > PACKED_SKINNY_MAX_M:
+        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
+    for name, tables in (("gate", gate_tables), ("up", up_tables)):
+        if tiles_hw(n, k) != (tables.tiles_h, tables.tiles_w):
+            raise MtqError(f"the {name} map is {tables.tiles_h}x{tables.tiles_w} tiles, a {n}x{k} weight has {'x'.join(map(str, tiles_hw(n, k)))}")
+    pg, pu = _packed_stream(gate_data, gate_tables, "gate data"), _packed_stream(up_data, up_tables, "up data")
+    bg = None if bias_gate is None else _buffer(bias_gate, torch.float32, n, "bias_gate")
+    bu = None if bias_up is None else _buffer(bias_up, torch.float32, n, "bias_up")
+    fn = _entry("mtq_packed_glu_skinny")
+    out, ldy = _glu_out(out, m, n, out_dtype, x.device)
+    if m == 0 or n == 0:                             # the entry refuses empty operands, as the skinny entry does: they end here
+        return out
+    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_skinny_workspace_bytes(m, n, k, split), x.device)
+    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
+             up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
+             _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_glu_skinny_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_glu_skinny_grouped_workspace_bytes (a host function: no GPU): packed_glu_skinny_workspace_bytes for the grouped call,
+    total_rows in place of m and the grouped entry's own split rule at split 0."""
+    return _size_or_raise(int(_entry("mtq_packed_glu_skinny_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k), int(split))))
+
+
+def packed_glu_skinny_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None, out=None,
+                              split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_glu_skinny_grouped on the current stream: packed_glu_wide_grouped's operands and product from the skinny family's
+    split over K, for decode-sized groups: per group the bits of two packed_linear_skinny_grouped calls into float32 at that split
+    and glu_combine.  An `out` allocated here starts as zeros, so rows outside every group are zeros."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    count, n, T, k, ldx, pg, sides, ptrs, ldb = _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up)
+    fn = _entry("mtq_packed_glu_skinny_grouped")
+    out, ldy = _glu_out(out, T, n, out_dtype, x.device, zeros=True)
+    if T == 0:
+        return out
+    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_skinny_grouped_workspace_bytes(T, count, n, k, split), x.device)
+    check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
              _packed_stream_ptr(stream)))
     return out
 

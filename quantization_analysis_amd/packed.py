@@ -65,6 +65,7 @@ AUTO_MATMUL_SKINNY_MAX_M = 32
 ACTS =("silu", "none")     # include/mtq.h MTQ_ACT_SILU, MTQ_ACT_NONE
 GLU_KERNELS = ("fused", "unfused", "auto")
 GLU_GROUPED_KERNELS = ("fused", "unfused")
+MLP_DECODE_KERNELS = ("pair", "fused")   # PackedMLP(decode_kernel=...): glu(kernel="auto")'s five launches at m <= 32, or glu_skinny's two
 # glu(kernel="auto") above the skinny range takes the fused kernel (mtq_packed_glu_wide) from this m on; None: never, "auto" stays
 # unfused there.  The rule of AUTO_WIDE_MIN_M: the smallest measured m from which on the fused median is below the unfused minimum of the
 # same run at every shape and map (profiles/packed_glu.txt).  Both routes give the same bits, so the gate changes no
@@ -1049,8 +1050,8 @@ def glu(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=No
     (GLU_KERNELS): "fused", mtq_packed_glu_wide, one launch in which a workgroup holds both projections of its outputs, so X is read
     once and no (m, n) intermediate reaches memory; "unfused", two linear(kernel="block") calls into float32 and hip_backend.glu_combine,
     bit for bit what "fused" gives; "auto": for m <= AUTO_SKINNY_MAX_M two linear(kernel="skinny") calls and the combine (the skinny
-    family's sums, which may differ from the block family's in the last bits, as linear(kernel="auto") already does; there is no fused
-    kernel for the decode range), above that "fused" from m = AUTO_GLU_FUSED_MIN_M on when that is not None, "unfused" otherwise.  A
+    family's sums, which may differ from the block family's in the last bits, as linear(kernel="auto") already does; glu_skinny is the same
+    bits from the fused decode kernel), above that "fused" from m = AUTO_GLU_FUSED_MIN_M on when that is not None, "unfused" otherwise.  A
     library without the gated entries raises MtqError under every name: there is no fall-back.
     emulation: float64 throughout from the unpacked weights, g = X·Ŵgᵀ + bg, u likewise, act(g) * u, rounded once to float32 and from
     there to bf16, as linear's emulation rounds; the same value under every kernel name."""
@@ -1106,6 +1107,42 @@ def glu_emulation_f64(xf: np.ndarray, gate: PackedTensor, up: PackedTensor, act:
     return _glu_host(sides[0], sides[1], act)
 
 
+def _need_glu_skinny(hb, what: str) -> None:
+    if not hb.has_packed_glu_skinny():
+        raise MtqError(f"{what} needs mtq_packed_glu_skinny and mtq_packed_glu_skinny_grouped, which this build of libmtq_hip.so lacks: "
+                       "rebuild it from this tree")
+
+
+def glu_skinny(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
+               backend: Optional[str] = None, split: int = 0, workspace=None):
+    """glu for decode, m <= SKINNY_MAX_M, from the fused split-K kernel: mtq_packed_glu_skinny, two launches in place of the five of
+    glu(kernel="auto") at these m, and at split 0 bit for bit its value; at any `split`, the bits of two linear(kernel="skinny") calls
+    into float32 at that split and hip_backend.glu_combine.  `split` and `workspace` as in linear(kernel="skinny"), the workspace of
+    hip_backend.packed_glu_skinny_workspace_bytes bytes (never 0), allocated when None.  m > SKINNY_MAX_M and a library without the
+    entry raise MtqError: there is no fall-back.
+    emulation: glu's float64 value rounded once, whatever m and split."""
+    _glu_pair(gate, up)
+    _check_act(act)
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    backend = backend or ("hip" if gate.on_device else "emulation")
+    n, k = gate.rows, gate.cols
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        if x.dim() != 2 or x.shape[1] != k:
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        _need_glu_skinny(hb, "glu_skinny")
+        if int(x.shape[0]) > SKINNY_MAX_M:
+            raise MtqError(f"glu_skinny takes m <= {SKINNY_MAX_M}, got m = {int(x.shape[0])}: glu(kernel=\"auto\") serves every m")
+        return hb.packed_glu_skinny(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act, bias_gate=bias_gate,
+                                    bias_up=bias_up, out_dtype=torch.float32 if out_dtype == "float32" else torch.bfloat16, split=split,
+                                    workspace=workspace)
+    return glu(x, gate, up, act=act, bias_gate=bias_gate, bias_up=bias_up, out_dtype=out_dtype, backend=backend)
+
+
 def glu_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
                 backend: Optional[str] = None, kernel: str = "fused", workspace=None):
     """glu for all experts of an MoE layer at once → (T, n): H[rows of group e] = act(X[rows]·Ŵg[e]ᵀ + bg[e]) * (X[rows]·Ŵu[e]ᵀ + bu[e]).
@@ -1116,10 +1153,26 @@ def glu_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gat
     into float32 and hip_backend.glu_combine over all T rows - the same bits on every row of a group (a row of no group is zero under
     "fused" and act(0) * 0 = 0 under "unfused").  T = 0 gives (0, n) without a call.
     emulation: per group glu's float64 value, rounded once."""
+    return _glu_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, GLU_GROUPED_KERNELS, 0, workspace)
+
+
+def glu_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
+                       backend: Optional[str] = None, split: int = 0, workspace=None):
+    """glu_grouped for decode-sized groups from the fused split-K kernel: mtq_packed_glu_skinny_grouped, two launches over both arenas.
+    The arguments are resolved as glu_grouped resolves them.  Per group the bits of two linear_grouped(kernel="walk") calls into float32
+    at that `split` and hip_backend.glu_combine: the skinny family's sums, which may differ from glu_grouped's in the last bits.  Rows
+    of no group are zeros.  workspace: an optional uint8 device tensor of hip_backend.packed_glu_skinny_grouped_workspace_bytes bytes.
+    T = 0 gives (0, n) without a call; a library without the entry raises MtqError: there is no fall-back.
+    emulation: glu_grouped's value."""
+    return _glu_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, "skinny", ("skinny",), split, workspace)
+
+
+def _glu_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, kernels, split, workspace):
+    """glu_grouped and glu_grouped_skinny: `kernel` one of `kernels`, GLU_GROUPED_KERNELS or, from the latter alone, ("skinny",)."""
     gate_b, up_b = _resolve_batch(gate_batch), _resolve_batch(up_batch)
     _check_act(act)
-    if kernel not in GLU_GROUPED_KERNELS:
-        raise MtqError(f"kernel must be one of {GLU_GROUPED_KERNELS}, got {kernel!r}")
+    if kernel not in kernels:
+        raise MtqError(f"kernel must be one of {kernels}, got {kernel!r}")
     if out_dtype not in ("float32", "bfloat16"):
         raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
     if (gate_b.count, gate_b.rows, gate_b.cols) != (up_b.count, up_b.rows, up_b.cols):
@@ -1140,7 +1193,10 @@ def glu_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gat
 
         from . import hip_backend as hb
 
-        _need_glu(hb, "glu_grouped")                 # a missing kernel is refused before any device work
+        if kernel == "skinny":                       # a missing kernel is refused before any device work
+            _need_glu_skinny(hb, "glu_grouped_skinny")
+        else:
+            _need_glu(hb, "glu_grouped")
         gate_b, up_b = batch_to_device(gate_b), batch_to_device(up_b)
         dev = gate_b.arena.device
         dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
@@ -1150,6 +1206,10 @@ def glu_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gat
             group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(dev)
         bias_gate, bias_up = (b if b is None or _is_torch(b) else torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(dev)
                               for b in (bias_gate, bias_up))
+        if kernel == "skinny":
+            return hb.packed_glu_skinny_grouped(x, group_rows, (gate_b.arena, gate_b.maps_dev, gate_b.offsets_dev, gate_b.bases_dev),
+                                                (up_b.arena, up_b.maps_dev, up_b.offsets_dev, up_b.bases_dev), count, n, act=act,
+                                                bias_gate=bias_gate, bias_up=bias_up, out_dtype=dtype, split=split, workspace=workspace)
         if kernel == "fused":
             return hb.packed_glu_wide_grouped(x, group_rows, (gate_b.arena, gate_b.maps_dev, gate_b.offsets_dev, gate_b.bases_dev),
                                               (up_b.arena, up_b.maps_dev, up_b.offsets_dev, up_b.bases_dev), count, n, act=act,
@@ -1185,11 +1245,15 @@ def _packed_mlp_class():
     class PackedMLP(torch.nn.Module):
         """A gated MLP over three packed weights, down(act(gate(x)) * up(x)): gate and up (n, k), down (k_out, n).  INFERENCE ONLY, as
         PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, runs glu(kernel="auto") into bf16 and
-        linear(kernel="auto") with `down`, and returns (..., k_out) in out_dtype; m = 0 gives the empty result without a call."""
+        linear(kernel="auto") with `down`, and returns (..., k_out) in out_dtype; m = 0 gives the empty result without a call.
+        decode_kernel (MLP_DECODE_KERNELS): "pair", that route at every m; "fused", m <= AUTO_SKINNY_MAX_M goes through glu_skinny
+        instead, the same bits from two launches in place of five."""
 
         def __init__(self, gate: PackedTensor, up: PackedTensor, down: PackedTensor, act: str = "silu", out_dtype: str = "bfloat16",
-                     backend: Optional[str] = None):
+                     backend: Optional[str] = None, decode_kernel: str = "pair"):
             super().__init__()
+            if decode_kernel not in MLP_DECODE_KERNELS:
+                raise MtqError(f"decode_kernel must be one of {MLP_DECODE_KERNELS}, got {decode_kernel!r}")
             _glu_pair(gate, up)
             _check_act(act)
             _check_layout(down.layout)
@@ -1204,10 +1268,12 @@ def _packed_mlp_class():
                 from . import hip_backend as hb
 
                 _need_glu(hb, "PackedMLP")           # refused here, not at the first forward
+                if decode_kernel == "fused":
+                    _need_glu_skinny(hb, 'PackedMLP(decode_kernel="fused")')
                 for pt in (gate, up, down):
                     _device_data(pt)
                     pt.tables()
-            self.gate, self.up, self.down, self.act, self.out_dtype = gate, up, down, act, out_dtype
+            self.gate, self.up, self.down, self.act, self.out_dtype, self.decode_kernel = gate, up, down, act, out_dtype, decode_kernel
             self.in_features, self.hidden_features, self.out_features = gate.cols, gate.rows, down.rows
 
         def extra_repr(self) -> str:
@@ -1222,7 +1288,10 @@ def _packed_mlp_class():
             x2 = x.reshape(-1, self.in_features)
             if x2.shape[0] == 0:
                 return torch.zeros(lead + (self.out_features,), dtype=torch.float32 if self.out_dtype == "float32" else torch.bfloat16, device=x.device)
-            h = glu(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="auto")
+            if self.decode_kernel == "fused" and x2.shape[0] <= AUTO_SKINNY_MAX_M:
+                h = glu_skinny(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend)
+            else:
+                h = glu(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="auto")
             y = linear(h, self.down, out_dtype=self.out_dtype, backend=self.backend, kernel="auto")
             if not _is_torch(y):
                 y = torch.from_numpy(y)
@@ -1238,11 +1307,17 @@ def _packed_experts_mlp_class():
         """The gated MLPs of the experts of one MoE layer: three batches of `count` experts, gate and up (n, k), down (k_out, n).
         INFERENCE ONLY.  forward(x, group_rows): x (T, k) bf16, group e owning rows [group_rows[e], group_rows[e + 1]) → (T, k_out):
         glu_grouped (kernel "fused") into bf16, then linear_grouped_wide with the down batch.  The batches are resolved once, here; on hip
-        the arenas, their tables and the one plan workspace both launches use stay on the device.  T = 0 gives the empty result."""
+        the arenas, their tables and the one plan workspace both launches use stay on the device.  T = 0 gives the empty result.
+        decode_max_rows: None, that route at every T; a positive number, a forward with T <= decode_max_rows goes through
+        glu_grouped_skinny into bf16 and linear_grouped(kernel="walk") with the down batch instead (the skinny family's sums, which may
+        differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows."""
 
-        def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", backend: Optional[str] = None):
+        def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", backend: Optional[str] = None,
+                     decode_max_rows: Optional[int] = None):
             super().__init__()
             _check_act(act)
+            if decode_max_rows is not None and (isinstance(decode_max_rows, bool) or not isinstance(decode_max_rows, int) or decode_max_rows <= 0):
+                raise MtqError(f"decode_max_rows must be None or a positive int, got {decode_max_rows!r}")
             if out_dtype not in ("float32", "bfloat16"):
                 raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
             gate, up, down = (_resolve_batch(b) for b in (gate_pts, up_pts, down_pts))
@@ -1254,15 +1329,23 @@ def _packed_experts_mlp_class():
             if self.backend not in BACKENDS:
                 raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
             self._workspace = None
+            self._decode_workspace = None
             if self.backend == "hip":
                 from . import hip_backend as hb
 
                 _need_glu(hb, "PackedExpertsMLP")    # refused here, not at the first forward
+                if decode_max_rows is not None:
+                    _need_glu_skinny(hb, "PackedExpertsMLP(decode_max_rows=...)")
                 if not hb.has_packed_linear_wide_grouped():
                     raise MtqError("PackedExpertsMLP needs mtq_packed_linear_wide_grouped, which this build of libmtq_hip.so lacks")
                 gate, up, down = (batch_to_device(b) for b in (gate, up, down))
                 need = hb.packed_glu_wide_grouped_workspace_bytes(1, gate.count, gate.rows, gate.cols)   # a function of count alone
                 self._workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
+                if decode_max_rows is not None:      # one buffer for both decode launches: each is done with it before the next starts
+                    need = max(hb.packed_glu_skinny_grouped_workspace_bytes(decode_max_rows, gate.count, gate.rows, gate.cols),
+                               hb.packed_linear_skinny_grouped_workspace_bytes(decode_max_rows, down.count, down.rows, down.cols))
+                    self._decode_workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
+            self.decode_max_rows = decode_max_rows
             self.gate, self.up, self.down, self.act, self.out_dtype = gate, up, down, act, out_dtype
             self.count, self.in_features, self.hidden_features, self.out_features = gate.count, gate.cols, gate.rows, down.rows
 
@@ -1274,6 +1357,12 @@ def _packed_experts_mlp_class():
         def forward(self, x, group_rows):
             if x.dim() != 2 or x.shape[1] != self.in_features:
                 raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
+            if self.decode_max_rows is not None and x.shape[0] <= self.decode_max_rows:
+                h = glu_grouped_skinny(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend,
+                                       workspace=self._decode_workspace)
+                y = linear_grouped(h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend, workspace=self._decode_workspace,
+                                   kernel="walk")
+                return y if _is_torch(y) else torch.from_numpy(y)
             h = glu_grouped(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="fused",
                             workspace=self._workspace)
             y = linear_grouped_wide(h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend, workspace=self._workspace)
