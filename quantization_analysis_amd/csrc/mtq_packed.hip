@@ -20,11 +20,11 @@
 //   packed_linear_skinny_kernel               the same product for m <= 32: one wave per (K slice, tile row), W straight to registers.
 //   packed_linear_skinny_grouped_kernel       that wave's work for every expert of an arena over the expert's own rows of X, one launch:
 //       for decode-sized groups (a group above 32 rows is walked in chunks and re-reads W; the block kernel is the route for large m).
-//   packed_grouped_plan_kernel, packed_linear_skinny_grouped_chunked_kernel
+//   packed_grouped_plan_kernel<32>, packed_linear_skinny_grouped_chunked_kernel
 //                                             the same product and bits with a wave per 32-row chunk of a group, for hot experts: the
 //       groups' chunk counts are prefix-summed on the device before the launch and each wave finds its group by a search of that prefix.
 //   packed_linear_wide_kernel                 the block kernel's bits from a 128 × 128 block whose waves decode whole tiles: for m >= 64.
-//   packed_grouped_wide_plan_kernel, packed_linear_wide_grouped_kernel
+//   packed_grouped_plan_kernel<128>, packed_linear_wide_grouped_kernel
 //                                             that block for every expert of an arena over the expert's own rows, one launch: the groups'
 //       128-row block counts are prefix-summed on the device and each workgroup finds its group by the chunked kernel's search.
 //   packed_glu_wide_kernel, packed_glu_wide_grouped_kernel, glu_combine_kernel
@@ -39,6 +39,9 @@
 //       that is read with the transposed LDS read (ds_read_b64_tr_b16); bit for bit the block kernel on the transposed weight.
 //   packed_matmul_skinny_kernel               that product for m <= 32: one wave per (K slice, tile column), each tile through a
 //       wave-private [32 k][32 n] LDS image and the transposed read; bit for bit the skinny linear kernel on the transposed weight.
+//
+// The four wide kernels are frames around one block function, wide_block; the six skinny kernels around one wave's run, skinny_run, and one
+// epilogue, store_lane_rows; all of them read a tensor through a PackedStream and guard a blob with stream_at.
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
 // blob does not fit is not written (pack), not stored (unpack) or read as zeros (linear).
@@ -820,32 +823,69 @@ __device__ __forceinline__ void store_y(void *__restrict__ yv, int64_t at, float
     else static_cast<float *>(yv)[at] = v;
 }
 
-template <bool BF16OUT>
-__global__ __launch_bounds__(64 * kSkinnyWaves) void packed_linear_skinny_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx,
-                                                                                  int x_vec, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
-                                                                                  const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets,
-                                                                                  int64_t N, int64_t tiles_h, int64_t tiles_w, int split,
-                                                                                  const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy,
-                                                                                  float *__restrict__ ws)
+// One tensor's stream as the wave that reads it holds it, for every kernel below: a single tensor, or one expert of an arena
+// (pack_tiles_batched's tables).
+struct PackedStream {
+    const uint8_t *packed;                           // the tensor's stream, or the arena
+    const int8_t *map;                               // the tensor's (the expert's) tables
+    const uint32_t *off;
+    uint64_t base, limit;                            // units: the blobs of this tensor lie in [base, limit)
+};
+
+__device__ __forceinline__ PackedStream tensor_stream(const uint8_t *packed, uint64_t packed_bytes, const int8_t *map, const uint32_t *offsets)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
-    if (unit >= tiles_h * split) return;             // wave-uniform; the kernel has no barrier
-    const int64_t s = unit / tiles_h, tr = unit % tiles_h;   // the waves of a workgroup share a slice of X
-    const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
-    const int row = lane & 31, half = lane >> 5, gi = 2 * row + half;
+    return {packed, map, offsets, 0, packed_bytes / kUnit};
+}
 
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+__device__ __forceinline__ PackedStream arena_stream(const uint8_t *packed, uint64_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                                     const uint64_t *bases, int64_t e, int64_t tiles)
+{
+    return {packed, maps + e * tiles, offsets + e * (tiles + 1), bases[e], std::min<uint64_t>(bases[e + 1], packed_bytes / kUnit)};
+}
 
+// tile_at's answer for a tile of code f at unit o of the stream, the guard made in units against [base, limit).  For a single tensor
+// (base = 0, limit = packed_bytes / 64) this is tile_at's byte guard: every offset and every blob size is a multiple of 64, so
+// 64 o + size > packed_bytes exactly when o + size / 64 > packed_bytes / 64.
+__device__ __forceinline__ TileAt stream_at(const PackedStream &st, int f, uint32_t o)
+{
+    TileAt a;
+    const uint32_t size = packed_tile_bytes(f);
+    const uint64_t pos = st.base + o;                // base <= limit < 2^58 where it counts
+    a.off = pos * kUnit;
+    a.f = (size == 0u || st.base > st.limit || pos + size / kUnit > st.limit) ? -1 : f;
+    return a;
+}
+
+// What a skinny wave does with a decoded group: W (n, k) feeds it to the MFMAs as the B operand as it is.
+struct FeedDirect {
+    static constexpr bool kGroupIsKRow = false;
+    __device__ __forceinline__ void operator()(int, const uint4 &xl, const uint4 &xh, const uint4 &lo, const uint4 &hi, f32x16 &acc) const
+    {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl), as_bf16x8(lo), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh), as_bf16x8(hi), acc, 0, 0, 0);
+    }
+};
+
+// A skinny wave's run: tiles t0 + c * tstep, c in [c0, c1), of one stream into one accumulator, X rows [0, M) at the K positions 32 c ...
+// The map codes and offsets of up to 64 tiles of the run are fetched with one load (a lane each) and handed out with readlane; the loads
+// of kSkinnyRing tiles (group gi of W, and X) are issued before the first is decoded; a blob is checked wave-uniformly (stream_at) before
+// it is touched; decode_skinny, then `feed` (two MFMAs per tile, ascending K).  `lane` hands out, (row, half, gi) address: the grouped
+// kernel forms the latter anew per chunk.  Feed::kGroupIsKRow: group gi is k-row gi / 2 of its tile, zeros at or past K.
+template <typename Feed>
+__device__ __forceinline__ void skinny_run(f32x16 &acc, const Feed &feed, const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx,
+                                           int x_vec, const PackedStream &st, int64_t t0, int64_t tstep, int64_t c0, int64_t c1, int lane, int row,
+                                           int half, int gi)
+{
+    const uint8_t *__restrict__ packed = st.packed;
+    const int8_t *__restrict__ map = st.map;
+    const uint32_t *__restrict__ off = st.off;
     for (int64_t cb = c0; cb < c1; cb += 64) {
         const int cnt = (int)std::min<int64_t>(64, c1 - cb);
-        int mf = -1, mo = 0;                         // lane i: map code and offset of tile cb + i
+        int mf = -1, mo = 0;                         // lane i: map code and offset of tile cb + i of the run
         if (lane < cnt) {
-            const int64_t t = tr * tiles_w + cb + lane;
+            const int64_t t = t0 + (cb + lane) * tstep;
             mf = map[t];
-            mo = (int)offsets[t];
+            mo = (int)off[t];
         }
         for (int b = 0; b < cnt; b += kSkinnyRing) {
             GroupRaw g[kSkinnyRing];
@@ -859,10 +899,10 @@ __global__ __launch_bounds__(64 * kSkinnyWaves) void packed_linear_skinny_kernel
                 xl[j] = make_uint4(0u, 0u, 0u, 0u);
                 xh[j] = xl[j];
                 if (i < cnt) {
-                    const int f = __builtin_amdgcn_readlane(mf, i);
-                    a.off = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(mo, i) * kUnit;
-                    const uint32_t size = packed_tile_bytes(f);
-                    a.f = (size == 0u || a.off + size > packed_bytes) ? -1 : f;
+                    a = stream_at(st, __builtin_amdgcn_readlane(mf, i), (uint32_t)__builtin_amdgcn_readlane(mo, i));
+                    if constexpr (Feed::kGroupIsKRow) {
+                        if ((cb + i) * kTile + (gi >> 1) >= K) a.f = -1;   // this lane's k-row
+                    }
                     load_x16(x, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
                 }
                 load_group(packed, a, gi, g[j]);
@@ -874,30 +914,68 @@ __global__ __launch_bounds__(64 * kSkinnyWaves) void packed_linear_skinny_kernel
                     decode_skinny(g[j], y);
                     uint4 lo, hi;
                     pack_halves(y, lo, hi);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(lo), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(hi), acc, 0, 0, 0);
+                    feed(j, xl[j], xh[j], lo, hi, acc);
                 }
             }
         }
     }
+}
+
+// A skinny lane's 16 accumulators are rows mu + 4 half, mu = (r&3) + 8(r>>2), of one column of a 32-row chunk: those below M go to
+// dst[at + mu * ld], `at` the lane's own part of the address, so that what varies with r is uniform.  PARTIAL: dst is an f32 workspace
+// slice and takes the sums as they are; otherwise dst is Y and takes them with the bias.
+template <bool BF16OUT, bool PARTIAL>
+__device__ __forceinline__ void store_lane_rows(const f32x16 &acc, int64_t M, int half, void *__restrict__ dst, int64_t at, int64_t ld, float bv)
+{
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int mu = (r & 3) + 8 * (r >> 2);
+        if (mu + 4 * half >= M) continue;
+        if constexpr (PARTIAL) static_cast<float *>(dst)[at + mu * ld] = acc[r];
+        else store_y<BF16OUT>(dst, at + mu * ld, acc[r] + bv);
+    }
+}
+
+// split == 1: rows row0 .. of Y with the bias value bv; otherwise rows row0 .. of slice s of ws [split][T][N]
+template <bool BF16OUT>
+__device__ __forceinline__ void store_skinny(const f32x16 &acc, int64_t M, int half, int64_t row0, int64_t n, int split, float bv,
+                                             void *__restrict__ yv, int64_t ldy, float *__restrict__ ws, int64_t s, int64_t T, int64_t N)
+{
+    const int64_t mh = row0 + 4 * half;
+    if (split == 1) store_lane_rows<BF16OUT, false>(acc, M, half, yv, mh * ldy + n, ldy, bv);
+    else store_lane_rows<false, true>(acc, M, half, ws, (s * T + mh) * N + n, N, 0.0f);
+}
+
+__device__ __forceinline__ f32x16 zero16()
+{
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    return acc;
+}
+
+template <bool BF16OUT>
+__global__ __launch_bounds__(64 * kSkinnyWaves) void packed_linear_skinny_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx,
+                                                                                  int x_vec, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+                                                                                  const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets,
+                                                                                  int64_t N, int64_t tiles_h, int64_t tiles_w, int split,
+                                                                                  const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy,
+                                                                                  float *__restrict__ ws)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= tiles_h * split) return;             // wave-uniform; the kernel has no barrier
+    const int64_t s = unit / tiles_h, tr = unit % tiles_h;   // the waves of a workgroup share a slice of X
+    const int row = lane & 31, half = lane >> 5;
+
+    f32x16 acc = zero16();
+    skinny_run(acc, FeedDirect(), x, M, K, ldx, x_vec, tensor_stream(packed, packed_bytes, map, offsets), tr * tiles_w, 1, s * tiles_w / split,
+               (s + 1) * tiles_w / split, lane, row, half, 2 * row + half);
 
     // lane's outputs are (m = (r&3) + 8(r>>2) + 4·half, n = 32·tr + row)
     const int64_t n = tr * kTile + row;
     if (n >= N) return;
-    if (split == 1) {
-        const float bv = bias ? bias[n] : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t m = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[r] + bv);
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t m = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (m < M) ws[(s * M + m) * N + n] = acc[r];
-        }
-    }
+    store_skinny<BF16OUT>(acc, M, half, 0, n, split, split == 1 && bias ? bias[n] : 0.0f, yv, ldy, ws, s, M, N);
 }
 
 // Y[m][n] = ((p0 + p1) + ... + p_{split-1}) + b: ascending slices from slice 0, the bias last, one rounding for a bf16 Y.
@@ -972,6 +1050,32 @@ size_t skinny_workspace(int64_t m, int64_t n, int split_eff)
 // next stores into that image behind them.  Two images per wave (4 KB; 16 KB a workgroup) alternate by tile.
 constexpr int kMmsImage = kTile * kMmPitch;          // bf16 per image: [32 k][32 n]
 
+// W (k, n): the group goes through the wave's image `j & 1` and comes back as two B operands by the transposed read.
+struct FeedTransposed {
+    static constexpr bool kGroupIsKRow = true;
+    uint16_t *st;                                    // where this lane stores its group, in image 0
+    const uint16_t *rd;                              // where its transposed reads start, in image 0
+    int up;                                          // this lane stores its upper 16 bytes first
+    __device__ __forceinline__ void operator()(int j, const uint4 &xl, const uint4 &xh, const uint4 &lo, const uint4 &hi, f32x16 &acc) const
+    {
+        uint16_t *dst = st + (j & 1) * kMmsImage;
+        *reinterpret_cast<uint4 *>(dst + 8 * up) = make_uint4(up ? hi.x : lo.x, up ? hi.y : lo.y, up ? hi.z : lo.z, up ? hi.w : lo.w);
+        *reinterpret_cast<uint4 *>(dst + 8 * (up ^ 1)) = make_uint4(up ? lo.x : hi.x, up ? lo.y : hi.y, up ? lo.z : hi.z, up ? lo.w : hi.w);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        const uint16_t *src = rd + (j & 1) * kMmsImage;
+        const i16x4 b0 = lds_read_tr16(src), b1 = lds_read_tr16(src + 4 * kMmPitch);         // k + 0..3, k + 4..7
+        const i16x4 b2 = lds_read_tr16(src + 8 * kMmPitch), b3 = lds_read_tr16(src + 12 * kMmPitch);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const i16x8 blo = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+        const i16x8 bhi = __builtin_shufflevector(b2, b3, 0, 1, 2, 3, 4, 5, 6, 7);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl), __builtin_bit_cast(bf16x8, blo), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh), __builtin_bit_cast(bf16x8, bhi), acc, 0, 0, 0);
+    }
+};
+
 template <bool BF16OUT>
 __global__ __launch_bounds__(64 * kSkinnyWaves) void packed_matmul_skinny_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx,
                                                                                   int x_vec, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
@@ -985,91 +1089,23 @@ __global__ __launch_bounds__(64 * kSkinnyWaves) void packed_matmul_skinny_kernel
     const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
     if (unit >= tiles_nw * split) return;            // wave-uniform; the kernel has no workgroup barrier
     const int64_t s = unit / tiles_nw, tc = unit % tiles_nw;   // the waves of a workgroup share a slice of X
-    const int64_t r0 = s * tiles_kh / split, r1 = (s + 1) * tiles_kh / split;
     const int row = lane & 31, half = lane >> 5;
 
     uint16_t *img = lds + wave * (2 * kMmsImage);
-    const int up = (lane >> 2) & 1;                  // this lane stores its upper 16 bytes first
-    uint16_t *st = img + lane * kGroup;
-    const uint16_t *rd = img + (kGroup * half + ((lane >> 2) & 3)) * kMmPitch + kGroup * ((lane >> 4) & 1) + 4 * (lane & 3);
+    FeedTransposed feed;
+    feed.st = img + lane * kGroup;
+    feed.rd = img + (kGroup * half + ((lane >> 2) & 3)) * kMmPitch + kGroup * ((lane >> 4) & 1) + 4 * (lane & 3);
+    feed.up = (lane >> 2) & 1;
 
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-
-    for (int64_t rb = r0; rb < r1; rb += 64) {
-        const int cnt = (int)std::min<int64_t>(64, r1 - rb);
-        int mf = -1, mo = 0;                         // lane i: map code and offset of tile (rb + i, tc)
-        if (lane < cnt) {
-            const int64_t t = (rb + lane) * tiles_nw + tc;
-            mf = map[t];
-            mo = (int)offsets[t];
-        }
-        for (int b = 0; b < cnt; b += kSkinnyRing) {
-            GroupRaw g[kSkinnyRing];
-            uint4 xl[kSkinnyRing], xh[kSkinnyRing];
-#pragma unroll
-            for (int j = 0; j < kSkinnyRing; ++j) {
-                const int i = b + j;                 // uniform
-                TileAt a;
-                a.off = 0;
-                a.f = -1;
-                xl[j] = make_uint4(0u, 0u, 0u, 0u);
-                xh[j] = xl[j];
-                if (i < cnt) {
-                    const int f = __builtin_amdgcn_readlane(mf, i);
-                    a.off = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(mo, i) * kUnit;
-                    const uint32_t size = packed_tile_bytes(f);
-                    const bool absent = size == 0u || a.off + size > packed_bytes || (rb + i) * kTile + (lane >> 1) >= K;   // the last: this lane's k-row
-                    a.f = absent ? -1 : f;
-                    load_x16(x, M, K, ldx, x_vec, row, (rb + i) * kTile + kGroup * half, xl[j], xh[j]);
-                }
-                load_group(packed, a, lane, g[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < kSkinnyRing; ++j) {
-                if (b + j < cnt) {
-                    uint32_t y[kGroup];
-                    decode_skinny(g[j], y);
-                    uint4 lo, hi;
-                    pack_halves(y, lo, hi);
-                    uint16_t *dst = st + (j & 1) * kMmsImage;
-                    *reinterpret_cast<uint4 *>(dst + 8 * up) = make_uint4(up ? hi.x : lo.x, up ? hi.y : lo.y, up ? hi.z : lo.z, up ? hi.w : lo.w);
-                    *reinterpret_cast<uint4 *>(dst + 8 * (up ^ 1)) = make_uint4(up ? lo.x : hi.x, up ? lo.y : hi.y, up ? lo.z : hi.z, up ? lo.w : hi.w);
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    const uint16_t *src = rd + (j & 1) * kMmsImage;
-                    const i16x4 b0 = lds_read_tr16(src), b1 = lds_read_tr16(src + 4 * kMmPitch);         // k + 0..3, k + 4..7
-                    const i16x4 b2 = lds_read_tr16(src + 8 * kMmPitch), b3 = lds_read_tr16(src + 12 * kMmPitch);
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    const i16x8 blo = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    const i16x8 bhi = __builtin_shufflevector(b2, b3, 0, 1, 2, 3, 4, 5, 6, 7);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), __builtin_bit_cast(bf16x8, blo), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), __builtin_bit_cast(bf16x8, bhi), acc, 0, 0, 0);
-                }
-            }
-        }
-    }
+    // the run is tile column tc over the slice's tile rows: tiles tiles_nw apart (a strided gather of the tables), group `lane`
+    f32x16 acc = zero16();
+    skinny_run(acc, feed, x, M, K, ldx, x_vec, tensor_stream(packed, packed_bytes, map, offsets), tc, tiles_nw, s * tiles_kh / split,
+               (s + 1) * tiles_kh / split, lane, row, half, lane);
 
     // lane's outputs are (m = (r&3) + 8(r>>2) + 4·half, n = 32·tc + row)
     const int64_t n = tc * kTile + row;
     if (n >= N) return;
-    if (split == 1) {
-        const float bv = bias ? bias[n] : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t m = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[r] + bv);
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t m = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (m < M) ws[(s * M + m) * N + n] = acc[r];
-        }
-    }
+    store_skinny<BF16OUT>(acc, M, half, 0, n, split, split == 1 && bias ? bias[n] : 0.0f, yv, ldy, ws, s, M, N);
 }
 
 // ---- grouped skinny linear: the experts of one arena (pack_tiles_batched's tables), each over its own rows of X, in one launch.
@@ -1107,87 +1143,20 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_linear_skinny_gro
     const int64_t tr = unit % tiles_h, se = unit / tiles_h, e = se % count, s = se / count;
     const GroupRows gr = group_rows_of(group_rows, e, T);
     if (gr.r1 == gr.r0) return;                      // nothing of this expert is read
-    const int64_t tiles = (int64_t)tiles_h * tiles_w;
-    const int8_t *map = maps + e * tiles;
-    const uint32_t *off = offsets + e * (tiles + 1);
-    const uint64_t base = bases[e], limit = std::min<uint64_t>(bases[e + 1], packed_bytes / kUnit);   // units
+    const PackedStream st = arena_stream(packed, packed_bytes, maps, offsets, bases, e, (int64_t)tiles_h * tiles_w);
     const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
 
     for (int64_t row0 = gr.r0; row0 < gr.r1; row0 += kTile) {
         int lv = lane;
         asm volatile("" : "+v"(lv));                 // the lane's addresses are formed per chunk, not kept in registers across chunks
-        const int row = lv & 31, half = lv >> 5, gi = 2 * row + half;
+        const int row = lv & 31, half = lv >> 5;
         const int64_t n = tr * kTile + row;
         const int64_t M = std::min<int64_t>(kTile, gr.r1 - row0);
-        const uint16_t *xc = x + row0 * ldx;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        f32x16 acc = zero16();
+        skinny_run(acc, FeedDirect(), x + row0 * ldx, M, K, ldx, x_vec, st, tr * tiles_w, 1, c0, c1, lane, row, half, 2 * row + half);
 
-        for (int64_t cb = c0; cb < c1; cb += 64) {
-            const int cnt = (int)std::min<int64_t>(64, c1 - cb);
-            int mf = -1, mo = 0;                     // lane i: map code and offset of tile cb + i
-            if (lane < cnt) {
-                const int64_t t = tr * tiles_w + cb + lane;
-                mf = map[t];
-                mo = (int)off[t];
-            }
-            for (int b = 0; b < cnt; b += kSkinnyRing) {
-                GroupRaw g[kSkinnyRing];
-                uint4 xl[kSkinnyRing], xh[kSkinnyRing];
-#pragma unroll
-                for (int j = 0; j < kSkinnyRing; ++j) {
-                    const int i = b + j;             // uniform
-                    TileAt a;
-                    a.off = 0;
-                    a.f = -1;
-                    xl[j] = make_uint4(0u, 0u, 0u, 0u);
-                    xh[j] = xl[j];
-                    if (i < cnt) {
-                        const int f = __builtin_amdgcn_readlane(mf, i);
-                        const uint64_t at = base + (uint32_t)__builtin_amdgcn_readlane(mo, i);   // base <= limit < 2^58 where it counts
-                        const uint32_t size = packed_tile_bytes(f);
-                        a.off = at * kUnit;
-                        a.f = (size == 0u || base > limit || at + size / kUnit > limit) ? -1 : f;
-                        load_x16(xc, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
-                    }
-                    load_group(packed, a, gi, g[j]);
-                }
-#pragma unroll
-                for (int j = 0; j < kSkinnyRing; ++j) {
-                    if (b + j < cnt) {
-                        uint32_t y[kGroup];
-                        decode_skinny(g[j], y);
-                        uint4 lo, hi;
-                        pack_halves(y, lo, hi);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(lo), acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(hi), acc, 0, 0, 0);
-                    }
-                }
-            }
-        }
-
-        // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row): the lane's own part of the address first, so that what
-        // varies with r is uniform
-        if (n < N) {
-            const int64_t mh = row0 + 4 * half;
-            if (split == 1) {
-                const float bv = bias ? bias[e * ldb + n] : 0.0f;
-                const int64_t at = mh * ldy + n;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int mu = (r & 3) + 8 * (r >> 2);
-                    if (mu + 4 * half < M) store_y<BF16OUT>(yv, at + mu * ldy, acc[r] + bv);
-                }
-            } else {
-                float *wl = ws + (s * T + mh) * N + n;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int mu = (r & 3) + 8 * (r >> 2);
-                    if (mu + 4 * half < M) wl[mu * N] = acc[r];
-                }
-            }
-        }
+        // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row)
+        if (n < N) store_skinny<BF16OUT>(acc, M, half, row0, n, split, split == 1 && bias ? bias[e * ldb + n] : 0.0f, yv, ldy, ws, s, T, N);
     }
 }
 
@@ -1224,13 +1193,15 @@ __global__ __launch_bounds__(256) void skinny_grouped_reduce_kernel(const float 
 // The wave finds its group by search, not from a per-chunk table: cstart is count + 1 words whatever T is, a table would be `slots`
 // words written by a plan kernel that walks them; the search is wave-uniform (scalar loads) down to a window of 64 entries, which one
 // load, a lane each, and a ballot finish - for count <= 64 that one load is the whole search.
-// On its chunk the wave issues the loads and MFMAs of the kernel above for (expert, chunk, slice) in the same order: the same bits.
+// On its chunk the wave calls skinny_run and store_skinny as the kernel above does for (expert, chunk, slice): the same bits.
 
-// cstart[0 .. count], by one workgroup: thread k sums the chunk counts of groups [k * per, (k + 1) * per), the workgroup scans the 256
-// sums, and a second pass over the same run writes the prefix (packed_bases_kernel's pattern).  Sums are 64-bit and stored saturated at
-// INT32_MAX, above every slot number, so the prefix stays nondecreasing whatever group_rows holds.
+// start[0 .. count], by one workgroup, for units of ROWS rows (32: the chunks of this kernel, cstart; 128: the blocks of the grouped wide
+// kernels, bstart): thread k sums the unit counts of groups [k * per, (k + 1) * per), the workgroup scans the 256 sums, and a second
+// pass over the same run writes the prefix (packed_bases_kernel's pattern).  Sums are 64-bit and stored saturated at INT32_MAX, above
+// every slot number, so the prefix stays nondecreasing whatever group_rows holds.
+template <int ROWS>
 __global__ __launch_bounds__(256) void packed_grouped_plan_kernel(const int32_t *__restrict__ group_rows, int count, int T,
-                                                                  int32_t *__restrict__ cstart)
+                                                                  int32_t *__restrict__ start)
 {
     __shared__ unsigned long long lds[4];
     const int64_t per = ((int64_t)count + 255) / 256;
@@ -1238,16 +1209,30 @@ __global__ __launch_bounds__(256) void packed_grouped_plan_kernel(const int32_t 
     unsigned long long sum = 0ull;
     for (int64_t e = i0; e < i1; ++e) {
         const GroupRows gr = group_rows_of(group_rows, e, T);
-        sum += (unsigned long long)((gr.r1 - gr.r0 + kTile - 1) / kTile);
+        sum += (unsigned long long)((gr.r1 - gr.r0 + ROWS - 1) / ROWS);
     }
     unsigned long long total;
     unsigned long long run = block_exclusive_scan(sum, lds, total);
     for (int64_t e = i0; e < i1; ++e) {
-        cstart[e] = (int32_t)std::min<unsigned long long>(run, INT32_MAX);
+        start[e] = (int32_t)std::min<unsigned long long>(run, INT32_MAX);
         const GroupRows gr = group_rows_of(group_rows, e, T);
-        run += (unsigned long long)((gr.r1 - gr.r0 + kTile - 1) / kTile);
+        run += (unsigned long long)((gr.r1 - gr.r0 + ROWS - 1) / ROWS);
     }
-    if (threadIdx.x == 0) cstart[count] = (int32_t)std::min<unsigned long long>(total, INT32_MAX);
+    if (threadIdx.x == 0) start[count] = (int32_t)std::min<unsigned long long>(total, INT32_MAX);
+}
+
+// The group of slot `slot` (below start[count]): the last e with start[e] <= slot.  Wave-uniform (scalar loads) down to a window of 64
+// entries, which one load, a lane each, and a ballot finish.
+__device__ __forceinline__ int group_of_slot(const int32_t *__restrict__ start, int count, int slot, int lane)
+{
+    int lo = 0, hi = count;                          // start[lo] <= slot < start[hi] throughout
+    while (hi - lo > 64) {
+        const int mid = lo + (hi - lo) / 2;
+        if (start[mid] <= slot) lo = mid;
+        else hi = mid;
+    }
+    const int at = lo + 1 + lane;
+    return lo + (int)__popcll(__ballot(at < hi && start[at] <= slot));
 }
 
 template <bool BF16OUT>
@@ -1263,95 +1248,22 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_linear_skinny_gro
     const int64_t tr = unit % tiles_h, sc = unit / tiles_h, s = sc / slots;
     const int c = (int)(sc % slots);
     if (c >= cstart[count]) return;                  // a surplus slot: nothing else is read
-
-    // the group of chunk c: the last e with cstart[e] <= c.  cstart[lo] <= c < cstart[hi] throughout
-    int lo = 0, hi = count;
-    while (hi - lo > 64) {
-        const int mid = lo + (hi - lo) / 2;
-        if (cstart[mid] <= c) lo = mid;
-        else hi = mid;
-    }
-    const int at = lo + 1 + lane;
-    const int e = lo + (int)__popcll(__ballot(at < hi && cstart[at] <= c));
+    const int e = group_of_slot(cstart, count, c, lane);
     const GroupRows gr = group_rows_of(group_rows, e, T);
     const int64_t row0 = gr.r0 + (int64_t)(c - cstart[e]) * kTile;
     if (row0 >= gr.r1) return;                       // never for a prefix this launch's plan kernel wrote
-    const int64_t tiles = (int64_t)tiles_h * tiles_w;
-    const int8_t *map = maps + e * tiles;
-    const uint32_t *off = offsets + e * (tiles + 1);
-    const uint64_t base = bases[e], limit = std::min<uint64_t>(bases[e + 1], packed_bytes / kUnit);   // units
-    const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
+    const PackedStream st = arena_stream(packed, packed_bytes, maps, offsets, bases, e, (int64_t)tiles_h * tiles_w);
 
-    const int row = lane & 31, half = lane >> 5, gi = 2 * row + half;
+    const int row = lane & 31, half = lane >> 5;
     const int64_t n = tr * kTile + row;
     const int64_t M = std::min<int64_t>(kTile, gr.r1 - row0);
-    const uint16_t *xc = x + row0 * ldx;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-
-    for (int64_t cb = c0; cb < c1; cb += 64) {
-        const int cnt = (int)std::min<int64_t>(64, c1 - cb);
-        int mf = -1, mo = 0;                         // lane i: map code and offset of tile cb + i
-        if (lane < cnt) {
-            const int64_t t = tr * tiles_w + cb + lane;
-            mf = map[t];
-            mo = (int)off[t];
-        }
-        for (int b = 0; b < cnt; b += kSkinnyRing) {
-            GroupRaw g[kSkinnyRing];
-            uint4 xl[kSkinnyRing], xh[kSkinnyRing];
-#pragma unroll
-            for (int j = 0; j < kSkinnyRing; ++j) {
-                const int i = b + j;                 // uniform
-                TileAt a;
-                a.off = 0;
-                a.f = -1;
-                xl[j] = make_uint4(0u, 0u, 0u, 0u);
-                xh[j] = xl[j];
-                if (i < cnt) {
-                    const int f = __builtin_amdgcn_readlane(mf, i);
-                    const uint64_t pos = base + (uint32_t)__builtin_amdgcn_readlane(mo, i);   // base <= limit < 2^58 where it counts
-                    const uint32_t size = packed_tile_bytes(f);
-                    a.off = pos * kUnit;
-                    a.f = (size == 0u || base > limit || pos + size / kUnit > limit) ? -1 : f;
-                    load_x16(xc, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
-                }
-                load_group(packed, a, gi, g[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < kSkinnyRing; ++j) {
-                if (b + j < cnt) {
-                    uint32_t y[kGroup];
-                    decode_skinny(g[j], y);
-                    uint4 wl, wh;
-                    pack_halves(y, wl, wh);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(wl), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(wh), acc, 0, 0, 0);
-                }
-            }
-        }
-    }
+    f32x16 acc = zero16();
+    skinny_run(acc, FeedDirect(), x + row0 * ldx, M, K, ldx, x_vec, st, tr * tiles_w, 1, s * tiles_w / split, (s + 1) * tiles_w / split, lane, row,
+               half, 2 * row + half);
 
     // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row)
     if (n >= N) return;
-    const int64_t mh = row0 + 4 * half;
-    if (split == 1) {
-        const float bv = bias ? bias[e * ldb + n] : 0.0f;
-        const int64_t to = mh * ldy + n;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int mu = (r & 3) + 8 * (r >> 2);
-            if (mu + 4 * half < M) store_y<BF16OUT>(yv, to + mu * ldy, acc[r] + bv);
-        }
-    } else {
-        float *wl = ws + (s * T + mh) * N + n;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int mu = (r & 3) + 8 * (r >> 2);
-            if (mu + 4 * half < M) wl[mu * N] = acc[r];
-        }
-    }
+    store_skinny<BF16OUT>(acc, M, half, row0, n, split, split == 1 && bias ? bias[e * ldb + n] : 0.0f, yv, ldy, ws, s, T, N);
 }
 
 // ---- wide linear (m above the decode range): packed_linear_kernel's bits from a 128 × 128 block.
@@ -1371,39 +1283,52 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_linear_skinny_gro
 // end: packed_linear_kernel's sequence for that output, operand for operand, so the result is that kernel's bit for bit.
 constexpr int kWideBM = 128, kWideBN = 128;
 
+constexpr int kWideImage = (kWideBM + kWideBN) * kLdk;   // one LDS image: the X block and four tile-row slots of W
+
 template <int V>
 struct Tag {                                         // a compile-time integer as an argument: a register set's parity
     static constexpr int value = V;
 };
 
-// The second launch bound is HIP's minimum of waves per SIMD, not workgroups per CU: a workgroup here is one wave per SIMD, so 2 is
-// what lets two workgroups share a CU and caps the kernel at 256 VGPRs, which it uses to the last: re-read `make report` on any edit.
-template <bool XV, bool BF16OUT>
-__global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
-    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
-    const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N, int64_t tiles_h, int64_t tiles_w,
-    const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy)
+// A 64-bit value every lane of the wave holds alike, into scalar registers.
+__device__ __forceinline__ uint64_t uniform64(uint64_t v)
 {
-    constexpr int BM = kWideBM, MT = BM / 64, XP = BM * 8 / kThreads;   // a wave's 32-row MFMA blocks; pieces of 8 bf16 of the X block per thread
-    constexpr int kImage = (BM + kWideBN) * kLdk;
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kImage];
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+// The 128-row block of every wide kernel: rows [m0, min(m0 + 128, M)) of x / y, M the row limit of every access.  Wave `wave` stages
+// slot `wave` of the W part of the image (rows 32 wave ..) from tile row wtr of the stream st, which with its tables and limits is
+// uniform over the wave and lives in scalar registers; wave (wm, wn) multiplies slots 2 wn and 2 wn + 1 into acc[mt][0] and acc[mt][1].
+// The frame chooses what the slots are, and GLU the epilogue that goes with the choice:
+//   linear  slot w is tile row n0 / 32 + w of one stream: a lane's two accumulators are two column tiles, n0 + 64 wn + 32 nt + lane % 32,
+//           one bias.
+//   GLU     slot w is hidden tile row n0 / 32 + (w >> 1), from the gate stream when w is even and from the up stream when w is odd: the
+//           two accumulators are the gate's and the up's output at the SAME column n0 + 32 wn + lane % 32, so glu_value is lane-local.
+// Launched with bounds (kThreads, 2): the second is HIP's minimum of waves per SIMD, not workgroups per CU; a workgroup here is one wave
+// per SIMD, so 2 is what lets two workgroups share a CU and caps the kernels at 256 VGPRs, which this function uses to the last:
+// re-read `make report` on any edit.
+template <bool GLU, bool XV, bool BF16OUT>
+__device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uint16_t *__restrict__ x, int64_t m0, int64_t M, int64_t K,
+                                           int64_t ldx, const PackedStream &st, int64_t wtr, int64_t n0, int64_t N, int64_t tiles_h,
+                                           int64_t tiles_w, const float *__restrict__ bias, const float *__restrict__ bias_up, int act,
+                                           void *__restrict__ yv, int64_t ldy, int wave)
+{
+    constexpr int BM = kWideBM, MT = BM / 64, XP = BM * 8 / kThreads, kImage = kWideImage;   // a wave's 32-row MFMA blocks; pieces of 8 bf16 of the X block per thread
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wm = wave >> 1, wn = wave & 1;
-    const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
-    const int64_t bm = blockIdx.x / nblocks, bn = blockIdx.x % nblocks;
-    const int64_t m0 = bm * BM, n0 = bn * kWideBN;
     const int64_t steps = (K + kBK - 1) / kBK;
+    const uint8_t *__restrict__ packed = st.packed;
+    const int8_t *__restrict__ map = st.map;
+    const uint32_t *__restrict__ off = st.off;
 
     f32x16 acc[MT][2];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
+        for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = zero16();
 
-    const int64_t wtr = (n0 >> 5) + wave;            // the wave's tile row
     uint4 xr[2][XP];                                 // register set p holds the steps of parity p
     GroupRaw wr[2][2];
     int tf[2];                                       // map code and offset of the wave's two tiles of the step after the last one loaded,
@@ -1415,23 +1340,24 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
             const bool there = wtr < tiles_h && wtc < tiles_w;
             const int64_t t = there ? wtr * tiles_w + wtc : 0;               // tile 0 is always there: the loads are unconditional
             const int f = map[t];
-            const uint32_t o = offsets[t];
+            const uint32_t o = off[t];
             tf[i] = there ? f : -1;
             to[i] = there ? o : 0u;
         }
     };
     // load_group for a whole tile by one wave (lane = group), with two loads whatever the tile is: every step issues the same
     // number of loads on every path, which is what a counted wait for an earlier step's registers needs (the compiler does not
-    // emit one yet: the kernel's head comment).
-    // A tile that is not there reads bytes of the first 320 of the stream instead (they are there: the entry checks packed_bytes
-    // against 320 bytes per tile) and keeps f < 0, which decodes as zeros.
+    // emit one yet: the wide section's head comment).
+    // A tile that is not there reads bytes of the first 320 of `packed`, the stream's or the ARENA's head (they are there: the entry
+    // checks packed_bytes against 320 bytes per tile), not of a group's own stream, which a cut-short `bases` may not own, and keeps
+    // f < 0, which decodes as zeros.
     auto load_tile = [&](const TileAt &a, GroupRaw &g) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) g.w[i] = 0u;
         g.E = 0u;
         g.f = a.f;
         const int f = __builtin_amdgcn_readfirstlane(a.f);                   // uniform over the wave
-        const uint8_t *blob = packed + (f < 0 ? 0 : __builtin_amdgcn_readfirstlane((uint32_t)(a.off / kUnit)) * (uint64_t)kUnit);
+        const uint8_t *blob = packed + (f < 0 ? 0 : uniform64(a.off));
         if (f == 0) {
             const uint4 *q = reinterpret_cast<const uint4 *>(blob + lane * 32);
             const uint4 lo = q[0], hi = q[1];
@@ -1450,26 +1376,19 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
             g.w[0] = *reinterpret_cast<const uint32_t *>(blob + kExpBytes + lane * 4);
         }
     };
-    auto located = [&](int i) __attribute__((always_inline)) {   // tile_at's answer from the fetched pair
-        TileAt a;
-        const uint32_t size = packed_tile_bytes(tf[i]);
-        a.off = (uint64_t)to[i] * kUnit;
-        a.f = (size == 0u || a.off + size > packed_bytes) ? -1 : tf[i];
-        return a;
-    };
     auto load_step = [&](auto par, int64_t s) __attribute__((always_inline)) {
         constexpr int p = decltype(par)::value;
         const int64_t k0 = s * kBK;
-        const TileAt at[2] = {located(0), located(1)};
+        const TileAt ta[2] = {stream_at(st, tf[0], to[0]), stream_at(st, tf[1], to[1])};   // the fetched pair, guarded
         fetch_tables(s + 1);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) load_tile(at[i], wr[p][i]);
+        for (int i = 0; i < 2; ++i) load_tile(ta[i], wr[p][i]);
 #pragma unroll
         for (int j = 0; j < XP; ++j) {               // columns past K and rows past M are zeros, never read
             const int q = tid + kThreads * j, row = q >> 3, c8 = (q & 7) * 8;
             const int64_t gm = m0 + row, gk = k0 + c8;
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if constexpr (XV) {                      // K % 8 == 0: a piece is inside or outside; the load is of a piece that is inside
+            if constexpr (XV) {                      // K % 8 == 0: a piece is inside or outside; the load is of a piece inside (m0 <= M - 1)
                 const bool inside = gm < M && gk < K;
                 const uint4 got = *reinterpret_cast<const uint4 *>(x + (gm < M ? gm : M - 1) * ldx + (gk < K ? gk : K - 8));
                 if (inside) v = got;
@@ -1477,13 +1396,13 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
                 const uint16_t *src = x + gm * ldx + gk;
                 uint32_t h[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) h[e] = gk + e < K ? (uint32_t)src[e] : 0u;
+                for (int c = 0; c < 8; ++c) h[c] = gk + c < K ? (uint32_t)src[c] : 0u;
                 v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
             }
             xr[p][j] = v;
         }
     };
-    // register set p → image `img`: tile i of the wave's tile row (rows 32 wave .. of the W part), and X pieces [j0, j1)
+    // register set p → image `img`: tile i of the wave's slot (rows 32 wave .. of the W part), and X pieces [j0, j1)
     auto stage_w = [&](auto par, int i, uint16_t *img) __attribute__((always_inline)) {
         constexpr int p = decltype(par)::value;
         uint32_t y[kGroup];
@@ -1502,7 +1421,7 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
             *reinterpret_cast<uint4 *>(img + (q >> 3) * kLdk + (q & 7) * 8) = xr[p][j];
         }
     };
-    // MFMA group kk of a step: the 16 K positions 16 kk .. of the images xs / ws, 2 MT MFMAs
+    // MFMA group kk of a step: the 16 K positions 16 kk .. of the images xs / ws, 2 MT MFMAs; nt = 0 is slot 2 wn, nt = 1 slot 2 wn + 1
     auto mfma_group = [&](const uint16_t *xs, const uint16_t *ws, int kk) __attribute__((always_inline)) {
         const int koff = kk * 16 + 8 * (lane >> 5);
         bf16x8 b[2];
@@ -1557,67 +1476,94 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
         for (int kk = 0; kk < kBK / 16; ++kk) mfma_group(lds, lds + BM * kLdk, kk);
     }
 
-    // epilogue: lane's outputs are (m0 + 32 MT·wm + 32 mt + (r&3) + 8(r>>2) + 4(lane>>5), n0 + 64·wn + 32 nt + (lane&31))
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        const int64_t n = n0 + 64 * wn + 32 * nt + (lane & 31);
-        if (n >= N) continue;
-        const float b = bias ? bias[n] : 0.0f;
+    // epilogue: lane's rows are m0 + 32 MT·wm + 32 mt + (r&3) + 8(r>>2) + 4(lane>>5); the bias is added as the block kernel adds it (+0
+    // without one), glu_value is the one place the activation is computed
+    if constexpr (GLU) {
+        const int64_t n = n0 + 32 * wn + (lane & 31);
+        if (n >= N) return;
+        const float bg = bias ? bias[n] : 0.0f, bu = bias_up ? bias_up[n] : 0.0f;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int64_t m = m0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[mt][nt][r] + b);
+                if (m < M) store_y<BF16OUT>(yv, m * ldy + n, glu_value(acc[mt][0][r] + bg, acc[mt][1][r] + bu, act));
             }
+    } else {
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const int64_t n = n0 + 64 * wn + 32 * nt + (lane & 31);
+            if (n >= N) continue;
+            const float b = bias ? bias[n] : 0.0f;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int64_t m = m0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[mt][nt][r] + b);
+                }
+        }
     }
+}
+
+template <bool XV, bool BF16OUT>
+__global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+    const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N, int64_t tiles_h, int64_t tiles_w,
+    const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
+    const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kWideBN;
+    wide_block<false, XV, BF16OUT>(lds, x, bm * kWideBM, M, K, ldx, tensor_stream(packed, packed_bytes, map, offsets), (n0 >> 5) + wave, n0, N,
+                                   tiles_h, tiles_w, bias, nullptr, 0, yv, ldy, wave);
 }
 
 // ---- grouped wide linear: packed_linear_wide_kernel's block for every expert of an arena over the expert's own rows, one launch.
 //
 // The 128-row blocks of all groups are numbered through, as the chunked kernel numbers 32-row chunks: group e owns blocks
 // [bstart[e], bstart[e + 1]), bstart the exclusive prefix sum of ceil(rows_e / 128) over the clamped groups, written by
-// packed_grouped_wide_plan_kernel on the same stream before this kernel.  The grid is slots × ceil(N / 128) workgroups, the column block
+// packed_grouped_plan_kernel<128> on the same stream before this kernel.  The grid is slots × ceil(N / 128) workgroups, the column block
 // fastest; slots is the host's bound on bstart[count], formed from (T, count) alone: floor((T + 127 min(count, T)) / 128).  A workgroup
 // whose slot is at or past bstart[count] returns before any other load and before any barrier; blocks at or past `slots` (overlapping
-// groups of a decreasing group_rows only) are not computed.  The group of a slot is found by the chunked kernel's search, by every wave
-// alike: the group, its rows, its tables and its stream are uniform over the workgroup and live in scalar registers.
-// On its block the workgroup does what packed_linear_wide_kernel does for x[r0:r1] and expert e's stream and tables at row block
-// (slot - bstart[e]): M is the group's end r1 (every row limit, the clamped 16-byte X loads included), a blob is checked against the
-// group's own stream and against packed_bytes, an absent tile's unconditional loads read the arena's first 320 bytes.  The same loads,
-// decode and MFMAs in the same order: that kernel's bits, which are the block kernel's.
+// groups of a decreasing group_rows only) are not computed.  The group of a slot is found by the chunked kernel's search
+// (group_of_slot), by every wave alike: the group, its rows, its tables and its stream are uniform over the workgroup and live in
+// scalar registers.
+// On its block the workgroup calls wide_block as packed_linear_wide_kernel does, for x[r0:r1] and expert e's stream and tables at row
+// block (slot - bstart[e]): M is the group's end r1 (every row limit, the clamped 16-byte X loads included), a blob is checked against
+// the group's own stream and against packed_bytes, an absent tile's unconditional loads read the arena's first 320 bytes.  The same
+// function, so that kernel's bits, which are the block kernel's.
 
-// bstart[0 .. count] by one workgroup: packed_grouped_plan_kernel with 128-row blocks for 32-row chunks.
-__global__ __launch_bounds__(256) void packed_grouped_wide_plan_kernel(const int32_t *__restrict__ group_rows, int count, int T,
-                                                                       int32_t *__restrict__ bstart)
+// What the grouped wide frames share: block `slot` is rows [m0, min(m0 + 128, M)) of group e, all uniform over the workgroup and in
+// scalar registers.  False for a surplus slot, after the load of bstart[count] alone: the frame returns, before any barrier.
+struct GroupBlock {
+    int e;
+    int64_t m0, M;
+};
+
+__device__ __forceinline__ bool group_block(const int32_t *__restrict__ bstart, int count, int slot, const int32_t *__restrict__ group_rows, int T,
+                                            int lane, GroupBlock &b)
 {
-    __shared__ unsigned long long lds[4];
-    const int64_t per = ((int64_t)count + 255) / 256;
-    const int64_t i0 = std::min<int64_t>((int64_t)threadIdx.x * per, count), i1 = std::min<int64_t>(i0 + per, count);
-    unsigned long long sum = 0ull;
-    for (int64_t e = i0; e < i1; ++e) {
-        const GroupRows gr = group_rows_of(group_rows, e, T);
-        sum += (unsigned long long)((gr.r1 - gr.r0 + kWideBM - 1) / kWideBM);
-    }
-    unsigned long long total;
-    unsigned long long run = block_exclusive_scan(sum, lds, total);
-    for (int64_t e = i0; e < i1; ++e) {
-        bstart[e] = (int32_t)std::min<unsigned long long>(run, INT32_MAX);
-        const GroupRows gr = group_rows_of(group_rows, e, T);
-        run += (unsigned long long)((gr.r1 - gr.r0 + kWideBM - 1) / kWideBM);
-    }
-    if (threadIdx.x == 0) bstart[count] = (int32_t)std::min<unsigned long long>(total, INT32_MAX);
+    if (slot >= bstart[count]) return false;
+    b.e = __builtin_amdgcn_readfirstlane(group_of_slot(bstart, count, slot, lane));
+    const GroupRows gr = group_rows_of(group_rows, b.e, T);
+    const int64_t r0 = __builtin_amdgcn_readfirstlane((int)gr.r0);           // 0 <= r0 <= M <= T
+    b.M = __builtin_amdgcn_readfirstlane((int)gr.r1);
+    b.m0 = r0 + (int64_t)kWideBM * (slot - __builtin_amdgcn_readfirstlane(bstart[b.e]));
+    return b.m0 < b.M;                               // never false for a prefix this launch's plan kernel wrote
 }
 
-// A 64-bit value every lane of the wave holds alike, into scalar registers.
-__device__ __forceinline__ uint64_t uniform64(uint64_t v)
+// arena_stream with its limits in scalar registers
+__device__ __forceinline__ PackedStream arena_stream_uniform(const uint8_t *packed, uint64_t packed_bytes, const int8_t *maps,
+                                                             const uint32_t *offsets, const uint64_t *bases, int64_t e, int64_t tiles)
 {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-    return ((uint64_t)hi << 32) | lo;
+    PackedStream st = arena_stream(packed, packed_bytes, maps, offsets, bases, e, tiles);
+    st.base = uniform64(st.base);
+    st.limit = uniform64(st.limit);
+    return st;
 }
 
-// 256 VGPRs at two waves per SIMD, as packed_linear_wide_kernel: re-read `make report` on any edit.
 template <bool XV, bool BF16OUT>
 __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_grouped_kernel(
     const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
@@ -1625,206 +1571,15 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_grouped_kernel
     const uint64_t *__restrict__ bases, int count, int64_t N, int64_t tiles_h, int64_t tiles_w, const float *__restrict__ bias, int64_t ldb,
     void *__restrict__ yv, int64_t ldy)
 {
-    constexpr int BM = kWideBM, MT = BM / 64, XP = BM * 8 / kThreads;
-    constexpr int kImage = (BM + kWideBN) * kLdk;
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kImage];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
-    const int slot = (int)(blockIdx.x / nblocks);
-    const int64_t bn = blockIdx.x % nblocks;
-    if (slot >= bstart[count]) return;               // a surplus slot: nothing else is read; uniform over the workgroup, before any barrier
-
-    // the group of block `slot`: the last e with bstart[e] <= slot.  bstart[lo] <= slot < bstart[hi] throughout
-    int lo = 0, hi = count;
-    while (hi - lo > 64) {
-        const int mid = lo + (hi - lo) / 2;
-        if (bstart[mid] <= slot) lo = mid;
-        else hi = mid;
-    }
-    const int at = lo + 1 + lane;
-    const int e = __builtin_amdgcn_readfirstlane(lo + (int)__popcll(__ballot(at < hi && bstart[at] <= slot)));
-    const GroupRows gr = group_rows_of(group_rows, e, T);
-    const int64_t r0 = __builtin_amdgcn_readfirstlane((int)gr.r0), M = __builtin_amdgcn_readfirstlane((int)gr.r1);   // 0 <= r0 <= M <= T
-    const int64_t m0 = r0 + (int64_t)BM * (slot - __builtin_amdgcn_readfirstlane(bstart[e]));
-    if (m0 >= M) return;                             // never for a prefix this launch's plan kernel wrote
-    const int64_t n0 = bn * kWideBN;
-    const int64_t steps = (K + kBK - 1) / kBK;
-    const int64_t tiles = tiles_h * tiles_w;
-    const int8_t *map = maps + e * tiles;
-    const uint32_t *off = offsets + e * (tiles + 1);
-    const uint64_t base = uniform64(bases[e]), limit = uniform64(std::min<uint64_t>(bases[e + 1], packed_bytes / kUnit));   // units
-
-    f32x16 acc[MT][2];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-
-    const int64_t wtr = (n0 >> 5) + wave;            // the wave's tile row
-    uint4 xr[2][XP];                                 // register set p holds the steps of parity p
-    GroupRaw wr[2][2];
-    int tf[2];                                       // as packed_linear_wide_kernel: fetched a step before they are looked at
-    uint32_t to[2];
-    auto fetch_tables = [&](int64_t s) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int64_t wtc = 2 * s + i;
-            const bool there = wtr < tiles_h && wtc < tiles_w;
-            const int64_t t = there ? wtr * tiles_w + wtc : 0;               // the group's tile 0 is always there: the loads are unconditional
-            const int f = map[t];
-            const uint32_t o = off[t];
-            tf[i] = there ? f : -1;
-            to[i] = there ? o : 0u;
-        }
-    };
-    // packed_linear_wide_kernel's load_tile.  A tile that is not there reads bytes of the first 320 of the ARENA (they are there: the
-    // entry checks packed_bytes against 320 bytes per tile), not of the group's stream, which a cut-short `bases` may not own.
-    auto load_tile = [&](const TileAt &a, GroupRaw &g) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) g.w[i] = 0u;
-        g.E = 0u;
-        g.f = a.f;
-        const int f = __builtin_amdgcn_readfirstlane(a.f);                   // uniform over the wave
-        const uint8_t *blob = packed + (f < 0 ? 0 : uniform64(a.off));
-        if (f == 0) {
-            const uint4 *q = reinterpret_cast<const uint4 *>(blob + lane * 32);
-            const uint4 lo = q[0], hi = q[1];
-            g.w[0] = lo.x; g.w[1] = lo.y; g.w[2] = lo.z; g.w[3] = lo.w;
-            g.w[4] = hi.x; g.w[5] = hi.y; g.w[6] = hi.z; g.w[7] = hi.w;
-        } else if (f == 1) {
-            g.E = blob[lane];
-            const uint4 v = *reinterpret_cast<const uint4 *>(blob + kExpBytes + lane * 16);
-            g.w[0] = v.x; g.w[1] = v.y; g.w[2] = v.z; g.w[3] = v.w;
-        } else if (f == 2) {
-            g.E = blob[lane];
-            const uint2 v = *reinterpret_cast<const uint2 *>(blob + kExpBytes + lane * 8);
-            g.w[0] = v.x; g.w[1] = v.y;
-        } else {
-            g.E = blob[lane];
-            g.w[0] = *reinterpret_cast<const uint32_t *>(blob + kExpBytes + lane * 4);
-        }
-    };
-    auto located = [&](int i) __attribute__((always_inline)) {   // the chunked kernel's guard on the fetched pair, in units
-        TileAt a;
-        const uint32_t size = packed_tile_bytes(tf[i]);
-        const uint64_t pos = base + to[i];           // base <= limit < 2^58 where it counts
-        a.off = pos * kUnit;
-        a.f = (size == 0u || base > limit || pos + size / kUnit > limit) ? -1 : tf[i];
-        return a;
-    };
-    auto load_step = [&](auto par, int64_t s) __attribute__((always_inline)) {
-        constexpr int p = decltype(par)::value;
-        const int64_t k0 = s * kBK;
-        const TileAt ta[2] = {located(0), located(1)};
-        fetch_tables(s + 1);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) load_tile(ta[i], wr[p][i]);
-#pragma unroll
-        for (int j = 0; j < XP; ++j) {               // columns past K and rows past the group's end are zeros, never read
-            const int q = tid + kThreads * j, row = q >> 3, c8 = (q & 7) * 8;
-            const int64_t gm = m0 + row, gk = k0 + c8;
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if constexpr (XV) {                      // K % 8 == 0: the load is of a piece inside the group's rows (m0 <= M - 1)
-                const bool inside = gm < M && gk < K;
-                const uint4 got = *reinterpret_cast<const uint4 *>(x + (gm < M ? gm : M - 1) * ldx + (gk < K ? gk : K - 8));
-                if (inside) v = got;
-            } else if (gm < M && gk < K) {
-                const uint16_t *src = x + gm * ldx + gk;
-                uint32_t h[8];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) h[c] = gk + c < K ? (uint32_t)src[c] : 0u;
-                v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
-            }
-            xr[p][j] = v;
-        }
-    };
-    auto stage_w = [&](auto par, int i, uint16_t *img) __attribute__((always_inline)) {
-        constexpr int p = decltype(par)::value;
-        uint32_t y[kGroup];
-        decode_skinny(wr[p][i], y);
-        uint4 lo, hi;
-        pack_halves(y, lo, hi);
-        uint4 *d = reinterpret_cast<uint4 *>(img + (BM + kTile * wave + (lane >> 1)) * kLdk + kTile * i + kGroup * (lane & 1));
-        d[0] = lo;
-        d[1] = hi;
-    };
-    auto stage_x = [&](auto par, int j0, int j1, uint16_t *img) __attribute__((always_inline)) {
-        constexpr int p = decltype(par)::value;
-#pragma unroll
-        for (int j = j0; j < j1; ++j) {
-            const int q = tid + kThreads * j;
-            *reinterpret_cast<uint4 *>(img + (q >> 3) * kLdk + (q & 7) * 8) = xr[p][j];
-        }
-    };
-    auto mfma_group = [&](const uint16_t *xs, const uint16_t *ws, int kk) __attribute__((always_inline)) {
-        const int koff = kk * 16 + 8 * (lane >> 5);
-        bf16x8 b[2];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) b[nt] = *reinterpret_cast<const bf16x8 *>(ws + (64 * wn + 32 * nt + (lane & 31)) * kLdk + koff);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (32 * MT * wm + 32 * mt + (lane & 31)) * kLdk + koff);
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[nt], acc[mt][nt], 0, 0, 0);
-        }
-    };
-    auto step = [&](auto par, int64_t s) __attribute__((always_inline)) {
-        constexpr int cur = decltype(par)::value;
-        const Tag<cur ^ 1> other;
-        const uint16_t *xs = lds + cur * kImage, *ws = xs + BM * kLdk;
-        uint16_t *next = lds + (cur ^ 1) * kImage;
-        const bool more = s + 1 < steps;
-        load_step(par, s + 2 < steps ? s + 2 : steps - 1);
-#pragma unroll
-        for (int kk = 0; kk < kBK / 16; ++kk) {
-            if (!more) {
-                mfma_group(xs, ws, kk);
-            } else if (kk < 2) {
-                mfma_group(xs, ws, kk);
-                stage_w(other, kk, next);
-            } else {
-                mfma_group(xs, ws, kk);
-                stage_x(other, (kk - 2) * (XP / 2), (kk - 1) * (XP / 2), next);
-            }
-        }
-        __syncthreads();
-    };
-
-    fetch_tables(0);
-    load_step(Tag<0>(), 0);
-    load_step(Tag<1>(), steps > 1 ? 1 : 0);
-    stage_w(Tag<0>(), 0, lds);
-    stage_w(Tag<0>(), 1, lds);
-    stage_x(Tag<0>(), 0, XP, lds);
-    __syncthreads();
-    int64_t s = 0;
-    for (; s + 1 < steps; s += 2) {
-        step(Tag<0>(), s);
-        step(Tag<1>(), s + 1);
-    }
-    if (s < steps) {                                 // an odd count's last step: nothing left to load or stage
-#pragma unroll
-        for (int kk = 0; kk < kBK / 16; ++kk) mfma_group(lds, lds + BM * kLdk, kk);
-    }
-
-    // epilogue: lane's outputs are (m0 + 32 MT·wm + 32 mt + (r&3) + 8(r>>2) + 4(lane>>5), n0 + 64·wn + 32 nt + (lane&31)), rows absolute
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        const int64_t n = n0 + 64 * wn + 32 * nt + (lane & 31);
-        if (n >= N) continue;
-        const float b = bias ? bias[e * ldb + n] : 0.0f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t m = m0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[mt][nt][r] + b);
-            }
-    }
+    const int64_t n0 = (blockIdx.x % nblocks) * kWideBN;
+    GroupBlock b;
+    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;
+    const PackedStream st = arena_stream_uniform(packed, packed_bytes, maps, offsets, bases, b.e, tiles_h * tiles_w);
+    wide_block<false, XV, BF16OUT>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + wave, n0, N, tiles_h, tiles_w, bias ? bias + b.e * ldb : nullptr,
+                                   nullptr, 0, yv, ldy, wave);
 }
 
 // ---- gated wide linear (SwiGLU): glu_value(X·Ŵgᵀ + bg, X·Ŵuᵀ + bu) from packed_linear_wide_kernel's step, one launch, one store.
@@ -1840,203 +1595,8 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_grouped_kernel
 // equal since every blob size is a multiple of 64).
 // Bits: each accumulator takes the block kernel's sequence for its projection, the bias is added once in f32 as there, and glu_value
 // (mtq_glu.hpp) is what mtq_glu_combine applies to the two stored f32 results: the unfused route's bits.
-struct GluStream {                                   // one projection's stream as the wave that stages it holds it
-    const uint8_t *packed;                           // the tensor's stream, or the arena
-    const int8_t *map;                               // the tensor's (the expert's) tables
-    const uint32_t *off;
-    uint64_t base, limit;                            // units: the blobs of this tensor lie in [base, limit)
-};
-
 constexpr int kGluBN = 64;                           // hidden columns of a workgroup
-constexpr int kGluImage = (kWideBM + kWideBN) * kLdk;
 
-// The block at rows [m0, min(m0 + 128, M)) of x / y and hidden columns [n0, n0 + 64): M is the row limit of every access.
-template <bool XV, bool BF16OUT>
-__device__ __forceinline__ void glu_wide_block(uint16_t *__restrict__ lds, const uint16_t *__restrict__ x, int64_t m0, int64_t M, int64_t K,
-                                               int64_t ldx, const GluStream &st, int64_t n0, int64_t N, int64_t tiles_h, int64_t tiles_w,
-                                               const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int act,
-                                               void *__restrict__ yv, int64_t ldy, int wave)
-{
-    constexpr int BM = kWideBM, MT = BM / 64, XP = BM * 8 / kThreads, kImage = kGluImage;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int64_t steps = (K + kBK - 1) / kBK;
-    const uint8_t *__restrict__ packed = st.packed;
-    const int8_t *__restrict__ map = st.map;
-    const uint32_t *__restrict__ off = st.off;
-    const uint64_t base = st.base, limit = st.limit;
-
-    f32x16 acc[MT][2];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-
-    const int64_t wtr = (n0 >> 5) + (wave >> 1);     // the hidden tile row of the wave's slot
-    uint4 xr[2][XP];                                 // register set p holds the steps of parity p
-    GroupRaw wr[2][2];
-    int tf[2];                                       // as packed_linear_wide_kernel: fetched a step before they are looked at
-    uint32_t to[2];
-    auto fetch_tables = [&](int64_t s) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int64_t wtc = 2 * s + i;
-            const bool there = wtr < tiles_h && wtc < tiles_w;
-            const int64_t t = there ? wtr * tiles_w + wtc : 0;               // tile 0 is always there: the loads are unconditional
-            const int f = map[t];
-            const uint32_t o = off[t];
-            tf[i] = there ? f : -1;
-            to[i] = there ? o : 0u;
-        }
-    };
-    // packed_linear_wide_grouped_kernel's load_tile.  A tile that is not there reads bytes of the first 320 of `packed` (they are there:
-    // the entry checks each stream's packed_bytes against 320 bytes per tile) and keeps f < 0, which decodes as zeros.
-    auto load_tile = [&](const TileAt &a, GroupRaw &g) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) g.w[i] = 0u;
-        g.E = 0u;
-        g.f = a.f;
-        const int f = __builtin_amdgcn_readfirstlane(a.f);                   // uniform over the wave
-        const uint8_t *blob = packed + (f < 0 ? 0 : uniform64(a.off));
-        if (f == 0) {
-            const uint4 *q = reinterpret_cast<const uint4 *>(blob + lane * 32);
-            const uint4 lo = q[0], hi = q[1];
-            g.w[0] = lo.x; g.w[1] = lo.y; g.w[2] = lo.z; g.w[3] = lo.w;
-            g.w[4] = hi.x; g.w[5] = hi.y; g.w[6] = hi.z; g.w[7] = hi.w;
-        } else if (f == 1) {
-            g.E = blob[lane];
-            const uint4 v = *reinterpret_cast<const uint4 *>(blob + kExpBytes + lane * 16);
-            g.w[0] = v.x; g.w[1] = v.y; g.w[2] = v.z; g.w[3] = v.w;
-        } else if (f == 2) {
-            g.E = blob[lane];
-            const uint2 v = *reinterpret_cast<const uint2 *>(blob + kExpBytes + lane * 8);
-            g.w[0] = v.x; g.w[1] = v.y;
-        } else {
-            g.E = blob[lane];
-            g.w[0] = *reinterpret_cast<const uint32_t *>(blob + kExpBytes + lane * 4);
-        }
-    };
-    auto located = [&](int i) __attribute__((always_inline)) {   // the grouped kernel's guard on the fetched pair, in units
-        TileAt a;
-        const uint32_t size = packed_tile_bytes(tf[i]);
-        const uint64_t pos = base + to[i];           // base <= limit < 2^58 where it counts
-        a.off = pos * kUnit;
-        a.f = (size == 0u || base > limit || pos + size / kUnit > limit) ? -1 : tf[i];
-        return a;
-    };
-    auto load_step = [&](auto par, int64_t s) __attribute__((always_inline)) {
-        constexpr int p = decltype(par)::value;
-        const int64_t k0 = s * kBK;
-        const TileAt ta[2] = {located(0), located(1)};
-        fetch_tables(s + 1);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) load_tile(ta[i], wr[p][i]);
-#pragma unroll
-        for (int j = 0; j < XP; ++j) {               // columns past K and rows past M are zeros, never read
-            const int q = tid + kThreads * j, row = q >> 3, c8 = (q & 7) * 8;
-            const int64_t gm = m0 + row, gk = k0 + c8;
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if constexpr (XV) {                      // K % 8 == 0: the load is of a piece inside the rows (m0 <= M - 1)
-                const bool inside = gm < M && gk < K;
-                const uint4 got = *reinterpret_cast<const uint4 *>(x + (gm < M ? gm : M - 1) * ldx + (gk < K ? gk : K - 8));
-                if (inside) v = got;
-            } else if (gm < M && gk < K) {
-                const uint16_t *src = x + gm * ldx + gk;
-                uint32_t h[8];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) h[c] = gk + c < K ? (uint32_t)src[c] : 0u;
-                v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
-            }
-            xr[p][j] = v;
-        }
-    };
-    auto stage_w = [&](auto par, int i, uint16_t *img) __attribute__((always_inline)) {   // slot `wave`: rows 32 wave .. of the W part
-        constexpr int p = decltype(par)::value;
-        uint32_t y[kGroup];
-        decode_skinny(wr[p][i], y);
-        uint4 lo, hi;
-        pack_halves(y, lo, hi);
-        uint4 *d = reinterpret_cast<uint4 *>(img + (BM + kTile * wave + (lane >> 1)) * kLdk + kTile * i + kGroup * (lane & 1));
-        d[0] = lo;
-        d[1] = hi;
-    };
-    auto stage_x = [&](auto par, int j0, int j1, uint16_t *img) __attribute__((always_inline)) {
-        constexpr int p = decltype(par)::value;
-#pragma unroll
-        for (int j = j0; j < j1; ++j) {
-            const int q = tid + kThreads * j;
-            *reinterpret_cast<uint4 *>(img + (q >> 3) * kLdk + (q & 7) * 8) = xr[p][j];
-        }
-    };
-    // nt = 0: slot 2 wn (gate), nt = 1: slot 2 wn + 1 (up), both of hidden tile row n0 / 32 + wn
-    auto mfma_group = [&](const uint16_t *xs, const uint16_t *ws, int kk) __attribute__((always_inline)) {
-        const int koff = kk * 16 + 8 * (lane >> 5);
-        bf16x8 b[2];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) b[nt] = *reinterpret_cast<const bf16x8 *>(ws + (64 * wn + 32 * nt + (lane & 31)) * kLdk + koff);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (32 * MT * wm + 32 * mt + (lane & 31)) * kLdk + koff);
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[nt], acc[mt][nt], 0, 0, 0);
-        }
-    };
-    auto step = [&](auto par, int64_t s) __attribute__((always_inline)) {
-        constexpr int cur = decltype(par)::value;
-        const Tag<cur ^ 1> other;
-        const uint16_t *xs = lds + cur * kImage, *ws = xs + BM * kLdk;
-        uint16_t *next = lds + (cur ^ 1) * kImage;
-        const bool more = s + 1 < steps;
-        load_step(par, s + 2 < steps ? s + 2 : steps - 1);
-#pragma unroll
-        for (int kk = 0; kk < kBK / 16; ++kk) {
-            if (!more) {
-                mfma_group(xs, ws, kk);
-            } else if (kk < 2) {
-                mfma_group(xs, ws, kk);
-                stage_w(other, kk, next);
-            } else {
-                mfma_group(xs, ws, kk);
-                stage_x(other, (kk - 2) * (XP / 2), (kk - 1) * (XP / 2), next);
-            }
-        }
-        __syncthreads();
-    };
-
-    fetch_tables(0);
-    load_step(Tag<0>(), 0);
-    load_step(Tag<1>(), steps > 1 ? 1 : 0);
-    stage_w(Tag<0>(), 0, lds);
-    stage_w(Tag<0>(), 1, lds);
-    stage_x(Tag<0>(), 0, XP, lds);
-    __syncthreads();
-    int64_t s = 0;
-    for (; s + 1 < steps; s += 2) {
-        step(Tag<0>(), s);
-        step(Tag<1>(), s + 1);
-    }
-    if (s < steps) {                                 // an odd count's last step: nothing left to load or stage
-#pragma unroll
-        for (int kk = 0; kk < kBK / 16; ++kk) mfma_group(lds, lds + BM * kLdk, kk);
-    }
-
-    // epilogue: lane's outputs are (m0 + 32 MT·wm + 32 mt + (r&3) + 8(r>>2) + 4(lane>>5), n0 + 32·wn + (lane&31)); the bias is added as
-    // the block kernel adds it (+0 without one), glu_value is the one place the activation is computed
-    const int64_t n = n0 + 32 * wn + (lane & 31);
-    if (n >= N) return;
-    const float bg = bias_gate ? bias_gate[n] : 0.0f, bu = bias_up ? bias_up[n] : 0.0f;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (m < M) store_y<BF16OUT>(yv, m * ldy + n, glu_value(acc[mt][0][r] + bg, acc[mt][1][r] + bu, act));
-        }
-}
-
-// 256 VGPRs at two waves per SIMD, as packed_linear_wide_kernel: re-read `make report` on any edit.
 template <bool XV, bool BF16OUT>
 __global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_kernel(
     const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ gate, uint64_t gate_bytes,
@@ -2044,23 +1604,19 @@ __global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_kernel(
     const int8_t *__restrict__ up_map, const uint32_t *__restrict__ up_offsets, int64_t N, int64_t tiles_h, int64_t tiles_w,
     const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int act, void *__restrict__ yv, int64_t ldy)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kGluImage];
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
-    const int64_t bm = blockIdx.x / nblocks, bn = blockIdx.x % nblocks;
+    const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kGluBN;
     const bool is_up = wave & 1;                     // the wave's slot: even from the gate stream, odd from the up stream
-    GluStream st;
-    st.packed = is_up ? up : gate;
-    st.map = is_up ? up_map : gate_map;
-    st.off = is_up ? up_offsets : gate_offsets;
-    st.base = 0;
-    st.limit = (is_up ? up_bytes : gate_bytes) / kUnit;
-    glu_wide_block<XV, BF16OUT>(lds, x, bm * kWideBM, M, K, ldx, st, bn * kGluBN, N, tiles_h, tiles_w, bias_gate, bias_up, act, yv, ldy, wave);
+    const PackedStream st = tensor_stream(is_up ? up : gate, is_up ? up_bytes : gate_bytes, is_up ? up_map : gate_map,
+                                          is_up ? up_offsets : gate_offsets);
+    wide_block<true, XV, BF16OUT>(lds, x, bm * kWideBM, M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_h, tiles_w, bias_gate, bias_up, act,
+                                  yv, ldy, wave);
 }
 
-// packed_linear_wide_grouped_kernel's frame around the same block: the plan (bstart, by packed_grouped_wide_plan_kernel), the slot bound,
-// the early return of a surplus workgroup before any other load or barrier, the group search and the clamped rows are that kernel's; the
-// column blocks are of 64 hidden columns.  A blob is checked against its own group's range of its own arena.
+// packed_linear_wide_grouped_kernel's frame with column blocks of 64 hidden columns: a blob is checked against its own group's range of
+// its own arena.
 template <bool XV, bool BF16OUT>
 __global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_grouped_kernel(
     const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
@@ -2069,37 +1625,17 @@ __global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_grouped_kernel(
     const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int64_t N, int64_t tiles_h, int64_t tiles_w,
     const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int64_t ldb, int act, void *__restrict__ yv, int64_t ldy)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kGluImage];
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
-    const int slot = (int)(blockIdx.x / nblocks);
-    const int64_t bn = blockIdx.x % nblocks;
-    if (slot >= bstart[count]) return;               // a surplus slot: nothing else is read; uniform over the workgroup, before any barrier
-
-    // the group of block `slot`: the last e with bstart[e] <= slot.  bstart[lo] <= slot < bstart[hi] throughout
-    int lo = 0, hi = count;
-    while (hi - lo > 64) {
-        const int mid = lo + (hi - lo) / 2;
-        if (bstart[mid] <= slot) lo = mid;
-        else hi = mid;
-    }
-    const int at = lo + 1 + lane;
-    const int e = __builtin_amdgcn_readfirstlane(lo + (int)__popcll(__ballot(at < hi && bstart[at] <= slot)));
-    const GroupRows gr = group_rows_of(group_rows, e, T);
-    const int64_t r0 = __builtin_amdgcn_readfirstlane((int)gr.r0), M = __builtin_amdgcn_readfirstlane((int)gr.r1);   // 0 <= r0 <= M <= T
-    const int64_t m0 = r0 + (int64_t)kWideBM * (slot - __builtin_amdgcn_readfirstlane(bstart[e]));
-    if (m0 >= M) return;                             // never for a prefix this launch's plan kernel wrote
-    const int64_t tiles = tiles_h * tiles_w;
+    const int64_t n0 = (blockIdx.x % nblocks) * kGluBN;
+    GroupBlock b;
+    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;
     const bool is_up = wave & 1;
-    const uint64_t *bases = is_up ? up_bases : gate_bases;
-    GluStream st;
-    st.packed = is_up ? up : gate;
-    st.map = (is_up ? up_maps : gate_maps) + e * tiles;
-    st.off = (is_up ? up_offsets : gate_offsets) + e * (tiles + 1);
-    st.base = uniform64(bases[e]);
-    st.limit = uniform64(std::min<uint64_t>(bases[e + 1], (is_up ? up_bytes : gate_bytes) / kUnit));
-    glu_wide_block<XV, BF16OUT>(lds, x, m0, M, K, ldx, st, bn * kGluBN, N, tiles_h, tiles_w, bias_gate ? bias_gate + e * ldb : nullptr,
-                                bias_up ? bias_up + e * ldb : nullptr, act, yv, ldy, wave);
+    const PackedStream st = arena_stream_uniform(is_up ? up : gate, is_up ? up_bytes : gate_bytes, is_up ? up_maps : gate_maps,
+                                                 is_up ? up_offsets : gate_offsets, is_up ? up_bases : gate_bases, b.e, tiles_h * tiles_w);
+    wide_block<true, XV, BF16OUT>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_h, tiles_w,
+                                  bias_gate ? bias_gate + b.e * ldb : nullptr, bias_up ? bias_up + b.e * ldb : nullptr, act, yv, ldy, wave);
 }
 
 // y[r][c] = glu_value(g[r][c], u[r][c], act): the second half of the unfused route, one thread per element in a grid-stride walk.
@@ -2132,68 +1668,17 @@ __global__ __launch_bounds__(64 * kSkinnyWaves) void packed_glu_skinny_kernel(
     const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
     if (unit >= 2 * tiles_h * split) return;         // wave-uniform; the kernel has no barrier
     const int64_t tr = unit % tiles_h, sp = unit / tiles_h, p = sp & 1, s = sp >> 1;
-    const uint8_t *__restrict__ packed = p ? up : gate;
-    const uint64_t packed_bytes = p ? up_bytes : gate_bytes;
-    const int8_t *__restrict__ map = p ? up_map : gate_map;
-    const uint32_t *__restrict__ offsets = p ? up_offsets : gate_offsets;
-    const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
-    const int row = lane & 31, half = lane >> 5, gi = 2 * row + half;
+    const PackedStream st = tensor_stream(p ? up : gate, p ? up_bytes : gate_bytes, p ? up_map : gate_map, p ? up_offsets : gate_offsets);
+    const int row = lane & 31, half = lane >> 5;
 
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-
-    for (int64_t cb = c0; cb < c1; cb += 64) {
-        const int cnt = (int)std::min<int64_t>(64, c1 - cb);
-        int mf = -1, mo = 0;                         // lane i: map code and offset of tile cb + i
-        if (lane < cnt) {
-            const int64_t t = tr * tiles_w + cb + lane;
-            mf = map[t];
-            mo = (int)offsets[t];
-        }
-        for (int b = 0; b < cnt; b += kSkinnyRing) {
-            GroupRaw g[kSkinnyRing];
-            uint4 xl[kSkinnyRing], xh[kSkinnyRing];
-#pragma unroll
-            for (int j = 0; j < kSkinnyRing; ++j) {
-                const int i = b + j;                 // uniform
-                TileAt a;
-                a.off = 0;
-                a.f = -1;
-                xl[j] = make_uint4(0u, 0u, 0u, 0u);
-                xh[j] = xl[j];
-                if (i < cnt) {
-                    const int f = __builtin_amdgcn_readlane(mf, i);
-                    a.off = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(mo, i) * kUnit;
-                    const uint32_t size = packed_tile_bytes(f);
-                    a.f = (size == 0u || a.off + size > packed_bytes) ? -1 : f;
-                    load_x16(x, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
-                }
-                load_group(packed, a, gi, g[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < kSkinnyRing; ++j) {
-                if (b + j < cnt) {
-                    uint32_t y[kGroup];
-                    decode_skinny(g[j], y);
-                    uint4 lo, hi;
-                    pack_halves(y, lo, hi);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(lo), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(hi), acc, 0, 0, 0);
-                }
-            }
-        }
-    }
+    f32x16 acc = zero16();
+    skinny_run(acc, FeedDirect(), x, M, K, ldx, x_vec, st, tr * tiles_w, 1, s * tiles_w / split, (s + 1) * tiles_w / split, lane, row, half,
+               2 * row + half);
 
     // lane's outputs are (m = (r&3) + 8(r>>2) + 4·half, n = 32·tr + row) of slice s of projection p
     const int64_t n = tr * kTile + row;
     if (n >= N) return;
-    float *wl = ws + (((int64_t)p * split + s) * M + 4 * half) * N + n;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int mu = (r & 3) + 8 * (r >> 2);
-        if (mu + 4 * half < M) wl[mu * N] = acc[r];
-    }
+    store_lane_rows<false, true>(acc, M, half, ws, (((int64_t)p * split + s) * M + 4 * half) * N + n, N, 0.0f);
 }
 
 // One thread per output: g = ((p0 + p1) + ... + p_{split-1}) + bias_gate over the gate's slices in ascending order from slice 0, the
@@ -2235,77 +1720,21 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_skinny_groupe
     const int64_t tr = unit % tiles_h, spe = unit / tiles_h, e = spe % count, sp = spe / count, p = sp & 1, s = sp >> 1;
     const GroupRows gr = group_rows_of(group_rows, e, T);
     if (gr.r1 == gr.r0) return;                      // nothing of this expert is read
-    const int64_t tiles = (int64_t)tiles_h * tiles_w;
-    const uint8_t *__restrict__ packed = p ? up : gate;
-    const int8_t *map = (p ? up_maps : gate_maps) + e * tiles;
-    const uint32_t *off = (p ? up_offsets : gate_offsets) + e * (tiles + 1);
-    const uint64_t *bases = p ? up_bases : gate_bases;
-    const uint64_t base = bases[e], limit = std::min<uint64_t>(bases[e + 1], (p ? up_bytes : gate_bytes) / kUnit);   // units
+    const PackedStream st = arena_stream(p ? up : gate, p ? up_bytes : gate_bytes, p ? up_maps : gate_maps, p ? up_offsets : gate_offsets,
+                                         p ? up_bases : gate_bases, e, (int64_t)tiles_h * tiles_w);
     const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
 
     for (int64_t row0 = gr.r0; row0 < gr.r1; row0 += kTile) {
         int lv = lane;
         asm volatile("" : "+v"(lv));                 // the lane's addresses are formed per chunk, not kept in registers across chunks
-        const int row = lv & 31, half = lv >> 5, gi = 2 * row + half;
+        const int row = lv & 31, half = lv >> 5;
         const int64_t n = tr * kTile + row;
         const int64_t M = std::min<int64_t>(kTile, gr.r1 - row0);
-        const uint16_t *xc = x + row0 * ldx;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-
-        for (int64_t cb = c0; cb < c1; cb += 64) {
-            const int cnt = (int)std::min<int64_t>(64, c1 - cb);
-            int mf = -1, mo = 0;                     // lane i: map code and offset of tile cb + i
-            if (lane < cnt) {
-                const int64_t t = tr * tiles_w + cb + lane;
-                mf = map[t];
-                mo = (int)off[t];
-            }
-            for (int b = 0; b < cnt; b += kSkinnyRing) {
-                GroupRaw g[kSkinnyRing];
-                uint4 xl[kSkinnyRing], xh[kSkinnyRing];
-#pragma unroll
-                for (int j = 0; j < kSkinnyRing; ++j) {
-                    const int i = b + j;             // uniform
-                    TileAt a;
-                    a.off = 0;
-                    a.f = -1;
-                    xl[j] = make_uint4(0u, 0u, 0u, 0u);
-                    xh[j] = xl[j];
-                    if (i < cnt) {
-                        const int f = __builtin_amdgcn_readlane(mf, i);
-                        const uint64_t at = base + (uint32_t)__builtin_amdgcn_readlane(mo, i);   // base <= limit < 2^58 where it counts
-                        const uint32_t size = packed_tile_bytes(f);
-                        a.off = at * kUnit;
-                        a.f = (size == 0u || base > limit || at + size / kUnit > limit) ? -1 : f;
-                        load_x16(xc, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
-                    }
-                    load_group(packed, a, gi, g[j]);
-                }
-#pragma unroll
-                for (int j = 0; j < kSkinnyRing; ++j) {
-                    if (b + j < cnt) {
-                        uint32_t y[kGroup];
-                        decode_skinny(g[j], y);
-                        uint4 lo, hi;
-                        pack_halves(y, lo, hi);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xl[j]), as_bf16x8(lo), acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xh[j]), as_bf16x8(hi), acc, 0, 0, 0);
-                    }
-                }
-            }
-        }
+        f32x16 acc = zero16();
+        skinny_run(acc, FeedDirect(), x + row0 * ldx, M, K, ldx, x_vec, st, tr * tiles_w, 1, c0, c1, lane, row, half, 2 * row + half);
 
         // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row) of slice s of projection p
-        if (n < N) {
-            float *wl = ws + ((((int64_t)p * split + s) * T + row0 + 4 * half) * N + n);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mu = (r & 3) + 8 * (r >> 2);
-                if (mu + 4 * half < M) wl[(int64_t)mu * N] = acc[r];
-            }
-        }
+        if (n < N) store_lane_rows<false, true>(acc, M, half, ws, (((int64_t)p * split + s) * T + row0 + 4 * half) * N + n, N, 0.0f);
     }
 }
 
@@ -2628,19 +2057,65 @@ extern "C" int mtq_packed_matmul(const void *x, int64_t m, int64_t k, int64_t ld
     return check_launch("mtq_packed_matmul");
 }
 
-template <bool XV>
-static void launch_wide(int64_t blocks, hipStream_t st, const uint16_t *xp, int64_t m, int64_t k, int64_t ldx, const uint8_t *pp,
-                        uint64_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t n, int64_t th, int64_t tw, const float *bias,
-                        void *y, int out_dtype, int64_t ldy)
+// One launch of the instantiation that stores a bf16 Y (kt) or an f32 Y (kf)
+template <typename... P, typename... A>
+static void launch_out(int out_dtype, void (*kt)(P...), void (*kf)(P...), dim3 grid, dim3 block, hipStream_t st, A... args)
 {
-    const dim3 grid((unsigned)blocks);
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL((packed_linear_wide_kernel<XV, true>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, pp, packed_bytes, map, offsets, n, th, tw,
-                           bias, y, ldy);
-    else
-        hipLaunchKernelGGL((packed_linear_wide_kernel<XV, false>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, pp, packed_bytes, map, offsets, n, th, tw,
-                           bias, y, ldy);
+    hipLaunchKernelGGL(out_dtype == MTQ_DTYPE_BF16 ? kt : kf, grid, block, 0, st, args...);
 }
+
+// kernel<XV, BF16OUT> of a wide kernel template for (x_vec, out_dtype)
+#define MTQ_WIDE_PAIR(kernel, x_vec) (x_vec) ? kernel<true, true> : kernel<false, true>, (x_vec) ? kernel<true, false> : kernel<false, false>
+
+// whole pieces of 8 bf16 of x by 16-byte loads: every row aligned (a group may start at any row).  The wide kernels also want k % 8 == 0
+// and take any other x (a ragged k included) element by element.
+static bool x_vec_of(const void *x, int64_t ldx) { return reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0; }
+
+// The argument block of the skinny, grouped and wide-grouped entries, checked in the one order they all report in: the pointers, the
+// output type, the entry's shape rule (skinny_shape, grouped_shape, glu_grouped_shape: it fills g), the pitches, then the streams.
+// count == 0: a single tensor, else an arena of count; a gated entry passes both streams, any other its one stream twice.
+struct SplitGrid {
+    int64_t th, tw;                                  // the tile grid of one weight
+    int eff;                                         // the effective split
+};
+
+struct StreamArg {
+    const void *packed;
+    size_t bytes;
+};
+
+template <typename Shape>
+static int gemm_args(bool any_null, int out_dtype, Shape shape, SplitGrid &g, int64_t k, int64_t ldx, int64_t n, int64_t ldy, bool bias_rows,
+                     int64_t ldb, int64_t count, StreamArg a, StreamArg b)
+{
+    if (any_null) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    if (int rc = shape(g)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if (bias_rows && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
+    if (reinterpret_cast<uintptr_t>(a.packed) % 16 != 0 || reinterpret_cast<uintptr_t>(b.packed) % 16 != 0)
+        return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    const uint64_t least = (uint64_t)(std::max<int64_t>(count, 1) * g.th * g.tw) * packed_tile_bytes(MTQ_FMT_BFP2);
+    if (a.bytes < least || b.bytes < least)
+        return fail(MTQ_ERR_INVALID, count ? "packed_bytes is smaller than the streams" : "packed_bytes is smaller than the stream");
+    return MTQ_OK;
+}
+
+// The workspace block: need == 0 asks for none; null_msg says why this entry needs one, `whose` is "split" or "call"
+static int workspace_args(const void *workspace, size_t workspace_bytes, size_t need, const char *null_msg, const char *whose)
+{
+    if (need == 0) return MTQ_OK;
+    if (!workspace) return fail(MTQ_ERR_INVALID, null_msg);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
+    if (workspace_bytes < need)
+        return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this %s needs", workspace_bytes, need, whose);
+    return MTQ_OK;
+}
+
+static const char *const kWsSplit = "workspace is null and this split needs one";
+static const char *const kWsPlan = "workspace is null and the block plan needs one";
+static const char *const kWsGlu = "workspace is null: the partial sums of both projections need one at every split";
 
 extern "C" int mtq_packed_linear_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                                       const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
@@ -2650,12 +2125,10 @@ extern "C" int mtq_packed_linear_wide(const void *x, int64_t m, int64_t k, int64
     const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kWideBN - 1) / kWideBN);
     if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
     if (int rc = require_device()) return rc;
-    // whole pieces of 8 bf16 by 16-byte loads; any other x (a ragged k included) element by element
-    const bool x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0 && k % 8 == 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *xp = static_cast<const uint16_t *>(x);
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
-    (x_vec ? launch_wide<true> : launch_wide<false>)(blocks, st, xp, m, k, ldx, pp, (uint64_t)packed_bytes, map, offsets, n, th, tw, bias, y, out_dtype, ldy);
+    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_linear_wide_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), static_cast<hipStream_t>(stream),
+               static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map, offsets, n, th, tw, bias,
+               y, ldy);
     return check_launch("mtq_packed_linear_wide");
 }
 
@@ -2671,44 +2144,24 @@ extern "C" int mtq_packed_linear_skinny(const void *x, int64_t m, int64_t k, int
                                         const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!x || !packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;
-    int eff;
-    if (int rc = skinny_shape(m, n, k, split, &th, &tw, &eff)) return rc;
-    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
-    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
-    const size_t need = skinny_workspace(m, n, eff);
-    if (need != 0) {
-        if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and this split needs one");
-        if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
-        if (workspace_bytes < need)
-            return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this split needs", workspace_bytes, need);
-    }
-    const int64_t blocks = (th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    SplitGrid g;
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !packed || !map || !offsets || !y, out_dtype,
+                           [&](SplitGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0, w, w))
+        return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(m, n, g.eff), kWsSplit, "split")) return rc;
+    const int64_t blocks = (g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
     if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *xp = static_cast<const uint16_t *>(x);
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
     float *ws = static_cast<float *>(workspace);
-    const dim3 grid((unsigned)blocks), block(64 * kSkinnyWaves);
-    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(packed_linear_skinny_kernel<true>, grid, block, 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th, tw,
-                           eff, bias, y, ldy, ws);
-    else
-        hipLaunchKernelGGL(packed_linear_skinny_kernel<false>, grid, block, 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th, tw,
-                           eff, bias, y, ldy, ws);
-    if (eff > 1) {
+    launch_out(out_dtype, packed_linear_skinny_kernel<true>, packed_linear_skinny_kernel<false>, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), st,
+               static_cast<const uint16_t *>(x), m, k, ldx, (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map,
+               offsets, n, g.th, g.tw, g.eff, bias, y, ldy, ws);
+    if (g.eff > 1) {
         if (int rc = check_launch("mtq_packed_linear_skinny")) return rc;
-        const dim3 rgrid((unsigned)((m * n + 255) / 256));
-        if (out_dtype == MTQ_DTYPE_BF16)
-            hipLaunchKernelGGL(skinny_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
-        else
-            hipLaunchKernelGGL(skinny_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
+        launch_out(out_dtype, skinny_reduce_kernel<true>, skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
+                   m * n, n, g.eff, bias, y, ldy);
     }
     return check_launch("mtq_packed_linear_skinny");
 }
@@ -2727,44 +2180,24 @@ extern "C" int mtq_packed_matmul_skinny(const void *x, int64_t m, int64_t k, int
                                         const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!x || !packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t tn, tk;
-    int eff;
-    if (int rc = skinny_shape(m, n, k, split, &tn, &tk, &eff)) return rc;
-    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
-    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(tn * tk) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
-    const size_t need = skinny_workspace(m, n, eff);
-    if (need != 0) {
-        if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and this split needs one");
-        if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
-        if (workspace_bytes < need)
-            return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this split needs", workspace_bytes, need);
-    }
-    const int64_t blocks = (tn * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !packed || !map || !offsets || !y, out_dtype,
+                           [&](SplitGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0, w, w))
+        return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(m, n, g.eff), kWsSplit, "split")) return rc;
+    const int64_t blocks = (g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
     if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *xp = static_cast<const uint16_t *>(x);
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
     float *ws = static_cast<float *>(workspace);
-    const dim3 grid((unsigned)blocks), block(64 * kSkinnyWaves);
-    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(packed_matmul_skinny_kernel<true>, grid, block, 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, tk, tn,
-                           eff, bias, y, ldy, ws);
-    else
-        hipLaunchKernelGGL(packed_matmul_skinny_kernel<false>, grid, block, 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, tk, tn,
-                           eff, bias, y, ldy, ws);
-    if (eff > 1) {
+    launch_out(out_dtype, packed_matmul_skinny_kernel<true>, packed_matmul_skinny_kernel<false>, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), st,
+               static_cast<const uint16_t *>(x), m, k, ldx, (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map,
+               offsets, n, g.tw, g.th, g.eff, bias, y, ldy, ws);
+    if (g.eff > 1) {
         if (int rc = check_launch("mtq_packed_matmul_skinny")) return rc;
-        const dim3 rgrid((unsigned)((m * n + 255) / 256));
-        if (out_dtype == MTQ_DTYPE_BF16)
-            hipLaunchKernelGGL(skinny_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
-        else
-            hipLaunchKernelGGL(skinny_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias, y, ldy);
+        launch_out(out_dtype, skinny_reduce_kernel<true>, skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
+                   m * n, n, g.eff, bias, y, ldy);
     }
     return check_launch("mtq_packed_matmul_skinny");
 }
@@ -2782,46 +2215,26 @@ extern "C" int mtq_packed_linear_skinny_grouped(const void *x, int64_t total_row
                                                 const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
                                                 int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!x || !group_rows || !packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;
-    int eff;
-    if (int rc = grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return rc;
-    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
-    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
-    if (bias && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
-    const size_t need = skinny_workspace(total_rows, n, eff);
-    if (need != 0) {
-        if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and this split needs one");
-        if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
-        if (workspace_bytes < need)
-            return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this split needs", workspace_bytes, need);
-    }
-    const int64_t blocks = (count * th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    SplitGrid g;
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
+                           bias != nullptr, ldb, count, w, w))
+        return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(total_rows, n, g.eff), kWsSplit, "split")) return rc;
+    const int64_t blocks = (count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
     const int64_t nchunks = (n + 255) / 256;
     if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *xp = static_cast<const uint16_t *>(x);
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
     float *ws = static_cast<float *>(workspace);
-    const dim3 grid((unsigned)blocks), block(64 * kSkinnyWaves);
-    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(packed_linear_skinny_grouped_kernel<true>, grid, block, 0, st, xp, total_rows, k, ldx, x_vec, group_rows, pp,
-                           (uint64_t)packed_bytes, maps, offsets, bases, count, n, th, tw, eff, bias, ldb, y, ldy, ws);
-    else
-        hipLaunchKernelGGL(packed_linear_skinny_grouped_kernel<false>, grid, block, 0, st, xp, total_rows, k, ldx, x_vec, group_rows, pp,
-                           (uint64_t)packed_bytes, maps, offsets, bases, count, n, th, tw, eff, bias, ldb, y, ldy, ws);
-    if (eff > 1) {
+    launch_out(out_dtype, packed_linear_skinny_grouped_kernel<true>, packed_linear_skinny_grouped_kernel<false>, dim3((unsigned)blocks),
+               dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx), group_rows,
+               static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.th, g.tw, g.eff, bias, ldb, y, ldy, ws);
+    if (g.eff > 1) {
         if (int rc = check_launch("mtq_packed_linear_skinny_grouped")) return rc;
-        const dim3 rgrid((unsigned)(count * nchunks));
-        if (out_dtype == MTQ_DTYPE_BF16)
-            hipLaunchKernelGGL(skinny_grouped_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
-        else
-            hipLaunchKernelGGL(skinny_grouped_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
+        launch_out(out_dtype, skinny_grouped_reduce_kernel<true>, skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
+                   st, ws, total_rows, n, g.eff, group_rows, nchunks, bias, ldb, y, ldy);
     }
     return check_launch("mtq_packed_linear_skinny_grouped");
 }
@@ -2847,49 +2260,35 @@ extern "C" int mtq_packed_linear_skinny_grouped_chunked(const void *x, int64_t t
                                                         int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
                                                         void *stream)
 {
-    if (!x || !group_rows || !packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;
-    int eff;
-    if (int rc = grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return rc;
-    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
-    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
-    if (bias && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
-    const size_t plan = grouped_plan_bytes(count), need = plan + skinny_workspace(total_rows, n, eff);
-    if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and the chunk plan needs one at every split");
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
-    if (workspace_bytes < need)
-        return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this call needs", workspace_bytes, need);
+    SplitGrid g;
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
+                           bias != nullptr, ldb, count, w, w))
+        return rc;
+    const size_t plan = grouped_plan_bytes(count);
+    if (int rc = workspace_args(workspace, workspace_bytes, plan + skinny_workspace(total_rows, n, g.eff),
+                                "workspace is null and the chunk plan needs one at every split", "call"))
+        return rc;
     // every chunk of disjoint groups has a slot: a group with rows adds at most 31/32 of a chunk over its rows / 32
     const int64_t slots = (total_rows + 31 * std::min(count, total_rows)) / kTile;
-    const int64_t blocks = (slots * th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    const int64_t blocks = (slots * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
     const int64_t nchunks = (n + 255) / 256;
     if (slots > INT32_MAX || blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *xp = static_cast<const uint16_t *>(x);
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
     int32_t *cstart = static_cast<int32_t *>(workspace);
     float *ws = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + plan);
-    hipLaunchKernelGGL(packed_grouped_plan_kernel, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, cstart);
+    hipLaunchKernelGGL(packed_grouped_plan_kernel<kTile>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, cstart);
     if (int rc = check_launch("mtq_packed_linear_skinny_grouped_chunked")) return rc;
-    const dim3 grid((unsigned)blocks), block(64 * kSkinnyWaves);
-    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(packed_linear_skinny_grouped_chunked_kernel<true>, grid, block, 0, st, xp, total_rows, k, ldx, x_vec, group_rows, cstart,
-                           (int)slots, pp, (uint64_t)packed_bytes, maps, offsets, bases, count, n, th, tw, eff, bias, ldb, y, ldy, ws);
-    else
-        hipLaunchKernelGGL(packed_linear_skinny_grouped_chunked_kernel<false>, grid, block, 0, st, xp, total_rows, k, ldx, x_vec, group_rows, cstart,
-                           (int)slots, pp, (uint64_t)packed_bytes, maps, offsets, bases, count, n, th, tw, eff, bias, ldb, y, ldy, ws);
-    if (eff > 1) {
+    launch_out(out_dtype, packed_linear_skinny_grouped_chunked_kernel<true>, packed_linear_skinny_grouped_chunked_kernel<false>,
+               dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx),
+               group_rows, cstart, (int)slots, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.th, g.tw,
+               g.eff, bias, ldb, y, ldy, ws);
+    if (g.eff > 1) {
         if (int rc = check_launch("mtq_packed_linear_skinny_grouped_chunked")) return rc;
-        const dim3 rgrid((unsigned)(count * nchunks));
-        if (out_dtype == MTQ_DTYPE_BF16)
-            hipLaunchKernelGGL(skinny_grouped_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
-        else
-            hipLaunchKernelGGL(skinny_grouped_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias, ldb, y, ldy);
+        launch_out(out_dtype, skinny_grouped_reduce_kernel<true>, skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
+                   st, ws, total_rows, n, g.eff, group_rows, nchunks, bias, ldb, y, ldy);
     }
     return check_launch("mtq_packed_linear_skinny_grouped_chunked");
 }
@@ -2902,57 +2301,32 @@ extern "C" size_t mtq_packed_linear_wide_grouped_workspace_bytes(int64_t total_r
     return grouped_plan_bytes(count);
 }
 
-template <bool XV>
-static void launch_wide_grouped(int64_t blocks, hipStream_t st, const uint16_t *xp, int64_t total_rows, int64_t k, int64_t ldx,
-                                const int32_t *group_rows, const int32_t *bstart, const uint8_t *pp, uint64_t packed_bytes, const int8_t *maps,
-                                const uint32_t *offsets, const uint64_t *bases, int64_t count, int64_t n, int64_t th, int64_t tw, const float *bias,
-                                int64_t ldb, void *y, int out_dtype, int64_t ldy)
-{
-    const dim3 grid((unsigned)blocks);
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL((packed_linear_wide_grouped_kernel<XV, true>), grid, dim3(kThreads), 0, st, xp, (int)total_rows, k, ldx, group_rows, bstart,
-                           pp, packed_bytes, maps, offsets, bases, (int)count, n, th, tw, bias, ldb, y, ldy);
-    else
-        hipLaunchKernelGGL((packed_linear_wide_grouped_kernel<XV, false>), grid, dim3(kThreads), 0, st, xp, (int)total_rows, k, ldx, group_rows, bstart,
-                           pp, packed_bytes, maps, offsets, bases, (int)count, n, th, tw, bias, ldb, y, ldy);
-}
 
 extern "C" int mtq_packed_linear_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
                                               const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
                                               const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
                                               int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!x || !group_rows || !packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;
-    int eff;
-    if (int rc = grouped_shape(total_rows, count, n, k, 1, &th, &tw, &eff)) return rc;
-    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
-    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
-    if (bias && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
-    const size_t need = grouped_plan_bytes(count);
-    if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and the block plan needs one");
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
-    if (workspace_bytes < need)
-        return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this call needs", workspace_bytes, need);
+    SplitGrid g;
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
+                           bias != nullptr, ldb, count, w, w))
+        return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
     // every block of disjoint groups has a slot: a group with rows adds at most 127/128 of a block over its rows / 128
     const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
     const int64_t blocks = slots * ((n + kWideBN - 1) / kWideBN);
     if (slots > INT32_MAX || blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *xp = static_cast<const uint16_t *>(x);
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
     int32_t *bstart = static_cast<int32_t *>(workspace);
-    hipLaunchKernelGGL(packed_grouped_wide_plan_kernel, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
+    hipLaunchKernelGGL(packed_grouped_plan_kernel<kWideBM>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
     if (int rc = check_launch("mtq_packed_linear_wide_grouped")) return rc;
-    // whole pieces of 8 bf16 by 16-byte loads (a group may start at any row: ldx % 8 == 0 keeps every row aligned); any other x
-    // (a ragged k included) element by element
-    const bool x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0 && k % 8 == 0;
-    (x_vec ? launch_wide_grouped<true> : launch_wide_grouped<false>)(blocks, st, xp, total_rows, k, ldx, group_rows, bstart, pp, (uint64_t)packed_bytes,
-                                                                     maps, offsets, bases, count, n, th, tw, bias, ldb, y, out_dtype, ldy);
+    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_linear_wide_grouped_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), st,
+               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(packed),
+               (uint64_t)packed_bytes, maps, offsets, bases, (int)count, n, g.th, g.tw, bias, ldb, y, ldy);
     return check_launch("mtq_packed_linear_wide_grouped");
 }
 
@@ -2982,20 +2356,6 @@ extern "C" int mtq_glu_combine(const float *g, int64_t ldg, const float *u, int6
     return check_launch("mtq_glu_combine");
 }
 
-template <bool XV>
-static void launch_glu_wide(int64_t blocks, hipStream_t st, const uint16_t *xp, int64_t m, int64_t k, int64_t ldx, const uint8_t *gp,
-                            uint64_t gate_bytes, const int8_t *gate_map, const uint32_t *gate_offsets, const uint8_t *up, uint64_t up_bytes,
-                            const int8_t *up_map, const uint32_t *up_offsets, int64_t n, int64_t th, int64_t tw, const float *bias_gate,
-                            const float *bias_up, int act, void *y, int out_dtype, int64_t ldy)
-{
-    const dim3 grid((unsigned)blocks);
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL((packed_glu_wide_kernel<XV, true>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, gp, gate_bytes, gate_map, gate_offsets, up,
-                           up_bytes, up_map, up_offsets, n, th, tw, bias_gate, bias_up, act, y, ldy);
-    else
-        hipLaunchKernelGGL((packed_glu_wide_kernel<XV, false>), grid, dim3(kThreads), 0, st, xp, m, k, ldx, gp, gate_bytes, gate_map, gate_offsets, up,
-                           up_bytes, up_map, up_offsets, n, th, tw, bias_gate, bias_up, act, y, ldy);
-}
 
 extern "C" int mtq_packed_glu_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
                                    const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
@@ -3009,12 +2369,10 @@ extern "C" int mtq_packed_glu_wide(const void *x, int64_t m, int64_t k, int64_t 
     const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kGluBN - 1) / kGluBN);
     if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
     if (int rc = require_device()) return rc;
-    // whole pieces of 8 bf16 by 16-byte loads; any other x (a ragged k included) element by element
-    const bool x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0 && k % 8 == 0;
-    (x_vec ? launch_glu_wide<true> : launch_glu_wide<false>)(blocks, static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(x), m, k, ldx,
-                                                             static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
-                                                             static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, th, tw,
-                                                             bias_gate, bias_up, act, y, out_dtype, ldy);
+    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_wide_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), static_cast<hipStream_t>(stream),
+               static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
+               static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, th, tw, bias_gate, bias_up, act, y, ldy);
     return check_launch("mtq_packed_glu_wide");
 }
 
@@ -3023,32 +2381,6 @@ extern "C" size_t mtq_packed_glu_wide_grouped_workspace_bytes(int64_t total_rows
     return mtq_packed_linear_wide_grouped_workspace_bytes(total_rows, count, n, k);   // the same plan
 }
 
-namespace {
-struct GluArena {                                    // one projection's arena as the grouped entry is given it
-    const uint8_t *packed;
-    uint64_t bytes;
-    const int8_t *maps;
-    const uint32_t *offsets;
-    const uint64_t *bases;
-};
-}
-
-template <bool XV>
-static void launch_glu_wide_grouped(int64_t blocks, hipStream_t st, const uint16_t *xp, int64_t total_rows, int64_t k, int64_t ldx,
-                                    const int32_t *group_rows, const int32_t *bstart, const GluArena &g, const GluArena &u, int64_t count, int64_t n,
-                                    int64_t th, int64_t tw, const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y,
-                                    int out_dtype, int64_t ldy)
-{
-    const dim3 grid((unsigned)blocks);
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL((packed_glu_wide_grouped_kernel<XV, true>), grid, dim3(kThreads), 0, st, xp, (int)total_rows, k, ldx, group_rows, bstart,
-                           g.packed, g.bytes, g.maps, g.offsets, g.bases, u.packed, u.bytes, u.maps, u.offsets, u.bases, (int)count, n, th, tw,
-                           bias_gate, bias_up, ldb, act, y, ldy);
-    else
-        hipLaunchKernelGGL((packed_glu_wide_grouped_kernel<XV, false>), grid, dim3(kThreads), 0, st, xp, (int)total_rows, k, ldx, group_rows, bstart,
-                           g.packed, g.bytes, g.maps, g.offsets, g.bases, u.packed, u.bytes, u.maps, u.offsets, u.bases, (int)count, n, th, tw,
-                           bias_gate, bias_up, ldb, act, y, ldy);
-}
 
 extern "C" int mtq_packed_glu_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
                                            const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
@@ -3057,25 +2389,14 @@ extern "C" int mtq_packed_glu_wide_grouped(const void *x, int64_t total_rows, in
                                            const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, void *workspace,
                                            size_t workspace_bytes, void *stream)
 {
-    if (!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets || !up_bases || !y)
-        return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;
-    int eff;
-    if (int rc = grouped_shape(total_rows, count, n, k, 1, &th, &tw, &eff)) return rc;
-    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
-    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
-    if ((bias_gate || bias_up) && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
-    if (reinterpret_cast<uintptr_t>(gate_packed) % 16 != 0 || reinterpret_cast<uintptr_t>(up_packed) % 16 != 0)
-        return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    const uint64_t least = (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2);
-    if (gate_bytes < least || up_bytes < least) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
+    SplitGrid g;
+    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
+                               !up_bases || !y,
+                           out_dtype, [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n,
+                           ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
     if (int rc = glu_act(act)) return rc;
-    const size_t need = grouped_plan_bytes(count);
-    if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null and the block plan needs one");
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
-    if (workspace_bytes < need)
-        return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this call needs", workspace_bytes, need);
+    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
     // mtq_packed_linear_wide_grouped's slot bound
     const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
     const int64_t blocks = slots * ((n + kGluBN - 1) / kGluBN);
@@ -3083,26 +2404,17 @@ extern "C" int mtq_packed_glu_wide_grouped(const void *x, int64_t total_rows, in
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int32_t *bstart = static_cast<int32_t *>(workspace);
-    hipLaunchKernelGGL(packed_grouped_wide_plan_kernel, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
+    hipLaunchKernelGGL(packed_grouped_plan_kernel<kWideBM>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
     if (int rc = check_launch("mtq_packed_glu_wide_grouped")) return rc;
-    const bool x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0 && k % 8 == 0;
-    const GluArena ga = {static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases};
-    const GluArena ua = {static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases};
-    (x_vec ? launch_glu_wide_grouped<true> : launch_glu_wide_grouped<false>)(blocks, st, static_cast<const uint16_t *>(x), total_rows, k, ldx,
-                                                                             group_rows, bstart, ga, ua, count, n, th, tw, bias_gate, bias_up, ldb,
-                                                                             act, y, out_dtype, ldy);
+    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_wide_grouped_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), st,
+               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(gate_packed),
+               (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps,
+               up_offsets, up_bases, (int)count, n, g.th, g.tw, bias_gate, bias_up, ldb, act, y, ldy);
     return check_launch("mtq_packed_glu_wide_grouped");
 }
 
 // ---- gated entries for decode: both projections in one split-K launch, the activation in the reduce
-static int glu_skinny_workspace_args(const void *workspace, size_t workspace_bytes, size_t need)
-{
-    if (!workspace) return fail(MTQ_ERR_INVALID, "workspace is null: the partial sums of both projections need one at every split");
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
-    if (workspace_bytes < need)
-        return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this split needs", workspace_bytes, need);
-    return MTQ_OK;
-}
 
 extern "C" size_t mtq_packed_glu_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
 {
@@ -3118,34 +2430,24 @@ extern "C" int mtq_packed_glu_skinny(const void *x, int64_t m, int64_t k, int64_
                                      int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
                                      void *stream)
 {
-    if (!x || !gate_packed || !gate_map || !gate_offsets || !up_packed || !up_map || !up_offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;
-    int eff;
-    if (int rc = skinny_shape(m, n, k, split, &th, &tw, &eff)) return rc;
-    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
-    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
-    if (reinterpret_cast<uintptr_t>(gate_packed) % 16 != 0 || reinterpret_cast<uintptr_t>(up_packed) % 16 != 0)
-        return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    const uint64_t least = (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2);
-    if (gate_bytes < least || up_bytes < least) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
+    SplitGrid g;
+    if (int rc = gemm_args(!x || !gate_packed || !gate_map || !gate_offsets || !up_packed || !up_map || !up_offsets || !y, out_dtype,
+                           [&](SplitGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0,
+                           {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
     if (int rc = glu_act(act)) return rc;
-    if (int rc = glu_skinny_workspace_args(workspace, workspace_bytes, glu_skinny_workspace(m, n, eff))) return rc;
-    const int64_t blocks = (2 * th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(m, n, g.eff), kWsGlu, "split")) return rc;
+    const int64_t blocks = (2 * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
     if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *ws = static_cast<float *>(workspace);
-    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
     hipLaunchKernelGGL(packed_glu_skinny_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), m, k, ldx,
-                       x_vec, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
-                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, th, tw, eff, ws);
+                       (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
+                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, g.th, g.tw, g.eff, ws);
     if (int rc = check_launch("mtq_packed_glu_skinny")) return rc;
-    const dim3 rgrid((unsigned)((m * n + 255) / 256));
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(glu_skinny_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias_gate, bias_up, act, y, ldy);
-    else
-        hipLaunchKernelGGL(glu_skinny_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, m * n, n, eff, bias_gate, bias_up, act, y, ldy);
+    launch_out(out_dtype, glu_skinny_reduce_kernel<true>, glu_skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
+               m * n, n, g.eff, bias_gate, bias_up, act, y, ldy);
     return check_launch("mtq_packed_glu_skinny");
 }
 
@@ -3172,40 +2474,27 @@ extern "C" int mtq_packed_glu_skinny_grouped(const void *x, int64_t total_rows, 
                                              const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y, int out_dtype,
                                              int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets || !up_bases || !y)
-        return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;
-    int eff;
-    if (int rc = glu_grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return rc;
-    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
-    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
-    if ((bias_gate || bias_up) && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
-    if (reinterpret_cast<uintptr_t>(gate_packed) % 16 != 0 || reinterpret_cast<uintptr_t>(up_packed) % 16 != 0)
-        return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    const uint64_t least = (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2);
-    if (gate_bytes < least || up_bytes < least) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
+    SplitGrid g;
+    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
+                               !up_bases || !y,
+                           out_dtype, [&](SplitGrid &s) { return glu_grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx,
+                           n, ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
     if (int rc = glu_act(act)) return rc;
-    if (int rc = glu_skinny_workspace_args(workspace, workspace_bytes, glu_skinny_workspace(total_rows, n, eff))) return rc;
-    const int64_t blocks = (2 * count * th * eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(total_rows, n, g.eff), kWsGlu, "split")) return rc;
+    const int64_t blocks = (2 * count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
     const int64_t nchunks = (n + 255) / 256;
     if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *ws = static_cast<float *>(workspace);
-    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
     hipLaunchKernelGGL(packed_glu_skinny_grouped_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x),
-                       (int)total_rows, (int)k, ldx, x_vec, group_rows, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps,
-                       gate_offsets, gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases, (int)count,
-                       (int)n, (int)th, (int)tw, eff, ws);
+                       (int)total_rows, (int)k, ldx, (int)x_vec_of(x, ldx), group_rows, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes,
+                       gate_maps, gate_offsets, gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases,
+                       (int)count, (int)n, (int)g.th, (int)g.tw, g.eff, ws);
     if (int rc = check_launch("mtq_packed_glu_skinny_grouped")) return rc;
-    const dim3 rgrid((unsigned)(count * nchunks));
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(glu_skinny_grouped_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias_gate, bias_up,
-                           ldb, act, y, ldy);
-    else
-        hipLaunchKernelGGL(glu_skinny_grouped_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, total_rows, n, eff, group_rows, nchunks, bias_gate,
-                           bias_up, ldb, act, y, ldy);
+    launch_out(out_dtype, glu_skinny_grouped_reduce_kernel<true>, glu_skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
+               st, ws, total_rows, n, g.eff, group_rows, nchunks, bias_gate, bias_up, ldb, act, y, ldy);
     return check_launch("mtq_packed_glu_skinny_grouped");
 }
 
