@@ -729,6 +729,22 @@ int mtq_packed_linear_wide(const void *x, int64_t m, int64_t k, int64_t ldx, con
 int mtq_packed_matmul(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                       const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream);
 
+/* mtq_packed_matmul's product from the wide block of mtq_packed_linear_wide, for m above the decode range: the same parameter list,
+ * argument checks, error texts and device guards (m = 0 and n = 0 are refused there: an empty product is the caller's, and the Python
+ * binding returns it without a call).  A workgroup of 4 waves, 2 x 2, owns 128 (M) x 128 (N) outputs and walks K in steps of 64; a
+ * step's block of P̂ is 2 tile rows x 4 tile columns, wave w decodes whole tiles of tile column n0 / 32 + w (a lane the group of its own
+ * number, the format uniform over the wave) and stores each group as it lies into its own [64 k][32 n] LDS sub-image; the B operand is
+ * read from two sub-images with the transposed LDS read of gfx950, two reads per operand.  X staging, two register sets, two LDS
+ * images, loads two steps ahead and one barrier per step are the wide linear kernel's.
+ *
+ * Bit contract: for every input, y equals mtq_packed_matmul's bit for bit, in both output types, with and without bias.  By that
+ * entry's contract it is also mtq_packed_linear_wide / mtq_packed_linear on the all-bf16 packing of unpack(P̂)ᵀ.  It holds by
+ * construction: the same k at the same lane half and element, ascending blocks of 16 K positions, the same K step, zeros at and past k
+ * (in the image, whatever the stream holds there).  No atomics, no workspace, nothing waits on another workgroup: two calls give the
+ * same bits.  Correct for any m >= 1.  Optional symbol: a build of this version may lack it. */
+int mtq_packed_matmul_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                           const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream);
+
 /* The same product for decode, 1 <= m <= MTQ_PACKED_SKINNY_MAX_M: a split over K.  One wave takes the run of tiles of one tile row over
  * one K slice (a contiguous byte range of the stream), loads it straight to registers several tiles ahead, decodes each lane's group to
  * the same bf16 words as the block kernel and feeds them to mfma_f32_32x32x16_bf16 directly (no LDS).  The K range is cut into `split`

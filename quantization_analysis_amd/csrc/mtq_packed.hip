@@ -39,8 +39,10 @@
 //       that is read with the transposed LDS read (ds_read_b64_tr_b16); bit for bit the block kernel on the transposed weight.
 //   packed_matmul_skinny_kernel               that product for m <= 32: one wave per (K slice, tile column), each tile through a
 //       wave-private [32 k][32 n] LDS image and the transposed read; bit for bit the skinny linear kernel on the transposed weight.
+//   packed_matmul_wide_kernel                 that product for m >= 64: the wide block with its W side fed from the k × n stream, four
+//       [64 k][32 n] sub-images read through the transposed LDS read; bit for bit packed_matmul_kernel.
 //
-// The four wide kernels are frames around one block function, wide_block; the six skinny kernels around one wave's run, skinny_run, and one
+// The five wide kernels are frames around one block function, wide_block; the six skinny kernels around one wave's run, skinny_run, and one
 // epilogue, store_lane_rows; all of them read a tensor through a PackedStream and guard a blob with stream_at.
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
@@ -1284,6 +1286,8 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_linear_skinny_gro
 constexpr int kWideBM = 128, kWideBN = 128;
 
 constexpr int kWideImage = (kWideBM + kWideBN) * kLdk;   // one LDS image: the X block and four tile-row slots of W
+constexpr int kMwSub = kBK * kMmPitch;               // a wave's [64 k][32 n] sub-image of the k × n wide block, in bf16: 4 KB, no stagger
+static_assert(kWideBM * kLdk + 4 * kMwSub <= kWideImage, "the k x n W part fits the n x k one");
 
 template <int V>
 struct Tag {                                         // a compile-time integer as an argument: a register set's parity
@@ -1309,7 +1313,7 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v)
 // Launched with bounds (kThreads, 2): the second is HIP's minimum of waves per SIMD, not workgroups per CU; a workgroup here is one wave
 // per SIMD, so 2 is what lets two workgroups share a CU and caps the kernels at 256 VGPRs, which this function uses to the last:
 // re-read `make report` on any edit.
-template <bool GLU, bool XV, bool BF16OUT>
+template <bool GLU, bool XV, bool BF16OUT, bool WT = false>
 __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uint16_t *__restrict__ x, int64_t m0, int64_t M, int64_t K,
                                            int64_t ldx, const PackedStream &st, int64_t wtr, int64_t n0, int64_t N, int64_t tiles_h,
                                            int64_t tiles_w, const float *__restrict__ bias, const float *__restrict__ bias_up, int act,
@@ -1333,16 +1337,32 @@ __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uin
     GroupRaw wr[2][2];
     int tf[2];                                       // map code and offset of the wave's two tiles of the step after the last one loaded,
     uint32_t to[2];                                  // fetched a step before they are looked at: no load waits for them
+    // WT: wtr is the wave's tile COLUMN and the pair is tile rows 2 s and 2 s + 1 of it, tiles_w tiles apart, so every fetch leaves the
+    // first-level caches.  A uniform byte load is read to a scalar register, and waited for, where it is issued - twice a step; so lane l
+    // loads the code of tile row 2 s + (l & 1) itself, the value stays in a vector register and is handed out with readlane when
+    // load_step looks at it a step later (tfv, tth), and an offset is not touched here either: nothing waits in this function.
+    int tfv = 0;
+    bool tth[2] = {false, false};
     auto fetch_tables = [&](int64_t s) __attribute__((always_inline)) {
+        if constexpr (WT) {
+            const int64_t tr = 2 * s + (lane & 1);
+            tfv = map[tr < tiles_h && wtr < tiles_w ? tr * tiles_w + wtr : 0];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int64_t wtc = 2 * s + i;
-            const bool there = wtr < tiles_h && wtc < tiles_w;
-            const int64_t t = there ? wtr * tiles_w + wtc : 0;               // tile 0 is always there: the loads are unconditional
-            const int f = map[t];
-            const uint32_t o = off[t];
-            tf[i] = there ? f : -1;
-            to[i] = there ? o : 0u;
+            for (int i = 0; i < 2; ++i) {
+                tth[i] = 2 * s + i < tiles_h && wtr < tiles_w;
+                to[i] = off[tth[i] ? (2 * s + i) * tiles_w + wtr : 0];       // of tile 0 when the tile is absent: never used (f < 0)
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int64_t wtc = 2 * s + i;
+                const bool there = wtr < tiles_h && wtc < tiles_w;
+                const int64_t t = there ? wtr * tiles_w + wtc : 0;           // tile 0 is always there: the loads are unconditional
+                const int f = map[t];
+                const uint32_t o = off[t];
+                tf[i] = there ? f : -1;
+                to[i] = there ? o : 0u;
+            }
         }
     };
     // load_group for a whole tile by one wave (lane = group), with two loads whatever the tile is: every step issues the same
@@ -1379,8 +1399,12 @@ __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uin
     auto load_step = [&](auto par, int64_t s) __attribute__((always_inline)) {
         constexpr int p = decltype(par)::value;
         const int64_t k0 = s * kBK;
+        if constexpr (WT) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) tf[i] = tth[i] ? __builtin_amdgcn_readlane(tfv, i) : -1;
+        }
         const TileAt ta[2] = {stream_at(st, tf[0], to[0]), stream_at(st, tf[1], to[1])};   // the fetched pair, guarded
-        fetch_tables(s + 1);
+        if constexpr (!WT) fetch_tables(s + 1);
 #pragma unroll
         for (int i = 0; i < 2; ++i) load_tile(ta[i], wr[p][i]);
 #pragma unroll
@@ -1401,17 +1425,31 @@ __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uin
             }
             xr[p][j] = v;
         }
+        // WT: the step's newest load.  The waits the compiler places before a register of an earlier step is written again count back
+        // from the newest load; behind the tile and X loads the fetch stays in flight through them, in front it would be waited for.
+        if constexpr (WT) fetch_tables(s + 1);
     };
     // register set p → image `img`: tile i of the wave's slot (rows 32 wave .. of the W part), and X pieces [j0, j1)
-    auto stage_w = [&](auto par, int i, uint16_t *img) __attribute__((always_inline)) {
+    // WT: the lane's group is k-row 32 i + lane / 2 of step s, 16 values along n, and goes as it lies to bytes 2048 i + 32 lane of the
+    // wave's [64 k][32 n] sub-image; a k-row at or past K is zeros in the image whatever the stream holds.  Lanes with (lane >> 2) & 1
+    // set store their upper piece first (FeedTransposed's order): each 16-byte store of an 8-lane group covers 32 distinct banks.
+    auto stage_w = [&](auto par, int i, uint16_t *img, int64_t s) __attribute__((always_inline)) {
         constexpr int p = decltype(par)::value;
         uint32_t y[kGroup];
         decode_skinny(wr[p][i], y);
         uint4 lo, hi;
         pack_halves(y, lo, hi);
-        uint4 *d = reinterpret_cast<uint4 *>(img + (BM + kTile * wave + (lane >> 1)) * kLdk + kTile * i + kGroup * (lane & 1));
-        d[0] = lo;
-        d[1] = hi;
+        if constexpr (WT) {
+            const bool pad = s * kBK + kTile * i + (lane >> 1) >= K, up = (lane >> 2) & 1;
+            if (pad) lo = hi = make_uint4(0u, 0u, 0u, 0u);
+            uint16_t *d = img + BM * kLdk + wave * kMwSub + (kTile * i) * kMmPitch + lane * kGroup;
+            *reinterpret_cast<uint4 *>(d + 8 * up) = make_uint4(up ? hi.x : lo.x, up ? hi.y : lo.y, up ? hi.z : lo.z, up ? hi.w : lo.w);
+            *reinterpret_cast<uint4 *>(d + 8 * (up ^ 1)) = make_uint4(up ? lo.x : hi.x, up ? lo.y : hi.y, up ? lo.z : hi.z, up ? lo.w : hi.w);
+        } else {
+            uint4 *d = reinterpret_cast<uint4 *>(img + (BM + kTile * wave + (lane >> 1)) * kLdk + kTile * i + kGroup * (lane & 1));
+            d[0] = lo;
+            d[1] = hi;
+        }
     };
     auto stage_x = [&](auto par, int j0, int j1, uint16_t *img) __attribute__((always_inline)) {
         constexpr int p = decltype(par)::value;
@@ -1426,7 +1464,16 @@ __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uin
         const int koff = kk * 16 + 8 * (lane >> 5);
         bf16x8 b[2];
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) b[nt] = *reinterpret_cast<const bf16x8 *>(ws + (64 * wn + 32 * nt + (lane & 31)) * kLdk + koff);
+        for (int nt = 0; nt < 2; ++nt) {
+            if constexpr (WT) {                      // packed_matmul_kernel's lane addressing in sub-image 2 wn + nt: k + 0..3, then k + 4..7
+                const uint16_t *src = ws + (2 * wn + nt) * kMwSub + (kk * 16 + 8 * (lane >> 5) + ((lane >> 2) & 3)) * kMmPitch +
+                                      16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+                const i16x4 b0 = lds_read_tr16(src), b1 = lds_read_tr16(src + 4 * kMmPitch);
+                b[nt] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7));
+            } else {
+                b[nt] = *reinterpret_cast<const bf16x8 *>(ws + (64 * wn + 32 * nt + (lane & 31)) * kLdk + koff);
+            }
+        }
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xs + (32 * MT * wm + 32 * mt + (lane & 31)) * kLdk + koff);
@@ -1450,7 +1497,7 @@ __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uin
                 mfma_group(xs, ws, kk);
             } else if (kk < 2) {
                 mfma_group(xs, ws, kk);
-                stage_w(other, kk, next);
+                stage_w(other, kk, next, s + 1);
             } else {
                 mfma_group(xs, ws, kk);
                 stage_x(other, (kk - 2) * (XP / 2), (kk - 1) * (XP / 2), next);
@@ -1462,8 +1509,8 @@ __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uin
     fetch_tables(0);
     load_step(Tag<0>(), 0);
     load_step(Tag<1>(), steps > 1 ? 1 : 0);
-    stage_w(Tag<0>(), 0, lds);
-    stage_w(Tag<0>(), 1, lds);
+    stage_w(Tag<0>(), 0, lds, 0);
+    stage_w(Tag<0>(), 1, lds, 0);
     stage_x(Tag<0>(), 0, XP, lds);
     __syncthreads();
     int64_t s = 0;
@@ -1518,6 +1565,34 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
     const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kWideBN;
     wide_block<false, XV, BF16OUT>(lds, x, bm * kWideBM, M, K, ldx, tensor_stream(packed, packed_bytes, map, offsets), (n0 >> 5) + wave, n0, N,
                                    tiles_h, tiles_w, bias, nullptr, 0, yv, ldy, wave);
+}
+
+// ---- wide matmul: Y = X·P̂ + b for a packed k × n matrix from the wide block, for m >= 64.
+//
+// wide_block<.., WT = true>: everything of the block but its W side.  The stream is of a k × n matrix, so a step's W block is 2 tile rows
+// × 4 tile columns: wave w takes tile column n0 / 32 + w and, at step s, its tiles of the tile rows 2 s and 2 s + 1, a lane the group of its
+// own number (k-row 64 s + 32 i + lane / 2, columns n0 + 32 w + 16 (lane & 1) ..).  The W part of an image is four [64 k][32 n] sub-images
+// at packed_matmul_kernel's 64-byte pitch, 4 KB each and back to back (16 KB of the 18 KB the n × k block takes): a wave writes its own
+// sub-image end to end, 32 bytes a lane, and wave (wm, wn) reads sub-images 2 wn and 2 wn + 1 through the transposed LDS read, two reads
+// per operand with packed_matmul_kernel's lane addressing.  The same k at the same lane half and element, ascending kk, the same K step,
+// zeros at and past K: packed_matmul_kernel's bits.
+// Banks: a 32-lane half of a transposed read takes 4 k-rows × 64 bytes of ONE sub-image, 256 consecutive bytes, every bank once.  A
+// 16-byte store goes by 8-lane groups over 32 banks; bytes 32 lane would put lanes i and i + 4 on the same banks, so those lanes store
+// their upper piece first.  No instruction touches two sub-images, and each starts on a multiple of 256 bytes: §A.6p's 16-byte shift
+// between sub-images has nothing left to separate.
+// EXEC is all ones at every transposed read: they sit in wave-uniform control flow only, and nothing returns before the epilogue.
+template <bool XV, bool BF16OUT>
+__global__ __launch_bounds__(kThreads, 2) void packed_matmul_wide_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+    const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N, int64_t tiles_h, int64_t tiles_w,
+    const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
+    const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kWideBN;
+    wide_block<false, XV, BF16OUT, true>(lds, x, bm * kWideBM, M, K, ldx, tensor_stream(packed, packed_bytes, map, offsets), (n0 >> 5) + wave, n0,
+                                         N, tiles_h, tiles_w, bias, nullptr, 0, yv, ldy, wave);
 }
 
 // ---- grouped wide linear: packed_linear_wide_kernel's block for every expert of an arena over the expert's own rows, one launch.
@@ -2130,6 +2205,22 @@ extern "C" int mtq_packed_linear_wide(const void *x, int64_t m, int64_t k, int64
                static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map, offsets, n, th, tw, bias,
                y, ldy);
     return check_launch("mtq_packed_linear_wide");
+}
+
+// The wide product with a packed k × n matrix: mtq_packed_matmul's checks and texts, the wide block's grid.
+extern "C" int mtq_packed_matmul_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                                      const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    int64_t tn, tk;
+    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, &tn, &tk)) return rc;
+    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kWideBN - 1) / kWideBN);
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
+    if (int rc = require_device()) return rc;
+    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_matmul_wide_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), static_cast<hipStream_t>(stream),
+               static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map, offsets, n, tk, tn, bias,
+               y, ldy);
+    return check_launch("mtq_packed_matmul_wide");
 }
 
 extern "C" size_t mtq_packed_linear_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)

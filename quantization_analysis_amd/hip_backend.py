@@ -140,6 +140,7 @@ SIGNATURES = {
     "mtq_packed_glu_skinny": ("i", "plllpzpppzpplppipilipzp", True),
     "mtq_packed_glu_skinny_grouped_workspace_bytes": ("z", "lllli", True),
     "mtq_packed_glu_skinny_grouped": ("i", "plllppzppppzpppllpplipilipzp", True),
+    "mtq_packed_matmul_wide": ("i", "plllpzpplppilp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1207,6 +1208,38 @@ def packed_matmul(x, data, tables: PackedTables, n: int, bias=None, out_dtype=No
     ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
     check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
     return out
+
+
+def packed_matmul_wide(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, stream="current"):
+    """mtq_packed_matmul_wide on the current stream: packed_matmul's product, arguments and bits from the wide-block kernel (a
+    128 x 128 block whose waves decode whole tiles of the (k, n) stream), for m above the decode range.  Correct for any m; m = 0 gives
+    the empty (0, n) tensor without a call."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code = _packed_out_code(out_dtype)
+    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if tiles_hw(k, n) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {k}x{n} matrix has {'x'.join(map(str, tiles_hw(k, n)))}")
+    ptr = _packed_stream(data, tables)
+    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
+    fn = _entry("mtq_packed_matmul_wide")
+    if out is None:
+        require_gpu()
+        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
+    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
+    if m == 0:                                       # the entry refuses empty operands, as the block entry does: they end here
+        return out
+    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
+    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+def has_packed_matmul_wide() -> bool:
+    """Whether this build of the library has mtq_packed_matmul_wide (an optional symbol: an older build of the same version lacks it)."""
+    return getattr(lib(), "mtq_packed_matmul_wide", None) is not None
 
 
 PACKED_SKINNY_MAX_M = 32   # include/mtq.h MTQ_PACKED_SKINNY_MAX_M

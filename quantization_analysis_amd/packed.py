@@ -20,7 +20,9 @@ transposed LDS read).  A weight stored input-major (y = x @ W) packs with pack()
 is that product for decode, m <= 32 (mtq_packed_matmul_skinny: the skinny linear kernel's split over K with each tile passed through
 a wave-private [k][n] LDS image), and PackedMatmul(kernel="skinny" | "auto") keeps its workspace across calls.
 
-Not built: a fused kernel for the decode range (the skinny family's split over K has partial sums); wide, grouped and GLU variants of
+matmul_wide is the (k, n) product above the decode range from the wide-block kernel (mtq_packed_matmul_wide), the block kernel's bits.
+
+Not built: a fused kernel for the decode range (the skinny family's split over K has partial sums); grouped and GLU variants of
 the (k, n) product; pack_batch and scripts/pack_model.py for transposed configs; pack_transposed of tensors of rank other than 2;
 activations other than ACTS.
 
@@ -62,6 +64,11 @@ MATMUL_KERNELS = ("block", "skinny", "auto")
 # "auto" is "block".  The largest measured m at which, at every shape and map, the skinny kernel's median is below mtq_packed_matmul's
 # minimum of the same run by more than that side's own minimum-to-median spread (profiles/packed_matmul_skinny.txt).
 AUTO_MATMUL_SKINNY_MAX_M = 32
+# matmul(kernel="auto") takes the wide-block (k, n) kernel (matmul_wide) from this m on when the library has it; None: never, "auto" stays
+# on the block kernel there.  AUTO_WIDE_MIN_M's rule: the smallest measured m from which on, at every shape and map, the wide median is
+# below mtq_packed_matmul's minimum of the same run by more than that side's own minimum-to-median spread (DESIGN.md §A.6t,
+# profiles/packed_matmul_wide.txt).  Both kernels give the same bits, so the gate changes no result.
+AUTO_MATMUL_WIDE_MIN_M = 64
 ACTS =("silu", "none")     # include/mtq.h MTQ_ACT_SILU, MTQ_ACT_NONE
 GLU_KERNELS = ("fused", "unfused", "auto")
 GLU_GROUPED_KERNELS = ("fused", "unfused")
@@ -511,8 +518,10 @@ def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     m <= 32; `split` slices of K, 0 = the library's choice, and an optional uint8 device `workspace` of
     hip_backend.packed_matmul_skinny_workspace_bytes bytes): bit for bit linear(kernel="skinny") at the same split on the all-bf16
     packing of unpack(pt)ᵀ, and MtqError naming the missing symbols on a library without them; "auto", the skinny kernel for
-    m <= AUTO_MATMUL_SKINNY_MAX_M when that is not None and the library has it, else block.  The two kernels sum in different orders:
-    each is bit-stable, they may differ in the last bits.  The emulation computes the same float64 product under all three names."""
+    m <= AUTO_MATMUL_SKINNY_MAX_M when that is not None and the library has it, else block; from m = AUTO_MATMUL_WIDE_MIN_M on, when
+    that is not None and the library has it, the wide-block kernel of matmul_wide, whose bits are the block kernel's.  The skinny and
+    the block kernel sum in different orders: each is bit-stable, they may differ in the last bits.  The emulation computes the same
+    float64 product under all three names."""
     _check_kn(pt, "matmul")
     if kernel not in MATMUL_KERNELS:
         raise MtqError(f"kernel must be one of {MATMUL_KERNELS}, got {kernel!r}")
@@ -531,6 +540,9 @@ def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
         dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
         if _matmul_takes_skinny(hb, kernel, int(x.shape[0])):
             return hb.packed_matmul_skinny(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype, split=split, workspace=workspace)
+        if (kernel == "auto" and AUTO_MATMUL_WIDE_MIN_M is not None and int(x.shape[0]) >= AUTO_MATMUL_WIDE_MIN_M
+                and hb.has_packed_matmul_wide()):
+            return hb.packed_matmul_wide(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
         return hb.packed_matmul(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
     if backend != "emulation":
         raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
@@ -546,6 +558,31 @@ def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     with np.errstate(over="ignore"):
         y32 = y.astype(np.float32)
     return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
+
+
+def matmul_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
+    """matmul(kernel="block")'s product and, on hip, its bits, through mtq_packed_matmul_wide: the wide-block kernel for m above the
+    decode range (prefill), 128 x 128 outputs to a workgroup, whose waves decode whole tiles of the (k, n) stream.  Correct for any m
+    (m = 0 gives (0, n)); faster than the block kernel from m = 64 on, the smallest m measured.  A library without
+    the symbol raises MtqError: there is no fall-back to the block kernel here (matmul(kernel="auto") is the call that chooses).
+    emulation: matmul's float64 product."""
+    _check_kn(pt, "matmul_wide")
+    backend = backend or ("hip" if pt.on_device else "emulation")
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    if backend != "hip":
+        return matmul(x, pt, bias=bias, out_dtype=out_dtype, backend=backend)
+    import torch
+
+    from . import hip_backend as hb
+
+    k, n = pt.rows, pt.cols
+    if x.dim() != 2 or x.shape[1] != k:
+        raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+    if not hb.has_packed_matmul_wide():
+        raise MtqError("matmul_wide needs mtq_packed_matmul_wide, which this build of libmtq_hip.so lacks: rebuild it from this tree")
+    dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+    return hb.packed_matmul_wide(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
 
 
 # ----------------------------------------------------------------------------- batches

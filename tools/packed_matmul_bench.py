@@ -19,8 +19,18 @@ directly, the weights rotated over --cold-mb of copies.
             minimum by more than the block side's own minimum-to-median spread; the last line names the largest m at which every
             row passes (packed.AUTO_MATMUL_SKINNY_MAX_M).  --sweep-splits times explicit splits on the first shape and map.
 
+  --wide  : mtq_packed_matmul_wide (the wide-block kernel for m above the decode range), m in {64, 128, 256, 512, 1024, 2048, 4096}, the
+            same shapes and maps.  Four sides: the new entry; mtq_packed_matmul (the route before it, the baseline of the gate);
+            mtq_packed_linear_wide on the n × k stream of Pᵀ under the transposed map (the same tiles, the same bytes: the kernel the
+            new one is expected to equal in time); torch.matmul on the unpacked bf16 P̂.  Before timing, the bit contract is checked:
+            the new entry against mtq_packed_matmul.  `gate` is pass when the new kernel's median is below the block side's minimum by
+            more than the block side's own minimum-to-median spread; `vs-lw` says whether the new median is above the wide linear's by
+            more than that side's spread; the last line names the smallest m from which on every row passes
+            (packed.AUTO_MATMUL_WIDE_MIN_M).
+
   python tools/packed_matmul_bench.py [--rounds 5] [--window-ms 30] [--out profiles/packed_matmul.txt] [--json out.json]
   python tools/packed_matmul_bench.py --skinny [--sweep-splits 1,2,4,8,16,32,64,128] [--out profiles/packed_matmul_skinny.txt]
+  python tools/packed_matmul_bench.py --wide [--out profiles/packed_matmul_wide.txt]
 """
 from __future__ import annotations
 
@@ -157,6 +167,93 @@ def skinny(args, say, rows) -> None:
     say(f"# gate: every shape and map passes at m in {good}; AUTO_MATMUL_SKINNY_MAX_M = {max(good) if good else None}")
 
 
+def wide(args, say, rows) -> None:
+    if not hb.has_packed_matmul_wide():
+        raise hb.MtqError("this build of libmtq_hip.so lacks mtq_packed_matmul_wide")
+    stream = torch.cuda.current_stream().cuda_stream
+    e_new, e_blk, e_lw = hb._entry("mtq_packed_matmul_wide"), hb._entry("mtq_packed_matmul"), hb._entry("mtq_packed_linear_wide")
+    ms = sorted(int(v) for v in args.ms.split(","))
+    passed = {m: True for m in ms}
+    worst = None                                             # the row whose new median is furthest above the wide linear's
+    for shape in args.shapes.split(","):
+        k, n = (int(v) for v in shape.split("x"))
+        g = torch.Generator(device="cuda").manual_seed(n + k)
+        pm = (torch.randn((k, n), generator=g, device="cuda") * 0.02).to(torch.bfloat16)      # P, k × n
+        w = pm.t().contiguous()
+        th, tw = hb.tiles_hw(k, n)
+        maps = {"bfp8": lambda: np.full((th, tw), 1, dtype=np.int8), "bfp4": lambda: np.full((th, tw), 2, dtype=np.int8), "greedy": lambda: greedy_map(pm)}
+        for name in args.maps.split(","):
+            amap = maps[name]()
+            counts = np.bincount(amap.reshape(-1), minlength=4).tolist()
+            tp = hb.PackedTables.on_device(amap)                                              # over P's grid
+            tl = hb.PackedTables.on_device(np.ascontiguousarray(amap.T))                      # over W's grid: the same counts
+            assert tp.nbytes == tl.nbytes
+            dp = hb.pack_tiles(pm, tp)
+            dl = hb.pack_tiles(w, tl)
+            pq = hb.unpack_tiles(dp, tp, k, n, dtype=torch.bfloat16)                          # P̂ bf16, k × n
+            copies_p = max(2, int(np.ceil(args.cold_mb * 1e6 / tp.nbytes)))
+            copies_w = max(2, int(np.ceil(args.cold_mb * 1e6 / (2 * n * k))))
+            dps = [dp] + [dp.clone() for _ in range(copies_p - 1)]
+            dls = [dl] + [dl.clone() for _ in range(copies_p - 1)]
+            pqs = [pq] + [pq.clone() for _ in range(copies_w - 1)]
+            for m in ms:
+                x = torch.randn((m, k), generator=g, device="cuda").to(torch.bfloat16)
+                ya, yb, yc, ym = (torch.empty((m, n), dtype=torch.bfloat16, device="cuda") for _ in range(4))
+                hb.packed_matmul_wide(x, dp, tp, n, out_dtype=torch.bfloat16, out=ya)          # the wrappers' checks, once
+                hb.packed_matmul(x, dp, tp, n, out_dtype=torch.bfloat16, out=yc)
+                same = bool(torch.equal(ya.view(torch.int16), yc.view(torch.int16)))
+                c_new = [(x.data_ptr(), m, k, x.stride(0), d.data_ptr(), tp.nbytes, tp.map_ptr, tp.offsets_ptr, n, None, ya.data_ptr(), hb.DTYPE_BF16, n,
+                          stream) for d in dps]
+                c_blk = [c[:10] + (yc.data_ptr(),) + c[11:] for c in c_new]
+                c_lw = [(x.data_ptr(), m, k, x.stride(0), d.data_ptr(), tl.nbytes, tl.map_ptr, tl.offsets_ptr, n, None, yb.data_ptr(), hb.DTYPE_BF16, n,
+                         stream) for d in dls]
+
+                def f_new(i):
+                    hb.check(e_new(*c_new[i % copies_p]))
+
+                def f_blk(i):
+                    hb.check(e_blk(*c_blk[i % copies_p]))
+
+                def f_lw(i):
+                    hb.check(e_lw(*c_lw[i % copies_p]))
+
+                def f_torch(i):
+                    torch.matmul(x, pqs[i % copies_w], out=ym)
+
+                med, mn = _timed((f_new, f_blk, f_lw, f_torch), args)
+                f_new(0)
+                f_torch(0)
+                err = float((ya.float() - ym.float()).abs().max() / ym.float().abs().max().clamp_min(1e-30))
+                gate = med[0] < mn[1] - (med[1] - mn[1])
+                above = med[0] > med[2] + (med[2] - mn[2])                                    # above the wide linear by more than its spread
+                passed[m] = passed[m] and gate and same
+                if above and (worst is None or med[0] / med[2] > worst[0]):
+                    worst = (med[0] / med[2], f"P {k}x{n} m={m} map={name}")
+                flop = 2.0 * m * n * k
+                rows.append({"what": "packed_matmul_wide", "k": k, "n": n, "m": m, "map": name, "counts": counts, "wide_ms_median": med[0],
+                             "wide_ms_min": mn[0], "block_ms_median": med[1], "block_ms_min": mn[1], "linear_wide_ms_median": med[2],
+                             "linear_wide_ms_min": mn[2], "torch_ms_median": med[3], "torch_ms_min": mn[3], "wide_over_block_min": med[0] / mn[1],
+                             "block_spread": med[1] / mn[1], "wide_over_linear_wide": med[0] / med[2], "linear_wide_spread": med[2] / mn[2],
+                             "above_linear_wide": bool(above), "wide_over_torch": med[0] / med[3], "wide_tflops": flop / med[0] / 1e9,
+                             "gate": bool(gate), "contract_bits_equal": same, "max_rel_diff_torch": err})
+                say(f"wide P {k}x{n} m={m:4d} map={name:6s} new {med[0] * 1e3:8.1f} us (min {mn[0] * 1e3:8.1f}, {flop / med[0] / 1e9:6.1f} TFLOP/s) "
+                    f"block {med[1] * 1e3:8.1f} us (min {mn[1] * 1e3:8.1f}) linear-wide {med[2] * 1e3:8.1f} us (min {mn[2] * 1e3:8.1f}) "
+                    f"torch {med[3] * 1e3:8.1f} us (min {mn[3] * 1e3:8.1f})  new/block-min {med[0] / mn[1]:6.3f} spread {med[1] / mn[1]:5.3f} "
+                    f"gate {'pass' if gate else 'FAIL'}  new/linear-wide {med[0] / med[2]:5.3f} its spread {med[2] / mn[2]:5.3f} "
+                    f"vs-lw {'ABOVE' if above else 'within'}  new/torch {med[0] / med[3]:5.2f}  bits equal the block kernel's: {same}  "
+                    f"max rel diff to torch {err:.2e}")
+            del dps, dls, pqs, dp, dl, pq
+        del pm, w
+    from_m = None                                            # the smallest m from which on every measured m passes
+    for m in reversed(ms):
+        if not passed[m]:
+            break
+        from_m = m
+    say(f"# gate: every shape and map passes at m in {[m for m in ms if passed[m]]}; AUTO_MATMUL_WIDE_MIN_M = {from_m}")
+    say(f"# rows whose median is above the wide linear's by more than that side's spread: "
+        f"{'none' if worst is None else 'worst ' + worst[1] + f' at {worst[0]:.3f}'}")
+
+
 def main() -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--rounds", type=int, default=5)
@@ -168,6 +265,7 @@ def main() -> int:
     p.add_argument("--maps", default="bfp8,bfp4,greedy")
     p.add_argument("--skip-pack", action="store_true", help="skip the pack / unpack timings")
     p.add_argument("--skinny", action="store_true", help="time mtq_packed_matmul_skinny (m <= 32) against the block entry, the skinny linear and torch")
+    p.add_argument("--wide", action="store_true", help="time mtq_packed_matmul_wide (m >= 64) against the block entry, the wide linear and torch")
     p.add_argument("--sweep-splits", default="", help="--skinny: explicit splits timed on the first shape and map, comma separated")
     p.add_argument("--out", default=None)
     p.add_argument("--json", default=None)
@@ -182,6 +280,12 @@ def main() -> int:
         print(line, flush=True)
         lines.append(line)
 
+    if args.wide:
+        args.ms = "64,128,256,512,1024,2048,4096" if args.ms == p.get_default("ms") else args.ms
+        say(f"# mtq_packed_matmul_wide on {torch.cuda.get_device_name(0)}; device events, {args.rounds} rounds of ~{args.window_ms:.0f} ms windows, "
+            f"sides alternated, weights rotated over {args.cold_mb:.0f} MB, bf16 output")
+        wide(args, say, rows)
+        return finish(args, lines, rows)
     if args.skinny:
         args.ms = "1,16,32" if args.ms == p.get_default("ms") else args.ms
         args.sweep_splits = [int(v) for v in args.sweep_splits.split(",") if v]
