@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTQ_VERSION 143 /* 0.1.4.9 (optional symbols as well): + mtq_packed_tile_bytes, mtq_packed_offsets, mtq_pack_tiles, mtq_unpack_tiles, mtq_packed_linear; 0.1.4.8 (optional symbols as well): + mtq_output_error_transposed, mtq_tile_error_tables_transposed; 0.1.4.7 (optional symbols as well): + mtq_gram_full / _scratch_doubles, mtq_gptq_sweep / _scratch_doubles; 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
+#define MTQ_VERSION 143 /* 0.1.4.10 (optional symbols as well, so the number stays 143): + mtq_pack_tiles_transposed_batched, mtq_unpack_tiles_transposed_batched; 0.1.4.9 (optional symbols as well): + mtq_packed_tile_bytes, mtq_packed_offsets, mtq_pack_tiles, mtq_unpack_tiles, mtq_packed_linear; 0.1.4.8 (optional symbols as well): + mtq_output_error_transposed, mtq_tile_error_tables_transposed; 0.1.4.7 (optional symbols as well): + mtq_gram_full / _scratch_doubles, mtq_gptq_sweep / _scratch_doubles; 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
 
 typedef enum {
     MTQ_OK = 0,
@@ -684,6 +684,29 @@ int mtq_pack_tiles_batched(const void *x, int in_dtype, int64_t count, int64_t r
                            const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, void *out, size_t out_bytes, void *stream);
 int mtq_unpack_tiles_batched(const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases,
                              int64_t count, int64_t rows, int64_t cols, void *y, int out_dtype, int64_t ldy, int64_t stride, void *stream);
+/* The batch in the transposed layout: the two entries above with the transposed pair's meaning.  w (y) holds `count` matrices, each
+ * rows × cols AS STORED (row pitch ld / ldy >= cols, matrix i starting i * stride elements in); maps[count][tiles] and
+ * offsets[count][tiles + 1] with tiles = ceil(cols/32) * ceil(rows/32) are over the grid of the TRANSPOSE, numbered as
+ * mtq_pack_tiles_transposed numbers it; mtq_packed_offsets_batched produces offsets and bases for them as for any maps.
+ *
+ * mtq_pack_tiles_transposed_batched: tile t of tensor i goes to out + 64 * (bases[i] + offsets[i][t]), byte for byte what
+ * mtq_pack_tiles_transposed writes for matrix i alone.  One wave per (tensor, tile) under the launch cap of the batched entries
+ * (a grid-stride loop); plain stores, no atomics: deterministic.  The wave reads the tile's 32 × 32 region of w by rows - 16-byte loads
+ * when w, ld and stride keep every matrix 16-byte aligned and the region lies inside rows × cols, element by element otherwise (ragged
+ * edges, unaligned views), +0 past rows or cols - into a wave-private padded LDS image, and each lane gathers its group's 16 values down a column of the image.
+ * mtq_unpack_tiles_transposed_batched: the arena → y[count][rows][cols] in W's orientation.  MTQ_DTYPE_F32: bit for bit what
+ * mtq_apply_assignment_transposed writes; MTQ_DTYPE_BF16: the upper halves.
+ *
+ * The guards are the batched entries': every blob is checked against the buffer's length on the device before it is touched, a tile
+ * whose code is outside 0..3 is skipped alone, nothing is stored outside rows × cols.  Argument errors (null pointers, a dtype,
+ * count <= 0, ld < cols, a stride below one matrix when count > 1, a buffer below 320 bytes per tile, an arena that is not 16-byte
+ * aligned) are MTQ_ERR_INVALID before a device is looked for.  Optional symbols (0.1.4.10; the number stays 143). */
+int mtq_pack_tiles_transposed_batched(const void *w, int in_dtype, int64_t count, int64_t rows, int64_t cols, int64_t ld, int64_t stride,
+                                      const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, void *out, size_t out_bytes,
+                                      void *stream);
+int mtq_unpack_tiles_transposed_batched(const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                        const uint64_t *bases, int64_t count, int64_t rows, int64_t cols, void *y, int out_dtype, int64_t ldy,
+                                        int64_t stride, void *stream);
 /* Y = X·Ŵᵀ + b: x m × k bf16 (ldx), Ŵ the packed n × k weight (nn.Linear convention; map grid ceil(n/32) × ceil(k/32)), bias n
  * float32 or NULL, y m × n float32 or bf16 (out_dtype, ldy).  The weight is decoded into a bf16 LDS image (exact) and multiplied by
  * mfma_f32_32x32x16_bf16 with f32 accumulation in a fixed K order; bias is added in f32, a bf16 y is rounded to nearest even once.

@@ -35,6 +35,9 @@
 //   pack_tiles_transposed_kernel / unpack_tiles_transposed_kernel
 //                                             the stream of the TRANSPOSE of a stored matrix, read / written in the stored orientation: a
 //       map over the transposed layout of W is a row-layout map of Wᵀ, so this is the same format (no new bytes, no new layout value).
+//   pack_tiles_transposed_batched_kernel / unpack_tiles_transposed_batched_kernel
+//                                             that pair for a batch and its arena, one wave per (tensor, tile); the pack reads each tile's
+//       region of w by rows into a wave-private LDS image and gathers the column groups from it.
 //   packed_matmul_kernel                      Y = X·P̂ + b for a packed k × n matrix: the block kernel's frame over a [k][n] LDS image
 //       that is read with the transposed LDS read (ds_read_b64_tr_b16); bit for bit the block kernel on the transposed weight.
 //   packed_matmul_skinny_kernel               that product for m <= 32: one wave per (K slice, tile column), each tile through a
@@ -353,6 +356,143 @@ __global__ __launch_bounds__(256) void unpack_tiles_batched_kernel(const uint8_t
         const TileAt a = tile_at(packed_bytes, maps + i * tiles, offsets + i * (tiles + 1), t, bases[i]);
         void *yi = BF16OUT ? static_cast<void *>(static_cast<uint16_t *>(yv) + i * stride) : static_cast<void *>(static_cast<uint32_t *>(yv) + i * stride);
         unpack_tile<BF16OUT>(packed, a, tiles_w, t, lane, rows, cols, yi, ldy, vec_ok != 0);
+    }
+}
+
+// ---- the batched transposed pair: pack_tiles_transposed_kernel / unpack_tiles_transposed_kernel over a batch and its arena
+//
+// Pack's read path.  pack_tiles_transposed_kernel has every lane walk 16 rows of one column of w: 16 scalar loads per lane.  Here the wave
+// first reads the tile's 32 × 32 region of w BY ROWS into an image of float32 words in LDS, 16 bytes per lane and load (a float32 row of
+// the region is 8 lanes, a bf16 row 4: four / two loads per lane), and each lane then gathers its group down a column of the image.
+// The 16-byte loads are taken when w, ld and stride keep every matrix 16-byte aligned (a region starts at a multiple of 32 columns) and
+// the whole region lies inside rows × cols: a wave-uniform choice, so the loads of a tile are all in flight before the first store.
+// Every other tile (a ragged edge, an unaligned view) is read element by element, +0 past an edge.
+//
+// Banks (stores and ds_read_b32: word address mod 32, by 32-lane halves).  The image's row pitch is 33 words, so word (r, c) is on
+// bank (r + c) mod 32.  A store instruction writes word j of every lane's piece: a half holds 4 (float32) or 8 (bf16) consecutive rows and
+// the pieces start 4 or 8 columns apart, r + c takes 32 distinct values.  A gather reads (16 (lane & 1) + i, lane >> 1): over a half
+// 16 (lane & 1) + (lane >> 1) takes every value 0..31 once.  Neither side has a conflict.
+//
+// The image is one wave's (4224 bytes; 16.5 KB a workgroup): no __syncthreads.  Stores and reads are by different lanes, so the ordering
+// is packed_matmul_skinny_kernel's: a workgroup-scope fence and a wave barrier between a tile's stores and its reads, a fence and a
+// wave barrier after the reads before the next tile's stores.  Every branch around them is wave-uniform.
+//
+// MTQ_PACK_TRANSPOSED_BATCHED_DIRECT (a compile-time switch for A/B measurements) takes the per-tensor kernel's direct
+// column reads instead; the group's words, and so the bytes, are the same.
+constexpr int kImgPitch = kTile + 1;                 // words per image row
+constexpr int kImgWords = kTile * kImgPitch;
+#ifdef MTQ_PACK_TRANSPOSED_BATCHED_DIRECT
+constexpr bool kPackTransposedStaged = false;
+#else
+constexpr bool kPackTransposedStaged = true;
+#endif
+
+// The region of w with its corner at (r0, c0) → img[32][kImgPitch] as float32 words, read by rows.  whole (wave-uniform): the region lies
+// inside rows × cols and every row of it starts 16-byte aligned.
+template <typename T>
+__device__ __forceinline__ void stage_region(const T *__restrict__ w, int64_t rows, int64_t cols, int64_t ld, bool whole, int64_t r0, int64_t c0,
+                                             int lane, uint32_t *__restrict__ img)
+{
+    constexpr int kPer = 16 / (int)sizeof(T);        // elements of a 16-byte piece: 4 float32, 8 bf16
+    constexpr int kRowLanes = kTile / kPer;          // lanes to a row of the region: 8, 4
+    constexpr int kPassRows = 64 / kRowLanes;        // rows to a load instruction: 8, 16
+    constexpr int kPasses = kTile / kPassRows;       // 4, 2
+    const int rl = lane / kRowLanes, cl = kPer * (lane % kRowLanes);
+    const int64_t col = c0 + cl;
+    uint32_t v[kPasses][kPer];
+    if (whole) {
+        uint4 q[kPasses];
+#pragma unroll
+        for (int p = 0; p < kPasses; ++p) q[p] = *reinterpret_cast<const uint4 *>(w + (r0 + p * kPassRows + rl) * ld + col);
+#pragma unroll
+        for (int p = 0; p < kPasses; ++p) {
+            const uint32_t d[4] = {q[p].x, q[p].y, q[p].z, q[p].w};
+#pragma unroll
+            for (int i = 0; i < kPer; ++i) {
+                if constexpr (sizeof(T) == 4) v[p][i] = d[i];
+                else v[p][i] = (i & 1) ? (d[i >> 1] & 0xFFFF0000u) : (d[i >> 1] << 16);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int p = 0; p < kPasses; ++p) {
+            const int64_t row = r0 + p * kPassRows + rl;
+#pragma unroll
+            for (int i = 0; i < kPer; ++i) v[p][i] = (row < rows && col + i < cols) ? word_of(w, row * ld + col + i) : 0u;
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < kPasses; ++p) {
+        uint32_t *dst = img + (p * kPassRows + rl) * kImgPitch + cl;
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) dst[i] = v[p][i];
+    }
+}
+
+// Wave g of count * tiles takes tile t = g % tiles of tensor i = g / tiles, as pack_tiles_batched_kernel; the grid (tiles, tiles_w) is the
+// transpose's, as pack_tiles_transposed_kernel's.
+template <typename T>
+__global__ __launch_bounds__(256) void pack_tiles_transposed_batched_kernel(const T *__restrict__ w, int64_t count, int64_t rows, int64_t cols,
+                                                                            int64_t ld, int64_t stride, int vec_ok, const int8_t *__restrict__ maps,
+                                                                            const uint32_t *__restrict__ offsets, const uint64_t *__restrict__ bases,
+                                                                            int64_t tiles, int64_t tiles_w, uint8_t *__restrict__ out, uint64_t out_bytes)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kPackTransposedStaged ? 4 * kImgWords : 4];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t *img = lds + (kPackTransposedStaged ? wave * kImgWords : 0);
+    const int64_t total = count * tiles;
+    for (int64_t g = (int64_t)blockIdx.x * 4 + wave; g < total; g += (int64_t)gridDim.x * 4) {
+        const int64_t i = g / tiles, t = g - i * tiles;
+        const int f = maps[g];
+        const uint32_t size = packed_tile_bytes(f);
+        const uint64_t off = (bases[i] + offsets[i * (tiles + 1) + t]) * kUnit;
+        if (size == 0u || off > out_bytes || size > out_bytes - off) continue;   // wave-uniform
+        const T *wi = w + i * stride;
+        const int64_t c0 = (t / tiles_w) * kTile, r0 = (t % tiles_w) * kTile;    // the region's corner in w
+        const int cl = lane >> 1, rl = kGroup * (lane & 1);                      // the lane's group: column cl, rows rl .. rl + 15 of it
+        uint32_t u[kGroup];
+        if constexpr (kPackTransposedStaged) {
+            stage_region(wi, rows, cols, ld, vec_ok != 0 && r0 + kTile <= rows && c0 + kTile <= cols, r0, c0, lane, img);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+            for (int j = 0; j < kGroup; ++j) u[j] = img[(rl + j) * kImgPitch + cl];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        } else {
+#pragma unroll
+            for (int j = 0; j < kGroup; ++j) u[j] = (c0 + cl < cols && r0 + rl + j < rows) ? word_of(wi, (r0 + rl + j) * ld + c0 + cl) : 0u;
+        }
+        pack_group(u, f, lane, out + off);
+    }
+}
+
+// unpack_tiles_transposed_kernel's tile (its direct strided stores) for every (tensor, tile) of an arena: matrix i of y starts i * stride
+// elements in.
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void unpack_tiles_transposed_batched_kernel(const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+                                                                              const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets,
+                                                                              const uint64_t *__restrict__ bases, int64_t count, int64_t tiles,
+                                                                              int64_t tiles_w, int64_t rows, int64_t cols, void *__restrict__ yv,
+                                                                              int64_t ldy, int64_t stride)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t total = count * tiles;
+    for (int64_t g = (int64_t)blockIdx.x * 4 + wave; g < total; g += (int64_t)gridDim.x * 4) {
+        const int64_t i = g / tiles, t = g - i * tiles;
+        const int64_t c = (t / tiles_w) * kTile + (lane >> 1), r0 = (t % tiles_w) * kTile + kGroup * (lane & 1);
+        GroupRaw gr;
+        load_group(packed, tile_at(packed_bytes, maps + i * tiles, offsets + i * (tiles + 1), t, bases[i]), lane, gr);
+        if (gr.f < 0 || c >= cols) continue;
+        uint32_t y[kGroup];
+        decode_group(gr, y);
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) {
+            if (r0 + j >= rows) continue;
+            if constexpr (BF16OUT) static_cast<uint16_t *>(yv)[i * stride + (r0 + j) * ldy + c] = (uint16_t)(y[j] >> 16);
+            else static_cast<uint32_t *>(yv)[i * stride + (r0 + j) * ldy + c] = y[j];
+        }
     }
 }
 
@@ -2069,6 +2209,57 @@ extern "C" int mtq_unpack_tiles_batched(const void *packed, size_t packed_bytes,
         hipLaunchKernelGGL(unpack_tiles_batched_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, maps, offsets, bases, count, th * tw, tw,
                            rows, cols, y, ldy, stride, vec_ok);
     return check_launch("mtq_unpack_tiles_batched");
+}
+
+// The batched transposed pair: w / y hold `count` matrices in the stored orientation (rows × cols), the arena the streams of their
+// cols × rows transposes; maps, offsets and the grid are the transposes'.
+extern "C" int mtq_pack_tiles_transposed_batched(const void *w, int in_dtype, int64_t count, int64_t rows, int64_t cols, int64_t ld, int64_t stride,
+                                                 const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, void *out, size_t out_bytes,
+                                                 void *stream)
+{
+    if (!w || !maps || !offsets || !bases || !out) return fail(MTQ_ERR_INVALID, "null argument");
+    if (in_dtype != MTQ_DTYPE_BF16 && in_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "in_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;                                   // of the transpose
+    if (int rc = batch_grid(count, cols, rows, &th, &tw)) return rc;
+    if (int rc = batch_pitch(count, rows, cols, ld, stride, "ld < cols")) return rc;
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(MTQ_ERR_INVALID, "out must be 16-byte aligned");
+    if (out_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "out_bytes is smaller than the streams");
+    if (int rc = require_device()) return rc;
+    const int64_t esz = in_dtype == MTQ_DTYPE_F32 ? 4 : 2;
+    const int vec_ok = reinterpret_cast<uintptr_t>(w) % 16 == 0 && (ld * esz) % 16 == 0 && (count == 1 || (stride * esz) % 16 == 0);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(count * th * tw));
+    if (in_dtype == MTQ_DTYPE_F32)
+        hipLaunchKernelGGL(pack_tiles_transposed_batched_kernel<float>, grid, dim3(256), 0, st, static_cast<const float *>(w), count, rows, cols, ld,
+                           stride, vec_ok, maps, offsets, bases, th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    else
+        hipLaunchKernelGGL(pack_tiles_transposed_batched_kernel<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(w), count, rows, cols,
+                           ld, stride, vec_ok, maps, offsets, bases, th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    return check_launch("mtq_pack_tiles_transposed_batched");
+}
+
+extern "C" int mtq_unpack_tiles_transposed_batched(const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                                   const uint64_t *bases, int64_t count, int64_t rows, int64_t cols, void *y, int out_dtype,
+                                                   int64_t ldy, int64_t stride, void *stream)
+{
+    if (!packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
+    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    int64_t th, tw;                                   // of the transpose
+    if (int rc = batch_grid(count, cols, rows, &th, &tw)) return rc;
+    if (int rc = batch_pitch(count, rows, cols, ldy, stride, "ldy < cols")) return rc;
+    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
+    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(count * th * tw));
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(unpack_tiles_transposed_batched_kernel<true>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, maps, offsets, bases, count,
+                           th * tw, tw, rows, cols, y, ldy, stride);
+    else
+        hipLaunchKernelGGL(unpack_tiles_transposed_batched_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, maps, offsets, bases, count,
+                           th * tw, tw, rows, cols, y, ldy, stride);
+    return check_launch("mtq_unpack_tiles_transposed_batched");
 }
 
 // What the block and the wide entry check before a device is looked for, and the tile grid

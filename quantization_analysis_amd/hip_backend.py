@@ -141,6 +141,8 @@ SIGNATURES = {
     "mtq_packed_glu_skinny_grouped_workspace_bytes": ("z", "lllli", True),
     "mtq_packed_glu_skinny_grouped": ("i", "plllppzppppzpppllpplipilipzp", True),
     "mtq_packed_matmul_wide": ("i", "plllpzpplppilp", True),
+    "mtq_pack_tiles_transposed_batched": ("i", "pilllllppppzp", True),
+    "mtq_unpack_tiles_transposed_batched": ("i", "pzppplllpillp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1181,6 +1183,50 @@ def unpack_tiles_transposed(data, tables: PackedTables, rows: int, cols: int, dt
         raise MtqError(f"out must be a {dtype} ({rows}, {cols}) device tensor with contiguous rows")
     ldy = out.stride(0) if rows > 1 else max(out.stride(0), cols)
     check(fn(ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, rows, cols, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+PACKED_BATCH_TRANSPOSED = ("mtq_pack_tiles_transposed_batched", "mtq_unpack_tiles_transposed_batched")
+
+
+def has_packed_batch_transposed() -> bool:
+    """Whether this build of the library has the batched transposed pack / unpack entries (optional symbols: an older build of the same
+    version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in PACKED_BATCH_TRANSPOSED)
+
+
+def pack_tiles_transposed_batched(w3d, maps_dev, offsets_dev, bases_dev, out, stream="current"):
+    """mtq_pack_tiles_transposed_batched on the current stream: a (count, rows, cols) bf16 / float32 device tensor with contiguous rows
+    (any row pitch and matrix stride: views are read in place) → the arena `out` of the streams of the (cols, rows) transposes, a uint8
+    device tensor of 64 * bases[count] bytes, tensor i's stream at byte 64 * bases[i].  The tables are over the transposes' grid."""
+    code, count, stride, rows, cols, ld = _matrix(w3d, (3,))
+    th, tw = tiles_hw(cols, rows)
+    pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+    fn = _entry("mtq_pack_tiles_transposed_batched")
+    ptr = _arena(out, count, th * tw, "out")
+    check(fn(w3d.data_ptr(), code, count, rows, cols, ld, stride, pm, po, pb, ptr, out.numel(), _packed_stream_ptr(stream)))
+    return out
+
+
+def unpack_tiles_transposed_batched(data, maps_dev, offsets_dev, bases_dev, count: int, rows: int, cols: int, dtype=None, out=None, stream="current"):
+    """mtq_unpack_tiles_transposed_batched on the current stream: the arena of `count` (cols, rows) streams → the (count, rows, cols)
+    transposes as a device tensor, float32 (the bits K3T writes) or bfloat16 (exact).  out: a tensor of that shape and type with
+    contiguous rows; what lies outside rows × cols of a pitched view stays."""
+    torch = _torch()
+    dtype = dtype or torch.float32
+    code = _packed_out_code(dtype)
+    count, rows, cols = int(count), int(rows), int(cols)
+    th, tw = tiles_hw(cols, rows)
+    pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+    ptr = _arena(data, count, th * tw, "data")
+    fn = _entry("mtq_unpack_tiles_transposed_batched")
+    if out is None:
+        require_gpu()
+        out = torch.empty((count, rows, cols), dtype=dtype, device=data.device)
+    elif out.dtype != dtype or out.dim() != 3 or tuple(out.shape) != (count, rows, cols) or out.stride(2) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {dtype} ({count}, {rows}, {cols}) device tensor with contiguous rows")
+    _code, _count, stride, _rows, _cols, ldy = _matrix(out, (3,))
+    check(fn(ptr, data.numel(), pm, po, pb, count, rows, cols, out.data_ptr(), code, ldy, stride, _packed_stream_ptr(stream)))
     return out
 
 

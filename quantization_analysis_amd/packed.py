@@ -22,8 +22,14 @@ a wave-private [k][n] LDS image), and PackedMatmul(kernel="skinny" | "auto") kee
 
 matmul_wide is the (k, n) product above the decode range from the wide-block kernel (mtq_packed_matmul_wide), the block kernel's bits.
 
+pack_batch_transposed / unpack_batch_transposed are pack_transposed / unpack_transposed for a batch of equal-shaped weights
+(count, n, k) and the maps of a layout="transpose" search: one arena of ordinary (k, n) tensors, pack_batch's launches and read-back
+(mtq_pack_tiles_transposed_batched reads each tile of W by rows through a wave-private LDS image; mtq_unpack_tiles_transposed_batched
+writes W's orientation).  scripts/pack_model.py --store-transposed packs a model under a transposed config this way; read_index gives a
+directory's index.json, where such a run marks its entries "stored": "transpose".
+
 Not built: a fused kernel for the decode range (the skinny family's split over K has partial sums); grouped and GLU variants of
-the (k, n) product; pack_batch and scripts/pack_model.py for transposed configs; pack_transposed of tensors of rank other than 2;
+the (k, n) product; pack_transposed of tensors of rank other than 2 (pack_model.py packs their permuted copies with pack);
 activations other than ACTS.
 
 Two backends:
@@ -33,7 +39,7 @@ Two backends:
 
 A map over the transposed layout (params["layout"] = "transpose") is refused by every row-layout entry (pack(layout=...), pack_batch,
 as_batch, linear, glu, ...): a group there runs down a column, and the packed format holds row groups only.  pack_transposed is the
-entry for such a map.
+entry for such a map, pack_batch_transposed for a batch of them.
 """
 from __future__ import annotations
 
@@ -640,6 +646,58 @@ def _batch_shapes(shapes, count: int, rows: int, cols: int) -> list:
     return shapes
 
 
+def _pack_batch_device(x3d, maps, rows: int, cols: int, shapes: list, pack_launch) -> list:
+    """The hip flow of pack_batch and pack_batch_transposed: `count` packed tensors of rows × cols (th × tw tiles each) from the batch x3d
+    through `pack_launch` (hip_backend.pack_tiles_batched, or pack_tiles_transposed_batched for a batch stored cols × rows)."""
+    import torch
+
+    from . import hip_backend as hb
+
+    count = int(x3d.shape[0])
+    th, tw = -(-rows // TILE), -(-cols // TILE)
+    tiles = th * tw
+    if not _is_torch(x3d):
+        x3d = torch.from_numpy(np.ascontiguousarray(x3d, dtype=np.float32))
+    if x3d.dtype not in (torch.bfloat16, torch.float32):
+        x3d = x3d.to(torch.float32)
+    if not x3d.is_cuda:
+        x3d = x3d.to(torch.device("cuda", torch.cuda.current_device()))
+    if x3d.stride(-1) != 1:
+        x3d = x3d.contiguous()
+    host_maps = None
+    if _is_torch(maps) and maps.is_cuda:
+        if maps.dtype != torch.int8 or maps.numel() != count * tiles:
+            raise MtqError(f"device maps must be int8 with {count} x {th}x{tw} entries, got {maps.dtype} with {maps.numel()}")
+        maps_dev = maps.contiguous().reshape(count, tiles)
+    else:
+        host_maps = _check_maps(maps.numpy() if _is_torch(maps) else maps, count, rows, cols)
+        maps_dev = torch.from_numpy(host_maps.reshape(count, tiles)).to(x3d.device)
+    offsets_dev, bases_dev, bad_dev = hb.packed_offsets_device(maps_dev, count, tiles)
+    # the one read-back: bases, bad and (device maps) the maps as one byte string
+    parts = [bases_dev.view(torch.uint8), bad_dev.view(torch.uint8)] + ([maps_dev.view(torch.uint8).reshape(-1)] if host_maps is None else [])
+    back = torch.cat(parts).cpu().numpy()
+    bases = back[: 8 * (count + 1)].view(np.uint64).copy()
+    bad = back[8 * (count + 1): 8 * (count + 1) + 4 * count].view(np.int32)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise MtqError(f"tensor {i} of the batch: {int(bad[i])} map codes are not MIXED_TILE_FORMATS codes 0..3 (bf16, bfp8, bfp4, bfp2)")
+    if host_maps is None:
+        host_maps = back[8 * (count + 1) + 4 * count:].view(np.int8).reshape(count, th, tw).copy()
+    arena = torch.empty((int(bases[count]) * 64,), dtype=torch.uint8, device=x3d.device)
+    pack_launch(x3d, maps_dev, offsets_dev, bases_dev, arena)
+    batch = PackedBatch(count, rows, cols, arena, bases, maps_dev, offsets_dev, bases_dev, maps=host_maps)
+    out = []
+    for i in range(count):
+        a = host_maps[i]
+        offsets = offsets_of(a)
+        if int(offsets[-1]) != int(bases[i + 1] - bases[i]):
+            raise MtqError(f"tensor {i} of the batch: the device's offsets are not those of the map")
+        tables = hb.PackedTables(a, maps_dev[i], offsets_dev[i])
+        data = arena[int(bases[i]) * 64: int(bases[i + 1]) * 64]
+        out.append(PackedTensor(shapes[i], ("nd", shapes[i]), rows, cols, a, offsets, data, _tables=tables, _batch=(batch, i)))
+    return out
+
+
 def pack_batch(x3d, maps, backend: str = "emulation", layout: str = "rows", shapes=None) -> list:
     """`count` tensors of one 2-D shape and their tile maps → a list of PackedTensor whose streams are slices of one arena.
 
@@ -660,55 +718,12 @@ def pack_batch(x3d, maps, backend: str = "emulation", layout: str = "rows", shap
     if len(x3d.shape) != 3 or 0 in tuple(x3d.shape):
         raise MtqError(f"pack_batch takes a non-empty (count, rows, cols) batch, got {tuple(x3d.shape)}")
     count, rows, cols = (int(v) for v in x3d.shape)
-    th, tw = -(-rows // TILE), -(-cols // TILE)
-    tiles = th * tw
     shapes = _batch_shapes(shapes, count, rows, cols)
     if backend == "hip":
-        import torch
-
         from . import hip_backend as hb
 
         hb.require_gpu()
-        if not _is_torch(x3d):
-            x3d = torch.from_numpy(np.ascontiguousarray(x3d, dtype=np.float32))
-        if x3d.dtype not in (torch.bfloat16, torch.float32):
-            x3d = x3d.to(torch.float32)
-        if not x3d.is_cuda:
-            x3d = x3d.to(torch.device("cuda", torch.cuda.current_device()))
-        if x3d.stride(-1) != 1:
-            x3d = x3d.contiguous()
-        host_maps = None
-        if _is_torch(maps) and maps.is_cuda:
-            if maps.dtype != torch.int8 or maps.numel() != count * tiles:
-                raise MtqError(f"device maps must be int8 with {count} x {th}x{tw} entries, got {maps.dtype} with {maps.numel()}")
-            maps_dev = maps.contiguous().reshape(count, tiles)
-        else:
-            host_maps = _check_maps(maps.numpy() if _is_torch(maps) else maps, count, rows, cols)
-            maps_dev = torch.from_numpy(host_maps.reshape(count, tiles)).to(x3d.device)
-        offsets_dev, bases_dev, bad_dev = hb.packed_offsets_device(maps_dev, count, tiles)
-        # the one read-back: bases, bad and (device maps) the maps as one byte string
-        parts = [bases_dev.view(torch.uint8), bad_dev.view(torch.uint8)] + ([maps_dev.view(torch.uint8).reshape(-1)] if host_maps is None else [])
-        back = torch.cat(parts).cpu().numpy()
-        bases = back[: 8 * (count + 1)].view(np.uint64).copy()
-        bad = back[8 * (count + 1): 8 * (count + 1) + 4 * count].view(np.int32)
-        if bad.any():
-            i = int(np.flatnonzero(bad)[0])
-            raise MtqError(f"tensor {i} of the batch: {int(bad[i])} map codes are not MIXED_TILE_FORMATS codes 0..3 (bf16, bfp8, bfp4, bfp2)")
-        if host_maps is None:
-            host_maps = back[8 * (count + 1) + 4 * count:].view(np.int8).reshape(count, th, tw).copy()
-        arena = torch.empty((int(bases[count]) * 64,), dtype=torch.uint8, device=x3d.device)
-        hb.pack_tiles_batched(x3d, maps_dev, offsets_dev, bases_dev, arena)
-        batch = PackedBatch(count, rows, cols, arena, bases, maps_dev, offsets_dev, bases_dev, maps=host_maps)
-        out = []
-        for i in range(count):
-            a = host_maps[i]
-            offsets = offsets_of(a)
-            if int(offsets[-1]) != int(bases[i + 1] - bases[i]):
-                raise MtqError(f"tensor {i} of the batch: the device's offsets are not those of the map")
-            tables = hb.PackedTables(a, maps_dev[i], offsets_dev[i])
-            data = arena[int(bases[i]) * 64: int(bases[i + 1]) * 64]
-            out.append(PackedTensor(shapes[i], ("nd", shapes[i]), rows, cols, a, offsets, data, _tables=tables, _batch=(batch, i)))
-        return out
+        return _pack_batch_device(x3d, maps, rows, cols, shapes, hb.pack_tiles_batched)
     xf = x3d.detach().to("cpu").float().numpy() if _is_torch(x3d) else np.asarray(x3d, dtype=np.float32)
     host_maps = _check_maps(maps.detach().to("cpu").numpy() if _is_torch(maps) else maps, count, rows, cols)
     streams = [encode(xf[i], host_maps[i]) for i in range(count)]
@@ -750,6 +765,77 @@ def unpack_batch(pts, backend: str = "emulation", dtype: str = "float32"):
     if dtype == "float32":
         return bits.view(np.float32)
     return torch.from_numpy((bits >> np.uint32(16)).astype(np.uint16).view(np.int16)).view(torch.bfloat16)
+
+
+def _need_batch_transposed(hb, what: str) -> None:
+    if not hb.has_packed_batch_transposed():
+        raise MtqError(f"{what} needs {' and '.join(hb.PACKED_BATCH_TRANSPOSED)}, which this build of libmtq_hip.so lacks: rebuild it from "
+                       "this tree")
+
+
+def pack_batch_transposed(w3d, maps, backend: str = "emulation") -> list:
+    """pack_transposed for a batch: `count` 2-D weights of one shape, w3d (count, n, k), under maps over the TRANSPOSES' tile grid, int8
+    (count, ceil(k/32), ceil(n/32)) - what the search pipelines give with layout="transpose" (np.stack([r.assignment ...])), as a NumPy
+    array or (hip) a device tensor.  Returns ordinary row-layout PackedTensors of shape (k, n), slices of one arena whose PackedBatch
+    has rows = k, cols = n: matmul*, PackedMatmul, unpack and unpack_batch (which give the transposes), as_batch and save_dir take them
+    as they are; unpack_batch_transposed gives W's orientation back.
+
+    hip: pack_batch's flow with mtq_pack_tiles_transposed_batched as its pack launch - w3d (a bf16 / float32 device tensor is read in
+    place, whatever its row pitch and matrix stride; no transposed copy), one offsets launch pair, one read-back (bases, bad-code
+    counts, device maps), one pack launch; a tensor with a code outside 0..3 raises MtqError before anything is packed.  Slice i is byte
+    for byte pack_transposed(w3d[i], maps[i]).  emulation: pack_batch of the transposed copies."""
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    if len(w3d.shape) != 3 or 0 in tuple(w3d.shape):
+        raise MtqError(f"pack_batch_transposed takes a non-empty (count, n, k) batch, got {tuple(w3d.shape)}")
+    count, n, k = (int(v) for v in w3d.shape)
+    th, tw = -(-k // TILE), -(-n // TILE)
+    given = tuple(int(v) for v in (maps.shape if _is_torch(maps) else np.shape(maps)))
+    if len(given) == 3 and given != (count, th, tw):
+        raise MtqError(f"the maps are {'x'.join(map(str, given))}, {count} transposed weights have {count}x{th}x{tw} tiles: "
+                       "pack_batch_transposed takes maps over the transposes' grid")
+    if backend == "hip":
+        from . import hip_backend as hb
+
+        _need_batch_transposed(hb, "pack_batch_transposed")
+        hb.require_gpu()
+        return _pack_batch_device(w3d, maps, k, n, [(k, n)] * count, hb.pack_tiles_transposed_batched)
+    wf = w3d.detach().to("cpu").float().numpy() if _is_torch(w3d) else np.asarray(w3d, dtype=np.float32)
+    return pack_batch(np.ascontiguousarray(wf.transpose(0, 2, 1)), maps, backend="emulation")
+
+
+def unpack_batch_transposed(pts, backend: str = "emulation", dtype: str = "float32"):
+    """unpack_transposed for a list of equal-shaped packed (k, n) tensors: the (count, n, k) weights whose packed transposes they are,
+    float32 (bit for bit K3T's) or bfloat16 (exact).  hip: one launch of mtq_unpack_tiles_transposed_batched when the list is one whole
+    batch in order, tensor by tensor through mtq_unpack_tiles_transposed otherwise → a device tensor.  emulation: unpack_batch,
+    transposed → a NumPy float32 array, or a torch CPU bfloat16 tensor."""
+    pts = list(pts)
+    if not pts:
+        raise MtqError("unpack_batch_transposed needs at least one packed tensor")
+    for pt in pts:
+        _check_kn(pt, "unpack_batch_transposed")
+    if dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"dtype must be 'float32' or 'bfloat16', got {dtype!r}")
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    k, n = pts[0].rows, pts[0].cols
+    if any((pt.rows, pt.cols) != (k, n) for pt in pts):
+        raise MtqError("unpack_batch_transposed takes tensors of one 2-D shape")
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        hb.require_gpu()
+        tdtype = torch.float32 if dtype == "float32" else torch.bfloat16
+        batch = batch_of(pts)
+        if batch is not None and batch.maps_dev is not None:
+            _need_batch_transposed(hb, "unpack_batch_transposed")
+            return hb.unpack_tiles_transposed_batched(batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, batch.count, n, k, tdtype)
+        _need_matmul(hb, "unpack_batch_transposed")
+        return torch.stack([hb.unpack_tiles_transposed(_device_data(pt), pt.tables(), n, k, tdtype) for pt in pts])
+    y = unpack_batch(pts, backend="emulation", dtype=dtype)
+    return y.transpose(1, 2).contiguous() if _is_torch(y) else np.ascontiguousarray(y.transpose(0, 2, 1))
 
 
 def _resolve_batch(pts_or_batch) -> PackedBatch:
@@ -1697,21 +1783,33 @@ def save_dir(path, named: dict, meta=None, run=None) -> dict:
     return index
 
 
-def load_dir(path, device=None) -> dict:
-    """`path` as save_dir wrote it → {tensor name: PackedTensor}, each file checked against its index entry (an unknown format version, a
-    missing file, another shape or a stream of another length than the index says is refused).  device: a torch device the streams are
-    uploaded to."""
+def read_index(path) -> dict:
+    """The index.json of a directory save_dir wrote, as a dict, after the checks load_dir makes of it (the file is there and its format
+    version is this package's): "run" and, per tensor under "tensors", the entry save_dir wrote with the caller's meta - where
+    scripts/pack_model.py --store-transposed records "stored": "transpose" and "source_shape" for a tensor whose packed form is its
+    transpose's."""
     import json
     from pathlib import Path
 
-    root = Path(path)
-    file = root / INDEX_NAME
+    file = Path(path) / INDEX_NAME
     if not file.exists():
         raise MtqError(f"{file} is missing: not a directory of packed tensors")
     index = json.loads(file.read_text(encoding="utf-8"))
     version = index.get("format_version") if isinstance(index, dict) else None
     if version != FORMAT_VERSION:
         raise MtqError(f"{file}: packed format version {version}, this package reads version {FORMAT_VERSION}")
+    return index
+
+
+def load_dir(path, device=None) -> dict:
+    """`path` as save_dir wrote it → {tensor name: PackedTensor}, each file checked against its index entry (an unknown format version, a
+    missing file, another shape or a stream of another length than the index says is refused).  device: a torch device the streams are
+    uploaded to."""
+    from pathlib import Path
+
+    root = Path(path)
+    file = root / INDEX_NAME
+    index = read_index(root)
     out = {}
     for name, entry in index.get("tensors", {}).items():
         f = root / str(entry.get("file"))

@@ -2,6 +2,7 @@
 """Search a model's tile maps under a compression config and write the packed weights the maps promise.
 
   pack_model.py MODEL [FILTER ...] --compression-config CFG --out-dir DIR [--backend hip|emulation] [--verify] [--limit N]
+                [--store-transposed]
 
 MODEL and FILTER are wq's: 'synthetic:<preset>[:seed]' or a local directory of *.safetensors, and an optional name filter.  DIR gets one
 <slug>.npz per tensor (packed.save) and an index.json (packed.save_dir) that also records the run (algorithm, parameters, the seed used)
@@ -15,7 +16,17 @@ takes the per-tensor path: the algorithm's run() and packed.pack.
 --verify unpacks what was packed and compares it bit for bit with the reconstruction: K3 (apply_assignment) on the batched path, the
 algorithm's own y on the per-tensor path.  A mismatch is reported per tensor and the exit status is 2.
 
-The packed format is the row layout: a config with "layout": "transpose" is refused (exit status 1)."""
+The packed format is the row layout: a config with "layout": "transpose" is refused (exit status 1) unless --store-transposed is given.
+
+--store-transposed (only with a "layout": "transpose" config; exit status 1 otherwise): every tensor's TRANSPOSE is packed under the map
+the search wrote for it, as pack_mixed_tile_assignment.py --store-transposed does for one tensor.  On hip with greedy or threshold the
+2-D tensors are grouped as above, the resident batch goes through the pipeline built with layout="transpose" and, with the results'
+maps, to packed.pack_batch_transposed, which reads it in place; --verify compares packed.unpack_batch_transposed with K3T
+(apply_assignment_transposed).  Every other case takes the per-tensor path: the algorithm's run() with the layout in its params, then
+packed.pack_transposed (2-D) or packed.pack of the permuted copy np.transpose(x) (other ranks; a vector is its own transpose), verified
+against the algorithm's own y brought to the stored orientation.  Every index entry says "stored": "transpose" and keeps the tensor's
+own shape as "source_shape"; "shape" is the packed tensor's, so packed.load_dir reads the directory as any other and its 2-D entries,
+of shape (k, n), go to packed.PackedMatmul (packed.read_index shows which entries those are)."""
 from __future__ import annotations
 
 import argparse
@@ -39,9 +50,13 @@ from quantization_analysis_amd.quantization_formats import SUPPORTED_FORMATS
 MIXED_ALGOS = ("mixed-tile-greedy", "mixed-tile-threshold", "mixed-tile-random")
 
 
-def _bits(y) -> np.ndarray:
+def _host(y) -> np.ndarray:
     y = y.cpu().numpy() if hasattr(y, "cpu") else np.asarray(y)
-    return np.ascontiguousarray(y, dtype=np.float32).view(np.uint32)
+    return np.ascontiguousarray(y, dtype=np.float32)
+
+
+def _bits(y) -> np.ndarray:
+    return _host(y).view(np.uint32)
 
 
 def _differing(got, want) -> int:
@@ -53,19 +68,22 @@ def _differing(got, want) -> int:
 class _Packer:
     """The run: tensors in, {name: PackedTensor} and their index entries out."""
 
-    def __init__(self, index, algo, formats, backend: str, verify: bool, cache_root: Path):
+    def __init__(self, index, algo, formats, backend: str, verify: bool, cache_root: Path, transposed: bool = False):
         self.index, self.algo, self.formats, self.backend, self.verify = index, algo, formats, backend, verify
+        self.transposed = transposed                 # --store-transposed: the packed tensors are the transposes'
         self.quantizer = Quantizer(backend=backend)
         self.cache_root = cache_root
         self.named, self.meta, self.mismatches = {}, {}, []
         self.batches = 0
 
-    def _add(self, name: str, pt, metric_value, route: str, differing) -> None:
+    def _add(self, name: str, pt, metric_value, route: str, differing, source_shape=None) -> None:
         counts = pt.counts()
         model = float(mixed_tile_total_bytes(counts))
         self.named[name] = pt
         self.meta[name] = {"size_model_bytes": model, "metric": self.algo.params.get("metric", "pcc"),
                            "metric_value": None if metric_value is None else float(metric_value), "route": route}
+        if self.transposed:
+            self.meta[name].update(stored="transpose", source_shape=[int(v) for v in source_shape])
         if differing is not None:
             self.meta[name]["verified"] = differing == 0
             if differing != 0:
@@ -84,13 +102,23 @@ class _Packer:
         cache = CacheContext(root=self.cache_root, tensor_name=name, backend=self.backend, recompute=True, run_tag="pack")
         res = next(r for r in self.algo.run(xf=x, formats=self.formats, quantizer=self.quantizer, cache=cache) if r.fmt == "MIXED")
         meta = res.meta or {}
-        pt = packed.pack(x, meta["assignment"], backend=self.backend)
+        want = res.y
+        if not self.transposed:
+            pt = packed.pack(x, meta["assignment"], backend=self.backend)
+        else:                                        # the stored orientation is np.transpose(x)'s, the one the map was written over
+            if len(x.shape) == 2:
+                pt = packed.pack_transposed(x, meta["assignment"], backend=self.backend)
+            else:
+                xt = x.permute(*reversed(range(x.dim()))).contiguous() if self.backend == "hip" else np.ascontiguousarray(np.transpose(x))
+                pt = packed.pack(xt, meta["assignment"], backend=self.backend)
+            want = np.transpose(_host(want)) if self.verify else None
         value = meta.get("metric_value", (meta.get("columns") or {}).get(self.algo.params.get("metric", "pcc")))
-        differing = _differing(packed.unpack(pt, backend=self.backend), res.y) if self.verify else None
-        self._add(name, pt, value, "per-tensor", differing)
+        differing = _differing(packed.unpack(pt, backend=self.backend), want) if self.verify else None
+        self._add(name, pt, value, "per-tensor", differing, source_shape=tuple(x.shape))
 
     def batched(self, names: list) -> None:
-        """The streamed route's groups: the search pipeline over a resident batch, then pack_batch on the same batch and the results' maps."""
+        """The streamed route's groups: the search pipeline over a resident batch, then pack_batch (--store-transposed: the transposed
+        pipeline and pack_batch_transposed) on the same batch and the results' maps."""
         import torch
 
         from quantization_analysis_amd import hip_backend as hb
@@ -101,11 +129,11 @@ class _Packer:
         tile_formats = a.tile_formats or [f for f in self.formats if f in MIXED_TILE_FORMATS]
         groups: dict = {}
         for name in names:
-            groups.setdefault(streamed.group_key(self.index, name), []).append(name)
+            groups.setdefault(streamed.group_key(self.index, name, layout=a.layout), []).append(name)
         if a.name == "mixed-tile-greedy":
-            pipe = GreedyPipeline(tile_formats, a.metric, a.threshold, a.seed, chunk=1, workers=default_workers())
+            pipe = GreedyPipeline(tile_formats, a.metric, a.threshold, a.seed, chunk=1, workers=default_workers(), layout=a.layout)
         else:
-            pipe = ThresholdPipeline(tile_formats, a.metric, a.threshold, chunk=1)
+            pipe = ThresholdPipeline(tile_formats, a.metric, a.threshold, chunk=1, layout=a.layout)
         with pipe:
             for (rows, cols, _dtype), items in groups.items():
                 tiles = -(-rows // 32) * -(-cols // 32)
@@ -117,12 +145,17 @@ class _Packer:
                     pipe.chunk = min(max(1, streamed.K1_LAUNCH_TILES // tiles), len(part))
                     results = pipe.run(x3d)
                     maps = np.stack([r.assignment for r in results])
-                    pts = packed.pack_batch(x3d, maps, backend="hip", shapes=[tuple(x.shape) for x in xs])
+                    if self.transposed:
+                        pts = packed.pack_batch_transposed(x3d, maps, backend="hip")
+                        unpack_batch, k3 = packed.unpack_batch_transposed, hb.apply_assignment_transposed
+                    else:
+                        pts = packed.pack_batch(x3d, maps, backend="hip", shapes=[tuple(x.shape) for x in xs])
+                        unpack_batch, k3 = packed.unpack_batch, hb.apply_assignment
                     self.batches += 1
-                    y = packed.unpack_batch(pts, backend="hip") if self.verify else None
+                    y = unpack_batch(pts, backend="hip") if self.verify else None
                     for i, (name, r, pt) in enumerate(zip(part, results, pts)):
-                        differing = _differing(y[i], hb.apply_assignment(x3d[i], r.assignment)) if self.verify else None
-                        self._add(name, pt, r.metric_value, "batched", differing)
+                        differing = _differing(y[i], k3(x3d[i], r.assignment)) if self.verify else None
+                        self._add(name, pt, r.metric_value, "batched", differing, source_shape=tuple(xs[i].shape))
                     del xs, x3d, y
 
 
@@ -136,6 +169,8 @@ def main(argv=None) -> int:
     p.add_argument("--revision", default="main")
     p.add_argument("--limit", type=int, default=None, help="Optional max matched tensors.")
     p.add_argument("--verify", action="store_true", help="Unpack every tensor and compare it bit for bit with the reconstruction.")
+    p.add_argument("--store-transposed", action="store_true",
+                   help='With a "layout": "transpose" config: pack every tensor\'s transpose under its map (2-D tensors become (k, n) row-layout tensors).')
     args = p.parse_args(argv)
 
     try:
@@ -145,7 +180,12 @@ def main(argv=None) -> int:
         algo = create_algorithm(config.algorithm, params)
         if algo.name not in MIXED_ALGOS:
             raise MtqError(f"algorithm {algo.name!r} writes no tile map: pack_model needs one of {', '.join(MIXED_ALGOS)}")
-        packed.check_layout(getattr(algo, "layout", "rows"))
+        layout = getattr(algo, "layout", "rows")
+        if args.store_transposed and layout != "transpose":
+            raise MtqError('--store-transposed packs the tensors\' transposes under maps written for "layout": "transpose"; this config\'s '
+                           f"layout is {layout!r}")
+        if not args.store_transposed:
+            packed.check_layout(layout)
         formats = resolve_format_list(config.quantization_formats, SUPPORTED_FORMATS)
         index = build_model_index(args.repo_or_url, revision=args.revision)
         try:
@@ -161,7 +201,7 @@ def main(argv=None) -> int:
         return 1
 
     out_dir = Path(args.out_dir)
-    run = _Packer(index, algo, formats, args.backend, args.verify, out_dir / "cache")
+    run = _Packer(index, algo, formats, args.backend, args.verify, out_dir / "cache", transposed=args.store_transposed)
     print(f"{index.repo_id} @{index.revision} - {len(names)} tensors, {algo.name} {params}, backend {args.backend}")
     try:
         batch_names = []
@@ -170,7 +210,7 @@ def main(argv=None) -> int:
                 from quantization_analysis_amd import hip_backend as hb
 
                 hb.require_gpu()
-            batch_names = [n for n in names if streamed.group_key(index, n) is not None]
+            batch_names = [n for n in names if streamed.group_key(index, n, layout=layout) is not None]
             run.batched(batch_names)
         for name in names:
             if name not in run.named:
@@ -180,7 +220,7 @@ def main(argv=None) -> int:
         return 1
     named = {n: run.named[n] for n in names}
     info = {"model": index.repo_id, "revision": index.revision, "algorithm": algo.name, "params": params, "seed": used_seed, "seed_source": seed_source,
-            "backend": args.backend, "formats": list(formats)}
+            "backend": args.backend, "formats": list(formats), **({"layout": layout, "stored": "transpose"} if args.store_transposed else {})}
     packed.save_dir(out_dir, named, meta=run.meta, run=info)
     total = sum(pt.nbytes for pt in named.values())
     total_all = sum(pt.total_bytes for pt in named.values())
