@@ -920,6 +920,69 @@ int mtq_packed_linear_wide_grouped(const void *x, int64_t total_rows, int64_t k,
                                    int64_t n, const float *bias, int64_t ldb, void *y, int out_dtype, int64_t ldy, void *workspace,
                                    size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ grouped matmul: (k, n) experts of one arena in one launch
+ * The three grouped entries above for experts stored as packed k x n tensors (mtq_packed_matmul's weight: the transposed BFP layout, or
+ * an input-major weight): `count` experts of one (k, n) shape in ONE arena (mtq_pack_tiles_transposed_batched's or
+ * mtq_pack_tiles_batched's maps / offsets / bases), each multiplied with its own rows of x:
+ *   y[r0:r1] = x[r0:r1] · P̂[e] (+ bias[e]),   P̂[e] the packed k x n expert e.
+ * n is the output width and k the contraction.  The map grid of an expert is ceil(k/32) x ceil(n/32), tiles_kh x tiles_nw;
+ * tiles = tiles_kh * tiles_nw is the stride of maps and tiles + 1 that of offsets.  The parameter list of each entry is that of the
+ * mtq_packed_linear_*_grouped* entry of the same name, one for one and in the same order, and group_rows, its clamping, overlapping
+ * groups (unspecified rows inside the allocation), rows of no group (not written), bias, ldb and the workspace rules are as stated
+ * there.
+ *
+ * mtq_packed_matmul_skinny_grouped: mtq_packed_matmul_skinny's wave, one per (slice, group, tile column) - 32 output columns over
+ * one K slice of whole tile rows of expert e's tables, through two wave-private [32 k][32 n] LDS images and the transposed LDS read; a
+ * group above 32 rows is walked in chunks of 32 rows by the same wave.  The effective split and the size function are
+ * mtq_packed_linear_skinny_grouped's for the same (total_rows, count, n, k, split): the single-tensor rule with count * ceil(n/32)
+ * output tile rows and ceil(k/32) contraction tiles.  An effective split above 1 writes f32 partials to
+ * workspace[slice][total_rows][n] and the grouped linear entry's reduce kernel finishes.
+ *
+ * mtq_packed_matmul_skinny_grouped_chunked: the same wave per (slice, 32-row chunk slot, tile column); the chunk list, the slot bound
+ * U, the early return of surplus waves, the search and the never-empty workspace (plan first, partials behind) are
+ * mtq_packed_linear_skinny_grouped_chunked's, and so is the size function's answer.
+ *
+ * mtq_packed_matmul_wide_grouped: mtq_packed_matmul_wide's 128 x 128 block in mtq_packed_linear_wide_grouped's frame - the block plan
+ * on the device, U x ceil(n/128) workgroups with the column block fastest, every row limit the group's clamped end; the workspace holds
+ * the plan only.
+ *
+ * Bit contracts.  For nondecreasing group_rows and every group with rows:
+ *  - both skinny entries equal, bit for bit, what mtq_packed_matmul_skinny gives for each 32-row chunk of the group with expert e's
+ *    stream and tables (and bias row e) at the same effective split; they therefore equal each other, and they equal
+ *    mtq_packed_linear_skinny_grouped on the arena of the all-bf16 row-layout packings of unpack(P̂[e])ᵀ at the same `split`, 0 included
+ *    (mtq_packed_matmul_skinny's contract, chunk by chunk; the split rules are the same function of the same arguments);
+ *  - the wide entry equals what mtq_packed_matmul gives for x[r0:r1] with expert e's stream and tables, which mtq_packed_matmul_wide
+ *    gives too: the block family's bits, not the skinny family's.
+ * In both output types, with and without bias, for any ldx / ldy.  Deterministic: no atomics, no counters, nothing waits on another
+ * workgroup, nothing in a workspace needs initialising.
+ *
+ * Device guards: a tile whose blob passes its group's [64 * bases[e], 64 * bases[e + 1]) or packed_bytes, or whose map code is outside
+ * 0..3, multiplies as zeros in its own tile only; k-rows of P̂[e] at or past k count as zeros whatever their bytes hold; a chunk's (a
+ * block's) rows end at its group's clamped end for every load of x; columns at or past n are never stored.
+ *
+ * Argument checks are the grouped linear entries', with mtq_packed_matmul's grid check for a k x n tensor (null pointers, total_rows,
+ * count, n, k positive, a negative split, ldx < k, ldy < n, ldb < n, an arena below 320 bytes per tile or not 16-byte aligned, a
+ * workspace that is null, not 16-byte aligned or too short where one is needed): MTQ_ERR_INVALID before a device is looked for.
+ *
+ * All six symbols are optional: a build of this version may lack them. */
+/* HOST functions: bytes of workspace, equal to the mtq_packed_linear_*_grouped* answer for the same arguments; (size_t)-1 for
+ * MTQ_ERR_INVALID arguments. */
+size_t mtq_packed_matmul_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split);
+int mtq_packed_matmul_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows, const void *packed,
+                                     size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, int64_t count,
+                                     int64_t n, const float *bias, int64_t ldb, void *y, int out_dtype, int64_t ldy, int split,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+size_t mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split);
+int mtq_packed_matmul_skinny_grouped_chunked(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                             const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                             const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                             int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream);
+size_t mtq_packed_matmul_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k);
+int mtq_packed_matmul_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows, const void *packed,
+                                   size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, int64_t count,
+                                   int64_t n, const float *bias, int64_t ldb, void *y, int out_dtype, int64_t ldy, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ gated MLP (SwiGLU) on packed weights
  * h = act(x·Ŵgᵀ + bg) * (x·Ŵuᵀ + bu), the first half of down(act(gate(x)) * up(x)), with the gate and the up projection as two
  * packed (n, k) weights of the format above (nothing is repacked: the tile rows of a packed weight are independent blobs).

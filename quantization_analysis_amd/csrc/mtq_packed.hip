@@ -1218,6 +1218,16 @@ struct FeedTransposed {
     }
 };
 
+// the lane's part of a FeedTransposed in the wave's pair of images
+__device__ __forceinline__ FeedTransposed feed_transposed(uint16_t *img, int lane)
+{
+    FeedTransposed feed;
+    feed.st = img + lane * kGroup;
+    feed.rd = img + (kGroup * (lane >> 5) + ((lane >> 2) & 3)) * kMmPitch + kGroup * ((lane >> 4) & 1) + 4 * (lane & 3);
+    feed.up = (lane >> 2) & 1;
+    return feed;
+}
+
 template <bool BF16OUT>
 __global__ __launch_bounds__(64 * kSkinnyWaves) void packed_matmul_skinny_kernel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx,
                                                                                   int x_vec, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
@@ -1233,11 +1243,7 @@ __global__ __launch_bounds__(64 * kSkinnyWaves) void packed_matmul_skinny_kernel
     const int64_t s = unit / tiles_nw, tc = unit % tiles_nw;   // the waves of a workgroup share a slice of X
     const int row = lane & 31, half = lane >> 5;
 
-    uint16_t *img = lds + wave * (2 * kMmsImage);
-    FeedTransposed feed;
-    feed.st = img + lane * kGroup;
-    feed.rd = img + (kGroup * half + ((lane >> 2) & 3)) * kMmPitch + kGroup * ((lane >> 4) & 1) + 4 * (lane & 3);
-    feed.up = (lane >> 2) & 1;
+    const FeedTransposed feed = feed_transposed(lds + wave * (2 * kMmsImage), lane);
 
     // the run is tile column tc over the slice's tile rows: tiles tiles_nw apart (a strided gather of the tables), group `lane`
     f32x16 acc = zero16();
@@ -1404,6 +1410,87 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_linear_skinny_gro
                half, 2 * row + half);
 
     // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row)
+    if (n >= N) return;
+    store_skinny<BF16OUT>(acc, M, half, row0, n, split, split == 1 && bias ? bias[e * ldb + n] : 0.0f, yv, ldy, ws, s, T, N);
+}
+
+// ---- grouped skinny matmul: the (k, n) experts of one arena, each over its own rows of X, in one launch.
+//
+// packed_matmul_skinny_kernel's wave in the two grouped frames above.  The walk kernel's unit is (slice s, group e, tile column tc),
+// numbered (s * count + e) * tiles_nw + tc, the chunked kernel's (slice s, chunk slot c, tile column tc), numbered
+// (s * slots + c) * tiles_nw + tc; the run is tiles tc + c * tiles_nw of expert e's tables over the slice's tile rows, through the wave's
+// two [32 k][32 n] images.  On a 32-row chunk the wave does what packed_matmul_skinny_kernel does for an m <= 32 call on that chunk with
+// expert e's stream and tables at the same split: that call's bits, hence the grouped linear kernels' on the transposed weight.
+//
+// EXEC at the transposed reads.  Everything a branch before or between runs depends on is wave-uniform and held in scalar registers: the
+// wave index, the unit, the group's clamped rows and the chunk's first row go through readfirstlane, so "unit past the grid", "empty
+// group", "surplus slot", "row0 >= r1" and the walk kernel's chunk loop (its trip count is the group's alone) are scalar branches taken
+// by the whole wave or by none of it.  The one lane-dependent branch is the n < N guard around the stores, after a run; EXEC is whole
+// again behind it, before the next chunk's run.  M = min(32, r1 - row0) is the row limit of every X load of a chunk; k-rows at or
+// past K and tiles with a bad code or a blob outside [64 bases[e], 64 bases[e + 1]) or past packed_bytes are zeros in the image.
+
+template <bool BF16OUT>
+__global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_matmul_skinny_grouped_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
+    const uint8_t *__restrict__ packed, uint64_t packed_bytes, const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets,
+    const uint64_t *__restrict__ bases, int count, int N, int tiles_kh, int tiles_nw, int split, const float *__restrict__ bias, int64_t ldb,
+    void *__restrict__ yv, int64_t ldy, float *__restrict__ ws)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[kSkinnyWaves * 2 * kMmsImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= (int64_t)tiles_nw * count * split) return;  // wave-uniform; the kernel has no workgroup barrier
+    const int64_t tc = unit % tiles_nw, se = unit / tiles_nw, e = se % count, s = se / count;
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    const int r0 = __builtin_amdgcn_readfirstlane((int)gr.r0), r1 = __builtin_amdgcn_readfirstlane((int)gr.r1);   // 0 <= r0 <= r1 <= T
+    if (r1 == r0) return;                            // nothing of this expert is read
+    const PackedStream st = arena_stream(packed, packed_bytes, maps, offsets, bases, e, (int64_t)tiles_kh * tiles_nw);
+    const int64_t c0 = s * tiles_kh / split, c1 = (s + 1) * tiles_kh / split;
+    uint16_t *img = lds + wave * (2 * kMmsImage);
+
+    for (int64_t row0 = r0; row0 < r1; row0 += kTile) {   // scalar: the trip count is the group's
+        int lv = lane;
+        asm volatile("" : "+v"(lv));                 // the lane's addresses are formed per chunk, not kept in registers across chunks
+        const int row = lv & 31, half = lv >> 5;
+        const int64_t n = tc * kTile + row;
+        const int64_t M = std::min<int64_t>(kTile, r1 - row0);
+        f32x16 acc = zero16();
+        skinny_run(acc, feed_transposed(img, lv), x + row0 * ldx, M, K, ldx, x_vec, st, tc, tiles_nw, c0, c1, lane, row, half, lv);
+
+        // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tc + row)
+        if (n < N) store_skinny<BF16OUT>(acc, M, half, row0, n, split, split == 1 && bias ? bias[e * ldb + n] : 0.0f, yv, ldy, ws, s, T, N);
+    }
+}
+
+template <bool BF16OUT>
+__global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_matmul_skinny_grouped_chunked_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
+    const int32_t *__restrict__ cstart, int slots, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+    const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets, const uint64_t *__restrict__ bases, int count, int N, int tiles_kh,
+    int tiles_nw, int split, const float *__restrict__ bias, int64_t ldb, void *__restrict__ yv, int64_t ldy, float *__restrict__ ws)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[kSkinnyWaves * 2 * kMmsImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= (int64_t)tiles_nw * slots * split) return;  // wave-uniform; the kernel has no workgroup barrier
+    const int64_t tc = unit % tiles_nw, sc = unit / tiles_nw, s = sc / slots;
+    const int c = (int)(sc % slots);
+    if (c >= cstart[count]) return;                  // a surplus slot: nothing else is read
+    const int e = __builtin_amdgcn_readfirstlane(group_of_slot(cstart, count, c, lane));
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    const int r1 = __builtin_amdgcn_readfirstlane((int)gr.r1);
+    const int64_t row0 = __builtin_amdgcn_readfirstlane((int)gr.r0) + (int64_t)(c - __builtin_amdgcn_readfirstlane(cstart[e])) * kTile;
+    if (row0 >= r1) return;                          // never for a prefix this launch's plan kernel wrote
+    const PackedStream st = arena_stream(packed, packed_bytes, maps, offsets, bases, e, (int64_t)tiles_kh * tiles_nw);
+
+    const int row = lane & 31, half = lane >> 5;
+    const int64_t n = tc * kTile + row;
+    const int64_t M = std::min<int64_t>(kTile, r1 - row0);
+    f32x16 acc = zero16();
+    skinny_run(acc, feed_transposed(lds + wave * (2 * kMmsImage), lane), x + row0 * ldx, M, K, ldx, x_vec, st, tc, tiles_nw, s * tiles_kh / split,
+               (s + 1) * tiles_kh / split, lane, row, half, lane);
+
+    // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tc + row)
     if (n >= N) return;
     store_skinny<BF16OUT>(acc, M, half, row0, n, split, split == 1 && bias ? bias[e * ldb + n] : 0.0f, yv, ldy, ws, s, T, N);
 }
@@ -1795,6 +1882,32 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_grouped_kernel
     const PackedStream st = arena_stream_uniform(packed, packed_bytes, maps, offsets, bases, b.e, tiles_h * tiles_w);
     wide_block<false, XV, BF16OUT>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + wave, n0, N, tiles_h, tiles_w, bias ? bias + b.e * ldb : nullptr,
                                    nullptr, 0, yv, ldy, wave);
+}
+
+// ---- grouped wide matmul: packed_matmul_wide_kernel's block for every (k, n) expert of an arena over the expert's own rows, one launch.
+//
+// The frame above with wide_block<.., WT = true>: the plan (packed_grouped_plan_kernel<128>), the slot bound, the grid of slots ×
+// ceil(N / 128) with the column block fastest, the search and the stream in scalar registers are that kernel's; wave w stages tile COLUMN
+// n0 / 32 + w of expert e's k × n tables, and M is the group's clamped end.  The same function as packed_matmul_wide_kernel on x[r0:r1]
+// with expert e's stream, so that kernel's bits, which are packed_matmul_kernel's.
+// EXEC is all ones at every transposed read: the surplus-slot return is taken by the whole workgroup before any barrier, and everything
+// behind it is wide_block's wave-uniform control flow.
+template <bool XV, bool BF16OUT>
+__global__ __launch_bounds__(kThreads, 2) void packed_matmul_wide_grouped_kernel(
+    const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
+    const uint8_t *__restrict__ packed, uint64_t packed_bytes, const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets,
+    const uint64_t *__restrict__ bases, int count, int64_t N, int64_t tiles_kh, int64_t tiles_nw, const float *__restrict__ bias, int64_t ldb,
+    void *__restrict__ yv, int64_t ldy)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
+    const int64_t n0 = (blockIdx.x % nblocks) * kWideBN;
+    GroupBlock b;
+    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;
+    const PackedStream st = arena_stream_uniform(packed, packed_bytes, maps, offsets, bases, b.e, tiles_kh * tiles_nw);
+    wide_block<false, XV, BF16OUT, true>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + wave, n0, N, tiles_kh, tiles_nw,
+                                         bias ? bias + b.e * ldb : nullptr, nullptr, 0, yv, ldy, wave);
 }
 
 // ---- gated wide linear (SwiGLU): glu_value(X·Ŵgᵀ + bg, X·Ŵuᵀ + bu) from packed_linear_wide_kernel's step, one launch, one store.
@@ -2610,6 +2723,128 @@ extern "C" int mtq_packed_linear_wide_grouped(const void *x, int64_t total_rows,
                static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(packed),
                (uint64_t)packed_bytes, maps, offsets, bases, (int)count, n, g.th, g.tw, bias, ldb, y, ldy);
     return check_launch("mtq_packed_linear_wide_grouped");
+}
+
+// ---- grouped entries for (k, n) experts: the grouped linear entries' checks, split rule, slot bounds and workspaces (tile_grid of n × k
+// is the grid check of k × n, mtq_packed_matmul's), the kernels with the grid the other way round.
+extern "C" size_t mtq_packed_matmul_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    int64_t th, tw;
+    int eff;
+    if (grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
+    return skinny_workspace(total_rows, n, eff);
+}
+
+extern "C" int mtq_packed_matmul_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                                const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                                int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
+                           bias != nullptr, ldb, count, w, w))
+        return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(total_rows, n, g.eff), kWsSplit, "split")) return rc;
+    const int64_t blocks = (count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    const int64_t nchunks = (n + 255) / 256;
+    if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    launch_out(out_dtype, packed_matmul_skinny_grouped_kernel<true>, packed_matmul_skinny_grouped_kernel<false>, dim3((unsigned)blocks),
+               dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx), group_rows,
+               static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.tw, g.th, g.eff, bias, ldb, y, ldy, ws);
+    if (g.eff > 1) {
+        if (int rc = check_launch("mtq_packed_matmul_skinny_grouped")) return rc;
+        launch_out(out_dtype, skinny_grouped_reduce_kernel<true>, skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
+                   st, ws, total_rows, n, g.eff, group_rows, nchunks, bias, ldb, y, ldy);
+    }
+    return check_launch("mtq_packed_matmul_skinny_grouped");
+}
+
+extern "C" size_t mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    int64_t th, tw;
+    int eff;
+    if (grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
+    return grouped_plan_bytes(count) + skinny_workspace(total_rows, n, eff);
+}
+
+extern "C" int mtq_packed_matmul_skinny_grouped_chunked(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                        const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                                        const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                                        int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                                        void *stream)
+{
+    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
+                           bias != nullptr, ldb, count, w, w))
+        return rc;
+    const size_t plan = grouped_plan_bytes(count);
+    if (int rc = workspace_args(workspace, workspace_bytes, plan + skinny_workspace(total_rows, n, g.eff),
+                                "workspace is null and the chunk plan needs one at every split", "call"))
+        return rc;
+    // every chunk of disjoint groups has a slot: a group with rows adds at most 31/32 of a chunk over its rows / 32
+    const int64_t slots = (total_rows + 31 * std::min(count, total_rows)) / kTile;
+    const int64_t blocks = (slots * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    const int64_t nchunks = (n + 255) / 256;
+    if (slots > INT32_MAX || blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *cstart = static_cast<int32_t *>(workspace);
+    float *ws = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + plan);
+    hipLaunchKernelGGL(packed_grouped_plan_kernel<kTile>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, cstart);
+    if (int rc = check_launch("mtq_packed_matmul_skinny_grouped_chunked")) return rc;
+    launch_out(out_dtype, packed_matmul_skinny_grouped_chunked_kernel<true>, packed_matmul_skinny_grouped_chunked_kernel<false>,
+               dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx),
+               group_rows, cstart, (int)slots, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.tw, g.th,
+               g.eff, bias, ldb, y, ldy, ws);
+    if (g.eff > 1) {
+        if (int rc = check_launch("mtq_packed_matmul_skinny_grouped_chunked")) return rc;
+        launch_out(out_dtype, skinny_grouped_reduce_kernel<true>, skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
+                   st, ws, total_rows, n, g.eff, group_rows, nchunks, bias, ldb, y, ldy);
+    }
+    return check_launch("mtq_packed_matmul_skinny_grouped_chunked");
+}
+
+extern "C" size_t mtq_packed_matmul_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
+{
+    int64_t th, tw;
+    int eff;
+    if (grouped_shape(total_rows, count, n, k, 1, &th, &tw, &eff)) return (size_t)-1;   // split 1: no split over K, no partials
+    return grouped_plan_bytes(count);
+}
+
+extern "C" int mtq_packed_matmul_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                              const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                              const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                              int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream)
+{
+    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
+                           bias != nullptr, ldb, count, w, w))
+        return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
+    // every block of disjoint groups has a slot: a group with rows adds at most 127/128 of a block over its rows / 128
+    const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
+    const int64_t blocks = slots * ((n + kWideBN - 1) / kWideBN);
+    if (slots > INT32_MAX || blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *bstart = static_cast<int32_t *>(workspace);
+    hipLaunchKernelGGL(packed_grouped_plan_kernel<kWideBM>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
+    if (int rc = check_launch("mtq_packed_matmul_wide_grouped")) return rc;
+    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_matmul_wide_grouped_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), st,
+               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(packed),
+               (uint64_t)packed_bytes, maps, offsets, bases, (int)count, n, g.tw, g.th, bias, ldb, y, ldy);
+    return check_launch("mtq_packed_matmul_wide_grouped");
 }
 
 // ---- gated entries

@@ -143,6 +143,12 @@ SIGNATURES = {
     "mtq_packed_matmul_wide": ("i", "plllpzpplppilp", True),
     "mtq_pack_tiles_transposed_batched": ("i", "pilllllppppzp", True),
     "mtq_unpack_tiles_transposed_batched": ("i", "pzppplllpillp", True),
+    "mtq_packed_matmul_skinny_grouped_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_matmul_skinny_grouped": ("i", "plllppzpppllplpilipzp", True),
+    "mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_matmul_skinny_grouped_chunked": ("i", "plllppzpppllplpilipzp", True),
+    "mtq_packed_matmul_wide_grouped_workspace_bytes": ("z", "llll", True),
+    "mtq_packed_matmul_wide_grouped": ("i", "plllppzpppllplpilpzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1516,6 +1522,80 @@ def packed_linear_wide_grouped(x, group_rows, arena, maps_dev, offsets_dev, base
     rows, not the skinny family's.  workspace: of packed_linear_wide_grouped_workspace_bytes(T, count, n, k) bytes; allocated here when
     none is given."""
     return _packed_linear_grouped_call("mtq_packed_linear_wide_grouped", packed_linear_wide_grouped_workspace_bytes, x, group_rows, arena,
+                                       maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out, None, workspace, stream)
+
+
+MATMUL_GROUPED = ("mtq_packed_matmul_skinny_grouped", "mtq_packed_matmul_skinny_grouped_workspace_bytes")
+MATMUL_GROUPED_CHUNKED = ("mtq_packed_matmul_skinny_grouped_chunked", "mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes")
+MATMUL_WIDE_GROUPED = ("mtq_packed_matmul_wide_grouped", "mtq_packed_matmul_wide_grouped_workspace_bytes")
+
+
+def has_packed_matmul_grouped() -> bool:
+    """Whether this build of the library has mtq_packed_matmul_skinny_grouped and its size function (optional symbols: an older build of
+    the same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in MATMUL_GROUPED)
+
+
+def has_packed_matmul_grouped_chunked() -> bool:
+    """The same for mtq_packed_matmul_skinny_grouped_chunked and its size function."""
+    return all(getattr(lib(), name, None) is not None for name in MATMUL_GROUPED_CHUNKED)
+
+
+def has_packed_matmul_wide_grouped() -> bool:
+    """The same for mtq_packed_matmul_wide_grouped and its size function."""
+    return all(getattr(lib(), name, None) is not None for name in MATMUL_WIDE_GROUPED)
+
+
+def _grouped_size(name, *args) -> int:
+    size = int(_entry(name)(*(int(a) for a in args)))
+    if size == ctypes.c_size_t(-1).value:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return size
+
+
+def packed_matmul_skinny_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_matmul_skinny_grouped_workspace_bytes (a host function: no GPU): packed_linear_skinny_grouped_workspace_bytes' answer
+    for the same arguments, n the output width and k the contraction of the `count` (k, n) experts."""
+    return _grouped_size("mtq_packed_matmul_skinny_grouped_workspace_bytes", total_rows, count, n, k, split)
+
+
+def packed_matmul_skinny_grouped(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None, out=None,
+                                 split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_matmul_skinny_grouped on the current stream: Y[rows of group e] = X[rows of group e]·P̂[e] (+ bias[e]) for the `count`
+    packed (k, n) experts of one arena (pack_tiles_transposed_batched's or pack_tiles_batched's tables) in one launch.  The arguments
+    are packed_linear_skinny_grouped's: x (T, k) bf16 with contiguous rows, group_rows a contiguous int32 device tensor of count + 1
+    entries, bias None or float32 (count, n).  → (T, n); an `out` allocated here starts as zeros.  Per 32-row chunk of a group the bits
+    of packed_matmul_skinny with that expert's stream and tables at the same split."""
+    return _packed_linear_grouped_call("mtq_packed_matmul_skinny_grouped", packed_matmul_skinny_grouped_workspace_bytes, x, group_rows, arena,
+                                       maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out, split, workspace, stream)
+
+
+def packed_matmul_skinny_grouped_chunked_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes (a host function: no GPU):
+    packed_linear_skinny_grouped_chunked_workspace_bytes' answer for the same arguments.  Never 0."""
+    return _grouped_size("mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes", total_rows, count, n, k, split)
+
+
+def packed_matmul_skinny_grouped_chunked(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None,
+                                         out=None, split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_matmul_skinny_grouped_chunked on the current stream: packed_matmul_skinny_grouped's product, arguments and bits with a
+    wave per 32-row chunk of a group (the chunk list is made from group_rows on the device), for routings with hot experts.  The
+    workspace is needed at every split; allocated here when none is given."""
+    return _packed_linear_grouped_call("mtq_packed_matmul_skinny_grouped_chunked", packed_matmul_skinny_grouped_chunked_workspace_bytes, x,
+                                       group_rows, arena, maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out, split, workspace, stream)
+
+
+def packed_matmul_wide_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int) -> int:
+    """mtq_packed_matmul_wide_grouped_workspace_bytes (a host function: no GPU): the block plan's bytes, a function of count.  Never 0."""
+    return _grouped_size("mtq_packed_matmul_wide_grouped_workspace_bytes", total_rows, count, n, k)
+
+
+def packed_matmul_wide_grouped(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None, out=None,
+                               workspace=None, stream="current"):
+    """mtq_packed_matmul_wide_grouped on the current stream: packed_matmul_skinny_grouped's product and arguments (no split) from the
+    wide-block kernel, a workgroup per 128 rows x 128 columns of one group, for experts with hundreds of rows.  Per group the bits of
+    packed_matmul / packed_matmul_wide on the group's rows, not the skinny family's."""
+    return _packed_linear_grouped_call("mtq_packed_matmul_wide_grouped", packed_matmul_wide_grouped_workspace_bytes, x, group_rows, arena,
                                        maps_dev, offsets_dev, bases_dev, count, n, bias, out_dtype, out, None, workspace, stream)
 
 

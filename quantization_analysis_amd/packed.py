@@ -1114,6 +1114,134 @@ def linear_grouped_wide(x, group_rows, pts_or_batch, bias=None, out_dtype: str =
                                          out_dtype=dtype, workspace=workspace)
 
 
+# ----------------------------------------------------------------------------- grouped products with (k, n) experts
+
+MATMUL_GROUPED_KERNELS = ("walk", "chunks", "auto")
+# What "auto" means for matmul_grouped.  The two kernels give the same bits, so this decides time alone, by the rule of DESIGN.md §A.6m:
+# "chunks", because in profiles/packed_matmul_grouped.txt (1) its median at split 0 is below the walking entry's minimum on all four
+# skewed rows (0.20-0.54 of it) and (2) on the twelve rows with 1, 4 or 32 rows per expert it is within the run's spread (1.0212) of the
+# walking entry's minimum (1.001-1.013).  Shapes, counts and routings outside that record are unmeasured.
+MATMUL_GROUPED_AUTO_KERNEL = "chunks"
+
+
+def _matmul_grouped_kernel(kernel: str) -> str:
+    """`kernel` of matmul_grouped, "auto" resolved."""
+    if kernel not in MATMUL_GROUPED_KERNELS:
+        raise MtqError(f"kernel must be one of {MATMUL_GROUPED_KERNELS}, got {kernel!r}")
+    return MATMUL_GROUPED_AUTO_KERNEL if kernel == "auto" else kernel
+
+
+def _matmul_grouped_entries(kernel: str):
+    """(the launch, its workspace-size function) of hip_backend for a resolved matmul_grouped kernel, or "wide" for matmul_grouped_wide;
+    a library without the symbols is an error that names them, never another kernel."""
+    from . import hip_backend as hb
+
+    has, names, launch, size = {
+        "walk": (hb.has_packed_matmul_grouped, hb.MATMUL_GROUPED, hb.packed_matmul_skinny_grouped, hb.packed_matmul_skinny_grouped_workspace_bytes),
+        "chunks": (hb.has_packed_matmul_grouped_chunked, hb.MATMUL_GROUPED_CHUNKED, hb.packed_matmul_skinny_grouped_chunked,
+                   hb.packed_matmul_skinny_grouped_chunked_workspace_bytes),
+        "wide": (hb.has_packed_matmul_wide_grouped, hb.MATMUL_WIDE_GROUPED, hb.packed_matmul_wide_grouped,
+                 hb.packed_matmul_wide_grouped_workspace_bytes),
+    }[kernel]
+    if not has():
+        what = "matmul_grouped_wide" if kernel == "wide" else f'matmul_grouped(kernel="{kernel}")'
+        raise MtqError(f"{what} needs {' and '.join(names)}, which this build of libmtq_hip.so lacks: rebuild it from this tree")
+    return launch, size
+
+
+def _matmul_grouped(x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, kernel):
+    """matmul_grouped (kernel "walk" / "chunks") and matmul_grouped_wide (kernel "wide", no split) behind their checks of `kernel`."""
+    batch = _resolve_batch(pts_or_batch)
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    count, k, n = batch.count, batch.rows, batch.cols
+    if len(x.shape) != 2 or x.shape[1] != k:
+        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
+    T = int(x.shape[0])
+    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
+    if not on_device:
+        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
+    import torch
+
+    if backend == "hip":
+        launch, _size = _matmul_grouped_entries(kernel)          # a missing kernel is refused before any device work
+        batch = batch_to_device(batch)
+        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        if T == 0:
+            return torch.zeros((0, n), dtype=dtype, device=batch.arena.device)
+        if not on_device:
+            group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(batch.arena.device)
+        if bias is not None and not _is_torch(bias):
+            bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32)).to(batch.arena.device)
+        more = {} if kernel == "wide" else {"split": split}
+        return launch(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias, out_dtype=dtype,
+                      workspace=workspace, **more)
+    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
+    if on_device:                                    # trusted, as on hip: what the kernel makes of it
+        if tuple(group_rows.shape) != (count + 1,):
+            raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {tuple(group_rows.shape)}")
+        r0, r1 = clamp_group_rows(group_rows.cpu().numpy(), T)
+    else:
+        r0, r1 = group_rows[:-1], group_rows[1:]
+    b = None if bias is None else (bias.detach().to("cpu").double().numpy() if _is_torch(bias) else np.asarray(bias, dtype=np.float64))
+    if b is not None and b.shape != (count, n):
+        raise MtqError(f"bias must be ({count}, {n}), got {b.shape}")
+    y = np.zeros((T, n), dtype=np.float64)
+    for e, (amap, offsets, data) in enumerate(_batch_host_tensors(batch)):
+        if r1[e] == r0[e]:
+            continue
+        w = decode(data, amap, offsets, k, n).view(np.float32)
+        ye = xf[r0[e]: r1[e]].astype(np.float64) @ w.astype(np.float64)
+        y[r0[e]: r1[e]] = ye if b is None else ye + b[e][None, :]
+    with np.errstate(over="ignore"):
+        y32 = y.astype(np.float32)
+    return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
+
+
+def matmul_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
+                   workspace=None, kernel: str = "walk"):
+    """Y[rows of group e] = X[rows of group e]·P̂[e] (+ bias[e]) for all (k, n) experts of a batch at once → (T, n): linear_grouped for
+    experts stored as matmul takes them, batch.rows == k and batch.cols == n.  The batch is a pack_batch_transposed list (the experts of
+    a transposed-layout search), as_batch of the entries of a pack_model --store-transposed directory, or pack_batch of input-major
+    weights.  x: (T, k); group_rows, pts_or_batch, bias (count, n), split and workspace as linear_grouped's: a host group_rows is
+    checked here, a device int32 one is passed on as it is and clamped by the kernel; T = 0 gives (0, n) without a call.
+    hip: one launch (two with a split over K) for decode-sized groups: for every group and 32-row chunk of it the bits of
+    matmul(kernel="skinny") on that chunk and that expert at the same effective split, hence linear_grouped's on the all-bf16 packings
+    of unpack(P̂[e])ᵀ.  Rows outside every group are zeros.  kernel (MATMUL_GROUPED_KERNELS): "walk", mtq_packed_matmul_skinny_grouped,
+    one wave per (slice, expert, tile column) that walks the expert's 32-row chunks; "chunks",
+    mtq_packed_matmul_skinny_grouped_chunked, one wave per (slice, chunk, tile column) with the chunk list made on the device - the
+    same bits, a workspace at every split; "auto", MATMUL_GROUPED_AUTO_KERNEL.  A library without the kernel's symbols raises MtqError
+    naming them before any device work: no other kernel runs in its place.
+    emulation: per group the float64 product of the decoded (k, n) matrix, rounded once, as matmul does, under every kernel name."""
+    return _matmul_grouped(x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, _matmul_grouped_kernel(kernel))
+
+
+def matmul_batch(x3d, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0, workspace=None,
+                 kernel: str = "walk"):
+    """x3d (count, m, k): expert e multiplies x3d[e] → (count, m, n).  matmul_grouped with group_rows = m * arange(count + 1)."""
+    batch = _resolve_batch(pts_or_batch)
+    if len(x3d.shape) != 3 or x3d.shape[0] != batch.count or x3d.shape[2] != batch.rows:
+        raise MtqError(f"x3d must be ({batch.count}, m, {batch.rows}), got {tuple(x3d.shape)}")
+    m = int(x3d.shape[1])
+    y = matmul_grouped(x3d.reshape(batch.count * m, batch.rows), m * np.arange(batch.count + 1, dtype=np.int64), batch,
+                       bias=bias, out_dtype=out_dtype, backend=backend, split=split, workspace=workspace, kernel=kernel)
+    return y.reshape(batch.count, m, batch.cols)
+
+
+def matmul_grouped_wide(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, workspace=None):
+    """matmul_grouped's product for experts that hold hundreds of rows (MoE prefill), through mtq_packed_matmul_wide_grouped: one launch
+    in which a workgroup owns 128 rows x 128 columns of one group.  Arguments as matmul_grouped's without a split; workspace: an
+    optional uint8 device tensor of hip_backend.packed_matmul_wide_grouped_workspace_bytes bytes (the block plan).
+    hip: for every group the bits of matmul(kernel="block") / matmul_wide on the group's rows and that expert - the block family's
+    bits, not matmul_grouped's, which is why this is a function of its own and no MATMUL_GROUPED_KERNELS name.  Rows outside every group
+    are zeros; T = 0 gives (0, n) without a call; a library without the symbol raises MtqError before any device work.
+    emulation: matmul_grouped's float64 product."""
+    return _matmul_grouped(x, group_rows, pts_or_batch, bias, out_dtype, backend, 0, workspace, "wide")
+
+
 # ----------------------------------------------------------------------------- the gated product (SwiGLU)
 
 def _check_act(act) -> None:
@@ -1703,10 +1831,79 @@ def _packed_experts_class():
     return PackedExperts
 
 
+def _packed_experts_matmul_class():
+    import torch
+
+    class PackedExpertsMatmul(torch.nn.Module):
+        """PackedExperts for (k, n) experts: the batch is what matmul_grouped takes, in_features = batch.rows, out_features = batch.cols.
+        INFERENCE ONLY.  forward(x, group_rows): x (T, k) → (T, n) through matmul_grouped, or, with wide_min_rows set and
+        T >= wide_min_rows, through matmul_grouped_wide (the block family's bits above the threshold, the skinny family's below).  The
+        batch is made once, here; hip: the arena, its tables, the bias and ONE kept workspace stay on the device (the plan's bytes from
+        the start when wide_min_rows is set, grown to the largest need seen).  A library without the symbols of `kernel`, or of the wide
+        kernel when wide_min_rows is set, is refused here, not at the first forward."""
+
+        def __init__(self, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
+                     kernel: str = "walk", wide_min_rows: Optional[int] = None):
+            super().__init__()
+            self.kernel = _matmul_grouped_kernel(kernel)
+            if wide_min_rows is not None and (isinstance(wide_min_rows, bool) or not isinstance(wide_min_rows, (int, np.integer)) or wide_min_rows < 0):
+                raise MtqError(f"wide_min_rows must be None or a non-negative int, got {wide_min_rows!r}")
+            self.wide_min_rows = None if wide_min_rows is None else int(wide_min_rows)
+            if out_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            batch = _resolve_batch(pts_or_batch)                # once: forward hands the batch down and walks no list
+            self.backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
+            if self.backend not in BACKENDS:
+                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            self._workspace = None
+            if self.backend == "hip":
+                self._size = _matmul_grouped_entries(self.kernel)[1]
+                wide_size = None if self.wide_min_rows is None else _matmul_grouped_entries("wide")[1]
+                batch = batch_to_device(batch)
+                if wide_size is not None:
+                    need = wide_size(1, batch.count, batch.cols, batch.rows)                            # a function of count alone
+                    self._workspace = torch.empty((need,), dtype=torch.uint8, device=batch.arena.device)   # only ever replaced by a larger one
+            self.batch = batch
+            self.out_dtype, self.split = out_dtype, int(split)
+            self.count, self.in_features, self.out_features = batch.count, batch.rows, batch.cols
+            if bias is not None:
+                if not _is_torch(bias):
+                    bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
+                if tuple(bias.shape) != (self.count, self.out_features):
+                    raise MtqError(f"bias must be ({self.count}, {self.out_features}), got {tuple(bias.shape)}")
+                bias = bias.detach().to(device=batch.arena.device if self.backend == "hip" else "cpu", dtype=torch.float32).contiguous()
+            self.register_buffer("bias", bias, persistent=False)
+
+        def extra_repr(self) -> str:
+            return f"count={self.count}, in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, " \
+                   f"backend={self.backend!r}, split={self.split}" + ("" if self.kernel == "walk" else f", kernel={self.kernel!r}") + \
+                   ("" if self.wide_min_rows is None else f", wide_min_rows={self.wide_min_rows}")
+
+        @torch.no_grad()
+        def forward(self, x, group_rows):
+            if x.dim() != 2 or x.shape[1] != self.in_features:
+                raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
+            T = int(x.shape[0])
+            if self.wide_min_rows is not None and T >= self.wide_min_rows:
+                y = matmul_grouped_wide(x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend,
+                                        workspace=self._workspace)
+                return y if _is_torch(y) else torch.from_numpy(y)
+            if self.backend == "hip" and T:
+                need = self._size(T, self.count, self.out_features, self.in_features, self.split)
+                if need and (self._workspace is None or self._workspace.numel() < need):
+                    self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.batch.arena.device)
+            y = matmul_grouped(x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype,
+                               backend=self.backend, split=self.split, workspace=self._workspace, kernel=self.kernel)
+            return y if _is_torch(y) else torch.from_numpy(y)
+
+    return PackedExpertsMatmul
+
+
 def __getattr__(name):
-    """PackedLinear, PackedMatmul, PackedExperts, PackedMLP and PackedExpertsMLP are torch.nn.Modules: a class is made on first use, so
-    that importing this module does not import torch."""
+    """PackedLinear, PackedMatmul, PackedExperts, PackedExpertsMatmul, PackedMLP and PackedExpertsMLP are torch.nn.Modules: a class is made
+    on first use, so that importing this module does not import torch."""
     makers = {"PackedLinear": _packed_linear_class, "PackedMatmul": _packed_matmul_class, "PackedExperts": _packed_experts_class,
+              "PackedExpertsMatmul": _packed_experts_matmul_class,
               "PackedMLP": _packed_mlp_class, "PackedExpertsMLP": _packed_experts_mlp_class}
     if name in makers:
         cls = makers[name]()
