@@ -1091,6 +1091,64 @@ int mtq_packed_glu_skinny_grouped(const void *x, int64_t total_rows, int64_t k, 
                                   const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace,
                                   size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ MoE routing: plan, dispatch, combine (csrc/mtq_moe.hip)
+ * From what a router emits, topk_ids and topk_weights of (tokens, topk), to the row layout the grouped entries above take, and from
+ * the experts' rows back to token order with the weighted sum.  Slot s = t * topk + j; S = tokens * topk.
+ *
+ * Plan.  A slot is live when 0 <= id < count; every other id (the INT32 / INT64 extremes included) is dropped: that is how expert
+ * parallelism passes the ids of experts of another rank.  A token may name one expert twice: both slots are live and get a row each.
+ *   group_rows  int32 [count + 1], the exclusive prefix sum of the live counts per expert; R = group_rows[count] <= S.
+ *   row_of      int32 [S]: a live slot's row in expert order, stable (within an expert rows ascend with s); -1 for a dropped slot.
+ *   src         int32 [S]: the inverse, src[row_of[s]] = s for live slots, and src[r] = -1 for every r in [R, S).
+ * So src[0 .. R) is the stable argsort of the slots by expert with the dropped slots last.
+ * Dispatch.  xs (S, k) bf16: xs[r] = x[src[r] / topk] when 0 <= src[r] < S, else the row is all +0: a bit copy.  Every one of the S
+ * rows is written, so xs goes to the grouped entries with total_rows = S and the device group_rows as it is (rows at or past R belong
+ * to no group); nothing is read back to the host.
+ * Combine.  For token t and column c an accumulator of float32 starts at (float) base[t][c] when base is given (a shared expert's
+ * output), else at +0; for j = 0 .. topk - 1 in that order, with r = row_of[t * topk + j]: if 0 <= r < S,
+ * acc = fl32(acc + fl32(w[t][j] * (float) ys[r][c])), product and sum rounded separately (no contraction).  A slot with r outside
+ * [0, S) is skipped, not multiplied by zero: an Inf in an unused row cannot reach y.  y is float32, or bf16 rounded to nearest even once.
+ *
+ * Limits: 1 <= topk <= MTQ_MOE_MAX_TOPK, 1 <= count <= MTQ_MOE_MAX_EXPERTS, tokens >= 1, S < 2^31; outside them, and for a null
+ * pointer (base may be NULL), a pitch below its row, a pointer not aligned to its type or a dtype code that is none:
+ * MTQ_ERR_INVALID before a device is looked for.  All launches are asynchronous on `stream`.  Deterministic: the only atomics are
+ * integer LDS adds of a histogram, no kernel waits on another workgroup, and two calls give the same words.  The four symbols are
+ * optional: a build of this version may lack them. */
+enum { MTQ_IDS_I32 = 0, MTQ_IDS_I64 = 1 };
+#define MTQ_MOE_MAX_TOPK 64
+#define MTQ_MOE_MAX_EXPERTS 4096
+#define MTQ_MOE_RUN 1024        /* slots one workgroup of the plan owns */
+
+/* HOST function: bytes of workspace for a plan, ceil(S / MTQ_MOE_RUN) * count * 4 rounded up to 16 (the runs' histograms); never 0.
+ * Arguments outside the limits give (size_t)-1. */
+size_t mtq_moe_plan_workspace_bytes(int64_t tokens, int64_t topk, int64_t count);
+
+/* topk_ids: device, int32 or int64 (id_dtype MTQ_IDS_I32 / MTQ_IDS_I64, read in their own width) at a row pitch of ld_ids >= topk
+ * elements → group_rows, row_of, src (device, as above).  A stable counting sort: a one-wave workgroup owns a run of MTQ_MOE_RUN
+ * consecutive slots; one kernel stores every run's histogram, one turns the histograms' columns into prefixes over the runs and
+ * writes group_rows, one places the slots and fills src[R .. S) with -1.  S <= MTQ_MOE_RUN, every decode call, is ONE launch of one
+ * workgroup that does all three and does not touch the workspace.  Nothing in the workspace needs initialising and nothing a call
+ * leaves there is needed later; a workspace that is NULL, not 16-byte aligned or shorter than the size function's answer is
+ * MTQ_ERR_INVALID at every size.  Nothing outside the three outputs and the first size-function bytes of the workspace is written; no
+ * id is used as an index before it is checked against [0, count). */
+int mtq_moe_plan(const void *topk_ids, int id_dtype, int64_t ld_ids, int64_t tokens, int64_t topk, int64_t count, int32_t *group_rows,
+                 int32_t *row_of, int32_t *src, void *workspace, size_t workspace_bytes, void *stream);
+
+/* x (tokens, k) bf16 at pitch ldx, src int32 [S] → xs (S, k) bf16 at pitch ldxs.  16-byte loads and stores when x and xs are 16-byte
+ * aligned, ldx % 8 == 0, ldxs % 8 == 0 and k % 8 == 0; element by element otherwise, the same bits.  Whatever src holds, no row of x
+ * at or past `tokens` is read and nothing outside S x k of xs is written (the pad of a pitched xs is left alone). */
+int mtq_moe_dispatch(const void *x, int64_t tokens, int64_t k, int64_t ldx, const int32_t *src, int64_t topk, void *xs, int64_t ldxs,
+                     void *stream);
+
+/* ys (S, n) bf16 or float32 (ys_dtype) at pitch ldys, row_of int32 [S], weights float32 (tokens, topk) at pitch ldw, base NULL or
+ * (tokens, n) bf16 / float32 (base_dtype, pitch ldbase; base_dtype and ldbase mean nothing without a base) → y (tokens, n) float32 or
+ * bf16 (out_dtype, pitch ldy).  A lane owns 8 consecutive columns of one token; 16-byte accesses when n % 8 == 0 and every operand's
+ * rows start 16-byte aligned, element by element otherwise, the same bits.  row_of is clamped as stated whatever it holds: no row of
+ * ys outside [0, S) is read, a row of ys that no kept slot names is never read, and nothing outside tokens x n of y is written. */
+int mtq_moe_combine(const void *ys, int ys_dtype, int64_t ldys, const int32_t *row_of, const float *weights, int64_t ldw, const void *base,
+                    int base_dtype, int64_t ldbase, int64_t tokens, int64_t topk, int64_t n, void *y, int out_dtype, int64_t ldy,
+                    void *stream);
+
 /* Test hook: the skinny kernel's decode (a cheaper form of the block kernel's for exponent bytes M..254, the same code elsewhere)
  * beside the reference decode, for fmt MTQ_FMT_BFP8 / BFP4 / BFP2.  got, want: device uint32 [16][256][16][16] = [rot][E][q][i], the
  * float32 word of code (16 q + (i + rot) % 16) mod 2^(M + 1) at element i of a group with exponent byte E: every (E, code) at every

@@ -149,6 +149,10 @@ SIGNATURES = {
     "mtq_packed_matmul_skinny_grouped_chunked": ("i", "plllppzpppllplpilipzp", True),
     "mtq_packed_matmul_wide_grouped_workspace_bytes": ("z", "llll", True),
     "mtq_packed_matmul_wide_grouped": ("i", "plllppzpppllplpilpzp", True),
+    "mtq_moe_plan_workspace_bytes": ("z", "lll", True),
+    "mtq_moe_plan": ("i", "pillllppppzp", True),
+    "mtq_moe_dispatch": ("i", "plllplplp", True),
+    "mtq_moe_combine": ("i", "pilpplpillllpilp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1829,6 +1833,108 @@ def packed_glu_skinny_grouped(x, group_rows, gate, up, count: int, n: int, act="
     ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_skinny_grouped_workspace_bytes(T, count, n, k, split), x.device)
     check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
              _packed_stream_ptr(stream)))
+    return out
+
+
+MOE = ("mtq_moe_plan_workspace_bytes", "mtq_moe_plan", "mtq_moe_dispatch", "mtq_moe_combine")
+MOE_MAX_TOPK, MOE_MAX_EXPERTS, MOE_RUN = 64, 4096, 1024   # include/mtq.h MTQ_MOE_MAX_TOPK, MTQ_MOE_MAX_EXPERTS, MTQ_MOE_RUN
+IDS_I32, IDS_I64 = 0, 1                                   # include/mtq.h MTQ_IDS_I32, MTQ_IDS_I64
+
+
+def has_moe() -> bool:
+    """Whether this build of the library has the MoE routing entries (mtq_moe_plan and its size function, mtq_moe_dispatch,
+    mtq_moe_combine; optional symbols: an older build of the same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in MOE)
+
+
+def moe_plan_workspace_bytes(tokens: int, topk: int, count: int) -> int:
+    """mtq_moe_plan_workspace_bytes (a host function: no GPU): ceil(tokens * topk / MOE_RUN) * count * 4 rounded up to 16.  Never 0."""
+    return _size_or_raise(int(_entry("mtq_moe_plan_workspace_bytes")(int(tokens), int(topk), int(count))))
+
+
+def _rows_ld(t, rows: int, cols: int) -> int:
+    """The row pitch of a 2-D tensor with contiguous rows, as the entries' pitch checks expect it of a single row."""
+    return t.stride(0) if rows > 1 else max(t.stride(0), cols)
+
+
+def moe_plan(topk_ids, count: int, workspace=None, stream="current"):
+    """mtq_moe_plan on the current stream: topk_ids, a (tokens, topk) int32 or int64 device tensor with contiguous rows (any row
+    pitch; read in its own width), → (group_rows int32 [count + 1], row_of int32 [S], src int32 [S]), S = tokens * topk: the stable
+    counting sort of the slots by expert, ids outside [0, count) dropped (row_of -1; src[R:] is -1).  One launch up to S = MOE_RUN,
+    three above; nothing is read back.  workspace: a uint8 device tensor of at least moe_plan_workspace_bytes(tokens, topk, count)
+    bytes, 16-byte aligned; allocated here when none is given."""
+    torch = _torch()
+    if topk_ids.dim() != 2:
+        raise MtqError(f"topk_ids must be a 2-D (tokens, topk) tensor, got {topk_ids.dim()}-D")
+    if topk_ids.dtype not in (torch.int32, torch.int64):
+        raise MtqError(f"topk_ids must be int32 or int64, got {topk_ids.dtype}")
+    T, K = (int(v) for v in topk_ids.shape)
+    if K > 1 and topk_ids.stride(1) != 1:
+        raise MtqError("topk_ids must have contiguous rows (stride(1) == 1)")
+    if not topk_ids.is_cuda:
+        raise MtqError("expected a device tensor (the hip backend has no CPU fallback)")
+    need = moe_plan_workspace_bytes(T, K, count)      # the limits on tokens, topk and count are the library's
+    fn = _entry("mtq_moe_plan")
+    ws_ptr, ws_bytes = _glu_workspace(workspace, need, topk_ids.device)
+    require_gpu()
+    group_rows = torch.empty((int(count) + 1,), dtype=torch.int32, device=topk_ids.device)
+    row_of, src = (torch.empty((T * K,), dtype=torch.int32, device=topk_ids.device) for _ in range(2))
+    check(fn(topk_ids.data_ptr(), IDS_I64 if topk_ids.dtype == torch.int64 else IDS_I32, _rows_ld(topk_ids, T, K), T, K, int(count),
+             group_rows.data_ptr(), row_of.data_ptr(), src.data_ptr(), ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
+    return group_rows, row_of, src
+
+
+def moe_dispatch(x, src, topk: int, out=None, stream="current"):
+    """mtq_moe_dispatch on the current stream: xs[r] = x[src[r] // topk] for x (tokens, k) bf16 with contiguous rows and src, a
+    contiguous int32 device tensor of S = tokens * topk entries, → xs (S, k) bf16; a row whose src is outside [0, S) is zeros.  Every
+    row of xs is written; `out`: a bf16 (S, k) device tensor with contiguous rows (any row pitch)."""
+    torch = _torch()
+    x_code, _count, _stride, T, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    topk = int(topk)
+    S = T * topk
+    if T <= 0 or k <= 0 or topk <= 0:
+        raise MtqError("tokens, k and topk must be positive")
+    ps = _buffer(src, torch.int32, S, "src")
+    if src.numel() != S:
+        raise MtqError(f"src must have tokens * topk = {S} entries, got {src.numel()}")
+    fn = _entry("mtq_moe_dispatch")
+    out, ldxs = _glu_out(out, S, k, torch.bfloat16, x.device)
+    check(fn(x.data_ptr(), T, k, ldx, ps, topk, out.data_ptr(), ldxs, _packed_stream_ptr(stream)))
+    return out
+
+
+def moe_combine(ys, row_of, weights, base=None, out_dtype=None, out=None, stream="current"):
+    """mtq_moe_combine on the current stream: y[t] = base[t] + the sum over j, in that order, of weights[t, j] * ys[row_of[t * topk + j]]
+    in separately rounded float32 operations, a slot whose row is outside [0, S) skipped.  ys: (>= S, n) bf16 or float32; row_of: a
+    contiguous int32 device tensor of S = tokens * topk entries; weights: (tokens, topk) float32; base: None or (tokens, n) bf16 or
+    float32; all device tensors with contiguous rows (any row pitch) → (tokens, n) float32 or bfloat16."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code = _packed_out_code(out_dtype)
+    if weights.dim() != 2 or weights.dtype != torch.float32 or (weights.shape[1] > 1 and weights.stride(1) != 1) or not weights.is_cuda:
+        raise MtqError("weights must be a float32 (tokens, topk) device tensor with contiguous rows")
+    T, K = (int(v) for v in weights.shape)
+    S = T * K
+    if T <= 0 or K <= 0:
+        raise MtqError("tokens and topk must be positive")
+    ys_code, _count, _stride, rows, n, ldys = _matrix(ys, (2,))
+    if rows < S or n <= 0:
+        raise MtqError(f"ys must be ({S}, n) or longer, got {tuple(ys.shape)}")
+    pr = _buffer(row_of, torch.int32, S, "row_of")
+    if row_of.numel() != S:
+        raise MtqError(f"row_of must have tokens * topk = {S} entries, got {row_of.numel()}")
+    base_ptr, base_code, ldbase = None, 0, 0
+    if base is not None:
+        base_code, _count, _stride, brows, bcols, ldbase = _matrix(base, (2,))
+        if (brows, bcols) != (T, n):
+            raise MtqError(f"base must be ({T}, {n}), got {tuple(base.shape)}")
+        base_ptr = base.data_ptr()
+    fn = _entry("mtq_moe_combine")
+    out, ldy = _glu_out(out, T, n, out_dtype, ys.device)
+    check(fn(ys.data_ptr(), ys_code, ldys, pr, weights.data_ptr(), _rows_ld(weights, T, K), base_ptr, base_code, ldbase, T, K, n,
+             out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
     return out
 
 

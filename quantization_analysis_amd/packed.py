@@ -28,6 +28,12 @@ pack_batch_transposed / unpack_batch_transposed are pack_transposed / unpack_tra
 writes W's orientation).  scripts/pack_model.py --store-transposed packs a model under a transposed config this way; read_index gives a
 directory's index.json, where such a run marks its entries "stored": "transpose".
 
+moe_plan / moe_dispatch / moe_combine / PackedMoE are the rest of an MoE layer around PackedExpertsMLP (csrc/mtq_moe.hip): from the
+router's (tokens, top_k) expert ids a stable counting sort on the device gives the grouped entries' row layout (MoEPlan), a row gather
+puts the tokens in it, and a weighted un-permute with a fixed summation order brings the experts' rows back; nothing is read back to
+the host.  Router scoring (softmax / sigmoid, group-limited top-k) stays the model's; the gather is not fused into the GEMMs' X loads
+and the combine not into the down projection's epilogue (both would change existing kernels); there is no MLP over (k, n) experts.
+
 Not built: a fused kernel for the decode range (the skinny family's split over K has partial sums); grouped and GLU variants of
 the (k, n) product; pack_transposed of tensors of rank other than 2 (pack_model.py packs their permuted copies with pack);
 activations other than ACTS.
@@ -1490,6 +1496,174 @@ def _glu_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, o
     return _round_out(h, out_dtype)
 
 
+# ----------------------------------------------------------------------------- MoE routing: plan, dispatch, combine
+
+MOE_MAX_TOPK = 64            # include/mtq.h MTQ_MOE_MAX_TOPK
+MOE_MAX_EXPERTS = 4096       # include/mtq.h MTQ_MOE_MAX_EXPERTS
+
+
+@dataclass
+class MoEPlan:
+    """The routing of one MoE forward (include/mtq.h "MoE routing"): slot s = t * topk + j of the router's (tokens, topk) ids.
+    group_rows: int32 [count + 1], the exclusive prefix sum of the live slots per expert; row_of: int32 [S], a live slot's row in expert
+    order (stable: within an expert rows ascend with s), -1 for a dropped slot; src: int32 [S], the inverse, -1 from row
+    R = group_rows[count] on.  Device tensors on hip, NumPy arrays on emulation."""
+    group_rows: object
+    row_of: object
+    src: object
+    tokens: int
+    topk: int
+    count: int
+
+    @property
+    def slots(self) -> int:
+        return self.tokens * self.topk
+
+    @property
+    def on_device(self) -> bool:
+        return bool(getattr(self.group_rows, "is_cuda", False))
+
+
+def _need_moe(hb, what: str) -> None:
+    if not hb.has_moe():
+        raise MtqError(f"{what} needs mtq_moe_plan, mtq_moe_dispatch and mtq_moe_combine, which this build of libmtq_hip.so lacks: rebuild it "
+                       "from this tree")
+
+
+def _moe_limits(tokens: int, topk: int, count: int) -> None:
+    if tokens < 1:
+        raise MtqError(f"topk_ids must hold at least one token, got {tokens}")
+    if not 1 <= topk <= MOE_MAX_TOPK:
+        raise MtqError(f"topk must be 1 .. {MOE_MAX_TOPK}, got {topk}")
+    if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or not 1 <= count <= MOE_MAX_EXPERTS:
+        raise MtqError(f"count must be an int in 1 .. {MOE_MAX_EXPERTS}, got {count!r}")
+    if tokens * topk >= 2 ** 31:
+        raise MtqError(f"tokens * topk must be below 2^31, got {tokens} * {topk}")
+
+
+def _plan_backend(plan: MoEPlan) -> str:
+    return "hip" if plan.on_device else "emulation"
+
+
+def moe_plan(topk_ids, count: int, backend: Optional[str] = None, workspace=None) -> MoEPlan:
+    """The routing plan of a router's expert ids: topk_ids (tokens, topk), int32 or int64 (torch.topk gives int64), → MoEPlan.
+    An id outside [0, count) is dropped (expert parallelism passes the ids of another rank's experts that way); a token that names
+    one expert twice gets a row for each slot.  1 <= topk <= MOE_MAX_TOPK, 1 <= count <= MOE_MAX_EXPERTS, tokens >= 1.
+    hip (the default for a device topk_ids): mtq_moe_plan, a stable counting sort on the device: one launch up to 1024 slots, three
+    above; nothing is read back.  workspace: an optional uint8 device tensor of hip_backend.moe_plan_workspace_bytes bytes.
+    emulation: NumPy's stable argsort of where(live, id, count); plan.src[:R] is its first R entries."""
+    if len(topk_ids.shape) != 2:
+        raise MtqError(f"topk_ids must be 2-D (tokens, topk), got shape {tuple(topk_ids.shape)}")
+    if str(topk_ids.dtype).replace("torch.", "") not in ("int32", "int64"):
+        raise MtqError(f"topk_ids must be int32 or int64, got {topk_ids.dtype}")
+    T, K = (int(v) for v in topk_ids.shape)
+    _moe_limits(T, K, count)
+    count = int(count)
+    backend = backend or ("hip" if _is_torch(topk_ids) and topk_ids.is_cuda else "emulation")
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    if backend == "hip":
+        from . import hip_backend as hb
+
+        _need_moe(hb, "moe_plan")
+        if not _is_torch(topk_ids):
+            import torch
+
+            topk_ids = torch.from_numpy(np.ascontiguousarray(topk_ids)).to("cuda")
+        group_rows, row_of, src = hb.moe_plan(topk_ids, count, workspace=workspace)
+        return MoEPlan(group_rows, row_of, src, T, K, count)
+    ids = (topk_ids.detach().to("cpu").numpy() if _is_torch(topk_ids) else np.asarray(topk_ids)).astype(np.int64).reshape(-1)
+    live = (ids >= 0) & (ids < count)
+    order = np.argsort(np.where(live, ids, count), kind="stable")
+    R = int(live.sum())
+    src = np.full(T * K, -1, dtype=np.int32)
+    src[:R] = order[:R]
+    row_of = np.full(T * K, -1, dtype=np.int32)
+    row_of[order[:R]] = np.arange(R, dtype=np.int32)
+    group_rows = np.concatenate([[0], np.cumsum(np.bincount(ids[live], minlength=count))]).astype(np.int32)
+    return MoEPlan(group_rows, row_of, src, T, K, count)
+
+
+def moe_dispatch(x, plan: MoEPlan, out=None):
+    """The tokens' rows in expert order: x (tokens, k) bf16 → xs (S, k), xs[r] = x[plan.src[r] // topk], a bit copy; a row from
+    R = group_rows[count] on (and any row whose src is no slot) is all +0.  Every one of the S rows is written, so xs goes to
+    linear_grouped / glu_grouped / PackedExpertsMLP with the plan's device group_rows as it is: their rows of no group.  The backend is
+    the plan's.  hip: mtq_moe_dispatch, one launch; out: an optional bf16 (S, k) device tensor with contiguous rows.
+    emulation: x a CPU tensor or an array, the result of its kind."""
+    T, K, S = plan.tokens, plan.topk, plan.slots
+    if len(x.shape) != 2 or x.shape[0] != T:
+        raise MtqError(f"x must be ({T}, k), got {tuple(x.shape)}")
+    if _plan_backend(plan) == "hip":
+        from . import hip_backend as hb
+
+        _need_moe(hb, "moe_dispatch")
+        return hb.moe_dispatch(x, plan.src, K, out=out)
+    src = np.asarray(plan.src, dtype=np.int64)
+    rows = np.nonzero((src >= 0) & (src < S))[0]
+    if _is_torch(x):
+        import torch
+
+        xs = torch.zeros((S, x.shape[1]), dtype=x.dtype)
+        xs[torch.from_numpy(rows)] = x.detach().to("cpu")[torch.from_numpy(src[rows] // K)]
+    else:
+        xs = np.zeros((S, x.shape[1]), dtype=np.asarray(x).dtype)
+        xs[rows] = np.asarray(x)[src[rows] // K]
+    if out is not None:
+        out[...] = xs
+        return out
+    return xs
+
+
+def moe_combine(ys, topk_weights, plan: MoEPlan, base=None, out_dtype: str = "float32", out=None):
+    """The experts' rows back in token order with the router's weights: ys (S, n) bf16 or float32 (rows in expert order; more rows are
+    allowed, fewer are not), topk_weights (tokens, topk) float32, base None or (tokens, n) bf16 / float32 (a shared expert's output)
+    → y (tokens, n) in out_dtype.  For every token and column a float32 accumulator starts at base (or +0) and takes, for j = 0 ..
+    topk - 1 in that order, fl32(acc + fl32(w[t, j] * ys[row_of[t * topk + j]])): product and sum rounded separately, so the result is
+    pinned to the bit.  A dropped slot (row outside [0, S)) is skipped, not multiplied by zero: the rows from R on are never read.
+    The backend is the plan's.  hip: mtq_moe_combine, one launch; out: an optional (tokens, n) device tensor of out_dtype.
+    emulation: the same sequence in NumPy's float32; a bf16 result is rounded to nearest even once."""
+    T, K, S = plan.tokens, plan.topk, plan.slots
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    if tuple(topk_weights.shape) != (T, K):
+        raise MtqError(f"topk_weights must be ({T}, {K}), got {tuple(topk_weights.shape)}")
+    if str(topk_weights.dtype).replace("torch.", "") != "float32":
+        raise MtqError(f"topk_weights must be float32, got {topk_weights.dtype}")
+    if len(ys.shape) != 2 or ys.shape[0] < S:
+        raise MtqError(f"ys must be ({S}, n), one row per slot, got {tuple(ys.shape)}")
+    n = int(ys.shape[1])
+    if base is not None and tuple(base.shape) != (T, n):
+        raise MtqError(f"base must be ({T}, {n}), got {tuple(base.shape)}")
+    if _plan_backend(plan) == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        _need_moe(hb, "moe_combine")
+        dev = plan.row_of.device
+        if not _is_torch(topk_weights):
+            topk_weights = torch.from_numpy(np.ascontiguousarray(topk_weights)).to(dev)
+        return hb.moe_combine(ys, plan.row_of, topk_weights, base=base, out_dtype=torch.float32 if out_dtype == "float32" else torch.bfloat16,
+                              out=out)
+
+    def host32(v):
+        return v.detach().to("cpu").float().numpy() if _is_torch(v) else np.asarray(v, dtype=np.float32)
+
+    ys32, w = host32(ys), host32(topk_weights)
+    acc = np.zeros((T, n), dtype=np.float32) if base is None else host32(base).copy()
+    row_of = np.asarray(plan.row_of, dtype=np.int64).reshape(T, K)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(K):
+            r = row_of[:, j]
+            t = np.nonzero((r >= 0) & (r < S))[0]
+            acc[t] = acc[t] + w[t, j][:, None] * ys32[r[t]]        # float32 throughout: two roundings per term
+    y = _round_out(acc, out_dtype)
+    if out is not None:
+        out[...] = y
+        return out
+    return y
+
+
 def _packed_mlp_class():
     import torch
 
@@ -1620,6 +1794,90 @@ def _packed_experts_mlp_class():
             return y if _is_torch(y) else torch.from_numpy(y)
 
     return PackedExpertsMLP
+
+
+MOE_PLAN_TOPK = 8   # PackedMoE sizes its first plan workspace for max_tokens tokens of this many slots each; a larger call regrows it
+
+
+def _packed_moe_class():
+    import torch
+
+    class PackedMoE(torch.nn.Module):
+        """One MoE layer on packed experts, from the router's output to the layer's: plan → dispatch → PackedExpertsMLP → combine.
+        INFERENCE ONLY.  forward(x, topk_ids, topk_weights, base=None): x (..., k) bf16, topk_ids and topk_weights (..., K) with x's
+        leading dimensions (ids int32 or int64, ids outside [0, count) dropped; weights float32), base None or (..., k_out), a shared
+        expert's output to start the sums from → (..., k_out) in out_dtype.  The leading dimensions are flattened to T tokens;
+        moe_plan, moe_dispatch, the experts on (xs, plan.group_rows) with all S = T * K rows, moe_combine.  T = 0 gives the empty
+        result without a call.  Router scoring (softmax / sigmoid, group-limited top-k) stays the model's.
+        expert_dtype: the type of the experts' rows the combine reads ("float32": the down projection's sums unrounded; "bfloat16":
+        half the bytes).  decode_max_rows: PackedExpertsMLP's, compared against S, the rows the experts see.
+        hip: no device-to-host copy and no .item() in a forward; the plan workspace is allocated here for max_tokens tokens and
+        regrown when a call needs more.  emulation: CPU tensors, for use without a GPU."""
+
+        def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", expert_dtype: str = "float32",
+                     backend: Optional[str] = None, decode_max_rows: Optional[int] = None, max_tokens: int = 4096):
+            super().__init__()
+            if out_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            if expert_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"expert_dtype must be 'float32' or 'bfloat16', got {expert_dtype!r}")
+            if isinstance(max_tokens, bool) or not isinstance(max_tokens, int) or max_tokens <= 0:
+                raise MtqError(f"max_tokens must be a positive int, got {max_tokens!r}")
+            experts_mlp = globals().get("PackedExpertsMLP") or __getattr__("PackedExpertsMLP")
+            self.experts = experts_mlp(gate_pts, up_pts, down_pts, act=act, out_dtype=expert_dtype, backend=backend,
+                                       decode_max_rows=decode_max_rows)
+            self.backend, self.out_dtype, self.expert_dtype = self.experts.backend, out_dtype, expert_dtype
+            self.count, self.in_features, self.out_features = self.experts.count, self.experts.in_features, self.experts.out_features
+            if self.count > MOE_MAX_EXPERTS:
+                raise MtqError(f"PackedMoE takes at most {MOE_MAX_EXPERTS} experts, got {self.count}")
+            self._plan_workspace = None
+            if self.backend == "hip":
+                from . import hip_backend as hb
+
+                _need_moe(hb, "PackedMoE")           # refused here, not at the first forward
+                need = hb.moe_plan_workspace_bytes(max_tokens, MOE_PLAN_TOPK, self.count)
+                self._plan_workspace = torch.empty((need,), dtype=torch.uint8, device=self.experts.gate.arena.device)
+
+        def extra_repr(self) -> str:
+            return f"count={self.count}, in_features={self.in_features}, out_features={self.out_features}, backend={self.backend!r}"
+
+        @torch.no_grad()
+        def forward(self, x, topk_ids, topk_weights, base=None):
+            if x.shape[-1] != self.in_features:
+                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
+            lead = tuple(x.shape[:-1])
+            if len(topk_ids.shape) != len(lead) + 1 or tuple(topk_ids.shape[:-1]) != lead:
+                raise MtqError(f"topk_ids must be {lead + ('K',)}, got {tuple(topk_ids.shape)}")
+            K = int(topk_ids.shape[-1])
+            if tuple(topk_weights.shape) != lead + (K,):
+                raise MtqError(f"topk_weights must be {lead + (K,)}, got {tuple(topk_weights.shape)}")
+            if base is not None and tuple(base.shape) != lead + (self.out_features,):
+                raise MtqError(f"base must be {lead + (self.out_features,)}, got {tuple(base.shape)}")
+            x2 = x.reshape(-1, self.in_features)
+            T = int(x2.shape[0])
+            if T == 0:
+                return torch.zeros(lead + (self.out_features,), dtype=torch.float32 if self.out_dtype == "float32" else torch.bfloat16, device=x.device)
+            if self.backend == "hip":
+                from . import hip_backend as hb
+
+                need = hb.moe_plan_workspace_bytes(T, K, self.count)
+                if self._plan_workspace.numel() < need:
+                    self._plan_workspace = torch.empty((need,), dtype=torch.uint8, device=self._plan_workspace.device)
+            plan = moe_plan(topk_ids.reshape(T, K), self.count, backend=self.backend, workspace=self._plan_workspace)
+            xs = moe_dispatch(x2, plan)
+            if self.backend == "hip":
+                ys = self.experts(xs, plan.group_rows)               # all S rows: the rows from R on belong to no group and stay zero
+            else:                                                    # a host group_rows ends at the rows it is given: the first R
+                R = int(plan.group_rows[-1])
+                ys = torch.zeros((plan.slots, self.out_features), dtype=torch.float32 if self.expert_dtype == "float32" else torch.bfloat16)
+                ys[:R] = self.experts(xs[:R], plan.group_rows)
+            y = moe_combine(ys, topk_weights.reshape(T, K), plan, base=None if base is None else base.reshape(T, self.out_features),
+                            out_dtype=self.out_dtype)
+            if not _is_torch(y):
+                y = torch.from_numpy(y)
+            return y.reshape(lead + (self.out_features,))
+
+    return PackedMoE
 
 
 def _packed_linear_class():
@@ -1900,11 +2158,11 @@ def _packed_experts_matmul_class():
 
 
 def __getattr__(name):
-    """PackedLinear, PackedMatmul, PackedExperts, PackedExpertsMatmul, PackedMLP and PackedExpertsMLP are torch.nn.Modules: a class is made
-    on first use, so that importing this module does not import torch."""
+    """PackedLinear, PackedMatmul, PackedExperts, PackedExpertsMatmul, PackedMLP, PackedExpertsMLP and PackedMoE are torch.nn.Modules: a
+    class is made on first use, so that importing this module does not import torch."""
     makers = {"PackedLinear": _packed_linear_class, "PackedMatmul": _packed_matmul_class, "PackedExperts": _packed_experts_class,
               "PackedExpertsMatmul": _packed_experts_matmul_class,
-              "PackedMLP": _packed_mlp_class, "PackedExpertsMLP": _packed_experts_mlp_class}
+              "PackedMLP": _packed_mlp_class, "PackedExpertsMLP": _packed_experts_mlp_class, "PackedMoE": _packed_moe_class}
     if name in makers:
         cls = makers[name]()
         globals()[name] = cls
