@@ -1091,6 +1091,74 @@ int mtq_packed_glu_skinny_grouped(const void *x, int64_t total_rows, int64_t k, 
                                   const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace,
                                   size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ gated MLP on packed (k, n) weights
+ * h = act(x·P̂g + bg) * (x·P̂u + bu) with the gate and the up projection as two packed k x n tensors (mtq_packed_matmul's weight: the
+ * transposed BFP layout, an input-major weight, what the transposed pack entries write).  The four gated entries above with
+ * the matmul family's feed: the parameter list of each entry is that of the mtq_packed_glu_* entry of the same name, one for one and in
+ * the same order; n is the output (hidden) width, k the contraction, and the map grid of each tensor is ceil(k/32) x ceil(n/32),
+ * tiles_kh x tiles_nw.  act, biases, group_rows and its clamping, rows of no group (not written), ldb and the workspace rules are as
+ * stated there.
+ *
+ * mtq_packed_glu_matmul_wide: mtq_packed_matmul_wide's block on 128 rows x 64 hidden columns.  Wave w stages sub-image w of the
+ * [64 k][32 n] weight part of the LDS image: hidden tile COLUMN n0/32 + (w >> 1), from the gate stream when w is even and from the up
+ * stream when w is odd; wave (wm, wn) reads sub-images 2 wn and 2 wn + 1 through the transposed LDS read and so holds the gate's and
+ * the up's accumulator of the same output: the activation is lane-local, the two float32 (m, n) intermediates never reach memory.  The
+ * grid is ceil(m / 128) x ceil(n / 64); no workspace.
+ * mtq_packed_glu_matmul_wide_grouped: the same block in mtq_packed_matmul_wide_grouped's frame over a gate arena and an up arena; the
+ * grid is U x ceil(n / 64), the workspace holds the plan only.
+ * mtq_packed_glu_matmul_skinny (1 <= m <= MTQ_PACKED_SKINNY_MAX_M): mtq_packed_matmul_skinny's wave, one per (slice, projection, tile
+ * column), through two wave-private [32 k][32 n] LDS images; float32 partials to workspace[projection][slice][m][n] at every split,
+ * mtq_packed_glu_skinny's reduce kernel finishes.  Two launches at every split, against five for the unfused route.
+ * mtq_packed_glu_matmul_skinny_grouped: that wave per (slice, projection, group, tile column) in mtq_packed_matmul_skinny_grouped's
+ * frame, a group above 32 rows walked in 32-row chunks; mtq_packed_glu_skinny_grouped's reduce kernel finishes.
+ *
+ * split: mtq_packed_matmul_skinny's and mtq_packed_matmul_skinny_grouped's rules for the same arguments; the projection axis is not
+ * counted.  The size functions return the mtq_packed_glu_* answer for the same arguments ((size_t)-1 on bad arguments).
+ *
+ * Bit contracts, in both output types, with or without either bias, for any ldx / ldy:
+ *  - wide: y equals bit for bit (1) mtq_packed_matmul on the gate stream with bias_gate into float32, (2) the same on the up stream
+ *    with bias_up, (3) mtq_glu_combine of the two.  The grouped entry holds this per group with rows, on x[r0:r1] with expert e's gate
+ *    and up streams and tables (and bias rows e), for nondecreasing group_rows.
+ *  - skinny: the same with mtq_packed_matmul_skinny at the same effective split (0 included); the grouped entry per 32-row chunk of a
+ *    group, i.e. with mtq_packed_matmul_skinny_grouped on each arena.
+ *  - across the families: each entry equals the mtq_packed_glu_* entry of the same name on the all-bf16 row-layout packings of
+ *    unpack(P̂g)ᵀ and unpack(P̂u)ᵀ, the skinny entries at the same `split` (the split rules are the same function of the same arguments).
+ * Deterministic: no atomics, no counters, nothing waits on another workgroup, nothing in a workspace needs initialising.
+ *
+ * Device guards: a tile whose map code is outside 0..3 or whose blob passes its own stream's bytes - for an arena, its own group's
+ * [64 * bases[e], 64 * bases[e + 1]) of its OWN arena, or that arena's bytes - multiplies as zeros in its own projection only; k-rows
+ * at or past k count as zeros whatever their bytes hold; rows of x at or past m (a group's clamped end) are never read; columns at or
+ * past n are never stored.
+ *
+ * Argument checks are the mtq_packed_glu_* entries', for each stream, with mtq_packed_matmul's grid check for a k x n tensor:
+ * MTQ_ERR_INVALID before a device is looked for; an unknown act is MTQ_ERR_UNSUPPORTED.
+ *
+ * All seven symbols are optional: a build of this version may lack them. */
+int mtq_packed_glu_matmul_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                               const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
+                               const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up,
+                               int act, void *y, int out_dtype, int64_t ldy, void *stream);
+size_t mtq_packed_glu_matmul_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k);
+int mtq_packed_glu_matmul_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                       const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                       const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                       const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n,
+                                       const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y, int out_dtype,
+                                       int64_t ldy, void *workspace, size_t workspace_bytes, void *stream);
+size_t mtq_packed_glu_matmul_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split);
+int mtq_packed_glu_matmul_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                                 const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
+                                 const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up,
+                                 int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+size_t mtq_packed_glu_matmul_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split);
+int mtq_packed_glu_matmul_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                         const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                         const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                         const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n,
+                                         const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y, int out_dtype,
+                                         int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ MoE routing: plan, dispatch, combine (csrc/mtq_moe.hip)
  * From what a router emits, topk_ids and topk_weights of (tokens, topk), to the row layout the grouped entries above take, and from
  * the experts' rows back to token order with the weighted sum.  Slot s = t * topk + j; S = tokens * topk.

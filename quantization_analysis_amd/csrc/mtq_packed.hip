@@ -44,8 +44,12 @@
 //       wave-private [32 k][32 n] LDS image and the transposed read; bit for bit the skinny linear kernel on the transposed weight.
 //   packed_matmul_wide_kernel                 that product for m >= 64: the wide block with its W side fed from the k × n stream, four
 //       [64 k][32 n] sub-images read through the transposed LDS read; bit for bit packed_matmul_kernel.
+//   packed_glu_matmul_wide_kernel, packed_glu_matmul_wide_grouped_kernel, packed_glu_matmul_skinny_kernel,
+//   packed_glu_matmul_skinny_grouped_kernel   the gated product for packed k × n gate and up matrices: the four gated frames with the
+//       matmul kernels' feed (the wide block's [64 k][32 n] sub-images alternating between the two streams; the skinny wave's two
+//       images on the projection axis); bit for bit two matmul calls into f32 and the combine.
 //
-// The five wide kernels are frames around one block function, wide_block; the six skinny kernels around one wave's run, skinny_run, and one
+// The wide kernels are frames around one block function, wide_block; the skinny kernels around one wave's run, skinny_run, and one
 // epilogue, store_lane_rows; all of them read a tensor through a PackedStream and guard a blob with stream_at.
 //
 // Every blob is checked against the buffer's length on the device before it is touched (offsets come from the caller): a tile whose
@@ -2097,6 +2101,136 @@ size_t glu_skinny_workspace(int64_t m, int64_t n, int split_eff)
     return (2 * (size_t)std::max(split_eff, 1) * (size_t)m * (size_t)n * sizeof(float) + 15) & ~(size_t)15;
 }
 
+// ---- gated matmul: glu_value(X·P̂g + bg, X·P̂u + bu) for packed k × n gate and up matrices, the four GLU frames with the matmul feed.
+//
+// Wide.  packed_glu_wide_kernel's frame around wide_block<true, .., WT = true>: a workgroup owns 128 rows × 64 hidden columns, wave w
+// stages sub-image w of the [64 k][32 n] W part, which is hidden tile COLUMN n0 / 32 + (w >> 1) of the k × n grid tiles_kh × tiles_nw, from
+// the gate stream when w is even and from the up stream when w is odd; wave (wm, wn) reads sub-images 2 wn and 2 wn + 1 through the
+// transposed LDS read, so acc[mt][0] is the gate's and acc[mt][1] the up's output at the same (row, hidden column n0 + 32 wn + lane % 32)
+// and the epilogue is lane-local glu_value.  Each accumulator takes packed_matmul_wide_kernel's sequence for its projection (that
+// kernel's bits are packed_matmul_kernel's), the bias is added once in f32 and glu_value is what mtq_glu_combine applies: the bits of
+// two mtq_packed_matmul calls into f32 and the combine.
+// Pad, don't mask: a bad map code, a blob past its own stream's range and k-rows at or past K are zeros in the image; columns at or past
+// N are never stored.  No atomics, no workspace but the grouped plan, nothing waits on another workgroup.
+// EXEC is all ones at every transposed read: the single-tensor frame returns nowhere before the epilogue; the grouped frame's
+// surplus-slot return is taken by the whole workgroup before any barrier; behind either is wide_block's wave-uniform control flow,
+// where no read sits in a lane-dependent branch.
+template <bool XV, bool BF16OUT>
+__global__ __launch_bounds__(kThreads, 2) void packed_glu_matmul_wide_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ gate, uint64_t gate_bytes,
+    const int8_t *__restrict__ gate_map, const uint32_t *__restrict__ gate_offsets, const uint8_t *__restrict__ up, uint64_t up_bytes,
+    const int8_t *__restrict__ up_map, const uint32_t *__restrict__ up_offsets, int64_t N, int64_t tiles_kh, int64_t tiles_nw,
+    const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int act, void *__restrict__ yv, int64_t ldy)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
+    const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kGluBN;
+    const bool is_up = wave & 1;                     // the wave's sub-image: even from the gate stream, odd from the up stream
+    const PackedStream st = tensor_stream(is_up ? up : gate, is_up ? up_bytes : gate_bytes, is_up ? up_map : gate_map,
+                                          is_up ? up_offsets : gate_offsets);
+    wide_block<true, XV, BF16OUT, true>(lds, x, bm * kWideBM, M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_kh, tiles_nw, bias_gate, bias_up,
+                                        act, yv, ldy, wave);
+}
+
+// packed_matmul_wide_grouped_kernel's frame with column blocks of 64 hidden columns: the plan, the slot bound, the search and the stream
+// in scalar registers are that kernel's; a blob is checked against its own group's range [64 bases[e], 64 bases[e + 1]) of its OWN arena.
+template <bool XV, bool BF16OUT>
+__global__ __launch_bounds__(kThreads, 2) void packed_glu_matmul_wide_grouped_kernel(
+    const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
+    const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps, const uint32_t *__restrict__ gate_offsets,
+    const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes, const int8_t *__restrict__ up_maps,
+    const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int64_t N, int64_t tiles_kh, int64_t tiles_nw,
+    const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int64_t ldb, int act, void *__restrict__ yv, int64_t ldy)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
+    const int64_t n0 = (blockIdx.x % nblocks) * kGluBN;
+    GroupBlock b;
+    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;   // the whole workgroup, before any barrier
+    const bool is_up = wave & 1;
+    const PackedStream st = arena_stream_uniform(is_up ? up : gate, is_up ? up_bytes : gate_bytes, is_up ? up_maps : gate_maps,
+                                                 is_up ? up_offsets : gate_offsets, is_up ? up_bases : gate_bases, b.e, tiles_kh * tiles_nw);
+    wide_block<true, XV, BF16OUT, true>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_kh, tiles_nw,
+                                        bias_gate ? bias_gate + b.e * ldb : nullptr, bias_up ? bias_up + b.e * ldb : nullptr, act, yv, ldy, wave);
+}
+
+// Skinny (m <= 32).  packed_matmul_skinny_kernel's wave on one more unit axis, the projection p (0 the gate, 1 the up): a unit is (slice s,
+// projection p, tile column tc), numbered (2 s + p) * tiles_nw + tc, the tile column fastest, so the four waves of a workgroup share a
+// slice of X.  The wave takes its projection's stream and tables and does what that kernel's wave does: the strided hand-out, the ring,
+// the blob check against its own stream, decode_skinny, the group through one of its two wave-private [32 k][32 n] images and back as two
+// B operands by the transposed read.  Its f32 partial goes to ws[p][s][m][n] with plain stores at every split; glu_skinny_reduce_kernel,
+// unchanged, is where the projections meet.  Per projection the sums are packed_matmul_skinny_kernel's at the same split.
+// EXEC is all ones at every transposed read: the only exit before a read is the unit bound, wave-uniform (the wave index is scalar);
+// the reads sit in no lane-dependent branch; the n < N guard comes after the run.  A bad map code, a blob past its stream and k-rows at
+// or past K are zeros in the image; columns at or past N are never stored.  No barrier across waves, no atomics.
+__global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_matmul_skinny_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec, const uint8_t *__restrict__ gate, uint64_t gate_bytes,
+    const int8_t *__restrict__ gate_map, const uint32_t *__restrict__ gate_offsets, const uint8_t *__restrict__ up, uint64_t up_bytes,
+    const int8_t *__restrict__ up_map, const uint32_t *__restrict__ up_offsets, int64_t N, int64_t tiles_kh, int64_t tiles_nw, int split,
+    float *__restrict__ ws)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[kSkinnyWaves * 2 * kMmsImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= 2 * tiles_nw * split) return;        // wave-uniform; the kernel has no workgroup barrier
+    const int64_t tc = unit % tiles_nw, sp = unit / tiles_nw, p = sp & 1, s = sp >> 1;
+    const PackedStream st = tensor_stream(p ? up : gate, p ? up_bytes : gate_bytes, p ? up_map : gate_map, p ? up_offsets : gate_offsets);
+    const int row = lane & 31, half = lane >> 5;
+
+    f32x16 acc = zero16();
+    skinny_run(acc, feed_transposed(lds + wave * (2 * kMmsImage), lane), x, M, K, ldx, x_vec, st, tc, tiles_nw, s * tiles_kh / split,
+               (s + 1) * tiles_kh / split, lane, row, half, lane);
+
+    // lane's outputs are (m = (r&3) + 8(r>>2) + 4·half, n = 32·tc + row) of slice s of projection p
+    const int64_t n = tc * kTile + row;
+    if (n >= N) return;
+    store_lane_rows<false, true>(acc, M, half, ws, (((int64_t)p * split + s) * M + 4 * half) * N + n, N, 0.0f);
+}
+
+// Grouped skinny.  packed_matmul_skinny_grouped_kernel's wave on the projection axis, over two arenas: a unit is (slice s, projection p,
+// group e, tile column tc), numbered ((2 s + p) * count + e) * tiles_nw + tc.  The group's clamped rows, the walk in 32-row chunks by the
+// same wave, the run and the images are that kernel's; the tables, bases and bytes are the wave's own arena's, and a blob is checked
+// against its own group's range of that arena.  The partial of every chunk goes to ws[p][s][row][n] with plain stores at every split;
+// glu_skinny_grouped_reduce_kernel finishes.
+// EXEC: as in packed_matmul_skinny_grouped_kernel, everything a branch before or between runs depends on (the unit bound, the group
+// without rows, the chunk loop's trip count) is wave-uniform and in scalar registers; the one lane-dependent branch is the n < N guard
+// around the stores, after a run, and EXEC is whole again behind it.
+__global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_matmul_skinny_grouped_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
+    const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps, const uint32_t *__restrict__ gate_offsets,
+    const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes, const int8_t *__restrict__ up_maps,
+    const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int N, int tiles_kh, int tiles_nw, int split,
+    float *__restrict__ ws)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[kSkinnyWaves * 2 * kMmsImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= (int64_t)2 * tiles_nw * count * split) return;   // wave-uniform; the kernel has no workgroup barrier
+    const int64_t tc = unit % tiles_nw, spe = unit / tiles_nw, e = spe % count, sp = spe / count, p = sp & 1, s = sp >> 1;
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    const int r0 = __builtin_amdgcn_readfirstlane((int)gr.r0), r1 = __builtin_amdgcn_readfirstlane((int)gr.r1);   // 0 <= r0 <= r1 <= T
+    if (r1 == r0) return;                            // nothing of this expert is read
+    const PackedStream st = arena_stream(p ? up : gate, p ? up_bytes : gate_bytes, p ? up_maps : gate_maps, p ? up_offsets : gate_offsets,
+                                         p ? up_bases : gate_bases, e, (int64_t)tiles_kh * tiles_nw);
+    const int64_t c0 = s * tiles_kh / split, c1 = (s + 1) * tiles_kh / split;
+    uint16_t *img = lds + wave * (2 * kMmsImage);
+
+    for (int64_t row0 = r0; row0 < r1; row0 += kTile) {   // scalar: the trip count is the group's
+        int lv = lane;
+        asm volatile("" : "+v"(lv));                 // the lane's addresses are formed per chunk, not kept in registers across chunks
+        const int row = lv & 31, half = lv >> 5;
+        const int64_t n = tc * kTile + row;
+        const int64_t M = std::min<int64_t>(kTile, r1 - row0);
+        f32x16 acc = zero16();
+        skinny_run(acc, feed_transposed(img, lv), x + row0 * ldx, M, K, ldx, x_vec, st, tc, tiles_nw, c0, c1, lane, row, half, lv);
+
+        // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tc + row) of slice s of projection p
+        if (n < N) store_lane_rows<false, true>(acc, M, half, ws, (((int64_t)p * split + s) * T + row0 + 4 * half) * N + n, N, 0.0f);
+    }
+}
+
 // skinny_shape for the grouped entry: skinny_split's rule with count * tiles_h tile rows, which for count == 1 is that rule.
 int grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *tiles_h, int64_t *tiles_w, int *split_eff)
 {
@@ -3013,6 +3147,136 @@ extern "C" int mtq_packed_glu_skinny_grouped(const void *x, int64_t total_rows, 
     launch_out(out_dtype, glu_skinny_grouped_reduce_kernel<true>, glu_skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
                st, ws, total_rows, n, g.eff, group_rows, nchunks, bias_gate, bias_up, ldb, act, y, ldy);
     return check_launch("mtq_packed_glu_skinny_grouped");
+}
+
+// ---- gated entries for (k, n) weights: the gated entries' checks, split rules, slot bounds and workspaces (tile_grid of n × k is the grid
+// check of k × n, mtq_packed_matmul's), the kernels with the grid the other way round.
+
+extern "C" int mtq_packed_glu_matmul_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                                          const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
+                                          const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate,
+                                          const float *bias_up, int act, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    int64_t tn, tk;                                  // tiles along n, tiles along k
+    if (int rc = linear_args(x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, n, y, out_dtype, ldy, &tn, &tk)) return rc;
+    if (int rc = linear_args(x, m, k, ldx, up_packed, up_bytes, up_map, up_offsets, n, y, out_dtype, ldy, &tn, &tk)) return rc;
+    if (int rc = glu_act(act)) return rc;
+    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kGluBN - 1) / kGluBN);
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
+    if (int rc = require_device()) return rc;
+    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_matmul_wide_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads),
+               static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(gate_packed),
+               (uint64_t)gate_bytes, gate_map, gate_offsets, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, tk, tn,
+               bias_gate, bias_up, act, y, ldy);
+    return check_launch("mtq_packed_glu_matmul_wide");
+}
+
+extern "C" size_t mtq_packed_glu_matmul_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
+{
+    return mtq_packed_glu_wide_grouped_workspace_bytes(total_rows, count, n, k);   // the same plan
+}
+
+extern "C" int mtq_packed_glu_matmul_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                  const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps,
+                                                  const uint32_t *gate_offsets, const uint64_t *gate_bases, const void *up_packed, size_t up_bytes,
+                                                  const int8_t *up_maps, const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count,
+                                                  int64_t n, const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y,
+                                                  int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream)
+{
+    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
+    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
+                               !up_bases || !y,
+                           out_dtype, [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n,
+                           ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
+    if (int rc = glu_act(act)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
+    // mtq_packed_linear_wide_grouped's slot bound
+    const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
+    const int64_t blocks = slots * ((n + kGluBN - 1) / kGluBN);
+    if (slots > INT32_MAX || blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *bstart = static_cast<int32_t *>(workspace);
+    hipLaunchKernelGGL(packed_grouped_plan_kernel<kWideBM>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
+    if (int rc = check_launch("mtq_packed_glu_matmul_wide_grouped")) return rc;
+    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_matmul_wide_grouped_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), st,
+               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(gate_packed),
+               (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps,
+               up_offsets, up_bases, (int)count, n, g.tw, g.th, bias_gate, bias_up, ldb, act, y, ldy);
+    return check_launch("mtq_packed_glu_matmul_wide_grouped");
+}
+
+extern "C" size_t mtq_packed_glu_matmul_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_glu_skinny_workspace_bytes(m, n, k, split);
+}
+
+extern "C" int mtq_packed_glu_matmul_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                                            const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
+                                            const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate,
+                                            const float *bias_up, int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace,
+                                            size_t workspace_bytes, void *stream)
+{
+    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
+    if (int rc = gemm_args(!x || !gate_packed || !gate_map || !gate_offsets || !up_packed || !up_map || !up_offsets || !y, out_dtype,
+                           [&](SplitGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0,
+                           {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
+    if (int rc = glu_act(act)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(m, n, g.eff), kWsGlu, "split")) return rc;
+    const int64_t blocks = (2 * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(packed_glu_matmul_skinny_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), m,
+                       k, ldx, (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
+                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, g.tw, g.th, g.eff, ws);
+    if (int rc = check_launch("mtq_packed_glu_matmul_skinny")) return rc;
+    launch_out(out_dtype, glu_skinny_reduce_kernel<true>, glu_skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
+               m * n, n, g.eff, bias_gate, bias_up, act, y, ldy);
+    return check_launch("mtq_packed_glu_matmul_skinny");
+}
+
+extern "C" size_t mtq_packed_glu_matmul_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_glu_skinny_grouped_workspace_bytes(total_rows, count, n, k, split);
+}
+
+extern "C" int mtq_packed_glu_matmul_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                    const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps,
+                                                    const uint32_t *gate_offsets, const uint64_t *gate_bases, const void *up_packed,
+                                                    size_t up_bytes, const int8_t *up_maps, const uint32_t *up_offsets, const uint64_t *up_bases,
+                                                    int64_t count, int64_t n, const float *bias_gate, const float *bias_up, int64_t ldb, int act,
+                                                    void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                                    void *stream)
+{
+    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
+    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
+                               !up_bases || !y,
+                           out_dtype, [&](SplitGrid &s) { return glu_grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx,
+                           n, ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
+    if (int rc = glu_act(act)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(total_rows, n, g.eff), kWsGlu, "split")) return rc;
+    const int64_t blocks = (2 * count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    const int64_t nchunks = (n + 255) / 256;
+    if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(packed_glu_matmul_skinny_grouped_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st,
+                       static_cast<const uint16_t *>(x), (int)total_rows, (int)k, ldx, (int)x_vec_of(x, ldx), group_rows,
+                       static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases,
+                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases, (int)count, (int)n, (int)g.tw,
+                       (int)g.th, g.eff, ws);
+    if (int rc = check_launch("mtq_packed_glu_matmul_skinny_grouped")) return rc;
+    launch_out(out_dtype, glu_skinny_grouped_reduce_kernel<true>, glu_skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
+               st, ws, total_rows, n, g.eff, group_rows, nchunks, bias_gate, bias_up, ldb, act, y, ldy);
+    return check_launch("mtq_packed_glu_matmul_skinny_grouped");
 }
 
 extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)

@@ -153,6 +153,13 @@ SIGNATURES = {
     "mtq_moe_plan": ("i", "pillllppppzp", True),
     "mtq_moe_dispatch": ("i", "plllplplp", True),
     "mtq_moe_combine": ("i", "pilpplpillllpilp", True),
+    "mtq_packed_glu_matmul_wide": ("i", "plllpzpppzpplppipilp", True),
+    "mtq_packed_glu_matmul_wide_grouped_workspace_bytes": ("z", "llll", True),
+    "mtq_packed_glu_matmul_wide_grouped": ("i", "plllppzppppzpppllpplipilpzp", True),
+    "mtq_packed_glu_matmul_skinny_workspace_bytes": ("z", "llli", True),
+    "mtq_packed_glu_matmul_skinny": ("i", "plllpzpppzpplppipilipzp", True),
+    "mtq_packed_glu_matmul_skinny_grouped_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_glu_matmul_skinny_grouped": ("i", "plllppzppppzpppllpplipilipzp", True),
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
@@ -1831,6 +1838,133 @@ def packed_glu_skinny_grouped(x, group_rows, gate, up, count: int, n: int, act="
     if T == 0:
         return out
     ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_skinny_grouped_workspace_bytes(T, count, n, k, split), x.device)
+    check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
+             _packed_stream_ptr(stream)))
+    return out
+
+
+PACKED_GLU_MATMUL = ("mtq_packed_glu_matmul_wide", "mtq_packed_glu_matmul_wide_grouped", "mtq_packed_glu_matmul_wide_grouped_workspace_bytes")
+PACKED_GLU_MATMUL_SKINNY = ("mtq_packed_glu_matmul_skinny_workspace_bytes", "mtq_packed_glu_matmul_skinny",
+                            "mtq_packed_glu_matmul_skinny_grouped_workspace_bytes", "mtq_packed_glu_matmul_skinny_grouped")
+
+
+def has_packed_glu_matmul() -> bool:
+    """Whether this build of the library has the gated entries for (k, n) weights (mtq_packed_glu_matmul_wide,
+    mtq_packed_glu_matmul_wide_grouped and its size function; optional symbols: an older build of the same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in PACKED_GLU_MATMUL)
+
+
+def has_packed_glu_matmul_skinny() -> bool:
+    """Whether this build of the library has the fused gated entries for (k, n) weights at decode (mtq_packed_glu_matmul_skinny,
+    mtq_packed_glu_matmul_skinny_grouped and their size functions; optional symbols)."""
+    return all(getattr(lib(), name, None) is not None for name in PACKED_GLU_MATMUL_SKINNY)
+
+
+def _glu_matmul_args(x, gate_data, gate_tables, up_data, up_tables, n, bias_gate, bias_up, skinny: bool):
+    """The single-tensor gated (k, n) entries' operands checked → (m, k, ldx, gate pointer, up pointer, bias_gate pointer, bias_up
+    pointer)."""
+    torch = _torch()
+    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if skinny and m > PACKED_SKINNY_MAX_M:
+        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
+    for name, tables in (("gate", gate_tables), ("up", up_tables)):
+        if tiles_hw(k, n) != (tables.tiles_h, tables.tiles_w):
+            raise MtqError(f"the {name} map is {tables.tiles_h}x{tables.tiles_w} tiles, a {k}x{n} matrix has {'x'.join(map(str, tiles_hw(k, n)))}")
+    pg, pu = _packed_stream(gate_data, gate_tables, "gate data"), _packed_stream(up_data, up_tables, "up data")
+    bg = None if bias_gate is None else _buffer(bias_gate, torch.float32, n, "bias_gate")
+    bu = None if bias_up is None else _buffer(bias_up, torch.float32, n, "bias_up")
+    return m, k, ldx, pg, pu, bg, bu
+
+
+def packed_glu_matmul_wide(x, gate_data, gate_tables: PackedTables, up_data, up_tables: PackedTables, n: int, act="silu", bias_gate=None,
+                           bias_up=None, out_dtype=None, out=None, stream="current"):
+    """mtq_packed_glu_matmul_wide on the current stream: act(X·P̂g + bg) * (X·P̂u + bu) for an (m, k) bf16 device tensor X and two packed
+    (k, n) matrices in one launch → (m, n) float32 or bfloat16: bit for bit two packed_matmul calls into float32 and glu_combine.
+    m = 0 or n = 0 gives the empty (m, n) tensor without a launch."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    m, k, ldx, pg, pu, bg, bu = _glu_matmul_args(x, gate_data, gate_tables, up_data, up_tables, n, bias_gate, bias_up, False)
+    fn = _entry("mtq_packed_glu_matmul_wide")
+    out, ldy = _glu_out(out, m, n, out_dtype, x.device)
+    if m == 0 or n == 0:                             # the entry refuses empty operands, as the wide entry does: they end here
+        return out
+    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
+             up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_glu_matmul_wide_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int) -> int:
+    """mtq_packed_glu_matmul_wide_grouped_workspace_bytes (a host function: no GPU): packed_glu_wide_grouped_workspace_bytes' answer."""
+    return _size_or_raise(int(_entry("mtq_packed_glu_matmul_wide_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k))))
+
+
+def packed_glu_matmul_wide_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None,
+                                   out=None, workspace=None, stream="current"):
+    """mtq_packed_glu_matmul_wide_grouped on the current stream: packed_glu_matmul_wide's product for the `count` (k, n) experts of two
+    arenas, each over its own rows of X, in one launch.  Operands as packed_glu_wide_grouped takes them.  Per group the bits of two
+    packed_matmul calls into float32 and glu_combine on the group's rows.  An `out` allocated here starts as zeros."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    count, n, T, k, ldx, pg, sides, ptrs, ldb = _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up)
+    fn = _entry("mtq_packed_glu_matmul_wide_grouped")
+    out, ldy = _glu_out(out, T, n, out_dtype, x.device, zeros=True)
+    if T == 0:
+        return out
+    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_matmul_wide_grouped_workspace_bytes(T, count, n, k), x.device)
+    check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, ws_ptr, ws_bytes,
+             _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_glu_matmul_skinny_workspace_bytes(m: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_glu_matmul_skinny_workspace_bytes (a host function: no GPU): packed_glu_skinny_workspace_bytes' answer."""
+    return _size_or_raise(int(_entry("mtq_packed_glu_matmul_skinny_workspace_bytes")(int(m), int(n), int(k), int(split))))
+
+
+def packed_glu_matmul_skinny(x, gate_data, gate_tables: PackedTables, up_data, up_tables: PackedTables, n: int, act="silu", bias_gate=None,
+                             bias_up=None, out_dtype=None, out=None, split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_glu_matmul_skinny on the current stream: packed_glu_matmul_wide's product for m <= 32 with a split over K (split 0: the
+    library's choice), two launches: bit for bit two packed_matmul_skinny calls into float32 at that split and glu_combine.  workspace
+    as packed_glu_skinny takes it.  m = 0 or n = 0 gives the empty (m, n) tensor without a launch."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    m, k, ldx, pg, pu, bg, bu = _glu_matmul_args(x, gate_data, gate_tables, up_data, up_tables, n, bias_gate, bias_up, True)
+    fn = _entry("mtq_packed_glu_matmul_skinny")
+    out, ldy = _glu_out(out, m, n, out_dtype, x.device)
+    if m == 0 or n == 0:                             # the entry refuses empty operands, as the skinny entry does: they end here
+        return out
+    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_matmul_skinny_workspace_bytes(m, n, k, split), x.device)
+    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
+             up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
+             _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_glu_matmul_skinny_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_glu_matmul_skinny_grouped_workspace_bytes (a host function: no GPU): packed_glu_skinny_grouped_workspace_bytes' answer."""
+    return _size_or_raise(int(_entry("mtq_packed_glu_matmul_skinny_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k),
+                                                                                             int(split))))
+
+
+def packed_glu_matmul_skinny_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None,
+                                     out=None, split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_glu_matmul_skinny_grouped on the current stream: packed_glu_matmul_wide_grouped's operands and product from the skinny
+    family's split over K, for decode-sized groups: per group the bits of two packed_matmul_skinny_grouped calls into float32 at that
+    split and glu_combine.  An `out` allocated here starts as zeros, so rows outside every group are zeros."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    count, n, T, k, ldx, pg, sides, ptrs, ldb = _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up)
+    fn = _entry("mtq_packed_glu_matmul_skinny_grouped")
+    out, ldy = _glu_out(out, T, n, out_dtype, x.device, zeros=True)
+    if T == 0:
+        return out
+    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_matmul_skinny_grouped_workspace_bytes(T, count, n, k, split), x.device)
     check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
              _packed_stream_ptr(stream)))
     return out

@@ -32,11 +32,16 @@ moe_plan / moe_dispatch / moe_combine / PackedMoE are the rest of an MoE layer a
 router's (tokens, top_k) expert ids a stable counting sort on the device gives the grouped entries' row layout (MoEPlan), a row gather
 puts the tokens in it, and a weighted un-permute with a fixed summation order brings the experts' rows back; nothing is read back to
 the host.  Router scoring (softmax / sigmoid, group-limited top-k) stays the model's; the gather is not fused into the GEMMs' X loads
-and the combine not into the down projection's epilogue (both would change existing kernels); there is no MLP over (k, n) experts.
+and the combine not into the down projection's epilogue (both would change existing kernels).
 
-Not built: a fused kernel for the decode range (the skinny family's split over K has partial sums); grouped and GLU variants of
-the (k, n) product; pack_transposed of tensors of rank other than 2 (pack_model.py packs their permuted copies with pack);
-activations other than ACTS.
+glu_matmul / glu_matmul_skinny / glu_matmul_grouped / glu_matmul_grouped_skinny are glu and its three variants for packed (k, n) gate and
+up matrices (mtq_packed_glu_matmul_wide, _wide_grouped, _skinny, _skinny_grouped: the gated frames with the matmul kernels' feed), bit
+for bit two matmul calls into float32 and the combine; PackedMatmulMLP and PackedExpertsMatmulMLP are PackedMLP and PackedExpertsMLP over
+such weights, and PackedMoE(stored="transpose") is the layer over them: a pack_model.py --store-transposed directory of an MoE layer's
+experts runs with no Python loop over experts.
+
+Not built: a chunked variant of the grouped skinny GLU kernels; pack_transposed of tensors of rank other than 2 (pack_model.py packs
+their permuted copies with pack); activations other than ACTS.
 
 Two backends:
   "hip"        the C ABI (csrc/mtq_packed.hip) through hip_backend's wrappers; data lives on the device.
@@ -90,6 +95,14 @@ MLP_DECODE_KERNELS = ("pair", "fused")   # PackedMLP(decode_kernel=...): glu(ker
 # same run at every shape and map (profiles/packed_glu.txt).  Both routes give the same bits, so the gate changes no
 # result.
 AUTO_GLU_FUSED_MIN_M = 64
+# glu_matmul(kernel="auto"), the same two gates for (k, n) weights, constants of their own: two matmul(kernel="skinny") calls and the
+# combine up to AUTO_GLU_MATMUL_SKINNY_MAX_M, the fused kernel (mtq_packed_glu_matmul_wide) from AUTO_GLU_MATMUL_FUSED_MIN_M on (None:
+# never), "unfused" between.  They start at the linear family's values; DESIGN.md §A.6x and profiles/packed_glu_matmul.txt have the
+# measurement that keeps or moves them.  All routes above the skinny range give the same bits, so the upper gate changes no result.
+AUTO_GLU_MATMUL_SKINNY_MAX_M = 32
+AUTO_GLU_MATMUL_FUSED_MIN_M = 64
+MATMUL_MLP_DECODE_KERNELS = ("pair", "fused")   # PackedMatmulMLP(decode_kernel=...): as MLP_DECODE_KERNELS, with glu_matmul / glu_matmul_skinny
+MOE_STORED = ("rows", "transpose")              # PackedMoE(stored=...): the index.json word of a pack_model directory
 # The largest error of the device's silu (csrc/mtq_glu.hpp glu_value at u = 1) against float64, in units of 2^-24 relative to the value,
 # over every 2^10-th float32 of [-88.7228, 100], rounded up to a hundredth: measured; the GPU tests hold the kernel to
 # it and form their bound's constant from it.  Below -88.7228 expf(-g) overflows and the sequence gives -0.
@@ -1496,9 +1509,229 @@ def _glu_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, o
     return _round_out(h, out_dtype)
 
 
+# ----------------------------------------------------------------------------- the gated product over (k, n) weights
+
+def _glu_matmul_pair(gate: PackedTensor, up: PackedTensor, what: str) -> None:
+    for pt in (gate, up):
+        _check_kn(pt, what)
+    if (gate.rows, gate.cols) != (up.rows, up.cols):
+        raise MtqError(f"gate and up must have one shape, got {gate.rows}x{gate.cols} and {up.rows}x{up.cols}")
+
+
+def _need_glu_matmul(hb, what: str) -> None:
+    if not hb.has_packed_glu() or not hb.has_packed_glu_matmul():
+        raise MtqError(f"{what} needs mtq_glu_combine and {' and '.join(hb.PACKED_GLU_MATMUL)}, which this build of libmtq_hip.so lacks: "
+                       "rebuild it from this tree")
+
+
+def _need_glu_matmul_skinny(hb, what: str) -> None:
+    if not hb.has_packed_glu_matmul_skinny():
+        raise MtqError(f"{what} needs {' and '.join(hb.PACKED_GLU_MATMUL_SKINNY)}, which this build of libmtq_hip.so lacks: rebuild it "
+                       "from this tree")
+
+
+def glu_matmul_emulation_f64(xf: np.ndarray, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None) -> np.ndarray:
+    """glu_emulation_f64 for packed (k, n) matrices: g = X·P̂g + bg, u = X·P̂u + bu in float64 on unpack's values, act(g) * u, before the
+    final rounding."""
+    k, n = gate.rows, gate.cols
+    x64 = np.asarray(xf, dtype=np.float32).astype(np.float64)
+    sides = []
+    for pt, bias, name in ((gate, bias_gate, "bias_gate"), (up, bias_up, "bias_up")):
+        w = decode(_host_data(pt), pt.map, pt.offsets, k, n).view(np.float32)
+        with np.errstate(over="ignore", invalid="ignore"):
+            y = x64 @ w.astype(np.float64)
+        b = _host_f64(bias, (n,), name)
+        sides.append(y if b is None else y + b[None, :])
+    return _glu_host(sides[0], sides[1], act)
+
+
+def glu_matmul(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
+               backend: Optional[str] = None, kernel: str = "auto"):
+    """H = act(X·P̂g + bg) * (X·P̂u + bu), glu for two packed (k, n) matrices of one shape: what matmul takes - pack_transposed's and
+    pack_batch_transposed's results, the entries of a pack_model --store-transposed directory, input-major weights.
+
+    hip (the default when the gate's stream is on the device): X an (m, k) bf16 device tensor, the biases float32 [n] or None.  kernel
+    (GLU_KERNELS): "fused", mtq_packed_glu_matmul_wide, one launch in which a workgroup holds both projections of its outputs;
+    "unfused", two matmul(kernel="block") calls into float32 and hip_backend.glu_combine, bit for bit what "fused" gives; "auto": for
+    m <= AUTO_GLU_MATMUL_SKINNY_MAX_M two matmul(kernel="skinny") calls and the combine (the skinny family's sums; glu_matmul_skinny is
+    the same bits from the fused decode kernel), above that "fused" from m = AUTO_GLU_MATMUL_FUSED_MIN_M on when that is not None,
+    "unfused" otherwise.  Every route equals glu's of the same name on the all-bf16 row-layout packings of unpack(P̂)ᵀ.  A library without
+    the entries raises MtqError under every name: there is no fall-back.
+    emulation: float64 throughout from the unpacked matrices (glu_matmul_emulation_f64), rounded once to float32 and from there to
+    bf16; the same value under every kernel name."""
+    _glu_matmul_pair(gate, up, "glu_matmul")
+    _check_act(act)
+    if kernel not in GLU_KERNELS:
+        raise MtqError(f"kernel must be one of {GLU_KERNELS}, got {kernel!r}")
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    backend = backend or ("hip" if gate.on_device else "emulation")
+    k, n = gate.rows, gate.cols
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        if x.dim() != 2 or x.shape[1] != k:
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        _need_matmul(hb, "glu_matmul")
+        _need_glu_matmul(hb, "glu_matmul")
+        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        m = int(x.shape[0])
+        if kernel == "auto":
+            if AUTO_GLU_MATMUL_SKINNY_MAX_M is not None and m <= AUTO_GLU_MATMUL_SKINNY_MAX_M:
+                kernel = "skinny"
+            else:
+                kernel = "fused" if AUTO_GLU_MATMUL_FUSED_MIN_M is not None and m >= AUTO_GLU_MATMUL_FUSED_MIN_M else "unfused"
+        if kernel == "fused":
+            return hb.packed_glu_matmul_wide(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act,
+                                             bias_gate=bias_gate, bias_up=bias_up, out_dtype=dtype)
+        if kernel == "skinny":
+            _need_matmul_skinny(hb, 'glu_matmul(kernel="auto")')
+            g = hb.packed_matmul_skinny(x, _device_data(gate), gate.tables(), n, bias=bias_gate, out_dtype=torch.float32)
+            u = hb.packed_matmul_skinny(x, _device_data(up), up.tables(), n, bias=bias_up, out_dtype=torch.float32)
+        else:
+            g = hb.packed_matmul(x, _device_data(gate), gate.tables(), n, bias=bias_gate, out_dtype=torch.float32)
+            u = hb.packed_matmul(x, _device_data(up), up.tables(), n, bias=bias_up, out_dtype=torch.float32)
+        return hb.glu_combine(g, u, act=act, out_dtype=dtype)
+    if backend != "emulation":
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
+    if xf.ndim != 2 or xf.shape[1] != k:
+        raise MtqError(f"x must be (m, {k}), got {xf.shape}")
+    return _round_out(glu_matmul_emulation_f64(xf, gate, up, act, bias_gate, bias_up), out_dtype)
+
+
+def glu_matmul_skinny(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
+                      backend: Optional[str] = None, split: int = 0, workspace=None):
+    """glu_matmul for decode, m <= SKINNY_MAX_M, from the fused split-K kernel: mtq_packed_glu_matmul_skinny, two launches in place of
+    the five of glu_matmul(kernel="auto") at these m, and at split 0 bit for bit its value; at any `split`, the bits of two
+    matmul(kernel="skinny") calls into float32 at that split and hip_backend.glu_combine, hence glu_skinny's on the all-bf16 row-layout
+    packings of unpack(P̂)ᵀ.  `split` and `workspace` as in glu_skinny.  m > SKINNY_MAX_M and a library without the entry raise
+    MtqError: there is no fall-back.
+    emulation: glu_matmul's float64 value rounded once, whatever m and split."""
+    _glu_matmul_pair(gate, up, "glu_matmul_skinny")
+    _check_act(act)
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    backend = backend or ("hip" if gate.on_device else "emulation")
+    k, n = gate.rows, gate.cols
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        if x.dim() != 2 or x.shape[1] != k:
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        _need_glu_matmul_skinny(hb, "glu_matmul_skinny")
+        if int(x.shape[0]) > SKINNY_MAX_M:
+            raise MtqError(f"glu_matmul_skinny takes m <= {SKINNY_MAX_M}, got m = {int(x.shape[0])}: glu_matmul(kernel=\"auto\") serves every m")
+        return hb.packed_glu_matmul_skinny(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act, bias_gate=bias_gate,
+                                           bias_up=bias_up, out_dtype=torch.float32 if out_dtype == "float32" else torch.bfloat16, split=split,
+                                           workspace=workspace)
+    return glu_matmul(x, gate, up, act=act, bias_gate=bias_gate, bias_up=bias_up, out_dtype=out_dtype, backend=backend)
+
+
+def glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
+                       backend: Optional[str] = None, kernel: str = "fused", workspace=None):
+    """glu_matmul for all (k, n) experts of an MoE layer at once → (T, n): glu_grouped for experts stored as matmul_grouped takes them,
+    batch.rows == k and batch.cols == n (a pack_batch_transposed list, as_batch of a pack_model --store-transposed directory's entries).
+    hip: kernel "fused", mtq_packed_glu_matmul_wide_grouped, one launch over both arenas with the block list made on the device
+    (workspace: an optional uint8 device tensor of hip_backend.packed_glu_matmul_wide_grouped_workspace_bytes bytes); "unfused", two
+    matmul_grouped_wide calls into float32 and hip_backend.glu_combine over all T rows - the same bits on every row of a group; a row of
+    no group is zero under both.  T = 0 gives (0, n) without a call.
+    emulation: per group glu_matmul's float64 value, rounded once."""
+    return _glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, GLU_GROUPED_KERNELS, 0,
+                               workspace)
+
+
+def glu_matmul_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
+                              backend: Optional[str] = None, split: int = 0, workspace=None):
+    """glu_matmul_grouped for decode-sized groups from the fused split-K kernel: mtq_packed_glu_matmul_skinny_grouped, two launches over
+    both arenas.  Per group the bits of two matmul_grouped(kernel="walk") calls into float32 at that `split` and
+    hip_backend.glu_combine: the skinny family's sums, which may differ from glu_matmul_grouped's in the last bits.  Rows of no group are
+    zeros.  workspace: an optional uint8 device tensor of hip_backend.packed_glu_matmul_skinny_grouped_workspace_bytes bytes.  T = 0
+    gives (0, n) without a call; a library without the entry raises MtqError: there is no fall-back.
+    emulation: glu_matmul_grouped's value."""
+    return _glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, "skinny", ("skinny",), split,
+                               workspace)
+
+
+def _glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, kernels, split, workspace):
+    """glu_matmul_grouped and glu_matmul_grouped_skinny: `kernel` one of `kernels`, GLU_GROUPED_KERNELS or, from the latter alone,
+    ("skinny",)."""
+    gate_b, up_b = _resolve_batch(gate_batch), _resolve_batch(up_batch)
+    _check_act(act)
+    if kernel not in kernels:
+        raise MtqError(f"kernel must be one of {kernels}, got {kernel!r}")
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    if (gate_b.count, gate_b.rows, gate_b.cols) != (up_b.count, up_b.rows, up_b.cols):
+        raise MtqError(f"the gate and the up batch must hold as many experts of one shape, got {gate_b.count} of {gate_b.rows}x{gate_b.cols} and "
+                       f"{up_b.count} of {up_b.rows}x{up_b.cols}")
+    backend = backend or ("hip" if _batch_on_device(gate_b) else "emulation")
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    count, k, n = gate_b.count, gate_b.rows, gate_b.cols
+    if len(x.shape) != 2 or x.shape[1] != k:
+        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
+    T = int(x.shape[0])
+    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
+    if not on_device:
+        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
+    if backend == "hip":
+        import torch
+
+        from . import hip_backend as hb
+
+        if kernel == "skinny":                       # a missing kernel is refused before any device work
+            _need_glu_matmul_skinny(hb, "glu_matmul_grouped_skinny")
+        else:
+            _need_glu_matmul(hb, "glu_matmul_grouped")
+        gate_b, up_b = batch_to_device(gate_b), batch_to_device(up_b)
+        dev = gate_b.arena.device
+        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        if T == 0:
+            return torch.zeros((0, n), dtype=dtype, device=dev)
+        if not on_device:
+            group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(dev)
+        bias_gate, bias_up = (b if b is None or _is_torch(b) else torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(dev)
+                              for b in (bias_gate, bias_up))
+        sides = ((gate_b.arena, gate_b.maps_dev, gate_b.offsets_dev, gate_b.bases_dev), (up_b.arena, up_b.maps_dev, up_b.offsets_dev, up_b.bases_dev))
+        if kernel == "skinny":
+            return hb.packed_glu_matmul_skinny_grouped(x, group_rows, sides[0], sides[1], count, n, act=act, bias_gate=bias_gate, bias_up=bias_up,
+                                                       out_dtype=dtype, split=split, workspace=workspace)
+        if kernel == "fused":
+            return hb.packed_glu_matmul_wide_grouped(x, group_rows, sides[0], sides[1], count, n, act=act, bias_gate=bias_gate, bias_up=bias_up,
+                                                     out_dtype=dtype, workspace=workspace)
+        g = matmul_grouped_wide(x, group_rows, gate_b, bias=bias_gate, out_dtype="float32", backend="hip", workspace=workspace)
+        u = matmul_grouped_wide(x, group_rows, up_b, bias=bias_up, out_dtype="float32", backend="hip", workspace=workspace)
+        return hb.glu_combine(g, u, act=act, out_dtype=dtype)
+    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
+    if on_device:                                    # trusted, as on hip: what the kernel makes of it
+        if tuple(group_rows.shape) != (count + 1,):
+            raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {tuple(group_rows.shape)}")
+        r0, r1 = clamp_group_rows(group_rows.cpu().numpy(), T)
+    else:
+        r0, r1 = group_rows[:-1], group_rows[1:]
+    bg, bu = _host_f64(bias_gate, (count, n), "bias_gate"), _host_f64(bias_up, (count, n), "bias_up")
+    h = np.zeros((T, n), dtype=np.float64)
+    x64 = xf.astype(np.float64)
+    for e, (tg, tu) in enumerate(zip(_batch_host_tensors(gate_b), _batch_host_tensors(up_b))):
+        if r1[e] == r0[e]:
+            continue
+        sides = []
+        for (amap, offsets, data), b in ((tg, bg), (tu, bu)):
+            w = decode(data, amap, offsets, k, n).view(np.float32)
+            y = x64[r0[e]: r1[e]] @ w.astype(np.float64)
+            sides.append(y if b is None else y + b[e][None, :])
+        h[r0[e]: r1[e]] = _glu_host(sides[0], sides[1], act)
+    return _round_out(h, out_dtype)
+
+
 # ----------------------------------------------------------------------------- MoE routing: plan, dispatch, combine
 
-MOE_MAX_TOPK = 64            # include/mtq.h MTQ_MOE_MAX_TOPK
+MOE_MAX_TOPK = 64           # include/mtq.h MTQ_MOE_MAX_TOPK
 MOE_MAX_EXPERTS = 4096       # include/mtq.h MTQ_MOE_MAX_EXPERTS
 
 
@@ -1796,6 +2029,141 @@ def _packed_experts_mlp_class():
     return PackedExpertsMLP
 
 
+def _packed_matmul_mlp_class():
+    import torch
+
+    class PackedMatmulMLP(torch.nn.Module):
+        """PackedMLP over three packed (k, n) matrices, as matmul takes them: gate and up (k, hidden), down (hidden, k_out) - the
+        entries of a pack_model --store-transposed directory, pack_transposed's results, input-major weights.  INFERENCE ONLY.
+        forward(x) takes bf16 (..., k), flattens the leading dimensions to m, runs glu_matmul(kernel="auto") into bf16 and
+        matmul(kernel="auto") with `down`, and returns (..., k_out) in out_dtype; m = 0 gives the empty result without a call.
+        decode_kernel (MATMUL_MLP_DECODE_KERNELS): "pair", that route at every m; "fused", m <= AUTO_GLU_MATMUL_SKINNY_MAX_M goes through
+        glu_matmul_skinny instead, the same bits from two launches in place of five."""
+
+        def __init__(self, gate_kn: PackedTensor, up_kn: PackedTensor, down_kn: PackedTensor, act: str = "silu", out_dtype: str = "bfloat16",
+                     backend: Optional[str] = None, decode_kernel: str = "pair"):
+            super().__init__()
+            if decode_kernel not in MATMUL_MLP_DECODE_KERNELS:
+                raise MtqError(f"decode_kernel must be one of {MATMUL_MLP_DECODE_KERNELS}, got {decode_kernel!r}")
+            _glu_matmul_pair(gate_kn, up_kn, "PackedMatmulMLP")
+            _check_act(act)
+            _check_layout(down_kn.layout)
+            if len(down_kn.shape) != 2 or down_kn.rows != gate_kn.cols:
+                raise MtqError(f"down must be a 2-D ({gate_kn.cols}, k_out) matrix, the packed tensor is {down_kn.shape}")
+            if out_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            self.backend = backend or ("hip" if gate_kn.on_device else "emulation")
+            if self.backend not in BACKENDS:
+                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            if self.backend == "hip":
+                from . import hip_backend as hb
+
+                _need_matmul(hb, "PackedMatmulMLP")  # refused here, not at the first forward
+                _need_glu_matmul(hb, "PackedMatmulMLP")
+                if decode_kernel == "fused":
+                    _need_glu_matmul_skinny(hb, 'PackedMatmulMLP(decode_kernel="fused")')
+                for pt in (gate_kn, up_kn, down_kn):
+                    _device_data(pt)
+                    pt.tables()
+            self.gate, self.up, self.down, self.act, self.out_dtype, self.decode_kernel = gate_kn, up_kn, down_kn, act, out_dtype, decode_kernel
+            self.in_features, self.hidden_features, self.out_features = gate_kn.rows, gate_kn.cols, down_kn.cols
+
+        def extra_repr(self) -> str:
+            return f"in_features={self.in_features}, hidden_features={self.hidden_features}, out_features={self.out_features}, " \
+                   f"act={self.act!r}, backend={self.backend!r}"
+
+        @torch.no_grad()
+        def forward(self, x):
+            if x.shape[-1] != self.in_features:
+                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
+            lead = tuple(x.shape[:-1])
+            x2 = x.reshape(-1, self.in_features)
+            if x2.shape[0] == 0:
+                return torch.zeros(lead + (self.out_features,), dtype=torch.float32 if self.out_dtype == "float32" else torch.bfloat16, device=x.device)
+            if self.decode_kernel == "fused" and AUTO_GLU_MATMUL_SKINNY_MAX_M is not None and x2.shape[0] <= AUTO_GLU_MATMUL_SKINNY_MAX_M:
+                h = glu_matmul_skinny(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend)
+            else:
+                h = glu_matmul(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="auto")
+            y = matmul(h, self.down, out_dtype=self.out_dtype, backend=self.backend, kernel="auto")
+            if not _is_torch(y):
+                y = torch.from_numpy(y)
+            return y.reshape(lead + (self.out_features,))
+
+    return PackedMatmulMLP
+
+
+def _packed_experts_matmul_mlp_class():
+    import torch
+
+    class PackedExpertsMatmulMLP(torch.nn.Module):
+        """PackedExpertsMLP over three batches of `count` (k, n) experts, as matmul_grouped takes them: gate and up (k, hidden), down
+        (hidden, k_out) - pack_batch_transposed lists, or as_batch of a pack_model --store-transposed directory's entries.  INFERENCE
+        ONLY.  forward(x, group_rows): x (T, k) bf16 → (T, k_out): glu_matmul_grouped (kernel "fused") into bf16, then
+        matmul_grouped_wide with the down batch.  The batches are resolved once, here; on hip the arenas, their tables and the one plan
+        workspace both launches use stay on the device.  T = 0 gives the empty result.
+        decode_max_rows: None, that route at every T; a positive number, a forward with T <= decode_max_rows goes through
+        glu_matmul_grouped_skinny into bf16 and matmul_grouped(kernel="walk") with the down batch instead (the skinny family's sums,
+        which may differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows."""
+
+        def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", backend: Optional[str] = None,
+                     decode_max_rows: Optional[int] = None):
+            super().__init__()
+            _check_act(act)
+            if decode_max_rows is not None and (isinstance(decode_max_rows, bool) or not isinstance(decode_max_rows, int) or decode_max_rows <= 0):
+                raise MtqError(f"decode_max_rows must be None or a positive int, got {decode_max_rows!r}")
+            if out_dtype not in ("float32", "bfloat16"):
+                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            gate, up, down = (_resolve_batch(b) for b in (gate_pts, up_pts, down_pts))
+            if (gate.count, gate.rows, gate.cols) != (up.count, up.rows, up.cols):
+                raise MtqError("the gate and the up batch must hold as many experts of one shape")
+            if down.count != gate.count or down.rows != gate.cols:
+                raise MtqError(f"the down batch must hold {gate.count} experts of ({gate.cols}, k_out), got {down.count} of {down.rows}x{down.cols}")
+            self.backend = backend or ("hip" if _batch_on_device(gate) else "emulation")
+            if self.backend not in BACKENDS:
+                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            self._workspace = None
+            self._decode_workspace = None
+            if self.backend == "hip":
+                from . import hip_backend as hb
+
+                _need_glu_matmul(hb, "PackedExpertsMatmulMLP")   # refused here, not at the first forward
+                _matmul_grouped_entries("wide")
+                if decode_max_rows is not None:
+                    _need_glu_matmul_skinny(hb, "PackedExpertsMatmulMLP(decode_max_rows=...)")
+                    _matmul_grouped_entries("walk")
+                gate, up, down = (batch_to_device(b) for b in (gate, up, down))
+                need = hb.packed_glu_matmul_wide_grouped_workspace_bytes(1, gate.count, gate.cols, gate.rows)   # a function of count alone
+                self._workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
+                if decode_max_rows is not None:      # one buffer for both decode launches: each is done with it before the next starts
+                    need = max(hb.packed_glu_matmul_skinny_grouped_workspace_bytes(decode_max_rows, gate.count, gate.cols, gate.rows),
+                               hb.packed_matmul_skinny_grouped_workspace_bytes(decode_max_rows, down.count, down.cols, down.rows))
+                    self._decode_workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
+            self.decode_max_rows = decode_max_rows
+            self.gate, self.up, self.down, self.act, self.out_dtype = gate, up, down, act, out_dtype
+            self.count, self.in_features, self.hidden_features, self.out_features = gate.count, gate.rows, gate.cols, down.cols
+
+        def extra_repr(self) -> str:
+            return f"count={self.count}, in_features={self.in_features}, hidden_features={self.hidden_features}, " \
+                   f"out_features={self.out_features}, act={self.act!r}, backend={self.backend!r}"
+
+        @torch.no_grad()
+        def forward(self, x, group_rows):
+            if x.dim() != 2 or x.shape[1] != self.in_features:
+                raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
+            if self.decode_max_rows is not None and x.shape[0] <= self.decode_max_rows:
+                h = glu_matmul_grouped_skinny(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend,
+                                              workspace=self._decode_workspace)
+                y = matmul_grouped(h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend, workspace=self._decode_workspace,
+                                   kernel="walk")
+                return y if _is_torch(y) else torch.from_numpy(y)
+            h = glu_matmul_grouped(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="fused",
+                                   workspace=self._workspace)
+            y = matmul_grouped_wide(h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend, workspace=self._workspace)
+            return y if _is_torch(y) else torch.from_numpy(y)
+
+    return PackedExpertsMatmulMLP
+
+
 MOE_PLAN_TOPK = 8   # PackedMoE sizes its first plan workspace for max_tokens tokens of this many slots each; a larger call regrows it
 
 
@@ -1811,22 +2179,28 @@ def _packed_moe_class():
         result without a call.  Router scoring (softmax / sigmoid, group-limited top-k) stays the model's.
         expert_dtype: the type of the experts' rows the combine reads ("float32": the down projection's sums unrounded; "bfloat16":
         half the bytes).  decode_max_rows: PackedExpertsMLP's, compared against S, the rows the experts see.
+        stored (MOE_STORED, the word of a pack_model directory's index.json): "rows", the experts are (n, k) batches and run through
+        PackedExpertsMLP; "transpose", they are (k, n) batches - gate and up (k, hidden), down (hidden, k_out), what pack_model
+        --store-transposed and pack_batch_transposed write - and run through PackedExpertsMatmulMLP.  Plan, dispatch and combine are the same.
         hip: no device-to-host copy and no .item() in a forward; the plan workspace is allocated here for max_tokens tokens and
         regrown when a call needs more.  emulation: CPU tensors, for use without a GPU."""
 
         def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", expert_dtype: str = "float32",
-                     backend: Optional[str] = None, decode_max_rows: Optional[int] = None, max_tokens: int = 4096):
+                     backend: Optional[str] = None, decode_max_rows: Optional[int] = None, max_tokens: int = 4096, stored: str = "rows"):
             super().__init__()
+            if stored not in MOE_STORED:
+                raise MtqError(f"stored must be one of {MOE_STORED}, got {stored!r}")
             if out_dtype not in ("float32", "bfloat16"):
                 raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
             if expert_dtype not in ("float32", "bfloat16"):
                 raise MtqError(f"expert_dtype must be 'float32' or 'bfloat16', got {expert_dtype!r}")
             if isinstance(max_tokens, bool) or not isinstance(max_tokens, int) or max_tokens <= 0:
                 raise MtqError(f"max_tokens must be a positive int, got {max_tokens!r}")
-            experts_mlp = globals().get("PackedExpertsMLP") or __getattr__("PackedExpertsMLP")
+            experts_name = "PackedExpertsMLP" if stored == "rows" else "PackedExpertsMatmulMLP"
+            experts_mlp = globals().get(experts_name) or __getattr__(experts_name)
             self.experts = experts_mlp(gate_pts, up_pts, down_pts, act=act, out_dtype=expert_dtype, backend=backend,
                                        decode_max_rows=decode_max_rows)
-            self.backend, self.out_dtype, self.expert_dtype = self.experts.backend, out_dtype, expert_dtype
+            self.backend, self.out_dtype, self.expert_dtype, self.stored = self.experts.backend, out_dtype, expert_dtype, stored
             self.count, self.in_features, self.out_features = self.experts.count, self.experts.in_features, self.experts.out_features
             if self.count > MOE_MAX_EXPERTS:
                 raise MtqError(f"PackedMoE takes at most {MOE_MAX_EXPERTS} experts, got {self.count}")
@@ -2158,11 +2532,12 @@ def _packed_experts_matmul_class():
 
 
 def __getattr__(name):
-    """PackedLinear, PackedMatmul, PackedExperts, PackedExpertsMatmul, PackedMLP, PackedExpertsMLP and PackedMoE are torch.nn.Modules: a
-    class is made on first use, so that importing this module does not import torch."""
+    """PackedLinear, PackedMatmul, PackedExperts, PackedExpertsMatmul, PackedMLP, PackedExpertsMLP, PackedMatmulMLP, PackedExpertsMatmulMLP
+    and PackedMoE are torch.nn.Modules: a class is made on first use, so that importing this module does not import torch."""
     makers = {"PackedLinear": _packed_linear_class, "PackedMatmul": _packed_matmul_class, "PackedExperts": _packed_experts_class,
               "PackedExpertsMatmul": _packed_experts_matmul_class,
-              "PackedMLP": _packed_mlp_class, "PackedExpertsMLP": _packed_experts_mlp_class, "PackedMoE": _packed_moe_class}
+              "PackedMLP": _packed_mlp_class, "PackedExpertsMLP": _packed_experts_mlp_class, "PackedMoE": _packed_moe_class,
+              "PackedMatmulMLP": _packed_matmul_mlp_class, "PackedExpertsMatmulMLP": _packed_experts_matmul_mlp_class}
     if name in makers:
         cls = makers[name]()
         globals()[name] = cls
