@@ -1101,60 +1101,99 @@ def unpack_tiles_batched(data, maps_dev, offsets_dev, bases_dev, count: int, row
     return out
 
 
-def packed_linear(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, stream="current"):
-    """mtq_packed_linear on the current stream: Y = X·Ŵᵀ + b for an (m, k) bf16 device tensor X with contiguous rows and the packed
-    (n, k) weight → (m, n) float32 or bfloat16 device tensor."""
+# The product entries below come in twins: one for a packed (n, k) weight (packed_linear*, packed_glu*) and one for a packed (k, n)
+# matrix (packed_matmul*, packed_glu_matmul*).  A twin pair shares one body, told apart by `kn`; what else differs between two
+# entries of a body is an argument of it, named where it is passed.
+
+def _has(names) -> bool:
+    """Whether this build of the library binds every one of `names` (optional symbols: an older build of the same version lacks them)."""
+    return all(getattr(lib(), name, None) is not None for name in names)
+
+
+def _workspace_size(name: str, *args) -> int:
+    """A size function of the library (a host function: no GPU) on int arguments; its (size_t)-1 is the library's refusal."""
+    size = int(_entry(name)(*map(int, args)))
+    if size == ctypes.c_size_t(-1).value:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return size
+
+
+def _packed_out(out, rows: int, cols: int, out_dtype, device, zeros: bool = False):
+    """`out` checked, or a new (rows, cols) tensor → (out, ldy)."""
+    torch = _torch()
+    if out is None:
+        require_gpu()
+        out = (torch.zeros if zeros else torch.empty)((rows, cols), dtype=out_dtype, device=device)
+    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (rows, cols) or out.stride(1) != 1 or not out.is_cuda:
+        raise MtqError(f"out must be a {out_dtype} ({rows}, {cols}) device tensor with contiguous rows")
+    return out, (out.stride(0) if rows > 1 else max(out.stride(0), cols))
+
+
+def _packed_workspace(workspace, need: int, device):
+    """`workspace` checked, or a new one of `need` bytes → (pointer, bytes)."""
+    torch = _torch()
+    if workspace is None:
+        require_gpu()
+        workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+    ws_ptr = _buffer(workspace, torch.uint8, need, "workspace")
+    if workspace.data_ptr() % 16:
+        raise MtqError("workspace must be 16-byte aligned")
+    return ws_ptr, int(workspace.numel())
+
+
+def _grid_error(tables, n: int, k: int, kn: bool, side: str = "") -> MtqError:
+    """The tables' tile grid is not the operand's: an (n, k) weight's, or with `kn` a (k, n) matrix's."""
+    rows, cols, noun = (k, n, "matrix") if kn else (n, k, "weight")
+    own = "x".join(map(str, tiles_hw(rows, cols)))
+    return MtqError(f"the {side}map is {tables.tiles_h}x{tables.tiles_w} tiles, a {rows}x{cols} {noun} has {own}")
+
+
+def _packed_product_call(name, kn, empty, x, data, tables, n, bias, out_dtype, out, stream, size=None, split=0, workspace=None, size_first=False):
+    """The checks and the call the single-tensor product entries share.  empty: which of "m" and "n" being 0 ends here with the empty
+    `out` ("" : the library's refusal of empty operands reaches the caller).  size: a skinny entry's own size function, which makes
+    the call one with m <= 32, a split and a workspace; size_first: it is asked before `out` is looked at."""
     torch = _torch()
     out_dtype = out_dtype or torch.float32
     code = _packed_out_code(out_dtype)
     x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
     if x_code != DTYPE_BF16:
         raise MtqError("x must be a bfloat16 tensor")
-    if tiles_hw(n, k) != (tables.tiles_h, tables.tiles_w):
-        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {n}x{k} weight has {'x'.join(map(str, tiles_hw(n, k)))}")
+    if size is not None and m > PACKED_SKINNY_MAX_M:
+        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
+    if (tiles_hw(k, n) if kn else tiles_hw(n, k)) != (tables.tiles_h, tables.tiles_w):
+        raise _grid_error(tables, n, k, kn)
     ptr = _packed_stream(data, tables)
     bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
-    fn = _entry("mtq_packed_linear")
-    if out is None:
-        require_gpu()
-        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
-    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
-        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
-    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
-    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    need = size(m, n, k, split) if size_first else None
+    fn = _entry(name)
+    out, ldy = _packed_out(out, m, n, out_dtype, x.device)
+    if (m == 0 and "m" in empty) or (n == 0 and "n" in empty):   # the entry refuses empty operands: they end here
+        return out
+    more = ()
+    if size is not None:
+        need = size(m, n, k, split) if need is None else need
+        more = (int(split), *(_packed_workspace(workspace, need, x.device) if need else (None, 0)))
+    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, *more,
+             _packed_stream_ptr(stream)))
     return out
+
+
+def packed_linear(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, stream="current"):
+    """mtq_packed_linear on the current stream: Y = X·Ŵᵀ + b for an (m, k) bf16 device tensor X with contiguous rows and the packed
+    (n, k) weight → (m, n) float32 or bfloat16 device tensor."""
+    return _packed_product_call("mtq_packed_linear", False, "", x, data, tables, n, bias, out_dtype, out, stream)
 
 
 def packed_linear_wide(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, stream="current"):
     """mtq_packed_linear_wide on the current stream: packed_linear's product, arguments and bits from the wide-block kernel (a
     128 x 128 block whose waves decode whole tiles), for m above the decode range.  Correct for any m; m = 0 or n = 0 gives the empty
     (m, n) tensor without a launch."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code = _packed_out_code(out_dtype)
-    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
-    if x_code != DTYPE_BF16:
-        raise MtqError("x must be a bfloat16 tensor")
-    if tiles_hw(n, k) != (tables.tiles_h, tables.tiles_w):
-        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {n}x{k} weight has {'x'.join(map(str, tiles_hw(n, k)))}")
-    ptr = _packed_stream(data, tables)
-    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
-    fn = _entry("mtq_packed_linear_wide")
-    if out is None:
-        require_gpu()
-        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
-    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
-        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
-    if m == 0 or n == 0:                             # the entry refuses empty operands, as the block entry does: they end here
-        return out
-    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
-    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
-    return out
+    return _packed_product_call("mtq_packed_linear_wide", False, "mn", x, data, tables, n, bias, out_dtype, out, stream)
 
 
 def has_packed_linear_wide() -> bool:
     """Whether this build of the library has mtq_packed_linear_wide (an optional symbol: an older build of the same version lacks it)."""
-    return getattr(lib(), "mtq_packed_linear_wide", None) is not None
+    return _has(("mtq_packed_linear_wide",))
 
 
 PACKED_MATMUL = ("mtq_pack_tiles_transposed", "mtq_unpack_tiles_transposed", "mtq_packed_matmul")
@@ -1163,7 +1202,7 @@ PACKED_MATMUL = ("mtq_pack_tiles_transposed", "mtq_unpack_tiles_transposed", "mt
 def has_packed_matmul() -> bool:
     """Whether this build of the library has the transposed pack / unpack entries and mtq_packed_matmul (optional symbols: an older build
     of the same version lacks them)."""
-    return all(getattr(lib(), name, None) is not None for name in PACKED_MATMUL)
+    return _has(PACKED_MATMUL)
 
 
 def pack_tiles_transposed(w2d, tables: PackedTables, out=None, stream="current"):
@@ -1209,7 +1248,7 @@ PACKED_BATCH_TRANSPOSED = ("mtq_pack_tiles_transposed_batched", "mtq_unpack_tile
 def has_packed_batch_transposed() -> bool:
     """Whether this build of the library has the batched transposed pack / unpack entries (optional symbols: an older build of the same
     version lacks them)."""
-    return all(getattr(lib(), name, None) is not None for name in PACKED_BATCH_TRANSPOSED)
+    return _has(PACKED_BATCH_TRANSPOSED)
 
 
 def pack_tiles_transposed_batched(w3d, maps_dev, offsets_dev, bases_dev, out, stream="current"):
@@ -1250,59 +1289,19 @@ def unpack_tiles_transposed_batched(data, maps_dev, offsets_dev, bases_dev, coun
 def packed_matmul(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, stream="current"):
     """mtq_packed_matmul on the current stream: Y = X·P̂ + b for an (m, k) bf16 device tensor X with contiguous rows and the packed
     (k, n) matrix → (m, n) float32 or bfloat16 device tensor.  m = 0 gives the empty (0, n) tensor without a launch."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code = _packed_out_code(out_dtype)
-    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
-    if x_code != DTYPE_BF16:
-        raise MtqError("x must be a bfloat16 tensor")
-    if tiles_hw(k, n) != (tables.tiles_h, tables.tiles_w):
-        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {k}x{n} matrix has {'x'.join(map(str, tiles_hw(k, n)))}")
-    ptr = _packed_stream(data, tables)
-    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
-    fn = _entry("mtq_packed_matmul")
-    if out is None:
-        require_gpu()
-        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
-    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
-        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
-    if m == 0:                                       # the entry refuses empty operands, as the block entry does: they end here
-        return out
-    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
-    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
-    return out
+    return _packed_product_call("mtq_packed_matmul", True, "m", x, data, tables, n, bias, out_dtype, out, stream)
 
 
 def packed_matmul_wide(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, stream="current"):
     """mtq_packed_matmul_wide on the current stream: packed_matmul's product, arguments and bits from the wide-block kernel (a
     128 x 128 block whose waves decode whole tiles of the (k, n) stream), for m above the decode range.  Correct for any m; m = 0 gives
     the empty (0, n) tensor without a call."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code = _packed_out_code(out_dtype)
-    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
-    if x_code != DTYPE_BF16:
-        raise MtqError("x must be a bfloat16 tensor")
-    if tiles_hw(k, n) != (tables.tiles_h, tables.tiles_w):
-        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {k}x{n} matrix has {'x'.join(map(str, tiles_hw(k, n)))}")
-    ptr = _packed_stream(data, tables)
-    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
-    fn = _entry("mtq_packed_matmul_wide")
-    if out is None:
-        require_gpu()
-        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
-    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
-        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
-    if m == 0:                                       # the entry refuses empty operands, as the block entry does: they end here
-        return out
-    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
-    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
-    return out
+    return _packed_product_call("mtq_packed_matmul_wide", True, "m", x, data, tables, n, bias, out_dtype, out, stream)
 
 
 def has_packed_matmul_wide() -> bool:
     """Whether this build of the library has mtq_packed_matmul_wide (an optional symbol: an older build of the same version lacks it)."""
-    return getattr(lib(), "mtq_packed_matmul_wide", None) is not None
+    return _has(("mtq_packed_matmul_wide",))
 
 
 PACKED_SKINNY_MAX_M = 32   # include/mtq.h MTQ_PACKED_SKINNY_MAX_M
@@ -1311,10 +1310,7 @@ PACKED_SKINNY_MAX_M = 32   # include/mtq.h MTQ_PACKED_SKINNY_MAX_M
 def packed_linear_skinny_workspace_bytes(m: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_linear_skinny_workspace_bytes (a host function: no GPU): the bytes of workspace the skinny kernel needs for
     (m, n, k, split); split 0 is the library's choice; 0 when the effective split is 1."""
-    size = int(_entry("mtq_packed_linear_skinny_workspace_bytes")(int(m), int(n), int(k), int(split)))
-    if size == ctypes.c_size_t(-1).value:
-        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
-    return size
+    return _workspace_size("mtq_packed_linear_skinny_workspace_bytes", m, n, k, split)
 
 
 def packed_linear_skinny(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, split: int = 0, workspace=None,
@@ -1322,37 +1318,8 @@ def packed_linear_skinny(x, data, tables: PackedTables, n: int, bias=None, out_d
     """mtq_packed_linear_skinny on the current stream: packed_linear for m <= 32 with a split over K (split 0: the library's choice).
     workspace: a uint8 device tensor of at least packed_linear_skinny_workspace_bytes(m, n, k, split) bytes, 16-byte aligned;
     allocated here when none is given.  The same inputs and the same split give the same bits."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code = _packed_out_code(out_dtype)
-    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
-    if x_code != DTYPE_BF16:
-        raise MtqError("x must be a bfloat16 tensor")
-    if m > PACKED_SKINNY_MAX_M:
-        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
-    if tiles_hw(n, k) != (tables.tiles_h, tables.tiles_w):
-        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {n}x{k} weight has {'x'.join(map(str, tiles_hw(n, k)))}")
-    ptr = _packed_stream(data, tables)
-    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
-    need = packed_linear_skinny_workspace_bytes(m, n, k, split)
-    fn = _entry("mtq_packed_linear_skinny")
-    if out is None:
-        require_gpu()
-        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
-    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
-        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
-    ws_ptr, ws_bytes = None, 0
-    if need:
-        if workspace is None:
-            require_gpu()
-            workspace = torch.empty((need,), dtype=torch.uint8, device=x.device)
-        ws_ptr, ws_bytes = _buffer(workspace, torch.uint8, need, "workspace"), int(workspace.numel())
-        if workspace.data_ptr() % 16:
-            raise MtqError("workspace must be 16-byte aligned")
-    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
-    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, int(split),
-             ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
-    return out
+    return _packed_product_call("mtq_packed_linear_skinny", False, "", x, data, tables, n, bias, out_dtype, out, stream,
+                                packed_linear_skinny_workspace_bytes, split, workspace, size_first=True)
 
 
 PACKED_MATMUL_SKINNY = ("mtq_packed_matmul_skinny_workspace_bytes", "mtq_packed_matmul_skinny")
@@ -1361,17 +1328,14 @@ PACKED_MATMUL_SKINNY = ("mtq_packed_matmul_skinny_workspace_bytes", "mtq_packed_
 def has_packed_matmul_skinny() -> bool:
     """Whether this build of the library has mtq_packed_matmul_skinny and its size function (optional symbols: an older build of the
     same version lacks them)."""
-    return all(getattr(lib(), name, None) is not None for name in PACKED_MATMUL_SKINNY)
+    return _has(PACKED_MATMUL_SKINNY)
 
 
 def packed_matmul_skinny_workspace_bytes(m: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_matmul_skinny_workspace_bytes (a host function: no GPU): the bytes of workspace the skinny (k, n) product needs for
     (m, n, k, split) - n outputs, k contraction; split 0 is the library's choice; 0 when the effective split is 1.  Equal to
     packed_linear_skinny_workspace_bytes for the same arguments."""
-    size = int(_entry("mtq_packed_matmul_skinny_workspace_bytes")(int(m), int(n), int(k), int(split)))
-    if size == ctypes.c_size_t(-1).value:
-        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
-    return size
+    return _workspace_size("mtq_packed_matmul_skinny_workspace_bytes", m, n, k, split)
 
 
 def packed_matmul_skinny(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, split: int = 0, workspace=None,
@@ -1380,48 +1344,14 @@ def packed_matmul_skinny(x, data, tables: PackedTables, n: int, bias=None, out_d
     workspace: a uint8 device tensor of at least packed_matmul_skinny_workspace_bytes(m, n, k, split) bytes, 16-byte aligned; allocated
     here when none is given.  Bit for bit packed_linear_skinny at the same split on the all-bf16 packing of the unpacked matrix's
     transpose.  m = 0 gives the empty (0, n) tensor without a launch."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code = _packed_out_code(out_dtype)
-    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
-    if x_code != DTYPE_BF16:
-        raise MtqError("x must be a bfloat16 tensor")
-    if m > PACKED_SKINNY_MAX_M:
-        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
-    if tiles_hw(k, n) != (tables.tiles_h, tables.tiles_w):
-        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {k}x{n} matrix has {'x'.join(map(str, tiles_hw(k, n)))}")
-    ptr = _packed_stream(data, tables)
-    bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
-    fn = _entry("mtq_packed_matmul_skinny")
-    if out is None:
-        require_gpu()
-        out = torch.empty((m, n), dtype=out_dtype, device=x.device)
-    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (m, n) or out.stride(1) != 1 or not out.is_cuda:
-        raise MtqError(f"out must be a {out_dtype} ({m}, {n}) device tensor with contiguous rows")
-    if m == 0:                                       # the entry refuses empty operands, as the block entry does: they end here
-        return out
-    need = packed_matmul_skinny_workspace_bytes(m, n, k, split)
-    ws_ptr, ws_bytes = None, 0
-    if need:
-        if workspace is None:
-            require_gpu()
-            workspace = torch.empty((need,), dtype=torch.uint8, device=x.device)
-        ws_ptr, ws_bytes = _buffer(workspace, torch.uint8, need, "workspace"), int(workspace.numel())
-        if workspace.data_ptr() % 16:
-            raise MtqError("workspace must be 16-byte aligned")
-    ldy = out.stride(0) if m > 1 else max(out.stride(0), n)
-    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, int(split),
-             ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
-    return out
+    return _packed_product_call("mtq_packed_matmul_skinny", True, "m", x, data, tables, n, bias, out_dtype, out, stream,
+                                packed_matmul_skinny_workspace_bytes, split, workspace)
 
 
 def packed_linear_skinny_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_linear_skinny_grouped_workspace_bytes (a host function: no GPU): the bytes of workspace the grouped skinny kernel needs
     for `count` (n, k) experts over total_rows rows; split 0 is the library's choice; 0 when the effective split is 1."""
-    size = int(_entry("mtq_packed_linear_skinny_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k), int(split)))
-    if size == ctypes.c_size_t(-1).value:
-        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
-    return size
+    return _workspace_size("mtq_packed_linear_skinny_grouped_workspace_bytes", total_rows, count, n, k, split)
 
 
 def packed_linear_skinny_grouped(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None, out=None,
@@ -1462,20 +1392,8 @@ def _packed_linear_grouped_call(name, workspace_bytes, x, group_rows, arena, map
         bias_ptr, ldb = bias.data_ptr(), bias.stride(0) if count > 1 else max(bias.stride(0), n)
     need = workspace_bytes(T, count, n, k) if split is None else workspace_bytes(T, count, n, k, split)
     fn = _entry(name)
-    if out is None:
-        require_gpu()
-        out = torch.zeros((T, n), dtype=out_dtype, device=x.device)
-    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (T, n) or out.stride(1) != 1 or not out.is_cuda:
-        raise MtqError(f"out must be a {out_dtype} ({T}, {n}) device tensor with contiguous rows")
-    ws_ptr, ws_bytes = None, 0
-    if need:
-        if workspace is None:
-            require_gpu()
-            workspace = torch.empty((need,), dtype=torch.uint8, device=x.device)
-        ws_ptr, ws_bytes = _buffer(workspace, torch.uint8, need, "workspace"), int(workspace.numel())
-        if workspace.data_ptr() % 16:
-            raise MtqError("workspace must be 16-byte aligned")
-    ldy = out.stride(0) if T > 1 else max(out.stride(0), n)
+    out, ldy = _packed_out(out, T, n, out_dtype, x.device, zeros=True)
+    ws_ptr, ws_bytes = _packed_workspace(workspace, need, x.device) if need else (None, 0)
     check(fn(x.data_ptr(), T, k, ldx, pg, ptr, arena.numel(), pm, po, pb, count, n, bias_ptr, ldb, out.data_ptr(), code, ldy,
              *(() if split is None else (int(split),)), ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
     return out
@@ -1484,17 +1402,13 @@ def _packed_linear_grouped_call(name, workspace_bytes, x, group_rows, arena, map
 def has_packed_linear_grouped_chunked() -> bool:
     """Whether this build of the library has mtq_packed_linear_skinny_grouped_chunked and its size function (optional symbols: an older
     build of the same version lacks them)."""
-    return all(getattr(lib(), name, None) is not None
-               for name in ("mtq_packed_linear_skinny_grouped_chunked", "mtq_packed_linear_skinny_grouped_chunked_workspace_bytes"))
+    return _has(("mtq_packed_linear_skinny_grouped_chunked", "mtq_packed_linear_skinny_grouped_chunked_workspace_bytes"))
 
 
 def packed_linear_skinny_grouped_chunked_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_linear_skinny_grouped_chunked_workspace_bytes (a host function: no GPU): packed_linear_skinny_grouped_workspace_bytes
     for the same arguments plus the chunk plan's (count + 1) * 4 bytes rounded up to 16.  Never 0."""
-    size = int(_entry("mtq_packed_linear_skinny_grouped_chunked_workspace_bytes")(int(total_rows), int(count), int(n), int(k), int(split)))
-    if size == ctypes.c_size_t(-1).value:
-        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
-    return size
+    return _workspace_size("mtq_packed_linear_skinny_grouped_chunked_workspace_bytes", total_rows, count, n, k, split)
 
 
 def packed_linear_skinny_grouped_chunked(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None,
@@ -1513,16 +1427,13 @@ WIDE_GROUPED = ("mtq_packed_linear_wide_grouped", "mtq_packed_linear_wide_groupe
 def has_packed_linear_wide_grouped() -> bool:
     """Whether this build of the library has mtq_packed_linear_wide_grouped and its size function (optional symbols: an older build of
     the same version lacks them)."""
-    return all(getattr(lib(), name, None) is not None for name in WIDE_GROUPED)
+    return _has(WIDE_GROUPED)
 
 
 def packed_linear_wide_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int) -> int:
     """mtq_packed_linear_wide_grouped_workspace_bytes (a host function: no GPU): the block plan's (count + 1) * 4 bytes rounded up to
     16, whatever (total_rows, n, k) is.  Never 0."""
-    size = int(_entry("mtq_packed_linear_wide_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k)))
-    if size == ctypes.c_size_t(-1).value:
-        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
-    return size
+    return _workspace_size("mtq_packed_linear_wide_grouped_workspace_bytes", total_rows, count, n, k)
 
 
 def packed_linear_wide_grouped(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None, out=None,
@@ -1544,30 +1455,23 @@ MATMUL_WIDE_GROUPED = ("mtq_packed_matmul_wide_grouped", "mtq_packed_matmul_wide
 def has_packed_matmul_grouped() -> bool:
     """Whether this build of the library has mtq_packed_matmul_skinny_grouped and its size function (optional symbols: an older build of
     the same version lacks them)."""
-    return all(getattr(lib(), name, None) is not None for name in MATMUL_GROUPED)
+    return _has(MATMUL_GROUPED)
 
 
 def has_packed_matmul_grouped_chunked() -> bool:
     """The same for mtq_packed_matmul_skinny_grouped_chunked and its size function."""
-    return all(getattr(lib(), name, None) is not None for name in MATMUL_GROUPED_CHUNKED)
+    return _has(MATMUL_GROUPED_CHUNKED)
 
 
 def has_packed_matmul_wide_grouped() -> bool:
     """The same for mtq_packed_matmul_wide_grouped and its size function."""
-    return all(getattr(lib(), name, None) is not None for name in MATMUL_WIDE_GROUPED)
-
-
-def _grouped_size(name, *args) -> int:
-    size = int(_entry(name)(*(int(a) for a in args)))
-    if size == ctypes.c_size_t(-1).value:
-        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
-    return size
+    return _has(MATMUL_WIDE_GROUPED)
 
 
 def packed_matmul_skinny_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_matmul_skinny_grouped_workspace_bytes (a host function: no GPU): packed_linear_skinny_grouped_workspace_bytes' answer
     for the same arguments, n the output width and k the contraction of the `count` (k, n) experts."""
-    return _grouped_size("mtq_packed_matmul_skinny_grouped_workspace_bytes", total_rows, count, n, k, split)
+    return _workspace_size("mtq_packed_matmul_skinny_grouped_workspace_bytes", total_rows, count, n, k, split)
 
 
 def packed_matmul_skinny_grouped(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None, out=None,
@@ -1584,7 +1488,7 @@ def packed_matmul_skinny_grouped(x, group_rows, arena, maps_dev, offsets_dev, ba
 def packed_matmul_skinny_grouped_chunked_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes (a host function: no GPU):
     packed_linear_skinny_grouped_chunked_workspace_bytes' answer for the same arguments.  Never 0."""
-    return _grouped_size("mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes", total_rows, count, n, k, split)
+    return _workspace_size("mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes", total_rows, count, n, k, split)
 
 
 def packed_matmul_skinny_grouped_chunked(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None,
@@ -1598,7 +1502,7 @@ def packed_matmul_skinny_grouped_chunked(x, group_rows, arena, maps_dev, offsets
 
 def packed_matmul_wide_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int) -> int:
     """mtq_packed_matmul_wide_grouped_workspace_bytes (a host function: no GPU): the block plan's bytes, a function of count.  Never 0."""
-    return _grouped_size("mtq_packed_matmul_wide_grouped_workspace_bytes", total_rows, count, n, k)
+    return _workspace_size("mtq_packed_matmul_wide_grouped_workspace_bytes", total_rows, count, n, k)
 
 
 def packed_matmul_wide_grouped(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, bias=None, out_dtype=None, out=None,
@@ -1617,24 +1521,13 @@ PACKED_GLU = ("mtq_glu_combine", "mtq_packed_glu_wide", "mtq_packed_glu_wide_gro
 def has_packed_glu() -> bool:
     """Whether this build of the library has the gated entries (mtq_glu_combine, mtq_packed_glu_wide, mtq_packed_glu_wide_grouped and
     its size function; optional symbols: an older build of the same version lacks them)."""
-    return all(getattr(lib(), name, None) is not None for name in PACKED_GLU)
+    return _has(PACKED_GLU)
 
 
 def _act_code(act) -> int:
     if act not in ACT_CODE:
         raise MtqError(f"act must be one of {tuple(ACT_CODE)}, got {act!r}")
     return ACT_CODE[act]
-
-
-def _glu_out(out, rows: int, cols: int, out_dtype, device, zeros: bool = False):
-    """`out` checked, or a new (rows, cols) tensor → (out, ldy)."""
-    torch = _torch()
-    if out is None:
-        require_gpu()
-        out = (torch.zeros if zeros else torch.empty)((rows, cols), dtype=out_dtype, device=device)
-    elif out.dtype != out_dtype or out.dim() != 2 or tuple(out.shape) != (rows, cols) or out.stride(1) != 1 or not out.is_cuda:
-        raise MtqError(f"out must be a {out_dtype} ({rows}, {cols}) device tensor with contiguous rows")
-    return out, (out.stride(0) if rows > 1 else max(out.stride(0), cols))
 
 
 def glu_combine(g, u, act="silu", out_dtype=None, out=None, stream="current"):
@@ -1651,11 +1544,40 @@ def glu_combine(g, u, act="silu", out_dtype=None, out=None, stream="current"):
         raise MtqError(f"g and u must have one shape, got {tuple(g.shape)} and {tuple(u.shape)}")
     rows, cols = (int(v) for v in g.shape)
     fn = _entry("mtq_glu_combine")
-    out, ldy = _glu_out(out, rows, cols, out_dtype, g.device)
+    out, ldy = _packed_out(out, rows, cols, out_dtype, g.device)
     if rows == 0 or cols == 0:
         return out
     ldg, ldu = (t.stride(0) if rows > 1 else max(t.stride(0), cols) for t in (g, u))
     check(fn(g.data_ptr(), ldg, u.data_ptr(), ldu, rows, cols, a, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+def _packed_glu_call(name, kn, x, gate_data, gate_tables, up_data, up_tables, n, act, bias_gate, bias_up, out_dtype, out, stream, size=None, split=0,
+                     workspace=None):
+    """The checks and the call the single-tensor gated entries share; m = 0 or n = 0 ends here with the empty `out`.  size: a skinny
+    entry's own size function, which makes the call one with m <= 32, a split and a workspace (never of 0 bytes)."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if size is not None and m > PACKED_SKINNY_MAX_M:
+        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
+    grid = tiles_hw(k, n) if kn else tiles_hw(n, k)
+    for side, tables in (("gate ", gate_tables), ("up ", up_tables)):
+        if grid != (tables.tiles_h, tables.tiles_w):
+            raise _grid_error(tables, n, k, kn, side)
+    pg, pu = _packed_stream(gate_data, gate_tables, "gate data"), _packed_stream(up_data, up_tables, "up data")
+    bg = None if bias_gate is None else _buffer(bias_gate, torch.float32, n, "bias_gate")
+    bu = None if bias_up is None else _buffer(bias_up, torch.float32, n, "bias_up")
+    fn = _entry(name)
+    out, ldy = _packed_out(out, m, n, out_dtype, x.device)
+    if m == 0 or n == 0:                             # the entry refuses empty operands: they end here
+        return out
+    more = () if size is None else (int(split), *_packed_workspace(workspace, size(m, n, k, split), x.device))
+    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
+             up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, *more, _packed_stream_ptr(stream)))
     return out
 
 
@@ -1664,39 +1586,22 @@ def packed_glu_wide(x, gate_data, gate_tables: PackedTables, up_data, up_tables:
     """mtq_packed_glu_wide on the current stream: act(X·Ŵgᵀ + bg) * (X·Ŵuᵀ + bu) for an (m, k) bf16 device tensor X and two packed
     (n, k) weights in one launch → (m, n) float32 or bfloat16: bit for bit two packed_linear calls into float32 and glu_combine.
     m = 0 or n = 0 gives the empty (m, n) tensor without a launch."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code, a = _packed_out_code(out_dtype), _act_code(act)
-    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
-    if x_code != DTYPE_BF16:
-        raise MtqError("x must be a bfloat16 tensor")
-    for name, tables in (("gate", gate_tables), ("up", up_tables)):
-        if tiles_hw(n, k) != (tables.tiles_h, tables.tiles_w):
-            raise MtqError(f"the {name} map is {tables.tiles_h}x{tables.tiles_w} tiles, a {n}x{k} weight has {'x'.join(map(str, tiles_hw(n, k)))}")
-    pg, pu = _packed_stream(gate_data, gate_tables, "gate data"), _packed_stream(up_data, up_tables, "up data")
-    bg = None if bias_gate is None else _buffer(bias_gate, torch.float32, n, "bias_gate")
-    bu = None if bias_up is None else _buffer(bias_up, torch.float32, n, "bias_up")
-    fn = _entry("mtq_packed_glu_wide")
-    out, ldy = _glu_out(out, m, n, out_dtype, x.device)
-    if m == 0 or n == 0:                             # the entry refuses empty operands, as the wide entry does: they end here
-        return out
-    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
-             up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
-    return out
+    return _packed_glu_call("mtq_packed_glu_wide", False, x, gate_data, gate_tables, up_data, up_tables, n, act, bias_gate, bias_up, out_dtype, out, stream)
 
 
 def packed_glu_wide_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int) -> int:
     """mtq_packed_glu_wide_grouped_workspace_bytes (a host function: no GPU): packed_linear_wide_grouped_workspace_bytes' answer."""
-    size = int(_entry("mtq_packed_glu_wide_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k)))
-    if size == ctypes.c_size_t(-1).value:
-        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
-    return size
+    return _workspace_size("mtq_packed_glu_wide_grouped_workspace_bytes", total_rows, count, n, k)
 
 
-def _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up):
-    """The grouped gated entries' operands checked → (count, n, T, k, ldx, group_rows pointer, the ten arena arguments, the two bias
-    pointers, ldb)."""
+def _packed_glu_grouped_call(name, workspace_bytes, x, group_rows, gate, up, count, n, act, bias_gate, bias_up, out_dtype, out, split, workspace,
+                             stream, size_first=False):
+    """The checks and the call the grouped gated entries of both orientations share (the grid of `count` (n, k) weights has as many tiles
+    as that of (k, n) matrices); `workspace_bytes` is the entry's own size function.  split None: an entry without a split parameter (a
+    wide one), whose size function takes (T, count, n, k).  size_first: the size is asked before the entry is looked up."""
     torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
     count, n = int(count), int(n)
     x_code, _count, _stride, T, k, ldx = _matrix(x, (2,))
     if x_code != DTYPE_BF16:
@@ -1705,25 +1610,34 @@ def _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up):
         raise MtqError("count and n must be positive")
     th, tw = tiles_hw(n, k)
     sides = []
-    for name, (arena, maps_dev, offsets_dev, bases_dev) in (("gate", gate), ("up", up)):
+    for which, (arena, maps_dev, offsets_dev, bases_dev) in (("gate", gate), ("up", up)):
         pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
-        sides += [_arena(arena, count, th * tw, f"the {name} arena"), arena.numel(), pm, po, pb]
+        sides += [_arena(arena, count, th * tw, f"the {which} arena"), arena.numel(), pm, po, pb]
     pg = _buffer(group_rows, torch.int32, count + 1, "group_rows")
     if group_rows.numel() != count + 1:
         raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got {group_rows.numel()}")
     ptrs, ldb = [], 0
-    for name, bias in (("bias_gate", bias_gate), ("bias_up", bias_up)):
+    for which, bias in (("bias_gate", bias_gate), ("bias_up", bias_up)):
         if bias is None:
             ptrs.append(None)
             continue
         if bias.dtype != torch.float32 or bias.dim() != 2 or tuple(bias.shape) != (count, n) or bias.stride(1) != 1 or not bias.is_cuda:
-            raise MtqError(f"{name} must be a float32 ({count}, {n}) device tensor with contiguous rows")
+            raise MtqError(f"{which} must be a float32 ({count}, {n}) device tensor with contiguous rows")
         pitch = bias.stride(0) if count > 1 else max(bias.stride(0), n)
         if ldb and pitch != ldb:
             raise MtqError("bias_gate and bias_up must have one row pitch")
         ptrs.append(bias.data_ptr())
         ldb = pitch
-    return count, n, T, k, ldx, pg, sides, ptrs, ldb
+    more = () if split is None else (int(split),)
+    need = workspace_bytes(T, count, n, k, *more) if size_first and T else None
+    fn = _entry(name)
+    out, ldy = _packed_out(out, T, n, out_dtype, x.device, zeros=True)
+    if T == 0:
+        return out
+    ws_ptr, ws_bytes = _packed_workspace(workspace, workspace_bytes(T, count, n, k, *more) if need is None else need, x.device)
+    check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, *more, ws_ptr, ws_bytes,
+             _packed_stream_ptr(stream)))
+    return out
 
 
 def packed_glu_wide_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None, out=None,
@@ -1733,24 +1647,8 @@ def packed_glu_wide_grouped(x, group_rows, gate, up, count: int, n: int, act="si
     `count` (n, k) experts each; x, group_rows, out and workspace as there; bias_gate, bias_up: None or float32 (count, n) device
     tensors of one row pitch.  Per group the bits of two packed_linear calls into float32 and glu_combine on the group's rows.  An
     `out` allocated here starts as zeros, so rows outside every group are zeros."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code, a = _packed_out_code(out_dtype), _act_code(act)
-    count, n, T, k, ldx, pg, sides, ptrs, ldb = _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up)
-    need = packed_glu_wide_grouped_workspace_bytes(T, count, n, k) if T else 0
-    fn = _entry("mtq_packed_glu_wide_grouped")
-    out, ldy = _glu_out(out, T, n, out_dtype, x.device, zeros=True)
-    if T == 0:
-        return out
-    if workspace is None:
-        require_gpu()
-        workspace = torch.empty((need,), dtype=torch.uint8, device=x.device)
-    ws_ptr, ws_bytes = _buffer(workspace, torch.uint8, need, "workspace"), int(workspace.numel())
-    if workspace.data_ptr() % 16:
-        raise MtqError("workspace must be 16-byte aligned")
-    check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, ws_ptr, ws_bytes,
-             _packed_stream_ptr(stream)))
-    return out
+    return _packed_glu_grouped_call("mtq_packed_glu_wide_grouped", packed_glu_wide_grouped_workspace_bytes, x, group_rows, gate, up, count, n, act,
+                                    bias_gate, bias_up, out_dtype, out, None, workspace, stream, size_first=True)
 
 
 PACKED_GLU_SKINNY = ("mtq_packed_glu_skinny_workspace_bytes", "mtq_packed_glu_skinny", "mtq_packed_glu_skinny_grouped_workspace_bytes",
@@ -1760,31 +1658,13 @@ PACKED_GLU_SKINNY = ("mtq_packed_glu_skinny_workspace_bytes", "mtq_packed_glu_sk
 def has_packed_glu_skinny() -> bool:
     """Whether this build of the library has the fused gated entries for decode (mtq_packed_glu_skinny, mtq_packed_glu_skinny_grouped and
     their size functions; optional symbols: an older build of the same version lacks them)."""
-    return all(getattr(lib(), name, None) is not None for name in PACKED_GLU_SKINNY)
-
-
-def _size_or_raise(size: int) -> int:
-    if size == ctypes.c_size_t(-1).value:
-        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
-    return size
-
-
-def _glu_workspace(workspace, need: int, device):
-    """`workspace` checked, or a new one of `need` bytes → (pointer, bytes)."""
-    torch = _torch()
-    if workspace is None:
-        require_gpu()
-        workspace = torch.empty((need,), dtype=torch.uint8, device=device)
-    ws_ptr = _buffer(workspace, torch.uint8, need, "workspace")
-    if workspace.data_ptr() % 16:
-        raise MtqError("workspace must be 16-byte aligned")
-    return ws_ptr, int(workspace.numel())
+    return _has(PACKED_GLU_SKINNY)
 
 
 def packed_glu_skinny_workspace_bytes(m: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_glu_skinny_workspace_bytes (a host function: no GPU): the bytes of workspace the fused decode call needs for
     (m, n, k, split); split 0 is the library's choice.  Never 0: both projections' partial sums go through it at every split."""
-    return _size_or_raise(int(_entry("mtq_packed_glu_skinny_workspace_bytes")(int(m), int(n), int(k), int(split))))
+    return _workspace_size("mtq_packed_glu_skinny_workspace_bytes", m, n, k, split)
 
 
 def packed_glu_skinny(x, gate_data, gate_tables: PackedTables, up_data, up_tables: PackedTables, n: int, act="silu", bias_gate=None,
@@ -1793,35 +1673,14 @@ def packed_glu_skinny(x, gate_data, gate_tables: PackedTables, up_data, up_table
     choice), two launches: bit for bit two packed_linear_skinny calls into float32 at that split and glu_combine.  workspace: a uint8
     device tensor of at least packed_glu_skinny_workspace_bytes(m, n, k, split) bytes, 16-byte aligned; allocated here when none is
     given.  m = 0 or n = 0 gives the empty (m, n) tensor without a launch."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code, a = _packed_out_code(out_dtype), _act_code(act)
-    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
-    if x_code != DTYPE_BF16:
-        raise MtqError("x must be a bfloat16 tensor")
-    if m > PACKED_SKINNY_MAX_M:
-        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
-    for name, tables in (("gate", gate_tables), ("up", up_tables)):
-        if tiles_hw(n, k) != (tables.tiles_h, tables.tiles_w):
-            raise MtqError(f"the {name} map is {tables.tiles_h}x{tables.tiles_w} tiles, a {n}x{k} weight has {'x'.join(map(str, tiles_hw(n, k)))}")
-    pg, pu = _packed_stream(gate_data, gate_tables, "gate data"), _packed_stream(up_data, up_tables, "up data")
-    bg = None if bias_gate is None else _buffer(bias_gate, torch.float32, n, "bias_gate")
-    bu = None if bias_up is None else _buffer(bias_up, torch.float32, n, "bias_up")
-    fn = _entry("mtq_packed_glu_skinny")
-    out, ldy = _glu_out(out, m, n, out_dtype, x.device)
-    if m == 0 or n == 0:                             # the entry refuses empty operands, as the skinny entry does: they end here
-        return out
-    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_skinny_workspace_bytes(m, n, k, split), x.device)
-    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
-             up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
-             _packed_stream_ptr(stream)))
-    return out
+    return _packed_glu_call("mtq_packed_glu_skinny", False, x, gate_data, gate_tables, up_data, up_tables, n, act, bias_gate, bias_up, out_dtype, out,
+                            stream, packed_glu_skinny_workspace_bytes, split, workspace)
 
 
 def packed_glu_skinny_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_glu_skinny_grouped_workspace_bytes (a host function: no GPU): packed_glu_skinny_workspace_bytes for the grouped call,
     total_rows in place of m and the grouped entry's own split rule at split 0."""
-    return _size_or_raise(int(_entry("mtq_packed_glu_skinny_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k), int(split))))
+    return _workspace_size("mtq_packed_glu_skinny_grouped_workspace_bytes", total_rows, count, n, k, split)
 
 
 def packed_glu_skinny_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None, out=None,
@@ -1829,18 +1688,8 @@ def packed_glu_skinny_grouped(x, group_rows, gate, up, count: int, n: int, act="
     """mtq_packed_glu_skinny_grouped on the current stream: packed_glu_wide_grouped's operands and product from the skinny family's
     split over K, for decode-sized groups: per group the bits of two packed_linear_skinny_grouped calls into float32 at that split
     and glu_combine.  An `out` allocated here starts as zeros, so rows outside every group are zeros."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code, a = _packed_out_code(out_dtype), _act_code(act)
-    count, n, T, k, ldx, pg, sides, ptrs, ldb = _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up)
-    fn = _entry("mtq_packed_glu_skinny_grouped")
-    out, ldy = _glu_out(out, T, n, out_dtype, x.device, zeros=True)
-    if T == 0:
-        return out
-    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_skinny_grouped_workspace_bytes(T, count, n, k, split), x.device)
-    check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
-             _packed_stream_ptr(stream)))
-    return out
+    return _packed_glu_grouped_call("mtq_packed_glu_skinny_grouped", packed_glu_skinny_grouped_workspace_bytes, x, group_rows, gate, up, count, n, act,
+                                    bias_gate, bias_up, out_dtype, out, split, workspace, stream)
 
 
 PACKED_GLU_MATMUL = ("mtq_packed_glu_matmul_wide", "mtq_packed_glu_matmul_wide_grouped", "mtq_packed_glu_matmul_wide_grouped_workspace_bytes")
@@ -1851,31 +1700,13 @@ PACKED_GLU_MATMUL_SKINNY = ("mtq_packed_glu_matmul_skinny_workspace_bytes", "mtq
 def has_packed_glu_matmul() -> bool:
     """Whether this build of the library has the gated entries for (k, n) weights (mtq_packed_glu_matmul_wide,
     mtq_packed_glu_matmul_wide_grouped and its size function; optional symbols: an older build of the same version lacks them)."""
-    return all(getattr(lib(), name, None) is not None for name in PACKED_GLU_MATMUL)
+    return _has(PACKED_GLU_MATMUL)
 
 
 def has_packed_glu_matmul_skinny() -> bool:
     """Whether this build of the library has the fused gated entries for (k, n) weights at decode (mtq_packed_glu_matmul_skinny,
     mtq_packed_glu_matmul_skinny_grouped and their size functions; optional symbols)."""
-    return all(getattr(lib(), name, None) is not None for name in PACKED_GLU_MATMUL_SKINNY)
-
-
-def _glu_matmul_args(x, gate_data, gate_tables, up_data, up_tables, n, bias_gate, bias_up, skinny: bool):
-    """The single-tensor gated (k, n) entries' operands checked → (m, k, ldx, gate pointer, up pointer, bias_gate pointer, bias_up
-    pointer)."""
-    torch = _torch()
-    x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
-    if x_code != DTYPE_BF16:
-        raise MtqError("x must be a bfloat16 tensor")
-    if skinny and m > PACKED_SKINNY_MAX_M:
-        raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
-    for name, tables in (("gate", gate_tables), ("up", up_tables)):
-        if tiles_hw(k, n) != (tables.tiles_h, tables.tiles_w):
-            raise MtqError(f"the {name} map is {tables.tiles_h}x{tables.tiles_w} tiles, a {k}x{n} matrix has {'x'.join(map(str, tiles_hw(k, n)))}")
-    pg, pu = _packed_stream(gate_data, gate_tables, "gate data"), _packed_stream(up_data, up_tables, "up data")
-    bg = None if bias_gate is None else _buffer(bias_gate, torch.float32, n, "bias_gate")
-    bu = None if bias_up is None else _buffer(bias_up, torch.float32, n, "bias_up")
-    return m, k, ldx, pg, pu, bg, bu
+    return _has(PACKED_GLU_MATMUL_SKINNY)
 
 
 def packed_glu_matmul_wide(x, gate_data, gate_tables: PackedTables, up_data, up_tables: PackedTables, n: int, act="silu", bias_gate=None,
@@ -1883,22 +1714,12 @@ def packed_glu_matmul_wide(x, gate_data, gate_tables: PackedTables, up_data, up_
     """mtq_packed_glu_matmul_wide on the current stream: act(X·P̂g + bg) * (X·P̂u + bu) for an (m, k) bf16 device tensor X and two packed
     (k, n) matrices in one launch → (m, n) float32 or bfloat16: bit for bit two packed_matmul calls into float32 and glu_combine.
     m = 0 or n = 0 gives the empty (m, n) tensor without a launch."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code, a = _packed_out_code(out_dtype), _act_code(act)
-    m, k, ldx, pg, pu, bg, bu = _glu_matmul_args(x, gate_data, gate_tables, up_data, up_tables, n, bias_gate, bias_up, False)
-    fn = _entry("mtq_packed_glu_matmul_wide")
-    out, ldy = _glu_out(out, m, n, out_dtype, x.device)
-    if m == 0 or n == 0:                             # the entry refuses empty operands, as the wide entry does: they end here
-        return out
-    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
-             up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
-    return out
+    return _packed_glu_call("mtq_packed_glu_matmul_wide", True, x, gate_data, gate_tables, up_data, up_tables, n, act, bias_gate, bias_up, out_dtype, out, stream)
 
 
 def packed_glu_matmul_wide_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int) -> int:
     """mtq_packed_glu_matmul_wide_grouped_workspace_bytes (a host function: no GPU): packed_glu_wide_grouped_workspace_bytes' answer."""
-    return _size_or_raise(int(_entry("mtq_packed_glu_matmul_wide_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k))))
+    return _workspace_size("mtq_packed_glu_matmul_wide_grouped_workspace_bytes", total_rows, count, n, k)
 
 
 def packed_glu_matmul_wide_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None,
@@ -1906,23 +1727,13 @@ def packed_glu_matmul_wide_grouped(x, group_rows, gate, up, count: int, n: int, 
     """mtq_packed_glu_matmul_wide_grouped on the current stream: packed_glu_matmul_wide's product for the `count` (k, n) experts of two
     arenas, each over its own rows of X, in one launch.  Operands as packed_glu_wide_grouped takes them.  Per group the bits of two
     packed_matmul calls into float32 and glu_combine on the group's rows.  An `out` allocated here starts as zeros."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code, a = _packed_out_code(out_dtype), _act_code(act)
-    count, n, T, k, ldx, pg, sides, ptrs, ldb = _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up)
-    fn = _entry("mtq_packed_glu_matmul_wide_grouped")
-    out, ldy = _glu_out(out, T, n, out_dtype, x.device, zeros=True)
-    if T == 0:
-        return out
-    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_matmul_wide_grouped_workspace_bytes(T, count, n, k), x.device)
-    check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, ws_ptr, ws_bytes,
-             _packed_stream_ptr(stream)))
-    return out
+    return _packed_glu_grouped_call("mtq_packed_glu_matmul_wide_grouped", packed_glu_matmul_wide_grouped_workspace_bytes, x, group_rows, gate, up, count, n, act,
+                                    bias_gate, bias_up, out_dtype, out, None, workspace, stream)
 
 
 def packed_glu_matmul_skinny_workspace_bytes(m: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_glu_matmul_skinny_workspace_bytes (a host function: no GPU): packed_glu_skinny_workspace_bytes' answer."""
-    return _size_or_raise(int(_entry("mtq_packed_glu_matmul_skinny_workspace_bytes")(int(m), int(n), int(k), int(split))))
+    return _workspace_size("mtq_packed_glu_matmul_skinny_workspace_bytes", m, n, k, split)
 
 
 def packed_glu_matmul_skinny(x, gate_data, gate_tables: PackedTables, up_data, up_tables: PackedTables, n: int, act="silu", bias_gate=None,
@@ -1930,25 +1741,13 @@ def packed_glu_matmul_skinny(x, gate_data, gate_tables: PackedTables, up_data, u
     """mtq_packed_glu_matmul_skinny on the current stream: packed_glu_matmul_wide's product for m <= 32 with a split over K (split 0: the
     library's choice), two launches: bit for bit two packed_matmul_skinny calls into float32 at that split and glu_combine.  workspace
     as packed_glu_skinny takes it.  m = 0 or n = 0 gives the empty (m, n) tensor without a launch."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code, a = _packed_out_code(out_dtype), _act_code(act)
-    m, k, ldx, pg, pu, bg, bu = _glu_matmul_args(x, gate_data, gate_tables, up_data, up_tables, n, bias_gate, bias_up, True)
-    fn = _entry("mtq_packed_glu_matmul_skinny")
-    out, ldy = _glu_out(out, m, n, out_dtype, x.device)
-    if m == 0 or n == 0:                             # the entry refuses empty operands, as the skinny entry does: they end here
-        return out
-    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_matmul_skinny_workspace_bytes(m, n, k, split), x.device)
-    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
-             up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
-             _packed_stream_ptr(stream)))
-    return out
+    return _packed_glu_call("mtq_packed_glu_matmul_skinny", True, x, gate_data, gate_tables, up_data, up_tables, n, act, bias_gate, bias_up, out_dtype,
+                            out, stream, packed_glu_matmul_skinny_workspace_bytes, split, workspace)
 
 
 def packed_glu_matmul_skinny_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:
     """mtq_packed_glu_matmul_skinny_grouped_workspace_bytes (a host function: no GPU): packed_glu_skinny_grouped_workspace_bytes' answer."""
-    return _size_or_raise(int(_entry("mtq_packed_glu_matmul_skinny_grouped_workspace_bytes")(int(total_rows), int(count), int(n), int(k),
-                                                                                             int(split))))
+    return _workspace_size("mtq_packed_glu_matmul_skinny_grouped_workspace_bytes", total_rows, count, n, k, split)
 
 
 def packed_glu_matmul_skinny_grouped(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None,
@@ -1956,18 +1755,8 @@ def packed_glu_matmul_skinny_grouped(x, group_rows, gate, up, count: int, n: int
     """mtq_packed_glu_matmul_skinny_grouped on the current stream: packed_glu_matmul_wide_grouped's operands and product from the skinny
     family's split over K, for decode-sized groups: per group the bits of two packed_matmul_skinny_grouped calls into float32 at that
     split and glu_combine.  An `out` allocated here starts as zeros, so rows outside every group are zeros."""
-    torch = _torch()
-    out_dtype = out_dtype or torch.float32
-    code, a = _packed_out_code(out_dtype), _act_code(act)
-    count, n, T, k, ldx, pg, sides, ptrs, ldb = _glu_grouped_args(x, group_rows, gate, up, count, n, bias_gate, bias_up)
-    fn = _entry("mtq_packed_glu_matmul_skinny_grouped")
-    out, ldy = _glu_out(out, T, n, out_dtype, x.device, zeros=True)
-    if T == 0:
-        return out
-    ws_ptr, ws_bytes = _glu_workspace(workspace, packed_glu_matmul_skinny_grouped_workspace_bytes(T, count, n, k, split), x.device)
-    check(fn(x.data_ptr(), T, k, ldx, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
-             _packed_stream_ptr(stream)))
-    return out
+    return _packed_glu_grouped_call("mtq_packed_glu_matmul_skinny_grouped", packed_glu_matmul_skinny_grouped_workspace_bytes, x, group_rows, gate, up, count, n, act,
+                                    bias_gate, bias_up, out_dtype, out, split, workspace, stream)
 
 
 MOE = ("mtq_moe_plan_workspace_bytes", "mtq_moe_plan", "mtq_moe_dispatch", "mtq_moe_combine")
@@ -1978,12 +1767,12 @@ IDS_I32, IDS_I64 = 0, 1                                   # include/mtq.h MTQ_ID
 def has_moe() -> bool:
     """Whether this build of the library has the MoE routing entries (mtq_moe_plan and its size function, mtq_moe_dispatch,
     mtq_moe_combine; optional symbols: an older build of the same version lacks them)."""
-    return all(getattr(lib(), name, None) is not None for name in MOE)
+    return _has(MOE)
 
 
 def moe_plan_workspace_bytes(tokens: int, topk: int, count: int) -> int:
     """mtq_moe_plan_workspace_bytes (a host function: no GPU): ceil(tokens * topk / MOE_RUN) * count * 4 rounded up to 16.  Never 0."""
-    return _size_or_raise(int(_entry("mtq_moe_plan_workspace_bytes")(int(tokens), int(topk), int(count))))
+    return _workspace_size("mtq_moe_plan_workspace_bytes", tokens, topk, count)
 
 
 def _rows_ld(t, rows: int, cols: int) -> int:
@@ -2009,7 +1798,7 @@ def moe_plan(topk_ids, count: int, workspace=None, stream="current"):
         raise MtqError("expected a device tensor (the hip backend has no CPU fallback)")
     need = moe_plan_workspace_bytes(T, K, count)      # the limits on tokens, topk and count are the library's
     fn = _entry("mtq_moe_plan")
-    ws_ptr, ws_bytes = _glu_workspace(workspace, need, topk_ids.device)
+    ws_ptr, ws_bytes = _packed_workspace(workspace, need, topk_ids.device)
     require_gpu()
     group_rows = torch.empty((int(count) + 1,), dtype=torch.int32, device=topk_ids.device)
     row_of, src = (torch.empty((T * K,), dtype=torch.int32, device=topk_ids.device) for _ in range(2))
@@ -2034,7 +1823,7 @@ def moe_dispatch(x, src, topk: int, out=None, stream="current"):
     if src.numel() != S:
         raise MtqError(f"src must have tokens * topk = {S} entries, got {src.numel()}")
     fn = _entry("mtq_moe_dispatch")
-    out, ldxs = _glu_out(out, S, k, torch.bfloat16, x.device)
+    out, ldxs = _packed_out(out, S, k, torch.bfloat16, x.device)
     check(fn(x.data_ptr(), T, k, ldx, ps, topk, out.data_ptr(), ldxs, _packed_stream_ptr(stream)))
     return out
 
@@ -2066,7 +1855,7 @@ def moe_combine(ys, row_of, weights, base=None, out_dtype=None, out=None, stream
             raise MtqError(f"base must be ({T}, {n}), got {tuple(base.shape)}")
         base_ptr = base.data_ptr()
     fn = _entry("mtq_moe_combine")
-    out, ldy = _glu_out(out, T, n, out_dtype, ys.device)
+    out, ldy = _packed_out(out, T, n, out_dtype, ys.device)
     check(fn(ys.data_ptr(), ys_code, ldys, pr, weights.data_ptr(), _rows_ld(weights, T, K), base_ptr, base_code, ldbase, T, K, n,
              out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
     return out

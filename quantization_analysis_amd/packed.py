@@ -55,11 +55,13 @@ entry for such a map, pack_batch_transposed for a batch of them.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from types import MappingProxyType
+from typing import Mapping, Optional
 
 import numpy as np
 
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS, flatten_2d, unflatten_2d
+from . import hip_backend as hb
 from .hip_backend import PACKED_TILE_BYTES, MtqError
 
 FORMAT_VERSION = 1
@@ -162,8 +164,6 @@ class PackedTensor:
         return {f: int(c[i]) for i, f in enumerate(MIXED_TILE_FORMATS)}
 
     def tables(self):
-        from . import hip_backend as hb
-
         if self._tables is None:
             self._tables = hb.PackedTables.on_device(self.map, self.offsets, self.data.device if self.on_device else None)
         return self._tables
@@ -307,11 +307,8 @@ def pack(x, amap, backend: str = "emulation", layout: str = "rows") -> PackedTen
     """x (NumPy array or torch tensor of any rank; bf16 and float32 storage are packed as they are, anything else as float32) under the
     int8 tile map `amap` of its 2-D flatten → PackedTensor.  hip: the stream stays on the device."""
     _check_layout(layout)
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    _check_backend(backend)
     if backend == "hip":
-        from . import hip_backend as hb
-
         hb.require_gpu()
         shape = tuple(x.shape) if hasattr(x, "shape") else ()
         x2d, info = hb.to_device_2d(x)
@@ -348,18 +345,14 @@ def unpack(pt: PackedTensor, backend: str = "emulation", dtype: str = "float32")
     """The tensor the map's quantisation writes, in the original shape.  dtype "float32": bit for bit the reconstruction (K3);
     "bfloat16": the same values as bf16, which is exact.  emulation → NumPy float32, or a torch CPU bfloat16 tensor; hip → device tensor."""
     _check_layout(pt.layout)
-    if dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"dtype must be 'float32' or 'bfloat16', got {dtype!r}")
+    _check_out_dtype(dtype, "dtype")
     if backend == "hip":
         import torch
 
-        from . import hip_backend as hb
-
         hb.require_gpu()
-        y = hb.unpack_tiles(_device_data(pt), pt.tables(), pt.rows, pt.cols, torch.float32 if dtype == "float32" else torch.bfloat16)
+        y = hb.unpack_tiles(_device_data(pt), pt.tables(), pt.rows, pt.cols, _torch_dtype(dtype))
         return hb.unflatten(y, pt.shape_info)
-    if backend != "emulation":
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    _check_backend(backend)
     bits = decode(_host_data(pt), pt.map, pt.offsets, pt.rows, pt.cols)
     if dtype == "float32":
         y = unflatten_2d(bits.view(np.float32), pt.shape_info)
@@ -369,6 +362,267 @@ def unpack(pt: PackedTensor, backend: str = "emulation", dtype: str = "float32")
     half = torch.from_numpy((bits >> np.uint32(16)).astype(np.uint16).view(np.int16)).view(torch.bfloat16)
     kind, v = pt.shape_info
     return half.reshape(()) if kind == "scalar" else (half.reshape(-1)[:v] if kind == "vector" else half.reshape(tuple(v)))
+
+
+# ----------------------------------------------------------------------------- the two orientations of a packed operand
+
+@dataclass(frozen=True)
+class _Orientation:
+    """What differs between the products with a packed (n, k) weight (linear, glu, PackedLinear, ...) and those with a packed (k, n)
+    matrix (matmul, glu_matmul, PackedMatmul, ...).  Every shared body below takes one of the two instances, _NK or _KN, first.  Apart
+    from the reading of (n, k) and the emulation's product it holds NAMES - of hip_backend's bindings, predicates and symbol tuples,
+    and of this module's constants, public functions and _need_* checks - which a body looks up when it runs (getattr(hb, name),
+    globals()[name]): replacing one of them by module attribute takes effect at the next call, as it always did.  A rule that holds
+    for one orientation only is a field here, not a test of the family inside a body."""
+
+    kn: bool                        # the operand is a (k, n) matrix: (n, k) = (cols, rows), the product x @ w; else (rows, cols), x @ w.T
+    noun: str                       # what messages call the operand
+    rank2: str                      # the refusal of an operand that is not 2-D; {what} is the caller's name
+    pair_rank2: str                 # the same for one of a gate / up pair
+    down_shape: str                 # a down projection's shape in messages
+    kernel_before_rank: bool        # a bad `kernel` is reported before a bad rank
+    # this module's constants
+    kernels: str
+    auto_skinny_max_m: str
+    auto_wide_min_m: str
+    skinny_gates_may_be_none: bool  # None in a *_SKINNY_MAX_M constant means never; else it is compared as it is
+    grouped_kernels: str
+    grouped_auto_kernel: str
+    glu_auto_skinny_max_m: str
+    glu_auto_fused_min_m: str
+    mlp_decode_kernels: str
+    # this module's public functions
+    product: str
+    grouped: str
+    grouped_wide: str
+    glu: str
+    glu_skinny: str
+    glu_grouped: str
+    glu_grouped_skinny: str
+    # hip_backend's bindings and predicates
+    hb_block: str
+    hb_wide: str
+    hb_skinny: str
+    hb_skinny_size: str
+    has_auto_skinny: Optional[str]  # what "auto" asks before it takes the skinny binding; None: nothing
+    has_auto_wide: str              # and before it takes the wide one
+    hb_grouped: Mapping             # resolved grouped kernel → (binding, size function, predicate or None, who needs it, symbols, hint)
+    hb_glu_fused: str
+    hb_glu_skinny: str
+    hb_glu_grouped_fused: str
+    hb_glu_grouped_fused_size: str
+    hb_glu_grouped_skinny: str
+    hb_glu_grouped_skinny_size: str
+    # the _need_* checks (hb, what) a hip call makes, by role; () where a call asks for no optional symbol
+    need_product: tuple
+    need_skinny: tuple
+    need_wide: tuple
+    need_glu: tuple
+    need_glu_auto_skinny: tuple
+    need_glu_skinny: tuple
+    need_glu_grouped: tuple
+    # the module classes
+    module_size_every_m: bool       # the dense module's workspace is the maximum over m = 1 .. 32 and needs no predicate; else it is
+    #                                 sized at m = 32 alone, when has_auto_skinny holds
+    module_needs: tuple             # what the dense module's constructor asks for on hip
+    experts_keep_size: bool         # the experts module keeps the size function it found in its constructor
+    experts_wide_lacks: Optional[tuple]   # (who, hint) of its refusal of wide_min_rows on a library without the wide kernel; None: hb_grouped's
+    experts_mlp_wide_last: bool     # the experts MLP looks for the wide grouped kernel after the gated ones, and words the refusal itself
+
+    def n_k(self, t):
+        """(n, k) of a PackedTensor or PackedBatch."""
+        return (t.cols, t.rows) if self.kn else (t.rows, t.cols)
+
+    def times(self, x64, w64):
+        """The emulation's product with the decoded (rows, cols) operand."""
+        return x64 @ w64 if self.kn else x64 @ w64.T
+
+
+_LACKS = "which this build of libmtq_hip.so lacks: rebuild it from this tree"
+
+_NK = _Orientation(
+    kn=False, noun="weight", rank2="{what} needs a 2-D (n, k) weight, the packed tensor is {shape}",
+    pair_rank2="glu needs 2-D (n, k) weights, the packed {name} tensor is {shape}", down_shape="(k_out, {n})", kernel_before_rank=True,
+    kernels="KERNELS", auto_skinny_max_m="AUTO_SKINNY_MAX_M", auto_wide_min_m="AUTO_WIDE_MIN_M", skinny_gates_may_be_none=False,
+    grouped_kernels="GROUPED_KERNELS", grouped_auto_kernel="GROUPED_AUTO_KERNEL", glu_auto_skinny_max_m="AUTO_SKINNY_MAX_M",
+    glu_auto_fused_min_m="AUTO_GLU_FUSED_MIN_M", mlp_decode_kernels="MLP_DECODE_KERNELS",
+    product="linear", grouped="linear_grouped", grouped_wide="linear_grouped_wide", glu="glu", glu_skinny="glu_skinny",
+    glu_grouped="glu_grouped", glu_grouped_skinny="glu_grouped_skinny",
+    hb_block="packed_linear", hb_wide="packed_linear_wide", hb_skinny="packed_linear_skinny", hb_skinny_size="packed_linear_skinny_workspace_bytes",
+    has_auto_skinny=None, has_auto_wide="has_packed_linear_wide",
+    hb_grouped=MappingProxyType({
+        # "walk" asks for nothing: its binding is looked up by name, as before there was a choice
+        "walk": ("packed_linear_skinny_grouped", "packed_linear_skinny_grouped_workspace_bytes", None, None, None, None),
+        "chunks": ("packed_linear_skinny_grouped_chunked", "packed_linear_skinny_grouped_chunked_workspace_bytes", "has_packed_linear_grouped_chunked",
+                   'kernel="chunks"', "mtq_packed_linear_skinny_grouped_chunked", ', or use kernel="walk"'),
+        "wide": ("packed_linear_wide_grouped", "packed_linear_wide_grouped_workspace_bytes", "has_packed_linear_wide_grouped",
+                 "linear_grouped_wide", "mtq_packed_linear_wide_grouped", ", or use linear_grouped")}),
+    hb_glu_fused="packed_glu_wide", hb_glu_skinny="packed_glu_skinny", hb_glu_grouped_fused="packed_glu_wide_grouped",
+    hb_glu_grouped_fused_size="packed_glu_wide_grouped_workspace_bytes", hb_glu_grouped_skinny="packed_glu_skinny_grouped",
+    hb_glu_grouped_skinny_size="packed_glu_skinny_grouped_workspace_bytes",
+    need_product=(), need_skinny=(), need_wide=(), need_glu=("_need_glu",), need_glu_auto_skinny=(), need_glu_skinny=("_need_glu_skinny",),
+    need_glu_grouped=("_need_glu",),
+    module_size_every_m=True, module_needs=(), experts_keep_size=False, experts_wide_lacks=("wide_min_rows", ", or leave wide_min_rows None"),
+    experts_mlp_wide_last=True)
+
+_KN = _Orientation(
+    kn=True, noun="matrix", rank2="{what} needs a 2-D packed (k, n) matrix, the packed tensor is {shape}",
+    pair_rank2="{what} needs a 2-D packed (k, n) matrix, the packed tensor is {shape}", down_shape="({n}, k_out)", kernel_before_rank=False,
+    kernels="MATMUL_KERNELS", auto_skinny_max_m="AUTO_MATMUL_SKINNY_MAX_M", auto_wide_min_m="AUTO_MATMUL_WIDE_MIN_M", skinny_gates_may_be_none=True,
+    grouped_kernels="MATMUL_GROUPED_KERNELS", grouped_auto_kernel="MATMUL_GROUPED_AUTO_KERNEL",
+    glu_auto_skinny_max_m="AUTO_GLU_MATMUL_SKINNY_MAX_M", glu_auto_fused_min_m="AUTO_GLU_MATMUL_FUSED_MIN_M",
+    mlp_decode_kernels="MATMUL_MLP_DECODE_KERNELS",
+    product="matmul", grouped="matmul_grouped", grouped_wide="matmul_grouped_wide", glu="glu_matmul", glu_skinny="glu_matmul_skinny",
+    glu_grouped="glu_matmul_grouped", glu_grouped_skinny="glu_matmul_grouped_skinny",
+    hb_block="packed_matmul", hb_wide="packed_matmul_wide", hb_skinny="packed_matmul_skinny", hb_skinny_size="packed_matmul_skinny_workspace_bytes",
+    has_auto_skinny="has_packed_matmul_skinny", has_auto_wide="has_packed_matmul_wide",
+    hb_grouped=MappingProxyType({   # every kernel is asked for, and the refusal names hip_backend's tuple of its symbols
+        "walk": ("packed_matmul_skinny_grouped", "packed_matmul_skinny_grouped_workspace_bytes", "has_packed_matmul_grouped",
+                 'matmul_grouped(kernel="walk")', "MATMUL_GROUPED", ""),
+        "chunks": ("packed_matmul_skinny_grouped_chunked", "packed_matmul_skinny_grouped_chunked_workspace_bytes", "has_packed_matmul_grouped_chunked",
+                   'matmul_grouped(kernel="chunks")', "MATMUL_GROUPED_CHUNKED", ""),
+        "wide": ("packed_matmul_wide_grouped", "packed_matmul_wide_grouped_workspace_bytes", "has_packed_matmul_wide_grouped",
+                 "matmul_grouped_wide", "MATMUL_WIDE_GROUPED", "")}),
+    hb_glu_fused="packed_glu_matmul_wide", hb_glu_skinny="packed_glu_matmul_skinny", hb_glu_grouped_fused="packed_glu_matmul_wide_grouped",
+    hb_glu_grouped_fused_size="packed_glu_matmul_wide_grouped_workspace_bytes", hb_glu_grouped_skinny="packed_glu_matmul_skinny_grouped",
+    hb_glu_grouped_skinny_size="packed_glu_matmul_skinny_grouped_workspace_bytes",
+    need_product=("_need_matmul",), need_skinny=("_need_matmul_skinny",), need_wide=("_need_matmul_wide",),
+    need_glu=("_need_matmul", "_need_glu_matmul"), need_glu_auto_skinny=("_need_matmul_skinny",), need_glu_skinny=("_need_glu_matmul_skinny",),
+    need_glu_grouped=("_need_glu_matmul",),
+    module_size_every_m=False, module_needs=("_need_matmul",), experts_keep_size=True, experts_wide_lacks=None, experts_mlp_wide_last=False)
+
+
+def _needs(names, hb, what: str) -> None:
+    """The _need_* checks `names` of this module, in order: the first optional symbols the library lacks raise, named, for `what`."""
+    for name in names:
+        globals()[name](hb, what)
+
+
+def _check_kernel(kernel, kernels) -> None:
+    if kernel not in kernels:
+        raise MtqError(f"kernel must be one of {kernels}, got {kernel!r}")
+
+
+def _check_backend(backend) -> None:
+    if backend not in BACKENDS:
+        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+
+
+def _check_out_dtype(out_dtype, name: str = "out_dtype") -> None:
+    if out_dtype not in ("float32", "bfloat16"):
+        raise MtqError(f"{name} must be 'float32' or 'bfloat16', got {out_dtype!r}")
+
+
+def _torch_dtype(out_dtype: str):
+    import torch
+
+    return torch.float32 if out_dtype == "float32" else torch.bfloat16
+
+
+def _check_rank2(o: _Orientation, pt: PackedTensor, what: str) -> None:
+    _check_layout(pt.layout)
+    if len(pt.shape) != 2:
+        raise MtqError(o.rank2.format(what=what, shape=pt.shape))
+
+
+def _check_pair(o: _Orientation, gate: PackedTensor, up: PackedTensor, what: str) -> None:
+    for name, pt in (("gate", gate), ("up", up)):
+        _check_layout(pt.layout)
+        if len(pt.shape) != 2:
+            raise MtqError(o.pair_rank2.format(what=what, name=name, shape=pt.shape))
+    if (gate.rows, gate.cols) != (up.rows, up.cols):
+        raise MtqError(f"gate and up must have one shape, got {gate.rows}x{gate.cols} and {up.rows}x{up.cols}")
+
+
+def _host_f32(x) -> np.ndarray:
+    return x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
+
+
+def _host_f64(v, shape=None, name: str = ""):
+    """A bias on the host in float64, or None; held to `shape` when one is given."""
+    if v is None:
+        return None
+    b = v.detach().to("cpu").double().numpy() if _is_torch(v) else np.asarray(v, dtype=np.float64)
+    if shape is not None and b.shape != shape:
+        raise MtqError(f"{name} must be {shape}, got {b.shape}")
+    return b
+
+
+def _round_out(h64: np.ndarray, out_dtype: str):
+    """float64 → float32 once, and from there to bf16: the emulation's one rounding."""
+    with np.errstate(over="ignore"):
+        y32 = h64.astype(np.float32)
+    if out_dtype == "float32":
+        return y32
+    import torch
+
+    return torch.from_numpy(y32).to(torch.bfloat16)
+
+
+def _at_most(o: _Orientation, name: str, m: int) -> bool:
+    """m <= the *_SKINNY_MAX_M constant `name` of this module."""
+    gate = globals()[name]
+    return (gate is not None or not o.skinny_gates_may_be_none) and m <= gate
+
+
+def _takes_skinny(o: _Orientation, hb, what: str, kernel: str, m: int) -> bool:
+    """Whether `kernel` means the skinny binding at this m: "skinny" always (what it needs is asked for, and no other kernel stands in),
+    "auto" up to the orientation's constant, on a library that has what the orientation asks for."""
+    if kernel == "skinny":
+        if m > SKINNY_MAX_M:
+            raise MtqError(f'kernel="skinny" takes m <= {SKINNY_MAX_M}, got m = {m}')
+        _needs(o.need_skinny, hb, f'{what}(kernel="skinny")')
+        return True
+    return kernel == "auto" and _at_most(o, o.auto_skinny_max_m, m) and (o.has_auto_skinny is None or getattr(hb, o.has_auto_skinny)())
+
+
+def _product(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dtype, backend, kernel, split, workspace):
+    """linear and matmul."""
+    _check_layout(pt.layout)
+    if o.kernel_before_rank:
+        _check_kernel(kernel, globals()[o.kernels])
+    if len(pt.shape) != 2:
+        raise MtqError(o.rank2.format(what=what, shape=pt.shape))
+    if not o.kernel_before_rank:
+        _check_kernel(kernel, globals()[o.kernels])
+    backend = backend or ("hip" if pt.on_device else "emulation")
+    _check_out_dtype(out_dtype)
+    n, k = o.n_k(pt)
+    if backend == "hip":
+        if x.dim() != 2 or x.shape[1] != k:
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        _needs(o.need_product, hb, what)
+        dtype = _torch_dtype(out_dtype)
+        m = int(x.shape[0])
+        if _takes_skinny(o, hb, what, kernel, m):
+            return getattr(hb, o.hb_skinny)(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype, split=split, workspace=workspace)
+        wide_min_m = globals()[o.auto_wide_min_m]
+        if kernel == "auto" and wide_min_m is not None and m >= wide_min_m and getattr(hb, o.has_auto_wide)():
+            return getattr(hb, o.hb_wide)(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
+        return getattr(hb, o.hb_block)(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
+    _check_backend(backend)
+    xf = _host_f32(x)
+    if xf.ndim != 2 or xf.shape[1] != k:
+        raise MtqError(f"x must be (m, {k}), got {xf.shape}")
+    w = decode(_host_data(pt), pt.map, pt.offsets, pt.rows, pt.cols).view(np.float32)
+    y = o.times(xf.astype(np.float64), w.astype(np.float64))
+    if bias is not None:
+        y = y + _host_f64(bias)[None, :]
+    return _round_out(y, out_dtype)
+
+
+def _product_wide(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dtype, backend):
+    """linear_wide and matmul_wide."""
+    _check_rank2(o, pt, what)
+    backend = backend or ("hip" if pt.on_device else "emulation")
+    _check_out_dtype(out_dtype)
+    if backend != "hip":
+        return globals()[o.product](x, pt, bias=bias, out_dtype=out_dtype, backend=backend)
+    n, k = o.n_k(pt)
+    if x.dim() != 2 or x.shape[1] != k:
+        raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+    _needs(o.need_wide, hb, what)
+    return getattr(hb, o.hb_wide)(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=_torch_dtype(out_dtype))
 
 
 def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block", split: int = 0,
@@ -382,45 +636,7 @@ def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     m <= AUTO_SKINNY_MAX_M, block above; from m = AUTO_WIDE_MIN_M on, when that is not None and the library has it, the wide-block
     kernel of linear_wide, whose bits are the block kernel's).  The skinny and the block kernel sum in different orders: each is
     bit-stable, they may differ in the last bits.  The emulation computes the same float64 product under all three names."""
-    _check_layout(pt.layout)
-    if kernel not in KERNELS:
-        raise MtqError(f"kernel must be one of {KERNELS}, got {kernel!r}")
-    if len(pt.shape) != 2:
-        raise MtqError(f"linear needs a 2-D (n, k) weight, the packed tensor is {pt.shape}")
-    backend = backend or ("hip" if pt.on_device else "emulation")
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    n, k = pt.rows, pt.cols
-    if backend == "hip":
-        import torch
-
-        from . import hip_backend as hb
-
-        if x.dim() != 2 or x.shape[1] != k:
-            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
-        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-        m = int(x.shape[0])
-        if kernel == "skinny" and m > SKINNY_MAX_M:
-            raise MtqError(f'kernel="skinny" takes m <= {SKINNY_MAX_M}, got m = {m}')
-        if kernel == "skinny" or (kernel == "auto" and m <= AUTO_SKINNY_MAX_M):
-            return hb.packed_linear_skinny(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype, split=split, workspace=workspace)
-        if kernel == "auto" and AUTO_WIDE_MIN_M is not None and m >= AUTO_WIDE_MIN_M and hb.has_packed_linear_wide():
-            return hb.packed_linear_wide(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
-        return hb.packed_linear(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
-    if backend != "emulation":
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
-    import torch
-
-    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
-    if xf.ndim != 2 or xf.shape[1] != k:
-        raise MtqError(f"x must be (m, {k}), got {xf.shape}")
-    w = decode(_host_data(pt), pt.map, pt.offsets, n, k).view(np.float32)
-    y = xf.astype(np.float64) @ w.astype(np.float64).T
-    if bias is not None:
-        y = y + (bias.detach().to("cpu").double().numpy() if _is_torch(bias) else np.asarray(bias, dtype=np.float64))[None, :]
-    with np.errstate(over="ignore"):
-        y32 = y.astype(np.float32)
-    return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
+    return _product(_NK, "linear", x, pt, bias, out_dtype, backend, kernel, split, workspace)
 
 
 def linear_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
@@ -428,23 +644,7 @@ def linear_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", back
     decode range (prefill), 128 x 128 outputs to a workgroup, whose waves decode whole tiles of the weight.  Correct for any m
     (m = 0 gives (0, n)); faster than the block kernel from m = 64 on, the smallest m measured.  A library without the symbol raises MtqError: there is no
     fall-back to the block kernel here (linear(kernel="auto") is the call that chooses).  emulation: linear's float64 product."""
-    _check_layout(pt.layout)
-    if len(pt.shape) != 2:
-        raise MtqError(f"linear needs a 2-D (n, k) weight, the packed tensor is {pt.shape}")
-    backend = backend or ("hip" if pt.on_device else "emulation")
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    if backend != "hip":
-        return linear(x, pt, bias=bias, out_dtype=out_dtype, backend=backend)
-    import torch
-
-    from . import hip_backend as hb
-
-    n, k = pt.rows, pt.cols
-    if x.dim() != 2 or x.shape[1] != k:
-        raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
-    dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-    return hb.packed_linear_wide(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
+    return _product_wide(_NK, "linear", x, pt, bias, out_dtype, backend)
 
 
 # ----------------------------------------------------------------------------- the transposed layout and (k, n) weights
@@ -455,10 +655,13 @@ def _need_matmul(hb, what: str) -> None:
                        "libmtq_hip.so lacks: rebuild it from this tree")
 
 
+def _need_matmul_wide(hb, what: str) -> None:
+    if not hb.has_packed_matmul_wide():
+        raise MtqError(f"{what} needs mtq_packed_matmul_wide, {_LACKS}")
+
+
 def _check_kn(pt: PackedTensor, what: str) -> None:
-    _check_layout(pt.layout)
-    if len(pt.shape) != 2:
-        raise MtqError(f"{what} needs a 2-D packed (k, n) matrix, the packed tensor is {pt.shape}")
+    _check_rank2(_KN, pt, what)
 
 
 def pack_transposed(w, amap, backend: str = "emulation") -> PackedTensor:
@@ -466,8 +669,7 @@ def pack_transposed(w, amap, backend: str = "emulation") -> PackedTensor:
     search with params["layout"] = "transpose" (or layer_output_error.py's budget_<B>_<basis>_transpose.npy) writes for W.  The result
     is an ordinary PackedTensor of shape (k, n) in the row layout: save / load, unpack (which gives Wᵀ) and matmul take it as it is.
     hip: w is read in place through mtq_pack_tiles_transposed (no transposed copy).  emulation: pack(np.ascontiguousarray(w.T), amap)."""
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    _check_backend(backend)
     if len(tuple(w.shape)) != 2 or 0 in tuple(w.shape):
         raise MtqError(f"pack_transposed takes a non-empty 2-D (n, k) weight, got {tuple(w.shape)}")
     n, k = (int(v) for v in w.shape)
@@ -477,8 +679,6 @@ def pack_transposed(w, amap, backend: str = "emulation") -> PackedTensor:
                        "pack_transposed takes a map over the transpose's grid")
     if backend == "hip":
         import torch
-
-        from . import hip_backend as hb
 
         _need_matmul(hb, "pack_transposed")
         hb.require_gpu()
@@ -498,18 +698,12 @@ def unpack_transposed(pt: PackedTensor, backend: str = "emulation", dtype: str =
     for bit what K3T (mtq_apply_assignment_transposed) and scripts/reconstruct_mixed_tile_assignment.py --layout transpose give for W
     and the map; bfloat16: the same values, exact.  hip: mtq_unpack_tiles_transposed, a device tensor."""
     _check_kn(pt, "unpack_transposed")
-    if dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"dtype must be 'float32' or 'bfloat16', got {dtype!r}")
+    _check_out_dtype(dtype, "dtype")
     if backend == "hip":
-        import torch
-
-        from . import hip_backend as hb
-
         _need_matmul(hb, "unpack_transposed")
         hb.require_gpu()
-        return hb.unpack_tiles_transposed(_device_data(pt), pt.tables(), pt.cols, pt.rows, torch.float32 if dtype == "float32" else torch.bfloat16)
-    if backend != "emulation":
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+        return hb.unpack_tiles_transposed(_device_data(pt), pt.tables(), pt.cols, pt.rows, _torch_dtype(dtype))
+    _check_backend(backend)
     y = unpack(pt, backend="emulation", dtype=dtype)
     return y.t().contiguous() if _is_torch(y) else np.ascontiguousarray(y.T)
 
@@ -518,17 +712,6 @@ def _need_matmul_skinny(hb, what: str) -> None:
     if not hb.has_packed_matmul_skinny():
         raise MtqError(f"{what} needs {' and '.join(hb.PACKED_MATMUL_SKINNY)}, which this build of libmtq_hip.so lacks: rebuild it from "
                        "this tree")
-
-
-def _matmul_takes_skinny(hb, kernel: str, m: int) -> bool:
-    """Whether matmul's `kernel` means the skinny entry at this m: "skinny" always (a library without it raises, no other kernel stands
-    in), "auto" up to AUTO_MATMUL_SKINNY_MAX_M on a library that has it."""
-    if kernel == "skinny":
-        if m > SKINNY_MAX_M:
-            raise MtqError(f'kernel="skinny" takes m <= {SKINNY_MAX_M}, got m = {m}')
-        _need_matmul_skinny(hb, 'matmul(kernel="skinny")')
-        return True
-    return kernel == "auto" and AUTO_MATMUL_SKINNY_MAX_M is not None and m <= AUTO_MATMUL_SKINNY_MAX_M and hb.has_packed_matmul_skinny()
 
 
 def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block", split: int = 0,
@@ -547,42 +730,7 @@ def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     that is not None and the library has it, the wide-block kernel of matmul_wide, whose bits are the block kernel's.  The skinny and
     the block kernel sum in different orders: each is bit-stable, they may differ in the last bits.  The emulation computes the same
     float64 product under all three names."""
-    _check_kn(pt, "matmul")
-    if kernel not in MATMUL_KERNELS:
-        raise MtqError(f"kernel must be one of {MATMUL_KERNELS}, got {kernel!r}")
-    backend = backend or ("hip" if pt.on_device else "emulation")
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    k, n = pt.rows, pt.cols
-    if backend == "hip":
-        import torch
-
-        from . import hip_backend as hb
-
-        if x.dim() != 2 or x.shape[1] != k:
-            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
-        _need_matmul(hb, "matmul")
-        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-        if _matmul_takes_skinny(hb, kernel, int(x.shape[0])):
-            return hb.packed_matmul_skinny(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype, split=split, workspace=workspace)
-        if (kernel == "auto" and AUTO_MATMUL_WIDE_MIN_M is not None and int(x.shape[0]) >= AUTO_MATMUL_WIDE_MIN_M
-                and hb.has_packed_matmul_wide()):
-            return hb.packed_matmul_wide(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
-        return hb.packed_matmul(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
-    if backend != "emulation":
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
-    import torch
-
-    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
-    if xf.ndim != 2 or xf.shape[1] != k:
-        raise MtqError(f"x must be (m, {k}), got {xf.shape}")
-    w = decode(_host_data(pt), pt.map, pt.offsets, k, n).view(np.float32)
-    y = xf.astype(np.float64) @ w.astype(np.float64)
-    if bias is not None:
-        y = y + (bias.detach().to("cpu").double().numpy() if _is_torch(bias) else np.asarray(bias, dtype=np.float64))[None, :]
-    with np.errstate(over="ignore"):
-        y32 = y.astype(np.float32)
-    return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
+    return _product(_KN, "matmul", x, pt, bias, out_dtype, backend, kernel, split, workspace)
 
 
 def matmul_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
@@ -591,23 +739,7 @@ def matmul_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", back
     (m = 0 gives (0, n)); faster than the block kernel from m = 64 on, the smallest m measured.  A library without
     the symbol raises MtqError: there is no fall-back to the block kernel here (matmul(kernel="auto") is the call that chooses).
     emulation: matmul's float64 product."""
-    _check_kn(pt, "matmul_wide")
-    backend = backend or ("hip" if pt.on_device else "emulation")
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    if backend != "hip":
-        return matmul(x, pt, bias=bias, out_dtype=out_dtype, backend=backend)
-    import torch
-
-    from . import hip_backend as hb
-
-    k, n = pt.rows, pt.cols
-    if x.dim() != 2 or x.shape[1] != k:
-        raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
-    if not hb.has_packed_matmul_wide():
-        raise MtqError("matmul_wide needs mtq_packed_matmul_wide, which this build of libmtq_hip.so lacks: rebuild it from this tree")
-    dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-    return hb.packed_matmul_wide(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype)
+    return _product_wide(_KN, "matmul_wide", x, pt, bias, out_dtype, backend)
 
 
 # ----------------------------------------------------------------------------- batches
@@ -670,8 +802,6 @@ def _pack_batch_device(x3d, maps, rows: int, cols: int, shapes: list, pack_launc
     through `pack_launch` (hip_backend.pack_tiles_batched, or pack_tiles_transposed_batched for a batch stored cols × rows)."""
     import torch
 
-    from . import hip_backend as hb
-
     count = int(x3d.shape[0])
     th, tw = -(-rows // TILE), -(-cols // TILE)
     tiles = th * tw
@@ -732,15 +862,12 @@ def pack_batch(x3d, maps, backend: str = "emulation", layout: str = "rows", shap
 
     Every returned tensor is a full PackedTensor (unpack, linear, PackedLinear, save); unpack_batch undoes the call in one launch."""
     _check_layout(layout)
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    _check_backend(backend)
     if len(x3d.shape) != 3 or 0 in tuple(x3d.shape):
         raise MtqError(f"pack_batch takes a non-empty (count, rows, cols) batch, got {tuple(x3d.shape)}")
     count, rows, cols = (int(v) for v in x3d.shape)
     shapes = _batch_shapes(shapes, count, rows, cols)
     if backend == "hip":
-        from . import hip_backend as hb
-
         hb.require_gpu()
         return _pack_batch_device(x3d, maps, rows, cols, shapes, hb.pack_tiles_batched)
     xf = x3d.detach().to("cpu").float().numpy() if _is_torch(x3d) else np.asarray(x3d, dtype=np.float32)
@@ -762,20 +889,16 @@ def unpack_batch(pts, backend: str = "emulation", dtype: str = "float32"):
         raise MtqError("unpack_batch needs at least one packed tensor")
     for pt in pts:
         _check_layout(pt.layout)
-    if dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"dtype must be 'float32' or 'bfloat16', got {dtype!r}")
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    _check_out_dtype(dtype, "dtype")
+    _check_backend(backend)
     rows, cols = pts[0].rows, pts[0].cols
     if any((pt.rows, pt.cols) != (rows, cols) for pt in pts):
         raise MtqError("unpack_batch takes tensors of one 2-D shape")
     import torch
 
     if backend == "hip":
-        from . import hip_backend as hb
-
         hb.require_gpu()
-        tdtype = torch.float32 if dtype == "float32" else torch.bfloat16
+        tdtype = _torch_dtype(dtype)
         batch = batch_of(pts)
         if batch is not None and batch.maps_dev is not None:
             return hb.unpack_tiles_batched(batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, batch.count, rows, cols, tdtype)
@@ -803,8 +926,7 @@ def pack_batch_transposed(w3d, maps, backend: str = "emulation") -> list:
     place, whatever its row pitch and matrix stride; no transposed copy), one offsets launch pair, one read-back (bases, bad-code
     counts, device maps), one pack launch; a tensor with a code outside 0..3 raises MtqError before anything is packed.  Slice i is byte
     for byte pack_transposed(w3d[i], maps[i]).  emulation: pack_batch of the transposed copies."""
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    _check_backend(backend)
     if len(w3d.shape) != 3 or 0 in tuple(w3d.shape):
         raise MtqError(f"pack_batch_transposed takes a non-empty (count, n, k) batch, got {tuple(w3d.shape)}")
     count, n, k = (int(v) for v in w3d.shape)
@@ -814,8 +936,6 @@ def pack_batch_transposed(w3d, maps, backend: str = "emulation") -> list:
         raise MtqError(f"the maps are {'x'.join(map(str, given))}, {count} transposed weights have {count}x{th}x{tw} tiles: "
                        "pack_batch_transposed takes maps over the transposes' grid")
     if backend == "hip":
-        from . import hip_backend as hb
-
         _need_batch_transposed(hb, "pack_batch_transposed")
         hb.require_gpu()
         return _pack_batch_device(w3d, maps, k, n, [(k, n)] * count, hb.pack_tiles_transposed_batched)
@@ -833,20 +953,16 @@ def unpack_batch_transposed(pts, backend: str = "emulation", dtype: str = "float
         raise MtqError("unpack_batch_transposed needs at least one packed tensor")
     for pt in pts:
         _check_kn(pt, "unpack_batch_transposed")
-    if dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"dtype must be 'float32' or 'bfloat16', got {dtype!r}")
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    _check_out_dtype(dtype, "dtype")
+    _check_backend(backend)
     k, n = pts[0].rows, pts[0].cols
     if any((pt.rows, pt.cols) != (k, n) for pt in pts):
         raise MtqError("unpack_batch_transposed takes tensors of one 2-D shape")
     if backend == "hip":
         import torch
 
-        from . import hip_backend as hb
-
         hb.require_gpu()
-        tdtype = torch.float32 if dtype == "float32" else torch.bfloat16
+        tdtype = _torch_dtype(dtype)
         batch = batch_of(pts)
         if batch is not None and batch.maps_dev is not None:
             _need_batch_transposed(hb, "unpack_batch_transposed")
@@ -889,8 +1005,6 @@ def as_batch(pts, device=None) -> PackedBatch:
         return PackedBatch(count, rows, cols, arena, bases, maps=maps)
     import torch
 
-    from . import hip_backend as hb
-
     hb.require_gpu()
     dev = _torch_device(device) if device is not None else next(pt.data.device for pt in pts if pt.on_device)
     parts = [(pt.data if pt.on_device else torch.from_numpy(np.ascontiguousarray(_host_data(pt))))[: pt.nbytes].to(dev) for pt in pts]
@@ -901,8 +1015,6 @@ def _device_batch(count: int, rows: int, cols: int, arena, bases: np.ndarray, ma
     """A device arena, its host bases and host maps → the PackedBatch with device tables: the maps uploaded, the offsets and bases
     computed on the device and held to the host's (one read-back)."""
     import torch
-
-    from . import hip_backend as hb
 
     maps_dev = torch.from_numpy(np.ascontiguousarray(maps.reshape(count, -1))).to(arena.device)
     offsets_dev, bases_dev, bad_dev = hb.packed_offsets_device(maps_dev, count, maps_dev.shape[1])
@@ -941,8 +1053,6 @@ def batch_to_device(batch: PackedBatch, device="cuda") -> PackedBatch:
     if _batch_on_device(batch):
         return batch
     import torch
-
-    from . import hip_backend as hb
 
     hb.require_gpu()
     arena = batch.arena if _is_torch(batch.arena) else torch.from_numpy(np.ascontiguousarray(batch.arena, dtype=np.uint8))
@@ -985,24 +1095,104 @@ GROUPED_KERNELS = ("walk", "chunks", "auto")
 GROUPED_AUTO_KERNEL = "chunks"
 
 
-def _grouped_kernel(kernel: str) -> str:
+def _grouped_kernel(o: _Orientation, kernel: str) -> str:
     """`kernel` of the grouped entries, "auto" resolved."""
-    if kernel not in GROUPED_KERNELS:
-        raise MtqError(f"kernel must be one of {GROUPED_KERNELS}, got {kernel!r}")
-    return GROUPED_AUTO_KERNEL if kernel == "auto" else kernel
+    _check_kernel(kernel, globals()[o.grouped_kernels])
+    return globals()[o.grouped_auto_kernel] if kernel == "auto" else kernel
 
 
-def _grouped_entries(kernel: str):
-    """(the launch, its workspace-size function) of hip_backend for a resolved grouped kernel; "chunks" on a library without the symbol is
-    an error, never the other kernel."""
-    from . import hip_backend as hb
+def _grouped_entry(o: _Orientation, hb, kernel: str, lacks=None):
+    """(the launch, its workspace-size function) of hip_backend for a resolved grouped kernel, or "wide" for the wide grouped product.
+    A kernel whose predicate says the library lacks it is an error that names its symbols, never another kernel; lacks: (who, hint)
+    in place of the orientation's own wording of that error."""
+    launch, size, has, who, symbols, hint = o.hb_grouped[kernel]
+    if has is not None and not getattr(hb, has)():
+        who, hint = lacks or (who, hint)
+        names = getattr(hb, symbols, None)           # the name of hip_backend's tuple of the symbols, or the text itself
+        raise MtqError(f"{who} needs {symbols if names is None else ' and '.join(names)}, {_LACKS}{hint}")
+    return getattr(hb, launch), getattr(hb, size)
 
-    if kernel == "walk":
-        return hb.packed_linear_skinny_grouped, hb.packed_linear_skinny_grouped_workspace_bytes
-    if not hb.has_packed_linear_grouped_chunked():
-        raise MtqError('kernel="chunks" needs mtq_packed_linear_skinny_grouped_chunked, which this build of libmtq_hip.so lacks: rebuild it '
-                       'from this tree, or use kernel="walk"')
-    return hb.packed_linear_skinny_grouped_chunked, hb.packed_linear_skinny_grouped_chunked_workspace_bytes
+
+def _resolve_group_rows(group_rows, count: int, T: int):
+    """→ (group_rows, on_device): a device tensor as it is (the kernel clamps it), anything else checked here, as int64 on the host."""
+    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
+    if not on_device:
+        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
+    return group_rows, on_device
+
+
+def _emulated_group_rows(group_rows, on_device: bool, count: int, T: int):
+    """(r0, r1) per group for the emulation: a checked host group_rows as it is, a device one as the kernel clamps it."""
+    if not on_device:
+        return group_rows[:-1], group_rows[1:]
+    if tuple(group_rows.shape) != (count + 1,):      # trusted, as on hip: what the kernel makes of it
+        raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {tuple(group_rows.shape)}")
+    return clamp_group_rows(group_rows.cpu().numpy(), T)
+
+
+def _device_group_rows(group_rows, on_device: bool, device):
+    import torch
+
+    return group_rows if on_device else torch.from_numpy(group_rows.astype(np.int32)).to(device)
+
+
+def _device_bias(bias, device):
+    if bias is None or _is_torch(bias):
+        return bias
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32)).to(device)
+
+
+def _arena_args(batch: PackedBatch) -> tuple:
+    return batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev
+
+
+def _grouped(o: _Orientation, x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, kernel):
+    """linear_grouped and matmul_grouped (kernel "walk" / "chunks", resolved) and the two *_grouped_wide (kernel "wide", no split)."""
+    batch = _resolve_batch(pts_or_batch)
+    _check_out_dtype(out_dtype)
+    backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
+    _check_backend(backend)
+    count, (n, k) = batch.count, o.n_k(batch)
+    if len(x.shape) != 2 or x.shape[1] != k:
+        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
+    T = int(x.shape[0])
+    group_rows, on_device = _resolve_group_rows(group_rows, count, T)
+    if backend == "hip":
+        launch, _size = _grouped_entry(o, hb, kernel)            # a missing kernel is refused before any device work
+        batch = batch_to_device(batch)
+        dtype = _torch_dtype(out_dtype)
+        if T == 0:
+            import torch
+
+            return torch.zeros((0, n), dtype=dtype, device=batch.arena.device)
+        more = {} if kernel == "wide" else {"split": split}
+        return launch(x, _device_group_rows(group_rows, on_device, batch.arena.device), *_arena_args(batch), count, n,
+                      bias=_device_bias(bias, batch.arena.device), out_dtype=dtype, workspace=workspace, **more)
+    xf = _host_f32(x)
+    r0, r1 = _emulated_group_rows(group_rows, on_device, count, T)
+    b = _host_f64(bias, (count, n), "bias")
+    y = np.zeros((T, n), dtype=np.float64)
+    for e, (amap, offsets, data) in enumerate(_batch_host_tensors(batch)):
+        if r1[e] == r0[e]:
+            continue
+        w = decode(data, amap, offsets, batch.rows, batch.cols).view(np.float32)
+        ye = o.times(xf[r0[e]: r1[e]].astype(np.float64), w.astype(np.float64))
+        y[r0[e]: r1[e]] = ye if b is None else ye + b[e][None, :]
+    return _round_out(y, out_dtype)
+
+
+def _grouped_batch(o: _Orientation, x3d, pts_or_batch, bias, out_dtype, backend, split, workspace, kernel):
+    """linear_batch and matmul_batch: the grouped product over equal groups of m rows."""
+    batch = _resolve_batch(pts_or_batch)
+    n, k = o.n_k(batch)
+    if len(x3d.shape) != 3 or x3d.shape[0] != batch.count or x3d.shape[2] != k:
+        raise MtqError(f"x3d must be ({batch.count}, m, {k}), got {tuple(x3d.shape)}")
+    m = int(x3d.shape[1])
+    y = globals()[o.grouped](x3d.reshape(batch.count * m, k), m * np.arange(batch.count + 1, dtype=np.int64), batch,
+                             bias=bias, out_dtype=out_dtype, backend=backend, split=split, workspace=workspace, kernel=kernel)
+    return y.reshape(batch.count, m, n)
 
 
 def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
@@ -1021,71 +1211,13 @@ def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "flo
     mtq_packed_linear_skinny_grouped_chunked, one wave per (slice, chunk, tile row) with the chunk list made on the device, for routings
     with hot experts — the same bits, a workspace at every split, MtqError when the library lacks it; "auto", GROUPED_AUTO_KERNEL.
     emulation: per group the float64 product of the decoded weight, rounded once, as linear does, under every kernel name."""
-    kernel = _grouped_kernel(kernel)
-    batch = _resolve_batch(pts_or_batch)
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
-    count, n, k = batch.count, batch.rows, batch.cols
-    if len(x.shape) != 2 or x.shape[1] != k:
-        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
-    T = int(x.shape[0])
-    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
-    if not on_device:
-        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
-    import torch
-
-    if backend == "hip":
-        from . import hip_backend as hb
-
-        launch = None if kernel == "walk" else _grouped_entries(kernel)[0]      # a missing kernel is refused before any device work
-        batch = batch_to_device(batch)
-        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-        if T == 0:
-            return torch.zeros((0, n), dtype=dtype, device=batch.arena.device)
-        if not on_device:
-            group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(batch.arena.device)
-        if bias is not None and not _is_torch(bias):
-            bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32)).to(batch.arena.device)
-        if launch is None:                           # "walk": looked up here, by name, as before there was a choice
-            return hb.packed_linear_skinny_grouped(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias,
-                                                   out_dtype=dtype, split=split, workspace=workspace)
-        return launch(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias, out_dtype=dtype,
-                      split=split, workspace=workspace)
-    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
-    if on_device:                                    # trusted, as on hip: what the kernel makes of it
-        if tuple(group_rows.shape) != (count + 1,):
-            raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {tuple(group_rows.shape)}")
-        r0, r1 = clamp_group_rows(group_rows.cpu().numpy(), T)
-    else:
-        r0, r1 = group_rows[:-1], group_rows[1:]
-    b = None if bias is None else (bias.detach().to("cpu").double().numpy() if _is_torch(bias) else np.asarray(bias, dtype=np.float64))
-    if b is not None and b.shape != (count, n):
-        raise MtqError(f"bias must be ({count}, {n}), got {b.shape}")
-    y = np.zeros((T, n), dtype=np.float64)
-    for e, (amap, offsets, data) in enumerate(_batch_host_tensors(batch)):
-        if r1[e] == r0[e]:
-            continue
-        w = decode(data, amap, offsets, n, k).view(np.float32)
-        ye = xf[r0[e]: r1[e]].astype(np.float64) @ w.astype(np.float64).T
-        y[r0[e]: r1[e]] = ye if b is None else ye + b[e][None, :]
-    with np.errstate(over="ignore"):
-        y32 = y.astype(np.float32)
-    return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
+    return _grouped(_NK, x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, _grouped_kernel(_NK, kernel))
 
 
 def linear_batch(x3d, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0, workspace=None,
                  kernel: str = "walk"):
     """x3d (count, m, k): expert e multiplies x3d[e] → (count, m, n).  linear_grouped with group_rows = m * arange(count + 1)."""
-    batch = _resolve_batch(pts_or_batch)
-    if len(x3d.shape) != 3 or x3d.shape[0] != batch.count or x3d.shape[2] != batch.cols:
-        raise MtqError(f"x3d must be ({batch.count}, m, {batch.cols}), got {tuple(x3d.shape)}")
-    m = int(x3d.shape[1])
-    y = linear_grouped(x3d.reshape(batch.count * m, batch.cols), m * np.arange(batch.count + 1, dtype=np.int64), batch,
-                       bias=bias, out_dtype=out_dtype, backend=backend, split=split, workspace=workspace, kernel=kernel)
-    return y.reshape(batch.count, m, batch.rows)
+    return _grouped_batch(_NK, x3d, pts_or_batch, bias, out_dtype, backend, split, workspace, kernel)
 
 
 def linear_grouped_wide(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, workspace=None):
@@ -1099,38 +1231,7 @@ def linear_grouped_wide(x, group_rows, pts_or_batch, bias=None, out_dtype: str =
     a function of its own and no GROUPED_KERNELS name.  Rows outside every group are zeros; T = 0 gives (0, n) without a call.  A library
     without the symbol raises MtqError before any device work: no other kernel runs in its place.
     emulation: linear_grouped's float64 product."""
-    batch = _resolve_batch(pts_or_batch)
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
-    if backend != "hip":
-        return linear_grouped(x, group_rows, batch, bias=bias, out_dtype=out_dtype, backend=backend)
-    import torch
-
-    from . import hip_backend as hb
-
-    count, n, k = batch.count, batch.rows, batch.cols
-    if len(x.shape) != 2 or x.shape[1] != k:
-        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
-    T = int(x.shape[0])
-    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
-    if not on_device:
-        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
-    if not hb.has_packed_linear_wide_grouped():      # a missing kernel is refused before any device work
-        raise MtqError("linear_grouped_wide needs mtq_packed_linear_wide_grouped, which this build of libmtq_hip.so lacks: rebuild it from "
-                       "this tree, or use linear_grouped")
-    batch = batch_to_device(batch)
-    dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-    if T == 0:
-        return torch.zeros((0, n), dtype=dtype, device=batch.arena.device)
-    if not on_device:
-        group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(batch.arena.device)
-    if bias is not None and not _is_torch(bias):
-        bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32)).to(batch.arena.device)
-    return hb.packed_linear_wide_grouped(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias,
-                                         out_dtype=dtype, workspace=workspace)
+    return _grouped(_NK, x, group_rows, pts_or_batch, bias, out_dtype, backend, 0, workspace, "wide")
 
 
 # ----------------------------------------------------------------------------- grouped products with (k, n) experts
@@ -1141,83 +1242,6 @@ MATMUL_GROUPED_KERNELS = ("walk", "chunks", "auto")
 # skewed rows (0.20-0.54 of it) and (2) on the twelve rows with 1, 4 or 32 rows per expert it is within the run's spread (1.0212) of the
 # walking entry's minimum (1.001-1.013).  Shapes, counts and routings outside that record are unmeasured.
 MATMUL_GROUPED_AUTO_KERNEL = "chunks"
-
-
-def _matmul_grouped_kernel(kernel: str) -> str:
-    """`kernel` of matmul_grouped, "auto" resolved."""
-    if kernel not in MATMUL_GROUPED_KERNELS:
-        raise MtqError(f"kernel must be one of {MATMUL_GROUPED_KERNELS}, got {kernel!r}")
-    return MATMUL_GROUPED_AUTO_KERNEL if kernel == "auto" else kernel
-
-
-def _matmul_grouped_entries(kernel: str):
-    """(the launch, its workspace-size function) of hip_backend for a resolved matmul_grouped kernel, or "wide" for matmul_grouped_wide;
-    a library without the symbols is an error that names them, never another kernel."""
-    from . import hip_backend as hb
-
-    has, names, launch, size = {
-        "walk": (hb.has_packed_matmul_grouped, hb.MATMUL_GROUPED, hb.packed_matmul_skinny_grouped, hb.packed_matmul_skinny_grouped_workspace_bytes),
-        "chunks": (hb.has_packed_matmul_grouped_chunked, hb.MATMUL_GROUPED_CHUNKED, hb.packed_matmul_skinny_grouped_chunked,
-                   hb.packed_matmul_skinny_grouped_chunked_workspace_bytes),
-        "wide": (hb.has_packed_matmul_wide_grouped, hb.MATMUL_WIDE_GROUPED, hb.packed_matmul_wide_grouped,
-                 hb.packed_matmul_wide_grouped_workspace_bytes),
-    }[kernel]
-    if not has():
-        what = "matmul_grouped_wide" if kernel == "wide" else f'matmul_grouped(kernel="{kernel}")'
-        raise MtqError(f"{what} needs {' and '.join(names)}, which this build of libmtq_hip.so lacks: rebuild it from this tree")
-    return launch, size
-
-
-def _matmul_grouped(x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, kernel):
-    """matmul_grouped (kernel "walk" / "chunks") and matmul_grouped_wide (kernel "wide", no split) behind their checks of `kernel`."""
-    batch = _resolve_batch(pts_or_batch)
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
-    count, k, n = batch.count, batch.rows, batch.cols
-    if len(x.shape) != 2 or x.shape[1] != k:
-        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
-    T = int(x.shape[0])
-    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
-    if not on_device:
-        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
-    import torch
-
-    if backend == "hip":
-        launch, _size = _matmul_grouped_entries(kernel)          # a missing kernel is refused before any device work
-        batch = batch_to_device(batch)
-        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-        if T == 0:
-            return torch.zeros((0, n), dtype=dtype, device=batch.arena.device)
-        if not on_device:
-            group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(batch.arena.device)
-        if bias is not None and not _is_torch(bias):
-            bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32)).to(batch.arena.device)
-        more = {} if kernel == "wide" else {"split": split}
-        return launch(x, group_rows, batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev, count, n, bias=bias, out_dtype=dtype,
-                      workspace=workspace, **more)
-    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
-    if on_device:                                    # trusted, as on hip: what the kernel makes of it
-        if tuple(group_rows.shape) != (count + 1,):
-            raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {tuple(group_rows.shape)}")
-        r0, r1 = clamp_group_rows(group_rows.cpu().numpy(), T)
-    else:
-        r0, r1 = group_rows[:-1], group_rows[1:]
-    b = None if bias is None else (bias.detach().to("cpu").double().numpy() if _is_torch(bias) else np.asarray(bias, dtype=np.float64))
-    if b is not None and b.shape != (count, n):
-        raise MtqError(f"bias must be ({count}, {n}), got {b.shape}")
-    y = np.zeros((T, n), dtype=np.float64)
-    for e, (amap, offsets, data) in enumerate(_batch_host_tensors(batch)):
-        if r1[e] == r0[e]:
-            continue
-        w = decode(data, amap, offsets, k, n).view(np.float32)
-        ye = xf[r0[e]: r1[e]].astype(np.float64) @ w.astype(np.float64)
-        y[r0[e]: r1[e]] = ye if b is None else ye + b[e][None, :]
-    with np.errstate(over="ignore"):
-        y32 = y.astype(np.float32)
-    return y32 if out_dtype == "float32" else torch.from_numpy(y32).to(torch.bfloat16)
 
 
 def matmul_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
@@ -1235,19 +1259,13 @@ def matmul_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "flo
     same bits, a workspace at every split; "auto", MATMUL_GROUPED_AUTO_KERNEL.  A library without the kernel's symbols raises MtqError
     naming them before any device work: no other kernel runs in its place.
     emulation: per group the float64 product of the decoded (k, n) matrix, rounded once, as matmul does, under every kernel name."""
-    return _matmul_grouped(x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, _matmul_grouped_kernel(kernel))
+    return _grouped(_KN, x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, _grouped_kernel(_KN, kernel))
 
 
 def matmul_batch(x3d, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0, workspace=None,
                  kernel: str = "walk"):
     """x3d (count, m, k): expert e multiplies x3d[e] → (count, m, n).  matmul_grouped with group_rows = m * arange(count + 1)."""
-    batch = _resolve_batch(pts_or_batch)
-    if len(x3d.shape) != 3 or x3d.shape[0] != batch.count or x3d.shape[2] != batch.rows:
-        raise MtqError(f"x3d must be ({batch.count}, m, {batch.rows}), got {tuple(x3d.shape)}")
-    m = int(x3d.shape[1])
-    y = matmul_grouped(x3d.reshape(batch.count * m, batch.rows), m * np.arange(batch.count + 1, dtype=np.int64), batch,
-                       bias=bias, out_dtype=out_dtype, backend=backend, split=split, workspace=workspace, kernel=kernel)
-    return y.reshape(batch.count, m, batch.cols)
+    return _grouped_batch(_KN, x3d, pts_or_batch, bias, out_dtype, backend, split, workspace, kernel)
 
 
 def matmul_grouped_wide(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, workspace=None):
@@ -1258,7 +1276,7 @@ def matmul_grouped_wide(x, group_rows, pts_or_batch, bias=None, out_dtype: str =
     bits, not matmul_grouped's, which is why this is a function of its own and no MATMUL_GROUPED_KERNELS name.  Rows outside every group
     are zeros; T = 0 gives (0, n) without a call; a library without the symbol raises MtqError before any device work.
     emulation: matmul_grouped's float64 product."""
-    return _matmul_grouped(x, group_rows, pts_or_batch, bias, out_dtype, backend, 0, workspace, "wide")
+    return _grouped(_KN, x, group_rows, pts_or_batch, bias, out_dtype, backend, 0, workspace, "wide")
 
 
 # ----------------------------------------------------------------------------- the gated product (SwiGLU)
@@ -1274,35 +1292,6 @@ def _glu_host(g64: np.ndarray, u64: np.ndarray, act: str) -> np.ndarray:
         return g64 * u64
     with np.errstate(over="ignore", invalid="ignore"):
         return g64 / (1.0 + np.exp(-g64)) * u64
-
-
-def _host_f64(v, shape, name: str):
-    if v is None:
-        return None
-    b = v.detach().to("cpu").double().numpy() if _is_torch(v) else np.asarray(v, dtype=np.float64)
-    if b.shape != shape:
-        raise MtqError(f"{name} must be {shape}, got {b.shape}")
-    return b
-
-
-def _round_out(h64: np.ndarray, out_dtype: str):
-    """float64 → float32 once, and from there to bf16, as linear's emulation rounds."""
-    with np.errstate(over="ignore"):
-        y32 = h64.astype(np.float32)
-    if out_dtype == "float32":
-        return y32
-    import torch
-
-    return torch.from_numpy(y32).to(torch.bfloat16)
-
-
-def _glu_pair(gate: PackedTensor, up: PackedTensor) -> None:
-    for name, pt in (("gate", gate), ("up", up)):
-        _check_layout(pt.layout)
-        if len(pt.shape) != 2:
-            raise MtqError(f"glu needs 2-D (n, k) weights, the packed {name} tensor is {pt.shape}")
-    if (gate.rows, gate.cols) != (up.rows, up.cols):
-        raise MtqError(f"gate and up must have one shape, got {gate.rows}x{gate.cols} and {up.rows}x{up.cols}")
 
 
 def _need_glu(hb, what: str) -> None:
@@ -1325,56 +1314,12 @@ def glu(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=No
     library without the gated entries raises MtqError under every name: there is no fall-back.
     emulation: float64 throughout from the unpacked weights, g = X·Ŵgᵀ + bg, u likewise, act(g) * u, rounded once to float32 and from
     there to bf16, as linear's emulation rounds; the same value under every kernel name."""
-    _glu_pair(gate, up)
-    _check_act(act)
-    if kernel not in GLU_KERNELS:
-        raise MtqError(f"kernel must be one of {GLU_KERNELS}, got {kernel!r}")
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    backend = backend or ("hip" if gate.on_device else "emulation")
-    n, k = gate.rows, gate.cols
-    if backend == "hip":
-        import torch
-
-        from . import hip_backend as hb
-
-        if x.dim() != 2 or x.shape[1] != k:
-            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
-        _need_glu(hb, "glu")
-        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-        m = int(x.shape[0])
-        if kernel == "auto":
-            kernel = "skinny" if m <= AUTO_SKINNY_MAX_M else ("fused" if AUTO_GLU_FUSED_MIN_M is not None and m >= AUTO_GLU_FUSED_MIN_M else "unfused")
-        if kernel == "fused":
-            return hb.packed_glu_wide(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act, bias_gate=bias_gate,
-                                      bias_up=bias_up, out_dtype=dtype)
-        if kernel == "skinny":
-            g = hb.packed_linear_skinny(x, _device_data(gate), gate.tables(), n, bias=bias_gate, out_dtype=torch.float32)
-            u = hb.packed_linear_skinny(x, _device_data(up), up.tables(), n, bias=bias_up, out_dtype=torch.float32)
-        else:
-            g = hb.packed_linear(x, _device_data(gate), gate.tables(), n, bias=bias_gate, out_dtype=torch.float32)
-            u = hb.packed_linear(x, _device_data(up), up.tables(), n, bias=bias_up, out_dtype=torch.float32)
-        return hb.glu_combine(g, u, act=act, out_dtype=dtype)
-    if backend != "emulation":
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
-    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
-    if xf.ndim != 2 or xf.shape[1] != k:
-        raise MtqError(f"x must be (m, {k}), got {xf.shape}")
-    return _round_out(glu_emulation_f64(xf, gate, up, act, bias_gate, bias_up), out_dtype)
+    return _glu(_NK, "glu", x, gate, up, act, bias_gate, bias_up, out_dtype, backend, kernel)
 
 
 def glu_emulation_f64(xf: np.ndarray, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None) -> np.ndarray:
     """The emulation's float64 (m, n) value before its final rounding: what the accuracy tests measure against."""
-    n, k = gate.rows, gate.cols
-    x64 = np.asarray(xf, dtype=np.float32).astype(np.float64)
-    sides = []
-    for pt, bias, name in ((gate, bias_gate, "bias_gate"), (up, bias_up, "bias_up")):
-        w = decode(_host_data(pt), pt.map, pt.offsets, n, k).view(np.float32)
-        with np.errstate(over="ignore", invalid="ignore"):
-            y = x64 @ w.astype(np.float64).T
-        b = _host_f64(bias, (n,), name)
-        sides.append(y if b is None else y + b[None, :])
-    return _glu_host(sides[0], sides[1], act)
+    return _glu_f64(_NK, xf, gate, up, act, bias_gate, bias_up)
 
 
 def _need_glu_skinny(hb, what: str) -> None:
@@ -1391,26 +1336,7 @@ def glu_skinny(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_
     hip_backend.packed_glu_skinny_workspace_bytes bytes (never 0), allocated when None.  m > SKINNY_MAX_M and a library without the
     entry raise MtqError: there is no fall-back.
     emulation: glu's float64 value rounded once, whatever m and split."""
-    _glu_pair(gate, up)
-    _check_act(act)
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    backend = backend or ("hip" if gate.on_device else "emulation")
-    n, k = gate.rows, gate.cols
-    if backend == "hip":
-        import torch
-
-        from . import hip_backend as hb
-
-        if x.dim() != 2 or x.shape[1] != k:
-            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
-        _need_glu_skinny(hb, "glu_skinny")
-        if int(x.shape[0]) > SKINNY_MAX_M:
-            raise MtqError(f"glu_skinny takes m <= {SKINNY_MAX_M}, got m = {int(x.shape[0])}: glu(kernel=\"auto\") serves every m")
-        return hb.packed_glu_skinny(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act, bias_gate=bias_gate,
-                                    bias_up=bias_up, out_dtype=torch.float32 if out_dtype == "float32" else torch.bfloat16, split=split,
-                                    workspace=workspace)
-    return glu(x, gate, up, act=act, bias_gate=bias_gate, bias_up=bias_up, out_dtype=out_dtype, backend=backend)
+    return _glu_skinny(_NK, "glu_skinny", x, gate, up, act, bias_gate, bias_up, out_dtype, backend, split, workspace)
 
 
 def glu_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
@@ -1423,7 +1349,8 @@ def glu_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gat
     into float32 and hip_backend.glu_combine over all T rows - the same bits on every row of a group (a row of no group is zero under
     "fused" and act(0) * 0 = 0 under "unfused").  T = 0 gives (0, n) without a call.
     emulation: per group glu's float64 value, rounded once."""
-    return _glu_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, GLU_GROUPED_KERNELS, 0, workspace)
+    return _glu_grouped(_NK, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, GLU_GROUPED_KERNELS, 0,
+                        workspace)
 
 
 def glu_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
@@ -1434,66 +1361,123 @@ def glu_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "silu", b
     of no group are zeros.  workspace: an optional uint8 device tensor of hip_backend.packed_glu_skinny_grouped_workspace_bytes bytes.
     T = 0 gives (0, n) without a call; a library without the entry raises MtqError: there is no fall-back.
     emulation: glu_grouped's value."""
-    return _glu_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, "skinny", ("skinny",), split, workspace)
+    return _glu_grouped(_NK, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, "skinny", ("skinny",), split,
+                        workspace)
 
 
-def _glu_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, kernels, split, workspace):
-    """glu_grouped and glu_grouped_skinny: `kernel` one of `kernels`, GLU_GROUPED_KERNELS or, from the latter alone, ("skinny",)."""
+def _glu(o: _Orientation, what: str, x, gate: PackedTensor, up: PackedTensor, act, bias_gate, bias_up, out_dtype, backend, kernel):
+    """glu and glu_matmul."""
+    _check_pair(o, gate, up, what)
+    _check_act(act)
+    _check_kernel(kernel, GLU_KERNELS)
+    _check_out_dtype(out_dtype)
+    backend = backend or ("hip" if gate.on_device else "emulation")
+    n, k = o.n_k(gate)
+    if backend == "hip":
+        import torch
+
+        if x.dim() != 2 or x.shape[1] != k:
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        _needs(o.need_glu, hb, what)
+        dtype = _torch_dtype(out_dtype)
+        m = int(x.shape[0])
+        if kernel == "auto":
+            fused_min_m = globals()[o.glu_auto_fused_min_m]
+            if _at_most(o, o.glu_auto_skinny_max_m, m):
+                kernel = "skinny"
+            else:
+                kernel = "fused" if fused_min_m is not None and m >= fused_min_m else "unfused"
+        if kernel == "fused":
+            return getattr(hb, o.hb_glu_fused)(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act, bias_gate=bias_gate,
+                                               bias_up=bias_up, out_dtype=dtype)
+        if kernel == "skinny":
+            _needs(o.need_glu_auto_skinny, hb, f'{what}(kernel="auto")')
+        side = getattr(hb, o.hb_skinny if kernel == "skinny" else o.hb_block)
+        g = side(x, _device_data(gate), gate.tables(), n, bias=bias_gate, out_dtype=torch.float32)
+        u = side(x, _device_data(up), up.tables(), n, bias=bias_up, out_dtype=torch.float32)
+        return hb.glu_combine(g, u, act=act, out_dtype=dtype)
+    _check_backend(backend)
+    xf = _host_f32(x)
+    if xf.ndim != 2 or xf.shape[1] != k:
+        raise MtqError(f"x must be (m, {k}), got {xf.shape}")
+    return _round_out(_glu_f64(o, xf, gate, up, act, bias_gate, bias_up), out_dtype)
+
+
+def _glu_f64(o: _Orientation, xf, gate: PackedTensor, up: PackedTensor, act, bias_gate, bias_up) -> np.ndarray:
+    """glu_emulation_f64 and glu_matmul_emulation_f64."""
+    n, _k = o.n_k(gate)
+    x64 = np.asarray(xf, dtype=np.float32).astype(np.float64)
+    sides = []
+    for pt, bias, name in ((gate, bias_gate, "bias_gate"), (up, bias_up, "bias_up")):
+        w = decode(_host_data(pt), pt.map, pt.offsets, pt.rows, pt.cols).view(np.float32)
+        with np.errstate(over="ignore", invalid="ignore"):
+            y = o.times(x64, w.astype(np.float64))
+        b = _host_f64(bias, (n,), name)
+        sides.append(y if b is None else y + b[None, :])
+    return _glu_host(sides[0], sides[1], act)
+
+
+def _glu_skinny(o: _Orientation, what: str, x, gate: PackedTensor, up: PackedTensor, act, bias_gate, bias_up, out_dtype, backend, split, workspace):
+    """glu_skinny and glu_matmul_skinny."""
+    _check_pair(o, gate, up, what)
+    _check_act(act)
+    _check_out_dtype(out_dtype)
+    backend = backend or ("hip" if gate.on_device else "emulation")
+    n, k = o.n_k(gate)
+    if backend == "hip":
+        if x.dim() != 2 or x.shape[1] != k:
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        _needs(o.need_glu_skinny, hb, what)
+        if int(x.shape[0]) > SKINNY_MAX_M:
+            raise MtqError(f"{what} takes m <= {SKINNY_MAX_M}, got m = {int(x.shape[0])}: {o.glu}(kernel=\"auto\") serves every m")
+        return getattr(hb, o.hb_glu_skinny)(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act, bias_gate=bias_gate,
+                                            bias_up=bias_up, out_dtype=_torch_dtype(out_dtype), split=split, workspace=workspace)
+    return globals()[o.glu](x, gate, up, act=act, bias_gate=bias_gate, bias_up=bias_up, out_dtype=out_dtype, backend=backend)
+
+
+def _glu_grouped(o: _Orientation, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, kernels, split, workspace):
+    """The grouped gated products: `kernel` one of `kernels`, GLU_GROUPED_KERNELS or, from the *_grouped_skinny functions alone,
+    ("skinny",)."""
     gate_b, up_b = _resolve_batch(gate_batch), _resolve_batch(up_batch)
     _check_act(act)
-    if kernel not in kernels:
-        raise MtqError(f"kernel must be one of {kernels}, got {kernel!r}")
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    _check_kernel(kernel, kernels)
+    _check_out_dtype(out_dtype)
     if (gate_b.count, gate_b.rows, gate_b.cols) != (up_b.count, up_b.rows, up_b.cols):
         raise MtqError(f"the gate and the up batch must hold as many experts of one shape, got {gate_b.count} of {gate_b.rows}x{gate_b.cols} and "
                        f"{up_b.count} of {up_b.rows}x{up_b.cols}")
     backend = backend or ("hip" if _batch_on_device(gate_b) else "emulation")
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
-    count, n, k = gate_b.count, gate_b.rows, gate_b.cols
+    _check_backend(backend)
+    count, (n, k) = gate_b.count, o.n_k(gate_b)
     if len(x.shape) != 2 or x.shape[1] != k:
         raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
     T = int(x.shape[0])
-    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
-    if not on_device:
-        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
+    group_rows, on_device = _resolve_group_rows(group_rows, count, T)
     if backend == "hip":
-        import torch
-
-        from . import hip_backend as hb
-
         if kernel == "skinny":                       # a missing kernel is refused before any device work
-            _need_glu_skinny(hb, "glu_grouped_skinny")
+            _needs(o.need_glu_skinny, hb, o.glu_grouped_skinny)
         else:
-            _need_glu(hb, "glu_grouped")
+            _needs(o.need_glu_grouped, hb, o.glu_grouped)
         gate_b, up_b = batch_to_device(gate_b), batch_to_device(up_b)
         dev = gate_b.arena.device
-        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        dtype = _torch_dtype(out_dtype)
         if T == 0:
+            import torch
+
             return torch.zeros((0, n), dtype=dtype, device=dev)
-        if not on_device:
-            group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(dev)
-        bias_gate, bias_up = (b if b is None or _is_torch(b) else torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(dev)
-                              for b in (bias_gate, bias_up))
+        group_rows = _device_group_rows(group_rows, on_device, dev)
+        bias_gate, bias_up = _device_bias(bias_gate, dev), _device_bias(bias_up, dev)
         if kernel == "skinny":
-            return hb.packed_glu_skinny_grouped(x, group_rows, (gate_b.arena, gate_b.maps_dev, gate_b.offsets_dev, gate_b.bases_dev),
-                                                (up_b.arena, up_b.maps_dev, up_b.offsets_dev, up_b.bases_dev), count, n, act=act,
-                                                bias_gate=bias_gate, bias_up=bias_up, out_dtype=dtype, split=split, workspace=workspace)
+            return getattr(hb, o.hb_glu_grouped_skinny)(x, group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, act=act, bias_gate=bias_gate,
+                                                        bias_up=bias_up, out_dtype=dtype, split=split, workspace=workspace)
         if kernel == "fused":
-            return hb.packed_glu_wide_grouped(x, group_rows, (gate_b.arena, gate_b.maps_dev, gate_b.offsets_dev, gate_b.bases_dev),
-                                              (up_b.arena, up_b.maps_dev, up_b.offsets_dev, up_b.bases_dev), count, n, act=act,
-                                              bias_gate=bias_gate, bias_up=bias_up, out_dtype=dtype, workspace=workspace)
-        g = linear_grouped_wide(x, group_rows, gate_b, bias=bias_gate, out_dtype="float32", backend="hip", workspace=workspace)
-        u = linear_grouped_wide(x, group_rows, up_b, bias=bias_up, out_dtype="float32", backend="hip", workspace=workspace)
+            return getattr(hb, o.hb_glu_grouped_fused)(x, group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, act=act, bias_gate=bias_gate,
+                                                       bias_up=bias_up, out_dtype=dtype, workspace=workspace)
+        wide = globals()[o.grouped_wide]
+        g = wide(x, group_rows, gate_b, bias=bias_gate, out_dtype="float32", backend="hip", workspace=workspace)
+        u = wide(x, group_rows, up_b, bias=bias_up, out_dtype="float32", backend="hip", workspace=workspace)
         return hb.glu_combine(g, u, act=act, out_dtype=dtype)
-    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
-    if on_device:                                    # trusted, as on hip: what the kernel makes of it
-        if tuple(group_rows.shape) != (count + 1,):
-            raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {tuple(group_rows.shape)}")
-        r0, r1 = clamp_group_rows(group_rows.cpu().numpy(), T)
-    else:
-        r0, r1 = group_rows[:-1], group_rows[1:]
+    xf = _host_f32(x)
+    r0, r1 = _emulated_group_rows(group_rows, on_device, count, T)
     bg, bu = _host_f64(bias_gate, (count, n), "bias_gate"), _host_f64(bias_up, (count, n), "bias_up")
     h = np.zeros((T, n), dtype=np.float64)
     x64 = xf.astype(np.float64)
@@ -1502,21 +1486,14 @@ def _glu_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, o
             continue
         sides = []
         for (amap, offsets, data), b in ((tg, bg), (tu, bu)):
-            w = decode(data, amap, offsets, n, k).view(np.float32)
-            y = x64[r0[e]: r1[e]] @ w.astype(np.float64).T
+            w = decode(data, amap, offsets, gate_b.rows, gate_b.cols).view(np.float32)
+            y = o.times(x64[r0[e]: r1[e]], w.astype(np.float64))
             sides.append(y if b is None else y + b[e][None, :])
         h[r0[e]: r1[e]] = _glu_host(sides[0], sides[1], act)
     return _round_out(h, out_dtype)
 
 
 # ----------------------------------------------------------------------------- the gated product over (k, n) weights
-
-def _glu_matmul_pair(gate: PackedTensor, up: PackedTensor, what: str) -> None:
-    for pt in (gate, up):
-        _check_kn(pt, what)
-    if (gate.rows, gate.cols) != (up.rows, up.cols):
-        raise MtqError(f"gate and up must have one shape, got {gate.rows}x{gate.cols} and {up.rows}x{up.cols}")
-
 
 def _need_glu_matmul(hb, what: str) -> None:
     if not hb.has_packed_glu() or not hb.has_packed_glu_matmul():
@@ -1533,16 +1510,7 @@ def _need_glu_matmul_skinny(hb, what: str) -> None:
 def glu_matmul_emulation_f64(xf: np.ndarray, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None) -> np.ndarray:
     """glu_emulation_f64 for packed (k, n) matrices: g = X·P̂g + bg, u = X·P̂u + bu in float64 on unpack's values, act(g) * u, before the
     final rounding."""
-    k, n = gate.rows, gate.cols
-    x64 = np.asarray(xf, dtype=np.float32).astype(np.float64)
-    sides = []
-    for pt, bias, name in ((gate, bias_gate, "bias_gate"), (up, bias_up, "bias_up")):
-        w = decode(_host_data(pt), pt.map, pt.offsets, k, n).view(np.float32)
-        with np.errstate(over="ignore", invalid="ignore"):
-            y = x64 @ w.astype(np.float64)
-        b = _host_f64(bias, (n,), name)
-        sides.append(y if b is None else y + b[None, :])
-    return _glu_host(sides[0], sides[1], act)
+    return _glu_f64(_KN, xf, gate, up, act, bias_gate, bias_up)
 
 
 def glu_matmul(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
@@ -1559,47 +1527,7 @@ def glu_matmul(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_
     the entries raises MtqError under every name: there is no fall-back.
     emulation: float64 throughout from the unpacked matrices (glu_matmul_emulation_f64), rounded once to float32 and from there to
     bf16; the same value under every kernel name."""
-    _glu_matmul_pair(gate, up, "glu_matmul")
-    _check_act(act)
-    if kernel not in GLU_KERNELS:
-        raise MtqError(f"kernel must be one of {GLU_KERNELS}, got {kernel!r}")
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    backend = backend or ("hip" if gate.on_device else "emulation")
-    k, n = gate.rows, gate.cols
-    if backend == "hip":
-        import torch
-
-        from . import hip_backend as hb
-
-        if x.dim() != 2 or x.shape[1] != k:
-            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
-        _need_matmul(hb, "glu_matmul")
-        _need_glu_matmul(hb, "glu_matmul")
-        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-        m = int(x.shape[0])
-        if kernel == "auto":
-            if AUTO_GLU_MATMUL_SKINNY_MAX_M is not None and m <= AUTO_GLU_MATMUL_SKINNY_MAX_M:
-                kernel = "skinny"
-            else:
-                kernel = "fused" if AUTO_GLU_MATMUL_FUSED_MIN_M is not None and m >= AUTO_GLU_MATMUL_FUSED_MIN_M else "unfused"
-        if kernel == "fused":
-            return hb.packed_glu_matmul_wide(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act,
-                                             bias_gate=bias_gate, bias_up=bias_up, out_dtype=dtype)
-        if kernel == "skinny":
-            _need_matmul_skinny(hb, 'glu_matmul(kernel="auto")')
-            g = hb.packed_matmul_skinny(x, _device_data(gate), gate.tables(), n, bias=bias_gate, out_dtype=torch.float32)
-            u = hb.packed_matmul_skinny(x, _device_data(up), up.tables(), n, bias=bias_up, out_dtype=torch.float32)
-        else:
-            g = hb.packed_matmul(x, _device_data(gate), gate.tables(), n, bias=bias_gate, out_dtype=torch.float32)
-            u = hb.packed_matmul(x, _device_data(up), up.tables(), n, bias=bias_up, out_dtype=torch.float32)
-        return hb.glu_combine(g, u, act=act, out_dtype=dtype)
-    if backend != "emulation":
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
-    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
-    if xf.ndim != 2 or xf.shape[1] != k:
-        raise MtqError(f"x must be (m, {k}), got {xf.shape}")
-    return _round_out(glu_matmul_emulation_f64(xf, gate, up, act, bias_gate, bias_up), out_dtype)
+    return _glu(_KN, "glu_matmul", x, gate, up, act, bias_gate, bias_up, out_dtype, backend, kernel)
 
 
 def glu_matmul_skinny(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
@@ -1610,26 +1538,7 @@ def glu_matmul_skinny(x, gate: PackedTensor, up: PackedTensor, act: str = "silu"
     packings of unpack(P̂)ᵀ.  `split` and `workspace` as in glu_skinny.  m > SKINNY_MAX_M and a library without the entry raise
     MtqError: there is no fall-back.
     emulation: glu_matmul's float64 value rounded once, whatever m and split."""
-    _glu_matmul_pair(gate, up, "glu_matmul_skinny")
-    _check_act(act)
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    backend = backend or ("hip" if gate.on_device else "emulation")
-    k, n = gate.rows, gate.cols
-    if backend == "hip":
-        import torch
-
-        from . import hip_backend as hb
-
-        if x.dim() != 2 or x.shape[1] != k:
-            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
-        _need_glu_matmul_skinny(hb, "glu_matmul_skinny")
-        if int(x.shape[0]) > SKINNY_MAX_M:
-            raise MtqError(f"glu_matmul_skinny takes m <= {SKINNY_MAX_M}, got m = {int(x.shape[0])}: glu_matmul(kernel=\"auto\") serves every m")
-        return hb.packed_glu_matmul_skinny(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, act=act, bias_gate=bias_gate,
-                                           bias_up=bias_up, out_dtype=torch.float32 if out_dtype == "float32" else torch.bfloat16, split=split,
-                                           workspace=workspace)
-    return glu_matmul(x, gate, up, act=act, bias_gate=bias_gate, bias_up=bias_up, out_dtype=out_dtype, backend=backend)
+    return _glu_skinny(_KN, "glu_matmul_skinny", x, gate, up, act, bias_gate, bias_up, out_dtype, backend, split, workspace)
 
 
 def glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
@@ -1641,8 +1550,8 @@ def glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", b
     matmul_grouped_wide calls into float32 and hip_backend.glu_combine over all T rows - the same bits on every row of a group; a row of
     no group is zero under both.  T = 0 gives (0, n) without a call.
     emulation: per group glu_matmul's float64 value, rounded once."""
-    return _glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, GLU_GROUPED_KERNELS, 0,
-                               workspace)
+    return _glu_grouped(_KN, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, GLU_GROUPED_KERNELS, 0,
+                        workspace)
 
 
 def glu_matmul_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
@@ -1653,80 +1562,8 @@ def glu_matmul_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "s
     zeros.  workspace: an optional uint8 device tensor of hip_backend.packed_glu_matmul_skinny_grouped_workspace_bytes bytes.  T = 0
     gives (0, n) without a call; a library without the entry raises MtqError: there is no fall-back.
     emulation: glu_matmul_grouped's value."""
-    return _glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, "skinny", ("skinny",), split,
-                               workspace)
-
-
-def _glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, kernels, split, workspace):
-    """glu_matmul_grouped and glu_matmul_grouped_skinny: `kernel` one of `kernels`, GLU_GROUPED_KERNELS or, from the latter alone,
-    ("skinny",)."""
-    gate_b, up_b = _resolve_batch(gate_batch), _resolve_batch(up_batch)
-    _check_act(act)
-    if kernel not in kernels:
-        raise MtqError(f"kernel must be one of {kernels}, got {kernel!r}")
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-    if (gate_b.count, gate_b.rows, gate_b.cols) != (up_b.count, up_b.rows, up_b.cols):
-        raise MtqError(f"the gate and the up batch must hold as many experts of one shape, got {gate_b.count} of {gate_b.rows}x{gate_b.cols} and "
-                       f"{up_b.count} of {up_b.rows}x{up_b.cols}")
-    backend = backend or ("hip" if _batch_on_device(gate_b) else "emulation")
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
-    count, k, n = gate_b.count, gate_b.rows, gate_b.cols
-    if len(x.shape) != 2 or x.shape[1] != k:
-        raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
-    T = int(x.shape[0])
-    on_device = _is_torch(group_rows) and bool(group_rows.is_cuda)
-    if not on_device:
-        group_rows = _host_group_rows(group_rows.numpy() if _is_torch(group_rows) else group_rows, count, T)
-    if backend == "hip":
-        import torch
-
-        from . import hip_backend as hb
-
-        if kernel == "skinny":                       # a missing kernel is refused before any device work
-            _need_glu_matmul_skinny(hb, "glu_matmul_grouped_skinny")
-        else:
-            _need_glu_matmul(hb, "glu_matmul_grouped")
-        gate_b, up_b = batch_to_device(gate_b), batch_to_device(up_b)
-        dev = gate_b.arena.device
-        dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
-        if T == 0:
-            return torch.zeros((0, n), dtype=dtype, device=dev)
-        if not on_device:
-            group_rows = torch.from_numpy(group_rows.astype(np.int32)).to(dev)
-        bias_gate, bias_up = (b if b is None or _is_torch(b) else torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(dev)
-                              for b in (bias_gate, bias_up))
-        sides = ((gate_b.arena, gate_b.maps_dev, gate_b.offsets_dev, gate_b.bases_dev), (up_b.arena, up_b.maps_dev, up_b.offsets_dev, up_b.bases_dev))
-        if kernel == "skinny":
-            return hb.packed_glu_matmul_skinny_grouped(x, group_rows, sides[0], sides[1], count, n, act=act, bias_gate=bias_gate, bias_up=bias_up,
-                                                       out_dtype=dtype, split=split, workspace=workspace)
-        if kernel == "fused":
-            return hb.packed_glu_matmul_wide_grouped(x, group_rows, sides[0], sides[1], count, n, act=act, bias_gate=bias_gate, bias_up=bias_up,
-                                                     out_dtype=dtype, workspace=workspace)
-        g = matmul_grouped_wide(x, group_rows, gate_b, bias=bias_gate, out_dtype="float32", backend="hip", workspace=workspace)
-        u = matmul_grouped_wide(x, group_rows, up_b, bias=bias_up, out_dtype="float32", backend="hip", workspace=workspace)
-        return hb.glu_combine(g, u, act=act, out_dtype=dtype)
-    xf = x.detach().to("cpu").float().numpy() if _is_torch(x) else np.asarray(x, dtype=np.float32)
-    if on_device:                                    # trusted, as on hip: what the kernel makes of it
-        if tuple(group_rows.shape) != (count + 1,):
-            raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got shape {tuple(group_rows.shape)}")
-        r0, r1 = clamp_group_rows(group_rows.cpu().numpy(), T)
-    else:
-        r0, r1 = group_rows[:-1], group_rows[1:]
-    bg, bu = _host_f64(bias_gate, (count, n), "bias_gate"), _host_f64(bias_up, (count, n), "bias_up")
-    h = np.zeros((T, n), dtype=np.float64)
-    x64 = xf.astype(np.float64)
-    for e, (tg, tu) in enumerate(zip(_batch_host_tensors(gate_b), _batch_host_tensors(up_b))):
-        if r1[e] == r0[e]:
-            continue
-        sides = []
-        for (amap, offsets, data), b in ((tg, bg), (tu, bu)):
-            w = decode(data, amap, offsets, k, n).view(np.float32)
-            y = x64[r0[e]: r1[e]] @ w.astype(np.float64)
-            sides.append(y if b is None else y + b[e][None, :])
-        h[r0[e]: r1[e]] = _glu_host(sides[0], sides[1], act)
-    return _round_out(h, out_dtype)
+    return _glu_grouped(_KN, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, "skinny", ("skinny",), split,
+                        workspace)
 
 
 # ----------------------------------------------------------------------------- MoE routing: plan, dispatch, combine
@@ -1793,11 +1630,8 @@ def moe_plan(topk_ids, count: int, backend: Optional[str] = None, workspace=None
     _moe_limits(T, K, count)
     count = int(count)
     backend = backend or ("hip" if _is_torch(topk_ids) and topk_ids.is_cuda else "emulation")
-    if backend not in BACKENDS:
-        raise MtqError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    _check_backend(backend)
     if backend == "hip":
-        from . import hip_backend as hb
-
         _need_moe(hb, "moe_plan")
         if not _is_torch(topk_ids):
             import torch
@@ -1827,8 +1661,6 @@ def moe_dispatch(x, plan: MoEPlan, out=None):
     if len(x.shape) != 2 or x.shape[0] != T:
         raise MtqError(f"x must be ({T}, k), got {tuple(x.shape)}")
     if _plan_backend(plan) == "hip":
-        from . import hip_backend as hb
-
         _need_moe(hb, "moe_dispatch")
         return hb.moe_dispatch(x, plan.src, K, out=out)
     src = np.asarray(plan.src, dtype=np.int64)
@@ -1856,8 +1688,7 @@ def moe_combine(ys, topk_weights, plan: MoEPlan, base=None, out_dtype: str = "fl
     The backend is the plan's.  hip: mtq_moe_combine, one launch; out: an optional (tokens, n) device tensor of out_dtype.
     emulation: the same sequence in NumPy's float32; a bf16 result is rounded to nearest even once."""
     T, K, S = plan.tokens, plan.topk, plan.slots
-    if out_dtype not in ("float32", "bfloat16"):
-        raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+    _check_out_dtype(out_dtype)
     if tuple(topk_weights.shape) != (T, K):
         raise MtqError(f"topk_weights must be ({T}, {K}), got {tuple(topk_weights.shape)}")
     if str(topk_weights.dtype).replace("torch.", "") != "float32":
@@ -1870,13 +1701,11 @@ def moe_combine(ys, topk_weights, plan: MoEPlan, base=None, out_dtype: str = "fl
     if _plan_backend(plan) == "hip":
         import torch
 
-        from . import hip_backend as hb
-
         _need_moe(hb, "moe_combine")
         dev = plan.row_of.device
         if not _is_torch(topk_weights):
             topk_weights = torch.from_numpy(np.ascontiguousarray(topk_weights)).to(dev)
-        return hb.moe_combine(ys, plan.row_of, topk_weights, base=base, out_dtype=torch.float32 if out_dtype == "float32" else torch.bfloat16,
+        return hb.moe_combine(ys, plan.row_of, topk_weights, base=base, out_dtype=_torch_dtype(out_dtype),
                               out=out)
 
     def host32(v):
@@ -1897,205 +1726,36 @@ def moe_combine(ys, topk_weights, plan: MoEPlan, base=None, out_dtype: str = "fl
     return y
 
 
-def _packed_mlp_class():
-    import torch
+def _named(cls, name: str):
+    """A class made by a factory under its public name and its docstring of _CLASS_DOCS."""
+    cls.__name__ = cls.__qualname__ = name
+    cls.__doc__ = _CLASS_DOCS[name]
+    return cls
 
-    class PackedMLP(torch.nn.Module):
+
+_CLASS_DOCS = {
+    "PackedMLP":
         """A gated MLP over three packed weights, down(act(gate(x)) * up(x)): gate and up (n, k), down (k_out, n).  INFERENCE ONLY, as
         PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, runs glu(kernel="auto") into bf16 and
         linear(kernel="auto") with `down`, and returns (..., k_out) in out_dtype; m = 0 gives the empty result without a call.
         decode_kernel (MLP_DECODE_KERNELS): "pair", that route at every m; "fused", m <= AUTO_SKINNY_MAX_M goes through glu_skinny
-        instead, the same bits from two launches in place of five."""
-
-        def __init__(self, gate: PackedTensor, up: PackedTensor, down: PackedTensor, act: str = "silu", out_dtype: str = "bfloat16",
-                     backend: Optional[str] = None, decode_kernel: str = "pair"):
-            super().__init__()
-            if decode_kernel not in MLP_DECODE_KERNELS:
-                raise MtqError(f"decode_kernel must be one of {MLP_DECODE_KERNELS}, got {decode_kernel!r}")
-            _glu_pair(gate, up)
-            _check_act(act)
-            _check_layout(down.layout)
-            if len(down.shape) != 2 or down.cols != gate.rows:
-                raise MtqError(f"down must be a 2-D (k_out, {gate.rows}) weight, the packed tensor is {down.shape}")
-            if out_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-            self.backend = backend or ("hip" if gate.on_device else "emulation")
-            if self.backend not in BACKENDS:
-                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
-            if self.backend == "hip":
-                from . import hip_backend as hb
-
-                _need_glu(hb, "PackedMLP")           # refused here, not at the first forward
-                if decode_kernel == "fused":
-                    _need_glu_skinny(hb, 'PackedMLP(decode_kernel="fused")')
-                for pt in (gate, up, down):
-                    _device_data(pt)
-                    pt.tables()
-            self.gate, self.up, self.down, self.act, self.out_dtype, self.decode_kernel = gate, up, down, act, out_dtype, decode_kernel
-            self.in_features, self.hidden_features, self.out_features = gate.cols, gate.rows, down.rows
-
-        def extra_repr(self) -> str:
-            return f"in_features={self.in_features}, hidden_features={self.hidden_features}, out_features={self.out_features}, " \
-                   f"act={self.act!r}, backend={self.backend!r}"
-
-        @torch.no_grad()
-        def forward(self, x):
-            if x.shape[-1] != self.in_features:
-                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
-            lead = tuple(x.shape[:-1])
-            x2 = x.reshape(-1, self.in_features)
-            if x2.shape[0] == 0:
-                return torch.zeros(lead + (self.out_features,), dtype=torch.float32 if self.out_dtype == "float32" else torch.bfloat16, device=x.device)
-            if self.decode_kernel == "fused" and x2.shape[0] <= AUTO_SKINNY_MAX_M:
-                h = glu_skinny(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend)
-            else:
-                h = glu(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="auto")
-            y = linear(h, self.down, out_dtype=self.out_dtype, backend=self.backend, kernel="auto")
-            if not _is_torch(y):
-                y = torch.from_numpy(y)
-            return y.reshape(lead + (self.out_features,))
-
-    return PackedMLP
-
-
-def _packed_experts_mlp_class():
-    import torch
-
-    class PackedExpertsMLP(torch.nn.Module):
+        instead, the same bits from two launches in place of five.""",
+    "PackedMatmulMLP":
+        """PackedMLP over three packed (k, n) matrices, as matmul takes them: gate and up (k, hidden), down (hidden, k_out) - the
+        entries of a pack_model --store-transposed directory, pack_transposed's results, input-major weights.  INFERENCE ONLY.
+        forward(x) takes bf16 (..., k), flattens the leading dimensions to m, runs glu_matmul(kernel="auto") into bf16 and
+        matmul(kernel="auto") with `down`, and returns (..., k_out) in out_dtype; m = 0 gives the empty result without a call.
+        decode_kernel (MATMUL_MLP_DECODE_KERNELS): "pair", that route at every m; "fused", m <= AUTO_GLU_MATMUL_SKINNY_MAX_M goes through
+        glu_matmul_skinny instead, the same bits from two launches in place of five.""",
+    "PackedExpertsMLP":
         """The gated MLPs of the experts of one MoE layer: three batches of `count` experts, gate and up (n, k), down (k_out, n).
         INFERENCE ONLY.  forward(x, group_rows): x (T, k) bf16, group e owning rows [group_rows[e], group_rows[e + 1]) → (T, k_out):
         glu_grouped (kernel "fused") into bf16, then linear_grouped_wide with the down batch.  The batches are resolved once, here; on hip
         the arenas, their tables and the one plan workspace both launches use stay on the device.  T = 0 gives the empty result.
         decode_max_rows: None, that route at every T; a positive number, a forward with T <= decode_max_rows goes through
         glu_grouped_skinny into bf16 and linear_grouped(kernel="walk") with the down batch instead (the skinny family's sums, which may
-        differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows."""
-
-        def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", backend: Optional[str] = None,
-                     decode_max_rows: Optional[int] = None):
-            super().__init__()
-            _check_act(act)
-            if decode_max_rows is not None and (isinstance(decode_max_rows, bool) or not isinstance(decode_max_rows, int) or decode_max_rows <= 0):
-                raise MtqError(f"decode_max_rows must be None or a positive int, got {decode_max_rows!r}")
-            if out_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-            gate, up, down = (_resolve_batch(b) for b in (gate_pts, up_pts, down_pts))
-            if (gate.count, gate.rows, gate.cols) != (up.count, up.rows, up.cols):
-                raise MtqError("the gate and the up batch must hold as many experts of one shape")
-            if down.count != gate.count or down.cols != gate.rows:
-                raise MtqError(f"the down batch must hold {gate.count} experts of (k_out, {gate.rows}), got {down.count} of {down.rows}x{down.cols}")
-            self.backend = backend or ("hip" if _batch_on_device(gate) else "emulation")
-            if self.backend not in BACKENDS:
-                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
-            self._workspace = None
-            self._decode_workspace = None
-            if self.backend == "hip":
-                from . import hip_backend as hb
-
-                _need_glu(hb, "PackedExpertsMLP")    # refused here, not at the first forward
-                if decode_max_rows is not None:
-                    _need_glu_skinny(hb, "PackedExpertsMLP(decode_max_rows=...)")
-                if not hb.has_packed_linear_wide_grouped():
-                    raise MtqError("PackedExpertsMLP needs mtq_packed_linear_wide_grouped, which this build of libmtq_hip.so lacks")
-                gate, up, down = (batch_to_device(b) for b in (gate, up, down))
-                need = hb.packed_glu_wide_grouped_workspace_bytes(1, gate.count, gate.rows, gate.cols)   # a function of count alone
-                self._workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
-                if decode_max_rows is not None:      # one buffer for both decode launches: each is done with it before the next starts
-                    need = max(hb.packed_glu_skinny_grouped_workspace_bytes(decode_max_rows, gate.count, gate.rows, gate.cols),
-                               hb.packed_linear_skinny_grouped_workspace_bytes(decode_max_rows, down.count, down.rows, down.cols))
-                    self._decode_workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
-            self.decode_max_rows = decode_max_rows
-            self.gate, self.up, self.down, self.act, self.out_dtype = gate, up, down, act, out_dtype
-            self.count, self.in_features, self.hidden_features, self.out_features = gate.count, gate.cols, gate.rows, down.rows
-
-        def extra_repr(self) -> str:
-            return f"count={self.count}, in_features={self.in_features}, hidden_features={self.hidden_features}, " \
-                   f"out_features={self.out_features}, act={self.act!r}, backend={self.backend!r}"
-
-        @torch.no_grad()
-        def forward(self, x, group_rows):
-            if x.dim() != 2 or x.shape[1] != self.in_features:
-                raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
-            if self.decode_max_rows is not None and x.shape[0] <= self.decode_max_rows:
-                h = glu_grouped_skinny(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend,
-                                       workspace=self._decode_workspace)
-                y = linear_grouped(h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend, workspace=self._decode_workspace,
-                                   kernel="walk")
-                return y if _is_torch(y) else torch.from_numpy(y)
-            h = glu_grouped(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="fused",
-                            workspace=self._workspace)
-            y = linear_grouped_wide(h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend, workspace=self._workspace)
-            return y if _is_torch(y) else torch.from_numpy(y)
-
-    return PackedExpertsMLP
-
-
-def _packed_matmul_mlp_class():
-    import torch
-
-    class PackedMatmulMLP(torch.nn.Module):
-        """PackedMLP over three packed (k, n) matrices, as matmul takes them: gate and up (k, hidden), down (hidden, k_out) - the
-        entries of a pack_model --store-transposed directory, pack_transposed's results, input-major weights.  INFERENCE ONLY.
-        forward(x) takes bf16 (..., k), flattens the leading dimensions to m, runs glu_matmul(kernel="auto") into bf16 and
-        matmul(kernel="auto") with `down`, and returns (..., k_out) in out_dtype; m = 0 gives the empty result without a call.
-        decode_kernel (MATMUL_MLP_DECODE_KERNELS): "pair", that route at every m; "fused", m <= AUTO_GLU_MATMUL_SKINNY_MAX_M goes through
-        glu_matmul_skinny instead, the same bits from two launches in place of five."""
-
-        def __init__(self, gate_kn: PackedTensor, up_kn: PackedTensor, down_kn: PackedTensor, act: str = "silu", out_dtype: str = "bfloat16",
-                     backend: Optional[str] = None, decode_kernel: str = "pair"):
-            super().__init__()
-            if decode_kernel not in MATMUL_MLP_DECODE_KERNELS:
-                raise MtqError(f"decode_kernel must be one of {MATMUL_MLP_DECODE_KERNELS}, got {decode_kernel!r}")
-            _glu_matmul_pair(gate_kn, up_kn, "PackedMatmulMLP")
-            _check_act(act)
-            _check_layout(down_kn.layout)
-            if len(down_kn.shape) != 2 or down_kn.rows != gate_kn.cols:
-                raise MtqError(f"down must be a 2-D ({gate_kn.cols}, k_out) matrix, the packed tensor is {down_kn.shape}")
-            if out_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-            self.backend = backend or ("hip" if gate_kn.on_device else "emulation")
-            if self.backend not in BACKENDS:
-                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
-            if self.backend == "hip":
-                from . import hip_backend as hb
-
-                _need_matmul(hb, "PackedMatmulMLP")  # refused here, not at the first forward
-                _need_glu_matmul(hb, "PackedMatmulMLP")
-                if decode_kernel == "fused":
-                    _need_glu_matmul_skinny(hb, 'PackedMatmulMLP(decode_kernel="fused")')
-                for pt in (gate_kn, up_kn, down_kn):
-                    _device_data(pt)
-                    pt.tables()
-            self.gate, self.up, self.down, self.act, self.out_dtype, self.decode_kernel = gate_kn, up_kn, down_kn, act, out_dtype, decode_kernel
-            self.in_features, self.hidden_features, self.out_features = gate_kn.rows, gate_kn.cols, down_kn.cols
-
-        def extra_repr(self) -> str:
-            return f"in_features={self.in_features}, hidden_features={self.hidden_features}, out_features={self.out_features}, " \
-                   f"act={self.act!r}, backend={self.backend!r}"
-
-        @torch.no_grad()
-        def forward(self, x):
-            if x.shape[-1] != self.in_features:
-                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
-            lead = tuple(x.shape[:-1])
-            x2 = x.reshape(-1, self.in_features)
-            if x2.shape[0] == 0:
-                return torch.zeros(lead + (self.out_features,), dtype=torch.float32 if self.out_dtype == "float32" else torch.bfloat16, device=x.device)
-            if self.decode_kernel == "fused" and AUTO_GLU_MATMUL_SKINNY_MAX_M is not None and x2.shape[0] <= AUTO_GLU_MATMUL_SKINNY_MAX_M:
-                h = glu_matmul_skinny(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend)
-            else:
-                h = glu_matmul(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="auto")
-            y = matmul(h, self.down, out_dtype=self.out_dtype, backend=self.backend, kernel="auto")
-            if not _is_torch(y):
-                y = torch.from_numpy(y)
-            return y.reshape(lead + (self.out_features,))
-
-    return PackedMatmulMLP
-
-
-def _packed_experts_matmul_mlp_class():
-    import torch
-
-    class PackedExpertsMatmulMLP(torch.nn.Module):
+        differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows.""",
+    "PackedExpertsMatmulMLP":
         """PackedExpertsMLP over three batches of `count` (k, n) experts, as matmul_grouped takes them: gate and up (k, hidden), down
         (hidden, k_out) - pack_batch_transposed lists, or as_batch of a pack_model --store-transposed directory's entries.  INFERENCE
         ONLY.  forward(x, group_rows): x (T, k) bf16 → (T, k_out): glu_matmul_grouped (kernel "fused") into bf16, then
@@ -2103,44 +1763,152 @@ def _packed_experts_matmul_mlp_class():
         workspace both launches use stay on the device.  T = 0 gives the empty result.
         decode_max_rows: None, that route at every T; a positive number, a forward with T <= decode_max_rows goes through
         glu_matmul_grouped_skinny into bf16 and matmul_grouped(kernel="walk") with the down batch instead (the skinny family's sums,
-        which may differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows."""
+        which may differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows.""",
+    "PackedLinear":
+        """A linear layer over a packed (n, k) weight.  INFERENCE ONLY: the kernels have no backward, no gradient reaches x, the weight
+        or the bias.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through linear() with
+        `kernel` ("auto": the skinny split-K kernel for decode-sized m, the block kernel above, the wide-block kernel with the same
+        bits from AUTO_WIDE_MIN_M on) and returns (..., n) in out_dtype.
+        hip: the tables, the bias and a workspace sized for every m <= 32 stay on the device across calls, so a decode step
+        allocates only its output.  emulation: CPU tensors, the float64 product (for use without a GPU).""",
+    "PackedMatmul":
+        """x @ P̂ + b over a packed (k, n) matrix (pack of an input-major weight, or pack_transposed of an (n, k) one).  INFERENCE ONLY,
+        as PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through matmul() and returns
+        (..., n) in out_dtype.  hip: the tables and the bias stay on the device across calls; a library without mtq_packed_matmul is
+        refused here, not at the first forward.  emulation: CPU tensors, the float64 product.
+        kernel: matmul's, "block" by default.  With "skinny" or "auto" on hip one workspace, sized for m = 32 at the library's split,
+        stays on the device across calls (its contents never need initialising), so a decode step allocates only its output;
+        "skinny" on a library without mtq_packed_matmul_skinny is refused here.""",
+    "PackedExperts":
+        """The experts of one batch as a module.  INFERENCE ONLY, as PackedLinear.  forward(x, group_rows): x (T, k), group e owning
+        rows [group_rows[e], group_rows[e + 1]) → (T, n) through linear_grouped.  The batch is made once, here (as_batch for a list), and
+        every forward multiplies with that arena: hip: the arena, its tables and the bias stay on the device, no host work per expert
+        and no synchronisation in forward (with a device group_rows), and the workspace grows to the largest T seen.  emulation: CPU tensors, the float64 product.
+        kernel: as linear_grouped's, resolved here; the kept workspace is sized by the size function of the kernel in use.
+        wide_min_rows: None (the default: every call goes through linear_grouped), or an int: a forward whose x has T >= wide_min_rows
+        rows goes through linear_grouped_wide, the wide-block kernel for experts with hundreds of rows (T is known on the host: no
+        synchronisation); its plan workspace is allocated once, here, and is the one kept workspace of both routes.  Crossing the threshold changes the summation order (the block
+        family's bits above it, the skinny family's below), so the last bits of a row may differ between a call below and a call at or
+        above it.  DESIGN.md §A.6n has the measurement that informs the choice of a value.""",
+    "PackedExpertsMatmul":
+        """PackedExperts for (k, n) experts: the batch is what matmul_grouped takes, in_features = batch.rows, out_features = batch.cols.
+        INFERENCE ONLY.  forward(x, group_rows): x (T, k) → (T, n) through matmul_grouped, or, with wide_min_rows set and
+        T >= wide_min_rows, through matmul_grouped_wide (the block family's bits above the threshold, the skinny family's below).  The
+        batch is made once, here; hip: the arena, its tables, the bias and ONE kept workspace stay on the device (the plan's bytes from
+        the start when wide_min_rows is set, grown to the largest need seen).  A library without the symbols of `kernel`, or of the wide
+        kernel when wide_min_rows is set, is refused here, not at the first forward.""",
+}
 
+
+def _as_torch(y):
+    if _is_torch(y):
+        return y
+    import torch
+
+    return torch.from_numpy(y)
+
+
+def _mlp_class(o: _Orientation, name: str):
+    """PackedMLP and PackedMatmulMLP."""
+    import torch
+
+    def init(self, gate, up, down, act, out_dtype, backend, decode_kernel):
+        torch.nn.Module.__init__(self)
+        decode_kernels = globals()[o.mlp_decode_kernels]
+        if decode_kernel not in decode_kernels:
+            raise MtqError(f"decode_kernel must be one of {decode_kernels}, got {decode_kernel!r}")
+        _check_pair(o, gate, up, name)
+        _check_act(act)
+        _check_layout(down.layout)
+        n, k = o.n_k(gate)
+        if len(down.shape) != 2 or o.n_k(down)[1] != n:
+            raise MtqError(f"down must be a 2-D {o.down_shape.format(n=n)} {o.noun}, the packed tensor is {down.shape}")
+        _check_out_dtype(out_dtype)
+        self.backend = backend or ("hip" if gate.on_device else "emulation")
+        _check_backend(self.backend)
+        if self.backend == "hip":
+            _needs(o.need_glu, hb, name)             # refused here, not at the first forward
+            if decode_kernel == "fused":
+                _needs(o.need_glu_skinny, hb, f'{name}(decode_kernel="fused")')
+            for pt in (gate, up, down):
+                _device_data(pt)
+                pt.tables()
+        self.gate, self.up, self.down, self.act, self.out_dtype, self.decode_kernel = gate, up, down, act, out_dtype, decode_kernel
+        self.in_features, self.hidden_features, self.out_features = k, n, o.n_k(down)[0]
+
+    class MLP(torch.nn.Module):
+        if o.kn:
+            def __init__(self, gate_kn: PackedTensor, up_kn: PackedTensor, down_kn: PackedTensor, act: str = "silu", out_dtype: str = "bfloat16",
+                         backend: Optional[str] = None, decode_kernel: str = "pair"):
+                init(self, gate_kn, up_kn, down_kn, act, out_dtype, backend, decode_kernel)
+        else:
+            def __init__(self, gate: PackedTensor, up: PackedTensor, down: PackedTensor, act: str = "silu", out_dtype: str = "bfloat16",
+                         backend: Optional[str] = None, decode_kernel: str = "pair"):
+                init(self, gate, up, down, act, out_dtype, backend, decode_kernel)
+
+        def extra_repr(self) -> str:
+            return f"in_features={self.in_features}, hidden_features={self.hidden_features}, out_features={self.out_features}, " \
+                   f"act={self.act!r}, backend={self.backend!r}"
+
+        @torch.no_grad()
+        def forward(self, x):
+            if x.shape[-1] != self.in_features:
+                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
+            lead = tuple(x.shape[:-1])
+            x2 = x.reshape(-1, self.in_features)
+            if x2.shape[0] == 0:
+                return torch.zeros(lead + (self.out_features,), dtype=_torch_dtype(self.out_dtype), device=x.device)
+            if self.decode_kernel == "fused" and _at_most(o, o.glu_auto_skinny_max_m, x2.shape[0]):
+                h = globals()[o.glu_skinny](x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend)
+            else:
+                h = globals()[o.glu](x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="auto")
+            y = globals()[o.product](h, self.down, out_dtype=self.out_dtype, backend=self.backend, kernel="auto")
+            return _as_torch(y).reshape(lead + (self.out_features,))
+
+    return _named(MLP, name)
+
+
+def _experts_mlp_class(o: _Orientation, name: str):
+    """PackedExpertsMLP and PackedExpertsMatmulMLP."""
+    import torch
+
+    class ExpertsMLP(torch.nn.Module):
         def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", backend: Optional[str] = None,
                      decode_max_rows: Optional[int] = None):
             super().__init__()
             _check_act(act)
             if decode_max_rows is not None and (isinstance(decode_max_rows, bool) or not isinstance(decode_max_rows, int) or decode_max_rows <= 0):
                 raise MtqError(f"decode_max_rows must be None or a positive int, got {decode_max_rows!r}")
-            if out_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            _check_out_dtype(out_dtype)
             gate, up, down = (_resolve_batch(b) for b in (gate_pts, up_pts, down_pts))
             if (gate.count, gate.rows, gate.cols) != (up.count, up.rows, up.cols):
                 raise MtqError("the gate and the up batch must hold as many experts of one shape")
-            if down.count != gate.count or down.rows != gate.cols:
-                raise MtqError(f"the down batch must hold {gate.count} experts of ({gate.cols}, k_out), got {down.count} of {down.rows}x{down.cols}")
+            (n, k), (n_down, k_down) = o.n_k(gate), o.n_k(down)
+            if down.count != gate.count or k_down != n:
+                raise MtqError(f"the down batch must hold {gate.count} experts of {o.down_shape.format(n=n)}, got {down.count} of {down.rows}x{down.cols}")
             self.backend = backend or ("hip" if _batch_on_device(gate) else "emulation")
-            if self.backend not in BACKENDS:
-                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            _check_backend(self.backend)
             self._workspace = None
             self._decode_workspace = None
             if self.backend == "hip":
-                from . import hip_backend as hb
-
-                _need_glu_matmul(hb, "PackedExpertsMatmulMLP")   # refused here, not at the first forward
-                _matmul_grouped_entries("wide")
+                _needs(o.need_glu_grouped, hb, name)             # refused here, not at the first forward
+                if not o.experts_mlp_wide_last:
+                    _grouped_entry(o, hb, "wide")
                 if decode_max_rows is not None:
-                    _need_glu_matmul_skinny(hb, "PackedExpertsMatmulMLP(decode_max_rows=...)")
-                    _matmul_grouped_entries("walk")
+                    _needs(o.need_glu_skinny, hb, f"{name}(decode_max_rows=...)")
+                    _grouped_entry(o, hb, "walk")
+                if o.experts_mlp_wide_last and not getattr(hb, o.hb_grouped["wide"][2])():
+                    raise MtqError(f"{name} needs {o.hb_grouped['wide'][4]}, which this build of libmtq_hip.so lacks")
                 gate, up, down = (batch_to_device(b) for b in (gate, up, down))
-                need = hb.packed_glu_matmul_wide_grouped_workspace_bytes(1, gate.count, gate.cols, gate.rows)   # a function of count alone
+                need = getattr(hb, o.hb_glu_grouped_fused_size)(1, gate.count, n, k)   # a function of count alone
                 self._workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
                 if decode_max_rows is not None:      # one buffer for both decode launches: each is done with it before the next starts
-                    need = max(hb.packed_glu_matmul_skinny_grouped_workspace_bytes(decode_max_rows, gate.count, gate.cols, gate.rows),
-                               hb.packed_matmul_skinny_grouped_workspace_bytes(decode_max_rows, down.count, down.cols, down.rows))
+                    need = max(getattr(hb, o.hb_glu_grouped_skinny_size)(decode_max_rows, gate.count, n, k),
+                               getattr(hb, o.hb_grouped["walk"][1])(decode_max_rows, down.count, n_down, k_down))
                     self._decode_workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
             self.decode_max_rows = decode_max_rows
             self.gate, self.up, self.down, self.act, self.out_dtype = gate, up, down, act, out_dtype
-            self.count, self.in_features, self.hidden_features, self.out_features = gate.count, gate.rows, gate.cols, down.cols
+            self.count, self.in_features, self.hidden_features, self.out_features = gate.count, k, n, n_down
 
         def extra_repr(self) -> str:
             return f"count={self.count}, in_features={self.in_features}, hidden_features={self.hidden_features}, " \
@@ -2151,17 +1919,16 @@ def _packed_experts_matmul_mlp_class():
             if x.dim() != 2 or x.shape[1] != self.in_features:
                 raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
             if self.decode_max_rows is not None and x.shape[0] <= self.decode_max_rows:
-                h = glu_matmul_grouped_skinny(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend,
-                                              workspace=self._decode_workspace)
-                y = matmul_grouped(h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend, workspace=self._decode_workspace,
-                                   kernel="walk")
-                return y if _is_torch(y) else torch.from_numpy(y)
-            h = glu_matmul_grouped(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="fused",
-                                   workspace=self._workspace)
-            y = matmul_grouped_wide(h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend, workspace=self._workspace)
-            return y if _is_torch(y) else torch.from_numpy(y)
+                h = globals()[o.glu_grouped_skinny](x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend,
+                                                    workspace=self._decode_workspace)
+                return _as_torch(globals()[o.grouped](h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend,
+                                                      workspace=self._decode_workspace, kernel="walk"))
+            h = globals()[o.glu_grouped](x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="fused",
+                                         workspace=self._workspace)
+            return _as_torch(globals()[o.grouped_wide](h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend,
+                                                       workspace=self._workspace))
 
-    return PackedExpertsMatmulMLP
+    return _named(ExpertsMLP, name)
 
 
 MOE_PLAN_TOPK = 8   # PackedMoE sizes its first plan workspace for max_tokens tokens of this many slots each; a larger call regrows it
@@ -2190,10 +1957,8 @@ def _packed_moe_class():
             super().__init__()
             if stored not in MOE_STORED:
                 raise MtqError(f"stored must be one of {MOE_STORED}, got {stored!r}")
-            if out_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-            if expert_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"expert_dtype must be 'float32' or 'bfloat16', got {expert_dtype!r}")
+            _check_out_dtype(out_dtype)
+            _check_out_dtype(expert_dtype, "expert_dtype")
             if isinstance(max_tokens, bool) or not isinstance(max_tokens, int) or max_tokens <= 0:
                 raise MtqError(f"max_tokens must be a positive int, got {max_tokens!r}")
             experts_name = "PackedExpertsMLP" if stored == "rows" else "PackedExpertsMatmulMLP"
@@ -2206,8 +1971,6 @@ def _packed_moe_class():
                 raise MtqError(f"PackedMoE takes at most {MOE_MAX_EXPERTS} experts, got {self.count}")
             self._plan_workspace = None
             if self.backend == "hip":
-                from . import hip_backend as hb
-
                 _need_moe(hb, "PackedMoE")           # refused here, not at the first forward
                 need = hb.moe_plan_workspace_bytes(max_tokens, MOE_PLAN_TOPK, self.count)
                 self._plan_workspace = torch.empty((need,), dtype=torch.uint8, device=self.experts.gate.arena.device)
@@ -2230,10 +1993,8 @@ def _packed_moe_class():
             x2 = x.reshape(-1, self.in_features)
             T = int(x2.shape[0])
             if T == 0:
-                return torch.zeros(lead + (self.out_features,), dtype=torch.float32 if self.out_dtype == "float32" else torch.bfloat16, device=x.device)
+                return torch.zeros(lead + (self.out_features,), dtype=_torch_dtype(self.out_dtype), device=x.device)
             if self.backend == "hip":
-                from . import hip_backend as hb
-
                 need = hb.moe_plan_workspace_bytes(T, K, self.count)
                 if self._plan_workspace.numel() < need:
                     self._plan_workspace = torch.empty((need,), dtype=torch.uint8, device=self._plan_workspace.device)
@@ -2243,7 +2004,7 @@ def _packed_moe_class():
                 ys = self.experts(xs, plan.group_rows)               # all S rows: the rows from R on belong to no group and stay zero
             else:                                                    # a host group_rows ends at the rows it is given: the first R
                 R = int(plan.group_rows[-1])
-                ys = torch.zeros((plan.slots, self.out_features), dtype=torch.float32 if self.expert_dtype == "float32" else torch.bfloat16)
+                ys = torch.zeros((plan.slots, self.out_features), dtype=_torch_dtype(self.expert_dtype))
                 ys[:R] = self.experts(xs[:R], plan.group_rows)
             y = moe_combine(ys, topk_weights.reshape(T, K), plan, base=None if base is None else base.reshape(T, self.out_features),
                             out_dtype=self.out_dtype)
@@ -2254,250 +2015,94 @@ def _packed_moe_class():
     return PackedMoE
 
 
-def _packed_linear_class():
+def _product_class(o: _Orientation, name: str):
+    """PackedLinear and PackedMatmul."""
     import torch
 
-    class PackedLinear(torch.nn.Module):
-        """A linear layer over a packed (n, k) weight.  INFERENCE ONLY: the kernels have no backward, no gradient reaches x, the weight
-        or the bias.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through linear() with
-        `kernel` ("auto": the skinny split-K kernel for decode-sized m, the block kernel above, the wide-block kernel with the same
-        bits from AUTO_WIDE_MIN_M on) and returns (..., n) in out_dtype.
-        hip: the tables, the bias and a workspace sized for every m <= 32 stay on the device across calls, so a decode step
-        allocates only its output.  emulation: CPU tensors, the float64 product (for use without a GPU)."""
-
-        def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", kernel: str = "auto", backend: Optional[str] = None):
-            super().__init__()
-            _check_layout(pt.layout)
-            if len(pt.shape) != 2:
-                raise MtqError(f"PackedLinear needs a 2-D (n, k) weight, the packed tensor is {pt.shape}")
-            if kernel not in KERNELS:
-                raise MtqError(f"kernel must be one of {KERNELS}, got {kernel!r}")
-            if out_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-            self.backend = backend or ("hip" if pt.on_device else "emulation")
-            if self.backend not in BACKENDS:
-                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
-            self.packed, self.kernel, self.out_dtype = pt, kernel, out_dtype
-            self.out_features, self.in_features = pt.rows, pt.cols
-            self._workspace = None
-            if bias is not None and not _is_torch(bias):
-                bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
-            if self.backend == "hip":
-                from . import hip_backend as hb
-
-                data = _device_data(pt)
-                pt.tables()
-                if bias is not None:
-                    bias = bias.detach().to(device=data.device, dtype=torch.float32).contiguous()
-                if kernel != "block":
-                    need = max(hb.packed_linear_skinny_workspace_bytes(m, pt.rows, pt.cols) for m in range(1, SKINNY_MAX_M + 1))
-                    self._workspace = torch.empty((need,), dtype=torch.uint8, device=data.device) if need else None
-            self.register_buffer("bias", None if bias is None else bias.detach(), persistent=False)
-
-        def extra_repr(self) -> str:
-            return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, kernel={self.kernel!r}, " \
-                   f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}"
-
-        @torch.no_grad()
-        def forward(self, x):
-            if x.shape[-1] != self.in_features:
-                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
-            lead = tuple(x.shape[:-1])
-            x2 = x.reshape(-1, self.in_features)
-            dtype = torch.float32 if self.out_dtype == "float32" else torch.bfloat16
-            if x2.shape[0] == 0:
-                return torch.zeros(lead + (self.out_features,), dtype=dtype, device=x.device)
-            y = linear(x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel,
-                       workspace=self._workspace)
-            if not _is_torch(y):
-                y = torch.from_numpy(y)
-            return y.reshape(lead + (self.out_features,))
-
-    return PackedLinear
-
-
-def _packed_matmul_class():
-    import torch
-
-    class PackedMatmul(torch.nn.Module):
-        """x @ P̂ + b over a packed (k, n) matrix (pack of an input-major weight, or pack_transposed of an (n, k) one).  INFERENCE ONLY,
-        as PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through matmul() and returns
-        (..., n) in out_dtype.  hip: the tables and the bias stay on the device across calls; a library without mtq_packed_matmul is
-        refused here, not at the first forward.  emulation: CPU tensors, the float64 product.
-        kernel: matmul's, "block" by default.  With "skinny" or "auto" on hip one workspace, sized for m = 32 at the library's split,
-        stays on the device across calls (its contents never need initialising), so a decode step allocates only its output;
-        "skinny" on a library without mtq_packed_matmul_skinny is refused here."""
-
-        def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block"):
-            super().__init__()
-            _check_kn(pt, "PackedMatmul")
-            if kernel not in MATMUL_KERNELS:
-                raise MtqError(f"kernel must be one of {MATMUL_KERNELS}, got {kernel!r}")
-            if out_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-            self.backend = backend or ("hip" if pt.on_device else "emulation")
-            if self.backend not in BACKENDS:
-                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
-            self.packed, self.out_dtype, self.kernel = pt, out_dtype, kernel
-            self.in_features, self.out_features = pt.rows, pt.cols
-            self._workspace = None
-            if bias is not None and not _is_torch(bias):
-                bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
-            if self.backend == "hip":
-                from . import hip_backend as hb
-
-                _need_matmul(hb, "PackedMatmul")
-                if kernel == "skinny":
-                    _need_matmul_skinny(hb, 'PackedMatmul(kernel="skinny")')
-                data = _device_data(pt)
-                pt.tables()
-                if bias is not None:
-                    bias = bias.detach().to(device=data.device, dtype=torch.float32).contiguous()
-                if kernel != "block" and hb.has_packed_matmul_skinny():
-                    need = hb.packed_matmul_skinny_workspace_bytes(SKINNY_MAX_M, pt.cols, pt.rows)   # monotone in m: serves every m <= 32
-                    self._workspace = torch.empty((need,), dtype=torch.uint8, device=data.device) if need else None
-            self.register_buffer("bias", None if bias is None else bias.detach(), persistent=False)
-
-        def extra_repr(self) -> str:
-            return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, kernel={self.kernel!r}, " \
-                   f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}"
-
-        @torch.no_grad()
-        def forward(self, x):
-            if x.shape[-1] != self.in_features:
-                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
-            lead = tuple(x.shape[:-1])
-            x2 = x.reshape(-1, self.in_features)
-            dtype = torch.float32 if self.out_dtype == "float32" else torch.bfloat16
-            if x2.shape[0] == 0:
-                return torch.zeros(lead + (self.out_features,), dtype=dtype, device=x.device)
-            y = matmul(x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel,
-                       workspace=self._workspace)
-            if not _is_torch(y):
-                y = torch.from_numpy(y)
-            return y.reshape(lead + (self.out_features,))
-
-    return PackedMatmul
-
-
-def _packed_experts_class():
-    import torch
-
-    class PackedExperts(torch.nn.Module):
-        """The experts of one batch as a module.  INFERENCE ONLY, as PackedLinear.  forward(x, group_rows): x (T, k), group e owning
-        rows [group_rows[e], group_rows[e + 1]) → (T, n) through linear_grouped.  The batch is made once, here (as_batch for a list), and
-        every forward multiplies with that arena: hip: the arena, its tables and the bias stay on the device, no host work per expert
-        and no synchronisation in forward (with a device group_rows), and the workspace grows to the largest T seen.  emulation: CPU tensors, the float64 product.
-        kernel: as linear_grouped's, resolved here; the kept workspace is sized by the size function of the kernel in use.
-        wide_min_rows: None (the default: every call goes through linear_grouped), or an int: a forward whose x has T >= wide_min_rows
-        rows goes through linear_grouped_wide, the wide-block kernel for experts with hundreds of rows (T is known on the host: no
-        synchronisation); its plan workspace is allocated once, here, and is the one kept workspace of both routes.  Crossing the threshold changes the summation order (the block
-        family's bits above it, the skinny family's below), so the last bits of a row may differ between a call below and a call at or
-        above it.  DESIGN.md §A.6n has the measurement that informs the choice of a value."""
-
-        def __init__(self, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
-                     kernel: str = "walk", wide_min_rows: Optional[int] = None):
-            super().__init__()
-            self.kernel = _grouped_kernel(kernel)
-            if wide_min_rows is not None and (isinstance(wide_min_rows, bool) or not isinstance(wide_min_rows, (int, np.integer)) or wide_min_rows < 0):
-                raise MtqError(f"wide_min_rows must be None or a non-negative int, got {wide_min_rows!r}")
-            self.wide_min_rows = None if wide_min_rows is None else int(wide_min_rows)
-            if out_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
-            batch = _resolve_batch(pts_or_batch)                # once: forward hands the batch down and walks no list
-            self.backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
-            if self.backend not in BACKENDS:
-                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
-            if self.backend == "hip":
-                if self.kernel != "walk":
-                    _grouped_entries(self.kernel)   # a library without the kernel is refused here, not at the first forward
-                if self.wide_min_rows is not None:
-                    from . import hip_backend as hb
-
-                    if not hb.has_packed_linear_wide_grouped():
-                        raise MtqError("wide_min_rows needs mtq_packed_linear_wide_grouped, which this build of libmtq_hip.so lacks: rebuild "
-                                       "it from this tree, or leave wide_min_rows None")
-                batch = batch_to_device(batch)
-            self.batch = batch
-            self.out_dtype, self.split = out_dtype, int(split)
-            self.count, self.out_features, self.in_features = batch.count, batch.rows, batch.cols
-            self._workspace = None
-            if self.backend == "hip" and self.wide_min_rows is not None:
-                from . import hip_backend as hb
-
-                need = hb.packed_linear_wide_grouped_workspace_bytes(1, self.count, self.out_features, self.in_features)   # count alone
-                self._workspace = torch.empty((need,), dtype=torch.uint8, device=batch.arena.device)   # only ever replaced by a larger one
+    def init(self, pt, bias, out_dtype, kernel, backend):
+        torch.nn.Module.__init__(self)
+        _check_rank2(o, pt, name)
+        _check_kernel(kernel, globals()[o.kernels])
+        _check_out_dtype(out_dtype)
+        self.backend = backend or ("hip" if pt.on_device else "emulation")
+        _check_backend(self.backend)
+        self.packed, self.kernel, self.out_dtype = pt, kernel, out_dtype
+        self.out_features, self.in_features = o.n_k(pt)
+        self._workspace = None
+        if bias is not None and not _is_torch(bias):
+            bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
+        if self.backend == "hip":
+            _needs(o.module_needs, hb, name)
+            if kernel == "skinny":
+                _needs(o.need_skinny, hb, f'{name}(kernel="skinny")')
+            data = _device_data(pt)
+            pt.tables()
             if bias is not None:
-                if not _is_torch(bias):
-                    bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
-                if tuple(bias.shape) != (self.count, self.out_features):
-                    raise MtqError(f"bias must be ({self.count}, {self.out_features}), got {tuple(bias.shape)}")
-                bias = bias.detach().to(device=batch.arena.device if self.backend == "hip" else "cpu", dtype=torch.float32).contiguous()
-            self.register_buffer("bias", bias, persistent=False)
+                bias = bias.detach().to(device=data.device, dtype=torch.float32).contiguous()
+            if kernel != "block" and (o.module_size_every_m or getattr(hb, o.has_auto_skinny)()):
+                size, (n, k) = getattr(hb, o.hb_skinny_size), o.n_k(pt)
+                # every m <= 32, or m = 32 alone (monotone in m: serves every m <= 32)
+                need = max(size(m, n, k) for m in (range(1, SKINNY_MAX_M + 1) if o.module_size_every_m else (SKINNY_MAX_M,)))
+                self._workspace = torch.empty((need,), dtype=torch.uint8, device=data.device) if need else None
+        self.register_buffer("bias", None if bias is None else bias.detach(), persistent=False)
+
+    class Product(torch.nn.Module):
+        if o.kn:
+            def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block"):
+                init(self, pt, bias, out_dtype, kernel, backend)
+        else:
+            def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", kernel: str = "auto", backend: Optional[str] = None):
+                init(self, pt, bias, out_dtype, kernel, backend)
 
         def extra_repr(self) -> str:
-            return f"count={self.count}, in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, " \
-                   f"backend={self.backend!r}, split={self.split}" + ("" if self.kernel == "walk" else f", kernel={self.kernel!r}") + \
-                   ("" if self.wide_min_rows is None else f", wide_min_rows={self.wide_min_rows}")
+            return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, kernel={self.kernel!r}, " \
+                   f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}"
 
         @torch.no_grad()
-        def forward(self, x, group_rows):
-            if x.dim() != 2 or x.shape[1] != self.in_features:
-                raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
-            T = int(x.shape[0])
-            if self.wide_min_rows is not None and T >= self.wide_min_rows:
-                y = linear_grouped_wide(x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend,
-                                        workspace=self._workspace)
-                return y if _is_torch(y) else torch.from_numpy(y)
-            if self.backend == "hip" and T:
-                from . import hip_backend as hb
+        def forward(self, x):
+            if x.shape[-1] != self.in_features:
+                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
+            lead = tuple(x.shape[:-1])
+            x2 = x.reshape(-1, self.in_features)
+            if x2.shape[0] == 0:
+                return torch.zeros(lead + (self.out_features,), dtype=_torch_dtype(self.out_dtype), device=x.device)
+            y = globals()[o.product](x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel,
+                                     workspace=self._workspace)
+            return _as_torch(y).reshape(lead + (self.out_features,))
 
-                size = hb.packed_linear_skinny_grouped_workspace_bytes if self.kernel == "walk" else _grouped_entries(self.kernel)[1]
-                need = size(T, self.count, self.out_features, self.in_features, self.split)
-                if need and (self._workspace is None or self._workspace.numel() < need):
-                    self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.batch.arena.device)
-            y = linear_grouped(x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype,
-                               backend=self.backend, split=self.split, workspace=self._workspace, kernel=self.kernel)
-            return y if _is_torch(y) else torch.from_numpy(y)
-
-    return PackedExperts
+    return _named(Product, name)
 
 
-def _packed_experts_matmul_class():
+def _experts_class(o: _Orientation, name: str):
+    """PackedExperts and PackedExpertsMatmul."""
     import torch
 
-    class PackedExpertsMatmul(torch.nn.Module):
-        """PackedExperts for (k, n) experts: the batch is what matmul_grouped takes, in_features = batch.rows, out_features = batch.cols.
-        INFERENCE ONLY.  forward(x, group_rows): x (T, k) → (T, n) through matmul_grouped, or, with wide_min_rows set and
-        T >= wide_min_rows, through matmul_grouped_wide (the block family's bits above the threshold, the skinny family's below).  The
-        batch is made once, here; hip: the arena, its tables, the bias and ONE kept workspace stay on the device (the plan's bytes from
-        the start when wide_min_rows is set, grown to the largest need seen).  A library without the symbols of `kernel`, or of the wide
-        kernel when wide_min_rows is set, is refused here, not at the first forward."""
-
+    class Experts(torch.nn.Module):
         def __init__(self, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
                      kernel: str = "walk", wide_min_rows: Optional[int] = None):
             super().__init__()
-            self.kernel = _matmul_grouped_kernel(kernel)
+            self.kernel = _grouped_kernel(o, kernel)
             if wide_min_rows is not None and (isinstance(wide_min_rows, bool) or not isinstance(wide_min_rows, (int, np.integer)) or wide_min_rows < 0):
                 raise MtqError(f"wide_min_rows must be None or a non-negative int, got {wide_min_rows!r}")
             self.wide_min_rows = None if wide_min_rows is None else int(wide_min_rows)
-            if out_dtype not in ("float32", "bfloat16"):
-                raise MtqError(f"out_dtype must be 'float32' or 'bfloat16', got {out_dtype!r}")
+            _check_out_dtype(out_dtype)
             batch = _resolve_batch(pts_or_batch)                # once: forward hands the batch down and walks no list
             self.backend = backend or ("hip" if _batch_on_device(batch) else "emulation")
-            if self.backend not in BACKENDS:
-                raise MtqError(f"backend must be one of {BACKENDS}, got {self.backend!r}")
+            _check_backend(self.backend)
             self._workspace = None
+            n, k = o.n_k(batch)
             if self.backend == "hip":
-                self._size = _matmul_grouped_entries(self.kernel)[1]
-                wide_size = None if self.wide_min_rows is None else _matmul_grouped_entries("wide")[1]
+                size = _grouped_entry(o, hb, self.kernel)[1]     # a library without the kernel is refused here, not at the first forward
+                if o.experts_keep_size:
+                    self._size = size
+                wide_size = None if self.wide_min_rows is None else _grouped_entry(o, hb, "wide", o.experts_wide_lacks)[1]
                 batch = batch_to_device(batch)
                 if wide_size is not None:
-                    need = wide_size(1, batch.count, batch.cols, batch.rows)                            # a function of count alone
+                    need = wide_size(1, batch.count, n, k)                                              # a function of count alone
                     self._workspace = torch.empty((need,), dtype=torch.uint8, device=batch.arena.device)   # only ever replaced by a larger one
             self.batch = batch
             self.out_dtype, self.split = out_dtype, int(split)
-            self.count, self.in_features, self.out_features = batch.count, batch.rows, batch.cols
+            self.count, self.in_features, self.out_features = batch.count, k, n
             if bias is not None:
                 if not _is_torch(bias):
                     bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
@@ -2517,29 +2122,31 @@ def _packed_experts_matmul_class():
                 raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
             T = int(x.shape[0])
             if self.wide_min_rows is not None and T >= self.wide_min_rows:
-                y = matmul_grouped_wide(x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend,
-                                        workspace=self._workspace)
-                return y if _is_torch(y) else torch.from_numpy(y)
+                return _as_torch(globals()[o.grouped_wide](x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend,
+                                                           workspace=self._workspace))
             if self.backend == "hip" and T:
-                need = self._size(T, self.count, self.out_features, self.in_features, self.split)
+                if o.experts_keep_size:
+                    size = self._size
+                else:                                # looked up at every forward, by name
+                    size = _grouped_entry(o, hb, self.kernel)[1]
+                need = size(T, self.count, self.out_features, self.in_features, self.split)
                 if need and (self._workspace is None or self._workspace.numel() < need):
                     self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.batch.arena.device)
-            y = matmul_grouped(x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype,
-                               backend=self.backend, split=self.split, workspace=self._workspace, kernel=self.kernel)
-            return y if _is_torch(y) else torch.from_numpy(y)
+            return _as_torch(globals()[o.grouped](x, group_rows, self.batch, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend,
+                                                  split=self.split, workspace=self._workspace, kernel=self.kernel))
 
-    return PackedExpertsMatmul
+    return _named(Experts, name)
 
 
 def __getattr__(name):
     """PackedLinear, PackedMatmul, PackedExperts, PackedExpertsMatmul, PackedMLP, PackedExpertsMLP, PackedMatmulMLP, PackedExpertsMatmulMLP
     and PackedMoE are torch.nn.Modules: a class is made on first use, so that importing this module does not import torch."""
-    makers = {"PackedLinear": _packed_linear_class, "PackedMatmul": _packed_matmul_class, "PackedExperts": _packed_experts_class,
-              "PackedExpertsMatmul": _packed_experts_matmul_class,
-              "PackedMLP": _packed_mlp_class, "PackedExpertsMLP": _packed_experts_mlp_class, "PackedMoE": _packed_moe_class,
-              "PackedMatmulMLP": _packed_matmul_mlp_class, "PackedExpertsMatmulMLP": _packed_experts_matmul_mlp_class}
+    makers = {"PackedLinear": (_product_class, _NK), "PackedMatmul": (_product_class, _KN), "PackedExperts": (_experts_class, _NK),
+              "PackedExpertsMatmul": (_experts_class, _KN), "PackedMLP": (_mlp_class, _NK), "PackedMatmulMLP": (_mlp_class, _KN),
+              "PackedExpertsMLP": (_experts_mlp_class, _NK), "PackedExpertsMatmulMLP": (_experts_mlp_class, _KN), "PackedMoE": (_packed_moe_class,)}
     if name in makers:
-        cls = makers[name]()
+        make, *orientation = makers[name]
+        cls = make(*orientation, name) if orientation else make()
         globals()[name] = cls
         return cls
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
