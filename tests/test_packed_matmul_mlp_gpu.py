@@ -6,7 +6,8 @@ packed.PackedMoE(stored="transpose") — against their written-out compositions,
   * PackedExpertsMatmulMLP on both sides of decode_max_rows: glu_matmul_grouped + matmul_grouped_wide, or glu_matmul_grouped_skinny +
     matmul_grouped(kernel="walk"); a pack_batch_transposed list goes in as it is; T = 0 empty;
   * PackedMoE(stored="transpose") equals plan → dispatch → PackedExpertsMatmulMLP → combine written out with the sort on the host:
-    dropped ids, a token that names an expert twice, a base, T = 1 and T = 70; stored="rows" still builds PackedExpertsMLP.
+    dropped ids, a token that names an expert twice, a base, T = 1 and T = 70; T = 130 with K = 8: S = 1040, the three-kernel plan and
+    the combine's second batch of four slots inside a forward; stored="rows" still builds PackedExpertsMLP.
 """
 from __future__ import annotations
 
@@ -155,6 +156,18 @@ def test_packed_moe_stored_transpose_is_sort_experts_combine(T, decode_max_rows,
                 assert np.array_equal(_bits(moe(x, ids_d.to(torch.int32), w_d, base=based)), want), "int32 ids give other words"
     empty = moe(x[:0], ids_d[:0], w_d[:0])
     assert tuple(empty.shape) == (0, K_OUT)
+
+
+def test_packed_moe_stored_transpose_above_one_run():
+    """T = 130, K = 8 (S = 1040): the three-kernel plan and the combine's second batch of slots inside a forward over (k, n) experts."""
+    T, K = 130, 8
+    assert T * K > hb.MOE_RUN and K > 4
+    x, ids, w, base = _layer_inputs(T, K, "uniform", 7 * T + K)
+    ids[1, ::3] = (-1, COUNT, COUNT + 3)                 # a token with dropped slots in either batch
+    moe = packed.PackedMoE(*_experts(), out_dtype="bfloat16", expert_dtype="float32", stored="transpose", max_tokens=1)
+    want = _layer_want(x, ids, w, base, "float32", "bfloat16", None)
+    y = moe(x, torch.from_numpy(ids).cuda(), torch.from_numpy(w).cuda(), base=torch.from_numpy(base).cuda().to(torch.bfloat16))
+    assert tuple(y.shape) == (T, K_OUT) and np.array_equal(_bits(y), want), np.argwhere(_bits(y) != want)[:4]
 
 
 def test_stored_rows_is_still_the_row_layout_layer_and_a_wrong_word_is_refused():

@@ -2,7 +2,15 @@
 mtq_moe_combine and the plan's size function) as far as they go without a device.  The emulation backend against a plain Python loop
 over the slots; the plan's invariants; every argument error; the C entries' refusals, which come back before a device is looked for
 (the pointers handed in are host addresses that no check may dereference); the size function's formula; PackedMoE on the emulation
-against sort on the host, PackedExpertsMLP(backend="emulation") and the combine on the host."""
+against sort on the host, PackedExpertsMLP(backend="emulation") and the combine on the host.
+
+The table of tests/test_packed_moe_gpu.py (tests/moe_cases.py) runs here too, on the emulation and against this file's own loops, so
+that the cases and the want-side the GPU file compares with are checked on a machine without a GPU:
+  plan      every (T, K, count) of moe_cases.ROUTINGS with every kind of moe_cases.KINDS, both id types;
+  dispatch  k = 8, 64, 300, 1000, 2056, 4096 with 111 rows; the strided grids' k = 129 and k = 520 at a tenth of their rows;
+  combine   n = 8, 72, 200, 1000, 1032, 2056, 2050, 4096 at K = 4; K = 1, 2, 3, 5, 7, 8, 9, 64 at n = 72 and n = 13; the strided
+            grids' permuted cases at a tenth of their tokens;
+  layer     T = 130, K = 8, then T = 3, K = 8 on the same module; T = 4, K = 9."""
 import re
 from pathlib import Path
 
@@ -12,6 +20,7 @@ import torch
 
 from quantization_analysis_amd import hip_backend as hb
 from quantization_analysis_amd import packed
+from tests import moe_cases
 from tests.inputs import gen, to_bf16_valued
 from tests.packed_cases import random_map
 from tests.test_capi_host import _load, _OnDevice, _StubLibrary
@@ -322,6 +331,99 @@ def test_the_emulated_dispatch_and_combine_are_the_loops():
             assert yb.dtype == torch.bfloat16 and torch.equal(yb.view(torch.int16), torch.from_numpy(acc).to(torch.bfloat16).view(torch.int16))
 
 
+# ----------------------------------------------------------------------------- the GPU file's table (tests/moe_cases.py) on the emulation
+
+def _loop_dispatch(x, src, K):
+    S = src.size
+    want = np.zeros((S, x.shape[1]), dtype=x.dtype)
+    for r in range(S):
+        if 0 <= src[r] < S:
+            want[r] = x[src[r] // K]
+    return want
+
+
+def _loop_combine(row_of, w, ys, base, T, K):
+    """The contract, slot by slot: acc = fl32(acc + fl32(w * ys[row])) with the two roundings as two NumPy float32 operations."""
+    S = T * K
+    acc = np.zeros((T, ys.shape[1]), dtype=np.float32) if base is None else np.array(base, dtype=np.float32)
+    for s in range(S):
+        r = int(row_of[s])
+        if 0 <= r < S:
+            product = np.multiply(w[s // K, s % K], ys[r], dtype=np.float32)
+            np.add(acc[s // K], product, out=acc[s // K], dtype=np.float32)
+    assert np.isfinite(acc).all()
+    return acc
+
+
+@pytest.mark.parametrize("T,K,count", moe_cases.ROUTINGS)
+def test_the_shared_routings_on_the_emulation_and_their_want_side(T, K, count):
+    """Every (T, K, count) and kind of the GPU file: the emulated plan and the want-side the GPU file compares with (moe_cases._want_plan)
+    against this file's loop, and what each kind promises (moe_cases.check_kind)."""
+    for kind in moe_cases.KINDS:
+        for np_type in (np.int32, np.int64):
+            if kind == "high_word" and np_type != np.int64:
+                continue
+            ids = moe_cases._routing(T, K, count, kind, np_type)
+            want = _loop_plan(ids, count)
+            moe_cases.check_kind(kind, ids, count, want)
+            plan = packed.moe_plan(ids, count)
+            for got, shared, w, name in zip((plan.group_rows, plan.row_of, plan.src), moe_cases._want_plan(ids, count), want,
+                                            ("group_rows", "row_of", "src")):
+                assert got.dtype == shared.dtype == np.int32 and np.array_equal(got, w) and np.array_equal(shared, w), (kind, name)
+            if kind == "none_live":
+                assert int(plan.group_rows[-1]) == 0
+            if (T, K, count) == (1025, 1, 1) and kind in ("uniform", "one", "twice", "distinct"):
+                assert np.array_equal(plan.row_of, np.arange(T))                           # every slot's row is its own index
+
+
+@pytest.mark.parametrize("k,T,K,far", tuple((k, moe_cases.DT, moe_cases.DK, None) for k in (8, 64, 300, 1000, 2056, 4096)) +
+                         ((129, 275, 3, 700), (520, 550, 3, 1500)))                       # the strided grids' cases at a tenth of the rows
+def test_the_shared_dispatch_cases_on_the_emulation(k, T, K, far):
+    x, src, want = moe_cases._dispatch_case(k, T, K, far)
+    assert np.array_equal(want, _loop_dispatch(x, src, K))
+    plan = packed.MoEPlan(np.zeros(2, dtype=np.int32), src, src, T, K, 1)
+    xs = packed.moe_dispatch(x.view(np.int16), plan)      # a bit copy: any 16-bit words
+    assert xs.dtype == np.int16 and np.array_equal(xs.view(np.uint16), want)
+    xt = packed.moe_dispatch(torch.from_numpy(x.view(np.int16)).view(torch.bfloat16), plan)
+    assert xt.dtype == torch.bfloat16 and np.array_equal(xt.view(torch.int16).numpy().view(np.uint16), want)
+
+
+def _emulated_combine_is_the_loop(row_of, w, ys, ys_given, base, T, K):
+    plan = packed.MoEPlan(np.zeros(2, dtype=np.int32), row_of, row_of, T, K, 1)
+    for b in (None, base):
+        want = _loop_combine(row_of, w, ys, b, T, K)
+        assert np.array_equal(moe_cases._want_combine(row_of, w, ys, b, T, K).view(np.int32), want.view(np.int32))    # the GPU file's want
+        y = packed.moe_combine(ys_given, w, plan, base=b)
+        assert y.dtype == np.float32 and np.array_equal(y.view(np.int32), want.view(np.int32)), (T, K, ys.shape[1], b is None)
+        bt = None if b is None else torch.from_numpy(b).to(torch.bfloat16)
+        yb = packed.moe_combine(torch.from_numpy(ys_given).to(torch.bfloat16), torch.from_numpy(w), plan, base=bt, out_dtype="bfloat16")
+        assert yb.dtype == torch.bfloat16 and np.array_equal(yb.view(torch.int16).numpy(), moe_cases._bf16_words(want).reshape(T, -1))
+
+
+@pytest.mark.parametrize("n,K", tuple((n, moe_cases.CK) for n in (8, 72, 200, 1000, 1032, 2056, 2050, 4096)) +
+                         tuple((n, K) for n in (72, 13) for K in (1, 2, 3, 5, 7, 8, 9, 64)))
+def test_the_shared_combine_cases_on_the_emulation(n, K):
+    row_of, w, ys, ys_dev, base = moe_cases._combine_case(n, K)
+    _emulated_combine_is_the_loop(row_of, w, ys, ys_dev, base, moe_cases.CT, K)           # ys_dev: NaN and Inf in the rows no slot names
+
+
+@pytest.mark.parametrize("n,T,K", ((8, 3280, 1), (5, 3280, 1), (1032, 820, 2)))           # the strided grids' cases at a tenth of the tokens
+def test_the_shared_permuted_combine_cases_on_the_emulation(n, T, K):
+    row_of, w, ys, base = moe_cases._combine_permuted_case(n, T, K, T - 8)
+    _emulated_combine_is_the_loop(row_of, w, ys, ys, base, T, K)
+
+
+def test_the_launch_geometry_the_gpu_tests_assert():
+    """moe_cases' copy of the host code's arithmetic at the sizes the GPU file claims: which k and n take a second trip, which n take
+    256 lanes, and how many rows a workgroup holds where the grids stride."""
+    assert [moe_cases.dispatch_geometry(k, True) for k in (8, 1000, 2048, 2056, 4096)] == [(1, 256, 1), (128, 2, 1), (256, 1, 1), (256, 1, 2), (256, 1, 2)]
+    assert moe_cases.dispatch_geometry(129, False) == (256, 1, 1) and moe_cases.dispatch_geometry(520, True) == (128, 2, 1)
+    assert [moe_cases.combine_geometry(n) for n in (5, 8, 13, 72, 1000, 1024, 1032, 2048, 2050, 2056, 4096)] == \
+        [(64, 4, 1)] * 4 + [(128, 2, 1), (128, 2, 1), (256, 1, 1), (256, 1, 1), (256, 1, 2), (256, 1, 2), (256, 1, 2)]
+    assert 2750 * 3 > moe_cases.MAX_BLOCKS * 1 and 5500 * 3 > moe_cases.MAX_BLOCKS * 2 and 32800 > moe_cases.MAX_BLOCKS * 4 and 8200 > moe_cases.MAX_BLOCKS
+    assert (moe_cases.plan_scan_per(4096, True), moe_cases.plan_scan_per(4096, False)) == (64, 16) and moe_cases.RUN == hb.MOE_RUN
+
+
 def test_every_argument_error():
     ids = _routing(7, 2, 5, "uniform")
     for bad in (ids.reshape(-1), ids.reshape(7, 2, 1), torch.from_numpy(ids)[0]):
@@ -426,3 +528,47 @@ def test_packed_moe_on_emulation_is_sort_experts_combine():
     for kw in ({"out_dtype": "float16"}, {"expert_dtype": "float64"}, {"max_tokens": 0}, {"decode_max_rows": -1}, {"act": "gelu"}):
         with pytest.raises(hb.MtqError):
             packed.PackedMoE(gates, ups, downs, **kw)
+
+
+def _emulated_layer_is_the_loops(moe_of, gates, ups, downs, T, K, ids, seed):
+    """PackedMoE on the emulation against _loop_plan, PackedExpertsMLP(backend="emulation") on the sorted rows and _loop_combine."""
+    rng = np.random.default_rng(seed)
+    w = (rng.random((T, K)) + 0.25).astype(np.float32)
+    x = torch.from_numpy(to_bf16_valued(gen("normal_f32", seed, (T, K_IN)) * 50)).to(torch.bfloat16)
+    base = torch.from_numpy(to_bf16_valued(rng.standard_normal((T, K_OUT)).astype(np.float32))).to(torch.bfloat16)
+    group_rows, row_of, src = _loop_plan(ids, COUNT)
+    R = int(group_rows[-1])
+    assert 0 < R <= T * K
+    for expert_dtype in ("float32", "bfloat16"):
+        mlp = packed.PackedExpertsMLP(gates, ups, downs, out_dtype=expert_dtype, backend="emulation")
+        ys = np.zeros((T * K, K_OUT), dtype=np.float32)
+        ys[:R] = mlp(x[torch.from_numpy(src[:R].astype(np.int64) // K)], [int(v) for v in group_rows]).float().numpy()
+        for b in (None, base):
+            acc = _loop_combine(row_of, w, ys, None if b is None else b.float().numpy(), T, K)
+            for out_dtype in ("bfloat16", "float32"):
+                y = moe_of(out_dtype, expert_dtype)(x, torch.from_numpy(ids), torch.from_numpy(w), base=b)
+                want = torch.from_numpy(acc) if out_dtype == "float32" else torch.from_numpy(acc).to(torch.bfloat16)
+                words = torch.int32 if out_dtype == "float32" else torch.int16
+                assert y.dtype == want.dtype and torch.equal(y.view(words), want.view(words)), (T, K, expert_dtype, out_dtype, b is None)
+
+
+def test_packed_moe_on_emulation_at_the_gpu_files_layer_cases():
+    """T = 130, K = 8 (S = 1040, two batches of slots, every token names an expert more than once), uniform and with dropped slots and
+    empty experts; then T = 3, K = 8 on the same modules; T = 4, K = 9."""
+    gates, ups, downs = _experts()
+    modules = {}
+
+    def moe_of(out_dtype, expert_dtype):                  # one module per pair of types for all calls: the small call follows the large one
+        if (out_dtype, expert_dtype) not in modules:
+            modules[out_dtype, expert_dtype] = packed.PackedMoE(gates, ups, downs, out_dtype=out_dtype, expert_dtype=expert_dtype,
+                                                                backend="emulation", max_tokens=1)
+        return modules[out_dtype, expert_dtype]
+
+    rng = np.random.default_rng(130)
+    for T, K in ((130, 8), (3, 8), (4, 9)):
+        assert K > 4 and (T != 130 or T * K > hb.MOE_RUN) and (K != 9 or K > packed.MOE_PLAN_TOPK)
+        uniform = rng.integers(0, COUNT, size=(T, K)).astype(np.int64)
+        sparse = rng.choice(np.array([0, 2, 4, -1, COUNT, COUNT + 3], dtype=np.int64), size=(T, K))
+        sparse[0, :5] = [-1, COUNT, -1, COUNT + 3, 4]     # a token whose first batch of four slots is all dropped
+        for seed, ids in enumerate((uniform, sparse)):
+            _emulated_layer_is_the_loops(moe_of, gates, ups, downs, T, K, ids, 10 * T + seed)
