@@ -1217,6 +1217,44 @@ int mtq_moe_combine(const void *ys, int ys_dtype, int64_t ldys, const int32_t *r
                     int base_dtype, int64_t ldbase, int64_t tokens, int64_t topk, int64_t n, void *y, int out_dtype, int64_t ldy,
                     void *stream);
 
+/* ------------------------------------------------------------------ MoE router: scoring and group-limited top-k (csrc/mtq_moe_route.hip)
+ * From the router's logits (tokens, count), bf16 or float32 (logits_dtype, MTQ_DTYPE_*) at pitch ld_logits, to what the plan and the
+ * combine above take: topk_ids int32 (tokens, topk) at pitch ld_ids and topk_weights float32 (tokens, topk) at pitch ld_w, in ONE
+ * launch.  The router GEMM (x · W_routerᵀ) stays the model's.  The rule for one token, every operation rounded once to float32:
+ *
+ * Score.  s[e] = softmax(logits)[e] (MTQ_ROUTE_SOFTMAX) or sigmoid(logits[e]) (MTQ_ROUTE_SIGMOID) in float32; a bf16 logit is widened
+ *   exactly.  How exp and the softmax denominator are formed is the kernel's business (the hardware exp2 of one product, the row
+ *   maximum subtracted, a per-lane sum then a butterfly); s is the one float32 value that selection, the weights and `scores` use, and
+ *   it does not depend on whether `scores` is given.  scores: NULL, or float32 (tokens, count) at pitch ld_scores: s, written only then.
+ * Key.    key[e] = fl32(s[e] + bias[e]) with a bias (float32 [count], a selection-only correction: DeepSeek's
+ *   e_score_correction_bias), else s[e].  a ranks before b iff key_a > key_b, or key_a == key_b and a < b, where a NaN key counts as
+ *   -Inf: -0 and +0 tie, NaN ties with -Inf, and ties go to the lower id.
+ * Groups  (n_group > 1).  Group g is the experts [g * count / n_group, (g + 1) * count / n_group).  Its score is its best key
+ *   (group_top = 1, DeepSeek-V2) or fl32(best key + second-best key) (group_top = 2, DeepSeek-V3), the keys as the ranking sees them
+ *   (NaN as -Inf).  The topk_group best groups stay, by the same ranking with the group index as id; the experts of the others are out.
+ * Select. ids[j], j = 0 .. topk - 1: the topk best remaining experts in rank order; distinct and in [0, count) whatever the logits hold.
+ * Weights. v[j] = s[ids[j]] (the score, not the key).  renormalize = 0: w[j] = fl32(v[j] * scale).  renormalize = 1: d = v[0];
+ *   d = fl32(d + v[j]) for j = 1 .. topk - 1 in that order; d = fl32(d + eps); w[j] = fl32(fl32(v[j] / d) * scale), the division
+ *   IEEE-correct.  eps and scale are rounded to float32 once, on the host.
+ * Special values.  A -Inf logit scores +0: that is how a caller masks experts.  For a token with a NaN or +Inf logit, or with every
+ *   logit -Inf, the ids stay distinct and in range and obey the ranking on whatever `scores` holds; its weights may be any words.  The
+ *   other tokens of the call are unaffected.
+ *
+ * Limits: 1 <= count <= MTQ_MOE_MAX_EXPERTS, 1 <= topk <= min(count, MTQ_MOE_MAX_TOPK), 1 <= n_group <= MTQ_MOE_MAX_GROUPS,
+ * count % n_group == 0, 1 <= topk_group <= n_group, topk <= topk_group * count / n_group, group_top 1 or 2 and at most count / n_group,
+ * renormalize 0 or 1, eps and scale finite (as float32 too), tokens >= 1.  Outside them, and for a null pointer (bias and scores may
+ * be NULL), a pitch below its row, a pointer not aligned to its type or a code that is none: MTQ_ERR_INVALID before a device is
+ * looked for.  Asynchronous on `stream`; no workspace, no atomics, and two calls give the same words.  A token is one wave's work:
+ * up to 256 experts the scores and keys stay in registers (one kernel each for count <= 64, <= 128, <= 256; four tokens a
+ * workgroup), above that they live in LDS (one token a workgroup); the grid stops at 2048 workgroups and strides on.  The symbol is
+ * optional: a build of this version may lack it. */
+enum { MTQ_ROUTE_SOFTMAX = 0, MTQ_ROUTE_SIGMOID = 1 };
+#define MTQ_MOE_MAX_GROUPS 64
+
+int mtq_moe_route(const void *logits, int logits_dtype, int64_t ld_logits, int64_t tokens, int64_t count, int64_t topk, int score,
+                  const float *bias, int64_t n_group, int64_t topk_group, int group_top, int renormalize, double eps, double scale,
+                  int32_t *topk_ids, int64_t ld_ids, float *topk_weights, int64_t ld_w, float *scores, int64_t ld_scores, void *stream);
+
 /* Test hook: the skinny kernel's decode (a cheaper form of the block kernel's for exponent bytes M..254, the same code elsewhere)
  * beside the reference decode, for fmt MTQ_FMT_BFP8 / BFP4 / BFP2.  got, want: device uint32 [16][256][16][16] = [rot][E][q][i], the
  * float32 word of code (16 q + (i + rot) % 16) mod 2^(M + 1) at element i of a group with exponent byte E: every (E, code) at every

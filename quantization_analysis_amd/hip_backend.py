@@ -153,6 +153,7 @@ SIGNATURES = {
     "mtq_moe_plan": ("i", "pillllppppzp", True),
     "mtq_moe_dispatch": ("i", "plllplplp", True),
     "mtq_moe_combine": ("i", "pilpplpillllpilp", True),
+    "mtq_moe_route": ("i", "pilllliplliiddplplplp", True),
     "mtq_packed_glu_matmul_wide": ("i", "plllpzpppzpplppipilp", True),
     "mtq_packed_glu_matmul_wide_grouped_workspace_bytes": ("z", "llll", True),
     "mtq_packed_glu_matmul_wide_grouped": ("i", "plllppzppppzpppllpplipilpzp", True),
@@ -1859,6 +1860,56 @@ def moe_combine(ys, row_of, weights, base=None, out_dtype=None, out=None, stream
     check(fn(ys.data_ptr(), ys_code, ldys, pr, weights.data_ptr(), _rows_ld(weights, T, K), base_ptr, base_code, ldbase, T, K, n,
              out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
     return out
+
+MOE_ROUTE = ("mtq_moe_route",)
+ROUTE_SOFTMAX, ROUTE_SIGMOID = 0, 1                       # include/mtq.h MTQ_ROUTE_SOFTMAX, MTQ_ROUTE_SIGMOID
+MOE_MAX_GROUPS = 64                                       # include/mtq.h MTQ_MOE_MAX_GROUPS
+ROUTE_SCORES = {"softmax": ROUTE_SOFTMAX, "sigmoid": ROUTE_SIGMOID}
+
+
+def _route_out(out, rows: int, cols: int, dtype, device, name: str):
+    """An output of moe_route checked, or a new (rows, cols) tensor → (tensor, pitch)."""
+    torch = _torch()
+    if out is None:
+        require_gpu()
+        out = torch.empty((rows, cols), dtype=dtype, device=device)
+    elif out.dtype != dtype or out.dim() != 2 or tuple(out.shape) != (rows, cols) or (cols > 1 and out.stride(1) != 1) or not out.is_cuda:
+        raise MtqError(f"{name} must be a {dtype} ({rows}, {cols}) device tensor with contiguous rows")
+    return out, _rows_ld(out, rows, cols)
+
+
+def moe_route(logits, topk: int, score: str = "softmax", bias=None, n_group: int = 1, topk_group: int = 1, group_top: int = 2,
+              renormalize: bool = True, eps: float = 0.0, scale: float = 1.0, return_scores: bool = False, out_ids=None, out_weights=None,
+              out_scores=None, stream="current"):
+    """mtq_moe_route on the current stream: logits, a (tokens, count) bf16 or float32 device tensor with contiguous rows (any row
+    pitch), → (topk_ids int32 (tokens, topk), topk_weights float32 (tokens, topk), scores float32 (tokens, count) or None) in one
+    launch: softmax or sigmoid scores, an optional float32 [count] selection bias, group-limited top-k and the weights' renormalising
+    and scaling, by the rule include/mtq.h states.  The scores are written when return_scores is set or out_scores is given.
+    out_ids, out_weights, out_scores: optional device tensors of those types and shapes with contiguous rows (any row pitch).  The
+    limits on count, topk, the groups, eps and scale are the library's.  Nothing is read back."""
+    torch = _torch()
+    if score not in ROUTE_SCORES:
+        raise MtqError(f"score must be one of {tuple(ROUTE_SCORES)}, got {score!r}")
+    code, _count, _stride, T, count, ld = _matrix(logits, (2,))
+    topk = int(topk)
+    if T <= 0 or count <= 0 or topk <= 0:
+        raise MtqError("tokens, count and topk must be positive")
+    bias_ptr = None
+    if bias is not None:
+        bias_ptr = _buffer(bias, torch.float32, count, "bias")
+        if bias.numel() != count:
+            raise MtqError(f"bias must have count = {count} entries, got {bias.numel()}")
+    fn = _entry("mtq_moe_route")
+    ids, ld_ids = _route_out(out_ids, T, topk, torch.int32, logits.device, "out_ids")
+    weights, ld_w = _route_out(out_weights, T, topk, torch.float32, logits.device, "out_weights")
+    scores, scores_ptr, ld_scores = None, None, 0
+    if return_scores or out_scores is not None:
+        scores, ld_scores = _route_out(out_scores, T, count, torch.float32, logits.device, "out_scores")
+        scores_ptr = scores.data_ptr()
+    check(fn(logits.data_ptr(), code, ld, T, count, topk, ROUTE_SCORES[score], bias_ptr, int(n_group), int(topk_group), int(group_top),
+             int(bool(renormalize)), float(eps), float(scale), ids.data_ptr(), ld_ids, weights.data_ptr(), ld_w, scores_ptr, ld_scores,
+             _packed_stream_ptr(stream)))
+    return ids, weights, scores
 
 
 def debug_packed_decode(fmt: str):

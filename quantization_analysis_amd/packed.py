@@ -31,8 +31,13 @@ directory's index.json, where such a run marks its entries "stored": "transpose"
 moe_plan / moe_dispatch / moe_combine / PackedMoE are the rest of an MoE layer around PackedExpertsMLP (csrc/mtq_moe.hip): from the
 router's (tokens, top_k) expert ids a stable counting sort on the device gives the grouped entries' row layout (MoEPlan), a row gather
 puts the tokens in it, and a weighted un-permute with a fixed summation order brings the experts' rows back; nothing is read back to
-the host.  Router scoring (softmax / sigmoid, group-limited top-k) stays the model's; the gather is not fused into the GEMMs' X loads
-and the combine not into the down projection's epilogue (both would change existing kernels).
+the host.  The gather is not fused into the GEMMs' X loads and the combine not into the down projection's epilogue (both would
+change existing kernels).
+
+moe_route / MoERouting / MOE_ROUTINGS are the router in front of that (csrc/mtq_moe_route.hip): from the router GEMM's logits to
+(topk_weights, topk_ids) in one launch - softmax or sigmoid scores, a selection-only bias, group-limited top-k, renormalised and scaled
+weights - by a rule include/mtq.h pins to the bit on the scores (ties to the lower id); PackedMoE(router=...).forward_logits runs it
+and then forward.  The router GEMM stays the model's; the route is not fused into the plan's one-launch kernel.
 
 glu_matmul / glu_matmul_skinny / glu_matmul_grouped / glu_matmul_grouped_skinny are glu and its three variants for packed (k, n) gate and
 up matrices (mtq_packed_glu_matmul_wide, _wide_grouped, _skinny, _skinny_grouped: the gated frames with the matmul kernels' feed), bit
@@ -1726,6 +1731,177 @@ def moe_combine(ys, topk_weights, plan: MoEPlan, base=None, out_dtype: str = "fl
     return y
 
 
+# ----------------------------------------------------------------------------- MoE router: scoring and group-limited top-k
+
+MOE_MAX_GROUPS = 64          # include/mtq.h MTQ_MOE_MAX_GROUPS
+ROUTE_SCORES = ("softmax", "sigmoid")
+
+
+@dataclass(frozen=True)
+class MoERouting:
+    """The parameters of moe_route (include/mtq.h "MoE router"), checked here as far as they can be without the expert count;
+    check_count(count) checks the rest.  expects_bias: the model routes with a selection bias (DeepSeek-V3's
+    e_score_correction_bias), and PackedMoE.forward_logits refuses a call without one."""
+    topk: int
+    score: str = "softmax"
+    n_group: int = 1
+    topk_group: int = 1
+    group_top: int = 2
+    renormalize: bool = True
+    eps: float = 0.0
+    scale: float = 1.0
+    expects_bias: bool = False
+
+    def __post_init__(self):
+        def is_int(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+        if not is_int(self.topk) or not 1 <= self.topk <= MOE_MAX_TOPK:
+            raise MtqError(f"topk must be an int in 1 .. {MOE_MAX_TOPK}, got {self.topk!r}")
+        if self.score not in ROUTE_SCORES:
+            raise MtqError(f"score must be one of {ROUTE_SCORES}, got {self.score!r}")
+        if not is_int(self.n_group) or not 1 <= self.n_group <= MOE_MAX_GROUPS:
+            raise MtqError(f"n_group must be an int in 1 .. {MOE_MAX_GROUPS}, got {self.n_group!r}")
+        if not is_int(self.topk_group) or not 1 <= self.topk_group <= self.n_group:
+            raise MtqError(f"topk_group must be an int in 1 .. n_group = {self.n_group}, got {self.topk_group!r}")
+        if not is_int(self.group_top) or self.group_top not in (1, 2):
+            raise MtqError(f"group_top must be 1 or 2, got {self.group_top!r}")
+        if not isinstance(self.renormalize, (bool, np.bool_)):
+            raise MtqError(f"renormalize must be a bool, got {self.renormalize!r}")
+        for name in ("eps", "scale"):
+            v = getattr(self, name)
+            with np.errstate(over="ignore"):
+                finite = not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and bool(np.isfinite(np.float32(v)))
+            if not finite:
+                raise MtqError(f"{name} must be a number that is finite in float32, got {v!r}")
+
+    def check_count(self, count: int) -> None:
+        """The limits that need the expert count."""
+        if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or not 1 <= count <= MOE_MAX_EXPERTS:
+            raise MtqError(f"count must be an int in 1 .. {MOE_MAX_EXPERTS}, got {count!r}")
+        if self.topk > count:
+            raise MtqError(f"topk must be at most count = {count}, got {self.topk}")
+        if count % self.n_group:
+            raise MtqError(f"count = {count} must be a multiple of n_group = {self.n_group}")
+        size = count // self.n_group
+        if self.topk > self.topk_group * size:
+            raise MtqError(f"topk = {self.topk} must be at most topk_group * count / n_group = {self.topk_group * size}")
+        if self.group_top > size:
+            raise MtqError(f"group_top = {self.group_top} must be at most count / n_group = {size}")
+
+
+# The routers of public model configurations (config.json of the released checkpoints).
+MOE_ROUTINGS: Mapping[str, MoERouting] = MappingProxyType({
+    "mixtral": MoERouting(topk=2, score="softmax", renormalize=True),
+    "qwen3-moe": MoERouting(topk=8, score="softmax", renormalize=True),
+    "deepseek-v2": MoERouting(topk=6, score="softmax", n_group=8, topk_group=3, group_top=1, renormalize=False, scale=16.0),
+    "deepseek-v3": MoERouting(topk=8, score="sigmoid", n_group=8, topk_group=4, group_top=2, renormalize=True, eps=1e-20, scale=2.5,
+                              expects_bias=True),
+})
+
+
+def _need_moe_route(hb, what: str) -> None:
+    if not hb._has(hb.MOE_ROUTE):
+        raise MtqError(f"{what} needs mtq_moe_route, which this build of libmtq_hip.so lacks: rebuild it from this tree")
+
+
+def _route_scores_f32(x: np.ndarray, score: str) -> np.ndarray:
+    """The emulation's float32 scores: the row maximum subtracted, NumPy's exp and sum in float32."""
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        if score == "sigmoid":
+            return (np.float32(1) / (np.float32(1) + np.exp(-x))).astype(np.float32)
+        p = np.exp(x - np.fmax.reduce(x, axis=1, keepdims=True))
+        return (p / p.sum(axis=1, keepdims=True, dtype=np.float32)).astype(np.float32)
+
+
+def _route_rank_key(key: np.ndarray) -> np.ndarray:
+    """A key as the ranking sees it: NaN as -Inf, -0 as +0."""
+    return np.where(np.isnan(key), np.float32(-np.inf), key).astype(np.float32) + np.float32(0)
+
+
+def _route_select(s: np.ndarray, bias, r: MoERouting):
+    """The pinned rule of include/mtq.h on float32 scores s (T, count) → (ids int32 (T, topk), weights float32 (T, topk)), whole
+    arrays at a time: stable sorts for the ranking, float32 array operations (each rounded once) for the weights."""
+    T, count = s.shape
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        k = _route_rank_key(s if bias is None else s + bias[None, :])
+        out = np.zeros((T, count), dtype=bool)
+        if r.n_group > 1:
+            size = count // r.n_group
+            top = -np.sort(-k.reshape(T, r.n_group, size), axis=2)[:, :, :2]
+            group = _route_rank_key(top[:, :, 0] if r.group_top == 1 else top[:, :, 0] + top[:, :, 1])
+            kept = np.argsort(-group, axis=1, kind="stable")[:, :r.topk_group]
+            keep = np.zeros((T, r.n_group), dtype=bool)
+            np.put_along_axis(keep, kept, True, axis=1)
+            out = ~np.repeat(keep, size, axis=1)
+        by_key = np.argsort(-k, axis=1, kind="stable")
+        order = np.take_along_axis(by_key, np.argsort(np.take_along_axis(out, by_key, axis=1), axis=1, kind="stable"), axis=1)
+        ids = order[:, :r.topk].astype(np.int32)
+        v = np.take_along_axis(s, ids.astype(np.int64), axis=1)
+        scale = np.float32(r.scale)
+        if not r.renormalize:
+            return ids, (v * scale).astype(np.float32)
+        d = v[:, 0].copy()
+        for j in range(1, r.topk):
+            d = d + v[:, j]
+        d = d + np.float32(r.eps)
+        return ids, ((v / d[:, None]) * scale).astype(np.float32)
+
+
+def moe_route(logits, topk: int, score: str = "softmax", bias=None, n_group: int = 1, topk_group: int = 1, group_top: int = 2,
+              renormalize: bool = True, eps: float = 0.0, scale: float = 1.0, backend: Optional[str] = None, return_scores: bool = False):
+    """The router of an MoE layer behind its GEMM: logits (..., count), bf16 or float32, → (topk_weights float32 (..., topk), topk_ids
+    int32 (..., topk)), and the float32 scores (..., count) the selection used when return_scores is set.  The rule is include/mtq.h's
+    ("MoE router"), pinned to the bit on the scores: softmax or sigmoid scores; key = score + bias (bias: float32 [count], selection
+    only); ranking by key, ties to the lower id, NaN as -Inf; with n_group > 1 the topk_group best groups stay (a group's score its
+    best key, group_top = 1, or the sum of its best two, group_top = 2); the topk best remaining experts in rank order; weights
+    the scores of the selected experts, with renormalize divided by their sum (added in order, + eps), times scale.
+    MOE_ROUTINGS has these parameters for public models, as MoERouting records; PackedMoE(router=...) takes one.
+    hip (the default for a device tensor): mtq_moe_route, one launch, nothing read back.  emulation: NumPy, float32 scores and the
+    same rule; the result is of the logits' kind (CPU tensors for a tensor, arrays for an array)."""
+    r = MoERouting(topk, score, n_group, topk_group, group_top, renormalize, eps, scale)
+    if len(logits.shape) < 1 or logits.shape[-1] < 1:
+        raise MtqError(f"logits must be (..., count), got shape {tuple(logits.shape)}")
+    lead, count = tuple(logits.shape[:-1]), int(logits.shape[-1])
+    r.check_count(count)
+    dtype = str(logits.dtype).replace("torch.", "")
+    if dtype not in ("bfloat16", "float32"):
+        raise MtqError(f"logits must be bfloat16 or float32, got {logits.dtype}")
+    if bias is not None and tuple(bias.shape) != (count,):
+        raise MtqError(f"bias must be ({count},), got {tuple(bias.shape)}")
+    T = int(np.prod(lead, dtype=np.int64))
+    if T < 1:
+        raise MtqError(f"logits must hold at least one token, got shape {tuple(logits.shape)}")
+    backend = backend or ("hip" if _is_torch(logits) and logits.is_cuda else "emulation")
+    _check_backend(backend)
+    if backend == "hip":
+        import torch
+
+        _need_moe_route(hb, "moe_route")
+        if not _is_torch(logits):
+            logits = torch.from_numpy(np.ascontiguousarray(logits)).to("cuda")
+        if bias is not None:
+            bias = (bias if _is_torch(bias) else torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))).to(
+                device=logits.device, dtype=torch.float32).contiguous()
+        ids, weights, scores = hb.moe_route(logits.reshape(T, count), r.topk, r.score, bias, r.n_group, r.topk_group, r.group_top,
+                                            r.renormalize, r.eps, r.scale, return_scores=return_scores)
+        got = (weights.reshape(lead + (r.topk,)), ids.reshape(lead + (r.topk,)))
+        return got + (scores.reshape(lead + (count,)),) if return_scores else got
+    as_torch = _is_torch(logits)
+    x = _host_f32(logits).reshape(T, count)
+    b = None if bias is None else _host_f32(bias).reshape(count)
+    s = _route_scores_f32(x, r.score)
+    ids, weights = _route_select(s, b, r)
+    got = (weights.reshape(lead + (r.topk,)), ids.reshape(lead + (r.topk,)))
+    if return_scores:
+        got += (s.reshape(lead + (count,)),)
+    if as_torch:
+        import torch
+
+        got = tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in got)
+    return got
+
+
 def _named(cls, name: str):
     """A class made by a factory under its public name and its docstring of _CLASS_DOCS."""
     cls.__name__ = cls.__qualname__ = name
@@ -1943,7 +2119,11 @@ def _packed_moe_class():
         leading dimensions (ids int32 or int64, ids outside [0, count) dropped; weights float32), base None or (..., k_out), a shared
         expert's output to start the sums from → (..., k_out) in out_dtype.  The leading dimensions are flattened to T tokens;
         moe_plan, moe_dispatch, the experts on (xs, plan.group_rows) with all S = T * K rows, moe_combine.  T = 0 gives the empty
-        result without a call.  Router scoring (softmax / sigmoid, group-limited top-k) stays the model's.
+        result without a call.
+        router: None, a MoERouting or a name of MOE_ROUTINGS.  With one, forward_logits(x, router_logits, bias=None, base=None) takes
+        the router GEMM's output (..., count), bf16 or float32, runs moe_route with the router's parameters (bias: the float32
+        [count] selection bias, required when the routing expects one) and then forward on its ids and weights: on hip one more
+        launch and still nothing read back.  The router GEMM itself stays the model's.
         expert_dtype: the type of the experts' rows the combine reads ("float32": the down projection's sums unrounded; "bfloat16":
         half the bytes).  decode_max_rows: PackedExpertsMLP's, compared against S, the rows the experts see.
         stored (MOE_STORED, the word of a pack_model directory's index.json): "rows", the experts are (n, k) batches and run through
@@ -1953,8 +2133,15 @@ def _packed_moe_class():
         regrown when a call needs more.  emulation: CPU tensors, for use without a GPU."""
 
         def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", expert_dtype: str = "float32",
-                     backend: Optional[str] = None, decode_max_rows: Optional[int] = None, max_tokens: int = 4096, stored: str = "rows"):
+                     backend: Optional[str] = None, decode_max_rows: Optional[int] = None, max_tokens: int = 4096, stored: str = "rows",
+                     router=None):
             super().__init__()
+            if isinstance(router, str):
+                if router not in MOE_ROUTINGS:
+                    raise MtqError(f"router must be a MoERouting or one of {tuple(MOE_ROUTINGS)}, got {router!r}")
+                router = MOE_ROUTINGS[router]
+            if router is not None and not isinstance(router, MoERouting):
+                raise MtqError(f"router must be None, a MoERouting or one of {tuple(MOE_ROUTINGS)}, got {router!r}")
             if stored not in MOE_STORED:
                 raise MtqError(f"stored must be one of {MOE_STORED}, got {stored!r}")
             _check_out_dtype(out_dtype)
@@ -1969,9 +2156,14 @@ def _packed_moe_class():
             self.count, self.in_features, self.out_features = self.experts.count, self.experts.in_features, self.experts.out_features
             if self.count > MOE_MAX_EXPERTS:
                 raise MtqError(f"PackedMoE takes at most {MOE_MAX_EXPERTS} experts, got {self.count}")
+            self.router = router
+            if router is not None:
+                router.check_count(self.count)
             self._plan_workspace = None
             if self.backend == "hip":
                 _need_moe(hb, "PackedMoE")           # refused here, not at the first forward
+                if router is not None:
+                    _need_moe_route(hb, "PackedMoE(router=...)")
                 need = hb.moe_plan_workspace_bytes(max_tokens, MOE_PLAN_TOPK, self.count)
                 self._plan_workspace = torch.empty((need,), dtype=torch.uint8, device=self.experts.gate.arena.device)
 
@@ -2011,6 +2203,25 @@ def _packed_moe_class():
             if not _is_torch(y):
                 y = torch.from_numpy(y)
             return y.reshape(lead + (self.out_features,))
+
+        @torch.no_grad()
+        def forward_logits(self, x, router_logits, bias=None, base=None):
+            """forward on moe_route's ids and weights of router_logits (..., count) under self.router."""
+            if self.router is None:
+                raise MtqError("forward_logits needs a router: PackedMoE(..., router=MoERouting(...) or a name of MOE_ROUTINGS)")
+            lead = tuple(x.shape[:-1])
+            if tuple(router_logits.shape) != lead + (self.count,):
+                raise MtqError(f"router_logits must be {lead + (self.count,)}, got {tuple(router_logits.shape)}")
+            if bias is None and self.router.expects_bias:
+                raise MtqError("this routing selects on score + bias: forward_logits needs the model's float32 [count] bias")
+            if x.shape[-1] != self.in_features:
+                raise MtqError(f"x must be (..., {self.in_features}), got {tuple(x.shape)}")
+            if int(np.prod(lead, dtype=np.int64)) == 0:
+                return torch.zeros(lead + (self.out_features,), dtype=_torch_dtype(self.out_dtype), device=x.device)
+            r = self.router
+            weights, ids = moe_route(router_logits, r.topk, r.score, bias, r.n_group, r.topk_group, r.group_top, r.renormalize, r.eps,
+                                     r.scale, backend=self.backend)
+            return self.forward(x, ids, weights, base=base)
 
     return PackedMoE
 
