@@ -23,11 +23,11 @@
 //   packed_grouped_plan_kernel<32>, packed_linear_skinny_grouped_chunked_kernel
 //                                             the same product and bits with a wave per 32-row chunk of a group, for hot experts: the
 //       groups' chunk counts are prefix-summed on the device before the launch and each wave finds its group by a search of that prefix.
-//   packed_linear_wide_kernel                 the block kernel's bits from a 128 × 128 block whose waves decode whole tiles: for m >= 64.
-//   packed_grouped_plan_kernel<128>, packed_linear_wide_grouped_kernel
+//   packed_wide_kernel<.., WT = false>        the block kernel's bits from a 128 × 128 block whose waves decode whole tiles: for m >= 64.
+//   packed_grouped_plan_kernel<128>, packed_wide_grouped_kernel<.., WT = false>
 //                                             that block for every expert of an arena over the expert's own rows, one launch: the groups'
 //       128-row block counts are prefix-summed on the device and each workgroup finds its group by the chunked kernel's search.
-//   packed_glu_wide_kernel, packed_glu_wide_grouped_kernel, glu_combine_kernel
+//   packed_glu_wide_kernel<.., WT = false>, packed_glu_wide_grouped_kernel<.., WT = false>, glu_combine_kernel
 //                                             the gated MLP's first half, glu_value(X·Ŵgᵀ + bg, X·Ŵuᵀ + bu): the wide kernel's step on a
 //       128 × 64 block whose four tile-row slots alternate between the gate and the up stream, so a lane holds both projections of its
 //       outputs; the same block in the grouped wide frame; and the element-wise combine that finishes the unfused route with the same
@@ -42,9 +42,10 @@
 //       that is read with the transposed LDS read (ds_read_b64_tr_b16); bit for bit the block kernel on the transposed weight.
 //   packed_matmul_skinny_kernel               that product for m <= 32: one wave per (K slice, tile column), each tile through a
 //       wave-private [32 k][32 n] LDS image and the transposed read; bit for bit the skinny linear kernel on the transposed weight.
-//   packed_matmul_wide_kernel                 that product for m >= 64: the wide block with its W side fed from the k × n stream, four
-//       [64 k][32 n] sub-images read through the transposed LDS read; bit for bit packed_matmul_kernel.
-//   packed_glu_matmul_wide_kernel, packed_glu_matmul_wide_grouped_kernel, packed_glu_matmul_skinny_kernel,
+//   packed_wide_kernel<.., WT = true>         that product for m >= 64: the wide block with its W side fed from the k × n stream, four
+//       [64 k][32 n] sub-images read through the transposed LDS read; bit for bit packed_matmul_kernel.  packed_wide_grouped_kernel<..,
+//       WT = true> is that block for every (k, n) expert of an arena.
+//   packed_glu_wide_kernel<.., WT = true>, packed_glu_wide_grouped_kernel<.., WT = true>, packed_glu_matmul_skinny_kernel,
 //   packed_glu_matmul_skinny_grouped_kernel   the gated product for packed k × n gate and up matrices: the four gated frames with the
 //       matmul kernels' feed (the wide block's [64 k][32 n] sub-images alternating between the two streams; the skinny wave's two
 //       images on the projection axis); bit for bit two matmul calls into f32 and the combine.
@@ -58,6 +59,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <initializer_list>
 
 #include "mtq_device.hpp"
 #include "mtq_error.hpp"
@@ -1784,21 +1786,10 @@ __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uin
     }
 }
 
-template <bool XV, bool BF16OUT>
-__global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
-    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
-    const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N, int64_t tiles_h, int64_t tiles_w,
-    const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy)
-{
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
-    const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kWideBN;
-    wide_block<false, XV, BF16OUT>(lds, x, bm * kWideBM, M, K, ldx, tensor_stream(packed, packed_bytes, map, offsets), (n0 >> 5) + wave, n0, N,
-                                   tiles_h, tiles_w, bias, nullptr, 0, yv, ldy, wave);
-}
-
-// ---- wide matmul: Y = X·P̂ + b for a packed k × n matrix from the wide block, for m >= 64.
+// The frames below take the orientation as WT and hand it to wide_block; tiles_h × tiles_w is the tile grid of the stream as it was
+// packed: of the n × k weight, or with WT of the k × n matrix.
+//
+// ---- wide matmul (WT): Y = X·P̂ + b for a packed k × n matrix from the wide block, for m >= 64.
 //
 // wide_block<.., WT = true>: everything of the block but its W side.  The stream is of a k × n matrix, so a step's W block is 2 tile rows
 // × 4 tile columns: wave w takes tile column n0 / 32 + w and, at step s, its tiles of the tile rows 2 s and 2 s + 1, a lane the group of its
@@ -1812,8 +1803,8 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_kernel(
 // their upper piece first.  No instruction touches two sub-images, and each starts on a multiple of 256 bytes: §A.6p's 16-byte shift
 // between sub-images has nothing left to separate.
 // EXEC is all ones at every transposed read: they sit in wave-uniform control flow only, and nothing returns before the epilogue.
-template <bool XV, bool BF16OUT>
-__global__ __launch_bounds__(kThreads, 2) void packed_matmul_wide_kernel(
+template <bool XV, bool BF16OUT, bool WT>
+__global__ __launch_bounds__(kThreads, 2) void packed_wide_kernel(
     const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
     const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N, int64_t tiles_h, int64_t tiles_w,
     const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy)
@@ -1822,11 +1813,11 @@ __global__ __launch_bounds__(kThreads, 2) void packed_matmul_wide_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
     const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kWideBN;
-    wide_block<false, XV, BF16OUT, true>(lds, x, bm * kWideBM, M, K, ldx, tensor_stream(packed, packed_bytes, map, offsets), (n0 >> 5) + wave, n0,
-                                         N, tiles_h, tiles_w, bias, nullptr, 0, yv, ldy, wave);
+    wide_block<false, XV, BF16OUT, WT>(lds, x, bm * kWideBM, M, K, ldx, tensor_stream(packed, packed_bytes, map, offsets), (n0 >> 5) + wave, n0,
+                                       N, tiles_h, tiles_w, bias, nullptr, 0, yv, ldy, wave);
 }
 
-// ---- grouped wide linear: packed_linear_wide_kernel's block for every expert of an arena over the expert's own rows, one launch.
+// ---- grouped wide linear: packed_wide_kernel's block for every expert of an arena over the expert's own rows, one launch.
 //
 // The 128-row blocks of all groups are numbered through, as the chunked kernel numbers 32-row chunks: group e owns blocks
 // [bstart[e], bstart[e + 1]), bstart the exclusive prefix sum of ceil(rows_e / 128) over the clamped groups, written by
@@ -1836,10 +1827,19 @@ __global__ __launch_bounds__(kThreads, 2) void packed_matmul_wide_kernel(
 // groups of a decreasing group_rows only) are not computed.  The group of a slot is found by the chunked kernel's search
 // (group_of_slot), by every wave alike: the group, its rows, its tables and its stream are uniform over the workgroup and live in
 // scalar registers.
-// On its block the workgroup calls wide_block as packed_linear_wide_kernel does, for x[r0:r1] and expert e's stream and tables at row
+// On its block the workgroup calls wide_block as packed_wide_kernel does, for x[r0:r1] and expert e's stream and tables at row
 // block (slot - bstart[e]): M is the group's end r1 (every row limit, the clamped 16-byte X loads included), a blob is checked against
 // the group's own stream and against packed_bytes, an absent tile's unconditional loads read the arena's first 320 bytes.  The same
 // function, so that kernel's bits, which are the block kernel's.
+//
+// ---- grouped wide matmul (WT): packed_wide_kernel<.., WT = true>'s block for every (k, n) expert of an arena over the expert's own rows.
+//
+// The same frame with wide_block<.., WT = true>: the plan (packed_grouped_plan_kernel<128>), the slot bound, the grid of slots ×
+// ceil(N / 128) with the column block fastest, the search and the stream in scalar registers are unchanged; wave w stages tile COLUMN
+// n0 / 32 + w of expert e's k × n tables, and M is the group's clamped end.  The same function as packed_wide_kernel<.., true> on
+// x[r0:r1] with expert e's stream, so that kernel's bits, which are packed_matmul_kernel's.
+// EXEC is all ones at every transposed read: the surplus-slot return is taken by the whole workgroup before any barrier, and everything
+// behind it is wide_block's wave-uniform control flow.
 
 // What the grouped wide frames share: block `slot` is rows [m0, min(m0 + 128, M)) of group e, all uniform over the workgroup and in
 // scalar registers.  False for a surplus slot, after the load of bstart[count] alone: the frame returns, before any barrier.
@@ -1870,8 +1870,8 @@ __device__ __forceinline__ PackedStream arena_stream_uniform(const uint8_t *pack
     return st;
 }
 
-template <bool XV, bool BF16OUT>
-__global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_grouped_kernel(
+template <bool XV, bool BF16OUT, bool WT>
+__global__ __launch_bounds__(kThreads, 2) void packed_wide_grouped_kernel(
     const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
     const uint8_t *__restrict__ packed, uint64_t packed_bytes, const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets,
     const uint64_t *__restrict__ bases, int count, int64_t N, int64_t tiles_h, int64_t tiles_w, const float *__restrict__ bias, int64_t ldb,
@@ -1882,39 +1882,13 @@ __global__ __launch_bounds__(kThreads, 2) void packed_linear_wide_grouped_kernel
     const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
     const int64_t n0 = (blockIdx.x % nblocks) * kWideBN;
     GroupBlock b;
-    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;
+    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;   // the whole workgroup, before any barrier
     const PackedStream st = arena_stream_uniform(packed, packed_bytes, maps, offsets, bases, b.e, tiles_h * tiles_w);
-    wide_block<false, XV, BF16OUT>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + wave, n0, N, tiles_h, tiles_w, bias ? bias + b.e * ldb : nullptr,
-                                   nullptr, 0, yv, ldy, wave);
+    wide_block<false, XV, BF16OUT, WT>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + wave, n0, N, tiles_h, tiles_w,
+                                       bias ? bias + b.e * ldb : nullptr, nullptr, 0, yv, ldy, wave);
 }
 
-// ---- grouped wide matmul: packed_matmul_wide_kernel's block for every (k, n) expert of an arena over the expert's own rows, one launch.
-//
-// The frame above with wide_block<.., WT = true>: the plan (packed_grouped_plan_kernel<128>), the slot bound, the grid of slots ×
-// ceil(N / 128) with the column block fastest, the search and the stream in scalar registers are that kernel's; wave w stages tile COLUMN
-// n0 / 32 + w of expert e's k × n tables, and M is the group's clamped end.  The same function as packed_matmul_wide_kernel on x[r0:r1]
-// with expert e's stream, so that kernel's bits, which are packed_matmul_kernel's.
-// EXEC is all ones at every transposed read: the surplus-slot return is taken by the whole workgroup before any barrier, and everything
-// behind it is wide_block's wave-uniform control flow.
-template <bool XV, bool BF16OUT>
-__global__ __launch_bounds__(kThreads, 2) void packed_matmul_wide_grouped_kernel(
-    const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
-    const uint8_t *__restrict__ packed, uint64_t packed_bytes, const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets,
-    const uint64_t *__restrict__ bases, int count, int64_t N, int64_t tiles_kh, int64_t tiles_nw, const float *__restrict__ bias, int64_t ldb,
-    void *__restrict__ yv, int64_t ldy)
-{
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nblocks = (N + kWideBN - 1) / kWideBN;
-    const int64_t n0 = (blockIdx.x % nblocks) * kWideBN;
-    GroupBlock b;
-    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;
-    const PackedStream st = arena_stream_uniform(packed, packed_bytes, maps, offsets, bases, b.e, tiles_kh * tiles_nw);
-    wide_block<false, XV, BF16OUT, true>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + wave, n0, N, tiles_kh, tiles_nw,
-                                         bias ? bias + b.e * ldb : nullptr, nullptr, 0, yv, ldy, wave);
-}
-
-// ---- gated wide linear (SwiGLU): glu_value(X·Ŵgᵀ + bg, X·Ŵuᵀ + bu) from packed_linear_wide_kernel's step, one launch, one store.
+// ---- gated wide linear (SwiGLU): glu_value(X·Ŵgᵀ + bg, X·Ŵuᵀ + bu) from packed_wide_kernel's step, one launch, one store.
 //
 // A workgroup of 4 waves owns 128 rows × 64 HIDDEN columns.  The W part of its LDS image keeps the wide kernel's four tile-row slots:
 // slot sl holds hidden tile row n0 / 32 + (sl >> 1), from the gate stream when sl is even and from the up stream when sl is odd.  Wave w
@@ -1922,14 +1896,29 @@ __global__ __launch_bounds__(kThreads, 2) void packed_matmul_wide_grouped_kernel
 // (wm, wn) multiplies slots 2 wn and 2 wn + 1 with the wide kernel's mfma_group unchanged, so acc[mt][0] is the gate's and acc[mt][1]
 // the up's output at the SAME (row, hidden column n0 + 32 wn + lane % 32): the epilogue is lane-local.  The loads (unconditional, an
 // absent tile clamped to its stream's tile 0 and read from the stream's head), the blob check against the tile's own stream, a map code
-// outside 0..3 as zeros, both X paths, two images, two register sets, one barrier per step: packed_linear_wide_grouped_kernel's, with
+// outside 0..3 as zeros, both X paths, two images, two register sets, one barrier per step: packed_wide_grouped_kernel's, with
 // the stream limits in units ([base, limit) of 64 bytes; for a single tensor base = 0, limit = packed_bytes / 64, the byte check's
 // equal since every blob size is a multiple of 64).
 // Bits: each accumulator takes the block kernel's sequence for its projection, the bias is added once in f32 as there, and glu_value
 // (mtq_glu.hpp) is what mtq_glu_combine applies to the two stored f32 results: the unfused route's bits.
+//
+// ---- gated wide matmul (WT): glu_value(X·P̂g + bg, X·P̂u + bu) for packed k × n gate and up matrices.
+//
+// The same frame around wide_block<true, .., WT = true>: a workgroup owns 128 rows × 64 hidden columns, wave w stages sub-image w of the
+// [64 k][32 n] W part, which is hidden tile COLUMN n0 / 32 + (w >> 1) of the k × n grid tiles_h × tiles_w, from the gate stream when w is
+// even and from the up stream when w is odd; wave (wm, wn) reads sub-images 2 wn and 2 wn + 1 through the transposed LDS read, so
+// acc[mt][0] is the gate's and acc[mt][1] the up's output at the same (row, hidden column n0 + 32 wn + lane % 32) and the epilogue is
+// lane-local glu_value.  Each accumulator takes packed_wide_kernel<.., WT = true>'s sequence for its projection (that kernel's bits are
+// packed_matmul_kernel's), the bias is added once in f32 and glu_value is what mtq_glu_combine applies: the bits of two
+// mtq_packed_matmul calls into f32 and the combine.
+// Pad, don't mask: a bad map code, a blob past its own stream's range and k-rows at or past K are zeros in the image; columns at or past
+// N are never stored.  No atomics, no workspace but the grouped plan, nothing waits on another workgroup.
+// EXEC is all ones at every transposed read: the single-tensor frame returns nowhere before the epilogue; the grouped frame's
+// surplus-slot return is taken by the whole workgroup before any barrier; behind either is wide_block's wave-uniform control flow,
+// where no read sits in a lane-dependent branch.
 constexpr int kGluBN = 64;                           // hidden columns of a workgroup
 
-template <bool XV, bool BF16OUT>
+template <bool XV, bool BF16OUT, bool WT>
 __global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_kernel(
     const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ gate, uint64_t gate_bytes,
     const int8_t *__restrict__ gate_map, const uint32_t *__restrict__ gate_offsets, const uint8_t *__restrict__ up, uint64_t up_bytes,
@@ -1940,16 +1929,16 @@ __global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
     const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kGluBN;
-    const bool is_up = wave & 1;                     // the wave's slot: even from the gate stream, odd from the up stream
+    const bool is_up = wave & 1;                     // the wave's slot or sub-image: even from the gate stream, odd from the up stream
     const PackedStream st = tensor_stream(is_up ? up : gate, is_up ? up_bytes : gate_bytes, is_up ? up_map : gate_map,
                                           is_up ? up_offsets : gate_offsets);
-    wide_block<true, XV, BF16OUT>(lds, x, bm * kWideBM, M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_h, tiles_w, bias_gate, bias_up, act,
-                                  yv, ldy, wave);
+    wide_block<true, XV, BF16OUT, WT>(lds, x, bm * kWideBM, M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_h, tiles_w, bias_gate, bias_up,
+                                      act, yv, ldy, wave);
 }
 
-// packed_linear_wide_grouped_kernel's frame with column blocks of 64 hidden columns: a blob is checked against its own group's range of
-// its own arena.
-template <bool XV, bool BF16OUT>
+// packed_wide_grouped_kernel's frame with column blocks of 64 hidden columns: the plan, the slot bound, the search and the stream in
+// scalar registers are that kernel's; a blob is checked against its own group's range [64 bases[e], 64 bases[e + 1]) of its OWN arena.
+template <bool XV, bool BF16OUT, bool WT>
 __global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_grouped_kernel(
     const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
     const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps, const uint32_t *__restrict__ gate_offsets,
@@ -1962,12 +1951,12 @@ __global__ __launch_bounds__(kThreads, 2) void packed_glu_wide_grouped_kernel(
     const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
     const int64_t n0 = (blockIdx.x % nblocks) * kGluBN;
     GroupBlock b;
-    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;
+    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;   // the whole workgroup, before any barrier
     const bool is_up = wave & 1;
     const PackedStream st = arena_stream_uniform(is_up ? up : gate, is_up ? up_bytes : gate_bytes, is_up ? up_maps : gate_maps,
                                                  is_up ? up_offsets : gate_offsets, is_up ? up_bases : gate_bases, b.e, tiles_h * tiles_w);
-    wide_block<true, XV, BF16OUT>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_h, tiles_w,
-                                  bias_gate ? bias_gate + b.e * ldb : nullptr, bias_up ? bias_up + b.e * ldb : nullptr, act, yv, ldy, wave);
+    wide_block<true, XV, BF16OUT, WT>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_h, tiles_w,
+                                      bias_gate ? bias_gate + b.e * ldb : nullptr, bias_up ? bias_up + b.e * ldb : nullptr, act, yv, ldy, wave);
 }
 
 // y[r][c] = glu_value(g[r][c], u[r][c], act): the second half of the unfused route, one thread per element in a grid-stride walk.
@@ -2101,62 +2090,8 @@ size_t glu_skinny_workspace(int64_t m, int64_t n, int split_eff)
     return (2 * (size_t)std::max(split_eff, 1) * (size_t)m * (size_t)n * sizeof(float) + 15) & ~(size_t)15;
 }
 
-// ---- gated matmul: glu_value(X·P̂g + bg, X·P̂u + bu) for packed k × n gate and up matrices, the four GLU frames with the matmul feed.
-//
-// Wide.  packed_glu_wide_kernel's frame around wide_block<true, .., WT = true>: a workgroup owns 128 rows × 64 hidden columns, wave w
-// stages sub-image w of the [64 k][32 n] W part, which is hidden tile COLUMN n0 / 32 + (w >> 1) of the k × n grid tiles_kh × tiles_nw, from
-// the gate stream when w is even and from the up stream when w is odd; wave (wm, wn) reads sub-images 2 wn and 2 wn + 1 through the
-// transposed LDS read, so acc[mt][0] is the gate's and acc[mt][1] the up's output at the same (row, hidden column n0 + 32 wn + lane % 32)
-// and the epilogue is lane-local glu_value.  Each accumulator takes packed_matmul_wide_kernel's sequence for its projection (that
-// kernel's bits are packed_matmul_kernel's), the bias is added once in f32 and glu_value is what mtq_glu_combine applies: the bits of
-// two mtq_packed_matmul calls into f32 and the combine.
-// Pad, don't mask: a bad map code, a blob past its own stream's range and k-rows at or past K are zeros in the image; columns at or past
-// N are never stored.  No atomics, no workspace but the grouped plan, nothing waits on another workgroup.
-// EXEC is all ones at every transposed read: the single-tensor frame returns nowhere before the epilogue; the grouped frame's
-// surplus-slot return is taken by the whole workgroup before any barrier; behind either is wide_block's wave-uniform control flow,
-// where no read sits in a lane-dependent branch.
-template <bool XV, bool BF16OUT>
-__global__ __launch_bounds__(kThreads, 2) void packed_glu_matmul_wide_kernel(
-    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ gate, uint64_t gate_bytes,
-    const int8_t *__restrict__ gate_map, const uint32_t *__restrict__ gate_offsets, const uint8_t *__restrict__ up, uint64_t up_bytes,
-    const int8_t *__restrict__ up_map, const uint32_t *__restrict__ up_offsets, int64_t N, int64_t tiles_kh, int64_t tiles_nw,
-    const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int act, void *__restrict__ yv, int64_t ldy)
-{
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
-    const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kGluBN;
-    const bool is_up = wave & 1;                     // the wave's sub-image: even from the gate stream, odd from the up stream
-    const PackedStream st = tensor_stream(is_up ? up : gate, is_up ? up_bytes : gate_bytes, is_up ? up_map : gate_map,
-                                          is_up ? up_offsets : gate_offsets);
-    wide_block<true, XV, BF16OUT, true>(lds, x, bm * kWideBM, M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_kh, tiles_nw, bias_gate, bias_up,
-                                        act, yv, ldy, wave);
-}
-
-// packed_matmul_wide_grouped_kernel's frame with column blocks of 64 hidden columns: the plan, the slot bound, the search and the stream
-// in scalar registers are that kernel's; a blob is checked against its own group's range [64 bases[e], 64 bases[e + 1]) of its OWN arena.
-template <bool XV, bool BF16OUT>
-__global__ __launch_bounds__(kThreads, 2) void packed_glu_matmul_wide_grouped_kernel(
-    const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, const int32_t *__restrict__ group_rows, const int32_t *__restrict__ bstart,
-    const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps, const uint32_t *__restrict__ gate_offsets,
-    const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes, const int8_t *__restrict__ up_maps,
-    const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int64_t N, int64_t tiles_kh, int64_t tiles_nw,
-    const float *__restrict__ bias_gate, const float *__restrict__ bias_up, int64_t ldb, int act, void *__restrict__ yv, int64_t ldy)
-{
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nblocks = (N + kGluBN - 1) / kGluBN;
-    const int64_t n0 = (blockIdx.x % nblocks) * kGluBN;
-    GroupBlock b;
-    if (!group_block(bstart, count, (int)(blockIdx.x / nblocks), group_rows, T, lane, b)) return;   // the whole workgroup, before any barrier
-    const bool is_up = wave & 1;
-    const PackedStream st = arena_stream_uniform(is_up ? up : gate, is_up ? up_bytes : gate_bytes, is_up ? up_maps : gate_maps,
-                                                 is_up ? up_offsets : gate_offsets, is_up ? up_bases : gate_bases, b.e, tiles_kh * tiles_nw);
-    wide_block<true, XV, BF16OUT, true>(lds, x, b.m0, b.M, K, ldx, st, (n0 >> 5) + (wave >> 1), n0, N, tiles_kh, tiles_nw,
-                                        bias_gate ? bias_gate + b.e * ldb : nullptr, bias_up ? bias_up + b.e * ldb : nullptr, act, yv, ldy, wave);
-}
-
-// Skinny (m <= 32).  packed_matmul_skinny_kernel's wave on one more unit axis, the projection p (0 the gate, 1 the up): a unit is (slice s,
+// ---- gated skinny matmul (m <= 32): glu_value(X·P̂g + bg, X·P̂u + bu) for packed k × n gate and up matrices; the wide frames of this
+// product are packed_glu_wide_kernel and packed_glu_wide_grouped_kernel with WT = true.  packed_matmul_skinny_kernel's wave on one more unit axis, the projection p (0 the gate, 1 the up): a unit is (slice s,
 // projection p, tile column tc), numbered (2 s + p) * tiles_nw + tc, the tile column fastest, so the four waves of a workgroup share a
 // slice of X.  The wave takes its projection's stream and tables and does what that kernel's wave does: the strided hand-out, the ring,
 // the blob check against its own stream, decode_skinny, the group through one of its two wave-private [32 k][32 n] images and back as two
@@ -2283,95 +2218,28 @@ extern "C" int mtq_packed_offsets(const int8_t *map, int64_t tiles, uint32_t *of
     return MTQ_OK;
 }
 
-extern "C" int mtq_pack_tiles(const void *x, int in_dtype, int64_t rows, int64_t cols, int64_t ld, const int8_t *map, const uint32_t *offsets,
-                              void *out, size_t out_bytes, void *stream)
+// ---- the checks that several entries word alike, each text in one place
+
+static const char *const kNullArg = "null argument";
+
+static int dtype_arg(int dtype, const char *name)
 {
-    if (!x || !map || !offsets || !out) return fail(MTQ_ERR_INVALID, "null argument");
-    if (in_dtype != MTQ_DTYPE_BF16 && in_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "in_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;
-    if (int rc = tile_grid(rows, cols, &th, &tw)) return rc;
-    if (ld < cols) return fail(MTQ_ERR_INVALID, "ld < cols");
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(MTQ_ERR_INVALID, "out must be 16-byte aligned");
-    if (out_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "out_bytes is smaller than the stream");
-    if (int rc = require_device()) return rc;
-    const int64_t esz = in_dtype == MTQ_DTYPE_F32 ? 4 : 2;
-    const int vec_ok = reinterpret_cast<uintptr_t>(x) % 16 == 0 && (ld * esz) % 16 == 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(tile_blocks(th * tw));
-    if (in_dtype == MTQ_DTYPE_F32)
-        hipLaunchKernelGGL(pack_tiles_kernel<float>, grid, dim3(256), 0, st, static_cast<const float *>(x), rows, cols, ld, vec_ok, map, offsets,
-                           th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
-    else
-        hipLaunchKernelGGL(pack_tiles_kernel<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(x), rows, cols, ld, vec_ok, map, offsets,
-                           th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
-    return check_launch("mtq_pack_tiles");
+    if (dtype != MTQ_DTYPE_BF16 && dtype != MTQ_DTYPE_F32) return failf(MTQ_ERR_INVALID, "%s must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32", name);
+    return MTQ_OK;
 }
 
-extern "C" int mtq_unpack_tiles(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows, int64_t cols,
-                                void *y, int out_dtype, int64_t ldy, void *stream)
+static int aligned_arg(const void *p, const char *name)
 {
-    if (!packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;
-    if (int rc = tile_grid(rows, cols, &th, &tw)) return rc;
-    if (ldy < cols) return fail(MTQ_ERR_INVALID, "ldy < cols");
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
-    if (int rc = require_device()) return rc;
-    const int64_t esz = out_dtype == MTQ_DTYPE_F32 ? 4 : 2;
-    const int vec_ok = reinterpret_cast<uintptr_t>(y) % 16 == 0 && (ldy * esz) % 16 == 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(tile_blocks(th * tw));
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(unpack_tiles_kernel<true>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy, vec_ok);
-    else
-        hipLaunchKernelGGL(unpack_tiles_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy, vec_ok);
-    return check_launch("mtq_unpack_tiles");
+    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return failf(MTQ_ERR_INVALID, "%s must be 16-byte aligned", name);
+    return MTQ_OK;
 }
 
-// The transposed pair: w / y in the stored orientation (rows × cols), the stream that of the cols × rows transpose.
-extern "C" int mtq_pack_tiles_transposed(const void *w, int in_dtype, int64_t rows, int64_t cols, int64_t ld, const int8_t *map,
-                                         const uint32_t *offsets, void *out, size_t out_bytes, void *stream)
+// A buffer of `tiles` tiles is at least as long as their bfp2 blobs; `plural`: the streams of a batch or an arena
+static int stream_bytes_arg(size_t bytes, int64_t tiles, const char *name, bool plural)
 {
-    if (!w || !map || !offsets || !out) return fail(MTQ_ERR_INVALID, "null argument");
-    if (in_dtype != MTQ_DTYPE_BF16 && in_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "in_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;                                   // of the transpose
-    if (int rc = tile_grid(cols, rows, &th, &tw)) return rc;
-    if (ld < cols) return fail(MTQ_ERR_INVALID, "ld < cols");
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(MTQ_ERR_INVALID, "out must be 16-byte aligned");
-    if (out_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "out_bytes is smaller than the stream");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(tile_blocks(th * tw));
-    if (in_dtype == MTQ_DTYPE_F32)
-        hipLaunchKernelGGL(pack_tiles_transposed_kernel<float>, grid, dim3(256), 0, st, static_cast<const float *>(w), rows, cols, ld, map, offsets,
-                           th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
-    else
-        hipLaunchKernelGGL(pack_tiles_transposed_kernel<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(w), rows, cols, ld, map,
-                           offsets, th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
-    return check_launch("mtq_pack_tiles_transposed");
-}
-
-extern "C" int mtq_unpack_tiles_transposed(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows,
-                                           int64_t cols, void *y, int out_dtype, int64_t ldy, void *stream)
-{
-    if (!packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    int64_t th, tw;                                   // of the transpose
-    if (int rc = tile_grid(cols, rows, &th, &tw)) return rc;
-    if (ldy < cols) return fail(MTQ_ERR_INVALID, "ldy < cols");
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(tile_blocks(th * tw));
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(unpack_tiles_transposed_kernel<true>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy);
-    else
-        hipLaunchKernelGGL(unpack_tiles_transposed_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy);
-    return check_launch("mtq_unpack_tiles_transposed");
+    if (bytes < (uint64_t)tiles * packed_tile_bytes(MTQ_FMT_BFP2))
+        return failf(MTQ_ERR_INVALID, "%s_bytes is smaller than the stream%s", name, plural ? "s" : "");
+    return MTQ_OK;
 }
 
 // What the batched entries share: the tile grid of one matrix and the batch's tile total
@@ -2392,10 +2260,104 @@ static int batch_pitch(int64_t count, int64_t rows, int64_t cols, int64_t ld, in
     return MTQ_OK;
 }
 
+// ---- pack / unpack.  The argument block of the eight entries, checked in the one order they all report in, down to the device: the
+// pointers, the matrix's type, the grid, the pitches, then the stream.  A pack entry names its matrix side in_dtype / ld and its stream
+// out, an unpack entry out_dtype / ldy and packed.  kTransposed: the matrix (rows × cols, pitch ld) is in the stored orientation, the
+// stream, its maps, offsets and the grid *th × *tw are those of the cols × rows transpose.  kBatched: count matrices `stride` elements
+// apart and an arena of their streams; without it the entry passes count 1 and stride 0.
+enum : unsigned { kUnpack = 0, kPack = 1, kTransposed = 2, kBatched = 4 };
+
+static int tiles_args(unsigned entry, bool any_null, int dtype, int64_t count, int64_t rows, int64_t cols, int64_t ld, int64_t stride,
+                      const void *stream_buf, size_t stream_bytes, int64_t *th, int64_t *tw)
+{
+    const bool pack = entry & kPack, batched = entry & kBatched;
+    if (any_null) return fail(MTQ_ERR_INVALID, kNullArg);
+    if (int rc = dtype_arg(dtype, pack ? "in_dtype" : "out_dtype")) return rc;
+    const int64_t grid_rows = entry & kTransposed ? cols : rows, grid_cols = entry & kTransposed ? rows : cols;
+    if (int rc = batched ? batch_grid(count, grid_rows, grid_cols, th, tw) : tile_grid(grid_rows, grid_cols, th, tw)) return rc;
+    if (int rc = batch_pitch(count, rows, cols, ld, stride, pack ? "ld < cols" : "ldy < cols")) return rc;
+    if (int rc = aligned_arg(stream_buf, pack ? "out" : "packed")) return rc;
+    if (int rc = stream_bytes_arg(stream_bytes, count * *th * *tw, pack ? "out" : "packed", batched)) return rc;
+    return require_device();
+}
+
+// whole 16-byte pieces of a matrix's rows: the base, the row pitch and, between the matrices of a batch, the stride
+static int tiles_vec_ok(const void *p, int dtype, int64_t ld, int64_t count, int64_t stride)
+{
+    const int64_t esz = dtype == MTQ_DTYPE_F32 ? 4 : 2;
+    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (ld * esz) % 16 == 0 && (count == 1 || (stride * esz) % 16 == 0);
+}
+
+extern "C" int mtq_pack_tiles(const void *x, int in_dtype, int64_t rows, int64_t cols, int64_t ld, const int8_t *map, const uint32_t *offsets,
+                              void *out, size_t out_bytes, void *stream)
+{
+    int64_t th, tw;
+    if (int rc = tiles_args(kPack, !x || !map || !offsets || !out, in_dtype, 1, rows, cols, ld, 0, out, out_bytes, &th, &tw)) return rc;
+    const int vec_ok = tiles_vec_ok(x, in_dtype, ld, 1, 0);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(th * tw));
+    if (in_dtype == MTQ_DTYPE_F32)
+        hipLaunchKernelGGL(pack_tiles_kernel<float>, grid, dim3(256), 0, st, static_cast<const float *>(x), rows, cols, ld, vec_ok, map, offsets,
+                           th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    else
+        hipLaunchKernelGGL(pack_tiles_kernel<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(x), rows, cols, ld, vec_ok, map, offsets,
+                           th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    return check_launch("mtq_pack_tiles");
+}
+
+extern "C" int mtq_unpack_tiles(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows, int64_t cols,
+                                void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    int64_t th, tw;
+    if (int rc = tiles_args(kUnpack, !packed || !map || !offsets || !y, out_dtype, 1, rows, cols, ldy, 0, packed, packed_bytes, &th, &tw)) return rc;
+    const int vec_ok = tiles_vec_ok(y, out_dtype, ldy, 1, 0);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(th * tw));
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(unpack_tiles_kernel<true>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy, vec_ok);
+    else
+        hipLaunchKernelGGL(unpack_tiles_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy, vec_ok);
+    return check_launch("mtq_unpack_tiles");
+}
+
+// The transposed pair: w / y in the stored orientation (rows × cols), the stream that of the cols × rows transpose.
+extern "C" int mtq_pack_tiles_transposed(const void *w, int in_dtype, int64_t rows, int64_t cols, int64_t ld, const int8_t *map,
+                                         const uint32_t *offsets, void *out, size_t out_bytes, void *stream)
+{
+    int64_t th, tw;                                   // of the transpose
+    if (int rc = tiles_args(kPack | kTransposed, !w || !map || !offsets || !out, in_dtype, 1, rows, cols, ld, 0, out, out_bytes, &th, &tw)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(th * tw));
+    if (in_dtype == MTQ_DTYPE_F32)
+        hipLaunchKernelGGL(pack_tiles_transposed_kernel<float>, grid, dim3(256), 0, st, static_cast<const float *>(w), rows, cols, ld, map, offsets,
+                           th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    else
+        hipLaunchKernelGGL(pack_tiles_transposed_kernel<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(w), rows, cols, ld, map,
+                           offsets, th * tw, tw, static_cast<uint8_t *>(out), (uint64_t)out_bytes);
+    return check_launch("mtq_pack_tiles_transposed");
+}
+
+extern "C" int mtq_unpack_tiles_transposed(const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t rows,
+                                           int64_t cols, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    int64_t th, tw;                                   // of the transpose
+    if (int rc = tiles_args(kUnpack | kTransposed, !packed || !map || !offsets || !y, out_dtype, 1, rows, cols, ldy, 0, packed, packed_bytes, &th, &tw))
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tile_blocks(th * tw));
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    if (out_dtype == MTQ_DTYPE_BF16)
+        hipLaunchKernelGGL(unpack_tiles_transposed_kernel<true>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy);
+    else
+        hipLaunchKernelGGL(unpack_tiles_transposed_kernel<false>, grid, dim3(256), 0, st, pp, (uint64_t)packed_bytes, map, offsets, th * tw, tw, rows, cols, y, ldy);
+    return check_launch("mtq_unpack_tiles_transposed");
+}
+
 extern "C" int mtq_packed_offsets_batched(const int8_t *maps, int64_t count, int64_t tiles, uint32_t *offsets, uint64_t *bases, int32_t *bad,
                                           void *stream)
 {
-    if (!maps || !offsets || !bases || !bad) return fail(MTQ_ERR_INVALID, "null argument");
+    if (!maps || !offsets || !bases || !bad) return fail(MTQ_ERR_INVALID, kNullArg);
     if (count <= 0) return fail(MTQ_ERR_INVALID, "count must be positive");
     if (tiles <= 0) return fail(MTQ_ERR_INVALID, "tiles must be positive");
     if (tiles > MTQ_PACKED_BATCH_MAX_TILES) return fail(MTQ_ERR_INVALID, "too many tiles: a tensor's stream must fit 32-bit units");
@@ -2412,16 +2374,11 @@ extern "C" int mtq_packed_offsets_batched(const int8_t *maps, int64_t count, int
 extern "C" int mtq_pack_tiles_batched(const void *x, int in_dtype, int64_t count, int64_t rows, int64_t cols, int64_t ld, int64_t stride,
                                       const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, void *out, size_t out_bytes, void *stream)
 {
-    if (!x || !maps || !offsets || !bases || !out) return fail(MTQ_ERR_INVALID, "null argument");
-    if (in_dtype != MTQ_DTYPE_BF16 && in_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "in_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
     int64_t th, tw;
-    if (int rc = batch_grid(count, rows, cols, &th, &tw)) return rc;
-    if (int rc = batch_pitch(count, rows, cols, ld, stride, "ld < cols")) return rc;
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(MTQ_ERR_INVALID, "out must be 16-byte aligned");
-    if (out_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "out_bytes is smaller than the streams");
-    if (int rc = require_device()) return rc;
-    const int64_t esz = in_dtype == MTQ_DTYPE_F32 ? 4 : 2;
-    const int vec_ok = reinterpret_cast<uintptr_t>(x) % 16 == 0 && (ld * esz) % 16 == 0 && (count == 1 || (stride * esz) % 16 == 0);
+    if (int rc = tiles_args(kPack | kBatched, !x || !maps || !offsets || !bases || !out, in_dtype, count, rows, cols, ld, stride, out, out_bytes, &th,
+                            &tw))
+        return rc;
+    const int vec_ok = tiles_vec_ok(x, in_dtype, ld, count, stride);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(tile_blocks(count * th * tw));
     if (in_dtype == MTQ_DTYPE_F32)
@@ -2436,16 +2393,11 @@ extern "C" int mtq_pack_tiles_batched(const void *x, int in_dtype, int64_t count
 extern "C" int mtq_unpack_tiles_batched(const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases,
                                         int64_t count, int64_t rows, int64_t cols, void *y, int out_dtype, int64_t ldy, int64_t stride, void *stream)
 {
-    if (!packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
     int64_t th, tw;
-    if (int rc = batch_grid(count, rows, cols, &th, &tw)) return rc;
-    if (int rc = batch_pitch(count, rows, cols, ldy, stride, "ldy < cols")) return rc;
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
-    if (int rc = require_device()) return rc;
-    const int64_t esz = out_dtype == MTQ_DTYPE_F32 ? 4 : 2;
-    const int vec_ok = reinterpret_cast<uintptr_t>(y) % 16 == 0 && (ldy * esz) % 16 == 0 && (count == 1 || (stride * esz) % 16 == 0);
+    if (int rc = tiles_args(kUnpack | kBatched, !packed || !maps || !offsets || !bases || !y, out_dtype, count, rows, cols, ldy, stride, packed,
+                            packed_bytes, &th, &tw))
+        return rc;
+    const int vec_ok = tiles_vec_ok(y, out_dtype, ldy, count, stride);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(tile_blocks(count * th * tw));
     const uint8_t *pp = static_cast<const uint8_t *>(packed);
@@ -2464,16 +2416,11 @@ extern "C" int mtq_pack_tiles_transposed_batched(const void *w, int in_dtype, in
                                                  const int8_t *maps, const uint32_t *offsets, const uint64_t *bases, void *out, size_t out_bytes,
                                                  void *stream)
 {
-    if (!w || !maps || !offsets || !bases || !out) return fail(MTQ_ERR_INVALID, "null argument");
-    if (in_dtype != MTQ_DTYPE_BF16 && in_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "in_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
     int64_t th, tw;                                   // of the transpose
-    if (int rc = batch_grid(count, cols, rows, &th, &tw)) return rc;
-    if (int rc = batch_pitch(count, rows, cols, ld, stride, "ld < cols")) return rc;
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(MTQ_ERR_INVALID, "out must be 16-byte aligned");
-    if (out_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "out_bytes is smaller than the streams");
-    if (int rc = require_device()) return rc;
-    const int64_t esz = in_dtype == MTQ_DTYPE_F32 ? 4 : 2;
-    const int vec_ok = reinterpret_cast<uintptr_t>(w) % 16 == 0 && (ld * esz) % 16 == 0 && (count == 1 || (stride * esz) % 16 == 0);
+    if (int rc = tiles_args(kPack | kTransposed | kBatched, !w || !maps || !offsets || !bases || !out, in_dtype, count, rows, cols, ld, stride, out,
+                            out_bytes, &th, &tw))
+        return rc;
+    const int vec_ok = tiles_vec_ok(w, in_dtype, ld, count, stride);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(tile_blocks(count * th * tw));
     if (in_dtype == MTQ_DTYPE_F32)
@@ -2489,14 +2436,10 @@ extern "C" int mtq_unpack_tiles_transposed_batched(const void *packed, size_t pa
                                                    const uint64_t *bases, int64_t count, int64_t rows, int64_t cols, void *y, int out_dtype,
                                                    int64_t ldy, int64_t stride, void *stream)
 {
-    if (!packed || !maps || !offsets || !bases || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
     int64_t th, tw;                                   // of the transpose
-    if (int rc = batch_grid(count, cols, rows, &th, &tw)) return rc;
-    if (int rc = batch_pitch(count, rows, cols, ldy, stride, "ldy < cols")) return rc;
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(count * th * tw) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the streams");
-    if (int rc = require_device()) return rc;
+    if (int rc = tiles_args(kUnpack | kTransposed | kBatched, !packed || !maps || !offsets || !bases || !y, out_dtype, count, rows, cols, ldy, stride,
+                            packed, packed_bytes, &th, &tw))
+        return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(tile_blocks(count * th * tw));
     const uint8_t *pp = static_cast<const uint8_t *>(packed);
@@ -2509,66 +2452,16 @@ extern "C" int mtq_unpack_tiles_transposed_batched(const void *packed, size_t pa
     return check_launch("mtq_unpack_tiles_transposed_batched");
 }
 
-// What the block and the wide entry check before a device is looked for, and the tile grid
-static int linear_args(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
-                       const uint32_t *offsets, int64_t n, const void *y, int out_dtype, int64_t ldy, int64_t *tiles_h, int64_t *tiles_w)
-{
-    if (!x || !packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
-    if (m <= 0) return fail(MTQ_ERR_INVALID, "m must be positive (empty operands are handled by the caller)");
-    if (int rc = tile_grid(n, k, tiles_h, tiles_w)) return rc;
-    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
-    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
-    if (m > (int64_t)1 << 40) return fail(MTQ_ERR_INVALID, "matrix too large");
-    if (reinterpret_cast<uintptr_t>(packed) % 16 != 0) return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    if (packed_bytes < (uint64_t)(*tiles_h * *tiles_w) * packed_tile_bytes(MTQ_FMT_BFP2)) return fail(MTQ_ERR_INVALID, "packed_bytes is smaller than the stream");
-    return MTQ_OK;
-}
-
-extern "C" int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
-                                 const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
-{
-    int64_t th, tw;
-    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, &th, &tw)) return rc;
-    const int64_t blocks = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
-    if (int rc = require_device()) return rc;
-    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *xp = static_cast<const uint16_t *>(x);
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
-    const dim3 grid((unsigned)blocks);
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(packed_linear_kernel<true>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th,
-                           tw, bias, y, ldy);
-    else
-        hipLaunchKernelGGL(packed_linear_kernel<false>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, th,
-                           tw, bias, y, ldy);
-    return check_launch("mtq_packed_linear");
-}
-
-// The product with a packed k × n matrix: the block entry's checks (the tile count of k × n is that of n × k), the grid the other way round.
-extern "C" int mtq_packed_matmul(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
-                                 const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
-{
-    int64_t tn, tk;
-    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, &tn, &tk)) return rc;
-    const int64_t blocks = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
-    if (int rc = require_device()) return rc;
-    const int x_vec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *xp = static_cast<const uint16_t *>(x);
-    const uint8_t *pp = static_cast<const uint8_t *>(packed);
-    const dim3 grid((unsigned)blocks);
-    if (out_dtype == MTQ_DTYPE_BF16)
-        hipLaunchKernelGGL(packed_matmul_kernel<true>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, tk,
-                           tn, bias, y, ldy);
-    else
-        hipLaunchKernelGGL(packed_matmul_kernel<false>, grid, dim3(kThreads), 0, st, xp, m, k, ldx, x_vec, pp, (uint64_t)packed_bytes, map, offsets, n, tk,
-                           tn, bias, y, ldy);
-    return check_launch("mtq_packed_matmul");
-}
+// ---- products.  Every entry for an (n, k) weight has a twin for a (k, n) matrix with the same arguments, checks, workspaces and texts:
+// a pair is ONE body below, which takes the orientation `kn` and the entry's name for check_launch, and the extern "C" entries forward
+// to it.  What kn changes is the kernel and which way round the kernel takes the tile grid: the checks form the grid of n × k (tile_grid
+// of n × k is the grid check of k × n), a kernel wants the grid of the stream as it was packed (TileGrid::sh / sw).
+struct TileGrid {
+    int64_t th, tw;                                  // the tile grid of one weight: th tiles along n, tw tiles along k
+    int eff;                                         // the effective split (the split entries)
+    int64_t sh(bool kn) const { return kn ? tw : th; }   // the stream's own grid, sh × sw
+    int64_t sw(bool kn) const { return kn ? th : tw; }
+};
 
 // One launch of the instantiation that stores a bf16 Y (kt) or an f32 Y (kf)
 template <typename... P, typename... A>
@@ -2577,42 +2470,64 @@ static void launch_out(int out_dtype, void (*kt)(P...), void (*kf)(P...), dim3 g
     hipLaunchKernelGGL(out_dtype == MTQ_DTYPE_BF16 ? kt : kf, grid, block, 0, st, args...);
 }
 
-// kernel<XV, BF16OUT> of a wide kernel template for (x_vec, out_dtype)
-#define MTQ_WIDE_PAIR(kernel, x_vec) (x_vec) ? kernel<true, true> : kernel<false, true>, (x_vec) ? kernel<true, false> : kernel<false, false>
+// launch_out's two kernels: <BF16OUT> of a twin pair's kernel templates for the orientation ...
+#define MTQ_TWIN_PAIR(kn, linear, matmul) (kn) ? matmul<true> : linear<true>, (kn) ? matmul<false> : linear<false>
+
+// ... and kernel<XV, BF16OUT, WT> of a wide kernel template for (x_vec, out_dtype, kn)
+#define MTQ_WIDE_OF(kernel, x_vec, out, kn)                                                                                                          \
+    ((kn) ? ((x_vec) ? kernel<true, out, true> : kernel<false, out, true>) : ((x_vec) ? kernel<true, out, false> : kernel<false, out, false>))
+#define MTQ_WIDE_PAIR(kernel, x_vec, kn) MTQ_WIDE_OF(kernel, x_vec, true, kn), MTQ_WIDE_OF(kernel, x_vec, false, kn)
 
 // whole pieces of 8 bf16 of x by 16-byte loads: every row aligned (a group may start at any row).  The wide kernels also want k % 8 == 0
 // and take any other x (a ragged k included) element by element.
 static bool x_vec_of(const void *x, int64_t ldx) { return reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0; }
+static bool x_vec_wide(const void *x, int64_t ldx, int64_t k) { return x_vec_of(x, ldx) && k % 8 == 0; }
+
+// No dimension of a grid may pass INT32_MAX.  The entries without a workspace say what the caller can do about it.
+static int grid_args(std::initializer_list<int64_t> dims, bool m_in_chunks = false)
+{
+    for (const int64_t d : dims)
+        if (d > INT32_MAX)
+            return fail(MTQ_ERR_INVALID, m_in_chunks ? "too many workgroups for one launch: pass M in chunks" : "too many workgroups for one launch");
+    return MTQ_OK;
+}
+
+// What the block and the wide entries check before a device is looked for, and the tile grid
+static int linear_args(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                       const uint32_t *offsets, int64_t n, const void *y, int out_dtype, int64_t ldy, TileGrid &g)
+{
+    if (!x || !packed || !map || !offsets || !y) return fail(MTQ_ERR_INVALID, kNullArg);
+    if (int rc = dtype_arg(out_dtype, "out_dtype")) return rc;
+    if (m <= 0) return fail(MTQ_ERR_INVALID, "m must be positive (empty operands are handled by the caller)");
+    if (int rc = tile_grid(n, k, &g.th, &g.tw)) return rc;
+    if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
+    if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
+    if (m > (int64_t)1 << 40) return fail(MTQ_ERR_INVALID, "matrix too large");
+    if (int rc = aligned_arg(packed, "packed")) return rc;
+    return stream_bytes_arg(packed_bytes, g.th * g.tw, "packed", false);
+}
 
 // The argument block of the skinny, grouped and wide-grouped entries, checked in the one order they all report in: the pointers, the
 // output type, the entry's shape rule (skinny_shape, grouped_shape, glu_grouped_shape: it fills g), the pitches, then the streams.
 // count == 0: a single tensor, else an arena of count; a gated entry passes both streams, any other its one stream twice.
-struct SplitGrid {
-    int64_t th, tw;                                  // the tile grid of one weight
-    int eff;                                         // the effective split
-};
-
 struct StreamArg {
     const void *packed;
     size_t bytes;
 };
 
 template <typename Shape>
-static int gemm_args(bool any_null, int out_dtype, Shape shape, SplitGrid &g, int64_t k, int64_t ldx, int64_t n, int64_t ldy, bool bias_rows,
+static int gemm_args(bool any_null, int out_dtype, Shape shape, TileGrid &g, int64_t k, int64_t ldx, int64_t n, int64_t ldy, bool bias_rows,
                      int64_t ldb, int64_t count, StreamArg a, StreamArg b)
 {
-    if (any_null) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    if (any_null) return fail(MTQ_ERR_INVALID, kNullArg);
+    if (int rc = dtype_arg(out_dtype, "out_dtype")) return rc;
     if (int rc = shape(g)) return rc;
     if (ldx < k) return fail(MTQ_ERR_INVALID, "ldx < k");
     if (ldy < n) return fail(MTQ_ERR_INVALID, "ldy < n");
     if (bias_rows && count > 1 && ldb < n) return fail(MTQ_ERR_INVALID, "ldb < n");
-    if (reinterpret_cast<uintptr_t>(a.packed) % 16 != 0 || reinterpret_cast<uintptr_t>(b.packed) % 16 != 0)
-        return fail(MTQ_ERR_INVALID, "packed must be 16-byte aligned");
-    const uint64_t least = (uint64_t)(std::max<int64_t>(count, 1) * g.th * g.tw) * packed_tile_bytes(MTQ_FMT_BFP2);
-    if (a.bytes < least || b.bytes < least)
-        return fail(MTQ_ERR_INVALID, count ? "packed_bytes is smaller than the streams" : "packed_bytes is smaller than the stream");
-    return MTQ_OK;
+    if (int rc = aligned_arg(a.packed, "packed")) return rc;
+    if (int rc = aligned_arg(b.packed, "packed")) return rc;
+    return stream_bytes_arg(std::min(a.bytes, b.bytes), std::max<int64_t>(count, 1) * g.th * g.tw, "packed", count != 0);
 }
 
 // The workspace block: need == 0 asks for none; null_msg says why this entry needs one, `whose` is "split" or "call"
@@ -2620,7 +2535,7 @@ static int workspace_args(const void *workspace, size_t workspace_bytes, size_t 
 {
     if (need == 0) return MTQ_OK;
     if (!workspace) return fail(MTQ_ERR_INVALID, null_msg);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(MTQ_ERR_INVALID, "workspace must be 16-byte aligned");
+    if (int rc = aligned_arg(workspace, "workspace")) return rc;
     if (workspace_bytes < need)
         return failf(MTQ_ERR_INVALID, "workspace_bytes %zu is smaller than the %zu bytes this %s needs", workspace_bytes, need, whose);
     return MTQ_OK;
@@ -2628,115 +2543,191 @@ static int workspace_args(const void *workspace, size_t workspace_bytes, size_t 
 
 static const char *const kWsSplit = "workspace is null and this split needs one";
 static const char *const kWsPlan = "workspace is null and the block plan needs one";
+static const char *const kWsChunks = "workspace is null and the chunk plan needs one at every split";
 static const char *const kWsGlu = "workspace is null: the partial sums of both projections need one at every split";
+
+// The grouped entries' plan region: start[0 .. count] as int32 at the head of the workspace, rounded to 16 so that the f32 partials
+// behind it keep the workspace's alignment.  A function of count alone.
+static size_t grouped_plan_bytes(int64_t count)
+{
+    return (((size_t)count + 1) * sizeof(int32_t) + 15) & ~(size_t)15;
+}
+
+// The plan's slot bound for pieces of `rows` rows (32-row chunks, 128-row blocks), formed from (total_rows, count) alone: every piece
+// of disjoint groups has a slot, since a group with rows adds at most (rows - 1) / rows of a piece over its own rows / rows.
+static int64_t grouped_slots(int64_t total_rows, int64_t count, int64_t rows)
+{
+    return (total_rows + (rows - 1) * std::min(count, total_rows)) / rows;
+}
+
+// The plan on the stream, before the kernel that searches it
+template <int ROWS>
+static int launch_plan(const char *name, hipStream_t st, const int32_t *group_rows, int64_t count, int64_t total_rows, int32_t *start)
+{
+    hipLaunchKernelGGL(packed_grouped_plan_kernel<ROWS>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, start);
+    return check_launch(name);
+}
+
+// The grouped reduces walk a group's columns in chunks of 256: count × grouped_nchunks(n) workgroups
+static int64_t grouped_nchunks(int64_t n) { return (n + 255) / 256; }
+
+// 1. block
+static int packed_block(bool kn, const char *name, const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes,
+                        const int8_t *map, const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    TileGrid g;
+    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, g)) return rc;
+    const int64_t blocks = ((m + kBM - 1) / kBM) * ((n + kBN - 1) / kBN);
+    if (int rc = grid_args({blocks}, true)) return rc;
+    if (int rc = require_device()) return rc;
+    launch_out(out_dtype, MTQ_TWIN_PAIR(kn, packed_linear_kernel, packed_matmul_kernel), dim3((unsigned)blocks), dim3(kThreads),
+               static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(x), m, k, ldx, (int)x_vec_of(x, ldx),
+               static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map, offsets, n, g.sh(kn), g.sw(kn), bias, y, ldy);
+    return check_launch(name);
+}
+
+extern "C" int mtq_packed_linear(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                                 const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    return packed_block(false, "mtq_packed_linear", x, m, k, ldx, packed, packed_bytes, map, offsets, n, bias, y, out_dtype, ldy, stream);
+}
+
+extern "C" int mtq_packed_matmul(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
+                                 const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    return packed_block(true, "mtq_packed_matmul", x, m, k, ldx, packed, packed_bytes, map, offsets, n, bias, y, out_dtype, ldy, stream);
+}
+
+// 2. wide
+static int packed_wide(bool kn, const char *name, const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes,
+                       const int8_t *map, const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    TileGrid g;
+    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, g)) return rc;
+    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kWideBN - 1) / kWideBN);
+    if (int rc = grid_args({blocks}, true)) return rc;
+    if (int rc = require_device()) return rc;
+    const bool x_vec = x_vec_wide(x, ldx, k);
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_wide_kernel, x_vec, kn), dim3((unsigned)blocks), dim3(kThreads), static_cast<hipStream_t>(stream),
+               static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map, offsets, n, g.sh(kn),
+               g.sw(kn), bias, y, ldy);
+    return check_launch(name);
+}
 
 extern "C" int mtq_packed_linear_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                                       const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
 {
-    int64_t th, tw;
-    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, &th, &tw)) return rc;
-    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kWideBN - 1) / kWideBN);
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
-    if (int rc = require_device()) return rc;
-    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
-    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_linear_wide_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), static_cast<hipStream_t>(stream),
-               static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map, offsets, n, th, tw, bias,
-               y, ldy);
-    return check_launch("mtq_packed_linear_wide");
+    return packed_wide(false, "mtq_packed_linear_wide", x, m, k, ldx, packed, packed_bytes, map, offsets, n, bias, y, out_dtype, ldy, stream);
 }
 
-// The wide product with a packed k × n matrix: mtq_packed_matmul's checks and texts, the wide block's grid.
 extern "C" int mtq_packed_matmul_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                                       const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
 {
-    int64_t tn, tk;
-    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, &tn, &tk)) return rc;
-    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kWideBN - 1) / kWideBN);
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
-    if (int rc = require_device()) return rc;
-    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
-    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_matmul_wide_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), static_cast<hipStream_t>(stream),
-               static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map, offsets, n, tk, tn, bias,
-               y, ldy);
-    return check_launch("mtq_packed_matmul_wide");
+    return packed_wide(true, "mtq_packed_matmul_wide", x, m, k, ldx, packed, packed_bytes, map, offsets, n, bias, y, out_dtype, ldy, stream);
 }
 
+// 3. skinny
 extern "C" size_t mtq_packed_linear_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
 {
-    int64_t th, tw;
-    int eff;
-    if (skinny_shape(m, n, k, split, &th, &tw, &eff)) return (size_t)-1;
-    return skinny_workspace(m, n, eff);
+    TileGrid g;
+    if (skinny_shape(m, n, k, split, &g.th, &g.tw, &g.eff)) return (size_t)-1;
+    return skinny_workspace(m, n, g.eff);
+}
+
+extern "C" size_t mtq_packed_matmul_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_linear_skinny_workspace_bytes(m, n, k, split);
+}
+
+static int packed_skinny(bool kn, const char *name, const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes,
+                         const int8_t *map, const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
+                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    TileGrid g;
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !packed || !map || !offsets || !y, out_dtype,
+                           [&](TileGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0, w, w))
+        return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(m, n, g.eff), kWsSplit, "split")) return rc;
+    const int64_t blocks = (g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (int rc = grid_args({blocks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    launch_out(out_dtype, MTQ_TWIN_PAIR(kn, packed_linear_skinny_kernel, packed_matmul_skinny_kernel), dim3((unsigned)blocks),
+               dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), m, k, ldx, (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(packed),
+               (uint64_t)packed_bytes, map, offsets, n, g.sh(kn), g.sw(kn), g.eff, bias, y, ldy, ws);
+    if (g.eff > 1) {
+        if (int rc = check_launch(name)) return rc;
+        launch_out(out_dtype, skinny_reduce_kernel<true>, skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
+                   m * n, n, g.eff, bias, y, ldy);
+    }
+    return check_launch(name);
 }
 
 extern "C" int mtq_packed_linear_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                                         const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    SplitGrid g;
-    const StreamArg w = {packed, packed_bytes};
-    if (int rc = gemm_args(!x || !packed || !map || !offsets || !y, out_dtype,
-                           [&](SplitGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0, w, w))
-        return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(m, n, g.eff), kWsSplit, "split")) return rc;
-    const int64_t blocks = (g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws = static_cast<float *>(workspace);
-    launch_out(out_dtype, packed_linear_skinny_kernel<true>, packed_linear_skinny_kernel<false>, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), st,
-               static_cast<const uint16_t *>(x), m, k, ldx, (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map,
-               offsets, n, g.th, g.tw, g.eff, bias, y, ldy, ws);
-    if (g.eff > 1) {
-        if (int rc = check_launch("mtq_packed_linear_skinny")) return rc;
-        launch_out(out_dtype, skinny_reduce_kernel<true>, skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
-                   m * n, n, g.eff, bias, y, ldy);
-    }
-    return check_launch("mtq_packed_linear_skinny");
-}
-
-// The skinny product with a packed k × n matrix: the skinny entry's checks and split rule (tile_grid of n × k is the grid check of k × n),
-// the grid the other way round.
-extern "C" size_t mtq_packed_matmul_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
-{
-    int64_t tn, tk;
-    int eff;
-    if (skinny_shape(m, n, k, split, &tn, &tk, &eff)) return (size_t)-1;
-    return skinny_workspace(m, n, eff);
+    return packed_skinny(false, "mtq_packed_linear_skinny", x, m, k, ldx, packed, packed_bytes, map, offsets, n, bias, y, out_dtype, ldy, split,
+                         workspace, workspace_bytes, stream);
 }
 
 extern "C" int mtq_packed_matmul_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes, const int8_t *map,
                                         const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, int split,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
+    return packed_skinny(true, "mtq_packed_matmul_skinny", x, m, k, ldx, packed, packed_bytes, map, offsets, n, bias, y, out_dtype, ldy, split,
+                         workspace, workspace_bytes, stream);
+}
+
+// 4. skinny grouped, and 5. its chunked form.  Both end in the same reduce when the split is above 1.
+extern "C" size_t mtq_packed_linear_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    TileGrid g;
+    if (grouped_shape(total_rows, count, n, k, split, &g.th, &g.tw, &g.eff)) return (size_t)-1;
+    return skinny_workspace(total_rows, n, g.eff);
+}
+
+extern "C" size_t mtq_packed_matmul_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_linear_skinny_grouped_workspace_bytes(total_rows, count, n, k, split);
+}
+
+static int grouped_reduce(const char *name, int out_dtype, hipStream_t st, const float *ws, int64_t total_rows, int64_t n, int split,
+                          const int32_t *group_rows, int64_t count, const float *bias, int64_t ldb, void *y, int64_t ldy)
+{
+    if (split > 1) {
+        if (int rc = check_launch(name)) return rc;
+        const int64_t nchunks = grouped_nchunks(n);
+        launch_out(out_dtype, skinny_grouped_reduce_kernel<true>, skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
+                   st, ws, total_rows, n, split, group_rows, nchunks, bias, ldb, y, ldy);
+    }
+    return check_launch(name);
+}
+
+static int packed_skinny_grouped(bool kn, const char *name, const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                 const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases,
+                                 int64_t count, int64_t n, const float *bias, int64_t ldb, void *y, int out_dtype, int64_t ldy, int split,
+                                 void *workspace, size_t workspace_bytes, void *stream)
+{
+    TileGrid g;
     const StreamArg w = {packed, packed_bytes};
-    if (int rc = gemm_args(!x || !packed || !map || !offsets || !y, out_dtype,
-                           [&](SplitGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0, w, w))
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](TileGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
+                           bias != nullptr, ldb, count, w, w))
         return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(m, n, g.eff), kWsSplit, "split")) return rc;
-    const int64_t blocks = (g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
+    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(total_rows, n, g.eff), kWsSplit, "split")) return rc;
+    const int64_t blocks = (count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (int rc = grid_args({blocks, count * grouped_nchunks(n)})) return rc;
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *ws = static_cast<float *>(workspace);
-    launch_out(out_dtype, packed_matmul_skinny_kernel<true>, packed_matmul_skinny_kernel<false>, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), st,
-               static_cast<const uint16_t *>(x), m, k, ldx, (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, map,
-               offsets, n, g.tw, g.th, g.eff, bias, y, ldy, ws);
-    if (g.eff > 1) {
-        if (int rc = check_launch("mtq_packed_matmul_skinny")) return rc;
-        launch_out(out_dtype, skinny_reduce_kernel<true>, skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
-                   m * n, n, g.eff, bias, y, ldy);
-    }
-    return check_launch("mtq_packed_matmul_skinny");
-}
-
-extern "C" size_t mtq_packed_linear_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
-{
-    int64_t th, tw;
-    int eff;
-    if (grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
-    return skinny_workspace(total_rows, n, eff);
+    launch_out(out_dtype, MTQ_TWIN_PAIR(kn, packed_linear_skinny_grouped_kernel, packed_matmul_skinny_grouped_kernel), dim3((unsigned)blocks),
+               dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx), group_rows,
+               static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.sh(kn), g.sw(kn), g.eff, bias, ldb, y,
+               ldy, ws);
+    return grouped_reduce(name, out_dtype, st, ws, total_rows, n, g.eff, group_rows, count, bias, ldb, y, ldy);
 }
 
 extern "C" int mtq_packed_linear_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
@@ -2744,43 +2735,57 @@ extern "C" int mtq_packed_linear_skinny_grouped(const void *x, int64_t total_row
                                                 const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
                                                 int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
 {
-    SplitGrid g;
-    const StreamArg w = {packed, packed_bytes};
-    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
-                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
-                           bias != nullptr, ldb, count, w, w))
-        return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(total_rows, n, g.eff), kWsSplit, "split")) return rc;
-    const int64_t blocks = (count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    const int64_t nchunks = (n + 255) / 256;
-    if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws = static_cast<float *>(workspace);
-    launch_out(out_dtype, packed_linear_skinny_grouped_kernel<true>, packed_linear_skinny_grouped_kernel<false>, dim3((unsigned)blocks),
-               dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx), group_rows,
-               static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.th, g.tw, g.eff, bias, ldb, y, ldy, ws);
-    if (g.eff > 1) {
-        if (int rc = check_launch("mtq_packed_linear_skinny_grouped")) return rc;
-        launch_out(out_dtype, skinny_grouped_reduce_kernel<true>, skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
-                   st, ws, total_rows, n, g.eff, group_rows, nchunks, bias, ldb, y, ldy);
-    }
-    return check_launch("mtq_packed_linear_skinny_grouped");
+    return packed_skinny_grouped(false, "mtq_packed_linear_skinny_grouped", x, total_rows, k, ldx, group_rows, packed, packed_bytes, maps, offsets,
+                                 bases, count, n, bias, ldb, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
 }
 
-// The chunked entry's plan region: cstart[0 .. count] as int32 at the head of the workspace, rounded to 16 so that the f32 partials
-// behind it keep the workspace's alignment.  A function of count alone.
-static size_t grouped_plan_bytes(int64_t count)
+extern "C" int mtq_packed_matmul_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                                const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                                int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return (((size_t)count + 1) * sizeof(int32_t) + 15) & ~(size_t)15;
+    return packed_skinny_grouped(true, "mtq_packed_matmul_skinny_grouped", x, total_rows, k, ldx, group_rows, packed, packed_bytes, maps, offsets,
+                                 bases, count, n, bias, ldb, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t mtq_packed_linear_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
 {
-    int64_t th, tw;
-    int eff;
-    if (grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
-    return grouped_plan_bytes(count) + skinny_workspace(total_rows, n, eff);
+    TileGrid g;
+    if (grouped_shape(total_rows, count, n, k, split, &g.th, &g.tw, &g.eff)) return (size_t)-1;
+    return grouped_plan_bytes(count) + skinny_workspace(total_rows, n, g.eff);
+}
+
+extern "C" size_t mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_linear_skinny_grouped_chunked_workspace_bytes(total_rows, count, n, k, split);
+}
+
+static int packed_skinny_grouped_chunked(bool kn, const char *name, const void *x, int64_t total_rows, int64_t k, int64_t ldx,
+                                         const int32_t *group_rows, const void *packed, size_t packed_bytes, const int8_t *maps,
+                                         const uint32_t *offsets, const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb,
+                                         void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    TileGrid g;
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](TileGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
+                           bias != nullptr, ldb, count, w, w))
+        return rc;
+    const size_t plan = grouped_plan_bytes(count);
+    if (int rc = workspace_args(workspace, workspace_bytes, plan + skinny_workspace(total_rows, n, g.eff), kWsChunks, "call")) return rc;
+    const int64_t slots = grouped_slots(total_rows, count, kTile);
+    const int64_t blocks = (slots * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (int rc = grid_args({slots, blocks, count * grouped_nchunks(n)})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *cstart = static_cast<int32_t *>(workspace);
+    float *ws = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + plan);
+    if (int rc = launch_plan<kTile>(name, st, group_rows, count, total_rows, cstart)) return rc;
+    launch_out(out_dtype, MTQ_TWIN_PAIR(kn, packed_linear_skinny_grouped_chunked_kernel, packed_matmul_skinny_grouped_chunked_kernel),
+               dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx),
+               group_rows, cstart, (int)slots, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n,
+               g.sh(kn), g.sw(kn), g.eff, bias, ldb, y, ldy, ws);
+    return grouped_reduce(name, out_dtype, st, ws, total_rows, n, g.eff, group_rows, count, bias, ldb, y, ldy);
 }
 
 extern "C" int mtq_packed_linear_skinny_grouped_chunked(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
@@ -2789,121 +2794,8 @@ extern "C" int mtq_packed_linear_skinny_grouped_chunked(const void *x, int64_t t
                                                         int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
                                                         void *stream)
 {
-    SplitGrid g;
-    const StreamArg w = {packed, packed_bytes};
-    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
-                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
-                           bias != nullptr, ldb, count, w, w))
-        return rc;
-    const size_t plan = grouped_plan_bytes(count);
-    if (int rc = workspace_args(workspace, workspace_bytes, plan + skinny_workspace(total_rows, n, g.eff),
-                                "workspace is null and the chunk plan needs one at every split", "call"))
-        return rc;
-    // every chunk of disjoint groups has a slot: a group with rows adds at most 31/32 of a chunk over its rows / 32
-    const int64_t slots = (total_rows + 31 * std::min(count, total_rows)) / kTile;
-    const int64_t blocks = (slots * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    const int64_t nchunks = (n + 255) / 256;
-    if (slots > INT32_MAX || blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t *cstart = static_cast<int32_t *>(workspace);
-    float *ws = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + plan);
-    hipLaunchKernelGGL(packed_grouped_plan_kernel<kTile>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, cstart);
-    if (int rc = check_launch("mtq_packed_linear_skinny_grouped_chunked")) return rc;
-    launch_out(out_dtype, packed_linear_skinny_grouped_chunked_kernel<true>, packed_linear_skinny_grouped_chunked_kernel<false>,
-               dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx),
-               group_rows, cstart, (int)slots, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.th, g.tw,
-               g.eff, bias, ldb, y, ldy, ws);
-    if (g.eff > 1) {
-        if (int rc = check_launch("mtq_packed_linear_skinny_grouped_chunked")) return rc;
-        launch_out(out_dtype, skinny_grouped_reduce_kernel<true>, skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
-                   st, ws, total_rows, n, g.eff, group_rows, nchunks, bias, ldb, y, ldy);
-    }
-    return check_launch("mtq_packed_linear_skinny_grouped_chunked");
-}
-
-extern "C" size_t mtq_packed_linear_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
-{
-    int64_t th, tw;
-    int eff;
-    if (grouped_shape(total_rows, count, n, k, 1, &th, &tw, &eff)) return (size_t)-1;   // split 1: no split over K, no partials
-    return grouped_plan_bytes(count);
-}
-
-
-extern "C" int mtq_packed_linear_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
-                                              const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
-                                              const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
-                                              int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream)
-{
-    SplitGrid g;
-    const StreamArg w = {packed, packed_bytes};
-    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
-                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
-                           bias != nullptr, ldb, count, w, w))
-        return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
-    // every block of disjoint groups has a slot: a group with rows adds at most 127/128 of a block over its rows / 128
-    const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
-    const int64_t blocks = slots * ((n + kWideBN - 1) / kWideBN);
-    if (slots > INT32_MAX || blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t *bstart = static_cast<int32_t *>(workspace);
-    hipLaunchKernelGGL(packed_grouped_plan_kernel<kWideBM>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
-    if (int rc = check_launch("mtq_packed_linear_wide_grouped")) return rc;
-    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
-    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_linear_wide_grouped_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), st,
-               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(packed),
-               (uint64_t)packed_bytes, maps, offsets, bases, (int)count, n, g.th, g.tw, bias, ldb, y, ldy);
-    return check_launch("mtq_packed_linear_wide_grouped");
-}
-
-// ---- grouped entries for (k, n) experts: the grouped linear entries' checks, split rule, slot bounds and workspaces (tile_grid of n × k
-// is the grid check of k × n, mtq_packed_matmul's), the kernels with the grid the other way round.
-extern "C" size_t mtq_packed_matmul_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
-{
-    int64_t th, tw;
-    int eff;
-    if (grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
-    return skinny_workspace(total_rows, n, eff);
-}
-
-extern "C" int mtq_packed_matmul_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
-                                                const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
-                                                const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
-                                                int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
-{
-    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
-    const StreamArg w = {packed, packed_bytes};
-    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
-                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
-                           bias != nullptr, ldb, count, w, w))
-        return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(total_rows, n, g.eff), kWsSplit, "split")) return rc;
-    const int64_t blocks = (count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    const int64_t nchunks = (n + 255) / 256;
-    if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws = static_cast<float *>(workspace);
-    launch_out(out_dtype, packed_matmul_skinny_grouped_kernel<true>, packed_matmul_skinny_grouped_kernel<false>, dim3((unsigned)blocks),
-               dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx), group_rows,
-               static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.tw, g.th, g.eff, bias, ldb, y, ldy, ws);
-    if (g.eff > 1) {
-        if (int rc = check_launch("mtq_packed_matmul_skinny_grouped")) return rc;
-        launch_out(out_dtype, skinny_grouped_reduce_kernel<true>, skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
-                   st, ws, total_rows, n, g.eff, group_rows, nchunks, bias, ldb, y, ldy);
-    }
-    return check_launch("mtq_packed_matmul_skinny_grouped");
-}
-
-extern "C" size_t mtq_packed_matmul_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
-{
-    int64_t th, tw;
-    int eff;
-    if (grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
-    return grouped_plan_bytes(count) + skinny_workspace(total_rows, n, eff);
+    return packed_skinny_grouped_chunked(false, "mtq_packed_linear_skinny_grouped_chunked", x, total_rows, k, ldx, group_rows, packed, packed_bytes,
+                                         maps, offsets, bases, count, n, bias, ldb, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mtq_packed_matmul_skinny_grouped_chunked(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
@@ -2912,45 +2804,56 @@ extern "C" int mtq_packed_matmul_skinny_grouped_chunked(const void *x, int64_t t
                                                         int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
                                                         void *stream)
 {
-    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
-    const StreamArg w = {packed, packed_bytes};
-    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
-                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
-                           bias != nullptr, ldb, count, w, w))
-        return rc;
-    const size_t plan = grouped_plan_bytes(count);
-    if (int rc = workspace_args(workspace, workspace_bytes, plan + skinny_workspace(total_rows, n, g.eff),
-                                "workspace is null and the chunk plan needs one at every split", "call"))
-        return rc;
-    // every chunk of disjoint groups has a slot: a group with rows adds at most 31/32 of a chunk over its rows / 32
-    const int64_t slots = (total_rows + 31 * std::min(count, total_rows)) / kTile;
-    const int64_t blocks = (slots * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    const int64_t nchunks = (n + 255) / 256;
-    if (slots > INT32_MAX || blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t *cstart = static_cast<int32_t *>(workspace);
-    float *ws = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + plan);
-    hipLaunchKernelGGL(packed_grouped_plan_kernel<kTile>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, cstart);
-    if (int rc = check_launch("mtq_packed_matmul_skinny_grouped_chunked")) return rc;
-    launch_out(out_dtype, packed_matmul_skinny_grouped_chunked_kernel<true>, packed_matmul_skinny_grouped_chunked_kernel<false>,
-               dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), st, static_cast<const uint16_t *>(x), total_rows, k, ldx, (int)x_vec_of(x, ldx),
-               group_rows, cstart, (int)slots, static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.tw, g.th,
-               g.eff, bias, ldb, y, ldy, ws);
-    if (g.eff > 1) {
-        if (int rc = check_launch("mtq_packed_matmul_skinny_grouped_chunked")) return rc;
-        launch_out(out_dtype, skinny_grouped_reduce_kernel<true>, skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
-                   st, ws, total_rows, n, g.eff, group_rows, nchunks, bias, ldb, y, ldy);
-    }
-    return check_launch("mtq_packed_matmul_skinny_grouped_chunked");
+    return packed_skinny_grouped_chunked(true, "mtq_packed_matmul_skinny_grouped_chunked", x, total_rows, k, ldx, group_rows, packed, packed_bytes,
+                                         maps, offsets, bases, count, n, bias, ldb, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
+}
+
+// 6. wide grouped
+extern "C" size_t mtq_packed_linear_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
+{
+    TileGrid g;
+    if (grouped_shape(total_rows, count, n, k, 1, &g.th, &g.tw, &g.eff)) return (size_t)-1;   // split 1: no split over K, no partials
+    return grouped_plan_bytes(count);
 }
 
 extern "C" size_t mtq_packed_matmul_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
 {
-    int64_t th, tw;
-    int eff;
-    if (grouped_shape(total_rows, count, n, k, 1, &th, &tw, &eff)) return (size_t)-1;   // split 1: no split over K, no partials
-    return grouped_plan_bytes(count);
+    return mtq_packed_linear_wide_grouped_workspace_bytes(total_rows, count, n, k);
+}
+
+static int packed_wide_grouped(bool kn, const char *name, const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                               const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases,
+                               int64_t count, int64_t n, const float *bias, int64_t ldb, void *y, int out_dtype, int64_t ldy, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    TileGrid g;
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](TileGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
+                           bias != nullptr, ldb, count, w, w))
+        return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
+    const int64_t slots = grouped_slots(total_rows, count, kWideBM);
+    const int64_t blocks = slots * ((n + kWideBN - 1) / kWideBN);
+    if (int rc = grid_args({slots, blocks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *bstart = static_cast<int32_t *>(workspace);
+    if (int rc = launch_plan<kWideBM>(name, st, group_rows, count, total_rows, bstart)) return rc;
+    const bool x_vec = x_vec_wide(x, ldx, k);
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_wide_grouped_kernel, x_vec, kn), dim3((unsigned)blocks), dim3(kThreads), st,
+               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(packed),
+               (uint64_t)packed_bytes, maps, offsets, bases, (int)count, n, g.sh(kn), g.sw(kn), bias, ldb, y, ldy);
+    return check_launch(name);
+}
+
+extern "C" int mtq_packed_linear_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                              const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                              const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
+                                              int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return packed_wide_grouped(false, "mtq_packed_linear_wide_grouped", x, total_rows, k, ldx, group_rows, packed, packed_bytes, maps, offsets, bases,
+                               count, n, bias, ldb, y, out_dtype, ldy, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mtq_packed_matmul_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
@@ -2958,27 +2861,8 @@ extern "C" int mtq_packed_matmul_wide_grouped(const void *x, int64_t total_rows,
                                               const uint64_t *bases, int64_t count, int64_t n, const float *bias, int64_t ldb, void *y,
                                               int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream)
 {
-    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
-    const StreamArg w = {packed, packed_bytes};
-    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
-                           [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy,
-                           bias != nullptr, ldb, count, w, w))
-        return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
-    // every block of disjoint groups has a slot: a group with rows adds at most 127/128 of a block over its rows / 128
-    const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
-    const int64_t blocks = slots * ((n + kWideBN - 1) / kWideBN);
-    if (slots > INT32_MAX || blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t *bstart = static_cast<int32_t *>(workspace);
-    hipLaunchKernelGGL(packed_grouped_plan_kernel<kWideBM>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
-    if (int rc = check_launch("mtq_packed_matmul_wide_grouped")) return rc;
-    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
-    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_matmul_wide_grouped_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), st,
-               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(packed),
-               (uint64_t)packed_bytes, maps, offsets, bases, (int)count, n, g.tw, g.th, bias, ldb, y, ldy);
-    return check_launch("mtq_packed_matmul_wide_grouped");
+    return packed_wide_grouped(true, "mtq_packed_matmul_wide_grouped", x, total_rows, k, ldx, group_rows, packed, packed_bytes, maps, offsets, bases,
+                               count, n, bias, ldb, y, out_dtype, ldy, workspace, workspace_bytes, stream);
 }
 
 // ---- gated entries
@@ -2991,8 +2875,8 @@ static int glu_act(int act)
 extern "C" int mtq_glu_combine(const float *g, int64_t ldg, const float *u, int64_t ldu, int64_t rows, int64_t cols, int act, void *y,
                                int out_dtype, int64_t ldy, void *stream)
 {
-    if (!g || !u || !y) return fail(MTQ_ERR_INVALID, "null argument");
-    if (out_dtype != MTQ_DTYPE_BF16 && out_dtype != MTQ_DTYPE_F32) return fail(MTQ_ERR_INVALID, "out_dtype must be MTQ_DTYPE_BF16 or MTQ_DTYPE_F32");
+    if (!g || !u || !y) return fail(MTQ_ERR_INVALID, kNullArg);
+    if (int rc = dtype_arg(out_dtype, "out_dtype")) return rc;
     if (rows <= 0 || cols <= 0) return fail(MTQ_ERR_INVALID, "rows and cols must be positive (empty operands are handled by the caller)");
     if (rows > (int64_t)1 << 40 || cols > (int64_t)1 << 30 || rows > ((int64_t)1 << 56) / cols) return fail(MTQ_ERR_INVALID, "matrix too large");
     if (ldg < cols) return fail(MTQ_ERR_INVALID, "ldg < cols");
@@ -3001,37 +2885,89 @@ extern "C" int mtq_glu_combine(const float *g, int64_t ldg, const float *u, int6
     if (int rc = glu_act(act)) return rc;
     if (int rc = require_device()) return rc;
     const dim3 grid((unsigned)std::min<int64_t>((rows * cols + 255) / 256, (int64_t)1 << 20));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (out_dtype == MTQ_DTYPE_BF16) hipLaunchKernelGGL(glu_combine_kernel<true>, grid, dim3(256), 0, st, g, ldg, u, ldu, rows, cols, act, y, ldy);
-    else hipLaunchKernelGGL(glu_combine_kernel<false>, grid, dim3(256), 0, st, g, ldg, u, ldu, rows, cols, act, y, ldy);
+    launch_out(out_dtype, glu_combine_kernel<true>, glu_combine_kernel<false>, grid, dim3(256), static_cast<hipStream_t>(stream), g, ldg, u, ldu, rows,
+               cols, act, y, ldy);
     return check_launch("mtq_glu_combine");
 }
 
+// 7. glu wide
+static int packed_glu_wide(bool kn, const char *name, const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                           const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes, const int8_t *up_map,
+                           const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up, int act, void *y, int out_dtype,
+                           int64_t ldy, void *stream)
+{
+    TileGrid g;
+    if (int rc = linear_args(x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, n, y, out_dtype, ldy, g)) return rc;
+    if (int rc = linear_args(x, m, k, ldx, up_packed, up_bytes, up_map, up_offsets, n, y, out_dtype, ldy, g)) return rc;
+    if (int rc = glu_act(act)) return rc;
+    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kGluBN - 1) / kGluBN);
+    if (int rc = grid_args({blocks}, true)) return rc;
+    if (int rc = require_device()) return rc;
+    const bool x_vec = x_vec_wide(x, ldx, k);
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_wide_kernel, x_vec, kn), dim3((unsigned)blocks), dim3(kThreads), static_cast<hipStream_t>(stream),
+               static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
+               static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, g.sh(kn), g.sw(kn), bias_gate, bias_up, act, y, ldy);
+    return check_launch(name);
+}
 
 extern "C" int mtq_packed_glu_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
                                    const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
                                    const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up,
                                    int act, void *y, int out_dtype, int64_t ldy, void *stream)
 {
-    int64_t th, tw;
-    if (int rc = linear_args(x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, n, y, out_dtype, ldy, &th, &tw)) return rc;
-    if (int rc = linear_args(x, m, k, ldx, up_packed, up_bytes, up_map, up_offsets, n, y, out_dtype, ldy, &th, &tw)) return rc;
-    if (int rc = glu_act(act)) return rc;
-    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kGluBN - 1) / kGluBN);
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
-    if (int rc = require_device()) return rc;
-    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
-    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_wide_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), static_cast<hipStream_t>(stream),
-               static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
-               static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, th, tw, bias_gate, bias_up, act, y, ldy);
-    return check_launch("mtq_packed_glu_wide");
+    return packed_glu_wide(false, "mtq_packed_glu_wide", x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, up_packed, up_bytes, up_map,
+                           up_offsets, n, bias_gate, bias_up, act, y, out_dtype, ldy, stream);
 }
 
+extern "C" int mtq_packed_glu_matmul_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                                          const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
+                                          const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate,
+                                          const float *bias_up, int act, void *y, int out_dtype, int64_t ldy, void *stream)
+{
+    return packed_glu_wide(true, "mtq_packed_glu_matmul_wide", x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, up_packed, up_bytes,
+                           up_map, up_offsets, n, bias_gate, bias_up, act, y, out_dtype, ldy, stream);
+}
+
+// 8. glu wide grouped: the wide grouped entry's plan and slot bound, column blocks of kGluBN
 extern "C" size_t mtq_packed_glu_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
 {
     return mtq_packed_linear_wide_grouped_workspace_bytes(total_rows, count, n, k);   // the same plan
 }
 
+extern "C" size_t mtq_packed_glu_matmul_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
+{
+    return mtq_packed_glu_wide_grouped_workspace_bytes(total_rows, count, n, k);
+}
+
+static int packed_glu_wide_grouped(bool kn, const char *name, const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                   const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                   const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                   const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n, const float *bias_gate,
+                                   const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, void *workspace,
+                                   size_t workspace_bytes, void *stream)
+{
+    TileGrid g;
+    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
+                               !up_bases || !y,
+                           out_dtype, [&](TileGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n,
+                           ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
+    if (int rc = glu_act(act)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
+    const int64_t slots = grouped_slots(total_rows, count, kWideBM);
+    const int64_t blocks = slots * ((n + kGluBN - 1) / kGluBN);
+    if (int rc = grid_args({slots, blocks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *bstart = static_cast<int32_t *>(workspace);
+    if (int rc = launch_plan<kWideBM>(name, st, group_rows, count, total_rows, bstart)) return rc;
+    const bool x_vec = x_vec_wide(x, ldx, k);
+    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_wide_grouped_kernel, x_vec, kn), dim3((unsigned)blocks), dim3(kThreads), st,
+               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(gate_packed),
+               (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps,
+               up_offsets, up_bases, (int)count, n, g.sh(kn), g.sw(kn), bias_gate, bias_up, ldb, act, y, ldy);
+    return check_launch(name);
+}
 
 extern "C" int mtq_packed_glu_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
                                            const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
@@ -3040,141 +2976,9 @@ extern "C" int mtq_packed_glu_wide_grouped(const void *x, int64_t total_rows, in
                                            const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, void *workspace,
                                            size_t workspace_bytes, void *stream)
 {
-    SplitGrid g;
-    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
-                               !up_bases || !y,
-                           out_dtype, [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n,
-                           ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
-        return rc;
-    if (int rc = glu_act(act)) return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
-    // mtq_packed_linear_wide_grouped's slot bound
-    const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
-    const int64_t blocks = slots * ((n + kGluBN - 1) / kGluBN);
-    if (slots > INT32_MAX || blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t *bstart = static_cast<int32_t *>(workspace);
-    hipLaunchKernelGGL(packed_grouped_plan_kernel<kWideBM>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
-    if (int rc = check_launch("mtq_packed_glu_wide_grouped")) return rc;
-    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
-    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_wide_grouped_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), st,
-               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(gate_packed),
-               (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps,
-               up_offsets, up_bases, (int)count, n, g.th, g.tw, bias_gate, bias_up, ldb, act, y, ldy);
-    return check_launch("mtq_packed_glu_wide_grouped");
-}
-
-// ---- gated entries for decode: both projections in one split-K launch, the activation in the reduce
-
-extern "C" size_t mtq_packed_glu_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
-{
-    int64_t th, tw;
-    int eff;
-    if (skinny_shape(m, n, k, split, &th, &tw, &eff)) return (size_t)-1;
-    return glu_skinny_workspace(m, n, eff);
-}
-
-extern "C" int mtq_packed_glu_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
-                                     const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
-                                     const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up,
-                                     int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
-                                     void *stream)
-{
-    SplitGrid g;
-    if (int rc = gemm_args(!x || !gate_packed || !gate_map || !gate_offsets || !up_packed || !up_map || !up_offsets || !y, out_dtype,
-                           [&](SplitGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0,
-                           {gate_packed, gate_bytes}, {up_packed, up_bytes}))
-        return rc;
-    if (int rc = glu_act(act)) return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(m, n, g.eff), kWsGlu, "split")) return rc;
-    const int64_t blocks = (2 * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(packed_glu_skinny_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), m, k, ldx,
-                       (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
-                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, g.th, g.tw, g.eff, ws);
-    if (int rc = check_launch("mtq_packed_glu_skinny")) return rc;
-    launch_out(out_dtype, glu_skinny_reduce_kernel<true>, glu_skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
-               m * n, n, g.eff, bias_gate, bias_up, act, y, ldy);
-    return check_launch("mtq_packed_glu_skinny");
-}
-
-// grouped_shape and the bound that keeps the two projections' partials inside size_t at every split
-static int glu_grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *th, int64_t *tw, int *eff)
-{
-    if (int rc = grouped_shape(total_rows, count, n, k, split, th, tw, eff)) return rc;
-    if (total_rows > ((int64_t)1 << 55) / n / *eff) return fail(MTQ_ERR_INVALID, "the workspace of this split is too large");
-    return MTQ_OK;
-}
-
-extern "C" size_t mtq_packed_glu_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
-{
-    int64_t th, tw;
-    int eff;
-    if (glu_grouped_shape(total_rows, count, n, k, split, &th, &tw, &eff)) return (size_t)-1;
-    return glu_skinny_workspace(total_rows, n, eff);
-}
-
-extern "C" int mtq_packed_glu_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
-                                             const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
-                                             const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
-                                             const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n,
-                                             const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y, int out_dtype,
-                                             int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
-{
-    SplitGrid g;
-    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
-                               !up_bases || !y,
-                           out_dtype, [&](SplitGrid &s) { return glu_grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx,
-                           n, ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
-        return rc;
-    if (int rc = glu_act(act)) return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(total_rows, n, g.eff), kWsGlu, "split")) return rc;
-    const int64_t blocks = (2 * count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    const int64_t nchunks = (n + 255) / 256;
-    if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(packed_glu_skinny_grouped_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x),
-                       (int)total_rows, (int)k, ldx, (int)x_vec_of(x, ldx), group_rows, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes,
-                       gate_maps, gate_offsets, gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases,
-                       (int)count, (int)n, (int)g.th, (int)g.tw, g.eff, ws);
-    if (int rc = check_launch("mtq_packed_glu_skinny_grouped")) return rc;
-    launch_out(out_dtype, glu_skinny_grouped_reduce_kernel<true>, glu_skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
-               st, ws, total_rows, n, g.eff, group_rows, nchunks, bias_gate, bias_up, ldb, act, y, ldy);
-    return check_launch("mtq_packed_glu_skinny_grouped");
-}
-
-// ---- gated entries for (k, n) weights: the gated entries' checks, split rules, slot bounds and workspaces (tile_grid of n × k is the grid
-// check of k × n, mtq_packed_matmul's), the kernels with the grid the other way round.
-
-extern "C" int mtq_packed_glu_matmul_wide(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
-                                          const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
-                                          const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate,
-                                          const float *bias_up, int act, void *y, int out_dtype, int64_t ldy, void *stream)
-{
-    int64_t tn, tk;                                  // tiles along n, tiles along k
-    if (int rc = linear_args(x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, n, y, out_dtype, ldy, &tn, &tk)) return rc;
-    if (int rc = linear_args(x, m, k, ldx, up_packed, up_bytes, up_map, up_offsets, n, y, out_dtype, ldy, &tn, &tk)) return rc;
-    if (int rc = glu_act(act)) return rc;
-    const int64_t blocks = ((m + kWideBM - 1) / kWideBM) * ((n + kGluBN - 1) / kGluBN);
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch: pass M in chunks");
-    if (int rc = require_device()) return rc;
-    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
-    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_matmul_wide_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads),
-               static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(x), m, k, ldx, static_cast<const uint8_t *>(gate_packed),
-               (uint64_t)gate_bytes, gate_map, gate_offsets, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, tk, tn,
-               bias_gate, bias_up, act, y, ldy);
-    return check_launch("mtq_packed_glu_matmul_wide");
-}
-
-extern "C" size_t mtq_packed_glu_matmul_wide_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k)
-{
-    return mtq_packed_glu_wide_grouped_workspace_bytes(total_rows, count, n, k);   // the same plan
+    return packed_glu_wide_grouped(false, "mtq_packed_glu_wide_grouped", x, total_rows, k, ldx, group_rows, gate_packed, gate_bytes, gate_maps,
+                                   gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate, bias_up, ldb, act,
+                                   y, out_dtype, ldy, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mtq_packed_glu_matmul_wide_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
@@ -3184,34 +2988,59 @@ extern "C" int mtq_packed_glu_matmul_wide_grouped(const void *x, int64_t total_r
                                                   int64_t n, const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y,
                                                   int out_dtype, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream)
 {
-    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
-    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
-                               !up_bases || !y,
-                           out_dtype, [&](SplitGrid &s) { return grouped_shape(total_rows, count, n, k, 1, &s.th, &s.tw, &s.eff); }, g, k, ldx, n,
-                           ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
-        return rc;
-    if (int rc = glu_act(act)) return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, grouped_plan_bytes(count), kWsPlan, "call")) return rc;
-    // mtq_packed_linear_wide_grouped's slot bound
-    const int64_t slots = (total_rows + (kWideBM - 1) * std::min(count, total_rows)) / kWideBM;
-    const int64_t blocks = slots * ((n + kGluBN - 1) / kGluBN);
-    if (slots > INT32_MAX || blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t *bstart = static_cast<int32_t *>(workspace);
-    hipLaunchKernelGGL(packed_grouped_plan_kernel<kWideBM>, dim3(1), dim3(256), 0, st, group_rows, (int)count, (int)total_rows, bstart);
-    if (int rc = check_launch("mtq_packed_glu_matmul_wide_grouped")) return rc;
-    const bool x_vec = x_vec_of(x, ldx) && k % 8 == 0;
-    launch_out(out_dtype, MTQ_WIDE_PAIR(packed_glu_matmul_wide_grouped_kernel, x_vec), dim3((unsigned)blocks), dim3(kThreads), st,
-               static_cast<const uint16_t *>(x), (int)total_rows, k, ldx, group_rows, bstart, static_cast<const uint8_t *>(gate_packed),
-               (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps,
-               up_offsets, up_bases, (int)count, n, g.tw, g.th, bias_gate, bias_up, ldb, act, y, ldy);
-    return check_launch("mtq_packed_glu_matmul_wide_grouped");
+    return packed_glu_wide_grouped(true, "mtq_packed_glu_matmul_wide_grouped", x, total_rows, k, ldx, group_rows, gate_packed, gate_bytes, gate_maps,
+                                   gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate, bias_up, ldb, act,
+                                   y, out_dtype, ldy, workspace, workspace_bytes, stream);
+}
+
+// 9. glu skinny: the gated entries for decode, both projections in one split-K launch, the activation in the reduce
+extern "C" size_t mtq_packed_glu_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
+{
+    TileGrid g;
+    if (skinny_shape(m, n, k, split, &g.th, &g.tw, &g.eff)) return (size_t)-1;
+    return glu_skinny_workspace(m, n, g.eff);
 }
 
 extern "C" size_t mtq_packed_glu_matmul_skinny_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
 {
     return mtq_packed_glu_skinny_workspace_bytes(m, n, k, split);
+}
+
+static int packed_glu_skinny(bool kn, const char *name, const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                             const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes, const int8_t *up_map,
+                             const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up, int act, void *y, int out_dtype,
+                             int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    TileGrid g;
+    if (int rc = gemm_args(!x || !gate_packed || !gate_map || !gate_offsets || !up_packed || !up_map || !up_offsets || !y, out_dtype,
+                           [&](TileGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0,
+                           {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
+    if (int rc = glu_act(act)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(m, n, g.eff), kWsGlu, "split")) return rc;
+    const int64_t blocks = (2 * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    if (int rc = grid_args({blocks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(kn ? packed_glu_matmul_skinny_kernel : packed_glu_skinny_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st,
+                       static_cast<const uint16_t *>(x), m, k, ldx, (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(gate_packed),
+                       (uint64_t)gate_bytes, gate_map, gate_offsets, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n,
+                       g.sh(kn), g.sw(kn), g.eff, ws);
+    if (int rc = check_launch(name)) return rc;
+    launch_out(out_dtype, glu_skinny_reduce_kernel<true>, glu_skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
+               m * n, n, g.eff, bias_gate, bias_up, act, y, ldy);
+    return check_launch(name);
+}
+
+extern "C" int mtq_packed_glu_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
+                                     const int8_t *gate_map, const uint32_t *gate_offsets, const void *up_packed, size_t up_bytes,
+                                     const int8_t *up_map, const uint32_t *up_offsets, int64_t n, const float *bias_gate, const float *bias_up,
+                                     int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                     void *stream)
+{
+    return packed_glu_skinny(false, "mtq_packed_glu_skinny", x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, up_packed, up_bytes, up_map,
+                             up_offsets, n, bias_gate, bias_up, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mtq_packed_glu_matmul_skinny(const void *x, int64_t m, int64_t k, int64_t ldx, const void *gate_packed, size_t gate_bytes,
@@ -3220,30 +3049,72 @@ extern "C" int mtq_packed_glu_matmul_skinny(const void *x, int64_t m, int64_t k,
                                             const float *bias_up, int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace,
                                             size_t workspace_bytes, void *stream)
 {
-    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
-    if (int rc = gemm_args(!x || !gate_packed || !gate_map || !gate_offsets || !up_packed || !up_map || !up_offsets || !y, out_dtype,
-                           [&](SplitGrid &s) { return skinny_shape(m, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx, n, ldy, false, 0, 0,
-                           {gate_packed, gate_bytes}, {up_packed, up_bytes}))
-        return rc;
-    if (int rc = glu_act(act)) return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(m, n, g.eff), kWsGlu, "split")) return rc;
-    const int64_t blocks = (2 * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    if (blocks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(packed_glu_matmul_skinny_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), m,
-                       k, ldx, (int)x_vec_of(x, ldx), static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
-                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, g.tw, g.th, g.eff, ws);
-    if (int rc = check_launch("mtq_packed_glu_matmul_skinny")) return rc;
-    launch_out(out_dtype, glu_skinny_reduce_kernel<true>, glu_skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
-               m * n, n, g.eff, bias_gate, bias_up, act, y, ldy);
-    return check_launch("mtq_packed_glu_matmul_skinny");
+    return packed_glu_skinny(true, "mtq_packed_glu_matmul_skinny", x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, up_packed, up_bytes,
+                             up_map, up_offsets, n, bias_gate, bias_up, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
+}
+
+// 10. glu skinny grouped.  grouped_shape and the bound that keeps the two projections' partials inside size_t at every split
+static int glu_grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *th, int64_t *tw, int *eff)
+{
+    if (int rc = grouped_shape(total_rows, count, n, k, split, th, tw, eff)) return rc;
+    if (total_rows > ((int64_t)1 << 55) / n / *eff) return fail(MTQ_ERR_INVALID, "the workspace of this split is too large");
+    return MTQ_OK;
+}
+
+extern "C" size_t mtq_packed_glu_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    TileGrid g;
+    if (glu_grouped_shape(total_rows, count, n, k, split, &g.th, &g.tw, &g.eff)) return (size_t)-1;
+    return glu_skinny_workspace(total_rows, n, g.eff);
 }
 
 extern "C" size_t mtq_packed_glu_matmul_skinny_grouped_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
 {
     return mtq_packed_glu_skinny_grouped_workspace_bytes(total_rows, count, n, k, split);
+}
+
+static int packed_glu_skinny_grouped(bool kn, const char *name, const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                     const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                     const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                     const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n, const float *bias_gate,
+                                     const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace,
+                                     size_t workspace_bytes, void *stream)
+{
+    TileGrid g;
+    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
+                               !up_bases || !y,
+                           out_dtype, [&](TileGrid &s) { return glu_grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx,
+                           n, ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
+    if (int rc = glu_act(act)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(total_rows, n, g.eff), kWsGlu, "split")) return rc;
+    const int64_t blocks = (2 * count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    const int64_t nchunks = grouped_nchunks(n);
+    if (int rc = grid_args({blocks, count * nchunks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(kn ? packed_glu_matmul_skinny_grouped_kernel : packed_glu_skinny_grouped_kernel, dim3((unsigned)blocks),
+                       dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), (int)total_rows, (int)k, ldx, (int)x_vec_of(x, ldx),
+                       group_rows, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases,
+                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases, (int)count, (int)n, (int)g.sh(kn),
+                       (int)g.sw(kn), g.eff, ws);
+    if (int rc = check_launch(name)) return rc;
+    launch_out(out_dtype, glu_skinny_grouped_reduce_kernel<true>, glu_skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
+               st, ws, total_rows, n, g.eff, group_rows, nchunks, bias_gate, bias_up, ldb, act, y, ldy);
+    return check_launch(name);
+}
+
+extern "C" int mtq_packed_glu_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                             const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                             const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                             const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n,
+                                             const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y, int out_dtype,
+                                             int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return packed_glu_skinny_grouped(false, "mtq_packed_glu_skinny_grouped", x, total_rows, k, ldx, group_rows, gate_packed, gate_bytes, gate_maps,
+                                     gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate, bias_up, ldb,
+                                     act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mtq_packed_glu_matmul_skinny_grouped(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
@@ -3254,30 +3125,11 @@ extern "C" int mtq_packed_glu_matmul_skinny_grouped(const void *x, int64_t total
                                                     void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
                                                     void *stream)
 {
-    SplitGrid g;                                     // th: tiles along n, tw: tiles along k
-    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
-                               !up_bases || !y,
-                           out_dtype, [&](SplitGrid &s) { return glu_grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx,
-                           n, ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
-        return rc;
-    if (int rc = glu_act(act)) return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(total_rows, n, g.eff), kWsGlu, "split")) return rc;
-    const int64_t blocks = (2 * count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
-    const int64_t nchunks = (n + 255) / 256;
-    if (blocks > INT32_MAX || count * nchunks > INT32_MAX) return fail(MTQ_ERR_INVALID, "too many workgroups for one launch");
-    if (int rc = require_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(packed_glu_matmul_skinny_grouped_kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st,
-                       static_cast<const uint16_t *>(x), (int)total_rows, (int)k, ldx, (int)x_vec_of(x, ldx), group_rows,
-                       static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases,
-                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases, (int)count, (int)n, (int)g.tw,
-                       (int)g.th, g.eff, ws);
-    if (int rc = check_launch("mtq_packed_glu_matmul_skinny_grouped")) return rc;
-    launch_out(out_dtype, glu_skinny_grouped_reduce_kernel<true>, glu_skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
-               st, ws, total_rows, n, g.eff, group_rows, nchunks, bias_gate, bias_up, ldb, act, y, ldy);
-    return check_launch("mtq_packed_glu_matmul_skinny_grouped");
+    return packed_glu_skinny_grouped(true, "mtq_packed_glu_matmul_skinny_grouped", x, total_rows, k, ldx, group_rows, gate_packed, gate_bytes,
+                                     gate_maps, gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate,
+                                     bias_up, ldb, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
 }
+
 
 extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)
 {

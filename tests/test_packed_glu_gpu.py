@@ -1,4 +1,4 @@
-"""GPU: the gated product on packed weights — packed_glu_wide_kernel, packed_glu_wide_grouped_kernel and glu_combine_kernel of
+"""GPU: the gated product on packed weights — packed_glu_wide_kernel and packed_glu_wide_grouped_kernel (WT = false) and glu_combine_kernel of
 csrc/mtq_packed.hip, the one activation function of csrc/mtq_glu.hpp — and what packed.py builds on them.
 
 The fused block is 128 (M) × 64 (hidden N) × 64 (K): four waves, each staging one of four tile-row slots that alternate between the gate

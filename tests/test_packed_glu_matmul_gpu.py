@@ -1,5 +1,5 @@
-"""GPU: the gated product on packed (k, n) weights, wide and wide-grouped — packed_glu_matmul_wide_kernel and
-packed_glu_matmul_wide_grouped_kernel of csrc/mtq_packed.hip (wide_block<GLU, .., WT>) — and packed.glu_matmul / glu_matmul_grouped.
+"""GPU: the gated product on packed (k, n) weights, wide and wide-grouped — packed_glu_wide_kernel and
+packed_glu_wide_grouped_kernel with WT = true of csrc/mtq_packed.hip (wide_block<GLU, .., WT>) — and packed.glu_matmul / glu_matmul_grouped.
 
 Names: W is the (n, k) weight as stored, P̂ its packed transpose (k, n), a map is over Wᵀ's grid ceil(k/32) × ceil(n/32).
 

@@ -1,4 +1,4 @@
-"""GPU: the grouped wide packed linear (packed_grouped_wide_plan_kernel + packed_linear_wide_grouped_kernel of csrc/mtq_packed.hip): a
+"""GPU: the grouped wide packed linear (packed_grouped_plan_kernel<128> + packed_wide_grouped_kernel<.., WT = false> of csrc/mtq_packed.hip): a
 workgroup per (128-row block of a group, 128 columns), the block list made from group_rows on the device.
 
 The oracle for bits is never the new code: the block kernel (hb.packed_linear) per group, the float64 emulation on the integer grid, the

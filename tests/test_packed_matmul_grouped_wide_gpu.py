@@ -1,4 +1,4 @@
-"""GPU: the grouped wide matmul for (k, n) experts - packed_matmul_wide_grouped_kernel of csrc/mtq_packed.hip (wide_block fed from the
+"""GPU: the grouped wide matmul for (k, n) experts - packed_wide_grouped_kernel<.., WT = true> of csrc/mtq_packed.hip (wide_block fed from the
 k x n stream in the grouped wide frame) - and packed.matmul_grouped_wide / PackedExpertsMatmul(wide_min_rows=...).
 
 Routings, in 128-row blocks: (0, 3, 3, 131, 132, 390) - 6 blocks in 8 slots; (0, 0, 300, 300, 300, 300) - a hot group of 2 x 128 + 44

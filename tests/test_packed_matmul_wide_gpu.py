@@ -1,4 +1,4 @@
-"""GPU: the wide-block product with a packed (k, n) matrix — packed_matmul_wide_kernel of csrc/mtq_packed.hip (wide_block with its W side
+"""GPU: the wide-block product with a packed (k, n) matrix — packed_wide_kernel<.., WT = true> of csrc/mtq_packed.hip (wide_block with its W side
 fed from the k × n stream) — and what packed.py builds on it: matmul_wide, and matmul(kernel="auto") / PackedMatmul(kernel="auto").
 
 Names: W is the (n, k) weight as stored, P̂ its packed transpose (k, n), the map is over Wᵀ's grid ceil(k/32) × ceil(n/32).

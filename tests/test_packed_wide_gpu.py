@@ -1,4 +1,4 @@
-"""GPU: the wide-block packed linear (packed_linear_wide_kernel, csrc/mtq_packed.hip) held to its bit contract — for every input the
+"""GPU: the wide-block packed linear (packed_wide_kernel<.., WT = false>, csrc/mtq_packed.hip) held to its bit contract — for every input the
 block kernel's output bit for bit — and, independently of the block kernel, to exact arithmetic and to the oracle's Ŵ.
 
 The block is 128 (M) × 128 (N) × 64 (K), four waves 2 × 2 of 64 × 64 outputs.  The shapes:
