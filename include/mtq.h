@@ -1217,6 +1217,10 @@ int mtq_moe_combine(const void *ys, int ys_dtype, int64_t ldys, const int32_t *r
                     int base_dtype, int64_t ldbase, int64_t tokens, int64_t topk, int64_t n, void *y, int out_dtype, int64_t ldy,
                     void *stream);
 
+/* The MoE decode entries without the staging copies - the gather inside the gated product's X loads, the combine inside the down
+ * projection's reduce - are declared in mtq_moe_decode.h, included at the end of this header: their contracts stand there, beside
+ * this section's, which they refer to. */
+
 /* ------------------------------------------------------------------ MoE router: scoring and group-limited top-k (csrc/mtq_moe_route.hip)
  * From the router's logits (tokens, count), bf16 or float32 (logits_dtype, MTQ_DTYPE_*) at pitch ld_logits, to what the plan and the
  * combine above take: topk_ids int32 (tokens, topk) at pitch ld_ids and topk_weights float32 (tokens, topk) at pitch ld_w, in ONE
@@ -1264,4 +1268,5 @@ int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream
 #ifdef __cplusplus
 }
 #endif
+#include "mtq_moe_decode.h"
 #endif /* MTQ_H */

@@ -49,6 +49,10 @@
 //   packed_glu_matmul_skinny_grouped_kernel   the gated product for packed k × n gate and up matrices: the four gated frames with the
 //       matmul kernels' feed (the wide block's [64 k][32 n] sub-images alternating between the two streams; the skinny wave's two
 //       images on the projection axis); bit for bit two matmul calls into f32 and the combine.
+//   packed_glu_skinny_grouped_kernel<GATHER = true>, packed_glu_matmul_skinny_grouped_kernel<GATHER = true>, skinny_grouped_combine_kernel
+//                                             an MoE layer's decode route without its staging copies (include/mtq_moe_decode.h): the two
+//       grouped skinny GLU waves reading their X groups from the token's own row through the plan's src (mtq_moe_dispatch's rule, its
+//       bits), and the grouped skinny down projection's reduce with mtq_moe_combine's weighted sum in it.
 //
 // The wide kernels are frames around one block function, wide_block; the skinny kernels around one wave's run, skinny_run, and one
 // epilogue, store_lane_rows; all of them read a tensor through a PackedStream and guard a blob with stream_at.
@@ -1334,6 +1338,40 @@ __global__ __launch_bounds__(256) void skinny_grouped_reduce_kernel(const float 
     }
 }
 
+// ---- the combine of an MoE layer in the grouped skinny reduce: skinny_grouped_reduce_kernel and moe_combine_kernel (mtq_moe.hip) in one.
+//
+// One workgroup per (token t, 256 columns), thread n.  acc starts at (float) base[t][n] or +0; for j = 0 .. K - 1 in order, with
+// r = row_of[t * K + j] inside [0, S): v = ((p0 + p1) + ... + p_{split-1}) + 0.0f over the slices of ws [split][S][N] ascending, the
+// + 0.0f being the grouped entries' bias add without a bias (it turns a -0 sum into +0); EXPERT_BF16 rounds v to bf16 once and widens
+// it, the rounding a bf16 ys would have had; acc = fl32(acc + fl32(w[t][j] * v)).  A slot with r outside [0, S) is skipped by a
+// branch the whole workgroup takes (t is the workgroup's), never multiplied by zero, so rows of ws that no kept slot names are never
+// read.  base_kind: 0 none, 1 bf16, 2 float32.  No atomics, nothing waits on another workgroup.
+template <bool EXPERT_BF16, bool BF16OUT>
+__global__ __launch_bounds__(256) void skinny_grouped_combine_kernel(const float *__restrict__ ws, int64_t S, int64_t N, int split,
+                                                                     const int32_t *__restrict__ row_of, const float *__restrict__ weights,
+                                                                     int64_t ldw, const void *__restrict__ base, int base_kind, int64_t ldbase,
+                                                                     int K, int64_t nchunks, void *__restrict__ yv, int64_t ldy)
+{
+#pragma clang fp contract(off)
+    const int64_t t = blockIdx.x / nchunks, n = (blockIdx.x % nchunks) * 256 + threadIdx.x;
+    if (n >= N) return;
+    float acc = 0.0f;
+    if (base_kind == 1) acc = __uint_as_float((uint32_t) static_cast<const uint16_t *>(base)[t * ldbase + n] << 16);
+    else if (base_kind == 2) acc = static_cast<const float *>(base)[t * ldbase + n];
+    const int32_t *rows = row_of + t * K;
+    const float *w = weights + t * ldw;
+    for (int j = 0; j < K; ++j) {
+        const int64_t r = rows[j];
+        if (r < 0 || r >= S) continue;               // uniform over the workgroup
+        float v = ws[r * N + n];
+        for (int s = 1; s < split; ++s) v += ws[((int64_t)s * S + r) * N + n];
+        v += 0.0f;
+        if constexpr (EXPERT_BF16) v = __uint_as_float((uint32_t)f32_to_bf16(v) << 16);
+        acc = __fadd_rn(acc, __fmul_rn(w[j], v));
+    }
+    store_y<BF16OUT>(yv, t * ldy + n, acc);
+}
+
 // ---- grouped skinny linear, a wave per 32-row chunk: the kernel above with its `for row0` loop handed out over waves.
 //
 // A unit is (slice s, chunk slot c, tile row tr), numbered ((s * slots + c) * tiles_h + tr): the four waves of a workgroup share a slice
@@ -2022,18 +2060,39 @@ __global__ __launch_bounds__(256) void glu_skinny_reduce_kernel(const float *__r
     store_y<BF16OUT>(yv, m * ldy + n, glu_value(g, u, act));
 }
 
+// ---- the gather of an MoE layer in a grouped skinny wave's X address (GATHER of the two grouped skinny GLU kernels below).
+//
+// x is the TOKEN matrix and row r of the matrix the wave multiplies is x[src[r] / topk] when 0 <= src[r] < T (T = S = tokens * topk,
+// so the token is below `tokens` whatever src holds), else a row of +0: moe_dispatch_kernel's rule, and the words load_x16 hands the
+// MFMAs are those it would read from the dispatched copy.  A lane looks its row's src up once per 32-row chunk and hands skinny_run
+// its own row base with row 0 of M = 1 rows, or M = 0 ("no row": load_x16 returns zeros before it forms an address).  Lanes at or past
+// the chunk's rows read no src.  x_vec keeps its meaning: every row starts at x + t * ldx.
+struct GatherRow {
+    const uint16_t *x;
+    int64_t m;
+};
+
+__device__ __forceinline__ GatherRow gather_row(const uint16_t *__restrict__ x, int64_t ldx, const int32_t *__restrict__ src, int topk, int T,
+                                                int64_t row0, int row, int64_t M)
+{
+    const int v = row < M ? src[row0 + row] : -1;    // row0 + row < r1 <= T
+    const bool from = v >= 0 && v < T;
+    return {x + (int64_t)(from ? v / topk : 0) * ldx, from ? 1 : 0};
+}
+
 // ---- grouped skinny GLU: packed_linear_skinny_grouped_kernel's wave on the projection axis, over two arenas.
 //
 // A unit is (slice s, projection p, group e, tile row tr), numbered (((2 s + p) * count + e) * tiles_h + tr).  The group's clamped rows,
 // the walk in 32-row chunks by the same wave, the hand-out, ring, decode and MFMAs are that kernel's; the maps, offsets, bases and bytes
 // are the wave's own arena's, and a blob is checked against its own group's range of that arena.  The partial of every chunk goes to
 // ws[p][s][row][n] with plain stores at every split.
+template <bool GATHER>
 __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_skinny_grouped_kernel(
     const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
     const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps, const uint32_t *__restrict__ gate_offsets,
     const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes, const int8_t *__restrict__ up_maps,
     const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int N, int tiles_h, int tiles_w, int split,
-    float *__restrict__ ws)
+    float *__restrict__ ws, const int32_t *__restrict__ src, int topk)
 {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
@@ -2052,7 +2111,12 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_skinny_groupe
         const int64_t n = tr * kTile + row;
         const int64_t M = std::min<int64_t>(kTile, gr.r1 - row0);
         f32x16 acc = zero16();
-        skinny_run(acc, FeedDirect(), x + row0 * ldx, M, K, ldx, x_vec, st, tr * tiles_w, 1, c0, c1, lane, row, half, 2 * row + half);
+        if constexpr (GATHER) {
+            const GatherRow xr = gather_row(x, ldx, src, topk, T, row0, row, M);
+            skinny_run(acc, FeedDirect(), xr.x, xr.m, K, ldx, x_vec, st, tr * tiles_w, 1, c0, c1, lane, 0, half, 2 * row + half);
+        } else {
+            skinny_run(acc, FeedDirect(), x + row0 * ldx, M, K, ldx, x_vec, st, tr * tiles_w, 1, c0, c1, lane, row, half, 2 * row + half);
+        }
 
         // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row) of slice s of projection p
         if (n < N) store_lane_rows<false, true>(acc, M, half, ws, (((int64_t)p * split + s) * T + row0 + 4 * half) * N + n, N, 0.0f);
@@ -2132,12 +2196,13 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_matmul_skinny
 // EXEC: as in packed_matmul_skinny_grouped_kernel, everything a branch before or between runs depends on (the unit bound, the group
 // without rows, the chunk loop's trip count) is wave-uniform and in scalar registers; the one lane-dependent branch is the n < N guard
 // around the stores, after a run, and EXEC is whole again behind it.
+template <bool GATHER>
 __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_matmul_skinny_grouped_kernel(
     const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
     const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps, const uint32_t *__restrict__ gate_offsets,
     const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes, const int8_t *__restrict__ up_maps,
     const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int N, int tiles_kh, int tiles_nw, int split,
-    float *__restrict__ ws)
+    float *__restrict__ ws, const int32_t *__restrict__ src, int topk)
 {
     __shared__ __attribute__((aligned(16))) uint16_t lds[kSkinnyWaves * 2 * kMmsImage];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2159,7 +2224,12 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_matmul_skinny
         const int64_t n = tc * kTile + row;
         const int64_t M = std::min<int64_t>(kTile, r1 - row0);
         f32x16 acc = zero16();
-        skinny_run(acc, feed_transposed(img, lv), x + row0 * ldx, M, K, ldx, x_vec, st, tc, tiles_nw, c0, c1, lane, row, half, lv);
+        if constexpr (GATHER) {
+            const GatherRow xr = gather_row(x, ldx, src, topk, T, row0, row, M);
+            skinny_run(acc, feed_transposed(img, lv), xr.x, xr.m, K, ldx, x_vec, st, tc, tiles_nw, c0, c1, lane, 0, half, lv);
+        } else {
+            skinny_run(acc, feed_transposed(img, lv), x + row0 * ldx, M, K, ldx, x_vec, st, tc, tiles_nw, c0, c1, lane, row, half, lv);
+        }
 
         // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tc + row) of slice s of projection p
         if (n < N) store_lane_rows<false, true>(acc, M, half, ws, (((int64_t)p * split + s) * T + row0 + 4 * half) * N + n, N, 0.0f);
@@ -2571,6 +2641,16 @@ static int launch_plan(const char *name, hipStream_t st, const int32_t *group_ro
 // The grouped reduces walk a group's columns in chunks of 256: count × grouped_nchunks(n) workgroups
 static int64_t grouped_nchunks(int64_t n) { return (n + 255) / 256; }
 
+// mtq_moe_plan's limits on (tokens, topk), for the entries that take a plan's src or row_of; *slots = S = tokens * topk
+static int moe_slots_arg(int64_t tokens, int64_t topk, int64_t *slots)
+{
+    if (tokens <= 0) return fail(MTQ_ERR_INVALID, "tokens must be positive");
+    if (topk <= 0 || topk > MTQ_MOE_MAX_TOPK) return fail(MTQ_ERR_INVALID, "topk must be 1 .. MTQ_MOE_MAX_TOPK (64)");
+    if (tokens > (((int64_t)1 << 31) - 1) / topk) return fail(MTQ_ERR_INVALID, "tokens * topk must be below 2^31");
+    *slots = tokens * topk;
+    return MTQ_OK;
+}
+
 // 1. block
 static int packed_block(bool kn, const char *name, const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes,
                         const int8_t *map, const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
@@ -2746,6 +2826,105 @@ extern "C" int mtq_packed_matmul_skinny_grouped(const void *x, int64_t total_row
 {
     return packed_skinny_grouped(true, "mtq_packed_matmul_skinny_grouped", x, total_rows, k, ldx, group_rows, packed, packed_bytes, maps, offsets,
                                  bases, count, n, bias, ldb, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
+}
+
+// 4c. skinny grouped with an MoE layer's combine in its reduce.  The wave is 4.'s, storing float32 to the workspace at every split: at an
+// effective split of 1 it is launched with the workspace as its float32 Y at pitch n and no bias, slice 0 of [1][S][n], and stores
+// acc + 0.0f there; the combine kernel's own + 0.0f leaves that value as it is.
+static size_t skinny_combine_workspace(int64_t total_rows, int64_t n, int split_eff)
+{
+    return ((size_t)std::max(split_eff, 1) * (size_t)total_rows * (size_t)n * sizeof(float) + 15) & ~(size_t)15;
+}
+
+extern "C" size_t mtq_packed_linear_skinny_grouped_combine_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    TileGrid g;
+    if (grouped_shape(total_rows, count, n, k, split, &g.th, &g.tw, &g.eff)) return (size_t)-1;
+    if (total_rows > ((int64_t)1 << 56) / n) return (size_t)-1;
+    return skinny_combine_workspace(total_rows, n, g.eff);
+}
+
+extern "C" size_t mtq_packed_matmul_skinny_grouped_combine_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_linear_skinny_grouped_combine_workspace_bytes(total_rows, count, n, k, split);
+}
+
+static int packed_skinny_grouped_combine(bool kn, const char *name, const void *x, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                         const void *packed, size_t packed_bytes, const int8_t *maps, const uint32_t *offsets,
+                                         const uint64_t *bases, int64_t count, int64_t n, int expert_dtype, const int32_t *row_of,
+                                         const float *weights, int64_t ldw, const void *base, int base_dtype, int64_t ldbase, int64_t tokens,
+                                         int64_t topk, void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    TileGrid g;
+    int64_t S = 0;
+    const StreamArg w = {packed, packed_bytes};
+    if (!row_of || !weights) return fail(MTQ_ERR_INVALID, kNullArg);
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](TileGrid &s) {
+                               if (int rc = dtype_arg(expert_dtype, "expert_dtype")) return rc;
+                               if (base)
+                                   if (int rc = dtype_arg(base_dtype, "base_dtype")) return rc;
+                               if (int rc = moe_slots_arg(tokens, topk, &S)) return rc;
+                               if (int rc = grouped_shape(S, count, n, k, split, &s.th, &s.tw, &s.eff)) return rc;
+                               if (S > ((int64_t)1 << 56) / n) return fail(MTQ_ERR_INVALID, "the workspace of this split is too large");
+                               return (int)MTQ_OK;
+                           },
+                           g, k, ldx, n, ldy, false, 0, count, w, w))
+        return rc;
+    if (ldw < topk) return fail(MTQ_ERR_INVALID, "ldw < topk");
+    if (base && ldbase < n) return fail(MTQ_ERR_INVALID, "ldbase < n");
+    if (ldw > (int64_t)1 << 31 || ldy > (int64_t)1 << 31 || (base && ldbase > (int64_t)1 << 31)) return fail(MTQ_ERR_INVALID, "matrix too large");
+    const size_t y_el = out_dtype == MTQ_DTYPE_BF16 ? 2 : 4, base_el = base_dtype == MTQ_DTYPE_BF16 ? 2 : 4;
+    if (reinterpret_cast<uintptr_t>(y) % y_el != 0 || reinterpret_cast<uintptr_t>(row_of) % 4 != 0 || reinterpret_cast<uintptr_t>(weights) % 4 != 0 ||
+        (base && reinterpret_cast<uintptr_t>(base) % base_el != 0))
+        return fail(MTQ_ERR_INVALID, "an operand is not aligned to its type");
+    if (int rc = workspace_args(workspace, workspace_bytes, skinny_combine_workspace(S, n, g.eff),
+                                "workspace is null: the experts' partial sums need one at every split", "split"))
+        return rc;
+    const int64_t blocks = (count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves, nchunks = grouped_nchunks(n);
+    if (int rc = grid_args({blocks, tokens * nchunks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(kn ? packed_matmul_skinny_grouped_kernel<false> : packed_linear_skinny_grouped_kernel<false>, dim3((unsigned)blocks),
+                       dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), S, k, ldx, (int)x_vec_of(x, ldx), group_rows,
+                       static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.sh(kn), g.sw(kn), g.eff,
+                       static_cast<const float *>(nullptr), (int64_t)0, static_cast<void *>(ws), n, ws);
+    if (int rc = check_launch(name)) return rc;
+    const int base_kind = !base ? 0 : (base_dtype == MTQ_DTYPE_BF16 ? 1 : 2);
+    const dim3 grid((unsigned)(tokens * nchunks));
+    if (expert_dtype == MTQ_DTYPE_BF16)
+        launch_out(out_dtype, skinny_grouped_combine_kernel<true, true>, skinny_grouped_combine_kernel<true, false>, grid, dim3(256), st, ws, S, n,
+                   g.eff, row_of, weights, ldw, base, base_kind, ldbase, (int)topk, nchunks, y, ldy);
+    else
+        launch_out(out_dtype, skinny_grouped_combine_kernel<false, true>, skinny_grouped_combine_kernel<false, false>, grid, dim3(256), st, ws, S, n,
+                   g.eff, row_of, weights, ldw, base, base_kind, ldbase, (int)topk, nchunks, y, ldy);
+    return check_launch(name);
+}
+
+extern "C" int mtq_packed_linear_skinny_grouped_combine(const void *x, int64_t k, int64_t ldx, const int32_t *group_rows, const void *packed,
+                                                        size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases,
+                                                        int64_t count, int64_t n, int expert_dtype, const int32_t *row_of, const float *weights,
+                                                        int64_t ldw, const void *base, int base_dtype, int64_t ldbase, int64_t tokens, int64_t topk,
+                                                        void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                                        void *stream)
+{
+    return packed_skinny_grouped_combine(false, "mtq_packed_linear_skinny_grouped_combine", x, k, ldx, group_rows, packed, packed_bytes, maps,
+                                         offsets, bases, count, n, expert_dtype, row_of, weights, ldw, base, base_dtype, ldbase, tokens, topk, y,
+                                         out_dtype, ldy, split, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mtq_packed_matmul_skinny_grouped_combine(const void *x, int64_t k, int64_t ldx, const int32_t *group_rows, const void *packed,
+                                                        size_t packed_bytes, const int8_t *maps, const uint32_t *offsets, const uint64_t *bases,
+                                                        int64_t count, int64_t n, int expert_dtype, const int32_t *row_of, const float *weights,
+                                                        int64_t ldw, const void *base, int base_dtype, int64_t ldbase, int64_t tokens, int64_t topk,
+                                                        void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                                        void *stream)
+{
+    return packed_skinny_grouped_combine(true, "mtq_packed_matmul_skinny_grouped_combine", x, k, ldx, group_rows, packed, packed_bytes, maps,
+                                         offsets, bases, count, n, expert_dtype, row_of, weights, ldw, base, base_dtype, ldbase, tokens, topk, y,
+                                         out_dtype, ldy, split, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t mtq_packed_linear_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
@@ -3073,19 +3252,33 @@ extern "C" size_t mtq_packed_glu_matmul_skinny_grouped_workspace_bytes(int64_t t
     return mtq_packed_glu_skinny_grouped_workspace_bytes(total_rows, count, n, k, split);
 }
 
+// gather: the *_gather entries - x is the (tokens, k) token matrix, src the plan's int32 [S], and total_rows is formed here as
+// S = tokens * topk once mtq_moe_plan's limits hold; what mtq_moe_dispatch refuses is refused here too.
 static int packed_glu_skinny_grouped(bool kn, const char *name, const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
                                      const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
                                      const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
                                      const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n, const float *bias_gate,
                                      const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace,
-                                     size_t workspace_bytes, void *stream)
+                                     size_t workspace_bytes, void *stream, bool gather = false, const int32_t *src = nullptr, int64_t tokens = 0,
+                                     int64_t topk = 0)
 {
     TileGrid g;
     if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
-                               !up_bases || !y,
-                           out_dtype, [&](TileGrid &s) { return glu_grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff); }, g, k, ldx,
-                           n, ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+                               !up_bases || !y || (gather && !src),
+                           out_dtype,
+                           [&](TileGrid &s) {
+                               if (gather) {
+                                   if (int rc = moe_slots_arg(tokens, topk, &total_rows)) return rc;
+                               }
+                               return glu_grouped_shape(total_rows, count, n, k, split, &s.th, &s.tw, &s.eff);
+                           },
+                           g, k, ldx, n, ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
         return rc;
+    if (gather) {
+        if (ldx > (int64_t)1 << 40) return fail(MTQ_ERR_INVALID, "matrix too large");
+        if (reinterpret_cast<uintptr_t>(x) % 2 != 0 || reinterpret_cast<uintptr_t>(src) % 4 != 0)
+            return fail(MTQ_ERR_INVALID, "x or src is not aligned to its type");
+    }
     if (int rc = glu_act(act)) return rc;
     if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(total_rows, n, g.eff), kWsGlu, "split")) return rc;
     const int64_t blocks = (2 * count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
@@ -3094,11 +3287,12 @@ static int packed_glu_skinny_grouped(bool kn, const char *name, const void *x, i
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *ws = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(kn ? packed_glu_matmul_skinny_grouped_kernel : packed_glu_skinny_grouped_kernel, dim3((unsigned)blocks),
-                       dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), (int)total_rows, (int)k, ldx, (int)x_vec_of(x, ldx),
-                       group_rows, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases,
-                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases, (int)count, (int)n, (int)g.sh(kn),
-                       (int)g.sw(kn), g.eff, ws);
+    hipLaunchKernelGGL(gather ? (kn ? packed_glu_matmul_skinny_grouped_kernel<true> : packed_glu_skinny_grouped_kernel<true>)
+                              : (kn ? packed_glu_matmul_skinny_grouped_kernel<false> : packed_glu_skinny_grouped_kernel<false>),
+                       dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), (int)total_rows, (int)k, ldx,
+                       (int)x_vec_of(x, ldx), group_rows, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps, gate_offsets,
+                       gate_bases, static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases, (int)count, (int)n,
+                       (int)g.sh(kn), (int)g.sw(kn), g.eff, ws, src, (int)topk);
     if (int rc = check_launch(name)) return rc;
     launch_out(out_dtype, glu_skinny_grouped_reduce_kernel<true>, glu_skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
                st, ws, total_rows, n, g.eff, group_rows, nchunks, bias_gate, bias_up, ldb, act, y, ldy);
@@ -3130,6 +3324,43 @@ extern "C" int mtq_packed_glu_matmul_skinny_grouped(const void *x, int64_t total
                                      bias_up, ldb, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
 }
 
+// 10g. glu skinny grouped with an MoE layer's gather in the wave's X loads: 10.'s body, workspace and reduce
+extern "C" size_t mtq_packed_glu_skinny_grouped_gather_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_glu_skinny_grouped_workspace_bytes(total_rows, count, n, k, split);
+}
+
+extern "C" size_t mtq_packed_glu_matmul_skinny_grouped_gather_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_glu_skinny_grouped_workspace_bytes(total_rows, count, n, k, split);
+}
+
+extern "C" int mtq_packed_glu_skinny_grouped_gather(const void *x, int64_t tokens, int64_t topk, int64_t k, int64_t ldx, const int32_t *src,
+                                                    const int32_t *group_rows, const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps,
+                                                    const uint32_t *gate_offsets, const uint64_t *gate_bases, const void *up_packed,
+                                                    size_t up_bytes, const int8_t *up_maps, const uint32_t *up_offsets, const uint64_t *up_bases,
+                                                    int64_t count, int64_t n, const float *bias_gate, const float *bias_up, int64_t ldb, int act,
+                                                    void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                                    void *stream)
+{
+    return packed_glu_skinny_grouped(false, "mtq_packed_glu_skinny_grouped_gather", x, 0, k, ldx, group_rows, gate_packed, gate_bytes, gate_maps,
+                                     gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate, bias_up, ldb,
+                                     act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream, true, src, tokens, topk);
+}
+
+extern "C" int mtq_packed_glu_matmul_skinny_grouped_gather(const void *x, int64_t tokens, int64_t topk, int64_t k, int64_t ldx, const int32_t *src,
+                                                           const int32_t *group_rows, const void *gate_packed, size_t gate_bytes,
+                                                           const int8_t *gate_maps, const uint32_t *gate_offsets, const uint64_t *gate_bases,
+                                                           const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                                           const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n,
+                                                           const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y,
+                                                           int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                                           void *stream)
+{
+    return packed_glu_skinny_grouped(true, "mtq_packed_glu_matmul_skinny_grouped_gather", x, 0, k, ldx, group_rows, gate_packed, gate_bytes,
+                                     gate_maps, gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate,
+                                     bias_up, ldb, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream, true, src, tokens, topk);
+}
 
 extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)
 {

@@ -164,6 +164,19 @@ SIGNATURES = {
 }
 EXPORTS = list(SIGNATURES)   # tests check the library exports exactly these
 OPTIONAL_EXPORTS = tuple(name for name, (_r, _p, optional) in SIGNATURES.items() if optional)
+# include/mtq_moe_decode.h, which mtq.h includes: the same description of its prototypes, bound by the same _bind; all optional.  A table
+# of its own as the header is a file of its own: SIGNATURES and EXPORTS are mtq.h's prototypes, name for name.
+MOE_DECODE_SIGNATURES = {
+    "mtq_packed_glu_skinny_grouped_gather_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_glu_skinny_grouped_gather": ("i", "pllllpppzppppzpppllpplipilipzp", True),
+    "mtq_packed_glu_matmul_skinny_grouped_gather_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_glu_matmul_skinny_grouped_gather": ("i", "pllllpppzppppzpppllpplipilipzp", True),
+    "mtq_packed_linear_skinny_grouped_combine_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_linear_skinny_grouped_combine": ("i", "pllppzpppllipplpilllpilipzp", True),
+    "mtq_packed_matmul_skinny_grouped_combine_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_matmul_skinny_grouped_combine": ("i", "pllppzpppllipplpilllpilipzp", True),
+}
+MOE_DECODE_EXPORTS = tuple(MOE_DECODE_SIGNATURES)
 _CTYPE = {"p": ctypes.c_void_p, "l": ctypes.c_int64, "u": ctypes.c_uint32, "i": ctypes.c_int, "d": ctypes.c_double, "z": ctypes.c_size_t,
           "q": ctypes.c_uint64, "v": None, "s": ctypes.c_char_p}
 
@@ -180,7 +193,7 @@ def build(force: bool = False) -> Path:
     """Compile libmtq_hip.so for gfx950 with hipcc (csrc/Makefile).  Cross-compiles without a GPU."""
     import subprocess
 
-    srcs = list((_PKG / "csrc").glob("*")) + [_PKG.parent / "include" / "mtq.h"]
+    srcs = list((_PKG / "csrc").glob("*")) + list((_PKG.parent / "include").glob("*.h"))
     stale = not LIB_PATH.exists() or any(p.stat().st_mtime > LIB_PATH.stat().st_mtime for p in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", str(_PKG / "csrc"), "-s"])
@@ -221,7 +234,7 @@ def _bind(L) -> None:
     found = version()
     if found < MTQ_VERSION:
         raise MtqError(f"{LIB_PATH} is version {found}, older than this package (it needs {MTQ_VERSION}): {_REBUILD}")
-    for name, (result, params, optional) in SIGNATURES.items():
+    for name, (result, params, optional) in (*SIGNATURES.items(), *MOE_DECODE_SIGNATURES.items()):
         fn = getattr(L, name, None)
         if fn is None:
             if optional:
@@ -1799,10 +1812,13 @@ def moe_plan(topk_ids, count: int, workspace=None, stream="current"):
         raise MtqError("expected a device tensor (the hip backend has no CPU fallback)")
     need = moe_plan_workspace_bytes(T, K, count)      # the limits on tokens, topk and count are the library's
     fn = _entry("mtq_moe_plan")
-    ws_ptr, ws_bytes = _packed_workspace(workspace, need, topk_ids.device)
+    if workspace is not None:
+        ws_ptr, ws_bytes = _packed_workspace(workspace, need, topk_ids.device)
     require_gpu()
     group_rows = torch.empty((int(count) + 1,), dtype=torch.int32, device=topk_ids.device)
     row_of, src = (torch.empty((T * K,), dtype=torch.int32, device=topk_ids.device) for _ in range(2))
+    if workspace is None:       # after the outputs: a workspace made here is the allocator's again once its pointer is taken, and must not
+        ws_ptr, ws_bytes = _packed_workspace(None, need, topk_ids.device)       # become one of them (the three-kernel plan reads it back)
     check(fn(topk_ids.data_ptr(), IDS_I64 if topk_ids.dtype == torch.int64 else IDS_I32, _rows_ld(topk_ids, T, K), T, K, int(count),
              group_rows.data_ptr(), row_of.data_ptr(), src.data_ptr(), ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
     return group_rows, row_of, src
@@ -1859,6 +1875,126 @@ def moe_combine(ys, row_of, weights, base=None, out_dtype=None, out=None, stream
     out, ldy = _packed_out(out, T, n, out_dtype, ys.device)
     check(fn(ys.data_ptr(), ys_code, ldys, pr, weights.data_ptr(), _rows_ld(weights, T, K), base_ptr, base_code, ldbase, T, K, n,
              out.data_ptr(), code, ldy, _packed_stream_ptr(stream)))
+    return out
+
+
+# ---- MoE decode without the staging copies (include/mtq_moe_decode.h): [kn] → (entry, size function)
+MOE_GATHER = (("mtq_packed_glu_skinny_grouped_gather", "mtq_packed_glu_skinny_grouped_gather_workspace_bytes"),
+              ("mtq_packed_glu_matmul_skinny_grouped_gather", "mtq_packed_glu_matmul_skinny_grouped_gather_workspace_bytes"))
+MOE_DOWN_COMBINE = (("mtq_packed_linear_skinny_grouped_combine", "mtq_packed_linear_skinny_grouped_combine_workspace_bytes"),
+                    ("mtq_packed_matmul_skinny_grouped_combine", "mtq_packed_matmul_skinny_grouped_combine_workspace_bytes"))
+
+
+def moe_decode_bound(kn: bool = False) -> bool:
+    """Whether this build of the library has the gathered grouped GLU and the down projection with the combine in its reduce for
+    (n, k) experts, or with `kn` for (k, n) experts (optional symbols: an older build of the same version lacks them)."""
+    return _has(MOE_GATHER[bool(kn)] + MOE_DOWN_COMBINE[bool(kn)])
+
+
+def moe_glu_gather_workspace_bytes(slots: int, count: int, n: int, k: int, split: int = 0, kn: bool = False) -> int:
+    """The *_gather_workspace_bytes size functions (host functions: no GPU): packed_glu_skinny_grouped_workspace_bytes' answer for
+    total_rows = slots = tokens * topk."""
+    return _workspace_size(MOE_GATHER[bool(kn)][1], slots, count, n, k, split)
+
+
+def moe_down_combine_workspace_bytes(slots: int, count: int, n: int, k: int, split: int = 0, kn: bool = False) -> int:
+    """The *_combine_workspace_bytes size functions (host functions: no GPU): max(effective split, 1) * slots * n * 4 bytes rounded up
+    to 16, the effective split packed_linear_skinny_grouped's for (slots, count, n, k, split).  Never 0."""
+    return _workspace_size(MOE_DOWN_COMBINE[bool(kn)][1], slots, count, n, k, split)
+
+
+def moe_glu_gather(x, src, topk: int, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None,
+                   out=None, split: int = 0, workspace=None, kn: bool = False, stream="current"):
+    """mtq_packed_glu_skinny_grouped_gather (kn: its matmul twin) on the current stream: packed_glu_skinny_grouped on the rows
+    moe_dispatch would have written, without writing them.  x: the (tokens, k) bf16 token matrix with contiguous rows; src: the plan's
+    contiguous int32 device tensor of S = tokens * topk entries; group_rows, gate, up, the biases, split and workspace as
+    packed_glu_skinny_grouped takes them → (S, n); an `out` allocated here starts as zeros, so rows of no group are zeros."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    count, n, topk = int(count), int(n), int(topk)
+    x_code, _count, _stride, T, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if count <= 0 or n <= 0 or T <= 0 or topk <= 0:
+        raise MtqError("tokens, topk, count and n must be positive")
+    S = T * topk
+    th, tw = tiles_hw(n, k)
+    sides = []
+    for which, (arena, maps_dev, offsets_dev, bases_dev) in (("gate", gate), ("up", up)):
+        pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+        sides += [_arena(arena, count, th * tw, f"the {which} arena"), arena.numel(), pm, po, pb]
+    pg = _buffer(group_rows, torch.int32, count + 1, "group_rows")
+    if group_rows.numel() != count + 1:
+        raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got {group_rows.numel()}")
+    ps = _buffer(src, torch.int32, S, "src")
+    if src.numel() != S:
+        raise MtqError(f"src must have tokens * topk = {S} entries, got {src.numel()}")
+    ptrs, ldb = [], 0
+    for which, bias in (("bias_gate", bias_gate), ("bias_up", bias_up)):
+        if bias is None:
+            ptrs.append(None)
+            continue
+        if bias.dtype != torch.float32 or bias.dim() != 2 or tuple(bias.shape) != (count, n) or bias.stride(1) != 1 or not bias.is_cuda:
+            raise MtqError(f"{which} must be a float32 ({count}, {n}) device tensor with contiguous rows")
+        pitch = bias.stride(0) if count > 1 else max(bias.stride(0), n)
+        if ldb and pitch != ldb:
+            raise MtqError("bias_gate and bias_up must have one row pitch")
+        ptrs.append(bias.data_ptr())
+        ldb = pitch
+    name, size = MOE_GATHER[bool(kn)]
+    fn = _entry(name)
+    need = _workspace_size(size, S, count, n, k, split)
+    out, ldy = _packed_out(out, S, n, out_dtype, x.device, zeros=True)
+    ws_ptr, ws_bytes = _packed_workspace(workspace, need, x.device)
+    check(fn(x.data_ptr(), T, topk, k, ldx, ps, pg, *sides, count, n, ptrs[0], ptrs[1], ldb, a, out.data_ptr(), code, ldy, int(split), ws_ptr,
+             ws_bytes, _packed_stream_ptr(stream)))
+    return out
+
+
+def moe_down_combine(h, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, row_of, weights, base=None, expert_dtype=None,
+                     out_dtype=None, out=None, split: int = 0, workspace=None, kn: bool = False, stream="current"):
+    """mtq_packed_linear_skinny_grouped_combine (kn: its matmul twin) on the current stream: packed_linear_skinny_grouped without bias
+    into expert_dtype and moe_combine of its rows, without those rows being written.  h: (S, k) bf16 with contiguous rows,
+    S = tokens * topk; group_rows and the arena's tables as packed_linear_skinny_grouped takes them; row_of, weights (tokens, topk)
+    float32 and base as moe_combine takes them → (tokens, n) float32 or bfloat16."""
+    torch = _torch()
+    out_dtype, expert_dtype = out_dtype or torch.float32, expert_dtype or torch.float32
+    code, expert_code = _packed_out_code(out_dtype), _packed_out_code(expert_dtype)
+    count, n = int(count), int(n)
+    if weights.dim() != 2 or weights.dtype != torch.float32 or (weights.shape[1] > 1 and weights.stride(1) != 1) or not weights.is_cuda:
+        raise MtqError("weights must be a float32 (tokens, topk) device tensor with contiguous rows")
+    T, K = (int(v) for v in weights.shape)
+    S = T * K
+    if T <= 0 or K <= 0 or count <= 0 or n <= 0:
+        raise MtqError("tokens, topk, count and n must be positive")
+    h_code, _count, _stride, rows, k, ldx = _matrix(h, (2,))
+    if h_code != DTYPE_BF16:
+        raise MtqError("h must be a bfloat16 tensor")
+    if rows != S:
+        raise MtqError(f"h must be ({S}, k), one row per slot, got {tuple(h.shape)}")
+    th, tw = tiles_hw(n, k)
+    pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+    ptr = _arena(arena, count, th * tw, "arena")
+    pg = _buffer(group_rows, torch.int32, count + 1, "group_rows")
+    if group_rows.numel() != count + 1:
+        raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got {group_rows.numel()}")
+    pr = _buffer(row_of, torch.int32, S, "row_of")
+    if row_of.numel() != S:
+        raise MtqError(f"row_of must have tokens * topk = {S} entries, got {row_of.numel()}")
+    base_ptr, base_code, ldbase = None, 0, 0
+    if base is not None:
+        base_code, _count, _stride, brows, bcols, ldbase = _matrix(base, (2,))
+        if (brows, bcols) != (T, n):
+            raise MtqError(f"base must be ({T}, {n}), got {tuple(base.shape)}")
+        base_ptr = base.data_ptr()
+    name, size = MOE_DOWN_COMBINE[bool(kn)]
+    fn = _entry(name)
+    need = _workspace_size(size, S, count, n, k, split)
+    out, ldy = _packed_out(out, T, n, out_dtype, h.device)
+    ws_ptr, ws_bytes = _packed_workspace(workspace, need, h.device)
+    check(fn(h.data_ptr(), k, ldx, pg, ptr, arena.numel(), pm, po, pb, count, n, expert_code, pr, weights.data_ptr(), _rows_ld(weights, T, K),
+             base_ptr, base_code, ldbase, T, K, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
     return out
 
 MOE_ROUTE = ("mtq_moe_route",)

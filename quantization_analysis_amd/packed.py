@@ -31,8 +31,10 @@ directory's index.json, where such a run marks its entries "stored": "transpose"
 moe_plan / moe_dispatch / moe_combine / PackedMoE are the rest of an MoE layer around PackedExpertsMLP (csrc/mtq_moe.hip): from the
 router's (tokens, top_k) expert ids a stable counting sort on the device gives the grouped entries' row layout (MoEPlan), a row gather
 puts the tokens in it, and a weighted un-permute with a fixed summation order brings the experts' rows back; nothing is read back to
-the host.  The gather is not fused into the GEMMs' X loads and the combine not into the down projection's epilogue (both would
-change existing kernels).
+the host.  On that staged route the gather and the combine are kernels of their own.
+moe_glu / moe_down_combine are the decode route without them (include/mtq_moe_decode.h): the gather inside the grouped skinny GLU
+wave's X loads, the combine inside the down projection's reduce, the staged route's bits from five launches for seven and without the
+(S, k) and (S, k_out) intermediates; PackedMoE(decode_route="fused") runs plan → moe_glu → moe_down_combine up to decode_max_rows slots.
 
 moe_route / MoERouting / MOE_ROUTINGS are the router in front of that (csrc/mtq_moe_route.hip): from the router GEMM's logits to
 (topk_weights, topk_ids) in one launch - softmax or sigmoid scores, a selection-only bias, group-limited top-k, renormalised and scaled
@@ -1731,6 +1733,116 @@ def moe_combine(ys, topk_weights, plan: MoEPlan, base=None, out_dtype: str = "fl
     return y
 
 
+# ----------------------------------------------------------------------------- MoE decode without the staging copies
+
+MOE_DECODE_ROUTES = ("staged", "fused")      # PackedMoE(decode_route=...)
+
+
+def _moe_orientation(stored) -> _Orientation:
+    if stored not in MOE_STORED:
+        raise MtqError(f"stored must be one of {MOE_STORED}, got {stored!r}")
+    return _KN if stored == "transpose" else _NK
+
+
+def _need_moe_decode(hb, what: str, kn: bool) -> None:
+    if not hb.moe_decode_bound(kn):
+        names = hb.MOE_GATHER[kn] + hb.MOE_DOWN_COMBINE[kn]
+        raise MtqError(f"{what} needs {' and '.join(names)}, which this build of libmtq_hip.so lacks: rebuild it from this tree")
+
+
+def _moe_stage_backend(plan: MoEPlan, backend) -> str:
+    backend = backend or _plan_backend(plan)
+    _check_backend(backend)
+    if backend != _plan_backend(plan):
+        raise MtqError(f"backend {backend!r} needs a plan made on it: this plan is the {_plan_backend(plan)} backend's")
+    return backend
+
+
+def moe_glu(x, plan: MoEPlan, gate_batch, up_batch, act: str = "silu", out_dtype: str = "bfloat16", stored: str = "rows", split: int = 0,
+            workspace=None, backend: Optional[str] = None):
+    """From the token matrix to the experts' gated rows in one step: x (tokens, k) bf16 → h (S, n) in expert order,
+    h[r] = act(x[t]·Ŵg[e]ᵀ) * (x[t]·Ŵu[e]ᵀ) for the slot s = plan.src[r] of token t = s // topk and the expert e that owns row r; rows from
+    R = group_rows[count] on are zeros.  stored (MOE_STORED): "rows", the batches hold (n, k) experts; "transpose", (k, n) experts.
+    hip: mtq_packed_glu_skinny_grouped_gather (its matmul twin), two launches: the grouped skinny GLU wave reads its X groups from the
+    token's own row, so the dispatched (S, k) copy is never written.  Bit for bit moe_dispatch then glu_grouped_skinny
+    (glu_matmul_grouped_skinny) at the same `split`.  workspace: an optional uint8 device tensor of
+    hip_backend.moe_glu_gather_workspace_bytes bytes.  For decode-sized S: a group above 32 rows is walked in chunks by one wave.
+    emulation: moe_dispatch and the emulated glu_grouped_skinny on the first R rows, composed."""
+    o = _moe_orientation(stored)
+    gate_b, up_b = _resolve_batch(gate_batch), _resolve_batch(up_batch)
+    _check_act(act)
+    _check_out_dtype(out_dtype)
+    if (gate_b.count, gate_b.rows, gate_b.cols) != (up_b.count, up_b.rows, up_b.cols):
+        raise MtqError(f"the gate and the up batch must hold as many experts of one shape, got {gate_b.count} of {gate_b.rows}x{gate_b.cols} and "
+                       f"{up_b.count} of {up_b.rows}x{up_b.cols}")
+    count, (n, k) = gate_b.count, o.n_k(gate_b)
+    T, K, S = plan.tokens, plan.topk, plan.slots
+    if count != plan.count:
+        raise MtqError(f"the plan is for {plan.count} experts, the batches hold {count}")
+    if len(x.shape) != 2 or tuple(x.shape) != (T, k):
+        raise MtqError(f"x must be ({T}, {k}), got {tuple(x.shape)}")
+    backend = _moe_stage_backend(plan, backend)
+    if backend == "hip":
+        _need_moe_decode(hb, "moe_glu", o.kn)        # a missing kernel is refused before any device work
+        gate_b, up_b = batch_to_device(gate_b), batch_to_device(up_b)
+        return hb.moe_glu_gather(x, plan.src, K, plan.group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, act=act,
+                                 out_dtype=_torch_dtype(out_dtype), split=split, workspace=workspace, kn=o.kn)
+    import torch
+
+    xs = _as_torch(moe_dispatch(x, plan))
+    R = int(plan.group_rows[-1])
+    h = torch.zeros((S, n), dtype=_torch_dtype(out_dtype))
+    if R:
+        h[:R] = _as_torch(globals()[o.glu_grouped_skinny](xs[:R], plan.group_rows, gate_b, up_b, act=act, out_dtype=out_dtype, backend="emulation"))
+    return h
+
+
+def moe_down_combine(h, topk_weights, plan: MoEPlan, down_batch, base=None, expert_dtype: str = "float32", out_dtype: str = "float32",
+                     stored: str = "rows", split: int = 0, workspace=None, out=None, backend: Optional[str] = None):
+    """From the experts' gated rows to the layer's output in one step: h (S, n) bf16 in expert order (moe_glu's result), topk_weights
+    (tokens, topk) float32, base None or (tokens, k_out) → y (tokens, k_out) in out_dtype: the down projection of every row by its
+    expert, rounded as a matrix of expert_dtype would hold it, then moe_combine's weighted sum in its order.
+    hip: mtq_packed_linear_skinny_grouped_combine (its matmul twin), two launches: the grouped skinny wave writes float32 partial sums
+    and one reduce kernel sums the slices, rounds, weighs and adds, so the experts' (S, k_out) rows are never written.  Bit for bit
+    linear_grouped(kernel="walk") (matmul_grouped) into expert_dtype at the same `split`, then moe_combine.  workspace: an optional
+    uint8 device tensor of hip_backend.moe_down_combine_workspace_bytes bytes; out: an optional (tokens, k_out) device tensor.
+    emulation: the emulated grouped product on the first R rows and the emulated moe_combine, composed."""
+    o = _moe_orientation(stored)
+    down = _resolve_batch(down_batch)
+    _check_out_dtype(out_dtype)
+    _check_out_dtype(expert_dtype, "expert_dtype")
+    count, (n, k) = down.count, o.n_k(down)
+    T, K, S = plan.tokens, plan.topk, plan.slots
+    if count != plan.count:
+        raise MtqError(f"the plan is for {plan.count} experts, the batch holds {count}")
+    if len(h.shape) != 2 or tuple(h.shape) != (S, k):
+        raise MtqError(f"h must be ({S}, {k}), one row per slot, got {tuple(h.shape)}")
+    if tuple(topk_weights.shape) != (T, K):
+        raise MtqError(f"topk_weights must be ({T}, {K}), got {tuple(topk_weights.shape)}")
+    if str(topk_weights.dtype).replace("torch.", "") != "float32":
+        raise MtqError(f"topk_weights must be float32, got {topk_weights.dtype}")
+    if base is not None and tuple(base.shape) != (T, n):
+        raise MtqError(f"base must be ({T}, {n}), got {tuple(base.shape)}")
+    backend = _moe_stage_backend(plan, backend)
+    if backend == "hip":
+        import torch
+
+        _need_moe_decode(hb, "moe_down_combine", o.kn)
+        down = batch_to_device(down)
+        if not _is_torch(topk_weights):
+            topk_weights = torch.from_numpy(np.ascontiguousarray(topk_weights)).to(plan.row_of.device)
+        return hb.moe_down_combine(h, plan.group_rows, *_arena_args(down), count, n, plan.row_of, topk_weights, base=base,
+                                   expert_dtype=_torch_dtype(expert_dtype), out_dtype=_torch_dtype(out_dtype), out=out, split=split,
+                                   workspace=workspace, kn=o.kn)
+    import torch
+
+    R = int(plan.group_rows[-1])
+    ys = torch.zeros((S, n), dtype=_torch_dtype(expert_dtype))
+    if R:
+        ys[:R] = _as_torch(globals()[o.grouped](_as_torch(h)[:R], plan.group_rows, down, out_dtype=expert_dtype, backend="emulation", kernel="walk"))
+    return moe_combine(ys, topk_weights, plan, base=base, out_dtype=out_dtype, out=out)
+
+
 # ----------------------------------------------------------------------------- MoE router: scoring and group-limited top-k
 
 MOE_MAX_GROUPS = 64          # include/mtq.h MTQ_MOE_MAX_GROUPS
@@ -2129,13 +2241,23 @@ def _packed_moe_class():
         stored (MOE_STORED, the word of a pack_model directory's index.json): "rows", the experts are (n, k) batches and run through
         PackedExpertsMLP; "transpose", they are (k, n) batches - gate and up (k, hidden), down (hidden, k_out), what pack_model
         --store-transposed and pack_batch_transposed write - and run through PackedExpertsMatmulMLP.  Plan, dispatch and combine are the same.
+        decode_route (MOE_DECODE_ROUTES): "staged", the chain above at every size; "fused" (needs decode_max_rows), a forward with
+        S <= decode_max_rows runs plan → moe_glu → moe_down_combine instead: the gather inside the gated product's X loads and the
+        combine inside the down projection's reduce, five launches for seven and no (S, k) or (S, k_out) intermediate, bit for bit the
+        staged decode route's result; a larger call takes the staged route.  One workspace sized here serves both launches.
         hip: no device-to-host copy and no .item() in a forward; the plan workspace is allocated here for max_tokens tokens and
         regrown when a call needs more.  emulation: CPU tensors, for use without a GPU."""
 
         def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", expert_dtype: str = "float32",
                      backend: Optional[str] = None, decode_max_rows: Optional[int] = None, max_tokens: int = 4096, stored: str = "rows",
-                     router=None):
+                     router=None, decode_route: str = "staged"):
             super().__init__()
+            if decode_route not in MOE_DECODE_ROUTES:
+                raise MtqError(f"decode_route must be one of {MOE_DECODE_ROUTES}, got {decode_route!r}")
+            if decode_route == "fused" and decode_max_rows is None:
+                raise MtqError('decode_route="fused" needs decode_max_rows: the fused route is the decode route, for calls of at most that many slots')
+            if decode_route == "fused" and backend == "hip" and stored in MOE_STORED:      # before any device work; asked again for a default backend
+                _need_moe_decode(hb, 'PackedMoE(decode_route="fused")', stored == "transpose")
             if isinstance(router, str):
                 if router not in MOE_ROUTINGS:
                     raise MtqError(f"router must be a MoERouting or one of {tuple(MOE_ROUTINGS)}, got {router!r}")
@@ -2160,10 +2282,18 @@ def _packed_moe_class():
             if router is not None:
                 router.check_count(self.count)
             self._plan_workspace = None
+            self.decode_route, self._fused_workspace = decode_route, None
             if self.backend == "hip":
                 _need_moe(hb, "PackedMoE")           # refused here, not at the first forward
                 if router is not None:
                     _need_moe_route(hb, "PackedMoE(router=...)")
+                if decode_route == "fused":          # one buffer for both launches: each is done with it before the next starts
+                    kn = stored == "transpose"
+                    _need_moe_decode(hb, 'PackedMoE(decode_route="fused")', kn)
+                    ex = self.experts
+                    need = max(hb.moe_glu_gather_workspace_bytes(decode_max_rows, ex.count, ex.hidden_features, ex.in_features, kn=kn),
+                               hb.moe_down_combine_workspace_bytes(decode_max_rows, ex.count, ex.out_features, ex.hidden_features, kn=kn))
+                    self._fused_workspace = torch.empty((need,), dtype=torch.uint8, device=ex.gate.arena.device)
                 need = hb.moe_plan_workspace_bytes(max_tokens, MOE_PLAN_TOPK, self.count)
                 self._plan_workspace = torch.empty((need,), dtype=torch.uint8, device=self.experts.gate.arena.device)
 
@@ -2191,6 +2321,14 @@ def _packed_moe_class():
                 if self._plan_workspace.numel() < need:
                     self._plan_workspace = torch.empty((need,), dtype=torch.uint8, device=self._plan_workspace.device)
             plan = moe_plan(topk_ids.reshape(T, K), self.count, backend=self.backend, workspace=self._plan_workspace)
+            if self.decode_route == "fused" and plan.slots <= self.experts.decode_max_rows:
+                ex = self.experts
+                h = moe_glu(x2, plan, ex.gate, ex.up, act=ex.act, out_dtype="bfloat16", stored=self.stored, workspace=self._fused_workspace,
+                            backend=self.backend)
+                y = moe_down_combine(h, topk_weights.reshape(T, K), plan, ex.down, base=None if base is None else base.reshape(T, self.out_features),
+                                     expert_dtype=self.expert_dtype, out_dtype=self.out_dtype, stored=self.stored,
+                                     workspace=self._fused_workspace, backend=self.backend)
+                return _as_torch(y).reshape(lead + (self.out_features,))
             xs = moe_dispatch(x2, plan)
             if self.backend == "hip":
                 ys = self.experts(xs, plan.group_rows)               # all S rows: the rows from R on belong to no group and stay zero
