@@ -1219,7 +1219,8 @@ int mtq_moe_combine(const void *ys, int ys_dtype, int64_t ldys, const int32_t *r
 
 /* The MoE decode entries without the staging copies - the gather inside the gated product's X loads, the combine inside the down
  * projection's reduce - are declared in mtq_moe_decode.h, included at the end of this header: their contracts stand there, beside
- * this section's, which they refer to. */
+ * this section's, which they refer to.  Their forms with a wave per 32-row chunk, for routings with hot experts, are declared in
+ * mtq_glu_chunked.h, included after it. */
 
 /* ------------------------------------------------------------------ MoE router: scoring and group-limited top-k (csrc/mtq_moe_route.hip)
  * From the router's logits (tokens, count), bf16 or float32 (logits_dtype, MTQ_DTYPE_*) at pitch ld_logits, to what the plan and the
@@ -1269,4 +1270,5 @@ int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream
 }
 #endif
 #include "mtq_moe_decode.h"
+#include "mtq_glu_chunked.h"
 #endif /* MTQ_H */

@@ -53,6 +53,10 @@
 //                                             an MoE layer's decode route without its staging copies (include/mtq_moe_decode.h): the two
 //       grouped skinny GLU waves reading their X groups from the token's own row through the plan's src (mtq_moe_dispatch's rule, its
 //       bits), and the grouped skinny down projection's reduce with mtq_moe_combine's weighted sum in it.
+//   packed_glu_skinny_grouped_chunked_kernel<GATHER>, packed_glu_matmul_skinny_grouped_chunked_kernel<GATHER>,
+//   glu_skinny_grouped_chunked_reduce_kernel  the grouped skinny GLU waves with a wave per 32-row chunk of a group, on the chunked linear
+//       kernels' plan and search (include/mtq_glu_chunked.h): the walking kernels' bits, for routings with hot experts; the reduce
+//       takes a workgroup per chunk slot.  The down projection with the combine uses the chunked linear kernels as they stand.
 //
 // The wide kernels are frames around one block function, wide_block; the skinny kernels around one wave's run, skinny_run, and one
 // epilogue, store_lane_rows; all of them read a tensor through a PackedStream and guard a blob with stream_at.
@@ -2236,6 +2240,131 @@ __global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_matmul_skinny
     }
 }
 
+// ---- grouped skinny GLU, a wave per 32-row chunk: packed_glu_skinny_grouped_kernel's wave on packed_linear_skinny_grouped_chunked_kernel's
+// frame.
+//
+// A unit is (slice s, projection p, chunk slot c, tile row tr), numbered (((2 s + p) * slots + c) * tiles_h + tr): the four waves of a
+// workgroup share a slice, a projection and, but for a seam, a chunk's rows of X.  cstart is packed_grouped_plan_kernel<32>'s prefix on
+// the same stream, slots the host's bound on cstart[count]; a wave whose slot is at or past cstart[count] returns before any other load,
+// the group comes from group_of_slot and row0 = r0 + 32 (c - cstart[e]).  On its chunk the wave does the body of the walking kernel's
+// `for row0` loop: the same arena_stream of its projection's arena, the same skinny_run arguments (gather_row as it stands with GATHER),
+// the same store_lane_rows into ws[p][s][row][n] at every split - that kernel's partials, bit for bit, for nondecreasing group_rows.
+template <bool GATHER>
+__global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_skinny_grouped_chunked_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
+    const int32_t *__restrict__ cstart, int slots, const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps,
+    const uint32_t *__restrict__ gate_offsets, const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes,
+    const int8_t *__restrict__ up_maps, const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int N,
+    int tiles_h, int tiles_w, int split, float *__restrict__ ws, const int32_t *__restrict__ src, int topk)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= (int64_t)2 * tiles_h * slots * split) return;   // wave-uniform; the kernel has no barrier
+    const int64_t tr = unit % tiles_h, spc = unit / tiles_h, sp = spc / slots, p = sp & 1, s = sp >> 1;
+    const int c = (int)(spc % slots);
+    if (c >= cstart[count]) return;                  // a surplus slot: nothing else is read
+    const int e = group_of_slot(cstart, count, c, lane);
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    const int64_t row0 = gr.r0 + (int64_t)(c - cstart[e]) * kTile;
+    if (row0 >= gr.r1) return;                       // never for a prefix this launch's plan kernel wrote
+    const PackedStream st = arena_stream(p ? up : gate, p ? up_bytes : gate_bytes, p ? up_maps : gate_maps, p ? up_offsets : gate_offsets,
+                                         p ? up_bases : gate_bases, e, (int64_t)tiles_h * tiles_w);
+    const int64_t c0 = s * tiles_w / split, c1 = (s + 1) * tiles_w / split;
+
+    const int row = lane & 31, half = lane >> 5;
+    const int64_t n = tr * kTile + row;
+    const int64_t M = std::min<int64_t>(kTile, gr.r1 - row0);
+    f32x16 acc = zero16();
+    if constexpr (GATHER) {
+        const GatherRow xr = gather_row(x, ldx, src, topk, T, row0, row, M);
+        skinny_run(acc, FeedDirect(), xr.x, xr.m, K, ldx, x_vec, st, tr * tiles_w, 1, c0, c1, lane, 0, half, 2 * row + half);
+    } else {
+        skinny_run(acc, FeedDirect(), x + row0 * ldx, M, K, ldx, x_vec, st, tr * tiles_w, 1, c0, c1, lane, row, half, 2 * row + half);
+    }
+
+    // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tr + row) of slice s of projection p
+    if (n >= N) return;
+    store_lane_rows<false, true>(acc, M, half, ws, (((int64_t)p * split + s) * T + row0 + 4 * half) * N + n, N, 0.0f);
+}
+
+// The (k, n) twin on packed_matmul_skinny_grouped_chunked_kernel's frame: a unit is (slice s, projection p, chunk slot c, tile column tc),
+// numbered (((2 s + p) * slots + c) * tiles_nw + tc), the run goes through the wave's two [32 k][32 n] images (feed_transposed).
+// EXEC: packed_matmul_skinny_grouped_chunked_kernel's rule.  Every branch before the run - the unit bound, the surplus slot,
+// row0 >= r1 - is wave-uniform: the wave index, the group, its clamped rows and row0 go through readfirstlane.  gather_row's src load is
+// a select on the lane's row, not a branch around the run; the one lane-dependent branch is the n < N guard after the run.
+template <bool GATHER>
+__global__ __launch_bounds__(64 * kSkinnyWaves, 2) void packed_glu_matmul_skinny_grouped_chunked_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, const int32_t *__restrict__ group_rows,
+    const int32_t *__restrict__ cstart, int slots, const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps,
+    const uint32_t *__restrict__ gate_offsets, const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes,
+    const int8_t *__restrict__ up_maps, const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int N,
+    int tiles_kh, int tiles_nw, int split, float *__restrict__ ws, const int32_t *__restrict__ src, int topk)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[kSkinnyWaves * 2 * kMmsImage];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit = (int64_t)blockIdx.x * kSkinnyWaves + wave;
+    if (unit >= (int64_t)2 * tiles_nw * slots * split) return;   // wave-uniform; the kernel has no workgroup barrier
+    const int64_t tc = unit % tiles_nw, spc = unit / tiles_nw, sp = spc / slots, p = sp & 1, s = sp >> 1;
+    const int c = (int)(spc % slots);
+    if (c >= cstart[count]) return;                  // a surplus slot: nothing else is read
+    const int e = __builtin_amdgcn_readfirstlane(group_of_slot(cstart, count, c, lane));
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    const int r1 = __builtin_amdgcn_readfirstlane((int)gr.r1);
+    const int64_t row0 = __builtin_amdgcn_readfirstlane((int)gr.r0) + (int64_t)(c - __builtin_amdgcn_readfirstlane(cstart[e])) * kTile;
+    if (row0 >= r1) return;                          // never for a prefix this launch's plan kernel wrote
+    const PackedStream st = arena_stream(p ? up : gate, p ? up_bytes : gate_bytes, p ? up_maps : gate_maps, p ? up_offsets : gate_offsets,
+                                         p ? up_bases : gate_bases, e, (int64_t)tiles_kh * tiles_nw);
+    const int64_t c0 = s * tiles_kh / split, c1 = (s + 1) * tiles_kh / split;
+
+    const int row = lane & 31, half = lane >> 5;
+    const int64_t n = tc * kTile + row;
+    const int64_t M = std::min<int64_t>(kTile, r1 - row0);
+    f32x16 acc = zero16();
+    const FeedTransposed feed = feed_transposed(lds + wave * (2 * kMmsImage), lane);
+    if constexpr (GATHER) {
+        const GatherRow xr = gather_row(x, ldx, src, topk, T, row0, row, M);
+        skinny_run(acc, feed, xr.x, xr.m, K, ldx, x_vec, st, tc, tiles_nw, c0, c1, lane, 0, half, lane);
+    } else {
+        skinny_run(acc, feed, x + row0 * ldx, M, K, ldx, x_vec, st, tc, tiles_nw, c0, c1, lane, row, half, lane);
+    }
+
+    // lane's outputs are (row0 + (r&3) + 8(r>>2) + 4·half, n = 32·tc + row) of slice s of projection p
+    if (n >= N) return;
+    store_lane_rows<false, true>(acc, M, half, ws, (((int64_t)p * split + s) * T + row0 + 4 * half) * N + n, N, 0.0f);
+}
+
+// The reduce over chunk slots: one workgroup per (chunk slot c, 256 columns), thread n walks the chunk's at most 32 rows, so a hot
+// group's rows are spread over its chunks' workgroups where glu_skinny_grouped_reduce_kernel gives them all to one thread per column.
+// The slot's group is the main kernel's (group_of_slot on the same cstart, by every wave of the workgroup alike, before the column
+// guard: the search's ballot wants the whole wave).  g, u and glu_value are formed as that kernel forms them - slices ascending, bias
+// last - and an output depends on its own row and column alone: that kernel's bits.  Only rows inside a clamped group are written.
+template <bool BF16OUT>
+__global__ __launch_bounds__(256) void glu_skinny_grouped_chunked_reduce_kernel(const float *__restrict__ ws, int64_t T, int64_t N, int split,
+                                                                                const int32_t *__restrict__ group_rows,
+                                                                                const int32_t *__restrict__ cstart, int count, int64_t nchunks,
+                                                                                const float *__restrict__ bias_gate,
+                                                                                const float *__restrict__ bias_up, int64_t ldb, int act,
+                                                                                void *__restrict__ yv, int64_t ldy)
+{
+    const int c = (int)(blockIdx.x / nchunks);
+    const int64_t n = (blockIdx.x % nchunks) * 256 + threadIdx.x;
+    if (c >= cstart[count]) return;                  // a surplus slot, the whole workgroup
+    const int e = group_of_slot(cstart, count, c, threadIdx.x & 63);
+    if (n >= N) return;
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    const int64_t row0 = gr.r0 + (int64_t)(c - cstart[e]) * kTile, row1 = std::min<int64_t>(row0 + kTile, gr.r1);
+    const float bg = bias_gate ? bias_gate[e * ldb + n] : 0.0f, bu = bias_up ? bias_up[e * ldb + n] : 0.0f;
+    const float *wu = ws + (int64_t)split * T * N;
+    for (int64_t m = row0; m < row1; ++m) {
+        float g = ws[m * N + n], u = wu[m * N + n];
+        for (int s = 1; s < split; ++s) g += ws[((int64_t)s * T + m) * N + n];
+        for (int s = 1; s < split; ++s) u += wu[((int64_t)s * T + m) * N + n];
+        g += bg;
+        u += bu;
+        store_y<BF16OUT>(yv, m * ldy + n, glu_value(g, u, act));
+    }
+}
+
 // skinny_shape for the grouped entry: skinny_split's rule with count * tiles_h tile rows, which for count == 1 is that rule.
 int grouped_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split, int64_t *tiles_h, int64_t *tiles_w, int *split_eff)
 {
@@ -2854,7 +2983,7 @@ static int packed_skinny_grouped_combine(bool kn, const char *name, const void *
                                          const uint64_t *bases, int64_t count, int64_t n, int expert_dtype, const int32_t *row_of,
                                          const float *weights, int64_t ldw, const void *base, int base_dtype, int64_t ldbase, int64_t tokens,
                                          int64_t topk, void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
-                                         void *stream)
+                                         void *stream, bool chunks = false)
 {
     TileGrid g;
     int64_t S = 0;
@@ -2879,18 +3008,31 @@ static int packed_skinny_grouped_combine(bool kn, const char *name, const void *
     if (reinterpret_cast<uintptr_t>(y) % y_el != 0 || reinterpret_cast<uintptr_t>(row_of) % 4 != 0 || reinterpret_cast<uintptr_t>(weights) % 4 != 0 ||
         (base && reinterpret_cast<uintptr_t>(base) % base_el != 0))
         return fail(MTQ_ERR_INVALID, "an operand is not aligned to its type");
-    if (int rc = workspace_args(workspace, workspace_bytes, skinny_combine_workspace(S, n, g.eff),
+    // chunks: the plan region at the workspace's head and 5.'s wave, a unit axis of `slots` chunk slots where the walk has `count` groups
+    const size_t plan = chunks ? grouped_plan_bytes(count) : 0;
+    if (int rc = workspace_args(workspace, workspace_bytes, plan + skinny_combine_workspace(S, n, g.eff),
                                 "workspace is null: the experts' partial sums need one at every split", "split"))
         return rc;
-    const int64_t blocks = (count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves, nchunks = grouped_nchunks(n);
-    if (int rc = grid_args({blocks, tokens * nchunks})) return rc;
+    const int64_t slots = chunks ? grouped_slots(S, count, kTile) : count;
+    const int64_t blocks = (slots * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves, nchunks = grouped_nchunks(n);
+    if (int rc = grid_args({slots, blocks, tokens * nchunks})) return rc;
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(kn ? packed_matmul_skinny_grouped_kernel<false> : packed_linear_skinny_grouped_kernel<false>, dim3((unsigned)blocks),
-                       dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), S, k, ldx, (int)x_vec_of(x, ldx), group_rows,
-                       static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.sh(kn), g.sw(kn), g.eff,
-                       static_cast<const float *>(nullptr), (int64_t)0, static_cast<void *>(ws), n, ws);
+    float *ws = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + plan);
+    if (chunks) {
+        int32_t *cstart = static_cast<int32_t *>(workspace);
+        if (int rc = launch_plan<kTile>(name, st, group_rows, count, S, cstart)) return rc;
+        hipLaunchKernelGGL(kn ? packed_matmul_skinny_grouped_chunked_kernel<false> : packed_linear_skinny_grouped_chunked_kernel<false>,
+                           dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), (int)S, (int)k, ldx,
+                           (int)x_vec_of(x, ldx), group_rows, static_cast<const int32_t *>(cstart), (int)slots,
+                           static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, (int)count, (int)n, (int)g.sh(kn),
+                           (int)g.sw(kn), g.eff, static_cast<const float *>(nullptr), (int64_t)0, static_cast<void *>(ws), n, ws);
+    } else {
+        hipLaunchKernelGGL(kn ? packed_matmul_skinny_grouped_kernel<false> : packed_linear_skinny_grouped_kernel<false>, dim3((unsigned)blocks),
+                           dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), S, k, ldx, (int)x_vec_of(x, ldx), group_rows,
+                           static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, count, n, g.sh(kn), g.sw(kn), g.eff,
+                           static_cast<const float *>(nullptr), (int64_t)0, static_cast<void *>(ws), n, ws);
+    }
     if (int rc = check_launch(name)) return rc;
     const int base_kind = !base ? 0 : (base_dtype == MTQ_DTYPE_BF16 ? 1 : 2);
     const dim3 grid((unsigned)(tokens * nchunks));
@@ -3260,7 +3402,7 @@ static int packed_glu_skinny_grouped(bool kn, const char *name, const void *x, i
                                      const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n, const float *bias_gate,
                                      const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, int split, void *workspace,
                                      size_t workspace_bytes, void *stream, bool gather = false, const int32_t *src = nullptr, int64_t tokens = 0,
-                                     int64_t topk = 0)
+                                     int64_t topk = 0, bool chunks = false)
 {
     TileGrid g;
     if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
@@ -3280,13 +3422,32 @@ static int packed_glu_skinny_grouped(bool kn, const char *name, const void *x, i
             return fail(MTQ_ERR_INVALID, "x or src is not aligned to its type");
     }
     if (int rc = glu_act(act)) return rc;
-    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(total_rows, n, g.eff), kWsGlu, "split")) return rc;
-    const int64_t blocks = (2 * count * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
+    // chunks: the plan region at the workspace's head, a unit axis of `slots` chunk slots where the walk has `count` groups
+    const size_t plan = chunks ? grouped_plan_bytes(count) : 0;
+    if (int rc = workspace_args(workspace, workspace_bytes, plan + glu_skinny_workspace(total_rows, n, g.eff), kWsGlu, "split")) return rc;
+    const int64_t slots = chunks ? grouped_slots(total_rows, count, kTile) : count;
+    const int64_t blocks = (2 * slots * g.th * g.eff + kSkinnyWaves - 1) / kSkinnyWaves;
     const int64_t nchunks = grouped_nchunks(n);
-    if (int rc = grid_args({blocks, count * nchunks})) return rc;
+    if (int rc = grid_args({slots, blocks, slots * nchunks})) return rc;
     if (int rc = require_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws = static_cast<float *>(workspace);
+    float *ws = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + plan);
+    if (chunks) {
+        int32_t *cstart = static_cast<int32_t *>(workspace);
+        if (int rc = launch_plan<kTile>(name, st, group_rows, count, total_rows, cstart)) return rc;
+        hipLaunchKernelGGL(gather ? (kn ? packed_glu_matmul_skinny_grouped_chunked_kernel<true> : packed_glu_skinny_grouped_chunked_kernel<true>)
+                                  : (kn ? packed_glu_matmul_skinny_grouped_chunked_kernel<false> : packed_glu_skinny_grouped_chunked_kernel<false>),
+                           dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), (int)total_rows, (int)k, ldx,
+                           (int)x_vec_of(x, ldx), group_rows, static_cast<const int32_t *>(cstart), (int)slots,
+                           static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases,
+                           static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases, (int)count, (int)n,
+                           (int)g.sh(kn), (int)g.sw(kn), g.eff, ws, src, (int)topk);
+        if (int rc = check_launch(name)) return rc;
+        launch_out(out_dtype, glu_skinny_grouped_chunked_reduce_kernel<true>, glu_skinny_grouped_chunked_reduce_kernel<false>,
+                   dim3((unsigned)(slots * nchunks)), dim3(256), st, ws, total_rows, n, g.eff, group_rows, static_cast<const int32_t *>(cstart),
+                   (int)count, nchunks, bias_gate, bias_up, ldb, act, y, ldy);
+        return check_launch(name);
+    }
     hipLaunchKernelGGL(gather ? (kn ? packed_glu_matmul_skinny_grouped_kernel<true> : packed_glu_skinny_grouped_kernel<true>)
                               : (kn ? packed_glu_matmul_skinny_grouped_kernel<false> : packed_glu_skinny_grouped_kernel<false>),
                        dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), 0, st, static_cast<const uint16_t *>(x), (int)total_rows, (int)k, ldx,
@@ -3360,6 +3521,121 @@ extern "C" int mtq_packed_glu_matmul_skinny_grouped_gather(const void *x, int64_
     return packed_glu_skinny_grouped(true, "mtq_packed_glu_matmul_skinny_grouped_gather", x, 0, k, ldx, group_rows, gate_packed, gate_bytes,
                                      gate_maps, gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate,
                                      bias_up, ldb, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream, true, src, tokens, topk);
+}
+
+// 10c. The decode route's entries with a wave per 32-row chunk (include/mtq_glu_chunked.h): the bodies of 10., 10g. and 4c. with
+// `chunks` set - the parent's checks in the parent's order, the plan region of 5. at the head of the parent's workspace.
+static size_t chunked_size(size_t parent, int64_t count) { return parent == (size_t)-1 ? parent : grouped_plan_bytes(count) + parent; }
+
+extern "C" size_t mtq_packed_glu_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return chunked_size(mtq_packed_glu_skinny_grouped_workspace_bytes(total_rows, count, n, k, split), count);
+}
+
+extern "C" size_t mtq_packed_glu_matmul_skinny_grouped_chunked_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_glu_skinny_grouped_chunked_workspace_bytes(total_rows, count, n, k, split);
+}
+
+extern "C" size_t mtq_packed_glu_skinny_grouped_chunked_gather_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_glu_skinny_grouped_chunked_workspace_bytes(total_rows, count, n, k, split);
+}
+
+extern "C" size_t mtq_packed_glu_matmul_skinny_grouped_chunked_gather_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k,
+                                                                                      int split)
+{
+    return mtq_packed_glu_skinny_grouped_chunked_workspace_bytes(total_rows, count, n, k, split);
+}
+
+extern "C" size_t mtq_packed_linear_skinny_grouped_chunked_combine_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return chunked_size(mtq_packed_linear_skinny_grouped_combine_workspace_bytes(total_rows, count, n, k, split), count);
+}
+
+extern "C" size_t mtq_packed_matmul_skinny_grouped_chunked_combine_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_linear_skinny_grouped_chunked_combine_workspace_bytes(total_rows, count, n, k, split);
+}
+
+extern "C" int mtq_packed_glu_skinny_grouped_chunked(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                     const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps,
+                                                     const uint32_t *gate_offsets, const uint64_t *gate_bases, const void *up_packed,
+                                                     size_t up_bytes, const int8_t *up_maps, const uint32_t *up_offsets, const uint64_t *up_bases,
+                                                     int64_t count, int64_t n, const float *bias_gate, const float *bias_up, int64_t ldb, int act,
+                                                     void *y, int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                                     void *stream)
+{
+    return packed_glu_skinny_grouped(false, "mtq_packed_glu_skinny_grouped_chunked", x, total_rows, k, ldx, group_rows, gate_packed, gate_bytes,
+                                     gate_maps, gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate,
+                                     bias_up, ldb, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream, false, nullptr, 0, 0, true);
+}
+
+extern "C" int mtq_packed_glu_matmul_skinny_grouped_chunked(const void *x, int64_t total_rows, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                            const void *gate_packed, size_t gate_bytes, const int8_t *gate_maps,
+                                                            const uint32_t *gate_offsets, const uint64_t *gate_bases, const void *up_packed,
+                                                            size_t up_bytes, const int8_t *up_maps, const uint32_t *up_offsets,
+                                                            const uint64_t *up_bases, int64_t count, int64_t n, const float *bias_gate,
+                                                            const float *bias_up, int64_t ldb, int act, void *y, int out_dtype, int64_t ldy,
+                                                            int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return packed_glu_skinny_grouped(true, "mtq_packed_glu_matmul_skinny_grouped_chunked", x, total_rows, k, ldx, group_rows, gate_packed, gate_bytes,
+                                     gate_maps, gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate,
+                                     bias_up, ldb, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream, false, nullptr, 0, 0, true);
+}
+
+extern "C" int mtq_packed_glu_skinny_grouped_chunked_gather(const void *x, int64_t tokens, int64_t topk, int64_t k, int64_t ldx, const int32_t *src,
+                                                            const int32_t *group_rows, const void *gate_packed, size_t gate_bytes,
+                                                            const int8_t *gate_maps, const uint32_t *gate_offsets, const uint64_t *gate_bases,
+                                                            const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                                            const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n,
+                                                            const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y,
+                                                            int out_dtype, int64_t ldy, int split, void *workspace, size_t workspace_bytes,
+                                                            void *stream)
+{
+    return packed_glu_skinny_grouped(false, "mtq_packed_glu_skinny_grouped_chunked_gather", x, 0, k, ldx, group_rows, gate_packed, gate_bytes,
+                                     gate_maps, gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate,
+                                     bias_up, ldb, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream, true, src, tokens, topk, true);
+}
+
+extern "C" int mtq_packed_glu_matmul_skinny_grouped_chunked_gather(const void *x, int64_t tokens, int64_t topk, int64_t k, int64_t ldx,
+                                                                   const int32_t *src, const int32_t *group_rows, const void *gate_packed,
+                                                                   size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                                                   const uint64_t *gate_bases, const void *up_packed, size_t up_bytes,
+                                                                   const int8_t *up_maps, const uint32_t *up_offsets, const uint64_t *up_bases,
+                                                                   int64_t count, int64_t n, const float *bias_gate, const float *bias_up,
+                                                                   int64_t ldb, int act, void *y, int out_dtype, int64_t ldy, int split,
+                                                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    return packed_glu_skinny_grouped(true, "mtq_packed_glu_matmul_skinny_grouped_chunked_gather", x, 0, k, ldx, group_rows, gate_packed, gate_bytes,
+                                     gate_maps, gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate,
+                                     bias_up, ldb, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream, true, src, tokens, topk, true);
+}
+
+extern "C" int mtq_packed_linear_skinny_grouped_chunked_combine(const void *x, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                                const void *packed, size_t packed_bytes, const int8_t *maps,
+                                                                const uint32_t *offsets, const uint64_t *bases, int64_t count, int64_t n,
+                                                                int expert_dtype, const int32_t *row_of, const float *weights, int64_t ldw,
+                                                                const void *base, int base_dtype, int64_t ldbase, int64_t tokens, int64_t topk,
+                                                                void *y, int out_dtype, int64_t ldy, int split, void *workspace,
+                                                                size_t workspace_bytes, void *stream)
+{
+    return packed_skinny_grouped_combine(false, "mtq_packed_linear_skinny_grouped_chunked_combine", x, k, ldx, group_rows, packed, packed_bytes, maps,
+                                         offsets, bases, count, n, expert_dtype, row_of, weights, ldw, base, base_dtype, ldbase, tokens, topk, y,
+                                         out_dtype, ldy, split, workspace, workspace_bytes, stream, true);
+}
+
+extern "C" int mtq_packed_matmul_skinny_grouped_chunked_combine(const void *x, int64_t k, int64_t ldx, const int32_t *group_rows,
+                                                                const void *packed, size_t packed_bytes, const int8_t *maps,
+                                                                const uint32_t *offsets, const uint64_t *bases, int64_t count, int64_t n,
+                                                                int expert_dtype, const int32_t *row_of, const float *weights, int64_t ldw,
+                                                                const void *base, int base_dtype, int64_t ldbase, int64_t tokens, int64_t topk,
+                                                                void *y, int out_dtype, int64_t ldy, int split, void *workspace,
+                                                                size_t workspace_bytes, void *stream)
+{
+    return packed_skinny_grouped_combine(true, "mtq_packed_matmul_skinny_grouped_chunked_combine", x, k, ldx, group_rows, packed, packed_bytes, maps,
+                                         offsets, bases, count, n, expert_dtype, row_of, weights, ldw, base, base_dtype, ldbase, tokens, topk, y,
+                                         out_dtype, ldy, split, workspace, workspace_bytes, stream, true);
 }
 
 extern "C" int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream)

@@ -177,6 +177,23 @@ MOE_DECODE_SIGNATURES = {
     "mtq_packed_matmul_skinny_grouped_combine": ("i", "pllppzpppllipplpilllpilipzp", True),
 }
 MOE_DECODE_EXPORTS = tuple(MOE_DECODE_SIGNATURES)
+# include/mtq_glu_chunked.h, which mtq.h includes after it: the grouped skinny GLU, its gather form and the down projection with the
+# combine, each with a wave per 32-row chunk; the walking parent's letters, all optional, a table of its own for the same reason.
+GLU_CHUNKED_SIGNATURES = {
+    "mtq_packed_glu_skinny_grouped_chunked_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_glu_skinny_grouped_chunked": ("i", "plllppzppppzpppllpplipilipzp", True),
+    "mtq_packed_glu_matmul_skinny_grouped_chunked_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_glu_matmul_skinny_grouped_chunked": ("i", "plllppzppppzpppllpplipilipzp", True),
+    "mtq_packed_glu_skinny_grouped_chunked_gather_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_glu_skinny_grouped_chunked_gather": ("i", "pllllpppzppppzpppllpplipilipzp", True),
+    "mtq_packed_glu_matmul_skinny_grouped_chunked_gather_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_glu_matmul_skinny_grouped_chunked_gather": ("i", "pllllpppzppppzpppllpplipilipzp", True),
+    "mtq_packed_linear_skinny_grouped_chunked_combine_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_linear_skinny_grouped_chunked_combine": ("i", "pllppzpppllipplpilllpilipzp", True),
+    "mtq_packed_matmul_skinny_grouped_chunked_combine_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_matmul_skinny_grouped_chunked_combine": ("i", "pllppzpppllipplpilllpilipzp", True),
+}
+GLU_CHUNKED_EXPORTS = tuple(GLU_CHUNKED_SIGNATURES)
 _CTYPE = {"p": ctypes.c_void_p, "l": ctypes.c_int64, "u": ctypes.c_uint32, "i": ctypes.c_int, "d": ctypes.c_double, "z": ctypes.c_size_t,
           "q": ctypes.c_uint64, "v": None, "s": ctypes.c_char_p}
 
@@ -234,7 +251,7 @@ def _bind(L) -> None:
     found = version()
     if found < MTQ_VERSION:
         raise MtqError(f"{LIB_PATH} is version {found}, older than this package (it needs {MTQ_VERSION}): {_REBUILD}")
-    for name, (result, params, optional) in (*SIGNATURES.items(), *MOE_DECODE_SIGNATURES.items()):
+    for name, (result, params, optional) in (*SIGNATURES.items(), *MOE_DECODE_SIGNATURES.items(), *GLU_CHUNKED_SIGNATURES.items()):
         fn = getattr(L, name, None)
         if fn is None:
             if optional:
@@ -1773,6 +1790,38 @@ def packed_glu_matmul_skinny_grouped(x, group_rows, gate, up, count: int, n: int
                                     bias_gate, bias_up, out_dtype, out, split, workspace, stream)
 
 
+# ---- the grouped skinny GLU with a wave per 32-row chunk (include/mtq_glu_chunked.h): [kn] → (entry, size function)
+PACKED_GLU_SKINNY_GROUPED_CHUNKED = (
+    ("mtq_packed_glu_skinny_grouped_chunked", "mtq_packed_glu_skinny_grouped_chunked_workspace_bytes"),
+    ("mtq_packed_glu_matmul_skinny_grouped_chunked", "mtq_packed_glu_matmul_skinny_grouped_chunked_workspace_bytes"))
+
+
+def glu_grouped_chunked_bound(kn: bool = False) -> bool:
+    """Whether this build of the library has mtq_packed_glu_skinny_grouped_chunked and its size function, or with `kn` the matmul twin's
+    pair (optional symbols: an older build of the same version lacks them)."""
+    return _has(PACKED_GLU_SKINNY_GROUPED_CHUNKED[bool(kn)])
+
+
+def glu_grouped_chunked_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0, kn: bool = False) -> int:
+    """mtq_packed_glu_skinny_grouped_chunked_workspace_bytes (kn: its matmul twin; host functions: no GPU): the plan region,
+    (count + 1) * 4 bytes rounded up to 16, and behind it packed_glu_skinny_grouped_workspace_bytes' answer."""
+    return _workspace_size(PACKED_GLU_SKINNY_GROUPED_CHUNKED[bool(kn)][1], total_rows, count, n, k, split)
+
+
+def glu_grouped_chunked(x, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None, out=None,
+                        split: int = 0, workspace=None, kn: bool = False, stream="current"):
+    """mtq_packed_glu_skinny_grouped_chunked (kn: its matmul twin) on the current stream: packed_glu_skinny_grouped's
+    (packed_glu_matmul_skinny_grouped's) operands and, for a nondecreasing group_rows, its bits at the same split, with a wave per 32-row
+    chunk of a group (the chunks are planned on the device: nothing is read back), for routings with experts of many rows.  workspace: an
+    optional uint8 device tensor of glu_grouped_chunked_workspace_bytes bytes."""
+    name = PACKED_GLU_SKINNY_GROUPED_CHUNKED[bool(kn)][0]
+
+    def size(*args):
+        return glu_grouped_chunked_workspace_bytes(*args, kn=kn)
+
+    return _packed_glu_grouped_call(name, size, x, group_rows, gate, up, count, n, act, bias_gate, bias_up, out_dtype, out, split, workspace, stream)
+
+
 MOE = ("mtq_moe_plan_workspace_bytes", "mtq_moe_plan", "mtq_moe_dispatch", "mtq_moe_combine")
 MOE_MAX_TOPK, MOE_MAX_EXPERTS, MOE_RUN = 64, 4096, 1024   # include/mtq.h MTQ_MOE_MAX_TOPK, MTQ_MOE_MAX_EXPERTS, MTQ_MOE_RUN
 IDS_I32, IDS_I64 = 0, 1                                   # include/mtq.h MTQ_IDS_I32, MTQ_IDS_I64
@@ -1883,6 +1932,26 @@ MOE_GATHER = (("mtq_packed_glu_skinny_grouped_gather", "mtq_packed_glu_skinny_gr
               ("mtq_packed_glu_matmul_skinny_grouped_gather", "mtq_packed_glu_matmul_skinny_grouped_gather_workspace_bytes"))
 MOE_DOWN_COMBINE = (("mtq_packed_linear_skinny_grouped_combine", "mtq_packed_linear_skinny_grouped_combine_workspace_bytes"),
                     ("mtq_packed_matmul_skinny_grouped_combine", "mtq_packed_matmul_skinny_grouped_combine_workspace_bytes"))
+# their forms with a wave per 32-row chunk (include/mtq_glu_chunked.h), and kernel → the tables
+MOE_GATHER_CHUNKED = (("mtq_packed_glu_skinny_grouped_chunked_gather", "mtq_packed_glu_skinny_grouped_chunked_gather_workspace_bytes"),
+                      ("mtq_packed_glu_matmul_skinny_grouped_chunked_gather", "mtq_packed_glu_matmul_skinny_grouped_chunked_gather_workspace_bytes"))
+MOE_DOWN_COMBINE_CHUNKED = (
+    ("mtq_packed_linear_skinny_grouped_chunked_combine", "mtq_packed_linear_skinny_grouped_chunked_combine_workspace_bytes"),
+    ("mtq_packed_matmul_skinny_grouped_chunked_combine", "mtq_packed_matmul_skinny_grouped_chunked_combine_workspace_bytes"))
+MOE_DECODE_KERNELS = ("walk", "chunks")
+_MOE_GATHER_OF = {"walk": MOE_GATHER, "chunks": MOE_GATHER_CHUNKED}
+_MOE_DOWN_COMBINE_OF = {"walk": MOE_DOWN_COMBINE, "chunks": MOE_DOWN_COMBINE_CHUNKED}
+
+
+def _moe_decode_pair(table, kernel: str, kn: bool):
+    if kernel not in MOE_DECODE_KERNELS:
+        raise MtqError(f"kernel must be one of {MOE_DECODE_KERNELS}, got {kernel!r}")
+    return table[kernel][bool(kn)]
+
+
+def moe_decode_chunked_bound(kn: bool = False) -> bool:
+    """moe_decode_bound for the entries with a wave per 32-row chunk (optional symbols)."""
+    return _has(MOE_GATHER_CHUNKED[bool(kn)] + MOE_DOWN_COMBINE_CHUNKED[bool(kn)])
 
 
 def moe_decode_bound(kn: bool = False) -> bool:
@@ -1891,24 +1960,27 @@ def moe_decode_bound(kn: bool = False) -> bool:
     return _has(MOE_GATHER[bool(kn)] + MOE_DOWN_COMBINE[bool(kn)])
 
 
-def moe_glu_gather_workspace_bytes(slots: int, count: int, n: int, k: int, split: int = 0, kn: bool = False) -> int:
+def moe_glu_gather_workspace_bytes(slots: int, count: int, n: int, k: int, split: int = 0, kn: bool = False, kernel: str = "walk") -> int:
     """The *_gather_workspace_bytes size functions (host functions: no GPU): packed_glu_skinny_grouped_workspace_bytes' answer for
-    total_rows = slots = tokens * topk."""
-    return _workspace_size(MOE_GATHER[bool(kn)][1], slots, count, n, k, split)
+    total_rows = slots = tokens * topk; kernel "chunks": the chunked entry's, the plan region more."""
+    return _workspace_size(_moe_decode_pair(_MOE_GATHER_OF, kernel, kn)[1], slots, count, n, k, split)
 
 
-def moe_down_combine_workspace_bytes(slots: int, count: int, n: int, k: int, split: int = 0, kn: bool = False) -> int:
+def moe_down_combine_workspace_bytes(slots: int, count: int, n: int, k: int, split: int = 0, kn: bool = False, kernel: str = "walk") -> int:
     """The *_combine_workspace_bytes size functions (host functions: no GPU): max(effective split, 1) * slots * n * 4 bytes rounded up
-    to 16, the effective split packed_linear_skinny_grouped's for (slots, count, n, k, split).  Never 0."""
-    return _workspace_size(MOE_DOWN_COMBINE[bool(kn)][1], slots, count, n, k, split)
+    to 16, the effective split packed_linear_skinny_grouped's for (slots, count, n, k, split).  Never 0.  kernel "chunks": the chunked
+    entry's, the plan region more."""
+    return _workspace_size(_moe_decode_pair(_MOE_DOWN_COMBINE_OF, kernel, kn)[1], slots, count, n, k, split)
 
 
 def moe_glu_gather(x, src, topk: int, group_rows, gate, up, count: int, n: int, act="silu", bias_gate=None, bias_up=None, out_dtype=None,
-                   out=None, split: int = 0, workspace=None, kn: bool = False, stream="current"):
+                   out=None, split: int = 0, workspace=None, kn: bool = False, stream="current", kernel: str = "walk"):
     """mtq_packed_glu_skinny_grouped_gather (kn: its matmul twin) on the current stream: packed_glu_skinny_grouped on the rows
     moe_dispatch would have written, without writing them.  x: the (tokens, k) bf16 token matrix with contiguous rows; src: the plan's
     contiguous int32 device tensor of S = tokens * topk entries; group_rows, gate, up, the biases, split and workspace as
-    packed_glu_skinny_grouped takes them → (S, n); an `out` allocated here starts as zeros, so rows of no group are zeros."""
+    packed_glu_skinny_grouped takes them → (S, n); an `out` allocated here starts as zeros, so rows of no group are zeros.
+    kernel (MOE_DECODE_KERNELS): "chunks", mtq_packed_glu_skinny_grouped_chunked_gather - the same bits from a wave per 32-row chunk."""
+    name, size = _moe_decode_pair(_MOE_GATHER_OF, kernel, kn)
     torch = _torch()
     out_dtype = out_dtype or torch.float32
     code, a = _packed_out_code(out_dtype), _act_code(act)
@@ -1942,7 +2014,6 @@ def moe_glu_gather(x, src, topk: int, group_rows, gate, up, count: int, n: int, 
             raise MtqError("bias_gate and bias_up must have one row pitch")
         ptrs.append(bias.data_ptr())
         ldb = pitch
-    name, size = MOE_GATHER[bool(kn)]
     fn = _entry(name)
     need = _workspace_size(size, S, count, n, k, split)
     out, ldy = _packed_out(out, S, n, out_dtype, x.device, zeros=True)
@@ -1953,11 +2024,13 @@ def moe_glu_gather(x, src, topk: int, group_rows, gate, up, count: int, n: int, 
 
 
 def moe_down_combine(h, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, row_of, weights, base=None, expert_dtype=None,
-                     out_dtype=None, out=None, split: int = 0, workspace=None, kn: bool = False, stream="current"):
+                     out_dtype=None, out=None, split: int = 0, workspace=None, kn: bool = False, stream="current", kernel: str = "walk"):
     """mtq_packed_linear_skinny_grouped_combine (kn: its matmul twin) on the current stream: packed_linear_skinny_grouped without bias
     into expert_dtype and moe_combine of its rows, without those rows being written.  h: (S, k) bf16 with contiguous rows,
     S = tokens * topk; group_rows and the arena's tables as packed_linear_skinny_grouped takes them; row_of, weights (tokens, topk)
-    float32 and base as moe_combine takes them → (tokens, n) float32 or bfloat16."""
+    float32 and base as moe_combine takes them → (tokens, n) float32 or bfloat16.
+    kernel (MOE_DECODE_KERNELS): "chunks", mtq_packed_linear_skinny_grouped_chunked_combine - the same bits from a wave per 32-row chunk."""
+    name, size = _moe_decode_pair(_MOE_DOWN_COMBINE_OF, kernel, kn)
     torch = _torch()
     out_dtype, expert_dtype = out_dtype or torch.float32, expert_dtype or torch.float32
     code, expert_code = _packed_out_code(out_dtype), _packed_out_code(expert_dtype)
@@ -1988,7 +2061,6 @@ def moe_down_combine(h, group_rows, arena, maps_dev, offsets_dev, bases_dev, cou
         if (brows, bcols) != (T, n):
             raise MtqError(f"base must be ({T}, {n}), got {tuple(base.shape)}")
         base_ptr = base.data_ptr()
-    name, size = MOE_DOWN_COMBINE[bool(kn)]
     fn = _entry(name)
     need = _workspace_size(size, S, count, n, k, split)
     out, ldy = _packed_out(out, T, n, out_dtype, h.device)

@@ -35,6 +35,9 @@ the host.  On that staged route the gather and the combine are kernels of their 
 moe_glu / moe_down_combine are the decode route without them (include/mtq_moe_decode.h): the gather inside the grouped skinny GLU
 wave's X loads, the combine inside the down projection's reduce, the staged route's bits from five launches for seven and without the
 (S, k) and (S, k_out) intermediates; PackedMoE(decode_route="fused") runs plan → moe_glu → moe_down_combine up to decode_max_rows slots.
+kernel="chunks" on glu_grouped_skinny, glu_matmul_grouped_skinny, moe_glu and moe_down_combine, and decode_grouped_kernel="chunks" on the
+expert MLPs and PackedMoE (include/mtq_glu_chunked.h), give every 32-row chunk of an expert a wave of its own, for routings with hot
+experts: the walking kernels' bits, planned on the device.
 
 moe_route / MoERouting / MOE_ROUTINGS are the router in front of that (csrc/mtq_moe_route.hip): from the router GEMM's logits to
 (topk_weights, topk_ids) in one launch - softmax or sigmoid scores, a selection-only bias, group-limited top-k, renormalised and scaled
@@ -1360,16 +1363,37 @@ def glu_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gat
                         workspace)
 
 
+GLU_SKINNY_GROUPED_KERNELS = ("walk", "chunks", "auto")   # glu_grouped_skinny, glu_matmul_grouped_skinny, moe_glu, moe_down_combine, the modules
+# What "auto" means.  The kernels give the same bits, so this decides time alone, by the rule of DESIGN.md §A.6m: "walk", because in
+# profiles/packed_glu_skinny_chunked.txt the chunked GLU's median with one row in every expert (64 and 256 experts, both orientations) is
+# 1.014–1.021 of the walking entry's minimum, above the run's own spread of 1.013; on the skew rows it is 0.35–0.65.
+GLU_SKINNY_GROUPED_AUTO_KERNEL = "walk"
+
+
+def _glu_skinny_grouped_kernel(kernel: str) -> str:
+    """`kernel` of the grouped skinny GLU and the MoE decode stages, "auto" resolved."""
+    _check_kernel(kernel, GLU_SKINNY_GROUPED_KERNELS)
+    return GLU_SKINNY_GROUPED_AUTO_KERNEL if kernel == "auto" else kernel
+
+
+def _need_glu_grouped_skinny_chunked(o: _Orientation, hb, what: str) -> None:
+    if not hb.glu_grouped_chunked_bound(o.kn):
+        raise MtqError(f"{what} needs {' and '.join(hb.PACKED_GLU_SKINNY_GROUPED_CHUNKED[o.kn])}, {_LACKS}")
+
+
 def glu_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
-                       backend: Optional[str] = None, split: int = 0, workspace=None):
+                       backend: Optional[str] = None, split: int = 0, workspace=None, kernel: str = "walk"):
     """glu_grouped for decode-sized groups from the fused split-K kernel: mtq_packed_glu_skinny_grouped, two launches over both arenas.
     The arguments are resolved as glu_grouped resolves them.  Per group the bits of two linear_grouped(kernel="walk") calls into float32
     at that `split` and hip_backend.glu_combine: the skinny family's sums, which may differ from glu_grouped's in the last bits.  Rows
     of no group are zeros.  workspace: an optional uint8 device tensor of hip_backend.packed_glu_skinny_grouped_workspace_bytes bytes.
     T = 0 gives (0, n) without a call; a library without the entry raises MtqError: there is no fall-back.
-    emulation: glu_grouped's value."""
+    kernel (GLU_SKINNY_GROUPED_KERNELS): "walk", one wave per (slice, projection, expert, tile row) that walks the expert's 32-row chunks;
+    "chunks", mtq_packed_glu_skinny_grouped_chunked, a wave per 32-row chunk from a plan made on the device, for routings with experts of
+    many rows - the same bits for a nondecreasing group_rows, its workspace hip_backend.glu_grouped_chunked_workspace_bytes bytes; "auto", GLU_SKINNY_GROUPED_AUTO_KERNEL.  A library without the kernel asked for raises MtqError, it never runs the other.
+    emulation: glu_grouped's value, under every kernel name."""
     return _glu_grouped(_NK, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, "skinny", ("skinny",), split,
-                        workspace)
+                        workspace, kernel)
 
 
 def _glu(o: _Orientation, what: str, x, gate: PackedTensor, up: PackedTensor, act, bias_gate, bias_up, out_dtype, backend, kernel):
@@ -1442,12 +1466,14 @@ def _glu_skinny(o: _Orientation, what: str, x, gate: PackedTensor, up: PackedTen
     return globals()[o.glu](x, gate, up, act=act, bias_gate=bias_gate, bias_up=bias_up, out_dtype=out_dtype, backend=backend)
 
 
-def _glu_grouped(o: _Orientation, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, kernels, split, workspace):
+def _glu_grouped(o: _Orientation, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, kernels, split, workspace,
+                 skinny_kernel: str = "walk"):
     """The grouped gated products: `kernel` one of `kernels`, GLU_GROUPED_KERNELS or, from the *_grouped_skinny functions alone,
-    ("skinny",)."""
+    ("skinny",), whose frame is skinny_kernel (GLU_SKINNY_GROUPED_KERNELS)."""
     gate_b, up_b = _resolve_batch(gate_batch), _resolve_batch(up_batch)
     _check_act(act)
     _check_kernel(kernel, kernels)
+    skinny_kernel = _glu_skinny_grouped_kernel(skinny_kernel)
     _check_out_dtype(out_dtype)
     if (gate_b.count, gate_b.rows, gate_b.cols) != (up_b.count, up_b.rows, up_b.cols):
         raise MtqError(f"the gate and the up batch must hold as many experts of one shape, got {gate_b.count} of {gate_b.rows}x{gate_b.cols} and "
@@ -1460,7 +1486,9 @@ def _glu_grouped(o: _Orientation, x, group_rows, gate_batch, up_batch, act, bias
     T = int(x.shape[0])
     group_rows, on_device = _resolve_group_rows(group_rows, count, T)
     if backend == "hip":
-        if kernel == "skinny":                       # a missing kernel is refused before any device work
+        if kernel == "skinny" and skinny_kernel == "chunks":     # a missing kernel is refused before any device work, never replaced
+            _need_glu_grouped_skinny_chunked(o, hb, f'{o.glu_grouped_skinny}(kernel="chunks")')
+        elif kernel == "skinny":
             _needs(o.need_glu_skinny, hb, o.glu_grouped_skinny)
         else:
             _needs(o.need_glu_grouped, hb, o.glu_grouped)
@@ -1474,8 +1502,10 @@ def _glu_grouped(o: _Orientation, x, group_rows, gate_batch, up_batch, act, bias
         group_rows = _device_group_rows(group_rows, on_device, dev)
         bias_gate, bias_up = _device_bias(bias_gate, dev), _device_bias(bias_up, dev)
         if kernel == "skinny":
-            return getattr(hb, o.hb_glu_grouped_skinny)(x, group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, act=act, bias_gate=bias_gate,
-                                                        bias_up=bias_up, out_dtype=dtype, split=split, workspace=workspace)
+            more = {"kn": o.kn} if skinny_kernel == "chunks" else {}         # one binding for both orientations
+            launch = hb.glu_grouped_chunked if skinny_kernel == "chunks" else getattr(hb, o.hb_glu_grouped_skinny)
+            return launch(x, group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, act=act, bias_gate=bias_gate, bias_up=bias_up,
+                          out_dtype=dtype, split=split, workspace=workspace, **more)
         if kernel == "fused":
             return getattr(hb, o.hb_glu_grouped_fused)(x, group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, act=act, bias_gate=bias_gate,
                                                        bias_up=bias_up, out_dtype=dtype, workspace=workspace)
@@ -1562,15 +1592,16 @@ def glu_matmul_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", b
 
 
 def glu_matmul_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
-                              backend: Optional[str] = None, split: int = 0, workspace=None):
+                              backend: Optional[str] = None, split: int = 0, workspace=None, kernel: str = "walk"):
     """glu_matmul_grouped for decode-sized groups from the fused split-K kernel: mtq_packed_glu_matmul_skinny_grouped, two launches over
     both arenas.  Per group the bits of two matmul_grouped(kernel="walk") calls into float32 at that `split` and
     hip_backend.glu_combine: the skinny family's sums, which may differ from glu_matmul_grouped's in the last bits.  Rows of no group are
     zeros.  workspace: an optional uint8 device tensor of hip_backend.packed_glu_matmul_skinny_grouped_workspace_bytes bytes.  T = 0
     gives (0, n) without a call; a library without the entry raises MtqError: there is no fall-back.
-    emulation: glu_matmul_grouped's value."""
+    kernel (GLU_SKINNY_GROUPED_KERNELS): as glu_grouped_skinny's; "chunks" is mtq_packed_glu_matmul_skinny_grouped_chunked.
+    emulation: glu_matmul_grouped's value, under every kernel name."""
     return _glu_grouped(_KN, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, "skinny", ("skinny",), split,
-                        workspace)
+                        workspace, kernel)
 
 
 # ----------------------------------------------------------------------------- MoE routing: plan, dispatch, combine
@@ -1744,7 +1775,13 @@ def _moe_orientation(stored) -> _Orientation:
     return _KN if stored == "transpose" else _NK
 
 
-def _need_moe_decode(hb, what: str, kn: bool) -> None:
+def _need_moe_decode(hb, what: str, kn: bool, kernel: str = "walk") -> None:
+    """The decode stages' symbols for a resolved kernel; "chunks" asks for its own and never for the walking ones."""
+    if kernel == "chunks":
+        if not hb.moe_decode_chunked_bound(kn):
+            names = hb.MOE_GATHER_CHUNKED[kn] + hb.MOE_DOWN_COMBINE_CHUNKED[kn]
+            raise MtqError(f"{what} needs {' and '.join(names)}, {_LACKS}")
+        return
     if not hb.moe_decode_bound(kn):
         names = hb.MOE_GATHER[kn] + hb.MOE_DOWN_COMBINE[kn]
         raise MtqError(f"{what} needs {' and '.join(names)}, which this build of libmtq_hip.so lacks: rebuild it from this tree")
@@ -1759,7 +1796,7 @@ def _moe_stage_backend(plan: MoEPlan, backend) -> str:
 
 
 def moe_glu(x, plan: MoEPlan, gate_batch, up_batch, act: str = "silu", out_dtype: str = "bfloat16", stored: str = "rows", split: int = 0,
-            workspace=None, backend: Optional[str] = None):
+            workspace=None, backend: Optional[str] = None, kernel: str = "walk"):
     """From the token matrix to the experts' gated rows in one step: x (tokens, k) bf16 → h (S, n) in expert order,
     h[r] = act(x[t]·Ŵg[e]ᵀ) * (x[t]·Ŵu[e]ᵀ) for the slot s = plan.src[r] of token t = s // topk and the expert e that owns row r; rows from
     R = group_rows[count] on are zeros.  stored (MOE_STORED): "rows", the batches hold (n, k) experts; "transpose", (k, n) experts.
@@ -1767,8 +1804,12 @@ def moe_glu(x, plan: MoEPlan, gate_batch, up_batch, act: str = "silu", out_dtype
     token's own row, so the dispatched (S, k) copy is never written.  Bit for bit moe_dispatch then glu_grouped_skinny
     (glu_matmul_grouped_skinny) at the same `split`.  workspace: an optional uint8 device tensor of
     hip_backend.moe_glu_gather_workspace_bytes bytes.  For decode-sized S: a group above 32 rows is walked in chunks by one wave.
-    emulation: moe_dispatch and the emulated glu_grouped_skinny on the first R rows, composed."""
+    kernel (GLU_SKINNY_GROUPED_KERNELS): "chunks", mtq_packed_glu_skinny_grouped_chunked_gather (its matmul twin), a wave per 32-row
+    chunk and the same bits, for routings with hot experts (the workspace: that size function with kernel="chunks"); "auto",
+    GLU_SKINNY_GROUPED_AUTO_KERNEL.  A library without the kernel asked for raises MtqError, it never runs the other.
+    emulation: moe_dispatch and the emulated glu_grouped_skinny on the first R rows, composed, under every kernel name."""
     o = _moe_orientation(stored)
+    kernel = _glu_skinny_grouped_kernel(kernel)
     gate_b, up_b = _resolve_batch(gate_batch), _resolve_batch(up_batch)
     _check_act(act)
     _check_out_dtype(out_dtype)
@@ -1783,10 +1824,10 @@ def moe_glu(x, plan: MoEPlan, gate_batch, up_batch, act: str = "silu", out_dtype
         raise MtqError(f"x must be ({T}, {k}), got {tuple(x.shape)}")
     backend = _moe_stage_backend(plan, backend)
     if backend == "hip":
-        _need_moe_decode(hb, "moe_glu", o.kn)        # a missing kernel is refused before any device work
+        _need_moe_decode(hb, "moe_glu", o.kn, kernel)            # a missing kernel is refused before any device work
         gate_b, up_b = batch_to_device(gate_b), batch_to_device(up_b)
         return hb.moe_glu_gather(x, plan.src, K, plan.group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, act=act,
-                                 out_dtype=_torch_dtype(out_dtype), split=split, workspace=workspace, kn=o.kn)
+                                 out_dtype=_torch_dtype(out_dtype), split=split, workspace=workspace, kn=o.kn, kernel=kernel)
     import torch
 
     xs = _as_torch(moe_dispatch(x, plan))
@@ -1798,7 +1839,7 @@ def moe_glu(x, plan: MoEPlan, gate_batch, up_batch, act: str = "silu", out_dtype
 
 
 def moe_down_combine(h, topk_weights, plan: MoEPlan, down_batch, base=None, expert_dtype: str = "float32", out_dtype: str = "float32",
-                     stored: str = "rows", split: int = 0, workspace=None, out=None, backend: Optional[str] = None):
+                     stored: str = "rows", split: int = 0, workspace=None, out=None, backend: Optional[str] = None, kernel: str = "walk"):
     """From the experts' gated rows to the layer's output in one step: h (S, n) bf16 in expert order (moe_glu's result), topk_weights
     (tokens, topk) float32, base None or (tokens, k_out) → y (tokens, k_out) in out_dtype: the down projection of every row by its
     expert, rounded as a matrix of expert_dtype would hold it, then moe_combine's weighted sum in its order.
@@ -1806,8 +1847,11 @@ def moe_down_combine(h, topk_weights, plan: MoEPlan, down_batch, base=None, expe
     and one reduce kernel sums the slices, rounds, weighs and adds, so the experts' (S, k_out) rows are never written.  Bit for bit
     linear_grouped(kernel="walk") (matmul_grouped) into expert_dtype at the same `split`, then moe_combine.  workspace: an optional
     uint8 device tensor of hip_backend.moe_down_combine_workspace_bytes bytes; out: an optional (tokens, k_out) device tensor.
-    emulation: the emulated grouped product on the first R rows and the emulated moe_combine, composed."""
+    kernel (GLU_SKINNY_GROUPED_KERNELS): "chunks", mtq_packed_linear_skinny_grouped_chunked_combine (its matmul twin): the plan,
+    linear_grouped(kernel="chunks")'s wave and the same reduce, the same bits; "auto", GLU_SKINNY_GROUPED_AUTO_KERNEL.
+    emulation: the emulated grouped product on the first R rows and the emulated moe_combine, composed, under every kernel name."""
     o = _moe_orientation(stored)
+    kernel = _glu_skinny_grouped_kernel(kernel)
     down = _resolve_batch(down_batch)
     _check_out_dtype(out_dtype)
     _check_out_dtype(expert_dtype, "expert_dtype")
@@ -1827,13 +1871,13 @@ def moe_down_combine(h, topk_weights, plan: MoEPlan, down_batch, base=None, expe
     if backend == "hip":
         import torch
 
-        _need_moe_decode(hb, "moe_down_combine", o.kn)
+        _need_moe_decode(hb, "moe_down_combine", o.kn, kernel)
         down = batch_to_device(down)
         if not _is_torch(topk_weights):
             topk_weights = torch.from_numpy(np.ascontiguousarray(topk_weights)).to(plan.row_of.device)
         return hb.moe_down_combine(h, plan.group_rows, *_arena_args(down), count, n, plan.row_of, topk_weights, base=base,
                                    expert_dtype=_torch_dtype(expert_dtype), out_dtype=_torch_dtype(out_dtype), out=out, split=split,
-                                   workspace=workspace, kn=o.kn)
+                                   workspace=workspace, kn=o.kn, kernel=kernel)
     import torch
 
     R = int(plan.group_rows[-1])
@@ -2042,7 +2086,11 @@ _CLASS_DOCS = {
         the arenas, their tables and the one plan workspace both launches use stay on the device.  T = 0 gives the empty result.
         decode_max_rows: None, that route at every T; a positive number, a forward with T <= decode_max_rows goes through
         glu_grouped_skinny into bf16 and linear_grouped(kernel="walk") with the down batch instead (the skinny family's sums, which may
-        differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows.""",
+        differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows.
+        decode_grouped_kernel (GLU_SKINNY_GROUPED_KERNELS; not decode_kernel, which is PackedMLP's pair or fused): the kernel of both
+        halves of that route.  "walk", the two above; "chunks", glu_grouped_skinny(kernel="chunks") and linear_grouped(kernel="chunks"),
+        a wave per 32-row chunk and the same bits, for routings with experts of many rows; "auto", GLU_SKINNY_GROUPED_AUTO_KERNEL.  The
+        kept workspace is sized with the chosen kernels' size functions; a name other than "walk" needs decode_max_rows.""",
     "PackedExpertsMatmulMLP":
         """PackedExpertsMLP over three batches of `count` (k, n) experts, as matmul_grouped takes them: gate and up (k, hidden), down
         (hidden, k_out) - pack_batch_transposed lists, or as_batch of a pack_model --store-transposed directory's entries.  INFERENCE
@@ -2051,7 +2099,8 @@ _CLASS_DOCS = {
         workspace both launches use stay on the device.  T = 0 gives the empty result.
         decode_max_rows: None, that route at every T; a positive number, a forward with T <= decode_max_rows goes through
         glu_matmul_grouped_skinny into bf16 and matmul_grouped(kernel="walk") with the down batch instead (the skinny family's sums,
-        which may differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows.""",
+        which may differ from the wide route's in the last bits), with one workspace sized here for decode_max_rows rows.
+        decode_grouped_kernel: PackedExpertsMLP's, for glu_matmul_grouped_skinny and matmul_grouped.""",
     "PackedLinear":
         """A linear layer over a packed (n, k) weight.  INFERENCE ONLY: the kernels have no backward, no gradient reaches x, the weight
         or the bias.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through linear() with
@@ -2156,17 +2205,27 @@ def _mlp_class(o: _Orientation, name: str):
     return _named(MLP, name)
 
 
+def _decode_grouped_kernel(decode_grouped_kernel, decode_max_rows) -> str:
+    """decode_grouped_kernel of the expert MLPs and PackedMoE, checked and resolved: one kernel for both halves of the decode route."""
+    if decode_grouped_kernel not in GLU_SKINNY_GROUPED_KERNELS:
+        raise MtqError(f"decode_grouped_kernel must be one of {GLU_SKINNY_GROUPED_KERNELS}, got {decode_grouped_kernel!r}")
+    if decode_grouped_kernel != "walk" and decode_max_rows is None:
+        raise MtqError(f"decode_grouped_kernel={decode_grouped_kernel!r} needs decode_max_rows: it chooses the kernels of the decode route")
+    return _glu_skinny_grouped_kernel(decode_grouped_kernel)
+
+
 def _experts_mlp_class(o: _Orientation, name: str):
     """PackedExpertsMLP and PackedExpertsMatmulMLP."""
     import torch
 
     class ExpertsMLP(torch.nn.Module):
         def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", backend: Optional[str] = None,
-                     decode_max_rows: Optional[int] = None):
+                     decode_max_rows: Optional[int] = None, decode_grouped_kernel: str = "walk"):
             super().__init__()
             _check_act(act)
             if decode_max_rows is not None and (isinstance(decode_max_rows, bool) or not isinstance(decode_max_rows, int) or decode_max_rows <= 0):
                 raise MtqError(f"decode_max_rows must be None or a positive int, got {decode_max_rows!r}")
+            decode_kernel = _decode_grouped_kernel(decode_grouped_kernel, decode_max_rows)
             _check_out_dtype(out_dtype)
             gate, up, down = (_resolve_batch(b) for b in (gate_pts, up_pts, down_pts))
             if (gate.count, gate.rows, gate.cols) != (up.count, up.rows, up.cols):
@@ -2182,7 +2241,10 @@ def _experts_mlp_class(o: _Orientation, name: str):
                 _needs(o.need_glu_grouped, hb, name)             # refused here, not at the first forward
                 if not o.experts_mlp_wide_last:
                     _grouped_entry(o, hb, "wide")
-                if decode_max_rows is not None:
+                if decode_max_rows is not None and decode_kernel == "chunks":     # its own symbols, never the walking ones in their place
+                    _need_glu_grouped_skinny_chunked(o, hb, f'{name}(decode_grouped_kernel="chunks")')
+                    _grouped_entry(o, hb, "chunks")
+                elif decode_max_rows is not None:
                     _needs(o.need_glu_skinny, hb, f"{name}(decode_max_rows=...)")
                     _grouped_entry(o, hb, "walk")
                 if o.experts_mlp_wide_last and not getattr(hb, o.hb_grouped["wide"][2])():
@@ -2191,10 +2253,12 @@ def _experts_mlp_class(o: _Orientation, name: str):
                 need = getattr(hb, o.hb_glu_grouped_fused_size)(1, gate.count, n, k)   # a function of count alone
                 self._workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
                 if decode_max_rows is not None:      # one buffer for both decode launches: each is done with it before the next starts
-                    need = max(getattr(hb, o.hb_glu_grouped_skinny_size)(decode_max_rows, gate.count, n, k),
-                               getattr(hb, o.hb_grouped["walk"][1])(decode_max_rows, down.count, n_down, k_down))
+                    glu_need = hb.glu_grouped_chunked_workspace_bytes(decode_max_rows, gate.count, n, k, kn=o.kn) if decode_kernel == "chunks" else \
+                        getattr(hb, o.hb_glu_grouped_skinny_size)(decode_max_rows, gate.count, n, k)
+                    need = max(glu_need,
+                               getattr(hb, o.hb_grouped[decode_kernel][1])(decode_max_rows, down.count, n_down, k_down))
                     self._decode_workspace = torch.empty((need,), dtype=torch.uint8, device=gate.arena.device)
-            self.decode_max_rows = decode_max_rows
+            self.decode_max_rows, self.decode_grouped_kernel, self._decode_kernel = decode_max_rows, decode_grouped_kernel, decode_kernel
             self.gate, self.up, self.down, self.act, self.out_dtype = gate, up, down, act, out_dtype
             self.count, self.in_features, self.hidden_features, self.out_features = gate.count, k, n, n_down
 
@@ -2208,9 +2272,9 @@ def _experts_mlp_class(o: _Orientation, name: str):
                 raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
             if self.decode_max_rows is not None and x.shape[0] <= self.decode_max_rows:
                 h = globals()[o.glu_grouped_skinny](x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend,
-                                                    workspace=self._decode_workspace)
+                                                    workspace=self._decode_workspace, kernel=self._decode_kernel)
                 return _as_torch(globals()[o.grouped](h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend,
-                                                      workspace=self._decode_workspace, kernel="walk"))
+                                                      workspace=self._decode_workspace, kernel=self._decode_kernel))
             h = globals()[o.glu_grouped](x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="fused",
                                          workspace=self._workspace)
             return _as_torch(globals()[o.grouped_wide](h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend,
@@ -2245,19 +2309,25 @@ def _packed_moe_class():
         S <= decode_max_rows runs plan → moe_glu → moe_down_combine instead: the gather inside the gated product's X loads and the
         combine inside the down projection's reduce, five launches for seven and no (S, k) or (S, k_out) intermediate, bit for bit the
         staged decode route's result; a larger call takes the staged route.  One workspace sized here serves both launches.
+        decode_grouped_kernel (GLU_SKINNY_GROUPED_KERNELS): PackedExpertsMLP's, handed to the experts for the staged decode route and
+        to moe_glu / moe_down_combine on the fused one, whose workspace is sized for it; "chunks" gives every 32-row chunk of an
+        expert a wave of its own, the same bits, for routings with hot experts.  A name other than "walk" needs decode_max_rows, and
+        a library without its symbols is refused here.
         hip: no device-to-host copy and no .item() in a forward; the plan workspace is allocated here for max_tokens tokens and
         regrown when a call needs more.  emulation: CPU tensors, for use without a GPU."""
 
         def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", expert_dtype: str = "float32",
                      backend: Optional[str] = None, decode_max_rows: Optional[int] = None, max_tokens: int = 4096, stored: str = "rows",
-                     router=None, decode_route: str = "staged"):
+                     router=None, decode_route: str = "staged", decode_grouped_kernel: str = "walk"):
             super().__init__()
             if decode_route not in MOE_DECODE_ROUTES:
                 raise MtqError(f"decode_route must be one of {MOE_DECODE_ROUTES}, got {decode_route!r}")
             if decode_route == "fused" and decode_max_rows is None:
                 raise MtqError('decode_route="fused" needs decode_max_rows: the fused route is the decode route, for calls of at most that many slots')
+            decode_kernel = _decode_grouped_kernel(decode_grouped_kernel, decode_max_rows)
+            fused_what = 'PackedMoE(decode_route="fused")' if decode_kernel == "walk" else 'PackedMoE(decode_route="fused", decode_grouped_kernel="chunks")'
             if decode_route == "fused" and backend == "hip" and stored in MOE_STORED:      # before any device work; asked again for a default backend
-                _need_moe_decode(hb, 'PackedMoE(decode_route="fused")', stored == "transpose")
+                _need_moe_decode(hb, fused_what, stored == "transpose", decode_kernel)
             if isinstance(router, str):
                 if router not in MOE_ROUTINGS:
                     raise MtqError(f"router must be a MoERouting or one of {tuple(MOE_ROUTINGS)}, got {router!r}")
@@ -2273,7 +2343,8 @@ def _packed_moe_class():
             experts_name = "PackedExpertsMLP" if stored == "rows" else "PackedExpertsMatmulMLP"
             experts_mlp = globals().get(experts_name) or __getattr__(experts_name)
             self.experts = experts_mlp(gate_pts, up_pts, down_pts, act=act, out_dtype=expert_dtype, backend=backend,
-                                       decode_max_rows=decode_max_rows)
+                                       decode_max_rows=decode_max_rows, decode_grouped_kernel=decode_grouped_kernel)
+            self.decode_grouped_kernel, self._decode_kernel = decode_grouped_kernel, decode_kernel
             self.backend, self.out_dtype, self.expert_dtype, self.stored = self.experts.backend, out_dtype, expert_dtype, stored
             self.count, self.in_features, self.out_features = self.experts.count, self.experts.in_features, self.experts.out_features
             if self.count > MOE_MAX_EXPERTS:
@@ -2289,10 +2360,12 @@ def _packed_moe_class():
                     _need_moe_route(hb, "PackedMoE(router=...)")
                 if decode_route == "fused":          # one buffer for both launches: each is done with it before the next starts
                     kn = stored == "transpose"
-                    _need_moe_decode(hb, 'PackedMoE(decode_route="fused")', kn)
+                    _need_moe_decode(hb, fused_what, kn, decode_kernel)
                     ex = self.experts
-                    need = max(hb.moe_glu_gather_workspace_bytes(decode_max_rows, ex.count, ex.hidden_features, ex.in_features, kn=kn),
-                               hb.moe_down_combine_workspace_bytes(decode_max_rows, ex.count, ex.out_features, ex.hidden_features, kn=kn))
+                    need = max(hb.moe_glu_gather_workspace_bytes(decode_max_rows, ex.count, ex.hidden_features, ex.in_features, kn=kn,
+                                                                 kernel=decode_kernel),
+                               hb.moe_down_combine_workspace_bytes(decode_max_rows, ex.count, ex.out_features, ex.hidden_features, kn=kn,
+                                                                   kernel=decode_kernel))
                     self._fused_workspace = torch.empty((need,), dtype=torch.uint8, device=ex.gate.arena.device)
                 need = hb.moe_plan_workspace_bytes(max_tokens, MOE_PLAN_TOPK, self.count)
                 self._plan_workspace = torch.empty((need,), dtype=torch.uint8, device=self.experts.gate.arena.device)
@@ -2324,10 +2397,10 @@ def _packed_moe_class():
             if self.decode_route == "fused" and plan.slots <= self.experts.decode_max_rows:
                 ex = self.experts
                 h = moe_glu(x2, plan, ex.gate, ex.up, act=ex.act, out_dtype="bfloat16", stored=self.stored, workspace=self._fused_workspace,
-                            backend=self.backend)
+                            backend=self.backend, kernel=self._decode_kernel)
                 y = moe_down_combine(h, topk_weights.reshape(T, K), plan, ex.down, base=None if base is None else base.reshape(T, self.out_features),
                                      expert_dtype=self.expert_dtype, out_dtype=self.out_dtype, stored=self.stored,
-                                     workspace=self._fused_workspace, backend=self.backend)
+                                     workspace=self._fused_workspace, backend=self.backend, kernel=self._decode_kernel)
                 return _as_torch(y).reshape(lead + (self.out_features,))
             xs = moe_dispatch(x2, plan)
             if self.backend == "hip":
