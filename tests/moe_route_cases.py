@@ -36,7 +36,16 @@ UNGROUPED = ((1, 1, 5), (2, 1, 3), (8, 2, 67), (8, 8, 1), (60, 5, 67), (64, 6, 6
              (257, 8, 67), (384, 8, 67), (4096, 64, 3))
 # (count, topk, n_group, topk_group, group_top, tokens)
 GROUPED = ((256, 8, 8, 4, 2, 67), (160, 6, 8, 3, 1, 67), (320, 8, 64, 8, 2, 67), (64, 4, 64, 4, 1, 67), (32, 8, 4, 2, 2, 67),
-           (256, 8, 8, 8, 2, 67))
+           (256, 8, 8, 8, 2, 67),
+           # n_group no power of two: kept_groups gives group g the lanes g << per_log2 of P = the power of two at or above n_group, so
+           # the lanes of groups n_group .. P - 1 are idle and must stay out of the ballot and the butterfly
+           (96, 4, 3, 2, 2, 67),                          # two experts a lane; 16 idle lanes
+           (60, 6, 6, 3, 1, 67),                          # one expert a lane; groups of 10; 16 idle lanes
+           (240, 8, 12, 5, 2, 67),                        # four experts a lane
+           (384, 8, 24, 6, 2, 67),                        # the LDS kernel; two lanes a group
+           (120, 6, 5, 2, 2, 67),                         # groups of 24; 24 idle lanes
+           (330, 8, 33, 8, 1, 5),                         # the LDS kernel; a lane a group; 31 idle lanes
+           (192, 8, 48, 12, 1, 67))
 # (score, with a bias, renormalize, eps, scale): both scores with and without a bias, both renormalize, both eps, both scales
 VARIANTS = (("softmax", False, True, 0.0, 1.0), ("softmax", True, False, 0.0, 2.5), ("sigmoid", False, False, 1e-20, 1.0),
             ("sigmoid", True, True, 1e-20, 2.5), ("softmax", True, True, 1e-20, 2.5), ("sigmoid", False, True, 0.0, 1.0))

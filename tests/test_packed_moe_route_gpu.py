@@ -13,14 +13,18 @@ Where a case is there for a kernel or a trip of the token loop, the test derives
             kernel's first, (384, 8), (4096, 64): both limits; grouped (256, 8, 8 groups, 4 kept, top 2): the flagship,
             (160, 6, 8, 3, top 1), (320, 8, 64, 8, top 2): the LDS kernel with a lane a group, (64, 4, 64, 4, top 1): groups of one
             expert, (32, 8, 4, 2, top 2): topk = every expert of the kept groups, (256, 8, 8, 8, top 2): every group kept, which equals
-            the ungrouped result; 1, 3, 5 or 67 tokens, so that a workgroup's last wave is ragged.  Each with one variant of
+            the ungrouped result; n_group no power of two, where the lanes of groups n_group .. P - 1 (P the power of two at or above
+            n_group) are idle and must stay out of kept_groups' ballot and butterfly: (96, 4, 3 groups, 2 kept), (60, 6, 6, 3),
+            (240, 8, 12, 5), (384, 8, 24, 6) and (330, 8, 33, 8) on the LDS kernel, (120, 6, 5, 2), (192, 8, 48, 12); 1, 3, 5 or 67
+            tokens, so that a workgroup's last wave is ragged.  Each with one variant of
             score / bias / renormalize / eps / scale; the flagship, (128, 8) and (384, 8) with every variant and a negative bias.
   grid      8195 tokens of 8 experts and 2051 tokens of 257: one token past 2048 workgroups' first pass and more.
   bf16      any values at 8, 256 (flat and grouped) and 384 experts: the words of the run on the same values widened to float32.
   views     logits a view of a wider buffer, and starting at an unaligned element; ids, weights and scores pitched views of sentinel
             buffers with sentinel rows behind them.
   special   all logits equal; pairs of equal logits straddling rank K; sigmoid saturation; experts masked at -Inf, fewer and more
-            than count - K of them; tokens holding NaN, +Inf and all -Inf among clean tokens.
+            than count - K of them; tokens holding NaN, +Inf and all -Inf among clean tokens; ungrouped, 8 groups of 256 experts, and
+            12 groups (5 kept) of a 240-expert copy of the same rows.
   layer     5 experts, 128 -> 96 -> 64: forward_logits equals forward on the route's outputs to the bit, T = 37 and T = 3, both
             `stored` values, with a base, leading dimensions (2, 5); nothing is read back.
 """
@@ -82,7 +86,8 @@ def _case(x, topk, n_group, topk_group, group_top, variant, negative_bias=False,
 @pytest.mark.parametrize("count,topk,n_group,topk_group,group_top,tokens,variant", tuple(rc.ungrouped_cases()) + tuple(rc.grouped_cases()))
 def test_route_is_the_rule_on_its_scores_and_agrees_with_float64(count, topk, n_group, topk_group, group_top, tokens, variant):
     per, waves = rc.route_path(count)
-    assert per == {1: 1, 2: 1, 8: 1, 60: 1, 64: 1, 65: 2, 128: 2, 129: 4, 160: 4, 256: 4, 257: 0, 320: 0, 384: 0, 4096: 0, 32: 1}[count]
+    assert per == {1: 1, 2: 1, 8: 1, 60: 1, 64: 1, 65: 2, 128: 2, 129: 4, 160: 4, 256: 4, 257: 0, 320: 0, 384: 0, 4096: 0, 32: 1,
+                   96: 2, 120: 2, 192: 4, 240: 4, 330: 0}[count]
     assert rc.route_grid(tokens, count) == (-(-tokens // waves), 1) and (waves == 1 or tokens % waves or tokens == 1)   # a ragged last workgroup
     if count == 4096:
         assert (count, topk) == (hb.MOE_MAX_EXPERTS, hb.MOE_MAX_TOPK) and not variant[1]          # the limits, without a bias
@@ -185,9 +190,11 @@ def test_ties_and_special_values():
     x[5, 7], x[6, 200], x[7] = np.nan, np.inf, -np.inf
     x[8] = np.where(np.arange(count) < 100, 20.0 + np.arange(count) % 7, x[8])     # sigmoid saturation: a hundred scores of 1.0f
     clean = [0, 1, 2, 3, 4, 8, 9, 10, 11]
+    whole = x
     for score in ("softmax", "sigmoid"):
-        for n_group, topk_group in ((1, 1), (8, 4)):
+        for n_group, topk_group in ((1, 1), (8, 4), (12, 5)):
             variant = (score, False, True, 0.0, 1.0)
+            x = whole[:, :240] if n_group == 12 else whole           # 12 groups of 20: a 240-expert copy of the same rows, 4 idle group slots
             ids, w, s = _run(_dev(x), None, K, n_group, topk_group, 2, variant)
             assert ids[1].tolist() == list(range(K))      # the first K experts (of the first topk_group groups: 32 an expert group)
             low, high = sorted((int(order[K - 1]), int(order[K])))
