@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTQ_VERSION 143 /* 0.1.4.10 (optional symbols as well, so the number stays 143): + mtq_pack_tiles_transposed_batched, mtq_unpack_tiles_transposed_batched; 0.1.4.9 (optional symbols as well): + mtq_packed_tile_bytes, mtq_packed_offsets, mtq_pack_tiles, mtq_unpack_tiles, mtq_packed_linear; 0.1.4.8 (optional symbols as well): + mtq_output_error_transposed, mtq_tile_error_tables_transposed; 0.1.4.7 (optional symbols as well): + mtq_gram_full / _scratch_doubles, mtq_gptq_sweep / _scratch_doubles; 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
+#define MTQ_VERSION 143 /* 0.1.4.11 (optional symbols as well, so the number stays 143): + mtq_tile_sq_error_batched, mtq_budget_allocate_device / _scratch_bytes; 0.1.4.10 (optional symbols as well, so the number stays 143): + mtq_pack_tiles_transposed_batched, mtq_unpack_tiles_transposed_batched; 0.1.4.9 (optional symbols as well): + mtq_packed_tile_bytes, mtq_packed_offsets, mtq_pack_tiles, mtq_unpack_tiles, mtq_packed_linear; 0.1.4.8 (optional symbols as well): + mtq_output_error_transposed, mtq_tile_error_tables_transposed; 0.1.4.7 (optional symbols as well): + mtq_gram_full / _scratch_doubles, mtq_gptq_sweep / _scratch_doubles; 0.1.4.6 (optional symbols as well): + mtq_gram_blocks / _scratch_doubles, mtq_tile_error_tables; 0.1.4.5 (optional symbols as well): + mtq_quantize_rows_bf16, mtq_output_error_qx; 0.1.4.4 (the number stays 143: its additions are optional symbols, found by name): + mtq_fp4_proxy_sums / _scratch_doubles, MTQ_FMT_MXFP4 / MTQ_FMT_NVFP4 in mtq_quantize; 0.1.4.3: + ragged batches (MtqMatrix, mtq_tile_stats_ragged, mtq_threshold_enqueue_ragged / _columns_ragged); 0.1.4.2: - chain records, + mtq_threshold_enqueue / _columns; 0.1.4.1: + partial / listed K1 (mtq_tile_stats_partial, mtq_tile_stats_listed), the search in phases with shared visiting orders, mtq_shutdown, mtq_knife_tiles_device */
 
 typedef enum {
     MTQ_OK = 0,
@@ -288,6 +288,35 @@ int mtq_tile_error_tables(const void *w, int w_dtype, int64_t n, int64_t k, int6
  */
 int mtq_tile_error_tables_transposed(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw, const double *h, size_t h_doubles,
                                      double *e_out, double *e_w, size_t table_doubles, void *stream);
+
+/*
+ * Tile maps at a size target (the mixed-tile-budget algorithm; budget_maps.allocate is the contract and the oracle).
+ *
+ * Weight-space error table, batched — e_w[b][t][f] = Σ (K2_f(x_b) − x_b)² for every tile t of `count` equally shaped resident matrices
+ * (matrix b at x + b · stride_elems, rows × cols, ld >= cols, bf16 or float32, row layout, ragged edges zero padded) in one launch:
+ * bit for bit the e_w that mtq_tile_error_tables writes for each matrix alone (the same per-tile order), without Gram blocks and
+ * without e_out.  e_w: device doubles [count][tiles][4].
+ *
+ * Allocation — table: device doubles [tiles][4] by format code; segment j is tiles seg_first[j] .. seg_first[j + 1] − 1 (seg_first:
+ * n_seg + 1 device entries, non-decreasing from 0 to tiles) with its own budget_bytes[j] (device doubles).  One segment per tensor of a
+ * batch gives every tensor its own budget; one segment over everything lets the tensors of a model share one.  For every segment whose
+ * table is finite, map (device int8 [tiles], format codes) and counts (device int64 [n_seg][4], tiles per format code) are those of
+ * budget_maps.allocate on the segment's rows with the candidates of fmt_mask: every tile walks the lower convex hull of its
+ * (bytes, error) points with allocate's float64 operations, the steps are ordered by (slope descending, tile ascending, step
+ * ascending) and taken while allocate's size expression stays within the budget.  status (device int32 [n_seg]): 0 done; 1 the budget
+ * is below the all-cheapest size; 2 a non-finite entry in the segment's rows (any of the four columns); map and counts of a segment
+ * with a non-zero status are unspecified.  scratch: 8-byte aligned device memory of at least mtq_budget_allocate_scratch_bytes bytes for
+ * (tiles, n_seg).  Everything is enqueued on `stream`; nothing is read back and no float atomics are used: equal tables give equal maps.
+ *
+ * A null pointer, count, rows, cols, tiles or n_seg <= 0, ld < cols, a fmt_mask without a tile format or a short scratch returns
+ * MTQ_ERR_INVALID before a device is looked for.  csrc/mtq_budget.hip.
+ */
+int mtq_tile_sq_error_batched(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                              double *e_w, void *stream);
+size_t mtq_budget_allocate_scratch_bytes(int64_t tiles, int64_t n_seg);
+int mtq_budget_allocate_device(const double *table, int64_t tiles, const int64_t *seg_first, int n_seg, uint32_t fmt_mask,
+                               const double *budget_bytes, int8_t *map, int64_t *counts, int32_t *status, void *scratch,
+                               size_t scratch_bytes, void *stream);
 
 /*
  * GPTQ's error-compensated BFP weights, device half (no reference counterpart; quantization_analysis_amd/gptq.py holds the host half

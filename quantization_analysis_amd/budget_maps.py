@@ -36,6 +36,10 @@ reconstruct_emulation(w, a, "transpose") is the map's Ŵ, as reconstruct_mixed_t
 
 Backends: emulation — float64 torch / NumPy on the host; hip — csrc/mtq_budget.hip (mtq_gram_blocks per chunk, then
 mtq_tile_error_tables or mtq_tile_error_tables_transposed and one device-to-host copy).
+
+The mixed-tile-budget algorithm (compression_algorithms/mixed_tile_budget.py) applies the same rule to e_w alone, per tensor or — scope
+"model", model_maps below — with one budget over the concatenated tables of a selection.  Its hip route allocates on the device
+(mtq_budget_allocate_device) under the contract that map and counts equal allocate's for every finite table: allocate is the oracle.
 """
 from __future__ import annotations
 
@@ -254,6 +258,33 @@ def allocate(table: np.ndarray, formats, bits: float, grid: Optional[tuple] = No
     assignment = codes[assign_idx].astype(np.int8).reshape(grid)
     counts = {f: int(np.count_nonzero(assignment == c)) for c, f in enumerate(MIXED_TILE_FORMATS)}
     return assignment, counts, mixed_tile_total_bytes(counts)
+
+
+def model_budget(bits: float, tiles: int) -> float:
+    """allocate's budget for `tiles` tiles in all: bits / 8 · 1024 · tiles bytes."""
+    return check_bits(bits) / 8.0 * float(TILE * TILE) * float(tiles)
+
+
+def split_maps(flat_map, grids) -> list:
+    """One map over the tiles of several tensors numbered through, tensor j's th_j · tw_j tiles behind tensor j−1's → the tensors' own
+    int8 [th_j, tw_j] maps."""
+    flat = np.asarray(flat_map, dtype=np.int8).reshape(-1)
+    sizes = [int(th) * int(tw) for th, tw in grids]
+    if sum(sizes) != flat.size:
+        raise ValueError(f"the grids hold {sum(sizes)} tiles, the map {flat.size}")
+    first = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    return [flat[first[j]:first[j + 1]].reshape(g) for j, g in enumerate(grids)]
+
+
+def model_maps(tables, grids, formats, bits: float) -> Union[tuple, str]:
+    """One budget over a whole selection (scope "model"): the tensors' tables [T_j, 4] are concatenated in order, tiles numbered
+    through, and allocate runs once with bits / 8 · 1024 · Σ T_j bytes, so a sensitive tensor takes bytes from an insensitive one →
+    (maps: each tensor's int8 [th_j, tw_j], counts over everything, tile_bytes), or allocate's reason."""
+    table = np.concatenate([np.asarray(t, dtype=np.float64).reshape(-1, len(MIXED_TILE_FORMATS)) for t in tables])
+    got = allocate(table, formats, bits)
+    if isinstance(got, str):
+        return got
+    return split_maps(got[0], grids), got[1], got[2]
 
 
 def predicted_sse(table: np.ndarray, assignment: np.ndarray) -> float:

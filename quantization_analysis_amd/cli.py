@@ -36,7 +36,7 @@ from .quantization_formats import PROXY_FORMATS, ROW_FORMATS, SUPPORTED_FORMATS
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 FORMAT_BYTES_PER_ELEM = {"mxfp4": 0.5, "nvfp4": 0.5, "bf16": 2.0, "bfp8": 1.088, "bfp4": 0.50097, "bfp2": 0.25097, "fp0": 0.0}  # wq:132-140
-MIXED_ALGOS = {"mixed-tile-greedy", "mixed-tile-random", "mixed-tile-threshold"}
+MIXED_ALGOS = {"mixed-tile-greedy", "mixed-tile-random", "mixed-tile-threshold", "mixed-tile-budget"}
 
 
 def display_name(algo) -> str:
@@ -492,6 +492,9 @@ def run(argv=None) -> int:
         ctx = {}
         try:
             selected_algo = create_algorithm(config.algorithm, algo_params)
+            if selected_algo.name == "mixed-tile-budget" and selected_algo.scope == "model":
+                raise _JobError('error: mixed-tile-budget with "scope": "model" allocates one budget over the whole selection, which wq\'s '
+                                "tensor-by-tensor tables do not show: run scripts/pack_model.py with this config")
             baseline = create_algorithm("none", {})
             algorithms = [baseline] if selected_algo.name == "none" else [baseline, selected_algo]
             filter_query = " ".join(args.filter_query).strip() or None

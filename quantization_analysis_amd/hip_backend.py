@@ -107,6 +107,9 @@ SIGNATURES = {
     "mtq_gptq_sweep": ("i", "pilllpzpzplppzp", True),
     "mtq_output_error_transposed": ("i", "plllpillpuppilppzppl", True),
     "mtq_tile_error_tables_transposed": ("i", "pilllpzppzp", True),
+    "mtq_tile_sq_error_batched": ("i", "pilllllpp", True),
+    "mtq_budget_allocate_scratch_bytes": ("z", "ll", True),
+    "mtq_budget_allocate_device": ("i", "plpiupppppzp", True),
     "mtq_debug_k1_grid": ("i", "iliiip", True),
     "mtq_debug_work_counters": ("i", "p", True),
     "mtq_packed_tile_bytes": ("z", "i", True),
@@ -877,6 +880,65 @@ def tile_error_tables_transposed(w, h, want_weight: bool = True):
     check(fn(w.data_ptr(), w_code, n, k, ldw, h.data_ptr(), h.numel(), out[0].data_ptr(), out[1].data_ptr() if want_weight else 0,
              th * tw * 4, _stream_ptr()))
     return out[0], (out[1] if want_weight else None)
+
+
+def tile_sq_error_batched(x, out=None):
+    """The weight-space error tables of a batch (mtq_tile_sq_error_batched) on the current stream → float64 device tensor [count, tiles, 4]
+    by MIXED_TILE_FORMATS code: Σ (K2_f(x) − x)² of every 32 × 32 tile, bit for bit tile_error_tables' e_w of each matrix.  x: a (rows,
+    cols) or (count, rows, cols) bf16 / float32 device tensor with contiguous rows (a strided batch view is read in place)."""
+    torch = _torch()
+    code, count, stride, rows, cols, ld = _matrix(x)
+    th, tw = tiles_hw(rows, cols)
+    if count > 1 and stride < (rows - 1) * ld + cols:
+        raise MtqError("the matrices of the batch overlap (stride(0) is shorter than a matrix)")
+    require_gpu()
+    fn = _entry("mtq_tile_sq_error_batched")
+    if out is None:
+        out = torch.empty((count, th * tw, 4), dtype=torch.float64, device=x.device)
+    check(fn(x.data_ptr(), code, count, stride, rows, cols, ld, _buffer(out, torch.float64, count * th * tw * 4, "out"), _stream_ptr()))
+    return out
+
+
+def budget_allocate_scratch_bytes(tiles: int, n_seg: int) -> int:
+    """Bytes of scratch one mtq_budget_allocate_device call over `tiles` tiles in `n_seg` segments needs."""
+    return int(_entry("mtq_budget_allocate_scratch_bytes")(int(tiles), int(n_seg)))
+
+
+BUDGET_STATUS_BELOW_FLOOR, BUDGET_STATUS_NON_FINITE = 1, 2   # include/mtq.h: mtq_budget_allocate_device's status
+
+
+def budget_allocate_device(table, seg_first, formats, budget_bytes, scratch=None):
+    """budget_maps.allocate on the device (mtq_budget_allocate_device) on the current stream, nothing read back → (maps int8 [tiles],
+    counts int64 [n_seg, 4], status int32 [n_seg]) device tensors.  table: contiguous float64 device tensor [tiles, 4]; seg_first: int64
+    device tensor [n_seg + 1], segment j = tiles seg_first[j] .. seg_first[j + 1] − 1; budget_bytes: float64 device tensor [n_seg];
+    formats: the candidates (those outside MIXED_TILE_FORMATS are ignored, as allocate ignores them).  scratch: a uint8 device tensor of
+    at least budget_allocate_scratch_bytes(tiles, n_seg) (allocated when None)."""
+    torch = _torch()
+    if table.dim() != 2 or table.shape[1] != 4:
+        raise MtqError(f"table must be [tiles, 4], got {tuple(table.shape)}")
+    T = int(table.shape[0])
+    if seg_first.dim() != 1 or seg_first.numel() < 2:
+        raise MtqError("seg_first must hold n_seg + 1 >= 2 entries")
+    n_seg = int(seg_first.numel()) - 1
+    mask = fmt_mask([f for f in formats if f in MIXED_TILE_FORMATS])
+    if T <= 0 or not mask:
+        raise MtqError("budget_allocate_device needs at least one tile and one mixed-tile format")
+    if table.device != seg_first.device or table.device != budget_bytes.device:
+        raise MtqError("table, seg_first and budget_bytes must be on one device")
+    tp = _buffer(table, torch.float64, T * 4, "table")
+    fp = _buffer(seg_first, torch.int64, n_seg + 1, "seg_first")
+    bp = _buffer(budget_bytes, torch.float64, n_seg, "budget_bytes")
+    require_gpu()
+    fn = _entry("mtq_budget_allocate_device")
+    need = budget_allocate_scratch_bytes(T, n_seg)
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=table.device)
+    sp = _buffer(scratch, torch.uint8, need, "scratch")
+    maps = torch.empty((T,), dtype=torch.int8, device=table.device)
+    counts = torch.empty((n_seg, 4), dtype=torch.int64, device=table.device)
+    status = torch.empty((n_seg,), dtype=torch.int32, device=table.device)
+    check(fn(tp, T, fp, n_seg, mask, bp, maps.data_ptr(), counts.data_ptr(), status.data_ptr(), sp, scratch.numel(), _stream_ptr()))
+    return maps, counts, status
 
 
 def gram_full(x, h, scratch=None):

@@ -44,7 +44,7 @@ from .quantization_formats import BASE_FORMATS as SUPPORTED_FORMATS, quantize_we
 FORMAT_BYTES_PER_ELEM = {"bf16": 2.0, "bfp8": 1.088, "bfp4": 0.50097, "bfp2": 0.25097, "fp0": 0.0}  # wq:132-140 (cli.py)
 SLOTS = ("bf16", "bfp8", "bfp4", "bfp2", "map", "fp0", "recorded")  # include/mtq.h MTQ_OE_*
 BACKENDS = ("emulation", "hip")
-MIXED_ALGOS = {"mixed-tile-greedy", "mixed-tile-random", "mixed-tile-threshold"}
+MIXED_ALGOS = {"mixed-tile-greedy", "mixed-tile-random", "mixed-tile-threshold", "mixed-tile-budget"}
 LAYOUTS = ("rows", "transpose")
 TRANSPOSE_FORMATS = ("bfp8", "bfp4", "bfp2")   # the formats with a +transpose row: bf16 and fp0 are elementwise
 TRANSPOSE_SUFFIX = "+transpose"

@@ -19,12 +19,12 @@ import time
 import numpy as np
 
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS
-from .pipeline import GreedyPipeline, ThresholdPipeline, cpu_budget, default_workers
+from .pipeline import BudgetPipeline, GreedyPipeline, ThresholdPipeline, cpu_budget, default_workers
 from .pipeline_common import gated_pcc
 from .quantization_formats import PROXY_FORMATS, ROW_FORMATS
 from .settings import settings
 
-STREAMED_ALGOS = {"mixed-tile-greedy", "mixed-tile-threshold"}
+STREAMED_ALGOS = {"mixed-tile-greedy", "mixed-tile-threshold", "mixed-tile-budget"}
 MAX_BATCH_TILES = 1 << 21      # tiles per pipeline batch: bounds the record buffers (≈ 0.3 GB device + 0.2 GB pinned per slot)
 K1_LAUNCH_TILES = 1 << 19      # tiles per K1 launch with the host scan (32 x 4096²: a chunk's records cross PCIe beside the next chunk's K1)
 MAX_SLOTS = settings().wq_max_slots   # record slots of the streamed pipeline (K1 records + scan scratch of a batch: a few hundred MB each)
@@ -79,6 +79,10 @@ class ShardEvaluator:
             if self._pipe is None:
                 self._pipe = GreedyPipeline(self.tile_formats, a.metric, a.threshold, a.seed, chunk=chunk, workers=default_workers(), pure_formats=self.search_pure,
                                             layout=self.layout)   # three search streams (the pipeline's default): 8, one per batch in flight, measured 27 % slower in round 3
+            self._pipe.chunk = chunk
+        elif a.name == "mixed-tile-budget":
+            if self._pipe is None:
+                self._pipe = BudgetPipeline(self.tile_formats, a.metric, a.bits, chunk=chunk, pure_formats=self.search_pure)
             self._pipe.chunk = chunk
         else:
             if self._pipe is None:
