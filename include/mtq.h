@@ -522,6 +522,28 @@ int mtq_greedy_scan_device_ex(const double *stats, int64_t count, int64_t tiles,
 size_t mtq_scan_orders_bytes(int64_t tiles);
 int mtq_scan_orders_device(uint64_t seed, int64_t tiles, int n_orders, void *orders, size_t orders_bytes, void *stream);
 
+/* Last-pass candidates finished inside K1 (the lazy route's early form).  Where every tile accepts the first BFP format, the tiles that reach
+ * the search's last pass are very nearly the first visits of the pass before it, whose order is one of the shared orders: "rank below a
+ * cutoff" predicts them before the search has run, and K1 evaluates their left-out statistics from the rows it holds anyway.
+ *   mtq_scan_rank_device: rank[0 .. tiles) (device uint32) = the inverse of order `which` (0: pass 1's, 1: pass 2's) of an orders buffer
+ *     mtq_scan_orders_device has filled: rank[order[i]] = i, np.argsort of the reference's permutation; all-ones when the order is not
+ *     complete.  Ordered behind mtq_scan_orders_device by the stream.
+ *   mtq_tile_stats_partial_begin_early: mtq_tile_stats_partial_begin, and for every tile with rank[tile] < cutoff (tile: index inside its
+ *     tensor) also what mtq_tile_stats_listed(full_mask bfp2, err_mask bfp4) writes, bit for bit.  Needs layout bfp8|bfp4|bfp2, full_mask
+ *     bfp8, sums_mask bfp4 (MTQ_ERR_UNSUPPORTED otherwise); cutoff 0 is mtq_tile_stats_partial_begin itself.  A ranked tile the kernel
+ *     cannot take is marked like any other, and _end writes its whole record.
+ *   mtq_greedy_scan_device_early: phase 1 of mtq_greedy_scan_device_ex that keeps the candidates with rank < cutoff off the list (the
+ *     same table and cutoff as the K1 launch of these records); the list may come out empty while the last pass still has candidates.
+ * The cutoff is a hint: any value gives the same maps.  All three symbols are optional: a build of this version may lack them. */
+int mtq_scan_rank_device(const void *orders, int64_t tiles, int which, uint32_t *rank, void *stream);
+int mtq_tile_stats_partial_begin_early(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols, int64_t ld,
+                                       uint32_t layout_mask, uint32_t full_mask, uint32_t sums_mask, double *stats, uint32_t *mark,
+                                       uint32_t *launch_id_out, const uint32_t *rank, uint32_t cutoff, void *stream);
+int mtq_greedy_scan_device_early(const double *stats, int64_t count, int64_t tiles, uint32_t fmt_mask, const int *formats, int n_formats,
+                                 int metric, double threshold, double elem_count, const uint64_t *seeds, int8_t *maps, int32_t *status,
+                                 int32_t *counts, void *scratch, size_t scratch_bytes, const void *orders, uint32_t *listed,
+                                 uint32_t *n_listed, void *carry, const uint32_t *rank, uint32_t cutoff, void *stream);
+
 /* The knife-edge tiles of the threshold rule, prepared on the device for the host's literal float32 score (replaces the gather of
  * tiles and the per-format Quantizer.quantize calls of mixed_tile_threshold.py:97-110 for the tiles whose float64 score fell inside
  * the noise band — `near` is the mask array mtq_threshold_assign_device wrote, one int8 per tile of `count` equally shaped tensors):

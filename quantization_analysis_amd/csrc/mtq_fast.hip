@@ -554,7 +554,12 @@ struct ListedArgs {
     uint32_t tiles_w32;              // tiles per tile row
 };
 
-template <uint32_t SUMS, uint32_t ERRS, bool XS, bool LISTED>
+// EARLY (the lazy route's <3,1> launch): `la.list` is a rank table over a tensor's tiles and `la.cap` a cutoff.  A tile whose
+// rank is below the cutoff is predicted to reach the search's last pass, and the wave that holds its rows forms what the listed launch
+// <4,6> would form for it — the left-out format whole, Σ|x−y| and max|x−y| of the one before — from the image, before the next unit's rows
+// overwrite it: all 64 lanes take one of the tile's 64 groups (lane 4j + g is the group the listed form's lane j takes g-th), a quad's
+// four terms are added in that order and the sixteen quads by the balanced tree, so the bits are the listed launch's.
+template <uint32_t SUMS, uint32_t ERRS, bool XS, bool LISTED, bool EARLY = false>
 __global__ __launch_bounds__(kFastWaves * 64)   // (the waves per SIMD go through the attribute: a second launch-bounds argument would replace it)
 __attribute__((amdgpu_waves_per_eu(rolled_waves(SUMS, ERRS), rolled_max_waves(SUMS, ERRS, LISTED)))) void tile_stats_bf16_rolled(
     const uint16_t *__restrict__ x, int64_t stride, int64_t ld, int tiles_w, int64_t tiles, int units_w, int units_per_tensor,
@@ -654,11 +659,11 @@ __attribute__((amdgpu_waves_per_eu(rolled_waves(SUMS, ERRS), rolled_max_waves(SU
     // Where a unit lives is worked out ONCE, when the unit is claimed: its first row segment (the DMA base) and its records' place.  (Round 3
     // divided by the launch's runtime tensor and row geometry in every issue_dma and again for the records: six 32-bit divisions per
     // unit, each a dozen vector instructions — 5 % of the kernel; the listed form did two per LANE and call.)
-    struct Where { const unsigned char *base; double *out; unsigned long long mine; };
+    struct Where { const unsigned char *base; double *out; unsigned long long mine; uint32_t rk; };   // rk (EARLY): lane q < 4 holds the rank of the unit's tile q
     // listed form: the global tile this lane's 16-lane group serves in unit u (a short last unit repeats the list's last tile)
     auto listed_tile = [&](int u, uint32_t q) -> uint32_t { return la.list[min((uint32_t)u * 4u + q, n_listed - 1u)]; };
     auto locate = [&](int u) -> Where {
-        Where w{nullptr, nullptr, 0ull};
+        Where w{nullptr, nullptr, 0ull, 0xFFFFFFFFu};
         if constexpr (LISTED) {
             // lane q < 4 works out where tile q of the unit starts; issue_rows lets every lane pick the start of the tile its chunk belongs to
             const uint32_t gt = listed_tile(u, (uint32_t)lane & 3u);
@@ -669,6 +674,7 @@ __attribute__((amdgpu_waves_per_eu(rolled_waves(SUMS, ERRS), rolled_max_waves(SU
             const int b = u / units_per_tensor, r = u - b * units_per_tensor, tr = r / units_w, uc = r - tr * units_w;
             w.base = reinterpret_cast<const unsigned char *>(x + (int64_t)b * stride + ((int64_t)tr * kTile) * ld + (int64_t)uc * kUnitCols);
             w.out = stats + ((int64_t)b * tiles + (int64_t)tr * tiles_w + uc * kUnitTiles) * rec;
+            if constexpr (EARLY) w.rk = la.list[(uint32_t)(tr * tiles_w + uc * kUnitTiles) + ((uint32_t)lane & 3u)];   // read a unit ahead of its use
         }
         return w;
     };
@@ -708,7 +714,7 @@ __attribute__((amdgpu_waves_per_eu(rolled_waves(SUMS, ERRS), rolled_max_waves(SU
     int u = claim_first();
     --left;
     uint32_t par = 0u;                                                        // the half the current unit's even rows are in
-    Where here{nullptr, nullptr, 0ull}, next{nullptr, nullptr, 0ull};
+    Where here{nullptr, nullptr, 0ull, 0xFFFFFFFFu}, next{nullptr, nullptr, 0ull, 0xFFFFFFFFu};
     if (u < total_units) { here = locate(u); issue_rows(here, 0, in_addr); issue_rows(here, 1, in_addr + kHalfBytes); }
     while (u < total_units) {
         unsigned char *half_a = in + par * kHalfBytes, *half_b = in + (par ^ 1u) * kHalfBytes;
@@ -766,7 +772,53 @@ __attribute__((amdgpu_waves_per_eu(rolled_waves(SUMS, ERRS), rolled_max_waves(SU
             mx[f] = row_max_nonneg(mx[f]);   // magnitudes (or the tile is marked and the value never used)
         }
         const unsigned long long bad_lanes = __ballot(bad);
-        const bool tile_bad = ((bad_lanes >> (16 * t)) & 0xFFFFull) != 0ull;
+        bool tile_bad = ((bad_lanes >> (16 * t)) & 0xFFFFull) != 0ull;
+
+        // EARLY: the unit's predicted tiles, one after the other (wave-uniform), while both halves still hold this unit's rows.  The lanes
+        // of tile q keep its seven results (terms 9..13 of the record order, the two maxima) until the record image exists.
+        double ev[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        float emx[2] = {0.0f, 0.0f};
+        bool early_mine = false;
+        if constexpr (EARLY) {
+            const uint32_t er = (uint32_t)lane >> 1, es = er >> 1;           // this lane's row of the tile and that row's slot in its half
+            const unsigned char *erow = ((er & 1u) ? half_b : half_a) + es * 256u;
+            const uint32_t ec0 = (2u * ((uint32_t)lane & 1u)) ^ swz(es);
+            for (uint32_t todo = (uint32_t)__ballot(here.rk < la.cap) & 0xFu; todo != 0u; todo &= todo - 1u) {
+                const uint32_t q = (uint32_t)__builtin_ctz(todo);
+                const uint32_t ec = ec0 ^ (4u * q);
+                const uint4 lo = *reinterpret_cast<const uint4 *>(erow + (ec << 4));
+                const uint4 hi = *reinterpret_cast<const uint4 *>(erow + ((ec ^ 1u) << 4));
+                const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                GroupOut G;
+                fast_group_f32<4u, 6u, false>((uint32_t)lane, w, G, [&](uint32_t owner) -> uint32_t {
+                    const uint32_t ro = owner >> 1, so = ro >> 1, co = ((4u * q + 2u * (owner & 1u)) ^ swz(so)) << 4;
+                    return *reinterpret_cast<const uint16_t *>(((ro & 1u) ? half_b : half_a) + so * 256u + (co ^ (2u * j)));
+                });
+                const bool mine = t == q;
+#pragma unroll
+                for (int k = 0; k < 5; ++k) {
+                    const double v = G.term[9 + k];
+                    // the listed form's lane: 0.0 + g0, + g1, + g2, + g3 ...
+                    double s = 0.0 + dpp_f64<0x00>(v);
+                    s = s + dpp_f64<0x55>(v); s = s + dpp_f64<0xAA>(v); s = s + dpp_f64<0xFF>(v);
+                    // ... and its tree over the sixteen row pairs: partners at distance 1, 2, 4, 8 (an addition commutes, so both partners
+                    // of a step hold the same bits)
+                    s = s + dpp_f64<kDppHalfMirror>(s);                       // every lane of a quad holds the quad's sum: the mirror of a half row swaps its two quads
+                    s = s + dpp_f64<0x128>(s);                                // row_ror:8
+                    s = s + __shfl_xor(s, 16, 64);
+                    s = s + __shfl_xor(s, 32, 64);
+                    ev[k] = mine ? s : ev[k];
+                }
+#pragma unroll
+                for (int f = 0; f < 2; ++f) {
+                    uint32_t m = f2u(row_max_nonneg(G.mx[1 + f]));
+                    m = max(m, (uint32_t)__shfl_xor((int)m, 16, 64)); m = max(m, (uint32_t)__shfl_xor((int)m, 32, 64));
+                    emx[f] = mine ? u2f(m) : emx[f];
+                }
+                tile_bad |= mine && __ballot(G.bad) != 0ull;                   // (the main loop has marked it already: the same groups)
+                early_mine |= mine;
+            }
+        }
         const int u_next = more ? claim_value(claimed) : 0x7FFFFFFF;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   // every lane's image reads are done: both halves are free
         if (u_next < total_units) { next = locate(u_next); issue_rows(next, 0, in_addr + (par ^ 1u) * kHalfBytes); }   // EARLY: the next unit's even rows, into the half the odd rows were in
@@ -822,6 +874,12 @@ __attribute__((amdgpu_waves_per_eu(rolled_waves(SUMS, ERRS), rolled_max_waves(SU
             if ((ERRS & 1u) && (eval_mask & ~part_mask & 2u)) rec_t[o8 + 4] = (double)mx[0];
             if ((ERRS & 2u) && (eval_mask & ~part_mask & 4u)) rec_t[o4 + 4] = (double)mx[1];
             if ((ERRS & 4u) && (eval_mask & ~part_mask & 8u)) rec_t[o2 + 4] = (double)mx[2];
+        }
+        if constexpr (EARLY) {
+            if (early_mine && j == 0) {
+                rec_t[o4 + 3] = ev[0]; rec_t[o4 + 4] = (double)emx[0];
+                rec_t[o2] = ev[1]; rec_t[o2 + 1] = ev[2]; rec_t[o2 + 2] = ev[3]; rec_t[o2 + 3] = ev[4]; rec_t[o2 + 4] = (double)emx[1];
+            }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (tile_bad && j == 0) {
@@ -911,7 +969,8 @@ extern "C" int mtq_debug_k1_grid(int kind, int64_t total, int cus, int waves_per
 // (served for the combinations instantiated below; any other part_mask is widened to full slots, which is always allowed).
 extern "C" int mtq_launch_tile_stats_bf16_fast(const void *x, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,
                                                int64_t ld, uint32_t fmt_mask, uint32_t eval_mask, uint32_t part_mask, double *stats, void *stream,
-                                               mtq::WorkSlot *work_out, unsigned launch_id, unsigned *mark, int self_reset)
+                                               mtq::WorkSlot *work_out, unsigned launch_id, unsigned *mark, int self_reset,
+                                               const uint32_t *rank, uint32_t cutoff)
 {
     const int64_t th = rows / kTile, tw = cols / kTile, tiles = th * tw;
     const int64_t units_w = cols / kUnitCols, upt = th * units_w, total = count * upt;
@@ -949,7 +1008,15 @@ extern "C" int mtq_launch_tile_stats_bf16_fast(const void *x, int64_t count, int
     case 0x77: MTQ_LAUNCH_FAST(7u, 7u); break;
     case 0x01: MTQ_LAUNCH_FAST(1u, 0u); break;           // partial records: the last evaluated format without Σ|x−y|, max|x−y|
     case 0x02: MTQ_LAUNCH_FAST(2u, 0u); break;
-    case 0x13: MTQ_LAUNCH_FAST(3u, 1u); break;
+    case 0x13:
+        // rank / cutoff (mtq_tile_stats_partial_begin_early): tiles ranked below the cutoff get the left-out statistics too; cutoff 0 is the plain launch
+        if (rank && cutoff != 0u && (fmt_mask & MTQ_MASK_ALL) == 0xEu) {
+            const ListedArgs early{rank, nullptr, cutoff, nullptr, nullptr, 0u};
+            hipLaunchKernelGGL((tile_stats_bf16_rolled<3u, 1u, true, false, true>), grid, block, lds_bytes, st, xp, stride_elems, ld, (int)tw, tiles, (int)units_w, (int)upt, (int)total, fmt_mask, eval_mask, part_mask, rec, stats, work, launch_id, kg.quota, early, mark, self_reset);
+        } else {
+            MTQ_LAUNCH_FAST(3u, 1u);
+        }
+        break;
     default:                                             // no BFP format evaluated: the launcher's callers never ask for that (they abandon the slot on any error: once, there)
         return fail(MTQ_ERR_INVALID, "the bf16 fast kernel needs at least one BFP format to evaluate");
     }

@@ -293,7 +293,8 @@ using namespace mtq;
 
 extern "C" int mtq_launch_tile_stats_bf16_fast(const void *x, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,
                                                int64_t ld, uint32_t fmt_mask, uint32_t eval_mask, uint32_t part_mask, double *stats, void *stream,
-                                               mtq::WorkSlot *work_out, unsigned launch_id, unsigned *mark, int self_reset);
+                                               mtq::WorkSlot *work_out, unsigned launch_id, unsigned *mark, int self_reset,
+                                               const uint32_t *rank, uint32_t cutoff);
 extern "C" int mtq_launch_tile_stats_direct(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,
                                             int64_t ld, uint32_t fmt_mask, double *stats, int vec_ok, void *stream, mtq::WorkSlot *work_out, unsigned launch_id);
 
@@ -760,7 +761,7 @@ static int tile_stats_launch(const void *x, int in_dtype, int64_t count, int64_t
         const unsigned launch_id = next_launch_id();
         // the exact-integer kernel serves partial evaluation; every other route below writes the whole layout (always allowed)
         const uint32_t ev = (eval_mask & 0xEu) ? eval_mask : fmt_mask;
-        if (int rc = mtq_launch_tile_stats_bf16_fast(x, count, stride_elems, rows, cols, ld, fmt_mask, ev, ev == eval_mask ? part_mask : 0u, stats, stream, &work, launch_id, nullptr, 0)) {
+        if (int rc = mtq_launch_tile_stats_bf16_fast(x, count, stride_elems, rows, cols, ld, fmt_mask, ev, ev == eval_mask ? part_mask : 0u, stats, stream, &work, launch_id, nullptr, 0, nullptr, 0u)) {
             work_counter_abandon(work);                  // the launch never happened: the slot keeps its previous user's event
             return rc;
         }
@@ -856,9 +857,10 @@ extern "C" int mtq_tile_stats_partial(const void *x, int in_dtype, int64_t count
 // mtq_tile_stats_partial in two launches the caller places itself: _begin is the exact-integer kernel alone (it resets its own unit
 // counters and leaves its launch id in *mark when it meets a tile it cannot take), _end the literal fix-up of those tiles.  The
 // streamed driver issues _begin on its K1 stream — nothing then sits between two K1 launches — and _end on the batch's search stream.
-extern "C" int mtq_tile_stats_partial_begin(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,
-                                            int64_t ld, uint32_t layout_mask, uint32_t full_mask, uint32_t sums_mask, double *stats,
-                                            uint32_t *mark, uint32_t *launch_id_out, void *stream)
+// rank / cutoff: mtq_tile_stats_partial_begin_early's (cutoff 0: the plain launch)
+static int partial_begin(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,
+                         int64_t ld, uint32_t layout_mask, uint32_t full_mask, uint32_t sums_mask, double *stats,
+                         uint32_t *mark, uint32_t *launch_id_out, const uint32_t *rank, uint32_t cutoff, void *stream)
 {
     if (!mark || !launch_id_out) return fail(MTQ_ERR_INVALID, "null argument");
     if (((full_mask | sums_mask) & ~layout_mask) != 0 || (full_mask & sums_mask) != 0 || (layout_mask & ~MTQ_MASK_ALL) != 0 || (sums_mask & 1u))
@@ -874,13 +876,33 @@ extern "C" int mtq_tile_stats_partial_begin(const void *x, int in_dtype, int64_t
         return fail(MTQ_ERR_UNSUPPORTED, "the two-launch form serves bf16 storage in whole 32x128 units with 16-byte aligned rows: use mtq_tile_stats_partial");
     WorkSlot work;
     const unsigned launch_id = next_launch_id();
-    if (int rc = mtq_launch_tile_stats_bf16_fast(x, count, stride_elems, rows, cols, ld, layout_mask, eval, sums_mask, stats, stream, &work, launch_id, mark, 1)) {
+    if (int rc = mtq_launch_tile_stats_bf16_fast(x, count, stride_elems, rows, cols, ld, layout_mask, eval, sums_mask, stats, stream, &work, launch_id, mark, 1, rank, cutoff)) {
         work_counter_abandon(work);
         return rc;
     }
     work_counter_release(work, stream);   // the kernel has reset the counters when it ends: the slot's next user is ordered behind it
     *launch_id_out = launch_id;
     return MTQ_OK;
+}
+
+extern "C" int mtq_tile_stats_partial_begin(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,
+                                            int64_t ld, uint32_t layout_mask, uint32_t full_mask, uint32_t sums_mask, double *stats,
+                                            uint32_t *mark, uint32_t *launch_id_out, void *stream)
+{
+    return partial_begin(x, in_dtype, count, stride_elems, rows, cols, ld, layout_mask, full_mask, sums_mask, stats, mark, launch_id_out, nullptr, 0u, stream);
+}
+
+// include/mtq.h: _begin that also completes the records of the tiles ranked below `cutoff` (what mtq_tile_stats_listed would write for them)
+extern "C" int mtq_tile_stats_partial_begin_early(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,
+                                                  int64_t ld, uint32_t layout_mask, uint32_t full_mask, uint32_t sums_mask, double *stats,
+                                                  uint32_t *mark, uint32_t *launch_id_out, const uint32_t *rank, uint32_t cutoff, void *stream)
+{
+    if (cutoff != 0u) {
+        if (!rank) return fail(MTQ_ERR_INVALID, "a cutoff needs a rank table");
+        if (layout_mask != 0xEu || full_mask != 0x2u || sums_mask != 0x4u)
+            return fail(MTQ_ERR_UNSUPPORTED, "the early form serves layout bfp8|bfp4|bfp2 with bfp8 in full and the sums of bfp4");
+    }
+    return partial_begin(x, in_dtype, count, stride_elems, rows, cols, ld, layout_mask, full_mask, sums_mask, stats, mark, launch_id_out, rank, cutoff, stream);
 }
 
 extern "C" int mtq_tile_stats_partial_end(const void *x, int in_dtype, int64_t count, int64_t stride_elems, int64_t rows, int64_t cols,

@@ -331,6 +331,8 @@ struct ScanArgs {
     int phase;                // 0: the whole search; 1: every pass but the last, then the last pass's candidates → listed; 2: the last pass
     uint32_t *listed, *n_listed;
     Carry *carry;             // [count] (phases 1 and 2)
+    const uint32_t *rank;     // phase 1 (mtq_greedy_scan_device_early): candidates of the last pass with rank[tile] < cutoff have their
+    uint32_t cutoff;          // left-out statistics already (mtq_tile_stats_partial_begin_early) and stay off the list; cutoff 0: none
 };
 
 constexpr int kNoOffset = 0xFF;
@@ -400,19 +402,30 @@ __device__ inline bool pcc_good(double n, double mean_x, double am2, double thr,
 // tile t0 + lane — 0x80, "fixed", past the end).  Eight blocks' bytes are in flight at once: one block per L2 round trip (≈ 750 cycles)
 // made each of these loops 670 k cycles on a 57 344-tile tensor — the two at the end of phase 1 and the two of phase 2 together more
 // than a pass's visits (round 4, found by adding up the shader-clock stamps: tools/scan_ticks.py).
-template <typename F>
-__device__ __forceinline__ void sift_map(const int8_t *map, int T, int lane, F &&f)
+// kTable: a per-tile uint32 table rides along, fetched in the same batches — f(t0, byte, table[t0 + lane]); without one f gets all-ones there.
+template <bool kTable, typename F>
+__device__ __forceinline__ void sift_map_with(const int8_t *map, const uint32_t *table, int T, int lane, F &&f)
 {
     for (int t00 = 0; t00 < T; t00 += 64 * 8) {
         uint8_t b[8];
+        uint32_t r[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) b[u] = (uint8_t)ld_l2(map + min(t00 + 64 * u + lane, T - 1));   // unconditional (a branch per load would put each in a block of its own)
+        for (int u = 0; u < 8; ++u) {   // unconditional (a branch per load would put each in a block of its own)
+            const int at = min(t00 + 64 * u + lane, T - 1);
+            b[u] = (uint8_t)ld_l2(map + at);
+            r[u] = kTable ? table[at] : 0xFFFFFFFFu;
+        }
 #pragma unroll
         for (int u = 0; u < 8; ++u) b[u] = t00 + 64 * u + lane < T ? b[u] : (uint8_t)0x80u;
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-            if (t00 + 64 * u < T) f(t00 + 64 * u, b[u]);
+            if (t00 + 64 * u < T) f(t00 + 64 * u, b[u], r[u]);
     }
+}
+template <typename F>
+__device__ __forceinline__ void sift_map(const int8_t *map, int T, int lane, F &&f)
+{
+    sift_map_with<false>(map, nullptr, T, lane, [&](int t0, uint8_t code, uint32_t) { f(t0, code); });
 }
 
 struct Offsets3 { uint32_t y, y2, xy; };   // packed by format code, one byte each (rec <= 22): a per-lane code picks its offset with a shift
@@ -879,14 +892,27 @@ __device__ __forceinline__ void scan_tensor(const ScanArgs &a, const Order &ord,
         // the last pass's candidates (:228) → the launch's list of tiles whose remaining statistics are evaluated now (mtq_tile_stats_listed)
         int nc = 0;
         if (status == 0 && !done) {
-            sift_map(map, T, lane, [&](int, uint8_t code) { nc += __builtin_popcountll(__ballot((code & 0x80u) == 0u)); });
+            // K1's early form has completed the records of the tiles ranked below the cutoff (one it could not take went to the literal
+            // fix-up, which writes every slot): only the other candidates are listed — possibly none, and the last pass still runs.
+            // Without a rank table every rank reads all-ones: every candidate is listed.
+            const bool ranked = a.rank != nullptr && a.cutoff != 0u;
+            auto sift = [&](auto &&f) {
+                if (ranked) sift_map_with<true>(map, a.rank, T, lane, f);
+                else sift_map_with<false>(map, nullptr, T, lane, f);
+            };
+            int nl = 0;
+            sift([&](int, uint8_t code, uint32_t rk) {
+                const bool cand = (code & 0x80u) == 0u;
+                nc += __builtin_popcountll(__ballot(cand));
+                nl += __builtin_popcountll(__ballot(cand && rk >= a.cutoff));
+            });
             unsigned first = 0u;
-            if (lane == 0 && nc > 0) first = atomicAdd(a.n_listed, (unsigned)nc);
+            if (lane == 0 && nl > 0) first = atomicAdd(a.n_listed, (unsigned)nl);
             first = (unsigned)__builtin_amdgcn_readfirstlane((int)first);
             int at = 0;
-            if (nc > 0)
-                sift_map(map, T, lane, [&](int t0, uint8_t code) {
-                    const bool cand = (code & 0x80u) == 0u;
+            if (nl > 0)
+                sift([&](int t0, uint8_t code, uint32_t rk) {
+                    const bool cand = (code & 0x80u) == 0u && rk >= a.cutoff;
                     const uint64_t bm = __ballot(cand);
                     if (cand) a.listed[first + (unsigned)(at + __builtin_popcountll(bm & below(lane)))] = (uint32_t)((int64_t)b * T + t0 + lane);
                     at += __builtin_popcountll(bm);
@@ -1056,6 +1082,19 @@ __global__ __launch_bounds__(64) void scan_orders(OrdersArgs a)
     }
 }
 
+// The inverse of one of the shared orders (mtq_scan_rank_device): rank[tile] = the position at which that pass visits the tile.  The
+// table is all-ones beforehand (the caller's memset) and stays so when the order is not complete: no tile then ranks below any cutoff.
+__global__ __launch_bounds__(256) void scan_rank(const unsigned char *orders, int64_t tiles, int which, uint32_t *rank)
+{
+    const OrdersHdr *hdr = reinterpret_cast<const OrdersHdr *>(orders);
+    if (hdr->tiles != (uint32_t)tiles || !hdr->ok[which]) return;
+    const uint32_t *P = reinterpret_cast<const uint32_t *>(orders + sizeof(OrdersHdr)) + (size_t)which * orders_stride(tiles);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < tiles; i += (int64_t)gridDim.x * 256) {
+        const uint32_t t = P[i];
+        if (t < (uint32_t)tiles) rank[t] = (uint32_t)i;
+    }
+}
+
 // jump-ahead tables A_q = a^q, G_q = 1 + a + … + a^(q−1) (mod 2^128), uploaded once per device (freed by mtq_shutdown)
 std::mutex g_jump_mu;
 U128 *g_jump_tab[64] = {nullptr};
@@ -1152,10 +1191,24 @@ extern "C" int mtq_scan_orders_device(uint64_t seed, int64_t tiles, int n_orders
     return check_launch("mtq_scan_orders_device");
 }
 
-extern "C" int mtq_greedy_scan_device_ex(const double *stats, int64_t count, int64_t tiles, uint32_t fmt_mask, const int *formats, int n_formats,
-                                         int metric, double threshold, double elem_count, const uint64_t *seeds, int8_t *maps, int32_t *status,
-                                         int32_t *counts, void *scratch, size_t scratch_bytes, const void *orders, int phase, uint32_t *listed,
-                                         uint32_t *n_listed, void *carry, void *stream)
+// include/mtq.h.  Runs behind mtq_scan_orders_device on the same stream (or any stream ordered behind it).
+extern "C" int mtq_scan_rank_device(const void *orders, int64_t tiles, int which, uint32_t *rank, void *stream)
+{
+    if (!orders || !rank) return fail(MTQ_ERR_INVALID, "null argument");
+    if (tiles <= 0 || tiles > MTQ_SCAN_DEVICE_MAX_TILES) return fail(MTQ_ERR_INVALID, "tiles out of range");
+    if (which < 0 || which > 1) return fail(MTQ_ERR_INVALID, "which must be 0 or 1");
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(rank, 0xFF, (size_t)tiles * sizeof(uint32_t), st) != hipSuccess) return fail(MTQ_ERR_HIP, "hipMemsetAsync failed");
+    const int64_t blocks = (tiles + 255) / 256;
+    hipLaunchKernelGGL(scan_rank, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, static_cast<const unsigned char *>(orders), tiles, which, rank);
+    return check_launch("mtq_scan_rank_device");
+}
+
+static int scan_device(const double *stats, int64_t count, int64_t tiles, uint32_t fmt_mask, const int *formats, int n_formats,
+                       int metric, double threshold, double elem_count, const uint64_t *seeds, int8_t *maps, int32_t *status,
+                       int32_t *counts, void *scratch, size_t scratch_bytes, const void *orders, int phase, uint32_t *listed,
+                       uint32_t *n_listed, void *carry, const uint32_t *rank, uint32_t cutoff, void *stream)
 {
     if (!stats || !formats || !seeds || !maps || !status || !scratch) return fail(MTQ_ERR_INVALID, "null argument");
     if (count <= 0 || count > (1 << 20) || tiles <= 0) return fail(MTQ_ERR_INVALID, "count and tiles must be positive");
@@ -1202,6 +1255,8 @@ extern "C" int mtq_greedy_scan_device_ex(const double *stats, int64_t count, int
     a.listed = listed;
     a.n_listed = n_listed;
     a.carry = static_cast<Carry *>(carry);
+    a.rank = phase == 1 ? rank : nullptr;
+    a.cutoff = cutoff;
     if (int rc = require_device()) return rc;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return fail(MTQ_ERR_HIP, "hipGetDevice failed");
@@ -1232,6 +1287,26 @@ extern "C" int mtq_greedy_scan_device_ex(const double *stats, int64_t count, int
         hipLaunchKernelGGL(greedy_scan_pcc_global, dim3((unsigned)count), dim3(threads), kFixedLds, st, a);
     }
     return check_launch("mtq_greedy_scan_device");
+}
+
+extern "C" int mtq_greedy_scan_device_ex(const double *stats, int64_t count, int64_t tiles, uint32_t fmt_mask, const int *formats, int n_formats,
+                                         int metric, double threshold, double elem_count, const uint64_t *seeds, int8_t *maps, int32_t *status,
+                                         int32_t *counts, void *scratch, size_t scratch_bytes, const void *orders, int phase, uint32_t *listed,
+                                         uint32_t *n_listed, void *carry, void *stream)
+{
+    return scan_device(stats, count, tiles, fmt_mask, formats, n_formats, metric, threshold, elem_count, seeds, maps, status, counts, scratch, scratch_bytes,
+                       orders, phase, listed, n_listed, carry, nullptr, 0u, stream);
+}
+
+// include/mtq.h: phase 1 of a split search behind mtq_tile_stats_partial_begin_early with the same rank table and cutoff
+extern "C" int mtq_greedy_scan_device_early(const double *stats, int64_t count, int64_t tiles, uint32_t fmt_mask, const int *formats, int n_formats,
+                                            int metric, double threshold, double elem_count, const uint64_t *seeds, int8_t *maps, int32_t *status,
+                                            int32_t *counts, void *scratch, size_t scratch_bytes, const void *orders, uint32_t *listed,
+                                            uint32_t *n_listed, void *carry, const uint32_t *rank, uint32_t cutoff, void *stream)
+{
+    if (cutoff != 0u && !rank) return fail(MTQ_ERR_INVALID, "a cutoff needs a rank table");
+    return scan_device(stats, count, tiles, fmt_mask, formats, n_formats, metric, threshold, elem_count, seeds, maps, status, counts, scratch, scratch_bytes,
+                       orders, 1, listed, n_listed, carry, rank, cutoff, stream);
 }
 
 extern "C" int mtq_greedy_scan_device(const double *stats, int64_t count, int64_t tiles, uint32_t fmt_mask, const int *formats, int n_formats,

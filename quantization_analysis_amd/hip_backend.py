@@ -79,6 +79,9 @@ SIGNATURES = {
     "mtq_scan_carry_bytes": ("z", "l", False),
     "mtq_scan_orders_bytes": ("z", "l", False),
     "mtq_scan_orders_device": ("i", "qlipzp", False),
+    "mtq_scan_rank_device": ("i", "plipp", True),
+    "mtq_tile_stats_partial_begin_early": ("i", "pillllluuuppppup", True),
+    "mtq_greedy_scan_device_early": ("i", "pllupiiddpppppzpppppup", True),
     "mtq_debug_scan_ticks": ("i", "p", False),
     "mtq_threshold_enqueue": ("i", "pillllluupiiddppplppppppp", False),
     "mtq_threshold_columns": ("i", "pllupppp", False),
@@ -553,9 +556,22 @@ def tile_stats_partial_begin(x3d, layout_mask: int, full_mask: int, sums_mask: i
     return int(lid.value)
 
 
+def tile_stats_partial_begin_early(x3d, layout_mask: int, full_mask: int, sums_mask: int, out, mark, rank, cutoff: int) -> int:
+    """mtq_tile_stats_partial_begin_early: tile_stats_partial_begin that also writes, for every tile with rank[tile] < cutoff (rank: int32 /
+    uint32 device tensor over a tensor's tiles, scan_rank_device), what tile_stats_listed would write for it.  cutoff 0: the plain launch."""
+    code, count, stride, rows, cols, ld = _matrix(x3d, (3,))   # views too: the entry checks the alignment of ld and the batch stride
+    th, tw = tiles_hw(rows, cols)
+    if rank.numel() < th * tw or rank.element_size() != 4:
+        raise ValueError("rank must hold one 32-bit entry per tile of a tensor")
+    lid = ctypes.c_uint32(0)
+    check(_entry("mtq_tile_stats_partial_begin_early")(x3d.data_ptr(), code, count, stride, rows, cols, ld, layout_mask, full_mask, sums_mask,
+                                                       out.data_ptr(), mark.data_ptr(), ctypes.byref(lid), rank.data_ptr(), int(cutoff), _stream_ptr()))
+    return int(lid.value)
+
+
 def tile_stats_partial_end(x3d, layout_mask: int, stats, mark, launch_id: int) -> None:
     """mtq_tile_stats_partial_end on the current stream: the literal fix-up of the tiles that launch could not take (usually none)."""
-    code, count, stride, rows, cols, ld = _contiguous_batch(x3d)
+    code, count, stride, rows, cols, ld = _matrix(x3d, (3,))
     check(lib().mtq_tile_stats_partial_end(x3d.data_ptr(), code, count, stride, rows, cols, ld, layout_mask, stats.data_ptr(),
                                            mark.data_ptr(), int(launch_id), _stream_ptr()))
 
@@ -2369,6 +2385,61 @@ def scan_orders_device(seed: int, tiles: int, n_orders: int = 2, out=None):
         raise ValueError("orders buffer is smaller than mtq_scan_orders_bytes()")
     check(lib().mtq_scan_orders_device(int(seed), int(tiles), int(n_orders), out.data_ptr(), int(out.numel()), _stream_ptr()))
     return out
+
+
+EARLY = ("mtq_scan_rank_device", "mtq_tile_stats_partial_begin_early", "mtq_greedy_scan_device_early")
+
+
+def early_bound() -> bool:
+    """Whether this build of the library binds the early form's entries (optional symbols: an older build of the same version lacks them)."""
+    return _has(EARLY)
+
+
+def rank_table_host(perm) -> np.ndarray:
+    """What mtq_scan_rank_device computes, restated on the host: rank[perm[i]] = i (uint32) — np.argsort(perm) of a permutation."""
+    perm = np.asarray(perm, dtype=np.int64)
+    rank = np.full(perm.size, 0xFFFFFFFF, dtype=np.uint32)
+    rank[perm] = np.arange(perm.size, dtype=np.uint32)
+    return rank
+
+
+def early_rank_host(seed: int, tiles: int, which: int = 1) -> np.ndarray:
+    """The table scan_rank_device(scan_orders_device(seed, tiles), tiles, which) holds, from the library's host generator: the search draws
+    one permutation of range(tiles) per pass while every tile is still a candidate; order `which` is the one after `which` + 1 others."""
+    rng = NumpyCompatRng(seed)
+    for _ in range(int(which) + 1):
+        rng.permutation(tiles)
+    return rank_table_host(rng.permutation(tiles))
+
+
+def scan_rank_device(orders, tiles: int, which: int, out=None):
+    """mtq_scan_rank_device: the inverse of order `which` (0: pass 1's, 1: pass 2's) of scan_orders_device's buffer → int32 device tensor
+    [tiles] holding uint32 ranks, asynchronous on the current stream (which must be ordered behind the orders' launch)."""
+    torch = _torch()
+    require_gpu()
+    if out is None:
+        out = torch.empty((int(tiles),), dtype=torch.int32, device=orders.device)
+    elif out.numel() < int(tiles) or out.element_size() != 4:
+        raise ValueError("rank must hold one 32-bit entry per tile")
+    check(_entry("mtq_scan_rank_device")(orders.data_ptr(), int(tiles), int(which), out.data_ptr(), _stream_ptr()))
+    return out
+
+
+def greedy_scan_device_early(stats_dev, mask: int, formats, metric: str, threshold: float, elem_count: float, seeds_dev, maps_out, status_out,
+                             scratch, counts_out, orders, listed, n_listed, carry, rank, cutoff: int) -> None:
+    """mtq_greedy_scan_device_early: phase 1 of greedy_scan_device_ex behind tile_stats_partial_begin_early with the same rank and cutoff —
+    the last pass's candidates ranked below the cutoff stay off the list."""
+    count, T = int(stats_dev.shape[0]), int(stats_dev.shape[1])
+    if scratch.numel() < greedy_scan_scratch_bytes(count, T):
+        raise ValueError("scratch is smaller than mtq_greedy_scan_scratch_bytes()")
+    if rank.numel() < T or rank.element_size() != 4:
+        raise ValueError("rank must hold one 32-bit entry per tile of a tensor")
+    fm = _format_codes(formats)
+    check(_entry("mtq_greedy_scan_device_early")(stats_dev.data_ptr(), count, T, mask, fm, len(formats), METRIC_CODE[metric], float(threshold), float(elem_count),
+                                                 seeds_dev.data_ptr(), maps_out.data_ptr(), status_out.data_ptr(),
+                                                 counts_out.data_ptr() if counts_out is not None else None, scratch.data_ptr(), int(scratch.numel()),
+                                                 orders.data_ptr() if orders is not None else None, listed.data_ptr(), n_listed.data_ptr(), carry.data_ptr(),
+                                                 rank.data_ptr(), int(cutoff), _stream_ptr()))
 
 
 def greedy_scan_device_ex(stats_dev, mask: int, formats, metric: str, threshold: float, elem_count: float, seeds_dev, maps_out, status_out,

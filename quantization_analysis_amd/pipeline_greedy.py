@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import concurrent.futures as cf
 import contextlib
+import math
 import os
 import time
 from dataclasses import dataclass, field
@@ -13,6 +14,34 @@ from . import hip_backend as hb
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS, mixed_tile_total_bytes
 from .settings import settings
 from .pipeline_common import KernelTiming, TensorResult, _scan_chunk, _sleep_until, _when_landed, columns_from_sums_batch, gated_pcc  # noqa: F401
+
+
+class EarlyCutoff:
+    """The cutoff hint of the lazy route's early form: one value per (tiles per tensor, formats, metric, threshold, seed).  The first batch
+    of a key runs with 0 (the plain route); afterwards the cutoff is the previous batch's largest per-tensor count of last-pass candidates
+    times 1 + margin, rounded up, capped at max_fraction x tiles.  Nothing but this number goes from one batch to the next, and no result
+    depends on it: too low leaves candidates to the listed launch, too high has K1 finish tiles nobody reads."""
+
+    def __init__(self, margin: float, max_fraction: float):
+        self.margin, self.max_fraction = float(margin), float(max_fraction)
+        self._next = {}
+
+    @staticmethod
+    def key(tiles: int, formats, metric: str, threshold: float, seed: int):
+        return (int(tiles), tuple(formats), str(metric), float(threshold), int(seed))
+
+    def cutoff(self, tiles: int, formats, metric: str, threshold: float, seeds) -> int:
+        """→ the cutoff of a batch about to be enqueued; seeds: the batch's per-tensor seeds — the route is off (0) unless they are all one."""
+        seeds = [int(v) for v in seeds]
+        if not seeds or len(set(seeds)) != 1:
+            return 0
+        return self._next.get(self.key(tiles, formats, metric, threshold, seeds[0]), 0)
+
+    def learn(self, tiles: int, formats, metric: str, threshold: float, seed: int, largest: int) -> int:
+        """A finished batch's largest per-tensor last-pass candidate count → the key's next cutoff."""
+        cut = min(int(math.ceil(int(largest) * (1.0 + self.margin))), int(self.max_fraction * int(tiles)))
+        self._next[self.key(tiles, formats, metric, threshold, seed)] = max(cut, 0)
+        return max(cut, 0)
 
 
 class GreedyPipeline:
@@ -87,6 +116,13 @@ class GreedyPipeline:
         # switches the route off for tensors of its tile count (the batches already in flight finish as they were enqueued).
         self.lazy_max_listed = settings().lazy_max_listed
         self.lazy_off = {}                       # tiles per tensor -> the listed fraction that switched the lazy route off
+        # early form of the lazy route: the last pass's candidates are very nearly the first visits of the pass before it, whose
+        # order is one of the shared ones — K1 finishes the tiles ranked below a cutoff in place and the listed launch keeps the rest.  The
+        # cutoff is a hint carried from the previous batch of the same key (EarlyCutoff); any value gives the same maps.
+        self.early = settings().early
+        self.early_cutoff = EarlyCutoff(settings().early_margin, self.lazy_max_listed)
+        self.early_tiles = 0                     # last-pass candidates K1 had finished already (diagnostics, beside listed_tiles)
+        self.early_force = None                  # test hook: a cutoff used whatever the policy says
         self.host_fallbacks = 0                  # tensors the device scan handed back (zero denominator)
         self.host_seconds = {"enqueue": 0.0, "wait": 0.0, "wrap": 0.0}   # driver-thread time: launching, waiting for results, wrapping them
         self._devbufs = {}
@@ -336,7 +372,15 @@ class GreedyPipeline:
         lazy = plan is not None
         if lazy:
             _lay, full_now, prev_bit, last_bit = plan
-        pending = []
+        # early form: the lazy route's <3,1> launch in its two-launch form over shared orders, with the left-out format last in the search
+        cutoff, rank_buf = 0, None
+        early_ok = (lazy and shared and self.early and hb.early_bound() and len(self.tile_formats) == 4
+                    and (k1_mask, full_now, prev_bit, last_bit) == (0xE, 0x2, 0x4, 0x8))
+        if early_ok:
+            cutoff = self.early_cutoff.cutoff(tiles, self.tile_formats, self.metric, self.threshold, sh.tolist())
+            if self.early_force is not None:
+                cutoff = max(0, min(int(self.early_force), tiles))
+        pending, early_chunks = [], []
         cur = torch.cuda.current_stream()
         if not cur.query():                             # x3d's producer may still be running there; an idle stream needs no event + barrier packet
             self.stream.wait_stream(cur)
@@ -362,8 +406,17 @@ class GreedyPipeline:
                         orders_ready.record(scan_stream)
                     if len(self._orders_cache) >= 32:       # a model's shape groups x seeds: a handful; bounded all the same (oldest out of the
                         self._orders_retired.append(self._orders_cache.pop(next(iter(self._orders_cache))))   # table, kept alive until close(): a search in flight may still read it)
-                    self._orders_cache[okey] = hit = [buf, orders_ready]
-                orders_buf, orders_ready = hit
+                    self._orders_cache[okey] = hit = [buf, orders_ready, None]
+                if hit[2] is None and early_ok and n_ord == 2:
+                    # the early form's ranks: the inverse of the last-but-one pass's order, drawn once by the first batch of the entry that can
+                    # use them (an entry may have been made by a batch off the early route) and read-only afterwards
+                    with torch.cuda.stream(scan_stream):
+                        if hit[1] is not None:
+                            scan_stream.wait_event(hit[1])
+                        hit[2] = hb.scan_rank_device(hit[0], tiles, 1)
+                        hit[1] = torch.cuda.Event()
+                        hit[1].record(scan_stream)          # orders and ranks are complete behind this one
+                orders_buf, orders_ready, rank_buf = hit
                 if orders_ready is not None and orders_ready.query():
                     hit[1] = orders_ready = None            # drawn and complete: no stream needs to wait for it any more
             with torch.cuda.stream(self.stream):
@@ -378,7 +431,13 @@ class GreedyPipeline:
                               and x3d.data_ptr() % 16 == 0 and (x3d.stride(0) * 2) % 16 == 0 and (x3d.stride(1) * 2) % 16 == 0
                               and os.environ.get("MTQ_FORCE_GENERIC", "0") != "1")
                 k1_id = None
-                if two_launch:
+                early_now = two_launch and cutoff > 0 and rank_buf is not None
+                if early_now:
+                    if orders_ready is not None:
+                        self.stream.wait_event(orders_ready)    # the ranks are drawn on a search stream (a key's second batch at the earliest: usually long done)
+                    k1_id = hb.tile_stats_partial_begin_early(x3d[first:first + n], k1_mask, full_now, prev_bit, b["dev"][first:first + n], b["mark"][ci:ci + 1],
+                                                              rank_buf, cutoff)
+                elif two_launch:
                     k1_id = hb.tile_stats_partial_begin(x3d[first:first + n], k1_mask, full_now if lazy else k1_mask, prev_bit if lazy else 0,
                                                         b["dev"][first:first + n], b["mark"][ci:ci + 1])
                 elif lazy:
@@ -412,7 +471,10 @@ class GreedyPipeline:
                     listed, nl = b["listed"][first * tiles:(first + n) * tiles], b["n_listed"][ci:ci + 1]
                     carry = b["carry"][first * per_carry:(first + n) * per_carry]
                     nl.zero_()
-                    hb.greedy_scan_device_ex(*args, counts_out=b["counts_dev"][first:first + n], orders=orders, phase=1, listed=listed, n_listed=nl, carry=carry)
+                    if early_now:
+                        hb.greedy_scan_device_early(*args, b["counts_dev"][first:first + n], orders, listed, nl, carry, rank_buf, cutoff)
+                    else:
+                        hb.greedy_scan_device_ex(*args, counts_out=b["counts_dev"][first:first + n], orders=orders, phase=1, listed=listed, n_listed=nl, carry=carry)
                     hb.tile_stats_listed(xs, k1_mask, last_bit, prev_bit, listed, nl, recs, scratch=b["lscr"][first * tiles + ci:(first + n) * tiles + ci + 1])
                     hb.greedy_scan_device_ex(*args, counts_out=b["counts_dev"][first:first + n], phase=2, carry=carry)
                 else:
@@ -438,10 +500,13 @@ class GreedyPipeline:
                 done = torch.cuda.Event(blocking=True, enable_timing=trace)
                 done.record(scan_stream)
             pending.append((done, first, n))
+            if lazy:
+                early_chunks.append(cutoff if early_now else 0)
             if trace:
                 self._trace_rows = getattr(self, "_trace_rows", []) + [(count, tiles, e0, e1, scanned, done, time.perf_counter())]
         enq = {"device": True, "buf": b, "pending": pending, "tiles_hw": (th, tw), "numel": n_el, "x": x3d, "dec_mask": dec_mask,
-               "seeds": sh.copy(), "lazy": lazy, "k1_mask": k1_mask}
+               "seeds": sh.copy(), "lazy": lazy, "k1_mask": k1_mask,
+               "early": early_chunks, "early_ok": early_ok}
         self._open.append(enq)
         self.host_seconds["enqueue"] += time.perf_counter() - t_enq
         if trace:
@@ -465,6 +530,7 @@ class GreedyPipeline:
         k = {"pcc": 0, "mae": 1, "atol": 2}[self.metric]
         results: list[TensorResult] = []
         names = MIXED_TILE_FORMATS
+        largest_cand = 0
         for done, first, n in enq["pending"]:
             t0 = time.perf_counter()
             _sleep_until(done)
@@ -486,6 +552,17 @@ class GreedyPipeline:
             if enq.get("lazy"):
                 listed = int(b["n_listed_host"][first // self.chunk])
                 self.listed_tiles += listed
+                # the last pass's candidates per tensor: the tiles that end in one of the last two formats (a tensor the search handed back
+                # counts nothing).  A search that ended before its last pass had no candidate left for a pass — every tile was fixed at an
+                # earlier format — so it has no tile in a later one: such a tensor counts 0 here without a look at the device's `done`.
+                i_prev, i_last = names.index(self.tile_formats[-2]), names.index(self.tile_formats[-1])
+                cand = [0 if status[j] else counts[j][i_prev] + counts[j][i_last] for j in range(n)]
+                if enq["early"][first // self.chunk] > 0:
+                    early = max(sum(cand) - listed, 0)          # what K1 had finished: the candidates that stayed off the list
+                    self.early_tiles += early
+                    listed += early
+                if enq["early_ok"]:
+                    largest_cand = max(largest_cand, max(cand))
                 if listed > self.lazy_max_listed * n * th * tw:
                     self.lazy_off.setdefault(th * tw, listed / float(n * th * tw))
             for j in bad:   # handed back by the device scan: the host scan on this tensor's records
@@ -505,7 +582,12 @@ class GreedyPipeline:
             self.host_seconds["wait"] += t1 - t0
             self.host_seconds["wrap"] += time.perf_counter() - t1
             if settings().pipe_trace:
-                print(f"[pipe] finish {n} x {th * tw}: waited {1e3 * (t1 - t0):.2f} ms, wrapped in {1e3 * (time.perf_counter() - t1):.2f} ms, handed back {bad.size}", flush=True)
+                spread = ""
+                if enq.get("lazy"):
+                    spread = f", last-pass candidates per tensor {min(cand)}..{max(cand)}, cutoff {enq['early'][first // self.chunk]}, listed {int(b['n_listed_host'][first // self.chunk])}"
+                print(f"[pipe] finish {n} x {th * tw}: waited {1e3 * (t1 - t0):.2f} ms, wrapped in {1e3 * (time.perf_counter() - t1):.2f} ms, handed back {bad.size}{spread}", flush=True)
+        if enq.get("early_ok") and len(set(int(v) for v in enq["seeds"])) == 1:
+            self.early_cutoff.learn(th * tw, self.tile_formats, self.metric, self.threshold, int(enq["seeds"][0]), largest_cand)
         self._open.pop(0)
         enq["x"] = None
         return results

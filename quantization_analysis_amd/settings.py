@@ -6,7 +6,8 @@ MEASUREMENT switches: A/B levers of experiments recorded in DESIGN.md / profiles
 MTQ_K1_UNITS_PER_WAVE x MTQ_K1_WAVES (every regime of the K1 grid), MTQ_K1_LDS_PAD, MTQ_LISTED_WAVES and MTQ_LISTED_DIRECT each run
 tests/k1_claim_cases.py in a process of their own (tests/test_k1_work_claim_gpu.py::test_geometry_switches_in_fresh_processes; the
 grid arithmetic at other CU counts: tests/test_k1_grid_host.py); MTQ_FORCE_GENERIC: test_pipeline_under_force_generic_switch;
-MTQ_LAZY / MTQ_K1_TWO_LAUNCH: test_lazy_pipeline_equals_whole_record_pipeline; MTQ_KNIFE_CAP: test_threshold_ragged_groups
+MTQ_LAZY / MTQ_K1_TWO_LAUNCH: test_lazy_pipeline_equals_whole_record_pipeline; MTQ_EARLY: every cutoff against MTQ_LAZY=0
+(tests/test_early_route_gpu.py); MTQ_KNIFE_CAP: test_threshold_ragged_groups
 (all tests/test_hip_kernels.py).  The other switches have no test that sets them: their defaults are what the suite runs.
 
 Python side (this module)
@@ -24,6 +25,8 @@ Python side (this module)
 | MTQ_SHARED_ORDERS | 1 | one set of visiting orders per (seed, tile count), cached across batches |
 | MTQ_LAZY | 1 | lazy route: K1 <3,1>, listed completion before the last pass |
 | MTQ_LAZY_MAX_LISTED | 0.35 | listed fraction above which a tile count leaves the lazy route |
+| MTQ_EARLY | 1 | lazy route: K1 finishes the tiles predicted to reach the last pass in place (rank below the previous batch's cutoff) |
+| MTQ_EARLY_MARGIN | 0.02 | the cutoff: the previous batch's largest per-tensor last-pass candidate count times 1 + this |
 | MTQ_IDENTITY_RECORDS | 1 | bf16 storage: no record slot for the identity bf16 candidate |
 | MTQ_SLIM_RECORDS | 1 | host-scan route, pcc: 3 doubles per format cross PCIe |
 | MTQ_K1_TWO_LAUNCH | 1 | K1 and its literal fix-up as two launches on two streams |
@@ -79,6 +82,8 @@ class Settings:
     shared_orders: bool
     lazy: bool
     lazy_max_listed: float
+    early: bool
+    early_margin: float
     identity_records: bool
     slim_records: bool
     k1_two_launch: bool
@@ -102,7 +107,8 @@ def settings(refresh: bool = False) -> Settings:
             pipe_slots=_int("MTQ_PIPE_SLOTS", 4), scan_streams=_int("MTQ_SCAN_STREAMS", None), scan_priority=_int("MTQ_SCAN_PRIORITY", -1),
             chunk_tasks=_int("MTQ_CHUNK_TASKS", 8), scan_workers=_int("MTQ_SCAN_WORKERS", None), device_scan=_flag("MTQ_DEVICE_SCAN", True),
             device_scan_max_tiles=_int("MTQ_DEVICE_SCAN_MAX_TILES", None), shared_orders=_flag("MTQ_SHARED_ORDERS", True), lazy=_flag("MTQ_LAZY", True),
-            lazy_max_listed=float(os.environ.get("MTQ_LAZY_MAX_LISTED", "0.35")), identity_records=_flag("MTQ_IDENTITY_RECORDS", True),
+            lazy_max_listed=float(os.environ.get("MTQ_LAZY_MAX_LISTED", "0.35")), early=_flag("MTQ_EARLY", True),
+            early_margin=float(os.environ.get("MTQ_EARLY_MARGIN", "0.02")), identity_records=_flag("MTQ_IDENTITY_RECORDS", True),
             slim_records=_flag("MTQ_SLIM_RECORDS", True), k1_two_launch=_flag("MTQ_K1_TWO_LAUNCH", True), knife_cap=_int("MTQ_KNIFE_CAP", 128), threshold_ragged=_flag("MTQ_THRESHOLD_RAGGED", True),
             sweep_threads=_int("MTQ_SWEEP_THREADS", None), wq_max_slots=_int("MTQ_WQ_MAX_SLOTS", 8),
             wq_device_scan_max_tiles=_int("MTQ_WQ_DEVICE_SCAN_MAX_TILES", 1 << 22), pipe_trace=os.environ.get("MTQ_PIPE_TRACE") == "1",

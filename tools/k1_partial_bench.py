@@ -1,6 +1,13 @@
 """K1 with partial records (mtq_tile_stats_partial): the promised statistics against a full launch's, bit for bit, and the timing of
-both on N 4096x4096 bf16 tensors (HIP events).  python tools/k1_partial_bench.py [n] [reps] [layout] [full] [sums]"""
+both on N 4096x4096 bf16 tensors (HIP events).  python tools/k1_partial_bench.py [n] [reps] [layout] [full] [sums] [--early FRACTION]
+--early: also the early form (mtq_tile_stats_partial_begin_early / _end) with seed 123's rank table at cutoff FRACTION x tiles: its early
+tiles against the full launch, every column, and its timing (the launch a counter run of this tool then sees beside the others)."""
 import sys
+early = None
+if "--early" in sys.argv:
+    at = sys.argv.index("--early")
+    early = float(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
 sys.path.insert(0, '/root/repo')
 import torch
 from quantization_analysis_amd import hip_backend as hb
@@ -48,7 +55,27 @@ def timeit(fn):
 
 
 tiles = n * 128 * 128
-for name, fn in (("full   ", lambda: hb.tile_stats_batched(x, layout, out=ref)), ("partial", lambda: hb.tile_stats_partial(x, layout, full, sums, out=got))):
+runs = [("full   ", lambda: hb.tile_stats_batched(x, layout, out=ref)), ("partial", lambda: hb.tile_stats_partial(x, layout, full, sums, out=got))]
+if early is not None:
+    T = 128 * 128
+    cutoff = int(early * T)
+    rank_host = hb.early_rank_host(123, T)
+    rank = torch.from_numpy(rank_host.view('int32')).cuda()
+    mark = torch.zeros((1,), dtype=torch.int32, device='cuda')
+    eout = torch.empty_like(got)
+
+    def early_launch():
+        lid = hb.tile_stats_partial_begin_early(x, layout, full, sums, eout, mark, rank, cutoff)
+        hb.tile_stats_partial_end(x, layout, eout, mark, lid)
+
+    early_launch()
+    torch.cuda.synchronize()
+    sel = torch.from_numpy(rank_host < cutoff).cuda()
+    ebad = (eout.view(torch.int64)[:, sel] != r[:, sel]).sum().item() + (eout.view(torch.int64)[..., cols] != r[..., cols]).sum().item()
+    print(f"early form, cutoff {cutoff} of {T} tiles per tensor: {int(sel.sum().item())} early tiles per tensor, {ebad} differing values")
+    bad += ebad
+    runs.append((f"early {early:.3f}", early_launch))
+for name, fn in runs:
     ms, mn = timeit(fn)
     print(f"K1 {name} n={n}: median {ms:.3f} ms  min {mn:.3f} ms  {tiles / ms / 1e6 * 1e3:.1f} M tiles/s  frac {2048 * tiles / ms / 1e6 / 8000:.4f}")
 sys.exit(1 if bad else 0)
