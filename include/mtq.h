@@ -348,6 +348,27 @@ int mtq_gptq_sweep(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw
                    size_t code_count, float *out, int64_t ldo, double *loss, double *scratch, size_t scratch_doubles, void *stream);
 
 /*
+ * GPTQ's factor on the device — U, the upper Cholesky factor of H_d⁻¹, from the damped Hessian H_d (the step between the two above;
+ * gptq.factor is its host counterpart).  H_d = R·Rᵀ with R upper triangular (a Cholesky factorisation from the bottom-right corner
+ * upwards), then U = R⁻¹: UᵀU = H_d⁻¹, U upper triangular with a positive diagonal.  Blocked by MTQ_GPTQ_FACTOR_BLOCK, float64
+ * throughout (v_mfma_f64_16x16x4_f64 for the panel, the trailing update and the blocked inverse; correctly rounded sqrt and division on
+ * the diagonal blocks).
+ * hd: device doubles k × k, row-major, symmetric; only its UPPER triangle (i <= j) is read.  u: device doubles k × k (u_doubles = k · k),
+ * receives U with zeros below the diagonal.  status: one device int32; 0 = done, j + 1 = the pivot of row/column j (hd's own numbering)
+ * was not positive and finite.  The factorisation runs from the last index to the first, so the pivot of index j is the Schur
+ * complement over the indices ABOVE j (not the leading minor of LAPACK's info), and a failure names the LARGEST failing index; u is
+ * then unspecified (the failed pivot is replaced by 1 and the launches run to their end: no trip count depends on the data).
+ * scratch: device doubles, 16-byte aligned, at least mtq_gptq_factor_scratch_doubles(k) (a padded work matrix and the inverted
+ * diagonal blocks; 0 for a k the entry refuses).  Everything is enqueued on `stream`, a few launches per block, ordered by the stream
+ * alone; nothing is read back.  Deterministic: no float atomics, equal inputs give equal bits.  A null pointer, k <= 0, k > 2^17,
+ * u_doubles != k · k, a short or misaligned scratch returns MTQ_ERR_INVALID before a device is looked for.  csrc/mtq_gptq_factor.hip.
+ */
+#define MTQ_GPTQ_FACTOR_BLOCK 64
+size_t mtq_gptq_factor_scratch_doubles(int64_t k);
+int mtq_gptq_factor(const double *hd, int64_t k, double *u, size_t u_doubles, int32_t *status, double *scratch, size_t scratch_doubles,
+                    void *stream);
+
+/*
  * K5 dequant_fp8_block (loader) — float8-e4m3fn weights × float32 inverse block scales → float32: the on-load
  * dequantisation of DeepSeek-style checkpoints, `w.float() * scale_inv.repeat_interleave(block)` with
  * block = ceil(dim / scale_dim) (hf_model_utils.py:199-215, used at :273-281).  w: rows × cols bytes (ldw),

@@ -9,7 +9,9 @@ Hessian (host, float64, shared by both backends):
   2. a dead column (H_jj == 0) gets H_jj := 1; W is NOT zeroed there (unlike reference GPTQ): with nothing to compensate, a dead
      column is rounded like RTN;
   3. λ = damp · mean(diag H) (damp finite and > 0, 0.01 by default), H_d = H + λI;
-  4. U = the upper Cholesky factor of H_d⁻¹, from torch float64 on the host (CPU LAPACK) for both backends.
+  4. U = the upper Cholesky factor of H_d⁻¹: `factor`, torch float64 on the host (CPU LAPACK), the default of both backends; or
+     `factor_hip`, on the device (hip backend, opt-in): H_d = R·Rᵀ with R upper triangular, U = R⁻¹, the same matrix by uniqueness
+     of the Cholesky factor, within rounding (H_d itself is bit-identical: same dead columns, same λ).
   No candidate is made (a reason is returned instead) when the calibration holds no tokens or a Cholesky factorisation fails.
 
 Fixed-exponent element rule q_E(x, f) of a float64 value x:
@@ -32,7 +34,10 @@ distance of the float64 value decided to the nearest value that would change tha
 group's BFP step or its bf16 ulp).  Two routes that agree within a small fraction of a step give the same row where it is clear.
 
 Backends: emulation — NumPy / torch float64 on the host, the oracle of the GPU tests; hip — csrc/mtq_gptq.hip (mtq_gram_full per
-chunk, the host factorisation, then mtq_gptq_sweep on the device).
+chunk, then the factorisation, then mtq_gptq_sweep on the device).  The factorisation is `factor` on the host (H goes down, U comes
+up) or, with factor="device", `factor_hip`: csrc/mtq_gptq_factor.hip (mtq_gptq_factor), where only H's diagonal and one status word
+are read back.  It is deterministic (equal H, equal bits of U); a pivot that is not positive and finite is named by its index in H,
+the largest failing one, since that route factorises from the last index upwards.
 """
 from __future__ import annotations
 
@@ -243,6 +248,34 @@ def factor(h, damp: float = DEFAULT_DAMP) -> Union[np.ndarray, str]:
     if int(info) != 0 or not bool(torch.isfinite(U).all()):
         return "Cholesky factorisation of the inverse damped Hessian failed"
     return U.numpy()
+
+
+def factor_hip(h, damp: float = DEFAULT_DAMP):
+    """`factor` on the device: h a float64 (k, k) device tensor → U as a float64 (k, k) device tensor (zeros below the diagonal), or
+    the reason there is none.  Only h's diagonal (for the dead columns and λ, by damped_hessian's own expressions) and the status word
+    cross to the host."""
+    import torch
+
+    from . import hip_backend as hb
+
+    damp = check_damp(damp)
+    if h.dim() != 2 or h.shape[0] != h.shape[1] or h.dtype != torch.float64 or not h.is_cuda:
+        raise ValueError(f"h must be a square float64 device tensor, got {tuple(h.shape)} {h.dtype}")
+    idx = np.arange(h.shape[0])
+    d = h.diagonal().cpu().numpy().copy()
+    dead = d == 0.0
+    d[idx[dead]] = 1.0
+    lam = damp * float(np.mean(d))
+    d += lam
+    hd = h.clone()
+    hd.diagonal().copy_(torch.from_numpy(d).to(h.device))
+    if not bool(torch.isfinite(hd).all()):
+        return "the calibration Hessian holds a non-finite value"
+    u, status = hb.gptq_factor(hd)
+    bad = int(status.cpu()[0])
+    if bad != 0:
+        return f"factorisation of the damped Hessian failed on the device (pivot of index {bad - 1}, taken over the indices above it, is not positive)"
+    return u
 
 
 # ----------------------------------------------------------------------------- sweep

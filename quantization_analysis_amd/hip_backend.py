@@ -108,6 +108,8 @@ SIGNATURES = {
     "mtq_gram_full": ("i", "plllpzpzp", True),
     "mtq_gptq_sweep_scratch_doubles": ("z", "ll", True),
     "mtq_gptq_sweep": ("i", "pilllpzpzplppzp", True),
+    "mtq_gptq_factor_scratch_doubles": ("z", "l", True),
+    "mtq_gptq_factor": ("i", "plpzppzp", True),
     "mtq_output_error_transposed": ("i", "plllpillpuppilppzppl", True),
     "mtq_tile_error_tables_transposed": ("i", "pilllpzppzp", True),
     "mtq_tile_sq_error_batched": ("i", "pilllllpp", True),
@@ -1011,6 +1013,35 @@ def gptq_sweep(w, u, codes, out=None, loss=None):
     check(fn(w.data_ptr(), w_code, n, k, ldw, u.data_ptr(), u.numel(), codes.data_ptr(), codes.numel(), out.data_ptr(), out.stride(0),
              loss.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream_ptr()))
     return out, loss
+
+
+GPTQ_FACTOR_BLOCK = 64   # include/mtq.h MTQ_GPTQ_FACTOR_BLOCK: the block size of mtq_gptq_factor
+
+
+def gptq_factor(hd, u=None):
+    """GPTQ's factor (mtq_gptq_factor) on the current stream → (U float64 (k, k), status int32 (1,)) device tensors: U is the upper
+    Cholesky factor of hd⁻¹ with zeros below the diagonal.  hd: contiguous float64 (k, k) device tensor, symmetric (its upper triangle
+    is read).  status 0 = done; j + 1 = the pivot of index j, the Schur complement over the indices above j, was not positive and
+    finite (the largest such index), and U is then unspecified.  Nothing is read back here."""
+    torch = _torch()
+    if hd.dim() != 2 or hd.shape[0] != hd.shape[1] or hd.shape[0] < 1:
+        raise MtqError(f"hd must be a square (k, k) matrix with k >= 1, got {tuple(hd.shape)}")
+    k = int(hd.shape[0])
+    if hd.dtype != torch.float64 or not hd.is_contiguous() or not hd.is_cuda:
+        raise MtqError(f"hd must be a contiguous float64 device tensor of shape ({k}, {k})")
+    if u is None:
+        u = torch.empty((k, k), dtype=torch.float64, device=hd.device)
+    elif u.dtype != torch.float64 or tuple(u.shape) != (k, k) or not u.is_contiguous() or not u.is_cuda or u.device != hd.device:
+        raise MtqError(f"u must be a contiguous float64 tensor of shape ({k}, {k}) on hd's device")
+    require_gpu()
+    fn = _entry("mtq_gptq_factor")
+    need = int(_entry("mtq_gptq_factor_scratch_doubles")(k))
+    if need == 0:
+        raise MtqError(f"mtq_gptq_factor takes no matrix of {k} columns")
+    scratch = torch.empty((need,), dtype=torch.float64, device=hd.device)
+    status = torch.empty((1,), dtype=torch.int32, device=hd.device)
+    check(fn(hd.data_ptr(), k, u.data_ptr(), u.numel(), status.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream_ptr()))
+    return u, status
 
 
 def apply_assignment(x2d, assignment, out=None):

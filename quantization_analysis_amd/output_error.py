@@ -300,14 +300,15 @@ def rows_from_sums(sums: np.ndarray, m: int, n: int, k: int, formats, map_cand: 
 
 def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation", chunk_rows: int = 16384,
                 x_format: str = "bf16", budgets=(), calib: Optional[OpIO] = None, gptq: bool = False, gptq_damp: float = 0.01,
-                transpose: bool = False) -> OpResult:
+                transpose: bool = False, gptq_factor: str = "host") -> OpResult:
     """One op of `select_ops` → its rows (or the reason it is skipped).  formats ⊆ SUPPORTED_FORMATS; config: a CompressionConfig
     whose mixed-tile algorithm adds the map candidate (None = pure formats only); x_format: the candidates' activation format.
     budgets: bits per weight, each adding the maps budget:<bits>:output and budget:<bits>:weight (budget_maps.py) chosen on the
     calibration activations `calib` (an OpIO of the same op) and evaluated here, after the other rows; bf16 x_format only.
     gptq: adds, after those, the error-compensated weights (gptq.py) built on `calib` with damp gptq_damp: gptq:<f> for each of bfp8 /
     bfp4 / bfp2 among the formats, gptq:<map name> for the config's map and gptq:budget:<bits>:output for each budget map, each with the
-    bytes of its round-to-nearest counterpart; bf16 x_format only.
+    bytes of its round-to-nearest counterpart; bf16 x_format only.  gptq_factor: "host" (gptq.factor, CPU LAPACK) or "device"
+    (gptq.factor_hip, hip backend only: H and U stay on the device).
     transpose: adds <f>+transpose for each of bfp8 / bfp4 / bfp2 among the formats and, with budgets, budget:<bits>:<basis>+transpose
     (implied by a config with the transpose algorithm); a config with "layout": "transpose" gives a map over Wᵀ's grid."""
     if backend not in BACKENDS:
@@ -327,6 +328,7 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
         if x_format != "bf16":
             raise ValueError("GPTQ weights are built and evaluated on bf16 activations: x_format must be bf16")
         check_damp(gptq_damp)
+        check_gptq_factor(gptq_factor, backend)
     check_layout(config, LAYOUTS)
     transpose = bool(transpose) or (config is not None and config.algorithm == "transpose")
     bad = [f for f in formats if f not in SUPPORTED_FORMATS]
@@ -367,7 +369,7 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
     if budgets:
         _budget_rows(res, index, op, w, bias, formats, backend, chunk_rows, budgets, calib, transpose)
     if gptq:
-        _gptq_rows(res, op, w, bias, formats, map_cand, backend, chunk_rows, budgets, calib, gptq_damp, transpose)
+        _gptq_rows(res, op, w, bias, formats, map_cand, backend, chunk_rows, budgets, calib, gptq_damp, transpose, gptq_factor)
     return res
 
 
@@ -438,14 +440,26 @@ def _gptq_outputs(chunk_iter: Iterable, what, bias):
         yield Chunk(x=ch.x, recorded=y, cast=ch.cast)
 
 
+GPTQ_FACTORS = ("host", "device")
+
+
+def check_gptq_factor(factor: str, backend: str) -> None:
+    if factor not in GPTQ_FACTORS:
+        raise ValueError(f"factor must be one of {', '.join(GPTQ_FACTORS)}, got {factor!r}")
+    if factor == "device" and backend != "hip":
+        raise ValueError("factor='device' is the hip backend's factorisation kernel: the emulation backend has only 'host'")
+
+
 def _gptq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[MapCandidate], backend: str, chunk_rows: int, budgets,
-               calib: Optional[OpIO], damp: float, transpose: bool = False) -> None:
-    """Appends the GPTQ rows to res: one Gram matrix and one host factorisation per op, one sweep and one LOE pass (Ŵ as the weight)
+               calib: Optional[OpIO], damp: float, transpose: bool = False, factor: str = "host") -> None:
+    """Appends the GPTQ rows to res: one Gram matrix and one factorisation per op (factor: on the host, or "device": on the hip
+    backend's device, where neither H nor U crosses to the host), one sweep and one LOE pass (Ŵ as the weight)
     per candidate; or records in res.budget_skipped why a candidate was not made.  Row layout only: every transposed candidate is
     listed in res.budget_skipped, and no map over Wᵀ's grid reaches a sweep."""
     from . import budget_maps as bm
     from . import gptq as gq
 
+    check_gptq_factor(factor, backend)
     n, k = res.shape
     row_only = "GPTQ is row-layout only: a transposed candidate has no GPTQ counterpart"
     if transpose:
@@ -473,12 +487,13 @@ def _gptq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[Map
         cal = chunks(calib, k, n, chunk_rows)
         if backend == "hip":
             h, m_cal = gq.gram_full_hip(cal, k, device=w.device)
-            h = h.cpu().numpy()
+            if factor == "host":
+                h = h.cpu().numpy()
         else:
             h, m_cal = gq.gram_full_emulation(cal, k)
         why = "the calibration samples hold no tokens" if not m_cal else None
     if why is None:
-        u = gq.factor(h, damp)
+        u = gq.factor_hip(h, damp) if factor == "device" else gq.factor(h, damp)
         if isinstance(u, str):
             why = u
     if why is not None:
@@ -487,7 +502,7 @@ def _gptq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[Map
     if backend == "hip":
         import torch
 
-        ud = torch.from_numpy(u).to(w.device)
+        ud = u if factor == "device" else torch.from_numpy(u).to(w.device)
     for name, codes, nbytes in cands:
         it = (Chunk(x=ch.x, cast=ch.cast) for ch in chunks(op, k, n, chunk_rows))   # Ŵ's slot alone: no recorded output
         if backend == "hip":

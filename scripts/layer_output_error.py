@@ -62,10 +62,14 @@ def parse_args(argv=None):
     p.add_argument("--gptq", action="store_true",
                    help="Add GPTQ error-compensated weights built on the calibration activations: gptq:<bfp*>, gptq:<map>, gptq:budget:<B>:output.")
     p.add_argument("--gptq-damp", type=float, default=0.01, metavar="D", help="GPTQ damping: λ = D · mean(diag H) (finite, > 0).")
+    p.add_argument("--gptq-factor", choices=("host", "device"), default="host",
+                   help="Where GPTQ factorises the damped Hessian: host (CPU LAPACK) or device (the hip backend's float64 MFMA kernels).")
     args = p.parse_args(argv)
     if args.gptq:
         if args.x_format != "bf16":
             p.error("--gptq needs --x-format bf16: the GPTQ weights are built and evaluated on bf16 activations")
+    if args.gptq_factor == "device" and args.backend != "hip":
+        p.error("--gptq-factor device needs --backend hip: the emulation factorises on the host")
     if not (math.isfinite(args.gptq_damp) and args.gptq_damp > 0.0):
         p.error(f"--gptq-damp: {args.gptq_damp:g} is not finite and > 0")
     if args.budget_bits:
@@ -106,7 +110,7 @@ def main(argv=None) -> int:
     for op in ops:
         extra = {"budgets": budgets, "calib": calib.get(op.op)} if budgets or args.gptq else {}
         if args.gptq:
-            extra.update(gptq=True, gptq_damp=args.gptq_damp)
+            extra.update(gptq=True, gptq_damp=args.gptq_damp, gptq_factor=args.gptq_factor)
         if transpose:
             extra.update(transpose=True)
         res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows, args.x_format, **extra)
@@ -153,7 +157,7 @@ def main(argv=None) -> int:
     if budgets or args.gptq:
         doc.update({"calib_io": calib_io, "calib_split": args.calib_split, "calib_max_samples": args.calib_max_samples})
     if args.gptq:
-        doc.update({"gptq_damp": args.gptq_damp})
+        doc.update({"gptq_damp": args.gptq_damp, "gptq_factor": args.gptq_factor})
     if transpose:
         doc.update({"transpose": True})
     (out_dir / "layer_output_error.json").write_text(json.dumps(doc, indent=2))

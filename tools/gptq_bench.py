@@ -2,7 +2,10 @@
 
   gram  : mtq_gram_full over m = --tokens bf16 N(0, 1) tokens for k = 7168 and 18432; bound = m·k² bf16 MFMA flop (half of 2·m·k², the
           symmetric half) at --mfma-tflops.
-  factor: gptq.factor (torch float64 Cholesky, inverse, Cholesky on the host) for k = 7168 (--factor-k).
+  factor: gptq.factor (torch float64 Cholesky, inverse, Cholesky on the host) for each k of --factor-k (7168 by default).
+  factor_device: gptq.factor_hip (mtq_gptq_factor, csrc/mtq_gptq_factor.hip) on the same H for k = 7168 and 18432; bound = 2k³/3 float64
+          flop (the factorisation and the triangular inverse, k³/3 each) at --fp64-tflops; with the host U of the same run, the
+          largest difference over max|U|.
   sweep : mtq_gptq_sweep for n × k = 7168 × 7168 and 7168 × 18432 on an upper-triangular U; bound = n·k²/2 float64 FMA at --fp64-tflops.
 Wall-clock times of the best of --reps calls after a warm-up; run under `rocprofv3 --kernel-trace --stats` for kernel times.
 
@@ -41,7 +44,7 @@ def main() -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--tokens", type=int, default=16384)
     p.add_argument("--reps", type=int, default=3)
-    p.add_argument("--factor-k", type=int, default=7168)
+    p.add_argument("--factor-k", type=int, nargs="*", default=[7168], help="sizes at which the host factorisation is timed (once each)")
     p.add_argument("--mfma-tflops", type=float, default=2500.0, help="dense bf16 MFMA peak used for the Gram bound")
     p.add_argument("--fp64-tflops", type=float, default=78.6, help="float64 vector peak used for the sweep bound")
     p.add_argument("--json", default=None)
@@ -57,12 +60,33 @@ def main() -> int:
         out.append({"what": "gram_full", "m": args.tokens, "k": k, "ms": t * 1e3, "bound_ms": bound * 1e3, "fraction": bound / t})
         print(json.dumps(out[-1]), flush=True)
         del x, h, scratch
-    xk = torch.randn((4096, args.factor_k), dtype=torch.float64)
-    hh = (xk.T @ xk).numpy()
-    t0 = time.perf_counter()
-    u = gq.factor(hh)
-    out.append({"what": "factor", "k": args.factor_k, "s": time.perf_counter() - t0, "ok": not isinstance(u, str)})
-    print(json.dumps(out[-1]), flush=True)
+    for k in (7168, 18432):
+        g = torch.Generator(device="cuda").manual_seed(k)
+        xk = torch.randn((4096, k), generator=g, device="cuda", dtype=torch.float64)
+        hd = xk.T @ xk
+        del xk
+        u_host = None
+        if k in args.factor_k:
+            hh = hd.cpu().numpy()
+            t0 = time.perf_counter()
+            u_host = gq.factor(hh)
+            out.append({"what": "factor", "k": k, "s": time.perf_counter() - t0, "ok": not isinstance(u_host, str)})
+            print(json.dumps(out[-1]), flush=True)
+            del hh
+        res = [None]
+
+        def run():
+            res[0] = gq.factor_hip(hd)          # ends in its one read-back, the status word
+
+        t = _time(run, args.reps)
+        bound = 2.0 * k ** 3 / 3.0 / (args.fp64_tflops * 1e12)
+        row = {"what": "factor_device", "k": k, "ms": t * 1e3, "bound_ms": bound * 1e3, "fraction": bound / t, "ok": not isinstance(res[0], str)}
+        if row["ok"] and u_host is not None and not isinstance(u_host, str):
+            row["max_diff_over_max_u"] = float(np.abs(res[0].cpu().numpy() - u_host).max() / np.abs(u_host).max())
+            row["host_over_device"] = out[-1]["s"] / t
+        out.append(row)
+        print(json.dumps(out[-1]), flush=True)
+        del hd, res, u_host
     n = 7168
     for k in (7168, 18432):
         g = torch.Generator(device="cuda").manual_seed(k)
