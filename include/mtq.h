@@ -348,6 +348,20 @@ int mtq_gptq_sweep(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw
                    size_t code_count, float *out, int64_t ldo, double *loss, double *scratch, size_t scratch_doubles, void *stream);
 
 /*
+ * The sweep in the transposed BFP layout — a shared-exponent group is 16 consecutive rows (16g .. 16g + 15, rows >= n count as +0) of
+ * one column, so rows are no longer independent.  For j = 0 .. k − 1 in order and every group: E = the maximum exponent field of
+ * float32 of the group's CURRENT column j, q = q_E(w_rj, f), e_rj = (w_rj − q) / U_jj, w_rj' −= e_rj · U_jj' for j' > j; E is the
+ * exponent of the values actually quantised, so Ŵ is a fixed point of the transposed quantiser (mtq_quantize_transposed /
+ * mtq_apply_assignment_transposed) up to the sign of zero.  The arguments are mtq_gptq_sweep's, except that codes is over Wᵀ's tile
+ * grid: int8 [ceil(k/32)][ceil(n/32)], element (r, j) of W takes codes[j / 32][r / 32] (code_count = ceil(k/32) · ceil(n/32)), the
+ * indexing of mtq_tile_error_tables_transposed.  scratch: at least mtq_gptq_sweep_scratch_doubles(n, k), which serves both sweeps.  The
+ * same checks in the same order; deterministic (no float atomics).  csrc/mtq_gptq_transpose.hip.
+ */
+int mtq_gptq_sweep_transposed(const void *w, int w_dtype, int64_t n, int64_t k, int64_t ldw, const double *u, size_t u_doubles,
+                              const int8_t *codes, size_t code_count, float *out, int64_t ldo, double *loss, double *scratch,
+                              size_t scratch_doubles, void *stream);
+
+/*
  * GPTQ's factor on the device — U, the upper Cholesky factor of H_d⁻¹, from the damped Hessian H_d (the step between the two above;
  * gptq.factor is its host counterpart).  H_d = R·Rᵀ with R upper triangular (a Cholesky factorisation from the bottom-right corner
  * upwards), then U = R⁻¹: UᵀU = H_d⁻¹, U upper triangular with a positive diagonal.  Blocked by MTQ_GPTQ_FACTOR_BLOCK, float64

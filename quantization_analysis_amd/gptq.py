@@ -33,8 +33,22 @@ Margin (emulation only): per row, over the decisions it makes (each BFP group's 
 distance of the float64 value decided to the nearest value that would change that decision, divided by the element's step (its
 group's BFP step or its bf16 ulp).  Two routes that agree within a small fraction of a step give the same row where it is clear.
 
+Transposed layout (sweep_emulation_transposed, sweep_hip_transposed; the same H, U and q_E): a shared-exponent group is 16 consecutive
+rows of one column, rows 16g .. 16g + 15 with rows ≥ n counting as zeros, and `codes_t` is int8 [ceil(k/32), ceil(n/32)] over Wᵀ's tile
+grid: element (r, j) of W takes codes_t[j // 32, r // 32], the indexing of the transposed tile tables and of every +transpose map.  For
+j = 0 .. k−1 in order and every group g:
+  1. E_g = the maximum exponent field of float32 of the group's CURRENT column j;
+  2. q_rj = q_E(w_rj, f);
+  3. e_rj = (w_rj − q_rj) / U_jj;
+  4. w_rj' −= e_rj · U_jj' for every j' > j.
+  Ŵ = q and loss_r = Σ_j e_rj², per row as above.  All 16 values of a group are final at the step that quantises them, so E is the
+  exponent of the values actually quantised: q_E is the literal rule with no stale exponent and no saturation, and Ŵ is a fixed point
+  of the transposed quantiser (up to the sign of zero).  The rows of a group meet at every column through E, so the margin is per
+  16-row group: the minimum over the group's rows and columns of the level margins, and of the exponent margin of each column group.
+
 Backends: emulation — NumPy / torch float64 on the host, the oracle of the GPU tests; hip — csrc/mtq_gptq.hip (mtq_gram_full per
-chunk, then the factorisation, then mtq_gptq_sweep on the device).  The factorisation is `factor` on the host (H goes down, U comes
+chunk, then the factorisation, then mtq_gptq_sweep on the device; mtq_gptq_sweep_transposed, csrc/mtq_gptq_transpose.hip, for the
+transposed layout).  The factorisation is `factor` on the host (H goes down, U comes
 up) or, with factor="device", `factor_hip`: csrc/mtq_gptq_factor.hip (mtq_gptq_factor), where only H's diagonal and one status word
 are read back.  It is deterministic (equal H, equal bits of U); a pivot that is not positive and finite is named by its index in H,
 the largest failing one, since that route factorises from the last index upwards.
@@ -64,6 +78,11 @@ def check_damp(damp) -> float:
 
 def constant_codes(n: int, k: int, fmt: str) -> np.ndarray:
     return np.full((-(-n // TILE), -(-k // TILE)), MIXED_TILE_FORMATS.index(fmt), dtype=np.int8)
+
+
+def constant_codes_transposed(n: int, k: int, fmt: str) -> np.ndarray:
+    """The constant map of an n × k weight over Wᵀ's tile grid."""
+    return constant_codes(k, n, fmt)
 
 
 # ----------------------------------------------------------------------------- element rule
@@ -329,17 +348,76 @@ def sweep_emulation(w, u, codes, block: int = 128) -> tuple[np.ndarray, np.ndarr
     return q, loss, margin
 
 
-def sweep_hip(w, u, codes):
-    """mtq_gptq_sweep on the device → (Ŵ float32 device tensor n × k, loss float64 device tensor [n])."""
-    import torch
+def sweep_emulation_transposed(w, u, codes_t, block: int = 128) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The transposed-layout sweep on the host in float64 → (Ŵ float32 n × k, loss float64 [n], margin float64 [ceil(n/16)])."""
+    w32 = _w32(w)
+    n, k = w32.shape
+    U = np.asarray(u.cpu().numpy() if hasattr(u, "cpu") else u, dtype=np.float64)
+    if U.shape != (k, k):
+        raise ValueError(f"u has shape {U.shape}, expected ({k}, {k})")
+    U = np.triu(U)
+    c = np.asarray(codes_t, dtype=np.int8)
+    if c.shape != (-(-k // TILE), -(-n // TILE)):
+        raise ValueError(f"codes_t has shape {c.shape}, expected {(-(-k // TILE), -(-n // TILE))}")
+    if c.size and (c.min() < 0 or c.max() >= len(MIXED_TILE_FORMATS)):
+        raise ValueError("codes_t must be MIXED_TILE_FORMATS codes 0..3")
+    groups = -(-n // GROUP)
+    ccol = np.repeat(c.astype(np.int64), TILE, axis=1)[:, :groups * GROUP]      # [tk, rows]: a group lies in one tile, so has one code
+    W = np.zeros((groups * GROUP, k), dtype=np.float64)                          # rows ≥ n: zeros, which never raise a maximum
+    W[:n] = w32
+    q = np.zeros((n, k), dtype=np.float32)
+    err = np.zeros((groups * GROUP, k), dtype=np.float64)
+    loss = np.zeros(n, dtype=np.float64)
+    margin = np.full(groups, np.inf)
+    real = (np.arange(groups * GROUP) < n).reshape(groups, GROUP)
+    mant = np.array([0, 7, 3, 1], dtype=np.int64)
+    for b0 in range(0, k, block):
+        b1 = min(k, b0 + block)
+        for j in range(b0, b1):
+            f = ccol[j // TILE]
+            x = W[:, j]
+            g = x.reshape(groups, GROUP)
+            Eg = group_exponent(g.astype(np.float32))
+            fg = f[::GROUP]
+            bfp = fg != 0
+            if bfp.any():
+                margin[bfp] = np.minimum(margin[bfp], _exponent_margin(g[bfp], Eg[bfp], mant[fg[bfp]]))
+            E = np.repeat(Eg, GROUP)
+            qj = q_fixed(x, f, E)
+            lm = np.where(real, _level_margin(x, qj, f, E).reshape(groups, GROUP), np.inf)
+            margin = np.minimum(margin, lm.min(axis=1))
+            e = (x - qj.astype(np.float64)) / U[j, j]
+            W[:, j + 1: b1] -= np.outer(e, U[j, j + 1: b1])
+            q[:, j] = qj[:n]
+            err[:, j] = e
+            loss += e[:n] * e[:n]
+        if b1 < k:
+            W[:, b1:] -= err[:, b0:b1] @ U[b0:b1, b1:]
+    return q, loss, margin
 
-    from . import hip_backend as hb
+
+def _sweep_hip(entry, w, u, codes):
+    import torch
 
     wd = w if w.dtype in (torch.bfloat16, torch.float32) else w.float()
     wd = wd if wd.stride(-1) == 1 else wd.contiguous()
     ud = u if hasattr(u, "is_cuda") and u.is_cuda else torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64)).to(wd.device)
     cd = torch.from_numpy(np.ascontiguousarray(codes, dtype=np.int8)).to(wd.device)
-    return hb.gptq_sweep(wd, ud.contiguous(), cd)
+    return entry(wd, ud.contiguous(), cd)
+
+
+def sweep_hip(w, u, codes):
+    """mtq_gptq_sweep on the device → (Ŵ float32 device tensor n × k, loss float64 device tensor [n])."""
+    from . import hip_backend as hb
+
+    return _sweep_hip(hb.gptq_sweep, w, u, codes)
+
+
+def sweep_hip_transposed(w, u, codes_t):
+    """mtq_gptq_sweep_transposed on the device (codes_t over Wᵀ's grid) → (Ŵ float32 device tensor n × k, loss float64 device tensor [n])."""
+    from . import hip_backend as hb
+
+    return _sweep_hip(hb.gptq_sweep_transposed, w, u, codes_t)
 
 
 def quadratic_loss(w, what, hd) -> np.ndarray:

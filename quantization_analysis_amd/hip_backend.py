@@ -108,6 +108,7 @@ SIGNATURES = {
     "mtq_gram_full": ("i", "plllpzpzp", True),
     "mtq_gptq_sweep_scratch_doubles": ("z", "ll", True),
     "mtq_gptq_sweep": ("i", "pilllpzpzplppzp", True),
+    "mtq_gptq_sweep_transposed": ("i", "pilllpzpzplppzp", True),
     "mtq_gptq_factor_scratch_doubles": ("z", "l", True),
     "mtq_gptq_factor": ("i", "plpzppzp", True),
     "mtq_output_error_transposed": ("i", "plllpillpuppilppzppl", True),
@@ -989,9 +990,19 @@ def gptq_sweep(w, u, codes, out=None, loss=None):
     """GPTQ's column sweep (mtq_gptq_sweep) on the current stream → (Ŵ float32 (n, k), loss float64 (n,)) device tensors.  w: (n, k)
     bf16 / float32 device tensor with contiguous rows; u: contiguous float64 (k, k) tensor on w's device (upper triangle read); codes:
     contiguous int8 (ceil(n/32), ceil(k/32)) device tensor of MIXED_TILE_FORMATS codes 0..3."""
+    return _gptq_sweep("mtq_gptq_sweep", False, w, u, codes, out, loss)
+
+
+def gptq_sweep_transposed(w, u, codes, out=None, loss=None):
+    """GPTQ's column sweep in the transposed BFP layout (mtq_gptq_sweep_transposed): gptq_sweep's arguments and results, except that
+    codes is over Wᵀ's tile grid, a contiguous int8 (ceil(k/32), ceil(n/32)) device tensor."""
+    return _gptq_sweep("mtq_gptq_sweep_transposed", True, w, u, codes, out, loss)
+
+
+def _gptq_sweep(entry, transposed, w, u, codes, out, loss):
     torch = _torch()
     w_code, _count, _stride, n, k, ldw = _matrix(w, (2,))
-    th, tw = tiles_hw(n, k)
+    th, tw = tiles_hw(k, n) if transposed else tiles_hw(n, k)
     if u.dtype != torch.float64 or tuple(u.shape) != (k, k) or not u.is_contiguous() or not u.is_cuda or u.device != w.device:
         raise MtqError(f"u must be a contiguous float64 tensor of shape ({k}, {k}) on w's device")
     if codes.dtype != torch.int8 or codes.numel() != th * tw or not codes.is_contiguous() or not codes.is_cuda or codes.device != w.device:
@@ -999,7 +1010,7 @@ def gptq_sweep(w, u, codes, out=None, loss=None):
     if codes.numel() and (int(codes.min()) < 0 or int(codes.max()) > 3):
         raise MtqError("codes must be MIXED_TILE_FORMATS codes 0..3")
     require_gpu()
-    fn = _entry("mtq_gptq_sweep")
+    fn = _entry(entry)
     if out is None:
         out = torch.empty((n, k), dtype=torch.float32, device=w.device)
     elif out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (n, k) or out.stride(1) != 1 or out.device != w.device:

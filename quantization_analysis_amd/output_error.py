@@ -16,9 +16,13 @@ candidates <f>+transpose for each of bfp8 / bfp4 / bfp2 among the formats have Å
 consecutive rows (N) of one column (k), aligned from row 0, a ragged last group completed with +0 â€” which is the transpose algorithm's y.
 bf16 and fp0 are elementwise and get no transposed row; the bytes are the row-layout format's.  A map in this layout is over Wáµ€'s tile
 grid, tiles_hw(k, n): the map of a "layout": "transpose" search (map:<algorithm>+transpose) and the budget maps budget:<B>:<basis>+transpose.
-Q(X) keeps X's row layout; only W's layout changes.  GPTQ is row-layout only: its transposed counterparts are listed in budget_skipped.
+Q(X) keeps X's row layout; only W's layout changes.  GPTQ is row-layout only by default: its transposed counterparts are listed in
+budget_skipped.  With gptq_transpose (opt-in) they are swept in the transposed layout instead (gptq.py: E is the exponent of the 16
+rows actually quantised at each column), on the same H and U: gptq:<f>+transpose, gptq:<map name> for a "layout": "transpose" map and
+gptq:budget:<B>:output+transpose, each with the bytes of its round-to-nearest +transpose row.
 Row order: the row-layout formats, the +transpose formats, the map, recorded, then per budget the two row-layout maps and their two
-transposed maps, then GPTQ.
+transposed maps, then GPTQ (its formats, their +transpose counterparts, the map, then per budget the row-layout map and its
+transposed counterpart).
 
 Backends:
   * hip       â€” csrc/mtq_output_error.hip: one pass per M-chunk with every candidate's W image built on the fly in LDS, the sums
@@ -300,7 +304,7 @@ def rows_from_sums(sums: np.ndarray, m: int, n: int, k: int, formats, map_cand: 
 
 def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation", chunk_rows: int = 16384,
                 x_format: str = "bf16", budgets=(), calib: Optional[OpIO] = None, gptq: bool = False, gptq_damp: float = 0.01,
-                transpose: bool = False, gptq_factor: str = "host") -> OpResult:
+                transpose: bool = False, gptq_factor: str = "host", gptq_transpose: bool = False) -> OpResult:
     """One op of `select_ops` â†’ its rows (or the reason it is skipped).  formats âŠ† SUPPORTED_FORMATS; config: a CompressionConfig
     whose mixed-tile algorithm adds the map candidate (None = pure formats only); x_format: the candidates' activation format.
     budgets: bits per weight, each adding the maps budget:<bits>:output and budget:<bits>:weight (budget_maps.py) chosen on the
@@ -310,7 +314,9 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
     bytes of its round-to-nearest counterpart; bf16 x_format only.  gptq_factor: "host" (gptq.factor, CPU LAPACK) or "device"
     (gptq.factor_hip, hip backend only: H and U stay on the device).
     transpose: adds <f>+transpose for each of bfp8 / bfp4 / bfp2 among the formats and, with budgets, budget:<bits>:<basis>+transpose
-    (implied by a config with the transpose algorithm); a config with "layout": "transpose" gives a map over Wáµ€'s grid."""
+    (implied by a config with the transpose algorithm); a config with "layout": "transpose" gives a map over Wáµ€'s grid.
+    gptq_transpose (with gptq): the transposed candidates get GPTQ rows of their own, swept in the transposed layout (gptq:<f>+transpose,
+    gptq:<map name> of a transposed map, gptq:budget:<bits>:output+transpose), instead of an entry in budget_skipped."""
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {', '.join(BACKENDS)}")
     check_x_format(x_format)
@@ -369,7 +375,8 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
     if budgets:
         _budget_rows(res, index, op, w, bias, formats, backend, chunk_rows, budgets, calib, transpose)
     if gptq:
-        _gptq_rows(res, op, w, bias, formats, map_cand, backend, chunk_rows, budgets, calib, gptq_damp, transpose, gptq_factor)
+        _gptq_rows(res, op, w, bias, formats, map_cand, backend, chunk_rows, budgets, calib, gptq_damp, transpose, gptq_factor,
+                   bool(gptq_transpose))
     return res
 
 
@@ -451,34 +458,41 @@ def check_gptq_factor(factor: str, backend: str) -> None:
 
 
 def _gptq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[MapCandidate], backend: str, chunk_rows: int, budgets,
-               calib: Optional[OpIO], damp: float, transpose: bool = False, factor: str = "host") -> None:
+               calib: Optional[OpIO], damp: float, transpose: bool = False, factor: str = "host", sweep_transposed: bool = False) -> None:
     """Appends the GPTQ rows to res: one Gram matrix and one factorisation per op (factor: on the host, or "device": on the hip
     backend's device, where neither H nor U crosses to the host), one sweep and one LOE pass (Å´ as the weight)
-    per candidate; or records in res.budget_skipped why a candidate was not made.  Row layout only: every transposed candidate is
-    listed in res.budget_skipped, and no map over Wáµ€'s grid reaches a sweep."""
+    per candidate; or records in res.budget_skipped why a candidate was not made.  Row layout only unless sweep_transposed: every
+    transposed candidate is then listed in res.budget_skipped, and no map over Wáµ€'s grid reaches a sweep.  With sweep_transposed the
+    transposed candidates are swept in the transposed layout on the same H and U."""
     from . import budget_maps as bm
     from . import gptq as gq
 
     check_gptq_factor(factor, backend)
     n, k = res.shape
     row_only = "GPTQ is row-layout only: a transposed candidate has no GPTQ counterpart"
-    if transpose:
-        res.budget_skipped.extend((f"gptq:{f}{TRANSPOSE_SUFFIX}", row_only) for f in gq.GPTQ_FORMATS if f in formats)
-    if map_cand is not None and map_cand.layout != "rows":
-        res.budget_skipped.append((f"gptq:{map_cand.name}", row_only))
-        map_cand = None
-    if transpose:
-        res.budget_skipped.extend((f"gptq:{bm.map_name(b, 'output')}{TRANSPOSE_SUFFIX}", row_only) for b in budgets)
-    cands = [(f"gptq:{f}", gq.constant_codes(n, k, f), FORMAT_BYTES_PER_ELEM[f] * float(n * k)) for f in gq.GPTQ_FORMATS if f in formats]
+    t_formats = [f for f in gq.GPTQ_FORMATS if f in formats] if transpose else []
+    if not sweep_transposed:
+        res.budget_skipped.extend((f"gptq:{f}{TRANSPOSE_SUFFIX}", row_only) for f in t_formats)
+        if map_cand is not None and map_cand.layout != "rows":
+            res.budget_skipped.append((f"gptq:{map_cand.name}", row_only))
+            map_cand = None
+        if transpose:
+            res.budget_skipped.extend((f"gptq:{bm.map_name(b, 'output')}{TRANSPOSE_SUFFIX}", row_only) for b in budgets)
+    # (name, codes, bytes, layout): codes over W's grid for "rows", over Wáµ€'s for "transpose"
+    cands = [(f"gptq:{f}", gq.constant_codes(n, k, f), FORMAT_BYTES_PER_ELEM[f] * float(n * k), "rows") for f in gq.GPTQ_FORMATS if f in formats]
+    if sweep_transposed:
+        cands.extend((f"gptq:{f}{TRANSPOSE_SUFFIX}", gq.constant_codes_transposed(n, k, f), FORMAT_BYTES_PER_ELEM[f] * float(n * k), "transpose")
+                     for f in t_formats)
     if map_cand is not None:
-        cands.append((f"gptq:{map_cand.name}", map_cand.assignment, map_cand.tile_bytes))
+        cands.append((f"gptq:{map_cand.name}", map_cand.assignment, map_cand.tile_bytes, map_cand.layout))
     for b in budgets:
-        name = bm.map_name(b, "output")
-        row = next((r for r in res.rows if r.candidate == name), None)
-        if row is not None:
-            cands.append((f"gptq:{name}", row.extra["assignment"], row.bytes))
-        else:
-            res.budget_skipped.append((f"gptq:{name}", f"no {name} map was made"))
+        for layout in (LAYOUTS if transpose and sweep_transposed else ("rows",)):
+            name = bm.map_name(b, "output") + (TRANSPOSE_SUFFIX if layout == "transpose" else "")
+            row = next((r for r in res.rows if r.candidate == name), None)
+            if row is not None:
+                cands.append((f"gptq:{name}", row.extra["assignment"], row.bytes, layout))
+            else:
+                res.budget_skipped.append((f"gptq:{name}", f"no {name} map was made"))
     if not cands:
         return
     why = "no calibration samples for this op" if calib is None else check_op(calib, (n, k))
@@ -497,26 +511,29 @@ def _gptq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[Map
         if isinstance(u, str):
             why = u
     if why is not None:
-        res.budget_skipped.extend((name, why) for name, _codes, _bytes in cands)
+        res.budget_skipped.extend((name, why) for name, _codes, _bytes, _layout in cands)
         return
     if backend == "hip":
         import torch
 
         ud = u if factor == "device" else torch.from_numpy(u).to(w.device)
-    for name, codes, nbytes in cands:
+    for name, codes, nbytes, layout in cands:
+        t = layout == "transpose"
         it = (Chunk(x=ch.x, cast=ch.cast) for ch in chunks(op, k, n, chunk_rows))   # Å´'s slot alone: no recorded output
         if backend == "hip":
-            what, loss = gq.sweep_hip(w, ud, codes)
+            what, loss = (gq.sweep_hip_transposed if t else gq.sweep_hip)(w, ud, codes)
             if not bool((what.to(torch.bfloat16).float() == what).all()):
                 raise RuntimeError(f"{name}: a GPTQ weight is not a bf16 value, so its products with X are not exact in float32")
             sums, m, _rec, _cast = hip_sums(_gptq_outputs(it, what, bias), w, [], bias)
             s = sums[SLOTS.index("recorded")]
             loss = float(loss.sum())
         else:
-            what, loss, _margin = gq.sweep_emulation(w, u, codes)
+            what, loss, _margin = (gq.sweep_emulation_transposed if t else gq.sweep_emulation)(w, u, codes)
             sums, m, _rec, _cast = emulation_sums(it, w, [], bias, what)
             s = sums[SLOTS.index("map")]
             loss = float(loss.sum())
         row = Row(name, nbytes, *_columns(s, float(m) * float(n)), tuple(s))
         row.extra = {"damp": float(damp), "calib_tokens": int(m_cal), "calib_loss": loss}
+        if t:
+            row.extra["layout"] = "transpose"
         res.rows.append(row)

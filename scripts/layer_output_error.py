@@ -9,7 +9,9 @@ maps budget:<B>:output and budget:<B>:weight chosen on the calibration activatio
 activations (quantization_analysis_amd/gptq.py): gptq:<bfp*>, gptq:<map> and gptq:budget:<B>:output, each at its RTN counterpart's bytes.
 --transpose (implied by a config with the transpose algorithm) adds <bfp*>+transpose, Ŵ = quantize(Wᵀ)ᵀ with one shared exponent per 16
 rows of a column, and with --budget-bits the maps budget:<B>:<basis>+transpose over Wᵀ's grid; a mixed-tile config with
-"layout": "transpose" gives map:<algorithm>+transpose.  GPTQ stays row-layout only.
+"layout": "transpose" gives map:<algorithm>+transpose.  GPTQ stays row-layout only unless --gptq-transpose (with --gptq and --transpose)
+is given: the transposed candidates are then swept in the transposed layout, on the same Hessian and factor, as gptq:<bfp*>+transpose,
+gptq:<map> of a transposed map and gptq:budget:<B>:output+transpose, each at its +transpose RTN counterpart's bytes.
 
   python scripts/layer_output_error.py /path/to/DeepSeek-R1 /path/to/io model.layers.0.mlp --backend hip -c bf16 bfp8 bfp4 bfp2 \\
       --compression-config compression_configs/compression_config.mixed_tile_greedy.example.json --split test --out-dir results/loe
@@ -64,7 +66,12 @@ def parse_args(argv=None):
     p.add_argument("--gptq-damp", type=float, default=0.01, metavar="D", help="GPTQ damping: λ = D · mean(diag H) (finite, > 0).")
     p.add_argument("--gptq-factor", choices=("host", "device"), default="host",
                    help="Where GPTQ factorises the damped Hessian: host (CPU LAPACK) or device (the hip backend's float64 MFMA kernels).")
+    p.add_argument("--gptq-transpose", action="store_true",
+                   help="With --gptq and --transpose: GPTQ rows of the transposed candidates too, swept in the transposed layout "
+                        "(gptq:<bfp*>+transpose, gptq:<map> of a transposed map, gptq:budget:<B>:output+transpose).")
     args = p.parse_args(argv)
+    if args.gptq_transpose and not (args.gptq and args.transpose):
+        p.error("--gptq-transpose needs --gptq and --transpose: it adds the GPTQ rows of the transposed candidates")
     if args.gptq:
         if args.x_format != "bf16":
             p.error("--gptq needs --x-format bf16: the GPTQ weights are built and evaluated on bf16 activations")
@@ -111,6 +118,8 @@ def main(argv=None) -> int:
         extra = {"budgets": budgets, "calib": calib.get(op.op)} if budgets or args.gptq else {}
         if args.gptq:
             extra.update(gptq=True, gptq_damp=args.gptq_damp, gptq_factor=args.gptq_factor)
+        if args.gptq_transpose:
+            extra.update(gptq_transpose=True)
         if transpose:
             extra.update(transpose=True)
         res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows, args.x_format, **extra)
@@ -158,6 +167,8 @@ def main(argv=None) -> int:
         doc.update({"calib_io": calib_io, "calib_split": args.calib_split, "calib_max_samples": args.calib_max_samples})
     if args.gptq:
         doc.update({"gptq_damp": args.gptq_damp, "gptq_factor": args.gptq_factor})
+    if args.gptq_transpose:
+        doc.update({"gptq_transpose": True})
     if transpose:
         doc.update({"transpose": True})
     (out_dir / "layer_output_error.json").write_text(json.dumps(doc, indent=2))
