@@ -243,6 +243,20 @@ int mtq_output_error_qx(const void *x, int64_t m, int64_t k, int64_t ldx, const 
 int mtq_quantize_rows_bf16(const void *x, int64_t rows, int64_t cols, int64_t ld, int fmt, void *y, int64_t ldy, void *stream);
 
 /*
+ * Block Hadamard rotation of rows — every aligned block of `block` = 2^p consecutive columns (32 <= block <= 4096, k % block == 0) of
+ * every row of the rows × k matrix x (x_dtype BF16 / F32, unit column stride, ldx >= k) becomes y = fl32(S · c_p): S = x_block · H_B with
+ * H_B the Sylvester–Hadamard matrix in natural order, formed by p stages of float32 add / subtract butterflies (stride 1 first),
+ * c_p = float32(2^(−p/2)) applied as one float32 multiply after the last stage.  y (y_dtype, ldy >= k): float32, or bf16 by RNE of that
+ * float32.  yq: NULL, or a second bf16 output (ldq >= k) written by the same launch, bit for bit mtq_quantize_rows_bf16(y, q_fmt) of the
+ * bf16 y; q_fmt is MTQ_FMT_BFP8, _BFP4 or _BFP2 (anything else MTQ_ERR_UNSUPPORTED) and y must be bf16.  y == x is allowed when dtype and
+ * stride are equal (a wave reads its whole segment before it writes); any other overlap of x, y and yq is MTQ_ERR_INVALID.  Checks, in
+ * order: null x or y, dtype codes, q_fmt, block, rows / k <= 0, k % block, ld < k, yq with a float32 y, sizes, overlap — each
+ * MTQ_ERR_INVALID before a device is looked for.  Deterministic: a fixed butterfly order, no atomics.  csrc/mtq_hadamard.hip.
+ */
+int mtq_hadamard_rows(const void *x, int x_dtype, int64_t rows, int64_t k, int64_t ldx, int64_t block, void *y, int y_dtype, int64_t ldy,
+                      void *yq, int q_fmt, int64_t ldq, void *stream);
+
+/*
  * LOE in the transposed BFP layout — mtq_output_error (xq == NULL) or mtq_output_error_qx (xq != NULL) with Ŵ_f = K2_f(wᵀ)ᵀ for the
  * bfp8 / bfp4 / bfp2 bits: a group is 16 consecutive rows (n) of one column (k), aligned from row 0, a ragged last group completed with
  * +0.  `map`, when not NULL, is over wᵀ's grid: ceil(k/32) × ceil(n/32) int8 codes, row-major (the code of w[n][k] is

@@ -101,6 +101,7 @@ SIGNATURES = {
     "mtq_fp4_proxy_sums": ("i", "pillllluppzp", True),
     "mtq_output_error_qx": ("i", "plllpillpuppilppzppl", True),
     "mtq_quantize_rows_bf16": ("i", "pllliplp", True),
+    "mtq_hadamard_rows": ("i", "pillllpilpilp", True),
     "mtq_gram_blocks_scratch_doubles": ("z", "ll", True),
     "mtq_gram_blocks": ("i", "plllpzpzp", True),
     "mtq_tile_error_tables": ("i", "pilllpzppzp", True),
@@ -769,6 +770,58 @@ def quantize_rows_bf16(x, fmt: str, out=None):
         raise MtqError(f"out must be a ({m}, {k}) bfloat16 tensor with contiguous rows on x's device")
     check(fn(x.data_ptr(), m, k, ld, FMT_CODE[fmt], out.data_ptr(), ldy, _stream_ptr()))
     return out
+
+
+HADAMARD_MIN_BLOCK, HADAMARD_MAX_BLOCK = 32, 4096   # include/mtq.h mtq_hadamard_rows
+
+
+def hadamard_rows(x, block: int, out=None, out_dtype=None, q_fmt=None, q_out=None):
+    """Block Hadamard rotation (mtq_hadamard_rows) on the current stream: every aligned block of `block` consecutive columns of every row
+    of the (rows, k) bf16 / float32 device tensor x (contiguous rows) times H_block · 2^(−p/2) → `out`, a (rows, k) float32 or bf16 tensor
+    with contiguous rows (allocated in out_dtype, x's dtype when None; `out is x` rotates in place).  q_fmt (bfp8 / bfp4 / bfp2): the
+    launch also writes Q(out) — quantize_rows_bf16(out, q_fmt), bit for bit — into q_out (allocated when None) and the result is
+    (out, q_out); out must then be bf16.  The checks that need no device come first: block, k % block, the twin's dtypes."""
+    torch = _torch()
+    block = int(block)
+    if block < HADAMARD_MIN_BLOCK or block > HADAMARD_MAX_BLOCK or block & (block - 1):
+        raise MtqError(f"block must be a power of two in [{HADAMARD_MIN_BLOCK}, {HADAMARD_MAX_BLOCK}], got {block}")
+    if x.dim() != 2:
+        raise MtqError(f"expected a 2-D device tensor, got {x.dim()}-D")
+    rows, k = int(x.shape[0]), int(x.shape[1])
+    if k % block:
+        raise MtqError(f"k = {k} is not a multiple of block = {block}")
+    if q_fmt is not None and q_fmt not in X_FORMATS[1:]:
+        raise ValueError(f"Unsupported twin format: {q_fmt} (one of {', '.join(X_FORMATS[1:])})")
+    if out_dtype is None:
+        out_dtype = x.dtype if out is None else out.dtype
+    if out is not None and out.dtype != out_dtype:
+        raise MtqError(f"out is {out.dtype}, out_dtype {out_dtype}")
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise MtqError(f"out_dtype must be bfloat16 or float32, got {out_dtype}")
+    if q_fmt is not None and out_dtype != torch.bfloat16:
+        raise MtqError("the quantised twin is Q(out) of a bfloat16 out: out_dtype must be bfloat16 with q_fmt")
+    if q_fmt is None and q_out is not None:
+        raise MtqError("q_out without q_fmt")
+    code, _count, _stride, _rows, _k, ldx = _matrix(x, (2,))
+    require_gpu()
+    fn = _entry("mtq_hadamard_rows")
+    if out is None:
+        out = torch.empty((rows, k), dtype=out_dtype, device=x.device)
+    y_code, _count, _stride, orows, ok, ldy = _matrix(out, (2,))
+    if (orows, ok) != (rows, k) or out.device != x.device:
+        raise MtqError(f"out must be a ({rows}, {k}) tensor with contiguous rows on x's device")
+    q_ptr, ldq = None, 0
+    if q_fmt is not None:
+        if q_out is None:
+            q_out = torch.empty((rows, k), dtype=torch.bfloat16, device=x.device)
+        _code, _count, _stride, qrows, qk, ldq = _matrix(q_out, (2,))
+        if q_out.dtype != torch.bfloat16 or (qrows, qk) != (rows, k) or q_out.device != x.device:
+            raise MtqError(f"q_out must be a ({rows}, {k}) bfloat16 tensor with contiguous rows on x's device")
+        q_ptr = q_out.data_ptr()
+    if rows and k:
+        check(fn(x.data_ptr(), code, rows, k, ldx, block, out.data_ptr(), y_code, ldy, q_ptr, FMT_CODE[q_fmt] if q_fmt else 0, ldq,
+                 _stream_ptr()))
+    return out if q_fmt is None else (out, q_out)
 
 
 def output_error(x, w, fmt_mask: int, sums, bias=None, assignment=None, recorded=None, scratch=None, xq=None):

@@ -42,6 +42,7 @@ class Chunk:
     x: object                  # torch (m, k) bfloat16, host
     recorded: object = None    # torch (m, n) host tensor or None
     cast: bool = False         # X.to(bfloat16) changed a value
+    xq: object = None          # Q(x) in the op's x_format, when the producer of x already has it (the rotation kernel's twin)
 
 
 def is_synthetic(io_root: str) -> bool:

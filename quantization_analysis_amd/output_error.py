@@ -24,6 +24,13 @@ Row order: the row-layout formats, the +transpose formats, the map, recorded, th
 transposed maps, then GPTQ (its formats, their +transpose counterparts, the map, then per budget the row-layout map and its
 transposed counterpart).
 
+Rotation (rotate = B, or "auto" for hadamard.auto_block(k)): the whole evaluation runs on the rotated op (hadamard.py).  W′ =
+rotate_weight(W, B) in float32 and every chunk's X′ = the bf16 block Hadamard transform of X, wherever chunks are opened: the sums, the
+budget maps, GPTQ and the calibration split of their Gram matrices (GPTQ's H becomes HᵀHH for free); a config's map is searched on W′.
+R is X′·W′ᵀ, the rotated layer: it equals X·Wᵀ up to the bf16 rounding of X′ and the float32 rounding of W′, and when the op has
+recorded outputs the `recorded` row shows that deviation.  Row names are unchanged.  On hip a chunk is rotated on the device
+(csrc/mtq_hadamard.hip), and with a BFP x_format Q(X′) is the same launch's second output instead of a row pre-pass.
+
 Backends:
   * hip       — csrc/mtq_output_error.hip: one pass per M-chunk with every candidate's W image built on the fly in LDS, the sums
                 reduced in the epilogue; neither Ŵ nor Y is materialised.  A BFP x_format adds one row pre-pass per chunk that writes
@@ -92,6 +99,7 @@ class OpResult:
     x_format: str = "bf16"
     budget_skipped: list = field(default_factory=list)   # (candidate, reason) of budget maps that were not made
     calib_splits: list = field(default_factory=list)
+    rotate: int = 0            # block of the Hadamard rotation the op was evaluated under (0 = none)
 
 
 def config_layout(config) -> str:
@@ -125,6 +133,34 @@ def quantize_x(x, x_format: str):
     check_x_format(x_format)
     x32 = x.float().cpu().numpy()
     return torch.from_numpy(quantize_weight_values(x32, x_format).astype(np.float64))
+
+
+def rotated_chunks(chunk_iter: Iterable, block: int, backend: str, x_format: str = "bf16") -> Iterable:
+    """Each chunk with X′ = the bf16 block Hadamard transform of its x (hadamard.py).  hip: the chunk is moved to the device and rotated
+    there, so the consumers' .to(device) is a no-op, and a BFP x_format takes Q(X′) from the same launch (Chunk.xq)."""
+    import torch
+
+    from . import hadamard as hd
+
+    for ch in chunk_iter:
+        xq = None
+        if backend == "hip":
+            from . import hip_backend as hb
+
+            xd = ch.x.to(torch.device("cuda", torch.cuda.current_device())).contiguous()
+            if x_format != "bf16":
+                x, xq = hb.hadamard_rows(xd, block, q_fmt=x_format)
+            else:
+                x = hb.hadamard_rows(xd, block)
+        else:
+            x = hd.hadamard_emulation(ch.x, block, torch.bfloat16)
+        yield Chunk(x=x, recorded=ch.recorded, cast=ch.cast, xq=xq)
+
+
+def op_chunks(op: OpIO, k: int, n: int, chunk_rows: int, rotate: int = 0, backend: str = "emulation", x_format: str = "bf16") -> Iterable:
+    """layer_io.chunks of the op, rotated by blocks of `rotate` when it is not 0."""
+    it = chunks(op, k, n, chunk_rows)
+    return rotated_chunks(it, rotate, backend, x_format) if rotate else it
 
 
 def search_map(w, config, backend: str, name: str = "weight") -> Optional[MapCandidate]:
@@ -267,8 +303,8 @@ def hip_sums(chunk_iter: Iterable, w, formats, bias=None, assignment=None, x_for
         need = hb.output_error_scratch(int(xd.shape[0]), int(wd.shape[0]))
         if scratch is None or scratch.numel() < need:
             scratch = torch.empty((need,), dtype=torch.float64, device=dev)
-        xq = None
-        if x_format != "bf16":
+        xq = ch.xq
+        if x_format != "bf16" and xq is None:
             if xq_buf is None or xq_buf.numel() < xd.numel():
                 xq_buf = torch.empty((xd.numel(),), dtype=torch.bfloat16, device=dev)
             xq = hb.quantize_rows_bf16(xd, x_format, out=xq_buf[: xd.numel()].view(xd.shape))
@@ -304,7 +340,7 @@ def rows_from_sums(sums: np.ndarray, m: int, n: int, k: int, formats, map_cand: 
 
 def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation", chunk_rows: int = 16384,
                 x_format: str = "bf16", budgets=(), calib: Optional[OpIO] = None, gptq: bool = False, gptq_damp: float = 0.01,
-                transpose: bool = False, gptq_factor: str = "host", gptq_transpose: bool = False) -> OpResult:
+                transpose: bool = False, gptq_factor: str = "host", gptq_transpose: bool = False, rotate=0) -> OpResult:
     """One op of `select_ops` → its rows (or the reason it is skipped).  formats ⊆ SUPPORTED_FORMATS; config: a CompressionConfig
     whose mixed-tile algorithm adds the map candidate (None = pure formats only); x_format: the candidates' activation format.
     budgets: bits per weight, each adding the maps budget:<bits>:output and budget:<bits>:weight (budget_maps.py) chosen on the
@@ -347,6 +383,16 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
         res.skipped = why
         return res
     n, k = int(shape[0]), int(shape[1])
+    if rotate:
+        from . import hadamard as hd
+
+        if rotate != "auto":
+            hd.check_block(int(rotate), int(rotate))       # a block no k could take is the caller's error, not this op's
+        try:
+            res.rotate = hd.auto_block(k) if rotate == "auto" else hd.check_block(k, rotate)
+        except ValueError as e:
+            res.skipped = str(e)
+            return res
     if backend == "hip":
         import torch
 
@@ -359,11 +405,13 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
     if bias is not None and bias.numel() != n:
         res.skipped = f"bias has {bias.numel()} elements, the weight {n} rows"
         return res
+    if res.rotate:
+        w = hd.rotate_weight(w, res.rotate, backend=backend)
     map_cand = search_map(w, config, backend, op.weight)
     map_r = map_cand if map_cand is not None and map_cand.layout == "rows" else None
     map_t = map_cand if map_cand is not None and map_cand.layout == "transpose" else None
     t_formats = [f for f in formats if f in TRANSPOSE_FORMATS] if transpose else []
-    it = chunks(op, k, n, chunk_rows)
+    it = op_chunks(op, k, n, chunk_rows, res.rotate, backend, x_format)
     if backend == "hip":
         sums, m, seen_rec, cast = hip_sums(it, w, formats, bias, None if map_r is None else map_r.assignment, x_format, t_formats,
                                            None if map_t is None else map_t.assignment)
@@ -395,7 +443,7 @@ def _budget_rows(res: OpResult, index, op: OpIO, w, bias, formats, backend: str,
     tables = {}
     if why is None:
         res.calib_splits = calib.splits
-        cal = chunks(calib, k, n, chunk_rows)
+        cal = op_chunks(calib, k, n, chunk_rows, res.rotate, backend)
         if backend == "hip":
             h, m_cal = bm.gram_blocks_hip(cal, k, device=w.device)
             if m_cal:
@@ -417,7 +465,7 @@ def _budget_rows(res: OpResult, index, op: OpIO, w, bias, formats, backend: str,
             res.budget_skipped.append((name, got))
             continue
         assignment, _counts, tile_bytes = got
-        it = (Chunk(x=ch.x, cast=ch.cast) for ch in chunks(op, k, n, chunk_rows))   # the map slot alone: no recorded output
+        it = (Chunk(x=ch.x, cast=ch.cast) for ch in op_chunks(op, k, n, chunk_rows, res.rotate, backend))   # the map slot alone: no recorded output
         if backend == "hip":
             sums, m, _rec, _cast = hip_sums(it, w, [], bias, None if t else assignment, t_assignment=assignment if t else None)
             y = None
@@ -498,7 +546,7 @@ def _gptq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[Map
     why = "no calibration samples for this op" if calib is None else check_op(calib, (n, k))
     if why is None:
         res.calib_splits = calib.splits
-        cal = chunks(calib, k, n, chunk_rows)
+        cal = op_chunks(calib, k, n, chunk_rows, res.rotate, backend)
         if backend == "hip":
             h, m_cal = gq.gram_full_hip(cal, k, device=w.device)
             if factor == "host":
@@ -519,7 +567,7 @@ def _gptq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[Map
         ud = u if factor == "device" else torch.from_numpy(u).to(w.device)
     for name, codes, nbytes, layout in cands:
         t = layout == "transpose"
-        it = (Chunk(x=ch.x, cast=ch.cast) for ch in chunks(op, k, n, chunk_rows))   # Ŵ's slot alone: no recorded output
+        it = (Chunk(x=ch.x, cast=ch.cast) for ch in op_chunks(op, k, n, chunk_rows, res.rotate, backend))   # Ŵ's slot alone: no recorded output
         if backend == "hip":
             what, loss = (gq.sweep_hip_transposed if t else gq.sweep_hip)(w, ud, codes)
             if not bool((what.to(torch.bfloat16).float() == what).all()):

@@ -72,6 +72,7 @@ import numpy as np
 
 from .compression_algorithms.tile_utils import MIXED_TILE_FORMATS, flatten_2d, unflatten_2d
 from . import hip_backend as hb
+from .hadamard import check_block, hadamard
 from .hip_backend import PACKED_TILE_BYTES, MtqError
 
 FORMAT_VERSION = 1
@@ -2441,9 +2442,10 @@ def _product_class(o: _Orientation, name: str):
     """PackedLinear and PackedMatmul."""
     import torch
 
-    def init(self, pt, bias, out_dtype, kernel, backend):
+    def init(self, pt, bias, out_dtype, kernel, backend, rotate):
         torch.nn.Module.__init__(self)
         _check_rank2(o, pt, name)
+        self.rotate = check_block(o.n_k(pt)[1], rotate) if rotate else 0
         _check_kernel(kernel, globals()[o.kernels])
         _check_out_dtype(out_dtype)
         self.backend = backend or ("hip" if pt.on_device else "emulation")
@@ -2470,11 +2472,13 @@ def _product_class(o: _Orientation, name: str):
 
     class Product(torch.nn.Module):
         if o.kn:
-            def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block"):
-                init(self, pt, bias, out_dtype, kernel, backend)
+            def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block",
+                         rotate: int = 0):
+                init(self, pt, bias, out_dtype, kernel, backend, rotate)
         else:
-            def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", kernel: str = "auto", backend: Optional[str] = None):
-                init(self, pt, bias, out_dtype, kernel, backend)
+            def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", kernel: str = "auto", backend: Optional[str] = None,
+                         rotate: int = 0):
+                init(self, pt, bias, out_dtype, kernel, backend, rotate)
 
         def extra_repr(self) -> str:
             return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, kernel={self.kernel!r}, " \
@@ -2488,6 +2492,8 @@ def _product_class(o: _Orientation, name: str):
             x2 = x.reshape(-1, self.in_features)
             if x2.shape[0] == 0:
                 return torch.zeros(lead + (self.out_features,), dtype=_torch_dtype(self.out_dtype), device=x.device)
+            if self.rotate:    # pt is packed from rotate_weight(w, rotate): the product needs x·H, formed online (csrc/mtq_hadamard.hip on hip)
+                x2 = hadamard(x2, self.rotate, out_dtype=torch.bfloat16, backend=self.backend)
             y = globals()[o.product](x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel,
                                      workspace=self._workspace)
             return _as_torch(y).reshape(lead + (self.out_features,))

@@ -31,6 +31,7 @@ import numpy as np
 
 from quantization_analysis_amd.budget_maps import bits_tag
 from quantization_analysis_amd.compression_algorithms import load_compression_config
+from quantization_analysis_amd.hadamard import check_block
 from quantization_analysis_amd.layer_io import select_ops
 from quantization_analysis_amd.model_source import build_model_index, resolve_format_list
 from quantization_analysis_amd.output_error import BACKENDS, LAYOUTS, X_FORMATS, check_layout, evaluate_op
@@ -69,7 +70,15 @@ def parse_args(argv=None):
     p.add_argument("--gptq-transpose", action="store_true",
                    help="With --gptq and --transpose: GPTQ rows of the transposed candidates too, swept in the transposed layout "
                         "(gptq:<bfp*>+transpose, gptq:<map> of a transposed map, gptq:budget:<B>:output+transpose).")
+    p.add_argument("--rotate", default=None, metavar="{B|auto}",
+                   help="Evaluate every op rotated by a block Hadamard transform along k: B a power of two in [32, 4096], or auto = the "
+                        "largest one dividing k.  An op whose k the block does not divide is skipped.")
     args = p.parse_args(argv)
+    if args.rotate is not None and args.rotate != "auto":
+        try:
+            args.rotate = check_block(int(args.rotate), int(args.rotate))
+        except ValueError as e:
+            p.error(f"--rotate: {e}")
     if args.gptq_transpose and not (args.gptq and args.transpose):
         p.error("--gptq-transpose needs --gptq and --transpose: it adds the GPTQ rows of the transposed candidates")
     if args.gptq:
@@ -122,21 +131,26 @@ def main(argv=None) -> int:
             extra.update(gptq_transpose=True)
         if transpose:
             extra.update(transpose=True)
+        if args.rotate:
+            extra.update(rotate=args.rotate)
         res = evaluate_op(index, op, formats, config, args.backend, args.chunk_rows, args.x_format, **extra)
         if res.skipped:
             skipped.append((op.op, res.skipped))
             continue
         n, k = res.shape
         xf = f"  X {res.x_format}" if res.x_format != "bf16" else ""
+        xf += f"  rotated by H_{res.rotate}" if res.rotate else ""
         print(f"\n{res.op}  W {n}x{k}{xf}  M {res.m}  splits {','.join(res.splits)}{'  (X cast to bf16)' if res.x_cast else ''}")
         print(f"{'candidate':<28} | {'bytes':>14} | {'pcc':>12} | {'mae':>12} | {'atol':>12}")
         print("-" * 90)
         for r in res.rows:
             print(f"{r.candidate:<28} | {_fmt(r.bytes, '14.0f')} | {r.pcc:12.8f} | {r.mae:12.6e} | {r.atol:12.6e}")
-            csv_rows.append([res.op, r.candidate, r.bytes, r.pcc, r.mae, r.atol, res.m, n, k])
+            csv_rows.append([res.op, r.candidate, r.bytes, r.pcc, r.mae, r.atol, res.m, n, k] + ([res.rotate] if args.rotate else []))
         rec = {"op": res.op, "weight": res.weight, "shape": [n, k], "M": res.m, "splits": res.splits, "x_cast": res.x_cast,
                "rows": [{"candidate": r.candidate, "bytes": r.bytes, "pcc": r.pcc, "mae": r.mae, "atol": r.atol,
                          **{key: v for key, v in r.extra.items() if key != "assignment"}} for r in res.rows]}
+        if args.rotate:
+            rec["rotate"] = res.rotate
         if budgets or args.gptq:
             rec["calib_splits"] = res.calib_splits
             rec["budget_skipped"] = [{"candidate": c, "reason": why} for c, why in res.budget_skipped]
@@ -156,7 +170,7 @@ def main(argv=None) -> int:
             print(f"  {op}: {why}")
     with open(out_dir / "layer_output_error.csv", "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["op", "candidate", "bytes", "pcc", "mae", "atol", "M", "N", "K"])
+        w.writerow(["op", "candidate", "bytes", "pcc", "mae", "atol", "M", "N", "K"] + (["rotate"] if args.rotate else []))
         w.writerows(csv_rows)
     doc = {"repo_or_url": args.repo_or_url, "io_root": args.io_root, "backend": args.backend, "formats": formats,
            "compression_config": args.compression_config, "split": args.split, "max_samples": args.max_samples, "x_format": args.x_format,
@@ -171,6 +185,8 @@ def main(argv=None) -> int:
         doc.update({"gptq_transpose": True})
     if transpose:
         doc.update({"transpose": True})
+    if args.rotate:
+        doc.update({"rotate": args.rotate})
     (out_dir / "layer_output_error.json").write_text(json.dumps(doc, indent=2))
     print(f"\nwrote {out_dir / 'layer_output_error.csv'} and {out_dir / 'layer_output_error.json'}")
     return 0
