@@ -110,6 +110,9 @@ SIGNATURES = {
     "mtq_gptq_sweep_scratch_doubles": ("z", "ll", True),
     "mtq_gptq_sweep": ("i", "pilllpzpzplppzp", True),
     "mtq_gptq_sweep_transposed": ("i", "pilllpzpzplppzp", True),
+    "mtq_awq_losses_scratch_doubles": ("z", "lli", True),
+    "mtq_awq_losses": ("i", "plllpillpzpippzp", True),
+    "mtq_awq_quantize": ("i", "pilllpzpplp", True),
     "mtq_gptq_factor_scratch_doubles": ("z", "l", True),
     "mtq_gptq_factor": ("i", "plpzppzp", True),
     "mtq_output_error_transposed": ("i", "plllpillpuppilppzppl", True),
@@ -1106,6 +1109,95 @@ def gptq_factor(hd, u=None):
     status = torch.empty((1,), dtype=torch.int32, device=hd.device)
     check(fn(hd.data_ptr(), k, u.data_ptr(), u.numel(), status.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream_ptr()))
     return u, status
+
+
+AWQ_MAX_SHIFT = 7   # the largest entry of a shift table (awq.py)
+AWQ_MAX_EXP_FIELD = 240   # the largest float32 exponent field of a weight the AWQ kernels take (include/mtq.h: the precondition)
+
+
+def awq_slots() -> int:
+    """The slots of one launch of mtq_awq_losses (csrc/mtq_awq.hip kS), read from the library: its scratch is one record of that many
+    doubles per workgroup."""
+    return awq_losses_scratch(1, 1, 1)
+
+
+def awq_check_values(w, codes, p) -> None:
+    """The value checks of the AWQ entries, each one device-to-host synchronisation: codes 0..3, shifts 0 .. 7, and the kernels'
+    precondition on W (every exponent field <= 240: finite and below 2^114; above it Ŵ would be silently wrong)."""
+    if codes.numel() and (int(codes.min()) < 0 or int(codes.max()) > 3):
+        raise MtqError("codes must be MIXED_TILE_FORMATS codes 0..3")
+    if p.numel() and (int(p.min()) < 0 or int(p.max()) > AWQ_MAX_SHIFT):
+        raise MtqError(f"the shifts must lie in 0 .. {AWQ_MAX_SHIFT}")
+    if bool((~(w.abs() < 2.0 ** (AWQ_MAX_EXP_FIELD - 126))).any()):
+        raise MtqError(f"w holds an exponent field above {AWQ_MAX_EXP_FIELD} (non-finite or huge values): a shift could overflow")
+
+
+def _awq_operands(w, codes, p, rows, checked):
+    """The checks awq_losses and awq_quantize share → (w_code, n, k, ldw); p: one shift row (k,) when rows == 1, a table (G, k) otherwise.
+    checked: the caller has run awq_check_values on these operands already."""
+    torch = _torch()
+    w_code, _count, _stride, n, k, ldw = _matrix(w, (2,))
+    th, tw = tiles_hw(n, k)
+    if codes.dtype != torch.int8 or codes.numel() != th * tw or not codes.is_contiguous() or not codes.is_cuda or codes.device != w.device:
+        raise MtqError(f"codes must be a contiguous int8 tensor of {th}x{tw} entries on w's device")
+    ok = tuple(p.shape) == (k,) if rows == 1 else (p.dim() == 2 and p.shape[0] >= 1 and p.shape[1] == k)
+    if p.dtype != torch.int8 or not ok or not p.is_contiguous() or not p.is_cuda or p.device != w.device:
+        raise MtqError(f"the shifts must be a contiguous int8 tensor of shape {'(k,)' if rows == 1 else '(G >= 1, k)'}, k = {k}, on w's device")
+    if not checked:
+        awq_check_values(w, codes, p)
+    return w_code, n, k, ldw
+
+
+def awq_losses_scratch(m: int, n: int, g_count: int) -> int:
+    """Doubles of scratch one mtq_awq_losses call over m × n outputs and g_count slots needs."""
+    return int(_entry("mtq_awq_losses_scratch_doubles")(m, n, g_count))
+
+
+def awq_losses(x, w, codes, p, loss, scratch=None, checked=False):
+    """AWQ's search (mtq_awq_losses) on the current stream: ADDS Σ (fl32(r − q_g))² of one M-chunk to loss[g] for every row g of the
+    shift table.  x: (m, k) bf16 device tensor with contiguous rows; w: (n, k) bf16 / float32 device tensor with contiguous rows;
+    codes: contiguous int8 (ceil(n/32), ceil(k/32)) device tensor of MIXED_TILE_FORMATS codes 0..3; p: contiguous int8 (G, k) device
+    tensor of shifts 0 .. 7; loss: contiguous float64 (G,) device tensor, zeroed by the caller once.  scratch: float64 device tensor of
+    at least awq_losses_scratch(m, n, G) elements (allocated when None).  w must hold no exponent field above 240 (finite, below 2^114):
+    refused here, with the ranges of codes and p, by awq_check_values, three synchronisations, unless checked=True says that the caller
+    ran it on these operands already (a loop over chunks checks once)."""
+    torch = _torch()
+    _code, _count, _stride, m, k, ldx = _matrix(x, (2,))
+    if x.dtype != torch.bfloat16:
+        raise MtqError(f"x must be bfloat16, got {x.dtype}")
+    w_code, n, kw, ldw = _awq_operands(w, codes, p, 0, checked)
+    if kw != k:
+        raise MtqError(f"x has {k} columns, w has {kw}")
+    g = int(p.shape[0])
+    if loss.dtype != torch.float64 or tuple(loss.shape) != (g,) or not loss.is_contiguous() or not loss.is_cuda or loss.device != w.device:
+        raise MtqError(f"loss must be a contiguous float64 tensor of {g} elements on w's device")
+    require_gpu()
+    fn = _entry("mtq_awq_losses")
+    need = awq_losses_scratch(m, n, g)
+    if scratch is None:
+        scratch = torch.empty((max(need, 1),), dtype=torch.float64, device=x.device)
+    elif scratch.dtype != torch.float64 or not scratch.is_contiguous() or not scratch.is_cuda or scratch.numel() < need:
+        raise MtqError(f"scratch must be a contiguous float64 device tensor of at least {need} elements")
+    check(fn(x.data_ptr(), m, k, ldx, w.data_ptr(), w_code, n, ldw, codes.data_ptr(), codes.numel(), p.data_ptr(), g, loss.data_ptr(),
+             scratch.data_ptr(), scratch.numel(), _stream_ptr()))
+    return loss
+
+
+def awq_quantize(w, codes, p_row, out=None, checked=False):
+    """Ŵ of one shift row (mtq_awq_quantize) on the current stream → float32 (n, k) device tensor.  w, codes: as awq_losses; p_row:
+    contiguous int8 (k,) device tensor of shifts 0 .. 7; out: float32 (n, k) with contiguous rows on w's device (allocated when None).
+    The precondition on w and `checked`: as awq_losses."""
+    torch = _torch()
+    w_code, n, k, ldw = _awq_operands(w, codes, p_row, 1, checked)
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=w.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (n, k) or out.stride(1) != 1 or out.device != w.device:
+        raise MtqError(f"out must be a float32 ({n}, {k}) tensor with contiguous rows on w's device")
+    require_gpu()
+    fn = _entry("mtq_awq_quantize")
+    check(fn(w.data_ptr(), w_code, n, k, ldw, codes.data_ptr(), codes.numel(), p_row.data_ptr(), out.data_ptr(),
+             out.stride(0) if n > 1 else max(out.stride(0), k), _stream_ptr()))
+    return out
 
 
 def apply_assignment(x2d, assignment, out=None):

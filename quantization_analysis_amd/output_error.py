@@ -340,7 +340,8 @@ def rows_from_sums(sums: np.ndarray, m: int, n: int, k: int, formats, map_cand: 
 
 def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation", chunk_rows: int = 16384,
                 x_format: str = "bf16", budgets=(), calib: Optional[OpIO] = None, gptq: bool = False, gptq_damp: float = 0.01,
-                transpose: bool = False, gptq_factor: str = "host", gptq_transpose: bool = False, rotate=0) -> OpResult:
+                transpose: bool = False, gptq_factor: str = "host", gptq_transpose: bool = False, rotate=0, awq: bool = False,
+                awq_grid: int = 20, awq_max_shift: int = 7) -> OpResult:
     """One op of `select_ops` → its rows (or the reason it is skipped).  formats ⊆ SUPPORTED_FORMATS; config: a CompressionConfig
     whose mixed-tile algorithm adds the map candidate (None = pure formats only); x_format: the candidates' activation format.
     budgets: bits per weight, each adding the maps budget:<bits>:output and budget:<bits>:weight (budget_maps.py) chosen on the
@@ -371,6 +372,12 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
             raise ValueError("GPTQ weights are built and evaluated on bf16 activations: x_format must be bf16")
         check_damp(gptq_damp)
         check_gptq_factor(gptq_factor, backend)
+    if awq:
+        from .awq import check_params
+
+        if x_format != "bf16":
+            raise ValueError("AWQ shifts are searched and evaluated on bf16 activations: x_format must be bf16")
+        check_params(awq_grid, awq_max_shift)
     check_layout(config, LAYOUTS)
     transpose = bool(transpose) or (config is not None and config.algorithm == "transpose")
     bad = [f for f in formats if f not in SUPPORTED_FORMATS]
@@ -425,6 +432,8 @@ def evaluate_op(index, op: OpIO, formats, config=None, backend: str = "emulation
     if gptq:
         _gptq_rows(res, op, w, bias, formats, map_cand, backend, chunk_rows, budgets, calib, gptq_damp, transpose, gptq_factor,
                    bool(gptq_transpose))
+    if awq:
+        _awq_rows(res, op, w, bias, formats, map_cand, backend, chunk_rows, calib, int(awq_grid), int(awq_max_shift), transpose)
     return res
 
 
@@ -584,4 +593,57 @@ def _gptq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[Map
         row.extra = {"damp": float(damp), "calib_tokens": int(m_cal), "calib_loss": loss}
         if t:
             row.extra["layout"] = "transpose"
+        res.rows.append(row)
+
+
+def _awq_rows(res: OpResult, op: OpIO, w, bias, formats, map_cand: Optional[MapCandidate], backend: str, chunk_rows: int,
+              calib: Optional[OpIO], grid: int, max_shift: int, transpose: bool = False) -> None:
+    """Appends the AWQ rows to res: one pass for the Gram blocks per op, then per candidate one search over the calibration chunks
+    (awq.search) and one LOE pass with Ŵ of the chosen shifts as the weight, as GPTQ's; or records in res.budget_skipped why a candidate
+    was not made.  Row layout only: a shift per input channel moves a whole column group and changes nothing in the transposed layout."""
+    from . import awq as aq
+    from . import budget_maps as bm
+    from .gptq import constant_codes
+
+    n, k = res.shape
+    row_only = "a per-input-channel shift moves all 16 rows of a column group together: it changes nothing in the transposed layout"
+    if transpose:
+        res.budget_skipped.extend((f"awq:{f}{TRANSPOSE_SUFFIX}", row_only) for f in aq.AWQ_FORMATS if f in formats)
+    cands = [(f"awq:{f}", constant_codes(n, k, f), FORMAT_BYTES_PER_ELEM[f] * float(n * k)) for f in aq.AWQ_FORMATS if f in formats]
+    if map_cand is not None:
+        if map_cand.layout == "rows":
+            cands.append((f"awq:{map_cand.name}", map_cand.assignment, map_cand.tile_bytes))
+        else:
+            res.budget_skipped.append((f"awq:{map_cand.name}", row_only))
+    if not cands:
+        return
+    why = "no calibration samples for this op" if calib is None else check_op(calib, (n, k))
+    if why is None:
+        res.calib_splits = calib.splits
+        cal = op_chunks(calib, k, n, chunk_rows, res.rotate, backend)
+        h, m_cal = bm.gram_blocks_hip(cal, k, device=w.device) if backend == "hip" else bm.gram_blocks_emulation(cal, k)
+        why = "the calibration samples hold no tokens" if not m_cal else None
+    if why is not None:
+        res.budget_skipped.extend((name, why) for name, _codes, _bytes in cands)
+        return
+    for name, codes, nbytes in cands:
+        got = aq.search(op_chunks(calib, k, n, chunk_rows, res.rotate, backend), w, codes, h, m_cal, backend, grid, max_shift)
+        if isinstance(got, str):
+            res.budget_skipped.append((name, got))
+            continue
+        it = (Chunk(x=ch.x, cast=ch.cast) for ch in op_chunks(op, k, n, chunk_rows, res.rotate, backend))   # Ŵ's slot alone: no recorded output
+        if backend == "hip":
+            import torch
+
+            what = aq.quantize_hip(w, codes, got.p_row)
+            if not bool((what.to(torch.bfloat16).float() == what).all()):
+                raise RuntimeError(f"{name}: an AWQ weight is not a bf16 value, so its products with X are not exact in float32")
+            sums, m, _rec, _cast = hip_sums(_gptq_outputs(it, what, bias), w, [], bias)
+            s = sums[SLOTS.index("recorded")]
+        else:
+            sums, m, _rec, _cast = emulation_sums(it, w, [], bias, aq.quantize_emulation(w, codes, got.p_row))
+            s = sums[SLOTS.index("map")]
+        row = Row(name, nbytes, *_columns(s, float(m) * float(n)), tuple(s))
+        row.extra = {"alpha": got.alpha, "g": got.g, "calib_tokens": int(m_cal), "calib_loss": float(got.losses[got.g]),
+                     "rtn_calib_loss": float(got.losses[0]), "shifted_channels": int(np.count_nonzero(got.p_row)), "exponents": got.p_row}
         res.rows.append(row)

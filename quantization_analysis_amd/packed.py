@@ -2442,10 +2442,16 @@ def _product_class(o: _Orientation, name: str):
     """PackedLinear and PackedMatmul."""
     import torch
 
-    def init(self, pt, bias, out_dtype, kernel, backend, rotate):
+    def init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents=None):
         torch.nn.Module.__init__(self)
         _check_rank2(o, pt, name)
         self.rotate = check_block(o.n_k(pt)[1], rotate) if rotate else 0
+        exps = None
+        if in_exponents is not None:    # pt is packed from awq.scale_weight(w, p): x·2^−p per input channel, exact in bf16 (awq.py)
+            exps = np.asarray(in_exponents.cpu().numpy() if _is_torch(in_exponents) else in_exponents)
+            if exps.shape != (o.n_k(pt)[1],) or exps.size and (exps.min() < 0 or exps.max() > 7 or not np.array_equal(exps, np.rint(exps))):
+                raise ValueError(f"in_exponents must be {o.n_k(pt)[1]} integers in 0 .. 7")
+            exps = -torch.from_numpy(exps.astype(np.int32))
         _check_kernel(kernel, globals()[o.kernels])
         _check_out_dtype(out_dtype)
         self.backend = backend or ("hip" if pt.on_device else "emulation")
@@ -2469,20 +2475,22 @@ def _product_class(o: _Orientation, name: str):
                 need = max(size(m, n, k) for m in (range(1, SKINNY_MAX_M + 1) if o.module_size_every_m else (SKINNY_MAX_M,)))
                 self._workspace = torch.empty((need,), dtype=torch.uint8, device=data.device) if need else None
         self.register_buffer("bias", None if bias is None else bias.detach(), persistent=False)
+        self.register_buffer("neg_exponents", exps if exps is None or self.backend != "hip" else exps.to(_device_data(pt).device), persistent=False)
 
     class Product(torch.nn.Module):
         if o.kn:
             def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block",
-                         rotate: int = 0):
-                init(self, pt, bias, out_dtype, kernel, backend, rotate)
+                         rotate: int = 0, in_exponents=None):
+                init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents)
         else:
             def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", kernel: str = "auto", backend: Optional[str] = None,
-                         rotate: int = 0):
-                init(self, pt, bias, out_dtype, kernel, backend, rotate)
+                         rotate: int = 0, in_exponents=None):
+                init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents)
 
         def extra_repr(self) -> str:
             return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, kernel={self.kernel!r}, " \
-                   f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}"
+                   f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}" \
+                   + (f", rotate={self.rotate}" if self.rotate else "") + (", in_exponents=True" if self.neg_exponents is not None else "")
 
         @torch.no_grad()
         def forward(self, x):
@@ -2494,6 +2502,8 @@ def _product_class(o: _Orientation, name: str):
                 return torch.zeros(lead + (self.out_features,), dtype=_torch_dtype(self.out_dtype), device=x.device)
             if self.rotate:    # pt is packed from rotate_weight(w, rotate): the product needs x·H, formed online (csrc/mtq_hadamard.hip on hip)
                 x2 = hadamard(x2, self.rotate, out_dtype=torch.bfloat16, backend=self.backend)
+            if self.neg_exponents is not None:    # a torch op, not a kernel; composes after the rotation
+                x2 = torch.ldexp(x2, self.neg_exponents.to(x2.device))
             y = globals()[o.product](x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel,
                                      workspace=self._workspace)
             return _as_torch(y).reshape(lead + (self.out_features,))

@@ -73,7 +73,16 @@ def parse_args(argv=None):
     p.add_argument("--rotate", default=None, metavar="{B|auto}",
                    help="Evaluate every op rotated by a block Hadamard transform along k: B a power of two in [32, 4096], or auto = the "
                         "largest one dividing k.  An op whose k the block does not divide is skipped.")
+    p.add_argument("--awq", action="store_true",
+                   help="Add AWQ rows: per-input-channel power-of-two scales searched on the calibration activations, awq:<bfp*> and awq:<map>.")
+    p.add_argument("--awq-grid", type=int, default=20, metavar="G", help="AWQ: values of α tried, α = g / G for g = 0 .. G − 1.")
+    p.add_argument("--awq-max-shift", type=int, default=7, metavar="P", help="AWQ: the largest exponent shift, 1 .. 7.")
     args = p.parse_args(argv)
+    if args.awq:
+        if args.x_format != "bf16":
+            p.error("--awq needs --x-format bf16: the shifts are searched and evaluated on bf16 activations")
+        if args.awq_grid < 1 or not 1 <= args.awq_max_shift <= 7:
+            p.error("--awq-grid must be >= 1 and --awq-max-shift in 1 .. 7")
     if args.rotate is not None and args.rotate != "auto":
         try:
             args.rotate = check_block(int(args.rotate), int(args.rotate))
@@ -117,18 +126,20 @@ def main(argv=None) -> int:
     budgets = tuple(args.budget_bits or ())
     calib_io = args.calib_io or args.io_root
     calib = {}
-    if budgets or args.gptq:
+    if budgets or args.gptq or args.awq:
         cal_ops, _cal_skipped = select_ops(index, calib_io, query, args.calib_split, args.calib_max_samples)
         calib = {o.op: o for o in cal_ops}
     out_dir = Path(args.out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     records, csv_rows = [], []
     for op in ops:
-        extra = {"budgets": budgets, "calib": calib.get(op.op)} if budgets or args.gptq else {}
+        extra = {"budgets": budgets, "calib": calib.get(op.op)} if budgets or args.gptq or args.awq else {}
         if args.gptq:
             extra.update(gptq=True, gptq_damp=args.gptq_damp, gptq_factor=args.gptq_factor)
         if args.gptq_transpose:
             extra.update(gptq_transpose=True)
+        if args.awq:
+            extra.update(awq=True, awq_grid=args.awq_grid, awq_max_shift=args.awq_max_shift)
         if transpose:
             extra.update(transpose=True)
         if args.rotate:
@@ -145,13 +156,14 @@ def main(argv=None) -> int:
         print("-" * 90)
         for r in res.rows:
             print(f"{r.candidate:<28} | {_fmt(r.bytes, '14.0f')} | {r.pcc:12.8f} | {r.mae:12.6e} | {r.atol:12.6e}")
-            csv_rows.append([res.op, r.candidate, r.bytes, r.pcc, r.mae, r.atol, res.m, n, k] + ([res.rotate] if args.rotate else []))
+            csv_rows.append([res.op, r.candidate, r.bytes, r.pcc, r.mae, r.atol, res.m, n, k] + ([res.rotate] if args.rotate else [])
+                            + ([r.extra.get("alpha"), r.extra.get("calib_loss") if "alpha" in r.extra else None] if args.awq else []))
         rec = {"op": res.op, "weight": res.weight, "shape": [n, k], "M": res.m, "splits": res.splits, "x_cast": res.x_cast,
                "rows": [{"candidate": r.candidate, "bytes": r.bytes, "pcc": r.pcc, "mae": r.mae, "atol": r.atol,
-                         **{key: v for key, v in r.extra.items() if key != "assignment"}} for r in res.rows]}
+                         **{key: v for key, v in r.extra.items() if key not in ("assignment", "exponents")}} for r in res.rows]}
         if args.rotate:
             rec["rotate"] = res.rotate
-        if budgets or args.gptq:
+        if budgets or args.gptq or args.awq:
             rec["calib_splits"] = res.calib_splits
             rec["budget_skipped"] = [{"candidate": c, "reason": why} for c, why in res.budget_skipped]
             for c, why in res.budget_skipped:
@@ -163,6 +175,10 @@ def main(argv=None) -> int:
                         d.mkdir(parents=True, exist_ok=True)
                         tag = "_transpose" if r.extra.get("layout") == "transpose" else ""
                         np.save(d / f"budget_{bits_tag(r.extra['bits'])}_{r.extra['basis']}{tag}.npy", r.extra["assignment"])
+                    if "exponents" in r.extra:
+                        d = out_dir / "maps" / res.op
+                        d.mkdir(parents=True, exist_ok=True)
+                        np.save(d / f"{r.candidate.replace(':', '_')}_exponents.npy", r.extra["exponents"])
         records.append(rec)
     if skipped:
         print("\nskipped:")
@@ -170,19 +186,22 @@ def main(argv=None) -> int:
             print(f"  {op}: {why}")
     with open(out_dir / "layer_output_error.csv", "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["op", "candidate", "bytes", "pcc", "mae", "atol", "M", "N", "K"] + (["rotate"] if args.rotate else []))
+        w.writerow(["op", "candidate", "bytes", "pcc", "mae", "atol", "M", "N", "K"] + (["rotate"] if args.rotate else [])
+                   + (["awq_alpha", "awq_calib_loss"] if args.awq else []))
         w.writerows(csv_rows)
     doc = {"repo_or_url": args.repo_or_url, "io_root": args.io_root, "backend": args.backend, "formats": formats,
            "compression_config": args.compression_config, "split": args.split, "max_samples": args.max_samples, "x_format": args.x_format,
            "ops": records, "skipped": [{"op": o, "reason": r} for o, r in skipped]}
     if budgets:
         doc.update({"budget_bits": list(budgets)})
-    if budgets or args.gptq:
+    if budgets or args.gptq or args.awq:
         doc.update({"calib_io": calib_io, "calib_split": args.calib_split, "calib_max_samples": args.calib_max_samples})
     if args.gptq:
         doc.update({"gptq_damp": args.gptq_damp, "gptq_factor": args.gptq_factor})
     if args.gptq_transpose:
         doc.update({"gptq_transpose": True})
+    if args.awq:
+        doc.update({"awq_grid": args.awq_grid, "awq_max_shift": args.awq_max_shift})
     if transpose:
         doc.update({"transpose": True})
     if args.rotate:
