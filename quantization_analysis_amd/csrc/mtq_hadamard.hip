@@ -28,6 +28,7 @@
 
 #include "mtq_device.hpp"
 #include "mtq_error.hpp"
+#include "mtq_hadamard_stages.hpp"
 
 namespace mtq {
 namespace {
@@ -35,49 +36,7 @@ namespace {
 constexpr int kHadWaves = 4;                      // independent waves per workgroup
 constexpr int64_t kHadMaxBlocks = 1 << 20;        // waves walk the segments beyond that
 
-__device__ __forceinline__ float bits_f(uint32_t v) { return __uint_as_float(v); }
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v)
-{
-    return bits_f((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), CTRL, 0xF, 0xF, true));
-}
-
-// the value of lane ^ D, D inside a DPP row
-template <int D>
-__device__ __forceinline__ float partner(float v)
-{
-    if constexpr (D == 1) return dpp_f<0xB1>(v);                 // quad_perm [1, 0, 3, 2]
-    else if constexpr (D == 2) return dpp_f<0x4E>(v);            // quad_perm [2, 3, 0, 1]
-    else if constexpr (D == 4) return dpp_f<0x1B>(dpp_f<0x141>(v));   // row_half_mirror (i ^ 7), then quad_perm [3, 2, 1, 0] (i ^ 3)
-    else return dpp_f<0x128>(v);                                 // row_ror:8 (i ^ 8 in a row of 16)
-}
-
-// lanes l and l ^ D, l & D == 0, hold a and b → a + b and a − b.  flip: the sign bit where lane & D.
-template <int D, int N>
-__device__ __forceinline__ void row_stage(float (&v)[N], uint32_t flip)
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = partner<D>(v[i]) + bits_f(__float_as_uint(v[i]) ^ flip);
-}
-
-// the same for D = 16 (HALF = false: the odd rows of the first operand change places with the even rows of the second) and D = 32
-// (HALF = true: the upper half of the first with the lower half of the second), two registers at a time
-template <bool HALF, int N>
-__device__ __forceinline__ void swap_stage(float (&v)[N])
-{
-#pragma unroll
-    for (int i = 0; i < N; i += 2) {
-        const uint32_t a = __float_as_uint(v[i]), b = __float_as_uint(v[i + 1]);
-        const auto r = HALF ? __builtin_amdgcn_permlane32_swap(a, b, false, false) : __builtin_amdgcn_permlane16_swap(a, b, false, false);
-        // r[0]: the lower partners' a, then their b, in the upper partners' lanes; r[1]: the upper partners' a in the lower lanes, then b
-        const float lo = bits_f(r[0]), hi = bits_f(r[1]);
-        const uint32_t s = __float_as_uint(lo + hi), d = __float_as_uint(lo - hi);
-        const auto q = HALF ? __builtin_amdgcn_permlane32_swap(s, d, false, false) : __builtin_amdgcn_permlane16_swap(s, d, false, false);
-        v[i] = bits_f(q[0]);
-        v[i + 1] = bits_f(q[1]);
-    }
-}
+using had::bits_f;
 
 template <int N>
 __device__ __forceinline__ void load_lane(const uint16_t *p, bool vec, float (&v)[N])
@@ -175,8 +134,6 @@ __global__ __launch_bounds__(64 * kHadWaves) void hadamard_rows_kernel(const TI 
     const int lane = threadIdx.x & 63;
     const int64_t first = (int64_t)blockIdx.x * kHadWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t step = (int64_t)gridDim.x * kHadWaves;
-    const uint32_t flip1 = (uint32_t)(lane & 1) << 31, flip2 = (uint32_t)(lane & 2) << 30, flip4 = (uint32_t)(lane & 4) << 29,
-                   flip8 = (uint32_t)(lane & 8) << 28;
     for (int64_t u = first; u < units; u += step) {
         const int64_t row = u / nseg, col = (u - row * nseg) * (64 * N) + (int64_t)lane * N;
         const bool live = col < k;
@@ -184,25 +141,7 @@ __global__ __launch_bounds__(64 * kHadWaves) void hadamard_rows_kernel(const TI 
 #pragma unroll
         for (int i = 0; i < N; ++i) v[i] = 0.0f;
         if (live) load_lane<N>(x + row * ldx + col, (vec & 1) != 0, v);
-#pragma unroll
-        for (int h = 1; h < N; h <<= 1) {
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                if (!(i & h)) {
-                    const float a = v[i], b = v[i + h];
-                    v[i] = a + b;
-                    v[i + h] = a - b;
-                }
-            }
-        }
-        row_stage<1, N>(v, flip1);
-        if (lane_stages > 1) row_stage<2, N>(v, flip2);
-        if (lane_stages > 2) row_stage<4, N>(v, flip4);
-        if (lane_stages > 3) row_stage<8, N>(v, flip8);
-        if (lane_stages > 4) swap_stage<false, N>(v);
-        if (lane_stages > 5) swap_stage<true, N>(v);
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[i] *= scale;
+        had::rotate_lanes<N>(v, lane, lane_stages, scale);
         if constexpr (sizeof(TO) == 4) {
             if (live) store_lane<N>(y + row * ldy + col, (vec & 2) != 0, v);
         } else {
@@ -298,14 +237,10 @@ extern "C" int mtq_hadamard_rows(const void *x, int x_dtype, int64_t rows, int64
     if (yq && (overlap(yq, qb, x, xb) || overlap(yq, qb, y, yb))) return fail(MTQ_ERR_INVALID, "yq overlaps x or y");
     if (int rc = require_device()) return rc;
 
-    int p = 0;
-    while (((int64_t)1 << p) < block) ++p;
     const int n = block <= 1024 ? 16 : (int)(block / 64);
-    int lanes_log = 0;
-    while ((n << lanes_log) < block) ++lanes_log;
     HadArgs a;
-    a.x = x; a.k = k; a.ldx = ldx; a.lane_stages = lanes_log;
-    a.scale = (float)std::ldexp((p & 1) ? std::sqrt(0.5) : 1.0, -(p / 2));          // float32(2^(−p/2))
+    a.x = x; a.k = k; a.ldx = ldx; a.lane_stages = had::lane_stages(block, n);
+    a.scale = had::block_scale(block);
     a.y = y; a.ldy = ldy; a.yq = static_cast<uint16_t *>(yq); a.ldq = ldq;
     a.vec = (vec16(x, ldx, xsz) ? 1 : 0) | (vec16(y, ldy, ysz) ? 2 : 0) | (yq && vec16(yq, ldq, 2) ? 4 : 0);
     a.nseg = (k + 64 * n - 1) / (64 * n);

@@ -71,6 +71,7 @@
 
 #include "mtq_device.hpp"
 #include "mtq_error.hpp"
+#include "mtq_hadamard_stages.hpp"
 #include "mtq_glu.hpp"
 
 namespace mtq {
@@ -1027,10 +1028,19 @@ struct FeedDirect {
 // of kSkinnyRing tiles (group gi of W, and X) are issued before the first is decoded; a blob is checked wave-uniformly (stream_at) before
 // it is touched; decode_skinny, then `feed` (two MFMAs per tile, ascending K).  `lane` hands out, (row, half, gi) address: the grouped
 // kernel forms the latter anew per chunk.  Feed::kGroupIsKRow: group gi is k-row gi / 2 of its tile, zeros at or past K.
-template <typename Feed>
+// XS: where the lane's 16 X values of tile c come from; XGlobal, load_x16 on x itself, is every kernel's but the _pre kernels'.
+struct XGlobal {
+    __device__ __forceinline__ void operator()(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec, int row, int64_t c,
+                                               int half, uint4 &lo, uint4 &hi) const
+    {
+        load_x16(x, M, K, ldx, x_vec, row, c * kTile + kGroup * half, lo, hi);
+    }
+};
+
+template <typename Feed, typename XS = XGlobal>
 __device__ __forceinline__ void skinny_run(f32x16 &acc, const Feed &feed, const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx,
                                            int x_vec, const PackedStream &st, int64_t t0, int64_t tstep, int64_t c0, int64_t c1, int lane, int row,
-                                           int half, int gi)
+                                           int half, int gi, const XS &xs = XS())
 {
     const uint8_t *__restrict__ packed = st.packed;
     const int8_t *__restrict__ map = st.map;
@@ -1059,7 +1069,7 @@ __device__ __forceinline__ void skinny_run(f32x16 &acc, const Feed &feed, const 
                     if constexpr (Feed::kGroupIsKRow) {
                         if ((cb + i) * kTile + (gi >> 1) >= K) a.f = -1;   // this lane's k-row
                     }
-                    load_x16(x, M, K, ldx, x_vec, row, (cb + i) * kTile + kGroup * half, xl[j], xh[j]);
+                    xs(x, M, K, ldx, x_vec, row, cb + i, half, xl[j], xh[j]);
                 }
                 load_group(packed, a, gi, g[j]);
             }
@@ -2062,6 +2072,191 @@ __global__ __launch_bounds__(256) void glu_skinny_reduce_kernel(const float *__r
     g += bias_gate ? bias_gate[n] : 0.0f;
     u += bias_up ? bias_up[n] : 0.0f;
     store_y<BF16OUT>(yv, m * ldy + n, glu_value(g, u, act));
+}
+
+// ---- the X prologue of the skinny kernels (the _pre entries): the wave multiplies X″ = bf16(X′ · 2^−p), X′ = mtq_hadamard_rows' bf16
+// output for block B (X′ = X for B = 0), p the per-channel shifts in 0..7 (none: X″ = X′), formed where the skinny wave reads X.
+//
+// B > 0.  A workgroup is four tile rows (the gated kernel: two tile rows × two projections) of ONE K slice, and walks the slice in panels
+// of P columns, P a multiple of B that divides the slice, at most kPreMaxPanel.  Per panel the m live rows × P / 16 lanes' worth of
+// 16-column pieces are numbered row-major and dealt to the waves 64 at a time (B / 16 divides 64 and P / 16, so a block's lanes are
+// neighbours of one pass): at m = 1 and P = 1024 wave 0 makes one pass and the others wait at the barrier; rows at or past m are not
+// formed.  A pass is hadamard_rows_kernel's for N = 16 (mtq_hadamard_stages.hpp: the same butterflies, the same multiply), then
+// bf16_round_bits, the shift on the bf16 word (bf16_shift_down) and one 32-byte store into the image [m][P] bf16.  The 32-byte pieces of
+// a row are swizzled by the row (piece ^ (row & 7), when a row has a multiple of 8 pieces): the MFMA-side read of lane (row, half) is
+// piece 2 (c − c_first) + half of row `row`, and without the swizzle all 32 rows of a half would start on one bank.  One barrier
+// publishes the panel, skinny_run takes its X words from it (XLds) for the panel's tiles - the same tiles, ascending, into the same
+// accumulator as the unfused wave - and a second barrier frees the image.  A wave whose tile row is past tiles_h takes part in the
+// passes and the barriers and skips the product and the store.
+// B = 0 (shifts only): no LDS and no barrier; the lane shifts its own 16 words after load_x16 (XShift).
+constexpr int kPreMaxPanel = 1024;                   // 32 rows × 1024 bf16 = 64 KB at m = 32: two workgroups to a CU
+
+// bf16 word h → RNE of its exact value · 2^−p, 0 <= p <= 7: an exponent-field subtract while the result is normal, the subnormal
+// rounding otherwise; Inf and NaN stay
+__device__ __forceinline__ uint32_t bf16_shift_down(uint32_t h, uint32_t p)
+{
+    const uint32_t e = (h >> 7) & 0xFFu;
+    if (e == 0xFFu || p == 0u) return h;
+    if (e > p) return h - (p << 7);
+    const uint32_t sig = e ? (0x80u | (h & 0x7Fu)) : (h & 0x7Fu), sh = p + 1u - (e ? e : 1u);   // the value is sig · 2^−sh subnormal units
+    const uint32_t r = sh ? (sig + ((1u << sh) >> 1) - 1u + ((sig >> sh) & 1u)) >> sh : sig;
+    return (h & 0x8000u) | r;
+}
+
+// two bf16 in a word, shifts in bytes 0 and 1 of e
+__device__ __forceinline__ uint32_t bf16x2_shift_down(uint32_t w, uint32_t e)
+{
+    return bf16_shift_down(w & 0xFFFFu, e & 7u) | (bf16_shift_down(w >> 16, (e >> 8) & 7u) << 16);
+}
+
+__device__ __forceinline__ void shift_x16(uint4 &lo, uint4 &hi, const uint4 &e)
+{
+    lo = make_uint4(bf16x2_shift_down(lo.x, e.x), bf16x2_shift_down(lo.y, e.x >> 16), bf16x2_shift_down(lo.z, e.y),
+                    bf16x2_shift_down(lo.w, e.y >> 16));
+    hi = make_uint4(bf16x2_shift_down(hi.x, e.z), bf16x2_shift_down(hi.y, e.z >> 16), bf16x2_shift_down(hi.z, e.w),
+                    bf16x2_shift_down(hi.w, e.w >> 16));
+}
+
+// the shifts of channels k0 .. k0 + 15 (k0 a multiple of 16, exps 16-byte aligned), zeros at or past K
+__device__ __forceinline__ uint4 load_shifts(const uint8_t *__restrict__ exps, int64_t k0, int64_t K)
+{
+    if (k0 + kGroup <= K) return *reinterpret_cast<const uint4 *>(exps + k0);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    for (int j = 0; j < kGroup; ++j)
+        if (k0 + j < K) w[j >> 2] |= (uint32_t)exps[k0 + j] << (8 * (j & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+struct XShift {
+    const uint8_t *__restrict__ exps;
+    __device__ __forceinline__ void operator()(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec, int row, int64_t c,
+                                               int half, uint4 &lo, uint4 &hi) const
+    {
+        const int64_t k0 = c * kTile + kGroup * half;
+        load_x16(x, M, K, ldx, x_vec, row, k0, lo, hi);
+        if (row >= M || k0 >= K) return;
+        shift_x16(lo, hi, load_shifts(exps, k0, K));
+    }
+};
+
+struct XLds {
+    const uint16_t *img;                             // [M][pitch] bf16, 32-byte pieces swizzled by `mask`
+    int pitch, mask;
+    int64_t c_first;                                 // the panel's first tile
+    __device__ __forceinline__ void operator()(const uint16_t *__restrict__, int64_t M, int64_t, int64_t, int, int row, int64_t c, int half,
+                                               uint4 &lo, uint4 &hi) const
+    {
+        if (row >= M) return;                        // zeros, as load_x16: rows at or past m are not in the image
+        const int piece = (2 * (int)(c - c_first) + half) ^ (row & mask);
+        const uint4 *src = reinterpret_cast<const uint4 *>(img + row * pitch + piece * kGroup);
+        lo = src[0];
+        hi = src[1];
+    }
+};
+
+struct PreArgs {
+    int panel, lane_stages;                          // P (0: shifts only) and log2(B / 16)
+    float scale;                                     // float32(2^(−log2(B)/2))
+    const uint8_t *exps;                             // K shifts, or null
+};
+
+// columns [col0, col0 + P) of rows [0, M) of x → the image; every wave of the workgroup calls it (wave: uniform)
+__device__ __forceinline__ void pre_panel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec, int64_t col0,
+                                          const PreArgs &a, uint16_t *img, int mask, int lane, int wave)
+{
+    const int lpr = a.panel / kGroup, items = (int)M * lpr;
+    for (int q0 = 64 * wave; q0 < items; q0 += 64 * kSkinnyWaves) {
+        const int q = q0 + lane, r = q / lpr, c = (q - r * lpr) * kGroup;
+        const bool live = q < items;                 // a dead lane rotates zeros: EXEC stays full for the cross-lane stages
+        float v[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) v[i] = 0.0f;
+        if (live) {
+            uint4 lo, hi;
+            load_x16(x, M, K, ldx, x_vec, r, col0 + c, lo, hi);
+            const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u); }
+        }
+        had::rotate_lanes<kGroup>(v, lane, a.lane_stages, a.scale);
+        uint32_t y[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) y[i] = bf16_round_bits(__float_as_uint(v[i]));
+        uint4 lo, hi;
+        pack_halves(y, lo, hi);
+        if (live) {
+            if (a.exps) shift_x16(lo, hi, load_shifts(a.exps, col0 + c, K));
+            uint4 *dst = reinterpret_cast<uint4 *>(img + r * a.panel + (((c / kGroup) ^ (r & mask)) * kGroup));
+            dst[0] = lo;
+            dst[1] = hi;
+        }
+    }
+}
+
+// one wave's part of a _pre kernel: the run of tile row tr over tiles [c0, c1) of `st`, `live` false for a wave without a unit
+template <bool ROT>
+__device__ __forceinline__ void pre_run(f32x16 &acc, bool live, const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec,
+                                        const PreArgs &a, const PackedStream &st, int64_t t0, int64_t c0, int64_t c1, uint16_t *img, int lane,
+                                        int wave)
+{
+    const int row = lane & 31, half = lane >> 5;
+    if constexpr (ROT) {
+        const int mask = (a.panel / kGroup) % 8 == 0 ? 7 : 0, step = a.panel / kTile;
+        for (int64_t cp = c0; cp < c1; cp += step) {
+            pre_panel(x, M, K, ldx, x_vec, cp * kTile, a, img, mask, lane, wave);
+            __syncthreads();
+            if (live) skinny_run(acc, FeedDirect(), x, M, K, ldx, x_vec, st, t0, 1, cp, cp + step, lane, row, half, 2 * row + half,
+                                 XLds{img, a.panel, mask, cp});
+            __syncthreads();
+        }
+    } else {
+        if (live) skinny_run(acc, FeedDirect(), x, M, K, ldx, x_vec, st, t0, 1, c0, c1, lane, row, half, 2 * row + half, XShift{a.exps});
+    }
+}
+
+// packed_linear_skinny_kernel on X″.  Workgroup b: slice b / ceil(tiles_h / 4), tile rows 4 (b % ceil(tiles_h / 4)) + wave.
+template <bool BF16OUT, bool ROT>
+__global__ __launch_bounds__(64 * kSkinnyWaves) void packed_linear_skinny_pre_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec, PreArgs a, const uint8_t *__restrict__ packed,
+    uint64_t packed_bytes, const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N, int64_t tiles_h, int64_t tiles_w,
+    int split, const float *__restrict__ bias, void *__restrict__ yv, int64_t ldy, float *__restrict__ ws)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t pre_img[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t rb = (tiles_h + kSkinnyWaves - 1) / kSkinnyWaves, s = blockIdx.x / rb, tr = (blockIdx.x % rb) * kSkinnyWaves + wave;
+    const bool live = tr < tiles_h;                  // wave-uniform
+
+    f32x16 acc = zero16();
+    pre_run<ROT>(acc, live, x, M, K, ldx, x_vec, a, tensor_stream(packed, packed_bytes, map, offsets), tr * tiles_w, s * tiles_w / split,
+                 (s + 1) * tiles_w / split, pre_img, lane, wave);
+
+    const int64_t n = tr * kTile + (lane & 31);
+    if (!live || n >= N) return;
+    store_skinny<BF16OUT>(acc, M, lane >> 5, 0, n, split, split == 1 && bias ? bias[n] : 0.0f, yv, ldy, ws, s, M, N);
+}
+
+// packed_glu_skinny_kernel on X″: wave w is projection w & 1 of tile row 2 (b % ceil(tiles_h / 2)) + (w >> 1), so the panel is formed
+// once for both streams.  Partials to ws[p][s][m][n], glu_skinny_reduce_kernel finishes.
+template <bool ROT>
+__global__ __launch_bounds__(64 * kSkinnyWaves) void packed_glu_skinny_pre_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec, PreArgs a, const uint8_t *__restrict__ gate, uint64_t gate_bytes,
+    const int8_t *__restrict__ gate_map, const uint32_t *__restrict__ gate_offsets, const uint8_t *__restrict__ up, uint64_t up_bytes,
+    const int8_t *__restrict__ up_map, const uint32_t *__restrict__ up_offsets, int64_t N, int64_t tiles_h, int64_t tiles_w, int split,
+    float *__restrict__ ws)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t pre_img[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t rb = (tiles_h + 1) / 2, s = blockIdx.x / rb, tr = (blockIdx.x % rb) * 2 + (wave >> 1);
+    const int p = wave & 1;
+    const bool live = tr < tiles_h;                  // wave-uniform
+    const PackedStream st = tensor_stream(p ? up : gate, p ? up_bytes : gate_bytes, p ? up_map : gate_map, p ? up_offsets : gate_offsets);
+
+    f32x16 acc = zero16();
+    pre_run<ROT>(acc, live, x, M, K, ldx, x_vec, a, st, tr * tiles_w, s * tiles_w / split, (s + 1) * tiles_w / split, pre_img, lane, wave);
+
+    const int64_t n = tr * kTile + (lane & 31);
+    if (!live || n >= N) return;
+    store_lane_rows<false, true>(acc, M, lane >> 5, ws, (((int64_t)p * split + s) * M + 4 * (lane >> 5)) * N + n, N, 0.0f);
 }
 
 // ---- the gather of an MoE layer in a grouped skinny wave's X address (GATHER of the two grouped skinny GLU kernels below).
@@ -3372,6 +3567,134 @@ extern "C" int mtq_packed_glu_matmul_skinny(const void *x, int64_t m, int64_t k,
 {
     return packed_glu_skinny(true, "mtq_packed_glu_matmul_skinny", x, m, k, ldx, gate_packed, gate_bytes, gate_map, gate_offsets, up_packed, up_bytes,
                              up_map, up_offsets, n, bias_gate, bias_up, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream);
+}
+
+// 9b. the skinny entries with the X prologue (rotation by block, shifts by in_exponents) inside the kernel
+// The split and the panel of (m, n, k, block, split): skinny_shape's answer for block 0; for a block, slices of equal length that are
+// whole blocks - split 0: the largest s <= skinny_split with tiles_w % s == 0 and (tiles_w / s) % (block / 32) == 0 - and the largest
+// panel <= kPreMaxPanel that is a multiple of block and divides a slice.
+static int pre_shape(int64_t m, int64_t n, int64_t k, int64_t block, int split, TileGrid &g, int *panel)
+{
+    if (int rc = skinny_shape(m, n, k, split, &g.th, &g.tw, &g.eff)) return rc;
+    *panel = 0;
+    if (block == 0) return MTQ_OK;
+    if (block < 32 || (block & (block - 1)) != 0) return fail(MTQ_ERR_INVALID, "block must be 0 or a power of two from 32 on");
+    if (k % block != 0) return fail(MTQ_ERR_INVALID, "k is not a multiple of block");
+    if (block > kPreMaxPanel) return fail(MTQ_ERR_INVALID, "no panel of this block fits the LDS image (block > 1024): use the staged route");
+    const int64_t bt = block / kTile;
+    if (split == 0) {
+        while (g.eff > 1 && (g.tw % g.eff != 0 || (g.tw / g.eff) % bt != 0)) --g.eff;
+    } else if (g.tw % g.eff != 0 || (g.tw / g.eff) % bt != 0) {
+        return fail(MTQ_ERR_INVALID, "this split does not cut K into equal slices of whole blocks");
+    }
+    const int64_t cols = g.tw / g.eff * kTile;
+    int64_t p = std::min<int64_t>(cols, kPreMaxPanel) / block * block;
+    while (cols % p != 0) p -= block;
+    *panel = (int)p;
+    return MTQ_OK;
+}
+
+extern "C" int mtq_packed_skinny_pre_split(int64_t m, int64_t n, int64_t k, int64_t block, int split)
+{
+    TileGrid g;
+    int panel;
+    if (pre_shape(m, n, k, block, split, g, &panel)) return -1;
+    return g.eff;
+}
+
+extern "C" size_t mtq_packed_linear_skinny_pre_workspace_bytes(int64_t m, int64_t n, int64_t k, int64_t block, int split)
+{
+    TileGrid g;
+    int panel;
+    if (pre_shape(m, n, k, block, split, g, &panel)) return (size_t)-1;
+    return skinny_workspace(m, n, g.eff);
+}
+
+extern "C" size_t mtq_packed_glu_skinny_pre_workspace_bytes(int64_t m, int64_t n, int64_t k, int64_t block, int split)
+{
+    TileGrid g;
+    int panel;
+    if (pre_shape(m, n, k, block, split, g, &panel)) return (size_t)-1;
+    return glu_skinny_workspace(m, n, g.eff);
+}
+
+static int pre_args(int64_t block, const uint8_t *in_exponents, int panel, PreArgs &a)
+{
+    if (block == 0 && !in_exponents) return fail(MTQ_ERR_INVALID, "block is 0 and in_exponents is null: there is no prologue to fuse");
+    if (in_exponents) {
+        if (int rc = aligned_arg(in_exponents, "in_exponents")) return rc;
+    }
+    a.panel = panel;
+    a.lane_stages = block ? had::lane_stages(block, kGroup) : 0;
+    a.scale = block ? had::block_scale(block) : 1.0f;
+    a.exps = in_exponents;
+    return MTQ_OK;
+}
+
+extern "C" int mtq_packed_linear_skinny_pre(const void *x, int64_t m, int64_t k, int64_t ldx, int64_t block, const uint8_t *in_exponents,
+                                            const void *packed, size_t packed_bytes, const int8_t *map, const uint32_t *offsets, int64_t n,
+                                            const float *bias, void *y, int out_dtype, int64_t ldy, int split, void *workspace,
+                                            size_t workspace_bytes, void *stream)
+{
+    const char *name = "mtq_packed_linear_skinny_pre";
+    TileGrid g;
+    int panel = 0;
+    const StreamArg w = {packed, packed_bytes};
+    if (int rc = gemm_args(!x || !packed || !map || !offsets || !y, out_dtype,
+                           [&](TileGrid &s) { return pre_shape(m, n, k, block, split, s, &panel); }, g, k, ldx, n, ldy, false, 0, 0, w, w))
+        return rc;
+    PreArgs a;
+    if (int rc = pre_args(block, in_exponents, panel, a)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(m, n, g.eff), kWsSplit, "split")) return rc;
+    const int64_t blocks = (g.th + kSkinnyWaves - 1) / kSkinnyWaves * g.eff;
+    if (int rc = grid_args({blocks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    const bool bf = out_dtype == MTQ_DTYPE_BF16;
+    auto kernel = block ? (bf ? packed_linear_skinny_pre_kernel<true, true> : packed_linear_skinny_pre_kernel<false, true>)
+                        : (bf ? packed_linear_skinny_pre_kernel<true, false> : packed_linear_skinny_pre_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), (size_t)m * panel * sizeof(uint16_t), st,
+                       static_cast<const uint16_t *>(x), m, k, ldx, (int)x_vec_of(x, ldx), a, static_cast<const uint8_t *>(packed),
+                       (uint64_t)packed_bytes, map, offsets, n, g.th, g.tw, g.eff, bias, y, ldy, ws);
+    if (g.eff > 1) {
+        if (int rc = check_launch(name)) return rc;
+        launch_out(out_dtype, skinny_reduce_kernel<true>, skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
+                   m * n, n, g.eff, bias, y, ldy);
+    }
+    return check_launch(name);
+}
+
+extern "C" int mtq_packed_glu_skinny_pre(const void *x, int64_t m, int64_t k, int64_t ldx, int64_t block, const uint8_t *in_exponents,
+                                         const void *gate_packed, size_t gate_bytes, const int8_t *gate_map, const uint32_t *gate_offsets,
+                                         const void *up_packed, size_t up_bytes, const int8_t *up_map, const uint32_t *up_offsets, int64_t n,
+                                         const float *bias_gate, const float *bias_up, int act, void *y, int out_dtype, int64_t ldy, int split,
+                                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *name = "mtq_packed_glu_skinny_pre";
+    TileGrid g;
+    int panel = 0;
+    if (int rc = gemm_args(!x || !gate_packed || !gate_map || !gate_offsets || !up_packed || !up_map || !up_offsets || !y, out_dtype,
+                           [&](TileGrid &s) { return pre_shape(m, n, k, block, split, s, &panel); }, g, k, ldx, n, ldy, false, 0, 0,
+                           {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
+    if (int rc = glu_act(act)) return rc;
+    PreArgs a;
+    if (int rc = pre_args(block, in_exponents, panel, a)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(m, n, g.eff), kWsGlu, "split")) return rc;
+    const int64_t blocks = (g.th + 1) / 2 * g.eff;
+    if (int rc = grid_args({blocks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(block ? packed_glu_skinny_pre_kernel<true> : packed_glu_skinny_pre_kernel<false>, dim3((unsigned)blocks),
+                       dim3(64 * kSkinnyWaves), (size_t)m * panel * sizeof(uint16_t), st, static_cast<const uint16_t *>(x), m, k, ldx,
+                       (int)x_vec_of(x, ldx), a, static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_map, gate_offsets,
+                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_map, up_offsets, n, g.th, g.tw, g.eff, ws);
+    if (int rc = check_launch(name)) return rc;
+    launch_out(out_dtype, glu_skinny_reduce_kernel<true>, glu_skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws,
+               m * n, n, g.eff, bias_gate, bias_up, act, y, ldy);
+    return check_launch(name);
 }
 
 // 10. glu skinny grouped.  grouped_shape and the bound that keeps the two projections' partials inside size_t at every split

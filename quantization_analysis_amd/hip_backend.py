@@ -207,6 +207,15 @@ GLU_CHUNKED_SIGNATURES = {
     "mtq_packed_matmul_skinny_grouped_chunked_combine": ("i", "pllppzpppllipplpilllpilipzp", True),
 }
 GLU_CHUNKED_EXPORTS = tuple(GLU_CHUNKED_SIGNATURES)
+# include/mtq_packed_pre.h, which mtq.h includes after it: the skinny products with the X prologue (rotation, channel shifts) inside
+PACKED_PRE_SIGNATURES = {
+    "mtq_packed_skinny_pre_split": ("i", "lllli", True),
+    "mtq_packed_linear_skinny_pre_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_linear_skinny_pre": ("i", "pllllppzpplppilipzp", True),
+    "mtq_packed_glu_skinny_pre_workspace_bytes": ("z", "lllli", True),
+    "mtq_packed_glu_skinny_pre": ("i", "pllllppzpppzpplppipilipzp", True),
+}
+PACKED_PRE_EXPORTS = tuple(PACKED_PRE_SIGNATURES)
 _CTYPE = {"p": ctypes.c_void_p, "l": ctypes.c_int64, "u": ctypes.c_uint32, "i": ctypes.c_int, "d": ctypes.c_double, "z": ctypes.c_size_t,
           "q": ctypes.c_uint64, "v": None, "s": ctypes.c_char_p}
 
@@ -264,7 +273,7 @@ def _bind(L) -> None:
     found = version()
     if found < MTQ_VERSION:
         raise MtqError(f"{LIB_PATH} is version {found}, older than this package (it needs {MTQ_VERSION}): {_REBUILD}")
-    for name, (result, params, optional) in (*SIGNATURES.items(), *MOE_DECODE_SIGNATURES.items(), *GLU_CHUNKED_SIGNATURES.items()):
+    for name, (result, params, optional) in (*SIGNATURES.items(), *MOE_DECODE_SIGNATURES.items(), *GLU_CHUNKED_SIGNATURES.items(), *PACKED_PRE_SIGNATURES.items()):
         fn = getattr(L, name, None)
         if fn is None:
             if optional:
@@ -1444,7 +1453,15 @@ def _grid_error(tables, n: int, k: int, kn: bool, side: str = "") -> MtqError:
     return MtqError(f"the {side}map is {tables.tiles_h}x{tables.tiles_w} tiles, a {rows}x{cols} {noun} has {own}")
 
 
-def _packed_product_call(name, kn, empty, x, data, tables, n, bias, out_dtype, out, stream, size=None, split=0, workspace=None, size_first=False):
+def _packed_pre_args(x, k: int, block, in_exponents) -> tuple:
+    """(block, pointer) of a _pre entry: in_exponents None, or a uint8 device tensor of k shifts in 0 .. 7."""
+    if in_exponents is None:
+        return int(block), None
+    return int(block), _buffer(in_exponents, _torch().uint8, k, "in_exponents")
+
+
+def _packed_product_call(name, kn, empty, x, data, tables, n, bias, out_dtype, out, stream, size=None, split=0, workspace=None, size_first=False,
+                         pre=None):
     """The checks and the call the single-tensor product entries share.  empty: which of "m" and "n" being 0 ends here with the empty
     `out` ("" : the library's refusal of empty operands reaches the caller).  size: a skinny entry's own size function, which makes
     the call one with m <= 32, a split and a workspace; size_first: it is asked before `out` is looked at."""
@@ -1460,6 +1477,8 @@ def _packed_product_call(name, kn, empty, x, data, tables, n, bias, out_dtype, o
         raise _grid_error(tables, n, k, kn)
     ptr = _packed_stream(data, tables)
     bias_ptr = None if bias is None else _buffer(bias, torch.float32, n, "bias")
+    if pre is not None:                              # a _pre entry: (block, in_exponents) behind ldx, and the size function takes the block
+        pre, block, size = _packed_pre_args(x, k, *pre), int(pre[0]), (lambda m, n, k, split, size=size: size(m, n, k, block, split))
     need = size(m, n, k, split) if size_first else None
     fn = _entry(name)
     out, ldy = _packed_out(out, m, n, out_dtype, x.device)
@@ -1469,7 +1488,7 @@ def _packed_product_call(name, kn, empty, x, data, tables, n, bias, out_dtype, o
     if size is not None:
         need = size(m, n, k, split) if need is None else need
         more = (int(split), *(_packed_workspace(workspace, need, x.device) if need else (None, 0)))
-    check(fn(x.data_ptr(), m, k, ldx, ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, *more,
+    check(fn(x.data_ptr(), m, k, ldx, *(pre or ()), ptr, tables.nbytes, tables.map_ptr, tables.offsets_ptr, n, bias_ptr, out.data_ptr(), code, ldy, *more,
              _packed_stream_ptr(stream)))
     return out
 
@@ -1616,6 +1635,41 @@ def packed_linear_skinny(x, data, tables: PackedTables, n: int, bias=None, out_d
     allocated here when none is given.  The same inputs and the same split give the same bits."""
     return _packed_product_call("mtq_packed_linear_skinny", False, "", x, data, tables, n, bias, out_dtype, out, stream,
                                 packed_linear_skinny_workspace_bytes, split, workspace, size_first=True)
+
+
+PACKED_PRE_MAX_BLOCK = 1024   # csrc/mtq_packed.hip kPreMaxPanel: the widest block one LDS panel holds
+
+
+def packed_pre_available() -> bool:
+    """Whether this build of the library has the skinny entries with the X prologue inside (mtq_packed_linear_skinny_pre,
+    mtq_packed_glu_skinny_pre, their size functions and the split rule; optional symbols)."""
+    return _has(PACKED_PRE_EXPORTS)
+
+
+def packed_skinny_pre_split(m: int, n: int, k: int, block: int, split: int = 0) -> int:
+    """mtq_packed_skinny_pre_split (a host function: no GPU): the effective split of the _pre entries for (m, n, k, block, split) - with a
+    block, equal slices of whole blocks; split 0 is the library's choice.  Arguments the entries refuse raise MtqError."""
+    eff = int(_entry("mtq_packed_skinny_pre_split")(int(m), int(n), int(k), int(block), int(split)))
+    if eff < 0:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return eff
+
+
+def packed_linear_skinny_pre_workspace(m: int, n: int, k: int, block: int, split: int = 0) -> int:
+    """mtq_packed_linear_skinny_pre_workspace_bytes (a host function: no GPU): packed_linear_skinny_workspace_bytes at the _pre entries'
+    effective split."""
+    return _workspace_size("mtq_packed_linear_skinny_pre_workspace_bytes", m, n, k, block, split)
+
+
+def packed_linear_skinny_pre(x, data, tables: PackedTables, n: int, block: int = 0, in_exponents=None, bias=None, out_dtype=None, out=None,
+                             split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_linear_skinny_pre on the current stream: packed_linear_skinny on bf16(hadamard_rows(x, block)·2^−in_exponents), the
+    transform formed inside the kernel; at an equal effective split, the bits of the three separate steps.  block: 0 or a power of two
+    in [32, 1024] dividing k; in_exponents: None or a uint8 device tensor of k shifts in 0 .. 7.  The split must cut K into equal slices
+    of whole blocks (packed_skinny_pre_split; 0: the library's choice); workspace as packed_linear_skinny's, of
+    packed_linear_skinny_pre_workspace bytes."""
+    return _packed_product_call("mtq_packed_linear_skinny_pre", False, "", x, data, tables, n, bias, out_dtype, out, stream,
+                                packed_linear_skinny_pre_workspace, split, workspace, size_first=True, pre=(block, in_exponents))
 
 
 PACKED_MATMUL_SKINNY = ("mtq_packed_matmul_skinny_workspace_bytes", "mtq_packed_matmul_skinny")
@@ -1849,7 +1903,7 @@ def glu_combine(g, u, act="silu", out_dtype=None, out=None, stream="current"):
 
 
 def _packed_glu_call(name, kn, x, gate_data, gate_tables, up_data, up_tables, n, act, bias_gate, bias_up, out_dtype, out, stream, size=None, split=0,
-                     workspace=None):
+                     workspace=None, pre=None):
     """The checks and the call the single-tensor gated entries share; m = 0 or n = 0 ends here with the empty `out`.  size: a skinny
     entry's own size function, which makes the call one with m <= 32, a split and a workspace (never of 0 bytes)."""
     torch = _torch()
@@ -1871,8 +1925,10 @@ def _packed_glu_call(name, kn, x, gate_data, gate_tables, up_data, up_tables, n,
     out, ldy = _packed_out(out, m, n, out_dtype, x.device)
     if m == 0 or n == 0:                             # the entry refuses empty operands: they end here
         return out
+    if pre is not None:                              # a _pre entry, as in _packed_product_call
+        pre, block, size = _packed_pre_args(x, k, *pre), int(pre[0]), (lambda m, n, k, split, size=size: size(m, n, k, block, split))
     more = () if size is None else (int(split), *_packed_workspace(workspace, size(m, n, k, split), x.device))
-    check(fn(x.data_ptr(), m, k, ldx, pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
+    check(fn(x.data_ptr(), m, k, ldx, *(pre or ()), pg, gate_tables.nbytes, gate_tables.map_ptr, gate_tables.offsets_ptr, pu, up_tables.nbytes,
              up_tables.map_ptr, up_tables.offsets_ptr, n, bg, bu, a, out.data_ptr(), code, ldy, *more, _packed_stream_ptr(stream)))
     return out
 
@@ -1971,6 +2027,20 @@ def packed_glu_skinny(x, gate_data, gate_tables: PackedTables, up_data, up_table
     given.  m = 0 or n = 0 gives the empty (m, n) tensor without a launch."""
     return _packed_glu_call("mtq_packed_glu_skinny", False, x, gate_data, gate_tables, up_data, up_tables, n, act, bias_gate, bias_up, out_dtype, out,
                             stream, packed_glu_skinny_workspace_bytes, split, workspace)
+
+
+def packed_glu_skinny_pre_workspace(m: int, n: int, k: int, block: int, split: int = 0) -> int:
+    """mtq_packed_glu_skinny_pre_workspace_bytes (a host function: no GPU): packed_glu_skinny_workspace_bytes at the _pre entries'
+    effective split."""
+    return _workspace_size("mtq_packed_glu_skinny_pre_workspace_bytes", m, n, k, block, split)
+
+
+def packed_glu_skinny_pre(x, gate_data, gate_tables: PackedTables, up_data, up_tables: PackedTables, n: int, block: int = 0, in_exponents=None,
+                          act="silu", bias_gate=None, bias_up=None, out_dtype=None, out=None, split: int = 0, workspace=None, stream="current"):
+    """mtq_packed_glu_skinny_pre on the current stream: packed_glu_skinny on bf16(hadamard_rows(x, block)·2^−in_exponents), the transform
+    formed once per workgroup for both projections; block, in_exponents and split as packed_linear_skinny_pre's."""
+    return _packed_glu_call("mtq_packed_glu_skinny_pre", False, x, gate_data, gate_tables, up_data, up_tables, n, act, bias_gate, bias_up, out_dtype,
+                            out, stream, packed_glu_skinny_pre_workspace, split, workspace, pre=(block, in_exponents))
 
 
 def packed_glu_skinny_grouped_workspace_bytes(total_rows: int, count: int, n: int, k: int, split: int = 0) -> int:

@@ -587,7 +587,84 @@ def _takes_skinny(o: _Orientation, hb, what: str, kernel: str, m: int) -> bool:
     return kernel == "auto" and _at_most(o, o.auto_skinny_max_m, m) and (o.has_auto_skinny is None or getattr(hb, o.has_auto_skinny)())
 
 
-def _product(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dtype, backend, kernel, split, workspace):
+PROLOGUES = ("staged", "fused", "auto")   # how rotate= / in_exponents= reach the product: separate launches, inside the skinny kernel, or by measurement
+
+
+AUTO_FUSED_MAX_M = 8   # prologue="auto" takes the fused entry for a rotated layer up to here (timed at m = 1 and 8)
+
+
+def _auto_takes_fused(m: int, rotate: int) -> bool:
+    """prologue="auto": the range in which profiles/packed_prologue.txt shows the fused entry faster than the staged route by more than the
+    spread of the staged medians, every block 32 .. 1024 at m = 1 and m = 8 (m = 2 .. 7 lie between two timed points).  At m = 32 it
+    loses from block 256 on at the 14336-wide shapes; shifts without a rotation and 8 < m < 32 were not timed: staged."""
+    return m <= AUTO_FUSED_MAX_M and rotate >= 32
+
+
+class _Shifts:
+    """k per-channel shifts in 0 .. 7 of an AWQ-scaled weight, on one device: `neg` (int32, −p) for torch.ldexp on the staged route, `u8`
+    for the fused entries."""
+
+    def __init__(self, in_exponents, k: int, device=None):
+        import torch
+
+        exps = np.asarray(in_exponents.cpu().numpy() if _is_torch(in_exponents) else in_exponents)
+        if exps.shape != (k,) or exps.size and (exps.min() < 0 or exps.max() > 7 or not np.array_equal(exps, np.rint(exps))):
+            raise ValueError(f"in_exponents must be {k} integers in 0 .. 7")
+        self.neg = -torch.from_numpy(exps.astype(np.int32))
+        self.u8 = torch.from_numpy(exps.astype(np.uint8))
+        if device is not None:
+            self.neg, self.u8 = self.neg.to(device), self.u8.to(device)
+
+
+def _shifts(in_exponents, k: int, device=None):
+    if in_exponents is None or isinstance(in_exponents, _Shifts):
+        return in_exponents
+    return _Shifts(in_exponents, k, device)
+
+
+def _staged_x(x2, rotate: int, shifts, backend: str):
+    """The staged prologue: x·H_rotate through hadamard (a launch of its own on hip), then torch.ldexp by −p, both into bf16."""
+    import torch
+
+    x2 = _as_torch(x2)
+    if rotate:    # the weight is packed from rotate_weight(w, rotate): the product needs x·H, formed online (csrc/mtq_hadamard.hip on hip)
+        x2 = hadamard(x2, rotate, out_dtype=torch.bfloat16, backend=backend)
+    if shifts is not None:    # a torch op, not a kernel; composes after the rotation
+        x2 = torch.ldexp(x2, shifts.neg.to(x2.device))
+    return x2
+
+
+def _takes_fused_prologue(o: _Orientation, what: str, prologue: str, backend: str, skinny: bool, m: int, n: int, k: int, rotate: int,
+                          split: int) -> bool:
+    """Whether this call goes through a _pre entry.  "fused" raises MtqError where that entry cannot serve it; "auto" takes it where the
+    unfused call would be the skinny kernel's, the entry can serve and _auto_takes_fused says it is faster."""
+    if prologue not in PROLOGUES:
+        raise MtqError(f"prologue must be one of {PROLOGUES}, got {prologue!r}")
+    if prologue == "staged" or (prologue == "auto" and not (skinny and _auto_takes_fused(m, rotate))):
+        return False
+    why = None
+    if o.kn:
+        why = "the (k, n) entries have no fused prologue"
+    elif backend != "hip":
+        why = "the emulation backend has no fused entry"
+    elif m > SKINNY_MAX_M:
+        why = f"m = {m} is above {SKINNY_MAX_M}"
+    elif not hb.packed_pre_available():
+        why = "this build of libmtq_hip.so lacks mtq_packed_linear_skinny_pre: rebuild it from this tree"
+    else:
+        try:
+            hb.packed_skinny_pre_split(m, n, k, rotate, split)
+        except MtqError as e:
+            why = str(e)
+    if why is None:
+        return True
+    if prologue == "fused":
+        raise MtqError(f'{what}(prologue="fused"): {why}')
+    return False
+
+
+def _product(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dtype, backend, kernel, split, workspace, rotate=0, in_exponents=None,
+             prologue="staged"):
     """linear and matmul."""
     _check_layout(pt.layout)
     if o.kernel_before_rank:
@@ -599,12 +676,26 @@ def _product(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dtype, b
     backend = backend or ("hip" if pt.on_device else "emulation")
     _check_out_dtype(out_dtype)
     n, k = o.n_k(pt)
+    fused = False
+    if rotate or in_exponents is not None or prologue != "staged":
+        rotate = check_block(k, rotate) if rotate else 0
+        shifts = _shifts(in_exponents, k, x.device if backend == "hip" else None)
+        if tuple(x.shape[1:]) != (k,):
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        m = int(x.shape[0])
+        skinny = kernel == "skinny" or (kernel == "auto" and _at_most(o, o.auto_skinny_max_m, m))
+        fused = (rotate or shifts is not None) and _takes_fused_prologue(o, what, prologue, backend, skinny, m, n, k, rotate, split)
+        if not fused:
+            x = _staged_x(x, rotate, shifts, backend)
     if backend == "hip":
         if x.dim() != 2 or x.shape[1] != k:
             raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
         _needs(o.need_product, hb, what)
         dtype = _torch_dtype(out_dtype)
         m = int(x.shape[0])
+        if fused:
+            return hb.packed_linear_skinny_pre(x, _device_data(pt), pt.tables(), n, block=rotate, in_exponents=None if shifts is None else shifts.u8,
+                                               bias=bias, out_dtype=dtype, split=split, workspace=workspace)
         if _takes_skinny(o, hb, what, kernel, m):
             return getattr(hb, o.hb_skinny)(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=dtype, split=split, workspace=workspace)
         wide_min_m = globals()[o.auto_wide_min_m]
@@ -637,7 +728,7 @@ def _product_wide(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dty
 
 
 def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block", split: int = 0,
-           workspace=None):
+           workspace=None, rotate: int = 0, in_exponents=None, prologue: str = "staged"):
     """Y = X·Ŵᵀ + b with the packed (n, k) weight `pt` (nn.Linear convention).  hip (the default when the stream is on the device):
     X an (m, k) bf16 device tensor, bias float32, through mtq_packed_linear.  emulation: the float64 product of the unpacked weight,
     rounded once to float32 (or from there to bf16) — the reference the GPU tests hold the kernel to, not a fast path.
@@ -646,8 +737,16 @@ def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     choice, and an optional uint8 device `workspace` of hip_backend.packed_linear_skinny_workspace_bytes bytes) or "auto" (skinny for
     m <= AUTO_SKINNY_MAX_M, block above; from m = AUTO_WIDE_MIN_M on, when that is not None and the library has it, the wide-block
     kernel of linear_wide, whose bits are the block kernel's).  The skinny and the block kernel sum in different orders: each is
-    bit-stable, they may differ in the last bits.  The emulation computes the same float64 product under all three names."""
-    return _product(_NK, "linear", x, pt, bias, out_dtype, backend, kernel, split, workspace)
+    bit-stable, they may differ in the last bits.  The emulation computes the same float64 product under all three names.
+
+    rotate, in_exponents: for a `pt` packed from hadamard.rotate_weight(w, rotate) / awq.scale_weight(w, in_exponents), the product
+    is taken with X″ = bf16(bf16(x·H_rotate)·2^−in_exponents) (x a bf16 torch tensor).  prologue (PROLOGUES) says where X″ is formed:
+    "staged" (the default), by hadamard and torch.ldexp in front of the call chosen by `kernel`; "fused", inside the skinny kernel
+    (mtq_packed_linear_skinny_pre, whatever `kernel` says; `split` must cut K into equal slices of whole blocks, 0 = that entry's own
+    choice) - at an equal effective split the staged route's bits with kernel="skinny" - and MtqError where that entry cannot serve:
+    m > 32, a block above 1024 or a split its slice rule refuses, the emulation backend; "auto", the fused entry where `kernel` would
+    take the skinny kernel, the entry can serve and the measured range has it faster, the staged route otherwise."""
+    return _product(_NK, "linear", x, pt, bias, out_dtype, backend, kernel, split, workspace, rotate, in_exponents, prologue)
 
 
 def linear_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
@@ -1340,14 +1439,17 @@ def _need_glu_skinny(hb, what: str) -> None:
 
 
 def glu_skinny(x, gate: PackedTensor, up: PackedTensor, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
-               backend: Optional[str] = None, split: int = 0, workspace=None):
+               backend: Optional[str] = None, split: int = 0, workspace=None, rotate: int = 0, in_exponents=None, prologue: str = "staged"):
     """glu for decode, m <= SKINNY_MAX_M, from the fused split-K kernel: mtq_packed_glu_skinny, two launches in place of the five of
     glu(kernel="auto") at these m, and at split 0 bit for bit its value; at any `split`, the bits of two linear(kernel="skinny") calls
     into float32 at that split and hip_backend.glu_combine.  `split` and `workspace` as in linear(kernel="skinny"), the workspace of
     hip_backend.packed_glu_skinny_workspace_bytes bytes (never 0), allocated when None.  m > SKINNY_MAX_M and a library without the
     entry raise MtqError: there is no fall-back.
-    emulation: glu's float64 value rounded once, whatever m and split."""
-    return _glu_skinny(_NK, "glu_skinny", x, gate, up, act, bias_gate, bias_up, out_dtype, backend, split, workspace)
+    emulation: glu's float64 value rounded once, whatever m and split.
+    rotate, in_exponents, prologue: as linear's, for gate and up packed from rotated / scaled weights; "fused" is
+    mtq_packed_glu_skinny_pre, which forms X″ once per workgroup for both projections."""
+    return _glu_skinny(_NK, "glu_skinny", x, gate, up, act, bias_gate, bias_up, out_dtype, backend, split, workspace, rotate, in_exponents,
+                       prologue)
 
 
 def glu_grouped(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
@@ -1449,13 +1551,25 @@ def _glu_f64(o: _Orientation, xf, gate: PackedTensor, up: PackedTensor, act, bia
     return _glu_host(sides[0], sides[1], act)
 
 
-def _glu_skinny(o: _Orientation, what: str, x, gate: PackedTensor, up: PackedTensor, act, bias_gate, bias_up, out_dtype, backend, split, workspace):
+def _glu_skinny(o: _Orientation, what: str, x, gate: PackedTensor, up: PackedTensor, act, bias_gate, bias_up, out_dtype, backend, split, workspace,
+                rotate=0, in_exponents=None, prologue="staged"):
     """glu_skinny and glu_matmul_skinny."""
     _check_pair(o, gate, up, what)
     _check_act(act)
     _check_out_dtype(out_dtype)
     backend = backend or ("hip" if gate.on_device else "emulation")
     n, k = o.n_k(gate)
+    if rotate or in_exponents is not None or prologue != "staged":
+        rotate = check_block(k, rotate) if rotate else 0
+        shifts = _shifts(in_exponents, k, x.device if backend == "hip" else None)
+        if tuple(x.shape[1:]) != (k,):
+            raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
+        m = int(x.shape[0])
+        if (rotate or shifts is not None) and _takes_fused_prologue(o, what, prologue, backend, True, m, n, k, rotate, split):
+            return hb.packed_glu_skinny_pre(x, _device_data(gate), gate.tables(), _device_data(up), up.tables(), n, block=rotate,
+                                            in_exponents=None if shifts is None else shifts.u8, act=act, bias_gate=bias_gate, bias_up=bias_up,
+                                            out_dtype=_torch_dtype(out_dtype), split=split, workspace=workspace)
+        x = _staged_x(x, rotate, shifts, backend)
     if backend == "hip":
         if x.dim() != 2 or x.shape[1] != k:
             raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
@@ -2072,7 +2186,12 @@ _CLASS_DOCS = {
         PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, runs glu(kernel="auto") into bf16 and
         linear(kernel="auto") with `down`, and returns (..., k_out) in out_dtype; m = 0 gives the empty result without a call.
         decode_kernel (MLP_DECODE_KERNELS): "pair", that route at every m; "fused", m <= AUTO_SKINNY_MAX_M goes through glu_skinny
-        instead, the same bits from two launches in place of five.""",
+        instead, the same bits from two launches in place of five.
+        rotate, in_exponents: gate and up are packed from rotated / AWQ-scaled weights, and x is transformed in front of them as
+        PackedLinear does; down_rotate, down_in_exponents: the same for `down` and the hidden activation h.  prologue (PROLOGUES):
+        "staged" applies hadamard and torch.ldexp in front of the existing routes; with decode_kernel="fused" and m <= 32, "fused" /
+        "auto" send both halves through glu_skinny and linear with that prologue (mtq_packed_glu_skinny_pre, mtq_packed_linear_skinny_pre
+        with h as its X); every other case is the staged transform.""",
     "PackedMatmulMLP":
         """PackedMLP over three packed (k, n) matrices, as matmul takes them: gate and up (k, hidden), down (hidden, k_out) - the
         entries of a pack_model --store-transposed directory, pack_transposed's results, input-major weights.  INFERENCE ONLY.
@@ -2108,7 +2227,11 @@ _CLASS_DOCS = {
         `kernel` ("auto": the skinny split-K kernel for decode-sized m, the block kernel above, the wide-block kernel with the same
         bits from AUTO_WIDE_MIN_M on) and returns (..., n) in out_dtype.
         hip: the tables, the bias and a workspace sized for every m <= 32 stay on the device across calls, so a decode step
-        allocates only its output.  emulation: CPU tensors, the float64 product (for use without a GPU).""",
+        allocates only its output.  emulation: CPU tensors, the float64 product (for use without a GPU).
+        rotate, in_exponents: for a weight packed from hadamard.rotate_weight / awq.scale_weight.  prologue: linear's - "staged" (the
+        default: hadamard and torch.ldexp in front of the product, today's bits), "fused" (inside the skinny kernel; MtqError where it
+        cannot serve: m > 32, a block its slice rule refuses, the emulation backend) or "auto" (fused in the measured range, else
+        staged).""",
     "PackedMatmul":
         """x @ P̂ + b over a packed (k, n) matrix (pack of an input-major weight, or pack_transposed of an (n, k) one).  INFERENCE ONLY,
         as PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, multiplies through matmul() and returns
@@ -2150,8 +2273,11 @@ def _mlp_class(o: _Orientation, name: str):
     """PackedMLP and PackedMatmulMLP."""
     import torch
 
-    def init(self, gate, up, down, act, out_dtype, backend, decode_kernel):
+    def init(self, gate, up, down, act, out_dtype, backend, decode_kernel, rotate=0, in_exponents=None, down_rotate=0, down_in_exponents=None,
+             prologue="staged"):
         torch.nn.Module.__init__(self)
+        if prologue not in PROLOGUES:
+            raise MtqError(f"prologue must be one of {PROLOGUES}, got {prologue!r}")
         decode_kernels = globals()[o.mlp_decode_kernels]
         if decode_kernel not in decode_kernels:
             raise MtqError(f"decode_kernel must be one of {decode_kernels}, got {decode_kernel!r}")
@@ -2173,6 +2299,9 @@ def _mlp_class(o: _Orientation, name: str):
                 pt.tables()
         self.gate, self.up, self.down, self.act, self.out_dtype, self.decode_kernel = gate, up, down, act, out_dtype, decode_kernel
         self.in_features, self.hidden_features, self.out_features = k, n, o.n_k(down)[0]
+        device = _device_data(gate).device if self.backend == "hip" and (in_exponents is not None or down_in_exponents is not None) else None
+        self.rotate, self.down_rotate, self.prologue = check_block(k, rotate) if rotate else 0, check_block(n, down_rotate) if down_rotate else 0, prologue
+        self._shifts, self._down_shifts = _shifts(in_exponents, k, device), _shifts(down_in_exponents, n, device)
 
     class MLP(torch.nn.Module):
         if o.kn:
@@ -2181,8 +2310,9 @@ def _mlp_class(o: _Orientation, name: str):
                 init(self, gate_kn, up_kn, down_kn, act, out_dtype, backend, decode_kernel)
         else:
             def __init__(self, gate: PackedTensor, up: PackedTensor, down: PackedTensor, act: str = "silu", out_dtype: str = "bfloat16",
-                         backend: Optional[str] = None, decode_kernel: str = "pair"):
-                init(self, gate, up, down, act, out_dtype, backend, decode_kernel)
+                         backend: Optional[str] = None, decode_kernel: str = "pair", rotate: int = 0, in_exponents=None, down_rotate: int = 0,
+                         down_in_exponents=None, prologue: str = "staged"):
+                init(self, gate, up, down, act, out_dtype, backend, decode_kernel, rotate, in_exponents, down_rotate, down_in_exponents, prologue)
 
         def extra_repr(self) -> str:
             return f"in_features={self.in_features}, hidden_features={self.hidden_features}, out_features={self.out_features}, " \
@@ -2196,10 +2326,21 @@ def _mlp_class(o: _Orientation, name: str):
             x2 = x.reshape(-1, self.in_features)
             if x2.shape[0] == 0:
                 return torch.zeros(lead + (self.out_features,), dtype=_torch_dtype(self.out_dtype), device=x.device)
+            pre = self.rotate or self.down_rotate or self._shifts is not None or self._down_shifts is not None
             if self.decode_kernel == "fused" and _at_most(o, o.glu_auto_skinny_max_m, x2.shape[0]):
+                if pre:                              # both halves through the _pre entries when `prologue` asks for them (PackedMLP only)
+                    h = glu_skinny(x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, rotate=self.rotate,
+                                   in_exponents=self._shifts, prologue=self.prologue)
+                    y = linear(_as_torch(h), self.down, out_dtype=self.out_dtype, backend=self.backend, kernel="auto", rotate=self.down_rotate,
+                               in_exponents=self._down_shifts, prologue=self.prologue)
+                    return _as_torch(y).reshape(lead + (self.out_features,))
                 h = globals()[o.glu_skinny](x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend)
             else:
+                if pre:
+                    x2 = _staged_x(x2, self.rotate, self._shifts, self.backend)
                 h = globals()[o.glu](x2, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="auto")
+            if pre:
+                h = _staged_x(h, self.down_rotate, self._down_shifts, self.backend)
             y = globals()[o.product](h, self.down, out_dtype=self.out_dtype, backend=self.backend, kernel="auto")
             return _as_torch(y).reshape(lead + (self.out_features,))
 
@@ -2442,20 +2583,19 @@ def _product_class(o: _Orientation, name: str):
     """PackedLinear and PackedMatmul."""
     import torch
 
-    def init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents=None):
+    def init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents=None, prologue="staged"):
         torch.nn.Module.__init__(self)
         _check_rank2(o, pt, name)
         self.rotate = check_block(o.n_k(pt)[1], rotate) if rotate else 0
-        exps = None
-        if in_exponents is not None:    # pt is packed from awq.scale_weight(w, p): x·2^−p per input channel, exact in bf16 (awq.py)
-            exps = np.asarray(in_exponents.cpu().numpy() if _is_torch(in_exponents) else in_exponents)
-            if exps.shape != (o.n_k(pt)[1],) or exps.size and (exps.min() < 0 or exps.max() > 7 or not np.array_equal(exps, np.rint(exps))):
-                raise ValueError(f"in_exponents must be {o.n_k(pt)[1]} integers in 0 .. 7")
-            exps = -torch.from_numpy(exps.astype(np.int32))
+        if prologue not in PROLOGUES:
+            raise MtqError(f"prologue must be one of {PROLOGUES}, got {prologue!r}")
+        self.prologue = prologue
         _check_kernel(kernel, globals()[o.kernels])
         _check_out_dtype(out_dtype)
         self.backend = backend or ("hip" if pt.on_device else "emulation")
         _check_backend(self.backend)
+        # pt is packed from awq.scale_weight(w, p): x·2^−p per input channel, exact in bf16 (awq.py)
+        self._shifts = _shifts(in_exponents, o.n_k(pt)[1], _device_data(pt).device if in_exponents is not None and self.backend == "hip" else None)
         self.packed, self.kernel, self.out_dtype = pt, kernel, out_dtype
         self.out_features, self.in_features = o.n_k(pt)
         self._workspace = None
@@ -2473,9 +2613,13 @@ def _product_class(o: _Orientation, name: str):
                 size, (n, k) = getattr(hb, o.hb_skinny_size), o.n_k(pt)
                 # every m <= 32, or m = 32 alone (monotone in m: serves every m <= 32)
                 need = max(size(m, n, k) for m in (range(1, SKINNY_MAX_M + 1) if o.module_size_every_m else (SKINNY_MAX_M,)))
+                if prologue != "staged" and not o.kn and hb.packed_pre_available():    # the fused entry's own split is never larger
+                    try:
+                        need = max(need, hb.packed_linear_skinny_pre_workspace(SKINNY_MAX_M, n, k, self.rotate))
+                    except MtqError:
+                        pass                         # a block the entry refuses: "fused" says so at the first forward, "auto" stages
                 self._workspace = torch.empty((need,), dtype=torch.uint8, device=data.device) if need else None
         self.register_buffer("bias", None if bias is None else bias.detach(), persistent=False)
-        self.register_buffer("neg_exponents", exps if exps is None or self.backend != "hip" else exps.to(_device_data(pt).device), persistent=False)
 
     class Product(torch.nn.Module):
         if o.kn:
@@ -2484,13 +2628,13 @@ def _product_class(o: _Orientation, name: str):
                 init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents)
         else:
             def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", kernel: str = "auto", backend: Optional[str] = None,
-                         rotate: int = 0, in_exponents=None):
-                init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents)
+                         rotate: int = 0, in_exponents=None, prologue: str = "staged"):
+                init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents, prologue)
 
         def extra_repr(self) -> str:
             return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, kernel={self.kernel!r}, " \
                    f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}" \
-                   + (f", rotate={self.rotate}" if self.rotate else "") + (", in_exponents=True" if self.neg_exponents is not None else "")
+                   + (f", rotate={self.rotate}" if self.rotate else "") + (", in_exponents=True" if self._shifts is not None else "")
 
         @torch.no_grad()
         def forward(self, x):
@@ -2500,12 +2644,12 @@ def _product_class(o: _Orientation, name: str):
             x2 = x.reshape(-1, self.in_features)
             if x2.shape[0] == 0:
                 return torch.zeros(lead + (self.out_features,), dtype=_torch_dtype(self.out_dtype), device=x.device)
-            if self.rotate:    # pt is packed from rotate_weight(w, rotate): the product needs x·H, formed online (csrc/mtq_hadamard.hip on hip)
-                x2 = hadamard(x2, self.rotate, out_dtype=torch.bfloat16, backend=self.backend)
-            if self.neg_exponents is not None:    # a torch op, not a kernel; composes after the rotation
-                x2 = torch.ldexp(x2, self.neg_exponents.to(x2.device))
-            y = globals()[o.product](x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel,
-                                     workspace=self._workspace)
+            if o.kn or self.prologue == "staged":    # hadamard, then torch.ldexp, in front of the product
+                y = globals()[o.product](_staged_x(x2, self.rotate, self._shifts, self.backend), self.packed, bias=self.bias,
+                                         out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel, workspace=self._workspace)
+            else:
+                y = linear(x2, self.packed, bias=self.bias, out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel,
+                           workspace=self._workspace, rotate=self.rotate, in_exponents=self._shifts, prologue=self.prologue)
             return _as_torch(y).reshape(lead + (self.out_features,))
 
     return _named(Product, name)
