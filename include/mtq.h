@@ -1401,4 +1401,5 @@ int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream
 #include "mtq_moe_decode.h"
 #include "mtq_glu_chunked.h"
 #include "mtq_packed_pre.h"
+#include "mtq_grouped_pre.h"
 #endif /* MTQ_H */

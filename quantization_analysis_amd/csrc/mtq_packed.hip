@@ -2160,9 +2160,25 @@ struct PreArgs {
     const uint8_t *exps;                             // K shifts, or null
 };
 
-// columns [col0, col0 + P) of rows [0, M) of x → the image; every wave of the workgroup calls it (wave: uniform)
-__device__ __forceinline__ void pre_panel(const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec, int64_t col0,
-                                          const PreArgs &a, uint16_t *img, int mask, int lane, int wave)
+// Where the M rows of a panel lie, as load_x16 takes a row: (base, rows, row).  at(r): row r, asked by all 64 lanes of a wave at once
+// (a grouped kernel's gather hands a row's token from lane to lane); own(row): the lane's own MFMA row.  RowsDirect: rows [0, M) of x.
+struct XRow {
+    const uint16_t *x;
+    int64_t m;
+    int row;
+};
+
+struct RowsDirect {
+    const uint16_t *__restrict__ x;
+    int64_t M;
+    __device__ __forceinline__ XRow at(int r) const { return {x, M, r}; }
+    __device__ __forceinline__ XRow own(int row) const { return {x, M, row}; }
+};
+
+// columns [col0, col0 + P) of the M rows of `rows` → the image; every wave of the workgroup calls it (wave: uniform)
+template <typename Rows>
+__device__ __forceinline__ void pre_panel(const Rows &rows, int64_t M, int64_t K, int64_t ldx, int x_vec, int64_t col0, const PreArgs &a,
+                                          uint16_t *img, int mask, int lane, int wave)
 {
     const int lpr = a.panel / kGroup, items = (int)M * lpr;
     for (int q0 = 64 * wave; q0 < items; q0 += 64 * kSkinnyWaves) {
@@ -2171,9 +2187,10 @@ __device__ __forceinline__ void pre_panel(const uint16_t *__restrict__ x, int64_
         float v[kGroup];
 #pragma unroll
         for (int i = 0; i < kGroup; ++i) v[i] = 0.0f;
+        const XRow xr = rows.at(r);                  // outside `live`: EXEC is full here
         if (live) {
             uint4 lo, hi;
-            load_x16(x, M, K, ldx, x_vec, r, col0 + c, lo, hi);
+            load_x16(xr.x, xr.m, K, ldx, x_vec, xr.row, col0 + c, lo, hi);
             const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
             for (int i = 0; i < 8; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u); }
@@ -2193,24 +2210,25 @@ __device__ __forceinline__ void pre_panel(const uint16_t *__restrict__ x, int64_
     }
 }
 
-// one wave's part of a _pre kernel: the run of tile row tr over tiles [c0, c1) of `st`, `live` false for a wave without a unit
-template <bool ROT>
-__device__ __forceinline__ void pre_run(f32x16 &acc, bool live, const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, int x_vec,
-                                        const PreArgs &a, const PackedStream &st, int64_t t0, int64_t c0, int64_t c1, uint16_t *img, int lane,
-                                        int wave)
+// one wave's part of a _pre kernel: the run of tile row tr over tiles [c0, c1) of `st` on the M rows of `rows`, `live` false for a wave
+// without a unit
+template <bool ROT, typename Rows>
+__device__ __forceinline__ void pre_run(f32x16 &acc, bool live, const Rows &rows, int64_t M, int64_t K, int64_t ldx, int x_vec, const PreArgs &a,
+                                        const PackedStream &st, int64_t t0, int64_t c0, int64_t c1, uint16_t *img, int lane, int wave)
 {
     const int row = lane & 31, half = lane >> 5;
     if constexpr (ROT) {
         const int mask = (a.panel / kGroup) % 8 == 0 ? 7 : 0, step = a.panel / kTile;
         for (int64_t cp = c0; cp < c1; cp += step) {
-            pre_panel(x, M, K, ldx, x_vec, cp * kTile, a, img, mask, lane, wave);
+            pre_panel(rows, M, K, ldx, x_vec, cp * kTile, a, img, mask, lane, wave);
             __syncthreads();
-            if (live) skinny_run(acc, FeedDirect(), x, M, K, ldx, x_vec, st, t0, 1, cp, cp + step, lane, row, half, 2 * row + half,
+            if (live) skinny_run(acc, FeedDirect(), nullptr, M, K, ldx, x_vec, st, t0, 1, cp, cp + step, lane, row, half, 2 * row + half,
                                  XLds{img, a.panel, mask, cp});
             __syncthreads();
         }
     } else {
-        if (live) skinny_run(acc, FeedDirect(), x, M, K, ldx, x_vec, st, t0, 1, c0, c1, lane, row, half, 2 * row + half, XShift{a.exps});
+        const XRow xr = rows.own(row);
+        if (live) skinny_run(acc, FeedDirect(), xr.x, xr.m, K, ldx, x_vec, st, t0, 1, c0, c1, lane, xr.row, half, 2 * row + half, XShift{a.exps});
     }
 }
 
@@ -2227,8 +2245,8 @@ __global__ __launch_bounds__(64 * kSkinnyWaves) void packed_linear_skinny_pre_ke
     const bool live = tr < tiles_h;                  // wave-uniform
 
     f32x16 acc = zero16();
-    pre_run<ROT>(acc, live, x, M, K, ldx, x_vec, a, tensor_stream(packed, packed_bytes, map, offsets), tr * tiles_w, s * tiles_w / split,
-                 (s + 1) * tiles_w / split, pre_img, lane, wave);
+    pre_run<ROT>(acc, live, RowsDirect{x, M}, M, K, ldx, x_vec, a, tensor_stream(packed, packed_bytes, map, offsets), tr * tiles_w,
+                 s * tiles_w / split, (s + 1) * tiles_w / split, pre_img, lane, wave);
 
     const int64_t n = tr * kTile + (lane & 31);
     if (!live || n >= N) return;
@@ -2252,7 +2270,8 @@ __global__ __launch_bounds__(64 * kSkinnyWaves) void packed_glu_skinny_pre_kerne
     const PackedStream st = tensor_stream(p ? up : gate, p ? up_bytes : gate_bytes, p ? up_map : gate_map, p ? up_offsets : gate_offsets);
 
     f32x16 acc = zero16();
-    pre_run<ROT>(acc, live, x, M, K, ldx, x_vec, a, st, tr * tiles_w, s * tiles_w / split, (s + 1) * tiles_w / split, pre_img, lane, wave);
+    pre_run<ROT>(acc, live, RowsDirect{x, M}, M, K, ldx, x_vec, a, st, tr * tiles_w, s * tiles_w / split, (s + 1) * tiles_w / split, pre_img,
+                 lane, wave);
 
     const int64_t n = tr * kTile + (lane & 31);
     if (!live || n >= N) return;
@@ -2351,6 +2370,102 @@ __global__ __launch_bounds__(256) void glu_skinny_grouped_reduce_kernel(const fl
 size_t glu_skinny_workspace(int64_t m, int64_t n, int split_eff)
 {
     return (2 * (size_t)std::max(split_eff, 1) * (size_t)m * (size_t)n * sizeof(float) + 15) & ~(size_t)15;
+}
+
+// ---- the X prologue in the grouped skinny kernels (the *_grouped_pre entries, include/mtq_grouped_pre.h): the _pre kernels' workgroup
+// in packed_linear_skinny_grouped_kernel's and packed_glu_skinny_grouped_kernel's frames, for a rotated or AWQ-scaled MoE layer's decode.
+//
+// A workgroup is four tile rows (the gated kernel: two tile rows × two projections) of ONE expert e in ONE K slice s: block
+// (s * count + e) * ceil(tiles_h / 4) + tile-row block.  The expert's clamped rows, the slice and so every chunk and panel count are the
+// same in its four waves, which is what the barriers of pre_run need: an expert without rows ends the workgroup as a whole before the
+// first, and a wave whose tile row is past tiles_h (`live` false) forms its share of every panel and meets every barrier.  Per 32-row
+// chunk the workgroup does what a _pre kernel does for an m <= 32 call on that chunk with expert e's stream and row e of the shifts:
+// pre_panel over the chunk's rows - its own rows of x, or with GATHER the token rows that src names, one lookup per lane and chunk, handed
+// from lane to lane where a pass needs another row's token -, then the unfused grouped wave's skinny_run on the image.  The second barrier
+// of the last panel is also what frees the image for the next chunk.  block 0 (ROT false): XShift on the lane's own loads, no LDS.
+// Stores are the unfused kernels': the partial of every chunk to ws[s][row][n] (gated: ws[p][s][row][n]), or to Y at split 1.
+struct RowsGather {
+    const uint16_t *__restrict__ x;
+    int64_t ldx;
+    int tok;                                         // the token of chunk row (lane & 31), -1: a row of +0
+    __device__ __forceinline__ XRow of(int t) const { return {x + (int64_t)(t < 0 ? 0 : t) * ldx, t < 0 ? 0 : 1, 0}; }
+    __device__ __forceinline__ XRow at(int r) const { return of(__shfl(tok, r & 31)); }
+    __device__ __forceinline__ XRow own(int) const { return of(tok); }
+};
+
+// the walk over the chunks of group gr; store(acc, M, row0, lv) takes a live wave's accumulators of the chunk at row0
+template <bool ROT, bool GATHER, typename Store>
+__device__ __forceinline__ void grouped_pre_walk(const uint16_t *__restrict__ x, int T, int64_t K, int64_t ldx, int x_vec, const PreArgs &a,
+                                                 const GroupRows &gr, const PackedStream &st, bool live, int64_t t0, int64_t c0, int64_t c1,
+                                                 const int32_t *__restrict__ src, int topk, uint16_t *img, int lane, int wave, const Store &store)
+{
+    for (int64_t row0 = gr.r0; row0 < gr.r1; row0 += kTile) {
+        int lv = lane;
+        asm volatile("" : "+v"(lv));                 // the lane's addresses are formed per chunk, not kept in registers across chunks
+        const int64_t M = std::min<int64_t>(kTile, gr.r1 - row0);
+        f32x16 acc = zero16();
+        if constexpr (GATHER) {
+            const int v = (lv & 31) < M ? src[row0 + (lv & 31)] : -1;   // row0 + row < r1 <= T; gather_row's rule
+            pre_run<ROT>(acc, live, RowsGather{x, ldx, v >= 0 && v < T ? v / topk : -1}, M, K, ldx, x_vec, a, st, t0, c0, c1, img, lane, wave);
+        } else {
+            pre_run<ROT>(acc, live, RowsDirect{x + row0 * ldx, M}, M, K, ldx, x_vec, a, st, t0, c0, c1, img, lane, wave);
+        }
+        if (live) store(acc, M, row0, lv);
+    }
+}
+
+// packed_linear_skinny_grouped_kernel on X″
+template <bool BF16OUT, bool ROT>
+__global__ __launch_bounds__(64 * kSkinnyWaves) void packed_linear_skinny_grouped_pre_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, PreArgs a, const int32_t *__restrict__ group_rows,
+    const uint8_t *__restrict__ packed, uint64_t packed_bytes, const int8_t *__restrict__ maps, const uint32_t *__restrict__ offsets,
+    const uint64_t *__restrict__ bases, int count, int N, int tiles_h, int tiles_w, int split, void *__restrict__ yv, int64_t ldy,
+    float *__restrict__ ws)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t pre_img[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t rb = (tiles_h + kSkinnyWaves - 1) / kSkinnyWaves, se = blockIdx.x / rb, e = se % count, s = se / count;
+    const int64_t tr = (blockIdx.x % rb) * kSkinnyWaves + wave;
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    if (gr.r1 == gr.r0) return;                      // the whole workgroup: e is its own
+    const bool live = tr < tiles_h;                  // wave-uniform
+    const PackedStream st = arena_stream(packed, packed_bytes, maps, offsets, bases, e, (int64_t)tiles_h * tiles_w);
+    if (a.exps) a.exps += e * K;
+    grouped_pre_walk<ROT, false>(x, T, K, ldx, x_vec, a, gr, st, live, tr * tiles_w, s * tiles_w / split, (s + 1) * tiles_w / split, nullptr, 1,
+                                 pre_img, lane, wave, [&](const f32x16 &acc, int64_t M, int64_t row0, int lv) {
+                                     const int64_t n = tr * kTile + (lv & 31);
+                                     if (n < N) store_skinny<BF16OUT>(acc, M, lv >> 5, row0, n, split, 0.0f, yv, ldy, ws, s, T, N);
+                                 });
+}
+
+// packed_glu_skinny_grouped_kernel<GATHER> on X″: wave w is projection w & 1 of tile row 2 (block % ceil(tiles_h / 2)) + (w >> 1)
+template <bool ROT, bool GATHER>
+__global__ __launch_bounds__(64 * kSkinnyWaves) void packed_glu_skinny_grouped_pre_kernel(
+    const uint16_t *__restrict__ x, int T, int K, int64_t ldx, int x_vec, PreArgs a, const int32_t *__restrict__ group_rows,
+    const uint8_t *__restrict__ gate, uint64_t gate_bytes, const int8_t *__restrict__ gate_maps, const uint32_t *__restrict__ gate_offsets,
+    const uint64_t *__restrict__ gate_bases, const uint8_t *__restrict__ up, uint64_t up_bytes, const int8_t *__restrict__ up_maps,
+    const uint32_t *__restrict__ up_offsets, const uint64_t *__restrict__ up_bases, int count, int N, int tiles_h, int tiles_w, int split,
+    float *__restrict__ ws, const int32_t *__restrict__ src, int topk)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t pre_img[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t rb = (tiles_h + 1) / 2, se = blockIdx.x / rb, e = se % count, s = se / count;
+    const int64_t tr = (blockIdx.x % rb) * 2 + (wave >> 1);
+    const int p = wave & 1;
+    const GroupRows gr = group_rows_of(group_rows, e, T);
+    if (gr.r1 == gr.r0) return;                      // the whole workgroup: e is its own
+    const bool live = tr < tiles_h;                  // wave-uniform
+    const PackedStream st = arena_stream(p ? up : gate, p ? up_bytes : gate_bytes, p ? up_maps : gate_maps, p ? up_offsets : gate_offsets,
+                                         p ? up_bases : gate_bases, e, (int64_t)tiles_h * tiles_w);
+    if (a.exps) a.exps += e * K;
+    grouped_pre_walk<ROT, GATHER>(x, T, K, ldx, x_vec, a, gr, st, live, tr * tiles_w, s * tiles_w / split, (s + 1) * tiles_w / split, src, topk,
+                                  pre_img, lane, wave, [&](const f32x16 &acc, int64_t M, int64_t row0, int lv) {
+                                      const int64_t n = tr * kTile + (lv & 31);
+                                      const int half = lv >> 5;
+                                      if (n < N)
+                                          store_lane_rows<false, true>(acc, M, half, ws, (((int64_t)p * split + s) * T + row0 + 4 * half) * N + n, N,
+                                                                       0.0f);
+                                  });
 }
 
 // ---- gated skinny matmul (m <= 32): glu_value(X·P̂g + bg, X·P̂u + bu) for packed k × n gate and up matrices; the wide frames of this
@@ -3573,9 +3688,17 @@ extern "C" int mtq_packed_glu_matmul_skinny(const void *x, int64_t m, int64_t k,
 // The split and the panel of (m, n, k, block, split): skinny_shape's answer for block 0; for a block, slices of equal length that are
 // whole blocks - split 0: the largest s <= skinny_split with tiles_w % s == 0 and (tiles_w / s) % (block / 32) == 0 - and the largest
 // panel <= kPreMaxPanel that is a multiple of block and divides a slice.
+static int pre_block_split(int64_t k, int64_t block, int split, TileGrid &g, int *panel);
+
 static int pre_shape(int64_t m, int64_t n, int64_t k, int64_t block, int split, TileGrid &g, int *panel)
 {
     if (int rc = skinny_shape(m, n, k, split, &g.th, &g.tw, &g.eff)) return rc;
+    return pre_block_split(k, block, split, g, panel);
+}
+
+// the block's part of the rule, on the unfused entry's answer g.eff for (.., split): shared with the grouped _pre entries
+static int pre_block_split(int64_t k, int64_t block, int split, TileGrid &g, int *panel)
+{
     *panel = 0;
     if (block == 0) return MTQ_OK;
     if (block < 32 || (block & (block - 1)) != 0) return fail(MTQ_ERR_INVALID, "block must be 0 or a power of two from 32 on");
@@ -3844,6 +3967,168 @@ extern "C" int mtq_packed_glu_matmul_skinny_grouped_gather(const void *x, int64_
     return packed_glu_skinny_grouped(true, "mtq_packed_glu_matmul_skinny_grouped_gather", x, 0, k, ldx, group_rows, gate_packed, gate_bytes,
                                      gate_maps, gate_offsets, gate_bases, up_packed, up_bytes, up_maps, up_offsets, up_bases, count, n, bias_gate,
                                      bias_up, ldb, act, y, out_dtype, ldy, split, workspace, workspace_bytes, stream, true, src, tokens, topk);
+}
+
+// 10p. the grouped skinny entries with the X prologue inside the kernel (include/mtq_grouped_pre.h): 9b.'s rule on grouped_shape's split
+static int grouped_pre_shape(int64_t total_rows, int64_t count, int64_t n, int64_t k, int64_t block, int split, bool glu, TileGrid &g, int *panel)
+{
+    if (int rc = glu ? glu_grouped_shape(total_rows, count, n, k, split, &g.th, &g.tw, &g.eff)
+                     : grouped_shape(total_rows, count, n, k, split, &g.th, &g.tw, &g.eff))
+        return rc;
+    return pre_block_split(k, block, split, g, panel);
+}
+
+// pre_args for an arena: row e of in_exponents is read at e * k, so every row must keep the alignment
+static int grouped_pre_args(int64_t k, int64_t block, const uint8_t *in_exponents, int panel, PreArgs &a)
+{
+    if (int rc = pre_args(block, in_exponents, panel, a)) return rc;
+    if (in_exponents && k % kGroup != 0) return fail(MTQ_ERR_INVALID, "in_exponents needs k % 16 == 0: every expert's row must be 16-byte aligned");
+    return MTQ_OK;
+}
+
+extern "C" int mtq_packed_grouped_pre_split(int64_t count, int64_t total_rows, int64_t n, int64_t k, int64_t block, int split)
+{
+    TileGrid g;
+    int panel;
+    if (grouped_pre_shape(total_rows, count, n, k, block, split, false, g, &panel)) return -1;
+    return g.eff;
+}
+
+extern "C" size_t mtq_packed_glu_skinny_grouped_pre_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int64_t block, int split)
+{
+    TileGrid g;
+    int panel;
+    if (grouped_pre_shape(total_rows, count, n, k, block, split, true, g, &panel)) return (size_t)-1;
+    return glu_skinny_workspace(total_rows, n, g.eff);
+}
+
+extern "C" size_t mtq_packed_linear_skinny_grouped_pre_workspace_bytes(int64_t total_rows, int64_t count, int64_t n, int64_t k, int64_t block,
+                                                                       int split, int combine)
+{
+    TileGrid g;
+    int panel;
+    if (grouped_pre_shape(total_rows, count, n, k, block, split, false, g, &panel)) return (size_t)-1;
+    if (!combine) return skinny_workspace(total_rows, n, g.eff);
+    if (total_rows > ((int64_t)1 << 56) / n) return (size_t)-1;
+    return skinny_combine_workspace(total_rows, n, g.eff);
+}
+
+extern "C" int mtq_packed_glu_skinny_grouped_pre(const void *x, int64_t tokens, int64_t topk, int64_t k, int64_t ldx, const int32_t *src,
+                                                 const int32_t *group_rows, int64_t block, const uint8_t *in_exponents, const void *gate_packed,
+                                                 size_t gate_bytes, const int8_t *gate_maps, const uint32_t *gate_offsets,
+                                                 const uint64_t *gate_bases, const void *up_packed, size_t up_bytes, const int8_t *up_maps,
+                                                 const uint32_t *up_offsets, const uint64_t *up_bases, int64_t count, int64_t n,
+                                                 const float *bias_gate, const float *bias_up, int64_t ldb, int act, void *y, int out_dtype,
+                                                 int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *name = "mtq_packed_glu_skinny_grouped_pre";
+    TileGrid g;
+    int panel = 0;
+    int64_t S = 0;
+    if (int rc = gemm_args(!x || !group_rows || !gate_packed || !gate_maps || !gate_offsets || !gate_bases || !up_packed || !up_maps || !up_offsets ||
+                               !up_bases || !y,
+                           out_dtype,
+                           [&](TileGrid &s) {
+                               if (int rc = moe_slots_arg(tokens, topk, &S)) return rc;
+                               return grouped_pre_shape(S, count, n, k, block, split, true, s, &panel);
+                           },
+                           g, k, ldx, n, ldy, bias_gate || bias_up, ldb, count, {gate_packed, gate_bytes}, {up_packed, up_bytes}))
+        return rc;
+    if (ldx > (int64_t)1 << 40) return fail(MTQ_ERR_INVALID, "matrix too large");
+    if (reinterpret_cast<uintptr_t>(x) % 2 != 0 || reinterpret_cast<uintptr_t>(src) % 4 != 0)
+        return fail(MTQ_ERR_INVALID, "x or src is not aligned to its type");
+    if (int rc = glu_act(act)) return rc;
+    PreArgs a;
+    if (int rc = grouped_pre_args(k, block, in_exponents, panel, a)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, glu_skinny_workspace(S, n, g.eff), kWsGlu, "split")) return rc;
+    const int64_t blocks = (g.th + 1) / 2 * count * g.eff, nchunks = grouped_nchunks(n);
+    if (int rc = grid_args({blocks, count * nchunks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    auto kernel = block ? (src ? packed_glu_skinny_grouped_pre_kernel<true, true> : packed_glu_skinny_grouped_pre_kernel<true, false>)
+                        : (src ? packed_glu_skinny_grouped_pre_kernel<false, true> : packed_glu_skinny_grouped_pre_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), (size_t)kTile * panel * sizeof(uint16_t), st,
+                       static_cast<const uint16_t *>(x), (int)S, (int)k, ldx, (int)x_vec_of(x, ldx), a, group_rows,
+                       static_cast<const uint8_t *>(gate_packed), (uint64_t)gate_bytes, gate_maps, gate_offsets, gate_bases,
+                       static_cast<const uint8_t *>(up_packed), (uint64_t)up_bytes, up_maps, up_offsets, up_bases, (int)count, (int)n, (int)g.th,
+                       (int)g.tw, g.eff, ws, src, (int)topk);
+    if (int rc = check_launch(name)) return rc;
+    launch_out(out_dtype, glu_skinny_grouped_reduce_kernel<true>, glu_skinny_grouped_reduce_kernel<false>, dim3((unsigned)(count * nchunks)), dim3(256),
+               st, ws, S, n, g.eff, group_rows, nchunks, bias_gate, bias_up, ldb, act, y, ldy);
+    return check_launch(name);
+}
+
+extern "C" int mtq_packed_linear_skinny_grouped_pre(const void *x, int64_t k, int64_t ldx, const int32_t *group_rows, int64_t block,
+                                                    const uint8_t *in_exponents, const void *packed, size_t packed_bytes, const int8_t *maps,
+                                                    const uint32_t *offsets, const uint64_t *bases, int64_t count, int64_t n, int expert_dtype,
+                                                    const int32_t *row_of, const float *weights, int64_t ldw, const void *base, int base_dtype,
+                                                    int64_t ldbase, int64_t tokens, int64_t topk, void *y, int out_dtype, int64_t ldy, int split,
+                                                    void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *name = "mtq_packed_linear_skinny_grouped_pre";
+    TileGrid g;
+    int panel = 0;
+    int64_t S = 0;
+    const StreamArg w = {packed, packed_bytes};
+    const bool combine = row_of || weights || base;
+    if (combine && (!row_of || !weights)) return fail(MTQ_ERR_INVALID, kNullArg);
+    if (int rc = gemm_args(!x || !group_rows || !packed || !maps || !offsets || !bases || !y, out_dtype,
+                           [&](TileGrid &s) {
+                               if (combine) {
+                                   if (int rc = dtype_arg(expert_dtype, "expert_dtype")) return rc;
+                                   if (base)
+                                       if (int rc = dtype_arg(base_dtype, "base_dtype")) return rc;
+                               }
+                               if (int rc = moe_slots_arg(tokens, topk, &S)) return rc;
+                               if (int rc = grouped_pre_shape(S, count, n, k, block, split, false, s, &panel)) return rc;
+                               if (combine && S > ((int64_t)1 << 56) / n) return fail(MTQ_ERR_INVALID, "the workspace of this split is too large");
+                               return (int)MTQ_OK;
+                           },
+                           g, k, ldx, n, ldy, false, 0, count, w, w))
+        return rc;
+    if (combine) {
+        if (ldw < topk) return fail(MTQ_ERR_INVALID, "ldw < topk");
+        if (base && ldbase < n) return fail(MTQ_ERR_INVALID, "ldbase < n");
+        if (ldw > (int64_t)1 << 31 || ldy > (int64_t)1 << 31 || (base && ldbase > (int64_t)1 << 31)) return fail(MTQ_ERR_INVALID, "matrix too large");
+        const size_t y_el = out_dtype == MTQ_DTYPE_BF16 ? 2 : 4, base_el = base_dtype == MTQ_DTYPE_BF16 ? 2 : 4;
+        if (reinterpret_cast<uintptr_t>(y) % y_el != 0 || reinterpret_cast<uintptr_t>(row_of) % 4 != 0 ||
+            reinterpret_cast<uintptr_t>(weights) % 4 != 0 || (base && reinterpret_cast<uintptr_t>(base) % base_el != 0))
+            return fail(MTQ_ERR_INVALID, "an operand is not aligned to its type");
+    }
+    PreArgs a;
+    if (int rc = grouped_pre_args(k, block, in_exponents, panel, a)) return rc;
+    if (combine) {
+        if (int rc = workspace_args(workspace, workspace_bytes, skinny_combine_workspace(S, n, g.eff),
+                                    "workspace is null: the experts' partial sums need one at every split", "split"))
+            return rc;
+    } else if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(S, n, g.eff), kWsSplit, "split")) {
+        return rc;
+    }
+    const int64_t blocks = (g.th + kSkinnyWaves - 1) / kSkinnyWaves * count * g.eff, nchunks = grouped_nchunks(n);
+    if (int rc = grid_args({blocks, (combine ? tokens : count) * nchunks})) return rc;
+    if (int rc = require_device()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws = static_cast<float *>(workspace);
+    // combine: the wave stores float32 to the workspace at every split, at an effective split of 1 as its Y at pitch n (4c.)
+    const bool bf = !combine && out_dtype == MTQ_DTYPE_BF16;
+    auto kernel = block ? (bf ? packed_linear_skinny_grouped_pre_kernel<true, true> : packed_linear_skinny_grouped_pre_kernel<false, true>)
+                        : (bf ? packed_linear_skinny_grouped_pre_kernel<true, false> : packed_linear_skinny_grouped_pre_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * kSkinnyWaves), (size_t)kTile * panel * sizeof(uint16_t), st,
+                       static_cast<const uint16_t *>(x), (int)S, (int)k, ldx, (int)x_vec_of(x, ldx), a, group_rows,
+                       static_cast<const uint8_t *>(packed), (uint64_t)packed_bytes, maps, offsets, bases, (int)count, (int)n, (int)g.th, (int)g.tw,
+                       g.eff, combine ? static_cast<void *>(ws) : y, combine ? n : ldy, ws);
+    if (!combine) return grouped_reduce(name, out_dtype, st, ws, S, n, g.eff, group_rows, count, nullptr, 0, y, ldy);
+    if (int rc = check_launch(name)) return rc;
+    const int base_kind = !base ? 0 : (base_dtype == MTQ_DTYPE_BF16 ? 1 : 2);
+    const dim3 grid((unsigned)(tokens * nchunks));
+    if (expert_dtype == MTQ_DTYPE_BF16)
+        launch_out(out_dtype, skinny_grouped_combine_kernel<true, true>, skinny_grouped_combine_kernel<true, false>, grid, dim3(256), st, ws, S, n,
+                   g.eff, row_of, weights, ldw, base, base_kind, ldbase, (int)topk, nchunks, y, ldy);
+    else
+        launch_out(out_dtype, skinny_grouped_combine_kernel<false, true>, skinny_grouped_combine_kernel<false, false>, grid, dim3(256), st, ws, S, n,
+                   g.eff, row_of, weights, ldw, base, base_kind, ldbase, (int)topk, nchunks, y, ldy);
+    return check_launch(name);
 }
 
 // 10c. The decode route's entries with a wave per 32-row chunk (include/mtq_glu_chunked.h): the bodies of 10., 10g. and 4c. with

@@ -216,6 +216,15 @@ PACKED_PRE_SIGNATURES = {
     "mtq_packed_glu_skinny_pre": ("i", "pllllppzpppzpplppipilipzp", True),
 }
 PACKED_PRE_EXPORTS = tuple(PACKED_PRE_SIGNATURES)
+# include/mtq_grouped_pre.h, which mtq.h includes last: the grouped skinny products of the MoE decode route with that prologue inside
+GROUPED_PRE_SIGNATURES = {
+    "mtq_packed_grouped_pre_split": ("i", "llllli", True),
+    "mtq_packed_glu_skinny_grouped_pre_workspace_bytes": ("z", "llllli", True),
+    "mtq_packed_glu_skinny_grouped_pre": ("i", "pllllpplppzppppzpppllpplipilipzp", True),
+    "mtq_packed_linear_skinny_grouped_pre_workspace_bytes": ("z", "lllllii", True),
+    "mtq_packed_linear_skinny_grouped_pre": ("i", "pllplppzpppllipplpilllpilipzp", True),
+}
+GROUPED_PRE_EXPORTS = tuple(GROUPED_PRE_SIGNATURES)
 _CTYPE = {"p": ctypes.c_void_p, "l": ctypes.c_int64, "u": ctypes.c_uint32, "i": ctypes.c_int, "d": ctypes.c_double, "z": ctypes.c_size_t,
           "q": ctypes.c_uint64, "v": None, "s": ctypes.c_char_p}
 
@@ -273,7 +282,8 @@ def _bind(L) -> None:
     found = version()
     if found < MTQ_VERSION:
         raise MtqError(f"{LIB_PATH} is version {found}, older than this package (it needs {MTQ_VERSION}): {_REBUILD}")
-    for name, (result, params, optional) in (*SIGNATURES.items(), *MOE_DECODE_SIGNATURES.items(), *GLU_CHUNKED_SIGNATURES.items(), *PACKED_PRE_SIGNATURES.items()):
+    for name, (result, params, optional) in (*SIGNATURES.items(), *MOE_DECODE_SIGNATURES.items(), *GLU_CHUNKED_SIGNATURES.items(),
+                                             *PACKED_PRE_SIGNATURES.items(), *GROUPED_PRE_SIGNATURES.items()):
         fn = getattr(L, name, None)
         if fn is None:
             if optional:
@@ -2403,6 +2413,158 @@ def moe_down_combine(h, group_rows, arena, maps_dev, offsets_dev, bases_dev, cou
     check(fn(h.data_ptr(), k, ldx, pg, ptr, arena.numel(), pm, po, pb, count, n, expert_code, pr, weights.data_ptr(), _rows_ld(weights, T, K),
              base_ptr, base_code, ldbase, T, K, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
     return out
+
+
+# ---- the grouped skinny products with the X prologue inside the kernel (include/mtq_grouped_pre.h): (n, k) experts, the walking kernel
+
+def grouped_pre_available() -> bool:
+    """Whether this build of the library has mtq_packed_glu_skinny_grouped_pre, mtq_packed_linear_skinny_grouped_pre, their size
+    functions and the split rule (optional symbols)."""
+    return _has(GROUPED_PRE_EXPORTS)
+
+
+def packed_grouped_pre_split(count: int, total_rows: int, n: int, k: int, block: int, split: int = 0) -> int:
+    """mtq_packed_grouped_pre_split (a host function: no GPU): the effective split of the *_grouped_pre entries - with a block, equal
+    slices of whole blocks, at most the unfused grouped entry's own choice; MtqError with the library's reason for refused arguments."""
+    eff = int(_entry("mtq_packed_grouped_pre_split")(int(count), int(total_rows), int(n), int(k), int(block), int(split)))
+    if eff < 0:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return eff
+
+
+def packed_glu_skinny_grouped_pre_workspace(total_rows: int, count: int, n: int, k: int, block: int, split: int = 0) -> int:
+    """mtq_packed_glu_skinny_grouped_pre_workspace_bytes (a host function: no GPU): packed_glu_skinny_grouped_workspace_bytes at the
+    effective split of packed_grouped_pre_split."""
+    return _workspace_size("mtq_packed_glu_skinny_grouped_pre_workspace_bytes", total_rows, count, n, k, block, split)
+
+
+def packed_linear_skinny_grouped_pre_workspace(total_rows: int, count: int, n: int, k: int, block: int, split: int = 0, combine: bool = False) -> int:
+    """mtq_packed_linear_skinny_grouped_pre_workspace_bytes (a host function: no GPU): at the effective split of
+    packed_grouped_pre_split, packed_linear_skinny_grouped_workspace_bytes, or with `combine` moe_down_combine_workspace_bytes."""
+    return _workspace_size("mtq_packed_linear_skinny_grouped_pre_workspace_bytes", total_rows, count, n, k, block, split, bool(combine))
+
+
+def _grouped_pre_args(count: int, k: int, block, in_exponents) -> tuple:
+    """(block, pointer) of a *_grouped_pre entry: in_exponents None, or a uint8 device tensor of count rows of k shifts in 0 .. 7."""
+    if in_exponents is None:
+        return int(block), None
+    if in_exponents.dim() != 2 or tuple(in_exponents.shape) != (count, k):
+        raise MtqError(f"in_exponents must be ({count}, {k}), one row per expert, got {tuple(in_exponents.shape)}")
+    return int(block), _buffer(in_exponents, _torch().uint8, count * k, "in_exponents")
+
+
+def _grouped_bias_args(count: int, n: int, bias_gate, bias_up) -> tuple:
+    """(bias_gate pointer, bias_up pointer, ldb) of the grouped gated entries: None or float32 (count, n) device tensors of one pitch."""
+    torch = _torch()
+    ptrs, ldb = [], 0
+    for which, bias in (("bias_gate", bias_gate), ("bias_up", bias_up)):
+        if bias is None:
+            ptrs.append(None)
+            continue
+        if bias.dtype != torch.float32 or bias.dim() != 2 or tuple(bias.shape) != (count, n) or bias.stride(1) != 1 or not bias.is_cuda:
+            raise MtqError(f"{which} must be a float32 ({count}, {n}) device tensor with contiguous rows")
+        pitch = bias.stride(0) if count > 1 else max(bias.stride(0), n)
+        if ldb and pitch != ldb:
+            raise MtqError("bias_gate and bias_up must have one row pitch")
+        ptrs.append(bias.data_ptr())
+        ldb = pitch
+    return ptrs[0], ptrs[1], ldb
+
+
+def packed_glu_skinny_grouped_pre(x, group_rows, gate, up, count: int, n: int, block: int = 0, in_exponents=None, src=None, topk: int = 1,
+                                  act="silu", bias_gate=None, bias_up=None, out_dtype=None, out=None, split: int = 0, workspace=None,
+                                  stream="current"):
+    """mtq_packed_glu_skinny_grouped_pre on the current stream: the grouped skinny GLU on bf16(hadamard_rows(row, block)·2^−in_exponents[e])
+    for every row of expert e, the transform formed inside the kernel once per workgroup.  src None: packed_glu_skinny_grouped's operands,
+    x (S, k) in expert order; src (the plan's int32 [S], S = tokens * topk): moe_glu_gather's, x the (tokens, k) token matrix.
+    in_exponents: None or a uint8 (count, k) device tensor of shifts in 0 .. 7.  split: an explicit split must cut K into equal slices of
+    whole blocks (packed_grouped_pre_split; 0: the library's choice).  → (S, n); an `out` allocated here starts as zeros."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.float32
+    code, a = _packed_out_code(out_dtype), _act_code(act)
+    count, n, topk = int(count), int(n), int(topk) if src is not None else 1
+    x_code, _count, _stride, T, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    if count <= 0 or n <= 0 or T <= 0 or topk <= 0:
+        raise MtqError("the rows of x, topk, count and n must be positive")
+    S = T * topk
+    th, tw = tiles_hw(n, k)
+    sides = []
+    for which, (arena, maps_dev, offsets_dev, bases_dev) in (("gate", gate), ("up", up)):
+        pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+        sides += [_arena(arena, count, th * tw, f"the {which} arena"), arena.numel(), pm, po, pb]
+    pg = _buffer(group_rows, torch.int32, count + 1, "group_rows")
+    if group_rows.numel() != count + 1:
+        raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got {group_rows.numel()}")
+    ps = None
+    if src is not None:
+        ps = _buffer(src, torch.int32, S, "src")
+        if src.numel() != S:
+            raise MtqError(f"src must have tokens * topk = {S} entries, got {src.numel()}")
+    pre = _grouped_pre_args(count, k, block, in_exponents)
+    bg, bu, ldb = _grouped_bias_args(count, n, bias_gate, bias_up)
+    fn = _entry("mtq_packed_glu_skinny_grouped_pre")
+    need = packed_glu_skinny_grouped_pre_workspace(S, count, n, k, block, split)
+    out, ldy = _packed_out(out, S, n, out_dtype, x.device, zeros=True)
+    ws_ptr, ws_bytes = _packed_workspace(workspace, need, x.device)
+    check(fn(x.data_ptr(), T, topk, k, ldx, ps, pg, *pre, *sides, count, n, bg, bu, ldb, a, out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes,
+             _packed_stream_ptr(stream)))
+    return out
+
+
+def packed_linear_skinny_grouped_pre(x, group_rows, arena, maps_dev, offsets_dev, bases_dev, count: int, n: int, block: int = 0, in_exponents=None,
+                                     row_of=None, weights=None, base=None, expert_dtype=None, out_dtype=None, out=None, split: int = 0,
+                                     workspace=None, stream="current"):
+    """mtq_packed_linear_skinny_grouped_pre on the current stream: the grouped skinny product (no bias) on
+    bf16(hadamard_rows(row, block)·2^−in_exponents[e]) for every row of expert e, the transform formed inside the kernel.  x: (S, k) bf16
+    in expert order.  row_of and weights None: packed_linear_skinny_grouped's result → (S, n), an `out` allocated here starting as zeros;
+    row_of, weights (tokens, topk) float32, base, expert_dtype as moe_down_combine takes them: that entry's result → (tokens, n).
+    block, in_exponents, split as packed_glu_skinny_grouped_pre's."""
+    torch = _torch()
+    out_dtype, expert_dtype = out_dtype or torch.float32, expert_dtype or torch.float32
+    code, expert_code = _packed_out_code(out_dtype), _packed_out_code(expert_dtype)
+    count, n = int(count), int(n)
+    x_code, _count, _stride, S, k, ldx = _matrix(x, (2,))
+    if x_code != DTYPE_BF16:
+        raise MtqError("x must be a bfloat16 tensor")
+    combine = weights is not None
+    if (row_of is None) == combine or (base is not None and not combine):
+        raise MtqError("row_of and weights come together, and base only with them")
+    T, K = S, 1
+    if combine:
+        if weights.dim() != 2 or weights.dtype != torch.float32 or (weights.shape[1] > 1 and weights.stride(1) != 1) or not weights.is_cuda:
+            raise MtqError("weights must be a float32 (tokens, topk) device tensor with contiguous rows")
+        T, K = (int(v) for v in weights.shape)
+        if T * K != S:
+            raise MtqError(f"x must be ({T * K}, k), one row per slot, got {tuple(x.shape)}")
+    if S <= 0 or K <= 0 or count <= 0 or n <= 0:
+        raise MtqError("the rows of x, topk, count and n must be positive")
+    th, tw = tiles_hw(n, k)
+    pm, po, pb = _batch_tables(maps_dev, offsets_dev, bases_dev, count, th * tw)
+    ptr = _arena(arena, count, th * tw, "arena")
+    pg = _buffer(group_rows, torch.int32, count + 1, "group_rows")
+    if group_rows.numel() != count + 1:
+        raise MtqError(f"group_rows must have count + 1 = {count + 1} entries, got {group_rows.numel()}")
+    pr, pw, ldw, base_ptr, base_code, ldbase = None, None, 0, None, 0, 0
+    if combine:
+        pr, pw, ldw = _buffer(row_of, torch.int32, S, "row_of"), weights.data_ptr(), _rows_ld(weights, T, K)
+        if row_of.numel() != S:
+            raise MtqError(f"row_of must have tokens * topk = {S} entries, got {row_of.numel()}")
+    if base is not None:
+        base_code, _count, _stride, brows, bcols, ldbase = _matrix(base, (2,))
+        if (brows, bcols) != (T, n):
+            raise MtqError(f"base must be ({T}, {n}), got {tuple(base.shape)}")
+        base_ptr = base.data_ptr()
+    pre = _grouped_pre_args(count, k, block, in_exponents)
+    fn = _entry("mtq_packed_linear_skinny_grouped_pre")
+    need = packed_linear_skinny_grouped_pre_workspace(S, count, n, k, block, split, combine)
+    out, ldy = _packed_out(out, T, n, out_dtype, x.device, zeros=not combine)
+    ws_ptr, ws_bytes = _packed_workspace(workspace, need, x.device) if need else (None, 0)
+    check(fn(x.data_ptr(), k, ldx, pg, *pre, ptr, arena.numel(), pm, po, pb, count, n, expert_code, pr, pw, ldw, base_ptr, base_code, ldbase, T, K,
+             out.data_ptr(), code, ldy, int(split), ws_ptr, ws_bytes, _packed_stream_ptr(stream)))
+    return out
+
 
 MOE_ROUTE = ("mtq_moe_route",)
 ROUTE_SOFTMAX, ROUTE_SIGMOID = 0, 1                       # include/mtq.h MTQ_ROUTE_SOFTMAX, MTQ_ROUTE_SIGMOID

@@ -663,6 +663,96 @@ def _takes_fused_prologue(o: _Orientation, what: str, prologue: str, backend: st
     return False
 
 
+AUTO_FUSED_GROUPED_BLOCK, AUTO_FUSED_GROUPED_MAX_ROWS = 256, 16   # prologue="auto" of the grouped entries
+
+
+def _auto_takes_fused_grouped(rows: int, rotate: int) -> bool:
+    """prologue="auto" of the grouped entries (linear_grouped, glu_grouped_skinny, moe_glu, moe_down_combine and the expert modules): the
+    range in which profiles/packed_grouped_prologue.txt shows the fused entry ahead of the staged route by more than the spread of the
+    staged medians on every row - block 256, the one block timed, up to 16 rows (S = 2, 8 and 16 there: 0.48-0.95 of the staged time,
+    the spread under 0.02).  Shifts without a rotation LOSE fused (1.2-2.4: every wave shifts all 32 row lanes of its own loads) and
+    stay staged; at 64 rows over 8 experts the unshifted rows lose (1.01-1.06); other blocks were not timed: staged."""
+    return rotate == AUTO_FUSED_GROUPED_BLOCK and rows <= AUTO_FUSED_GROUPED_MAX_ROWS
+
+
+class _GroupShifts:
+    """_Shifts for an arena: (count, k) shifts in 0 .. 7, row e those of expert e (shared by its gate and up)."""
+
+    def __init__(self, in_exponents, count: int, k: int, device=None):
+        import torch
+
+        exps = np.asarray(in_exponents.cpu().numpy() if _is_torch(in_exponents) else in_exponents)
+        if exps.shape != (count, k) or exps.size and (exps.min() < 0 or exps.max() > 7 or not np.array_equal(exps, np.rint(exps))):
+            raise ValueError(f"in_exponents must be ({count}, {k}) integers in 0 .. 7")
+        self.neg = -torch.from_numpy(exps.astype(np.int32))
+        self.u8 = torch.from_numpy(exps.astype(np.uint8))
+        if device is not None:
+            self.neg, self.u8 = self.neg.to(device), self.u8.to(device)
+
+
+def _group_shifts(in_exponents, count: int, k: int, device=None):
+    if in_exponents is None or isinstance(in_exponents, _GroupShifts):
+        return in_exponents
+    return _GroupShifts(in_exponents, count, k, device)
+
+
+def _staged_x_grouped(x2, group_rows, rotate: int, shifts, backend: str):
+    """The staged prologue of a grouped call: hadamard over the rows, then torch.ldexp by −p[e] with each row's expert e found from
+    group_rows by torch.searchsorted on the tensor's own device: nothing is read back.  A row of no group takes the last expert's shifts;
+    no product reads it."""
+    import torch
+
+    x2 = _as_torch(x2)
+    if rotate:
+        x2 = hadamard(x2, rotate, out_dtype=torch.bfloat16, backend=backend)
+    if shifts is not None:
+        g = group_rows if _is_torch(group_rows) else torch.from_numpy(np.asarray(group_rows))
+        ends = g[1:].to(device=x2.device, dtype=torch.int64).contiguous()
+        e = torch.searchsorted(ends, torch.arange(x2.shape[0], device=x2.device), right=True).clamp_(max=ends.numel() - 1)
+        x2 = torch.ldexp(x2, shifts.neg.to(x2.device)[e])
+    return x2
+
+
+def _no_fused_grouped(o: _Orientation, backend: str, kernel: str, bias: bool = False):
+    """Why no *_grouped_pre entry serves this orientation, backend and resolved kernel whatever the shape, or None."""
+    if o.kn:
+        return 'stored="transpose": the (k, n) entries have no fused prologue'
+    if kernel != "walk":
+        return f'kernel="{kernel}": only the walking kernel (kernel="walk") has a fused prologue'
+    if backend != "hip":
+        return "the emulation backend has no fused entry"
+    if bias:
+        return "the fused entries take no bias"
+    if not hb.grouped_pre_available():
+        return f"it needs {' and '.join(hb.GROUPED_PRE_EXPORTS[2::2])}, {_LACKS}"
+    return None
+
+
+def _grouped_prologue(o: _Orientation, what: str, backend: str, kernel: str, prologue: str, rotate: int, in_exponents, count: int, rows: int,
+                      n: int, k: int, split: int, device=None, bias: bool = False):
+    """rotate=, in_exponents=, prologue= of a grouped call → (rotate, shifts, fused).  fused: the call goes through a *_grouped_pre entry;
+    "fused" raises MtqError with the reason where that entry cannot serve, "auto" asks _auto_takes_fused_grouped."""
+    if prologue not in PROLOGUES:
+        raise MtqError(f"prologue must be one of {PROLOGUES}, got {prologue!r}")
+    if not rotate and in_exponents is None:
+        return 0, None, False
+    rotate = check_block(k, rotate) if rotate else 0
+    shifts = _group_shifts(in_exponents, count, k, device)
+    if prologue == "staged" or (prologue == "auto" and not _auto_takes_fused_grouped(rows, rotate)):
+        return rotate, shifts, False
+    why = _no_fused_grouped(o, backend, kernel, bias)
+    if why is None and rows:
+        try:
+            hb.packed_grouped_pre_split(count, rows, n, k, rotate, split)
+        except MtqError as e:
+            why = str(e)
+    if why is None:
+        return rotate, shifts, True
+    if prologue == "fused":
+        raise MtqError(f'{what}(prologue="fused"): {why}')
+    return rotate, shifts, False
+
+
 def _product(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dtype, backend, kernel, split, workspace, rotate=0, in_exponents=None,
              prologue="staged"):
     """linear and matmul."""
@@ -1258,7 +1348,8 @@ def _arena_args(batch: PackedBatch) -> tuple:
     return batch.arena, batch.maps_dev, batch.offsets_dev, batch.bases_dev
 
 
-def _grouped(o: _Orientation, x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, kernel):
+def _grouped(o: _Orientation, x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, kernel, rotate=0, in_exponents=None,
+             prologue="staged"):
     """linear_grouped and matmul_grouped (kernel "walk" / "chunks", resolved) and the two *_grouped_wide (kernel "wide", no split)."""
     batch = _resolve_batch(pts_or_batch)
     _check_out_dtype(out_dtype)
@@ -1269,6 +1360,10 @@ def _grouped(o: _Orientation, x, group_rows, pts_or_batch, bias, out_dtype, back
         raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
     T = int(x.shape[0])
     group_rows, on_device = _resolve_group_rows(group_rows, count, T)
+    rotate, shifts, fused = _grouped_prologue(o, "linear_grouped", backend, kernel, prologue, rotate, in_exponents, count, T, n, k, split,
+                                              x.device if backend == "hip" and _is_torch(x) else None, bias is not None)
+    if (rotate or shifts is not None) and not fused and T:
+        x = _staged_x_grouped(x, group_rows, rotate, shifts, backend)
     if backend == "hip":
         launch, _size = _grouped_entry(o, hb, kernel)            # a missing kernel is refused before any device work
         batch = batch_to_device(batch)
@@ -1277,6 +1372,10 @@ def _grouped(o: _Orientation, x, group_rows, pts_or_batch, bias, out_dtype, back
             import torch
 
             return torch.zeros((0, n), dtype=dtype, device=batch.arena.device)
+        if fused:
+            return hb.packed_linear_skinny_grouped_pre(x, _device_group_rows(group_rows, on_device, batch.arena.device), *_arena_args(batch), count,
+                                                       n, block=rotate, in_exponents=None if shifts is None else shifts.u8, out_dtype=dtype,
+                                                       split=split, workspace=workspace)
         more = {} if kernel == "wide" else {"split": split}
         return launch(x, _device_group_rows(group_rows, on_device, batch.arena.device), *_arena_args(batch), count, n,
                       bias=_device_bias(bias, batch.arena.device), out_dtype=dtype, workspace=workspace, **more)
@@ -1306,8 +1405,15 @@ def _grouped_batch(o: _Orientation, x3d, pts_or_batch, bias, out_dtype, backend,
 
 
 def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0,
-                   workspace=None, kernel: str = "walk"):
+                   workspace=None, kernel: str = "walk", rotate: int = 0, in_exponents=None, prologue: str = "staged"):
     """Y[rows of group e] = X[rows of group e]·Ŵ[e]ᵀ (+ bias[e]) for all experts of a batch at once → (T, n).
+
+    rotate, in_exponents, prologue: for experts packed from hadamard.rotate_weight / awq.scale_weight, the product is taken with
+    X″[r] = bf16(bf16(x[r]·H_rotate)·2^−in_exponents[e]) for the expert e that owns row r (x a bf16 torch tensor); in_exponents: (count, k)
+    integers in 0 .. 7.  prologue (PROLOGUES): "staged", hadamard over the rows and one torch.ldexp with each row's expert from
+    torch.searchsorted on group_rows, in front of the unchanged entry, on every backend and kernel; "fused" (hip, kernel="walk", no
+    bias), mtq_packed_linear_skinny_grouped_pre forms X″ inside the kernel - bit for bit the staged result at the effective split of
+    hip_backend.packed_grouped_pre_split, MtqError with the reason where it cannot serve; "auto", _auto_takes_fused_grouped.
 
     x: (T, k); group_rows: count + 1 entries, group e owning rows [group_rows[e], group_rows[e + 1]) — a list or NumPy array is checked
     here (count + 1 entries, nondecreasing, first 0, last T), a device tensor (int32) is passed on as it is and clamped by the kernel;
@@ -1321,7 +1427,8 @@ def linear_grouped(x, group_rows, pts_or_batch, bias=None, out_dtype: str = "flo
     mtq_packed_linear_skinny_grouped_chunked, one wave per (slice, chunk, tile row) with the chunk list made on the device, for routings
     with hot experts — the same bits, a workspace at every split, MtqError when the library lacks it; "auto", GROUPED_AUTO_KERNEL.
     emulation: per group the float64 product of the decoded weight, rounded once, as linear does, under every kernel name."""
-    return _grouped(_NK, x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, _grouped_kernel(_NK, kernel))
+    return _grouped(_NK, x, group_rows, pts_or_batch, bias, out_dtype, backend, split, workspace, _grouped_kernel(_NK, kernel), rotate,
+                    in_exponents, prologue)
 
 
 def linear_batch(x3d, pts_or_batch, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 0, workspace=None,
@@ -1485,8 +1592,11 @@ def _need_glu_grouped_skinny_chunked(o: _Orientation, hb, what: str) -> None:
 
 
 def glu_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "silu", bias_gate=None, bias_up=None, out_dtype: str = "float32",
-                       backend: Optional[str] = None, split: int = 0, workspace=None, kernel: str = "walk"):
+                       backend: Optional[str] = None, split: int = 0, workspace=None, kernel: str = "walk", rotate: int = 0, in_exponents=None,
+                       prologue: str = "staged"):
     """glu_grouped for decode-sized groups from the fused split-K kernel: mtq_packed_glu_skinny_grouped, two launches over both arenas.
+    rotate, in_exponents, prologue: linear_grouped's, one row of shifts per expert for its gate and up; "fused" is
+    mtq_packed_glu_skinny_grouped_pre, which forms X″ once per workgroup for both projections (biases allowed).
     The arguments are resolved as glu_grouped resolves them.  Per group the bits of two linear_grouped(kernel="walk") calls into float32
     at that `split` and hip_backend.glu_combine: the skinny family's sums, which may differ from glu_grouped's in the last bits.  Rows
     of no group are zeros.  workspace: an optional uint8 device tensor of hip_backend.packed_glu_skinny_grouped_workspace_bytes bytes.
@@ -1496,7 +1606,7 @@ def glu_grouped_skinny(x, group_rows, gate_batch, up_batch, act: str = "silu", b
     many rows - the same bits for a nondecreasing group_rows, its workspace hip_backend.glu_grouped_chunked_workspace_bytes bytes; "auto", GLU_SKINNY_GROUPED_AUTO_KERNEL.  A library without the kernel asked for raises MtqError, it never runs the other.
     emulation: glu_grouped's value, under every kernel name."""
     return _glu_grouped(_NK, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, "skinny", ("skinny",), split,
-                        workspace, kernel)
+                        workspace, kernel, rotate, in_exponents, prologue)
 
 
 def _glu(o: _Orientation, what: str, x, gate: PackedTensor, up: PackedTensor, act, bias_gate, bias_up, out_dtype, backend, kernel):
@@ -1582,9 +1692,9 @@ def _glu_skinny(o: _Orientation, what: str, x, gate: PackedTensor, up: PackedTen
 
 
 def _glu_grouped(o: _Orientation, x, group_rows, gate_batch, up_batch, act, bias_gate, bias_up, out_dtype, backend, kernel, kernels, split, workspace,
-                 skinny_kernel: str = "walk"):
+                 skinny_kernel: str = "walk", rotate=0, in_exponents=None, prologue="staged"):
     """The grouped gated products: `kernel` one of `kernels`, GLU_GROUPED_KERNELS or, from the *_grouped_skinny functions alone,
-    ("skinny",), whose frame is skinny_kernel (GLU_SKINNY_GROUPED_KERNELS)."""
+    ("skinny",), whose frame is skinny_kernel (GLU_SKINNY_GROUPED_KERNELS).  rotate, in_exponents, prologue: glu_grouped_skinny's."""
     gate_b, up_b = _resolve_batch(gate_batch), _resolve_batch(up_batch)
     _check_act(act)
     _check_kernel(kernel, kernels)
@@ -1600,6 +1710,10 @@ def _glu_grouped(o: _Orientation, x, group_rows, gate_batch, up_batch, act, bias
         raise MtqError(f"x must be (T, {k}), got {tuple(x.shape)}")
     T = int(x.shape[0])
     group_rows, on_device = _resolve_group_rows(group_rows, count, T)
+    rotate, shifts, fused = _grouped_prologue(o, o.glu_grouped_skinny, backend, skinny_kernel, prologue, rotate, in_exponents, count, T, n, k, split,
+                                              x.device if backend == "hip" and _is_torch(x) else None)
+    if (rotate or shifts is not None) and not fused and T:
+        x = _staged_x_grouped(x, group_rows, rotate, shifts, backend)
     if backend == "hip":
         if kernel == "skinny" and skinny_kernel == "chunks":     # a missing kernel is refused before any device work, never replaced
             _need_glu_grouped_skinny_chunked(o, hb, f'{o.glu_grouped_skinny}(kernel="chunks")')
@@ -1616,6 +1730,10 @@ def _glu_grouped(o: _Orientation, x, group_rows, gate_batch, up_batch, act, bias
             return torch.zeros((0, n), dtype=dtype, device=dev)
         group_rows = _device_group_rows(group_rows, on_device, dev)
         bias_gate, bias_up = _device_bias(bias_gate, dev), _device_bias(bias_up, dev)
+        if fused:
+            return hb.packed_glu_skinny_grouped_pre(x, group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, block=rotate,
+                                                    in_exponents=None if shifts is None else shifts.u8, act=act, bias_gate=bias_gate,
+                                                    bias_up=bias_up, out_dtype=dtype, split=split, workspace=workspace)
         if kernel == "skinny":
             more = {"kn": o.kn} if skinny_kernel == "chunks" else {}         # one binding for both orientations
             launch = hb.glu_grouped_chunked if skinny_kernel == "chunks" else getattr(hb, o.hb_glu_grouped_skinny)
@@ -1911,8 +2029,11 @@ def _moe_stage_backend(plan: MoEPlan, backend) -> str:
 
 
 def moe_glu(x, plan: MoEPlan, gate_batch, up_batch, act: str = "silu", out_dtype: str = "bfloat16", stored: str = "rows", split: int = 0,
-            workspace=None, backend: Optional[str] = None, kernel: str = "walk"):
-    """From the token matrix to the experts' gated rows in one step: x (tokens, k) bf16 → h (S, n) in expert order,
+            workspace=None, backend: Optional[str] = None, kernel: str = "walk", rotate: int = 0, in_exponents=None, prologue: str = "staged"):
+    """rotate, in_exponents, prologue: glu_grouped_skinny's.  "staged": moe_dispatch, the staged transform of the dispatched rows, then
+    glu_grouped_skinny with `kernel`; "fused": mtq_packed_glu_skinny_grouped_pre reads the token rows through plan.src and forms X″ in
+    the kernel, so neither the dispatched nor the transformed (S, k) copy exists.  Without them:
+    From the token matrix to the experts' gated rows in one step: x (tokens, k) bf16 → h (S, n) in expert order,
     h[r] = act(x[t]·Ŵg[e]ᵀ) * (x[t]·Ŵu[e]ᵀ) for the slot s = plan.src[r] of token t = s // topk and the expert e that owns row r; rows from
     R = group_rows[count] on are zeros.  stored (MOE_STORED): "rows", the batches hold (n, k) experts; "transpose", (k, n) experts.
     hip: mtq_packed_glu_skinny_grouped_gather (its matmul twin), two launches: the grouped skinny GLU wave reads its X groups from the
@@ -1938,7 +2059,18 @@ def moe_glu(x, plan: MoEPlan, gate_batch, up_batch, act: str = "silu", out_dtype
     if len(x.shape) != 2 or tuple(x.shape) != (T, k):
         raise MtqError(f"x must be ({T}, {k}), got {tuple(x.shape)}")
     backend = _moe_stage_backend(plan, backend)
+    rotate, shifts, fused = _grouped_prologue(o, "moe_glu", backend, kernel, prologue, rotate, in_exponents, count, S, n, k, split,
+                                              x.device if backend == "hip" and _is_torch(x) else None)
     if backend == "hip":
+        if fused:
+            gate_b, up_b = batch_to_device(gate_b), batch_to_device(up_b)
+            return hb.packed_glu_skinny_grouped_pre(x, plan.group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, block=rotate,
+                                                    in_exponents=None if shifts is None else shifts.u8, src=plan.src, topk=K, act=act,
+                                                    out_dtype=_torch_dtype(out_dtype), split=split, workspace=workspace)
+        if rotate or shifts is not None:             # staged: the dispatched copy, transformed, through the unchanged grouped entry
+            xs = _staged_x_grouped(moe_dispatch(x, plan), plan.group_rows, rotate, shifts, backend)
+            return globals()[o.glu_grouped_skinny](xs, plan.group_rows, gate_b, up_b, act=act, out_dtype=out_dtype, backend="hip", split=split,
+                                                   workspace=workspace, kernel=kernel)
         _need_moe_decode(hb, "moe_glu", o.kn, kernel)            # a missing kernel is refused before any device work
         gate_b, up_b = batch_to_device(gate_b), batch_to_device(up_b)
         return hb.moe_glu_gather(x, plan.src, K, plan.group_rows, _arena_args(gate_b), _arena_args(up_b), count, n, act=act,
@@ -1946,6 +2078,8 @@ def moe_glu(x, plan: MoEPlan, gate_batch, up_batch, act: str = "silu", out_dtype
     import torch
 
     xs = _as_torch(moe_dispatch(x, plan))
+    if rotate or shifts is not None:
+        xs = _staged_x_grouped(xs, plan.group_rows, rotate, shifts, backend)
     R = int(plan.group_rows[-1])
     h = torch.zeros((S, n), dtype=_torch_dtype(out_dtype))
     if R:
@@ -1954,8 +2088,11 @@ def moe_glu(x, plan: MoEPlan, gate_batch, up_batch, act: str = "silu", out_dtype
 
 
 def moe_down_combine(h, topk_weights, plan: MoEPlan, down_batch, base=None, expert_dtype: str = "float32", out_dtype: str = "float32",
-                     stored: str = "rows", split: int = 0, workspace=None, out=None, backend: Optional[str] = None, kernel: str = "walk"):
-    """From the experts' gated rows to the layer's output in one step: h (S, n) bf16 in expert order (moe_glu's result), topk_weights
+                     stored: str = "rows", split: int = 0, workspace=None, out=None, backend: Optional[str] = None, kernel: str = "walk",
+                     rotate: int = 0, in_exponents=None, prologue: str = "staged"):
+    """rotate, in_exponents, prologue: linear_grouped's, for down experts packed from rotated / scaled weights: "staged" transforms h in
+    front of the unchanged entry, "fused" is mtq_packed_linear_skinny_grouped_pre with the combine in its reduce.  Without them:
+    From the experts' gated rows to the layer's output in one step: h (S, n) bf16 in expert order (moe_glu's result), topk_weights
     (tokens, topk) float32, base None or (tokens, k_out) → y (tokens, k_out) in out_dtype: the down projection of every row by its
     expert, rounded as a matrix of expert_dtype would hold it, then moe_combine's weighted sum in its order.
     hip: mtq_packed_linear_skinny_grouped_combine (its matmul twin), two launches: the grouped skinny wave writes float32 partial sums
@@ -1983,13 +2120,23 @@ def moe_down_combine(h, topk_weights, plan: MoEPlan, down_batch, base=None, expe
     if base is not None and tuple(base.shape) != (T, n):
         raise MtqError(f"base must be ({T}, {n}), got {tuple(base.shape)}")
     backend = _moe_stage_backend(plan, backend)
+    rotate, shifts, fused = _grouped_prologue(o, "moe_down_combine", backend, kernel, prologue, rotate, in_exponents, count, S, n, k, split,
+                                              h.device if backend == "hip" and _is_torch(h) else None)
+    if (rotate or shifts is not None) and not fused:
+        h = _staged_x_grouped(h, plan.group_rows, rotate, shifts, backend)
     if backend == "hip":
         import torch
 
-        _need_moe_decode(hb, "moe_down_combine", o.kn, kernel)
+        if not fused:
+            _need_moe_decode(hb, "moe_down_combine", o.kn, kernel)
         down = batch_to_device(down)
         if not _is_torch(topk_weights):
             topk_weights = torch.from_numpy(np.ascontiguousarray(topk_weights)).to(plan.row_of.device)
+        if fused:
+            return hb.packed_linear_skinny_grouped_pre(h, plan.group_rows, *_arena_args(down), count, n, block=rotate,
+                                                       in_exponents=None if shifts is None else shifts.u8, row_of=plan.row_of,
+                                                       weights=topk_weights, base=base, expert_dtype=_torch_dtype(expert_dtype),
+                                                       out_dtype=_torch_dtype(out_dtype), out=out, split=split, workspace=workspace)
         return hb.moe_down_combine(h, plan.group_rows, *_arena_args(down), count, n, plan.row_of, topk_weights, base=base,
                                    expert_dtype=_torch_dtype(expert_dtype), out_dtype=_torch_dtype(out_dtype), out=out, split=split,
                                    workspace=workspace, kn=o.kn, kernel=kernel)
@@ -2362,8 +2509,14 @@ def _experts_mlp_class(o: _Orientation, name: str):
 
     class ExpertsMLP(torch.nn.Module):
         def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", backend: Optional[str] = None,
-                     decode_max_rows: Optional[int] = None, decode_grouped_kernel: str = "walk"):
+                     decode_max_rows: Optional[int] = None, decode_grouped_kernel: str = "walk", rotate: int = 0, in_exponents=None,
+                     down_rotate: int = 0, down_in_exponents=None, prologue: str = "staged"):
+            """rotate, in_exponents (count, k): for gate and up experts packed from hadamard.rotate_weight / awq.scale_weight, as
+            PackedMLP has them; down_rotate, down_in_exponents (count, hidden): the same for the down experts and h.  prologue
+            (PROLOGUES): on the decode route it goes to glu_grouped_skinny and linear_grouped; the wide route is staged."""
             super().__init__()
+            if prologue not in PROLOGUES:
+                raise MtqError(f"prologue must be one of {PROLOGUES}, got {prologue!r}")
             _check_act(act)
             if decode_max_rows is not None and (isinstance(decode_max_rows, bool) or not isinstance(decode_max_rows, int) or decode_max_rows <= 0):
                 raise MtqError(f"decode_max_rows must be None or a positive int, got {decode_max_rows!r}")
@@ -2403,6 +2556,16 @@ def _experts_mlp_class(o: _Orientation, name: str):
             self.decode_max_rows, self.decode_grouped_kernel, self._decode_kernel = decode_max_rows, decode_grouped_kernel, decode_kernel
             self.gate, self.up, self.down, self.act, self.out_dtype = gate, up, down, act, out_dtype
             self.count, self.in_features, self.hidden_features, self.out_features = gate.count, k, n, n_down
+            device = gate.arena.device if self.backend == "hip" else None
+            self.rotate, self.down_rotate, self.prologue = check_block(k, rotate) if rotate else 0, check_block(n, down_rotate) if down_rotate else 0, prologue
+            self._shifts, self._down_shifts = _group_shifts(in_exponents, gate.count, k, device), _group_shifts(down_in_exponents, gate.count, n, device)
+            self._pre = bool(self.rotate or self.down_rotate or self._shifts is not None or self._down_shifts is not None)
+            if self._pre and prologue == "fused":    # refused here, not at the first forward
+                if decode_max_rows is None:
+                    raise MtqError(f'{name}(prologue="fused") needs decode_max_rows: the fused prologue is the decode route\'s')
+                why = _no_fused_grouped(o, self.backend, decode_kernel)
+                if why:
+                    raise MtqError(f'{name}(prologue="fused"): {why}')
 
         def extra_repr(self) -> str:
             return f"count={self.count}, in_features={self.in_features}, hidden_features={self.hidden_features}, " \
@@ -2412,13 +2575,26 @@ def _experts_mlp_class(o: _Orientation, name: str):
         def forward(self, x, group_rows):
             if x.dim() != 2 or x.shape[1] != self.in_features:
                 raise MtqError(f"x must be (T, {self.in_features}), got {tuple(x.shape)}")
-            if self.decode_max_rows is not None and x.shape[0] <= self.decode_max_rows:
+            decode = self.decode_max_rows is not None and x.shape[0] <= self.decode_max_rows
+            if self._pre and decode and not o.kn:    # the decode route of (n, k) experts: `prologue` says where X″ and H″ are formed
+                h = glu_grouped_skinny(x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend,
+                                       workspace=self._decode_workspace, kernel=self._decode_kernel, rotate=self.rotate,
+                                       in_exponents=self._shifts, prologue=self.prologue)
+                return _as_torch(linear_grouped(_as_torch(h), group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend,
+                                                workspace=self._decode_workspace, kernel=self._decode_kernel, rotate=self.down_rotate,
+                                                in_exponents=self._down_shifts, prologue=self.prologue))
+            if self._pre and x.shape[0]:             # staged in front of both halves
+                x = _staged_x_grouped(x, group_rows, self.rotate, self._shifts, self.backend)
+                stage_h = lambda h: _staged_x_grouped(h, group_rows, self.down_rotate, self._down_shifts, self.backend)
+            else:
+                stage_h = lambda h: h
+            if decode:
                 h = globals()[o.glu_grouped_skinny](x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend,
                                                     workspace=self._decode_workspace, kernel=self._decode_kernel)
-                return _as_torch(globals()[o.grouped](h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend,
+                return _as_torch(globals()[o.grouped](stage_h(h), group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend,
                                                       workspace=self._decode_workspace, kernel=self._decode_kernel))
-            h = globals()[o.glu_grouped](x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend, kernel="fused",
-                                         workspace=self._workspace)
+            h = stage_h(globals()[o.glu_grouped](x, group_rows, self.gate, self.up, act=self.act, out_dtype="bfloat16", backend=self.backend,
+                                                 kernel="fused", workspace=self._workspace))
             return _as_torch(globals()[o.grouped_wide](h, group_rows, self.down, out_dtype=self.out_dtype, backend=self.backend,
                                                        workspace=self._workspace))
 
@@ -2460,7 +2636,10 @@ def _packed_moe_class():
 
         def __init__(self, gate_pts, up_pts, down_pts, act: str = "silu", out_dtype: str = "bfloat16", expert_dtype: str = "float32",
                      backend: Optional[str] = None, decode_max_rows: Optional[int] = None, max_tokens: int = 4096, stored: str = "rows",
-                     router=None, decode_route: str = "staged", decode_grouped_kernel: str = "walk"):
+                     router=None, decode_route: str = "staged", decode_grouped_kernel: str = "walk", rotate: int = 0, in_exponents=None,
+                     down_rotate: int = 0, down_in_exponents=None, prologue: str = "staged"):
+            """rotate, in_exponents, down_rotate, down_in_exponents, prologue: PackedExpertsMLP's, for rotated or AWQ-scaled experts;
+            the fused decode_route hands them to moe_glu and moe_down_combine, every other route to the experts."""
             super().__init__()
             if decode_route not in MOE_DECODE_ROUTES:
                 raise MtqError(f"decode_route must be one of {MOE_DECODE_ROUTES}, got {decode_route!r}")
@@ -2485,7 +2664,8 @@ def _packed_moe_class():
             experts_name = "PackedExpertsMLP" if stored == "rows" else "PackedExpertsMatmulMLP"
             experts_mlp = globals().get(experts_name) or __getattr__(experts_name)
             self.experts = experts_mlp(gate_pts, up_pts, down_pts, act=act, out_dtype=expert_dtype, backend=backend,
-                                       decode_max_rows=decode_max_rows, decode_grouped_kernel=decode_grouped_kernel)
+                                       decode_max_rows=decode_max_rows, decode_grouped_kernel=decode_grouped_kernel, rotate=rotate,
+                                       in_exponents=in_exponents, down_rotate=down_rotate, down_in_exponents=down_in_exponents, prologue=prologue)
             self.decode_grouped_kernel, self._decode_kernel = decode_grouped_kernel, decode_kernel
             self.backend, self.out_dtype, self.expert_dtype, self.stored = self.experts.backend, out_dtype, expert_dtype, stored
             self.count, self.in_features, self.out_features = self.experts.count, self.experts.in_features, self.experts.out_features
@@ -2539,10 +2719,12 @@ def _packed_moe_class():
             if self.decode_route == "fused" and plan.slots <= self.experts.decode_max_rows:
                 ex = self.experts
                 h = moe_glu(x2, plan, ex.gate, ex.up, act=ex.act, out_dtype="bfloat16", stored=self.stored, workspace=self._fused_workspace,
-                            backend=self.backend, kernel=self._decode_kernel)
-                y = moe_down_combine(h, topk_weights.reshape(T, K), plan, ex.down, base=None if base is None else base.reshape(T, self.out_features),
+                            backend=self.backend, kernel=self._decode_kernel, rotate=ex.rotate, in_exponents=ex._shifts, prologue=ex.prologue)
+                y = moe_down_combine(_as_torch(h), topk_weights.reshape(T, K), plan, ex.down,
+                                     base=None if base is None else base.reshape(T, self.out_features),
                                      expert_dtype=self.expert_dtype, out_dtype=self.out_dtype, stored=self.stored,
-                                     workspace=self._fused_workspace, backend=self.backend, kernel=self._decode_kernel)
+                                     workspace=self._fused_workspace, backend=self.backend, kernel=self._decode_kernel, rotate=ex.down_rotate,
+                                     in_exponents=ex._down_shifts, prologue=ex.prologue)
                 return _as_torch(y).reshape(lead + (self.out_features,))
             xs = moe_dispatch(x2, plan)
             if self.backend == "hip":
