@@ -1598,16 +1598,22 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v)
 // Launched with bounds (kThreads, 2): the second is HIP's minimum of waves per SIMD, not workgroups per CU; a workgroup here is one wave
 // per SIMD, so 2 is what lets two workgroups share a CU and caps the kernels at 256 VGPRs, which this function uses to the last:
 // re-read `make report` on any edit.
-template <bool GLU, bool XV, bool BF16OUT, bool WT = false>
+// PART (packed_wide_split_kernel): the block over the steps [s0, s1) of K alone, s0 < s1 <= steps, everything slice-relative - the
+// prologue loads steps s0 and s0 + 1, the image and register parity of step s is (s - s0) & 1, "the last step" is s1 - 1, and a one-step
+// slice takes the one-step path.  A step's K positions stay absolute, so the zero-fill past K falls to the slice that holds the last
+// step.  The epilogue stores the accumulators as they are, f32, to yv at pitch ldy: no bias, no rounding.  Without PART s0 and s1 are
+// not looked at and the range is [0, steps): the function it was.
+template <bool GLU, bool XV, bool BF16OUT, bool WT = false, bool PART = false>
 __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uint16_t *__restrict__ x, int64_t m0, int64_t M, int64_t K,
                                            int64_t ldx, const PackedStream &st, int64_t wtr, int64_t n0, int64_t N, int64_t tiles_h,
                                            int64_t tiles_w, const float *__restrict__ bias, const float *__restrict__ bias_up, int act,
-                                           void *__restrict__ yv, int64_t ldy, int wave)
+                                           void *__restrict__ yv, int64_t ldy, int wave, int64_t s0 = 0, int64_t s1 = 0)
 {
+    static_assert(!(PART && (GLU || BF16OUT)), "a partial block is a linear block with an f32 store");
     constexpr int BM = kWideBM, MT = BM / 64, XP = BM * 8 / kThreads, kImage = kWideImage;   // a wave's 32-row MFMA blocks; pieces of 8 bf16 of the X block per thread
     const int tid = threadIdx.x, lane = tid & 63;
     const int wm = wave >> 1, wn = wave & 1;
-    const int64_t steps = (K + kBK - 1) / kBK;
+    const int64_t first = PART ? s0 : 0, steps = PART ? s1 : (K + kBK - 1) / kBK;   // the range walked: [first, steps)
     const uint8_t *__restrict__ packed = st.packed;
     const int8_t *__restrict__ map = st.map;
     const uint32_t *__restrict__ off = st.off;
@@ -1791,14 +1797,14 @@ __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uin
         __syncthreads();
     };
 
-    fetch_tables(0);
-    load_step(Tag<0>(), 0);
-    load_step(Tag<1>(), steps > 1 ? 1 : 0);
-    stage_w(Tag<0>(), 0, lds, 0);
-    stage_w(Tag<0>(), 1, lds, 0);
+    fetch_tables(first);
+    load_step(Tag<0>(), first);
+    load_step(Tag<1>(), steps > first + 1 ? first + 1 : first);
+    stage_w(Tag<0>(), 0, lds, first);
+    stage_w(Tag<0>(), 1, lds, first);
     stage_x(Tag<0>(), 0, XP, lds);
     __syncthreads();
-    int64_t s = 0;
+    int64_t s = first;
     for (; s + 1 < steps; s += 2) {
         step(Tag<0>(), s);
         step(Tag<1>(), s + 1);
@@ -1826,13 +1832,13 @@ __device__ __forceinline__ void wide_block(uint16_t *__restrict__ lds, const uin
         for (int nt = 0; nt < 2; ++nt) {
             const int64_t n = n0 + 64 * wn + 32 * nt + (lane & 31);
             if (n >= N) continue;
-            const float b = bias ? bias[n] : 0.0f;
+            const float b = !PART && bias ? bias[n] : 0.0f;
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int64_t m = m0 + 32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    if (m < M) store_y<BF16OUT>(yv, m * ldy + n, acc[mt][nt][r] + b);
+                    if (m < M) store_y<BF16OUT>(yv, m * ldy + n, PART ? acc[mt][nt][r] : acc[mt][nt][r] + b);
                 }
         }
     }
@@ -1867,6 +1873,45 @@ __global__ __launch_bounds__(kThreads, 2) void packed_wide_kernel(
     const int64_t bm = blockIdx.x / nblocks, n0 = (blockIdx.x % nblocks) * kWideBN;
     wide_block<false, XV, BF16OUT, WT>(lds, x, bm * kWideBM, M, K, ldx, tensor_stream(packed, packed_bytes, map, offsets), (n0 >> 5) + wave, n0,
                                        N, tiles_h, tiles_w, bias, nullptr, 0, yv, ldy, wave);
+}
+
+// ---- wide split (the mid range of m): packed_wide_kernel's block over ONE K slice, the slices summed by skinny_reduce_kernel.
+//
+// At m <= 256 and n = 4096 the wide launch is 32 - 64 workgroups on 256 CUs, each paying all of K's steps in a row.  Here the 1-D grid is
+// blocks × split workgroups, workgroup = (slice · row blocks + row block) · column blocks + column block: the column block fastest, then
+// the row block, the slice slowest, so the workgroups that run together read one slice's columns of X and share them in L2.  Slice s owns
+// the whole steps [s steps / split, (s + 1) steps / split), cut as skinny_run's slices are; the host passes split <= steps, so no slice is
+// empty, and every 16-wide MFMA block and every BFP group lies inside one slice.  blockIdx is uniform: the slice bounds are scalar.
+// The block stores its accumulators as f32 to ws[s][m][n] (row pitch N, rows < M and columns < N only) with plain vector stores: no
+// atomics, no counters, nothing waits on another workgroup.  Per output the partial p_s is one accumulator from +0 over the slice's
+// ascending 16-wide blocks, and Y = ((p0 + p1) + ... + p_{split-1}) + b is skinny_reduce_kernel's, the next launch on the stream.
+template <bool XV, bool WT>
+__global__ __launch_bounds__(kThreads, 2) void packed_wide_split_kernel(
+    const uint16_t *__restrict__ x, int64_t M, int64_t K, int64_t ldx, const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+    const int8_t *__restrict__ map, const uint32_t *__restrict__ offsets, int64_t N, int64_t tiles_h, int64_t tiles_w, int split,
+    float *__restrict__ ws)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * kWideImage];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nblocks = (N + kWideBN - 1) / kWideBN, mblocks = (M + kWideBM - 1) / kWideBM;
+    const int64_t n0 = (blockIdx.x % nblocks) * kWideBN, rest = blockIdx.x / nblocks;
+    const int64_t bm = rest % mblocks, s = rest / mblocks;
+    const int64_t steps = (K + kBK - 1) / kBK;
+    wide_block<false, XV, false, WT, true>(lds, x, bm * kWideBM, M, K, ldx, tensor_stream(packed, packed_bytes, map, offsets), (n0 >> 5) + wave, n0,
+                                           N, tiles_h, tiles_w, nullptr, nullptr, 0, ws + s * M * N, N, wave, s * steps / split,
+                                           (s + 1) * steps / split);
+}
+
+// The library's split of the wide block for (m, n, k): a pure function of the shape.  The most slices with which blocks × split stays
+// within the chip's workgroup slots (256 CUs × 2: one workgroup over that and a second round starts, which measured slower than split 1
+// at 448 blocks), no slice below kWideMinSteps steps, and 1 from 257 blocks on, where the blocks alone fill more than half the slots
+// (DESIGN.md §A.6zk has the measurement behind both).
+constexpr int64_t kWideSlots = 512, kWideMinSteps = 4;
+
+int wide_split(int64_t blocks, int64_t steps)
+{
+    const int64_t by_slots = kWideSlots / blocks, by_run = steps / kWideMinSteps;
+    return (int)std::max<int64_t>(1, std::min(by_slots, by_run));
 }
 
 // ---- grouped wide linear: packed_wide_kernel's block for every expert of an arena over the expert's own rows, one launch.
@@ -3143,6 +3188,80 @@ extern "C" int mtq_packed_matmul_wide(const void *x, int64_t m, int64_t k, int64
                                       const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy, void *stream)
 {
     return packed_wide(true, "mtq_packed_matmul_wide", x, m, k, ldx, packed, packed_bytes, map, offsets, n, bias, y, out_dtype, ldy, stream);
+}
+
+// 2s. wide split (include/mtq_wide_split.h)
+static int64_t wide_blocks(int64_t m, int64_t n) { return ((m + kWideBM - 1) / kWideBM) * ((n + kWideBN - 1) / kWideBN); }
+
+// The effective split of (m, n, k) under `split` (0: wide_split's choice), at most the steps of K; -1 with the message set
+extern "C" int mtq_packed_wide_split(int64_t m, int64_t n, int64_t k, int split)
+{
+    int64_t th, tw;
+    if (m <= 0) return fail(MTQ_ERR_INVALID, "m must be positive (empty operands are handled by the caller)"), -1;
+    if (tile_grid(n, k, &th, &tw)) return -1;
+    if (m > (int64_t)1 << 40) return fail(MTQ_ERR_INVALID, "matrix too large"), -1;
+    if (split < 0) return fail(MTQ_ERR_INVALID, "split must not be negative (0: the library's choice)"), -1;
+    const int64_t steps = (k + kBK - 1) / kBK;
+    return (int)std::min<int64_t>(split == 0 ? wide_split(wide_blocks(m, n), steps) : split, steps);
+}
+
+extern "C" size_t mtq_packed_linear_wide_split_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
+{
+    const int eff = mtq_packed_wide_split(m, n, k, split);
+    return eff < 0 ? (size_t)-1 : skinny_workspace(m, n, eff);
+}
+
+extern "C" size_t mtq_packed_matmul_wide_split_workspace_bytes(int64_t m, int64_t n, int64_t k, int split)
+{
+    return mtq_packed_linear_wide_split_workspace_bytes(m, n, k, split);
+}
+
+static int packed_wide_split(bool kn, const char *name, const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes,
+                             const int8_t *map, const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype, int64_t ldy,
+                             int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    TileGrid g;
+    if (int rc = linear_args(x, m, k, ldx, packed, packed_bytes, map, offsets, n, y, out_dtype, ldy, g)) return rc;
+    g.eff = mtq_packed_wide_split(m, n, k, split);
+    if (g.eff < 0) return MTQ_ERR_INVALID;
+    const int64_t blocks = wide_blocks(m, n) * g.eff;                        // the grid first: under its limit the workspace size cannot wrap
+    if (int rc = grid_args({blocks}, true)) return rc;
+    if (int rc = workspace_args(workspace, workspace_bytes, skinny_workspace(m, n, g.eff), kWsSplit, "split")) return rc;
+    if (int rc = require_device()) return rc;
+    const bool x_vec = x_vec_wide(x, ldx, k);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t *xp = static_cast<const uint16_t *>(x);
+    const uint8_t *pp = static_cast<const uint8_t *>(packed);
+    if (g.eff == 1) {                                // the wide kernel itself: its bits, no workspace touched
+        launch_out(out_dtype, MTQ_WIDE_PAIR(packed_wide_kernel, x_vec, kn), dim3((unsigned)blocks), dim3(kThreads), st, xp, m, k, ldx, pp,
+                   (uint64_t)packed_bytes, map, offsets, n, g.sh(kn), g.sw(kn), bias, y, ldy);
+        return check_launch(name);
+    }
+    float *ws = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(kn ? (x_vec ? packed_wide_split_kernel<true, true> : packed_wide_split_kernel<false, true>)
+                          : (x_vec ? packed_wide_split_kernel<true, false> : packed_wide_split_kernel<false, false>),
+                       dim3((unsigned)blocks), dim3(kThreads), 0, st, xp, m, k, ldx, pp, (uint64_t)packed_bytes, map, offsets, n, g.sh(kn), g.sw(kn),
+                       g.eff, ws);
+    if (int rc = check_launch(name)) return rc;
+    launch_out(out_dtype, skinny_reduce_kernel<true>, skinny_reduce_kernel<false>, dim3((unsigned)((m * n + 255) / 256)), dim3(256), st, ws, m * n,
+               n, g.eff, bias, y, ldy);
+    return check_launch(name);
+}
+
+extern "C" int mtq_packed_linear_wide_split(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes,
+                                            const int8_t *map, const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype,
+                                            int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return packed_wide_split(false, "mtq_packed_linear_wide_split", x, m, k, ldx, packed, packed_bytes, map, offsets, n, bias, y, out_dtype, ldy,
+                             split, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mtq_packed_matmul_wide_split(const void *x, int64_t m, int64_t k, int64_t ldx, const void *packed, size_t packed_bytes,
+                                            const int8_t *map, const uint32_t *offsets, int64_t n, const float *bias, void *y, int out_dtype,
+                                            int64_t ldy, int split, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return packed_wide_split(true, "mtq_packed_matmul_wide_split", x, m, k, ldx, packed, packed_bytes, map, offsets, n, bias, y, out_dtype, ldy,
+                             split, workspace, workspace_bytes, stream);
 }
 
 // 3. skinny

@@ -216,7 +216,7 @@ PACKED_PRE_SIGNATURES = {
     "mtq_packed_glu_skinny_pre": ("i", "pllllppzpppzpplppipilipzp", True),
 }
 PACKED_PRE_EXPORTS = tuple(PACKED_PRE_SIGNATURES)
-# include/mtq_grouped_pre.h, which mtq.h includes last: the grouped skinny products of the MoE decode route with that prologue inside
+# include/mtq_grouped_pre.h, which mtq.h includes after it: the grouped skinny products of the MoE decode route with that prologue inside
 GROUPED_PRE_SIGNATURES = {
     "mtq_packed_grouped_pre_split": ("i", "llllli", True),
     "mtq_packed_glu_skinny_grouped_pre_workspace_bytes": ("z", "llllli", True),
@@ -225,6 +225,15 @@ GROUPED_PRE_SIGNATURES = {
     "mtq_packed_linear_skinny_grouped_pre": ("i", "pllplppzpppllipplpilllpilipzp", True),
 }
 GROUPED_PRE_EXPORTS = tuple(GROUPED_PRE_SIGNATURES)
+# include/mtq_wide_split.h, which mtq.h includes last: the wide-block products with a split over K, for the mid range of m
+WIDE_SPLIT_SIGNATURES = {
+    "mtq_packed_wide_split": ("i", "llli", True),
+    "mtq_packed_linear_wide_split_workspace_bytes": ("z", "llli", True),
+    "mtq_packed_matmul_wide_split_workspace_bytes": ("z", "llli", True),
+    "mtq_packed_linear_wide_split": ("i", "plllpzpplppilipzp", True),
+    "mtq_packed_matmul_wide_split": ("i", "plllpzpplppilipzp", True),
+}
+WIDE_SPLIT_EXPORTS = tuple(WIDE_SPLIT_SIGNATURES)
 _CTYPE = {"p": ctypes.c_void_p, "l": ctypes.c_int64, "u": ctypes.c_uint32, "i": ctypes.c_int, "d": ctypes.c_double, "z": ctypes.c_size_t,
           "q": ctypes.c_uint64, "v": None, "s": ctypes.c_char_p}
 
@@ -283,7 +292,8 @@ def _bind(L) -> None:
     if found < MTQ_VERSION:
         raise MtqError(f"{LIB_PATH} is version {found}, older than this package (it needs {MTQ_VERSION}): {_REBUILD}")
     for name, (result, params, optional) in (*SIGNATURES.items(), *MOE_DECODE_SIGNATURES.items(), *GLU_CHUNKED_SIGNATURES.items(),
-                                             *PACKED_PRE_SIGNATURES.items(), *GROUPED_PRE_SIGNATURES.items()):
+                                             *PACKED_PRE_SIGNATURES.items(), *GROUPED_PRE_SIGNATURES.items(),
+                                             *WIDE_SPLIT_SIGNATURES.items()):
         fn = getattr(L, name, None)
         if fn is None:
             if optional:
@@ -1471,17 +1481,18 @@ def _packed_pre_args(x, k: int, block, in_exponents) -> tuple:
 
 
 def _packed_product_call(name, kn, empty, x, data, tables, n, bias, out_dtype, out, stream, size=None, split=0, workspace=None, size_first=False,
-                         pre=None):
+                         pre=None, any_m=False):
     """The checks and the call the single-tensor product entries share.  empty: which of "m" and "n" being 0 ends here with the empty
-    `out` ("" : the library's refusal of empty operands reaches the caller).  size: a skinny entry's own size function, which makes
-    the call one with m <= 32, a split and a workspace; size_first: it is asked before `out` is looked at."""
+    `out` ("" : the library's refusal of empty operands reaches the caller).  size: a split entry's own size function, which makes
+    the call one with m <= 32 (any_m: the wide split entries, any m), a split and a workspace; size_first: it is asked before `out` is
+    looked at."""
     torch = _torch()
     out_dtype = out_dtype or torch.float32
     code = _packed_out_code(out_dtype)
     x_code, _count, _stride, m, k, ldx = _matrix(x, (2,))
     if x_code != DTYPE_BF16:
         raise MtqError("x must be a bfloat16 tensor")
-    if size is not None and m > PACKED_SKINNY_MAX_M:
+    if size is not None and not any_m and m > PACKED_SKINNY_MAX_M:
         raise MtqError(f"the skinny kernel takes m <= {PACKED_SKINNY_MAX_M}, got m = {m}")
     if (tiles_hw(k, n) if kn else tiles_hw(n, k)) != (tables.tiles_h, tables.tiles_w):
         raise _grid_error(tables, n, k, kn)
@@ -1627,6 +1638,52 @@ def packed_matmul_wide(x, data, tables: PackedTables, n: int, bias=None, out_dty
 def has_packed_matmul_wide() -> bool:
     """Whether this build of the library has mtq_packed_matmul_wide (an optional symbol: an older build of the same version lacks it)."""
     return _has(("mtq_packed_matmul_wide",))
+
+
+def packed_wide_split_available() -> bool:
+    """Whether this build of the library has the wide-block entries with a split over K (mtq_packed_linear_wide_split,
+    mtq_packed_matmul_wide_split, their size functions and the split rule; optional symbols)."""
+    return _has(WIDE_SPLIT_EXPORTS)
+
+
+def packed_wide_split(m: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_wide_split (a host function: no GPU): the effective split of the wide split entries for (m, n, k, split) - at most
+    ceil(k / 64); split 0 is the library's choice.  Arguments the entries refuse raise MtqError."""
+    eff = int(_entry("mtq_packed_wide_split")(int(m), int(n), int(k), int(split)))
+    if eff < 0:
+        raise MtqError(f"libmtq_hip error -1: {lib().mtq_last_error().decode()}")
+    return eff
+
+
+def packed_linear_wide_split_workspace(m: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_linear_wide_split_workspace_bytes (a host function: no GPU): the bytes of f32 partials the wide block needs for
+    (m, n, k, split); 0 when the effective split is 1."""
+    return _workspace_size("mtq_packed_linear_wide_split_workspace_bytes", m, n, k, split)
+
+
+def packed_matmul_wide_split_workspace(m: int, n: int, k: int, split: int = 0) -> int:
+    """mtq_packed_matmul_wide_split_workspace_bytes: packed_linear_wide_split_workspace for a (k, n) matrix - n outputs, k contraction."""
+    return _workspace_size("mtq_packed_matmul_wide_split_workspace_bytes", m, n, k, split)
+
+
+def packed_linear_wide_split(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, split: int = 0, workspace=None,
+                             stream="current"):
+    """mtq_packed_linear_wide_split on the current stream: packed_linear_wide with a split over K (split 0: the library's choice) - the
+    wide block over one K slice per workgroup, f32 partials, the slices summed in ascending order with the bias last.  workspace: a uint8
+    device tensor of at least packed_linear_wide_split_workspace(m, n, k, split) bytes, 16-byte aligned; allocated here when none is
+    given.  At an effective split of 1, packed_linear_wide's bits; the same inputs and the same split give the same bits.  m = 0 or
+    n = 0 gives the empty (m, n) tensor without a call."""
+    return _packed_product_call("mtq_packed_linear_wide_split", False, "mn", x, data, tables, n, bias, out_dtype, out, stream,
+                                packed_linear_wide_split_workspace, split, workspace, any_m=True)
+
+
+def packed_matmul_wide_split(x, data, tables: PackedTables, n: int, bias=None, out_dtype=None, out=None, split: int = 0, workspace=None,
+                             stream="current"):
+    """mtq_packed_matmul_wide_split on the current stream: packed_matmul_wide with a split over K, as packed_linear_wide_split.  Bit for
+    bit that entry at the same split on the all-bf16 packing of the unpacked matrix's transpose.  m = 0 gives the empty (0, n) tensor
+    without a call."""
+    return _packed_product_call("mtq_packed_matmul_wide_split", True, "m", x, data, tables, n, bias, out_dtype, out, stream,
+                                packed_matmul_wide_split_workspace, split, workspace, any_m=True)
 
 
 PACKED_SKINNY_MAX_M = 32   # include/mtq.h MTQ_PACKED_SKINNY_MAX_M

@@ -803,18 +803,29 @@ def _product(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dtype, b
     return _round_out(y, out_dtype)
 
 
-def _product_wide(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dtype, backend):
-    """linear_wide and matmul_wide."""
+def _need_wide_split(hb, what: str) -> None:
+    if not hb.packed_wide_split_available():
+        raise MtqError(f"{what} needs {' and '.join(hb.WIDE_SPLIT_EXPORTS)}, {_LACKS}")
+
+
+def _product_wide(o: _Orientation, what: str, x, pt: PackedTensor, bias, out_dtype, backend, split=1, workspace=None):
+    """linear_wide and matmul_wide.  split 1: the wide entry, as before there was a choice; any other: the wide split entry."""
     _check_rank2(o, pt, what)
     backend = backend or ("hip" if pt.on_device else "emulation")
     _check_out_dtype(out_dtype)
+    if isinstance(split, bool) or not isinstance(split, (int, np.integer)) or split < 0:
+        raise MtqError(f"split must be a non-negative integer (0: the library's choice), got {split!r}")
     if backend != "hip":
         return globals()[o.product](x, pt, bias=bias, out_dtype=out_dtype, backend=backend)
     n, k = o.n_k(pt)
     if x.dim() != 2 or x.shape[1] != k:
         raise MtqError(f"x must be (m, {k}), got {tuple(x.shape)}")
     _needs(o.need_wide, hb, what)
-    return getattr(hb, o.hb_wide)(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=_torch_dtype(out_dtype))
+    if split == 1:
+        return getattr(hb, o.hb_wide)(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=_torch_dtype(out_dtype))
+    _need_wide_split(hb, f"{what}(split={split})")
+    return getattr(hb, o.hb_wide + "_split")(x, _device_data(pt), pt.tables(), n, bias=bias, out_dtype=_torch_dtype(out_dtype), split=int(split),
+                                             workspace=workspace)
 
 
 def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block", split: int = 0,
@@ -839,12 +850,18 @@ def linear(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     return _product(_NK, "linear", x, pt, bias, out_dtype, backend, kernel, split, workspace, rotate, in_exponents, prologue)
 
 
-def linear_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
+def linear_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 1, workspace=None):
     """linear(kernel="block")'s product and, on hip, its bits, through mtq_packed_linear_wide: the wide-block kernel for m above the
     decode range (prefill), 128 x 128 outputs to a workgroup, whose waves decode whole tiles of the weight.  Correct for any m
     (m = 0 gives (0, n)); faster than the block kernel from m = 64 on, the smallest m measured.  A library without the symbol raises MtqError: there is no
-    fall-back to the block kernel here (linear(kernel="auto") is the call that chooses).  emulation: linear's float64 product."""
-    return _product_wide(_NK, "linear", x, pt, bias, out_dtype, backend)
+    fall-back to the block kernel here (linear(kernel="auto") is the call that chooses).  emulation: linear's float64 product.
+
+    split: 1 (the default) is that call.  Any other goes through mtq_packed_linear_wide_split, the wide block with K cut into `split`
+    slices of whole 64-wide steps (0 = the library's choice), for the mid range of m where 128 x 128 blocks alone leave most of the
+    chip idle: f32 partials in `workspace` (an optional uint8 device tensor of
+    hip_backend.packed_linear_wide_split_workspace bytes), summed in ascending order, the bias last.  Bit-stable at a given split;
+    different splits may differ in the last bits.  A library without the symbols raises MtqError; the emulation ignores `split`."""
+    return _product_wide(_NK, "linear", x, pt, bias, out_dtype, backend, split, workspace)
 
 
 # ----------------------------------------------------------------------------- the transposed layout and (k, n) weights
@@ -933,13 +950,17 @@ def matmul(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: 
     return _product(_KN, "matmul", x, pt, bias, out_dtype, backend, kernel, split, workspace)
 
 
-def matmul_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None):
+def matmul_wide(x, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, split: int = 1, workspace=None):
     """matmul(kernel="block")'s product and, on hip, its bits, through mtq_packed_matmul_wide: the wide-block kernel for m above the
     decode range (prefill), 128 x 128 outputs to a workgroup, whose waves decode whole tiles of the (k, n) stream.  Correct for any m
     (m = 0 gives (0, n)); faster than the block kernel from m = 64 on, the smallest m measured.  A library without
     the symbol raises MtqError: there is no fall-back to the block kernel here (matmul(kernel="auto") is the call that chooses).
-    emulation: matmul's float64 product."""
-    return _product_wide(_KN, "matmul_wide", x, pt, bias, out_dtype, backend)
+    emulation: matmul's float64 product.
+
+    split, workspace: as linear_wide's, through mtq_packed_matmul_wide_split (the workspace of
+    hip_backend.packed_matmul_wide_split_workspace bytes): bit for bit linear_wide at the same split on the all-bf16 packing of
+    unpack(pt)ᵀ."""
+    return _product_wide(_KN, "matmul_wide", x, pt, bias, out_dtype, backend, split, workspace)
 
 
 # ----------------------------------------------------------------------------- batches
@@ -2765,9 +2786,12 @@ def _product_class(o: _Orientation, name: str):
     """PackedLinear and PackedMatmul."""
     import torch
 
-    def init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents=None, prologue="staged"):
+    def init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents=None, prologue="staged", wide_split=1):
         torch.nn.Module.__init__(self)
         _check_rank2(o, pt, name)
+        if isinstance(wide_split, bool) or not isinstance(wide_split, (int, np.integer)) or wide_split < 0:
+            raise MtqError(f"wide_split must be a non-negative integer (0: the library's choice), got {wide_split!r}")
+        self.wide_split, self._wide_workspace = int(wide_split), None
         self.rotate = check_block(o.n_k(pt)[1], rotate) if rotate else 0
         if prologue not in PROLOGUES:
             raise MtqError(f"prologue must be one of {PROLOGUES}, got {prologue!r}")
@@ -2785,6 +2809,9 @@ def _product_class(o: _Orientation, name: str):
             bias = torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
         if self.backend == "hip":
             _needs(o.module_needs, hb, name)
+            if self.wide_split != 1:
+                _needs(o.need_wide, hb, f"{name}(wide_split={wide_split})")
+                _need_wide_split(hb, f"{name}(wide_split={wide_split})")
             if kernel == "skinny":
                 _needs(o.need_skinny, hb, f'{name}(kernel="skinny")')
             data = _device_data(pt)
@@ -2806,17 +2833,30 @@ def _product_class(o: _Orientation, name: str):
     class Product(torch.nn.Module):
         if o.kn:
             def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", backend: Optional[str] = None, kernel: str = "block",
-                         rotate: int = 0, in_exponents=None):
-                init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents)
+                         rotate: int = 0, in_exponents=None, wide_split: int = 1):
+                init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents, wide_split=wide_split)
         else:
             def __init__(self, pt: PackedTensor, bias=None, out_dtype: str = "float32", kernel: str = "auto", backend: Optional[str] = None,
-                         rotate: int = 0, in_exponents=None, prologue: str = "staged"):
-                init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents, prologue)
+                         rotate: int = 0, in_exponents=None, prologue: str = "staged", wide_split: int = 1):
+                init(self, pt, bias, out_dtype, kernel, backend, rotate, in_exponents, prologue, wide_split)
 
         def extra_repr(self) -> str:
             return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, kernel={self.kernel!r}, " \
                    f"backend={self.backend!r}, packed_bytes={self.packed.nbytes}" \
-                   + (f", rotate={self.rotate}" if self.rotate else "") + (", in_exponents=True" if self._shifts is not None else "")
+                   + (f", rotate={self.rotate}" if self.rotate else "") + (", in_exponents=True" if self._shifts is not None else "") \
+                   + (f", wide_split={self.wide_split}" if self.wide_split != 1 else "")
+
+        def _wide_split_forward(self, x2):
+            """m above the skinny range with wide_split != 1: *_wide(split=wide_split) on the staged X, the partials' workspace kept and
+            only ever replaced by a larger one."""
+            if self.backend == "hip":
+                n, k = self.out_features, self.in_features
+                need = getattr(hb, o.hb_wide + "_split_workspace")(int(x2.shape[0]), n, k, self.wide_split)
+                if need and (self._wide_workspace is None or self._wide_workspace.numel() < need):
+                    self._wide_workspace = torch.empty((need,), dtype=torch.uint8, device=x2.device)
+            return globals()[o.product + "_wide"](_staged_x(x2, self.rotate, self._shifts, self.backend), self.packed, bias=self.bias,
+                                                  out_dtype=self.out_dtype, backend=self.backend, split=self.wide_split,
+                                                  workspace=self._wide_workspace)
 
         @torch.no_grad()
         def forward(self, x):
@@ -2826,7 +2866,9 @@ def _product_class(o: _Orientation, name: str):
             x2 = x.reshape(-1, self.in_features)
             if x2.shape[0] == 0:
                 return torch.zeros(lead + (self.out_features,), dtype=_torch_dtype(self.out_dtype), device=x.device)
-            if o.kn or self.prologue == "staged":    # hadamard, then torch.ldexp, in front of the product
+            if self.wide_split != 1 and x2.shape[0] > SKINNY_MAX_M and self.prologue != "fused":
+                y = self._wide_split_forward(x2)
+            elif o.kn or self.prologue == "staged":  # hadamard, then torch.ldexp, in front of the product
                 y = globals()[o.product](_staged_x(x2, self.rotate, self._shifts, self.backend), self.packed, bias=self.bias,
                                          out_dtype=self.out_dtype, backend=self.backend, kernel=self.kernel, workspace=self._workspace)
             else:

@@ -15,9 +15,16 @@
                   side of the same alternation; `wide/block-min` is the wide median over the block kernel's MINIMUM of the same run,
                   the gate of DESIGN.md §A.6k; the line also says whether the result's bits are the block kernel's.
 
+  wide splits   : --wide-splits 0,2,4,8,16 (with --wide) adds the wide block with a split over K (mtq_packed_linear_wide_split, the C entry
+                  with a preallocated workspace) once per value, 0 = the library's choice: `split/wide` is the side's
+                  median over the split-1 wide median of the same run, `spread` that wide side's median over its minimum; the line
+                  says the effective split and the largest difference to the wide result relative to the result's largest value.
+
   python tools/packed_linear_bench.py [--rounds 5] [--window-ms 30] [--out profiles/packed_linear.txt] [--json out.json]
   python tools/packed_linear_bench.py --linear-only --ms 1,4,16,32 --out profiles/packed_linear_skinny.txt
   python tools/packed_linear_bench.py --linear-only --wide --ms 64,128,256,512,1024,2048,4096 --out profiles/packed_linear_wide.txt
+  python tools/packed_linear_bench.py --linear-only --wide --wide-splits 0,2,4,8,16 --ms 33,48,64,128,256,512,1024 \
+      --out profiles/packed_linear_wide_split.txt
   (the record kept there also has rows=256 lines: a 256 x 128 instantiation that was measured beside the kernel, lost and was removed)
 """
 from __future__ import annotations
@@ -75,6 +82,7 @@ def main() -> int:
     p.add_argument("--ms", default="1,16,256,4096")
     p.add_argument("--splits", default="0", help="skinny side: the split values to time, comma separated (0: the library's choice)")
     p.add_argument("--wide", action="store_true", help="time the wide-block kernel beside the block kernel and torch.matmul")
+    p.add_argument("--wide-splits", default="", help="with --wide: the wide split entry at these splits, comma separated (0: the library's choice)")
     p.add_argument("--linear-only", action="store_true", help="skip the pack / unpack timings")
     p.add_argument("--out", default=None)
     p.add_argument("--json", default=None)
@@ -164,6 +172,18 @@ def main() -> int:
                         hb.check(wentry(*wcalls[i % copies_p]))
 
                     wide.append({"fn": f_wide, "iters": calibrate(f_wide, args.window_ms), "ts": []})
+                    sentry_w = hb._entry("mtq_packed_linear_wide_split") if args.wide_splits else None
+                    for split in (int(v) for v in args.wide_splits.split(",") if v):
+                        need = hb.packed_linear_wide_split_workspace(m, n, k, split)
+                        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device="cuda")
+                        hb.packed_linear_wide_split(x, data, tables, n, out_dtype=torch.bfloat16, out=yw, split=split, workspace=ws)   # the checks, once
+                        pcalls = [c[:13] + (split, ws.data_ptr(), need, stream) for c in wcalls]
+
+                        def f_split(i, pcalls=pcalls):
+                            hb.check(sentry_w(*pcalls[i % copies_p]))
+
+                        wide.append({"split": split, "eff": hb.packed_wide_split(m, n, k, split), "workspace_bytes": need, "ws": ws, "fn": f_split,
+                                     "iters": calibrate(f_split, args.window_ms), "ts": []})
 
                 ip, im = calibrate(f_packed, args.window_ms), calibrate(f_matmul, args.window_ms)
                 tp, tm = [], []
@@ -186,7 +206,21 @@ def main() -> int:
                     f"matmul {mm * 1e3:9.1f} us (min {min(tm) * 1e3:9.1f}, {2 * n * k / mm / 1e6:7.1f} GB/s of bf16 W)  packed/matmul {mp / mm:6.2f}  "
                     f"max rel diff {err:.2e}")
                 flop = 2.0 * m * n * k
-                for side in wide:
+                for side in wide[1:]:                # the split sides, against the wide side of the same run
+                    wide[0]["fn"](0)
+                    ref = yw.float()
+                    side["fn"](0)
+                    diff = float((yw.float() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
+                    ms_, mn_, mw = statistics.median(side["ts"]), min(side["ts"]), statistics.median(wide[0]["ts"])
+                    rows.append({"what": "packed_linear_wide_split", "n": n, "k": k, "m": m, "map": name, "counts": counts, "split": side["split"],
+                                 "split_effective": side["eff"], "workspace_bytes": side["workspace_bytes"], "split_ms_median": ms_, "split_ms_min": mn_,
+                                 "wide_ms_median": mw, "wide_ms_min": min(wide[0]["ts"]), "block_ms_min": min(tp), "matmul_ms_median": mm,
+                                 "split_over_wide": ms_ / mw, "wide_spread": mw / min(wide[0]["ts"]), "split_over_block_min": ms_ / min(tp),
+                                 "split_over_matmul": ms_ / mm, "max_rel_diff_to_wide": diff})
+                    say(f"wide split   {n}x{k} m={m:5d} map={name:6s} split={side['split']:3d} (eff {side['eff']:3d}) {ms_ * 1e3:9.1f} us (min {mn_ * 1e3:9.1f})  "
+                        f"split/wide {ms_ / mw:6.3f} (spread {mw / min(wide[0]['ts']):5.3f})  split/block-min {ms_ / min(tp):6.3f}  "
+                        f"split/matmul {ms_ / mm:6.2f}  max rel diff to wide {diff:.2e}")
+                for side in wide[:1]:
                     yw.zero_()
                     side["fn"](0)
                     same = bool(torch.equal(yw.view(torch.int16), yp.view(torch.int16)))
