@@ -1403,4 +1403,5 @@ int mtq_debug_packed_decode(int fmt, uint32_t *got, uint32_t *want, void *stream
 #include "mtq_packed_pre.h"
 #include "mtq_grouped_pre.h"
 #include "mtq_wide_split.h"
+#include "mtq_packed_gather.h"
 #endif /* MTQ_H */

@@ -234,6 +234,11 @@ WIDE_SPLIT_SIGNATURES = {
     "mtq_packed_matmul_wide_split": ("i", "plllpzpplppilipzp", True),
 }
 WIDE_SPLIT_EXPORTS = tuple(WIDE_SPLIT_SIGNATURES)
+# include/mtq_packed_gather.h, which mtq.h includes last: the input embedding, token rows gathered straight from a packed table
+PACKED_GATHER_SIGNATURES = {
+    "mtq_packed_embedding": ("i", "pillpzpplliidpilp", True),
+}
+PACKED_GATHER_EXPORTS = tuple(PACKED_GATHER_SIGNATURES)
 _CTYPE = {"p": ctypes.c_void_p, "l": ctypes.c_int64, "u": ctypes.c_uint32, "i": ctypes.c_int, "d": ctypes.c_double, "z": ctypes.c_size_t,
           "q": ctypes.c_uint64, "v": None, "s": ctypes.c_char_p}
 
@@ -293,7 +298,7 @@ def _bind(L) -> None:
         raise MtqError(f"{LIB_PATH} is version {found}, older than this package (it needs {MTQ_VERSION}): {_REBUILD}")
     for name, (result, params, optional) in (*SIGNATURES.items(), *MOE_DECODE_SIGNATURES.items(), *GLU_CHUNKED_SIGNATURES.items(),
                                              *PACKED_PRE_SIGNATURES.items(), *GROUPED_PRE_SIGNATURES.items(),
-                                             *WIDE_SPLIT_SIGNATURES.items()):
+                                             *WIDE_SPLIT_SIGNATURES.items(), *PACKED_GATHER_SIGNATURES.items()):
         fn = getattr(L, name, None)
         if fn is None:
             if optional:
@@ -1684,6 +1689,46 @@ def packed_matmul_wide_split(x, data, tables: PackedTables, n: int, bias=None, o
     without a call."""
     return _packed_product_call("mtq_packed_matmul_wide_split", True, "m", x, data, tables, n, bias, out_dtype, out, stream,
                                 packed_matmul_wide_split_workspace, split, workspace, any_m=True)
+
+
+GATHER_ROWS, GATHER_TRANSPOSE = 0, 1   # include/mtq_packed_gather.h MTQ_GATHER_ROWS, MTQ_GATHER_TRANSPOSE
+
+
+def packed_gather_available() -> bool:
+    """Whether this build of the library has mtq_packed_embedding (an optional symbol: an older build of the same version lacks it)."""
+    return _has(PACKED_GATHER_EXPORTS)
+
+
+def packed_embedding(ids, data, tables: PackedTables, rows: int, cols: int, stored: int = GATHER_ROWS, scale=None, id_first: int = 0,
+                     out_dtype=None, out=None, stream="current"):
+    """mtq_packed_embedding on the current stream: the rows ids - id_first of the packed (vocab, hidden) table (stored GATHER_ROWS;
+    rows x cols = vocab x hidden), or the columns of the packed (hidden, vocab) transpose (GATHER_TRANSPOSE; rows x cols =
+    hidden x vocab), → a (tokens, hidden) float32 or bfloat16 device tensor, tokens = ids.numel().  ids: an int32 or int64 device tensor
+    of any shape (a strided view is made contiguous); an id outside the table gives a row of +0.  scale: None, or a number the values are
+    multiplied by in float32.  out: a (tokens, hidden) device tensor with contiguous rows at any pitch.  No ids, no call."""
+    torch = _torch()
+    out_dtype = out_dtype or torch.bfloat16
+    code = _packed_out_code(out_dtype)
+    if ids.dtype not in (torch.int32, torch.int64):
+        raise MtqError(f"ids must be int32 or int64, got {ids.dtype}")
+    if not ids.is_cuda:
+        raise MtqError("expected a device tensor (the hip backend has no CPU fallback)")
+    if stored not in (GATHER_ROWS, GATHER_TRANSPOSE):
+        raise MtqError(f"stored must be GATHER_ROWS or GATHER_TRANSPOSE, got {stored!r}")
+    rows, cols = int(rows), int(cols)
+    if tiles_hw(rows, cols) != (tables.tiles_h, tables.tiles_w):
+        raise MtqError(f"the map is {tables.tiles_h}x{tables.tiles_w} tiles, a {rows}x{cols} stream has {'x'.join(map(str, tiles_hw(rows, cols)))}")
+    ptr = _packed_stream(data, tables)
+    fn = _entry("mtq_packed_embedding")
+    flat = ids.reshape(-1).contiguous()
+    tokens, hidden = int(flat.numel()), (rows if stored == GATHER_TRANSPOSE else cols)
+    out, ldy = _packed_out(out, tokens, hidden, out_dtype, ids.device)
+    if tokens == 0:
+        return out
+    check(fn(flat.data_ptr(), IDS_I64 if flat.dtype == torch.int64 else IDS_I32, tokens, int(id_first), ptr, tables.nbytes, tables.map_ptr,
+             tables.offsets_ptr, rows, cols, int(stored), int(scale is not None), float(0.0 if scale is None else scale), out.data_ptr(), code,
+             ldy, _packed_stream_ptr(stream)))
+    return out
 
 
 PACKED_SKINNY_MAX_M = 32   # include/mtq.h MTQ_PACKED_SKINNY_MAX_M

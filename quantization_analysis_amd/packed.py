@@ -50,6 +50,10 @@ for bit two matmul calls into float32 and the combine; PackedMatmulMLP and Packe
 such weights, and PackedMoE(stored="transpose") is the layer over them: a pack_model.py --store-transposed directory of an MoE layer's
 experts runs with no Python loop over experts.
 
+embedding / PackedEmbedding are the input embedding over a packed table (csrc/mtq_packed_gather.hip, include/mtq_packed_gather.h): the
+rows the ids name gathered straight from the stream of a (vocab, hidden) table, or the columns of its packed (hidden, vocab) transpose,
+bit for bit unpack(pt)[ids] without ever unpacking the table; PackedEmbedding.head() is the tied LM head over the same tensor.
+
 Not built: a chunked variant of the grouped skinny GLU kernels; pack_transposed of tensors of rank other than 2 (pack_model.py packs
 their permuted copies with pack); activations other than ACTS.
 
@@ -2341,6 +2345,125 @@ def moe_route(logits, topk: int, score: str = "softmax", bias=None, n_group: int
     return got
 
 
+# ----------------------------------------------------------------------------- the input embedding
+
+def _need_gather(hb, what: str) -> None:
+    if not hb.packed_gather_available():
+        raise MtqError(f"{what} needs {' and '.join(hb.PACKED_GATHER_EXPORTS)}, {_LACKS}")
+
+
+def _embedding_words(ids: np.ndarray, pt: PackedTensor, transposed: bool) -> np.ndarray:
+    """uint32 words (tokens, hidden) of the emulation: `decode` over the tile rows (stored "rows") or tile columns ("transpose") the
+    ids touch, one strip at a time, never the whole table; an id outside the table leaves its row +0."""
+    data, th, tw = _host_data(pt), *pt.map.shape
+    vocab, hidden = (pt.cols, pt.rows) if transposed else (pt.rows, pt.cols)
+    words = np.zeros((ids.size, hidden), dtype=np.uint32)
+    inside = np.flatnonzero((ids >= 0) & (ids < vocab))
+    strip_of = ids[inside] >> 5
+    for s in np.unique(strip_of):
+        sel = inside[strip_of == s]
+        depth = min(TILE, vocab - TILE * int(s))
+        if transposed:          # tile column s: tiles s, s + tw, ...; decode reads a tile's start only, so the closing offset is unused
+            starts = np.append(pt.offsets[int(s):th * tw:tw], 0)
+            strip = decode(data, pt.map[:, int(s):int(s) + 1], starts, hidden, depth).T
+        else:
+            strip = decode(data, pt.map[int(s):int(s) + 1], pt.offsets[int(s) * tw:(int(s) + 1) * tw + 1], depth, hidden)
+        words[sel] = strip[ids[sel] & 31]
+    return words
+
+
+def embedding(ids, pt: PackedTensor, out_dtype: str = "bfloat16", stored: str = "rows", scale=None, id_first: int = 0,
+              backend: Optional[str] = None, out=None):
+    """The input embedding over a packed table: ids of any shape (...) → (..., hidden), row ids[i] - id_first of the table, read straight
+    from the packed stream (mtq_packed_embedding); the table is never unpacked.
+
+    stored (MOE_STORED, the index.json words): "rows", `pt` is the packed (vocab, hidden) table - pack, a pack_batch member, a load_dir
+    tensor; "transpose", `pt` is the packed (hidden, vocab) transpose - pack_transposed, a pack_batch_transposed member, an entry of a
+    pack_model.py --store-transposed directory.  id_first is subtracted from every id (a vocabulary-parallel rank holds rows
+    [id_first, id_first + vocab)); an id outside the table after that gives a row of +0, which also serves as a padding index.
+    scale (Gemma's sqrt(hidden)): None, or a number rounded to float32; the values are multiplied by it in float32 and a bfloat16 output
+    is rounded once.  Without a scale the result is bit for bit unpack(pt)[ids] (unpack_transposed for "transpose") in both types.
+
+    hip (the default when the stream is on the device): ids an int32 or int64 tensor, a device tensor out; `out`, a (ids.numel(), hidden)
+    device tensor with contiguous rows at any pitch, is written and returned as it is.  emulation: NumPy, decoding only the tile rows
+    (tile columns) the ids touch → a NumPy float32 array or a torch CPU bfloat16 tensor.  An empty ids returns the empty result without
+    a launch."""
+    _check_rank2(_moe_orientation(stored), pt, "embedding")
+    transposed = stored == "transpose"
+    _check_out_dtype(out_dtype)
+    backend = backend or ("hip" if pt.on_device else "emulation")
+    _check_backend(backend)
+    hidden = pt.rows if transposed else pt.cols
+    if isinstance(id_first, bool) or not isinstance(id_first, (int, np.integer)):
+        raise MtqError(f"id_first must be an integer, got {id_first!r}")
+    if scale is not None:
+        scale = float(np.float32(scale))
+    lead = tuple(ids.shape) if hasattr(ids, "shape") else np.shape(ids)
+    if backend == "hip":
+        import torch
+
+        _need_gather(hb, "embedding")
+        if not _is_torch(ids):
+            ids = torch.from_numpy(np.ascontiguousarray(ids))
+        if ids.numel() == 0 and out is None:
+            return torch.zeros(lead + (hidden,), dtype=_torch_dtype(out_dtype), device=_device_data(pt).device if pt.on_device else "cpu")
+        data = _device_data(pt)
+        y = hb.packed_embedding(ids.to(data.device), data, pt.tables(), pt.rows, pt.cols, stored=hb.GATHER_TRANSPOSE if transposed else hb.GATHER_ROWS,
+                                scale=scale, id_first=int(id_first), out_dtype=_torch_dtype(out_dtype), out=out)
+        return y if out is not None else y.reshape(lead + (hidden,))
+    if out is not None:
+        raise MtqError("out is for the hip backend")
+    host = ids.detach().to("cpu").numpy() if _is_torch(ids) else np.asarray(ids)
+    if host.size and host.dtype.kind not in "iu":
+        raise MtqError(f"ids must be integers, got {host.dtype}")
+    words = _embedding_words(host.astype(np.int64).reshape(-1) - int(id_first), pt, transposed).reshape(lead + (hidden,))
+    if scale is not None:
+        return _round_out(words.view(np.float32).astype(np.float64) * np.float64(scale), out_dtype)
+    if out_dtype == "float32":
+        return words.view(np.float32)
+    import torch
+
+    return torch.from_numpy((words >> np.uint32(16)).astype(np.uint16).view(np.int16)).view(torch.bfloat16)
+
+
+def _embedding_class():
+    import torch
+
+    class PackedEmbedding(torch.nn.Module):
+        def __init__(self, pt: PackedTensor, stored: str = "rows", scale=None, id_first: int = 0, out_dtype: str = "bfloat16",
+                     backend: Optional[str] = None):
+            super().__init__()
+            _check_rank2(_moe_orientation(stored), pt, "PackedEmbedding")
+            _check_out_dtype(out_dtype)
+            self.backend = backend or ("hip" if pt.on_device else "emulation")
+            _check_backend(self.backend)
+            self.packed, self.stored, self.scale, self.id_first, self.out_dtype = pt, stored, scale, int(id_first), out_dtype
+            self.num_embeddings, self.embedding_dim = (pt.cols, pt.rows) if stored == "transpose" else (pt.rows, pt.cols)
+            if self.backend == "hip":               # a library without the kernel is refused here, not at the first forward
+                _need_gather(hb, "PackedEmbedding")
+                _device_data(pt)
+                pt.tables()
+
+        def extra_repr(self) -> str:
+            return f"num_embeddings={self.num_embeddings}, embedding_dim={self.embedding_dim}, stored={self.stored!r}, backend={self.backend!r}, " \
+                   f"packed_bytes={self.packed.nbytes}" + ("" if self.scale is None else f", scale={self.scale}") \
+                   + (f", id_first={self.id_first}" if self.id_first else "")
+
+        @torch.no_grad()
+        def forward(self, ids):
+            return _as_torch(embedding(ids, self.packed, out_dtype=self.out_dtype, stored=self.stored, scale=self.scale, id_first=self.id_first,
+                                       backend=self.backend))
+
+        def head(self, **kw):
+            """The LM head of a model with tied weights, over the same PackedTensor and without a copy: PackedLinear(pt, **kw) for
+            stored "rows", PackedMatmul(pt, **kw) for "transpose"; x (..., hidden) → logits (..., vocab)."""
+            kw.setdefault("backend", self.backend)
+            name = "PackedMatmul" if self.stored == "transpose" else "PackedLinear"
+            return (globals().get(name) or __getattr__(name))(self.packed, **kw)
+
+    return _named(PackedEmbedding, "PackedEmbedding")
+
+
 def _named(cls, name: str):
     """A class made by a factory under its public name and its docstring of _CLASS_DOCS."""
     cls.__name__ = cls.__qualname__ = name
@@ -2349,6 +2472,12 @@ def _named(cls, name: str):
 
 
 _CLASS_DOCS = {
+    "PackedEmbedding":
+        """The input embedding over a packed table, embedding() as a module.  INFERENCE ONLY, as PackedLinear.  forward(ids) takes integer
+        ids of any shape (...) and returns (..., embedding_dim) in out_dtype; an empty ids gives the empty result without a launch.
+        stored: "rows", `pt` is the packed (vocab, hidden) table; "transpose", the packed (hidden, vocab) transpose.  scale, id_first:
+        embedding's.  hip: the stream and its tables go to the device once, here.  head(**kw) is the LM head of a model with tied
+        weights over the same PackedTensor, without a copy: a PackedLinear ("rows") or a PackedMatmul ("transpose").""",
     "PackedMLP":
         """A gated MLP over three packed weights, down(act(gate(x)) * up(x)): gate and up (n, k), down (k_out, n).  INFERENCE ONLY, as
         PackedLinear.  forward(x) takes bf16 (..., k), flattens the leading dimensions to m, runs glu(kernel="auto") into bf16 and
@@ -2945,11 +3074,12 @@ def _experts_class(o: _Orientation, name: str):
 
 
 def __getattr__(name):
-    """PackedLinear, PackedMatmul, PackedExperts, PackedExpertsMatmul, PackedMLP, PackedExpertsMLP, PackedMatmulMLP, PackedExpertsMatmulMLP
-    and PackedMoE are torch.nn.Modules: a class is made on first use, so that importing this module does not import torch."""
+    """PackedLinear, PackedMatmul, PackedExperts, PackedExpertsMatmul, PackedMLP, PackedExpertsMLP, PackedMatmulMLP, PackedExpertsMatmulMLP,
+    PackedMoE and PackedEmbedding are torch.nn.Modules: a class is made on first use, so that importing this module does not import torch."""
     makers = {"PackedLinear": (_product_class, _NK), "PackedMatmul": (_product_class, _KN), "PackedExperts": (_experts_class, _NK),
               "PackedExpertsMatmul": (_experts_class, _KN), "PackedMLP": (_mlp_class, _NK), "PackedMatmulMLP": (_mlp_class, _KN),
-              "PackedExpertsMLP": (_experts_mlp_class, _NK), "PackedExpertsMatmulMLP": (_experts_mlp_class, _KN), "PackedMoE": (_packed_moe_class,)}
+              "PackedExpertsMLP": (_experts_mlp_class, _NK), "PackedExpertsMatmulMLP": (_experts_mlp_class, _KN), "PackedMoE": (_packed_moe_class,),
+              "PackedEmbedding": (_embedding_class,)}
     if name in makers:
         make, *orientation = makers[name]
         cls = make(*orientation, name) if orientation else make()
